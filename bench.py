@@ -3,14 +3,25 @@ SegOFA-Base, bf16).  One "step" = criterion forward (HIP model + upsample/CE los
 backward (HIP) + gradient all-reduce (N>1) + clip + Adam, on one batch of 8 synthetic
 images per GPU that is already resident in HBM.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
 N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` (RANK / WORLD_SIZE in
 the environment) or started plainly -- bench.py then re-executes itself under torch.distributed.run with N ranks, one
 per GPU over RCCL, and fails loudly when the box has fewer than N GPUs.
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
+A plain run sets up, runs W warm-up and K timed steps and prints ONE JSON line (rank 0) with the driver's contract
+fields (metric, value, unit, higher_is_better, dtype, ms_per_step = wall time of the K timed steps / K, ...).
+
+--dump-outputs DIR: after the timed steps, what the last timed step handed its caller is written as DIR/<name>.npy
+(float32 / float64): the step's logging outputs (log_*), the logits of its forward, and a fixed seeded sample of the
+updated fp32 master weights and of the step's gradient arena (param_index holds the sampled positions).  Same
+arguments, same inputs: two builds can be compared array for array.
+
+--full adds the diagnostics that take time of their own (off by default):
   "roofline":     dominant kernel family, algorithmic FLOP / measured kernel time (HIP events on
-                  the launch stream inside the timed region) vs the 2.5 PFLOP/s dense bf16 MFMA peak
+                  the launch stream inside the timed region) vs the 2.5 PFLOP/s dense bf16 MFMA peak,
+                  plus roofline_gemm_kernel / roofline_other_kernels / kernel_families_ms_per_step
+                  (passes of their own after the timed region)
+  "steady_state": the same step >= --steady-steps times / >= 3 s right after the timed region
   "cpu_baseline": the CPU oracle (oracle/segofa_ref.py, fp32, all host cores) timed on a bounded
                   sample (4 images) of the same workload.
 """
@@ -158,6 +169,34 @@ def _group_roofline(rs, steps):
             "measured": "separate pass of %d steps after the timed region (per-launch events on every GEMM slow the step)" % steps}
 
 
+DUMP_SAMPLE = 1 << 20                      # sampled positions of the weight / gradient arenas in --dump-outputs
+
+
+def dump_outputs(path, trainer, logs, nseg):
+    """--dump-outputs: what the last timed step handed its caller, as <path>/<name>.npy -- its logging outputs (float64),
+    the logits of its forward (float32) and, at DUMP_SAMPLE fixed seeded positions of the trainable arena, the updated fp32
+    master weights and the step's gradients (float32; the positions themselves in param_index, float64).  ~17 MB at c2."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    trainer.params_ready()
+    torch.cuda.synchronize()
+    eng = trainer.eng
+    arrays = {}
+    for k, v in logs[-1].items():
+        if isinstance(v, torch.Tensor):
+            arrays["log_" + k] = v.detach().to("cpu", torch.float64).numpy()
+        elif isinstance(v, (int, float)) and not isinstance(v, bool):
+            arrays["log_" + k] = np.asarray(v, dtype=np.float64)
+    arrays["logits"] = eng.ws["logits_pad"][:, :, :nseg].float().cpu().numpy()
+    idx = np.unique(np.random.default_rng(0).integers(0, eng.n_train, size=min(eng.n_train, DUMP_SAMPLE)))
+    ti = torch.from_numpy(idx).to(eng.g16.device)
+    arrays["param_index"] = idx.astype(np.float64)
+    arrays["params_fp32_sample"] = trainer.p32[ti].float().cpu().numpy()
+    arrays["grads_sample"] = eng.g16[ti].float().cpu().numpy()
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -168,11 +207,17 @@ def main():
                          "and c4 = configs[3] (Large, 640x640, 171 classes) at their per-GPU size")
     ap.add_argument("--batch", type=int, default=None, help="images per GPU (default: the configuration's, 8)")
     ap.add_argument("--nseg", type=int, default=None, help="override the configuration's class count")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel-family timing and roofline figures, the "
+                         "steady-state cross-check, the host enqueue cost on an empty queue and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, fixed seeded sample "
+                         "of the weights and gradients)")
     ap.add_argument("--steady-steps", type=int, default=200,
-                    help="steps of the steady-state cross-check run right after the timed region (0: skip)")
+                    help="steps of the steady-state cross-check run right after the timed region (--full only; 0: skip)")
     ap.add_argument("--dropout", type=float, default=0.1, help="dropout (coco_unseen.sh:22)")
     ap.add_argument("--drop-path", type=float, default=0.1, help="encoder/decoder drop-path rate (coco_unseen.sh:20-21)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-prefetch", action="store_true", help="run the frozen trunk in line instead of one batch ahead")
     ap.add_argument("--graph", action="store_true",
                     help="replay the HIP-graph-captured update (Trainer.train_step(graph=True): captured once per resident "
@@ -269,32 +314,33 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # discovery pass: every family timed over the last TWO warm-up steps -- one trunk pass serves two batches, so a single step
-    # either contains a whole pass (conv family counted twice) or none; per-step values are the two-step sums halved
+    # --full: discovery pass -- every family timed over the last TWO warm-up steps -- one trunk pass serves two batches, so a
+    # single step either contains a whole pass (conv family counted twice) or none; per-step values are the two-step sums halved
     n_disc = (1 if a.no_prefetch else max(1, trainer.eng.trunk_lookahead))
     n_disc = n_disc if a.warmup >= n_disc else 1
     for i in range(a.warmup):
-        if i == a.warmup - n_disc:
+        if a.full and i == a.warmup - n_disc:
             hip.prof_reset(); hip.prof_enable(0x1FF)
         one_step()
     torch.cuda.synchronize()
-    fam = [hip.prof_read(k) for k in range(len(hip.PROF_KINDS))]
-    for f in fam:
-        f["ms"] /= n_disc
-    # the `roofline` object goes to the largest family BY MEASURED KERNEL TIME of this run (discovery pass above).  The
-    # attention backward is one operation executed as two concurrent kernels (dK/dV and dQ): they count as one family
-    # (sum of their kernel times); every family keeps its own entry in roofline_gemm_kernel / roofline_other_kernels.
-    kinds = list(hip.PROF_KINDS)
-    fam_ms = {n: f["ms"] for n, f in zip(kinds, fam)}
-    merged = {n: m for n, m in fam_ms.items() if n not in ("attn_bwd_dkv", "attn_bwd_dq")}
-    merged["attn_bwd_dkv"] = fam_ms.get("attn_bwd_dkv", 0.0) + fam_ms.get("attn_bwd_dq", 0.0)
-    dominant = kinds.index(max(merged, key=merged.get)) if a.warmup > 0 else kinds.index("attn_bwd_dkv")
-    # the dK/dV and dQ kernels of the attention backward run side by side on two streams and share the GPU: they are
-    # timed as ONE unit (delta + dK/dV + dQ, an event pair on the main stream around the three launches)
-    pair = hip.PROF_KINDS[dominant] in ("attn_bwd_dkv", "attn_bwd_dq") and trainer.eng.overlap
     graphed = world == 1 and a.graph and not a.image_free and a.warmup >= 3
-    hip.prof_reset()
-    hip.prof_enable(0)
+    if a.full:
+        fam = [hip.prof_read(k) for k in range(len(hip.PROF_KINDS))]
+        for f in fam:
+            f["ms"] /= n_disc
+        # the `roofline` object goes to the largest family BY MEASURED KERNEL TIME of this run (discovery pass above).  The
+        # attention backward is one operation executed as two concurrent kernels (dK/dV and dQ): they count as one family
+        # (sum of their kernel times); every family keeps its own entry in roofline_gemm_kernel / roofline_other_kernels.
+        kinds = list(hip.PROF_KINDS)
+        fam_ms = {n: f["ms"] for n, f in zip(kinds, fam)}
+        merged = {n: m for n, m in fam_ms.items() if n not in ("attn_bwd_dkv", "attn_bwd_dq")}
+        merged["attn_bwd_dkv"] = fam_ms.get("attn_bwd_dkv", 0.0) + fam_ms.get("attn_bwd_dq", 0.0)
+        dominant = kinds.index(max(merged, key=merged.get)) if a.warmup > 0 else kinds.index("attn_bwd_dkv")
+        # the dK/dV and dQ kernels of the attention backward run side by side on two streams and share the GPU: they are
+        # timed as ONE unit (delta + dK/dV + dQ, an event pair on the main stream around the three launches)
+        pair = hip.PROF_KINDS[dominant] in ("attn_bwd_dkv", "attn_bwd_dq") and trainer.eng.overlap
+        hip.prof_reset()
+        hip.prof_enable(0)
 
     def dominant_pass(nsteps):
         """event pairs around the dominant kernel (every PROF_STRIDE-th launch), on eagerly enqueued steps"""
@@ -313,7 +359,7 @@ def main():
         use_graph[0] = True
         for _ in range(4):
             one_step()                        # 2 captures + 2 replays
-    else:
+    elif a.full:
         dominant_pass(0)
     sync()
     t0 = time.time()
@@ -328,70 +374,73 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     dt = tt.item()
     loss = float(logs[-1]["loss"])
-    # steady-state cross-check of the (short) driver-timed region: the same step, >= 200 times / >= 3 s, measured the same
-    # way right after it -- long enough for an external utilisation sampler to see a busy GPU
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, trainer, logs, a.nseg)
     steady = None
-    if a.steady_steps > 0:
-        n_ss, t_ss = 0, 0.0
-        sync()
-        t1 = time.time()
-        while n_ss < a.steady_steps or (time.time() - t1) < 3.0:
-            for _ in range(20):
-                one_step()
-            n_ss += 20
-            if n_ss >= 4000:
-                break
-        sync()
-        t_ss = time.time() - t1
-        ts = torch.tensor([t_ss], device=dev)
-        if world > 1:
-            dist.all_reduce(ts, op=dist.ReduceOp.MAX)
-        t_ss = ts.item()
-        steady = {"steps": n_ss, "seconds": round(t_ss, 3), "ms_per_step": round(t_ss / n_ss * 1e3, 3),
-                  "images_per_sec": round(a.batch * world * n_ss / t_ss, 2)}
-    # what one step costs the HOST: the enqueue of a step into an EMPTY GPU queue (device drained first), so that no
-    # back-pressure from a full queue is inside the figure -- `host_enqueue_ms_per_step` of the timed region converges to the
-    # GPU time whenever the host is ahead.  Median of 7, after the timed regions.
-    host_empty = []
-    for _ in range(7):
+    if a.full:
+        # steady-state cross-check of the (short) driver-timed region: the same step, >= 200 times / >= 3 s, measured the same
+        # way right after it -- long enough for an external utilisation sampler to see a busy GPU
+        if a.steady_steps > 0:
+            n_ss, t_ss = 0, 0.0
+            sync()
+            t1 = time.time()
+            while n_ss < a.steady_steps or (time.time() - t1) < 3.0:
+                for _ in range(20):
+                    one_step()
+                n_ss += 20
+                if n_ss >= 4000:
+                    break
+            sync()
+            t_ss = time.time() - t1
+            ts = torch.tensor([t_ss], device=dev)
+            if world > 1:
+                dist.all_reduce(ts, op=dist.ReduceOp.MAX)
+            t_ss = ts.item()
+            steady = {"steps": n_ss, "seconds": round(t_ss, 3), "ms_per_step": round(t_ss / n_ss * 1e3, 3),
+                      "images_per_sec": round(a.batch * world * n_ss / t_ss, 2)}
+        # what one step costs the HOST: the enqueue of a step into an EMPTY GPU queue (device drained first), so that no
+        # back-pressure from a full queue is inside the figure -- `host_enqueue_ms_per_step` of the timed region converges to the
+        # GPU time whenever the host is ahead.  Median of 7, after the timed regions.
+        host_empty = []
+        for _ in range(7):
+            torch.cuda.synchronize()
+            th = time.time()
+            one_step()
+            host_empty.append((time.time() - th) * 1e3)
         torch.cuda.synchronize()
-        th = time.time()
-        one_step()
-        host_empty.append((time.time() - th) * 1e3)
-    torch.cuda.synchronize()
-    host_empty.sort()
-    if graphed:
-        use_graph[0] = False
-        dominant_pass(min(10, a.steps))
-    if pair:
-        prs = trainer.eng.attn_bwd_timing["pairs"]
-        trainer.eng.attn_bwd_timing = None
-        tr = [_pmc_traffic(k) for k in ("attn_bwd_dkv", "attn_bwd_dq")]
-        dom = {"kind": "attn_bwd (delta + dK/dV kernel + dQ kernel, the two side by side on two streams)",
-               "ms": sum(a_.elapsed_time(b_) for a_, b_, _ in prs), "flops": sum(f for _, _, f in prs), "launches": len(prs),
-               "traffic": (tr[0] + tr[1]) if all(t is not None for t in tr) else None}
-    else:
-        dom = hip.prof_read(dominant)
-        dom["traffic"] = _pmc_traffic(dom["kind"])
-    hip.prof_enable(0)
-    # second view, outside the timed region (timing ~300 launches per step with events costs ~8 % of the step): the four
-    # GEMM-shaped families are instantiations of ONE kernel, gemm_kernel (csrc/gemm.hip); together they are the largest
-    # time consumer, so their aggregate MFMA rate is reported next to the dominant single family
-    gk = [k for k, n in enumerate(hip.PROF_KINDS) if n.startswith("gemm_") or n == "conv"]
-    hip.prof_reset(); hip.prof_enable(sum(1 << k for k in gk))
-    extra = min(3, a.steps)
-    for _ in range(extra):
-        one_step()
-    torch.cuda.synchronize()
-    grs = [hip.prof_read(k) for k in gk]
-    # third view: every other family on its own (attention forward / dQ / dK,dV, LayerNorm), same method
-    ok_ = [k for k in range(len(hip.PROF_KINDS)) if k not in gk]
-    hip.prof_reset(); hip.prof_enable(sum(1 << k for k in ok_))
-    for _ in range(extra):
-        one_step()
-    torch.cuda.synchronize()
-    ors = [hip.prof_read(k) for k in ok_]
-    hip.prof_enable(0)
+        host_empty.sort()
+        if graphed:
+            use_graph[0] = False
+            dominant_pass(min(10, a.steps))
+        if pair:
+            prs = trainer.eng.attn_bwd_timing["pairs"]
+            trainer.eng.attn_bwd_timing = None
+            tr = [_pmc_traffic(k) for k in ("attn_bwd_dkv", "attn_bwd_dq")]
+            dom = {"kind": "attn_bwd (delta + dK/dV kernel + dQ kernel, the two side by side on two streams)",
+                   "ms": sum(a_.elapsed_time(b_) for a_, b_, _ in prs), "flops": sum(f for _, _, f in prs), "launches": len(prs),
+                   "traffic": (tr[0] + tr[1]) if all(t is not None for t in tr) else None}
+        else:
+            dom = hip.prof_read(dominant)
+            dom["traffic"] = _pmc_traffic(dom["kind"])
+        hip.prof_enable(0)
+        # second view, outside the timed region (timing ~300 launches per step with events costs ~8 % of the step): the four
+        # GEMM-shaped families are instantiations of ONE kernel, gemm_kernel (csrc/gemm.hip); together they are the largest
+        # time consumer, so their aggregate MFMA rate is reported next to the dominant single family
+        gk = [k for k, n in enumerate(hip.PROF_KINDS) if n.startswith("gemm_") or n == "conv"]
+        hip.prof_reset(); hip.prof_enable(sum(1 << k for k in gk))
+        extra = min(3, a.steps)
+        for _ in range(extra):
+            one_step()
+        torch.cuda.synchronize()
+        grs = [hip.prof_read(k) for k in gk]
+        # third view: every other family on its own (attention forward / dQ / dK,dV, LayerNorm), same method
+        ok_ = [k for k in range(len(hip.PROF_KINDS)) if k not in gk]
+        hip.prof_reset(); hip.prof_enable(sum(1 << k for k in ok_))
+        for _ in range(extra):
+            one_step()
+        torch.cuda.synchronize()
+        ors = [hip.prof_read(k) for k in ok_]
+        hip.prof_enable(0)
     rccl_stats = trainer.reducer.stats()
     if world > 1 and rccl_stats["mode"] != "direct" and lab.get("REDUCE_MODE") is None:
         raise RuntimeError("bench.py: %d ranks but the gradient all-reduce did not run through the direct RCCL communicator (%r)"
@@ -401,7 +450,6 @@ def main():
     if rank == 0:
         imgs = a.batch * world * a.steps
         value = imgs / dt
-        ach = dom["flops"] / (dom["ms"] * 1e-3) / 1e12 if dom["ms"] > 0 else 0.0
         out = {
             "metric": "images/sec (%dx%d, SegOFA-%s fwd+bwd)" % (size, size, "Large" if arch == "segofa_large" else "Base"),
             "value": round(value, 2), "unit": "images/sec",
@@ -415,24 +463,30 @@ def main():
                                       "; every step is one replay of the HIP-graph-captured update" if graphed else "; steps enqueued from the host"),
                        "global_batch": a.batch * world, "parallelism": "dp%d" % world, "loss": round(loss, 4),
                        "env": env_seen},
-            "roofline": {"bound": "mfma", "kernel": dom["kind"], "achieved": round(ach, 2), "peak": MFMA_PEAK_TF,
-                         "unit": "TFLOP/s", "frac": round(ach / MFMA_PEAK_TF, 4), "traffic": dom["traffic"],
-                         "traffic_source": _traffic_source(),
-                         "launches": dom["launches"], "avg_launch_us": round(dom["ms"] * 1e3 / max(1, dom["launches"]), 2),
-                         "sampled": "every %d. launch timed with a HIP event pair on its stream%s" % (
-                             PROF_STRIDE, " (on %d eagerly enqueued steps after the timed graph replays)" % min(10, a.steps) if graphed else ""),
-                         "whole_step_frac": round(value / world * gf_img / 1e3 / MFMA_PEAK_TF, 4) if gf_img else None,
-                         "gflop_per_image": gf_img},
-            **({"lab": True} if os.environ.get("IFSEG_LAB") == "1" else {}),
-            "roofline_gemm_kernel": _group_roofline(grs, extra),
-            "roofline_other_kernels": {r["kind"]: _one_roofline(r, extra) for r in ors},
-            "kernel_families_ms_per_step": {f["kind"]: round(f["ms"], 3) for f in fam},
+            "full": a.full,
         }
+        if a.full:
+            ach = dom["flops"] / (dom["ms"] * 1e-3) / 1e12 if dom["ms"] > 0 else 0.0
+            out["roofline"] = {"bound": "mfma", "kernel": dom["kind"], "achieved": round(ach, 2), "peak": MFMA_PEAK_TF,
+                               "unit": "TFLOP/s", "frac": round(ach / MFMA_PEAK_TF, 4), "traffic": dom["traffic"],
+                               "traffic_source": _traffic_source(),
+                               "launches": dom["launches"], "avg_launch_us": round(dom["ms"] * 1e3 / max(1, dom["launches"]), 2),
+                               "sampled": "every %d. launch timed with a HIP event pair on its stream%s" % (
+                                   PROF_STRIDE, " (on %d eagerly enqueued steps after the timed graph replays)" % min(10, a.steps) if graphed else ""),
+                               "whole_step_frac": round(value / world * gf_img / 1e3 / MFMA_PEAK_TF, 4) if gf_img else None,
+                               "gflop_per_image": gf_img}
+        if os.environ.get("IFSEG_LAB") == "1":
+            out["lab"] = True
+        if a.full:
+            out["roofline_gemm_kernel"] = _group_roofline(grs, extra)
+            out["roofline_other_kernels"] = {r["kind"]: _one_roofline(r, extra) for r in ors}
+            out["kernel_families_ms_per_step"] = {f["kind"]: round(f["ms"], 3) for f in fam}
         # the data-parallel leg as it actually ran (live from the reducer): N ranks in ONE RCCL communicator, how many
         # collectives and bytes per step.  Any N > 1 run that did not go through the direct communicator fails loudly below.
         out["rccl"] = rccl_stats
         out["host_enqueue_ms_per_step"] = round(t_enq / a.steps * 1e3, 3)
-        out["host_ms_per_step_empty_queue"] = round(host_empty[len(host_empty) // 2], 3)
+        if a.full:
+            out["host_ms_per_step_empty_queue"] = round(host_empty[len(host_empty) // 2], 3)
         if trainer.eng.marks:                    # IFSEG_PHASE_TIMING=1: main-stream (and host) time between the phase marks
             torch.cuda.synchronize()
             allm = trainer.eng.marks[:n_marks]
@@ -453,7 +507,7 @@ def main():
             out["end_of_backward_wait_ms"] = round(sum(w) / len(w), 3)
         if steady is not None:
             out["steady_state"] = steady
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(a.nseg, task.src_len, arch, size)
         print(json.dumps(out))
     trainer.close()

@@ -39,6 +39,57 @@ import _refshim  # noqa: E402
 import segofa_ref as O  # noqa: E402
 
 GOLDEN = os.path.join(os.path.dirname(HERE), "tests", "golden")
+MAX_FILE = 1 << 20          # no committed file reaches 1 MiB
+PART_BYTES = 900_000        # raw array bytes per part of a split golden
+
+
+def save_golden(out_name, arrays):
+    """np.savez_compressed into tests/golden; a golden that would reach MAX_FILE is split by keys, in order, into
+    <stem>.part0.npz, <stem>.part1.npz, ... (load_golden merges them again)"""
+    path = os.path.join(GOLDEN, out_name)
+    stem = path[:-len(".npz")]
+    for f in os.listdir(GOLDEN):
+        if f.startswith(os.path.basename(stem) + ".part") and f.endswith(".npz"):
+            os.remove(os.path.join(GOLDEN, f))
+    np.savez_compressed(path, **arrays)
+    if os.path.getsize(path) < MAX_FILE:
+        return
+    os.remove(path)
+    parts, cur, size = [], {}, 0
+    for k, v in arrays.items():
+        nb = np.asarray(v).nbytes
+        if cur and size + nb > PART_BYTES:
+            parts.append(cur)
+            cur, size = {}, 0
+        cur[k] = v
+        size += nb
+    parts.append(cur)
+    for i, part in enumerate(parts):
+        pp = "%s.part%d.npz" % (stem, i)
+        np.savez_compressed(pp, **part)
+        assert os.path.getsize(pp) < MAX_FILE, pp
+
+
+def load_golden(golden_dir, name):
+    """the arrays of golden `name` by key, in file order: <name> itself or its parts merged (see save_golden).  The
+    result answers like np.load's NpzFile: `files`, `[key]`.  Used by the tests: needs no reference tree."""
+    paths = [os.path.join(golden_dir, name)]
+    if not os.path.exists(paths[0]):
+        paths = []
+        while os.path.exists(os.path.join(golden_dir, "%s.part%d.npz" % (name[:-4], len(paths)))):
+            paths.append(os.path.join(golden_dir, "%s.part%d.npz" % (name[:-4], len(paths))))
+        assert paths, "golden %s not found in %s" % (name, golden_dir)
+    g = Golden()
+    for p in paths:
+        with np.load(p) as z:
+            g.update((k, z[k]) for k in z.files)
+    return g
+
+
+class Golden(dict):
+    @property
+    def files(self):
+        return list(self)
 
 GRAD_KEYS = [
     "encoder.layers.0.self_attn.q_proj.weight",
@@ -223,7 +274,7 @@ def case_train(cfg, arch, overrides, batch_size, src_len, out_name, grad_keys, f
         save["gradnorm:" + k] = np.float64(g_ref.norm().item())
         if full_grads or g_ref.numel() <= 16384:
             save["grad:" + k] = g_ref.numpy()
-    np.savez_compressed(os.path.join(GOLDEN, out_name), **save)
+    save_golden(out_name, save)
     print("  wrote", out_name, "%.1fs" % (time.time() - t0))
 
 
@@ -288,7 +339,7 @@ def case_imfree(cfg, arch, overrides, batch_size, src_len, out_name, grad_keys, 
         save["gradnorm:" + k] = np.float64(g_ref.norm().item())
         if g_ref.numel() <= 65536:
             save["grad:" + k] = g_ref.numpy()
-    np.savez_compressed(os.path.join(GOLDEN, out_name), **save)
+    save_golden(out_name, save)
     print("  wrote", out_name, "%.1fs" % (time.time() - t0))
 
 
@@ -337,7 +388,7 @@ def case_eval(cfg, arch, overrides, out_name, ori_hw=(150, 200), iters=25, topk=
         assert torch.equal(a, logs[nme + "_resnet_postprocess"]), nme
         save[nme + "_pp"] = logs[nme + "_resnet_postprocess"].numpy()
     print("[%s] eval loss %.6f; hist and smoothed-hist equal to the reference" % (out_name, loss.item()))
-    np.savez_compressed(os.path.join(GOLDEN, out_name), **save)
+    save_golden(out_name, save)
 
 
 def case_optim(cfg, arch, overrides, out_name, n_updates=3, lr=5e-5, total_updates=2000):
@@ -386,7 +437,7 @@ def case_optim(cfg, arch, overrides, out_name, n_updates=3, lr=5e-5, total_updat
             save["param:" + k] = named[k].detach().numpy().copy()
             save["init:" + k] = sd[k].numpy()
     save.update(losses=np.array(losses), gnorms=np.array(gnorms), lrs=np.array(lrs))
-    np.savez_compressed(os.path.join(GOLDEN, out_name), **save)
+    save_golden(out_name, save)
     print("  wrote", out_name)
 
 
@@ -412,7 +463,7 @@ def case_upgrade(cfg, arch, overrides, out_name):
     save["enc_ipos_tail"] = ck["encoder.embed_image_positions.weight"][-41:].numpy()
     save["dec_ipos_tail"] = ck["decoder.embed_image_positions.weight"][-41:].numpy()
     save["seg_embed"] = ck["encoder.seg_embed_tokens.weight"].numpy()
-    np.savez_compressed(os.path.join(GOLDEN, out_name), **save)
+    save_golden(out_name, save)
     print("[%s] %d keys after up-conversion; token table %s" % (out_name, len(ck), tuple(ck["encoder.embed_tokens.weight"].shape)))
 
 

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import segofa_ref as O
+from gen_golden import load_golden as _load_golden
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -120,7 +121,7 @@ def _golden_weights(g, sd, ocfg, batch):
 
 def _golden_case(golden_dir, name, ocfg, B, **model_over):
     dev = torch.device("cuda:0")
-    g = np.load(os.path.join(golden_dir, name))
+    g = _load_golden(golden_dir, name)
     assert int(g["batch_size"]) == B
     sd = O.procedural_state_dict(ocfg)
     batch = O.synthetic_batch(ocfg, B, int(g["src_len"]))
@@ -182,7 +183,7 @@ def test_base_config1_padded_prompts_vs_reference_golden(golden_dir):
     34 key blocks of the encoder's self-attention and of the decoder's cross-attention.  Same tolerances as the unpadded golden."""
     m, batch, logits, g = _golden_case(golden_dir, "base_c1_padded.npz", O.base_config(), 2, padded_prompts=True)
     assert (batch["src_tokens"] == O.PAD).sum(1).tolist() == [0, 9]
-    un = np.load(os.path.join(golden_dir, "base_c1_b2.npz"))
+    un = _load_golden(golden_dir, "base_c1_b2.npz")
     # the padding matters: sample 1 of the reference moved against the unpadded golden (same weights, same images), sample 0 did not
     d0 = _rel(torch.from_numpy(g["logits_causal"][0]), torch.from_numpy(un["logits_causal"][0]))
     d1 = _rel(torch.from_numpy(g["logits_causal"][1]), torch.from_numpy(un["logits_causal"][1]))
@@ -231,7 +232,7 @@ def test_base_config3_batch8_per_gpu_size(golden_dir):
     within tolerance; the loss kernel at B = 8 against the fp32 CE of its own logits; the step is bit-deterministic."""
     dev = torch.device("cuda:0")
     ocfg = O.base_config(num_seg_tokens=150, vocab_size=59458)
-    g = np.load(os.path.join(golden_dir, "base_c3.npz"))
+    g = _load_golden(golden_dir, "base_c3.npz")
     sd = O.procedural_state_dict(ocfg)
     b1, b8 = O.synthetic_batch(ocfg, 1, 215), O.synthetic_batch(ocfg, 8, 215)
     assert torch.equal(b1["patch_images"], b8["patch_images"][:1]) and torch.equal(b1["src_tokens"], b8["src_tokens"][:1])
@@ -269,7 +270,7 @@ def test_base_config2_batch8_consistent_with_batch2_golden(golden_dir):
     forward never depends on its batch mates); the step is bit-deterministic."""
     dev = torch.device("cuda:0")
     ocfg = O.base_config()
-    g = np.load(os.path.join(golden_dir, "base_c1_b2.npz"))
+    g = _load_golden(golden_dir, "base_c1_b2.npz")
     sd = O.procedural_state_dict(ocfg)
     b2, b8 = O.synthetic_batch(ocfg, 2, 36), O.synthetic_batch(ocfg, 8, 36)
     assert torch.equal(b2["patch_images"], b8["patch_images"][:2]) and torch.equal(b2["src_tokens"], b8["src_tokens"][:2])

@@ -9,7 +9,7 @@ import test_configs_gpu as T
 
 dev = torch.device("cuda:0")
 ocfg = O.base_config()
-g = np.load(os.path.join(ROOT, "tests", "golden", "base_c1_b2.npz"))
+g = T._load_golden(os.path.join(ROOT, "tests", "golden"), "base_c1_b2.npz")
 sd = O.procedural_state_dict(ocfg)
 batch = O.synthetic_batch(ocfg, 2, int(g["src_len"]))
 sd = T._golden_weights(g, sd, ocfg, batch)
