@@ -481,6 +481,8 @@ static int gemm_impl(int layout, const void* A, const void* B, void* C, int M, i
   g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
   g.bias = (const bf16_t*)bias; g.resid = (const bf16_t*)resid; g.ldr = ldr;
   g.alpha = alpha; g.alpha_ncols = (alpha == 1.0f) ? 0 : (alpha_ncols < 0 ? N : alpha_ncols);
+  // a lane scales runs of 4 columns: a boundary inside a run would scale up to 3 columns too many
+  if (g.alpha_ncols < N && (g.alpha_ncols & 3)) return IFSEG_ERR_BAD_ARG;
   g.flags = flags; g.sA = strideA; g.sB = strideB; g.sC = strideC; g.sR = strideR;
   if (dot) {
     // plain bf16 output, 128-wide tiles (a wave = 64 columns = one head), one batch

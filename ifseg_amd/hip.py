@@ -261,17 +261,18 @@ def dw_groupable(dy, x, out, bias_out):
 
 
 def linear_dw_group(tasks, wgs=None):
-    """tasks: list of (dy [M,N], x [M,K], out [N,K] bf16, bias_out or None): every dW (+ db) in ONE launch
+    """tasks: list of (dy [M,N], x [M,K], out [N,K] bf16, bias_out or None[, accumulate]): every dW (+ db) in ONE launch
     (ifseg_gemm_tn_group), at most GEMM_GROUP_MAX per launch.  `wgs`: workgroup cap (default DW_GROUP_WGS; 0 = one workgroup per
-    tile, for a launch with the GPU to itself)"""
+    tile, for a launch with the GPU to itself).  The optional fifth element adds to what out / bias_out hold (the engine
+    passes four: its grouped launches overwrite)"""
     for i in range(0, len(tasks), GEMM_GROUP_MAX):
         chunk = tasks[i:i + GEMM_GROUP_MAX]
         arr = (_TnProblem * len(chunk))()
-        for q, (dy, x, out, bias_out) in zip(arr, chunk):
+        for q, (dy, x, out, bias_out, *acc) in zip(arr, chunk):
             M, N = dy.shape
             q.A, q.B, q.C = _p(_bf(dy)), _p(_bf(x)), _p(out)
             q.M, q.N, q.K, q.lda, q.ldb = N, x.shape[1], M, dy.stride(0), x.stride(0)
-            q.colsum, q.accumulate = (1 if bias_out is not None else 0), 0
+            q.colsum, q.accumulate = (1 if bias_out is not None else 0), (1 if acc and acc[0] else 0)
         _check(lib().ifseg_gemm_tn_group(c_int(len(chunk)), arr, c_int(DW_GROUP_WGS if wgs is None else wgs), _stream()), "gemm_tn_group")
 
 

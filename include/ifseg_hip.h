@@ -50,6 +50,8 @@ int ifseg_experimental_build(void);
  * (unify_multihead_attention.py:346) and `* pos_scaling`; `resid` the
  * residual_connection (unify_transformer_layer.py:196,289).
  * N, lda, ldb must be multiples of 8 (16-byte rows); bias/resid bf16.
+ * alpha_ncols < 0 means all N columns; 0 <= alpha_ncols < N must be a multiple of 4 when alpha != 1 (the epilogue
+ * works on runs of 4 columns), anything else is refused with IFSEG_ERR_BAD_ARG.
  * splitk > 1: the reduction is cut into ceil(K/kchunk) slices (kchunk = K/splitk rounded up
  * to 64); slice z writes its partial product to the fp32 workspace C + z*M*ldc (requires
  * IFSEG_GEMM_OUT_F32, no epilogue terms); the caller sums the slices (ifseg_reduce_parts).
