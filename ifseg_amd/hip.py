@@ -21,7 +21,7 @@ GEMM_RELU, GEMM_OUT_F32, GEMM_ACCUMULATE = 1, 2, 4
 c_void_p, c_int, c_float, c_ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_longlong
 
 
-ABI_VERSION = 18          # == IFSEG_ABI_VERSION of include/ifseg_hip.h (checked at load time and by __graft_entry__.build)
+ABI_VERSION = 19         # == IFSEG_ABI_VERSION of include/ifseg_hip.h (checked at load time and by __graft_entry__.build)
 
 
 def lib():
@@ -515,6 +515,34 @@ def attn_dbias_grads(dbias, S, pos_q=None, pos_k=None, dpq_acc=None, dpk_acc=Non
     a.drel2d, a.drel1d, a.drelx = _p(drel2d), _p(drel1d), _p(drelx)
     a.causal = 1 if causal else 0
     _check(lib().ifseg_attn_dbias_grads(ctypes.byref(a), _stream()), "attn_dbias_grads")
+
+
+# ---- attention with a bias the caller computed (csrc/attention_ops.hip)
+def attn_bias_pack(dense, bias, causal=False, P=None):
+    """dense.D = the operand of attn_fwd_bi / attn_bwd_bi for an ordinary bias tensor: bf16(bias) on [:, :T, :S], -inf on the
+    padding and (causal) on the pairs attn_dense_bias masks; every element is written.  bias: fp32 / bf16 [H, T, S] with a
+    contiguous last dimension (any head / row strides), or None for a zero bias"""
+    f32, hs, rs = 0, 0, 0
+    if bias is not None:
+        assert bias.dtype in (torch.float32, torch.bfloat16) and tuple(bias.shape) == (dense.H, dense.T, dense.S), "bias: fp32 / bf16 [H, T, S]"
+        assert bias.stride(2) == 1 or dense.S == 1, "bias: the last dimension must be contiguous"
+        f32, hs, rs = int(bias.dtype == torch.float32), bias.stride(0), bias.stride(1)
+    _check(lib().ifseg_attn_bias_pack(_ptr(bias), c_int(f32), c_ll(hs), c_ll(rs), c_int(dense.H), c_int(dense.T),
+                                      c_int(dense.S), c_int(1 if causal else 0), c_int(P if P is not None else dense.S),
+                                      _ptr(dense.D), c_int(dense.Sp), c_int(dense.Tp), _stream()), "attn_bias_pack")
+    return dense
+
+
+def attn_dbias_sum(dbias, S, out):
+    """out [H, T, S] (fp32 / bf16, contiguous last dimension) = the sum over the slabs of dbias [ng, H, T, Sp] (bf16, as
+    attn_bwd_bi writes them), in fp32 and in slab order"""
+    ng, H, T, Sp = dbias.shape
+    assert dbias.dtype == torch.bfloat16 and dbias.is_contiguous()
+    assert out.dtype in (torch.float32, torch.bfloat16) and tuple(out.shape) == (H, T, S) and (out.stride(2) == 1 or S == 1)
+    _check(lib().ifseg_attn_dbias_sum(_ptr(dbias), c_int(ng), c_int(H), c_int(T), c_int(S), c_int(Sp), _ptr(out),
+                                      c_int(int(out.dtype == torch.float32)), c_ll(out.stride(0)), c_ll(out.stride(1)),
+                                      _stream()), "attn_dbias_sum")
+    return out
 
 
 # ------------------------------------------------------------------------ row ops

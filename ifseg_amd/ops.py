@@ -13,6 +13,11 @@ compose them with other PyTorch code (`torch.compile`, `torch.autograd.gradcheck
                                                                                          encoder_module.py:757-809
 Each op has its backward registered as further ops (`linear_bwd`, `layer_norm_bwd`, `bias_attention_bwd`), so the backward
 is dispatcher-visible too.  No CPU implementation is registered: on a CPU tensor the dispatcher raises.
+
+The second half of the file puts the training-path kernels there as well (see the comment above `_check_qkv`):
+`attention_bias` (the bias is an ordinary tensor with a gradient), `bias_attention_bi` (bias_attention on the batch-inner
+kernels, with key counts and attention dropout) and `seg_loss` (csrc/loss.hip), with `*_bwd` ops of their own;
+`ifseg_amd.modules.MultiheadAttention` composes `linear` and `attention_bias` under the reference module's parameter names.
 """
 from typing import Optional, Tuple
 
@@ -236,3 +241,420 @@ def _attn_backward(ctx, gout, glse):
 
 
 bias_attention.register_autograd(_attn_backward, setup_context=_attn_setup)
+
+
+# =============================================================================================== training-path ops
+# The batch-inner attention kernels (csrc/attention_bi.hip: dense bf16 bias operand, four batch elements per workgroup,
+# sum_b dS once per tile, per-sample key counts, in-kernel attention dropout) and the fused criterion kernel (csrc/loss.hip):
+#
+#   torch.ops.ifseg.attention_bias(q, k, v, bias, gain, kv_len, causal, P, dropout_p, seed)      the bias is a tensor with a gradient
+#   torch.ops.ifseg.bias_attention_bi(q, k, v, pos_q, pos_k, gain, gcode, rel2d, rel1d, relx, P, code_bias, grid_w, causal,
+#                                     kv_len, dropout_p, seed)                                   bias_attention + key counts + dropout
+#   torch.ops.ifseg.seg_loss(logits, target, hp, wp, H, W, seg_id_offset, label_smoothing)       x16 upsample + CE + histograms
+#
+# Every op has ONE check helper that its real and its fake implementation call first: tracing refuses what running refuses,
+# and nothing is launched (the library is not even loaded) before the arguments have passed.
+_pad32 = hip._pad32
+
+
+def _check_qkv(op, q, k, v):
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if t.dim() != 3 or t.dtype != BF:
+            raise ValueError("%s: %s must be a bf16 [batch, tokens, heads * 64] tensor, got %s %s" % (op, name, t.dtype, tuple(t.shape)))
+        if t.stride(2) != 1:
+            raise ValueError("%s: %s must have a contiguous last dimension (stride %d)" % (op, name, t.stride(2)))
+    B, T, C = q.shape
+    if C % 64 != 0 or C == 0:
+        raise ValueError("%s: the kernels take a head dimension of 64 only: q.shape[-1] = %d is not a multiple of 64" % (op, C))
+    if k.shape[0] != B or k.shape[2] != C or tuple(v.shape) != tuple(k.shape):
+        raise ValueError("%s: k / v must be [%d, S, %d], got %s / %s" % (op, B, C, tuple(k.shape), tuple(v.shape)))
+    if B == 0 or T == 0 or k.shape[1] == 0:
+        raise ValueError("%s: empty batch or sequence" % op)
+    return B, T, k.shape[1], C // 64
+
+
+def _check_common(op, q, k, v, gain, kv_len, causal, P, dropout_p):
+    B, T, S, H = _check_qkv(op, q, k, v)
+    if gain is not None and (gain.dtype != torch.float32 or tuple(gain.shape) != (H,)):
+        raise ValueError("%s: gain must be fp32 [%d], got %s %s" % (op, H, gain.dtype, tuple(gain.shape)))
+    if kv_len is not None and (kv_len.dtype != torch.int32 or tuple(kv_len.shape) != (B,)):
+        raise ValueError("%s: kv_len must be int32 [%d] (valid key counts), got %s %s" % (op, B, kv_len.dtype, tuple(kv_len.shape)))
+    if not (0.0 <= dropout_p < 1.0):
+        raise ValueError("%s: dropout_p must lie in [0, 1), got %r" % (op, dropout_p))
+    if causal and (P <= 0 or P % 64 != 0 or P > min(T, S)):
+        raise ValueError("%s: causal needs P (grid tokens) > 0, P %% 64 == 0 and P <= min(T, S); got P = %d, T = %d, S = %d"
+                         % (op, P, T, S))
+    Tp, Sp = _pad32(T), _pad32(S)
+    if Tp * Sp * 2 >= 2 ** 31:
+        raise ValueError("%s: the padded bias of one head (T_p * S_p * 2 = %d bytes) must stay below 2**31" % (op, Tp * Sp * 2))
+    return B, T, S, H, Tp, Sp
+
+
+def _attention_bias_check(q, k, v, bias, gain, kv_len, causal, P, dropout_p):
+    op = "ifseg::attention_bias"
+    B, T, S, H, Tp, Sp = _check_common(op, q, k, v, gain, kv_len, causal, P, dropout_p)
+    if bias is not None:
+        if bias.dtype not in (torch.float32, BF) or tuple(bias.shape) != (H, T, S):
+            raise ValueError("%s: bias must be fp32 or bf16 [H, T, S] = [%d, %d, %d] (batch-invariant), got %s %s"
+                             % (op, H, T, S, bias.dtype, tuple(bias.shape)))
+        if bias.stride(2) != 1:
+            raise ValueError("%s: bias must have a contiguous last dimension (stride %d)" % (op, bias.stride(2)))
+    return B, T, S, H, Tp, Sp
+
+
+def _bias_attention_bi_check(q, k, v, pos_q, pos_k, gain, gcode, rel2d, rel1d, relx, P, code_bias, grid_w, causal, kv_len,
+                             dropout_p):
+    op = "ifseg::bias_attention_bi"
+    B, T, S, H, Tp, Sp = _check_common(op, q, k, v, gain, kv_len, causal, P, dropout_p)
+    C = H * 64
+    for name, t, n in (("pos_q", pos_q, T), ("pos_k", pos_k, S)):
+        if t.dtype != BF or tuple(t.shape) != (n, C):
+            raise ValueError("%s: %s must be bf16 [%d, %d], got %s %s" % (op, name, n, C, t.dtype, tuple(t.shape)))
+        if t.stride(1) != 1:
+            raise ValueError("%s: %s must have a contiguous last dimension (stride %d)" % (op, name, t.stride(1)))
+    tabs = (gcode, rel2d, rel1d, relx)
+    if any(t is None for t in tabs) != all(t is None for t in tabs):
+        raise ValueError("%s: gcode, rel2d, rel1d and relx come together or not at all" % op)
+    if gcode is not None:
+        # what ifseg_attn_dbias_grads needs for the table gradients
+        if T != S:
+            raise ValueError("%s: a relative-position bias needs T == S, got T = %d, S = %d" % (op, T, S))
+        if grid_w <= 0 or grid_w > 64 or grid_w % 8 != 0:
+            raise ValueError("%s: grid_w must be a multiple of 8 and at most 64, got %d" % (op, grid_w))
+        if P <= 0 or P % grid_w != 0 or P > T:
+            raise ValueError("%s: P = grid_h * grid_w grid tokens with P <= T; got P = %d, grid_w = %d, T = %d" % (op, P, grid_w, T))
+        Lt = T - P
+        if gcode.dtype != torch.int32 or tuple(gcode.shape) != (P,):
+            raise ValueError("%s: gcode must be int32 [P] = [%d], got %s %s" % (op, P, gcode.dtype, tuple(gcode.shape)))
+        for name, t, n in (("rel2d", rel2d, None), ("rel1d", rel1d, max(2 * Lt - 1, 0)), ("relx", relx, 2)):
+            if t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] != H or (n is not None and t.shape[1] != n):
+                raise ValueError("%s: %s must be fp32 [%d, %s], got %s %s" % (op, name, H, n if n is not None else "n2d", t.dtype, tuple(t.shape)))
+    return B, T, S, H, Tp, Sp
+
+
+def _aligned(t):
+    """the attention kernels read 16-byte row pieces: base 16-byte aligned, row and batch strides multiples of 8 elements
+    (csrc/attention_bi.hip, the entry points' checks); anything else is copied, not refused"""
+    if t.data_ptr() % 16 == 0 and all(s % 8 == 0 for s in t.stride()[:-1]):
+        return t
+    return t.contiguous()
+
+
+class _seed_as_given:
+    """the dropout seed of these ops is used as given: no per-update seed word (hip.set_seed_add) during their launches"""
+
+    def __enter__(self):
+        self.prev = hip.set_seed_add(None)
+
+    def __exit__(self, *exc):
+        hip.set_seed_add(self.prev)
+
+
+def _dense_view(packed, H, T, S):
+    d = hip.DenseBias.__new__(hip.DenseBias)
+    d.H, d.T, d.S, d.Tp, d.Sp, d.D = H, T, S, packed.shape[1], packed.shape[2], packed
+    return d
+
+
+def _fwd_bi(q, k, v, dense, gain, kv_len, causal, P, dropout_p, seed):
+    B, T, C = q.shape
+    S, H = k.shape[1], C // 64
+    out = torch.empty(B, T, C, dtype=BF, device=q.device)
+    lse = torch.empty(B, H, T, dtype=torch.float32, device=q.device)
+    with _seed_as_given():
+        hip.attn_fwd_bi(_aligned(q), _aligned(k), _aligned(v), dense, out, lse, B, H, T, S, causal=causal, P=P, gain=gain,
+                        kv_len=kv_len, drop=(dropout_p, seed) if dropout_p > 0 else None)
+    return out, lse
+
+
+def _bwd_bi(dout, q, k, v, gain, kv_len, out, lse, dense, causal, P, dropout_p, seed, zero_slabs):
+    """delta, then dQ / dK|dV of the batch-inner kernels -> (dq, dk, dv, slabs of sum_b dS, per-row terms of d gain)"""
+    B, T, C = q.shape
+    S, H = k.shape[1], C // 64
+    dev = q.device
+    q, k, v, dout = _aligned(q), _aligned(k), _aligned(v), dout.contiguous()
+    dq = torch.empty(B, T, C, dtype=BF, device=dev)
+    dk, dv = torch.empty(B, S, C, dtype=BF, device=dev), torch.empty(B, S, C, dtype=BF, device=dev)
+    delta = torch.empty(B, H, T, dtype=torch.float32, device=dev)
+    dgr = torch.empty(B, H, T, dtype=torch.float32, device=dev)
+    # causal launches skip the 32-blocks above the diagonal: those entries of the slabs are never written
+    slabs = (torch.zeros if zero_slabs else torch.empty)((B + 3) // 4, H, T, dense.Sp, dtype=BF, device=dev)
+    hip.attn_bwd(q, k, v, None, None, out, dout, lse, delta, dq, dk, dv, None, None, B, H, T, S, phases=hip.ATTN_BWD_DELTA)
+    with _seed_as_given():
+        hip.attn_bwd_bi(q, k, v, dout, lse, delta, dense, dq, dk, dv, slabs, B, H, T, S, causal=causal, P=P, gain=gain,
+                        dgain_rows=dgr, kv_len=kv_len, drop=(dropout_p, seed) if dropout_p > 0 else None)
+    return dq, dk, dv, slabs, dgr
+
+
+# ----------------------------------------------------------------------------------------------- attention_bias
+@custom_op("ifseg::attention_bias", mutates_args=(), device_types="cuda")
+def attention_bias(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bias: Optional[torch.Tensor],
+                   gain: Optional[torch.Tensor], kv_len: Optional[torch.Tensor], causal: bool, P: int, dropout_p: float,
+                   seed: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """out = gain_h * dropout(softmax(q k^T + bias [+ masks])) v on the batch-inner kernels (unify_multihead_attention.py:459-512
+    with `attn_bias` an ordinary tensor, :130,464-465).
+
+    q [B,T,H*64] bf16, already scaled; k, v [B,S,H*64] bf16 (row-strided views such as slices of a fused QKV projection are
+    fine; views that miss the kernels' 16-byte alignment are copied).
+    bias: None or [H,T,S], fp32 or bf16, batch-invariant, -inf = masked, differentiable (the kernels see its bf16 rounding).
+    gain: None or fp32 [H] (c_attn), differentiable.  kv_len: None or int32 [B], the valid key counts (key padding as a suffix).
+    causal / P: the engine's decoder layout -- P grid tokens first (P % 64 == 0), the tail behind them; grid query i sees grid
+    keys j <= i and EVERY tail key, tail query i sees tail keys j <= i and no grid key.  An ordinary causal mask goes into
+    `bias` as -inf with causal=False.
+    dropout_p, seed: the counter-based keep mask of the kernels, the seed used as given: hip.attn_dropout_mask(B, H, T, S,
+    dropout_p, seed, device) reproduces it.
+    Every query row must keep at least one visible key: a fully masked row is as undefined as in the reference's softmax.
+    Whole leading key blocks of a row may be masked.
+    -> (out [B,T,H*64] bf16, lse fp32 [B,H,T] in log2 units, the packed bias operand bf16 [H,T_p,S_p] (not differentiable))"""
+    B, T, S, H, Tp, Sp = _attention_bias_check(q, k, v, bias, gain, kv_len, causal, P, dropout_p)
+    prev = _stream_scope(q)
+    try:
+        dense = hip.DenseBias(H, T, S, q.device)
+        hip.attn_bias_pack(dense, bias, causal=causal, P=P)
+        out, lse = _fwd_bi(q, k, v, dense, gain, kv_len, causal, P, dropout_p, seed)
+        return out, lse, dense.D
+    finally:
+        hip.set_stream(prev)
+
+
+@attention_bias.register_fake
+def _(q, k, v, bias, gain, kv_len, causal, P, dropout_p, seed):
+    B, T, S, H, Tp, Sp = _attention_bias_check(q, k, v, bias, gain, kv_len, causal, P, dropout_p)
+    return q.new_empty(B, T, H * 64), q.new_empty(B, H, T, dtype=torch.float32), q.new_empty(H, Tp, Sp)
+
+
+@custom_op("ifseg::attention_bias_bwd", mutates_args=(), device_types="cuda")
+def attention_bias_bwd(dout: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bias: Optional[torch.Tensor],
+                       gain: Optional[torch.Tensor], kv_len: Optional[torch.Tensor], out: torch.Tensor, lse: torch.Tensor,
+                       packed: torch.Tensor, causal: bool, P: int, dropout_p: float, seed: int
+                       ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """-> (dq, dk, dv, dbias, dgain): dbias = sum_b dS in bias's dtype and shape (an empty tensor without a bias; exactly 0
+    where the bias is -inf), dgain fp32 [H]"""
+    B, T, S, H, Tp, Sp = _attention_bias_check(q, k, v, bias, gain, kv_len, causal, P, dropout_p)
+    prev = _stream_scope(q)
+    try:
+        dense = _dense_view(packed, H, T, S)
+        dq, dk, dv, slabs, dgr = _bwd_bi(dout, q, k, v, gain, kv_len, out, lse, dense, causal, P, dropout_p, seed, causal)
+        if bias is not None:
+            dbias = torch.empty(H, T, S, dtype=bias.dtype, device=q.device)
+            hip.attn_dbias_sum(slabs, S, dbias)
+        else:
+            dbias = torch.empty(0, dtype=torch.float32, device=q.device)
+        return dq, dk, dv, dbias, dgr.sum((0, 2))
+    finally:
+        hip.set_stream(prev)
+
+
+@attention_bias_bwd.register_fake
+def _(dout, q, k, v, bias, gain, kv_len, out, lse, packed, causal, P, dropout_p, seed):
+    B, T, S, H, Tp, Sp = _attention_bias_check(q, k, v, bias, gain, kv_len, causal, P, dropout_p)
+    dbias = q.new_empty(0, dtype=torch.float32) if bias is None else q.new_empty(H, T, S, dtype=bias.dtype)
+    return q.new_empty(B, T, H * 64), q.new_empty(B, S, H * 64), q.new_empty(B, S, H * 64), dbias, q.new_empty(H, dtype=torch.float32)
+
+
+def _ab_setup(ctx, inputs, output):
+    q, k, v, bias, gain, kv_len, causal, P, dropout_p, seed = inputs
+    ctx.save_for_backward(q, k, v, bias, gain, kv_len, output[0], output[1], output[2])
+    ctx.mark_non_differentiable(output[2])
+    ctx.meta = (causal, P, dropout_p, seed)
+
+
+def _ab_backward(ctx, gout, glse, gpacked):
+    q, k, v, bias, gain, kv_len, out, lse, packed = ctx.saved_tensors
+    causal, P, dropout_p, seed = ctx.meta
+    dq, dk, dv, dbias, dgain = torch.ops.ifseg.attention_bias_bwd(gout, q, k, v, bias, gain, kv_len, out, lse, packed, causal,
+                                                                  P, dropout_p, seed)
+    return (dq, dk, dv, dbias if bias is not None else None, dgain if gain is not None else None, None, None, None, None, None)
+
+
+attention_bias.register_autograd(_ab_backward, setup_context=_ab_setup)
+
+
+# ----------------------------------------------------------------------------------------------- bias_attention_bi
+@custom_op("ifseg::bias_attention_bi", mutates_args=(), device_types="cuda")
+def bias_attention_bi(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pos_q: torch.Tensor, pos_k: torch.Tensor,
+                      gain: torch.Tensor, gcode: Optional[torch.Tensor], rel2d: Optional[torch.Tensor],
+                      rel1d: Optional[torch.Tensor], relx: Optional[torch.Tensor], P: int, code_bias: int, grid_w: int,
+                      causal: bool, kv_len: Optional[torch.Tensor], dropout_p: float, seed: int
+                      ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """the arguments of bias_attention plus key counts and attention dropout (see attention_bias), on the batch-inner kernels:
+    the bias pos_q pos_k^T + rel is built once as the dense bf16 operand (ifseg_attn_dense_bias) and shared by the batch.
+    -> (out, lse, the dense operand bf16 [H,T_p,S_p] (not differentiable))"""
+    B, T, S, H, Tp, Sp = _bias_attention_bi_check(q, k, v, pos_q, pos_k, gain, gcode, rel2d, rel1d, relx, P, code_bias, grid_w,
+                                                  causal, kv_len, dropout_p)
+    prev = _stream_scope(q)
+    try:
+        dense = hip.DenseBias(H, T, S, q.device)
+        if causal:
+            dense.D.fill_(float("-inf"))       # the builder leaves masked tiles that no schedule reads unwritten
+        hip.attn_dense_bias(dense, _aligned(pos_q), _aligned(pos_k), rel=_rel(P, gcode, rel2d, rel1d, relx, code_bias, grid_w), causal=causal, P=P)
+        out, lse = _fwd_bi(q, k, v, dense, gain, kv_len, causal, P, dropout_p, seed)
+        return out, lse, dense.D
+    finally:
+        hip.set_stream(prev)
+
+
+@bias_attention_bi.register_fake
+def _(q, k, v, pos_q, pos_k, gain, gcode, rel2d, rel1d, relx, P, code_bias, grid_w, causal, kv_len, dropout_p, seed):
+    B, T, S, H, Tp, Sp = _bias_attention_bi_check(q, k, v, pos_q, pos_k, gain, gcode, rel2d, rel1d, relx, P, code_bias, grid_w,
+                                                  causal, kv_len, dropout_p)
+    return q.new_empty(B, T, H * 64), q.new_empty(B, H, T, dtype=torch.float32), q.new_empty(H, Tp, Sp)
+
+
+@custom_op("ifseg::bias_attention_bi_bwd", mutates_args=(), device_types="cuda")
+def bias_attention_bi_bwd(dout: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pos_q: torch.Tensor,
+                          pos_k: torch.Tensor, gain: torch.Tensor, out: torch.Tensor, lse: torch.Tensor, packed: torch.Tensor,
+                          gcode: Optional[torch.Tensor], rel2d: Optional[torch.Tensor], rel1d: Optional[torch.Tensor],
+                          relx: Optional[torch.Tensor], P: int, code_bias: int, grid_w: int, causal: bool,
+                          kv_len: Optional[torch.Tensor], dropout_p: float, seed: int
+                          ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor,
+                                     torch.Tensor, torch.Tensor, torch.Tensor]:
+    """-> (dq, dk, dv, dpos_q, dpos_k, dgain, drel2d, drel1d, drelx) as bias_attention_bwd; everything behind sum_b dS comes
+    from ifseg_attn_dbias_grads, the partial tables summed in part order"""
+    B, T, S, H, Tp, Sp = _bias_attention_bi_check(q, k, v, pos_q, pos_k, gain, gcode, rel2d, rel1d, relx, P, code_bias, grid_w,
+                                                  causal, kv_len, dropout_p)
+    prev = _stream_scope(q)
+    try:
+        dev, C = q.device, H * 64
+        dense = _dense_view(packed, H, T, S)
+        # (zero-filled always: on grids that are not 32 wide the table kernel reads masked pairs of blocks a causal launch skips)
+        dq, dk, dv, slabs, dgr = _bwd_bi(dout, q, k, v, gain, kv_len, out, lse, dense, causal, P, dropout_p, seed, True)
+        dpq = torch.empty(T, C, dtype=torch.float32, device=dev)
+        dpk = torch.empty(S, C, dtype=torch.float32, device=dev)
+        kw, parts = {}, None
+        if gcode is not None:
+            NP = hip.dbias_nparts()
+            parts = [torch.empty(H, NP, t.shape[1], dtype=torch.float32, device=dev) for t in (rel2d, rel1d, relx)]
+            kw = dict(P=P, grid_h=P // grid_w, grid_w=grid_w, drel2d=parts[0], drel1d=parts[1], drelx=parts[2])
+        hip.attn_dbias_grads(slabs, S, pos_q=_aligned(pos_q), pos_k=_aligned(pos_k), dpq_acc=dpq, dpk_acc=dpk, accumulate_pos=False, causal=causal, **kw)
+        e = torch.empty(0, dtype=torch.float32, device=dev)
+        tabs = [e, e.clone(), e.clone()]
+        if parts is not None:
+            tabs = []
+            for p in parts:
+                t = torch.empty(H, p.shape[2], dtype=torch.float32, device=dev)
+                tabs.append(hip.reduce_parts(p, t, H, p.shape[1], p.shape[2]) if p.shape[2] else t)
+        return dq, dk, dv, dpq.to(pos_q.dtype), dpk.to(pos_k.dtype), dgr.sum((0, 2)), tabs[0], tabs[1], tabs[2]
+    finally:
+        hip.set_stream(prev)
+
+
+@bias_attention_bi_bwd.register_fake
+def _(dout, q, k, v, pos_q, pos_k, gain, out, lse, packed, gcode, rel2d, rel1d, relx, P, code_bias, grid_w, causal, kv_len,
+      dropout_p, seed):
+    _bias_attention_bi_check(q, k, v, pos_q, pos_k, gain, gcode, rel2d, rel1d, relx, P, code_bias, grid_w, causal, kv_len, dropout_p)
+    f = lambda t: q.new_empty(0, dtype=torch.float32) if t is None else t.new_empty(t.shape)
+    return (q.new_empty(q.shape), k.new_empty(k.shape), v.new_empty(v.shape), pos_q.new_empty(pos_q.shape),
+            pos_k.new_empty(pos_k.shape), gain.new_empty(gain.shape, dtype=torch.float32), f(rel2d), f(rel1d), f(relx))
+
+
+def _abi_setup(ctx, inputs, output):
+    q, k, v, pos_q, pos_k, gain, gcode, rel2d, rel1d, relx, P, code_bias, grid_w, causal, kv_len, dropout_p, seed = inputs
+    ctx.save_for_backward(q, k, v, pos_q, pos_k, gain, output[0], output[1], output[2], gcode, rel2d, rel1d, relx, kv_len)
+    ctx.mark_non_differentiable(output[2])
+    ctx.meta = (P, code_bias, grid_w, causal, dropout_p, seed)
+
+
+def _abi_backward(ctx, gout, glse, gpacked):
+    q, k, v, pos_q, pos_k, gain, out, lse, packed, gcode, rel2d, rel1d, relx, kv_len = ctx.saved_tensors
+    P, code_bias, grid_w, causal, dropout_p, seed = ctx.meta
+    dq, dk, dv, dpq, dpk, dgain, d2, d1, dx = torch.ops.ifseg.bias_attention_bi_bwd(
+        gout, q, k, v, pos_q, pos_k, gain, out, lse, packed, gcode, rel2d, rel1d, relx, P, code_bias, grid_w, causal, kv_len,
+        dropout_p, seed)
+    has = gcode is not None
+    return (dq, dk, dv, dpq, dpk, dgain, None, d2 if has else None, d1 if has else None, dx if has else None,
+            None, None, None, None, None, None, None)
+
+
+bias_attention_bi.register_autograd(_abi_backward, setup_context=_abi_setup)
+
+
+# ----------------------------------------------------------------------------------------------- seg_loss
+SEG_LOSS_MAX_CLASSES = 512       # csrc/loss.hip NS_MAX (criterions.seg_criterion.FUSED_MAX_CLASSES)
+
+
+def _seg_loss_check(logits, target, hp, wp, H, W):
+    op = "ifseg::seg_loss"
+    if logits.dim() != 3 or logits.dtype != BF:
+        raise ValueError("%s: logits must be bf16 [B, hp*wp + 1, nseg], got %s %s" % (op, logits.dtype, tuple(logits.shape)))
+    B, rows, nseg = logits.shape
+    if hp <= 0 or wp <= 0 or rows != hp * wp + 1:
+        raise ValueError("%s: logits.shape[1] = %d, expected hp * wp + 1 = %d" % (op, rows, hp * wp + 1))
+    if H != 16 * hp or W != 16 * wp:
+        raise ValueError("%s: the fused kernel upsamples x16: H = %d, W = %d, expected H == 16 * hp = %d and W == 16 * wp = %d"
+                         % (op, H, W, 16 * hp, 16 * wp))
+    if nseg < 1 or nseg > SEG_LOSS_MAX_CLASSES:
+        raise ValueError("%s: nseg = %d classes, the kernel takes 1 .. FUSED_MAX_CLASSES = %d" % (op, nseg, SEG_LOSS_MAX_CLASSES))
+    if target.dtype != torch.int64 or target.dim() != 2 or target.shape[0] != B or target.shape[1] != H * W + 1:
+        raise ValueError("%s: target must be int64 [B, H * W + 1] = [%d, %d], got %s %s"
+                         % (op, B, H * W + 1, target.dtype, tuple(target.shape)))
+    return B, nseg, (nseg + 7) // 8 * 8
+
+
+@custom_op("ifseg::seg_loss", mutates_args=(), device_types="cuda")
+def seg_loss(logits: torch.Tensor, target: torch.Tensor, hp: int, wp: int, H: int, W: int, seg_id_offset: int,
+             label_smoothing: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """mean cross entropy of the x16 bilinear upsample of the per-patch logits (seg_criterion.py:237-244,269-347) in the fused
+    kernel pair of csrc/loss.hip.  logits bf16 [B, hp*wp+1, nseg] (the last row is eos; a row-strided view is allowed),
+    target int64 [B, H*W+1] dictionary ids (pad = 1, eos = 2 and seg_id_offset + nseg are ignored).
+    -> (loss fp32 [], stats fp32 [2 + 3 nseg] = CE sum, pixel count, intersect / predicted / label areas,
+        dlogits bf16 [B, hp*wp+1, nseg rounded up to 8] = d loss / d logits (padding columns zero),
+        bad int32 [1]: non-zero when a label is neither a class nor pad / eos / ignore -- read it when convenient, the op
+        does not synchronise).  Differentiable in logits only."""
+    B, nseg, npad = _seg_loss_check(logits, target, hp, wp, H, W)
+    prev = _stream_scope(logits)
+    try:
+        dev, P = logits.device, hp * wp
+        # the kernel reads 16-byte pieces of a class axis padded to a multiple of 8: a view that already lies in such a
+        # buffer is taken as it is
+        lp = logits
+        if not (lp.stride(2) == 1 and lp.stride(1) % 8 == 0 and lp.stride(1) >= npad and lp.stride(0) % 8 == 0
+                and lp.data_ptr() % 16 == 0):
+            lp = torch.zeros(B, P + 1, npad, dtype=BF, device=dev)
+            lp[:, :, :nseg].copy_(logits)
+        n_tiles, nstat = B * P, 2 + 3 * nseg
+        tile = torch.empty(n_tiles * 9 * nseg, dtype=torch.float32, device=dev)
+        sp = torch.empty(n_tiles * nstat, dtype=torch.float32, device=dev)
+        stats = torch.empty(nstat, dtype=torch.float32, device=dev)
+        dl = torch.empty(B, P + 1, npad, dtype=BF, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        hip.seg_loss(lp, target.contiguous(), hp, wp, H, W, nseg, seg_id_offset, tile, sp, stats, dl, loss, bad_label=bad,
+                     label_smoothing=float(label_smoothing))
+        return loss, stats, dl, bad
+    finally:
+        hip.set_stream(prev)
+
+
+@seg_loss.register_fake
+def _(logits, target, hp, wp, H, W, seg_id_offset, label_smoothing):
+    B, nseg, npad = _seg_loss_check(logits, target, hp, wp, H, W)
+    f32 = torch.float32
+    return (logits.new_empty((), dtype=f32), logits.new_empty(2 + 3 * nseg, dtype=f32), logits.new_empty(B, hp * wp + 1, npad),
+            logits.new_empty(1, dtype=torch.int32))
+
+
+@custom_op("ifseg::seg_loss_bwd", mutates_args=(), device_types="cuda")
+def seg_loss_bwd(grad_loss: torch.Tensor, dlogits: torch.Tensor, nseg: int) -> torch.Tensor:
+    """the gradient the forward kernel already produced, times the upstream gradient of the loss -> bf16 [B, hp*wp+1, nseg]"""
+    g = dlogits[:, :, :nseg]
+    return g * grad_loss.to(g.dtype)
+
+
+@seg_loss_bwd.register_fake
+def _(grad_loss, dlogits, nseg):
+    return dlogits.new_empty(dlogits.shape[0], dlogits.shape[1], nseg)
+
+
+def _sl_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[2])
+    ctx.mark_non_differentiable(output[1], output[2], output[3])
+    ctx.nseg = inputs[0].shape[2]
+
+
+def _sl_backward(ctx, gloss, gstats, gdl, gbad):
+    (dl,) = ctx.saved_tensors
+    return torch.ops.ifseg.seg_loss_bwd(gloss, dl, ctx.nseg), None, None, None, None, None, None, None
+
+
+seg_loss.register_autograd(_sl_backward, setup_context=_sl_setup)

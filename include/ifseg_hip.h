@@ -19,7 +19,7 @@
 extern "C" {
 #endif
 
-#define IFSEG_ABI_VERSION 18
+#define IFSEG_ABI_VERSION 19
 #define IFSEG_ERR_BAD_SHAPE (-2)
 #define IFSEG_ERR_BAD_ARG (-3)
 
@@ -289,6 +289,21 @@ typedef struct ifseg_attn_dbias_args {
 } ifseg_attn_dbias_args;
 int ifseg_attn_dbias_grads(const ifseg_attn_dbias_args* args, void* stream);
 int ifseg_attn_dbias_nparts(void);
+
+/* ---- attention with a bias the caller computed (csrc/attention_ops.hip; torch.ops.ifseg.attention_bias) ----
+ * The reference's attention module takes the bias as an ordinary tensor (unify_multihead_attention.py:130,464-465, `attn_bias`).
+ * ifseg_attn_bias_pack: D[h][i][j] (bf16 [H,Tp,Sp], the operand of ifseg_attn_fwd_bi / _bwd_bi) = bf16_rne(bias[h][i][j]) for
+ *   i < T, j < S; -inf for the padding rows / columns and, when `causal`, for the pairs ifseg_attn_dense_bias masks
+ *   ("tail-first" order with P grid tokens; P % 64 == 0, P <= min(T, S)).  EVERY element of D is written.  bias: fp32
+ *   (bias_is_f32) or bf16 [H,T,S], last dimension contiguous, head / row strides in elements; NULL = a zero bias.
+ * ifseg_attn_dbias_sum: out[h][i][j] = sum_{g < ng} dbias[g][h][i][j] for j < S (dbias: the bf16 slabs [ng][H][T][Sp] of
+ *   ifseg_attn_bwd_bi), added in fp32 in slab order (bit-reproducible), stored as fp32 (out_is_f32) or bf16 with the strides
+ *   of `out` in elements.
+ * One pass each, 16-byte accesses along j wherever the unpadded side allows them. */
+int ifseg_attn_bias_pack(const void* bias, int bias_is_f32, long long head_stride, long long row_stride, int H, int T, int S,
+                         int causal, int P, void* D, int Sp, int Tp, void* stream);
+int ifseg_attn_dbias_sum(const void* dbias, int ng, int H, int T, int S, int Sp, void* out, int out_is_f32,
+                         long long head_stride, long long row_stride, void* stream);
 
 /* -------------------------------------------------------------- row ops */
 /* Row addressing used below: logical row r lives at element offset
