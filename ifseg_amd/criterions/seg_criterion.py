@@ -119,6 +119,11 @@ class SegCriterion(CriterionBase):
         if self.id2rawtext and len(self.id2rawtext) != self.num_seg:
             raise AssertionError("category_list names %d classes, num_seg_tokens is %d" % (len(self.id2rawtext), self.num_seg))
         self.padding_idx = PAD
+        # image-free samples drawn on the device (ifseg_amd/artificial.py).  The trainer sets the seed and, before every
+        # micro-batch, the ordinal of its first sample (an int, or a device int64 word inside a captured step); without a
+        # trainer the criterion counts the samples it has drawn.
+        self.imfree_seed, self.imfree_first_ordinal = 1, None
+        self._imfree_sampler, self._imfree_drawn = None, 0
 
     def _lazy_initialization(self, sample, model, ema_model=None):
         """seg_criterion.py:373-407: every <seg_i> embedding := mean token embedding of its category name
@@ -146,6 +151,22 @@ class SegCriterion(CriterionBase):
             if ema_model is not None:
                 ema_model.decoder.seg_projection.weight.data = avg
 
+    def _artificial_sample(self, sample):
+        """aux_input / text2seg_target of this batch from the device sampler; the prompt is the real image's prompt"""
+        net = sample["net_input"]
+        src = net["src_tokens"]
+        if self._imfree_sampler is None:
+            if self.task is None or not hasattr(self.task, "build_artificial_sampler"):
+                raise RuntimeError("seg_criterion: the sample carries no aux_input and there is no task to build the "
+                                   "artificial-image sampler from")
+            self._imfree_sampler = self.task.build_artificial_sampler(src.device, seed=self.imfree_seed)
+        B = src.shape[0]
+        first = self.imfree_first_ordinal
+        if first is None:
+            first = self._imfree_drawn
+            self._imfree_drawn += B
+        return self._imfree_sampler.sample(B, first, src, net.get("src_lengths"))
+
     def forward(self, model, sample, update_num=0, reduce=True, ema_model=None):
         """seg_criterion.py:165-235 (lazy init on the first call, image-free / supervised train branches, eval branch)."""
         if self.iter == -1:
@@ -156,6 +177,8 @@ class SegCriterion(CriterionBase):
         if self.unsupervised_segmentation and model.training:
             # image-free training (seg_criterion.py:179-186): the loss comes from the artificial image; the real
             # images are only evaluated (no grad) for the logged metrics
+            if getattr(getattr(self.task, "cfg", None), "artificial_image_on_device", False) or sample.get("aux_input") is None:
+                sample = dict(sample, **self._artificial_sample(sample))
             net_output = model(full_context_alignment=self.full_context_alignment, aux_input=sample["aux_input"])
             imfree_loss = self.compute_imfree_loss(model, net_output[1]["aux_output"], sample, update_num, reduce=reduce)
             loss = imfree_loss

@@ -64,6 +64,14 @@ __device__ __forceinline__ float erf_as(float x, float e) {
   const float r = 1.f - poly * e;
   return x < 0.f ? -r : r;
 }
+// Counter-based generator of the dropout / DropPath masks (rowops.hip) and of the artificial images (imfree.hip):
+// one 64-bit draw per counter value, nothing stored.
+__device__ __forceinline__ unsigned long long splitmix64(unsigned long long z) {
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
 union U128 {
   uint4 v;
   bf16x8 b;

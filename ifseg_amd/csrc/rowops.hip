@@ -50,12 +50,7 @@ __device__ __forceinline__ uint4 pack8(const float* f) {
 // (unify_transformer_layer.py:19-35) inside residual_connection (:196).  The RNG stream necessarily
 // differs from torch's.  The same mask is applied by the stand-alone kernel (ifseg_dropout) and by the
 // fused epilogue of ln_fwd / prologue of ln_bwd.
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
+// (splitmix64, the counter-based generator: common.h)
 struct DropArgs {   // on == 0: identity
   int on; float p; unsigned long long seed; const float* dpscale; int rows_per_batch;
   const unsigned long long* seed_add;   // device word added to `seed` (the per-update part: a captured step replays with new masks)

@@ -21,7 +21,7 @@ GEMM_RELU, GEMM_OUT_F32, GEMM_ACCUMULATE = 1, 2, 4
 c_void_p, c_int, c_float, c_ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_longlong
 
 
-ABI_VERSION = 19         # == IFSEG_ABI_VERSION of include/ifseg_hip.h (checked at load time and by __graft_entry__.build)
+ABI_VERSION = 20         # == IFSEG_ABI_VERSION of include/ifseg_hip.h (checked at load time and by __graft_entry__.build)
 
 
 def lib():
@@ -752,6 +752,38 @@ def embed_bag_mean(table, ids, ends, add, out):
                                     c_int(maxlen), c_int(rpb), c_ll(ob), c_int(ol), _stream())
     _check(rc, "embed_bag_mean")
     return out
+
+
+def imfree_draw(seed, first_ordinal, B, l, r, nseg, shapes, coarse):
+    """shapes int32 [B, 2], coarse int32 [B, (r-1)^2] <- the artificial images of sample ordinals first_ordinal + b
+    (csrc/imfree.hip); first_ordinal: a python int, or a device int64 word (read at execution time: graph replays)"""
+    assert shapes.dtype == torch.int32 and coarse.dtype == torch.int32 and shapes.is_contiguous() and coarse.is_contiguous()
+    assert tuple(shapes.shape) == (B, 2) and tuple(coarse.shape) == (B, (r - 1) * (r - 1))
+    word = first_ordinal if isinstance(first_ordinal, torch.Tensor) else None
+    if word is not None:
+        assert word.dtype == torch.int64 and word.numel() == 1
+    rc = lib().ifseg_imfree_draw(ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), c_ll(0 if word is not None else int(first_ordinal)),
+                                 _ptr(word), c_int(B), c_int(l), c_int(r), c_int(nseg), _ptr(shapes), _ptr(coarse), _stream())
+    _check(rc, "imfree_draw")
+    return shapes, coarse
+
+
+def imfree_expand(shapes, coarse, name_ids, name_len, hp, wp, seg_id_offset, bos, eos, pad, ids, ends, prev, target):
+    """the collater layout of the artificial images (csrc/imfree.hip): coarse int32 [B, max_side^2] -> ids int64 [B, P*Lmax],
+    ends int64 [B*P], prev int64 [B, P+1], target int64 [B, 256*P + 1]"""
+    B, P = shapes.shape[0], hp * wp
+    nseg, Lmax = name_ids.shape[0] - 1, name_ids.shape[1]
+    max_side = int(round(coarse.shape[1] ** 0.5))
+    assert shapes.dtype == torch.int32 and coarse.dtype == torch.int32 and shapes.is_contiguous() and coarse.is_contiguous()
+    assert tuple(shapes.shape) == (B, 2) and tuple(coarse.shape) == (B, max_side * max_side)
+    assert name_ids.dtype == torch.int64 and name_len.dtype == torch.int32 and name_ids.is_contiguous() and name_len.is_contiguous()
+    assert name_len.numel() == nseg + 1
+    for t, n in ((ids, B * P * Lmax), (ends, B * P), (prev, B * (P + 1)), (target, B * (256 * P + 1))):
+        assert t.dtype == torch.int64 and t.is_contiguous() and t.numel() == n, (tuple(t.shape), n)
+    rc = lib().ifseg_imfree_expand(_ptr(shapes), _ptr(coarse), c_int(max_side), _ptr(name_ids), _ptr(name_len), c_int(nseg),
+                                   c_int(Lmax), c_int(B), c_int(hp), c_int(wp), c_ll(seg_id_offset), c_ll(bos), c_ll(eos), c_ll(pad),
+                                   _ptr(ids), _ptr(ends), _ptr(prev), _ptr(target), _stream())
+    _check(rc, "imfree_expand")
 
 
 def embed_rows(table, ids, add, out):

@@ -65,6 +65,8 @@ class SegmentationConfig(OFAConfig):
     num_seg_tokens: int = _f(150, "number of seg tokens")
     category_list: str = _f("", "list of semantic category words (comma separated)")
     epoch_row_count: int = _f(-1, "if -1, disabled.")
+    artificial_image_on_device: bool = _f(False, "draw the artificial image of every image-free update on the device "
+                                                 "(ifseg_amd/artificial.py); the sample's own aux_input is then ignored")
 
 
 class SizeDictionary:
@@ -257,6 +259,32 @@ class SegmentationTask(TaskBase):
                               "patch_images": padded.to(device), "patch_masks": torch.cat(ends).to(device),
                               "prev_output_tokens": torch.zeros(batch, 1, dtype=torch.long, device=device)},
                 "text2seg_target": torch.stack(tgts).to(device)}
+
+    def build_artificial_sampler(self, device, seed=1):
+        """The generator of the image-free samples for `--artificial-image-type rand_k[-L-R]` (ifseg_amd/artificial.py) on
+        this task's patch grid.  The class names come from where the criterion's lazy seg-token initialisation takes them:
+        `category_token_ids`, else `category_list` through the BPE encoder; the 'unknown' name (id2rawtext's last entry,
+        segmentation_dataset.py:183; never drawn) is `unknown_token_ids` / the BPE of " unknown", else an empty bag."""
+        from ...artificial import ArtificialImageSampler, parse_artificial_image_type
+        lr = parse_artificial_image_type(self.cfg.artificial_image_type)
+        if lr is None:
+            raise RuntimeError("artificial_image_type 'none': this task has no artificial image to draw")
+        nseg = self.num_seg_tokens
+        names = self.category_token_ids
+        if names is None:
+            cats = [x.strip() for x in self.category_list.split(",")] if self.category_list else []
+            if not cats:
+                raise RuntimeError("build_artificial_sampler: the task carries neither category_list (+ BPE) nor category_token_ids")
+            names = [self.encode_category(" %s" % x) for x in cats]
+        names = [torch.as_tensor(x, dtype=torch.long).reshape(-1) for x in names]
+        if len(names) != nseg:
+            raise AssertionError("%d category names for %d seg tokens" % (len(names), nseg))
+        unknown = getattr(self, "unknown_token_ids", None)
+        if unknown is None:
+            unknown = self.encode_category(" unknown") if self.bpe is not None else torch.zeros(0, dtype=torch.long)
+        hp = self.cfg.patch_image_size // 16
+        return ArtificialImageSampler(names + [torch.as_tensor(unknown, dtype=torch.long)], self.seg_id_offset, hp, hp, lr[0], lr[1],
+                                      seed=seed, device=device, bos=BOS, eos=EOS, pad=PAD)
 
     def train_step(self, sample, model, criterion, optimizer, update_num, ignore_grad=False, **extra_kwargs):
         """tasks/mm_tasks/segmentation.py:190-222."""

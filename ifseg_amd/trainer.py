@@ -432,6 +432,7 @@ class Trainer:
                     # update, then the next call's samples (HipEngine._prefetch_request)
                     eng._pf_request = [q["net_input"]["patch_images"] for q in list(samples[i + 1:]) + ahead
                                        if "patch_images" in q.get("net_input", {})]
+                self._set_imfree_ordinal(i, len(samples), sample, captured)
                 eng.mark("step_start")
                 loss, ss, lg = self.task.train_step(sample, self.model, self.criterion, None, self.num_updates)
                 logs.append(lg)
@@ -462,6 +463,55 @@ class Trainer:
         if captured and eng._pf is not None:
             torch.cuda.current_stream().wait_event(eng._pf["done"])     # every forked stream rejoins before the capture ends
         return logs
+
+    def _imfree_on_device(self, sample):
+        """does the criterion draw this sample's artificial image itself (SegCriterion.forward, image-free branch)?"""
+        crit = self.criterion
+        if not hasattr(crit, "imfree_first_ordinal") or not getattr(crit, "unsupervised_segmentation", False):
+            return False
+        return bool(getattr(getattr(self.task, "cfg", None), "artificial_image_on_device", False)) or sample.get("aux_input") is None
+
+    def _set_imfree_ordinal(self, micro, n_micro, sample, captured):
+        """Tell the criterion which artificial images this micro-batch draws (ifseg_amd/artificial.py; seed = this trainer's
+        seed).  Sample b of micro-batch `micro` of this rank in update `num_updates` (0-based) has the ordinal
+
+            ((num_updates * n_micro + micro) * world + rank) * batch + b
+
+        (`artificial.trainer_first_ordinal`) with n_micro, world and batch -- the micro-batches per update, the ranks and the
+        samples per micro-batch -- fixed for the run (a smaller last batch is fine, a change of shape is refused).  A
+        mixed-radix number: no two samples of a run share an ordinal across ranks, micro-batches and updates, and a run
+        resumed at update k (num_updates restored) draws what the uninterrupted run would.  Inside a captured step the
+        ordinal is a device word the graph's draw kernel reads on every replay (`_upload_imfree_ordinal`)."""
+        crit = self.criterion
+        if not self._imfree_on_device(sample):
+            return
+        from .artificial import trainer_first_ordinal
+        crit.imfree_seed = self.seed
+        B = sample["net_input"]["src_tokens"].shape[0] if "net_input" in sample else 1
+        shape = getattr(self, "_imfree_shape", None)
+        if shape is None:
+            shape = self._imfree_shape = (n_micro, B)
+        if n_micro != shape[0] or B > shape[1]:
+            raise RuntimeError("Trainer: the artificial-image ordinals need a fixed run shape: %d micro-batches of at most %d "
+                               "samples per update, got %d of %d" % (shape[0], shape[1], n_micro, B))
+        rank = dist.get_rank() if dist.is_initialized() else 0
+        first = trainer_first_ordinal(self.num_updates, micro, rank, shape[0], self.world, shape[1])
+        if captured:
+            crit.imfree_first_ordinal = self._upload_imfree_ordinal(first, enqueue=False)
+        else:
+            crit.imfree_first_ordinal = first
+
+    def _upload_imfree_ordinal(self, first, enqueue=True):
+        """first ordinal of the next (captured) step -> its device word, by an async copy from a ring of pinned words"""
+        if getattr(self, "_imfree_word", None) is None:
+            self._imfree_word = torch.zeros(1, dtype=torch.int64, device=self.device)
+            self._imfree_pin = torch.zeros(64, dtype=torch.int64).pin_memory()
+            self._imfree_pin_i = 0
+        if enqueue:
+            i = self._imfree_pin_i = (self._imfree_pin_i + 1) % 64
+            self._imfree_pin[i] = first
+            self._imfree_word.copy_(self._imfree_pin[i:i + 1], non_blocking=True)
+        return self._imfree_word
 
     def _adam_deferred(self, lr, step, gscale):
         """clip + Adam of this update on the optimizer's own stream, one launch per range of `optimizer_plan`, in the order the
@@ -545,6 +595,10 @@ class Trainer:
         # per-update scalars go to the device BEFORE the replay, in stream order
         eng.upload_step_seed()
         self._upload_hyper(self.get_lr(), self.num_updates + 1, self._last_gscale or 1.0)
+        if self._imfree_on_device(sample):
+            from .artificial import trainer_first_ordinal
+            shape = getattr(self, "_imfree_shape", None) or (1, sample["net_input"]["src_tokens"].shape[0])
+            self._upload_imfree_ordinal(trainer_first_ordinal(self.num_updates, 0, 0, 1, 1, shape[1]))
         if ent is None:
             if self.num_updates < 2:
                 raise RuntimeError("Trainer.train_step(graph=True): run at least two eager updates first (workspaces, "

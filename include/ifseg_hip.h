@@ -19,7 +19,7 @@
 extern "C" {
 #endif
 
-#define IFSEG_ABI_VERSION 19
+#define IFSEG_ABI_VERSION 20
 #define IFSEG_ERR_BAD_SHAPE (-2)
 #define IFSEG_ERR_BAD_ARG (-3)
 
@@ -488,6 +488,37 @@ int ifseg_seg_loss_tiles(const void* logits, int ldl, long long logits_bs, const
                          pad / eos / ignore (F.cross_entropy would raise); may be NULL */, float label_smoothing, void* stream);
 int ifseg_seg_loss_gather(const float* tile_partial, const float* stats, void* dlogits, int ldl,
                           long long dlogits_bs, int B, int hp, int wp, int nseg, float* loss_out, void* stream);
+
+/* ---------------------------------------------------- image-free samples */
+/* The artificial image of `--artificial-image-type rand_k-L-R` (data/mm_data/segmentation_dataset.py:303-345) and its collater
+ * layout (:85-107), generated on the device (csrc/imfree.hip; ifseg_amd/artificial.py is the bit-exact host specification).
+ *
+ * ifseg_imfree_draw: for sample ordinal n = first + b (first = *first_ordinal_dev when that device int64 word is given -- a
+ * captured step then draws new images on every replay -- otherwise first_ordinal, 0 <= first, first + B <= 2^32), with
+ * u(n, i) = splitmix64(seed + (n << 32) + i) (mod 2^64, the generator of ifseg_dropout):
+ *   sh = l + (((u(n,0) >> 32) * (r - l)) >> 32),  sw = l + (((u(n,1) >> 32) * (r - l)) >> 32)        uniform in [l, r)
+ *   coarse[y][x] = ((u(n, 2 + y*sw + x) >> 32) * nseg) >> 32                                          uniform in [0, nseg)
+ * shapes int32 [B, 2] = (sh, sw); coarse int32 [B, (r-1)^2]: the sh x sw map row-major in the leading entries, 0 beyond.
+ * 1 <= l < r <= 129, 1 <= nseg <= 65535, else IFSEG_ERR_BAD_ARG.
+ *
+ * ifseg_imfree_expand: from shapes / coarse (int32 [B, max_side^2], drawn with r = max_side + 1 or supplied by the caller; sh, sw
+ * are clamped to [1, max_side], classes to [0, nseg]), the name table name_ids int64 [nseg+1, Lmax] / name_len int32 [nseg+1]
+ * (clamped to [0, Lmax]) and the hp x wp patch grid (image S_h x S_w = 16hp x 16wp), with iy / ix PyTorch's `nearest` index
+ * src = min((int)floorf(dst * ((float)in / (float)out)), in - 1):
+ *   low[p] = coarse[iy(py)][ix(px)]                                              p = py*wp + px, P = hp*wp
+ *   ends int64 [B, P]                 inclusive running sum of name_len[low[p]] per sample
+ *   ids  int64 [B, P*Lmax]            the bags' tokens back to back, `pad` behind ends[b, P-1] (static width: no host sync;
+ *                                     ifseg_embed_bag_mean never reads past `ends`)
+ *   prev_output_tokens int64 [B, P+1] bos, seg_id_offset + low[p]
+ *   text2seg_target int64 [B, S_h*S_w + 1]   seg_id_offset + coarse[iy(y)][ix(x)], eos
+ * 1 <= max_side <= 128, 1 <= Lmax <= 16, 1 <= nseg <= 65535 (IFSEG_ERR_BAD_ARG); 1 <= P <= 4096, wp <= 2048
+ * (IFSEG_ERR_BAD_SHAPE).  All outputs contiguous; 8-byte alignment suffices. */
+int ifseg_imfree_draw(unsigned long long seed, long long first_ordinal, const long long* first_ordinal_dev, int B, int l, int r,
+                      int nseg, int* shapes, int* coarse, void* stream);
+int ifseg_imfree_expand(const int* shapes, const int* coarse, int max_side, const long long* name_ids, const int* name_len,
+                        int nseg, int Lmax, int B, int hp, int wp, long long seg_id_offset, long long bos, long long eos,
+                        long long pad, long long* ids, long long* ends, long long* prev_output_tokens,
+                        long long* text2seg_target, void* stream);
 
 /* -------------------------------------------------------------- optimizer */
 /* ---- eval-time post-processing of the criterion (BASELINE config 5) ----------------------
