@@ -21,7 +21,7 @@ GEMM_RELU, GEMM_OUT_F32, GEMM_ACCUMULATE = 1, 2, 4
 c_void_p, c_int, c_float, c_ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_longlong
 
 
-ABI_VERSION = 20         # == IFSEG_ABI_VERSION of include/ifseg_hip.h (checked at load time and by __graft_entry__.build)
+ABI_VERSION = 21         # == IFSEG_ABI_VERSION of include/ifseg_hip.h (checked at load time and by __graft_entry__.build)
 
 
 def lib():
@@ -1018,6 +1018,37 @@ def seg_eval(scores, hp, wp, target, h, w, seg_id_offset):
     tot = torch.empty(2, dtype=torch.float32, device=dev)
     reduce_parts(part, tot, 1, nblk, 2)
     return tot[0] / tot[1], hist
+
+
+SEG_PREDICT_MAX_CLASSES = 512
+
+
+def seg_predict(scores, hp, wp, h, w, conf=False, probs=False, staging_bytes=None, label_dtype=None):
+    """scores fp32 [B, hp*wp, n] (class fastest: what rows_to_f32 / neighbour_smoothing return) -> (labels [B, h, w], uint8 for
+    n <= 256 else int16; conf fp32 [B, h, w] or None; probs fp32 [B, n, h, w] or None): bilinear resize to h x w
+    (align_corners=False), argmax, the winning value and every value in one pass (csrc/predict.hip).
+    staging_bytes: size of the kernel's LDS staging buffer for this call (0: every tile reads global memory), None: the default;
+    label_dtype: None, or torch.uint8 (n <= 256 only) / torch.int16 to choose the width"""
+    assert scores.dtype == torch.float32 and scores.dim() == 3 and scores.is_contiguous(), (scores.dtype, tuple(scores.shape), scores.stride())
+    B, P, n = scores.shape
+    assert P == hp * wp and B >= 1 and hp >= 1 and wp >= 1 and h >= 1 and w >= 1, (tuple(scores.shape), hp, wp, h, w)
+    assert 1 <= n <= SEG_PREDICT_MAX_CLASSES, n
+    assert B * h * w < 2 ** 31, (B, h, w)
+    dev = scores.device
+    if label_dtype is None:
+        label_dtype = torch.uint8 if n <= 256 else torch.int16
+    assert label_dtype in (torch.uint8, torch.int16) and (n <= 256 or label_dtype == torch.int16), (label_dtype, n)
+    labels = torch.empty(B, h, w, dtype=label_dtype, device=dev)
+    cf = torch.empty(B, h, w, dtype=torch.float32, device=dev) if conf else None
+    pr = torch.empty(B, n, h, w, dtype=torch.float32, device=dev) if probs else None
+    prev = lib().ifseg_seg_predict_staging(c_int(staging_bytes)) if staging_bytes is not None else None
+    try:
+        _check(lib().ifseg_seg_predict(_ptr(scores), c_int(B), c_int(hp), c_int(wp), c_int(n), c_int(h), c_int(w), _ptr(labels),
+                                       c_int(labels.element_size()), _ptr(cf), _ptr(pr), _stream()), "seg_predict")
+    finally:
+        if prev is not None:
+            lib().ifseg_seg_predict_staging(c_int(prev))
+    return labels, cf, pr
 
 
 def dropout(x, resid, out, p, seed, drop_path_scale=None, rows_per_batch=None):

@@ -18,6 +18,7 @@ The second half of the file puts the training-path kernels there as well (see th
 `attention_bias` (the bias is an ordinary tensor with a gradient), `bias_attention_bi` (bias_attention on the batch-inner
 kernels, with key counts and attention dropout) and `seg_loss` (csrc/loss.hip), with `*_bwd` ops of their own;
 `ifseg_amd.modules.MultiheadAttention` composes `linear` and `attention_bias` under the reference module's parameter names.
+The last op, `seg_predict` (csrc/predict.hip: label maps at image resolution), is inference only and has no backward.
 """
 from typing import Optional, Tuple
 
@@ -658,3 +659,47 @@ def _sl_backward(ctx, gloss, gstats, gdl, gbad):
 
 
 seg_loss.register_autograd(_sl_backward, setup_context=_sl_setup)
+
+
+# ----------------------------------------------------------------------------------------------- seg_predict
+def _seg_predict_check(scores, hp, wp, h, w):
+    op = "ifseg::seg_predict"
+    if scores.dtype != torch.float32:
+        raise ValueError("%s: scores must be fp32 (hip.rows_to_f32 / hip.neighbour_smoothing give it), got dtype %s" % (op, scores.dtype))
+    if scores.dim() != 3:
+        raise ValueError("%s: scores must be [B, hp*wp, n], got %s" % (op, tuple(scores.shape)))
+    B, P, n = scores.shape
+    if B == 0:
+        raise ValueError("%s: empty batch" % op)
+    if hp <= 0 or wp <= 0 or P != hp * wp:
+        raise ValueError("%s: scores.shape[1] = %d, expected hp * wp = %d" % (op, P, hp * wp))
+    if n < 1 or n > SEG_LOSS_MAX_CLASSES:
+        raise ValueError("%s: n = %d classes, the kernel takes 1 .. FUSED_MAX_CLASSES = %d" % (op, n, SEG_LOSS_MAX_CLASSES))
+    if h < 1 or w < 1 or B * h * w >= 2 ** 31:
+        raise ValueError("%s: the label map [%d, %d, %d] must have 1 <= h, w and B * h * w < 2**31" % (op, B, h, w))
+    return B, n, (torch.uint8 if n <= 256 else torch.int16)
+
+
+@custom_op("ifseg::seg_predict", mutates_args=(), device_types="cuda")
+def seg_predict(scores: torch.Tensor, hp: int, wp: int, h: int, w: int, want_conf: bool, want_probs: bool
+                ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """label map at h x w from per-patch class scores fp32 [B, hp*wp, n] (csrc/predict.hip): bilinear resize
+    (align_corners=False, any ratio), argmax with torch.argmax's tie rule, in one pass.
+    -> (labels [B, h, w] uint8 (n <= 256) or int16, conf fp32 [B, h, w] = the winning value, probs fp32 [B, n, h, w] = every
+    interpolated value); an output that was not asked for is an empty tensor.  Not differentiable."""
+    _seg_predict_check(scores, hp, wp, h, w)
+    prev = _stream_scope(scores)
+    try:
+        labels, conf, probs = hip.seg_predict(scores.contiguous(), hp, wp, h, w, conf=want_conf, probs=want_probs)
+        e = lambda t: torch.empty(0, dtype=torch.float32, device=scores.device) if t is None else t
+        return labels, e(conf), e(probs)
+    finally:
+        hip.set_stream(prev)
+
+
+@seg_predict.register_fake
+def _(scores, hp, wp, h, w, want_conf, want_probs):
+    B, n, ldt = _seg_predict_check(scores, hp, wp, h, w)
+    f32 = torch.float32
+    return (scores.new_empty(B, h, w, dtype=ldt), scores.new_empty((B, h, w) if want_conf else (0,), dtype=f32),
+            scores.new_empty((B, n, h, w) if want_probs else (0,), dtype=f32))

@@ -1,0 +1,190 @@
+"""Inference entry point: images in, label maps at image resolution out.
+
+The reference's user-facing demo is model forward -> softmax per patch -> optional top-k neighbour smoothing on the trunk
+features -> bilinear resize of the class probabilities to the image shape -> optional dense CRF -> argmax.  Here the forward is
+the HIP engine, the smoothing `hip.neighbour_smoothing`, the CRF `crf.rgb_dense_crf`, and softmax / resize / argmax at image
+resolution one fused kernel (`hip.seg_predict`, csrc/predict.hip): the [B, n, h, w] probabilities are only written when the CRF
+or the caller asks for them.
+
+    seg = Segmenter(model, task)                      # or task.build_segmenter(model)
+    res = seg(images)                                 # float [B, 3, H, W] (normalised) or uint8 RGB [B, H, W, 3] / [H, W, 3]
+    res.labels                                        # uint8 (int16 above 256 classes) [B, H, W], on the device
+
+Nothing in the call synchronises with the host; `labels`, `conf` and `probs` stay on the device.  There is no CPU fallback:
+`upsample_argmax_reference` is the specification the tests compare against, not a second implementation of the path.
+"""
+from typing import NamedTuple, Optional
+
+import torch
+import torch.nn.functional as F
+
+from . import hip
+from .tasks.mm_tasks.segmentation import BOS, EOS, PROMPT_IDS
+
+MAX_CLASSES = hip.SEG_PREDICT_MAX_CLASSES
+
+
+class SegmentationResult(NamedTuple):
+    labels: torch.Tensor                       # [B, h, w] uint8 (n <= 256) or int16
+    conf: Optional[torch.Tensor]               # [B, h, w] fp32: the value of the winning class
+    probs: Optional[torch.Tensor]              # [B, n, h, w] fp32: every class
+
+
+def upsample_argmax_reference(scores, hp, wp, h, w, dtype=torch.float64):
+    """CPU specification of hip.seg_predict: scores [B, hp*wp, n] -> (labels int64 [B, h, w], conf [B, h, w], probs
+    [B, n, h, w]) with F.interpolate(bilinear, align_corners=False) evaluated in `dtype`, then argmax (first maximum).
+    Runs on any device."""
+    B, P, n = scores.shape
+    assert P == hp * wp, (tuple(scores.shape), hp, wp)
+    grid = scores.to(dtype).transpose(1, 2).reshape(B, n, hp, wp)
+    probs = F.interpolate(grid, size=(h, w), mode="bilinear", align_corners=False)
+    labels = probs.argmax(dim=1)
+    return labels, probs.gather(1, labels[:, None]).squeeze(1), probs
+
+
+def source_tokens(category_token_ids, prompt_ids=PROMPT_IDS, num_seg_tokens=None):
+    """bos + prompt + the category names back to back + eos, int64 [L] (segmentation_dataset.py:143-160: the prompt the
+    model was tuned with, then every class name)"""
+    names = [torch.as_tensor(x, dtype=torch.long).reshape(-1) for x in category_token_ids]
+    if num_seg_tokens is not None and len(names) != num_seg_tokens:
+        raise ValueError("Segmenter: %d category names for a model with num_seg_tokens = %d" % (len(names), num_seg_tokens))
+    return torch.cat([torch.tensor([BOS], dtype=torch.long), torch.as_tensor(list(prompt_ids), dtype=torch.long)] + names
+                     + [torch.tensor([EOS], dtype=torch.long)])
+
+
+def _check_classes(n, want_uint8=False):
+    if n < 1 or n > MAX_CLASSES:
+        raise ValueError("Segmenter: n = %d classes, hip.seg_predict takes 1 .. %d" % (n, MAX_CLASSES))
+    if want_uint8 and n > 256:
+        raise ValueError("Segmenter: uint8 labels hold at most 256 classes, the model has n = %d (int16 labels)" % n)
+
+
+class Segmenter:
+    def __init__(self, model, task=None, category_token_ids=None, prompt_ids=PROMPT_IDS, upsample="probs", smooth_iters=0,
+                 smooth_topk=3, temperature=1.0, crf_iters=0, full_context_alignment=False, label_dtype=None):
+        """model: a SegOFAModel on the device.  The class names come from `category_token_ids` (one id sequence per class),
+        else the task's `category_token_ids`, else the task's `category_list` through `task.encode_category`.
+        upsample: "probs" resizes the per-patch softmax (temperature), the reference demo's order; "logits" resizes the raw
+        scores, the criterion's eval order.  smooth_iters > 0: both feed hip.neighbour_smoothing's probabilities.
+        crf_iters > 0: mean-field iterations of crf.rgb_dense_crf on the resized values.
+        label_dtype: None (uint8 up to 256 classes, else int16) or torch.uint8 to insist on bytes."""
+        if upsample not in ("probs", "logits"):
+            raise ValueError("Segmenter: upsample must be 'probs' or 'logits', got %r" % (upsample,))
+        self.model, self.task = model, task
+        self.n = int(model.cfg.num_seg_tokens)
+        if label_dtype not in (None, torch.uint8, torch.int16):
+            raise ValueError("Segmenter: label_dtype must be None, torch.uint8 or torch.int16, got %r" % (label_dtype,))
+        _check_classes(self.n, want_uint8=label_dtype == torch.uint8)
+        names = category_token_ids
+        if names is None:
+            names = getattr(task, "category_token_ids", None)
+        if names is None:
+            cats = getattr(task, "category_list", "") or ""
+            cats = [x.strip() for x in cats.split(",")] if cats else []
+            if task is None or not cats:
+                raise ValueError("Segmenter: no class names -- pass category_token_ids, or a task with category_token_ids "
+                                 "or category_list (+ BPE)")
+            names = [task.encode_category(" %s" % x) for x in cats]
+        self.src = source_tokens(names, prompt_ids, self.n)
+        self.upsample, self.temperature = upsample, float(temperature)
+        self.smooth_iters, self.smooth_topk, self.crf_iters = int(smooth_iters), int(smooth_topk), int(crf_iters)
+        self.full_context_alignment = bool(full_context_alignment)
+        self.label_dtype = label_dtype
+        self._src_dev = None
+
+    # -- inputs --------------------------------------------------------------------------
+    @staticmethod
+    def prepare_images(images):
+        """-> (normalised float [B, 3, H, W], RGB in 0..255 as float [B, H, W, 3] or None when the input was already normalised)"""
+        if images.dtype == torch.uint8:
+            if images.dim() == 3:
+                images = images[None]
+            if images.dim() != 4 or images.shape[-1] != 3:
+                raise ValueError("Segmenter: uint8 images must be RGB [B, H, W, 3] or [H, W, 3], got %s" % (tuple(images.shape),))
+            rgb = images.float()
+            return ((rgb / 255.0 - 0.5) / 0.5).permute(0, 3, 1, 2).contiguous(), rgb
+        if not images.dtype.is_floating_point or images.dim() != 4 or images.shape[1] != 3:
+            raise ValueError("Segmenter: images must be normalised float [B, 3, H, W] or uint8 RGB [B, H, W, 3] / [H, W, 3], "
+                             "got %s %s" % (images.dtype, tuple(images.shape)))
+        return images, None
+
+    def net_input(self, patch_images):
+        B, dev = patch_images.shape[0], patch_images.device
+        if self._src_dev is None or self._src_dev.device != dev:
+            self._src_dev = self.src.to(dev)
+        L = self.src.numel()
+        return {"src_tokens": self._src_dev[None].expand(B, L).contiguous(),
+                "src_lengths": torch.full((B,), L, dtype=torch.long, device=dev),
+                "patch_images": patch_images,
+                "patch_masks": torch.ones(B, dtype=torch.bool, device=dev),
+                "prev_output_tokens": torch.full((B, 1), BOS, dtype=torch.long, device=dev)}
+
+    @staticmethod
+    def _sizes(out_hw, B, HW, crf, has_crf_images):
+        """-> (list of B (h, w) or None for one size, the one size)"""
+        if out_hw is None:
+            return None, tuple(HW)
+        if len(out_hw) == 2 and all(isinstance(v, int) for v in out_hw):
+            one = (int(out_hw[0]), int(out_hw[1]))
+            if crf and one != tuple(HW) and not has_crf_images:
+                raise ValueError("Segmenter: crf_images is required when out_hw %s differs from the input size %s (the CRF needs "
+                                 "the image at the output resolution)" % (one, tuple(HW)))
+            return None, one
+        sizes = [(int(a), int(b)) for a, b in out_hw]
+        if len(sizes) != B:
+            raise ValueError("Segmenter: out_hw lists %d sizes for a batch of %d" % (len(sizes), B))
+        if crf and not has_crf_images and any(s != tuple(HW) for s in sizes):
+            raise ValueError("Segmenter: crf_images is required when out_hw %s differs from the input size %s (the CRF needs "
+                             "the image at the output resolution)" % (sizes, tuple(HW)))
+        return sizes, None
+
+    # -- the call ------------------------------------------------------------------------
+    def patch_scores(self, patch_images):
+        """model forward -> (scores fp32 [B, hp*wp, n] in the chosen mode, hp, wp)"""
+        model = self.model
+        was_training = model.training
+        if was_training:
+            model.eval()
+        try:
+            with torch.no_grad():
+                _, extra = model(**self.net_input(patch_images), full_context_alignment=self.full_context_alignment)
+                pad = extra["logits_padded"]
+                hp, wp = extra["encoder_returns"]["image_embed_shape"][0]
+                if self.smooth_iters > 0:
+                    feat = extra["encoder_returns"]["image_embed_before_proj"][0]
+                    scores = hip.neighbour_smoothing(pad, self.n, feat, self.smooth_iters, self.smooth_topk, self.temperature)
+                else:
+                    scores = hip.rows_to_f32(pad, self.n, hp * wp, softmax=self.upsample == "probs", temperature=self.temperature)
+        finally:
+            if was_training:
+                model.train()
+        return scores, hp, wp
+
+    def _finish(self, scores, hp, wp, h, w, rgb, return_conf, return_probs):
+        crf = self.crf_iters > 0
+        labels, conf, probs = hip.seg_predict(scores, hp, wp, h, w, conf=return_conf and not crf, probs=return_probs or crf,
+                                              label_dtype=self.label_dtype)
+        if crf:
+            from .crf import rgb_dense_crf
+            q = torch.stack([rgb_dense_crf(rgb[b], probs[b], self.crf_iters) for b in range(probs.shape[0])])
+            labels = q.argmax(1).to(labels.dtype)
+            conf = q.amax(1) if return_conf else None
+            probs = q if return_probs else None
+        return SegmentationResult(labels, conf, probs)
+
+    def __call__(self, images, out_hw=None, crf_images=None, return_conf=False, return_probs=False):
+        patch_images, rgb = self.prepare_images(images)
+        B, _, H, W = patch_images.shape
+        crf = self.crf_iters > 0
+        sizes, one = self._sizes(out_hw, B, (H, W), crf, crf_images is not None)
+        if crf:
+            if crf_images is not None:
+                rgb = [torch.as_tensor(c).to(patch_images.device).float() for c in crf_images]
+            elif rgb is None:
+                rgb = ((patch_images.float() * 0.5 + 0.5) * 255.0).permute(0, 2, 3, 1).contiguous()
+        scores, hp, wp = self.patch_scores(patch_images)
+        with torch.no_grad():
+            if sizes is None:
+                return self._finish(scores, hp, wp, one[0], one[1], rgb, return_conf, return_probs)
+            return [self._finish(scores[b:b + 1], hp, wp, s[0], s[1], rgb[b:b + 1] if crf else None, return_conf, return_probs)
+                    for b, s in enumerate(sizes)]

@@ -194,6 +194,11 @@ class SegmentationTask(TaskBase):
         return SequenceGenerator(models, self.target_dictionary, beam_size=g("beam", 5), max_len=g("max_len", None),
                                  min_len=g("min_len", 1), temperature=g("temperature", 1.0))
 
+    def build_segmenter(self, model, **kw):
+        """images -> label maps at image resolution on this task's categories (ifseg_amd/predict.py)"""
+        from ...predict import Segmenter
+        return Segmenter(model, task=self, **kw)
+
     def inference_step(self, generator, models, sample, prefix_tokens=None, constraints=None):
         """fairseq_task.py `inference_step` -> [B, max_len] seg-class indices of the best beam (segmentation.py:266-268)"""
         with torch.no_grad():

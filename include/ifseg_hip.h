@@ -19,7 +19,7 @@
 extern "C" {
 #endif
 
-#define IFSEG_ABI_VERSION 20
+#define IFSEG_ABI_VERSION 21
 #define IFSEG_ERR_BAD_SHAPE (-2)
 #define IFSEG_ERR_BAD_ARG (-3)
 
@@ -538,6 +538,26 @@ int ifseg_softmax_rows(const void* logits /* bf16 */, long long batch_stride, in
 int ifseg_gather_mean(const float* in, const int* idx, float* out, int B, int P, int n, int k, void* stream);
 int ifseg_seg_eval(const float* scores, int hp, int wp, int n, const long long* target, int h, int w,
                    long long seg_id_offset, unsigned long long* hist, float* loss_part, int nblocks, void* stream);
+
+/* ---- label maps at image resolution (ifseg_amd/predict.py; the reference's demo: softmax, resize to the image, argmax) ----
+ * ifseg_seg_predict resizes the class scores [B, hp*wp, n] (fp32, class fastest: the layout of ifseg_softmax_rows /
+ * ifseg_gather_mean) bilinearly to [B, h, w] with ifseg_seg_eval's value rule (align_corners=False, any ratio, downscaling
+ * included):
+ *   sy = max((y + 0.5f) * ((float)hp / (float)h) - 0.5f, 0),  y0 = min((int)sy, hp-1),  y1 = min(y0+1, hp-1),  ly = sy - y0
+ *   (the same in x),  v_c = w00 p00[c] + w01 p01[c] + w10 p10[c] + w11 p11[c]
+ * and writes, in one pass and without a [n, h, w] intermediate,
+ *   labels [B, h, w]     the smallest c with maximal v_c (torch.argmax's tie rule); label_bytes 1 -> uint8 (n <= 256), 2 -> int16
+ *   conf   [B, h, w]     fp32 v_label, or NULL
+ *   probs  [B, n, h, w]  fp32, every v_c, class-major (ifseg_crf_update's input layout), or NULL
+ * 1 <= n <= 512, label_bytes 1 or 2 (1 only for n <= 256), labels / conf 16-byte aligned: else IFSEG_ERR_BAD_ARG.
+ * B, hp, wp, h, w >= 1, B*h*w < 2^31, hp*wp < 2^22: else IFSEG_ERR_BAD_SHAPE.
+ * A workgroup owns 16 x 64 pixels and stages the patch rows they touch in LDS; a tile whose footprint exceeds the staging
+ * buffer reads global memory instead (same values).  ifseg_seg_predict_staging sets the size of that buffer in bytes for
+ * the launches that follow (0: every tile reads global memory; < 0 or above the built-in limit: the limit) and returns
+ * the previous setting -- a test and measurement switch, process-wide. */
+int ifseg_seg_predict(const float* scores, int B, int hp, int wp, int n, int h, int w, void* labels, int label_bytes,
+                      float* conf, float* probs, void* stream);
+int ifseg_seg_predict_staging(int max_bytes);
 
 /* sum of squares of a bf16 gradient arena -> out_sumsq[0] (device). */
 int ifseg_grad_sumsq_bf16(const void* g, long long n, float* workspace, float* out_sumsq, void* stream);
