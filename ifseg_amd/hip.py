@@ -1051,6 +1051,50 @@ def seg_predict(scores, hp, wp, h, w, conf=False, probs=False, staging_bytes=Non
     return labels, cf, pr
 
 
+_image_luts = {}          # (mean, std, device) -> fp32 [3, 256] on the device; at most 16 entries
+
+
+def image_load(images_u8, oh, ow, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), reverse_channels=False, dtype=torch.float32,
+               staging_bytes=None, out=None):
+    """uint8 [B, H0, W0, 3] (HWC, contiguous, on the device) -> patch_images [B, 3, oh, ow] in `dtype` (fp32 or bf16): the
+    reference's evaluation transform in one kernel (csrc/imgload.hip) -- bilinear resize (align_corners=False, no antialiasing,
+    integer source coordinates), rounding to a grey level, optional channel reversal (off by default: the reference's two
+    reversals, segmentation_dataset.py:218 and :256, cancel, so the network sees RGB) and
+    (x / 255 - mean) / std from a [3, 256] table built on the host.  `imageio.image_load_reference` is the specification.
+    staging_bytes: size of the kernel's LDS staging buffer for this call (0: every tile reads global memory), None: the default;
+    out: a contiguous [B, 3, oh, ow] tensor of `dtype` to write into."""
+    from .imageio import normalisation_table
+    assert images_u8.dtype == torch.uint8 and images_u8.dim() == 4 and images_u8.shape[-1] == 3 and images_u8.is_contiguous(), \
+        (images_u8.dtype, tuple(images_u8.shape), images_u8.stride())
+    B, H0, W0, _ = images_u8.shape
+    oh, ow = int(oh), int(ow)
+    assert B >= 1 and H0 >= 1 and W0 >= 1 and oh >= 1 and ow >= 1, (tuple(images_u8.shape), oh, ow)
+    assert dtype in (torch.float32, torch.bfloat16), dtype
+    assert images_u8.is_cuda, "device tensor required"
+    dev = images_u8.device
+    key = (tuple(float(x) for x in mean), tuple(float(x) for x in std), dev)
+    lut = _image_luts.get(key)
+    if lut is None:
+        # the first call per (mean, std, device) copies the table from the host: it blocks the host and cannot be captured
+        if len(_image_luts) >= 16:
+            _image_luts.clear()
+        lut = _image_luts[key] = normalisation_table(mean, std).to(dev)
+    if out is None:
+        out = torch.empty(B, 3, oh, ow, dtype=dtype, device=dev)
+    else:
+        assert out.dtype == dtype and tuple(out.shape) == (B, 3, oh, ow) and out.is_contiguous() and out.device == dev, \
+            (out.dtype, tuple(out.shape), out.stride(), out.device)
+    prev = lib().ifseg_image_load_staging(c_int(staging_bytes)) if staging_bytes is not None else None
+    try:
+        _check(lib().ifseg_image_load(_ptr(images_u8), c_int(B), c_int(H0), c_int(W0), c_int(oh), c_int(ow), _ptr(lut),
+                                      c_int(1 if reverse_channels else 0), _ptr(out), c_int(out.element_size()), _stream()),
+               "image_load")
+    finally:
+        if prev is not None:
+            lib().ifseg_image_load_staging(c_int(prev))
+    return out
+
+
 def dropout(x, resid, out, p, seed, drop_path_scale=None, rows_per_batch=None):
     """x / resid / out: [rows, C] or [B, rpb, C] bf16 views (last dim contiguous)"""
     C = x.shape[-1]

@@ -1,0 +1,102 @@
+"""The reference's evaluation transform for raw images: sizes, the CPU specification of `hip.image_load`, and the grouping
+of `Segmenter.segment_raw`.  Needs no GPU to import.
+
+The reference evaluates an image as it comes off disk (segmentation_dataset.py:169-172,218,256):
+`MultiScaleFlipAug(img_scale=(4 P, P), flip=False, [Resize(keep_ratio=True), ...])` resizes it so that the short side is at
+most P and the long side at most 4 P (`eval_size`), and the result is normalised with mean / std 0.5, or the ImageNet
+values under `imagenet_default_mean_and_std` (:148-156).  The dataset reverses the channels TWICE -- :218 `to BGR` in front of
+the mmseg transforms, which expect BGR, and :256 (:243 in training) `to RGB` behind them -- so the two cancel: the network
+sees RGB, as PIL delivers it, and `reverse_channels` is off by default (the switch is for a model trained on BGR).  `image_load_reference` is that transform as a specification in plain torch
+indexing; `hip.image_load` (csrc/imgload.hip) is the implementation.
+"""
+import torch
+
+IMAGENET_DEFAULT_MEAN = (0.485, 0.456, 0.406)
+IMAGENET_DEFAULT_STD = (0.229, 0.224, 0.225)
+HALF = (0.5, 0.5, 0.5)
+
+
+def eval_size(h, w, patch_image_size):
+    """-> (oh, ow): mmcv's `rescale_size((w, h), (4 P, P))` in Python floats"""
+    P = int(patch_image_size)
+    if h < 1 or w < 1 or P < 1:
+        raise ValueError("eval_size: h, w and patch_image_size must be >= 1, got %r %r %r" % (h, w, patch_image_size))
+    s = min(4 * P / max(h, w), P / min(h, w))
+    return int(h * s + 0.5), int(w * s + 0.5)
+
+
+def _triple(v, what):
+    v = tuple(float(x) for x in v)
+    if len(v) != 3:
+        raise ValueError("image_load: %s must have three entries, got %r" % (what, v))
+    return v
+
+
+def normalisation_table(mean=HALF, std=HALF):
+    """fp32 [3, 256] on the host: (k / 255 - mean[c]) / std[c] in torch fp32 -- every value `image_load` can return"""
+    mean, std = _triple(mean, "mean"), _triple(std, "std")
+    k = torch.arange(256, dtype=torch.float32) / 255
+    return torch.stack([(k - mean[c]) / std[c] for c in range(3)])
+
+
+def source_coords(out, inn, dtype=torch.float64, device=None):
+    """one axis of the resize, `out` samples over `inn`: (i0 int64 [out], i1 int64 [out], lambda `dtype` [out]) by the
+    integer rule -- num = max((2d+1) in - out, 0), i0 = min(num // (2 out), in-1), i1 = min(i0+1, in-1),
+    lambda = float(num - i0 2 out) / float(2 out), 0 where i0 == i1"""
+    d = torch.arange(out, dtype=torch.int64, device=device)
+    num = ((2 * d + 1) * inn - out).clamp_min(0)
+    i0 = (num // (2 * out)).clamp_max(inn - 1)
+    i1 = (i0 + 1).clamp_max(inn - 1)
+    lam = (num - i0 * (2 * out)).to(dtype) / torch.tensor(2 * out, dtype=torch.int64, device=device).to(dtype)
+    return i0, i1, torch.where(i0 == i1, torch.zeros_like(lam), lam)
+
+
+def image_load_reference(images_u8, oh, ow, mean=HALF, std=HALF, reverse_channels=False, dtype=torch.float64,
+                         out_dtype=torch.float32):
+    """CPU specification of hip.image_load: uint8 [B, H0, W0, 3] -> (normalised `out_dtype` [B, 3, oh, ow], q uint8
+    [B, 3, oh, ow], v `dtype` [B, 3, oh, ow]).  Bilinear resize with align_corners=False and no antialiasing
+    (`F.interpolate` / `cv2.INTER_LINEAR`), the source coordinate in integers (`source_coords`), weights and the
+    four-term sum v = w00 a + w01 b + w10 c + w11 d in `dtype`; q = clamp(floor(v + 0.5), 0, 255) as the reference's
+    uint8 resize; the output is `normalisation_table(mean, std)[c][q]`, channel c reading source channel 2 - c when
+    `reverse_channels`.  Runs on any device.
+
+    NOT pinned: `cv2` (what mmcv's Resize calls) evaluates the same filter with 11-bit fixed-point weights, and `cv2` is
+    not available where this project is tested.  The share of pixels at which that fixed-point rounding lands on the
+    neighbouring grey level has not been measured."""
+    if images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[-1] != 3:
+        raise ValueError("image_load: images must be uint8 [B, H0, W0, 3], got %s %s" % (images_u8.dtype, tuple(images_u8.shape)))
+    B, H0, W0, _ = images_u8.shape
+    if B < 1 or H0 < 1 or W0 < 1 or oh < 1 or ow < 1:
+        raise ValueError("image_load: empty source %s or destination %s" % (tuple(images_u8.shape), (oh, ow)))
+    dev = images_u8.device
+    src = images_u8.permute(0, 3, 1, 2)
+    if reverse_channels:
+        src = src.flip(1)
+    src = src.to(dtype)
+    y0, y1, ly = source_coords(oh, H0, dtype, dev)
+    x0, x1, lx = source_coords(ow, W0, dtype, dev)
+    ly, lx = ly[:, None], lx[None, :]
+    top, bot = src[:, :, y0], src[:, :, y1]
+    v = ((1 - ly) * (1 - lx)) * top[..., x0] + ((1 - ly) * lx) * top[..., x1] + (ly * (1 - lx)) * bot[..., x0] \
+        + (ly * lx) * bot[..., x1]
+    q = (v + 0.5).floor().clamp(0, 255).to(torch.uint8)
+    lut = normalisation_table(mean, std).to(dev)
+    norm = torch.stack([lut[c][q[:, c].long()] for c in range(3)], 1).to(out_dtype)
+    return norm, q, v
+
+
+def plan_groups(shapes, patch_image_size, max_batch=8):
+    """The launches of Segmenter.segment_raw for images of the given (H, W) shapes, as a pure function:
+    -> (loads, forwards).  loads: [((H, W), (oh, ow), [indices])], one `image_load` launch per distinct source shape, in order
+    of first appearance; forwards: [((oh, ow), [indices])], one model forward per entry: images of equal network size in
+    input order, at most `max_batch` of them."""
+    if max_batch < 1:
+        raise ValueError("segment_raw: max_batch must be >= 1, got %r" % (max_batch,))
+    loads, by_size = {}, {}
+    for i, (h, w) in enumerate(shapes):
+        h, w = int(h), int(w)
+        size = eval_size(h, w, patch_image_size)
+        loads.setdefault((h, w), (size, []))[1].append(i)
+        by_size.setdefault(size, []).append(i)
+    forwards = [(size, idx[k:k + max_batch]) for size, idx in by_size.items() for k in range(0, len(idx), max_batch)]
+    return [(hw, size, idx) for hw, (size, idx) in loads.items()], forwards

@@ -18,9 +18,10 @@ The second half of the file puts the training-path kernels there as well (see th
 `attention_bias` (the bias is an ordinary tensor with a gradient), `bias_attention_bi` (bias_attention on the batch-inner
 kernels, with key counts and attention dropout) and `seg_loss` (csrc/loss.hip), with `*_bwd` ops of their own;
 `ifseg_amd.modules.MultiheadAttention` composes `linear` and `attention_bias` under the reference module's parameter names.
-The last op, `seg_predict` (csrc/predict.hip: label maps at image resolution), is inference only and has no backward.
+`seg_predict` (csrc/predict.hip: label maps at image resolution) and `image_load` (csrc/imgload.hip: raw uint8 images to
+normalised patch_images, the reference's evaluation transform) are inference only and have no backward.
 """
-from typing import Optional, Tuple
+from typing import Optional, Sequence, Tuple
 
 import torch
 from torch.library import custom_op
@@ -703,3 +704,46 @@ def _(scores, hp, wp, h, w, want_conf, want_probs):
     f32 = torch.float32
     return (scores.new_empty(B, h, w, dtype=ldt), scores.new_empty((B, h, w) if want_conf else (0,), dtype=f32),
             scores.new_empty((B, n, h, w) if want_probs else (0,), dtype=f32))
+
+
+# ----------------------------------------------------------------------------------------------- image_load
+def _image_load_check(images, oh, ow, mean, std, dtype):
+    op = "ifseg::image_load"
+    if images.dtype != torch.uint8:
+        raise ValueError("%s: images must be uint8 (raw grey levels; normalised floats go to the model as they are), got dtype %s"
+                         % (op, images.dtype))
+    if images.dim() != 4 or images.shape[-1] != 3:
+        raise ValueError("%s: images must be [B, H0, W0, 3] (HWC), got %s" % (op, tuple(images.shape)))
+    B, H0, W0, _ = images.shape
+    if B == 0 or H0 == 0 or W0 == 0:
+        raise ValueError("%s: empty images %s" % (op, tuple(images.shape)))
+    if oh < 1 or ow < 1:
+        raise ValueError("%s: the destination size must be >= 1 x 1, got %d x %d" % (op, oh, ow))
+    if B * H0 * W0 * 3 >= 2 ** 31 or B * 3 * oh * ow >= 2 ** 31 or 2 * H0 * oh >= 2 ** 31 or 2 * W0 * ow >= 2 ** 31:
+        raise ValueError("%s: B * H0 * W0 * 3, B * 3 * oh * ow, 2 * H0 * oh and 2 * W0 * ow must stay below 2**31, got %s -> %d x %d"
+                         % (op, tuple(images.shape), oh, ow))
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("%s: mean and std must have three entries, got %d and %d" % (op, len(mean), len(std)))
+    if dtype not in (torch.float32, BF):
+        raise ValueError("%s: the output dtype must be torch.float32 or torch.bfloat16, got %s" % (op, dtype))
+    return B
+
+
+@custom_op("ifseg::image_load", mutates_args=(), device_types="cuda")
+def image_load(images: torch.Tensor, oh: int, ow: int, mean: Sequence[float], std: Sequence[float], reverse_channels: bool,
+               dtype: torch.dtype) -> torch.Tensor:
+    """the reference's evaluation transform (csrc/imgload.hip): uint8 [B, H0, W0, 3] -> patch_images [B, 3, oh, ow] in `dtype`
+    (fp32 / bf16) by bilinear resize (align_corners=False), rounding to a grey level, optional channel reversal and
+    (x / 255 - mean) / std.  The input is integer: not differentiable."""
+    _image_load_check(images, oh, ow, mean, std, dtype)
+    prev = _stream_scope(images)
+    try:
+        return hip.image_load(images.contiguous(), oh, ow, mean, std, reverse_channels, dtype)
+    finally:
+        hip.set_stream(prev)
+
+
+@image_load.register_fake
+def _(images, oh, ow, mean, std, reverse_channels, dtype):
+    B = _image_load_check(images, oh, ow, mean, std, dtype)
+    return images.new_empty((B, 3, oh, ow), dtype=dtype)

@@ -9,6 +9,8 @@ or the caller asks for them.
     seg = Segmenter(model, task)                      # or task.build_segmenter(model)
     res = seg(images)                                 # float [B, 3, H, W] (normalised) or uint8 RGB [B, H, W, 3] / [H, W, 3]
     res.labels                                        # uint8 (int16 above 256 classes) [B, H, W], on the device
+    out = seg.segment_raw(photos)                     # uint8 RGB [H, W, 3] images of ANY size, one or a list: the reference's
+    out[i].labels                                     # evaluation transform on the device (hip.image_load), labels [H_i, W_i]
 
 Nothing in the call synchronises with the host; `labels`, `conf` and `probs` stay on the device.  There is no CPU fallback:
 `upsample_argmax_reference` is the specification the tests compare against, not a second implementation of the path.
@@ -19,6 +21,7 @@ import torch
 import torch.nn.functional as F
 
 from . import hip
+from .imageio import HALF, eval_size, plan_groups
 from .tasks.mm_tasks.segmentation import BOS, EOS, PROMPT_IDS
 
 MAX_CLASSES = hip.SEG_PREDICT_MAX_CLASSES
@@ -188,3 +191,51 @@ class Segmenter:
                 return self._finish(scores, hp, wp, one[0], one[1], rgb, return_conf, return_probs)
             return [self._finish(scores[b:b + 1], hp, wp, s[0], s[1], rgb[b:b + 1] if crf else None, return_conf, return_probs)
                     for b, s in enumerate(sizes)]
+
+    # -- raw images of any size ----------------------------------------------------------
+    def segment_raw(self, images, max_batch=8, mean=None, std=None, reverse_channels=False, return_conf=False,
+                    return_probs=False):
+        """Raw images in, as they come off disk: one uint8 RGB [H, W, 3] tensor or a list of them, of differing shapes, on the
+        host or the device -> a list of SegmentationResult in input order, image i with labels [H_i, W_i] (conf [H_i, W_i],
+        probs [n, H_i, W_i]) on the device.
+
+        Every image goes through the reference's evaluation transform (segmentation_dataset.py:169-172,218,256) in one kernel,
+        `hip.image_load`: resized with its aspect kept so that the short side is at most P = model.cfg.patch_image_size and
+        the long side at most 4 P (`imageio.eval_size`), the channel order KEPT (the reference reverses it twice, :218 `to BGR`
+        for the mmseg transforms and :256 `to RGB` behind them, so the network was tuned on RGB, the order `__call__` feeds
+        too; `reverse_channels=True` is for a model trained on BGR), normalised with `mean` / `std` -- 0.5 by
+        default; `imageio.IMAGENET_DEFAULT_MEAN` / `IMAGENET_DEFAULT_STD` is the reference's other choice
+        (`imagenet_default_mean_and_std`, :148-156).  The network runs at that variable aspect and the scores are resized to
+        the image's own shape, as the reference scores at `ori_shape`.
+
+        Images of equal source shape share one `image_load` launch, images of equal network size one forward of at most
+        `max_batch` (`imageio.plan_groups`).  With the CRF on, the ORIGINAL image is the CRF image, in RGB, not reversed.
+        With device images nothing synchronises with the host, after the first call per (mean, std), which copies the
+        normalisation table to the device."""
+        single = torch.is_tensor(images)
+        imgs = [images] if single else list(images)
+        if not imgs:
+            return []
+        for im in imgs:
+            if not torch.is_tensor(im) or im.dtype != torch.uint8 or im.dim() != 3 or im.shape[-1] != 3 or im.numel() == 0:
+                raise ValueError("Segmenter.segment_raw: every image must be a uint8 RGB [H, W, 3] tensor, got %s"
+                                 % ((im.dtype, tuple(im.shape)) if torch.is_tensor(im) else type(im),))
+        mean, std = HALF if mean is None else mean, HALF if std is None else std
+        dev = next(self.model.parameters()).device
+        imgs = [im.to(dev, non_blocking=True) for im in imgs]
+        shapes = [(int(im.shape[0]), int(im.shape[1])) for im in imgs]
+        loads, forwards = plan_groups(shapes, self.model.cfg.patch_image_size, max_batch)
+        crf = self.crf_iters > 0
+        x, out = [None] * len(imgs), [None] * len(imgs)
+        with torch.no_grad():
+            for _, (oh, ow), idx in loads:
+                t = hip.image_load(torch.stack([imgs[i] for i in idx]), oh, ow, mean, std, reverse_channels)
+                for k, i in enumerate(idx):
+                    x[i] = t[k]
+            for _, idx in forwards:
+                scores, hp, wp = self.patch_scores(torch.stack([x[i] for i in idx]))
+                for k, i in enumerate(idx):
+                    r = self._finish(scores[k:k + 1], hp, wp, shapes[i][0], shapes[i][1], imgs[i][None].float() if crf else None,
+                                     return_conf, return_probs)
+                    out[i] = SegmentationResult(*(None if t is None else t[0] for t in r))
+        return out

@@ -195,7 +195,8 @@ class SegmentationTask(TaskBase):
                                  min_len=g("min_len", 1), temperature=g("temperature", 1.0))
 
     def build_segmenter(self, model, **kw):
-        """images -> label maps at image resolution on this task's categories (ifseg_amd/predict.py)"""
+        """images -> label maps at image resolution on this task's categories (ifseg_amd/predict.py); raw uint8 images of
+        any size go through `Segmenter.segment_raw`, the evaluation transform of the data pipeline on the device"""
         from ...predict import Segmenter
         return Segmenter(model, task=self, **kw)
 

@@ -559,6 +559,31 @@ int ifseg_seg_predict(const float* scores, int B, int hp, int wp, int n, int h, 
                       float* conf, float* probs, void* stream);
 int ifseg_seg_predict_staging(int max_bytes);
 
+/* ---- raw images in (ifseg_amd/predict.py Segmenter.segment_raw; the reference's evaluation transform: Resize(keep_ratio),
+ * Normalize of :148-156; the dataset's two channel reversals, :218 and :256, cancel, so reverse_channels is 0 for a
+ * checkpoint tuned by the reference) ----
+ * ifseg_image_load turns uint8 images [B, H0, W0, 3] (HWC, contiguous, any byte alignment) into patch_images
+ * [B, 3, oh, ow] (NCHW; out_bytes 4 -> fp32, 2 -> bf16 round-to-nearest-even).  Per output element:
+ *   source coordinate in integers, per axis (d of `out` samples over `in`):
+ *     num = max((2d+1) in - out, 0),  i0 = min(num / (2 out), in-1),  i1 = min(i0+1, in-1),
+ *     l = float(num - i0 2 out) / float(2 out),  0 when i0 == i1          (align_corners=False, no antialiasing)
+ *   v = w00 a + w01 b + w10 c + w11 d in fp32 (w00 = (1-ly)(1-lx), ...),  q = clamp(floor(v + 0.5), 0, 255),
+ *   out = lut[c_out][q], where channel c_out reads source channel 2 - c_out when reverse_channels != 0, else c_out.
+ * lut: fp32 [3][256] on the device, built by the caller ((k/255 - mean[c]) / std[c]): the normalised value is a table entry,
+ * whatever the device's division does.
+ * The staging loads are aligned dwords: up to 3 bytes in front of `images` and behind its last byte may be READ (never past
+ * a page boundary, so a view at the start or end of an allocation is safe); nothing outside `out` is written.
+ * NULL images / lut / out, out_bytes other than 2 or 4, out not 16-byte aligned: IFSEG_ERR_BAD_ARG.
+ * B, H0, W0, oh, ow >= 1; B*H0*W0*3, B*3*oh*ow, 2*H0*oh and 2*W0*ow < 2^31: else IFSEG_ERR_BAD_SHAPE.
+ * A workgroup owns 16 x 64 output pixels and stages the source bytes they touch in LDS; a tile whose footprint exceeds the
+ * staging buffer reads global memory instead (same values), and so does every tile when the bound of the largest footprint
+ * exceeds it (no buffer is requested then).  ifseg_image_load_staging sets the size of that buffer in
+ * bytes for the launches that follow (0: every tile reads global memory; < 0 or above the built-in limit: the limit) and
+ * returns the previous setting -- a test and measurement switch, process-wide. */
+int ifseg_image_load(const void* images, int B, int H0, int W0, int oh, int ow, const float* lut, int reverse_channels,
+                     void* out, int out_bytes, void* stream);
+int ifseg_image_load_staging(int max_bytes);
+
 /* sum of squares of a bf16 gradient arena -> out_sumsq[0] (device). */
 int ifseg_grad_sumsq_bf16(const void* g, long long n, float* workspace, float* out_sumsq, void* stream);
 /* Fused grad scaling + clip-by-global-norm + Adam with decoupled weight decay over a
