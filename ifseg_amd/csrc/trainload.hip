@@ -1,0 +1,423 @@
+// The reference's TRAINING transform on the device (ifseg_amd/augment.py is the specification, bit for bit): raw uint8 images
+// [H0, W0, 3] and raw uint8 label maps [H0, W0] of any size -> patch_images [B, 3, P, P] (fp32 or bf16) and target int64
+// [B, P*P + 1] in the collater's layout.  mmseg's Resize(ratio_range) / RandomCrop(cat_max_ratio) / RandomFlip /
+// PhotoMetricDistortion of data/mm_data/segmentation_dataset.py:157-163, as a pure function of (seed, sample ordinal).
+//
+//   ifseg_train_draw   records int32 [B, 16] <- splitmix64(seed + (ordinal << 32) + slot)       one memset node + one launch
+//                      One workgroup per (sample, crop candidate k = 0..9): the class histogram of the candidate's P x P window
+//                      of the nearest-resized label map in LDS (integer atomics, so arrival order cannot matter), its verdict
+//                      4 max < 3 P^2 into slot 15 of the record with ONE global integer atomicAdd that also counts the
+//                      arrivals; the workgroup that arrives tenth holds all ten verdicts in the value the atomic returned,
+//                      picks the first good candidate (else candidate 10) and writes the record.
+//   ifseg_train_load   one launch per batch whatever the source shapes, csrc/imgload.hip's shape: a 256-thread workgroup owns a
+//                      16 x 64 output tile, a thread a pixel with its three channels.  The source footprint of the tile is staged
+//                      in LDS with aligned dword loads where it fits, else read from global memory.  Per pixel: 12 byte taps ->
+//                      grey levels q -> the photometric chain in registers (integers, and convert() as ONE fp32 operation) ->
+//                      table -> three coalesced plane stores (bf16: pairs); one nearest label tap -> one int64 target store.
+//                      A record that does not hold a P x P window (only a caller's own records can) poisons its sample: NaN
+//                      images and target -1, nothing is read through it.
+// No scratch buffer, static launch shapes, nothing read back.
+#include <algorithm>
+#include "common.h"
+#include "../../include/ifseg_hip.h"
+
+namespace {
+
+constexpr int TL_ROWS = 16, TL_COLS = 64;
+constexpr int TL_LUT_BYTES = 3 * 256 * 4;
+constexpr int TL_STAGE_LIMIT = 65536 - TL_LUT_BYTES;
+constexpr int TL_CANDIDATES = 10;                 // the checked ones; candidate 10 is taken unchecked
+constexpr int TL_MAX_P = 4096;
+constexpr int HSV_D = 7650;
+
+int g_tl_stage_limit = TL_STAGE_LIMIT;
+
+enum { R_NEW_H, R_NEW_W, R_OFF_H, R_OFF_W, R_K, R_FLIP, R_BRIGHT, R_CONTRAST, R_SAT, R_HUE, R_MODE, R_BETA, R_ALPHA_C, R_ALPHA_S,
+       R_DELTA, R_ZERO };
+
+__device__ __forceinline__ unsigned draw32(unsigned long long base, unsigned slot) { return (unsigned)(splitmix64(base + slot) >> 32); }
+
+__device__ __forceinline__ int remap_class(int x, int nseg, int raw) {
+  if (raw) x = (x == 0 || x == 255) ? nseg : x - 1;
+  return min(x, nseg);
+}
+
+// (new_h, new_w) of a source of H0 x W0 whose short side becomes ns: the long side is (2 ns long + s) / (2 s)
+__device__ __forceinline__ void resized_size(int H0, int W0, int ns, int* nh, int* nw) {
+  const long long s = min(H0, W0);
+  const int lg = (int)min((2ll * ns * max(H0, W0) + s) / (2 * s), (long long)0x7fffffff);
+  *nh = H0 <= W0 ? ns : lg;
+  *nw = H0 <= W0 ? lg : ns;
+}
+
+// ------------------------------------------------------------------------------------------------------------- draw
+__global__ __launch_bounds__(256) void train_draw_kernel(const ifseg_train_src* __restrict__ tab, unsigned long long seed,
+                                                         unsigned long long first, int P, int nseg, int raw, int lo2, int span2,
+                                                         int enable, int* __restrict__ params) {
+  extern __shared__ int tl_draw_smem[];
+  int* hist = tl_draw_smem;             // [256]
+  int* red = hist + 256;                // [4]
+  int* syt = red + 4;                   // [P] source row of window row y, times W0 -- fits 31 bits: H0 W0 < 2^31 is checked
+  int* sxt = syt + P;                   // [P]
+  const int b = blockIdx.y, k = blockIdx.x, tid = threadIdx.x;
+  const ifseg_train_src s = tab[b];
+  const unsigned long long base = seed + ((first + (unsigned)b) << 32);
+  const unsigned t0 = draw32(base, 0);
+  const int ns = max(P, (int)(((unsigned long long)P * (((unsigned long long)lo2 << 32) + (unsigned long long)span2 * t0)) >> 33));
+  int nh, nw;
+  resized_size(s.H0, s.W0, ns, &nh, &nw);
+  const int oh = (int)__umulhi(draw32(base, 1 + 2 * k), (unsigned)(nh - P + 1));
+  const int ow = (int)__umulhi(draw32(base, 2 + 2 * k), (unsigned)(nw - P + 1));
+  hist[tid] = 0;
+  for (int i = tid; i < P; i += 256) {
+    syt[i] = min((int)((long long)(oh + i) * s.H0 / nh), s.H0 - 1) * s.W0;
+    sxt[i] = min((int)((long long)(ow + i) * s.W0 / nw), s.W0 - 1);
+  }
+  __syncthreads();
+  const unsigned char* lab = (const unsigned char*)s.label;
+  const int n = P * P;
+  for (int i = tid; i < n; i += 256) {
+    const int y = i / P, x = i - y * P;
+    const int c = remap_class(lab[(long long)syt[y] + sxt[x]], nseg, raw);
+    // large flat regions are the rule in a label map: a wave of one class sends one atomic
+    const int c0 = __builtin_amdgcn_readfirstlane(c);
+    const unsigned long long act = __ballot(1);
+    if (__all(c == c0)) {
+      if ((int)(threadIdx.x & 63) == __ffsll((long long)act) - 1) atomicAdd(&hist[c0], (int)__popcll(act));
+    } else {
+      atomicAdd(&hist[c], 1);
+    }
+  }
+  __syncthreads();
+  int mx = hist[tid];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = max(mx, __shfl_xor(mx, o));
+  if ((tid & 63) == 0) red[tid >> 6] = mx;
+  __syncthreads();
+  if (tid != 0) return;
+  mx = max(max(red[0], red[1]), max(red[2], red[3]));
+  const int ok = 4ll * mx < 3ll * n ? 1 : 0;                 // implies more than one class
+  int* rec = params + (long long)b * 16;
+  const int old = atomicAdd(&rec[R_ZERO], (1 << 16) | (ok << k));
+  if ((old >> 16) != TL_CANDIDATES - 1) return;
+  // the tenth arrival: `old` carries the nine other verdicts (distinct bits: the sum is their union)
+  const int mask = (old | (ok << k)) & ((1 << TL_CANDIDATES) - 1);
+  const int kk = mask ? __ffs(mask) - 1 : TL_CANDIDATES;
+  const unsigned bits = draw32(base, 23);
+  const int ph = (enable >> 1) & 1;
+  rec[R_NEW_H] = nh;
+  rec[R_NEW_W] = nw;
+  rec[R_OFF_H] = (int)__umulhi(draw32(base, 1 + 2 * kk), (unsigned)(nh - P + 1));
+  rec[R_OFF_W] = (int)__umulhi(draw32(base, 2 + 2 * kk), (unsigned)(nw - P + 1));
+  rec[R_K] = kk;
+  rec[R_FLIP] = (enable & 1) & bits;
+  rec[R_BRIGHT] = ph & (bits >> 1);
+  rec[R_MODE] = (bits >> 2) & 1;
+  rec[R_CONTRAST] = ph & (bits >> 3);
+  rec[R_SAT] = ph & (bits >> 4);
+  rec[R_HUE] = ph & (bits >> 5);
+  // exact in fp32: integers below 2^24 times a power of two
+  rec[R_BETA] = __float_as_int((float)((int)(draw32(base, 24) >> 9) - (1 << 22)) * (1.f / 131072.f));
+  rec[R_ALPHA_C] = __float_as_int((float)((1 << 22) + (int)(draw32(base, 25) >> 9)) * (1.f / 8388608.f));
+  rec[R_ALPHA_S] = __float_as_int((float)((1 << 22) + (int)(draw32(base, 26) >> 9)) * (1.f / 8388608.f));
+  rec[R_DELTA] = (int)__umulhi(draw32(base, 27), 36u) - 18;
+  rec[R_ZERO] = 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------- photometric
+// convert(x, alpha, 0) and convert(x, 1, beta): one fp32 operation each, nothing for the compiler to contract
+__device__ __forceinline__ int cvt_mul(int x, float a) { return (int)fminf(fmaxf((float)x * a, 0.f), 255.f); }
+__device__ __forceinline__ int cvt_add(int x, float b) { return (int)fminf(fmaxf((float)x + b, 0.f), 255.f); }
+
+__device__ __forceinline__ void rgb_to_hsv8(int r, int g, int b, int* H, int* S, int* V) {
+  const int v = max(r, max(g, b)), d = v - min(r, min(g, b));
+  *V = v;
+  *S = v ? (int)((unsigned)(510 * d + v) / (unsigned)(2 * v)) : 0;
+  if (d == 0) { *H = 0; return; }
+  int x, off;
+  if (v == r) { x = g - b; off = 0; }
+  else if (v == g) { x = b - r; off = 60; }
+  else { x = r - g; off = 120; }
+  const int n = 30 * x + (off + 180) * d;                   // + 180 d: positive, and a whole turn
+  *H = (int)((unsigned)(2 * n + d) / (unsigned)(2 * d)) % 180;
+}
+
+__device__ __forceinline__ int hsv_rd(int n) { return (int)((unsigned)(2 * n + HSV_D) / (unsigned)(2 * HSV_D)); }
+
+__device__ __forceinline__ void hsv8_to_rgb(int H, int S, int V, int* r, int* g, int* b) {
+  const int sec = H / 30, f = H - 30 * sec;
+  const int p = hsv_rd(30 * V * (255 - S)), q = hsv_rd(V * (HSV_D - S * f)), t = hsv_rd(V * (HSV_D - S * (30 - f)));
+  *r = sec == 0 || sec == 5 ? V : (sec == 1 ? q : (sec == 4 ? t : p));
+  *g = sec == 1 || sec == 2 ? V : (sec == 0 ? t : (sec == 3 ? q : p));
+  *b = sec == 3 || sec == 4 ? V : (sec == 2 ? t : (sec == 5 ? q : p));
+}
+
+struct Photo {
+  int bright, contrast, sat, hue, mode, delta;      // delta already in [0, 180)
+  float beta, alpha_c, alpha_s;
+};
+
+__device__ __forceinline__ void photometric(const Photo& ph, int* r, int* g, int* b) {
+  if (ph.bright) { *r = cvt_add(*r, ph.beta); *g = cvt_add(*g, ph.beta); *b = cvt_add(*b, ph.beta); }
+  if (ph.contrast && ph.mode == 1) { *r = cvt_mul(*r, ph.alpha_c); *g = cvt_mul(*g, ph.alpha_c); *b = cvt_mul(*b, ph.alpha_c); }
+  if (ph.sat) {
+    int H, S, V;
+    rgb_to_hsv8(*r, *g, *b, &H, &S, &V);
+    hsv8_to_rgb(H, cvt_mul(S, ph.alpha_s), V, r, g, b);
+  }
+  if (ph.hue) {
+    int H, S, V;
+    rgb_to_hsv8(*r, *g, *b, &H, &S, &V);
+    H += ph.delta;
+    hsv8_to_rgb(H >= 180 ? H - 180 : H, S, V, r, g, b);
+  }
+  if (ph.contrast && ph.mode == 0) { *r = cvt_mul(*r, ph.alpha_c); *g = cvt_mul(*g, ph.alpha_c); *b = cvt_mul(*b, ph.alpha_c); }
+}
+
+// ------------------------------------------------------------------------------------------------------------- load
+// (2 d + 1) in - out and 2 out stay below 2^31: the kernel poisons a record with 2 in out >= 2^31
+__device__ __forceinline__ void src_coord(int d, int in, int out, int* i0, int* i1, float* l) {
+  const int num = max((2 * d + 1) * in - out, 0), den = 2 * out;
+  *i0 = min((int)((unsigned)num / (unsigned)den), in - 1);
+  *i1 = min(*i0 + 1, in - 1);
+  *l = *i0 == *i1 ? 0.f : (float)(num - *i0 * den) / (float)den;          // IEEE division: the fraction is rounded once
+}
+
+__host__ __device__ inline int tl_rstride(int fw) { return (fw * 3 + 3 + 3) & ~3; }
+
+__device__ __forceinline__ void store_plane(float* out, long long e, bool ok, float v, int, int, int) {
+  if (ok) out[e] = v;
+}
+// bf16: e = flat element index of the lane's pixel; pairs on even e
+__device__ __forceinline__ void store_plane(bf16_t* out, long long e, bool ok, float v, int lane, int x, int xend) {
+  const uint32_t h = f2bf(v);
+  const uint32_t right = (uint32_t)__shfl_down((int)h, 1);                // every lane takes part
+  if (!ok) return;
+  if ((e & 1) == 0) {
+    if (lane < TL_COLS - 1 && x + 1 < xend) *reinterpret_cast<uint32_t*>(out + e) = h | (right << 16);
+    else out[e] = (bf16_t)h;
+  } else if (lane == 0) {
+    out[e] = (bf16_t)h;
+  }
+}
+
+// the thread's four pixels (rows j = 0..3 of its wave, one x).  r0[j] / r1[j]: wave-uniform byte offset of the upper / lower
+// source row from `base`, o0 / o1: per-lane byte offset of the left / right pixel
+template <typename T, typename Ptr>
+__device__ __forceinline__ void pixel_loop(Ptr base, const long long (&r0)[4], const long long (&r1)[4], int o0, int o1,
+                                           const float (&ly)[4], float lx, const float* lut, bool rev, const Photo& ph, T* out,
+                                           const long long (&erow)[4], long long plane, const bool (&ok)[4], int lane, int x,
+                                           int xend) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float w00 = (1.f - ly[j]) * (1.f - lx), w01 = (1.f - ly[j]) * lx, w10 = ly[j] * (1.f - lx), w11 = ly[j] * lx;
+    int q[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float a = (float)base[r0[j] + o0 + c], b = (float)base[r0[j] + o1 + c];
+      const float d = (float)base[r1[j] + o0 + c], e = (float)base[r1[j] + o1 + c];
+      const float v = w00 * a + w01 * b + w10 * d + w11 * e;
+      q[c] = (int)fminf(fmaxf(floorf(v + 0.5f), 0.f), 255.f);
+    }
+    photometric(ph, &q[0], &q[1], &q[2]);
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      store_plane(out, erow[j] + c * plane + x, ok[j], lut[c * 256 + q[rev ? 2 - c : c]], lane, x, xend);
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void train_load_kernel(const ifseg_train_src* __restrict__ tab, const int* __restrict__ params,
+                                                         int P, int tiles_x, int tiles_y, int nseg, int raw, long long seg0,
+                                                         long long eos, const float* __restrict__ lut_g, int rev,
+                                                         T* __restrict__ out, long long* __restrict__ target, int stage_bytes) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  float* lut = reinterpret_cast<float*>(smem);
+  unsigned char* stage = smem + TL_LUT_BYTES;
+
+  const int tx = blockIdx.x % tiles_x, ty = (blockIdx.x / tiles_x) % tiles_y, b = blockIdx.x / (tiles_x * tiles_y);
+  const int X0 = tx * TL_COLS, Y0 = ty * TL_ROWS;
+  const int xend = min(X0 + TL_COLS, P), yend = min(Y0 + TL_ROWS, P);
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const ifseg_train_src s = tab[b];
+  const int* rec = params + (long long)b * 16;
+  const int H0 = s.H0, W0 = s.W0, nh = rec[R_NEW_H], nw = rec[R_NEW_W], offh = rec[R_OFF_H], offw = rec[R_OFF_W];
+  const bool flip = rec[R_FLIP] != 0;
+  Photo ph;
+  ph.bright = rec[R_BRIGHT]; ph.contrast = rec[R_CONTRAST]; ph.sat = rec[R_SAT]; ph.hue = rec[R_HUE]; ph.mode = rec[R_MODE];
+  ph.delta = (rec[R_DELTA] % 180 + 180) % 180;
+  ph.beta = __int_as_float(rec[R_BETA]); ph.alpha_c = __int_as_float(rec[R_ALPHA_C]); ph.alpha_s = __int_as_float(rec[R_ALPHA_S]);
+
+  const long long plane = (long long)P * P;
+  long long* tgt = target + (long long)b * (plane + 1);
+  if (blockIdx.x % (tiles_x * tiles_y) == 0 && threadIdx.x == 0) tgt[plane] = eos;
+
+  const int x = min(X0 + lane, P - 1);
+  const bool bad = nh < P || nw < P || offh < 0 || offw < 0 || offh > nh - P || offw > nw - P || 2ll * H0 * nh >= (1ll << 31) ||
+                   2ll * W0 * nw >= (1ll << 31);                                 // workgroup-uniform
+  if (bad) {
+    const float nanv = __int_as_float(0x7fc00000);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int yr = Y0 + wave * 4 + j;
+      const bool ok = yr < P && X0 + lane < P;
+      const long long erow = (long long)b * 3 * plane + (long long)min(yr, P - 1) * P;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) store_plane(out, erow + c * plane + x, ok, nanv, lane, x, xend);
+      if (ok) tgt[(long long)yr * P + x] = -1;
+    }
+    return;
+  }
+
+  for (int i = threadIdx.x; i < 768; i += 256) lut[i] = lut_g[i];
+
+  // the tile's footprint in the source: window pixel (y, x) is pixel (offh + y, offw + xs) of the resized image, xs = x or its
+  // mirror; source coordinates are monotone, so the first and the last pixel bound the footprint
+  const int RX0 = offw + (flip ? P - xend : X0), RX1 = offw + (flip ? P - 1 - X0 : xend - 1);
+  int ylo, yhi, xlo, xhi, t0;
+  float tf;
+  src_coord(offh + Y0, H0, nh, &ylo, &t0, &tf);
+  src_coord(offh + yend - 1, H0, nh, &t0, &yhi, &tf);
+  src_coord(RX0, W0, nw, &xlo, &t0, &tf);
+  src_coord(RX1, W0, nw, &t0, &xhi, &tf);
+  const int fh = yhi - ylo + 1, fw = xhi - xlo + 1, rstride = tl_rstride(fw);
+  const bool staged = (long long)fh * rstride <= (long long)stage_bytes;            // workgroup-uniform
+  const unsigned char* sb = (const unsigned char*)s.image;
+  const unsigned char* row0 = sb + ((long long)ylo * W0 + xlo) * 3;
+  if (staged) {
+    const int dpr = rstride >> 2;
+    uint32_t* st32 = reinterpret_cast<uint32_t*>(stage);
+    for (int i = threadIdx.x; i < fh * dpr; i += 256) {
+      const int ry = i / dpr, k = i - ry * dpr;
+      const unsigned char* a = row0 + (long long)ry * W0 * 3;
+      const int sh = (int)((size_t)a & 3);
+      // aligned dwords: up to 3 bytes in front of the first pixel and behind the last one are read with them, also in front of /
+      // behind the caller's buffer (an aligned dword never crosses a page)
+      if (4 * k < sh + fw * 3) st32[i] = *reinterpret_cast<const uint32_t*>(a - sh + 4 * k);
+    }
+  }
+  __syncthreads();
+
+  const int xs = offw + (flip ? P - 1 - x : x);
+  int x0, x1;
+  float lx;
+  src_coord(xs, W0, nw, &x0, &x1, &lx);
+  const int lsx = min((int)((long long)xs * W0 / nw), W0 - 1);
+  int y0[4], y1[4];
+  float ly[4];
+  bool ok[4];
+  long long erow[4], r0[4], r1[4];
+  const unsigned char* lab = (const unsigned char*)s.label;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int yr = Y0 + wave * 4 + j, y = min(yr, P - 1);
+    src_coord(offh + y, H0, nh, &y0[j], &y1[j], &ly[j]);
+    ok[j] = yr < P && X0 + lane < P;
+    erow[j] = (long long)b * 3 * plane + (long long)y * P;
+    if (ok[j]) {
+      const int lsy = min((int)((long long)(offh + y) * H0 / nh), H0 - 1);
+      tgt[(long long)y * P + x] = seg0 + remap_class(lab[(long long)lsy * W0 + lsx], nseg, raw);
+    }
+  }
+  if (staged) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      r0[j] = (y0[j] - ylo) * rstride + (int)((size_t)(row0 + (long long)(y0[j] - ylo) * W0 * 3) & 3);
+      r1[j] = (y1[j] - ylo) * rstride + (int)((size_t)(row0 + (long long)(y1[j] - ylo) * W0 * 3) & 3);
+    }
+    pixel_loop<T>(stage, r0, r1, (x0 - xlo) * 3, (x1 - xlo) * 3, ly, lx, lut, rev != 0, ph, out, erow, plane, ok, lane, x, xend);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { r0[j] = (long long)y0[j] * W0 * 3; r1[j] = (long long)y1[j] * W0 * 3; }
+    pixel_loop<T>(sb, r0, r1, x0 * 3, x1 * 3, ly, lx, lut, rev != 0, ph, out, erow, plane, ok, lane, x, xend);
+  }
+}
+
+// what both entry points ask of the host copy of the table
+int check_table(const ifseg_train_src* th, int B, bool want_images, long long max_short) {
+  const long long lim = 1ll << 31;
+  for (int b = 0; b < B; ++b) {
+    if (!th[b].label || (want_images && !th[b].image)) return IFSEG_ERR_BAD_ARG;
+    const long long H0 = th[b].H0, W0 = th[b].W0;
+    if (H0 < 1 || W0 < 1 || H0 * W0 * 3 >= lim) return IFSEG_ERR_BAD_SHAPE;
+    if (max_short) {
+      // the largest resized size this source can be drawn to
+      const long long s = std::min(H0, W0), lg = (2 * max_short * std::max(H0, W0) + s) / (2 * s);
+      if (2 * s * max_short >= lim || 2 * std::max(H0, W0) * lg >= lim) return IFSEG_ERR_BAD_SHAPE;
+    }
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int ifseg_train_draw(const ifseg_train_src* table_host, const ifseg_train_src* table, int B, int P, int nseg,
+                                int raw_labels, unsigned long long seed, long long first_ordinal, int ratio_lo2, int ratio_span2,
+                                int enable, int* params, void* stream) {
+  (void)hipGetLastError();
+  if (!table_host || !table || !params || ((size_t)params & 3) || ((size_t)table & 7)) return IFSEG_ERR_BAD_ARG;
+  if (nseg < 1 || nseg > 255 || ratio_lo2 < 0 || ratio_span2 < 0 || ratio_lo2 + ratio_span2 > 64) return IFSEG_ERR_BAD_ARG;
+  if (first_ordinal < 0 || first_ordinal + (long long)B > (1ll << 32)) return IFSEG_ERR_BAD_ARG;
+  if (B < 1 || B > 65535 || P < 16 || P % 16 || P > TL_MAX_P) return IFSEG_ERR_BAD_SHAPE;
+  const long long max_short = std::max<long long>(P, ((long long)P * (ratio_lo2 + ratio_span2)) >> 1);
+  if (int rc = check_table(table_host, B, false, max_short)) return rc;
+  // slot 15 of every record collects the verdicts: zero before the launch, zero again behind it
+  hipError_t e = hipMemsetAsync(params, 0, (size_t)B * 16 * sizeof(int), (hipStream_t)stream);
+  if (e != hipSuccess) return (int)e;
+  const size_t lds = (size_t)(256 + 4 + 2 * P) * sizeof(int);
+  hipLaunchKernelGGL(train_draw_kernel, dim3(TL_CANDIDATES, B), dim3(256), lds, (hipStream_t)stream, table, seed,
+                     (unsigned long long)first_ordinal, P, nseg, raw_labels, ratio_lo2, ratio_span2, enable, params);
+  IFSEG_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ifseg_train_load_staging(int max_bytes) {
+  const int prev = g_tl_stage_limit;
+  g_tl_stage_limit = max_bytes < 0 ? TL_STAGE_LIMIT : (max_bytes < TL_STAGE_LIMIT ? max_bytes : TL_STAGE_LIMIT);
+  return prev;
+}
+
+extern "C" int ifseg_train_load(const ifseg_train_src* table_host, const ifseg_train_src* table, const int* params,
+                                const int* params_host, int B, int P, int nseg, int raw_labels, long long seg_id_offset,
+                                long long eos, const float* lut, int reverse_channels, void* out, int out_bytes,
+                                long long* target, void* stream) {
+  (void)hipGetLastError();
+  if (!table_host || !table || !params || !lut || !out || !target || (out_bytes != 4 && out_bytes != 2)) return IFSEG_ERR_BAD_ARG;
+  if (((size_t)out & 15) || ((size_t)lut & 3) || ((size_t)target & 7) || ((size_t)params & 3) || ((size_t)table & 7))
+    return IFSEG_ERR_BAD_ARG;
+  if (nseg < 1 || nseg > 255) return IFSEG_ERR_BAD_ARG;
+  if (B < 1 || P < 16 || P % 16 || P > TL_MAX_P) return IFSEG_ERR_BAD_SHAPE;
+  const long long lim = 1ll << 31;
+  if ((long long)B * 3 * P * P >= lim) return IFSEG_ERR_BAD_SHAPE;
+  if (int rc = check_table(table_host, B, true, 0)) return rc;
+  if (params_host) {
+    for (int b = 0; b < B; ++b) {
+      const int* r = params_host + 16 * b;
+      if (r[R_NEW_H] < P || r[R_NEW_W] < P || r[R_OFF_H] < 0 || r[R_OFF_W] < 0 || r[R_OFF_H] > r[R_NEW_H] - P ||
+          r[R_OFF_W] > r[R_NEW_W] - P)
+        return IFSEG_ERR_BAD_SHAPE;
+      if (2ll * table_host[b].H0 * r[R_NEW_H] >= lim || 2ll * table_host[b].W0 * r[R_NEW_W] >= lim) return IFSEG_ERR_BAD_SHAPE;
+    }
+  }
+  const int tiles_x = (P + TL_COLS - 1) / TL_COLS, tiles_y = P / TL_ROWS;
+  const long long blocks = (long long)tiles_x * tiles_y * B;
+  // an upper bound of any tile's footprint: the resized short side is at least P, so a step of the window is at most s / P
+  // source samples on either axis (the long side's rounding adds less than one sample over a tile); + 1 for the lower / right
+  // neighbour, + 1 for the rounding of the coordinate, + 1 for the long side
+  long long need = 0;
+  for (int b = 0; b < B; ++b) {
+    const long long H0 = table_host[b].H0, W0 = table_host[b].W0, s = std::min(H0, W0);
+    const long long fh = std::min(H0, (long long)TL_ROWS * s / P + 4), fw = std::min(W0, (long long)TL_COLS * s / P + 4);
+    need = std::max(need, fh * ((fw * 3 + 6) & ~3ll));
+  }
+  const int stage = need > g_tl_stage_limit ? g_tl_stage_limit & ~15 : (int)((need + 15) & ~15ll);
+  const int lds = TL_LUT_BYTES + stage;
+  if (out_bytes == 4)
+    hipLaunchKernelGGL(train_load_kernel<float>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, table, params, P,
+                       tiles_x, tiles_y, nseg, raw_labels, seg_id_offset, eos, lut, reverse_channels, (float*)out, target, stage);
+  else
+    hipLaunchKernelGGL(train_load_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, table, params, P,
+                       tiles_x, tiles_y, nseg, raw_labels, seg_id_offset, eos, lut, reverse_channels, (bf16_t*)out, target, stage);
+  IFSEG_CHECK_LAUNCH();
+  return 0;
+}

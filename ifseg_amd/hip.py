@@ -1095,6 +1095,102 @@ def image_load(images_u8, oh, ow, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), rev
     return out
 
 
+def _image_lut(mean, std, dev):
+    from .imageio import normalisation_table
+    key = (tuple(float(x) for x in mean), tuple(float(x) for x in std), dev)
+    lut = _image_luts.get(key)
+    if lut is None:
+        if len(_image_luts) >= 16:
+            _image_luts.clear()
+        lut = _image_luts[key] = normalisation_table(mean, std).to(dev)
+    return lut
+
+
+def _train_table(images, labels):
+    """the descriptor table of a batch (include/ifseg_hip.h ifseg_train_src: image pointer, label pointer, H0 | W0 << 32) ->
+    (pinned host int64 [B, 3], its device copy): one small H2D copy on the current stream.  The sources are recorded on that
+    stream, so their memory is not handed out again before the kernels have read it."""
+    dev = labels[0].device
+    rows = []
+    stream = torch.cuda.current_stream(dev)
+    for i, lab in enumerate(labels):
+        assert lab.is_cuda and lab.device == dev and lab.dtype == torch.uint8 and lab.dim() == 2 and lab.is_contiguous(), \
+            (lab.device, lab.dtype, tuple(lab.shape))
+        H0, W0 = lab.shape
+        assert 1 <= H0 < 2 ** 31 and 1 <= W0 < 2 ** 31, (H0, W0)
+        img_ptr = 0
+        if images is not None:
+            img = images[i]
+            assert img.is_cuda and img.device == dev and img.dtype == torch.uint8 and tuple(img.shape) == (H0, W0, 3) \
+                and img.is_contiguous(), (img.device, img.dtype, tuple(img.shape), (H0, W0))
+            img_ptr = img.data_ptr()
+            img.record_stream(stream)
+        lab.record_stream(stream)
+        rows.append((img_ptr, lab.data_ptr(), H0 | (W0 << 32)))
+    host = torch.tensor(rows, dtype=torch.int64).pin_memory()
+    return host, host.to(dev, non_blocking=True)
+
+
+def train_draw(labels, P, nseg, seed, first_ordinal, ratio_range=(0.5, 2.0), photometric=True, flip=True, raw_labels=True,
+               out=None, table=None):
+    """records int32 [B, 16] of the training transform for the samples at ordinals first_ordinal + b (csrc/trainload.hip;
+    `augment.draw_params` is the specification).  labels: uint8 [H0, W0] device tensors of any sizes.  table: the batch's
+    `_train_table(images, labels)` when the caller shares one between this call and `train_load`."""
+    from .augment import ratio_halves
+    lo2, span2 = ratio_halves(ratio_range)
+    B = len(labels)
+    assert B >= 1
+    host, table = table if table is not None else _train_table(None, labels)
+    if out is None:
+        out = torch.empty(B, 16, dtype=torch.int32, device=labels[0].device)
+    else:
+        assert out.dtype == torch.int32 and tuple(out.shape) == (B, 16) and out.is_contiguous() and out.device == labels[0].device
+    _check(lib().ifseg_train_draw(c_void_p(host.data_ptr()), _ptr(table), c_int(B), c_int(P), c_int(nseg),
+                                  c_int(1 if raw_labels else 0), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+                                  c_ll(int(first_ordinal)), c_int(lo2), c_int(span2),
+                                  c_int((1 if flip else 0) | (2 if photometric else 0)), _ptr(out), _stream()), "train_draw")
+    return out
+
+
+def train_load(images, labels, params, P, nseg, seg_id_offset, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), reverse_channels=False,
+               raw_labels=True, dtype=torch.float32, eos=2, staging_bytes=None, out=None, target=None, table=None):
+    """the training transform under the given records, one launch (csrc/trainload.hip; `augment.train_load_reference` is the
+    specification): uint8 images [H0, W0, 3] and label maps [H0, W0] of any sizes on the device ->
+    (patch_images [B, 3, P, P] in `dtype`, target int64 [B, P*P + 1]).  params: int32 [B, 16]; records on the host are checked
+    by the entry point before they are copied, records on the device are checked by the kernel (a bad one poisons its
+    sample).  staging_bytes: the LDS staging buffer of this call (0: every tile reads global memory), None: the default."""
+    B = len(images)
+    assert B >= 1 and len(labels) == B and dtype in (torch.float32, torch.bfloat16), (B, len(labels), dtype)
+    dev = labels[0].device
+    assert params.dtype == torch.int32 and tuple(params.shape) == (B, 16), (params.dtype, tuple(params.shape))
+    params_host = None
+    if not params.is_cuda:
+        params_host = params.contiguous()
+        params = params_host.to(dev)
+    params = params.contiguous()
+    lut = _image_lut(mean, std, dev)
+    host, table = table if table is not None else _train_table(images, labels)
+    if out is None:
+        out = torch.empty(B, 3, P, P, dtype=dtype, device=dev)
+    else:
+        assert out.dtype == dtype and tuple(out.shape) == (B, 3, P, P) and out.is_contiguous() and out.device == dev
+    if target is None:
+        target = torch.empty(B, P * P + 1, dtype=torch.int64, device=dev)
+    else:
+        assert target.dtype == torch.int64 and tuple(target.shape) == (B, P * P + 1) and target.is_contiguous() and target.device == dev
+    prev = lib().ifseg_train_load_staging(c_int(staging_bytes)) if staging_bytes is not None else None
+    try:
+        _check(lib().ifseg_train_load(c_void_p(host.data_ptr()), _ptr(table), _ptr(params),
+                                      c_void_p(params_host.data_ptr()) if params_host is not None else None, c_int(B), c_int(P),
+                                      c_int(nseg), c_int(1 if raw_labels else 0), c_ll(seg_id_offset), c_ll(eos), _ptr(lut),
+                                      c_int(1 if reverse_channels else 0), _ptr(out), c_int(out.element_size()), _ptr(target),
+                                      _stream()), "train_load")
+    finally:
+        if prev is not None:
+            lib().ifseg_train_load_staging(c_int(prev))
+    return out, target
+
+
 def dropout(x, resid, out, p, seed, drop_path_scale=None, rows_per_batch=None):
     """x / resid / out: [rows, C] or [B, rpb, C] bf16 views (last dim contiguous)"""
     C = x.shape[-1]

@@ -19,7 +19,9 @@ The second half of the file puts the training-path kernels there as well (see th
 kernels, with key counts and attention dropout) and `seg_loss` (csrc/loss.hip), with `*_bwd` ops of their own;
 `ifseg_amd.modules.MultiheadAttention` composes `linear` and `attention_bias` under the reference module's parameter names.
 `seg_predict` (csrc/predict.hip: label maps at image resolution) and `image_load` (csrc/imgload.hip: raw uint8 images to
-normalised patch_images, the reference's evaluation transform) are inference only and have no backward.
+normalised patch_images, the reference's evaluation transform) are inference only and have no backward; `train_load`
+(csrc/trainload.hip: raw images and label maps of any sizes to a training batch under given records, the reference's training
+transform) has integer inputs and no backward either.
 """
 from typing import Optional, Sequence, Tuple
 
@@ -747,3 +749,52 @@ def image_load(images: torch.Tensor, oh: int, ow: int, mean: Sequence[float], st
 def _(images, oh, ow, mean, std, reverse_channels, dtype):
     B = _image_load_check(images, oh, ow, mean, std, dtype)
     return images.new_empty((B, 3, oh, ow), dtype=dtype)
+
+
+# ----------------------------------------------------------------------------------------------- train_load
+def _train_load_check(images, labels, params, P, nseg, mean, std, dtype):
+    op = "ifseg::train_load"
+    B = len(images)
+    if B == 0 or len(labels) != B:
+        raise ValueError("%s: %d images and %d label maps (one label map per image, at least one)" % (op, B, len(labels)))
+    for img, lab in zip(images, labels):
+        if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[-1] != 3 or img.numel() == 0:
+            raise ValueError("%s: images must be non-empty uint8 [H0, W0, 3] (HWC), got %s %s" % (op, img.dtype, tuple(img.shape)))
+        if lab.dtype != torch.uint8 or tuple(lab.shape) != tuple(img.shape[:2]):
+            raise ValueError("%s: label maps must be uint8 [H0, W0] of the image's size, got %s %s for an image of %s"
+                             % (op, lab.dtype, tuple(lab.shape), tuple(img.shape)))
+        if img.shape[0] * img.shape[1] * 3 >= 2 ** 31:
+            raise ValueError("%s: H0 * W0 * 3 must stay below 2**31, got %s" % (op, tuple(img.shape)))
+    if params.dtype != torch.int32 or tuple(params.shape) != (B, 16):
+        raise ValueError("%s: params must be int32 [%d, 16], got %s %s" % (op, B, params.dtype, tuple(params.shape)))
+    if P < 16 or P % 16 or P > 4096 or B * 3 * P * P >= 2 ** 31:
+        raise ValueError("%s: P must be a multiple of 16 in 16 .. 4096 with B * 3 * P * P < 2**31, got P = %d, B = %d" % (op, P, B))
+    if not 1 <= nseg <= 255:
+        raise ValueError("%s: nseg must lie in 1 .. 255 (uint8 label maps), got %d" % (op, nseg))
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("%s: mean and std must have three entries, got %d and %d" % (op, len(mean), len(std)))
+    if dtype not in (torch.float32, BF):
+        raise ValueError("%s: the output dtype must be torch.float32 or torch.bfloat16, got %s" % (op, dtype))
+    return B
+
+
+@custom_op("ifseg::train_load", mutates_args=(), device_types="cuda")
+def train_load(images: Sequence[torch.Tensor], labels: Sequence[torch.Tensor], params: torch.Tensor, P: int, nseg: int,
+               seg_id_offset: int, mean: Sequence[float], std: Sequence[float], reverse_channels: bool, raw_labels: bool,
+               dtype: torch.dtype) -> Tuple[torch.Tensor, torch.Tensor]:
+    """the reference's training transform under the given records (csrc/trainload.hip; ifseg_amd/augment.py is the
+    specification): uint8 images [H0, W0, 3] and label maps [H0, W0] of any sizes, params int32 [B, 16] ->
+    (patch_images [B, 3, P, P] in `dtype`, target int64 [B, P*P + 1]).  Integer inputs: not differentiable."""
+    _train_load_check(images, labels, params, P, nseg, mean, std, dtype)
+    prev = _stream_scope(params)
+    try:
+        return hip.train_load([t.contiguous() for t in images], [t.contiguous() for t in labels], params.contiguous(), P, nseg,
+                              seg_id_offset, mean, std, reverse_channels, raw_labels, dtype)
+    finally:
+        hip.set_stream(prev)
+
+
+@train_load.register_fake
+def _(images, labels, params, P, nseg, seg_id_offset, mean, std, reverse_channels, raw_labels, dtype):
+    B = _train_load_check(images, labels, params, P, nseg, mean, std, dtype)
+    return params.new_empty((B, 3, P, P), dtype=dtype), params.new_empty((B, P * P + 1), dtype=torch.int64)

@@ -8,7 +8,8 @@ dictionary = dict.txt + <mask> + <code_i> + <bin_i> + (nseg+1) <seg_i>), ``build
 ``train_step`` (:190-222), ``valid_step`` (:225-229) and the ``sample`` dict layout of
 data/mm_data/segmentation_dataset.py:110-127.  Data loading (TSV / mmseg pipeline) is out of scope (SURVEY.md
 section 2.1): ``load_dataset`` refuses; samples for the bundled harness are synthetic tensors of the right shapes
-(SURVEY.md 8d).
+(SURVEY.md 8d), and ``train_sample`` turns decoded images and label maps into a batch of that layout through the
+training transform of the pipeline (ifseg_amd/augment.py, csrc/trainload.hip).
 """
 import os
 from dataclasses import dataclass, field
@@ -120,6 +121,7 @@ class SegmentationTask(TaskBase):
         # token ids of every category name, for the criterion's lazy seg-token initialisation where no BPE encoder
         # exists (the reference encodes `category_list` with task.bpe: seg_criterion.py:373-388)
         self.category_token_ids = category_token_ids
+        self.prompt_ids = PROMPT_IDS              # the prompt in front of the category names (`train_sample`)
         self.bpe = None
         # L = bos + 12 prompt ids + class-name ids + eos: 36 / 215 / 239 for 15 / 150 / 171 classes
         self.src_len = src_len or {15: 36, 150: 215, 171: 239}.get(nseg, 14 + 2 * nseg)
@@ -291,6 +293,56 @@ class SegmentationTask(TaskBase):
         hp = self.cfg.patch_image_size // 16
         return ArtificialImageSampler(names + [torch.as_tensor(unknown, dtype=torch.long)], self.seg_id_offset, hp, hp, lr[0], lr[1],
                                       seed=seed, device=device, bos=BOS, eos=EOS, pad=PAD)
+
+    def build_train_transform(self, device="cpu", seed=1, **kw):
+        """The training transform of the data pipeline for this task (ifseg_amd/augment.py: Resize(ratio_range), RandomCrop,
+        RandomFlip, PhotoMetricDistortion, Normalize of segmentation_dataset.py:148-163 on raw uint8 images and raw label
+        maps), with the task's patch size, class count and normalisation; on a GPU device it runs csrc/trainload.hip."""
+        from ...augment import TrainTransform
+        from ...imageio import HALF, IMAGENET_DEFAULT_MEAN, IMAGENET_DEFAULT_STD
+        if getattr(self.cfg, "imagenet_default_mean_and_std", False):
+            kw.setdefault("mean", IMAGENET_DEFAULT_MEAN)
+            kw.setdefault("std", IMAGENET_DEFAULT_STD)
+        else:
+            kw.setdefault("mean", HALF)
+            kw.setdefault("std", HALF)
+        kw.setdefault("eos", EOS)
+        self.train_transform = TrainTransform(self.cfg.patch_image_size, self.num_seg_tokens, self.seg_id_offset, seed=seed,
+                                              device=device, **kw)
+        return self.train_transform
+
+    def _train_src_tokens(self):
+        """bos + prompt + the category names + eos, as `predict.source_tokens` builds them for the Segmenter"""
+        if getattr(self, "_train_src", None) is None:
+            from ...predict import source_tokens
+            names = self.category_token_ids
+            if names is None:
+                cats = [x.strip() for x in self.category_list.split(",")] if self.category_list else []
+                if not cats:
+                    raise RuntimeError("train_sample: the task carries neither category_list (+ BPE) nor category_token_ids")
+                names = [self.encode_category(" %s" % x) for x in cats]
+            self._train_src = source_tokens(names, self.prompt_ids, self.num_seg_tokens)
+        return self._train_src
+
+    def train_sample(self, images, labels, first_ordinal):
+        """Raw uint8 images [H0, W0, 3] (RGB) and raw uint8 label maps [H0, W0] of any sizes -> the batch `Trainer.train_step`
+        takes, in `synthetic_sample`'s layout, through `build_train_transform`'s transform (built on first use, on the CPU,
+        if the caller has not built one).  `first_ordinal` is the ordinal of sample 0 (`artificial.trainer_first_ordinal`):
+        the batch is a pure function of (seed, ordinal)."""
+        tf = getattr(self, "train_transform", None) or self.build_train_transform()
+        img, tgt = tf(images, labels, first_ordinal)
+        B, P, dev = len(images), tf.P, tf.device
+        src = self._train_src_tokens()
+        if src.device != dev:
+            src = self._train_src = src.to(dev)
+        L = src.numel()
+        return {
+            "id": list(range(B)), "nsentences": B, "ntokens": int(B * (P * P + 1)),
+            "net_input": {"src_tokens": src.repeat(B, 1), "src_lengths": torch.full((B,), L, device=dev),
+                          "patch_images": img, "patch_masks": torch.ones(B, dtype=torch.bool, device=dev),
+                          "prev_output_tokens": torch.zeros(B, 1, dtype=torch.long, device=dev)},
+            "target": tgt,
+        }
 
     def train_step(self, sample, model, criterion, optimizer, update_num, ignore_grad=False, **extra_kwargs):
         """tasks/mm_tasks/segmentation.py:190-222."""

@@ -584,6 +584,47 @@ int ifseg_image_load(const void* images, int B, int H0, int W0, int oh, int ow, 
                      void* out, int out_bytes, void* stream);
 int ifseg_image_load_staging(int max_bytes);
 
+/* ---- raw images and raw label maps in, a training batch out (ifseg_amd/augment.py is the specification, bit for bit; the
+ * reference's training transform, segmentation_dataset.py:157-163, 239-251: Resize(ratio_range), RandomCrop(cat_max_ratio 0.75),
+ * RandomFlip, PhotoMetricDistortion, Normalize) ----
+ * A batch is described by a table of B entries, once in host memory (read by the entry points for their checks) and once on
+ * the device (read by the kernels; the caller copies it on the stream of the call). */
+typedef struct {
+  const void* image; /* device, uint8 [H0, W0, 3] RGB, contiguous, any byte alignment (unused by ifseg_train_draw) */
+  const void* label; /* device, uint8 [H0, W0], contiguous */
+  int H0, W0;
+} ifseg_train_src;
+/* ifseg_train_draw writes the records int32 [B, 16] of the samples at ordinals first_ordinal + b from
+ * t(n, i) = splitmix64(seed + (n << 32) + i) >> 32 (slots and layout: the docstring of ifseg_amd/augment.py):
+ *   0 new_h  1 new_w  2 off_h  3 off_w  4 k  5 flip  6 brightness on  7 contrast on  8 saturation on  9 hue on  10 mode
+ *   11 beta  12 alpha_c  13 alpha_s (fp32 bit patterns)  14 delta  15 zero
+ * new_short = max(P, (P (ratio_lo2 2^32 + ratio_span2 t)) >> 33); the crop is the first of candidates 0..9 whose P x P window
+ * of the remapped (raw_labels != 0: raw 0 and 255 -> nseg, x -> x - 1), nearest-resized label map has 4 max(count) < 3 P^2,
+ * else candidate 10.  enable: bit 0 flips, bit 1 the photometric stage (a cleared bit leaves the on-bits zero).
+ * One memset node and one launch of 10 B workgroups; integer counts only, so the result does not depend on arrival order.
+ * NULL or misaligned pointers, nseg outside 1..255, a ratio outside 0 <= lo2, span2, lo2 + span2 <= 64, ordinals outside
+ * [0, 2^32): IFSEG_ERR_BAD_ARG.  B outside 1..65535, P not a multiple of 16 in 16..4096, H0 or W0 < 1, H0*W0*3 >= 2^31, or
+ * 2 in out >= 2^31 on an axis at the largest size the ratio can draw: IFSEG_ERR_BAD_SHAPE. */
+int ifseg_train_draw(const ifseg_train_src* table_host, const ifseg_train_src* table, int B, int P, int nseg, int raw_labels,
+                     unsigned long long seed, long long first_ordinal, int ratio_lo2, int ratio_span2, int enable, int* params,
+                     void* stream);
+/* ifseg_train_load: records (device) -> out [B, 3, P, P] (out_bytes 4 -> fp32, 2 -> bf16) and target int64 [B, P*P + 1]
+ * (seg_id_offset + class, then eos), one launch.  Window pixel (y, x) is pixel (off_h + y, off_w + xs) of the source resized
+ * to new_h x new_w, xs = x or P - 1 - x under flip: the image by ifseg_image_load's rule (integer source coordinates, the
+ * four-weight sum in fp32, q = clamp(floor(v + 0.5), 0, 255)), the label by src = min(dst in / out, in - 1).  The grey levels go
+ * through the photometric chain (brightness; contrast if mode 1; saturation; hue; contrast if mode 0; convert() as a single
+ * fp32 operation, HSV in exact integers) and then lut fp32 [3][256]; reverse_channels reverses the order of the output planes.
+ * params_host (may be NULL): the same records in host memory, when the caller has them -- then a record with new_h or new_w
+ * < P, an offset outside the resized image or 2 in out >= 2^31 is refused with IFSEG_ERR_BAD_SHAPE and nothing is launched.
+ * Without it such a record poisons its sample on the device (NaN images, target -1) and reads nothing through it.
+ * The staging loads are aligned dwords, as in ifseg_image_load; ifseg_train_load_staging is the same switch.
+ * NULL / misaligned pointers (out 16 bytes, target 8), out_bytes, nseg: IFSEG_ERR_BAD_ARG; B < 1, P not a multiple of 16 in
+ * 16..4096, B*3*P*P >= 2^31, a bad table entry: IFSEG_ERR_BAD_SHAPE. */
+int ifseg_train_load(const ifseg_train_src* table_host, const ifseg_train_src* table, const int* params, const int* params_host,
+                     int B, int P, int nseg, int raw_labels, long long seg_id_offset, long long eos, const float* lut,
+                     int reverse_channels, void* out, int out_bytes, long long* target, void* stream);
+int ifseg_train_load_staging(int max_bytes);
+
 /* sum of squares of a bf16 gradient arena -> out_sumsq[0] (device). */
 int ifseg_grad_sumsq_bf16(const void* g, long long n, float* workspace, float* out_sumsq, void* stream);
 /* Fused grad scaling + clip-by-global-norm + Adam with decoupled weight decay over a
