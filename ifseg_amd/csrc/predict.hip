@@ -34,9 +34,10 @@ __host__ __device__ inline int pt_stride(int n) {
   return ((q & 1) ? q : q + 1) << 2;
 }
 
-// F.interpolate(bilinear, align_corners=False): src = (dst + 0.5) * in/out - 0.5, clamped at 0 (evalops.hip:102-107)
+// F.interpolate(bilinear, align_corners=False): src = (dst + 0.5) * in/out - 0.5, clamped at 0 (evalops.hip:102-107).  The
+// fma is what the compiler contracted the expression to at every call; written out, so that it stays one rule for both kernels
 __device__ __forceinline__ void src_coord(int d, float scale, int in, int* i0, int* i1, float* l) {
-  const float s = fmaxf(((float)d + 0.5f) * scale - 0.5f, 0.f);
+  const float s = fmaxf(__builtin_fmaf((float)d + 0.5f, scale, -0.5f), 0.f);
   *i0 = min((int)s, in - 1);
   *i1 = min(*i0 + 1, in - 1);
   *l = s - (float)*i0;
@@ -47,8 +48,11 @@ struct Best {
   int c;
 };
 
-// one class of one pixel: the flat four-weight rule, first maximum wins
+// one class of one pixel: the flat four-weight rule, first maximum wins.  Four rounded products, added in order: contraction
+// is off here, because which of the products the compiler fuses into an fma depends on the code around the call, and the two
+// kernels of this file have to give the same bits for the same view
 __device__ __forceinline__ float blend(float w00, float w01, float w10, float w11, float a, float b, float c, float d) {
+#pragma clang fp contract(off)
   return w00 * a + w01 * b + w10 * c + w11 * d;
 }
 
@@ -99,6 +103,40 @@ __device__ __forceinline__ void class_loop(Ptr base, int n, int o0, int o1, cons
       if (probs && ok[j]) probs[(long long)c * cstride + pofs[j]] = v;
     }
   }
+}
+
+// phase 2 of both kernels: the 16 x 64 label / conf tile of image b at (X0, Y0) leaves LDS in wide, aligned stores
+__device__ __forceinline__ void store_tile(const int (&t_lab)[PT_ROWS][PT_COLS], const float (&t_conf)[PT_ROWS][PT_COLS], int b,
+                                           int X0, int Y0, int xend, int h, int w, void* __restrict__ labels, int label_bytes,
+                                           float* __restrict__ conf) {
+  // 16 lanes per row; lane k takes the aligned quad at X0 - a + 4k, lanes k < a also one pixel of the last a
+  const int r = threadIdx.x >> 4, k = threadIdx.x & 15, y = Y0 + r;
+  if (y >= h) return;
+  const long long row = ((long long)b * h + y) * w;
+  const int a = (int)((row + X0) & 3);
+  unsigned char* l8 = (unsigned char*)labels;
+  short* l16 = (short*)labels;
+  auto put = [&](int xx) {
+    const int v = t_lab[r][xx - X0];
+    if (label_bytes == 1) l8[row + xx] = (unsigned char)v; else l16[row + xx] = (short)v;
+    if (conf) conf[row + xx] = t_conf[r][xx - X0];
+  };
+  const int xs = X0 - a + 4 * k;
+  if (xs >= X0 && xs + 4 <= xend) {
+    const int* tl = &t_lab[r][xs - X0];
+    if (label_bytes == 1)
+      *reinterpret_cast<uint32_t*>(l8 + row + xs) = (uint32_t)tl[0] | ((uint32_t)tl[1] << 8) | ((uint32_t)tl[2] << 16) | ((uint32_t)tl[3] << 24);
+    else
+      *reinterpret_cast<uint2*>(l16 + row + xs) = make_uint2((uint32_t)tl[0] | ((uint32_t)tl[1] << 16), (uint32_t)tl[2] | ((uint32_t)tl[3] << 16));
+    if (conf) {
+      const float* tc = &t_conf[r][xs - X0];
+      *reinterpret_cast<float4*>(conf + row + xs) = make_float4(tc[0], tc[1], tc[2], tc[3]);
+    }
+  } else {
+    for (int e = 0; e < 4; ++e)
+      if (xs + e >= X0 && xs + e < xend) put(xs + e);
+  }
+  if (k < a && X0 + PT_COLS - a + k < xend) put(X0 + PT_COLS - a + k);
 }
 
 __global__ __launch_bounds__(256) void seg_predict_kernel(const float* __restrict__ scores, int hp, int wp, int n, int h, int w,
@@ -169,34 +207,206 @@ __global__ __launch_bounds__(256) void seg_predict_kernel(const float* __restric
   for (int j = 0; j < 4; ++j) { t_lab[wave * 4 + j][lane] = best[j].c; t_conf[wave * 4 + j][lane] = best[j].v; }
   __syncthreads();
 
-  // phase 2: 16 lanes per row; lane k takes the aligned quad at X0 - a + 4k, lanes k < a also one pixel of the last a
-  const int r = threadIdx.x >> 4, k = threadIdx.x & 15, y = Y0 + r;
-  if (y >= h) return;
-  const long long row = ((long long)b * h + y) * w;
-  const int a = (int)((row + X0) & 3);
-  unsigned char* l8 = (unsigned char*)labels;
-  short* l16 = (short*)labels;
-  auto put = [&](int xx) {
-    const int v = t_lab[r][xx - X0];
-    if (label_bytes == 1) l8[row + xx] = (unsigned char)v; else l16[row + xx] = (short)v;
-    if (conf) conf[row + xx] = t_conf[r][xx - X0];
-  };
-  const int xs = X0 - a + 4 * k;
-  if (xs >= X0 && xs + 4 <= xend) {
-    const int* tl = &t_lab[r][xs - X0];
-    if (label_bytes == 1)
-      *reinterpret_cast<uint32_t*>(l8 + row + xs) = (uint32_t)tl[0] | ((uint32_t)tl[1] << 8) | ((uint32_t)tl[2] << 16) | ((uint32_t)tl[3] << 24);
-    else
-      *reinterpret_cast<uint2*>(l16 + row + xs) = make_uint2((uint32_t)tl[0] | ((uint32_t)tl[1] << 16), (uint32_t)tl[2] | ((uint32_t)tl[3] << 16));
-    if (conf) {
-      const float* tc = &t_conf[r][xs - X0];
-      *reinterpret_cast<float4*>(conf + row + xs) = make_float4(tc[0], tc[1], tc[2], tc[3]);
+  // phase 2
+  store_tile(t_lab, t_conf, b, X0, Y0, xend, h, w, labels, label_bytes, conf);
+}
+
+// ---- K views of different grids into one label map (multi-scale + flip test-time augmentation) ----
+// The tile, the lane mapping and phase 2 are those of seg_predict_kernel.  The classes are walked in chunks of PV_CHUNK: per
+// chunk the footprints of all views are staged side by side in LDS (PV_CHUNK floats per patch at the odd-slot stride), then a
+// wave takes its four rows one after the other, and per row the view loop runs innermost and adds each view's flat
+// four-weight value into the row's PV_CHUNK registers, in view order.  The running maximum of a pixel lives in the label / conf
+// tile between the chunks.  A flipped view is staged in its mirrored (logical) column order, so the inner loop is the same for
+// both.  Views are given LDS in order while the buffer lasts; a view that no longer fits reads global memory in the same loop.
+// The source coordinates of a view under the tile do not depend on the class: they are worked out once, as offsets into
+// the view's staged footprint (or its grid in global memory), and kept in LDS, PV_COORDS dwords per view.
+constexpr int PV_MAX_VIEWS = 16, PV_CHUNK = 16, PV_STRIDE = 20;   // PV_STRIDE == pt_stride(PV_CHUNK)
+constexpr int PV_COORDS = 3 * PT_COLS + 3 * PT_ROWS;              // per view: o0, o1, lx per column; r0, r1, ly per row
+constexpr int PV_META_LDS = 1024;                                 // >= sizeof(ViewMeta) * PV_MAX_VIEWS
+constexpr int PV_STAGE_LIMIT = 65536 - PT_TILE_LDS - PV_META_LDS; // coordinates + staged footprints
+
+int g_views_stage_limit = PV_STAGE_LIMIT;
+
+struct ViewTable {
+  ifseg_predict_view v[PV_MAX_VIEWS];
+};
+
+// one view under one tile; off: its first float in the staging buffer, < 0 when it reads global memory
+struct ViewMeta {
+  const float* base;      // the image's grid
+  int hp, wp, flip, ylo, xlo, fw, cells, off;
+};
+static_assert(sizeof(ViewMeta) * PV_MAX_VIEWS <= PV_META_LDS, "PV_META_LDS");
+
+// four consecutive classes of one patch: a 16-byte LDS read, or (global memory) single reads of the classes below cn
+template <bool VEC>
+__device__ __forceinline__ f32x4 quad(const float* p, int c, int cn) {
+  if (VEC) return *reinterpret_cast<const f32x4*>(p + c);
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (c + k < cn) v[k] = p[c + k];
+  return v;
+}
+
+// blend for four consecutive classes at once, element by element the same operations in the same order.  Written on the
+// vectors, so that the compiler packs two classes into one instruction and not the two products of one class, whose sum
+// would then be an addition across the halves of a register pair (tools/check_isa.py)
+__device__ __forceinline__ f32x4 blend4(float w00, float w01, float w10, float w11, f32x4 a, f32x4 b, f32x4 c, f32x4 d) {
+#pragma clang fp contract(off)
+  return w00 * a + w01 * b + w10 * c + w11 * d;
+}
+
+// acc[c] += the view's value of class c at one pixel, whose four patches start at p00 .. p11
+template <bool VEC>
+__device__ __forceinline__ void add_view(const float* p00, const float* p01, const float* p10, const float* p11, int cn, float ly,
+                                         float lx, f32x4 (&acc)[PV_CHUNK / 4]) {
+  // the empty asm keeps 1 - ly and 1 - lx in registers of their own: computed as a pair, their product is a packed multiply
+  // that reads across the halves of the pair (tools/check_isa.py again)
+  float my = 1.f - ly, mx = 1.f - lx;
+  asm("" : "+v"(my), "+v"(mx));
+  const float w00 = my * mx, w01 = my * lx, w10 = ly * mx, w11 = ly * lx;
+#pragma unroll
+  for (int c = 0; c < PV_CHUNK; c += 4) {
+    if (VEC || c < cn) {
+      const f32x4 a = quad<VEC>(p00, c, cn), b = quad<VEC>(p01, c, cn), d = quad<VEC>(p10, c, cn), e = quad<VEC>(p11, c, cn);
+      acc[c >> 2] += blend4(w00, w01, w10, w11, a, b, d, e);
     }
-  } else {
-    for (int e = 0; e < 4; ++e)
-      if (xs + e >= X0 && xs + e < xend) put(xs + e);
   }
-  if (k < a && X0 + PT_COLS - a + k < xend) put(X0 + PT_COLS - a + k);
+}
+
+__global__ __launch_bounds__(256) void seg_predict_views_kernel(ViewTable views, int K, float inv_k, int n, int h, int w,
+                                                                int tiles_x, int tiles_y, void* __restrict__ labels,
+                                                                int label_bytes, float* __restrict__ conf,
+                                                                float* __restrict__ probs, int stage_floats) {
+  extern __shared__ __attribute__((aligned(16))) float dyn[];     // K * PV_COORDS coordinates, then stage_floats of footprints
+  __shared__ int t_lab[PT_ROWS][PT_COLS];
+  __shared__ float t_conf[PT_ROWS][PT_COLS];
+  __shared__ ViewMeta vm[PV_MAX_VIEWS];
+  int* coords = reinterpret_cast<int*>(dyn);
+  float* stage = dyn + K * PV_COORDS;
+
+  const int tx = blockIdx.x % tiles_x, ty = (blockIdx.x / tiles_x) % tiles_y, b = blockIdx.x / (tiles_x * tiles_y);
+  const int X0 = tx * PT_COLS, Y0 = ty * PT_ROWS;
+  const int xend = min(X0 + PT_COLS, w), yend = min(Y0 + PT_ROWS, h);
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+
+  // every view's footprint under this tile, in the view's logical (un-mirrored) columns: thread k takes view k (picked by a
+  // chain of selects: the table is a kernel argument, and indexing it by a variable would move it to private memory)
+  if (threadIdx.x < K) {
+    ifseg_predict_view v = views.v[0];
+#pragma unroll
+    for (int i = 1; i < PV_MAX_VIEWS; ++i)
+      if (threadIdx.x == i) v = views.v[i];
+    const float sy = (float)v.hp / (float)h, sx = (float)v.wp / (float)w;
+    int ylo, yhi, xlo, xhi, t0;
+    float tf;
+    src_coord(Y0, sy, v.hp, &ylo, &t0, &tf);
+    src_coord(yend - 1, sy, v.hp, &t0, &yhi, &tf);
+    src_coord(X0, sx, v.wp, &xlo, &t0, &tf);
+    src_coord(xend - 1, sx, v.wp, &t0, &xhi, &tf);
+    ViewMeta& m = vm[threadIdx.x];
+    m.base = v.scores + (long long)b * v.hp * v.wp * n;
+    m.hp = v.hp; m.wp = v.wp; m.flip = v.flip;
+    m.ylo = ylo; m.xlo = xlo; m.fw = xhi - xlo + 1; m.cells = (yhi - ylo + 1) * m.fw;
+  }
+  __syncthreads();
+  // its place in the staging buffer: in view order, while the buffer lasts
+  if (threadIdx.x == 0) {
+    int used = 0;
+    for (int k = 0; k < K; ++k) {
+      const long long need = (long long)vm[k].cells * PV_STRIDE;
+      const bool fits = need <= (long long)(stage_floats - used);
+      vm[k].off = fits ? used : -1;
+      if (fits) used += (int)need;
+    }
+  }
+  __syncthreads();
+  // the coordinates of the tile's 64 columns and 16 rows in every view, as float offsets from the view's base: into its staged
+  // footprint, or into its grid (below 2^31: hp wp < 2^22, n <= 512), there with the mirroring applied
+  for (int i = threadIdx.x; i < K * (PT_COLS + PT_ROWS); i += 256) {
+    const int k = i / (PT_COLS + PT_ROWS), r = i - k * (PT_COLS + PT_ROWS);
+    const ViewMeta& m = vm[k];
+    int* cv = coords + k * PV_COORDS;
+    int i0, i1;
+    float l;
+    if (r < PT_COLS) {
+      src_coord(min(X0 + r, w - 1), (float)m.wp / (float)w, m.wp, &i0, &i1, &l);
+      if (m.off >= 0) { i0 = (i0 - m.xlo) * PV_STRIDE; i1 = (i1 - m.xlo) * PV_STRIDE; }
+      else { i0 = (m.flip ? m.wp - 1 - i0 : i0) * n; i1 = (m.flip ? m.wp - 1 - i1 : i1) * n; }
+      cv[r] = i0; cv[PT_COLS + r] = i1; cv[2 * PT_COLS + r] = __float_as_int(l);
+    } else {
+      const int rr = r - PT_COLS, rowlen = m.off >= 0 ? m.fw * PV_STRIDE : m.wp * n;
+      src_coord(min(Y0 + rr, h - 1), (float)m.hp / (float)h, m.hp, &i0, &i1, &l);
+      if (m.off >= 0) { i0 -= m.ylo; i1 -= m.ylo; }
+      int* cr = cv + 3 * PT_COLS;
+      cr[rr] = i0 * rowlen; cr[PT_ROWS + rr] = i1 * rowlen; cr[2 * PT_ROWS + rr] = __float_as_int(l);
+    }
+  }
+
+  const int x = min(X0 + lane, w - 1);
+  float* pb = probs ? probs + (long long)b * n * h * w : nullptr;
+  const long long cstride = (long long)h * w;
+
+  for (int c0 = 0; c0 < n; c0 += PV_CHUNK) {
+    const int cn = min(PV_CHUNK, n - c0);
+    if (c0) __syncthreads();                      // the previous chunk has been read
+    // phase 0: 16 threads per patch, one class each; the classes past n are zero
+    for (int k = 0; k < K; ++k) {
+      const int off = vm[k].off;
+      if (off < 0) continue;
+      const float* base = vm[k].base + c0;
+      const int wp = vm[k].wp, flip = vm[k].flip, ylo = vm[k].ylo, xlo = vm[k].xlo, fw = vm[k].fw, cells = vm[k].cells;
+      const int cc = threadIdx.x & 15;
+      for (int p = threadIdx.x >> 4; p < cells; p += 16) {
+        const int ry = p / fw, col = xlo + p - ry * fw;
+        const long long src = ((long long)(ylo + ry) * wp + (flip ? wp - 1 - col : col)) * n;
+        stage[off + p * PV_STRIDE + cc] = cc < cn ? base[src + cc] : 0.f;
+      }
+    }
+    __syncthreads();                              // (the first one publishes the coordinates as well)
+
+    // phase 1, row by row.  -0 is the neutral element of the addition: -0 + v == v for every v, the sign of a zero included
+#pragma unroll 1
+    for (int j = 0; j < 4; ++j) {
+      const int row = wave * 4 + j, yr = Y0 + row;
+      f32x4 acc[PV_CHUNK / 4];
+#pragma unroll
+      for (int c = 0; c < PV_CHUNK / 4; ++c) acc[c] = f32x4{-0.f, -0.f, -0.f, -0.f};
+      for (int k = 0; k < K; ++k) {
+        const int* cv = coords + k * PV_COORDS;
+        const int o0 = cv[lane], o1 = cv[PT_COLS + lane];
+        const float lx = __int_as_float(cv[2 * PT_COLS + lane]);
+        const int r0 = cv[3 * PT_COLS + row], r1 = cv[3 * PT_COLS + PT_ROWS + row];
+        const float ly = __int_as_float(cv[3 * PT_COLS + 2 * PT_ROWS + row]);
+        const int off = __builtin_amdgcn_readfirstlane(vm[k].off);
+        if (off >= 0) {
+          const float* s = stage + off;
+          add_view<true>(s + r0 + o0, s + r0 + o1, s + r1 + o0, s + r1 + o1, cn, ly, lx, acc);
+        } else {
+          const float* s = vm[k].base + c0;
+          add_view<false>(s + r0 + o0, s + r0 + o1, s + r1 + o0, s + r1 + o1, cn, ly, lx, acc);
+        }
+      }
+      float bv = c0 ? t_conf[row][lane] : -INFINITY;
+      int bc = c0 ? t_lab[row][lane] : 0;
+      const bool ok = yr < h && X0 + lane < w;
+      float* pp = pb + (long long)c0 * cstride + min(yr, h - 1) * w + x;
+#pragma unroll
+      for (int c = 0; c < PV_CHUNK; ++c) {
+        if (c < cn) {
+          const float v = acc[c >> 2][c & 3] * inv_k;
+          if (v > bv) { bv = v; bc = c0 + c; }
+          if (pb && ok) pp[c * cstride] = v;
+        }
+      }
+      t_conf[row][lane] = bv; t_lab[row][lane] = bc;
+    }
+  }
+  __syncthreads();
+
+  // phase 2
+  store_tile(t_lab, t_conf, b, X0, Y0, xend, h, w, labels, label_bytes, conf);
 }
 
 }  // namespace
@@ -226,6 +436,43 @@ extern "C" int ifseg_seg_predict(const float* scores, int B, int hp, int wp, int
   const int lds = (int)std::min<long long>(need, g_stage_limit) & ~15;
   hipLaunchKernelGGL(seg_predict_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, scores, hp, wp, n, h, w,
                      tiles_x, tiles_y, labels, label_bytes, conf, probs, lds / 4);
+  IFSEG_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ifseg_seg_predict_views_staging(int max_bytes) {
+  const int prev = g_views_stage_limit;
+  g_views_stage_limit = max_bytes < 0 ? PV_STAGE_LIMIT : (max_bytes < PV_STAGE_LIMIT ? max_bytes : PV_STAGE_LIMIT);
+  return prev;
+}
+
+extern "C" int ifseg_seg_predict_views(const ifseg_predict_view* views, int K, int B, int n, int h, int w, void* labels,
+                                       int label_bytes, float* conf, float* probs, void* stream) {
+  (void)hipGetLastError();
+  if (!views || K < 1 || K > PV_MAX_VIEWS || !labels || (label_bytes != 1 && label_bytes != 2)) return IFSEG_ERR_BAD_ARG;
+  if (n < 1 || n > PT_MAX_CLASSES || (label_bytes == 1 && n > 256)) return IFSEG_ERR_BAD_ARG;
+  if (B < 1 || h < 1 || w < 1 || (long long)B * h * w >= (1ll << 31)) return IFSEG_ERR_BAD_SHAPE;
+  if (((size_t)labels & 15) || ((size_t)conf & 15) || ((size_t)probs & 3)) return IFSEG_ERR_BAD_ARG;
+  const int tiles_x = (w + PT_COLS - 1) / PT_COLS, tiles_y = (h + PT_ROWS - 1) / PT_ROWS;
+  const long long blocks = (long long)tiles_x * tiles_y * B;
+  if (blocks >= (1ll << 31)) return IFSEG_ERR_BAD_SHAPE;
+  ViewTable table = {};
+  long long need = 0;
+  for (int k = 0; k < K; ++k) {
+    const ifseg_predict_view& v = views[k];
+    if (!v.scores || ((size_t)v.scores & 3)) return IFSEG_ERR_BAD_ARG;
+    if (v.hp < 1 || v.wp < 1 || (long long)v.hp * v.wp >= (1ll << 31) / PT_MAX_CLASSES) return IFSEG_ERR_BAD_SHAPE;
+    table.v[k] = v;
+    table.v[k].flip = v.flip != 0;
+    // the bound of ifseg_seg_predict on any tile's footprint, per view
+    const long long fh = std::min<long long>(v.hp, (long long)PT_ROWS * v.hp / h + 3), fw = std::min<long long>(v.wp, (long long)PT_COLS * v.wp / w + 3);
+    need += fh * fw * PV_STRIDE * 4;
+  }
+  // the coordinates come first; what the limit leaves is the staging buffer
+  const int coords = K * PV_COORDS * 4;
+  const int stage = (int)std::min<long long>(need, std::max(g_views_stage_limit - coords, 0)) & ~15;
+  hipLaunchKernelGGL(seg_predict_views_kernel, dim3((unsigned)blocks), dim3(256), coords + stage, (hipStream_t)stream, table, K,
+                     (float)(1.0 / K), n, h, w, tiles_x, tiles_y, labels, label_bytes, conf, probs, stage / 4);
   IFSEG_CHECK_LAUNCH();
   return 0;
 }

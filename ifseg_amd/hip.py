@@ -1051,7 +1051,51 @@ def seg_predict(scores, hp, wp, h, w, conf=False, probs=False, staging_bytes=Non
     return labels, cf, pr
 
 
-_image_luts = {}          # (mean, std, device) -> fp32 [3, 256] on the device; at most 16 entries
+SEG_PREDICT_MAX_VIEWS = 16
+
+
+class _PredictView(ctypes.Structure):
+    _fields_ = [("scores", c_void_p), ("hp", c_int), ("wp", c_int), ("flip", c_int)]
+
+
+def seg_predict_views(views, h, w, conf=False, probs=False, staging_bytes=None, label_dtype=None):
+    """views: a list of 1 .. 16 (scores fp32 [B, hp*wp, n], hp, wp, flip), one per forward of the same images at its own grid;
+    flip: the network saw the image mirrored along its width -> (labels, conf, probs) as `seg_predict`, of the MEAN of the
+    views: each is resized to h x w by seg_predict's rule (a flipped one on its mirrored columns), the values are added in
+    fp32 in view order and multiplied by float(1 / K), in one launch (csrc/predict.hip); `predict.upsample_views_reference` is
+    the specification.  One unflipped view gives seg_predict's outputs bit for bit.  The view table is a kernel argument:
+    nothing is copied to the device.  staging_bytes, label_dtype: as in `seg_predict`."""
+    views = list(views)
+    assert 1 <= len(views) <= SEG_PREDICT_MAX_VIEWS, len(views)
+    for k, (scores, hp, wp, flip) in enumerate(views):
+        assert scores.dtype == torch.float32 and scores.dim() == 3 and scores.is_contiguous(), (k, scores.dtype, tuple(scores.shape), scores.stride())
+    B, _, n = views[0][0].shape
+    dev = views[0][0].device
+    table = (_PredictView * len(views))()
+    for k, (scores, hp, wp, flip) in enumerate(views):
+        assert scores.shape[0] == B and scores.shape[2] == n and scores.device == dev, (k, tuple(scores.shape), B, n)
+        assert scores.shape[1] == hp * wp and hp >= 1 and wp >= 1, (k, tuple(scores.shape), hp, wp)
+        table[k] = _PredictView(_ptr(scores), int(hp), int(wp), 1 if flip else 0)
+    assert B >= 1 and h >= 1 and w >= 1, (B, h, w)
+    assert 1 <= n <= SEG_PREDICT_MAX_CLASSES, n
+    assert B * h * w < 2 ** 31, (B, h, w)
+    if label_dtype is None:
+        label_dtype = torch.uint8 if n <= 256 else torch.int16
+    assert label_dtype in (torch.uint8, torch.int16) and (n <= 256 or label_dtype == torch.int16), (label_dtype, n)
+    labels = torch.empty(B, h, w, dtype=label_dtype, device=dev)
+    cf = torch.empty(B, h, w, dtype=torch.float32, device=dev) if conf else None
+    pr = torch.empty(B, n, h, w, dtype=torch.float32, device=dev) if probs else None
+    prev = lib().ifseg_seg_predict_views_staging(c_int(staging_bytes)) if staging_bytes is not None else None
+    try:
+        _check(lib().ifseg_seg_predict_views(table, c_int(len(views)), c_int(B), c_int(n), c_int(h), c_int(w), _ptr(labels),
+                                             c_int(labels.element_size()), _ptr(cf), _ptr(pr), _stream()), "seg_predict_views")
+    finally:
+        if prev is not None:
+            lib().ifseg_seg_predict_views_staging(c_int(prev))
+    return labels, cf, pr
+
+
+_image_luts = {}         # (mean, std, device) -> fp32 [3, 256] on the device; at most 16 entries
 
 
 def image_load(images_u8, oh, ow, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), reverse_channels=False, dtype=torch.float32,

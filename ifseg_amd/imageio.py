@@ -1,5 +1,5 @@
 """The reference's evaluation transform for raw images: sizes, the CPU specification of `hip.image_load`, and the grouping
-of `Segmenter.segment_raw`.  Needs no GPU to import.
+of `Segmenter.segment_raw` (`plan_views`; `plan_groups` is its single-view form).  Needs no GPU to import.
 
 The reference evaluates an image as it comes off disk (segmentation_dataset.py:169-172,218,256):
 `MultiScaleFlipAug(img_scale=(4 P, P), flip=False, [Resize(keep_ratio=True), ...])` resizes it so that the short side is at
@@ -16,12 +16,18 @@ IMAGENET_DEFAULT_STD = (0.229, 0.224, 0.225)
 HALF = (0.5, 0.5, 0.5)
 
 
-def eval_size(h, w, patch_image_size):
-    """-> (oh, ow): mmcv's `rescale_size((w, h), (4 P, P))` in Python floats"""
+def eval_size(h, w, patch_image_size, ratio=1.0):
+    """-> (oh, ow): mmcv's `rescale_size((w, h), (int(4 P ratio), int(P ratio)))` in Python floats.  `ratio` is one entry of
+    `MultiScaleFlipAug(img_ratios=...)`, which scales the pair before `Resize(keep_ratio=True)` sees it."""
     P = int(patch_image_size)
     if h < 1 or w < 1 or P < 1:
         raise ValueError("eval_size: h, w and patch_image_size must be >= 1, got %r %r %r" % (h, w, patch_image_size))
-    s = min(4 * P / max(h, w), P / min(h, w))
+    if not ratio > 0:
+        raise ValueError("eval_size: ratio must be > 0, got %r" % (ratio,))
+    long_side, short_side = int(4 * P * ratio), int(P * ratio)
+    if short_side < 1:
+        raise ValueError("eval_size: int(patch_image_size * ratio) = int(%d * %r) is below 1" % (P, ratio))
+    s = min(long_side / max(h, w), short_side / min(h, w))
     return int(h * s + 0.5), int(w * s + 0.5)
 
 
@@ -86,7 +92,8 @@ def image_load_reference(images_u8, oh, ow, mean=HALF, std=HALF, reverse_channel
 
 
 def plan_groups(shapes, patch_image_size, max_batch=8):
-    """The launches of Segmenter.segment_raw for images of the given (H, W) shapes, as a pure function:
+    """The launches of Segmenter.segment_raw for images of the given (H, W) shapes at one view per image (`plan_views` with its
+    default arguments gives the same plan), as a pure function:
     -> (loads, forwards).  loads: [((H, W), (oh, ow), [indices])], one `image_load` launch per distinct source shape, in order
     of first appearance; forwards: [((oh, ow), [indices])], one model forward per entry: images of equal network size in
     input order, at most `max_batch` of them."""
@@ -100,3 +107,43 @@ def plan_groups(shapes, patch_image_size, max_batch=8):
         by_size.setdefault(size, []).append(i)
     forwards = [(size, idx[k:k + max_batch]) for size, idx in by_size.items() for k in range(0, len(idx), max_batch)]
     return [(hw, size, idx) for hw, (size, idx) in loads.items()], forwards
+
+
+MAX_VIEWS = 16
+
+
+def view_list(scales=(1.0,), flip=False):
+    """-> [(ratio, flipped)]: the views of one image in mmseg's MultiScaleFlipAug order -- per ratio, in the order given, the
+    unflipped view and then, with `flip`, the mirrored one"""
+    scales = [float(r) for r in scales]
+    if not scales or any(not r > 0 for r in scales):
+        raise ValueError("segment_raw: scales must be a non-empty sequence of ratios > 0, got %r" % (scales,))
+    views = [(r, f) for r in scales for f in ((False, True) if flip else (False,))]
+    if len(views) > MAX_VIEWS:
+        raise ValueError("segment_raw: %d views (%d scales%s), hip.seg_predict_views takes at most %d"
+                         % (len(views), len(scales), " x 2 flips" if flip else "", MAX_VIEWS))
+    return views
+
+
+def plan_views(shapes, patch_image_size, scales=(1.0,), flip=False, max_batch=8):
+    """`plan_groups` for multi-scale + flip inference, as a pure function: -> (views, loads, forwards).
+    views: `view_list(scales, flip)`; view v of image i is the pair (i, v).
+    loads: [((H, W), (oh, ow), [image indices])], one `image_load` launch per distinct (source shape, network size), in order
+    of first appearance -- a mirrored view is the loaded tensor flipped, and ratios that give one size share the load.
+    forwards: [((oh, ow), [(i, v)])], one model forward per entry: the views of equal network size, mirrored or not, in
+    (image, view) order, at most `max_batch` of them; the entries of one size follow each other, so the engine meets every
+    size once."""
+    if max_batch < 1:
+        raise ValueError("segment_raw: max_batch must be >= 1, got %r" % (max_batch,))
+    views = view_list(scales, flip)
+    loads, by_size = {}, {}
+    for i, (h, w) in enumerate(shapes):
+        h, w = int(h), int(w)
+        for v, (ratio, _) in enumerate(views):
+            size = eval_size(h, w, patch_image_size, ratio)
+            idx = loads.setdefault(((h, w), size), [])
+            if i not in idx:
+                idx.append(i)
+            by_size.setdefault(size, []).append((i, v))
+    forwards = [(size, iv[k:k + max_batch]) for size, iv in by_size.items() for k in range(0, len(iv), max_batch)]
+    return views, [(hw, size, idx) for (hw, size), idx in loads.items()], forwards

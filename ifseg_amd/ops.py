@@ -18,7 +18,8 @@ The second half of the file puts the training-path kernels there as well (see th
 `attention_bias` (the bias is an ordinary tensor with a gradient), `bias_attention_bi` (bias_attention on the batch-inner
 kernels, with key counts and attention dropout) and `seg_loss` (csrc/loss.hip), with `*_bwd` ops of their own;
 `ifseg_amd.modules.MultiheadAttention` composes `linear` and `attention_bias` under the reference module's parameter names.
-`seg_predict` (csrc/predict.hip: label maps at image resolution) and `image_load` (csrc/imgload.hip: raw uint8 images to
+`seg_predict` (csrc/predict.hip: label maps at image resolution), `seg_predict_views` (the same from the mean of K views of
+differing grids, mirrored ones included: multi-scale + flip inference) and `image_load` (csrc/imgload.hip: raw uint8 images to
 normalised patch_images, the reference's evaluation transform) are inference only and have no backward; `train_load`
 (csrc/trainload.hip: raw images and label maps of any sizes to a training batch under given records, the reference's training
 transform) has integer inputs and no backward either.
@@ -706,6 +707,58 @@ def _(scores, hp, wp, h, w, want_conf, want_probs):
     f32 = torch.float32
     return (scores.new_empty(B, h, w, dtype=ldt), scores.new_empty((B, h, w) if want_conf else (0,), dtype=f32),
             scores.new_empty((B, n, h, w) if want_probs else (0,), dtype=f32))
+
+
+# ----------------------------------------------------------------------------------------------- seg_predict_views
+def _seg_predict_views_check(scores, hps, wps, flips, h, w):
+    op = "ifseg::seg_predict_views"
+    K = len(scores)
+    if K < 1 or K > hip.SEG_PREDICT_MAX_VIEWS:
+        raise ValueError("%s: %d views, the kernel takes 1 .. %d" % (op, K, hip.SEG_PREDICT_MAX_VIEWS))
+    if len(hps) != K or len(wps) != K or len(flips) != K:
+        raise ValueError("%s: %d views with %d hps, %d wps and %d flips (one of each per view)" % (op, K, len(hps), len(wps), len(flips)))
+    for k, (s, hp, wp) in enumerate(zip(scores, hps, wps)):
+        if s.dtype != torch.float32:
+            raise ValueError("%s: scores must be fp32 (hip.rows_to_f32 / hip.neighbour_smoothing give it), view %d has dtype %s" % (op, k, s.dtype))
+        if s.dim() != 3:
+            raise ValueError("%s: scores must be [B, hp*wp, n], view %d is %s" % (op, k, tuple(s.shape)))
+        if s.shape[0] != scores[0].shape[0] or s.shape[2] != scores[0].shape[2]:
+            raise ValueError("%s: all views share B and n, view %d is %s against %s" % (op, k, tuple(s.shape), tuple(scores[0].shape)))
+        if hp <= 0 or wp <= 0 or s.shape[1] != hp * wp:
+            raise ValueError("%s: view %d: scores.shape[1] = %d, expected hp * wp = %d" % (op, k, s.shape[1], hp * wp))
+    B, _, n = scores[0].shape
+    if B == 0:
+        raise ValueError("%s: empty batch" % op)
+    if n < 1 or n > SEG_LOSS_MAX_CLASSES:
+        raise ValueError("%s: n = %d classes, the kernel takes 1 .. FUSED_MAX_CLASSES = %d" % (op, n, SEG_LOSS_MAX_CLASSES))
+    if h < 1 or w < 1 or B * h * w >= 2 ** 31:
+        raise ValueError("%s: the label map [%d, %d, %d] must have 1 <= h, w and B * h * w < 2**31" % (op, B, h, w))
+    return B, n, (torch.uint8 if n <= 256 else torch.int16)
+
+
+@custom_op("ifseg::seg_predict_views", mutates_args=(), device_types="cuda")
+def seg_predict_views(scores: Sequence[torch.Tensor], hps: Sequence[int], wps: Sequence[int], flips: Sequence[bool], h: int, w: int,
+                      want_conf: bool, want_probs: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """label map at h x w from K views of the same images (csrc/predict.hip): view k is fp32 [B, hps[k]*wps[k], n], mirrored
+    along the width when flips[k]; every view is resized as `seg_predict` does, the mean over the views (fp32, in view order)
+    is what labels, conf and probs are taken from, in one launch.  Outputs and conventions as `seg_predict`.  Not differentiable."""
+    _seg_predict_views_check(scores, hps, wps, flips, h, w)
+    prev = _stream_scope(scores[0])
+    try:
+        views = [(s.contiguous(), hp, wp, bool(f)) for s, hp, wp, f in zip(scores, hps, wps, flips)]
+        labels, conf, probs = hip.seg_predict_views(views, h, w, conf=want_conf, probs=want_probs)
+        e = lambda t: torch.empty(0, dtype=torch.float32, device=scores[0].device) if t is None else t
+        return labels, e(conf), e(probs)
+    finally:
+        hip.set_stream(prev)
+
+
+@seg_predict_views.register_fake
+def _(scores, hps, wps, flips, h, w, want_conf, want_probs):
+    B, n, ldt = _seg_predict_views_check(scores, hps, wps, flips, h, w)
+    f32, s = torch.float32, scores[0]
+    return (s.new_empty(B, h, w, dtype=ldt), s.new_empty((B, h, w) if want_conf else (0,), dtype=f32),
+            s.new_empty((B, n, h, w) if want_probs else (0,), dtype=f32))
 
 
 # ----------------------------------------------------------------------------------------------- image_load

@@ -11,6 +11,15 @@ or the caller asks for them.
     res.labels                                        # uint8 (int16 above 256 classes) [B, H, W], on the device
     out = seg.segment_raw(photos)                     # uint8 RGB [H, W, 3] images of ANY size, one or a list: the reference's
     out[i].labels                                     # evaluation transform on the device (hip.image_load), labels [H_i, W_i]
+    out = seg.segment_raw(photos, scales=(0.5, 0.75, 1.0, 1.25, 1.5, 1.75), flip=True)      # "ms+flip", see below
+
+Multi-scale + flip (mmseg's `MultiScaleFlipAug(img_ratios=scales, flip=True)`, the setting mIoU tables call "ms+flip"): every
+image is loaded once per ratio at `imageio.eval_size(H, W, P, ratio)`, mirrored views are the loaded tensor flipped, each view
+runs the same forward (and smoothing), and ONE launch of `hip.seg_predict_views` resizes the K per-patch score grids to the
+image's shape, un-mirrors, averages and takes the argmax: no [n, H, W] tensor per view is written or added.  The reference
+never turns this on, so there is no golden for it: parity is to the specification `upsample_views_reference`.  Cost: every
+distinct view size is one more entry of the engine's resized-bias cache (`engine.py:_resized_biases`), whose entries grow
+with the square of the grid; the views are therefore run size by size (`imageio.plan_views`).
 
 Nothing in the call synchronises with the host; `labels`, `conf` and `probs` stay on the device.  There is no CPU fallback:
 `upsample_argmax_reference` is the specification the tests compare against, not a second implementation of the path.
@@ -21,7 +30,7 @@ import torch
 import torch.nn.functional as F
 
 from . import hip
-from .imageio import HALF, eval_size, plan_groups
+from .imageio import HALF, eval_size, plan_views, view_list
 from .tasks.mm_tasks.segmentation import BOS, EOS, PROMPT_IDS
 
 MAX_CLASSES = hip.SEG_PREDICT_MAX_CLASSES
@@ -41,6 +50,26 @@ def upsample_argmax_reference(scores, hp, wp, h, w, dtype=torch.float64):
     assert P == hp * wp, (tuple(scores.shape), hp, wp)
     grid = scores.to(dtype).transpose(1, 2).reshape(B, n, hp, wp)
     probs = F.interpolate(grid, size=(h, w), mode="bilinear", align_corners=False)
+    labels = probs.argmax(dim=1)
+    return labels, probs.gather(1, labels[:, None]).squeeze(1), probs
+
+
+def upsample_views_reference(views, h, w, dtype=torch.float64):
+    """CPU specification of hip.seg_predict_views: `views` is a list of (scores [B, hp*wp, n], hp, wp, flip).  View k is
+    reshaped to [B, n, hp, wp], its columns reversed if `flip` (a permutation, in front of the resize: the network saw the
+    mirrored image), resized with F.interpolate(bilinear, align_corners=False) in `dtype`; the K results are added in the
+    order k = 0 .. K-1 and multiplied by 1 / K rounded to `dtype`; labels are the first maximum.
+    -> (labels int64 [B, h, w], conf [B, h, w], probs [B, n, h, w]) as `upsample_argmax_reference`.  Runs on any device."""
+    total = None
+    for scores, hp, wp, flip in views:
+        B, P, n = scores.shape
+        assert P == hp * wp, (tuple(scores.shape), hp, wp)
+        grid = scores.to(dtype).transpose(1, 2).reshape(B, n, hp, wp)
+        if flip:
+            grid = grid.flip(-1)
+        up = F.interpolate(grid, size=(h, w), mode="bilinear", align_corners=False)
+        total = up if total is None else total + up
+    probs = total * torch.tensor(1.0 / len(views), dtype=dtype, device=total.device)
     labels = probs.argmax(dim=1)
     return labels, probs.gather(1, labels[:, None]).squeeze(1), probs
 
@@ -165,9 +194,20 @@ class Segmenter:
 
     def _finish(self, scores, hp, wp, h, w, rgb, return_conf, return_probs):
         crf = self.crf_iters > 0
-        labels, conf, probs = hip.seg_predict(scores, hp, wp, h, w, conf=return_conf and not crf, probs=return_probs or crf,
-                                              label_dtype=self.label_dtype)
-        if crf:
+        out = hip.seg_predict(scores, hp, wp, h, w, conf=return_conf and not crf, probs=return_probs or crf,
+                              label_dtype=self.label_dtype)
+        return self._crf(out, rgb, return_conf, return_probs)
+
+    def _finish_views(self, views, h, w, rgb, return_conf, return_probs):
+        """`_finish` on the mean of K views (scores, hp, wp, flip) of the same images"""
+        crf = self.crf_iters > 0
+        out = hip.seg_predict_views(views, h, w, conf=return_conf and not crf, probs=return_probs or crf,
+                                    label_dtype=self.label_dtype)
+        return self._crf(out, rgb, return_conf, return_probs)
+
+    def _crf(self, out, rgb, return_conf, return_probs):
+        labels, conf, probs = out
+        if self.crf_iters > 0:
             from .crf import rgb_dense_crf
             q = torch.stack([rgb_dense_crf(rgb[b], probs[b], self.crf_iters) for b in range(probs.shape[0])])
             labels = q.argmax(1).to(labels.dtype)
@@ -194,7 +234,7 @@ class Segmenter:
 
     # -- raw images of any size ----------------------------------------------------------
     def segment_raw(self, images, max_batch=8, mean=None, std=None, reverse_channels=False, return_conf=False,
-                    return_probs=False):
+                    return_probs=False, scales=(1.0,), flip=False):
         """Raw images in, as they come off disk: one uint8 RGB [H, W, 3] tensor or a list of them, of differing shapes, on the
         host or the device -> a list of SegmentationResult in input order, image i with labels [H_i, W_i] (conf [H_i, W_i],
         probs [n, H_i, W_i]) on the device.
@@ -209,9 +249,21 @@ class Segmenter:
         the image's own shape, as the reference scores at `ori_shape`.
 
         Images of equal source shape share one `image_load` launch, images of equal network size one forward of at most
-        `max_batch` (`imageio.plan_groups`).  With the CRF on, the ORIGINAL image is the CRF image, in RGB, not reversed.
+        `max_batch` (`imageio.plan_views`).  With the CRF on, the ORIGINAL image is the CRF image, in RGB, not reversed.
         With device images nothing synchronises with the host, after the first call per (mean, std), which copies the
-        normalisation table to the device."""
+        normalisation table to the device.
+
+        scales, flip: mmseg's `MultiScaleFlipAug(img_ratios=scales, flip=flip)`.  The views of an image are, per ratio in the
+        order given, the image at `eval_size(H, W, P, ratio)` and then, with `flip`, that tensor mirrored along its width
+        (mirrored after the resize, as mmseg does); each runs the forward above, views of equal network size sharing it
+        (`imageio.plan_views`), and `hip.seg_predict_views` turns the views of an image into one label map at [H_i, W_i]: the
+        mean of the resized, un-mirrored scores, which is also what the CRF takes.  At most 16 views; more than one view
+        needs upsample="probs" (averaging raw logits is not mmseg's rule).  The default is the single view above: the same
+        launches as without these arguments, `hip.seg_predict` at the end."""
+        views = view_list(scales, flip)
+        if len(views) > 1 and self.upsample != "probs":
+            raise ValueError("Segmenter.segment_raw: %d views need upsample='probs' (mmseg averages the resized probabilities; "
+                             "averaging raw logits is not its rule), this Segmenter has upsample=%r" % (len(views), self.upsample))
         single = torch.is_tensor(images)
         imgs = [images] if single else list(images)
         if not imgs:
@@ -224,18 +276,23 @@ class Segmenter:
         dev = next(self.model.parameters()).device
         imgs = [im.to(dev, non_blocking=True) for im in imgs]
         shapes = [(int(im.shape[0]), int(im.shape[1])) for im in imgs]
-        loads, forwards = plan_groups(shapes, self.model.cfg.patch_image_size, max_batch)
+        _, loads, forwards = plan_views(shapes, self.model.cfg.patch_image_size, scales, flip, max_batch)
         crf = self.crf_iters > 0
-        x, out = [None] * len(imgs), [None] * len(imgs)
+        x, per_image, out = {}, [[None] * len(views) for _ in imgs], []
         with torch.no_grad():
-            for _, (oh, ow), idx in loads:
-                t = hip.image_load(torch.stack([imgs[i] for i in idx]), oh, ow, mean, std, reverse_channels)
+            for _, size, idx in loads:
+                t = hip.image_load(torch.stack([imgs[i] for i in idx]), size[0], size[1], mean, std, reverse_channels)
                 for k, i in enumerate(idx):
-                    x[i] = t[k]
-            for _, idx in forwards:
-                scores, hp, wp = self.patch_scores(torch.stack([x[i] for i in idx]))
-                for k, i in enumerate(idx):
-                    r = self._finish(scores[k:k + 1], hp, wp, shapes[i][0], shapes[i][1], imgs[i][None].float() if crf else None,
-                                     return_conf, return_probs)
-                    out[i] = SegmentationResult(*(None if t is None else t[0] for t in r))
+                    x[i, size] = t[k]
+            for size, iv in forwards:
+                scores, hp, wp = self.patch_scores(torch.stack([x[i, size].flip(-1) if views[v][1] else x[i, size] for i, v in iv]))
+                for k, (i, v) in enumerate(iv):
+                    per_image[i][v] = (scores[k:k + 1], hp, wp, views[v][1])
+            for i, vs in enumerate(per_image):
+                (H, W), rgb = shapes[i], imgs[i][None].float() if crf else None
+                if len(vs) == 1 and not vs[0][3]:             # one plain view: the single-view kernel
+                    r = self._finish(*vs[0][:3], H, W, rgb, return_conf, return_probs)
+                else:
+                    r = self._finish_views(vs, H, W, rgb, return_conf, return_probs)
+                out.append(SegmentationResult(*(None if t is None else t[0] for t in r)))
         return out

@@ -559,6 +559,31 @@ int ifseg_seg_predict(const float* scores, int B, int hp, int wp, int n, int h, 
                       float* conf, float* probs, void* stream);
 int ifseg_seg_predict_staging(int max_bytes);
 
+/* ---- K views into one label map (Segmenter.segment_raw(scales=..., flip=...): mmseg's MultiScaleFlipAug with img_ratios and
+ * flip, the "ms+flip" evaluation) ----
+ * A view is the score grid [B, hp*wp, n] of one forward at one scale; flip != 0 says that the network saw the image mirrored
+ * along its width, so the view's logical column x is the grid's column wp-1-x. */
+typedef struct {
+  const float* scores; /* device, fp32 [B, hp*wp, n], class fastest, 4-byte aligned */
+  int hp, wp, flip;
+} ifseg_predict_view;
+/* ifseg_seg_predict_views resizes every view to [B, h, w] by ifseg_seg_predict's rule (coordinates and the flat four-weight
+ * value v_c per view, on the view's logical columns), adds the K values of a class in fp32 in view order, multiplies by
+ * (float)(1.0 / K) and writes labels / conf / probs of that mean exactly as ifseg_seg_predict does (first maximum; conf and
+ * probs may be NULL).  With K = 1 and flip = 0 the three outputs are bit-identical to ifseg_seg_predict's.
+ * `views` is a HOST array of K entries; it travels as a kernel argument, so the call copies nothing to the device and does
+ * not synchronise.  All views share B and n.  One launch, no atomics, no scratch buffer, and no [n, h, w] intermediate unless
+ * probs is given.
+ * NULL views / labels / a view's scores, K outside 1..16, n outside 1..512, label_bytes other than 1 or 2 (1 only for n <= 256),
+ * labels / conf not 16-byte aligned: IFSEG_ERR_BAD_ARG.  B, h, w, a view's hp, wp < 1, B*h*w >= 2^31, a view's
+ * hp*wp >= 2^22: IFSEG_ERR_BAD_SHAPE.
+ * A workgroup owns 16 x 64 pixels and walks the classes in chunks of 16; per chunk it stages the footprints of the views in
+ * LDS, in view order while the buffer lasts, and a view that does not fit reads global memory (same values).
+ * ifseg_seg_predict_views_staging sets the size of that buffer like ifseg_seg_predict_staging, for this entry point only. */
+int ifseg_seg_predict_views(const ifseg_predict_view* views, int K, int B, int n, int h, int w, void* labels, int label_bytes,
+                            float* conf, float* probs, void* stream);
+int ifseg_seg_predict_views_staging(int max_bytes);
+
 /* ---- raw images in (ifseg_amd/predict.py Segmenter.segment_raw; the reference's evaluation transform: Resize(keep_ratio),
  * Normalize of :148-156; the dataset's two channel reversals, :218 and :256, cancel, so reverse_channels is 0 for a
  * checkpoint tuned by the reference) ----
