@@ -60,7 +60,7 @@ import numpy as np
 import torch
 
 from .artificial import _M64, splitmix64
-from .imageio import HALF, normalisation_table, source_coords
+from .imageio import HALF, normalisation_table, resize_to_grey, source_coords
 
 RECORD = 16
 (R_NEW_H, R_NEW_W, R_OFF_H, R_OFF_W, R_K, R_FLIP, R_BRIGHT, R_CONTRAST, R_SAT, R_HUE, R_MODE, R_BETA, R_ALPHA_C, R_ALPHA_S,
@@ -268,14 +268,8 @@ def train_load_reference(images, labels, params, P, nseg, seg_id_offset, mean=HA
         new_h, new_w, off_h, off_w = check_record(rec, H0, W0, P)
         ys = off_h + torch.arange(P)
         xs = off_w + (torch.arange(P - 1, -1, -1) if rec[R_FLIP] else torch.arange(P))
-        y0, y1, ly = (v[ys] for v in source_coords(new_h, H0, dtype))
-        x0, x1, lx = (v[xs] for v in source_coords(new_w, W0, dtype))
-        src = img.permute(2, 0, 1).to(dtype)
-        ly, lx = ly[:, None], lx[None, :]
-        top, bot = src[:, y0], src[:, y1]
-        v = ((1 - ly) * (1 - lx)) * top[..., x0] + ((1 - ly) * lx) * top[..., x1] + (ly * (1 - lx)) * bot[..., x0] \
-            + (ly * lx) * bot[..., x1]
-        q0 = (v + 0.5).floor().clamp(0, 255).to(torch.uint8).permute(1, 2, 0).contiguous()
+        q0 = resize_to_grey(img.permute(2, 0, 1).to(dtype), [v[ys] for v in source_coords(new_h, H0, dtype)],
+                            [v[xs] for v in source_coords(new_w, W0, dtype)])[0].permute(1, 2, 0).contiguous()
         q = torch.from_numpy(photometric(q0.numpy(), rec))
         q0s.append(q0)
         qs.append(q)

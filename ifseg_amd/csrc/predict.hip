@@ -3,7 +3,8 @@
 // argmax over the classes (first maximum), optionally the winning value and every interpolated value, in one pass: the
 // [n, h, w] tensor is only written when the caller asks for it.
 //
-// A workgroup of 256 threads owns a tile of 16 rows x 64 pixels.
+// A workgroup of 256 threads owns a tile of 16 rows x 64 pixels (the tile decode, the coordinate rule and the footprint on top of
+// it are tile.h's).
 //   phase 0  the patch rows the tile touches (3 x 6 patches at x16) are copied to LDS once, each padded to a stride of an ODD
 //            number of 16-byte slots: the 16 slots of a bank row then hold 16 consecutive patches, so lanes of one ds_read_b128
 //            that sit in different patches hit different banks for every n (n % 64 == 0 included) and lanes in the same patch
@@ -16,14 +17,15 @@
 //            four pixels of a 4-ALIGNED element quad of the flat [B, h, w] index, so the wide stores are aligned whatever w is;
 //            the up to three pixels in front of the first whole quad and behind the last one leave as single elements.
 // No atomics, no scratch buffer, static launch shape, nothing read back.
-#include <algorithm>
-#include "common.h"
+#include "tile.h"
 #include "../../include/ifseg_hip.h"
 
 namespace {
 
-constexpr int PT_ROWS = 16, PT_COLS = 64, PT_MAX_CLASSES = 512;
-constexpr int PT_TILE_LDS = PT_ROWS * PT_COLS * 8;                // the label + conf tile of phase 2
+using namespace tile;
+
+constexpr int PT_MAX_CLASSES = 512;
+constexpr int PT_TILE_LDS = TILE_ROWS * TILE_COLS * 8;            // the label + conf tile of phase 2
 constexpr int PT_STAGE_LIMIT = 65536 - PT_TILE_LDS;               // 64 KiB of LDS per workgroup in all
 
 int g_stage_limit = PT_STAGE_LIMIT;
@@ -32,15 +34,6 @@ int g_stage_limit = PT_STAGE_LIMIT;
 __host__ __device__ inline int pt_stride(int n) {
   const int q = (n + 3) >> 2;
   return ((q & 1) ? q : q + 1) << 2;
-}
-
-// F.interpolate(bilinear, align_corners=False): src = (dst + 0.5) * in/out - 0.5, clamped at 0 (evalops.hip:102-107).  The
-// fma is what the compiler contracted the expression to at every call; written out, so that it stays one rule for both kernels
-__device__ __forceinline__ void src_coord(int d, float scale, int in, int* i0, int* i1, float* l) {
-  const float s = fmaxf(__builtin_fmaf((float)d + 0.5f, scale, -0.5f), 0.f);
-  *i0 = min((int)s, in - 1);
-  *i1 = min(*i0 + 1, in - 1);
-  *l = s - (float)*i0;
 }
 
 struct Best {
@@ -106,9 +99,9 @@ __device__ __forceinline__ void class_loop(Ptr base, int n, int o0, int o1, cons
 }
 
 // phase 2 of both kernels: the 16 x 64 label / conf tile of image b at (X0, Y0) leaves LDS in wide, aligned stores
-__device__ __forceinline__ void store_tile(const int (&t_lab)[PT_ROWS][PT_COLS], const float (&t_conf)[PT_ROWS][PT_COLS], int b,
-                                           int X0, int Y0, int xend, int h, int w, void* __restrict__ labels, int label_bytes,
-                                           float* __restrict__ conf) {
+__device__ __forceinline__ void store_tile(const int (&t_lab)[TILE_ROWS][TILE_COLS], const float (&t_conf)[TILE_ROWS][TILE_COLS],
+                                           int b, int X0, int Y0, int xend, int h, int w, void* __restrict__ labels,
+                                           int label_bytes, float* __restrict__ conf) {
   // 16 lanes per row; lane k takes the aligned quad at X0 - a + 4k, lanes k < a also one pixel of the last a
   const int r = threadIdx.x >> 4, k = threadIdx.x & 15, y = Y0 + r;
   if (y >= h) return;
@@ -136,7 +129,7 @@ __device__ __forceinline__ void store_tile(const int (&t_lab)[PT_ROWS][PT_COLS],
     for (int e = 0; e < 4; ++e)
       if (xs + e >= X0 && xs + e < xend) put(xs + e);
   }
-  if (k < a && X0 + PT_COLS - a + k < xend) put(X0 + PT_COLS - a + k);
+  if (k < a && X0 + TILE_COLS - a + k < xend) put(X0 + TILE_COLS - a + k);
 }
 
 __global__ __launch_bounds__(256) void seg_predict_kernel(const float* __restrict__ scores, int hp, int wp, int n, int h, int w,
@@ -144,23 +137,16 @@ __global__ __launch_bounds__(256) void seg_predict_kernel(const float* __restric
                                                           float* __restrict__ conf, float* __restrict__ probs,
                                                           int stage_floats) {
   extern __shared__ __attribute__((aligned(16))) float stage[];
-  __shared__ int t_lab[PT_ROWS][PT_COLS];
-  __shared__ float t_conf[PT_ROWS][PT_COLS];
+  __shared__ int t_lab[TILE_ROWS][TILE_COLS];
+  __shared__ float t_conf[TILE_ROWS][TILE_COLS];
 
-  const int tx = blockIdx.x % tiles_x, ty = (blockIdx.x / tiles_x) % tiles_y, b = blockIdx.x / (tiles_x * tiles_y);
-  const int X0 = tx * PT_COLS, Y0 = ty * PT_ROWS;
-  const int xend = min(X0 + PT_COLS, w), yend = min(Y0 + PT_ROWS, h);
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const float sy = (float)hp / (float)h, sx = (float)wp / (float)w;
+  const auto [b, X0, Y0, xend, yend, lane, wave] = tile_decode(tiles_x, tiles_y, h, w);
+  const FloatCoord cy{(float)hp / (float)h, hp}, cx{(float)wp / (float)w, wp};
   const float* sb = scores + (long long)b * hp * wp * n;
 
-  // the tile's footprint: source coordinates are monotone in the destination, so the first and the last pixel bound it
-  int ylo, yhi, xlo, xhi, t0;
-  float tf;
-  src_coord(Y0, sy, hp, &ylo, &t0, &tf);
-  src_coord(yend - 1, sy, hp, &t0, &yhi, &tf);
-  src_coord(X0, sx, wp, &xlo, &t0, &tf);
-  src_coord(xend - 1, sx, wp, &t0, &xhi, &tf);
+  int ylo, yhi, xlo, xhi;
+  footprint(cy, Y0, yend - 1, &ylo, &yhi);
+  footprint(cx, X0, xend - 1, &xlo, &xhi);
   const int fh = yhi - ylo + 1, fw = xhi - xlo + 1, stride = pt_stride(n);
   const bool staged = (long long)fh * fw * stride <= (long long)stage_floats;       // workgroup-uniform
   if (staged) {
@@ -177,7 +163,7 @@ __global__ __launch_bounds__(256) void seg_predict_kernel(const float* __restric
   const int x = min(X0 + lane, w - 1);
   int x0, x1;
   float lx;
-  src_coord(x, sx, wp, &x0, &x1, &lx);
+  cx(x, &x0, &x1, &lx);
   int y0[4], y1[4];
   float ly[4];
   bool fresh[4], ok[4];
@@ -185,7 +171,7 @@ __global__ __launch_bounds__(256) void seg_predict_kernel(const float* __restric
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int yr = Y0 + wave * 4 + j, y = min(yr, h - 1);
-    src_coord(y, sy, hp, &y0[j], &y1[j], &ly[j]);
+    cy(y, &y0[j], &y1[j], &ly[j]);
     fresh[j] = j == 0 || y0[j] != y0[j - 1] || y1[j] != y1[j - 1];
     ok[j] = yr < h && X0 + lane < w;
     pofs[j] = y * w + x;
@@ -221,7 +207,7 @@ __global__ __launch_bounds__(256) void seg_predict_kernel(const float* __restric
 // The source coordinates of a view under the tile do not depend on the class: they are worked out once, as offsets into
 // the view's staged footprint (or its grid in global memory), and kept in LDS, PV_COORDS dwords per view.
 constexpr int PV_MAX_VIEWS = 16, PV_CHUNK = 16, PV_STRIDE = 20;   // PV_STRIDE == pt_stride(PV_CHUNK)
-constexpr int PV_COORDS = 3 * PT_COLS + 3 * PT_ROWS;              // per view: o0, o1, lx per column; r0, r1, ly per row
+constexpr int PV_COORDS = 3 * TILE_COLS + 3 * TILE_ROWS;          // per view: o0, o1, lx per column; r0, r1, ly per row
 constexpr int PV_META_LDS = 1024;                                 // >= sizeof(ViewMeta) * PV_MAX_VIEWS
 constexpr int PV_STAGE_LIMIT = 65536 - PT_TILE_LDS - PV_META_LDS; // coordinates + staged footprints
 
@@ -280,16 +266,13 @@ __global__ __launch_bounds__(256) void seg_predict_views_kernel(ViewTable views,
                                                                 int label_bytes, float* __restrict__ conf,
                                                                 float* __restrict__ probs, int stage_floats) {
   extern __shared__ __attribute__((aligned(16))) float dyn[];     // K * PV_COORDS coordinates, then stage_floats of footprints
-  __shared__ int t_lab[PT_ROWS][PT_COLS];
-  __shared__ float t_conf[PT_ROWS][PT_COLS];
+  __shared__ int t_lab[TILE_ROWS][TILE_COLS];
+  __shared__ float t_conf[TILE_ROWS][TILE_COLS];
   __shared__ ViewMeta vm[PV_MAX_VIEWS];
   int* coords = reinterpret_cast<int*>(dyn);
   float* stage = dyn + K * PV_COORDS;
 
-  const int tx = blockIdx.x % tiles_x, ty = (blockIdx.x / tiles_x) % tiles_y, b = blockIdx.x / (tiles_x * tiles_y);
-  const int X0 = tx * PT_COLS, Y0 = ty * PT_ROWS;
-  const int xend = min(X0 + PT_COLS, w), yend = min(Y0 + PT_ROWS, h);
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const auto [b, X0, Y0, xend, yend, lane, wave] = tile_decode(tiles_x, tiles_y, h, w);
 
   // every view's footprint under this tile, in the view's logical (un-mirrored) columns: thread k takes view k (picked by a
   // chain of selects: the table is a kernel argument, and indexing it by a variable would move it to private memory)
@@ -298,13 +281,9 @@ __global__ __launch_bounds__(256) void seg_predict_views_kernel(ViewTable views,
 #pragma unroll
     for (int i = 1; i < PV_MAX_VIEWS; ++i)
       if (threadIdx.x == i) v = views.v[i];
-    const float sy = (float)v.hp / (float)h, sx = (float)v.wp / (float)w;
-    int ylo, yhi, xlo, xhi, t0;
-    float tf;
-    src_coord(Y0, sy, v.hp, &ylo, &t0, &tf);
-    src_coord(yend - 1, sy, v.hp, &t0, &yhi, &tf);
-    src_coord(X0, sx, v.wp, &xlo, &t0, &tf);
-    src_coord(xend - 1, sx, v.wp, &t0, &xhi, &tf);
+    int ylo, yhi, xlo, xhi;
+    footprint(FloatCoord{(float)v.hp / (float)h, v.hp}, Y0, yend - 1, &ylo, &yhi);
+    footprint(FloatCoord{(float)v.wp / (float)w, v.wp}, X0, xend - 1, &xlo, &xhi);
     ViewMeta& m = vm[threadIdx.x];
     m.base = v.scores + (long long)b * v.hp * v.wp * n;
     m.hp = v.hp; m.wp = v.wp; m.flip = v.flip;
@@ -324,23 +303,23 @@ __global__ __launch_bounds__(256) void seg_predict_views_kernel(ViewTable views,
   __syncthreads();
   // the coordinates of the tile's 64 columns and 16 rows in every view, as float offsets from the view's base: into its staged
   // footprint, or into its grid (below 2^31: hp wp < 2^22, n <= 512), there with the mirroring applied
-  for (int i = threadIdx.x; i < K * (PT_COLS + PT_ROWS); i += 256) {
-    const int k = i / (PT_COLS + PT_ROWS), r = i - k * (PT_COLS + PT_ROWS);
+  for (int i = threadIdx.x; i < K * (TILE_COLS + TILE_ROWS); i += 256) {
+    const int k = i / (TILE_COLS + TILE_ROWS), r = i - k * (TILE_COLS + TILE_ROWS);
     const ViewMeta& m = vm[k];
     int* cv = coords + k * PV_COORDS;
     int i0, i1;
     float l;
-    if (r < PT_COLS) {
-      src_coord(min(X0 + r, w - 1), (float)m.wp / (float)w, m.wp, &i0, &i1, &l);
+    if (r < TILE_COLS) {
+      FloatCoord{(float)m.wp / (float)w, m.wp}(min(X0 + r, w - 1), &i0, &i1, &l);
       if (m.off >= 0) { i0 = (i0 - m.xlo) * PV_STRIDE; i1 = (i1 - m.xlo) * PV_STRIDE; }
       else { i0 = (m.flip ? m.wp - 1 - i0 : i0) * n; i1 = (m.flip ? m.wp - 1 - i1 : i1) * n; }
-      cv[r] = i0; cv[PT_COLS + r] = i1; cv[2 * PT_COLS + r] = __float_as_int(l);
+      cv[r] = i0; cv[TILE_COLS + r] = i1; cv[2 * TILE_COLS + r] = __float_as_int(l);
     } else {
-      const int rr = r - PT_COLS, rowlen = m.off >= 0 ? m.fw * PV_STRIDE : m.wp * n;
-      src_coord(min(Y0 + rr, h - 1), (float)m.hp / (float)h, m.hp, &i0, &i1, &l);
+      const int rr = r - TILE_COLS, rowlen = m.off >= 0 ? m.fw * PV_STRIDE : m.wp * n;
+      FloatCoord{(float)m.hp / (float)h, m.hp}(min(Y0 + rr, h - 1), &i0, &i1, &l);
       if (m.off >= 0) { i0 -= m.ylo; i1 -= m.ylo; }
-      int* cr = cv + 3 * PT_COLS;
-      cr[rr] = i0 * rowlen; cr[PT_ROWS + rr] = i1 * rowlen; cr[2 * PT_ROWS + rr] = __float_as_int(l);
+      int* cr = cv + 3 * TILE_COLS;
+      cr[rr] = i0 * rowlen; cr[TILE_ROWS + rr] = i1 * rowlen; cr[2 * TILE_ROWS + rr] = __float_as_int(l);
     }
   }
 
@@ -375,10 +354,10 @@ __global__ __launch_bounds__(256) void seg_predict_views_kernel(ViewTable views,
       for (int c = 0; c < PV_CHUNK / 4; ++c) acc[c] = f32x4{-0.f, -0.f, -0.f, -0.f};
       for (int k = 0; k < K; ++k) {
         const int* cv = coords + k * PV_COORDS;
-        const int o0 = cv[lane], o1 = cv[PT_COLS + lane];
-        const float lx = __int_as_float(cv[2 * PT_COLS + lane]);
-        const int r0 = cv[3 * PT_COLS + row], r1 = cv[3 * PT_COLS + PT_ROWS + row];
-        const float ly = __int_as_float(cv[3 * PT_COLS + 2 * PT_ROWS + row]);
+        const int o0 = cv[lane], o1 = cv[TILE_COLS + lane];
+        const float lx = __int_as_float(cv[2 * TILE_COLS + lane]);
+        const int r0 = cv[3 * TILE_COLS + row], r1 = cv[3 * TILE_COLS + TILE_ROWS + row];
+        const float ly = __int_as_float(cv[3 * TILE_COLS + 2 * TILE_ROWS + row]);
         const int off = __builtin_amdgcn_readfirstlane(vm[k].off);
         if (off >= 0) {
           const float* s = stage + off;
@@ -411,11 +390,7 @@ __global__ __launch_bounds__(256) void seg_predict_views_kernel(ViewTable views,
 
 }  // namespace
 
-extern "C" int ifseg_seg_predict_staging(int max_bytes) {
-  const int prev = g_stage_limit;
-  g_stage_limit = max_bytes < 0 ? PT_STAGE_LIMIT : (max_bytes < PT_STAGE_LIMIT ? max_bytes : PT_STAGE_LIMIT);
-  return prev;
-}
+extern "C" int ifseg_seg_predict_staging(int max_bytes) { return swap_limit(g_stage_limit, PT_STAGE_LIMIT, max_bytes); }
 
 extern "C" int ifseg_seg_predict(const float* scores, int B, int hp, int wp, int n, int h, int w, void* labels, int label_bytes,
                                  float* conf, float* probs, void* stream) {
@@ -426,13 +401,10 @@ extern "C" int ifseg_seg_predict(const float* scores, int B, int hp, int wp, int
   if ((long long)B * h * w >= (1ll << 31) || (long long)hp * wp >= (1ll << 31) / PT_MAX_CLASSES) return IFSEG_ERR_BAD_SHAPE;
   // the wide stores of phase 2 want 16-byte aligned bases
   if (((size_t)labels & 15) || ((size_t)conf & 15) || ((size_t)scores & 3) || ((size_t)probs & 3)) return IFSEG_ERR_BAD_ARG;
-  const int tiles_x = (w + PT_COLS - 1) / PT_COLS, tiles_y = (h + PT_ROWS - 1) / PT_ROWS;
-  const long long blocks = (long long)tiles_x * tiles_y * B;
-  if (blocks >= (1ll << 31)) return IFSEG_ERR_BAD_SHAPE;
-  // an upper bound of any tile's footprint: R destination rows span at most floor((R - 1) in/out) + 1 source rows, + 1 for the
-  // lower neighbour, + 1 for the rounding of the coordinate
-  const long long fh = std::min<long long>(hp, (long long)PT_ROWS * hp / h + 3), fw = std::min<long long>(wp, (long long)PT_COLS * wp / w + 3);
-  const long long need = fh * fw * pt_stride(n) * 4;
+  int tiles_x, tiles_y;
+  long long blocks;
+  if (!tile_grid(h, w, B, &tiles_x, &tiles_y, &blocks)) return IFSEG_ERR_BAD_SHAPE;
+  const long long need = footprint_bound(hp, hp, h, TILE_ROWS, 3) * footprint_bound(wp, wp, w, TILE_COLS, 3) * pt_stride(n) * 4;
   const int lds = (int)std::min<long long>(need, g_stage_limit) & ~15;
   hipLaunchKernelGGL(seg_predict_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, scores, hp, wp, n, h, w,
                      tiles_x, tiles_y, labels, label_bytes, conf, probs, lds / 4);
@@ -441,9 +413,7 @@ extern "C" int ifseg_seg_predict(const float* scores, int B, int hp, int wp, int
 }
 
 extern "C" int ifseg_seg_predict_views_staging(int max_bytes) {
-  const int prev = g_views_stage_limit;
-  g_views_stage_limit = max_bytes < 0 ? PV_STAGE_LIMIT : (max_bytes < PV_STAGE_LIMIT ? max_bytes : PV_STAGE_LIMIT);
-  return prev;
+  return swap_limit(g_views_stage_limit, PV_STAGE_LIMIT, max_bytes);
 }
 
 extern "C" int ifseg_seg_predict_views(const ifseg_predict_view* views, int K, int B, int n, int h, int w, void* labels,
@@ -453,9 +423,9 @@ extern "C" int ifseg_seg_predict_views(const ifseg_predict_view* views, int K, i
   if (n < 1 || n > PT_MAX_CLASSES || (label_bytes == 1 && n > 256)) return IFSEG_ERR_BAD_ARG;
   if (B < 1 || h < 1 || w < 1 || (long long)B * h * w >= (1ll << 31)) return IFSEG_ERR_BAD_SHAPE;
   if (((size_t)labels & 15) || ((size_t)conf & 15) || ((size_t)probs & 3)) return IFSEG_ERR_BAD_ARG;
-  const int tiles_x = (w + PT_COLS - 1) / PT_COLS, tiles_y = (h + PT_ROWS - 1) / PT_ROWS;
-  const long long blocks = (long long)tiles_x * tiles_y * B;
-  if (blocks >= (1ll << 31)) return IFSEG_ERR_BAD_SHAPE;
+  int tiles_x, tiles_y;
+  long long blocks;
+  if (!tile_grid(h, w, B, &tiles_x, &tiles_y, &blocks)) return IFSEG_ERR_BAD_SHAPE;
   ViewTable table = {};
   long long need = 0;
   for (int k = 0; k < K; ++k) {
@@ -464,9 +434,7 @@ extern "C" int ifseg_seg_predict_views(const ifseg_predict_view* views, int K, i
     if (v.hp < 1 || v.wp < 1 || (long long)v.hp * v.wp >= (1ll << 31) / PT_MAX_CLASSES) return IFSEG_ERR_BAD_SHAPE;
     table.v[k] = v;
     table.v[k].flip = v.flip != 0;
-    // the bound of ifseg_seg_predict on any tile's footprint, per view
-    const long long fh = std::min<long long>(v.hp, (long long)PT_ROWS * v.hp / h + 3), fw = std::min<long long>(v.wp, (long long)PT_COLS * v.wp / w + 3);
-    need += fh * fw * PV_STRIDE * 4;
+    need += footprint_bound(v.hp, v.hp, h, TILE_ROWS, 3) * footprint_bound(v.wp, v.wp, w, TILE_COLS, 3) * PV_STRIDE * 4;
   }
   // the coordinates come first; what the limit leaves is the staging buffer
   const int coords = K * PV_COORDS * 4;

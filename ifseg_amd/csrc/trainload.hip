@@ -9,28 +9,27 @@
 //                      4 max < 3 P^2 into slot 15 of the record with ONE global integer atomicAdd that also counts the
 //                      arrivals; the workgroup that arrives tenth holds all ten verdicts in the value the atomic returned,
 //                      picks the first good candidate (else candidate 10) and writes the record.
-//   ifseg_train_load   one launch per batch whatever the source shapes, csrc/imgload.hip's shape: a 256-thread workgroup owns a
-//                      16 x 64 output tile, a thread a pixel with its three channels.  The source footprint of the tile is staged
-//                      in LDS with aligned dword loads where it fits, else read from global memory.  Per pixel: 12 byte taps ->
-//                      grey levels q -> the photometric chain in registers (integers, and convert() as ONE fp32 operation) ->
-//                      table -> three coalesced plane stores (bf16: pairs); one nearest label tap -> one int64 target store.
+//   ifseg_train_load   one launch per batch whatever the source shapes, csrc/imgload.hip's shape and code (tile.h): a 256-thread
+//                      workgroup owns a 16 x 64 output tile, a thread a pixel with its three channels.  The source footprint of
+//                      the tile is staged in LDS with aligned dword loads where it fits, else read from global memory.  Per
+//                      pixel: 12 byte taps -> grey levels q -> the photometric chain in registers, tile.h's pixel hook (integers,
+//                      and convert() as ONE fp32 operation) -> table -> three coalesced plane stores (bf16: pairs); one nearest
+//                      label tap -> one int64 target store.
 //                      A record that does not hold a P x P window (only a caller's own records can) poisons its sample: NaN
 //                      images and target -1, nothing is read through it.
 // No scratch buffer, static launch shapes, nothing read back.
-#include <algorithm>
-#include "common.h"
+#include "tile.h"
 #include "../../include/ifseg_hip.h"
 
 namespace {
 
-constexpr int TL_ROWS = 16, TL_COLS = 64;
-constexpr int TL_LUT_BYTES = 3 * 256 * 4;
-constexpr int TL_STAGE_LIMIT = 65536 - TL_LUT_BYTES;
+using namespace tile;
+
 constexpr int TL_CANDIDATES = 10;                 // the checked ones; candidate 10 is taken unchecked
 constexpr int TL_MAX_P = 4096;
 constexpr int HSV_D = 7650;
 
-int g_tl_stage_limit = TL_STAGE_LIMIT;
+int g_tl_stage_limit = U8_STAGE_LIMIT;
 
 enum { R_NEW_H, R_NEW_W, R_OFF_H, R_OFF_W, R_K, R_FLIP, R_BRIGHT, R_CONTRAST, R_SAT, R_HUE, R_MODE, R_BETA, R_ALPHA_C, R_ALPHA_S,
        R_DELTA, R_ZERO };
@@ -175,57 +174,6 @@ __device__ __forceinline__ void photometric(const Photo& ph, int* r, int* g, int
 }
 
 // ------------------------------------------------------------------------------------------------------------- load
-// (2 d + 1) in - out and 2 out stay below 2^31: the kernel poisons a record with 2 in out >= 2^31
-__device__ __forceinline__ void src_coord(int d, int in, int out, int* i0, int* i1, float* l) {
-  const int num = max((2 * d + 1) * in - out, 0), den = 2 * out;
-  *i0 = min((int)((unsigned)num / (unsigned)den), in - 1);
-  *i1 = min(*i0 + 1, in - 1);
-  *l = *i0 == *i1 ? 0.f : (float)(num - *i0 * den) / (float)den;          // IEEE division: the fraction is rounded once
-}
-
-__host__ __device__ inline int tl_rstride(int fw) { return (fw * 3 + 3 + 3) & ~3; }
-
-__device__ __forceinline__ void store_plane(float* out, long long e, bool ok, float v, int, int, int) {
-  if (ok) out[e] = v;
-}
-// bf16: e = flat element index of the lane's pixel; pairs on even e
-__device__ __forceinline__ void store_plane(bf16_t* out, long long e, bool ok, float v, int lane, int x, int xend) {
-  const uint32_t h = f2bf(v);
-  const uint32_t right = (uint32_t)__shfl_down((int)h, 1);                // every lane takes part
-  if (!ok) return;
-  if ((e & 1) == 0) {
-    if (lane < TL_COLS - 1 && x + 1 < xend) *reinterpret_cast<uint32_t*>(out + e) = h | (right << 16);
-    else out[e] = (bf16_t)h;
-  } else if (lane == 0) {
-    out[e] = (bf16_t)h;
-  }
-}
-
-// the thread's four pixels (rows j = 0..3 of its wave, one x).  r0[j] / r1[j]: wave-uniform byte offset of the upper / lower
-// source row from `base`, o0 / o1: per-lane byte offset of the left / right pixel
-template <typename T, typename Ptr>
-__device__ __forceinline__ void pixel_loop(Ptr base, const long long (&r0)[4], const long long (&r1)[4], int o0, int o1,
-                                           const float (&ly)[4], float lx, const float* lut, bool rev, const Photo& ph, T* out,
-                                           const long long (&erow)[4], long long plane, const bool (&ok)[4], int lane, int x,
-                                           int xend) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float w00 = (1.f - ly[j]) * (1.f - lx), w01 = (1.f - ly[j]) * lx, w10 = ly[j] * (1.f - lx), w11 = ly[j] * lx;
-    int q[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float a = (float)base[r0[j] + o0 + c], b = (float)base[r0[j] + o1 + c];
-      const float d = (float)base[r1[j] + o0 + c], e = (float)base[r1[j] + o1 + c];
-      const float v = w00 * a + w01 * b + w10 * d + w11 * e;
-      q[c] = (int)fminf(fmaxf(floorf(v + 0.5f), 0.f), 255.f);
-    }
-    photometric(ph, &q[0], &q[1], &q[2]);
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-      store_plane(out, erow[j] + c * plane + x, ok[j], lut[c * 256 + q[rev ? 2 - c : c]], lane, x, xend);
-  }
-}
-
 template <typename T>
 __global__ __launch_bounds__(256) void train_load_kernel(const ifseg_train_src* __restrict__ tab, const int* __restrict__ params,
                                                          int P, int tiles_x, int tiles_y, int nseg, int raw, long long seg0,
@@ -233,12 +181,8 @@ __global__ __launch_bounds__(256) void train_load_kernel(const ifseg_train_src* 
                                                          T* __restrict__ out, long long* __restrict__ target, int stage_bytes) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* lut = reinterpret_cast<float*>(smem);
-  unsigned char* stage = smem + TL_LUT_BYTES;
 
-  const int tx = blockIdx.x % tiles_x, ty = (blockIdx.x / tiles_x) % tiles_y, b = blockIdx.x / (tiles_x * tiles_y);
-  const int X0 = tx * TL_COLS, Y0 = ty * TL_ROWS;
-  const int xend = min(X0 + TL_COLS, P), yend = min(Y0 + TL_ROWS, P);
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const auto [b, X0, Y0, xend, yend, lane, wave] = tile_decode(tiles_x, tiles_y, P, P);
   const ifseg_train_src s = tab[b];
   const int* rec = params + (long long)b * 16;
   const int H0 = s.H0, W0 = s.W0, nh = rec[R_NEW_H], nw = rec[R_NEW_W], offh = rec[R_OFF_H], offw = rec[R_OFF_W];
@@ -272,46 +216,27 @@ __global__ __launch_bounds__(256) void train_load_kernel(const ifseg_train_src* 
   for (int i = threadIdx.x; i < 768; i += 256) lut[i] = lut_g[i];
 
   // the tile's footprint in the source: window pixel (y, x) is pixel (offh + y, offw + xs) of the resized image, xs = x or its
-  // mirror; source coordinates are monotone, so the first and the last pixel bound the footprint
-  const int RX0 = offw + (flip ? P - xend : X0), RX1 = offw + (flip ? P - 1 - X0 : xend - 1);
-  int ylo, yhi, xlo, xhi, t0;
-  float tf;
-  src_coord(offh + Y0, H0, nh, &ylo, &t0, &tf);
-  src_coord(offh + yend - 1, H0, nh, &t0, &yhi, &tf);
-  src_coord(RX0, W0, nw, &xlo, &t0, &tf);
-  src_coord(RX1, W0, nw, &t0, &xhi, &tf);
-  const int fh = yhi - ylo + 1, fw = xhi - xlo + 1, rstride = tl_rstride(fw);
-  const bool staged = (long long)fh * rstride <= (long long)stage_bytes;            // workgroup-uniform
-  const unsigned char* sb = (const unsigned char*)s.image;
-  const unsigned char* row0 = sb + ((long long)ylo * W0 + xlo) * 3;
-  if (staged) {
-    const int dpr = rstride >> 2;
-    uint32_t* st32 = reinterpret_cast<uint32_t*>(stage);
-    for (int i = threadIdx.x; i < fh * dpr; i += 256) {
-      const int ry = i / dpr, k = i - ry * dpr;
-      const unsigned char* a = row0 + (long long)ry * W0 * 3;
-      const int sh = (int)((size_t)a & 3);
-      // aligned dwords: up to 3 bytes in front of the first pixel and behind the last one are read with them, also in front of /
-      // behind the caller's buffer (an aligned dword never crosses a page)
-      if (4 * k < sh + fw * 3) st32[i] = *reinterpret_cast<const uint32_t*>(a - sh + 4 * k);
-    }
-  }
+  // mirror.  (2 d + 1) in - out and 2 out stay below 2^31: a record with 2 in out >= 2^31 was poisoned above
+  const IntCoord cy{H0, nh}, cx{W0, nw};
+  const U8Source src = u8_stage((const unsigned char*)s.image, W0, cy, offh + Y0, offh + yend - 1, cx,
+                                offw + (flip ? P - xend : X0), offw + (flip ? P - 1 - X0 : xend - 1), smem + U8_LUT_BYTES,
+                                stage_bytes);
   __syncthreads();
 
   const int xs = offw + (flip ? P - 1 - x : x);
   int x0, x1;
   float lx;
-  src_coord(xs, W0, nw, &x0, &x1, &lx);
+  cx(xs, &x0, &x1, &lx);
   const int lsx = min((int)((long long)xs * W0 / nw), W0 - 1);
   int y0[4], y1[4];
   float ly[4];
   bool ok[4];
-  long long erow[4], r0[4], r1[4];
+  long long erow[4];
   const unsigned char* lab = (const unsigned char*)s.label;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int yr = Y0 + wave * 4 + j, y = min(yr, P - 1);
-    src_coord(offh + y, H0, nh, &y0[j], &y1[j], &ly[j]);
+    cy(offh + y, &y0[j], &y1[j], &ly[j]);
     ok[j] = yr < P && X0 + lane < P;
     erow[j] = (long long)b * 3 * plane + (long long)y * P;
     if (ok[j]) {
@@ -319,18 +244,8 @@ __global__ __launch_bounds__(256) void train_load_kernel(const ifseg_train_src* 
       tgt[(long long)y * P + x] = seg0 + remap_class(lab[(long long)lsy * W0 + lsx], nseg, raw);
     }
   }
-  if (staged) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      r0[j] = (y0[j] - ylo) * rstride + (int)((size_t)(row0 + (long long)(y0[j] - ylo) * W0 * 3) & 3);
-      r1[j] = (y1[j] - ylo) * rstride + (int)((size_t)(row0 + (long long)(y1[j] - ylo) * W0 * 3) & 3);
-    }
-    pixel_loop<T>(stage, r0, r1, (x0 - xlo) * 3, (x1 - xlo) * 3, ly, lx, lut, rev != 0, ph, out, erow, plane, ok, lane, x, xend);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { r0[j] = (long long)y0[j] * W0 * 3; r1[j] = (long long)y1[j] * W0 * 3; }
-    pixel_loop<T>(sb, r0, r1, x0 * 3, x1 * 3, ly, lx, lut, rev != 0, ph, out, erow, plane, ok, lane, x, xend);
-  }
+  u8_pixels(src, y0, y1, x0, x1, ly, lx, lut, rev != 0, [&ph](int* r, int* g, int* b) { photometric(ph, r, g, b); }, out, erow,
+            plane, ok, lane, x, xend);
 }
 
 // what both entry points ask of the host copy of the table
@@ -371,11 +286,7 @@ extern "C" int ifseg_train_draw(const ifseg_train_src* table_host, const ifseg_t
   return 0;
 }
 
-extern "C" int ifseg_train_load_staging(int max_bytes) {
-  const int prev = g_tl_stage_limit;
-  g_tl_stage_limit = max_bytes < 0 ? TL_STAGE_LIMIT : (max_bytes < TL_STAGE_LIMIT ? max_bytes : TL_STAGE_LIMIT);
-  return prev;
-}
+extern "C" int ifseg_train_load_staging(int max_bytes) { return swap_limit(g_tl_stage_limit, U8_STAGE_LIMIT, max_bytes); }
 
 extern "C" int ifseg_train_load(const ifseg_train_src* table_host, const ifseg_train_src* table, const int* params,
                                 const int* params_host, int B, int P, int nseg, int raw_labels, long long seg_id_offset,
@@ -399,19 +310,18 @@ extern "C" int ifseg_train_load(const ifseg_train_src* table_host, const ifseg_t
       if (2ll * table_host[b].H0 * r[R_NEW_H] >= lim || 2ll * table_host[b].W0 * r[R_NEW_W] >= lim) return IFSEG_ERR_BAD_SHAPE;
     }
   }
-  const int tiles_x = (P + TL_COLS - 1) / TL_COLS, tiles_y = P / TL_ROWS;
-  const long long blocks = (long long)tiles_x * tiles_y * B;
-  // an upper bound of any tile's footprint: the resized short side is at least P, so a step of the window is at most s / P
-  // source samples on either axis (the long side's rounding adds less than one sample over a tile); + 1 for the lower / right
-  // neighbour, + 1 for the rounding of the coordinate, + 1 for the long side
+  int tiles_x, tiles_y;
+  long long blocks;
+  if (!tile_grid(P, P, B, &tiles_x, &tiles_y, &blocks)) return IFSEG_ERR_BAD_SHAPE;
+  // the resized short side is at least P, so a step of the window is at most s / P source samples on either axis (the long
+  // side's rounding adds less than one sample over a tile): tile.h's bound at the ratio s / P, + 1 for the long side
   long long need = 0;
   for (int b = 0; b < B; ++b) {
     const long long H0 = table_host[b].H0, W0 = table_host[b].W0, s = std::min(H0, W0);
-    const long long fh = std::min(H0, (long long)TL_ROWS * s / P + 4), fw = std::min(W0, (long long)TL_COLS * s / P + 4);
-    need = std::max(need, fh * ((fw * 3 + 6) & ~3ll));
+    need = std::max(need, footprint_bound(H0, s, P, TILE_ROWS, 4) * u8_rstride(footprint_bound(W0, s, P, TILE_COLS, 4)));
   }
   const int stage = need > g_tl_stage_limit ? g_tl_stage_limit & ~15 : (int)((need + 15) & ~15ll);
-  const int lds = TL_LUT_BYTES + stage;
+  const int lds = U8_LUT_BYTES + stage;
   if (out_bytes == 4)
     hipLaunchKernelGGL(train_load_kernel<float>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, table, params, P,
                        tiles_x, tiles_y, nseg, raw_labels, seg_id_offset, eos, lut, reverse_channels, (float*)out, target, stage);

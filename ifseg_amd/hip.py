@@ -4,6 +4,7 @@ PyTorch tensors are used only as owners of device memory and for the current
 HIP stream; every call passes raw device pointers + sizes.  There is NO
 fallback: a missing library or a non-zero return code raises RuntimeError.
 """
+import contextlib
 import ctypes
 import os
 
@@ -1023,6 +1024,29 @@ def seg_eval(scores, hp, wp, target, h, w, seg_id_offset):
 SEG_PREDICT_MAX_CLASSES = 512
 
 
+@contextlib.contextmanager
+def _staging(setter, staging_bytes):
+    """the LDS staging limit of one kernel (an ifseg_*_staging setter) at staging_bytes for the calls inside; None: untouched"""
+    prev = setter(c_int(staging_bytes)) if staging_bytes is not None else None
+    try:
+        yield
+    finally:
+        if prev is not None:
+            setter(c_int(prev))
+
+
+def _predict_outputs(B, n, h, w, dev, conf, probs, label_dtype):
+    """-> (labels [B, h, w] uint8 for n <= 256 else int16, or `label_dtype`; conf fp32 [B, h, w] or None; probs fp32 [B, n, h, w]
+    or None), uninitialised"""
+    if label_dtype is None:
+        label_dtype = torch.uint8 if n <= 256 else torch.int16
+    assert label_dtype in (torch.uint8, torch.int16) and (n <= 256 or label_dtype == torch.int16), (label_dtype, n)
+    labels = torch.empty(B, h, w, dtype=label_dtype, device=dev)
+    cf = torch.empty(B, h, w, dtype=torch.float32, device=dev) if conf else None
+    pr = torch.empty(B, n, h, w, dtype=torch.float32, device=dev) if probs else None
+    return labels, cf, pr
+
+
 def seg_predict(scores, hp, wp, h, w, conf=False, probs=False, staging_bytes=None, label_dtype=None):
     """scores fp32 [B, hp*wp, n] (class fastest: what rows_to_f32 / neighbour_smoothing return) -> (labels [B, h, w], uint8 for
     n <= 256 else int16; conf fp32 [B, h, w] or None; probs fp32 [B, n, h, w] or None): bilinear resize to h x w
@@ -1034,20 +1058,10 @@ def seg_predict(scores, hp, wp, h, w, conf=False, probs=False, staging_bytes=Non
     assert P == hp * wp and B >= 1 and hp >= 1 and wp >= 1 and h >= 1 and w >= 1, (tuple(scores.shape), hp, wp, h, w)
     assert 1 <= n <= SEG_PREDICT_MAX_CLASSES, n
     assert B * h * w < 2 ** 31, (B, h, w)
-    dev = scores.device
-    if label_dtype is None:
-        label_dtype = torch.uint8 if n <= 256 else torch.int16
-    assert label_dtype in (torch.uint8, torch.int16) and (n <= 256 or label_dtype == torch.int16), (label_dtype, n)
-    labels = torch.empty(B, h, w, dtype=label_dtype, device=dev)
-    cf = torch.empty(B, h, w, dtype=torch.float32, device=dev) if conf else None
-    pr = torch.empty(B, n, h, w, dtype=torch.float32, device=dev) if probs else None
-    prev = lib().ifseg_seg_predict_staging(c_int(staging_bytes)) if staging_bytes is not None else None
-    try:
+    labels, cf, pr = _predict_outputs(B, n, h, w, scores.device, conf, probs, label_dtype)
+    with _staging(lib().ifseg_seg_predict_staging, staging_bytes):
         _check(lib().ifseg_seg_predict(_ptr(scores), c_int(B), c_int(hp), c_int(wp), c_int(n), c_int(h), c_int(w), _ptr(labels),
                                        c_int(labels.element_size()), _ptr(cf), _ptr(pr), _stream()), "seg_predict")
-    finally:
-        if prev is not None:
-            lib().ifseg_seg_predict_staging(c_int(prev))
     return labels, cf, pr
 
 
@@ -1079,19 +1093,10 @@ def seg_predict_views(views, h, w, conf=False, probs=False, staging_bytes=None, 
     assert B >= 1 and h >= 1 and w >= 1, (B, h, w)
     assert 1 <= n <= SEG_PREDICT_MAX_CLASSES, n
     assert B * h * w < 2 ** 31, (B, h, w)
-    if label_dtype is None:
-        label_dtype = torch.uint8 if n <= 256 else torch.int16
-    assert label_dtype in (torch.uint8, torch.int16) and (n <= 256 or label_dtype == torch.int16), (label_dtype, n)
-    labels = torch.empty(B, h, w, dtype=label_dtype, device=dev)
-    cf = torch.empty(B, h, w, dtype=torch.float32, device=dev) if conf else None
-    pr = torch.empty(B, n, h, w, dtype=torch.float32, device=dev) if probs else None
-    prev = lib().ifseg_seg_predict_views_staging(c_int(staging_bytes)) if staging_bytes is not None else None
-    try:
+    labels, cf, pr = _predict_outputs(B, n, h, w, dev, conf, probs, label_dtype)
+    with _staging(lib().ifseg_seg_predict_views_staging, staging_bytes):
         _check(lib().ifseg_seg_predict_views(table, c_int(len(views)), c_int(B), c_int(n), c_int(h), c_int(w), _ptr(labels),
                                              c_int(labels.element_size()), _ptr(cf), _ptr(pr), _stream()), "seg_predict_views")
-    finally:
-        if prev is not None:
-            lib().ifseg_seg_predict_views_staging(c_int(prev))
     return labels, cf, pr
 
 
@@ -1107,7 +1112,6 @@ def image_load(images_u8, oh, ow, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), rev
     (x / 255 - mean) / std from a [3, 256] table built on the host.  `imageio.image_load_reference` is the specification.
     staging_bytes: size of the kernel's LDS staging buffer for this call (0: every tile reads global memory), None: the default;
     out: a contiguous [B, 3, oh, ow] tensor of `dtype` to write into."""
-    from .imageio import normalisation_table
     assert images_u8.dtype == torch.uint8 and images_u8.dim() == 4 and images_u8.shape[-1] == 3 and images_u8.is_contiguous(), \
         (images_u8.dtype, tuple(images_u8.shape), images_u8.stride())
     B, H0, W0, _ = images_u8.shape
@@ -1116,26 +1120,16 @@ def image_load(images_u8, oh, ow, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), rev
     assert dtype in (torch.float32, torch.bfloat16), dtype
     assert images_u8.is_cuda, "device tensor required"
     dev = images_u8.device
-    key = (tuple(float(x) for x in mean), tuple(float(x) for x in std), dev)
-    lut = _image_luts.get(key)
-    if lut is None:
-        # the first call per (mean, std, device) copies the table from the host: it blocks the host and cannot be captured
-        if len(_image_luts) >= 16:
-            _image_luts.clear()
-        lut = _image_luts[key] = normalisation_table(mean, std).to(dev)
+    lut = _image_lut(mean, std, dev)
     if out is None:
         out = torch.empty(B, 3, oh, ow, dtype=dtype, device=dev)
     else:
         assert out.dtype == dtype and tuple(out.shape) == (B, 3, oh, ow) and out.is_contiguous() and out.device == dev, \
             (out.dtype, tuple(out.shape), out.stride(), out.device)
-    prev = lib().ifseg_image_load_staging(c_int(staging_bytes)) if staging_bytes is not None else None
-    try:
+    with _staging(lib().ifseg_image_load_staging, staging_bytes):
         _check(lib().ifseg_image_load(_ptr(images_u8), c_int(B), c_int(H0), c_int(W0), c_int(oh), c_int(ow), _ptr(lut),
                                       c_int(1 if reverse_channels else 0), _ptr(out), c_int(out.element_size()), _stream()),
                "image_load")
-    finally:
-        if prev is not None:
-            lib().ifseg_image_load_staging(c_int(prev))
     return out
 
 
@@ -1144,6 +1138,7 @@ def _image_lut(mean, std, dev):
     key = (tuple(float(x) for x in mean), tuple(float(x) for x in std), dev)
     lut = _image_luts.get(key)
     if lut is None:
+        # the first call per (mean, std, device) copies the table from the host: it blocks the host and cannot be captured
         if len(_image_luts) >= 16:
             _image_luts.clear()
         lut = _image_luts[key] = normalisation_table(mean, std).to(dev)
@@ -1222,16 +1217,12 @@ def train_load(images, labels, params, P, nseg, seg_id_offset, mean=(0.5, 0.5, 0
         target = torch.empty(B, P * P + 1, dtype=torch.int64, device=dev)
     else:
         assert target.dtype == torch.int64 and tuple(target.shape) == (B, P * P + 1) and target.is_contiguous() and target.device == dev
-    prev = lib().ifseg_train_load_staging(c_int(staging_bytes)) if staging_bytes is not None else None
-    try:
+    with _staging(lib().ifseg_train_load_staging, staging_bytes):
         _check(lib().ifseg_train_load(c_void_p(host.data_ptr()), _ptr(table), _ptr(params),
                                       c_void_p(params_host.data_ptr()) if params_host is not None else None, c_int(B), c_int(P),
                                       c_int(nseg), c_int(1 if raw_labels else 0), c_ll(seg_id_offset), c_ll(eos), _ptr(lut),
                                       c_int(1 if reverse_channels else 0), _ptr(out), c_int(out.element_size()), _ptr(target),
                                       _stream()), "train_load")
-    finally:
-        if prev is not None:
-            lib().ifseg_train_load_staging(c_int(prev))
     return out, target
 
 

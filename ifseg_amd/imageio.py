@@ -57,13 +57,25 @@ def source_coords(out, inn, dtype=torch.float64, device=None):
     return i0, i1, torch.where(i0 == i1, torch.zeros_like(lam), lam)
 
 
+def resize_to_grey(src, ycoords, xcoords):
+    """the resize step of both specifications (`image_load_reference`, `augment.train_load_reference`): src `dtype` [..., H0, W0],
+    ycoords / xcoords: (i0, i1, lambda) per destination row / column as `source_coords` returns them (or a window of them) ->
+    (q uint8 [..., rows, columns], v `dtype` the same shape): weights and the four-term sum
+    v = w00 a + w01 b + w10 c + w11 d in `dtype`, q = clamp(floor(v + 0.5), 0, 255) as the reference's uint8 resize"""
+    (y0, y1, ly), (x0, x1, lx) = ycoords, xcoords
+    ly, lx = ly[:, None], lx[None, :]
+    top, bot = src[..., y0, :], src[..., y1, :]
+    v = ((1 - ly) * (1 - lx)) * top[..., x0] + ((1 - ly) * lx) * top[..., x1] + (ly * (1 - lx)) * bot[..., x0] \
+        + (ly * lx) * bot[..., x1]
+    return (v + 0.5).floor().clamp(0, 255).to(torch.uint8), v
+
+
 def image_load_reference(images_u8, oh, ow, mean=HALF, std=HALF, reverse_channels=False, dtype=torch.float64,
                          out_dtype=torch.float32):
     """CPU specification of hip.image_load: uint8 [B, H0, W0, 3] -> (normalised `out_dtype` [B, 3, oh, ow], q uint8
     [B, 3, oh, ow], v `dtype` [B, 3, oh, ow]).  Bilinear resize with align_corners=False and no antialiasing
-    (`F.interpolate` / `cv2.INTER_LINEAR`), the source coordinate in integers (`source_coords`), weights and the
-    four-term sum v = w00 a + w01 b + w10 c + w11 d in `dtype`; q = clamp(floor(v + 0.5), 0, 255) as the reference's
-    uint8 resize; the output is `normalisation_table(mean, std)[c][q]`, channel c reading source channel 2 - c when
+    (`F.interpolate` / `cv2.INTER_LINEAR`), the source coordinate in integers (`source_coords`), v and q by
+    `resize_to_grey` in `dtype`; the output is `normalisation_table(mean, std)[c][q]`, channel c reading source channel 2 - c when
     `reverse_channels`.  Runs on any device.
 
     NOT pinned: `cv2` (what mmcv's Resize calls) evaluates the same filter with 11-bit fixed-point weights, and `cv2` is
@@ -79,13 +91,7 @@ def image_load_reference(images_u8, oh, ow, mean=HALF, std=HALF, reverse_channel
     if reverse_channels:
         src = src.flip(1)
     src = src.to(dtype)
-    y0, y1, ly = source_coords(oh, H0, dtype, dev)
-    x0, x1, lx = source_coords(ow, W0, dtype, dev)
-    ly, lx = ly[:, None], lx[None, :]
-    top, bot = src[:, :, y0], src[:, :, y1]
-    v = ((1 - ly) * (1 - lx)) * top[..., x0] + ((1 - ly) * lx) * top[..., x1] + (ly * (1 - lx)) * bot[..., x0] \
-        + (ly * lx) * bot[..., x1]
-    q = (v + 0.5).floor().clamp(0, 255).to(torch.uint8)
+    q, v = resize_to_grey(src, source_coords(oh, H0, dtype, dev), source_coords(ow, W0, dtype, dev))
     lut = normalisation_table(mean, std).to(dev)
     norm = torch.stack([lut[c][q[:, c].long()] for c in range(3)], 1).to(out_dtype)
     return norm, q, v
