@@ -17,6 +17,12 @@
 //            four pixels of a 4-ALIGNED element quad of the flat [B, h, w] index, so the wide stores are aligned whatever w is;
 //            the up to three pixels in front of the first whole quad and behind the last one leave as single elements.
 // No atomics, no scratch buffer, static launch shape, nothing read back.
+//
+// Scoring (ifseg_seg_score / ifseg_seg_score_views / ifseg_seg_areas): the same kernels with an epilogue behind a template flag
+// that counts the tile's pixels against ground truth -- per class #(pred = gt = c), #(pred = c), #(gt = c) and the two tallies --
+// in a workgroup-private uint32 table in LDS (LDS atomics), and a stand-alone kernel that does the same for label maps that come
+// from elsewhere.  Only the non-zero bins leave a workgroup, one 64-bit integer atomic each: integer sums, so the counters
+// are bit-reproducible.  The instantiations without the flag have none of this.
 #include "tile.h"
 #include "../../include/ifseg_hip.h"
 
@@ -98,7 +104,9 @@ __device__ __forceinline__ void class_loop(Ptr base, int n, int o0, int o1, cons
   }
 }
 
-// phase 2 of both kernels: the 16 x 64 label / conf tile of image b at (X0, Y0) leaves LDS in wide, aligned stores
+// phase 2 of both kernels: the 16 x 64 label / conf tile of image b at (X0, Y0) leaves LDS in wide, aligned stores.
+// OPT: labels may be null (the scoring launches)
+template <bool OPT>
 __device__ __forceinline__ void store_tile(const int (&t_lab)[TILE_ROWS][TILE_COLS], const float (&t_conf)[TILE_ROWS][TILE_COLS],
                                            int b, int X0, int Y0, int xend, int h, int w, void* __restrict__ labels,
                                            int label_bytes, float* __restrict__ conf) {
@@ -111,13 +119,17 @@ __device__ __forceinline__ void store_tile(const int (&t_lab)[TILE_ROWS][TILE_CO
   short* l16 = (short*)labels;
   auto put = [&](int xx) {
     const int v = t_lab[r][xx - X0];
-    if (label_bytes == 1) l8[row + xx] = (unsigned char)v; else l16[row + xx] = (short)v;
+    if (!OPT || labels) {
+      if (label_bytes == 1) l8[row + xx] = (unsigned char)v; else l16[row + xx] = (short)v;
+    }
     if (conf) conf[row + xx] = t_conf[r][xx - X0];
   };
   const int xs = X0 - a + 4 * k;
   if (xs >= X0 && xs + 4 <= xend) {
     const int* tl = &t_lab[r][xs - X0];
-    if (label_bytes == 1)
+    if (OPT && !labels)
+      ;
+    else if (label_bytes == 1)
       *reinterpret_cast<uint32_t*>(l8 + row + xs) = (uint32_t)tl[0] | ((uint32_t)tl[1] << 8) | ((uint32_t)tl[2] << 16) | ((uint32_t)tl[3] << 24);
     else
       *reinterpret_cast<uint2*>(l16 + row + xs) = make_uint2((uint32_t)tl[0] | ((uint32_t)tl[1] << 16), (uint32_t)tl[2] | ((uint32_t)tl[3] << 16));
@@ -132,13 +144,99 @@ __device__ __forceinline__ void store_tile(const int (&t_lab)[TILE_ROWS][TILE_CO
   if (k < a && X0 + TILE_COLS - a + k < xend) put(X0 + TILE_COLS - a + k);
 }
 
+
+// ---- scoring against ground truth ----
+// The table of one workgroup: uint32 [3][n] (intersect, predicted, label) + [2] (scored, out of range), in the dynamic LDS
+// (behind seg_predict_kernel's staging buffer, in front of seg_predict_views_kernel's coordinates), zeroed at entry.
+struct NoScore {
+  static constexpr bool on = false;
+};
+struct Score {
+  static constexpr bool on = true;
+  const void* gt;                 // [B, h, w] uint8 or int16
+  int gt_bytes, raw;
+  unsigned long long* areas;      // [3, n]
+  unsigned long long* tally;      // [2]
+};
+
+// the table's dwords, in whole 16-byte slots
+__host__ __device__ inline int score_dwords(int n) { return (3 * n + 2 + 3) & ~3; }
+
+__device__ __forceinline__ void score_zero(uint32_t* tab, int n) {
+  for (int i = threadIdx.x; i < 3 * n + 2; i += 256) tab[i] = 0;
+}
+
+// tab[idx] += 1 for every lane with `on`; whole (converged) waves call it.  A label map is piecewise constant, so most lanes
+// of a wave name the same bin, and an LDS atomic takes the lanes of one address one after the other: the lanes that share the
+// first active lane's bin leave as one add of their count, the others one each
+__device__ __forceinline__ void bin_add(uint32_t* tab, int idx, bool on) {
+  const unsigned long long m = __ballot(on);
+  if (!m) return;
+  const int lead = __ffsll((long long)m) - 1;
+  const int first = __builtin_amdgcn_readlane(idx, lead);
+  const unsigned long long same = __ballot(on && idx == first);
+  if ((int)(threadIdx.x & 63) == lead) atomicAdd(&tab[first], (uint32_t)__popcll(same));
+  else if (on && idx != first) atomicAdd(&tab[idx], 1u);
+}
+
+// one pixel (where `live`) into the table: the ground-truth rule of include/ifseg_hip.h, then the three bins.  scored / bad:
+// the thread's own tallies, added by score_flush
+__device__ __forceinline__ void score_pixel(uint32_t* tab, int n, int raw, int pred, int g, bool live, int& scored, int& bad) {
+  const bool ign = raw ? (g == 0 || g == 255) : (g == n || g == 255);
+  const int cls = raw ? g - 1 : g;
+  const bool inr = (unsigned)cls < (unsigned)n;
+  const bool sc = live && !ign && inr, pin = sc && (unsigned)pred < (unsigned)n;
+  scored += sc;
+  bad += live && !ign && !inr;
+  bin_add(tab, 2 * n + cls, sc);
+  bin_add(tab, n + pred, pin);
+  bin_add(tab, cls, pin && pred == cls);
+}
+
+// the tallies join the table, a barrier, and the non-zero bins leave: one 64-bit atomic per workgroup and bin
+__device__ __forceinline__ void score_flush(uint32_t* tab, int n, int scored, int bad, unsigned long long* areas,
+                                            unsigned long long* tally) {
+#pragma unroll
+  for (int o = 32; o; o >>= 1) { scored += __shfl_xor(scored, o); bad += __shfl_xor(bad, o); }
+  if ((threadIdx.x & 63) == 0) {
+    if (scored) atomicAdd(&tab[3 * n], (uint32_t)scored);
+    if (bad) atomicAdd(&tab[3 * n + 1], (uint32_t)bad);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 3 * n + 2; i += 256) {
+    const uint32_t v = tab[i];
+    if (v) atomicAdd(i < 3 * n ? areas + i : tally + (i - 3 * n), (unsigned long long)v);
+  }
+}
+
+template <int EB>
+__device__ __forceinline__ int elem_at(const void* p, long long i) {
+  return EB == 1 ? (int)((const unsigned char*)p)[i] : (int)((const short*)p)[i];
+}
+
+// the epilogue of both predict kernels: lane = x, the wave's four rows; pred[j] is the label of row wave * 4 + j
+__device__ __forceinline__ void score_tile(const Score& sc, uint32_t* tab, int n, long long image, const int (&pofs)[4],
+                                           const bool (&ok)[4], const int (&pred)[4]) {
+  int scored = 0, bad = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    int g = 0;
+    if (ok[j]) g = sc.gt_bytes == 1 ? elem_at<1>(sc.gt, image + pofs[j]) : elem_at<2>(sc.gt, image + pofs[j]);
+    score_pixel(tab, n, sc.raw, pred[j], g, ok[j], scored, bad);
+  }
+  score_flush(tab, n, scored, bad, sc.areas, sc.tally);
+}
+
+template <typename S>
 __global__ __launch_bounds__(256) void seg_predict_kernel(const float* __restrict__ scores, int hp, int wp, int n, int h, int w,
                                                           int tiles_x, int tiles_y, void* __restrict__ labels, int label_bytes,
                                                           float* __restrict__ conf, float* __restrict__ probs,
-                                                          int stage_floats) {
-  extern __shared__ __attribute__((aligned(16))) float stage[];
+                                                          int stage_floats, S sc) {
+  extern __shared__ __attribute__((aligned(16))) float stage[];   // stage_floats of footprint (scoring: then the table)
   __shared__ int t_lab[TILE_ROWS][TILE_COLS];
   __shared__ float t_conf[TILE_ROWS][TILE_COLS];
+  uint32_t* tab = reinterpret_cast<uint32_t*>(stage + stage_floats);
+  if constexpr (S::on) score_zero(tab, n);                        // published by the barrier in front of phase 2
 
   const auto [b, X0, Y0, xend, yend, lane, wave] = tile_decode(tiles_x, tiles_y, h, w);
   const FloatCoord cy{(float)hp / (float)h, hp}, cx{(float)wp / (float)w, wp};
@@ -194,7 +292,13 @@ __global__ __launch_bounds__(256) void seg_predict_kernel(const float* __restric
   __syncthreads();
 
   // phase 2
-  store_tile(t_lab, t_conf, b, X0, Y0, xend, h, w, labels, label_bytes, conf);
+  if constexpr (S::on) {
+    if (labels || conf) store_tile<true>(t_lab, t_conf, b, X0, Y0, xend, h, w, labels, label_bytes, conf);
+    const int pred[4] = {best[0].c, best[1].c, best[2].c, best[3].c};
+    score_tile(sc, tab, n, (long long)b * h * w, pofs, ok, pred);
+  } else {
+    store_tile<false>(t_lab, t_conf, b, X0, Y0, xend, h, w, labels, label_bytes, conf);
+  }
 }
 
 // ---- K views of different grids into one label map (multi-scale + flip test-time augmentation) ----
@@ -261,16 +365,22 @@ __device__ __forceinline__ void add_view(const float* p00, const float* p01, con
   }
 }
 
+template <typename S>
 __global__ __launch_bounds__(256) void seg_predict_views_kernel(ViewTable views, int K, float inv_k, int n, int h, int w,
                                                                 int tiles_x, int tiles_y, void* __restrict__ labels,
                                                                 int label_bytes, float* __restrict__ conf,
-                                                                float* __restrict__ probs, int stage_floats) {
-  extern __shared__ __attribute__((aligned(16))) float dyn[];     // K * PV_COORDS coordinates, then stage_floats of footprints
+                                                                float* __restrict__ probs, int stage_floats, S sc) {
+  // (scoring: the table,) K * PV_COORDS coordinates, then stage_floats of footprints
+  extern __shared__ __attribute__((aligned(16))) float dyn[];
   __shared__ int t_lab[TILE_ROWS][TILE_COLS];
   __shared__ float t_conf[TILE_ROWS][TILE_COLS];
   __shared__ ViewMeta vm[PV_MAX_VIEWS];
   int* coords = reinterpret_cast<int*>(dyn);
-  float* stage = dyn + K * PV_COORDS;
+  if constexpr (S::on) {
+    score_zero(reinterpret_cast<uint32_t*>(dyn), n);              // published by the barriers below
+    coords += score_dwords(n);
+  }
+  float* stage = reinterpret_cast<float*>(coords) + K * PV_COORDS;
 
   const auto [b, X0, Y0, xend, yend, lane, wave] = tile_decode(tiles_x, tiles_y, h, w);
 
@@ -385,18 +495,111 @@ __global__ __launch_bounds__(256) void seg_predict_views_kernel(ViewTable views,
   __syncthreads();
 
   // phase 2
-  store_tile(t_lab, t_conf, b, X0, Y0, xend, h, w, labels, label_bytes, conf);
+  if constexpr (S::on) {
+    if (labels || conf) store_tile<true>(t_lab, t_conf, b, X0, Y0, xend, h, w, labels, label_bytes, conf);
+    int pofs[4], pred[4];
+    bool ok[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int row = wave * 4 + j;
+      pofs[j] = min(Y0 + row, h - 1) * w + x;
+      ok[j] = Y0 + row < h && X0 + lane < w;
+      pred[j] = t_lab[row][lane];
+    }
+    score_tile(sc, reinterpret_cast<uint32_t*>(dyn), n, (long long)b * h * w, pofs, ok, pred);
+  } else {
+    store_tile<false>(t_lab, t_conf, b, X0, Y0, xend, h, w, labels, label_bytes, conf);
+  }
 }
 
-}  // namespace
+// ---- labels from elsewhere (the CRF's argmax, another model) against ground truth ----
+// A lane takes 16 consecutive pixels per step: their labels and their ground truth come as aligned 16-byte loads.  The body
+// starts at the first 16-byte boundary of `lab`; the ground truth of the same pixels then sits s bytes behind a boundary of
+// its own, s the same for every lane: it is read as the aligned chunks around it and shifted into place.  The pixels in front
+// of the body and behind its last whole group of 16 (fewer than 16 each) are read one by one.  Grid-stride over at most
+// SA_MAX_BLOCKS workgroups, so the flush does not grow with the image.
+constexpr int SA_MAX_BLOCKS = 512;
 
-extern "C" int ifseg_seg_predict_staging(int max_bytes) { return swap_limit(g_stage_limit, PT_STAGE_LIMIT, max_bytes); }
+// o[i] = dword i of the byte string w shifted down by 4 SD + sb bytes
+template <int SD, int N>
+__device__ __forceinline__ void shifted(const uint32_t (&w)[N + 4], int sb, uint32_t (&o)[N]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) o[i] = __builtin_amdgcn_alignbyte(w[i + SD + 1], w[i + SD], (uint32_t)sb);
+}
 
-extern "C" int ifseg_seg_predict(const float* scores, int B, int hp, int wp, int n, int h, int w, void* labels, int label_bytes,
-                                 float* conf, float* probs, void* stream) {
+// v[0..16) = the 16 elements of EB bytes that start s bytes (0 <= s < 16, wave-uniform) behind the 16-byte boundary p: EB
+// aligned chunks, and one more only where s != 0 -- that one holds bytes of the elements, so it lies inside their buffer's pages
+template <int EB>
+__device__ __forceinline__ void load16(const unsigned char* p, int s, int (&v)[16]) {
+  constexpr int N = 4 * EB;
+  uint32_t w[N + 4], o[N];
+#pragma unroll
+  for (int c = 0; c <= EB; ++c) {
+    uint4 q = make_uint4(0, 0, 0, 0);
+    if (c < EB || s) q = *reinterpret_cast<const uint4*>(p + 16 * c);
+    w[4 * c] = q.x; w[4 * c + 1] = q.y; w[4 * c + 2] = q.z; w[4 * c + 3] = q.w;
+  }
+  switch (s >> 2) {
+    case 0: shifted<0, N>(w, s & 3, o); break;
+    case 1: shifted<1, N>(w, s & 3, o); break;
+    case 2: shifted<2, N>(w, s & 3, o); break;
+    default: shifted<3, N>(w, s & 3, o); break;
+  }
+#pragma unroll
+  for (int i = 0; i < 16; ++i)
+    v[i] = EB == 1 ? (int)((o[i >> 2] >> (8 * (i & 3))) & 255u) : (int)(short)(o[i >> 1] >> (16 * (i & 1)));
+}
+
+template <int LB, int GB>
+__global__ __launch_bounds__(256) void seg_areas_kernel(const unsigned char* __restrict__ lab, const unsigned char* __restrict__ gt,
+                                                        int head, int groups, int tail, int n, int raw,
+                                                        unsigned long long* areas, unsigned long long* tally) {
+  __shared__ uint32_t tab[3 * PT_MAX_CLASSES + 2];
+  score_zero(tab, n);
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  int scored = 0, bad = 0;
+  // head and tail: lanes 0..15 and 16..31 of the grid's first wave, one pixel each
+  if (blockIdx.x == 0 && wave == 0) {
+    long long i = -1;
+    if (lane < head) i = lane;
+    else if (lane >= 16 && lane - 16 < tail) i = (long long)head + (long long)groups * 16 + (lane - 16);
+    const bool live = i >= 0;
+    score_pixel(tab, n, raw, live ? elem_at<LB>(lab, i) : 0, live ? elem_at<GB>(gt, i) : 0, live, scored, bad);
+  }
+  const unsigned char* lb = lab + (long long)head * LB;           // on a 16-byte boundary
+  const unsigned char* gb = gt + (long long)head * GB;
+  const int s = __builtin_amdgcn_readfirstlane((int)((size_t)gb & 15));
+  gb -= s;
+  for (long long base = (long long)blockIdx.x * 256 + wave * 64; base < groups; base += (long long)gridDim.x * 256) {
+    const long long g = base + lane;
+    const bool live = g < groups;
+    int pv[16] = {}, gv[16] = {};
+    if (live) {
+      load16<LB>(lb + g * (16 * LB), 0, pv);
+      load16<GB>(gb + g * (16 * GB), s, gv);
+    }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) score_pixel(tab, n, raw, pv[i], gv[i], live, scored, bad);
+  }
+  score_flush(tab, n, scored, bad, areas, tally);
+}
+
+// what the scoring entry points refuse on top of their predict counterparts
+int score_refusal(const void* gt, int gt_bytes, const unsigned long long* areas, const unsigned long long* tally) {
+  if (!gt || !areas || !tally || (gt_bytes != 1 && gt_bytes != 2)) return IFSEG_ERR_BAD_ARG;
+  if (((size_t)areas & 7) || ((size_t)tally & 7) || ((size_t)gt & (size_t)(gt_bytes - 1))) return IFSEG_ERR_BAD_ARG;
+  return 0;
+}
+
+// ifseg_seg_predict (S = NoScore) and ifseg_seg_score
+template <typename S>
+int launch_predict(const float* scores, int B, int hp, int wp, int n, int h, int w, void* labels, int label_bytes, float* conf,
+                   float* probs, void* stream, S sc) {
   (void)hipGetLastError();
-  if (!scores || !labels || (label_bytes != 1 && label_bytes != 2)) return IFSEG_ERR_BAD_ARG;
-  if (n < 1 || n > PT_MAX_CLASSES || (label_bytes == 1 && n > 256)) return IFSEG_ERR_BAD_ARG;
+  if (!scores) return IFSEG_ERR_BAD_ARG;
+  if ((!S::on || labels) && (!labels || (label_bytes != 1 && label_bytes != 2))) return IFSEG_ERR_BAD_ARG;
+  if (n < 1 || n > PT_MAX_CLASSES || (labels && label_bytes == 1 && n > 256)) return IFSEG_ERR_BAD_ARG;
   if (B < 1 || hp < 1 || wp < 1 || h < 1 || w < 1) return IFSEG_ERR_BAD_SHAPE;
   if ((long long)B * h * w >= (1ll << 31) || (long long)hp * wp >= (1ll << 31) / PT_MAX_CLASSES) return IFSEG_ERR_BAD_SHAPE;
   // the wide stores of phase 2 want 16-byte aligned bases
@@ -404,23 +607,25 @@ extern "C" int ifseg_seg_predict(const float* scores, int B, int hp, int wp, int
   int tiles_x, tiles_y;
   long long blocks;
   if (!tile_grid(h, w, B, &tiles_x, &tiles_y, &blocks)) return IFSEG_ERR_BAD_SHAPE;
+  // the scoring launches take their table out of the staging budget
+  const int table = S::on ? score_dwords(n) * 4 : 0;
+  const int limit = std::max(std::min(g_stage_limit, PT_STAGE_LIMIT - table), 0);
   const long long need = footprint_bound(hp, hp, h, TILE_ROWS, 3) * footprint_bound(wp, wp, w, TILE_COLS, 3) * pt_stride(n) * 4;
-  const int lds = (int)std::min<long long>(need, g_stage_limit) & ~15;
-  hipLaunchKernelGGL(seg_predict_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, scores, hp, wp, n, h, w,
-                     tiles_x, tiles_y, labels, label_bytes, conf, probs, lds / 4);
+  const int lds = (int)std::min<long long>(need, limit) & ~15;
+  hipLaunchKernelGGL(seg_predict_kernel<S>, dim3((unsigned)blocks), dim3(256), lds + table, (hipStream_t)stream, scores, hp, wp,
+                     n, h, w, tiles_x, tiles_y, labels, label_bytes, conf, probs, lds / 4, sc);
   IFSEG_CHECK_LAUNCH();
   return 0;
 }
 
-extern "C" int ifseg_seg_predict_views_staging(int max_bytes) {
-  return swap_limit(g_views_stage_limit, PV_STAGE_LIMIT, max_bytes);
-}
-
-extern "C" int ifseg_seg_predict_views(const ifseg_predict_view* views, int K, int B, int n, int h, int w, void* labels,
-                                       int label_bytes, float* conf, float* probs, void* stream) {
+// ifseg_seg_predict_views (S = NoScore) and ifseg_seg_score_views
+template <typename S>
+int launch_views(const ifseg_predict_view* views, int K, int B, int n, int h, int w, void* labels, int label_bytes, float* conf,
+                 float* probs, void* stream, S sc) {
   (void)hipGetLastError();
-  if (!views || K < 1 || K > PV_MAX_VIEWS || !labels || (label_bytes != 1 && label_bytes != 2)) return IFSEG_ERR_BAD_ARG;
-  if (n < 1 || n > PT_MAX_CLASSES || (label_bytes == 1 && n > 256)) return IFSEG_ERR_BAD_ARG;
+  if (!views || K < 1 || K > PV_MAX_VIEWS) return IFSEG_ERR_BAD_ARG;
+  if ((!S::on || labels) && (!labels || (label_bytes != 1 && label_bytes != 2))) return IFSEG_ERR_BAD_ARG;
+  if (n < 1 || n > PT_MAX_CLASSES || (labels && label_bytes == 1 && n > 256)) return IFSEG_ERR_BAD_ARG;
   if (B < 1 || h < 1 || w < 1 || (long long)B * h * w >= (1ll << 31)) return IFSEG_ERR_BAD_SHAPE;
   if (((size_t)labels & 15) || ((size_t)conf & 15) || ((size_t)probs & 3)) return IFSEG_ERR_BAD_ARG;
   int tiles_x, tiles_y;
@@ -436,11 +641,74 @@ extern "C" int ifseg_seg_predict_views(const ifseg_predict_view* views, int K, i
     table.v[k].flip = v.flip != 0;
     need += footprint_bound(v.hp, v.hp, h, TILE_ROWS, 3) * footprint_bound(v.wp, v.wp, w, TILE_COLS, 3) * PV_STRIDE * 4;
   }
-  // the coordinates come first; what the limit leaves is the staging buffer
+  // (the scoring table and) the coordinates come first; what the limit leaves is the staging buffer
+  const int counters = S::on ? score_dwords(n) * 4 : 0;
   const int coords = K * PV_COORDS * 4;
-  const int stage = (int)std::min<long long>(need, std::max(g_views_stage_limit - coords, 0)) & ~15;
-  hipLaunchKernelGGL(seg_predict_views_kernel, dim3((unsigned)blocks), dim3(256), coords + stage, (hipStream_t)stream, table, K,
-                     (float)(1.0 / K), n, h, w, tiles_x, tiles_y, labels, label_bytes, conf, probs, stage / 4);
+  const int limit = std::min(g_views_stage_limit, PV_STAGE_LIMIT - counters);
+  const int stage = (int)std::min<long long>(need, std::max(limit - coords, 0)) & ~15;
+  hipLaunchKernelGGL(seg_predict_views_kernel<S>, dim3((unsigned)blocks), dim3(256), counters + coords + stage,
+                     (hipStream_t)stream, table, K, (float)(1.0 / K), n, h, w, tiles_x, tiles_y, labels, label_bytes, conf,
+                     probs, stage / 4, sc);
+  IFSEG_CHECK_LAUNCH();
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int ifseg_seg_predict_staging(int max_bytes) { return swap_limit(g_stage_limit, PT_STAGE_LIMIT, max_bytes); }
+
+extern "C" int ifseg_seg_predict(const float* scores, int B, int hp, int wp, int n, int h, int w, void* labels, int label_bytes,
+                                 float* conf, float* probs, void* stream) {
+  return launch_predict(scores, B, hp, wp, n, h, w, labels, label_bytes, conf, probs, stream, NoScore{});
+}
+
+extern "C" int ifseg_seg_score(const float* scores, int B, int hp, int wp, int n, int h, int w, void* labels, int label_bytes,
+                               float* conf, float* probs, const void* gt, int gt_bytes, int raw_labels,
+                               unsigned long long* areas, unsigned long long* tally, void* stream) {
+  if (const int rc = score_refusal(gt, gt_bytes, areas, tally)) return rc;
+  return launch_predict(scores, B, hp, wp, n, h, w, labels, label_bytes, conf, probs, stream,
+                        Score{gt, gt_bytes, raw_labels != 0, areas, tally});
+}
+
+extern "C" int ifseg_seg_predict_views_staging(int max_bytes) {
+  return swap_limit(g_views_stage_limit, PV_STAGE_LIMIT, max_bytes);
+}
+
+extern "C" int ifseg_seg_predict_views(const ifseg_predict_view* views, int K, int B, int n, int h, int w, void* labels,
+                                       int label_bytes, float* conf, float* probs, void* stream) {
+  return launch_views(views, K, B, n, h, w, labels, label_bytes, conf, probs, stream, NoScore{});
+}
+
+extern "C" int ifseg_seg_score_views(const ifseg_predict_view* views, int K, int B, int n, int h, int w, void* labels,
+                                     int label_bytes, float* conf, float* probs, const void* gt, int gt_bytes, int raw_labels,
+                                     unsigned long long* areas, unsigned long long* tally, void* stream) {
+  if (const int rc = score_refusal(gt, gt_bytes, areas, tally)) return rc;
+  return launch_views(views, K, B, n, h, w, labels, label_bytes, conf, probs, stream,
+                      Score{gt, gt_bytes, raw_labels != 0, areas, tally});
+}
+
+extern "C" int ifseg_seg_areas(const void* labels, int label_bytes, const void* gt, int gt_bytes, long long npix, int n,
+                               int raw_labels, unsigned long long* areas, unsigned long long* tally, void* stream) {
+  (void)hipGetLastError();
+  if (!labels || (label_bytes != 1 && label_bytes != 2) || ((size_t)labels & (size_t)(label_bytes - 1))) return IFSEG_ERR_BAD_ARG;
+  if (const int rc = score_refusal(gt, gt_bytes, areas, tally)) return rc;
+  if (n < 1 || n > PT_MAX_CLASSES) return IFSEG_ERR_BAD_ARG;
+  if (npix < 1 || npix >= (1ll << 31)) return IFSEG_ERR_BAD_SHAPE;
+  // the pixels in front of the labels' first 16-byte boundary, whole groups of 16, the rest
+  const int head = (int)std::min<long long>(npix, (long long)((0 - (size_t)labels) & 15) / label_bytes);
+  const int groups = (int)((npix - head) / 16), tail = (int)(npix - head - 16ll * groups);
+  const int blocks = std::min(std::max((groups + 255) / 256, 1), SA_MAX_BLOCKS);
+  const unsigned char* l = (const unsigned char*)labels;
+  const unsigned char* g = (const unsigned char*)gt;
+  const int raw = raw_labels != 0;
+#define IFSEG_AREAS(LB, GB)                                                                                                  \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(seg_areas_kernel<LB, GB>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, l, g, head, \
+                     groups, tail, n, raw, areas, tally)
+  if (label_bytes == 1 && gt_bytes == 1) IFSEG_AREAS(1, 1);
+  else if (label_bytes == 1) IFSEG_AREAS(1, 2);
+  else if (gt_bytes == 1) IFSEG_AREAS(2, 1);
+  else IFSEG_AREAS(2, 2);
+#undef IFSEG_AREAS
   IFSEG_CHECK_LAUNCH();
   return 0;
 }

@@ -1035,13 +1035,13 @@ def _staging(setter, staging_bytes):
             setter(c_int(prev))
 
 
-def _predict_outputs(B, n, h, w, dev, conf, probs, label_dtype):
-    """-> (labels [B, h, w] uint8 for n <= 256 else int16, or `label_dtype`; conf fp32 [B, h, w] or None; probs fp32 [B, n, h, w]
-    or None), uninitialised"""
+def _predict_outputs(B, n, h, w, dev, conf, probs, label_dtype, want_labels=True):
+    """-> (labels [B, h, w] uint8 for n <= 256 else int16, or `label_dtype` (None without want_labels: the scoring calls); conf
+    fp32 [B, h, w] or None; probs fp32 [B, n, h, w] or None), uninitialised"""
     if label_dtype is None:
         label_dtype = torch.uint8 if n <= 256 else torch.int16
     assert label_dtype in (torch.uint8, torch.int16) and (n <= 256 or label_dtype == torch.int16), (label_dtype, n)
-    labels = torch.empty(B, h, w, dtype=label_dtype, device=dev)
+    labels = torch.empty(B, h, w, dtype=label_dtype, device=dev) if want_labels else None
     cf = torch.empty(B, h, w, dtype=torch.float32, device=dev) if conf else None
     pr = torch.empty(B, n, h, w, dtype=torch.float32, device=dev) if probs else None
     return labels, cf, pr
@@ -1098,6 +1098,94 @@ def seg_predict_views(views, h, w, conf=False, probs=False, staging_bytes=None, 
         _check(lib().ifseg_seg_predict_views(table, c_int(len(views)), c_int(B), c_int(n), c_int(h), c_int(w), _ptr(labels),
                                              c_int(labels.element_size()), _ptr(cf), _ptr(pr), _stream()), "seg_predict_views")
     return labels, cf, pr
+
+
+# --------------------------------------------------------------------------- scoring against ground truth
+def _score_counters(n, dev, areas, tally):
+    """the counters a scoring call adds to: the caller's (int64 [3, n] and [2], contiguous, on `dev`) or fresh zeroed ones"""
+    if areas is None:
+        areas = torch.zeros(3, n, dtype=torch.int64, device=dev)
+    if tally is None:
+        tally = torch.zeros(2, dtype=torch.int64, device=dev)
+    assert areas.dtype == torch.int64 and tuple(areas.shape) == (3, n) and areas.is_contiguous() and areas.device == dev, \
+        (areas.dtype, tuple(areas.shape), areas.device, n)
+    assert tally.dtype == torch.int64 and tuple(tally.shape) == (2,) and tally.is_contiguous() and tally.device == dev, \
+        (tally.dtype, tuple(tally.shape), tally.device)
+    return areas, tally
+
+
+def _score_gt(gt, B, dev):
+    assert gt.dtype in (torch.uint8, torch.int16) and gt.dim() == 3 and gt.is_contiguous(), (gt.dtype, tuple(gt.shape), gt.stride())
+    assert gt.shape[0] == B and gt.device == dev and gt.shape[1] >= 1 and gt.shape[2] >= 1, (tuple(gt.shape), B, gt.device, dev)
+    return int(gt.shape[1]), int(gt.shape[2])
+
+
+def seg_areas(labels, gt, n, raw_labels=True, areas=None, tally=None):
+    """labels uint8 / int16 [...] (predicted classes), gt uint8 / int16 of the same shape -> (areas int64 [3, n], tally int64 [2]):
+    per class #(pred = gt = c), #(pred = c), #(gt = c) over the scored pixels; #scored pixels, #pixels with a ground truth out of
+    range (csrc/predict.hip; `predict.areas_reference` is the specification and states the ground-truth rule).  `areas` / `tally`
+    given: ACCUMULATED into, else fresh zeroed ones.  For label maps that do not come out of seg_score / seg_score_views."""
+    assert labels.dtype in (torch.uint8, torch.int16) and labels.is_contiguous(), (labels.dtype, labels.stride())
+    assert gt.dtype in (torch.uint8, torch.int16) and gt.is_contiguous(), (gt.dtype, gt.stride())
+    assert labels.shape == gt.shape and labels.device == gt.device, (tuple(labels.shape), tuple(gt.shape), labels.device, gt.device)
+    assert 1 <= n <= SEG_PREDICT_MAX_CLASSES, n
+    assert 1 <= labels.numel() < 2 ** 31, tuple(labels.shape)
+    areas, tally = _score_counters(n, labels.device, areas, tally)
+    _check(lib().ifseg_seg_areas(_ptr(labels), c_int(labels.element_size()), _ptr(gt), c_int(gt.element_size()),
+                                 c_ll(labels.numel()), c_int(n), c_int(1 if raw_labels else 0), _ptr(areas), _ptr(tally),
+                                 _stream()), "seg_areas")
+    return areas, tally
+
+
+def seg_score(scores, hp, wp, gt, raw_labels=True, labels=False, conf=False, probs=False, areas=None, tally=None,
+              staging_bytes=None, label_dtype=None):
+    """`seg_predict` at gt's own [B, h, w] with the scoring in the kernel's epilogue: -> (areas, tally, labels | None,
+    conf | None, probs | None).  The counters are `seg_areas`' of the labels the launch decides on, whether it writes them or
+    not; the three outputs are optional, and with none of them the launch writes nothing but counters.  What is written is
+    `seg_predict`'s, bit for bit.  areas / tally given: accumulated into.  staging_bytes, label_dtype: as in `seg_predict`."""
+    assert scores.dtype == torch.float32 and scores.dim() == 3 and scores.is_contiguous(), (scores.dtype, tuple(scores.shape), scores.stride())
+    B, P, n = scores.shape
+    assert P == hp * wp and B >= 1 and hp >= 1 and wp >= 1, (tuple(scores.shape), hp, wp)
+    assert 1 <= n <= SEG_PREDICT_MAX_CLASSES, n
+    h, w = _score_gt(gt, B, scores.device)
+    assert B * h * w < 2 ** 31, (B, h, w)
+    areas, tally = _score_counters(n, scores.device, areas, tally)
+    lab, cf, pr = _predict_outputs(B, n, h, w, scores.device, conf, probs, label_dtype, labels)
+    with _staging(lib().ifseg_seg_predict_staging, staging_bytes):
+        _check(lib().ifseg_seg_score(_ptr(scores), c_int(B), c_int(hp), c_int(wp), c_int(n), c_int(h), c_int(w), _ptr(lab),
+                                     c_int(lab.element_size() if labels else 0), _ptr(cf), _ptr(pr), _ptr(gt),
+                                     c_int(gt.element_size()), c_int(1 if raw_labels else 0), _ptr(areas), _ptr(tally),
+                                     _stream()), "seg_score")
+    return areas, tally, lab, cf, pr
+
+
+def seg_score_views(views, gt, raw_labels=True, labels=False, conf=False, probs=False, areas=None, tally=None,
+                    staging_bytes=None, label_dtype=None):
+    """`seg_predict_views` at gt's own [B, h, w] with the scoring in the kernel's epilogue; arguments and results as
+    `seg_score`, `views` as in `seg_predict_views`."""
+    views = list(views)
+    assert 1 <= len(views) <= SEG_PREDICT_MAX_VIEWS, len(views)
+    for k, (scores, hp, wp, flip) in enumerate(views):
+        assert scores.dtype == torch.float32 and scores.dim() == 3 and scores.is_contiguous(), (k, scores.dtype, tuple(scores.shape), scores.stride())
+    B, _, n = views[0][0].shape
+    dev = views[0][0].device
+    for k, (scores, hp, wp, flip) in enumerate(views):
+        assert scores.shape[0] == B and scores.shape[2] == n and scores.device == dev, (k, tuple(scores.shape), B, n)
+        assert scores.shape[1] == hp * wp and hp >= 1 and wp >= 1, (k, tuple(scores.shape), hp, wp)
+    assert B >= 1 and 1 <= n <= SEG_PREDICT_MAX_CLASSES, (B, n)
+    h, w = _score_gt(gt, B, dev)
+    assert B * h * w < 2 ** 31, (B, h, w)
+    areas, tally = _score_counters(n, dev, areas, tally)
+    lab, cf, pr = _predict_outputs(B, n, h, w, dev, conf, probs, label_dtype, labels)
+    table = (_PredictView * len(views))()
+    for k, (scores, hp, wp, flip) in enumerate(views):
+        table[k] = _PredictView(_ptr(scores), int(hp), int(wp), 1 if flip else 0)
+    with _staging(lib().ifseg_seg_predict_views_staging, staging_bytes):
+        _check(lib().ifseg_seg_score_views(table, c_int(len(views)), c_int(B), c_int(n), c_int(h), c_int(w), _ptr(lab),
+                                           c_int(lab.element_size() if labels else 0), _ptr(cf), _ptr(pr), _ptr(gt),
+                                           c_int(gt.element_size()), c_int(1 if raw_labels else 0), _ptr(areas), _ptr(tally),
+                                           _stream()), "seg_score_views")
+    return areas, tally, lab, cf, pr
 
 
 _image_luts = {}         # (mean, std, device) -> fp32 [3, 256] on the device; at most 16 entries

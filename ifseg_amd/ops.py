@@ -19,7 +19,8 @@ The second half of the file puts the training-path kernels there as well (see th
 kernels, with key counts and attention dropout) and `seg_loss` (csrc/loss.hip), with `*_bwd` ops of their own;
 `ifseg_amd.modules.MultiheadAttention` composes `linear` and `attention_bias` under the reference module's parameter names.
 `seg_predict` (csrc/predict.hip: label maps at image resolution), `seg_predict_views` (the same from the mean of K views of
-differing grids, mirrored ones included: multi-scale + flip inference) and `image_load` (csrc/imgload.hip: raw uint8 images to
+differing grids, mirrored ones included: multi-scale + flip inference), `seg_areas` / `seg_score_views` (label maps counted
+against ground truth, stand-alone and in the predict kernel's epilogue: mIoU on the device) and `image_load` (csrc/imgload.hip: raw uint8 images to
 normalised patch_images, the reference's evaluation transform) are inference only and have no backward; `train_load`
 (csrc/trainload.hip: raw images and label maps of any sizes to a training batch under given records, the reference's training
 transform) has integer inputs and no backward either.
@@ -758,6 +759,86 @@ def _(scores, hps, wps, flips, h, w, want_conf, want_probs):
     B, n, ldt = _seg_predict_views_check(scores, hps, wps, flips, h, w)
     f32, s = torch.float32, scores[0]
     return (s.new_empty(B, h, w, dtype=ldt), s.new_empty((B, h, w) if want_conf else (0,), dtype=f32),
+            s.new_empty((B, n, h, w) if want_probs else (0,), dtype=f32))
+
+
+# ----------------------------------------------------------------------------------------------- seg_areas
+def _gt_check(op, gt):
+    if gt.dtype not in (torch.uint8, torch.int16):
+        raise ValueError("%s: ground truth must be uint8 or int16 (label PNG values or class ids), got dtype %s" % (op, gt.dtype))
+
+
+def _seg_areas_check(labels, gt, n):
+    op = "ifseg::seg_areas"
+    if labels.dtype not in (torch.uint8, torch.int16):
+        raise ValueError("%s: labels must be uint8 or int16 (what seg_predict gives), got dtype %s" % (op, labels.dtype))
+    _gt_check(op, gt)
+    if labels.shape != gt.shape:
+        raise ValueError("%s: labels %s and ground truth %s must have one shape" % (op, tuple(labels.shape), tuple(gt.shape)))
+    if labels.numel() < 1 or labels.numel() >= 2 ** 31:
+        raise ValueError("%s: 1 <= pixels < 2**31, got %s" % (op, tuple(labels.shape)))
+    if n < 1 or n > SEG_LOSS_MAX_CLASSES:
+        raise ValueError("%s: n = %d classes, the kernel takes 1 .. FUSED_MAX_CLASSES = %d" % (op, n, SEG_LOSS_MAX_CLASSES))
+
+
+@custom_op("ifseg::seg_areas", mutates_args=(), device_types="cuda")
+def seg_areas(labels: torch.Tensor, gt: torch.Tensor, n: int, raw_labels: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """predicted labels (uint8 / int16) against ground truth (uint8 / int16) of the same shape (csrc/predict.hip) ->
+    (areas int64 [3, n] = per class intersect / predicted / label pixel counts over the scored pixels, tally int64 [2] = scored
+    pixels, pixels with a ground truth out of range), fresh tensors; `ifseg_amd.predict.areas_reference` is the specification.
+    Integer inputs: not differentiable."""
+    _seg_areas_check(labels, gt, n)
+    prev = _stream_scope(labels)
+    try:
+        return hip.seg_areas(labels.contiguous(), gt.contiguous(), n, raw_labels)
+    finally:
+        hip.set_stream(prev)
+
+
+@seg_areas.register_fake
+def _(labels, gt, n, raw_labels):
+    _seg_areas_check(labels, gt, n)
+    return labels.new_empty((3, n), dtype=torch.int64), labels.new_empty((2,), dtype=torch.int64)
+
+
+# ----------------------------------------------------------------------------------------------- seg_score_views
+def _seg_score_views_check(scores, hps, wps, flips, gt):
+    op = "ifseg::seg_score_views"
+    _gt_check(op, gt)
+    if gt.dim() != 3:
+        raise ValueError("%s: ground truth must be [B, h, w], got %s" % (op, tuple(gt.shape)))
+    B, n, ldt = _seg_predict_views_check(scores, hps, wps, flips, gt.shape[1], gt.shape[2])
+    if gt.shape[0] != B:
+        raise ValueError("%s: ground truth %s for a batch of %d" % (op, tuple(gt.shape), B))
+    return B, n, ldt
+
+
+@custom_op("ifseg::seg_score_views", mutates_args=(), device_types="cuda")
+def seg_score_views(scores: Sequence[torch.Tensor], hps: Sequence[int], wps: Sequence[int], flips: Sequence[bool], gt: torch.Tensor,
+                    raw_labels: bool, want_labels: bool, want_conf: bool, want_probs: bool
+                    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """`seg_predict_views` at the shape of the ground truth gt (uint8 / int16 [B, h, w]) with the label map counted against it
+    in the kernel's epilogue (a single view is K = 1) -> (areas, tally, labels, conf, probs): the counters of `seg_areas`,
+    fresh, and the outputs of `seg_predict_views`, each an empty tensor when it was not asked for.  Not differentiable."""
+    _seg_score_views_check(scores, hps, wps, flips, gt)
+    prev = _stream_scope(scores[0])
+    try:
+        views = [(s.contiguous(), hp, wp, bool(f)) for s, hp, wp, f in zip(scores, hps, wps, flips)]
+        areas, tally, labels, conf, probs = hip.seg_score_views(views, gt.contiguous(), raw_labels, labels=want_labels,
+                                                                conf=want_conf, probs=want_probs)
+        e = lambda t, dt: torch.empty(0, dtype=dt, device=gt.device) if t is None else t
+        ldt = torch.uint8 if scores[0].shape[2] <= 256 else torch.int16
+        return areas, tally, e(labels, ldt), e(conf, torch.float32), e(probs, torch.float32)
+    finally:
+        hip.set_stream(prev)
+
+
+@seg_score_views.register_fake
+def _(scores, hps, wps, flips, gt, raw_labels, want_labels, want_conf, want_probs):
+    B, n, ldt = _seg_score_views_check(scores, hps, wps, flips, gt)
+    f32, s, (h, w) = torch.float32, scores[0], gt.shape[1:]
+    return (s.new_empty((3, n), dtype=torch.int64), s.new_empty((2,), dtype=torch.int64),
+            s.new_empty((B, h, w) if want_labels else (0,), dtype=ldt), s.new_empty((B, h, w) if want_conf else (0,), dtype=f32),
             s.new_empty((B, n, h, w) if want_probs else (0,), dtype=f32))
 
 

@@ -21,6 +21,17 @@ never turns this on, so there is no golden for it: parity is to the specificatio
 distinct view size is one more entry of the engine's resized-bias cache (`engine.py:_resized_biases`), whose entries grow
 with the square of the grid; the views are therefore run size by size (`imageio.plan_views`).
 
+Scoring against ground truth: `seg.evaluate_raw(photos, label_maps, ...)` is `segment_raw` with the same arguments whose last
+launch per image also counts the label map against the image's ground truth (`hip.seg_score` / `hip.seg_score_views`: the
+predict kernels with the counting in their epilogue; `hip.seg_areas` behind the CRF), into one `SegmentationScore` on the
+device; `score.summary()` gives aAcc / mIoU / mAcc by `SegCriterion.reduce_metrics`' formulas and is the only host round trip.
+`areas_reference` is the specification of the counters.  With upsample="logits" and one view this is the reference's
+`valid_step` metric (seg_criterion.py:289-347); with the defaults it is the demo's order, probabilities resized.
+
+    score = seg.evaluate_raw(photos, label_pngs, scales=(0.5, 0.75, 1.0, 1.25, 1.5, 1.75), flip=True)   # uint8 [H_i, W_i] maps
+    for more in batches: seg.evaluate_raw(*more, into=score)                                             # a whole validation set
+    score.summary()                                    # {"aAcc", "mIoU", "mAcc", "IoU": [n], "Acc": [n], "pixels"}
+
 Nothing in the call synchronises with the host; `labels`, `conf` and `probs` stay on the device.  There is no CPU fallback:
 `upsample_argmax_reference` is the specification the tests compare against, not a second implementation of the path.
 """
@@ -72,6 +83,79 @@ def upsample_views_reference(views, h, w, dtype=torch.float64):
     probs = total * torch.tensor(1.0 / len(views), dtype=dtype, device=total.device)
     labels = probs.argmax(dim=1)
     return labels, probs.gather(1, labels[:, None]).squeeze(1), probs
+
+
+def areas_reference(labels, gt, n, raw_labels=True):
+    """Specification of the scoring counters (hip.seg_areas, hip.seg_score, hip.seg_score_views): labels integer [..., h, w]
+    (predicted classes), gt uint8 / int16 of the same shape -> (areas int64 [3, n], tally int64 [2]).
+
+    Ground truth, raw_labels=True (augment.remap_label's rule, segmentation_dataset.py:231-233): raw 0 and raw 255 are ignored,
+    any other x is class x - 1.  raw_labels=False: the value is the class id, n ('unknown') and 255 are ignored.  A class id
+    outside [0, n) that is not an ignore value is out of range: not scored, counted in tally[1].  tally[0] is the number of
+    scored pixels; over those only (seg_criterion.py:306-314 drops masked pixels from the prediction histogram too, :349-362)
+    areas[0][c] = #(pred = c and gt = c), areas[1][c] = #(pred = c), areas[2][c] = #(gt = c).  A predicted label outside
+    [0, n) on a scored pixel is in no bin of areas[0] and areas[1].  Runs on any device."""
+    labels, gt = torch.as_tensor(labels), torch.as_tensor(gt)
+    if gt.dtype not in (torch.uint8, torch.int16):
+        raise ValueError("areas_reference: ground truth must be uint8 or int16, got %s" % gt.dtype)
+    if labels.dtype.is_floating_point or labels.dtype == torch.bool or labels.shape != gt.shape:
+        raise ValueError("areas_reference: labels must be integer and of the ground truth's shape %s, got %s %s"
+                         % (tuple(gt.shape), labels.dtype, tuple(labels.shape)))
+    pred, g = labels.reshape(-1).long(), gt.reshape(-1).long().to(labels.device)
+    ignored = (g == 0) | (g == 255) if raw_labels else (g == n) | (g == 255)
+    cls = g - 1 if raw_labels else g
+    in_range = (cls >= 0) & (cls < n)
+    scored = ~ignored & in_range
+    tally = torch.stack([scored.sum(), (~ignored & ~in_range).sum()])
+    pred, cls = pred[scored], cls[scored]
+    known = (pred >= 0) & (pred < n)
+    areas = torch.stack([torch.bincount(pred[known & (pred == cls)], minlength=n), torch.bincount(pred[known], minlength=n),
+                         torch.bincount(cls, minlength=n)])
+    return areas, tally
+
+
+class SegmentationScore:
+    """The counters of `areas_reference` on the device, summed over everything scored into them: `areas` int64 [3, n],
+    `tally` int64 [2].  The scoring kernels add to these tensors in place."""
+
+    def __init__(self, n, device=None, areas=None, tally=None):
+        self.n = int(n)
+        self.areas = torch.zeros(3, self.n, dtype=torch.int64, device=device) if areas is None else areas
+        self.tally = torch.zeros(2, dtype=torch.int64, device=device) if tally is None else tally
+        if self.areas.dtype != torch.int64 or tuple(self.areas.shape) != (3, self.n) or self.tally.dtype != torch.int64 \
+                or tuple(self.tally.shape) != (2,) or self.areas.device != self.tally.device:
+            raise ValueError("SegmentationScore: areas must be int64 [3, %d] and tally int64 [2] on one device, got %s %s and %s %s"
+                             % (self.n, self.areas.dtype, tuple(self.areas.shape), self.tally.dtype, tuple(self.tally.shape)))
+
+    def add_(self, other):
+        if other.n != self.n:
+            raise ValueError("SegmentationScore.add_: %d classes against %d" % (other.n, self.n))
+        self.areas += other.areas.to(self.areas.device)
+        self.tally += other.tally.to(self.tally.device)
+        return self
+
+    def logging_output(self):
+        """the four histograms under the reference's keys, as `SegCriterion.reduce_metrics` takes them (float64, not the
+        reference's float32: the counts of a validation set pass 2^24)"""
+        a = self.areas.double()
+        return {"area_intersect": a[0], "area_pred_label": a[1], "area_label": a[2], "area_union": a[1] + a[2] - a[0]}
+
+    def summary(self):
+        """-> {"aAcc", "mIoU", "mAcc", "IoU": [n], "Acc": [n], "pixels"} by `SegCriterion.reduce_metrics`' formulas and rounding
+        (nanmean over the classes, round(..., 4)).  The one place that synchronises with the host.  Ground truth out of range
+        is an IndexError: the reference's F.cross_entropy fails on such a label, and a score that left pixels out is not
+        reported as if it had not."""
+        m, n = self.logging_output(), self.n
+        ai, ap, al, au = m["area_intersect"], m["area_pred_label"], m["area_label"], m["area_union"]
+        iou, acc = ai / au, ai / al
+        flat = torch.cat([torch.stack([ai.sum() / ap.sum(), torch.nanmean(iou), torch.nanmean(acc)]), iou, acc,
+                          self.tally.double()]).tolist()
+        if flat[-1] != 0:
+            raise IndexError("SegmentationScore: tally[1] = %d ground-truth pixels hold a class outside [0, %d) that is not an "
+                             "ignore value (wrong raw_labels, or a label map of another dataset?)" % (int(flat[-1]), n))
+        r4 = lambda v: round(float(v), 4)
+        return {"aAcc": r4(flat[0]), "mIoU": r4(flat[1]), "mAcc": r4(flat[2]), "IoU": [r4(v) for v in flat[3:3 + n]],
+                "Acc": [r4(v) for v in flat[3 + n:3 + 2 * n]], "pixels": int(flat[-2])}
 
 
 def source_tokens(category_token_ids, prompt_ids=PROMPT_IDS, num_seg_tokens=None):
@@ -260,25 +344,46 @@ class Segmenter:
         mean of the resized, un-mirrored scores, which is also what the CRF takes.  At most 16 views; more than one view
         needs upsample="probs" (averaging raw logits is not mmseg's rule).  The default is the single view above: the same
         launches as without these arguments, `hip.seg_predict` at the end."""
+        checked = self._check_raw("segment_raw", images, scales, flip)
+        if checked is None:
+            return []
+        imgs, shapes, per_image = self._raw_views(*checked, max_batch, mean, std, reverse_channels)
+        crf, out = self.crf_iters > 0, []
+        with torch.no_grad():
+            for i, vs in enumerate(per_image):
+                (H, W), rgb = shapes[i], imgs[i][None].float() if crf else None
+                if len(vs) == 1 and not vs[0][3]:             # one plain view: the single-view kernel
+                    r = self._finish(*vs[0][:3], H, W, rgb, return_conf, return_probs)
+                else:
+                    r = self._finish_views(vs, H, W, rgb, return_conf, return_probs)
+                out.append(SegmentationResult(*(None if t is None else t[0] for t in r)))
+        return out
+
+    def _check_raw(self, what, images, scales, flip):
+        """the arguments of `segment_raw` / `evaluate_raw`, checked on the host -> (the (ratio, flip) views, the images as a
+        list, scales, flip), or None for an empty list"""
         views = view_list(scales, flip)
         if len(views) > 1 and self.upsample != "probs":
-            raise ValueError("Segmenter.segment_raw: %d views need upsample='probs' (mmseg averages the resized probabilities; "
-                             "averaging raw logits is not its rule), this Segmenter has upsample=%r" % (len(views), self.upsample))
-        single = torch.is_tensor(images)
-        imgs = [images] if single else list(images)
+            raise ValueError("Segmenter.%s: %d views need upsample='probs' (mmseg averages the resized probabilities; "
+                             "averaging raw logits is not its rule), this Segmenter has upsample=%r" % (what, len(views), self.upsample))
+        imgs = [images] if torch.is_tensor(images) else list(images)
         if not imgs:
-            return []
+            return None
         for im in imgs:
             if not torch.is_tensor(im) or im.dtype != torch.uint8 or im.dim() != 3 or im.shape[-1] != 3 or im.numel() == 0:
-                raise ValueError("Segmenter.segment_raw: every image must be a uint8 RGB [H, W, 3] tensor, got %s"
-                                 % ((im.dtype, tuple(im.shape)) if torch.is_tensor(im) else type(im),))
+                raise ValueError("Segmenter.%s: every image must be a uint8 RGB [H, W, 3] tensor, got %s"
+                                 % (what, (im.dtype, tuple(im.shape)) if torch.is_tensor(im) else type(im),))
+        return views, imgs, scales, flip
+
+    def _raw_views(self, views, imgs, scales, flip, max_batch, mean, std, reverse_channels):
+        """the front of `segment_raw` and `evaluate_raw`: every image loaded once per ratio, one forward per network size ->
+        (the images on the device, their (H, W), per image its views (scores [1, hp*wp, n], hp, wp, flip) in view order)"""
         mean, std = HALF if mean is None else mean, HALF if std is None else std
         dev = next(self.model.parameters()).device
         imgs = [im.to(dev, non_blocking=True) for im in imgs]
         shapes = [(int(im.shape[0]), int(im.shape[1])) for im in imgs]
         _, loads, forwards = plan_views(shapes, self.model.cfg.patch_image_size, scales, flip, max_batch)
-        crf = self.crf_iters > 0
-        x, per_image, out = {}, [[None] * len(views) for _ in imgs], []
+        x, per_image = {}, [[None] * len(views) for _ in imgs]
         with torch.no_grad():
             for _, size, idx in loads:
                 t = hip.image_load(torch.stack([imgs[i] for i in idx]), size[0], size[1], mean, std, reverse_channels)
@@ -288,11 +393,87 @@ class Segmenter:
                 scores, hp, wp = self.patch_scores(torch.stack([x[i, size].flip(-1) if views[v][1] else x[i, size] for i, v in iv]))
                 for k, (i, v) in enumerate(iv):
                     per_image[i][v] = (scores[k:k + 1], hp, wp, views[v][1])
+        return imgs, shapes, per_image
+
+    # -- scoring against ground truth -----------------------------------------------------
+    def _score_into(self, what, into, dev):
+        if into is None:
+            return SegmentationScore(self.n, dev)
+        if not isinstance(into, SegmentationScore) or into.n != self.n or into.areas.device != dev:
+            raise ValueError("Segmenter.%s: into must be a SegmentationScore of %d classes on %s" % (what, self.n, dev))
+        return into
+
+    def _score(self, score, vs, gt, raw_labels, rgb, return_labels):
+        """one image's (or batch's) views against gt [B, h, w] into `score` -> its labels [B, h, w] or None"""
+        kw = dict(raw_labels=raw_labels, areas=score.areas, tally=score.tally)
+        h, w = int(gt.shape[1]), int(gt.shape[2])
+        if self.crf_iters > 0:                                # the label map comes from the CRF, not from the predict kernel
+            one = len(vs) == 1 and not vs[0][3]
+            labels = (self._finish(*vs[0][:3], h, w, rgb, False, False) if one else self._finish_views(vs, h, w, rgb, False, False)).labels
+            hip.seg_areas(labels.contiguous(), gt, self.n, **kw)
+            return labels if return_labels else None
+        if len(vs) == 1 and not vs[0][3]:
+            return hip.seg_score(*vs[0][:3], gt, labels=return_labels, label_dtype=self.label_dtype, **kw)[2]
+        return hip.seg_score_views(vs, gt, labels=return_labels, label_dtype=self.label_dtype, **kw)[2]
+
+    def evaluate_raw(self, images, label_maps, raw_labels=True, scales=(1.0,), flip=False, max_batch=8, mean=None, std=None,
+                     reverse_channels=False, into=None, return_labels=False):
+        """`segment_raw` scored against ground truth on the device -> a `SegmentationScore` (or (score, [labels [H_i, W_i], ...])
+        with `return_labels`, the labels being `segment_raw`'s).
+
+        images, scales, flip, max_batch, mean, std, reverse_channels: as in `segment_raw`, whose pipeline this runs unchanged
+        up to the last launch per image; that launch (`hip.seg_score` / `hip.seg_score_views`) also counts the label map it
+        decides on against the image's ground truth and, without `return_labels`, writes nothing else.  With the CRF on, the
+        CRF's argmax is counted by `hip.seg_areas`.
+        label_maps: one uint8 / int16 [H, W] tensor or a list, on the host or the device, entry i of image i's shape.
+        raw_labels=True: the label PNGs' values, 0 and 255 ignored and x -> class x - 1 (`areas_reference` states the rule);
+        False: class ids, n and 255 ignored.  into: a score to accumulate into (a whole validation set needs no host round
+        trip; `summary()` is the only one).  A mismatch of count, shape or dtype is a ValueError before anything is launched."""
+        checked = self._check_raw("evaluate_raw", images, scales, flip)
+        gts = [label_maps] if torch.is_tensor(label_maps) else list(label_maps)
+        imgs = [] if checked is None else checked[1]
+        if len(gts) != len(imgs):
+            raise ValueError("Segmenter.evaluate_raw: %d label maps for %d images" % (len(gts), len(imgs)))
+        for i, (im, g) in enumerate(zip(imgs, gts)):
+            if not torch.is_tensor(g) or g.dtype not in (torch.uint8, torch.int16) or tuple(g.shape) != tuple(im.shape[:2]):
+                raise ValueError("Segmenter.evaluate_raw: label map %d must be a uint8 or int16 tensor of its image's shape %s, got %s"
+                                 % (i, tuple(im.shape[:2]), (g.dtype, tuple(g.shape)) if torch.is_tensor(g) else type(g)))
+        dev = next(self.model.parameters()).device
+        score = self._score_into("evaluate_raw", into, dev)
+        if checked is None:
+            return (score, []) if return_labels else score
+        gts = [g.to(dev, non_blocking=True).contiguous() for g in gts]
+        imgs, shapes, per_image = self._raw_views(*checked, max_batch, mean, std, reverse_channels)
+        crf, out = self.crf_iters > 0, []
+        with torch.no_grad():
             for i, vs in enumerate(per_image):
-                (H, W), rgb = shapes[i], imgs[i][None].float() if crf else None
-                if len(vs) == 1 and not vs[0][3]:             # one plain view: the single-view kernel
-                    r = self._finish(*vs[0][:3], H, W, rgb, return_conf, return_probs)
-                else:
-                    r = self._finish_views(vs, H, W, rgb, return_conf, return_probs)
-                out.append(SegmentationResult(*(None if t is None else t[0] for t in r)))
-        return out
+                labels = self._score(score, vs, gts[i][None], raw_labels, imgs[i][None].float() if crf else None, return_labels)
+                out.append(None if labels is None else labels[0])
+        return (score, out) if return_labels else score
+
+    def evaluate(self, images, label_maps, raw_labels=True, into=None, return_labels=False):
+        """`__call__` scored against ground truth: images as `__call__` takes them (normalised float [B, 3, H, W] or uint8 RGB
+        [B, H, W, 3] / [H, W, 3]), label_maps uint8 / int16 [B, h, w] (or [h, w] for one image): the label map is taken at the
+        ground truth's own size, as `out_hw` would.  -> a `SegmentationScore`, or (score, labels [B, h, w]) with `return_labels`;
+        raw_labels, into: as in `evaluate_raw`."""
+        gt = label_maps
+        if not torch.is_tensor(gt) or gt.dtype not in (torch.uint8, torch.int16) or gt.dim() not in (2, 3) or gt.numel() == 0:
+            raise ValueError("Segmenter.evaluate: label_maps must be a uint8 or int16 tensor [B, h, w], got %s"
+                             % ((gt.dtype, tuple(gt.shape)) if torch.is_tensor(gt) else type(gt),))
+        gt = gt[None] if gt.dim() == 2 else gt
+        if torch.is_tensor(images) and images.dim() >= 3 and gt.shape[0] != (1 if images.dim() == 3 else images.shape[0]):
+            raise ValueError("Segmenter.evaluate: %d label maps for images %s" % (gt.shape[0], tuple(images.shape)))
+        patch_images, rgb = self.prepare_images(images)
+        B, _, H, W = patch_images.shape
+        crf = self.crf_iters > 0
+        if crf and tuple(gt.shape[1:]) != (H, W):
+            raise ValueError("Segmenter.evaluate: with the CRF on, the label maps must have the images' size %s, got %s"
+                             % ((H, W), tuple(gt.shape[1:])))
+        score = self._score_into("evaluate", into, patch_images.device)
+        if crf and rgb is None:
+            rgb = ((patch_images.float() * 0.5 + 0.5) * 255.0).permute(0, 2, 3, 1).contiguous()
+        scores, hp, wp = self.patch_scores(patch_images)
+        with torch.no_grad():
+            labels = self._score(score, [(scores, hp, wp, False)], gt.to(patch_images.device).contiguous(), raw_labels, rgb,
+                                 return_labels)
+        return (score, labels) if return_labels else score

@@ -584,6 +584,35 @@ int ifseg_seg_predict_views(const ifseg_predict_view* views, int K, int B, int n
                             float* conf, float* probs, void* stream);
 int ifseg_seg_predict_views_staging(int max_bytes);
 
+/* ---- scoring against ground truth on the device (Segmenter.evaluate_raw; the reference's valid_step metric,
+ * seg_criterion.py:306-314, 349-362, for any number of images and views) ----
+ * Counters: areas uint64 [3, n] = per class #(pred = c and gt = c), #(pred = c), #(gt = c) over the SCORED pixels, tally
+ * uint64 [2] = #scored pixels, #pixels whose ground truth is out of range.  Ground truth is uint8 (gt_bytes 1) or int16 (2):
+ *   raw_labels != 0   0 and 255 are ignored, any other x is class x - 1 (segmentation_dataset.py:231-233)
+ *   raw_labels == 0   n and 255 are ignored, any other x is class x
+ * a class outside [0, n) is out of range: not scored, counted in tally[1].  Every entry point ADDS to areas and tally (64-bit
+ * integer atomics, one per workgroup and non-zero bin; the sums do not depend on the order) and never clears them.
+ * A predicted label outside [0, n) -- only ifseg_seg_areas can be handed one -- is counted in tally[0] and areas[2] alone.
+ *
+ * ifseg_seg_areas scores npix predicted labels (uint8, label_bytes 1, or int16, 2) against npix ground-truth values; both
+ * pointers may have any element alignment.  NULL labels / gt / areas / tally, label_bytes or gt_bytes outside {1, 2}, n
+ * outside 1..512, an int16 pointer at an odd address, areas or tally not 8-byte aligned: IFSEG_ERR_BAD_ARG; npix < 1 or
+ * >= 2^31: IFSEG_ERR_BAD_SHAPE.
+ *
+ * ifseg_seg_score / ifseg_seg_score_views are ifseg_seg_predict / ifseg_seg_predict_views with the counting in the kernel's
+ * epilogue: gt is [B, h, w].  labels, conf and probs are ALL optional here (NULL: not written; label_bytes is then ignored);
+ * what is written is what the predict entry point writes, bit for bit, for the same staging decision (the counters' table
+ * takes (3 n + 2) * 4 bytes of the LDS staging budget).  The refusals of the predict entry points, and as above for gt,
+ * gt_bytes, areas and tally; nothing is launched on a refusal.  The *_staging setters apply. */
+int ifseg_seg_areas(const void* labels, int label_bytes, const void* gt, int gt_bytes, long long npix, int n, int raw_labels,
+                    unsigned long long* areas, unsigned long long* tally, void* stream);
+int ifseg_seg_score(const float* scores, int B, int hp, int wp, int n, int h, int w, void* labels, int label_bytes, float* conf,
+                    float* probs, const void* gt, int gt_bytes, int raw_labels, unsigned long long* areas,
+                    unsigned long long* tally, void* stream);
+int ifseg_seg_score_views(const ifseg_predict_view* views, int K, int B, int n, int h, int w, void* labels, int label_bytes,
+                          float* conf, float* probs, const void* gt, int gt_bytes, int raw_labels, unsigned long long* areas,
+                          unsigned long long* tally, void* stream);
+
 /* ---- raw images in (ifseg_amd/predict.py Segmenter.segment_raw; the reference's evaluation transform: Resize(keep_ratio),
  * Normalize of :148-156; the dataset's two channel reversals, :218 and :256, cancel, so reverse_channels is 0 for a
  * checkpoint tuned by the reference) ----
