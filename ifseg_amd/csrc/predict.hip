@@ -512,6 +512,197 @@ __global__ __launch_bounds__(256) void seg_predict_views_kernel(ViewTable views,
   }
 }
 
+// ---- the windows of one image into one label map (sliding-window inference) ----
+// scores [B, Nw, hpw * wpw, n]: window k = iy gx + ix of the [oh, ow] plane (tile.h's SlideAxis) ran the network on its own
+// hpw x wpw grid.  A pixel of the [h, w] output takes its (up to four) taps in the plane by the coordinate rule; per tap the
+// flat four-weight values of the windows that hold it are added in window order (rows outer) and divided by their number; a
+// tap of weight zero contributes nothing.  Neither a window's [n, ch, cw] tensor nor the plane is ever written.
+// The tile, the lane mapping, the class chunks, add_view and phase 2 are those of seg_predict_views_kernel.  The windows are a
+// cross product, so everything is kept per axis: the windows iya..iyb / ixa..ixb hold the tile's plane footprint, each with its
+// own run of patch rows / columns under it, and the runs of an axis laid end to end span a staged grid of FH x FW patches
+// (PV_CHUNK classes each, at the odd-slot stride) in which window (i, j) owns the block rows(i) x cols(j).  A tile whose
+// grid does not fit the buffer reads global memory in the same loop.
+constexpr int SW_MAX_WINDOWS = IFSEG_SLIDE_MAX_WINDOWS;
+constexpr int SW_META_LDS = 3 * 2 * SW_MAX_WINDOWS * 4 + 16;      // sw_lo, sw_ext, sw_adj, sw_tot
+constexpr int SW_STAGE_LIMIT = 65536 - PT_TILE_LDS - SW_META_LDS; // source cells + staged patches
+
+int g_windows_stage_limit = SW_STAGE_LIMIT;
+
+struct Slide {
+  SlideAxis y, x;
+  int hpw, wpw;
+};
+
+// out += wt * (acc / cnt) where wt != 0: a rounded quotient, a rounded product, a rounded sum
+__device__ __forceinline__ void add_tap(f32x4 (&out)[PV_CHUNK / 4], const f32x4 (&acc)[PV_CHUNK / 4], float cnt, float wt) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int c = 0; c < PV_CHUNK / 4; ++c) {
+    const f32x4 v = out[c] + wt * (acc[c] / cnt);
+    if (wt != 0.f) out[c] = v;
+  }
+}
+
+// one pixel's PV_CHUNK classes: plane rows Yt[0..1] (weight 1 - ly2, ly2; wave-uniform), plane columns Xt[0..1] (1 - lx2, lx2).
+// VEC: s is the staged grid, adj the runs' offsets in it, rowlen = FW PV_STRIDE; else s is the image's windows in global memory
+template <bool VEC>
+__device__ __forceinline__ void slide_pixel(const float* s, const Slide& sl, const FloatCoord& cwy, const FloatCoord& cwx,
+                                            const int (&adj)[2][SW_MAX_WINDOWS], int iya, int ixa, int rowlen, int n, int cn,
+                                            const int (&Yt)[2], float ly2, const int (&Xt)[2], float lx2, bool anyx1,
+                                            f32x4 (&out)[PV_CHUNK / 4]) {
+  const int cells = sl.hpw * sl.wpw;
+  const int nty = ly2 != 0.f ? 2 : 1, ntx = anyx1 ? 2 : 1;
+  for (int ty = 0; ty < nty; ++ty) {
+    const int Y = Yt[ty], ia = sl.y.first(Y), ib = sl.y.last(Y);
+    const float wy = ty ? ly2 : 1.f - ly2;
+    for (int tx = 0; tx < ntx; ++tx) {
+      const int X = Xt[tx], ja = sl.x.first(X), jb = sl.x.last(X);
+      const float wx = tx ? lx2 : 1.f - lx2;
+      f32x4 acc[PV_CHUNK / 4];
+#pragma unroll
+      for (int c = 0; c < PV_CHUNK / 4; ++c) acc[c] = f32x4{-0.f, -0.f, -0.f, -0.f};
+      for (int i = ia; i <= ib; ++i) {
+        int p0, p1, q0, q1;
+        float ly, lx;
+        cwy(Y - sl.y.start(i), &p0, &p1, &ly);
+        const int rb = VEC ? adj[0][i - iya] * rowlen : i * sl.x.g * cells * n, rl = VEC ? rowlen : sl.wpw * n;
+        for (int j = ja; j <= jb; ++j) {
+          cwx(X - sl.x.start(j), &q0, &q1, &lx);
+          const int cb = VEC ? adj[1][j - ixa] * PV_STRIDE : j * cells * n, cl = VEC ? PV_STRIDE : n;
+          const float* r0 = s + (rb + p0 * rl + cb);
+          const float* r1 = s + (rb + p1 * rl + cb);
+          add_view<VEC>(r0 + q0 * cl, r0 + q1 * cl, r1 + q0 * cl, r1 + q1 * cl, cn, ly, lx, acc);
+        }
+      }
+      add_tap(out, acc, (float)((ib - ia + 1) * (jb - ja + 1)), wy * wx);
+    }
+  }
+}
+
+template <typename S>
+__global__ __launch_bounds__(256) void seg_predict_windows_kernel(const float* __restrict__ scores, Slide sl, int n, int h, int w,
+                                                                  int tiles_x, int tiles_y, void* __restrict__ labels,
+                                                                  int label_bytes, float* __restrict__ conf,
+                                                                  float* __restrict__ probs, int stage_floats, S sc) {
+  // (scoring: the table,) the source cells of the staged rows and columns, then the staged grid: stage_floats in all
+  extern __shared__ __attribute__((aligned(16))) float dyn[];
+  __shared__ int t_lab[TILE_ROWS][TILE_COLS];
+  __shared__ float t_conf[TILE_ROWS][TILE_COLS];
+  // per axis (0: y, 1: x) and window of the tile's range: first patch of its run, their number, run offset - first patch
+  __shared__ int sw_lo[2][SW_MAX_WINDOWS], sw_ext[2][SW_MAX_WINDOWS], sw_adj[2][SW_MAX_WINDOWS], sw_tot[2];
+  int* cellsrc = reinterpret_cast<int*>(dyn);
+  if constexpr (S::on) {
+    score_zero(reinterpret_cast<uint32_t*>(dyn), n);              // published by the barriers below
+    cellsrc += score_dwords(n);
+  }
+
+  const auto [b, X0, Y0, xend, yend, lane, wave] = tile_decode(tiles_x, tiles_y, h, w);
+  const FloatCoord c2y{(float)sl.y.o / (float)h, sl.y.o}, c2x{(float)sl.x.o / (float)w, sl.x.o};            // output -> plane
+  const FloatCoord cwy{(float)sl.hpw / (float)sl.y.e, sl.hpw}, cwx{(float)sl.wpw / (float)sl.x.e, sl.wpw};  // window -> grid
+  const int cells = sl.hpw * sl.wpw;
+  const float* sb = scores + (long long)b * sl.y.g * sl.x.g * cells * n;
+
+  // the tile's footprint in the plane and the windows that hold any of it
+  int Ylo, Yhi, Xlo, Xhi;
+  footprint(c2y, Y0, yend - 1, &Ylo, &Yhi);
+  footprint(c2x, X0, xend - 1, &Xlo, &Xhi);
+  const int iya = sl.y.first(Ylo), ny = sl.y.last(Yhi) - iya + 1, ixa = sl.x.first(Xlo), nx = sl.x.last(Xhi) - ixa + 1;
+  const int t = threadIdx.x;
+  const bool isx = t >= ny;
+  const int ai = isx ? t - ny : t;                                // thread t < ny + nx takes one window of one axis
+  if (t < ny + nx) {
+    const SlideAxis a = isx ? sl.x : sl.y;
+    const int st = a.start((isx ? ixa : iya) + ai), lo = isx ? Xlo : Ylo, hi = isx ? Xhi : Yhi;
+    int plo, phi;
+    footprint(isx ? cwx : cwy, max(lo, st) - st, min(hi, st + a.e - 1) - st, &plo, &phi);
+    sw_lo[isx][ai] = plo; sw_ext[isx][ai] = phi - plo + 1;
+  }
+  __syncthreads();
+  if (t < 2) {
+    int used = 0;
+    for (int k = 0; k < (t ? nx : ny); ++k) { sw_adj[t][k] = used - sw_lo[t][k]; used += sw_ext[t][k]; }
+    sw_tot[t] = used;
+  }
+  __syncthreads();
+  const int FH = sw_tot[0], FW = sw_tot[1], ncs = (FH + FW + 3) & ~3;
+  const bool staged = (long long)FH * FW * PV_STRIDE + ncs <= (long long)stage_floats;          // workgroup-uniform
+  float* stage = reinterpret_cast<float*>(cellsrc + ncs);
+  if (staged && t < ny + nx) {
+    // the source of staged row R / column C, in patches from the image's first window: cellsrc[R] + cellsrc[FH + C]
+    const int i = (isx ? ixa : iya) + ai, first = sw_adj[isx][ai] + sw_lo[isx][ai];
+    for (int r = 0; r < sw_ext[isx][ai]; ++r)
+      cellsrc[(isx ? FH : 0) + first + r] = isx ? i * cells + sw_lo[1][ai] + r : i * sl.x.g * cells + (sw_lo[0][ai] + r) * sl.wpw;
+  }
+  __syncthreads();
+
+  const int x = min(X0 + lane, w - 1);
+  int Xt[2];
+  float lx2;
+  c2x(x, &Xt[0], &Xt[1], &lx2);
+  const bool anyx1 = __ballot(lx2 != 0.f) != 0;
+  float* pb = probs ? probs + (long long)b * n * h * w : nullptr;
+  const long long cstride = (long long)h * w;
+
+  for (int c0 = 0; c0 < n; c0 += PV_CHUNK) {
+    const int cn = min(PV_CHUNK, n - c0);
+    if (c0) __syncthreads();                      // the previous chunk has been read
+    // phase 0: 16 threads per patch, one class each; the classes past n are zero
+    if (staged) {
+      const int cc = t & 15;
+      for (int p = t >> 4; p < FH * FW; p += 16) {
+        const int R = p / FW, C = p - R * FW;
+        stage[p * PV_STRIDE + cc] = cc < cn ? sb[(long long)(cellsrc[R] + cellsrc[FH + C]) * n + c0 + cc] : 0.f;
+      }
+    }
+    __syncthreads();
+
+    // phase 1, row by row
+#pragma unroll 1
+    for (int j = 0; j < 4; ++j) {
+      const int row = wave * 4 + j, yr = Y0 + row;
+      int Yt[2];
+      float ly2;
+      c2y(min(yr, h - 1), &Yt[0], &Yt[1], &ly2);
+      f32x4 out[PV_CHUNK / 4];
+#pragma unroll
+      for (int c = 0; c < PV_CHUNK / 4; ++c) out[c] = f32x4{-0.f, -0.f, -0.f, -0.f};
+      if (staged) slide_pixel<true>(stage, sl, cwy, cwx, sw_adj, iya, ixa, FW * PV_STRIDE, n, cn, Yt, ly2, Xt, lx2, anyx1, out);
+      else slide_pixel<false>(sb + c0, sl, cwy, cwx, sw_adj, iya, ixa, 0, n, cn, Yt, ly2, Xt, lx2, anyx1, out);
+      float bv = c0 ? t_conf[row][lane] : -INFINITY;
+      int bc = c0 ? t_lab[row][lane] : 0;
+      const bool ok = yr < h && X0 + lane < w;
+      float* pp = pb + (long long)c0 * cstride + min(yr, h - 1) * w + x;
+#pragma unroll
+      for (int c = 0; c < PV_CHUNK; ++c) {
+        if (c < cn) {
+          const float v = out[c >> 2][c & 3];
+          if (v > bv) { bv = v; bc = c0 + c; }
+          if (pb && ok) pp[c * cstride] = v;
+        }
+      }
+      t_conf[row][lane] = bv; t_lab[row][lane] = bc;
+    }
+  }
+  __syncthreads();
+
+  // phase 2
+  if constexpr (S::on) {
+    if (labels || conf) store_tile<true>(t_lab, t_conf, b, X0, Y0, xend, h, w, labels, label_bytes, conf);
+    int pofs[4], pred[4];
+    bool ok[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int row = wave * 4 + j;
+      pofs[j] = min(Y0 + row, h - 1) * w + x;
+      ok[j] = Y0 + row < h && X0 + lane < w;
+      pred[j] = t_lab[row][lane];
+    }
+    score_tile(sc, reinterpret_cast<uint32_t*>(dyn), n, (long long)b * h * w, pofs, ok, pred);
+  } else {
+    store_tile<false>(t_lab, t_conf, b, X0, Y0, xend, h, w, labels, label_bytes, conf);
+  }
+}
+
 // ---- labels from elsewhere (the CRF's argmax, another model) against ground truth ----
 // A lane takes 16 consecutive pixels per step: their labels and their ground truth come as aligned 16-byte loads.  The body
 // starts at the first 16-byte boundary of `lab`; the ground truth of the same pixels then sits s bytes behind a boundary of
@@ -653,6 +844,42 @@ int launch_views(const ifseg_predict_view* views, int K, int B, int n, int h, in
   return 0;
 }
 
+// ifseg_seg_predict_windows (S = NoScore) and ifseg_seg_score_windows
+template <typename S>
+int launch_windows(const float* scores, int B, int hpw, int wpw, int n, int oh, int ow, int crop_h, int crop_w, int stride_h,
+                   int stride_w, int h, int w, void* labels, int label_bytes, float* conf, float* probs, void* stream, S sc) {
+  (void)hipGetLastError();
+  if (!scores) return IFSEG_ERR_BAD_ARG;
+  if ((!S::on || labels) && (!labels || (label_bytes != 1 && label_bytes != 2))) return IFSEG_ERR_BAD_ARG;
+  if (n < 1 || n > PT_MAX_CLASSES || (labels && label_bytes == 1 && n > 256)) return IFSEG_ERR_BAD_ARG;
+  if (B < 1 || hpw < 1 || wpw < 1 || h < 1 || w < 1 || (long long)B * h * w >= (1ll << 31)) return IFSEG_ERR_BAD_SHAPE;
+  if (((size_t)labels & 15) || ((size_t)conf & 15) || ((size_t)scores & 3) || ((size_t)probs & 3)) return IFSEG_ERR_BAD_ARG;
+  Slide sl = {{}, {}, hpw, wpw};
+  if (!slide_axis(oh, crop_h, stride_h, &sl.y) || !slide_axis(ow, crop_w, stride_w, &sl.x)) return IFSEG_ERR_BAD_SHAPE;
+  const long long nw = (long long)sl.y.g * sl.x.g;
+  // offsets inside one image's windows are ints: Nw hpw wpw n < 2^31
+  if (nw > SW_MAX_WINDOWS || nw * hpw * wpw >= (1ll << 31) / PT_MAX_CLASSES) return IFSEG_ERR_BAD_SHAPE;
+  int tiles_x, tiles_y;
+  long long blocks;
+  if (!tile_grid(h, w, B, &tiles_x, &tiles_y, &blocks)) return IFSEG_ERR_BAD_SHAPE;
+  // an upper bound of any tile's staged grid, per axis: the windows that hold any of the tile's plane footprint (a regular
+  // grid, + the pulled-back last one), times the patches of one window under it
+  auto axis_bound = [](const SlideAxis& a, int out, int grid, int tile) {
+    const long long plane = footprint_bound(a.o, a.o, out, tile, 3);
+    const long long windows = std::min<long long>(a.g, (plane + a.e - 1) / a.s + 2);
+    return windows * footprint_bound(grid, grid, a.e, (int)std::min<long long>(plane, a.e), 3);
+  };
+  const long long fh = axis_bound(sl.y, h, hpw, TILE_ROWS), fw = axis_bound(sl.x, w, wpw, TILE_COLS);
+  const long long need = (fh * fw * PV_STRIDE + fh + fw + 4) * 4;
+  const int counters = S::on ? score_dwords(n) * 4 : 0;
+  const int limit = std::max(std::min(g_windows_stage_limit, SW_STAGE_LIMIT - counters), 0);
+  const int stage = (int)std::min<long long>(need, limit) & ~15;
+  hipLaunchKernelGGL(seg_predict_windows_kernel<S>, dim3((unsigned)blocks), dim3(256), counters + stage, (hipStream_t)stream,
+                     scores, sl, n, h, w, tiles_x, tiles_y, labels, label_bytes, conf, probs, stage / 4, sc);
+  IFSEG_CHECK_LAUNCH();
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int ifseg_seg_predict_staging(int max_bytes) { return swap_limit(g_stage_limit, PT_STAGE_LIMIT, max_bytes); }
@@ -685,6 +912,26 @@ extern "C" int ifseg_seg_score_views(const ifseg_predict_view* views, int K, int
   if (const int rc = score_refusal(gt, gt_bytes, areas, tally)) return rc;
   return launch_views(views, K, B, n, h, w, labels, label_bytes, conf, probs, stream,
                       Score{gt, gt_bytes, raw_labels != 0, areas, tally});
+}
+
+extern "C" int ifseg_seg_predict_windows_staging(int max_bytes) {
+  return swap_limit(g_windows_stage_limit, SW_STAGE_LIMIT, max_bytes);
+}
+
+extern "C" int ifseg_seg_predict_windows(const float* scores, int B, int hpw, int wpw, int n, int oh, int ow, int crop_h,
+                                         int crop_w, int stride_h, int stride_w, int h, int w, void* labels, int label_bytes,
+                                         float* conf, float* probs, void* stream) {
+  return launch_windows(scores, B, hpw, wpw, n, oh, ow, crop_h, crop_w, stride_h, stride_w, h, w, labels, label_bytes, conf, probs,
+                        stream, NoScore{});
+}
+
+extern "C" int ifseg_seg_score_windows(const float* scores, int B, int hpw, int wpw, int n, int oh, int ow, int crop_h, int crop_w,
+                                       int stride_h, int stride_w, int h, int w, void* labels, int label_bytes, float* conf,
+                                       float* probs, const void* gt, int gt_bytes, int raw_labels, unsigned long long* areas,
+                                       unsigned long long* tally, void* stream) {
+  if (const int rc = score_refusal(gt, gt_bytes, areas, tally)) return rc;
+  return launch_windows(scores, B, hpw, wpw, n, oh, ow, crop_h, crop_w, stride_h, stride_w, h, w, labels, label_bytes, conf, probs,
+                        stream, Score{gt, gt_bytes, raw_labels != 0, areas, tally});
 }
 
 extern "C" int ifseg_seg_areas(const void* labels, int label_bytes, const void* gt, int gt_bytes, long long npix, int n,

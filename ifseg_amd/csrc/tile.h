@@ -64,6 +64,31 @@ __device__ __forceinline__ void footprint(const Coord& coord, int first, int las
   coord(last, &t, hi, &tf);
 }
 
+// ---- sliding windows (imgload.hip, predict.hip): mmseg's slide_inference rule on one axis ----
+// An axis of o samples under crop c and stride s (1 <= s <= c) carries g = max(o - c + s - 1, 0) / s + 1 windows of
+// e = min(c, o) samples; window i starts at max(min(i s + c, o) - c, 0): a regular grid whose last window is pulled back
+// inside, so the starts increase strictly and the windows that hold a sample are a contiguous range of indices.
+struct SlideAxis {
+  int o, s, e, g;
+  __host__ __device__ int start(int i) const {
+    const int end = i * s + e < o ? i * s + e : o;
+    return end - e;
+  }
+  // the first / last window that holds sample p (0 <= p < o)
+  __host__ __device__ int first(int p) const {
+    const int i = p < e ? 0 : (p - e) / s + 1;
+    return i < g - 1 ? i : g - 1;
+  }
+  __host__ __device__ int last(int p) const { return p >= o - e ? g - 1 : p / s; }
+};
+
+// false for what the rule excludes (and for sizes whose i s + e would leave 31 bits)
+inline bool slide_axis(int o, int c, int s, SlideAxis* a) {
+  if (o < 1 || c < 1 || s < 1 || s > c || o >= (1 << 30) || c >= (1 << 30)) return false;
+  *a = {o, s, std::min(c, o), std::max(o - c + s - 1, 0) / s + 1};
+  return true;
+}
+
 // ---- uint8 HWC sources -> normalised planes (imgload.hip, trainload.hip) ----
 // Dynamic LDS: the [3, 256] table first, the staged footprint behind it.
 constexpr int U8_LUT_BYTES = 3 * 256 * 4;

@@ -1188,6 +1188,68 @@ def seg_score_views(views, gt, raw_labels=True, labels=False, conf=False, probs=
     return areas, tally, lab, cf, pr
 
 
+SLIDE_MAX_WINDOWS = 64       # == IFSEG_SLIDE_MAX_WINDOWS of include/ifseg_hip.h
+
+
+def _slide_geometry(oh, ow, crop, stride):
+    """-> (oh, ow, (crop_h, crop_w), (stride_h, stride_w), Nw, ch, cw) by `imageio.slide_windows`, whose refusals become
+    assertions here as every other precondition of a binding"""
+    from .imageio import _pair, slide_windows
+    try:
+        ys, xs, ch, cw = slide_windows(oh, ow, crop, stride)
+    except ValueError as e:
+        raise AssertionError(str(e))
+    return int(oh), int(ow), _pair(crop, "crop"), _pair(stride, "stride"), len(ys) * len(xs), ch, cw
+
+
+def _windows_scores(scores, hpw, wpw, nw):
+    assert scores.dtype == torch.float32 and scores.dim() == 4 and scores.is_contiguous(), (scores.dtype, tuple(scores.shape), scores.stride())
+    B, Nw, P, n = scores.shape
+    assert Nw == nw, (tuple(scores.shape), "the window rule gives %d windows" % nw)
+    assert P == hpw * wpw and B >= 1 and hpw >= 1 and wpw >= 1, (tuple(scores.shape), hpw, wpw)
+    assert 1 <= n <= SEG_PREDICT_MAX_CLASSES, n
+    assert Nw * P < 2 ** 22, (Nw, P)
+    return B, n
+
+
+def seg_predict_windows(scores, hpw, wpw, oh, ow, crop, stride, h, w, conf=False, probs=False, staging_bytes=None, label_dtype=None):
+    """Sliding-window inference, the merge: scores fp32 [B, Nw, hpw*wpw, n], window k of `imageio.slide_windows(oh, ow, crop,
+    stride)` having run the network on its own hpw x wpw grid -> (labels, conf, probs) at h x w as `seg_predict`: every window
+    resized to its (ch, cw) by seg_predict's rule, the windows that cover a pixel of the [oh, ow] plane added in window order
+    and divided by their number, the result resized to h x w, in ONE launch (csrc/predict.hip) that writes neither a window's
+    [n, ch, cw] tensor nor the plane; `predict.slide_reference` is the specification.  One window that covers the plane and
+    (h, w) == (oh, ow) give seg_predict's outputs bit for bit.  crop, stride: an int or an (h, w) pair each.
+    staging_bytes, label_dtype: as in `seg_predict`."""
+    oh, ow, crop, stride, nw, _, _ = _slide_geometry(oh, ow, crop, stride)
+    B, n = _windows_scores(scores, hpw, wpw, nw)
+    assert h >= 1 and w >= 1 and B * h * w < 2 ** 31, (B, h, w)
+    labels, cf, pr = _predict_outputs(B, n, h, w, scores.device, conf, probs, label_dtype)
+    with _staging(lib().ifseg_seg_predict_windows_staging, staging_bytes):
+        _check(lib().ifseg_seg_predict_windows(_ptr(scores), c_int(B), c_int(hpw), c_int(wpw), c_int(n), c_int(oh), c_int(ow),
+                                               c_int(crop[0]), c_int(crop[1]), c_int(stride[0]), c_int(stride[1]), c_int(h),
+                                               c_int(w), _ptr(labels), c_int(labels.element_size()), _ptr(cf), _ptr(pr),
+                                               _stream()), "seg_predict_windows")
+    return labels, cf, pr
+
+
+def seg_score_windows(scores, hpw, wpw, oh, ow, crop, stride, gt, raw_labels=True, labels=False, conf=False, probs=False,
+                      areas=None, tally=None, staging_bytes=None, label_dtype=None):
+    """`seg_predict_windows` at gt's own [B, h, w] with the scoring in the kernel's epilogue; results as `seg_score`."""
+    oh, ow, crop, stride, nw, _, _ = _slide_geometry(oh, ow, crop, stride)
+    B, n = _windows_scores(scores, hpw, wpw, nw)
+    h, w = _score_gt(gt, B, scores.device)
+    assert B * h * w < 2 ** 31, (B, h, w)
+    areas, tally = _score_counters(n, scores.device, areas, tally)
+    lab, cf, pr = _predict_outputs(B, n, h, w, scores.device, conf, probs, label_dtype, labels)
+    with _staging(lib().ifseg_seg_predict_windows_staging, staging_bytes):
+        _check(lib().ifseg_seg_score_windows(_ptr(scores), c_int(B), c_int(hpw), c_int(wpw), c_int(n), c_int(oh), c_int(ow),
+                                             c_int(crop[0]), c_int(crop[1]), c_int(stride[0]), c_int(stride[1]), c_int(h),
+                                             c_int(w), _ptr(lab), c_int(lab.element_size() if labels else 0), _ptr(cf), _ptr(pr),
+                                             _ptr(gt), c_int(gt.element_size()), c_int(1 if raw_labels else 0), _ptr(areas),
+                                             _ptr(tally), _stream()), "seg_score_windows")
+    return areas, tally, lab, cf, pr
+
+
 _image_luts = {}         # (mean, std, device) -> fp32 [3, 256] on the device; at most 16 entries
 
 
@@ -1218,6 +1280,31 @@ def image_load(images_u8, oh, ow, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), rev
         _check(lib().ifseg_image_load(_ptr(images_u8), c_int(B), c_int(H0), c_int(W0), c_int(oh), c_int(ow), _ptr(lut),
                                       c_int(1 if reverse_channels else 0), _ptr(out), c_int(out.element_size()), _stream()),
                "image_load")
+    return out
+
+
+def image_load_windows(images_u8, oh, ow, crop, stride, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), reverse_channels=False,
+                       dtype=torch.float32, staging_bytes=None):
+    """uint8 [B, H0, W0, 3] -> the window batch [B Nw, 3, ch, cw] in `dtype` of sliding-window inference, written directly
+    (csrc/imgload.hip): element (b Nw + k, c, y, x) is `image_load(..., oh, ow)`'s element (b, c, ys[k] + y, xs[k] + x), bit for
+    bit, for the windows of `imageio.slide_windows(oh, ow, crop, stride)`; no [B, 3, oh, ow] image is written.
+    `imageio.image_load_windows_reference` is the specification.  crop, stride: an int or an (h, w) pair each; the other
+    arguments as in `image_load`."""
+    assert images_u8.dtype == torch.uint8 and images_u8.dim() == 4 and images_u8.shape[-1] == 3 and images_u8.is_contiguous(), \
+        (images_u8.dtype, tuple(images_u8.shape), images_u8.stride())
+    B, H0, W0, _ = images_u8.shape
+    assert B >= 1 and H0 >= 1 and W0 >= 1, tuple(images_u8.shape)
+    oh, ow, crop, stride, nw, ch, cw = _slide_geometry(oh, ow, crop, stride)
+    assert dtype in (torch.float32, torch.bfloat16), dtype
+    assert images_u8.is_cuda, "device tensor required"
+    dev = images_u8.device
+    lut = _image_lut(mean, std, dev)
+    out = torch.empty(B * nw, 3, ch, cw, dtype=dtype, device=dev)
+    with _staging(lib().ifseg_image_load_staging, staging_bytes):
+        _check(lib().ifseg_image_load_windows(_ptr(images_u8), c_int(B), c_int(H0), c_int(W0), c_int(oh), c_int(ow), c_int(crop[0]),
+                                              c_int(crop[1]), c_int(stride[0]), c_int(stride[1]), _ptr(lut),
+                                              c_int(1 if reverse_channels else 0), _ptr(out), c_int(out.element_size()), _stream()),
+               "image_load_windows")
     return out
 
 

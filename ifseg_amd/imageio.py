@@ -8,6 +8,9 @@ values under `imagenet_default_mean_and_std` (:148-156).  The dataset reverses t
 the mmseg transforms, which expect BGR, and :256 (:243 in training) `to RGB` behind them -- so the two cancel: the network
 sees RGB, as PIL delivers it, and `reverse_channels` is off by default (the switch is for a model trained on BGR).  `image_load_reference` is that transform as a specification in plain torch
 indexing; `hip.image_load` (csrc/imgload.hip) is the implementation.
+
+Sliding-window inference (`Segmenter.segment_raw(slide=...)`, mmseg's `test_cfg mode='slide'`): `slide_windows` is the window
+rule, `plan_slide` the grouping of a call, `image_load_windows_reference` the specification of `hip.image_load_windows`.
 """
 import torch
 
@@ -153,3 +156,75 @@ def plan_views(shapes, patch_image_size, scales=(1.0,), flip=False, max_batch=8)
             by_size.setdefault(size, []).append((i, v))
     forwards = [(size, iv[k:k + max_batch]) for size, iv in by_size.items() for k in range(0, len(iv), max_batch)]
     return views, [(hw, size, idx) for (hw, size), idx in loads.items()], forwards
+
+
+# ---- sliding-window inference (mmseg's test_cfg mode='slide'; Segmenter.segment_raw(slide=...)) ----
+MAX_WINDOWS = 64         # == IFSEG_SLIDE_MAX_WINDOWS of include/ifseg_hip.h
+
+
+def _pair(v, what):
+    if isinstance(v, (tuple, list)):
+        if len(v) != 2:
+            raise ValueError("slide_windows: %s must be an int or an (h, w) pair, got %r" % (what, v))
+        return int(v[0]), int(v[1])
+    return int(v), int(v)
+
+
+def slide_windows(oh, ow, crop, stride):
+    """The windows of an [oh, ow] image by mmseg's `slide_inference` rule -> (ys, xs, ch, cw).  `crop` and `stride` are each
+    an int or an (h, w) pair.  Per axis of length o with crop c and stride s there are g = max(o - c + s - 1, 0) // s + 1
+    windows, window i starting at max(min(i s + c, o) - c, 0), every one of extent min(c, o): the last window is pulled back
+    inside the image, and an axis shorter than the crop has one shorter window.  The windows of the image are the cross
+    product of the starts `ys` and `xs`, ys outer (window k = iy len(xs) + ix), each of size (ch, cw).
+    ValueError: a crop or stride < 1, a stride above its crop (gaps), more than MAX_WINDOWS windows."""
+    (c_h, c_w), (s_h, s_w) = _pair(crop, "crop"), _pair(stride, "stride")
+    oh, ow = int(oh), int(ow)
+    if oh < 1 or ow < 1:
+        raise ValueError("slide_windows: the image must be at least 1 x 1, got %d x %d" % (oh, ow))
+    if min(c_h, c_w) < 1 or min(s_h, s_w) < 1:
+        raise ValueError("slide_windows: crop and stride must be >= 1, got crop %r, stride %r" % (crop, stride))
+    if s_h > c_h or s_w > c_w:
+        raise ValueError("slide_windows: a stride above the crop leaves pixels uncovered, got crop %r, stride %r" % (crop, stride))
+
+    def axis(o, c, s):
+        g = max(o - c + s - 1, 0) // s + 1
+        return [max(min(i * s + c, o) - c, 0) for i in range(g)], min(c, o)
+
+    (ys, ch), (xs, cw) = axis(oh, c_h, s_h), axis(ow, c_w, s_w)
+    if len(ys) * len(xs) > MAX_WINDOWS:
+        raise ValueError("slide_windows: %d x %d windows of an image of %d x %d (crop %r, stride %r), at most %d"
+                         % (len(ys), len(xs), oh, ow, crop, stride, MAX_WINDOWS))
+    return ys, xs, ch, cw
+
+
+def plan_slide(shapes, patch_image_size, crop, stride, ratio=1.0, max_batch=8):
+    """`plan_views` for sliding-window inference, as a pure function: -> (per_image, loads, forwards).
+    per_image: [((oh, ow), ys, xs, (ch, cw))], image i at `eval_size(H, W, P, ratio)` and its `slide_windows`; window k of
+    image i is the pair (i, k).
+    loads: [((H, W), (oh, ow), [image indices])], one `image_load_windows` launch per distinct (source shape, (oh, ow)), in
+    order of first appearance.
+    forwards: [((ch, cw), [(i, k)])], one model forward per entry: the windows of one size, of whatever image, in
+    (image, window) order, at most `max_batch` of them; the entries of one size follow each other."""
+    if max_batch < 1:
+        raise ValueError("segment_raw: max_batch must be >= 1, got %r" % (max_batch,))
+    per_image, loads, by_size = [], {}, {}
+    for i, (h, w) in enumerate(shapes):
+        h, w = int(h), int(w)
+        size = eval_size(h, w, patch_image_size, ratio)
+        ys, xs, ch, cw = slide_windows(size[0], size[1], crop, stride)
+        per_image.append((size, ys, xs, (ch, cw)))
+        loads.setdefault(((h, w), size), []).append(i)
+        by_size.setdefault((ch, cw), []).extend((i, k) for k in range(len(ys) * len(xs)))
+    forwards = [(size, ik[k:k + max_batch]) for size, ik in by_size.items() for k in range(0, len(ik), max_batch)]
+    return per_image, [(hw, size, idx) for (hw, size), idx in loads.items()], forwards
+
+
+def image_load_windows_reference(images_u8, oh, ow, crop, stride, mean=HALF, std=HALF, reverse_channels=False,
+                                 dtype=torch.float64, out_dtype=torch.float32):
+    """CPU specification of hip.image_load_windows: uint8 [B, H0, W0, 3] -> normalised `out_dtype` [B Nw, 3, ch, cw]: element
+    (b Nw + k, c, y, x) is `image_load_reference`'s element (b, c, ys[k] + y, xs[k] + x) at (oh, ow), the windows being
+    `slide_windows(oh, ow, crop, stride)`.  A window is a slice of the loaded image, never a resize of its own."""
+    ys, xs, ch, cw = slide_windows(oh, ow, crop, stride)
+    full = image_load_reference(images_u8, oh, ow, mean, std, reverse_channels, dtype, out_dtype)[0]
+    wins = torch.stack([full[:, :, y:y + ch, x:x + cw] for y in ys for x in xs], 1)
+    return wins.reshape(full.shape[0] * len(ys) * len(xs), 3, ch, cw)

@@ -20,8 +20,10 @@ kernels, with key counts and attention dropout) and `seg_loss` (csrc/loss.hip), 
 `ifseg_amd.modules.MultiheadAttention` composes `linear` and `attention_bias` under the reference module's parameter names.
 `seg_predict` (csrc/predict.hip: label maps at image resolution), `seg_predict_views` (the same from the mean of K views of
 differing grids, mirrored ones included: multi-scale + flip inference), `seg_areas` / `seg_score_views` (label maps counted
-against ground truth, stand-alone and in the predict kernel's epilogue: mIoU on the device) and `image_load` (csrc/imgload.hip: raw uint8 images to
-normalised patch_images, the reference's evaluation transform) are inference only and have no backward; `train_load`
+against ground truth, stand-alone and in the predict kernel's epilogue: mIoU on the device), `image_load` (csrc/imgload.hip: raw uint8 images to
+normalised patch_images, the reference's evaluation transform) and the three ops of sliding-window inference (`image_load_windows`,
+`seg_predict_windows`, `seg_score_windows`: the window batch written directly, and the windows' scores merged into one label
+map in one launch) are inference only and have no backward; `train_load`
 (csrc/trainload.hip: raw images and label maps of any sizes to a training batch under given records, the reference's training
 transform) has integer inputs and no backward either.
 """
@@ -843,8 +845,7 @@ def _(scores, hps, wps, flips, gt, raw_labels, want_labels, want_conf, want_prob
 
 
 # ----------------------------------------------------------------------------------------------- image_load
-def _image_load_check(images, oh, ow, mean, std, dtype):
-    op = "ifseg::image_load"
+def _image_load_check(images, oh, ow, mean, std, dtype, op="ifseg::image_load"):
     if images.dtype != torch.uint8:
         raise ValueError("%s: images must be uint8 (raw grey levels; normalised floats go to the model as they are), got dtype %s"
                          % (op, images.dtype))
@@ -883,6 +884,134 @@ def image_load(images: torch.Tensor, oh: int, ow: int, mean: Sequence[float], st
 def _(images, oh, ow, mean, std, reverse_channels, dtype):
     B = _image_load_check(images, oh, ow, mean, std, dtype)
     return images.new_empty((B, 3, oh, ow), dtype=dtype)
+
+
+# ----------------------------------------------------------------------------------------------- sliding windows
+def _slide_check(op, oh, ow, crop, stride):
+    """-> (Nw, ch, cw) of `imageio.slide_windows`; crop and stride are (h, w) pairs here (the schema has no int-or-pair)"""
+    from .imageio import slide_windows
+    if len(crop) != 2 or len(stride) != 2:
+        raise ValueError("%s: crop and stride must be (h, w) pairs, got %r and %r" % (op, list(crop), list(stride)))
+    try:
+        ys, xs, ch, cw = slide_windows(oh, ow, tuple(crop), tuple(stride))
+    except ValueError as e:
+        raise ValueError("%s: %s" % (op, e))
+    return len(ys) * len(xs), ch, cw
+
+
+def _seg_predict_windows_check(scores, hpw, wpw, oh, ow, crop, stride, h, w, op="ifseg::seg_predict_windows"):
+    if scores.dtype != torch.float32:
+        raise ValueError("%s: scores must be fp32 (hip.rows_to_f32 / hip.neighbour_smoothing give it), got dtype %s" % (op, scores.dtype))
+    if scores.dim() != 4:
+        raise ValueError("%s: scores must be [B, Nw, hpw*wpw, n], got %s" % (op, tuple(scores.shape)))
+    B, Nw, P, n = scores.shape
+    if B == 0:
+        raise ValueError("%s: empty batch" % op)
+    nw, _, _ = _slide_check(op, oh, ow, crop, stride)
+    if Nw != nw:
+        raise ValueError("%s: scores.shape[1] = %d, the window rule gives %d windows" % (op, Nw, nw))
+    if hpw <= 0 or wpw <= 0 or P != hpw * wpw:
+        raise ValueError("%s: scores.shape[2] = %d, expected hpw * wpw = %d" % (op, P, hpw * wpw))
+    if Nw * P >= 2 ** 22:
+        raise ValueError("%s: Nw * hpw * wpw = %d must stay below 2**22" % (op, Nw * P))
+    if n < 1 or n > SEG_LOSS_MAX_CLASSES:
+        raise ValueError("%s: n = %d classes, the kernel takes 1 .. FUSED_MAX_CLASSES = %d" % (op, n, SEG_LOSS_MAX_CLASSES))
+    if h < 1 or w < 1 or B * h * w >= 2 ** 31:
+        raise ValueError("%s: the label map [%d, %d, %d] must have 1 <= h, w and B * h * w < 2**31" % (op, B, h, w))
+    return B, n, (torch.uint8 if n <= 256 else torch.int16)
+
+
+@custom_op("ifseg::seg_predict_windows", mutates_args=(), device_types="cuda")
+def seg_predict_windows(scores: torch.Tensor, hpw: int, wpw: int, oh: int, ow: int, crop: Sequence[int], stride: Sequence[int],
+                        h: int, w: int, want_conf: bool, want_probs: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """label map at h x w from the windows of sliding-window inference (csrc/predict.hip): scores fp32 [B, Nw, hpw*wpw, n],
+    window k of `imageio.slide_windows(oh, ow, crop, stride)`; the windows are resized, averaged where they overlap and the
+    result resized to h x w in one launch.  Outputs and conventions as `seg_predict`.  Not differentiable."""
+    _seg_predict_windows_check(scores, hpw, wpw, oh, ow, crop, stride, h, w)
+    prev = _stream_scope(scores)
+    try:
+        labels, conf, probs = hip.seg_predict_windows(scores.contiguous(), hpw, wpw, oh, ow, tuple(crop), tuple(stride), h, w,
+                                                      conf=want_conf, probs=want_probs)
+        e = lambda t: torch.empty(0, dtype=torch.float32, device=scores.device) if t is None else t
+        return labels, e(conf), e(probs)
+    finally:
+        hip.set_stream(prev)
+
+
+@seg_predict_windows.register_fake
+def _(scores, hpw, wpw, oh, ow, crop, stride, h, w, want_conf, want_probs):
+    B, n, ldt = _seg_predict_windows_check(scores, hpw, wpw, oh, ow, crop, stride, h, w)
+    f32 = torch.float32
+    return (scores.new_empty(B, h, w, dtype=ldt), scores.new_empty((B, h, w) if want_conf else (0,), dtype=f32),
+            scores.new_empty((B, n, h, w) if want_probs else (0,), dtype=f32))
+
+
+def _seg_score_windows_check(scores, hpw, wpw, oh, ow, crop, stride, gt):
+    op = "ifseg::seg_score_windows"
+    _gt_check(op, gt)
+    if gt.dim() != 3:
+        raise ValueError("%s: ground truth must be [B, h, w], got %s" % (op, tuple(gt.shape)))
+    B, n, ldt = _seg_predict_windows_check(scores, hpw, wpw, oh, ow, crop, stride, gt.shape[1], gt.shape[2], op)
+    if gt.shape[0] != B:
+        raise ValueError("%s: ground truth %s for a batch of %d" % (op, tuple(gt.shape), B))
+    return B, n, ldt
+
+
+@custom_op("ifseg::seg_score_windows", mutates_args=(), device_types="cuda")
+def seg_score_windows(scores: torch.Tensor, hpw: int, wpw: int, oh: int, ow: int, crop: Sequence[int], stride: Sequence[int],
+                      gt: torch.Tensor, raw_labels: bool, want_labels: bool, want_conf: bool, want_probs: bool
+                      ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """`seg_predict_windows` at the shape of the ground truth gt (uint8 / int16 [B, h, w]) with the label map counted against
+    it in the kernel's epilogue -> (areas, tally, labels, conf, probs) as `seg_score_views`.  Not differentiable."""
+    _seg_score_windows_check(scores, hpw, wpw, oh, ow, crop, stride, gt)
+    prev = _stream_scope(scores)
+    try:
+        areas, tally, labels, conf, probs = hip.seg_score_windows(scores.contiguous(), hpw, wpw, oh, ow, tuple(crop), tuple(stride),
+                                                                  gt.contiguous(), raw_labels, labels=want_labels, conf=want_conf,
+                                                                  probs=want_probs)
+        e = lambda t, dt: torch.empty(0, dtype=dt, device=gt.device) if t is None else t
+        ldt = torch.uint8 if scores.shape[3] <= 256 else torch.int16
+        return areas, tally, e(labels, ldt), e(conf, torch.float32), e(probs, torch.float32)
+    finally:
+        hip.set_stream(prev)
+
+
+@seg_score_windows.register_fake
+def _(scores, hpw, wpw, oh, ow, crop, stride, gt, raw_labels, want_labels, want_conf, want_probs):
+    B, n, ldt = _seg_score_windows_check(scores, hpw, wpw, oh, ow, crop, stride, gt)
+    f32, s, (h, w) = torch.float32, scores, gt.shape[1:]
+    return (s.new_empty((3, n), dtype=torch.int64), s.new_empty((2,), dtype=torch.int64),
+            s.new_empty((B, h, w) if want_labels else (0,), dtype=ldt), s.new_empty((B, h, w) if want_conf else (0,), dtype=f32),
+            s.new_empty((B, n, h, w) if want_probs else (0,), dtype=f32))
+
+
+def _image_load_windows_check(images, oh, ow, crop, stride, mean, std, dtype):
+    op = "ifseg::image_load_windows"
+    B = _image_load_check(images, oh, ow, mean, std, dtype, op)
+    nw, ch, cw = _slide_check(op, oh, ow, crop, stride)
+    if B * nw * 3 * ch * cw >= 2 ** 31:
+        raise ValueError("%s: the window batch [%d, 3, %d, %d] must stay below 2**31 elements" % (op, B * nw, ch, cw))
+    return B * nw, ch, cw
+
+
+@custom_op("ifseg::image_load_windows", mutates_args=(), device_types="cuda")
+def image_load_windows(images: torch.Tensor, oh: int, ow: int, crop: Sequence[int], stride: Sequence[int], mean: Sequence[float],
+                       std: Sequence[float], reverse_channels: bool, dtype: torch.dtype) -> torch.Tensor:
+    """the windows of sliding-window inference, written directly (csrc/imgload.hip): uint8 [B, H0, W0, 3] -> [B Nw, 3, ch, cw] in
+    `dtype`, the slices of `image_load`'s [B, 3, oh, ow] at the windows of `imageio.slide_windows(oh, ow, crop, stride)`, bit
+    for bit.  The input is integer: not differentiable."""
+    _image_load_windows_check(images, oh, ow, crop, stride, mean, std, dtype)
+    prev = _stream_scope(images)
+    try:
+        return hip.image_load_windows(images.contiguous(), oh, ow, tuple(crop), tuple(stride), mean, std, reverse_channels, dtype)
+    finally:
+        hip.set_stream(prev)
+
+
+@image_load_windows.register_fake
+def _(images, oh, ow, crop, stride, mean, std, reverse_channels, dtype):
+    nb, ch, cw = _image_load_windows_check(images, oh, ow, crop, stride, mean, std, dtype)
+    return images.new_empty((nb, 3, ch, cw), dtype=dtype)
 
 
 # ----------------------------------------------------------------------------------------------- train_load

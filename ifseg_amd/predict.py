@@ -21,6 +21,18 @@ never turns this on, so there is no golden for it: parity is to the specificatio
 distinct view size is one more entry of the engine's resized-bias cache (`engine.py:_resized_biases`), whose entries grow
 with the square of the grid; the views are therefore run size by size (`imageio.plan_views`).
 
+Sliding-window inference (mmseg's `test_cfg=dict(mode='slide', crop_size=(P, P), stride=(s, s))`, how fixed-grid transformer
+segmenters are scored): `seg.segment_raw(photos, slide=True)` cuts the resized image into overlapping P x P windows
+(`imageio.slide_windows`, written directly by `hip.image_load_windows`), runs every window at the trained grid -- one network
+size for a whole data set, no resized-bias entry, the windows of all images in the same batches (`imageio.plan_slide`) -- and
+ONE launch of `hip.seg_predict_windows` per image resizes the windows' scores, averages them where windows overlap and
+resizes the result to the image's shape: no per-window [n, P, P] tensor, sum or count plane is written.  Limits: the
+reference never slides, so there is no golden and parity is to the specification `slide_reference`; a single view only
+(`slide` with several scales or `flip` is a ValueError).
+
+    out = seg.segment_raw(photos, slide=True)                                                # crop P, stride 2 P // 3
+    score = seg.evaluate_raw(photos, label_pngs, slide=(512, 341))                           # (crop, stride), ints or (h, w)
+
 Scoring against ground truth: `seg.evaluate_raw(photos, label_maps, ...)` is `segment_raw` with the same arguments whose last
 launch per image also counts the label map against the image's ground truth (`hip.seg_score` / `hip.seg_score_views`: the
 predict kernels with the counting in their epilogue; `hip.seg_areas` behind the CRF), into one `SegmentationScore` on the
@@ -41,7 +53,7 @@ import torch
 import torch.nn.functional as F
 
 from . import hip
-from .imageio import HALF, eval_size, plan_views, view_list
+from .imageio import HALF, eval_size, plan_slide, plan_views, slide_windows, view_list
 from .tasks.mm_tasks.segmentation import BOS, EOS, PROMPT_IDS
 
 MAX_CLASSES = hip.SEG_PREDICT_MAX_CLASSES
@@ -81,6 +93,30 @@ def upsample_views_reference(views, h, w, dtype=torch.float64):
         up = F.interpolate(grid, size=(h, w), mode="bilinear", align_corners=False)
         total = up if total is None else total + up
     probs = total * torch.tensor(1.0 / len(views), dtype=dtype, device=total.device)
+    labels = probs.argmax(dim=1)
+    return labels, probs.gather(1, labels[:, None]).squeeze(1), probs
+
+
+def slide_reference(scores, hpw, wpw, oh, ow, crop, stride, h, w, dtype=torch.float64):
+    """CPU specification of hip.seg_predict_windows: scores [B, Nw, hpw*wpw, n], window k of `slide_windows(oh, ow, crop,
+    stride)` having run the network on its own hpw x wpw grid.  Each window is reshaped to [B, n, hpw, wpw] and resized with
+    F.interpolate(bilinear, align_corners=False) to the window's (ch, cw) in `dtype`; the results are added into a zero
+    [B, n, oh, ow] plane at the windows' places, in window order, a count plane takes 1 per window, and the sum is divided by
+    the count (mmseg's `slide_inference`); where (h, w) != (oh, ow) the quotient is resized to (h, w) the same way.  Labels are
+    the first maximum.  -> (labels int64 [B, h, w], conf [B, h, w], probs [B, n, h, w]) as `upsample_argmax_reference`.
+    Runs on any device."""
+    ys, xs, ch, cw = slide_windows(oh, ow, crop, stride)
+    B, Nw, P, n = scores.shape
+    assert Nw == len(ys) * len(xs) and P == hpw * wpw, (tuple(scores.shape), len(ys), len(xs), hpw, wpw)
+    total = torch.zeros(B, n, oh, ow, dtype=dtype, device=scores.device)
+    count = torch.zeros(1, 1, oh, ow, dtype=dtype, device=scores.device)
+    for k, (y, x) in enumerate((y, x) for y in ys for x in xs):
+        grid = scores[:, k].to(dtype).transpose(1, 2).reshape(B, n, hpw, wpw)
+        total[:, :, y:y + ch, x:x + cw] += F.interpolate(grid, size=(ch, cw), mode="bilinear", align_corners=False)
+        count[:, :, y:y + ch, x:x + cw] += 1
+    probs = total / count
+    if (h, w) != (oh, ow):
+        probs = F.interpolate(probs, size=(h, w), mode="bilinear", align_corners=False)
     labels = probs.argmax(dim=1)
     return labels, probs.gather(1, labels[:, None]).squeeze(1), probs
 
@@ -318,7 +354,7 @@ class Segmenter:
 
     # -- raw images of any size ----------------------------------------------------------
     def segment_raw(self, images, max_batch=8, mean=None, std=None, reverse_channels=False, return_conf=False,
-                    return_probs=False, scales=(1.0,), flip=False):
+                    return_probs=False, scales=(1.0,), flip=False, slide=None):
         """Raw images in, as they come off disk: one uint8 RGB [H, W, 3] tensor or a list of them, of differing shapes, on the
         host or the device -> a list of SegmentationResult in input order, image i with labels [H_i, W_i] (conf [H_i, W_i],
         probs [n, H_i, W_i]) on the device.
@@ -343,12 +379,37 @@ class Segmenter:
         (`imageio.plan_views`), and `hip.seg_predict_views` turns the views of an image into one label map at [H_i, W_i]: the
         mean of the resized, un-mirrored scores, which is also what the CRF takes.  At most 16 views; more than one view
         needs upsample="probs" (averaging raw logits is not mmseg's rule).  The default is the single view above: the same
-        launches as without these arguments, `hip.seg_predict` at the end."""
+        launches as without these arguments, `hip.seg_predict` at the end.
+
+        slide: sliding-window inference, mmseg's `test_cfg=dict(mode='slide', crop_size, stride)`.  None: off, the launches
+        above.  True: crop = P and stride = 2 P // 3 (341 at 512, 426 at 640, the usual configs); (crop, stride), each an int
+        or an (h, w) pair: as given.  The image is resized to `eval_size(H, W, P, scales[0])` and cut into overlapping windows
+        (`imageio.slide_windows`), written directly by `hip.image_load_windows`; every window runs the forward above (and
+        the smoothing, per window) at the window's size -- with crop = P the trained grid, so no resized-bias entry is
+        built and the windows of all images fill the same batches (`imageio.plan_slide`) -- and ONE launch of
+        `hip.seg_predict_windows` per image resizes the windows' scores, averages them where windows overlap and resizes
+        the result to [H_i, W_i]: no per-window [n, crop, crop] tensor, sum or count plane is written.  `slide_reference` is
+        the specification; the reference never slides, so there is no golden for it.  Both `upsample` modes are allowed:
+        "logits" is mmseg's single-scale order (the logits are merged, and the argmax is unchanged by the softmax mmseg
+        applies afterwards), "probs" the demo's order (the per-patch softmax is merged).  A single view only: `slide` with
+        several scales or `flip` is a ValueError, because mmseg applies the softmax between the window merge and the view
+        average, which a kernel that is linear in the scores cannot express."""
+        sl = self._check_slide("segment_raw", slide, scales, flip)
         checked = self._check_raw("segment_raw", images, scales, flip)
+        plan = self._plan_slide(checked, sl, max_batch)
         if checked is None:
             return []
-        imgs, shapes, per_image = self._raw_views(*checked, max_batch, mean, std, reverse_channels)
         crf, out = self.crf_iters > 0, []
+        if sl is not None:
+            imgs, shapes, per_image = self._raw_windows(checked[1], sl, plan, mean, std, reverse_channels)
+            with torch.no_grad():
+                for i, (scores, hpw, wpw, (oh, ow)) in enumerate(per_image):
+                    r = hip.seg_predict_windows(scores, hpw, wpw, oh, ow, sl[0], sl[1], *shapes[i], conf=return_conf and not crf,
+                                                probs=return_probs or crf, label_dtype=self.label_dtype)
+                    r = self._crf(r, imgs[i][None].float() if crf else None, return_conf, return_probs)
+                    out.append(SegmentationResult(*(None if t is None else t[0] for t in r)))
+            return out
+        imgs, shapes, per_image = self._raw_views(*checked, max_batch, mean, std, reverse_channels)
         with torch.no_grad():
             for i, vs in enumerate(per_image):
                 (H, W), rgb = shapes[i], imgs[i][None].float() if crf else None
@@ -374,6 +435,52 @@ class Segmenter:
                 raise ValueError("Segmenter.%s: every image must be a uint8 RGB [H, W, 3] tensor, got %s"
                                  % (what, (im.dtype, tuple(im.shape)) if torch.is_tensor(im) else type(im),))
         return views, imgs, scales, flip
+
+    def _check_slide(self, what, slide, scales, flip):
+        """the `slide` argument of `segment_raw` / `evaluate_raw`, checked on the host -> None (off) or (crop, stride)"""
+        if slide is None or slide is False:
+            return None
+        if len(view_list(scales, flip)) > 1:
+            raise ValueError("Segmenter.%s: slide takes a single view, got scales=%r, flip=%r (mmseg applies the softmax between "
+                             "the window merge and the view average)" % (what, tuple(scales), flip))
+        P = int(self.model.cfg.patch_image_size)
+        if slide is True:
+            return P, 2 * P // 3
+        if not isinstance(slide, (tuple, list)) or len(slide) != 2:
+            raise ValueError("Segmenter.%s: slide must be None, True or (crop, stride), got %r" % (what, slide))
+        crop, stride = slide
+        slide_windows(1, 1, crop, stride)                     # crop and stride against the rule, on an image of one window
+        return crop, stride
+
+    def _plan_slide(self, checked, sl, max_batch):
+        """the windows and launches of a `slide` call, on the host (more than 64 windows of an image is a ValueError here) ->
+        (the images' (H, W), `imageio.plan_slide`'s result), or None without `slide` or images"""
+        if sl is None or checked is None:
+            return None
+        shapes = [(int(im.shape[0]), int(im.shape[1])) for im in checked[1]]
+        return shapes, plan_slide(shapes, self.model.cfg.patch_image_size, sl[0], sl[1], float(checked[2][0]), max_batch)
+
+    def _raw_windows(self, imgs, sl, plan, mean, std, reverse_channels):
+        """the front of `segment_raw` and `evaluate_raw` with `slide`: every image's windows loaded in one launch per source
+        shape, one forward per window size and `max_batch` windows (`plan`: what `_plan_slide` gave) -> (the images on the
+        device, their (H, W), per image
+        (scores [1, Nw, hpw*wpw, n], hpw, wpw, (oh, ow)))"""
+        mean, std = HALF if mean is None else mean, HALF if std is None else std
+        dev = next(self.model.parameters()).device
+        shapes, (per_image, loads, forwards) = plan
+        imgs = [im.to(dev, non_blocking=True) for im in imgs]
+        x, got, grid = {}, [[None] * (len(ys) * len(xs)) for _, ys, xs, _ in per_image], {}
+        with torch.no_grad():
+            for _, size, idx in loads:
+                t = hip.image_load_windows(torch.stack([imgs[i] for i in idx]), size[0], size[1], sl[0], sl[1], mean, std,
+                                           reverse_channels)
+                for k, wins in enumerate(t.chunk(len(idx))):
+                    x[idx[k]] = wins
+            for size, ik in forwards:
+                scores, hp, wp = self.patch_scores(torch.stack([x[i][k] for i, k in ik]))
+                for j, (i, k) in enumerate(ik):
+                    got[i][k], grid[i] = scores[j], (hp, wp)
+        return imgs, shapes, [(torch.stack(got[i])[None], *grid[i], per_image[i][0]) for i in range(len(imgs))]
 
     def _raw_views(self, views, imgs, scales, flip, max_batch, mean, std, reverse_channels):
         """the front of `segment_raw` and `evaluate_raw`: every image loaded once per ratio, one forward per network size ->
@@ -417,7 +524,7 @@ class Segmenter:
         return hip.seg_score_views(vs, gt, labels=return_labels, label_dtype=self.label_dtype, **kw)[2]
 
     def evaluate_raw(self, images, label_maps, raw_labels=True, scales=(1.0,), flip=False, max_batch=8, mean=None, std=None,
-                     reverse_channels=False, into=None, return_labels=False):
+                     reverse_channels=False, into=None, return_labels=False, slide=None):
         """`segment_raw` scored against ground truth on the device -> a `SegmentationScore` (or (score, [labels [H_i, W_i], ...])
         with `return_labels`, the labels being `segment_raw`'s).
 
@@ -428,8 +535,11 @@ class Segmenter:
         label_maps: one uint8 / int16 [H, W] tensor or a list, on the host or the device, entry i of image i's shape.
         raw_labels=True: the label PNGs' values, 0 and 255 ignored and x -> class x - 1 (`areas_reference` states the rule);
         False: class ids, n and 255 ignored.  into: a score to accumulate into (a whole validation set needs no host round
-        trip; `summary()` is the only one).  A mismatch of count, shape or dtype is a ValueError before anything is launched."""
+        trip; `summary()` is the only one).  A mismatch of count, shape or dtype is a ValueError before anything is launched.
+        slide: as in `segment_raw`; the last launch per image is then `hip.seg_score_windows`."""
+        sl = self._check_slide("evaluate_raw", slide, scales, flip)
         checked = self._check_raw("evaluate_raw", images, scales, flip)
+        plan = self._plan_slide(checked, sl, max_batch)
         gts = [label_maps] if torch.is_tensor(label_maps) else list(label_maps)
         imgs = [] if checked is None else checked[1]
         if len(gts) != len(imgs):
@@ -443,8 +553,23 @@ class Segmenter:
         if checked is None:
             return (score, []) if return_labels else score
         gts = [g.to(dev, non_blocking=True).contiguous() for g in gts]
-        imgs, shapes, per_image = self._raw_views(*checked, max_batch, mean, std, reverse_channels)
         crf, out = self.crf_iters > 0, []
+        if sl is not None:
+            imgs, shapes, per_image = self._raw_windows(checked[1], sl, plan, mean, std, reverse_channels)
+            kw = dict(raw_labels=raw_labels, areas=score.areas, tally=score.tally)
+            with torch.no_grad():
+                for i, (scores, hpw, wpw, (oh, ow)) in enumerate(per_image):
+                    if crf:                                   # the label map comes from the CRF, not from the predict kernel
+                        r = hip.seg_predict_windows(scores, hpw, wpw, oh, ow, sl[0], sl[1], *shapes[i], probs=True,
+                                                    label_dtype=self.label_dtype)
+                        labels = self._crf(r, imgs[i][None].float(), False, False).labels
+                        hip.seg_areas(labels.contiguous(), gts[i][None], self.n, **kw)
+                    else:
+                        labels = hip.seg_score_windows(scores, hpw, wpw, oh, ow, sl[0], sl[1], gts[i][None], labels=return_labels,
+                                                       label_dtype=self.label_dtype, **kw)[2]
+                    out.append(labels[0] if return_labels else None)
+            return (score, out) if return_labels else score
+        imgs, shapes, per_image = self._raw_views(*checked, max_batch, mean, std, reverse_channels)
         with torch.no_grad():
             for i, vs in enumerate(per_image):
                 labels = self._score(score, vs, gts[i][None], raw_labels, imgs[i][None].float() if crf else None, return_labels)

@@ -202,14 +202,14 @@ class SegmentationTask(TaskBase):
         from ...predict import Segmenter
         return Segmenter(model, task=self, **kw)
 
-    def evaluate_raw(self, model, images, label_maps, **kw):
+    def evaluate_raw(self, model, images, label_maps, slide=None, **kw):
         """raw uint8 images and their label maps -> a `SegmentationScore` (aAcc / mIoU / mAcc through `.summary()`), counted on
         the device: `build_segmenter(model, ...).evaluate_raw(images, label_maps, ...)`.  Keywords of the Segmenter's constructor
-        go to it, the others to `Segmenter.evaluate_raw`."""
+        go to it, the others to `Segmenter.evaluate_raw`; `slide` (None, True or (crop, stride)) is its sliding-window switch."""
         ctor = ("category_token_ids", "prompt_ids", "upsample", "smooth_iters", "smooth_topk", "temperature", "crf_iters",
                 "full_context_alignment", "label_dtype")
         seg = self.build_segmenter(model, **{k: kw.pop(k) for k in ctor if k in kw})
-        return seg.evaluate_raw(images, label_maps, **kw)
+        return seg.evaluate_raw(images, label_maps, slide=slide, **kw)
 
     def inference_step(self, generator, models, sample, prefix_tokens=None, constraints=None):
         """fairseq_task.py `inference_step` -> [B, max_len] seg-class indices of the best beam (segmentation.py:266-268)"""

@@ -638,6 +638,43 @@ int ifseg_image_load(const void* images, int B, int H0, int W0, int oh, int ow, 
                      void* out, int out_bytes, void* stream);
 int ifseg_image_load_staging(int max_bytes);
 
+/* ---- sliding-window inference (Segmenter.segment_raw(slide=...): mmseg's test_cfg mode='slide') ----
+ * The window rule, per axis of o samples with crop c and stride s (1 <= s <= c): g = max(o - c + s - 1, 0) / s + 1 windows of
+ * e = min(c, o) samples, window i starting at max(min(i s + c, o) - c, 0) -- the last window is pulled back inside, an axis
+ * shorter than the crop has one shorter window.  The windows of an [oh, ow] plane are the cross product, rows outer:
+ * window k = iy gx + ix, Nw = gy gx <= IFSEG_SLIDE_MAX_WINDOWS, all of extent (ch, cw) = (e_y, e_x).  Every entry point below
+ * derives the windows from (oh, ow, crop_h, crop_w, stride_h, stride_w); a crop or stride < 1, a stride above its crop, oh or
+ * ow < 1 and Nw above the limit are IFSEG_ERR_BAD_SHAPE. */
+#define IFSEG_SLIDE_MAX_WINDOWS 64
+/* ifseg_image_load_windows writes the window batch [B Nw, 3, ch, cw] of ifseg_image_load's [B, 3, oh, ow] directly: element
+ * (b Nw + k, c, y, x) is ifseg_image_load's element (b, c, ys[k] + y, xs[k] + x), bit for bit (a window is a slice of the
+ * loaded image, never a resize of its own), and no [B, 3, oh, ow] image is written.  Arguments, alignment, reads around
+ * `images`, refusals and staging (ifseg_image_load_staging) as ifseg_image_load; B*Nw*3*ch*cw < 2^31. */
+int ifseg_image_load_windows(const void* images, int B, int H0, int W0, int oh, int ow, int crop_h, int crop_w, int stride_h,
+                             int stride_w, const float* lut, int reverse_channels, void* out, int out_bytes, void* stream);
+/* ifseg_seg_predict_windows merges the per-window class scores [B, Nw, hpw*wpw, n] (fp32, class fastest; window k of image b
+ * ran the network on its own hpw x wpw grid) into one label map [B, h, w], in one launch:
+ *   u_k  = window k's grid resized to (ch, cw) by ifseg_seg_predict's rule (coordinates and the flat four-weight value)
+ *   m    = (sum of u_k over the windows that cover a pixel of the [oh, ow] plane, in window order) / their number
+ *   v    = m resized to (h, w) by the same coordinate rule, sum of weight * m over the taps of NON-ZERO weight
+ * labels / conf / probs of v as ifseg_seg_predict writes them (first maximum; conf and probs may be NULL).  Neither the u_k nor
+ * m is written.  With one window that covers the plane and (h, w) == (oh, ow) the outputs are ifseg_seg_predict's bit for
+ * bit.  ifseg_seg_score_windows is the same launch with ifseg_seg_score's counting in its epilogue (labels optional).
+ * Refusals: those of ifseg_seg_predict for scores, n, labels, label_bytes, conf, probs, B, h, w; the window rule's;
+ * hpw, wpw < 1 or Nw*hpw*wpw >= 2^22: IFSEG_ERR_BAD_SHAPE; and ifseg_seg_score's for gt, gt_bytes, areas, tally.  Nothing is
+ * launched on a refusal.
+ * A workgroup owns 16 x 64 pixels and walks the classes in chunks of 16; per chunk it stages the patches of every window
+ * under the tile in LDS, or, where they do not fit the staging buffer, reads global memory (same values).
+ * ifseg_seg_predict_windows_staging sets the size of that buffer like ifseg_seg_predict_staging, for these two only. */
+int ifseg_seg_predict_windows(const float* scores, int B, int hpw, int wpw, int n, int oh, int ow, int crop_h, int crop_w,
+                              int stride_h, int stride_w, int h, int w, void* labels, int label_bytes, float* conf, float* probs,
+                              void* stream);
+int ifseg_seg_score_windows(const float* scores, int B, int hpw, int wpw, int n, int oh, int ow, int crop_h, int crop_w,
+                            int stride_h, int stride_w, int h, int w, void* labels, int label_bytes, float* conf, float* probs,
+                            const void* gt, int gt_bytes, int raw_labels, unsigned long long* areas, unsigned long long* tally,
+                            void* stream);
+int ifseg_seg_predict_windows_staging(int max_bytes);
+
 /* ---- raw images and raw label maps in, a training batch out (ifseg_amd/augment.py is the specification, bit for bit; the
  * reference's training transform, segmentation_dataset.py:157-163, 239-251: Resize(ratio_range), RandomCrop(cat_max_ratio 0.75),
  * RandomFlip, PhotoMetricDistortion, Normalize) ----
