@@ -31,8 +31,9 @@ using namespace tile;
 
 int g_stage_limit = U8_STAGE_LIMIT;
 
-// one tile of a [dh, dw] destination plane whose first element is out[ebase]: cy / cx map its rows / columns to the source
-template <typename T, typename Coord>
+// one tile of a [dh, dw] destination plane whose first element is out[ebase]: cy / cx map its rows / columns to the source.
+// MIRROR: cx runs DOWN the source columns, so the tile's last column bounds its footprint from below
+template <typename T, bool MIRROR = false, typename Coord>
 __device__ __forceinline__ void load_tile(const unsigned char* sb, int W0, const Coord& cy, const Coord& cx, const Tile& t, int dh,
                                           int dw, long long ebase, const float* __restrict__ lut_g, int rev, T* __restrict__ out,
                                           int stage_bytes) {
@@ -41,7 +42,8 @@ __device__ __forceinline__ void load_tile(const unsigned char* sb, int W0, const
   const auto [b, X0, Y0, xend, yend, lane, wave] = t;
 
   for (int i = threadIdx.x; i < 768; i += 256) lut[i] = lut_g[i];
-  const U8Source s = u8_stage(sb, W0, cy, Y0, yend - 1, cx, X0, xend - 1, smem + U8_LUT_BYTES, stage_bytes);
+  const U8Source s = u8_stage(sb, W0, cy, Y0, yend - 1, cx, MIRROR ? xend - 1 : X0, MIRROR ? X0 : xend - 1,
+                              smem + U8_LUT_BYTES, stage_bytes);
   __syncthreads();
 
   // phase 1
@@ -81,16 +83,28 @@ struct WinCoord {
   int off;
   __device__ __forceinline__ void operator()(int d, int* i0, int* i1, float* l) const { c(d + off, i0, i1, l); }
 };
+// the windows of the MIRRORED plane: column d of a window at offset off is column ow - 1 - off - d of the plane (dir = -1);
+// the rows are WinCoord's (dir = 1): one type for both axes, as u8_stage takes them
+struct MirrorCoord {
+  IntCoord c;
+  int off, dir;
+  __device__ __forceinline__ void operator()(int d, int* i0, int* i1, float* l) const { c(off + dir * d, i0, i1, l); }
+};
 
-template <typename T>
+template <typename T, bool MIRROR>
 __global__ __launch_bounds__(256) void image_load_windows_kernel(const unsigned char* __restrict__ src, int H0, int W0, SlideAxis ay,
                                                                  SlideAxis ax, int tiles_x, int tiles_y,
                                                                  const float* __restrict__ lut_g, int rev, T* __restrict__ out,
                                                                  int stage_bytes) {
   const Tile t = tile_decode(tiles_x, tiles_y, ay.e, ax.e);       // t.b: the window's index in the batch, b Nw + iy gx + ix
   const int nw = ay.g * ax.g, b = t.b / nw, k = t.b - b * nw, iy = k / ax.g, ix = k - iy * ax.g;
-  load_tile(src + (long long)b * H0 * W0 * 3, W0, WinCoord{{H0, ay.o}, ay.start(iy)}, WinCoord{{W0, ax.o}, ax.start(ix)}, t, ay.e,
-            ax.e, (long long)t.b * 3 * ay.e * ax.e, lut_g, rev, out, stage_bytes);
+  if constexpr (MIRROR)
+    load_tile<T, true>(src + (long long)b * H0 * W0 * 3, W0, MirrorCoord{{H0, ay.o}, ay.start(iy), 1},
+                       MirrorCoord{{W0, ax.o}, ax.o - 1 - ax.start(ix), -1}, t, ay.e, ax.e, (long long)t.b * 3 * ay.e * ax.e, lut_g, rev,
+                       out, stage_bytes);
+  else
+    load_tile(src + (long long)b * H0 * W0 * 3, W0, WinCoord{{H0, ay.o}, ay.start(iy)}, WinCoord{{W0, ax.o}, ax.start(ix)}, t, ay.e,
+              ax.e, (long long)t.b * 3 * ay.e * ax.e, lut_g, rev, out, stage_bytes);
 }
 
 }  // namespace
@@ -125,9 +139,12 @@ extern "C" int ifseg_image_load(const void* images, int B, int H0, int W0, int o
   return 0;
 }
 
-extern "C" int ifseg_image_load_windows(const void* images, int B, int H0, int W0, int oh, int ow, int crop_h, int crop_w,
-                                        int stride_h, int stride_w, const float* lut, int reverse_channels, void* out,
-                                        int out_bytes, void* stream) {
+namespace {
+
+// ifseg_image_load_windows and ifseg_image_load_windows_mirrored
+template <bool MIRROR>
+int launch_load_windows(const void* images, int B, int H0, int W0, int oh, int ow, int crop_h, int crop_w, int stride_h,
+                        int stride_w, const float* lut, int reverse_channels, void* out, int out_bytes, void* stream) {
   (void)hipGetLastError();
   if (!images || !lut || !out || (out_bytes != 4 && out_bytes != 2)) return IFSEG_ERR_BAD_ARG;
   if (((size_t)out & 15) || ((size_t)lut & 3)) return IFSEG_ERR_BAD_ARG;
@@ -147,11 +164,27 @@ extern "C" int ifseg_image_load_windows(const void* images, int B, int H0, int W
   const int lds = U8_LUT_BYTES + stage;
   const unsigned char* src = (const unsigned char*)images;
   if (out_bytes == 4)
-    hipLaunchKernelGGL(image_load_windows_kernel<float>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, src, H0, W0,
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(image_load_windows_kernel<float, MIRROR>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, src, H0, W0,
                        ay, ax, tiles_x, tiles_y, lut, reverse_channels, (float*)out, stage);
   else
-    hipLaunchKernelGGL(image_load_windows_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, src, H0, W0,
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(image_load_windows_kernel<bf16_t, MIRROR>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, src, H0, W0,
                        ay, ax, tiles_x, tiles_y, lut, reverse_channels, (bf16_t*)out, stage);
   IFSEG_CHECK_LAUNCH();
   return 0;
+}
+
+}  // namespace
+
+extern "C" int ifseg_image_load_windows(const void* images, int B, int H0, int W0, int oh, int ow, int crop_h, int crop_w,
+                                        int stride_h, int stride_w, const float* lut, int reverse_channels, void* out,
+                                        int out_bytes, void* stream) {
+  return launch_load_windows<false>(images, B, H0, W0, oh, ow, crop_h, crop_w, stride_h, stride_w, lut, reverse_channels, out,
+                                    out_bytes, stream);
+}
+
+extern "C" int ifseg_image_load_windows_mirrored(const void* images, int B, int H0, int W0, int oh, int ow, int crop_h, int crop_w,
+                                                 int stride_h, int stride_w, const float* lut, int reverse_channels, void* out,
+                                                 int out_bytes, void* stream) {
+  return launch_load_windows<true>(images, B, H0, W0, oh, ow, crop_h, crop_w, stride_h, stride_w, lut, reverse_channels, out,
+                                   out_bytes, stream);
 }

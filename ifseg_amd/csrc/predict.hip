@@ -17,6 +17,8 @@
 //            four pixels of a 4-ALIGNED element quad of the flat [B, h, w] index, so the wide stores are aligned whatever w is;
 //            the up to three pixels in front of the first whole quad and behind the last one leave as single elements.
 // No atomics, no scratch buffer, static launch shape, nothing read back.
+// Three more kernels on the same tile and phase 2 follow it: K views of differing grids (seg_predict_views_kernel), the sliding
+// windows of one plane (seg_predict_windows_kernel), and K views of sliding windows (seg_predict_slide_views_kernel).
 //
 // Scoring (ifseg_seg_score / ifseg_seg_score_views / ifseg_seg_areas): the same kernels with an epilogue behind a template flag
 // that counts the tile's pixels against ground truth -- per class #(pred = gt = c), #(pred = c), #(gt = c) and the two tallies --
@@ -703,6 +705,287 @@ __global__ __launch_bounds__(256) void seg_predict_windows_kernel(const float* _
   }
 }
 
+// ---- K views, each the windows of its own plane, into one label map (multi-scale + flip over sliding-window inference) ----
+// View k is seg_predict_windows_kernel's input at its own [oh_k, ow_k] plane and window grid; all views share crop, stride and
+// the [h, w] output.  Per pixel and class the view's value is slide_pixel's -- the same function on the same arguments, so one
+// unflipped view gives that kernel's bits -- a flipped view sampled at the mirrored output column w - 1 - x.
+//   linear   the K values of a class are added in view order and multiplied by inv_k;
+//   softmax  every view's value is first normalised over the classes, exp(v - max) / sum with the sum in class order (mmseg's
+//            order: slide_inference -> resize -> softmax -> un-flip, averaged over the views).  The normaliser needs all
+//            classes of a pixel and view before anything can be accumulated: two passes over the class chunks leave max and
+//            sum in LDS (SV_NORM_DWORDS per view), the third recomputes the values -- the same inlined code on the same staged
+//            data, contraction off, so the same bits -- normalises and accumulates.
+// The tile, the lane mapping, the class chunks and phase 2 are seg_predict_windows_kernel's.  Its per-axis window bookkeeping is
+// done once per view, view after view through one pair of scratch arrays, and what the class loop needs of it stays in LDS:
+// per view the runs' offsets (sw_adj), the two scales of its coordinate rules and, for a staged view, the source cells of its
+// grid.  (The plane taps of a pixel are one fma and a floor per axis: they are recomputed where they are used, and their LDS
+// goes to the normalisers.)  Views are given staging room in view order while the buffer lasts; a view that no longer fits
+// reads global memory in the same loop.
+// LDS: the linear mode budgets 64 KiB per workgroup as the other kernels do; the softmax mode adds its normalisers (8 KiB per
+// view) on top, up to the device's limit (160 KiB on gfx950), and the staging buffer takes what is left.
+constexpr int SV_VIEW_DWORDS = 2 * SW_MAX_WINDOWS;                // per view: sw_adj [2][SW_MAX_WINDOWS]
+constexpr int SV_NORM_DWORDS = 2 * TILE_ROWS * TILE_COLS;         // per view (softmax): max, then sum, of every pixel
+constexpr int SV_META_LDS = 2560;                                 // >= vm + sw_lo + sw_ext + sw_tot
+constexpr int SV_LDS_CEILING = 160 * 1024;
+constexpr int SV_STAGE_LIMIT = 65536 - PT_TILE_LDS - SV_META_LDS; // the linear mode's: per-view data + staged grids
+
+int g_slide_views_stage_limit = SV_STAGE_LIMIT;
+
+struct SlideView {
+  const float* scores;
+  Slide sl;
+  int flip;
+};
+struct SlideViewTable {
+  SlideView v[PV_MAX_VIEWS];
+};
+
+// one view under one tile; off: its first float in the staging buffer (cells, then the grid), < 0 when it reads global memory
+struct SlideMeta {
+  const float* base;      // the image's windows
+  Slide sl;
+  float sy, sx, py, px;   // window -> grid and output -> plane scales
+  int flip, iya, ixa, FH, FW, off;
+};
+static_assert(sizeof(SlideMeta) * PV_MAX_VIEWS + 2 * 2 * SW_MAX_WINDOWS * 4 + 16 <= SV_META_LDS, "SV_META_LDS");
+
+// out = view m's merged and resized value of classes c0 .. c0 + cn - 1 at output pixel (y, x), y wave-uniform; vd: the view's
+// SV_VIEW_DWORDS, stage: the staging buffer with the chunk's patches in place
+__device__ __forceinline__ void slide_view_value(const SlideMeta& m, const int* vd, const float* stage, int n, int c0, int cn,
+                                                 int y, int x, int w, f32x4 (&out)[PV_CHUNK / 4]) {
+  const Slide sl = m.sl;
+  const FloatCoord cwy{m.sy, sl.hpw}, cwx{m.sx, sl.wpw};
+  int Yt[2], Xt[2];
+  float ly2, lx2;
+  FloatCoord{m.py, sl.y.o}(y, &Yt[0], &Yt[1], &ly2);
+  // the row is the wave's: so are its plane rows and their weight
+  Yt[0] = __builtin_amdgcn_readfirstlane(Yt[0]); Yt[1] = __builtin_amdgcn_readfirstlane(Yt[1]);
+  ly2 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(ly2)));
+  FloatCoord{m.px, sl.x.o}(m.flip ? w - 1 - x : x, &Xt[0], &Xt[1], &lx2);
+  const bool anyx1 = __ballot(lx2 != 0.f) != 0;
+  const int (&adj)[2][SW_MAX_WINDOWS] = *reinterpret_cast<const int (*)[2][SW_MAX_WINDOWS]>(vd);
+  const int iya = __builtin_amdgcn_readfirstlane(m.iya), ixa = __builtin_amdgcn_readfirstlane(m.ixa);
+  const int off = __builtin_amdgcn_readfirstlane(m.off);
+#pragma unroll
+  for (int c = 0; c < PV_CHUNK / 4; ++c) out[c] = f32x4{-0.f, -0.f, -0.f, -0.f};
+  if (off >= 0) {
+    const int FH = __builtin_amdgcn_readfirstlane(m.FH), FW = __builtin_amdgcn_readfirstlane(m.FW);
+    slide_pixel<true>(stage + off + ((FH + FW + 3) & ~3), sl, cwy, cwx, adj, iya, ixa, FW * PV_STRIDE, n, cn, Yt, ly2, Xt, lx2,
+                      anyx1, out);
+  } else {
+    slide_pixel<false>(m.base + c0, sl, cwy, cwx, adj, iya, ixa, 0, n, cn, Yt, ly2, Xt, lx2, anyx1, out);
+  }
+}
+
+template <typename S>
+__global__ __launch_bounds__(256) void seg_predict_slide_views_kernel(SlideViewTable views, int K, float inv_k, int softmax, int n,
+                                                                      int h, int w, int tiles_x, int tiles_y,
+                                                                      void* __restrict__ labels, int label_bytes,
+                                                                      float* __restrict__ conf, float* __restrict__ probs,
+                                                                      int stage_floats, S sc) {
+  // (scoring: the table,) K * SV_VIEW_DWORDS of per-view data, (softmax: K * SV_NORM_DWORDS of normalisers,) then stage_floats
+  // of source cells and staged grids
+  extern __shared__ __attribute__((aligned(16))) float dyn[];
+  __shared__ int t_lab[TILE_ROWS][TILE_COLS];
+  __shared__ float t_conf[TILE_ROWS][TILE_COLS];
+  __shared__ SlideMeta vm[PV_MAX_VIEWS];
+  // scratch of the view being set up: per axis and window of the tile's range, first patch of its run and their number
+  __shared__ int sw_lo[2][SW_MAX_WINDOWS], sw_ext[2][SW_MAX_WINDOWS], sw_tot[2];
+  int* vdata = reinterpret_cast<int*>(dyn);
+  if constexpr (S::on) {
+    score_zero(reinterpret_cast<uint32_t*>(dyn), n);              // published by the barriers below
+    vdata += score_dwords(n);
+  }
+  float* norm = reinterpret_cast<float*>(vdata + K * SV_VIEW_DWORDS);
+  float* stage = norm + (softmax ? K * SV_NORM_DWORDS : 0);
+
+  const auto [b, X0, Y0, xend, yend, lane, wave] = tile_decode(tiles_x, tiles_y, h, w);
+  const int t = threadIdx.x;
+
+  // thread k takes view k out of the kernel argument (a chain of selects, as in seg_predict_views_kernel)
+  if (t < K) {
+    SlideView v = views.v[0];
+#pragma unroll
+    for (int i = 1; i < PV_MAX_VIEWS; ++i)
+      if (t == i) v = views.v[i];
+    SlideMeta& m = vm[t];
+    m.base = v.scores + (long long)b * v.sl.y.g * v.sl.x.g * v.sl.hpw * v.sl.wpw * n;
+    m.sl = v.sl;
+    m.sy = (float)v.sl.hpw / (float)v.sl.y.e; m.sx = (float)v.sl.wpw / (float)v.sl.x.e;
+    m.py = (float)v.sl.y.o / (float)h; m.px = (float)v.sl.x.o / (float)w;
+    m.flip = v.flip;
+  }
+  __syncthreads();
+
+  // seg_predict_windows_kernel's bookkeeping, view after view; a flipped view is under the mirrored columns of the tile
+  int used = 0;
+  for (int k = 0; k < K; ++k) {
+    const Slide sl = vm[k].sl;
+    const int flip = vm[k].flip;
+    const FloatCoord c2y{vm[k].py, sl.y.o}, c2x{vm[k].px, sl.x.o};                                          // output -> plane
+    const FloatCoord cwy{vm[k].sy, sl.hpw}, cwx{vm[k].sx, sl.wpw};                                          // window -> grid
+    const int cells = sl.hpw * sl.wpw;
+    int* vd = vdata + k * SV_VIEW_DWORDS;
+    int (&adj)[2][SW_MAX_WINDOWS] = *reinterpret_cast<int (*)[2][SW_MAX_WINDOWS]>(vd);
+    int Ylo, Yhi, Xlo, Xhi;
+    footprint(c2y, Y0, yend - 1, &Ylo, &Yhi);
+    footprint(c2x, flip ? w - xend : X0, flip ? w - 1 - X0 : xend - 1, &Xlo, &Xhi);
+    const int iya = sl.y.first(Ylo), ny = sl.y.last(Yhi) - iya + 1, ixa = sl.x.first(Xlo), nx = sl.x.last(Xhi) - ixa + 1;
+    const bool isx = t >= ny;
+    const int ai = isx ? t - ny : t;                              // thread t < ny + nx takes one window of one axis
+    if (t < ny + nx) {
+      const SlideAxis a = isx ? sl.x : sl.y;
+      const int st = a.start((isx ? ixa : iya) + ai), lo = isx ? Xlo : Ylo, hi = isx ? Xhi : Yhi;
+      int plo, phi;
+      footprint(isx ? cwx : cwy, max(lo, st) - st, min(hi, st + a.e - 1) - st, &plo, &phi);
+      sw_lo[isx][ai] = plo; sw_ext[isx][ai] = phi - plo + 1;
+    }
+    __syncthreads();
+    if (t < 2) {
+      int run = 0;
+      for (int i = 0; i < (t ? nx : ny); ++i) { adj[t][i] = run - sw_lo[t][i]; run += sw_ext[t][i]; }
+      sw_tot[t] = run;
+    }
+    __syncthreads();
+    const int FH = sw_tot[0], FW = sw_tot[1], ncs = (FH + FW + 3) & ~3;
+    const long long need = (long long)FH * FW * PV_STRIDE + ncs;
+    const bool staged = need <= (long long)(stage_floats - used);                               // workgroup-uniform
+    if (staged && t < ny + nx) {
+      // the source of staged row R / column C, in patches from the image's first window: cellsrc[R] + cellsrc[FH + C]
+      int* cellsrc = reinterpret_cast<int*>(stage + used);
+      const int i = (isx ? ixa : iya) + ai, first = adj[isx][ai] + sw_lo[isx][ai];
+      for (int r = 0; r < sw_ext[isx][ai]; ++r)
+        cellsrc[(isx ? FH : 0) + first + r] = isx ? i * cells + sw_lo[1][ai] + r : i * sl.x.g * cells + (sw_lo[0][ai] + r) * sl.wpw;
+    }
+    if (t == 0) {
+      SlideMeta& m = vm[k];
+      m.iya = iya; m.ixa = ixa; m.FH = FH; m.FW = FW; m.off = staged ? used : -1;
+    }
+    if (staged) used += (int)need;
+    __syncthreads();                              // the scratch is free for the next view; the last one publishes everything
+  }
+
+  // phase 0 of a class chunk: 16 threads per patch, one class each; the classes past n are zero
+  auto stage_chunk = [&](int c0, int cn) {
+    const int cc = t & 15;
+    for (int k = 0; k < K; ++k) {
+      const int off = vm[k].off;
+      if (off < 0) continue;
+      const int FH = vm[k].FH, FW = vm[k].FW;
+      const int* cellsrc = reinterpret_cast<const int*>(stage + off);
+      float* grid = stage + off + ((FH + FW + 3) & ~3);
+      const float* sb = vm[k].base + c0;
+      for (int p = t >> 4; p < FH * FW; p += 16) {
+        const int R = p / FW, C = p - R * FW;
+        grid[p * PV_STRIDE + cc] = cc < cn ? sb[(long long)(cellsrc[R] + cellsrc[FH + C]) * n + cc] : 0.f;
+      }
+    }
+  };
+
+  const int x = min(X0 + lane, w - 1);
+  // softmax: the maximum of every pixel and view over all classes, then the sum of exp(v - max) in class order
+  if (softmax) {
+#pragma unroll 1
+    for (int pass = 0; pass < 2; ++pass) {
+#pragma unroll 1
+      for (int c0 = 0; c0 < n; c0 += PV_CHUNK) {
+        const int cn = min(PV_CHUNK, n - c0);
+        __syncthreads();                          // the previous chunk has been read
+        stage_chunk(c0, cn);
+        __syncthreads();
+#pragma unroll 1
+        for (int j = 0; j < 4; ++j) {
+          const int row = wave * 4 + j;
+#pragma unroll 1
+          for (int k = 0; k < K; ++k) {
+            f32x4 out[PV_CHUNK / 4];
+            slide_view_value(vm[k], vdata + k * SV_VIEW_DWORDS, stage, n, c0, cn, min(Y0 + row, h - 1), x, w, out);
+            float* nm = norm + k * SV_NORM_DWORDS + row * TILE_COLS + lane;   // the thread's own pixel: no barrier needed
+            if (pass == 0) {
+              float mx = c0 ? nm[0] : -INFINITY;
+#pragma unroll
+              for (int c = 0; c < PV_CHUNK; ++c)
+                if (c < cn) mx = fmaxf(mx, out[c >> 2][c & 3]);
+              nm[0] = mx;
+            } else {
+              const float mx = nm[0];
+              float s = c0 ? nm[TILE_ROWS * TILE_COLS] : 0.f;
+#pragma unroll
+              for (int c = 0; c < PV_CHUNK; ++c)
+                if (c < cn) s += expf(out[c >> 2][c & 3] - mx);
+              nm[TILE_ROWS * TILE_COLS] = s;
+            }
+          }
+        }
+      }
+    }
+  }
+
+  float* pb = probs ? probs + (long long)b * n * h * w : nullptr;
+  const long long cstride = (long long)h * w;
+
+  for (int c0 = 0; c0 < n; c0 += PV_CHUNK) {
+    const int cn = min(PV_CHUNK, n - c0);
+    __syncthreads();                              // the previous chunk has been read
+    stage_chunk(c0, cn);
+    __syncthreads();
+
+    // phase 1, row by row; the view loop adds in view order.  -0 is the neutral element of the addition
+#pragma unroll 1
+    for (int j = 0; j < 4; ++j) {
+      const int row = wave * 4 + j, yr = Y0 + row;
+      f32x4 acc[PV_CHUNK / 4];
+#pragma unroll
+      for (int c = 0; c < PV_CHUNK / 4; ++c) acc[c] = f32x4{-0.f, -0.f, -0.f, -0.f};
+#pragma unroll 1
+      for (int k = 0; k < K; ++k) {
+        f32x4 out[PV_CHUNK / 4];
+        slide_view_value(vm[k], vdata + k * SV_VIEW_DWORDS, stage, n, c0, cn, min(Y0 + row, h - 1), x, w, out);
+        if (softmax) {
+          const float* nm = norm + k * SV_NORM_DWORDS + row * TILE_COLS + lane;
+          const float mx = nm[0], s = nm[TILE_ROWS * TILE_COLS];
+#pragma unroll
+          for (int c = 0; c < PV_CHUNK; ++c)
+            if (c < cn) out[c >> 2][c & 3] = expf(out[c >> 2][c & 3] - mx) / s;
+        }
+#pragma unroll
+        for (int c = 0; c < PV_CHUNK / 4; ++c) acc[c] += out[c];
+      }
+      float bv = c0 ? t_conf[row][lane] : -INFINITY;
+      int bc = c0 ? t_lab[row][lane] : 0;
+      const bool ok = yr < h && X0 + lane < w;
+      float* pp = pb + (long long)c0 * cstride + min(yr, h - 1) * w + x;
+#pragma unroll
+      for (int c = 0; c < PV_CHUNK; ++c) {
+        if (c < cn) {
+          const float v = acc[c >> 2][c & 3] * inv_k;
+          if (v > bv) { bv = v; bc = c0 + c; }
+          if (pb && ok) pp[c * cstride] = v;
+        }
+      }
+      t_conf[row][lane] = bv; t_lab[row][lane] = bc;
+    }
+  }
+  __syncthreads();
+
+  // phase 2
+  if constexpr (S::on) {
+    if (labels || conf) store_tile<true>(t_lab, t_conf, b, X0, Y0, xend, h, w, labels, label_bytes, conf);
+    int pofs[4], pred[4];
+    bool ok[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int row = wave * 4 + j;
+      pofs[j] = min(Y0 + row, h - 1) * w + x;
+      ok[j] = Y0 + row < h && X0 + lane < w;
+      pred[j] = t_lab[row][lane];
+    }
+    score_tile(sc, reinterpret_cast<uint32_t*>(dyn), n, (long long)b * h * w, pofs, ok, pred);
+  } else {
+    store_tile<false>(t_lab, t_conf, b, X0, Y0, xend, h, w, labels, label_bytes, conf);
+  }
+}
+
 // ---- labels from elsewhere (the CRF's argmax, another model) against ground truth ----
 // A lane takes 16 consecutive pixels per step: their labels and their ground truth come as aligned 16-byte loads.  The body
 // starts at the first 16-byte boundary of `lab`; the ground truth of the same pixels then sits s bytes behind a boundary of
@@ -844,6 +1127,19 @@ int launch_views(const ifseg_predict_view* views, int K, int B, int n, int h, in
   return 0;
 }
 
+// an upper bound, in bytes, of the source cells and the staged grid of any tile of an [h, w] output under the windows of sl.
+// Per axis: the windows that hold any of the tile's plane footprint (a regular grid, + the pulled-back last one), times the
+// patches of one window under it
+long long slide_stage_bound(const Slide& sl, int h, int w) {
+  auto axis_bound = [](const SlideAxis& a, int out, int grid, int tile) {
+    const long long plane = footprint_bound(a.o, a.o, out, tile, 3);
+    const long long windows = std::min<long long>(a.g, (plane + a.e - 1) / a.s + 2);
+    return windows * footprint_bound(grid, grid, a.e, (int)std::min<long long>(plane, a.e), 3);
+  };
+  const long long fh = axis_bound(sl.y, h, sl.hpw, TILE_ROWS), fw = axis_bound(sl.x, w, sl.wpw, TILE_COLS);
+  return (fh * fw * PV_STRIDE + fh + fw + 4) * 4;
+}
+
 // ifseg_seg_predict_windows (S = NoScore) and ifseg_seg_score_windows
 template <typename S>
 int launch_windows(const float* scores, int B, int hpw, int wpw, int n, int oh, int ow, int crop_h, int crop_w, int stride_h,
@@ -862,15 +1158,7 @@ int launch_windows(const float* scores, int B, int hpw, int wpw, int n, int oh, 
   int tiles_x, tiles_y;
   long long blocks;
   if (!tile_grid(h, w, B, &tiles_x, &tiles_y, &blocks)) return IFSEG_ERR_BAD_SHAPE;
-  // an upper bound of any tile's staged grid, per axis: the windows that hold any of the tile's plane footprint (a regular
-  // grid, + the pulled-back last one), times the patches of one window under it
-  auto axis_bound = [](const SlideAxis& a, int out, int grid, int tile) {
-    const long long plane = footprint_bound(a.o, a.o, out, tile, 3);
-    const long long windows = std::min<long long>(a.g, (plane + a.e - 1) / a.s + 2);
-    return windows * footprint_bound(grid, grid, a.e, (int)std::min<long long>(plane, a.e), 3);
-  };
-  const long long fh = axis_bound(sl.y, h, hpw, TILE_ROWS), fw = axis_bound(sl.x, w, wpw, TILE_COLS);
-  const long long need = (fh * fw * PV_STRIDE + fh + fw + 4) * 4;
+  const long long need = slide_stage_bound(sl, h, w);
   const int counters = S::on ? score_dwords(n) * 4 : 0;
   const int limit = std::max(std::min(g_windows_stage_limit, SW_STAGE_LIMIT - counters), 0);
   const int stage = (int)std::min<long long>(need, limit) & ~15;
@@ -880,7 +1168,81 @@ int launch_windows(const float* scores, int B, int hpw, int wpw, int n, int oh, 
   return 0;
 }
 
+// the most LDS one workgroup of the current device may take, at least the 64 KiB every launch of this file assumes
+int device_lds_limit() {
+  int dev = 0, lim = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&lim, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess)
+    (void)hipGetLastError();
+  return std::min(std::max(lim, 65536), SV_LDS_CEILING);
+}
+
+// ifseg_seg_predict_slide_views (S = NoScore) and ifseg_seg_score_slide_views
+template <typename S>
+int launch_slide_views(const ifseg_slide_view* views, int K, int B, int n, int crop_h, int crop_w, int stride_h, int stride_w, int h,
+                       int w, int softmax, void* labels, int label_bytes, float* conf, float* probs, void* stream, S sc) {
+  (void)hipGetLastError();
+  if (!views || K < 1 || K > PV_MAX_VIEWS) return IFSEG_ERR_BAD_ARG;
+  if ((!S::on || labels) && (!labels || (label_bytes != 1 && label_bytes != 2))) return IFSEG_ERR_BAD_ARG;
+  if (n < 1 || n > PT_MAX_CLASSES || (labels && label_bytes == 1 && n > 256)) return IFSEG_ERR_BAD_ARG;
+  if (B < 1 || h < 1 || w < 1 || (long long)B * h * w >= (1ll << 31)) return IFSEG_ERR_BAD_SHAPE;
+  if (((size_t)labels & 15) || ((size_t)conf & 15) || ((size_t)probs & 3)) return IFSEG_ERR_BAD_ARG;
+  int tiles_x, tiles_y;
+  long long blocks;
+  if (!tile_grid(h, w, B, &tiles_x, &tiles_y, &blocks)) return IFSEG_ERR_BAD_SHAPE;
+  SlideViewTable table = {};
+  long long need = 0;
+  for (int k = 0; k < K; ++k) {
+    const ifseg_slide_view& v = views[k];
+    if (!v.scores || ((size_t)v.scores & 3)) return IFSEG_ERR_BAD_ARG;
+    if (v.hpw < 1 || v.wpw < 1) return IFSEG_ERR_BAD_SHAPE;
+    Slide sl = {{}, {}, v.hpw, v.wpw};
+    if (!slide_axis(v.oh, crop_h, stride_h, &sl.y) || !slide_axis(v.ow, crop_w, stride_w, &sl.x)) return IFSEG_ERR_BAD_SHAPE;
+    const long long nw = (long long)sl.y.g * sl.x.g;
+    // offsets inside one image's windows are ints: Nw hpw wpw n < 2^31
+    if (nw > SW_MAX_WINDOWS || nw * v.hpw * v.wpw >= (1ll << 31) / PT_MAX_CLASSES) return IFSEG_ERR_BAD_SHAPE;
+    table.v[k] = {v.scores, sl, v.flip != 0};
+    need += slide_stage_bound(sl, h, w);
+  }
+  // (the scoring table,) the per-view data and the normalisers come first; what the limit leaves is the staging buffer
+  const int counters = S::on ? score_dwords(n) * 4 : 0;
+  const int norms = softmax ? K * SV_NORM_DWORDS * 4 : 0;
+  const int fixed = counters + K * SV_VIEW_DWORDS * 4 + norms;
+  const int fixed_lds = PT_TILE_LDS + SV_META_LDS;
+  const int total = softmax ? std::min(65536 + norms, device_lds_limit()) : 65536;
+  if (fixed_lds + fixed > total) return IFSEG_ERR_BAD_SHAPE;     // a device whose LDS does not hold the normalisers
+  const int limit = std::min(g_slide_views_stage_limit, total - fixed_lds - fixed);
+  const int stage = (int)std::min<long long>(need, std::max(limit, 0)) & ~15;
+  if (fixed_lds + fixed + stage > 65536)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&seg_predict_slide_views_kernel<S>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, fixed + stage);
+  hipLaunchKernelGGL(seg_predict_slide_views_kernel<S>, dim3((unsigned)blocks), dim3(256), fixed + stage, (hipStream_t)stream,
+                     table, K, (float)(1.0 / K), softmax != 0, n, h, w, tiles_x, tiles_y, labels, label_bytes, conf, probs,
+                     stage / 4, sc);
+  IFSEG_CHECK_LAUNCH();
+  return 0;
+}
+
 }  // namespace
+
+extern "C" int ifseg_seg_predict_slide_views_staging(int max_bytes) {
+  return swap_limit(g_slide_views_stage_limit, SV_STAGE_LIMIT, max_bytes);
+}
+
+extern "C" int ifseg_seg_predict_slide_views(const ifseg_slide_view* views, int K, int B, int n, int crop_h, int crop_w,
+                                             int stride_h, int stride_w, int h, int w, int softmax, void* labels, int label_bytes,
+                                             float* conf, float* probs, void* stream) {
+  return launch_slide_views(views, K, B, n, crop_h, crop_w, stride_h, stride_w, h, w, softmax, labels, label_bytes, conf, probs,
+                            stream, NoScore{});
+}
+
+extern "C" int ifseg_seg_score_slide_views(const ifseg_slide_view* views, int K, int B, int n, int crop_h, int crop_w, int stride_h,
+                                           int stride_w, int h, int w, int softmax, void* labels, int label_bytes, float* conf,
+                                           float* probs, const void* gt, int gt_bytes, int raw_labels, unsigned long long* areas,
+                                           unsigned long long* tally, void* stream) {
+  if (const int rc = score_refusal(gt, gt_bytes, areas, tally)) return rc;
+  return launch_slide_views(views, K, B, n, crop_h, crop_w, stride_h, stride_w, h, w, softmax, labels, label_bytes, conf, probs,
+                            stream, Score{gt, gt_bytes, raw_labels != 0, areas, tally});
+}
 
 extern "C" int ifseg_seg_predict_staging(int max_bytes) { return swap_limit(g_stage_limit, PT_STAGE_LIMIT, max_bytes); }
 

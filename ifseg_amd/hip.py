@@ -1250,6 +1250,64 @@ def seg_score_windows(scores, hpw, wpw, oh, ow, crop, stride, gt, raw_labels=Tru
     return areas, tally, lab, cf, pr
 
 
+class _SlideView(ctypes.Structure):
+    _fields_ = [("scores", c_void_p), ("hpw", c_int), ("wpw", c_int), ("oh", c_int), ("ow", c_int), ("flip", c_int)]
+
+
+def _slide_views_table(views, crop, stride):
+    """the checks of the two slide-views bindings -> (table, K, B, n, device, (crop_h, crop_w), (stride_h, stride_w))"""
+    views = list(views)
+    assert 1 <= len(views) <= SEG_PREDICT_MAX_VIEWS, len(views)
+    table = (_SlideView * len(views))()
+    B = n = dev = None
+    for k, (scores, hpw, wpw, oh, ow, flip) in enumerate(views):
+        oh, ow, cr, st, nw, _, _ = _slide_geometry(oh, ow, crop, stride)
+        b, m = _windows_scores(scores, hpw, wpw, nw)
+        if k == 0:
+            B, n, dev = b, m, scores.device
+        assert b == B and m == n and scores.device == dev, (k, tuple(scores.shape), B, n)
+        table[k] = _SlideView(_ptr(scores), int(hpw), int(wpw), oh, ow, 1 if flip else 0)
+    return table, len(views), B, n, dev, cr, st
+
+
+def seg_predict_slide_views(views, crop, stride, h, w, softmax, conf=False, probs=False, staging_bytes=None, label_dtype=None):
+    """Multi-scale + flip over sliding windows, the merge: views is a list of 1 .. 16 (scores fp32 [B, Nw, hpw*wpw, n], hpw, wpw,
+    oh, ow, flip), each an input of `seg_predict_windows` at its own [oh, ow] plane under the call's crop and stride; flip: the
+    network saw the resized image mirrored -> (labels, conf, probs) at h x w as `seg_predict`, of the MEAN of the views: every
+    view merged and resized by seg_predict_windows' rule (a flipped one taken at the mirrored column), with `softmax`
+    normalised over the classes per pixel (mmseg's order: logits merged, then softmax), the values added in fp32 in view order
+    and multiplied by float(1 / K), in ONE launch (csrc/predict.hip); `predict.slide_views_reference` is the specification.
+    One unflipped view without softmax gives seg_predict_windows' outputs bit for bit.  crop, stride: an int or an (h, w) pair
+    each.  staging_bytes, label_dtype: as in `seg_predict`."""
+    table, K, B, n, dev, crop, stride = _slide_views_table(views, crop, stride)
+    assert h >= 1 and w >= 1 and B * h * w < 2 ** 31, (B, h, w)
+    labels, cf, pr = _predict_outputs(B, n, h, w, dev, conf, probs, label_dtype)
+    with _staging(lib().ifseg_seg_predict_slide_views_staging, staging_bytes):
+        _check(lib().ifseg_seg_predict_slide_views(table, c_int(K), c_int(B), c_int(n), c_int(crop[0]), c_int(crop[1]),
+                                                   c_int(stride[0]), c_int(stride[1]), c_int(h), c_int(w),
+                                                   c_int(1 if softmax else 0), _ptr(labels), c_int(labels.element_size()),
+                                                   _ptr(cf), _ptr(pr), _stream()), "seg_predict_slide_views")
+    return labels, cf, pr
+
+
+def seg_score_slide_views(views, crop, stride, gt, softmax, raw_labels=True, labels=False, conf=False, probs=False, areas=None,
+                          tally=None, staging_bytes=None, label_dtype=None):
+    """`seg_predict_slide_views` at gt's own [B, h, w] with the scoring in the kernel's epilogue; results as `seg_score`."""
+    table, K, B, n, dev, crop, stride = _slide_views_table(views, crop, stride)
+    h, w = _score_gt(gt, B, dev)
+    assert B * h * w < 2 ** 31, (B, h, w)
+    areas, tally = _score_counters(n, dev, areas, tally)
+    lab, cf, pr = _predict_outputs(B, n, h, w, dev, conf, probs, label_dtype, labels)
+    with _staging(lib().ifseg_seg_predict_slide_views_staging, staging_bytes):
+        _check(lib().ifseg_seg_score_slide_views(table, c_int(K), c_int(B), c_int(n), c_int(crop[0]), c_int(crop[1]),
+                                                 c_int(stride[0]), c_int(stride[1]), c_int(h), c_int(w),
+                                                 c_int(1 if softmax else 0), _ptr(lab), c_int(lab.element_size() if labels else 0),
+                                                 _ptr(cf), _ptr(pr), _ptr(gt), c_int(gt.element_size()),
+                                                 c_int(1 if raw_labels else 0), _ptr(areas), _ptr(tally), _stream()),
+               "seg_score_slide_views")
+    return areas, tally, lab, cf, pr
+
+
 _image_luts = {}         # (mean, std, device) -> fp32 [3, 256] on the device; at most 16 entries
 
 
@@ -1284,12 +1342,14 @@ def image_load(images_u8, oh, ow, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), rev
 
 
 def image_load_windows(images_u8, oh, ow, crop, stride, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), reverse_channels=False,
-                       dtype=torch.float32, staging_bytes=None):
+                       dtype=torch.float32, staging_bytes=None, flip=False):
     """uint8 [B, H0, W0, 3] -> the window batch [B Nw, 3, ch, cw] in `dtype` of sliding-window inference, written directly
     (csrc/imgload.hip): element (b Nw + k, c, y, x) is `image_load(..., oh, ow)`'s element (b, c, ys[k] + y, xs[k] + x), bit for
     bit, for the windows of `imageio.slide_windows(oh, ow, crop, stride)`; no [B, 3, oh, ow] image is written.
     `imageio.image_load_windows_reference` is the specification.  crop, stride: an int or an (h, w) pair each; the other
-    arguments as in `image_load`."""
+    arguments as in `image_load`.  flip: the windows of the MIRRORED resized image, bit for bit the `slide_windows` slices of
+    `image_load(...).flip(-1)` (mirrored after the resize, as mmseg does; not the unmirrored windows flipped: the last window
+    of an axis is pulled back inside, so the starts are not symmetric)."""
     assert images_u8.dtype == torch.uint8 and images_u8.dim() == 4 and images_u8.shape[-1] == 3 and images_u8.is_contiguous(), \
         (images_u8.dtype, tuple(images_u8.shape), images_u8.stride())
     B, H0, W0, _ = images_u8.shape
@@ -1301,10 +1361,10 @@ def image_load_windows(images_u8, oh, ow, crop, stride, mean=(0.5, 0.5, 0.5), st
     lut = _image_lut(mean, std, dev)
     out = torch.empty(B * nw, 3, ch, cw, dtype=dtype, device=dev)
     with _staging(lib().ifseg_image_load_staging, staging_bytes):
-        _check(lib().ifseg_image_load_windows(_ptr(images_u8), c_int(B), c_int(H0), c_int(W0), c_int(oh), c_int(ow), c_int(crop[0]),
-                                              c_int(crop[1]), c_int(stride[0]), c_int(stride[1]), _ptr(lut),
-                                              c_int(1 if reverse_channels else 0), _ptr(out), c_int(out.element_size()), _stream()),
-               "image_load_windows")
+        entry = lib().ifseg_image_load_windows_mirrored if flip else lib().ifseg_image_load_windows
+        _check(entry(_ptr(images_u8), c_int(B), c_int(H0), c_int(W0), c_int(oh), c_int(ow), c_int(crop[0]), c_int(crop[1]),
+                     c_int(stride[0]), c_int(stride[1]), _ptr(lut), c_int(1 if reverse_channels else 0), _ptr(out),
+                     c_int(out.element_size()), _stream()), "image_load_windows")
     return out
 
 

@@ -10,7 +10,8 @@ sees RGB, as PIL delivers it, and `reverse_channels` is off by default (the swit
 indexing; `hip.image_load` (csrc/imgload.hip) is the implementation.
 
 Sliding-window inference (`Segmenter.segment_raw(slide=...)`, mmseg's `test_cfg mode='slide'`): `slide_windows` is the window
-rule, `plan_slide` the grouping of a call, `image_load_windows_reference` the specification of `hip.image_load_windows`.
+rule, `plan_slide` the grouping of a call, `image_load_windows_reference` the specification of `hip.image_load_windows`;
+`plan_slide_views` groups a call that slides over every view of multi-scale + flip (`Segmenter(slide_views=True)`).
 """
 import torch
 
@@ -219,12 +220,45 @@ def plan_slide(shapes, patch_image_size, crop, stride, ratio=1.0, max_batch=8):
     return per_image, [(hw, size, idx) for (hw, size), idx in loads.items()], forwards
 
 
+def plan_slide_views(shapes, patch_image_size, crop, stride, scales=(1.0,), flip=False, max_batch=8):
+    """`plan_slide` for multi-scale + flip over sliding windows, as a pure function: -> (views, per_image, loads, forwards).
+    views: `view_list(scales, flip)`; view v of image i is the pair (i, v), window k of it the triple (i, v, k).
+    per_image: [[((oh, ow), ys, xs, (ch, cw))] per view], image i at `eval_size(H, W, P, ratio_v)` and its `slide_windows`
+    (a mirrored view has its unmirrored twin's geometry; its windows are cut from the mirrored image).
+    loads: [((H, W), (oh, ow), flipped, [image indices])], one `image_load_windows` launch per distinct (source shape, size,
+    flip), in order of first appearance; ratios that give one size share the load.
+    forwards: [((ch, cw), [(i, v, k)])], one model forward per entry: the windows of one size, of whatever view and image, in
+    (image, view, window) order, at most `max_batch` of them; the entries of one size follow each other.
+    ValueError: more than MAX_VIEWS views, more than MAX_WINDOWS windows in any view, a crop or stride outside the rule."""
+    if max_batch < 1:
+        raise ValueError("segment_raw: max_batch must be >= 1, got %r" % (max_batch,))
+    views = view_list(scales, flip)
+    per_image, loads, by_size = [], {}, {}
+    for i, (h, w) in enumerate(shapes):
+        h, w = int(h), int(w)
+        mine = []
+        for v, (ratio, flipped) in enumerate(views):
+            size = eval_size(h, w, patch_image_size, ratio)
+            ys, xs, ch, cw = slide_windows(size[0], size[1], crop, stride)
+            mine.append((size, ys, xs, (ch, cw)))
+            idx = loads.setdefault(((h, w), size, flipped), [])
+            if i not in idx:
+                idx.append(i)
+            by_size.setdefault((ch, cw), []).extend((i, v, k) for k in range(len(ys) * len(xs)))
+        per_image.append(mine)
+    forwards = [(size, ivk[k:k + max_batch]) for size, ivk in by_size.items() for k in range(0, len(ivk), max_batch)]
+    return views, per_image, [(hw, size, f, idx) for (hw, size, f), idx in loads.items()], forwards
+
+
 def image_load_windows_reference(images_u8, oh, ow, crop, stride, mean=HALF, std=HALF, reverse_channels=False,
-                                 dtype=torch.float64, out_dtype=torch.float32):
+                                 dtype=torch.float64, out_dtype=torch.float32, flip=False):
     """CPU specification of hip.image_load_windows: uint8 [B, H0, W0, 3] -> normalised `out_dtype` [B Nw, 3, ch, cw]: element
     (b Nw + k, c, y, x) is `image_load_reference`'s element (b, c, ys[k] + y, xs[k] + x) at (oh, ow), the windows being
-    `slide_windows(oh, ow, crop, stride)`.  A window is a slice of the loaded image, never a resize of its own."""
+    `slide_windows(oh, ow, crop, stride)`.  A window is a slice of the loaded image, never a resize of its own.
+    flip: the windows are slices of the loaded image mirrored along its width (after the resize, as mmseg mirrors)."""
     ys, xs, ch, cw = slide_windows(oh, ow, crop, stride)
     full = image_load_reference(images_u8, oh, ow, mean, std, reverse_channels, dtype, out_dtype)[0]
+    if flip:
+        full = full.flip(-1)
     wins = torch.stack([full[:, :, y:y + ch, x:x + cw] for y in ys for x in xs], 1)
     return wins.reshape(full.shape[0] * len(ys) * len(xs), 3, ch, cw)

@@ -23,7 +23,9 @@ differing grids, mirrored ones included: multi-scale + flip inference), `seg_are
 against ground truth, stand-alone and in the predict kernel's epilogue: mIoU on the device), `image_load` (csrc/imgload.hip: raw uint8 images to
 normalised patch_images, the reference's evaluation transform) and the three ops of sliding-window inference (`image_load_windows`,
 `seg_predict_windows`, `seg_score_windows`: the window batch written directly, and the windows' scores merged into one label
-map in one launch) are inference only and have no backward; `train_load`
+map in one launch) and the two of multi-scale + flip over sliding windows (`seg_predict_slide_views`, `seg_score_slide_views`:
+K views, each a set of windows, merged in one launch, optionally softmaxed per view as mmseg does) are inference only and
+have no backward; `train_load`
 (csrc/trainload.hip: raw images and label maps of any sizes to a training batch under given records, the reference's training
 transform) has integer inputs and no backward either.
 """
@@ -1012,6 +1014,93 @@ def image_load_windows(images: torch.Tensor, oh: int, ow: int, crop: Sequence[in
 def _(images, oh, ow, crop, stride, mean, std, reverse_channels, dtype):
     nb, ch, cw = _image_load_windows_check(images, oh, ow, crop, stride, mean, std, dtype)
     return images.new_empty((nb, 3, ch, cw), dtype=dtype)
+
+
+# ----------------------------------------------------------------------------------------------- views of sliding windows
+def _seg_predict_slide_views_check(scores, hpws, wpws, ohs, ows, flips, crop, stride, h, w, op="ifseg::seg_predict_slide_views"):
+    K = len(scores)
+    if K < 1 or K > hip.SEG_PREDICT_MAX_VIEWS:
+        raise ValueError("%s: %d views, the kernel takes 1 .. %d" % (op, K, hip.SEG_PREDICT_MAX_VIEWS))
+    if any(len(x) != K for x in (hpws, wpws, ohs, ows, flips)):
+        raise ValueError("%s: %d views with %d hpws, %d wpws, %d ohs, %d ows and %d flips (one of each per view)"
+                         % (op, K, len(hpws), len(wpws), len(ohs), len(ows), len(flips)))
+    for k, s in enumerate(scores):
+        if s.dim() == 4 and scores[0].dim() == 4 and (s.shape[0] != scores[0].shape[0] or s.shape[3] != scores[0].shape[3]):
+            raise ValueError("%s: all views share B and n, view %d is %s against %s" % (op, k, tuple(s.shape), tuple(scores[0].shape)))
+        B, n, ldt = _seg_predict_windows_check(s, hpws[k], wpws[k], ohs[k], ows[k], crop, stride, h, w, "%s: view %d" % (op, k))
+    return B, n, ldt
+
+
+def _slide_views_list(scores, hpws, wpws, ohs, ows, flips):
+    return [(s.contiguous(), hp, wp, oh, ow, bool(f)) for s, hp, wp, oh, ow, f in zip(scores, hpws, wpws, ohs, ows, flips)]
+
+
+@custom_op("ifseg::seg_predict_slide_views", mutates_args=(), device_types="cuda")
+def seg_predict_slide_views(scores: Sequence[torch.Tensor], hpws: Sequence[int], wpws: Sequence[int], ohs: Sequence[int],
+                            ows: Sequence[int], flips: Sequence[bool], crop: Sequence[int], stride: Sequence[int], h: int, w: int,
+                            softmax: bool, want_conf: bool, want_probs: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """label map at h x w from K views, each the windows of sliding-window inference at its own [ohs[k], ows[k]] plane
+    (csrc/predict.hip): view k is fp32 [B, Nw_k, hpws[k]*wpws[k], n], mirrored when flips[k]; every view is merged and resized
+    as `seg_predict_windows` does, normalised over the classes when `softmax` (mmseg's order), and the mean over the views is
+    what labels, conf and probs are taken from, in one launch.  Outputs and conventions as `seg_predict`.  Not differentiable."""
+    _seg_predict_slide_views_check(scores, hpws, wpws, ohs, ows, flips, crop, stride, h, w)
+    prev = _stream_scope(scores[0])
+    try:
+        labels, conf, probs = hip.seg_predict_slide_views(_slide_views_list(scores, hpws, wpws, ohs, ows, flips), tuple(crop),
+                                                          tuple(stride), h, w, softmax, conf=want_conf, probs=want_probs)
+        e = lambda t: torch.empty(0, dtype=torch.float32, device=scores[0].device) if t is None else t
+        return labels, e(conf), e(probs)
+    finally:
+        hip.set_stream(prev)
+
+
+@seg_predict_slide_views.register_fake
+def _(scores, hpws, wpws, ohs, ows, flips, crop, stride, h, w, softmax, want_conf, want_probs):
+    B, n, ldt = _seg_predict_slide_views_check(scores, hpws, wpws, ohs, ows, flips, crop, stride, h, w)
+    f32, s = torch.float32, scores[0]
+    return (s.new_empty(B, h, w, dtype=ldt), s.new_empty((B, h, w) if want_conf else (0,), dtype=f32),
+            s.new_empty((B, n, h, w) if want_probs else (0,), dtype=f32))
+
+
+def _seg_score_slide_views_check(scores, hpws, wpws, ohs, ows, flips, crop, stride, gt):
+    op = "ifseg::seg_score_slide_views"
+    _gt_check(op, gt)
+    if gt.dim() != 3:
+        raise ValueError("%s: ground truth must be [B, h, w], got %s" % (op, tuple(gt.shape)))
+    B, n, ldt = _seg_predict_slide_views_check(scores, hpws, wpws, ohs, ows, flips, crop, stride, gt.shape[1], gt.shape[2], op)
+    if gt.shape[0] != B:
+        raise ValueError("%s: ground truth %s for a batch of %d" % (op, tuple(gt.shape), B))
+    return B, n, ldt
+
+
+@custom_op("ifseg::seg_score_slide_views", mutates_args=(), device_types="cuda")
+def seg_score_slide_views(scores: Sequence[torch.Tensor], hpws: Sequence[int], wpws: Sequence[int], ohs: Sequence[int],
+                          ows: Sequence[int], flips: Sequence[bool], crop: Sequence[int], stride: Sequence[int], gt: torch.Tensor,
+                          softmax: bool, raw_labels: bool, want_labels: bool, want_conf: bool, want_probs: bool
+                          ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """`seg_predict_slide_views` at the shape of the ground truth gt (uint8 / int16 [B, h, w]) with the label map counted
+    against it in the kernel's epilogue -> (areas, tally, labels, conf, probs) as `seg_score_views`.  Not differentiable."""
+    _seg_score_slide_views_check(scores, hpws, wpws, ohs, ows, flips, crop, stride, gt)
+    prev = _stream_scope(scores[0])
+    try:
+        areas, tally, labels, conf, probs = hip.seg_score_slide_views(_slide_views_list(scores, hpws, wpws, ohs, ows, flips),
+                                                                      tuple(crop), tuple(stride), gt.contiguous(), softmax,
+                                                                      raw_labels, labels=want_labels, conf=want_conf,
+                                                                      probs=want_probs)
+        e = lambda t, dt: torch.empty(0, dtype=dt, device=gt.device) if t is None else t
+        ldt = torch.uint8 if scores[0].shape[3] <= 256 else torch.int16
+        return areas, tally, e(labels, ldt), e(conf, torch.float32), e(probs, torch.float32)
+    finally:
+        hip.set_stream(prev)
+
+
+@seg_score_slide_views.register_fake
+def _(scores, hpws, wpws, ohs, ows, flips, crop, stride, gt, softmax, raw_labels, want_labels, want_conf, want_probs):
+    B, n, ldt = _seg_score_slide_views_check(scores, hpws, wpws, ohs, ows, flips, crop, stride, gt)
+    f32, s, (h, w) = torch.float32, scores[0], gt.shape[1:]
+    return (s.new_empty((3, n), dtype=torch.int64), s.new_empty((2,), dtype=torch.int64),
+            s.new_empty((B, h, w) if want_labels else (0,), dtype=ldt), s.new_empty((B, h, w) if want_conf else (0,), dtype=f32),
+            s.new_empty((B, n, h, w) if want_probs else (0,), dtype=f32))
 
 
 # ----------------------------------------------------------------------------------------------- train_load

@@ -28,7 +28,20 @@ size for a whole data set, no resized-bias entry, the windows of all images in t
 ONE launch of `hip.seg_predict_windows` per image resizes the windows' scores, averages them where windows overlap and
 resizes the result to the image's shape: no per-window [n, P, P] tensor, sum or count plane is written.  Limits: the
 reference never slides, so there is no golden and parity is to the specification `slide_reference`; a single view only
-(`slide` with several scales or `flip` is a ValueError).
+(`slide` with several scales or `flip` is a ValueError) unless the Segmenter was built with `slide_views=True`.
+
+Multi-scale + flip OVER sliding windows (mmseg's `MultiScaleFlipAug(img_ratios, flip=True)` over `test_cfg mode='slide'`, the
+setting the mIoU tables of fixed-grid transformer segmenters report): `Segmenter(..., slide_views=True)` is the opt-in.  Every
+view of every image is cut into windows (mirrored views from the mirrored resized image, `hip.image_load_windows(flip=True)`),
+all windows of all views and images share batches (`imageio.plan_slide_views`; with crop = P one network size and no
+resized-bias entry for the whole evaluation), and ONE launch of `hip.seg_predict_slide_views` per image merges every view's
+windows, resizes, un-mirrors, and averages the views.  Two orders: upsample="logits" is mmseg's (the merged, resized logits
+of a view are softmaxed per pixel inside the launch, then averaged); upsample="probs" and the neighbour smoothing hand over
+probabilities, and everything behind them is linear.  Limits: 16 views, 64 windows per view, 512 classes; no golden (the
+reference never slides): parity is to the specification `slide_views_reference`.
+
+    seg = Segmenter(model, task, upsample="logits", slide_views=True)
+    score = seg.evaluate_raw(photos, label_pngs, slide=True, scales=(0.5, 0.75, 1.0, 1.25, 1.5, 1.75), flip=True)
 
     out = seg.segment_raw(photos, slide=True)                                                # crop P, stride 2 P // 3
     score = seg.evaluate_raw(photos, label_pngs, slide=(512, 341))                           # (crop, stride), ints or (h, w)
@@ -53,7 +66,7 @@ import torch
 import torch.nn.functional as F
 
 from . import hip
-from .imageio import HALF, eval_size, plan_slide, plan_views, slide_windows, view_list
+from .imageio import HALF, eval_size, plan_slide, plan_slide_views, plan_views, slide_windows, view_list
 from .tasks.mm_tasks.segmentation import BOS, EOS, PROMPT_IDS
 
 MAX_CLASSES = hip.SEG_PREDICT_MAX_CLASSES
@@ -117,6 +130,29 @@ def slide_reference(scores, hpw, wpw, oh, ow, crop, stride, h, w, dtype=torch.fl
     probs = total / count
     if (h, w) != (oh, ow):
         probs = F.interpolate(probs, size=(h, w), mode="bilinear", align_corners=False)
+    labels = probs.argmax(dim=1)
+    return labels, probs.gather(1, labels[:, None]).squeeze(1), probs
+
+
+def slide_views_reference(views, crop, stride, h, w, softmax, dtype=torch.float64):
+    """CPU specification of hip.seg_predict_slide_views: `views` is a list of K entries (scores [B, Nw_k, hpw_k*wpw_k, n], hpw_k,
+    wpw_k, oh_k, ow_k, flip_k), view k being an input of `slide_reference` at its own [oh_k, ow_k] plane.  Per view, in order:
+    p = slide_reference(...)[2], the window merge and the resize to (h, w), unchanged; if flip_k, p = p.flip(-1) (the network
+    saw the resized image mirrored, and mmseg un-mirrors after the resize to the image's shape); if `softmax`,
+    p = p.softmax(1).  The K results are added in view order and multiplied by 1 / K rounded to `dtype`; labels are the first
+    maximum.  softmax=True is mmseg's order (`slide_inference` -> resize -> softmax -> un-flip, summed over the views, divided
+    by K); softmax=False is this project's "probs" order, the per-patch softmax applied in front of the merge and everything
+    behind it linear.  -> (labels int64 [B, h, w], conf [B, h, w], probs [B, n, h, w]) as `upsample_argmax_reference`.
+    Runs on any device."""
+    total = None
+    for scores, hpw, wpw, oh, ow, flip in views:
+        p = slide_reference(scores, hpw, wpw, oh, ow, crop, stride, h, w, dtype)[2]
+        if flip:
+            p = p.flip(-1)
+        if softmax:
+            p = p.softmax(1)
+        total = p if total is None else total + p
+    probs = total * torch.tensor(1.0 / len(views), dtype=dtype, device=total.device)
     labels = probs.argmax(dim=1)
     return labels, probs.gather(1, labels[:, None]).squeeze(1), probs
 
@@ -213,13 +249,16 @@ def _check_classes(n, want_uint8=False):
 
 class Segmenter:
     def __init__(self, model, task=None, category_token_ids=None, prompt_ids=PROMPT_IDS, upsample="probs", smooth_iters=0,
-                 smooth_topk=3, temperature=1.0, crf_iters=0, full_context_alignment=False, label_dtype=None):
+                 smooth_topk=3, temperature=1.0, crf_iters=0, full_context_alignment=False, label_dtype=None, slide_views=False):
         """model: a SegOFAModel on the device.  The class names come from `category_token_ids` (one id sequence per class),
         else the task's `category_token_ids`, else the task's `category_list` through `task.encode_category`.
         upsample: "probs" resizes the per-patch softmax (temperature), the reference demo's order; "logits" resizes the raw
         scores, the criterion's eval order.  smooth_iters > 0: both feed hip.neighbour_smoothing's probabilities.
         crf_iters > 0: mean-field iterations of crf.rgb_dense_crf on the resized values.
-        label_dtype: None (uint8 up to 256 classes, else int16) or torch.uint8 to insist on bytes."""
+        label_dtype: None (uint8 up to 256 classes, else int16) or torch.uint8 to insist on bytes.
+        slide_views: False: `slide` takes a single view, as ever.  True: `segment_raw` / `evaluate_raw(slide=...)` slide over
+        EVERY view of `scales` and `flip` and finish each image with one launch of `hip.seg_predict_slide_views` (see
+        `segment_raw`)."""
         if upsample not in ("probs", "logits"):
             raise ValueError("Segmenter: upsample must be 'probs' or 'logits', got %r" % (upsample,))
         self.model, self.task = model, task
@@ -242,6 +281,7 @@ class Segmenter:
         self.smooth_iters, self.smooth_topk, self.crf_iters = int(smooth_iters), int(smooth_topk), int(crf_iters)
         self.full_context_alignment = bool(full_context_alignment)
         self.label_dtype = label_dtype
+        self.slide_views = bool(slide_views)
         self._src_dev = None
 
     # -- inputs --------------------------------------------------------------------------
@@ -393,13 +433,29 @@ class Segmenter:
         "logits" is mmseg's single-scale order (the logits are merged, and the argmax is unchanged by the softmax mmseg
         applies afterwards), "probs" the demo's order (the per-patch softmax is merged).  A single view only: `slide` with
         several scales or `flip` is a ValueError, because mmseg applies the softmax between the window merge and the view
-        average, which a kernel that is linear in the scores cannot express."""
+        average, which a kernel that is linear in the scores cannot express -- unless the Segmenter was built with
+        `slide_views=True`: then every view of `scales` / `flip` is cut into windows (a mirrored view from the mirrored
+        resized image), the windows of all views and images share the forwards (`imageio.plan_slide_views`), and ONE launch
+        of `hip.seg_predict_slide_views` per image merges each view's windows, resizes to [H_i, W_i], un-mirrors and averages
+        the views.  With upsample="logits" (and no smoothing) the launch applies the softmax per view between the merge and
+        the average, mmseg's order, so several views are allowed with it here; with "probs" or the smoothing the scores are
+        probabilities already and the launch is linear.  `slide_views_reference` is the specification.  At most 16 views
+        and 64 windows per view."""
         sl = self._check_slide("segment_raw", slide, scales, flip)
-        checked = self._check_raw("segment_raw", images, scales, flip)
+        checked = self._check_raw("segment_raw", images, scales, flip, sl)
         plan = self._plan_slide(checked, sl, max_batch)
         if checked is None:
             return []
         crf, out = self.crf_iters > 0, []
+        if sl is not None and self.slide_views:
+            imgs, shapes, per_image = self._raw_window_views(checked[1], sl, plan, mean, std, reverse_channels)
+            with torch.no_grad():
+                for i, vs in enumerate(per_image):
+                    r = hip.seg_predict_slide_views(vs, sl[0], sl[1], *shapes[i], self._views_softmax(), conf=return_conf and not crf,
+                                                    probs=return_probs or crf, label_dtype=self.label_dtype)
+                    r = self._crf(r, imgs[i][None].float() if crf else None, return_conf, return_probs)
+                    out.append(SegmentationResult(*(None if t is None else t[0] for t in r)))
+            return out
         if sl is not None:
             imgs, shapes, per_image = self._raw_windows(checked[1], sl, plan, mean, std, reverse_channels)
             with torch.no_grad():
@@ -420,11 +476,11 @@ class Segmenter:
                 out.append(SegmentationResult(*(None if t is None else t[0] for t in r)))
         return out
 
-    def _check_raw(self, what, images, scales, flip):
+    def _check_raw(self, what, images, scales, flip, sl=None):
         """the arguments of `segment_raw` / `evaluate_raw`, checked on the host -> (the (ratio, flip) views, the images as a
-        list, scales, flip), or None for an empty list"""
+        list, scales, flip), or None for an empty list.  sl: what `_check_slide` gave"""
         views = view_list(scales, flip)
-        if len(views) > 1 and self.upsample != "probs":
+        if len(views) > 1 and self.upsample != "probs" and not (self.slide_views and sl is not None):
             raise ValueError("Segmenter.%s: %d views need upsample='probs' (mmseg averages the resized probabilities; "
                              "averaging raw logits is not its rule), this Segmenter has upsample=%r" % (what, len(views), self.upsample))
         imgs = [images] if torch.is_tensor(images) else list(images)
@@ -440,7 +496,7 @@ class Segmenter:
         """the `slide` argument of `segment_raw` / `evaluate_raw`, checked on the host -> None (off) or (crop, stride)"""
         if slide is None or slide is False:
             return None
-        if len(view_list(scales, flip)) > 1:
+        if len(view_list(scales, flip)) > 1 and not self.slide_views:
             raise ValueError("Segmenter.%s: slide takes a single view, got scales=%r, flip=%r (mmseg applies the softmax between "
                              "the window merge and the view average)" % (what, tuple(scales), flip))
         P = int(self.model.cfg.patch_image_size)
@@ -458,6 +514,8 @@ class Segmenter:
         if sl is None or checked is None:
             return None
         shapes = [(int(im.shape[0]), int(im.shape[1])) for im in checked[1]]
+        if self.slide_views:
+            return shapes, plan_slide_views(shapes, self.model.cfg.patch_image_size, sl[0], sl[1], checked[2], checked[3], max_batch)
         return shapes, plan_slide(shapes, self.model.cfg.patch_image_size, sl[0], sl[1], float(checked[2][0]), max_batch)
 
     def _raw_windows(self, imgs, sl, plan, mean, std, reverse_channels):
@@ -481,6 +539,35 @@ class Segmenter:
                 for j, (i, k) in enumerate(ik):
                     got[i][k], grid[i] = scores[j], (hp, wp)
         return imgs, shapes, [(torch.stack(got[i])[None], *grid[i], per_image[i][0]) for i in range(len(imgs))]
+
+    def _views_softmax(self):
+        """the `softmax` of the slide-views launch: raw logits are normalised per view behind the merge (mmseg's order); the
+        per-patch softmax and the neighbour smoothing hand over probabilities, whose merge is linear"""
+        return self.upsample == "logits" and self.smooth_iters == 0
+
+    def _raw_window_views(self, imgs, sl, plan, mean, std, reverse_channels):
+        """`_raw_windows` for `slide_views`: the windows of every view loaded in one launch per (source shape, size, flip), one
+        forward per window size and `max_batch` windows of whatever view and image (`plan`: what `_plan_slide` gave) -> (the
+        images on the device, their (H, W), per image its views (scores [1, Nw, hpw*wpw, n], hpw, wpw, oh, ow, flip) in view
+        order)"""
+        mean, std = HALF if mean is None else mean, HALF if std is None else std
+        dev = next(self.model.parameters()).device
+        shapes, (views, per_image, loads, forwards) = plan
+        imgs = [im.to(dev, non_blocking=True) for im in imgs]
+        x, grid = {}, {}
+        got = [[[None] * (len(ys) * len(xs)) for _, ys, xs, _ in pv] for pv in per_image]
+        with torch.no_grad():
+            for _, size, flipped, idx in loads:
+                t = hip.image_load_windows(torch.stack([imgs[i] for i in idx]), size[0], size[1], sl[0], sl[1], mean, std,
+                                           reverse_channels, flip=flipped)
+                for k, wins in enumerate(t.chunk(len(idx))):
+                    x[idx[k], size, flipped] = wins
+            for size, ivk in forwards:
+                scores, hp, wp = self.patch_scores(torch.stack([x[i, per_image[i][v][0], views[v][1]][k] for i, v, k in ivk]))
+                for j, (i, v, k) in enumerate(ivk):
+                    got[i][v][k], grid[i, v] = scores[j], (hp, wp)
+        return imgs, shapes, [[(torch.stack(got[i][v])[None], *grid[i, v], *per_image[i][v][0], views[v][1])
+                               for v in range(len(views))] for i in range(len(imgs))]
 
     def _raw_views(self, views, imgs, scales, flip, max_batch, mean, std, reverse_channels):
         """the front of `segment_raw` and `evaluate_raw`: every image loaded once per ratio, one forward per network size ->
@@ -536,9 +623,10 @@ class Segmenter:
         raw_labels=True: the label PNGs' values, 0 and 255 ignored and x -> class x - 1 (`areas_reference` states the rule);
         False: class ids, n and 255 ignored.  into: a score to accumulate into (a whole validation set needs no host round
         trip; `summary()` is the only one).  A mismatch of count, shape or dtype is a ValueError before anything is launched.
-        slide: as in `segment_raw`; the last launch per image is then `hip.seg_score_windows`."""
+        slide: as in `segment_raw`; the last launch per image is then `hip.seg_score_windows` (`hip.seg_score_slide_views` on a
+        Segmenter built with `slide_views=True`)."""
         sl = self._check_slide("evaluate_raw", slide, scales, flip)
-        checked = self._check_raw("evaluate_raw", images, scales, flip)
+        checked = self._check_raw("evaluate_raw", images, scales, flip, sl)
         plan = self._plan_slide(checked, sl, max_batch)
         gts = [label_maps] if torch.is_tensor(label_maps) else list(label_maps)
         imgs = [] if checked is None else checked[1]
@@ -554,6 +642,21 @@ class Segmenter:
             return (score, []) if return_labels else score
         gts = [g.to(dev, non_blocking=True).contiguous() for g in gts]
         crf, out = self.crf_iters > 0, []
+        if sl is not None and self.slide_views:
+            imgs, shapes, per_image = self._raw_window_views(checked[1], sl, plan, mean, std, reverse_channels)
+            kw = dict(raw_labels=raw_labels, areas=score.areas, tally=score.tally)
+            with torch.no_grad():
+                for i, vs in enumerate(per_image):
+                    if crf:                                   # the label map comes from the CRF, not from the predict kernel
+                        r = hip.seg_predict_slide_views(vs, sl[0], sl[1], *shapes[i], self._views_softmax(), probs=True,
+                                                        label_dtype=self.label_dtype)
+                        labels = self._crf(r, imgs[i][None].float(), False, False).labels
+                        hip.seg_areas(labels.contiguous(), gts[i][None], self.n, **kw)
+                    else:
+                        labels = hip.seg_score_slide_views(vs, sl[0], sl[1], gts[i][None], self._views_softmax(),
+                                                           labels=return_labels, label_dtype=self.label_dtype, **kw)[2]
+                    out.append(labels[0] if return_labels else None)
+            return (score, out) if return_labels else score
         if sl is not None:
             imgs, shapes, per_image = self._raw_windows(checked[1], sl, plan, mean, std, reverse_channels)
             kw = dict(raw_labels=raw_labels, areas=score.areas, tally=score.tally)

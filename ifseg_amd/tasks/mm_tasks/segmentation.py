@@ -198,7 +198,8 @@ class SegmentationTask(TaskBase):
 
     def build_segmenter(self, model, **kw):
         """images -> label maps at image resolution on this task's categories (ifseg_amd/predict.py); raw uint8 images of
-        any size go through `Segmenter.segment_raw`, the evaluation transform of the data pipeline on the device"""
+        any size go through `Segmenter.segment_raw`, the evaluation transform of the data pipeline on the device; every keyword
+        of the constructor passes through (`slide_views=True`: multi-scale + flip over sliding windows)"""
         from ...predict import Segmenter
         return Segmenter(model, task=self, **kw)
 
@@ -207,7 +208,7 @@ class SegmentationTask(TaskBase):
         the device: `build_segmenter(model, ...).evaluate_raw(images, label_maps, ...)`.  Keywords of the Segmenter's constructor
         go to it, the others to `Segmenter.evaluate_raw`; `slide` (None, True or (crop, stride)) is its sliding-window switch."""
         ctor = ("category_token_ids", "prompt_ids", "upsample", "smooth_iters", "smooth_topk", "temperature", "crf_iters",
-                "full_context_alignment", "label_dtype")
+                "full_context_alignment", "label_dtype", "slide_views")
         seg = self.build_segmenter(model, **{k: kw.pop(k) for k in ctor if k in kw})
         return seg.evaluate_raw(images, label_maps, slide=slide, **kw)
 

@@ -675,6 +675,47 @@ int ifseg_seg_score_windows(const float* scores, int B, int hpw, int wpw, int n,
                             void* stream);
 int ifseg_seg_predict_windows_staging(int max_bytes);
 
+/* ---- multi-scale + flip OVER sliding windows (Segmenter(slide_views=True): mmseg's MultiScaleFlipAug over test_cfg mode='slide') ----
+ * ifseg_image_load_windows_mirrored is ifseg_image_load_windows on the MIRRORED resized image: element (b Nw + k, c, y, x) is
+ * ifseg_image_load's element (b, c, ys[k] + y, ow - 1 - (xs[k] + x)), bit for bit -- the image is mirrored after the resize, as
+ * mmseg does, and still never written.  (The window starts are not symmetric, the last window being pulled back inside: these
+ * are not the unmirrored windows flipped.)  Everything else as ifseg_image_load_windows. */
+int ifseg_image_load_windows_mirrored(const void* images, int B, int H0, int W0, int oh, int ow, int crop_h, int crop_w,
+                                      int stride_h, int stride_w, const float* lut, int reverse_channels, void* out, int out_bytes,
+                                      void* stream);
+/* View k of ifseg_seg_predict_slide_views is an input of ifseg_seg_predict_windows at its own plane: the window rule on
+ * (oh, ow) with the call's crop and stride, every window on an hpw x wpw grid; flip: the network saw the resized image
+ * mirrored along its width. */
+typedef struct {
+  const float* scores; /* device, fp32 [B, Nw, hpw*wpw, n], class fastest, 4-byte aligned */
+  int hpw, wpw, oh, ow, flip;
+} ifseg_slide_view;
+/* ifseg_seg_predict_slide_views merges 1 .. 16 such views of the same images into one label map [B, h, w], in one launch:
+ *   v_k  = ifseg_seg_predict_windows' v of view k (the same operations: with K = 1, flip = 0 and softmax = 0 the three outputs
+ *          are that entry point's, bit for bit), a flipped view taken at the mirrored output column w - 1 - x
+ *   softmax != 0:  v_k <- exp(v_k - max_c v_k) / sum_c exp(v_k - max_c v_k), the sum in class order (mmseg's order: the views'
+ *          logits are merged and resized, THEN normalised, un-mirrored and averaged); softmax == 0: v_k as it is (scores that
+ *          are probabilities already: everything after the per-patch softmax is linear)
+ *   mean = (v_0 + ... + v_{K-1}, added in view order) * (float)(1.0 / K)
+ * labels / conf / probs of the mean as ifseg_seg_predict writes them.  ifseg_seg_score_slide_views is the same launch with
+ * ifseg_seg_score's counting in its epilogue (labels optional).
+ * Refusals: K outside 1..16, a NULL or misaligned view: IFSEG_ERR_BAD_ARG; per view those of ifseg_seg_predict_windows
+ * (window rule, at most IFSEG_SLIDE_MAX_WINDOWS windows, Nw*hpw*wpw < 2^22); the rest as ifseg_seg_predict_views /
+ * ifseg_seg_score_views.  Nothing is launched on a refusal.
+ * A workgroup owns 16 x 64 pixels and walks the classes in chunks of 16.  softmax takes three walks (maximum, sum, mean) and
+ * keeps max and sum of every pixel and view in LDS, 8 KiB per view on top of the 64 KiB the other kernels budget (gfx950 gives
+ * a workgroup 160 KiB; a device that cannot hold them: IFSEG_ERR_BAD_SHAPE).  Views are staged in LDS in view order while the
+ * buffer lasts; a view that does not fit reads global memory (same values).  ifseg_seg_predict_slide_views_staging sets the
+ * size of that buffer like ifseg_seg_predict_staging, for these two only. */
+int ifseg_seg_predict_slide_views(const ifseg_slide_view* views, int K, int B, int n, int crop_h, int crop_w, int stride_h,
+                                  int stride_w, int h, int w, int softmax, void* labels, int label_bytes, float* conf,
+                                  float* probs, void* stream);
+int ifseg_seg_score_slide_views(const ifseg_slide_view* views, int K, int B, int n, int crop_h, int crop_w, int stride_h,
+                                int stride_w, int h, int w, int softmax, void* labels, int label_bytes, float* conf, float* probs,
+                                const void* gt, int gt_bytes, int raw_labels, unsigned long long* areas,
+                                unsigned long long* tally, void* stream);
+int ifseg_seg_predict_slide_views_staging(int max_bytes);
+
 /* ---- raw images and raw label maps in, a training batch out (ifseg_amd/augment.py is the specification, bit for bit; the
  * reference's training transform, segmentation_dataset.py:157-163, 239-251: Resize(ratio_range), RandomCrop(cat_max_ratio 0.75),
  * RandomFlip, PhotoMetricDistortion, Normalize) ----
