@@ -1308,7 +1308,57 @@ def seg_score_slide_views(views, crop, stride, gt, softmax, raw_labels=True, lab
     return areas, tally, lab, cf, pr
 
 
-_image_luts = {}         # (mean, std, device) -> fp32 [3, 256] on the device; at most 16 entries
+# --------------------------------------------------------------------------- the label map as a picture
+SEG_RENDER_MAX_BOUNDARY = 4
+
+
+def render_alpha(opacity):
+    """the opacity in 256ths, floor(opacity * 256 + 0.5): the `alpha` of ifseg_seg_render"""
+    assert 0.0 <= float(opacity) <= 1.0, opacity
+    return int(float(opacity) * 256.0 + 0.5)
+
+
+def _overlap(a, b):
+    sa, sb = a.data_ptr(), b.data_ptr()
+    return a.device == b.device and sa < sb + b.numel() * b.element_size() and sb < sa + a.numel() * a.element_size()
+
+
+def seg_render(labels, image, palette, opacity=0.5, boundary=0, boundary_color=(255, 255, 255), conf=None, out=None):
+    """labels uint8 / int16 [H, W] or [B, H, W], image uint8 [.., H, W, 3] (HWC), palette uint8 [n, 3], 1 <= n <= 512 -> the
+    picture uint8 [.., H, W, 3] in one launch (csrc/render.hip): the palette's colour blended over the image at `opacity`
+    (in 256ths, by `conf` fp32 [.., H, W] per pixel when given), a label outside the palette keeps the image's pixel, and with
+    boundary = r in 1..4 every pixel with another label value within r pixels becomes `boundary_color`.
+    `predict.render_reference` is the specification and states the rule; opacity 0.5 is the reference demo's "overlap" picture,
+    1.0 its "segmentation" picture, bit for bit.  Every tensor contiguous, at any byte (labels: element) offset of its
+    storage; out: written in place when given, it must not overlap image or labels."""
+    assert labels.dtype in (torch.uint8, torch.int16) and labels.dim() in (2, 3) and labels.is_contiguous(), \
+        (labels.dtype, tuple(labels.shape), labels.stride())
+    assert image.dtype == torch.uint8 and image.is_contiguous() and tuple(image.shape) == tuple(labels.shape) + (3,) \
+        and image.device == labels.device, (image.dtype, tuple(image.shape), image.stride(), tuple(labels.shape), image.device)
+    assert palette.dtype == torch.uint8 and palette.dim() == 2 and palette.shape[1] == 3 and palette.is_contiguous() \
+        and 1 <= palette.shape[0] <= SEG_PREDICT_MAX_CLASSES and palette.device == labels.device, \
+        (palette.dtype, tuple(palette.shape), palette.stride(), palette.device)
+    assert isinstance(boundary, int) and 0 <= boundary <= SEG_RENDER_MAX_BOUNDARY, boundary
+    rgb = tuple(int(c) for c in boundary_color)
+    assert len(rgb) == 3 and all(0 <= c <= 255 for c in rgb) and rgb == tuple(boundary_color), boundary_color
+    alpha = render_alpha(opacity)
+    assert 1 <= labels.numel() < 2 ** 31, tuple(labels.shape)
+    if conf is not None:
+        assert conf.dtype == torch.float32 and conf.shape == labels.shape and conf.is_contiguous() and conf.device == labels.device, \
+            (conf.dtype, tuple(conf.shape), conf.stride(), conf.device)
+    if out is None:
+        out = torch.empty_like(image)
+    assert out.dtype == torch.uint8 and out.shape == image.shape and out.is_contiguous() and out.device == image.device, \
+        (out.dtype, tuple(out.shape), out.stride(), out.device)
+    assert not _overlap(out, image) and not _overlap(out, labels), "seg_render: out overlaps the image or the labels"
+    H, W = labels.shape[-2:]
+    _check(lib().ifseg_seg_render(_ptr(labels), c_int(labels.element_size()), _ptr(image), _ptr(palette), c_int(palette.shape[0]),
+                                  _ptr(conf), c_int(labels.numel() // (H * W)), c_int(H), c_int(W), c_int(alpha), c_int(boundary),
+                                  c_int(rgb[0] | rgb[1] << 8 | rgb[2] << 16), _ptr(out), _stream()), "seg_render")
+    return out
+
+
+_image_luts = {}        # (mean, std, device) -> fp32 [3, 256] on the device; at most 16 entries
 
 
 def image_load(images_u8, oh, ow, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), reverse_channels=False, dtype=torch.float32,

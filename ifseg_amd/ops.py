@@ -23,7 +23,7 @@ differing grids, mirrored ones included: multi-scale + flip inference), `seg_are
 against ground truth, stand-alone and in the predict kernel's epilogue: mIoU on the device), `image_load` (csrc/imgload.hip: raw uint8 images to
 normalised patch_images, the reference's evaluation transform) and the three ops of sliding-window inference (`image_load_windows`,
 `seg_predict_windows`, `seg_score_windows`: the window batch written directly, and the windows' scores merged into one label
-map in one launch) and the two of multi-scale + flip over sliding windows (`seg_predict_slide_views`, `seg_score_slide_views`:
+map in one launch), `seg_render` (csrc/render.hip: the label map coloured over its image, with class contours) and the two of multi-scale + flip over sliding windows (`seg_predict_slide_views`, `seg_score_slide_views`:
 K views, each a set of windows, merged in one launch, optionally softmaxed per view as mmseg does) are inference only and
 have no backward; `train_load`
 (csrc/trainload.hip: raw images and label maps of any sizes to a training batch under given records, the reference's training
@@ -844,6 +844,52 @@ def _(scores, hps, wps, flips, gt, raw_labels, want_labels, want_conf, want_prob
     return (s.new_empty((3, n), dtype=torch.int64), s.new_empty((2,), dtype=torch.int64),
             s.new_empty((B, h, w) if want_labels else (0,), dtype=ldt), s.new_empty((B, h, w) if want_conf else (0,), dtype=f32),
             s.new_empty((B, n, h, w) if want_probs else (0,), dtype=f32))
+
+
+# ----------------------------------------------------------------------------------------------- seg_render
+def _seg_render_check(labels, image, palette, opacity, boundary, boundary_color, conf):
+    op = "ifseg::seg_render"
+    if labels.dtype not in (torch.uint8, torch.int16):
+        raise ValueError("%s: labels must be uint8 or int16 (what seg_predict gives), got dtype %s" % (op, labels.dtype))
+    if labels.dim() not in (2, 3) or labels.numel() < 1 or labels.numel() >= 2 ** 31:
+        raise ValueError("%s: labels must be [H, W] or [B, H, W] with 1 <= pixels < 2**31, got %s" % (op, tuple(labels.shape)))
+    if image.dtype != torch.uint8 or tuple(image.shape) != tuple(labels.shape) + (3,):
+        raise ValueError("%s: the image must be uint8 %s (HWC, the labels' shape), got %s %s"
+                         % (op, tuple(labels.shape) + (3,), image.dtype, tuple(image.shape)))
+    if palette.dtype != torch.uint8 or palette.dim() != 2 or palette.shape[1] != 3 or not 1 <= palette.shape[0] <= hip.SEG_PREDICT_MAX_CLASSES:
+        raise ValueError("%s: the palette must be uint8 [n, 3], 1 <= n <= %d, got %s %s"
+                         % (op, hip.SEG_PREDICT_MAX_CLASSES, palette.dtype, tuple(palette.shape)))
+    if not 0.0 <= opacity <= 1.0:
+        raise ValueError("%s: opacity must be in [0, 1], got %r" % (op, opacity))
+    if not 0 <= boundary <= hip.SEG_RENDER_MAX_BOUNDARY:
+        raise ValueError("%s: boundary must be in 0 .. %d, got %d" % (op, hip.SEG_RENDER_MAX_BOUNDARY, boundary))
+    if len(boundary_color) != 3 or any(not 0 <= c <= 255 for c in boundary_color):
+        raise ValueError("%s: boundary_color must be three ints in 0 .. 255, got %s" % (op, list(boundary_color)))
+    if conf is not None and (conf.dtype != torch.float32 or conf.shape != labels.shape):
+        raise ValueError("%s: conf must be float32 of the labels' shape %s, got %s %s"
+                         % (op, tuple(labels.shape), conf.dtype, tuple(conf.shape)))
+
+
+@custom_op("ifseg::seg_render", mutates_args=(), device_types="cuda")
+def seg_render(labels: torch.Tensor, image: torch.Tensor, palette: torch.Tensor, opacity: float, boundary: int,
+               boundary_color: Sequence[int], conf: Optional[torch.Tensor]) -> torch.Tensor:
+    """the label map as a picture (csrc/render.hip): labels uint8 / int16 [.., H, W] coloured by palette uint8 [n, 3] over image
+    uint8 [.., H, W, 3] at `opacity` (scaled per pixel by conf fp32 [.., H, W] when given), contours of half width `boundary`
+    in `boundary_color` -> uint8 [.., H, W, 3], a fresh tensor; `ifseg_amd.predict.render_reference` is the specification.
+    Integer inputs: not differentiable."""
+    _seg_render_check(labels, image, palette, opacity, boundary, boundary_color, conf)
+    prev = _stream_scope(labels)
+    try:
+        return hip.seg_render(labels.contiguous(), image.contiguous(), palette.contiguous(), opacity, boundary,
+                              tuple(int(c) for c in boundary_color), conf=None if conf is None else conf.contiguous())
+    finally:
+        hip.set_stream(prev)
+
+
+@seg_render.register_fake
+def _(labels, image, palette, opacity, boundary, boundary_color, conf):
+    _seg_render_check(labels, image, palette, opacity, boundary, boundary_color, conf)
+    return image.new_empty(tuple(labels.shape) + (3,), dtype=torch.uint8)
 
 
 # ----------------------------------------------------------------------------------------------- image_load

@@ -57,6 +57,14 @@ device; `score.summary()` gives aAcc / mIoU / mAcc by `SegCriterion.reduce_metri
     for more in batches: seg.evaluate_raw(*more, into=score)                                             # a whole validation set
     score.summary()                                    # {"aAcc", "mIoU", "mAcc", "IoU": [n], "Acc": [n], "pixels"}
 
+The label map as a picture: `seg.render_raw(photos, ...)` is `segment_raw` followed by one launch of `hip.seg_render`
+(csrc/render.hip) per image, which blends the classes' colours over the original photo and draws class contours -- the demo's
+`cmap[labels]` and `image * (1 - opacity) + cmap[labels] * opacity`, without the label map leaving the device.  The rule is
+integer and `render_reference` states it; there is no reference golden (the notebook's figure goes through matplotlib and
+PIL): parity is exact to `render_reference`, which equals the demo's formula at the demo's opacity.
+
+    pics = seg.render_raw(photos, opacity=0.5, boundary=1)          # [RenderResult(picture uint8 [H_i, W_i, 3], labels, conf)]
+
 Nothing in the call synchronises with the host; `labels`, `conf` and `probs` stay on the device.  There is no CPU fallback:
 `upsample_argmax_reference` is the specification the tests compare against, not a second implementation of the path.
 """
@@ -186,6 +194,84 @@ def areas_reference(labels, gt, n, raw_labels=True):
     return areas, tally
 
 
+class RenderResult(NamedTuple):
+    picture: torch.Tensor                      # [H, W, 3] uint8: the labels' colours over the image, on the device
+    labels: torch.Tensor                       # [H, W] uint8 / int16: what `segment_raw` gave
+    conf: Optional[torch.Tensor]               # [H, W] fp32 with fade_by_conf, else None
+
+
+def default_palette(n):
+    """-> uint8 [n, 3]: the PASCAL-VOC colour map (bit 7 - j of red, green, blue from bits 3 j, 3 j + 1, 3 j + 2 of the index)
+    with the loop run over all eight rounds of three index bits, so that it is one-to-one beyond 256 classes as well:
+    0 -> (0, 0, 0), 1 -> (128, 0, 0), 255 -> (224, 224, 192), 256 -> (0, 0, 32)."""
+    idx = torch.arange(int(n), dtype=torch.int64)
+    rgb = torch.zeros(int(n), 3, dtype=torch.int64)
+    for j in range(8):
+        for c in range(3):
+            rgb[:, c] |= ((idx >> (3 * j + c)) & 1) << (7 - j)
+    return rgb.to(torch.uint8)
+
+
+def _render_args(what, opacity, boundary, boundary_color):
+    """the scalar arguments of a rendering call, checked on the host -> (alpha in 0..256, r, the contour colour as three ints)"""
+    if not isinstance(opacity, (int, float)) or not 0.0 <= opacity <= 1.0:
+        raise ValueError("%s: opacity must be a number in [0, 1], got %r" % (what, opacity))
+    if not isinstance(boundary, int) or isinstance(boundary, bool) or not 0 <= boundary <= hip.SEG_RENDER_MAX_BOUNDARY:
+        raise ValueError("%s: boundary must be an int in 0 .. %d (the contour's half width in pixels), got %r"
+                         % (what, hip.SEG_RENDER_MAX_BOUNDARY, boundary))
+    color = tuple(boundary_color)
+    if len(color) != 3 or any(not isinstance(c, int) or not 0 <= c <= 255 for c in color):
+        raise ValueError("%s: boundary_color must be three ints in 0 .. 255, got %r" % (what, boundary_color))
+    return int(float(opacity) * 256.0 + 0.5), boundary, color
+
+
+def render_reference(labels, image, palette, opacity=0.5, boundary=0, boundary_color=(255, 255, 255), conf=None):
+    """CPU specification of hip.seg_render, in integers: labels integer [H, W] (or [B, H, W]), image uint8 [.., H, W, 3],
+    palette uint8 [n, 3] -> the picture uint8 [.., H, W, 3].
+
+      alpha = floor(opacity * 256 + 0.5), 0 .. 256 (opacity outside [0, 1]: ValueError); with conf (fp32, labels' shape) the
+              pixel's own  a = (alpha q + 127) // 255,  q = clamp(floor(conf * 255 + 0.5), 0, 255) in fp32, NaN -> 0
+      a pixel with 0 <= label < n:  (image (256 - a) + palette[label] a) >> 8  per channel
+      any other label (255 "ignore", a negative int16):  the image's pixel
+      boundary = r, 0 .. 4:  a pixel for which some pixel INSIDE the image with |dx| <= r and |dy| <= r carries a different
+              raw label value becomes `boundary_color`, unblended, whatever its own label; r = 0: no contours
+
+    opacity 0.5 is the reference demo's `(image * 0.5 + cmap[labels] * 0.5).astype(uint8)` bit for bit ("overlap"), 1.0 its
+    `cmap[labels]` ("segmentation"); at any other opacity the rule is within one grey level of the float64 formula."""
+    alpha, r, color = _render_args("render_reference", opacity, boundary, boundary_color)
+    labels, image, palette = torch.as_tensor(labels), torch.as_tensor(image), torch.as_tensor(palette)
+    if labels.dtype.is_floating_point or labels.dtype == torch.bool or labels.dim() not in (2, 3):
+        raise ValueError("render_reference: labels must be integer [H, W] or [B, H, W], got %s %s" % (labels.dtype, tuple(labels.shape)))
+    if image.dtype != torch.uint8 or tuple(image.shape) != tuple(labels.shape) + (3,):
+        raise ValueError("render_reference: image must be uint8 %s, got %s %s"
+                         % (tuple(labels.shape) + (3,), image.dtype, tuple(image.shape)))
+    if palette.dtype != torch.uint8 or palette.dim() != 2 or palette.shape[1] != 3 or palette.shape[0] < 1:
+        raise ValueError("render_reference: palette must be uint8 [n, 3], n >= 1, got %s %s" % (palette.dtype, tuple(palette.shape)))
+    lab, img, n = labels.cpu().long(), image.cpu().int(), palette.shape[0]
+    a = torch.full(lab.shape, alpha, dtype=torch.int32)
+    if conf is not None:
+        conf = torch.as_tensor(conf)
+        if conf.dtype != torch.float32 or conf.shape != labels.shape:
+            raise ValueError("render_reference: conf must be float32 %s, got %s %s" % (tuple(labels.shape), conf.dtype, tuple(conf.shape)))
+        q = torch.floor(conf.cpu() * 255.0 + 0.5)
+        q = torch.where(torch.isnan(q), torch.zeros_like(q), q).clamp(0.0, 255.0).int()
+        a = (alpha * q + 127) // 255
+    inside = (lab >= 0) & (lab < n)
+    colour = palette.cpu().int()[lab.clamp(0, n - 1)]
+    out = torch.where(inside[..., None], (img * (256 - a[..., None]) + colour * a[..., None]) >> 8, img)
+    H, W = lab.shape[-2:]
+    edge = torch.zeros_like(inside)
+    for dy in range(-r, r + 1):
+        for dx in range(-r, r + 1):
+            if abs(dy) >= H or abs(dx) >= W:
+                continue                                   # no pixel of the image has this neighbour
+            here = (slice(max(-dy, 0), H - max(dy, 0)), slice(max(-dx, 0), W - max(dx, 0)))
+            there = (slice(max(dy, 0), H - max(-dy, 0)), slice(max(dx, 0), W - max(-dx, 0)))
+            edge[(..., *here)] |= lab[(..., *here)] != lab[(..., *there)]
+    out = torch.where(edge[..., None], torch.tensor(color, dtype=torch.int32), out)
+    return out.to(torch.uint8)
+
+
 class SegmentationScore:
     """The counters of `areas_reference` on the device, summed over everything scored into them: `areas` int64 [3, n],
     `tally` int64 [2].  The scoring kernels add to these tensors in place."""
@@ -283,6 +369,7 @@ class Segmenter:
         self.label_dtype = label_dtype
         self.slide_views = bool(slide_views)
         self._src_dev = None
+        self._palette_dev = None
 
     # -- inputs --------------------------------------------------------------------------
     @staticmethod
@@ -588,6 +675,48 @@ class Segmenter:
                 for k, (i, v) in enumerate(iv):
                     per_image[i][v] = (scores[k:k + 1], hp, wp, views[v][1])
         return imgs, shapes, per_image
+
+    # -- the label map as a picture --------------------------------------------------------
+    def render_raw(self, images, palette=None, opacity=0.5, boundary=0, boundary_color=(255, 255, 255), fade_by_conf=False,
+                   **segment_raw_kwargs):
+        """`segment_raw` and the two pictures a person looks at, the reference demo's last three lines
+        (visualize_segmentation_web.ipynb cell 4: `cmap[labels]` and `image * (1 - opacity) + cmap[labels] * opacity`), on the
+        device -> a list of `RenderResult(picture, labels, conf)` in input order, picture uint8 [H_i, W_i, 3].
+
+        images, and the keywords scales, flip, slide, max_batch, mean, std, reverse_channels: as in `segment_raw`, which runs
+        unchanged (the CRF and the smoothing follow the Segmenter's construction); then ONE launch of `hip.seg_render` per
+        image colours its label map over the ORIGINAL uint8 photo (`render_reference` states the rule, in integers).
+        palette: None (`default_palette(n)`) or uint8 [>= n, 3], on the host or the device.  opacity in [0, 1]: 0.5 is the
+        demo's "overlap" picture bit for bit, 1.0 its "segmentation" picture.  boundary = r in 0 .. 4: pixels with another class
+        within r pixels are drawn in `boundary_color` (0: no contours).  fade_by_conf: the opacity of a pixel is scaled by the
+        winning class's value there, so uncertain regions show the photo (`segment_raw(return_conf=True)`; a ValueError with
+        the CRF on).  Host images are uploaded once and the pictures stay on the device; with device images (and a device or
+        default palette after the first call) nothing synchronises with the host.  A bad argument is a ValueError before
+        anything is launched."""
+        extra = sorted(set(segment_raw_kwargs) - {"scales", "flip", "slide", "max_batch", "mean", "std", "reverse_channels"})
+        if extra:
+            raise TypeError("Segmenter.render_raw: unexpected keyword(s) %s" % ", ".join(extra))
+        _render_args("Segmenter.render_raw", opacity, boundary, boundary_color)
+        if fade_by_conf and self.crf_iters > 0:
+            raise ValueError("Segmenter.render_raw: fade_by_conf needs the winning class's value, which the CRF path does not "
+                             "hand over (crf_iters = %d)" % self.crf_iters)
+        if palette is not None and (not torch.is_tensor(palette) or palette.dtype != torch.uint8 or palette.dim() != 2
+                                    or palette.shape[1] != 3 or palette.shape[0] < self.n):
+            raise ValueError("Segmenter.render_raw: palette must be a uint8 [>= %d, 3] tensor, got %s" % (
+                self.n, (palette.dtype, tuple(palette.shape)) if torch.is_tensor(palette) else type(palette)))
+        dev = next(self.model.parameters()).device
+        imgs = [images] if torch.is_tensor(images) else list(images)
+        imgs = [im.to(dev, non_blocking=True) if torch.is_tensor(im) else im for im in imgs]       # the one upload
+        res = self.segment_raw(imgs, return_conf=fade_by_conf, **segment_raw_kwargs)
+        if palette is None:
+            if self._palette_dev is None or self._palette_dev.device != dev:
+                self._palette_dev = default_palette(self.n).to(dev)
+            palette = self._palette_dev
+        palette = palette[:MAX_CLASSES].to(dev).contiguous()        # the labels are below n <= MAX_CLASSES
+        with torch.no_grad():
+            return [RenderResult(hip.seg_render(r.labels, im.contiguous(), palette, opacity, boundary, tuple(boundary_color),
+                                                conf=r.conf if fade_by_conf else None), r.labels, r.conf if fade_by_conf else None)
+                    for im, r in zip(imgs, res)]
 
     # -- scoring against ground truth -----------------------------------------------------
     def _score_into(self, what, into, dev):

@@ -212,6 +212,15 @@ class SegmentationTask(TaskBase):
         seg = self.build_segmenter(model, **{k: kw.pop(k) for k in ctor if k in kw})
         return seg.evaluate_raw(images, label_maps, slide=slide, **kw)
 
+    def render_raw(self, model, images, **kw):
+        """raw uint8 images -> a list of `RenderResult(picture, labels, conf)`, the label maps coloured over the photos on the
+        device: `build_segmenter(model, ...).render_raw(images, ...)`.  Keywords of the Segmenter's constructor go to it, the
+        others to `Segmenter.render_raw`."""
+        ctor = ("category_token_ids", "prompt_ids", "upsample", "smooth_iters", "smooth_topk", "temperature", "crf_iters",
+                "full_context_alignment", "label_dtype", "slide_views")
+        seg = self.build_segmenter(model, **{k: kw.pop(k) for k in ctor if k in kw})
+        return seg.render_raw(images, **kw)
+
     def inference_step(self, generator, models, sample, prefix_tokens=None, constraints=None):
         """fairseq_task.py `inference_step` -> [B, max_len] seg-class indices of the best beam (segmentation.py:266-268)"""
         with torch.no_grad():

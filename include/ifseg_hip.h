@@ -716,6 +716,28 @@ int ifseg_seg_score_slide_views(const ifseg_slide_view* views, int K, int B, int
                                 unsigned long long* tally, void* stream);
 int ifseg_seg_predict_slide_views_staging(int max_bytes);
 
+/* ---- the label map as a picture (Segmenter.render_raw; cell 4 of the reference's visualize_segmentation_web.ipynb:
+ * `cmap[labels]` and `image * (1 - opacity) + cmap[labels] * opacity`) ----
+ * ifseg_seg_render colours labels [B, H, W] (uint8, label_bytes 1, or int16, 2) over image uint8 [B, H, W, 3] (HWC) into
+ * out uint8 [B, H, W, 3], one launch, in integers (ifseg_amd/predict.py render_reference is the specification):
+ *   a    = alpha (0..256, the opacity in 256ths); with conf (fp32 [B, H, W], may be NULL):
+ *          q = clamp(floor(conf * 255 + 0.5), 0, 255) in fp32 (a rounded product, a rounded sum), NaN -> 0,  a = (alpha q + 127) / 255
+ *   out  = (image (256 - a) + palette[l] a) >> 8 per channel for a label 0 <= l < n (palette uint8 [n, 3]);
+ *          the image's pixel for any other label (255 "ignore", a negative int16)
+ *   boundary = r (0..4): a pixel with a pixel INSIDE the image at |dx| <= r and |dy| <= r whose raw label value differs becomes
+ *          boundary_rgb (r | g << 8 | b << 16) unblended, whatever its own label; r = 0: no contours.
+ * alpha = 128 is the demo's (image * 0.5 + cmap * 0.5).astype(uint8) bit for bit, alpha = 256 its cmap[labels].
+ * image, palette and out may sit at ANY byte address and labels at any element address: rows are 3 W bytes, of any residue
+ * modulo 4.  Reads of the image are aligned dwords as in ifseg_image_load (up to 3 bytes in front of and behind it may be
+ * READ, never past a page boundary).  Nothing outside out's B H W 3 bytes is written: a workgroup owns 16 x 64 pixels and
+ * stores aligned dwords where a dword lies inside its bytes of a row and single bytes at the two ends, so no dword has two
+ * writers.  out must not overlap image or labels (the caller's duty: rows are read by other workgroups than write them).
+ * NULL labels / image / palette / out, label_bytes outside {1, 2}, int16 labels at an odd address, conf not 4-byte aligned,
+ * n outside 1..512, boundary outside 0..4, alpha outside 0..256, boundary_rgb outside 0..0xffffff: IFSEG_ERR_BAD_ARG;
+ * B, H, W < 1 or B*H*W >= 2^31: IFSEG_ERR_BAD_SHAPE.  Nothing is launched on a refusal. */
+int ifseg_seg_render(const void* labels, int label_bytes, const void* image, const void* palette, int n, const float* conf,
+                     int B, int H, int W, int alpha, int boundary, int boundary_rgb, void* out, void* stream);
+
 /* ---- raw images and raw label maps in, a training batch out (ifseg_amd/augment.py is the specification, bit for bit; the
  * reference's training transform, segmentation_dataset.py:157-163, 239-251: Resize(ratio_range), RandomCrop(cat_max_ratio 0.75),
  * RandomFlip, PhotoMetricDistortion, Normalize) ----
