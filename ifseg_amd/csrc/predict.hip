@@ -25,6 +25,8 @@
 // in a workgroup-private uint32 table in LDS (LDS atomics), and a stand-alone kernel that does the same for label maps that come
 // from elsewhere.  Only the non-zero bins leave a workgroup, one 64-bit integer atomic each: integer sums, so the counters
 // are bit-reproducible.  The instantiations without the flag have none of this.
+// The confusion matrix (ifseg_seg_confusion) is a second stand-alone kernel on a label map, seg_confusion_kernel: its table does
+// not fit the epilogues' LDS budget.
 #include "tile.h"
 #include "../../include/ifseg_hip.h"
 
@@ -181,15 +183,27 @@ __device__ __forceinline__ void bin_add(uint32_t* tab, int idx, bool on) {
   else if (on && idx != first) atomicAdd(&tab[idx], 1u);
 }
 
-// one pixel (where `live`) into the table: the ground-truth rule of include/ifseg_hip.h, then the three bins.  scored / bad:
-// the thread's own tallies, added by score_flush
-__device__ __forceinline__ void score_pixel(uint32_t* tab, int n, int raw, int pred, int g, bool live, int& scored, int& bad) {
+// the ground-truth rule of include/ifseg_hip.h, its one statement: the class of the value g, whether the pixel (where `live`)
+// is scored, and whether it is not ignored but of a class outside [0, n)
+struct GtClass {
+  int cls;
+  bool sc, oor;
+};
+__device__ __forceinline__ GtClass gt_class(int n, int raw, int g, bool live) {
   const bool ign = raw ? (g == 0 || g == 255) : (g == n || g == 255);
   const int cls = raw ? g - 1 : g;
   const bool inr = (unsigned)cls < (unsigned)n;
-  const bool sc = live && !ign && inr, pin = sc && (unsigned)pred < (unsigned)n;
+  return {cls, live && !ign && inr, live && !ign && !inr};
+}
+
+// one pixel (where `live`) into the table: the ground-truth rule, then the three bins.  scored / bad: the thread's own
+// tallies, added by score_flush
+__device__ __forceinline__ void score_pixel(uint32_t* tab, int n, int raw, int pred, int g, bool live, int& scored, int& bad) {
+  const GtClass t = gt_class(n, raw, g, live);
+  const int cls = t.cls;
+  const bool sc = t.sc, pin = sc && (unsigned)pred < (unsigned)n;
   scored += sc;
-  bad += live && !ign && !inr;
+  bad += t.oor;
   bin_add(tab, 2 * n + cls, sc);
   bin_add(tab, n + pred, pin);
   bin_add(tab, cls, pin && pred == cls);
@@ -1024,22 +1038,18 @@ __device__ __forceinline__ void load16(const unsigned char* p, int s, int (&v)[1
     v[i] = EB == 1 ? (int)((o[i >> 2] >> (8 * (i & 3))) & 255u) : (int)(short)(o[i >> 1] >> (16 * (i & 1)));
 }
 
-template <int LB, int GB>
-__global__ __launch_bounds__(256) void seg_areas_kernel(const unsigned char* __restrict__ lab, const unsigned char* __restrict__ gt,
-                                                        int head, int groups, int tail, int n, int raw,
-                                                        unsigned long long* areas, unsigned long long* tally) {
-  __shared__ uint32_t tab[3 * PT_MAX_CLASSES + 2];
-  score_zero(tab, n);
-  __syncthreads();
+// the walk of a label map and its ground truth, its one statement: f(pred, g, live) for every pixel, called by whole
+// (converged) waves.  Head and tail go to lanes 0..15 and 16..31 of the grid's first wave, one pixel each; the body's groups
+// of 16 to the lanes, grid-stride
+template <int LB, int GB, typename F>
+__device__ __forceinline__ void walk_pixels(const unsigned char* lab, const unsigned char* gt, int head, int groups, int tail, F f) {
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  int scored = 0, bad = 0;
-  // head and tail: lanes 0..15 and 16..31 of the grid's first wave, one pixel each
   if (blockIdx.x == 0 && wave == 0) {
     long long i = -1;
     if (lane < head) i = lane;
     else if (lane >= 16 && lane - 16 < tail) i = (long long)head + (long long)groups * 16 + (lane - 16);
     const bool live = i >= 0;
-    score_pixel(tab, n, raw, live ? elem_at<LB>(lab, i) : 0, live ? elem_at<GB>(gt, i) : 0, live, scored, bad);
+    f(live ? elem_at<LB>(lab, i) : 0, live ? elem_at<GB>(gt, i) : 0, live);
   }
   const unsigned char* lb = lab + (long long)head * LB;           // on a 16-byte boundary
   const unsigned char* gb = gt + (long long)head * GB;
@@ -1054,9 +1064,116 @@ __global__ __launch_bounds__(256) void seg_areas_kernel(const unsigned char* __r
       load16<GB>(gb + g * (16 * GB), s, gv);
     }
 #pragma unroll
-    for (int i = 0; i < 16; ++i) score_pixel(tab, n, raw, pv[i], gv[i], live, scored, bad);
+    for (int i = 0; i < 16; ++i) f(pv[i], gv[i], live);
   }
+}
+
+// the host's side of the walk: the pixels in front of the labels' first 16-byte boundary, whole groups of 16, the rest, and
+// the workgroups of the launch
+struct WalkSplit {
+  int head, groups, tail, blocks;
+};
+WalkSplit walk_split(const void* labels, int label_bytes, long long npix) {
+  WalkSplit w;
+  w.head = (int)std::min<long long>(npix, (long long)((0 - (size_t)labels) & 15) / label_bytes);
+  w.groups = (int)((npix - w.head) / 16);
+  w.tail = (int)(npix - w.head - 16ll * w.groups);
+  w.blocks = std::min(std::max((w.groups + 255) / 256, 1), SA_MAX_BLOCKS);
+  return w;
+}
+
+template <int LB, int GB>
+__global__ __launch_bounds__(256) void seg_areas_kernel(const unsigned char* __restrict__ lab, const unsigned char* __restrict__ gt,
+                                                        int head, int groups, int tail, int n, int raw,
+                                                        unsigned long long* areas, unsigned long long* tally) {
+  __shared__ uint32_t tab[3 * PT_MAX_CLASSES + 2];
+  score_zero(tab, n);
+  __syncthreads();
+  int scored = 0, bad = 0;
+  walk_pixels<LB, GB>(lab, gt, head, groups, tail,
+                      [&](int pred, int g, bool live) { score_pixel(tab, n, raw, pred, g, live, scored, bad); });
   score_flush(tab, n, scored, bad, areas, tally);
+}
+
+// ---- which class is taken for which: the confusion matrix of a label map ----
+// confusion[c][p] counts the scored pixels of ground-truth class c with predicted label p; column n takes every label outside
+// [0, n).  The walk over the two maps is seg_areas_kernel's; the table of a workgroup is one of two, chosen by the host:
+//   direct   n (n + 1) <= SC_DIRECT_MAX (n <= 127): uint32 [n][n + 1] in LDS, the pair's key = c (n + 1) + p its index
+//   hashed   the matrix does not fit 64 KiB: SC_SLOTS keys (SC_EMPTY = free) and SC_SLOTS counts.  A key takes the first slot of
+//            its SC_PROBES-long probe sequence that is free (claimed by an LDS compare-and-swap) or already its own; a key
+//            that finds none adds to the global matrix directly, so the result never depends on the table's size
+// In front of both, pair_add's wave pre-aggregation (bin_add's: label maps are piecewise constant).  A workgroup sees fewer
+// than 2^31 pixels in all (npix < 2^31), so no uint32 count wraps.  After a barrier every non-zero bin / claimed slot leaves
+// as one 64-bit atomic; a workgroup never walks the global matrix.
+constexpr int SC_DIRECT_MAX = 16384;     // table entries of the direct regime: 64 KiB
+constexpr int SC_SLOT_BITS = 12;
+constexpr int SC_SLOTS = 1 << SC_SLOT_BITS;     // slots of the hashed regime (4096): 32 KiB of keys and counts
+constexpr int SC_STEP_PIXELS = 256 * 16;  // the pixels a workgroup takes per step of the walk
+constexpr int SC_PROBES = 16;
+constexpr uint32_t SC_EMPTY = 0xffffffffu;     // no key: keys are below 512 * 513
+
+__host__ __device__ inline bool sc_hashed(int n) { return n * (n + 1) > SC_DIRECT_MAX; }
+__host__ __device__ inline int sc_dwords(int n) { return sc_hashed(n) ? 2 * SC_SLOTS : n * (n + 1); }
+
+// cnt pixels of the pair `key` into the workgroup's table, or past a crowded hashed table into the matrix itself
+__device__ __forceinline__ void pair_count(uint32_t* tab, bool hashed, uint32_t key, uint32_t cnt, unsigned long long* confusion) {
+  if (!hashed) {
+    atomicAdd(&tab[key], cnt);
+    return;
+  }
+  uint32_t s = (key * 2654435761u) >> (32 - SC_SLOT_BITS);        // Fibonacci hashing to a slot
+  for (int probe = 0; probe < SC_PROBES; ++probe, s = (s + 1) & (SC_SLOTS - 1)) {
+    const uint32_t was = atomicCAS(&tab[s], SC_EMPTY, key);
+    if (was == SC_EMPTY || was == key) {
+      atomicAdd(&tab[SC_SLOTS + s], cnt);
+      return;
+    }
+  }
+  atomicAdd(&confusion[key], (unsigned long long)cnt);
+}
+
+// bin_add for a pair: the lanes that share the first active lane's key leave as one add of their count, the others one each;
+// whole (converged) waves call it
+__device__ __forceinline__ void pair_add(uint32_t* tab, bool hashed, int key, bool on, unsigned long long* confusion) {
+  const unsigned long long m = __ballot(on);
+  if (!m) return;
+  const int lead = __ffsll((long long)m) - 1;
+  const int first = __builtin_amdgcn_readlane(key, lead);
+  const unsigned long long same = __ballot(on && key == first);
+  if ((int)(threadIdx.x & 63) == lead) pair_count(tab, hashed, (uint32_t)first, (uint32_t)__popcll(same), confusion);
+  else if (on && key != first) pair_count(tab, hashed, (uint32_t)key, 1u, confusion);
+}
+
+__device__ __forceinline__ void confusion_pixel(uint32_t* tab, bool hashed, int n, int raw, int pred, int g, bool live,
+                                                unsigned long long* confusion) {
+  const GtClass t = gt_class(n, raw, g, live);
+  const int col = (unsigned)pred < (unsigned)n ? pred : n;
+  pair_add(tab, hashed, t.sc ? t.cls * (n + 1) + col : 0, t.sc, confusion);
+}
+
+template <int LB, int GB>
+__global__ __launch_bounds__(256) void seg_confusion_kernel(const unsigned char* __restrict__ lab, const unsigned char* __restrict__ gt,
+                                                            int head, int groups, int tail, int n, int raw,
+                                                            unsigned long long* confusion) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t ctab[];  // sc_dwords(n)
+  const bool hashed = sc_hashed(n);                                // uniform over the grid
+  const int keys = hashed ? SC_SLOTS : 0, dwords = sc_dwords(n);
+  for (int i = threadIdx.x; i < dwords; i += 256) ctab[i] = i < keys ? SC_EMPTY : 0u;
+  __syncthreads();
+  walk_pixels<LB, GB>(lab, gt, head, groups, tail,
+                      [&](int pred, int g, bool live) { confusion_pixel(ctab, hashed, n, raw, pred, g, live, confusion); });
+  __syncthreads();
+  if (hashed) {
+    for (int i = threadIdx.x; i < SC_SLOTS; i += 256) {
+      const uint32_t key = ctab[i];
+      if (key != SC_EMPTY) atomicAdd(&confusion[key], (unsigned long long)ctab[SC_SLOTS + i]);
+    }
+  } else {
+    for (int i = threadIdx.x; i < dwords; i += 256) {
+      const uint32_t v = ctab[i];
+      if (v) atomicAdd(&confusion[i], (unsigned long long)v);
+    }
+  }
 }
 
 // what the scoring entry points refuse on top of their predict counterparts
@@ -1303,16 +1420,13 @@ extern "C" int ifseg_seg_areas(const void* labels, int label_bytes, const void* 
   if (const int rc = score_refusal(gt, gt_bytes, areas, tally)) return rc;
   if (n < 1 || n > PT_MAX_CLASSES) return IFSEG_ERR_BAD_ARG;
   if (npix < 1 || npix >= (1ll << 31)) return IFSEG_ERR_BAD_SHAPE;
-  // the pixels in front of the labels' first 16-byte boundary, whole groups of 16, the rest
-  const int head = (int)std::min<long long>(npix, (long long)((0 - (size_t)labels) & 15) / label_bytes);
-  const int groups = (int)((npix - head) / 16), tail = (int)(npix - head - 16ll * groups);
-  const int blocks = std::min(std::max((groups + 255) / 256, 1), SA_MAX_BLOCKS);
+  const WalkSplit w = walk_split(labels, label_bytes, npix);
   const unsigned char* l = (const unsigned char*)labels;
   const unsigned char* g = (const unsigned char*)gt;
   const int raw = raw_labels != 0;
 #define IFSEG_AREAS(LB, GB)                                                                                                  \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(seg_areas_kernel<LB, GB>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, l, g, head, \
-                     groups, tail, n, raw, areas, tally)
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(seg_areas_kernel<LB, GB>), dim3(w.blocks), dim3(256), 0, (hipStream_t)stream, l, g,  \
+                     w.head, w.groups, w.tail, n, raw, areas, tally)
   if (label_bytes == 1 && gt_bytes == 1) IFSEG_AREAS(1, 1);
   else if (label_bytes == 1) IFSEG_AREAS(1, 2);
   else if (gt_bytes == 1) IFSEG_AREAS(2, 1);
@@ -1320,4 +1434,39 @@ extern "C" int ifseg_seg_areas(const void* labels, int label_bytes, const void* 
 #undef IFSEG_AREAS
   IFSEG_CHECK_LAUNCH();
   return 0;
+}
+
+extern "C" int ifseg_seg_confusion(const void* labels, int label_bytes, const void* gt, int gt_bytes, long long npix, int n,
+                                   int raw_labels, unsigned long long* confusion, void* stream) {
+  (void)hipGetLastError();
+  if (!labels || (label_bytes != 1 && label_bytes != 2) || ((size_t)labels & (size_t)(label_bytes - 1))) return IFSEG_ERR_BAD_ARG;
+  if (!gt || !confusion || (gt_bytes != 1 && gt_bytes != 2)) return IFSEG_ERR_BAD_ARG;
+  if (((size_t)confusion & 7) || ((size_t)gt & (size_t)(gt_bytes - 1))) return IFSEG_ERR_BAD_ARG;
+  if (n < 1 || n > PT_MAX_CLASSES) return IFSEG_ERR_BAD_ARG;
+  if (npix < 1 || npix >= (1ll << 31)) return IFSEG_ERR_BAD_SHAPE;
+  const WalkSplit w = walk_split(labels, label_bytes, npix);
+  const size_t lds = (size_t)sc_dwords(n) * sizeof(uint32_t);
+  const unsigned char* l = (const unsigned char*)labels;
+  const unsigned char* g = (const unsigned char*)gt;
+  const int raw = raw_labels != 0;
+#define IFSEG_CONFUSION(LB, GB)                                                                                            \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(seg_confusion_kernel<LB, GB>), dim3(w.blocks), dim3(256), lds, (hipStream_t)stream, l, \
+                     g, w.head, w.groups, w.tail, n, raw, confusion)
+  if (label_bytes == 1 && gt_bytes == 1) IFSEG_CONFUSION(1, 1);
+  else if (label_bytes == 1) IFSEG_CONFUSION(1, 2);
+  else if (gt_bytes == 1) IFSEG_CONFUSION(2, 1);
+  else IFSEG_CONFUSION(2, 2);
+#undef IFSEG_CONFUSION
+  IFSEG_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ifseg_seg_confusion_limit(int which) {
+  switch (which) {
+    case 0: return SC_DIRECT_MAX;
+    case 1: return SC_SLOTS;
+    case 2: return SC_STEP_PIXELS;
+    case 3: return SA_MAX_BLOCKS;
+    default: return IFSEG_ERR_BAD_ARG;
+  }
 }

@@ -1137,6 +1137,39 @@ def seg_areas(labels, gt, n, raw_labels=True, areas=None, tally=None):
     return areas, tally
 
 
+# the tables of seg_confusion_kernel (csrc/predict.hip), for callers and tests that size an input against them
+SEG_CONFUSION_DIRECT_MAX = 16384    # == SC_DIRECT_MAX: n (n + 1) up to this (n <= 127) counts in a direct LDS table, else hashed
+SEG_CONFUSION_SLOTS = 4096          # == SC_SLOTS: the (class, label) pairs a workgroup's hashed table holds at most
+SEG_CONFUSION_STEP_PIXELS = 4096    # the pixels a workgroup takes per step: 256 lanes of 16
+SEG_CONFUSION_MAX_BLOCKS = 512      # == SA_MAX_BLOCKS: the workgroups of a launch at most (grid-stride beyond)
+
+
+def seg_confusion_limits():
+    """-> (direct table entries, hashed slots, pixels per workgroup step, workgroups at most) as the loaded library states them
+    (`ifseg_seg_confusion_limit`): the four constants above, which the tests hold against it"""
+    return tuple(int(lib().ifseg_seg_confusion_limit(c_int(k))) for k in range(4))
+
+
+def seg_confusion(labels, gt, n, raw_labels=True, confusion=None):
+    """labels uint8 / int16 [...] (predicted classes), gt uint8 / int16 of the same shape -> confusion int64 [n, n + 1]: over the
+    scored pixels of `seg_areas`, [c, p] = #(gt = c and pred = p), column n taking every predicted label outside [0, n)
+    (csrc/predict.hip; `predict.confusion_reference` is the specification).  `confusion` given: ACCUMULATED into, else fresh
+    zeros.  Its sum is seg_areas' tally[0], the diagonal / column sums of [:, :n] areas[0] / areas[1], its row sums areas[2]."""
+    assert labels.dtype in (torch.uint8, torch.int16) and labels.is_contiguous(), (labels.dtype, labels.stride())
+    assert gt.dtype in (torch.uint8, torch.int16) and gt.is_contiguous(), (gt.dtype, gt.stride())
+    assert labels.shape == gt.shape and labels.device == gt.device, (tuple(labels.shape), tuple(gt.shape), labels.device, gt.device)
+    assert 1 <= n <= SEG_PREDICT_MAX_CLASSES, n
+    assert 1 <= labels.numel() < 2 ** 31, tuple(labels.shape)
+    if confusion is None:
+        confusion = torch.zeros(n, n + 1, dtype=torch.int64, device=labels.device)
+    assert confusion.dtype == torch.int64 and tuple(confusion.shape) == (n, n + 1) and confusion.is_contiguous() \
+        and confusion.device == labels.device, (confusion.dtype, tuple(confusion.shape), confusion.device, n)
+    _check(lib().ifseg_seg_confusion(_ptr(labels), c_int(labels.element_size()), _ptr(gt), c_int(gt.element_size()),
+                                     c_ll(labels.numel()), c_int(n), c_int(1 if raw_labels else 0), _ptr(confusion), _stream()),
+           "seg_confusion")
+    return confusion
+
+
 def seg_score(scores, hp, wp, gt, raw_labels=True, labels=False, conf=False, probs=False, areas=None, tally=None,
               staging_bytes=None, label_dtype=None):
     """`seg_predict` at gt's own [B, h, w] with the scoring in the kernel's epilogue: -> (areas, tally, labels | None,

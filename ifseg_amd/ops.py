@@ -20,7 +20,8 @@ kernels, with key counts and attention dropout) and `seg_loss` (csrc/loss.hip), 
 `ifseg_amd.modules.MultiheadAttention` composes `linear` and `attention_bias` under the reference module's parameter names.
 `seg_predict` (csrc/predict.hip: label maps at image resolution), `seg_predict_views` (the same from the mean of K views of
 differing grids, mirrored ones included: multi-scale + flip inference), `seg_areas` / `seg_score_views` (label maps counted
-against ground truth, stand-alone and in the predict kernel's epilogue: mIoU on the device), `image_load` (csrc/imgload.hip: raw uint8 images to
+against ground truth, stand-alone and in the predict kernel's epilogue: mIoU on the device), `seg_confusion` (the class
+confusion matrix of a label map against ground truth, [n, n + 1] with an "outside" column), `image_load` (csrc/imgload.hip: raw uint8 images to
 normalised patch_images, the reference's evaluation transform) and the three ops of sliding-window inference (`image_load_windows`,
 `seg_predict_windows`, `seg_score_windows`: the window batch written directly, and the windows' scores merged into one label
 map in one launch), `seg_render` (csrc/render.hip: the label map coloured over its image, with class contours) and the two of multi-scale + flip over sliding windows (`seg_predict_slide_views`, `seg_score_slide_views`:
@@ -772,8 +773,7 @@ def _gt_check(op, gt):
         raise ValueError("%s: ground truth must be uint8 or int16 (label PNG values or class ids), got dtype %s" % (op, gt.dtype))
 
 
-def _seg_areas_check(labels, gt, n):
-    op = "ifseg::seg_areas"
+def _seg_areas_check(labels, gt, n, op="ifseg::seg_areas"):
     if labels.dtype not in (torch.uint8, torch.int16):
         raise ValueError("%s: labels must be uint8 or int16 (what seg_predict gives), got dtype %s" % (op, labels.dtype))
     _gt_check(op, gt)
@@ -803,6 +803,27 @@ def seg_areas(labels: torch.Tensor, gt: torch.Tensor, n: int, raw_labels: bool) 
 def _(labels, gt, n, raw_labels):
     _seg_areas_check(labels, gt, n)
     return labels.new_empty((3, n), dtype=torch.int64), labels.new_empty((2,), dtype=torch.int64)
+
+
+# ----------------------------------------------------------------------------------------------- seg_confusion
+@custom_op("ifseg::seg_confusion", mutates_args=(), device_types="cuda")
+def seg_confusion(labels: torch.Tensor, gt: torch.Tensor, n: int, raw_labels: bool) -> torch.Tensor:
+    """predicted labels (uint8 / int16) against ground truth (uint8 / int16) of the same shape (csrc/predict.hip) -> the
+    confusion matrix int64 [n, n + 1] over `seg_areas`' scored pixels: [c, p] = #(gt = c and pred = p), column n = predicted
+    labels outside [0, n); a fresh tensor.  `ifseg_amd.predict.confusion_reference` is the specification.  Integer inputs:
+    not differentiable."""
+    _seg_areas_check(labels, gt, n, "ifseg::seg_confusion")
+    prev = _stream_scope(labels)
+    try:
+        return hip.seg_confusion(labels.contiguous(), gt.contiguous(), n, raw_labels)
+    finally:
+        hip.set_stream(prev)
+
+
+@seg_confusion.register_fake
+def _(labels, gt, n, raw_labels):
+    _seg_areas_check(labels, gt, n, "ifseg::seg_confusion")
+    return labels.new_empty((n, n + 1), dtype=torch.int64)
 
 
 # ----------------------------------------------------------------------------------------------- seg_score_views

@@ -57,6 +57,16 @@ device; `score.summary()` gives aAcc / mIoU / mAcc by `SegCriterion.reduce_metri
     for more in batches: seg.evaluate_raw(*more, into=score)                                             # a whole validation set
     score.summary()                                    # {"aAcc", "mIoU", "mAcc", "IoU": [n], "Acc": [n], "pixels"}
 
+Which class is taken for which: `seg.evaluate_raw(..., confusion=True)` also fills `score.confusion`, int64 [n, n + 1] (row = the
+ground truth's class, column = the predicted label, the last column for labels outside [0, n)): the scoring launch then
+writes its label map and one launch of `hip.seg_confusion` per image counts the pairs, in every setting above.
+`confusion_reference` is the specification; the matrix's sum, diagonal, column and row sums are `tally[0]` and `areas`.
+
+    score = seg.evaluate_raw(photos, label_pngs, confusion=True)
+    score.confusions(10)                               # [(gt class, predicted class, pixels, share of the gt class), ...]
+    score.merged(class_to_super_category).summary()    # the same evaluation under a coarser label set, no second pass
+    score.group_summary({"seen": seen_ids, "unseen": unseen_ids})   # per-group mIoU / mAcc and hIoU (needs `areas` only)
+
 The label map as a picture: `seg.render_raw(photos, ...)` is `segment_raw` followed by one launch of `hip.seg_render`
 (csrc/render.hip) per image, which blends the classes' colours over the original photo and draws class contours -- the demo's
 `cmap[labels]` and `image * (1 - opacity) + cmap[labels] * opacity`, without the label map leaving the device.  The rule is
@@ -175,23 +185,40 @@ def areas_reference(labels, gt, n, raw_labels=True):
     scored pixels; over those only (seg_criterion.py:306-314 drops masked pixels from the prediction histogram too, :349-362)
     areas[0][c] = #(pred = c and gt = c), areas[1][c] = #(pred = c), areas[2][c] = #(gt = c).  A predicted label outside
     [0, n) on a scored pixel is in no bin of areas[0] and areas[1].  Runs on any device."""
+    pred, cls, tally = _scored_pixels("areas_reference", labels, gt, n, raw_labels)
+    known = (pred >= 0) & (pred < n)
+    areas = torch.stack([torch.bincount(pred[known & (pred == cls)], minlength=n), torch.bincount(pred[known], minlength=n),
+                         torch.bincount(cls, minlength=n)])
+    return areas, tally
+
+
+def _scored_pixels(what, labels, gt, n, raw_labels):
+    """the ground-truth rule of `areas_reference`, its one statement -> (the predicted labels and the classes of the scored
+    pixels, int64 [tally[0]] each, and tally)"""
     labels, gt = torch.as_tensor(labels), torch.as_tensor(gt)
     if gt.dtype not in (torch.uint8, torch.int16):
-        raise ValueError("areas_reference: ground truth must be uint8 or int16, got %s" % gt.dtype)
+        raise ValueError("%s: ground truth must be uint8 or int16, got %s" % (what, gt.dtype))
     if labels.dtype.is_floating_point or labels.dtype == torch.bool or labels.shape != gt.shape:
-        raise ValueError("areas_reference: labels must be integer and of the ground truth's shape %s, got %s %s"
-                         % (tuple(gt.shape), labels.dtype, tuple(labels.shape)))
+        raise ValueError("%s: labels must be integer and of the ground truth's shape %s, got %s %s"
+                         % (what, tuple(gt.shape), labels.dtype, tuple(labels.shape)))
     pred, g = labels.reshape(-1).long(), gt.reshape(-1).long().to(labels.device)
     ignored = (g == 0) | (g == 255) if raw_labels else (g == n) | (g == 255)
     cls = g - 1 if raw_labels else g
     in_range = (cls >= 0) & (cls < n)
     scored = ~ignored & in_range
     tally = torch.stack([scored.sum(), (~ignored & ~in_range).sum()])
-    pred, cls = pred[scored], cls[scored]
-    known = (pred >= 0) & (pred < n)
-    areas = torch.stack([torch.bincount(pred[known & (pred == cls)], minlength=n), torch.bincount(pred[known], minlength=n),
-                         torch.bincount(cls, minlength=n)])
-    return areas, tally
+    return pred[scored], cls[scored], tally
+
+
+def confusion_reference(labels, gt, n, raw_labels=True):
+    """Specification of the confusion matrix (hip.seg_confusion): labels and gt as in `areas_reference`, whose ground-truth rule
+    and set of scored pixels these are -> int64 [n, n + 1].  A scored pixel of ground-truth class c with predicted label p adds
+    1 to C[c, p] where 0 <= p < n, else to C[c, n], the "outside" column (255 in a uint8 map of another source, a negative
+    int16).  With (areas, tally) of the same inputs: C.sum() == tally[0], C[:, :n].diagonal() == areas[0],
+    C[:, :n].sum(0) == areas[1], C.sum(1) == areas[2].  Runs on any device."""
+    pred, cls, _ = _scored_pixels("confusion_reference", labels, gt, n, raw_labels)
+    col = torch.where((pred >= 0) & (pred < n), pred, torch.full_like(pred, n))
+    return torch.bincount(cls * (n + 1) + col, minlength=n * (n + 1)).reshape(n, n + 1)
 
 
 class RenderResult(NamedTuple):
@@ -274,9 +301,13 @@ def render_reference(labels, image, palette, opacity=0.5, boundary=0, boundary_c
 
 class SegmentationScore:
     """The counters of `areas_reference` on the device, summed over everything scored into them: `areas` int64 [3, n],
-    `tally` int64 [2].  The scoring kernels add to these tensors in place."""
+    `tally` int64 [2].  The scoring kernels add to these tensors in place.
 
-    def __init__(self, n, device=None, areas=None, tally=None):
+    confusion: None (the default: no matrix, memory and behaviour as without the argument), True (a zeroed one) or a tensor:
+    `confusion_reference`'s matrix int64 [n, n + 1] on the same device, which class is taken for which; `evaluate_raw(...,
+    confusion=True)` fills it (`hip.seg_confusion`).  `confusions`, `confusion_summary` and `merged` read it."""
+
+    def __init__(self, n, device=None, areas=None, tally=None, confusion=None):
         self.n = int(n)
         self.areas = torch.zeros(3, self.n, dtype=torch.int64, device=device) if areas is None else areas
         self.tally = torch.zeros(2, dtype=torch.int64, device=device) if tally is None else tally
@@ -284,19 +315,113 @@ class SegmentationScore:
                 or tuple(self.tally.shape) != (2,) or self.areas.device != self.tally.device:
             raise ValueError("SegmentationScore: areas must be int64 [3, %d] and tally int64 [2] on one device, got %s %s and %s %s"
                              % (self.n, self.areas.dtype, tuple(self.areas.shape), self.tally.dtype, tuple(self.tally.shape)))
+        if confusion is None or confusion is False:
+            self.confusion = None
+        elif confusion is True:
+            self.confusion = torch.zeros(self.n, self.n + 1, dtype=torch.int64, device=self.areas.device)
+        else:
+            self.confusion = confusion
+            if not torch.is_tensor(confusion) or confusion.dtype != torch.int64 or tuple(confusion.shape) != (self.n, self.n + 1) \
+                    or confusion.device != self.areas.device:
+                raise ValueError("SegmentationScore: confusion must be None, True or int64 [%d, %d] on the device of areas, got %s"
+                                 % (self.n, self.n + 1, (confusion.dtype, tuple(confusion.shape), confusion.device)
+                                    if torch.is_tensor(confusion) else type(confusion)))
 
     def add_(self, other):
         if other.n != self.n:
             raise ValueError("SegmentationScore.add_: %d classes against %d" % (other.n, self.n))
+        if (self.confusion is None) != (other.confusion is None):
+            raise ValueError("SegmentationScore.add_: one score has a confusion matrix and the other has none")
         self.areas += other.areas.to(self.areas.device)
         self.tally += other.tally.to(self.tally.device)
+        if self.confusion is not None:
+            self.confusion += other.confusion.to(self.confusion.device)
         return self
+
+    def _matrix(self, what):
+        if self.confusion is None:
+            raise ValueError("SegmentationScore.%s needs a confusion matrix: SegmentationScore(n, confusion=True), "
+                             "evaluate_raw(..., confusion=True)" % what)
+        return self.confusion
+
+    def confusions(self, k=10):
+        """the k largest off-diagonal entries of the matrix, largest first (ties: lower gt class, then lower predicted class)
+        -> [(gt class, predicted class, pixels, share of the gt class's scored pixels)], entries of no pixels left out.
+        Predicted class n is the outside column.  One host round trip."""
+        C = self._matrix("confusions").cpu()
+        n, rows = self.n, C.sum(1)
+        off = C.clone()
+        off[:, :n].fill_diagonal_(0)
+        flat = off.reshape(-1)
+        order = torch.argsort(flat, descending=True, stable=True)[:max(int(k), 0)].tolist()
+        return [(i // (n + 1), i % (n + 1), int(flat[i]), int(flat[i]) / int(rows[i // (n + 1)])) for i in order if int(flat[i]) > 0]
+
+    def confusion_summary(self):
+        """-> the row-normalised matrix, float64 [n, n + 1] on the matrix's device: entry [c, p] is the share of class c's scored
+        pixels labelled p (its diagonal is `summary()["Acc"]`, unrounded).  The row of a class without pixels is NaN, as
+        `summary()` reports an absent class."""
+        C = self._matrix("confusion_summary").double()
+        return C / C.sum(1, keepdim=True)
+
+    def merged(self, mapping, m=None):
+        """The score under a coarser label set (171 classes to 27 super-categories, seen / unseen groups) -> a new
+        `SegmentationScore(m, confusion=True)`.  mapping: a list / tensor of n new class ids in [0, m), or -1 to drop the class
+        from the ground truth; m: None is max(mapping) + 1.  The new matrix is the old one with rows and columns summed per
+        new id; the rows of dropped classes are removed, and predictions of a dropped class go to the outside column.  areas
+        and tally[0] are rebuilt from it (the identities of `confusion_reference`), tally[1] is carried over.  By
+        specification this is scoring the mapped label maps: `confusion_reference(mapping[labels], mapping[gt], m,
+        raw_labels=False)` with -1 -> m in the ground truth.  Needs a confusion matrix (ValueError without one)."""
+        C = self._matrix("merged")
+        mp = torch.as_tensor(mapping).reshape(-1)
+        if mp.dtype.is_floating_point or mp.dtype == torch.bool or mp.numel() != self.n:
+            raise ValueError("SegmentationScore.merged: mapping must hold %d integer class ids, got %s %s" % (self.n, mp.dtype, tuple(mp.shape)))
+        mp = mp.long().cpu()
+        m = int(mp.max()) + 1 if m is None else int(m)
+        if m < 1 or int(mp.min()) < -1 or int(mp.max()) >= m:
+            raise ValueError("SegmentationScore.merged: new class ids must lie in [0, %d), or be -1, got %d .. %d" % (m, int(mp.min()), int(mp.max())))
+        to = torch.where(mp < 0, torch.full_like(mp, m), mp).to(C.device)          # dropped: row m (removed), column m (outside)
+        rows = torch.zeros(m + 1, self.n + 1, dtype=torch.int64, device=C.device).index_add_(0, to, C)
+        cols = torch.cat([to, torch.full_like(to[:1], m)])                        # the outside column stays outside
+        M = torch.zeros(m + 1, m + 1, dtype=torch.int64, device=C.device).index_add_(1, cols, rows)[:m].contiguous()
+        areas = torch.stack([M[:, :m].diagonal(), M[:, :m].sum(0), M.sum(1)])
+        return SegmentationScore(m, areas=areas, tally=torch.stack([M.sum(), self.tally[1].to(C.device)]), confusion=M)
+
+    def group_summary(self, groups):
+        """groups: {name: class ids} (seen / unseen, things / stuff) -> {name: {"mIoU", "mAcc"}, ..., "hIoU"}: per group the nanmean
+        of `summary()`'s per-class IoU / Acc over the group's classes, unrounded, then rounded to 4 digits as `summary()` does;
+        hIoU is the harmonic mean of the groups' mIoU, the seen / unseen figure of zero-shot segmentation tables (0 where a
+        group's mIoU is 0, NaN where a group has no class with pixels).  Needs `areas` only; one host round trip; ground
+        truth out of range is `summary()`'s IndexError."""
+        names = list(groups)
+        ids = []
+        for name in names:
+            c = torch.as_tensor(list(groups[name]), dtype=torch.long).reshape(-1)
+            if name == "hIoU" or c.numel() == 0 or int(c.min()) < 0 or int(c.max()) >= self.n:
+                raise ValueError("SegmentationScore.group_summary: group %r must hold class ids in [0, %d) (and not be named "
+                                 "'hIoU'), got %s" % (name, self.n, c.tolist()))
+            ids.append(c)
+        flat = torch.cat([self.areas.reshape(-1), self.tally]).cpu()
+        self._refuse_out_of_range(int(flat[-1]))
+        a = flat[:3 * self.n].reshape(3, self.n).double()
+        iou, acc = a[0] / (a[1] + a[2] - a[0]), a[0] / a[2]
+        r4 = lambda v: round(float(v), 4)
+        mious = [torch.nanmean(iou[c]) for c in ids]
+        out = {name: {"mIoU": r4(mi), "mAcc": r4(torch.nanmean(acc[c]))} for name, c, mi in zip(names, ids, mious)}
+        mi = torch.stack(mious)
+        out["hIoU"] = r4(0.0 if bool((mi == 0).any()) else len(names) / (1.0 / mi).sum())
+        return out
 
     def logging_output(self):
         """the four histograms under the reference's keys, as `SegCriterion.reduce_metrics` takes them (float64, not the
         reference's float32: the counts of a validation set pass 2^24)"""
         a = self.areas.double()
         return {"area_intersect": a[0], "area_pred_label": a[1], "area_label": a[2], "area_union": a[1] + a[2] - a[0]}
+
+    def _refuse_out_of_range(self, bad):
+        """bad: tally[1] as the host read it"""
+        if bad != 0:
+            raise IndexError("SegmentationScore: tally[1] = %d ground-truth pixels hold a class outside [0, %d) that is not an "
+                             "ignore value (wrong raw_labels, or a label map of another dataset?)" % (int(bad), self.n))
 
     def summary(self):
         """-> {"aAcc", "mIoU", "mAcc", "IoU": [n], "Acc": [n], "pixels"} by `SegCriterion.reduce_metrics`' formulas and rounding
@@ -308,9 +433,7 @@ class SegmentationScore:
         iou, acc = ai / au, ai / al
         flat = torch.cat([torch.stack([ai.sum() / ap.sum(), torch.nanmean(iou), torch.nanmean(acc)]), iou, acc,
                           self.tally.double()]).tolist()
-        if flat[-1] != 0:
-            raise IndexError("SegmentationScore: tally[1] = %d ground-truth pixels hold a class outside [0, %d) that is not an "
-                             "ignore value (wrong raw_labels, or a label map of another dataset?)" % (int(flat[-1]), n))
+        self._refuse_out_of_range(flat[-1])
         r4 = lambda v: round(float(v), 4)
         return {"aAcc": r4(flat[0]), "mIoU": r4(flat[1]), "mAcc": r4(flat[2]), "IoU": [r4(v) for v in flat[3:3 + n]],
                 "Acc": [r4(v) for v in flat[3 + n:3 + 2 * n]], "pixels": int(flat[-2])}
@@ -719,28 +842,51 @@ class Segmenter:
                     for im, r in zip(imgs, res)]
 
     # -- scoring against ground truth -----------------------------------------------------
-    def _score_into(self, what, into, dev):
+    def _score_into(self, what, into, dev, confusion=False):
+        if not isinstance(confusion, bool):
+            raise ValueError("Segmenter.%s: confusion must be True or False (a matrix to add to goes in with `into`), got %s"
+                             % (what, type(confusion)))
         if into is None:
-            return SegmentationScore(self.n, dev)
+            return SegmentationScore(self.n, dev, confusion=confusion)
         if not isinstance(into, SegmentationScore) or into.n != self.n or into.areas.device != dev:
             raise ValueError("Segmenter.%s: into must be a SegmentationScore of %d classes on %s" % (what, self.n, dev))
+        if confusion and into.confusion is None:
+            raise ValueError("Segmenter.%s: confusion=True, but `into` carries no confusion matrix (SegmentationScore(n, device, "
+                             "confusion=True))" % what)
         return into
+
+    def _count(self, score, gt, raw_labels, return_labels, launch=None, labels=None):
+        """The scoring step of every branch of `evaluate_raw` / `evaluate`, for gt [B, h, w] -> the labels [B, h, w] or None.
+        launch(want_labels, counters): the scoring launch, whose epilogue adds to `counters` (raw_labels, areas, tally as
+        keywords) -> its label map or None.  labels instead: a label map from elsewhere (the CRF's argmax), counted by
+        `hip.seg_areas`.  Where the score carries a confusion matrix, the launch is asked for its label map and
+        `hip.seg_confusion` counts the pairs of the same labels behind it on the same stream."""
+        kw = dict(raw_labels=raw_labels, areas=score.areas, tally=score.tally)
+        pairs = score.confusion is not None
+        if labels is None:
+            labels = launch(return_labels or pairs, kw)
+        else:
+            labels = labels.contiguous()
+            hip.seg_areas(labels, gt, self.n, **kw)
+        if pairs:
+            hip.seg_confusion(labels, gt, self.n, raw_labels, confusion=score.confusion)
+        return labels if return_labels else None
 
     def _score(self, score, vs, gt, raw_labels, rgb, return_labels):
         """one image's (or batch's) views against gt [B, h, w] into `score` -> its labels [B, h, w] or None"""
-        kw = dict(raw_labels=raw_labels, areas=score.areas, tally=score.tally)
         h, w = int(gt.shape[1]), int(gt.shape[2])
+        one = len(vs) == 1 and not vs[0][3]
         if self.crf_iters > 0:                                # the label map comes from the CRF, not from the predict kernel
-            one = len(vs) == 1 and not vs[0][3]
             labels = (self._finish(*vs[0][:3], h, w, rgb, False, False) if one else self._finish_views(vs, h, w, rgb, False, False)).labels
-            hip.seg_areas(labels.contiguous(), gt, self.n, **kw)
-            return labels if return_labels else None
-        if len(vs) == 1 and not vs[0][3]:
-            return hip.seg_score(*vs[0][:3], gt, labels=return_labels, label_dtype=self.label_dtype, **kw)[2]
-        return hip.seg_score_views(vs, gt, labels=return_labels, label_dtype=self.label_dtype, **kw)[2]
+            return self._count(score, gt, raw_labels, return_labels, labels=labels)
+        if one:
+            return self._count(score, gt, raw_labels, return_labels,
+                               lambda want, kw: hip.seg_score(*vs[0][:3], gt, labels=want, label_dtype=self.label_dtype, **kw)[2])
+        return self._count(score, gt, raw_labels, return_labels,
+                           lambda want, kw: hip.seg_score_views(vs, gt, labels=want, label_dtype=self.label_dtype, **kw)[2])
 
     def evaluate_raw(self, images, label_maps, raw_labels=True, scales=(1.0,), flip=False, max_batch=8, mean=None, std=None,
-                     reverse_channels=False, into=None, return_labels=False, slide=None):
+                     reverse_channels=False, into=None, return_labels=False, slide=None, confusion=False):
         """`segment_raw` scored against ground truth on the device -> a `SegmentationScore` (or (score, [labels [H_i, W_i], ...])
         with `return_labels`, the labels being `segment_raw`'s).
 
@@ -753,7 +899,13 @@ class Segmenter:
         False: class ids, n and 255 ignored.  into: a score to accumulate into (a whole validation set needs no host round
         trip; `summary()` is the only one).  A mismatch of count, shape or dtype is a ValueError before anything is launched.
         slide: as in `segment_raw`; the last launch per image is then `hip.seg_score_windows` (`hip.seg_score_slide_views` on a
-        Segmenter built with `slide_views=True`)."""
+        Segmenter built with `slide_views=True`).
+        confusion: True, or an `into` that carries a matrix: the score also counts which class is taken for which
+        (`SegmentationScore.confusion`, int64 [n, n + 1]; `confusion_reference` is the specification).  In every setting the
+        scoring launch then writes its label map and one launch of `hip.seg_confusion` per image counts the pairs of the same
+        labels on the same stream; areas / tally still come from the epilogue and are bit for bit what they are without it,
+        and no host synchronisation is added.  confusion=True with an `into` that has no matrix is a ValueError before
+        anything is launched."""
         sl = self._check_slide("evaluate_raw", slide, scales, flip)
         checked = self._check_raw("evaluate_raw", images, scales, flip, sl)
         plan = self._plan_slide(checked, sl, max_batch)
@@ -766,39 +918,37 @@ class Segmenter:
                 raise ValueError("Segmenter.evaluate_raw: label map %d must be a uint8 or int16 tensor of its image's shape %s, got %s"
                                  % (i, tuple(im.shape[:2]), (g.dtype, tuple(g.shape)) if torch.is_tensor(g) else type(g)))
         dev = next(self.model.parameters()).device
-        score = self._score_into("evaluate_raw", into, dev)
+        score = self._score_into("evaluate_raw", into, dev, confusion)
         if checked is None:
             return (score, []) if return_labels else score
         gts = [g.to(dev, non_blocking=True).contiguous() for g in gts]
         crf, out = self.crf_iters > 0, []
         if sl is not None and self.slide_views:
             imgs, shapes, per_image = self._raw_window_views(checked[1], sl, plan, mean, std, reverse_channels)
-            kw = dict(raw_labels=raw_labels, areas=score.areas, tally=score.tally)
             with torch.no_grad():
                 for i, vs in enumerate(per_image):
                     if crf:                                   # the label map comes from the CRF, not from the predict kernel
                         r = hip.seg_predict_slide_views(vs, sl[0], sl[1], *shapes[i], self._views_softmax(), probs=True,
                                                         label_dtype=self.label_dtype)
-                        labels = self._crf(r, imgs[i][None].float(), False, False).labels
-                        hip.seg_areas(labels.contiguous(), gts[i][None], self.n, **kw)
+                        labels = self._count(score, gts[i][None], raw_labels, return_labels,
+                                             labels=self._crf(r, imgs[i][None].float(), False, False).labels)
                     else:
-                        labels = hip.seg_score_slide_views(vs, sl[0], sl[1], gts[i][None], self._views_softmax(),
-                                                           labels=return_labels, label_dtype=self.label_dtype, **kw)[2]
+                        labels = self._count(score, gts[i][None], raw_labels, return_labels, lambda want, kw: hip.seg_score_slide_views(
+                            vs, sl[0], sl[1], gts[i][None], self._views_softmax(), labels=want, label_dtype=self.label_dtype, **kw)[2])
                     out.append(labels[0] if return_labels else None)
             return (score, out) if return_labels else score
         if sl is not None:
             imgs, shapes, per_image = self._raw_windows(checked[1], sl, plan, mean, std, reverse_channels)
-            kw = dict(raw_labels=raw_labels, areas=score.areas, tally=score.tally)
             with torch.no_grad():
                 for i, (scores, hpw, wpw, (oh, ow)) in enumerate(per_image):
                     if crf:                                   # the label map comes from the CRF, not from the predict kernel
                         r = hip.seg_predict_windows(scores, hpw, wpw, oh, ow, sl[0], sl[1], *shapes[i], probs=True,
                                                     label_dtype=self.label_dtype)
-                        labels = self._crf(r, imgs[i][None].float(), False, False).labels
-                        hip.seg_areas(labels.contiguous(), gts[i][None], self.n, **kw)
+                        labels = self._count(score, gts[i][None], raw_labels, return_labels,
+                                             labels=self._crf(r, imgs[i][None].float(), False, False).labels)
                     else:
-                        labels = hip.seg_score_windows(scores, hpw, wpw, oh, ow, sl[0], sl[1], gts[i][None], labels=return_labels,
-                                                       label_dtype=self.label_dtype, **kw)[2]
+                        labels = self._count(score, gts[i][None], raw_labels, return_labels, lambda want, kw: hip.seg_score_windows(
+                            scores, hpw, wpw, oh, ow, sl[0], sl[1], gts[i][None], labels=want, label_dtype=self.label_dtype, **kw)[2])
                     out.append(labels[0] if return_labels else None)
             return (score, out) if return_labels else score
         imgs, shapes, per_image = self._raw_views(*checked, max_batch, mean, std, reverse_channels)
@@ -808,11 +958,11 @@ class Segmenter:
                 out.append(None if labels is None else labels[0])
         return (score, out) if return_labels else score
 
-    def evaluate(self, images, label_maps, raw_labels=True, into=None, return_labels=False):
+    def evaluate(self, images, label_maps, raw_labels=True, into=None, return_labels=False, confusion=False):
         """`__call__` scored against ground truth: images as `__call__` takes them (normalised float [B, 3, H, W] or uint8 RGB
         [B, H, W, 3] / [H, W, 3]), label_maps uint8 / int16 [B, h, w] (or [h, w] for one image): the label map is taken at the
         ground truth's own size, as `out_hw` would.  -> a `SegmentationScore`, or (score, labels [B, h, w]) with `return_labels`;
-        raw_labels, into: as in `evaluate_raw`."""
+        raw_labels, into, confusion: as in `evaluate_raw`."""
         gt = label_maps
         if not torch.is_tensor(gt) or gt.dtype not in (torch.uint8, torch.int16) or gt.dim() not in (2, 3) or gt.numel() == 0:
             raise ValueError("Segmenter.evaluate: label_maps must be a uint8 or int16 tensor [B, h, w], got %s"
@@ -826,7 +976,7 @@ class Segmenter:
         if crf and tuple(gt.shape[1:]) != (H, W):
             raise ValueError("Segmenter.evaluate: with the CRF on, the label maps must have the images' size %s, got %s"
                              % ((H, W), tuple(gt.shape[1:])))
-        score = self._score_into("evaluate", into, patch_images.device)
+        score = self._score_into("evaluate", into, patch_images.device, confusion)
         if crf and rgb is None:
             rgb = ((patch_images.float() * 0.5 + 0.5) * 255.0).permute(0, 2, 3, 1).contiguous()
         scores, hp, wp = self.patch_scores(patch_images)

@@ -606,6 +606,22 @@ int ifseg_seg_predict_views_staging(int max_bytes);
  * gt_bytes, areas and tally; nothing is launched on a refusal.  The *_staging setters apply. */
 int ifseg_seg_areas(const void* labels, int label_bytes, const void* gt, int gt_bytes, long long npix, int n, int raw_labels,
                     unsigned long long* areas, unsigned long long* tally, void* stream);
+/* ifseg_seg_confusion counts which class is taken for which: confusion uint64 [n][n + 1], ADDED to and never cleared.  Inputs,
+ * the ground-truth rule and the set of scored pixels are ifseg_seg_areas'; a scored pixel of ground-truth class c with
+ * predicted label p adds 1 to confusion[c][p] where 0 <= p < n, else to confusion[c][n] (the "outside" column).  So, over
+ * the same inputs: the sum of all entries is tally[0], the diagonal of the first n columns areas[0], their column sums
+ * areas[1], the row sums areas[2].  Integer sums: exact and bit-reproducible.
+ * A workgroup counts in a private LDS table -- the matrix itself up to n = 127, a hashed table of 4096 (class, label) pairs
+ * above, a pair that finds no slot adding to global memory directly -- and only the pairs it met leave it, one 64-bit atomic
+ * each.  NULL labels / gt / confusion, label_bytes or gt_bytes outside {1, 2}, n outside 1..512, an int16 pointer at an odd
+ * address, confusion not 8-byte aligned: IFSEG_ERR_BAD_ARG; npix < 1 or >= 2^31: IFSEG_ERR_BAD_SHAPE; nothing is launched on
+ * a refusal. */
+int ifseg_seg_confusion(const void* labels, int label_bytes, const void* gt, int gt_bytes, long long npix, int n, int raw_labels,
+                        unsigned long long* confusion, void* stream);
+/* the kernel's table sizes, for callers that size an input against them: which = 0 the entries of the direct table (n (n + 1)
+ * up to this counts in it), 1 the slots of the hashed table, 2 the pixels a workgroup takes per step, 3 the workgroups of a
+ * launch at most; any other which: IFSEG_ERR_BAD_ARG. */
+int ifseg_seg_confusion_limit(int which);
 int ifseg_seg_score(const float* scores, int B, int hp, int wp, int n, int h, int w, void* labels, int label_bytes, float* conf,
                     float* probs, const void* gt, int gt_bytes, int raw_labels, unsigned long long* areas,
                     unsigned long long* tally, void* stream);
