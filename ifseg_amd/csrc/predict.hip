@@ -17,8 +17,14 @@
 //            four pixels of a 4-ALIGNED element quad of the flat [B, h, w] index, so the wide stores are aligned whatever w is;
 //            the up to three pixels in front of the first whole quad and behind the last one leave as single elements.
 // No atomics, no scratch buffer, static launch shape, nothing read back.
-// Three more kernels on the same tile and phase 2 follow it: K views of differing grids (seg_predict_views_kernel), the sliding
-// windows of one plane (seg_predict_windows_kernel), and K views of sliding windows (seg_predict_slide_views_kernel).
+// Three more kernels on the same tile follow it: K views of differing grids (seg_predict_views_kernel), the sliding windows of
+// one plane (seg_predict_windows_kernel), and K views of sliding windows (seg_predict_slide_views_kernel).  They walk the
+// classes in chunks.  What the kernels share is written once: phase 2 is finish_tile (the views kernel, whose scoring
+// instantiation measured slower through it, keeps those lines in place), a view's value add_view; the two sliding kernels
+// share the window bookkeeping of a plane under a tile (plane_tile) and a pixel's merged value (slide_pixel).  Two loops
+// stay written out in each chunked kernel because as functions they measured slower: the running maximum between the chunks
+// (both view kernels) and the staging of a grid (the windows kernel at few classes).  The launchers share their refusals
+// and the tile grid (launch_grid), the two sliding ones the check of their windows (make_slide).
 //
 // Scoring (ifseg_seg_score / ifseg_seg_score_views / ifseg_seg_areas): the same kernels with an epilogue behind a template flag
 // that counts the tile's pixels against ground truth -- per class #(pred = gt = c), #(pred = c), #(gt = c) and the two tallies --
@@ -243,6 +249,44 @@ __device__ __forceinline__ void score_tile(const Score& sc, uint32_t* tab, int n
   score_flush(tab, n, scored, bad, sc.areas, sc.tally);
 }
 
+// phase 2 of the four predict kernels, behind the barrier that publishes the label / conf tile: store_tile writes the tile
+// out, and the scoring instantiations (whose labels and conf are optional) count it against ground truth into the table `tab`.
+// pofs, ok, pred: score_tile's, the lane's column in its wave's four rows
+template <typename S>
+__device__ __forceinline__ void finish_tile(const S& sc, uint32_t* tab, int n, const int (&t_lab)[TILE_ROWS][TILE_COLS],
+                                            const float (&t_conf)[TILE_ROWS][TILE_COLS], int b, int X0, int Y0, int xend, int h,
+                                            int w, void* __restrict__ labels, int label_bytes, float* __restrict__ conf,
+                                            const int (&pofs)[4], const bool (&ok)[4], const int (&pred)[4]) {
+  if constexpr (S::on) {
+    if (labels || conf) store_tile<true>(t_lab, t_conf, b, X0, Y0, xend, h, w, labels, label_bytes, conf);
+    score_tile(sc, tab, n, (long long)b * h * w, pofs, ok, pred);
+  } else {
+    store_tile<false>(t_lab, t_conf, b, X0, Y0, xend, h, w, labels, label_bytes, conf);
+  }
+}
+
+// the same for a kernel that kept nothing of its pixels in registers (the three chunked ones): the offsets and the validity
+// are worked out again and the labels gathered from the tile
+template <typename S>
+__device__ __forceinline__ void finish_tile(const S& sc, uint32_t* tab, int n, const int (&t_lab)[TILE_ROWS][TILE_COLS],
+                                            const float (&t_conf)[TILE_ROWS][TILE_COLS], int b, int X0, int Y0, int xend, int h,
+                                            int w, void* __restrict__ labels, int label_bytes, float* __restrict__ conf, int lane,
+                                            int wave) {
+  int pofs[4], pred[4];
+  bool ok[4];
+  if constexpr (S::on) {
+    const int x = min(X0 + lane, w - 1);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int row = wave * 4 + j;
+      pofs[j] = min(Y0 + row, h - 1) * w + x;
+      ok[j] = Y0 + row < h && X0 + lane < w;
+      pred[j] = t_lab[row][lane];
+    }
+  }
+  finish_tile(sc, tab, n, t_lab, t_conf, b, X0, Y0, xend, h, w, labels, label_bytes, conf, pofs, ok, pred);
+}
+
 template <typename S>
 __global__ __launch_bounds__(256) void seg_predict_kernel(const float* __restrict__ scores, int hp, int wp, int n, int h, int w,
                                                           int tiles_x, int tiles_y, void* __restrict__ labels, int label_bytes,
@@ -307,23 +351,18 @@ __global__ __launch_bounds__(256) void seg_predict_kernel(const float* __restric
   for (int j = 0; j < 4; ++j) { t_lab[wave * 4 + j][lane] = best[j].c; t_conf[wave * 4 + j][lane] = best[j].v; }
   __syncthreads();
 
-  // phase 2
-  if constexpr (S::on) {
-    if (labels || conf) store_tile<true>(t_lab, t_conf, b, X0, Y0, xend, h, w, labels, label_bytes, conf);
-    const int pred[4] = {best[0].c, best[1].c, best[2].c, best[3].c};
-    score_tile(sc, tab, n, (long long)b * h * w, pofs, ok, pred);
-  } else {
-    store_tile<false>(t_lab, t_conf, b, X0, Y0, xend, h, w, labels, label_bytes, conf);
-  }
+  const int pred[4] = {best[0].c, best[1].c, best[2].c, best[3].c};
+  finish_tile(sc, tab, n, t_lab, t_conf, b, X0, Y0, xend, h, w, labels, label_bytes, conf, pofs, ok, pred);
 }
 
 // ---- K views of different grids into one label map (multi-scale + flip test-time augmentation) ----
-// The tile, the lane mapping and phase 2 are those of seg_predict_kernel.  The classes are walked in chunks of PV_CHUNK: per
-// chunk the footprints of all views are staged side by side in LDS (PV_CHUNK floats per patch at the odd-slot stride), then a
-// wave takes its four rows one after the other, and per row the view loop runs innermost and adds each view's flat
-// four-weight value into the row's PV_CHUNK registers, in view order.  The running maximum of a pixel lives in the label / conf
-// tile between the chunks.  A flipped view is staged in its mirrored (logical) column order, so the inner loop is the same for
-// both.  Views are given LDS in order while the buffer lasts; a view that no longer fits reads global memory in the same loop.
+// The tile and the lane mapping are those of seg_predict_kernel, phase 2 is finish_tile's lines.  The classes are walked in
+// chunks of PV_CHUNK: per chunk the footprints of all views are staged side by side in LDS (PV_CHUNK floats per patch at the odd-slot
+// stride), then a wave takes its four rows one after the other, and per row the view loop runs innermost and adds each view's
+// flat four-weight value into the row's PV_CHUNK registers, in view order.  The running maximum of a pixel lives in the label /
+// conf tile between the chunks.  A flipped view is staged in its mirrored (logical) column order, so the inner
+// loop is the same for both.  Views are given LDS in order while the buffer lasts; a view that no longer fits reads global
+// memory in the same loop.
 // The source coordinates of a view under the tile do not depend on the class: they are worked out once, as offsets into
 // the view's staged footprint (or its grid in global memory), and kept in LDS, PV_COORDS dwords per view.
 constexpr int PV_MAX_VIEWS = 16, PV_CHUNK = 16, PV_STRIDE = 20;   // PV_STRIDE == pt_stride(PV_CHUNK)
@@ -510,7 +549,8 @@ __global__ __launch_bounds__(256) void seg_predict_views_kernel(ViewTable views,
   }
   __syncthreads();
 
-  // phase 2
+  // phase 2: finish_tile, written out -- through the function the scoring instantiation of this kernel (alone) measured
+  // 0.7 % slower at twelve views
   if constexpr (S::on) {
     if (labels || conf) store_tile<true>(t_lab, t_conf, b, X0, Y0, xend, h, w, labels, label_bytes, conf);
     int pofs[4], pred[4];
@@ -533,7 +573,7 @@ __global__ __launch_bounds__(256) void seg_predict_views_kernel(ViewTable views,
 // hpw x wpw grid.  A pixel of the [h, w] output takes its (up to four) taps in the plane by the coordinate rule; per tap the
 // flat four-weight values of the windows that hold it are added in window order (rows outer) and divided by their number; a
 // tap of weight zero contributes nothing.  Neither a window's [n, ch, cw] tensor nor the plane is ever written.
-// The tile, the lane mapping, the class chunks, add_view and phase 2 are those of seg_predict_views_kernel.  The windows are a
+// The tile, the lane mapping, the class chunks and add_view are those of seg_predict_views_kernel.  The windows are a
 // cross product, so everything is kept per axis: the windows iya..iyb / ixa..ixb hold the tile's plane footprint, each with its
 // own run of patch rows / columns under it, and the runs of an axis laid end to end span a staged grid of FH x FW patches
 // (PV_CHUNK classes each, at the odd-slot stride) in which window (i, j) owns the block rows(i) x cols(j).  A tile whose
@@ -595,35 +635,27 @@ __device__ __forceinline__ void slide_pixel(const float* s, const Slide& sl, con
   }
 }
 
-template <typename S>
-__global__ __launch_bounds__(256) void seg_predict_windows_kernel(const float* __restrict__ scores, Slide sl, int n, int h, int w,
-                                                                  int tiles_x, int tiles_y, void* __restrict__ labels,
-                                                                  int label_bytes, float* __restrict__ conf,
-                                                                  float* __restrict__ probs, int stage_floats, S sc) {
-  // (scoring: the table,) the source cells of the staged rows and columns, then the staged grid: stage_floats in all
-  extern __shared__ __attribute__((aligned(16))) float dyn[];
-  __shared__ int t_lab[TILE_ROWS][TILE_COLS];
-  __shared__ float t_conf[TILE_ROWS][TILE_COLS];
-  // per axis (0: y, 1: x) and window of the tile's range: first patch of its run, their number, run offset - first patch
-  __shared__ int sw_lo[2][SW_MAX_WINDOWS], sw_ext[2][SW_MAX_WINDOWS], sw_adj[2][SW_MAX_WINDOWS], sw_tot[2];
-  int* cellsrc = reinterpret_cast<int*>(dyn);
-  if constexpr (S::on) {
-    score_zero(reinterpret_cast<uint32_t*>(dyn), n);              // published by the barriers below
-    cellsrc += score_dwords(n);
-  }
-
-  const auto [b, X0, Y0, xend, yend, lane, wave] = tile_decode(tiles_x, tiles_y, h, w);
-  const FloatCoord c2y{(float)sl.y.o / (float)h, sl.y.o}, c2x{(float)sl.x.o / (float)w, sl.x.o};            // output -> plane
-  const FloatCoord cwy{(float)sl.hpw / (float)sl.y.e, sl.hpw}, cwx{(float)sl.wpw / (float)sl.x.e, sl.wpw};  // window -> grid
-  const int cells = sl.hpw * sl.wpw;
-  const float* sb = scores + (long long)b * sl.y.g * sl.x.g * cells * n;
-
-  // the tile's footprint in the plane and the windows that hold any of it
+// The window bookkeeping of one plane under one tile, per axis, by all threads of the workgroup (two barriers inside): the
+// plane footprint of the tile's output rows Ya..Yb and columns Xa..Xb, the windows iya.. / ixa.. that hold any of it, per axis
+// (0: y, 1: x) and window the run of patches under it (the caller's scratch: sw_lo its first patch, sw_ext their number; sw_tot
+// the axis' total) and the runs' places in a grid of FH x FW patches (adj: run offset - first patch).  The grid is staged if
+// it fits `room` floats behind `cellsrc` together with its source cells, FH + FW in whole 16-byte slots; those are then
+// written -- staged row R / column C comes from patch cellsrc[R] + cellsrc[FH + C] of the image's windows -- and published by
+// the caller's next barrier.
+struct PlaneTile {
+  int iya, ixa, FH, FW;
+  long long need;         // floats of the source cells and the grid
+  bool staged;            // workgroup-uniform
+};
+__device__ __forceinline__ PlaneTile plane_tile(const Slide& sl, const FloatCoord& c2y, const FloatCoord& c2x, const FloatCoord& cwy,
+                                                const FloatCoord& cwx, int Ya, int Yb, int Xa, int Xb,
+                                                int (&sw_lo)[2][SW_MAX_WINDOWS], int (&sw_ext)[2][SW_MAX_WINDOWS],
+                                                int (&adj)[2][SW_MAX_WINDOWS], int (&sw_tot)[2], int* cellsrc, int room) {
+  const int t = threadIdx.x, cells = sl.hpw * sl.wpw;
   int Ylo, Yhi, Xlo, Xhi;
-  footprint(c2y, Y0, yend - 1, &Ylo, &Yhi);
-  footprint(c2x, X0, xend - 1, &Xlo, &Xhi);
+  footprint(c2y, Ya, Yb, &Ylo, &Yhi);
+  footprint(c2x, Xa, Xb, &Xlo, &Xhi);
   const int iya = sl.y.first(Ylo), ny = sl.y.last(Yhi) - iya + 1, ixa = sl.x.first(Xlo), nx = sl.x.last(Xhi) - ixa + 1;
-  const int t = threadIdx.x;
   const bool isx = t >= ny;
   const int ai = isx ? t - ny : t;                                // thread t < ny + nx takes one window of one axis
   if (t < ny + nx) {
@@ -636,19 +668,48 @@ __global__ __launch_bounds__(256) void seg_predict_windows_kernel(const float* _
   __syncthreads();
   if (t < 2) {
     int used = 0;
-    for (int k = 0; k < (t ? nx : ny); ++k) { sw_adj[t][k] = used - sw_lo[t][k]; used += sw_ext[t][k]; }
+    for (int k = 0; k < (t ? nx : ny); ++k) { adj[t][k] = used - sw_lo[t][k]; used += sw_ext[t][k]; }
     sw_tot[t] = used;
   }
   __syncthreads();
-  const int FH = sw_tot[0], FW = sw_tot[1], ncs = (FH + FW + 3) & ~3;
-  const bool staged = (long long)FH * FW * PV_STRIDE + ncs <= (long long)stage_floats;          // workgroup-uniform
-  float* stage = reinterpret_cast<float*>(cellsrc + ncs);
+  const int FH = sw_tot[0], FW = sw_tot[1];
+  const long long need = (long long)FH * FW * PV_STRIDE + ((FH + FW + 3) & ~3);
+  const bool staged = need <= (long long)room;
   if (staged && t < ny + nx) {
-    // the source of staged row R / column C, in patches from the image's first window: cellsrc[R] + cellsrc[FH + C]
-    const int i = (isx ? ixa : iya) + ai, first = sw_adj[isx][ai] + sw_lo[isx][ai];
+    const int i = (isx ? ixa : iya) + ai, first = adj[isx][ai] + sw_lo[isx][ai];
     for (int r = 0; r < sw_ext[isx][ai]; ++r)
       cellsrc[(isx ? FH : 0) + first + r] = isx ? i * cells + sw_lo[1][ai] + r : i * sl.x.g * cells + (sw_lo[0][ai] + r) * sl.wpw;
   }
+  return {iya, ixa, FH, FW, need, staged};
+}
+
+template <typename S>
+__global__ __launch_bounds__(256) void seg_predict_windows_kernel(const float* __restrict__ scores, Slide sl, int n, int h, int w,
+                                                                  int tiles_x, int tiles_y, void* __restrict__ labels,
+                                                                  int label_bytes, float* __restrict__ conf,
+                                                                  float* __restrict__ probs, int stage_floats, S sc) {
+  // (scoring: the table,) the source cells of the staged rows and columns, then the staged grid: stage_floats in all
+  extern __shared__ __attribute__((aligned(16))) float dyn[];
+  __shared__ int t_lab[TILE_ROWS][TILE_COLS];
+  __shared__ float t_conf[TILE_ROWS][TILE_COLS];
+  // plane_tile's, per axis and window of the tile's range: first patch of its run, their number, run offset - first patch
+  __shared__ int sw_lo[2][SW_MAX_WINDOWS], sw_ext[2][SW_MAX_WINDOWS], sw_adj[2][SW_MAX_WINDOWS], sw_tot[2];
+  int* cellsrc = reinterpret_cast<int*>(dyn);
+  if constexpr (S::on) {
+    score_zero(reinterpret_cast<uint32_t*>(dyn), n);              // published by the barriers below
+    cellsrc += score_dwords(n);
+  }
+
+  const auto [b, X0, Y0, xend, yend, lane, wave] = tile_decode(tiles_x, tiles_y, h, w);
+  const FloatCoord c2y{(float)sl.y.o / (float)h, sl.y.o}, c2x{(float)sl.x.o / (float)w, sl.x.o};            // output -> plane
+  const FloatCoord cwy{(float)sl.hpw / (float)sl.y.e, sl.hpw}, cwx{(float)sl.wpw / (float)sl.x.e, sl.wpw};  // window -> grid
+  const float* sb = scores + (long long)b * sl.y.g * sl.x.g * sl.hpw * sl.wpw * n;
+
+  const PlaneTile pt =
+      plane_tile(sl, c2y, c2x, cwy, cwx, Y0, yend - 1, X0, xend - 1, sw_lo, sw_ext, sw_adj, sw_tot, cellsrc, stage_floats);
+  const int iya = pt.iya, ixa = pt.ixa, FH = pt.FH, FW = pt.FW;
+  const bool staged = pt.staged;
+  float* stage = reinterpret_cast<float*>(cellsrc + ((FH + FW + 3) & ~3));
   __syncthreads();
 
   const int x = min(X0 + lane, w - 1);
@@ -664,7 +725,7 @@ __global__ __launch_bounds__(256) void seg_predict_windows_kernel(const float* _
     if (c0) __syncthreads();                      // the previous chunk has been read
     // phase 0: 16 threads per patch, one class each; the classes past n are zero
     if (staged) {
-      const int cc = t & 15;
+      const int t = threadIdx.x, cc = t & 15;
       for (int p = t >> 4; p < FH * FW; p += 16) {
         const int R = p / FW, C = p - R * FW;
         stage[p * PV_STRIDE + cc] = cc < cn ? sb[(long long)(cellsrc[R] + cellsrc[FH + C]) * n + c0 + cc] : 0.f;
@@ -701,22 +762,8 @@ __global__ __launch_bounds__(256) void seg_predict_windows_kernel(const float* _
   }
   __syncthreads();
 
-  // phase 2
-  if constexpr (S::on) {
-    if (labels || conf) store_tile<true>(t_lab, t_conf, b, X0, Y0, xend, h, w, labels, label_bytes, conf);
-    int pofs[4], pred[4];
-    bool ok[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int row = wave * 4 + j;
-      pofs[j] = min(Y0 + row, h - 1) * w + x;
-      ok[j] = Y0 + row < h && X0 + lane < w;
-      pred[j] = t_lab[row][lane];
-    }
-    score_tile(sc, reinterpret_cast<uint32_t*>(dyn), n, (long long)b * h * w, pofs, ok, pred);
-  } else {
-    store_tile<false>(t_lab, t_conf, b, X0, Y0, xend, h, w, labels, label_bytes, conf);
-  }
+  finish_tile(sc, reinterpret_cast<uint32_t*>(dyn), n, t_lab, t_conf, b, X0, Y0, xend, h, w, labels, label_bytes, conf, lane,
+              wave);
 }
 
 // ---- K views, each the windows of its own plane, into one label map (multi-scale + flip over sliding-window inference) ----
@@ -729,8 +776,8 @@ __global__ __launch_bounds__(256) void seg_predict_windows_kernel(const float* _
 //            classes of a pixel and view before anything can be accumulated: two passes over the class chunks leave max and
 //            sum in LDS (SV_NORM_DWORDS per view), the third recomputes the values -- the same inlined code on the same staged
 //            data, contraction off, so the same bits -- normalises and accumulates.
-// The tile, the lane mapping, the class chunks and phase 2 are seg_predict_windows_kernel's.  Its per-axis window bookkeeping is
-// done once per view, view after view through one pair of scratch arrays, and what the class loop needs of it stays in LDS:
+// The tile, the lane mapping and the class chunks are seg_predict_windows_kernel's.  Its per-axis window bookkeeping (plane_tile)
+// is done once per view, view after view through one pair of scratch arrays, and what the class loop needs of it stays in LDS:
 // per view the runs' offsets (sw_adj), the two scales of its coordinate rules and, for a staged view, the source cells of its
 // grid.  (The plane taps of a pixel are one fma and a floor per axis: they are recomputed where they are used, and their LDS
 // goes to the normalisers.)  Views are given staging room in view order while the buffer lasts; a view that no longer fits
@@ -831,46 +878,18 @@ __global__ __launch_bounds__(256) void seg_predict_slide_views_kernel(SlideViewT
   }
   __syncthreads();
 
-  // seg_predict_windows_kernel's bookkeeping, view after view; a flipped view is under the mirrored columns of the tile
+  // plane_tile, view after view; a flipped view is under the mirrored columns of the tile
   int used = 0;
   for (int k = 0; k < K; ++k) {
     const Slide sl = vm[k].sl;
     const int flip = vm[k].flip;
     const FloatCoord c2y{vm[k].py, sl.y.o}, c2x{vm[k].px, sl.x.o};                                          // output -> plane
     const FloatCoord cwy{vm[k].sy, sl.hpw}, cwx{vm[k].sx, sl.wpw};                                          // window -> grid
-    const int cells = sl.hpw * sl.wpw;
     int* vd = vdata + k * SV_VIEW_DWORDS;
     int (&adj)[2][SW_MAX_WINDOWS] = *reinterpret_cast<int (*)[2][SW_MAX_WINDOWS]>(vd);
-    int Ylo, Yhi, Xlo, Xhi;
-    footprint(c2y, Y0, yend - 1, &Ylo, &Yhi);
-    footprint(c2x, flip ? w - xend : X0, flip ? w - 1 - X0 : xend - 1, &Xlo, &Xhi);
-    const int iya = sl.y.first(Ylo), ny = sl.y.last(Yhi) - iya + 1, ixa = sl.x.first(Xlo), nx = sl.x.last(Xhi) - ixa + 1;
-    const bool isx = t >= ny;
-    const int ai = isx ? t - ny : t;                              // thread t < ny + nx takes one window of one axis
-    if (t < ny + nx) {
-      const SlideAxis a = isx ? sl.x : sl.y;
-      const int st = a.start((isx ? ixa : iya) + ai), lo = isx ? Xlo : Ylo, hi = isx ? Xhi : Yhi;
-      int plo, phi;
-      footprint(isx ? cwx : cwy, max(lo, st) - st, min(hi, st + a.e - 1) - st, &plo, &phi);
-      sw_lo[isx][ai] = plo; sw_ext[isx][ai] = phi - plo + 1;
-    }
-    __syncthreads();
-    if (t < 2) {
-      int run = 0;
-      for (int i = 0; i < (t ? nx : ny); ++i) { adj[t][i] = run - sw_lo[t][i]; run += sw_ext[t][i]; }
-      sw_tot[t] = run;
-    }
-    __syncthreads();
-    const int FH = sw_tot[0], FW = sw_tot[1], ncs = (FH + FW + 3) & ~3;
-    const long long need = (long long)FH * FW * PV_STRIDE + ncs;
-    const bool staged = need <= (long long)(stage_floats - used);                               // workgroup-uniform
-    if (staged && t < ny + nx) {
-      // the source of staged row R / column C, in patches from the image's first window: cellsrc[R] + cellsrc[FH + C]
-      int* cellsrc = reinterpret_cast<int*>(stage + used);
-      const int i = (isx ? ixa : iya) + ai, first = adj[isx][ai] + sw_lo[isx][ai];
-      for (int r = 0; r < sw_ext[isx][ai]; ++r)
-        cellsrc[(isx ? FH : 0) + first + r] = isx ? i * cells + sw_lo[1][ai] + r : i * sl.x.g * cells + (sw_lo[0][ai] + r) * sl.wpw;
-    }
+    const auto [iya, ixa, FH, FW, need, staged] =
+        plane_tile(sl, c2y, c2x, cwy, cwx, Y0, yend - 1, flip ? w - xend : X0, flip ? w - 1 - X0 : xend - 1, sw_lo, sw_ext, adj,
+                   sw_tot, reinterpret_cast<int*>(stage + used), stage_floats - used);
     if (t == 0) {
       SlideMeta& m = vm[k];
       m.iya = iya; m.ixa = ixa; m.FH = FH; m.FW = FW; m.off = staged ? used : -1;
@@ -982,22 +1001,8 @@ __global__ __launch_bounds__(256) void seg_predict_slide_views_kernel(SlideViewT
   }
   __syncthreads();
 
-  // phase 2
-  if constexpr (S::on) {
-    if (labels || conf) store_tile<true>(t_lab, t_conf, b, X0, Y0, xend, h, w, labels, label_bytes, conf);
-    int pofs[4], pred[4];
-    bool ok[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int row = wave * 4 + j;
-      pofs[j] = min(Y0 + row, h - 1) * w + x;
-      ok[j] = Y0 + row < h && X0 + lane < w;
-      pred[j] = t_lab[row][lane];
-    }
-    score_tile(sc, reinterpret_cast<uint32_t*>(dyn), n, (long long)b * h * w, pofs, ok, pred);
-  } else {
-    store_tile<false>(t_lab, t_conf, b, X0, Y0, xend, h, w, labels, label_bytes, conf);
-  }
+  finish_tile(sc, reinterpret_cast<uint32_t*>(dyn), n, t_lab, t_conf, b, X0, Y0, xend, h, w, labels, label_bytes, conf, lane,
+              wave);
 }
 
 // ---- labels from elsewhere (the CRF's argmax, another model) against ground truth ----
@@ -1183,21 +1188,45 @@ int score_refusal(const void* gt, int gt_bytes, const unsigned long long* areas,
   return 0;
 }
 
+// The tile grid of a launch, behind what all four launchers refuse, in this order.  src_ok: the launcher's own look at its
+// scores or view table; grids_ok: its patch grids are at least 1 x 1 and small enough; scores: what has to be float-aligned.
+// OPT (the scoring launches): labels may be null
+struct TileGrid {
+  int rc, tiles_x, tiles_y;
+  long long blocks;
+};
+template <bool OPT>
+TileGrid launch_grid(bool src_ok, bool grids_ok, const void* scores, int B, int n, int h, int w, const void* labels, int label_bytes,
+                     const float* conf, const float* probs) {
+  TileGrid g = {0, 0, 0, 0};
+  (void)hipGetLastError();
+  if (!src_ok) g.rc = IFSEG_ERR_BAD_ARG;
+  else if ((!OPT || labels) && (!labels || (label_bytes != 1 && label_bytes != 2))) g.rc = IFSEG_ERR_BAD_ARG;
+  else if (n < 1 || n > PT_MAX_CLASSES || (labels && label_bytes == 1 && n > 256)) g.rc = IFSEG_ERR_BAD_ARG;
+  else if (B < 1 || !grids_ok || h < 1 || w < 1 || (long long)B * h * w >= (1ll << 31)) g.rc = IFSEG_ERR_BAD_SHAPE;
+  // the wide stores of phase 2 want 16-byte aligned bases
+  else if (((size_t)labels & 15) || ((size_t)conf & 15) || ((size_t)scores & 3) || ((size_t)probs & 3)) g.rc = IFSEG_ERR_BAD_ARG;
+  else if (!tile_grid(h, w, B, &g.tiles_x, &g.tiles_y, &g.blocks)) g.rc = IFSEG_ERR_BAD_SHAPE;
+  return g;
+}
+
+// the windows of an [oh, ow] plane whose windows ran the network on hpw x wpw grids; false: refused
+bool make_slide(int hpw, int wpw, int oh, int ow, int crop_h, int crop_w, int stride_h, int stride_w, Slide* sl) {
+  *sl = {{}, {}, hpw, wpw};
+  if (hpw < 1 || wpw < 1 || !slide_axis(oh, crop_h, stride_h, &sl->y) || !slide_axis(ow, crop_w, stride_w, &sl->x)) return false;
+  const long long nw = (long long)sl->y.g * sl->x.g;
+  // offsets inside one image's windows are ints: Nw hpw wpw n < 2^31
+  return nw <= SW_MAX_WINDOWS && nw * hpw * wpw < (1ll << 31) / PT_MAX_CLASSES;
+}
+
 // ifseg_seg_predict (S = NoScore) and ifseg_seg_score
 template <typename S>
 int launch_predict(const float* scores, int B, int hp, int wp, int n, int h, int w, void* labels, int label_bytes, float* conf,
                    float* probs, void* stream, S sc) {
-  (void)hipGetLastError();
-  if (!scores) return IFSEG_ERR_BAD_ARG;
-  if ((!S::on || labels) && (!labels || (label_bytes != 1 && label_bytes != 2))) return IFSEG_ERR_BAD_ARG;
-  if (n < 1 || n > PT_MAX_CLASSES || (labels && label_bytes == 1 && n > 256)) return IFSEG_ERR_BAD_ARG;
-  if (B < 1 || hp < 1 || wp < 1 || h < 1 || w < 1) return IFSEG_ERR_BAD_SHAPE;
-  if ((long long)B * h * w >= (1ll << 31) || (long long)hp * wp >= (1ll << 31) / PT_MAX_CLASSES) return IFSEG_ERR_BAD_SHAPE;
-  // the wide stores of phase 2 want 16-byte aligned bases
-  if (((size_t)labels & 15) || ((size_t)conf & 15) || ((size_t)scores & 3) || ((size_t)probs & 3)) return IFSEG_ERR_BAD_ARG;
-  int tiles_x, tiles_y;
-  long long blocks;
-  if (!tile_grid(h, w, B, &tiles_x, &tiles_y, &blocks)) return IFSEG_ERR_BAD_SHAPE;
+  const bool grids_ok = hp >= 1 && wp >= 1 && (long long)hp * wp < (1ll << 31) / PT_MAX_CLASSES;
+  const auto [rc, tiles_x, tiles_y, blocks] =
+      launch_grid<S::on>(scores != nullptr, grids_ok, scores, B, n, h, w, labels, label_bytes, conf, probs);
+  if (rc) return rc;
   // the scoring launches take their table out of the staging budget
   const int table = S::on ? score_dwords(n) * 4 : 0;
   const int limit = std::max(std::min(g_stage_limit, PT_STAGE_LIMIT - table), 0);
@@ -1213,15 +1242,9 @@ int launch_predict(const float* scores, int B, int hp, int wp, int n, int h, int
 template <typename S>
 int launch_views(const ifseg_predict_view* views, int K, int B, int n, int h, int w, void* labels, int label_bytes, float* conf,
                  float* probs, void* stream, S sc) {
-  (void)hipGetLastError();
-  if (!views || K < 1 || K > PV_MAX_VIEWS) return IFSEG_ERR_BAD_ARG;
-  if ((!S::on || labels) && (!labels || (label_bytes != 1 && label_bytes != 2))) return IFSEG_ERR_BAD_ARG;
-  if (n < 1 || n > PT_MAX_CLASSES || (labels && label_bytes == 1 && n > 256)) return IFSEG_ERR_BAD_ARG;
-  if (B < 1 || h < 1 || w < 1 || (long long)B * h * w >= (1ll << 31)) return IFSEG_ERR_BAD_SHAPE;
-  if (((size_t)labels & 15) || ((size_t)conf & 15) || ((size_t)probs & 3)) return IFSEG_ERR_BAD_ARG;
-  int tiles_x, tiles_y;
-  long long blocks;
-  if (!tile_grid(h, w, B, &tiles_x, &tiles_y, &blocks)) return IFSEG_ERR_BAD_SHAPE;
+  const auto [rc, tiles_x, tiles_y, blocks] =
+      launch_grid<S::on>(views && K >= 1 && K <= PV_MAX_VIEWS, true, nullptr, B, n, h, w, labels, label_bytes, conf, probs);
+  if (rc) return rc;
   ViewTable table = {};
   long long need = 0;
   for (int k = 0; k < K; ++k) {
@@ -1261,20 +1284,11 @@ long long slide_stage_bound(const Slide& sl, int h, int w) {
 template <typename S>
 int launch_windows(const float* scores, int B, int hpw, int wpw, int n, int oh, int ow, int crop_h, int crop_w, int stride_h,
                    int stride_w, int h, int w, void* labels, int label_bytes, float* conf, float* probs, void* stream, S sc) {
-  (void)hipGetLastError();
-  if (!scores) return IFSEG_ERR_BAD_ARG;
-  if ((!S::on || labels) && (!labels || (label_bytes != 1 && label_bytes != 2))) return IFSEG_ERR_BAD_ARG;
-  if (n < 1 || n > PT_MAX_CLASSES || (labels && label_bytes == 1 && n > 256)) return IFSEG_ERR_BAD_ARG;
-  if (B < 1 || hpw < 1 || wpw < 1 || h < 1 || w < 1 || (long long)B * h * w >= (1ll << 31)) return IFSEG_ERR_BAD_SHAPE;
-  if (((size_t)labels & 15) || ((size_t)conf & 15) || ((size_t)scores & 3) || ((size_t)probs & 3)) return IFSEG_ERR_BAD_ARG;
-  Slide sl = {{}, {}, hpw, wpw};
-  if (!slide_axis(oh, crop_h, stride_h, &sl.y) || !slide_axis(ow, crop_w, stride_w, &sl.x)) return IFSEG_ERR_BAD_SHAPE;
-  const long long nw = (long long)sl.y.g * sl.x.g;
-  // offsets inside one image's windows are ints: Nw hpw wpw n < 2^31
-  if (nw > SW_MAX_WINDOWS || nw * hpw * wpw >= (1ll << 31) / PT_MAX_CLASSES) return IFSEG_ERR_BAD_SHAPE;
-  int tiles_x, tiles_y;
-  long long blocks;
-  if (!tile_grid(h, w, B, &tiles_x, &tiles_y, &blocks)) return IFSEG_ERR_BAD_SHAPE;
+  const auto [rc, tiles_x, tiles_y, blocks] =
+      launch_grid<S::on>(scores != nullptr, hpw >= 1 && wpw >= 1, scores, B, n, h, w, labels, label_bytes, conf, probs);
+  if (rc) return rc;
+  Slide sl;
+  if (!make_slide(hpw, wpw, oh, ow, crop_h, crop_w, stride_h, stride_w, &sl)) return IFSEG_ERR_BAD_SHAPE;
   const long long need = slide_stage_bound(sl, h, w);
   const int counters = S::on ? score_dwords(n) * 4 : 0;
   const int limit = std::max(std::min(g_windows_stage_limit, SW_STAGE_LIMIT - counters), 0);
@@ -1297,26 +1311,16 @@ int device_lds_limit() {
 template <typename S>
 int launch_slide_views(const ifseg_slide_view* views, int K, int B, int n, int crop_h, int crop_w, int stride_h, int stride_w, int h,
                        int w, int softmax, void* labels, int label_bytes, float* conf, float* probs, void* stream, S sc) {
-  (void)hipGetLastError();
-  if (!views || K < 1 || K > PV_MAX_VIEWS) return IFSEG_ERR_BAD_ARG;
-  if ((!S::on || labels) && (!labels || (label_bytes != 1 && label_bytes != 2))) return IFSEG_ERR_BAD_ARG;
-  if (n < 1 || n > PT_MAX_CLASSES || (labels && label_bytes == 1 && n > 256)) return IFSEG_ERR_BAD_ARG;
-  if (B < 1 || h < 1 || w < 1 || (long long)B * h * w >= (1ll << 31)) return IFSEG_ERR_BAD_SHAPE;
-  if (((size_t)labels & 15) || ((size_t)conf & 15) || ((size_t)probs & 3)) return IFSEG_ERR_BAD_ARG;
-  int tiles_x, tiles_y;
-  long long blocks;
-  if (!tile_grid(h, w, B, &tiles_x, &tiles_y, &blocks)) return IFSEG_ERR_BAD_SHAPE;
+  const auto [rc, tiles_x, tiles_y, blocks] =
+      launch_grid<S::on>(views && K >= 1 && K <= PV_MAX_VIEWS, true, nullptr, B, n, h, w, labels, label_bytes, conf, probs);
+  if (rc) return rc;
   SlideViewTable table = {};
   long long need = 0;
   for (int k = 0; k < K; ++k) {
     const ifseg_slide_view& v = views[k];
     if (!v.scores || ((size_t)v.scores & 3)) return IFSEG_ERR_BAD_ARG;
-    if (v.hpw < 1 || v.wpw < 1) return IFSEG_ERR_BAD_SHAPE;
-    Slide sl = {{}, {}, v.hpw, v.wpw};
-    if (!slide_axis(v.oh, crop_h, stride_h, &sl.y) || !slide_axis(v.ow, crop_w, stride_w, &sl.x)) return IFSEG_ERR_BAD_SHAPE;
-    const long long nw = (long long)sl.y.g * sl.x.g;
-    // offsets inside one image's windows are ints: Nw hpw wpw n < 2^31
-    if (nw > SW_MAX_WINDOWS || nw * v.hpw * v.wpw >= (1ll << 31) / PT_MAX_CLASSES) return IFSEG_ERR_BAD_SHAPE;
+    Slide sl;
+    if (!make_slide(v.hpw, v.wpw, v.oh, v.ow, crop_h, crop_w, stride_h, stride_w, &sl)) return IFSEG_ERR_BAD_SHAPE;
     table.v[k] = {v.scores, sl, v.flip != 0};
     need += slide_stage_bound(sl, h, w);
   }

@@ -1035,6 +1035,9 @@ def _staging(setter, staging_bytes):
             setter(c_int(prev))
 
 
+_UNSTAGED = contextlib.nullcontext()
+
+
 def _predict_outputs(B, n, h, w, dev, conf, probs, label_dtype, want_labels=True):
     """-> (labels [B, h, w] uint8 for n <= 256 else int16, or `label_dtype` (None without want_labels: the scoring calls); conf
     fp32 [B, h, w] or None; probs fp32 [B, n, h, w] or None), uninitialised"""
@@ -1047,22 +1050,51 @@ def _predict_outputs(B, n, h, w, dev, conf, probs, label_dtype, want_labels=True
     return labels, cf, pr
 
 
+def _seg_launch(checked, hw, gt, raw_labels=True, labels=True, conf=False, probs=False, areas=None, tally=None,
+                staging_bytes=None, label_dtype=None):
+    """The shared end of the seg_predict* / seg_score* bindings.  checked: what the pair's own checks of its inputs gave,
+    (symbols, head, tail, B, n, device); symbols: the kernel's (predict, score, staging) entry points.  gt None: the predict
+    call (head..., h, w, tail..., labels, their size, conf, probs, stream) at hw = (h, w) -> (labels, conf, probs).  gt given:
+    the ground truth and the counters are checked, the output size is gt's own, and the score call takes the same arguments
+    followed by gt and the counters -> (areas, tally, labels | None, conf | None, probs | None).  head: called behind every
+    check -> the leading arguments (device pointers are taken there); tail: the ones behind h, w; both as ctypes values."""
+    symbols, head, tail, B, n, dev = checked
+    if gt is None:
+        h, w = hw
+        assert h >= 1 and w >= 1 and B * h * w < 2 ** 31, (B, h, w)
+    else:
+        h, w = _score_gt(gt, B, dev)
+        assert B * h * w < 2 ** 31, (B, h, w)
+        areas, tally = _score_counters(n, dev, areas, tally)
+    lab, cf, pr = _predict_outputs(B, n, h, w, dev, conf, probs, label_dtype, labels)
+    args = head() + (c_int(h), c_int(w)) + tail + (_ptr(lab), c_int(lab.element_size() if labels else 0), _ptr(cf), _ptr(pr))
+    if gt is not None:
+        args += (_ptr(gt), c_int(gt.element_size()), c_int(1 if raw_labels else 0), _ptr(areas), _ptr(tally))
+    symbol = symbols[0] if gt is None else symbols[1]
+    # (a call that leaves the staging limit alone pays for no context manager: these launches are short)
+    with _staging(getattr(lib(), symbols[2]), staging_bytes) if staging_bytes is not None else _UNSTAGED:
+        _check(getattr(lib(), symbol)(*args, _stream()), symbol[6:])
+    return (lab, cf, pr) if gt is None else (areas, tally, lab, cf, pr)
+
+
+def _seg_single(scores, hp, wp):
+    """the inputs of seg_predict and seg_score, checked -> `_seg_launch`'s first argument"""
+    assert scores.dtype == torch.float32 and scores.dim() == 3 and scores.is_contiguous(), (scores.dtype, tuple(scores.shape), scores.stride())
+    B, P, n = scores.shape
+    assert P == hp * wp and B >= 1 and hp >= 1 and wp >= 1, (tuple(scores.shape), hp, wp)
+    assert 1 <= n <= SEG_PREDICT_MAX_CLASSES, n
+    return (("ifseg_seg_predict", "ifseg_seg_score", "ifseg_seg_predict_staging"),
+            lambda: (_ptr(scores), c_int(B), c_int(hp), c_int(wp), c_int(n)), (), B, n, scores.device)
+
+
 def seg_predict(scores, hp, wp, h, w, conf=False, probs=False, staging_bytes=None, label_dtype=None):
     """scores fp32 [B, hp*wp, n] (class fastest: what rows_to_f32 / neighbour_smoothing return) -> (labels [B, h, w], uint8 for
     n <= 256 else int16; conf fp32 [B, h, w] or None; probs fp32 [B, n, h, w] or None): bilinear resize to h x w
     (align_corners=False), argmax, the winning value and every value in one pass (csrc/predict.hip).
     staging_bytes: size of the kernel's LDS staging buffer for this call (0: every tile reads global memory), None: the default;
     label_dtype: None, or torch.uint8 (n <= 256 only) / torch.int16 to choose the width"""
-    assert scores.dtype == torch.float32 and scores.dim() == 3 and scores.is_contiguous(), (scores.dtype, tuple(scores.shape), scores.stride())
-    B, P, n = scores.shape
-    assert P == hp * wp and B >= 1 and hp >= 1 and wp >= 1 and h >= 1 and w >= 1, (tuple(scores.shape), hp, wp, h, w)
-    assert 1 <= n <= SEG_PREDICT_MAX_CLASSES, n
-    assert B * h * w < 2 ** 31, (B, h, w)
-    labels, cf, pr = _predict_outputs(B, n, h, w, scores.device, conf, probs, label_dtype)
-    with _staging(lib().ifseg_seg_predict_staging, staging_bytes):
-        _check(lib().ifseg_seg_predict(_ptr(scores), c_int(B), c_int(hp), c_int(wp), c_int(n), c_int(h), c_int(w), _ptr(labels),
-                                       c_int(labels.element_size()), _ptr(cf), _ptr(pr), _stream()), "seg_predict")
-    return labels, cf, pr
+    return _seg_launch(_seg_single(scores, hp, wp), (h, w), None, conf=conf, probs=probs, staging_bytes=staging_bytes,
+                       label_dtype=label_dtype)
 
 
 SEG_PREDICT_MAX_VIEWS = 16
@@ -1079,25 +1111,30 @@ def seg_predict_views(views, h, w, conf=False, probs=False, staging_bytes=None, 
     fp32 in view order and multiplied by float(1 / K), in one launch (csrc/predict.hip); `predict.upsample_views_reference` is
     the specification.  One unflipped view gives seg_predict's outputs bit for bit.  The view table is a kernel argument:
     nothing is copied to the device.  staging_bytes, label_dtype: as in `seg_predict`."""
+    return _seg_launch(_seg_views(views), (h, w), None, conf=conf, probs=probs, staging_bytes=staging_bytes,
+                       label_dtype=label_dtype)
+
+
+def _seg_views(views):
+    """the inputs of seg_predict_views and seg_score_views, checked -> `_seg_launch`'s first argument"""
     views = list(views)
     assert 1 <= len(views) <= SEG_PREDICT_MAX_VIEWS, len(views)
     for k, (scores, hp, wp, flip) in enumerate(views):
         assert scores.dtype == torch.float32 and scores.dim() == 3 and scores.is_contiguous(), (k, scores.dtype, tuple(scores.shape), scores.stride())
     B, _, n = views[0][0].shape
     dev = views[0][0].device
-    table = (_PredictView * len(views))()
     for k, (scores, hp, wp, flip) in enumerate(views):
         assert scores.shape[0] == B and scores.shape[2] == n and scores.device == dev, (k, tuple(scores.shape), B, n)
         assert scores.shape[1] == hp * wp and hp >= 1 and wp >= 1, (k, tuple(scores.shape), hp, wp)
-        table[k] = _PredictView(_ptr(scores), int(hp), int(wp), 1 if flip else 0)
-    assert B >= 1 and h >= 1 and w >= 1, (B, h, w)
-    assert 1 <= n <= SEG_PREDICT_MAX_CLASSES, n
-    assert B * h * w < 2 ** 31, (B, h, w)
-    labels, cf, pr = _predict_outputs(B, n, h, w, dev, conf, probs, label_dtype)
-    with _staging(lib().ifseg_seg_predict_views_staging, staging_bytes):
-        _check(lib().ifseg_seg_predict_views(table, c_int(len(views)), c_int(B), c_int(n), c_int(h), c_int(w), _ptr(labels),
-                                             c_int(labels.element_size()), _ptr(cf), _ptr(pr), _stream()), "seg_predict_views")
-    return labels, cf, pr
+    assert B >= 1 and 1 <= n <= SEG_PREDICT_MAX_CLASSES, (B, n)
+
+    def head():
+        table = (_PredictView * len(views))()
+        for k, (scores, hp, wp, flip) in enumerate(views):
+            table[k] = _PredictView(_ptr(scores), int(hp), int(wp), 1 if flip else 0)
+        return table, c_int(len(views)), c_int(B), c_int(n)
+
+    return ("ifseg_seg_predict_views", "ifseg_seg_score_views", "ifseg_seg_predict_views_staging"), head, (), B, n, dev
 
 
 # --------------------------------------------------------------------------- scoring against ground truth
@@ -1176,49 +1213,16 @@ def seg_score(scores, hp, wp, gt, raw_labels=True, labels=False, conf=False, pro
     conf | None, probs | None).  The counters are `seg_areas`' of the labels the launch decides on, whether it writes them or
     not; the three outputs are optional, and with none of them the launch writes nothing but counters.  What is written is
     `seg_predict`'s, bit for bit.  areas / tally given: accumulated into.  staging_bytes, label_dtype: as in `seg_predict`."""
-    assert scores.dtype == torch.float32 and scores.dim() == 3 and scores.is_contiguous(), (scores.dtype, tuple(scores.shape), scores.stride())
-    B, P, n = scores.shape
-    assert P == hp * wp and B >= 1 and hp >= 1 and wp >= 1, (tuple(scores.shape), hp, wp)
-    assert 1 <= n <= SEG_PREDICT_MAX_CLASSES, n
-    h, w = _score_gt(gt, B, scores.device)
-    assert B * h * w < 2 ** 31, (B, h, w)
-    areas, tally = _score_counters(n, scores.device, areas, tally)
-    lab, cf, pr = _predict_outputs(B, n, h, w, scores.device, conf, probs, label_dtype, labels)
-    with _staging(lib().ifseg_seg_predict_staging, staging_bytes):
-        _check(lib().ifseg_seg_score(_ptr(scores), c_int(B), c_int(hp), c_int(wp), c_int(n), c_int(h), c_int(w), _ptr(lab),
-                                     c_int(lab.element_size() if labels else 0), _ptr(cf), _ptr(pr), _ptr(gt),
-                                     c_int(gt.element_size()), c_int(1 if raw_labels else 0), _ptr(areas), _ptr(tally),
-                                     _stream()), "seg_score")
-    return areas, tally, lab, cf, pr
+    return _seg_launch(_seg_single(scores, hp, wp), None, gt, raw_labels=raw_labels, labels=labels, conf=conf, probs=probs,
+                       areas=areas, tally=tally, staging_bytes=staging_bytes, label_dtype=label_dtype)
 
 
 def seg_score_views(views, gt, raw_labels=True, labels=False, conf=False, probs=False, areas=None, tally=None,
                     staging_bytes=None, label_dtype=None):
     """`seg_predict_views` at gt's own [B, h, w] with the scoring in the kernel's epilogue; arguments and results as
     `seg_score`, `views` as in `seg_predict_views`."""
-    views = list(views)
-    assert 1 <= len(views) <= SEG_PREDICT_MAX_VIEWS, len(views)
-    for k, (scores, hp, wp, flip) in enumerate(views):
-        assert scores.dtype == torch.float32 and scores.dim() == 3 and scores.is_contiguous(), (k, scores.dtype, tuple(scores.shape), scores.stride())
-    B, _, n = views[0][0].shape
-    dev = views[0][0].device
-    for k, (scores, hp, wp, flip) in enumerate(views):
-        assert scores.shape[0] == B and scores.shape[2] == n and scores.device == dev, (k, tuple(scores.shape), B, n)
-        assert scores.shape[1] == hp * wp and hp >= 1 and wp >= 1, (k, tuple(scores.shape), hp, wp)
-    assert B >= 1 and 1 <= n <= SEG_PREDICT_MAX_CLASSES, (B, n)
-    h, w = _score_gt(gt, B, dev)
-    assert B * h * w < 2 ** 31, (B, h, w)
-    areas, tally = _score_counters(n, dev, areas, tally)
-    lab, cf, pr = _predict_outputs(B, n, h, w, dev, conf, probs, label_dtype, labels)
-    table = (_PredictView * len(views))()
-    for k, (scores, hp, wp, flip) in enumerate(views):
-        table[k] = _PredictView(_ptr(scores), int(hp), int(wp), 1 if flip else 0)
-    with _staging(lib().ifseg_seg_predict_views_staging, staging_bytes):
-        _check(lib().ifseg_seg_score_views(table, c_int(len(views)), c_int(B), c_int(n), c_int(h), c_int(w), _ptr(lab),
-                                           c_int(lab.element_size() if labels else 0), _ptr(cf), _ptr(pr), _ptr(gt),
-                                           c_int(gt.element_size()), c_int(1 if raw_labels else 0), _ptr(areas), _ptr(tally),
-                                           _stream()), "seg_score_views")
-    return areas, tally, lab, cf, pr
+    return _seg_launch(_seg_views(views), None, gt, raw_labels=raw_labels, labels=labels, conf=conf, probs=probs, areas=areas,
+                       tally=tally, staging_bytes=staging_bytes, label_dtype=label_dtype)
 
 
 SLIDE_MAX_WINDOWS = 64       # == IFSEG_SLIDE_MAX_WINDOWS of include/ifseg_hip.h
@@ -1253,54 +1257,53 @@ def seg_predict_windows(scores, hpw, wpw, oh, ow, crop, stride, h, w, conf=False
     [n, ch, cw] tensor nor the plane; `predict.slide_reference` is the specification.  One window that covers the plane and
     (h, w) == (oh, ow) give seg_predict's outputs bit for bit.  crop, stride: an int or an (h, w) pair each.
     staging_bytes, label_dtype: as in `seg_predict`."""
+    return _seg_launch(_seg_windows(scores, hpw, wpw, oh, ow, crop, stride), (h, w), None, conf=conf, probs=probs,
+                       staging_bytes=staging_bytes, label_dtype=label_dtype)
+
+
+def _seg_windows(scores, hpw, wpw, oh, ow, crop, stride):
+    """the inputs of seg_predict_windows and seg_score_windows, checked -> `_seg_launch`'s first argument"""
     oh, ow, crop, stride, nw, _, _ = _slide_geometry(oh, ow, crop, stride)
     B, n = _windows_scores(scores, hpw, wpw, nw)
-    assert h >= 1 and w >= 1 and B * h * w < 2 ** 31, (B, h, w)
-    labels, cf, pr = _predict_outputs(B, n, h, w, scores.device, conf, probs, label_dtype)
-    with _staging(lib().ifseg_seg_predict_windows_staging, staging_bytes):
-        _check(lib().ifseg_seg_predict_windows(_ptr(scores), c_int(B), c_int(hpw), c_int(wpw), c_int(n), c_int(oh), c_int(ow),
-                                               c_int(crop[0]), c_int(crop[1]), c_int(stride[0]), c_int(stride[1]), c_int(h),
-                                               c_int(w), _ptr(labels), c_int(labels.element_size()), _ptr(cf), _ptr(pr),
-                                               _stream()), "seg_predict_windows")
-    return labels, cf, pr
+    head = lambda: (_ptr(scores), c_int(B), c_int(hpw), c_int(wpw), c_int(n), c_int(oh), c_int(ow), c_int(crop[0]), c_int(crop[1]),
+                    c_int(stride[0]), c_int(stride[1]))
+    return (("ifseg_seg_predict_windows", "ifseg_seg_score_windows", "ifseg_seg_predict_windows_staging"), head, (), B, n,
+            scores.device)
 
 
 def seg_score_windows(scores, hpw, wpw, oh, ow, crop, stride, gt, raw_labels=True, labels=False, conf=False, probs=False,
                       areas=None, tally=None, staging_bytes=None, label_dtype=None):
     """`seg_predict_windows` at gt's own [B, h, w] with the scoring in the kernel's epilogue; results as `seg_score`."""
-    oh, ow, crop, stride, nw, _, _ = _slide_geometry(oh, ow, crop, stride)
-    B, n = _windows_scores(scores, hpw, wpw, nw)
-    h, w = _score_gt(gt, B, scores.device)
-    assert B * h * w < 2 ** 31, (B, h, w)
-    areas, tally = _score_counters(n, scores.device, areas, tally)
-    lab, cf, pr = _predict_outputs(B, n, h, w, scores.device, conf, probs, label_dtype, labels)
-    with _staging(lib().ifseg_seg_predict_windows_staging, staging_bytes):
-        _check(lib().ifseg_seg_score_windows(_ptr(scores), c_int(B), c_int(hpw), c_int(wpw), c_int(n), c_int(oh), c_int(ow),
-                                             c_int(crop[0]), c_int(crop[1]), c_int(stride[0]), c_int(stride[1]), c_int(h),
-                                             c_int(w), _ptr(lab), c_int(lab.element_size() if labels else 0), _ptr(cf), _ptr(pr),
-                                             _ptr(gt), c_int(gt.element_size()), c_int(1 if raw_labels else 0), _ptr(areas),
-                                             _ptr(tally), _stream()), "seg_score_windows")
-    return areas, tally, lab, cf, pr
+    return _seg_launch(_seg_windows(scores, hpw, wpw, oh, ow, crop, stride), None, gt, raw_labels=raw_labels, labels=labels,
+                       conf=conf, probs=probs, areas=areas, tally=tally, staging_bytes=staging_bytes, label_dtype=label_dtype)
 
 
 class _SlideView(ctypes.Structure):
     _fields_ = [("scores", c_void_p), ("hpw", c_int), ("wpw", c_int), ("oh", c_int), ("ow", c_int), ("flip", c_int)]
 
 
-def _slide_views_table(views, crop, stride):
-    """the checks of the two slide-views bindings -> (table, K, B, n, device, (crop_h, crop_w), (stride_h, stride_w))"""
+def _seg_slide_views(views, crop, stride, softmax):
+    """the inputs of seg_predict_slide_views and seg_score_slide_views, checked -> `_seg_launch`'s first argument"""
     views = list(views)
     assert 1 <= len(views) <= SEG_PREDICT_MAX_VIEWS, len(views)
-    table = (_SlideView * len(views))()
     B = n = dev = None
+    planes = []
     for k, (scores, hpw, wpw, oh, ow, flip) in enumerate(views):
         oh, ow, cr, st, nw, _, _ = _slide_geometry(oh, ow, crop, stride)
         b, m = _windows_scores(scores, hpw, wpw, nw)
         if k == 0:
             B, n, dev = b, m, scores.device
         assert b == B and m == n and scores.device == dev, (k, tuple(scores.shape), B, n)
-        table[k] = _SlideView(_ptr(scores), int(hpw), int(wpw), oh, ow, 1 if flip else 0)
-    return table, len(views), B, n, dev, cr, st
+        planes.append((oh, ow))
+
+    def head():
+        table = (_SlideView * len(views))()
+        for k, (scores, hpw, wpw, _, _, flip) in enumerate(views):
+            table[k] = _SlideView(_ptr(scores), int(hpw), int(wpw), *planes[k], 1 if flip else 0)
+        return table, c_int(len(views)), c_int(B), c_int(n), c_int(cr[0]), c_int(cr[1]), c_int(st[0]), c_int(st[1])
+
+    return (("ifseg_seg_predict_slide_views", "ifseg_seg_score_slide_views", "ifseg_seg_predict_slide_views_staging"), head,
+            (c_int(1 if softmax else 0),), B, n, dev)
 
 
 def seg_predict_slide_views(views, crop, stride, h, w, softmax, conf=False, probs=False, staging_bytes=None, label_dtype=None):
@@ -1312,33 +1315,15 @@ def seg_predict_slide_views(views, crop, stride, h, w, softmax, conf=False, prob
     and multiplied by float(1 / K), in ONE launch (csrc/predict.hip); `predict.slide_views_reference` is the specification.
     One unflipped view without softmax gives seg_predict_windows' outputs bit for bit.  crop, stride: an int or an (h, w) pair
     each.  staging_bytes, label_dtype: as in `seg_predict`."""
-    table, K, B, n, dev, crop, stride = _slide_views_table(views, crop, stride)
-    assert h >= 1 and w >= 1 and B * h * w < 2 ** 31, (B, h, w)
-    labels, cf, pr = _predict_outputs(B, n, h, w, dev, conf, probs, label_dtype)
-    with _staging(lib().ifseg_seg_predict_slide_views_staging, staging_bytes):
-        _check(lib().ifseg_seg_predict_slide_views(table, c_int(K), c_int(B), c_int(n), c_int(crop[0]), c_int(crop[1]),
-                                                   c_int(stride[0]), c_int(stride[1]), c_int(h), c_int(w),
-                                                   c_int(1 if softmax else 0), _ptr(labels), c_int(labels.element_size()),
-                                                   _ptr(cf), _ptr(pr), _stream()), "seg_predict_slide_views")
-    return labels, cf, pr
+    return _seg_launch(_seg_slide_views(views, crop, stride, softmax), (h, w), None, conf=conf, probs=probs,
+                       staging_bytes=staging_bytes, label_dtype=label_dtype)
 
 
 def seg_score_slide_views(views, crop, stride, gt, softmax, raw_labels=True, labels=False, conf=False, probs=False, areas=None,
                           tally=None, staging_bytes=None, label_dtype=None):
     """`seg_predict_slide_views` at gt's own [B, h, w] with the scoring in the kernel's epilogue; results as `seg_score`."""
-    table, K, B, n, dev, crop, stride = _slide_views_table(views, crop, stride)
-    h, w = _score_gt(gt, B, dev)
-    assert B * h * w < 2 ** 31, (B, h, w)
-    areas, tally = _score_counters(n, dev, areas, tally)
-    lab, cf, pr = _predict_outputs(B, n, h, w, dev, conf, probs, label_dtype, labels)
-    with _staging(lib().ifseg_seg_predict_slide_views_staging, staging_bytes):
-        _check(lib().ifseg_seg_score_slide_views(table, c_int(K), c_int(B), c_int(n), c_int(crop[0]), c_int(crop[1]),
-                                                 c_int(stride[0]), c_int(stride[1]), c_int(h), c_int(w),
-                                                 c_int(1 if softmax else 0), _ptr(lab), c_int(lab.element_size() if labels else 0),
-                                                 _ptr(cf), _ptr(pr), _ptr(gt), c_int(gt.element_size()),
-                                                 c_int(1 if raw_labels else 0), _ptr(areas), _ptr(tally), _stream()),
-               "seg_score_slide_views")
-    return areas, tally, lab, cf, pr
+    return _seg_launch(_seg_slide_views(views, crop, stride, softmax), None, gt, raw_labels=raw_labels, labels=labels,
+                       conf=conf, probs=probs, areas=areas, tally=tally, staging_bytes=staging_bytes, label_dtype=label_dtype)
 
 
 # --------------------------------------------------------------------------- the label map as a picture

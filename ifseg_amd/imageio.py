@@ -199,25 +199,17 @@ def slide_windows(oh, ow, crop, stride):
 
 
 def plan_slide(shapes, patch_image_size, crop, stride, ratio=1.0, max_batch=8):
-    """`plan_views` for sliding-window inference, as a pure function: -> (per_image, loads, forwards).
+    """`plan_views` for sliding-window inference, as a pure function: `plan_slide_views`' plan for the one unflipped view at
+    `ratio`, without the view index -> (per_image, loads, forwards).
     per_image: [((oh, ow), ys, xs, (ch, cw))], image i at `eval_size(H, W, P, ratio)` and its `slide_windows`; window k of
     image i is the pair (i, k).
     loads: [((H, W), (oh, ow), [image indices])], one `image_load_windows` launch per distinct (source shape, (oh, ow)), in
     order of first appearance.
     forwards: [((ch, cw), [(i, k)])], one model forward per entry: the windows of one size, of whatever image, in
     (image, window) order, at most `max_batch` of them; the entries of one size follow each other."""
-    if max_batch < 1:
-        raise ValueError("segment_raw: max_batch must be >= 1, got %r" % (max_batch,))
-    per_image, loads, by_size = [], {}, {}
-    for i, (h, w) in enumerate(shapes):
-        h, w = int(h), int(w)
-        size = eval_size(h, w, patch_image_size, ratio)
-        ys, xs, ch, cw = slide_windows(size[0], size[1], crop, stride)
-        per_image.append((size, ys, xs, (ch, cw)))
-        loads.setdefault(((h, w), size), []).append(i)
-        by_size.setdefault((ch, cw), []).extend((i, k) for k in range(len(ys) * len(xs)))
-    forwards = [(size, ik[k:k + max_batch]) for size, ik in by_size.items() for k in range(0, len(ik), max_batch)]
-    return per_image, [(hw, size, idx) for (hw, size), idx in loads.items()], forwards
+    per_image, loads, forwards = _plan_windows(shapes, patch_image_size, crop, stride, [(ratio, False)], max_batch)
+    return ([mine[0] for mine in per_image], [(hw, size, idx) for hw, size, _, idx in loads],
+            [(size, [(i, k) for i, _, k in ivk]) for size, ivk in forwards])
 
 
 def plan_slide_views(shapes, patch_image_size, crop, stride, scales=(1.0,), flip=False, max_batch=8):
@@ -230,9 +222,16 @@ def plan_slide_views(shapes, patch_image_size, crop, stride, scales=(1.0,), flip
     forwards: [((ch, cw), [(i, v, k)])], one model forward per entry: the windows of one size, of whatever view and image, in
     (image, view, window) order, at most `max_batch` of them; the entries of one size follow each other.
     ValueError: more than MAX_VIEWS views, more than MAX_WINDOWS windows in any view, a crop or stride outside the rule."""
-    if max_batch < 1:
+    if max_batch < 1:                                         # here as well: this refusal comes before view_list's
         raise ValueError("segment_raw: max_batch must be >= 1, got %r" % (max_batch,))
     views = view_list(scales, flip)
+    return (views,) + _plan_windows(shapes, patch_image_size, crop, stride, views, max_batch)
+
+
+def _plan_windows(shapes, patch_image_size, crop, stride, views, max_batch):
+    """the plan of `plan_slide_views` for the given (ratio, flipped) views -> (per_image, loads, forwards)"""
+    if max_batch < 1:
+        raise ValueError("segment_raw: max_batch must be >= 1, got %r" % (max_batch,))
     per_image, loads, by_size = [], {}, {}
     for i, (h, w) in enumerate(shapes):
         h, w = int(h), int(w)
@@ -247,7 +246,7 @@ def plan_slide_views(shapes, patch_image_size, crop, stride, scales=(1.0,), flip
             by_size.setdefault((ch, cw), []).extend((i, v, k) for k in range(len(ys) * len(xs)))
         per_image.append(mine)
     forwards = [(size, ivk[k:k + max_batch]) for size, ivk in by_size.items() for k in range(0, len(ivk), max_batch)]
-    return views, per_image, [(hw, size, f, idx) for (hw, size, f), idx in loads.items()], forwards
+    return per_image, [(hw, size, f, idx) for (hw, size, f), idx in loads.items()], forwards
 
 
 def image_load_windows_reference(images_u8, oh, ow, crop, stride, mean=HALF, std=HALF, reverse_channels=False,

@@ -24,7 +24,8 @@ with the square of the grid; the views are therefore run size by size (`imageio.
 Sliding-window inference (mmseg's `test_cfg=dict(mode='slide', crop_size=(P, P), stride=(s, s))`, how fixed-grid transformer
 segmenters are scored): `seg.segment_raw(photos, slide=True)` cuts the resized image into overlapping P x P windows
 (`imageio.slide_windows`, written directly by `hip.image_load_windows`), runs every window at the trained grid -- one network
-size for a whole data set, no resized-bias entry, the windows of all images in the same batches (`imageio.plan_slide`) -- and
+size for a whole data set, no resized-bias entry, the windows of all images in the same batches (`imageio.plan_slide_views`,
+here with one view) -- and
 ONE launch of `hip.seg_predict_windows` per image resizes the windows' scores, averages them where windows overlap and
 resizes the result to the image's shape: no per-window [n, P, P] tensor, sum or count plane is written.  Limits: the
 reference never slides, so there is no golden and parity is to the specification `slide_reference`; a single view only
@@ -75,16 +76,23 @@ PIL): parity is exact to `render_reference`, which equals the demo's formula at 
 
     pics = seg.render_raw(photos, opacity=0.5, boundary=1)          # [RenderResult(picture uint8 [H_i, W_i, 3], labels, conf)]
 
+How the four settings share their code: a front (`Segmenter._raw_views` without `slide`, `_raw_window_views` with it, for one
+view or many) runs the loads and the forwards and hands back one `_Merge` per image -- the setting's last launch, as its
+`hip.seg_predict*` and its `hip.seg_score*`, bound to the image's scores and geometry.  `Segmenter._label` finishes an image
+from its merge (the predict launch, then the CRF) and `Segmenter._count` scores it (the scoring launch; with the CRF on
+`_label` and `hip.seg_areas`; `hip.seg_confusion` behind either); `__call__` and `evaluate` go through the same two with the
+single-view merge of their batch.
+
 Nothing in the call synchronises with the host; `labels`, `conf` and `probs` stay on the device.  There is no CPU fallback:
 `upsample_argmax_reference` is the specification the tests compare against, not a second implementation of the path.
 """
-from typing import NamedTuple, Optional
+from typing import Callable, NamedTuple, Optional
 
 import torch
 import torch.nn.functional as F
 
 from . import hip
-from .imageio import HALF, eval_size, plan_slide, plan_slide_views, plan_views, slide_windows, view_list
+from .imageio import HALF, eval_size, plan_slide_views, plan_views, slide_windows, view_list
 from .tasks.mm_tasks.segmentation import BOS, EOS, PROMPT_IDS
 
 MAX_CLASSES = hip.SEG_PREDICT_MAX_CLASSES
@@ -94,6 +102,13 @@ class SegmentationResult(NamedTuple):
     labels: torch.Tensor                       # [B, h, w] uint8 (n <= 256) or int16
     conf: Optional[torch.Tensor]               # [B, h, w] fp32: the value of the winning class
     probs: Optional[torch.Tensor]              # [B, n, h, w] fp32: every class
+
+
+class _Merge(NamedTuple):
+    """What a front of the Segmenter hands back per image (or batch): the last launch of its setting, bound to its scores and
+    geometry.  Every setting is finished (`Segmenter._label`) and scored (`Segmenter._count`) through these two."""
+    predict: Callable                          # (h, w, conf=, probs=, label_dtype=) -> what its hip.seg_predict* returns
+    score: Callable                            # (gt, labels=, label_dtype=, raw_labels=, areas=, tally=) -> its hip.seg_score*'s
 
 
 def upsample_argmax_reference(scores, hp, wp, h, w, dtype=torch.float64):
@@ -562,17 +577,31 @@ class Segmenter:
                 model.train()
         return scores, hp, wp
 
-    def _finish(self, scores, hp, wp, h, w, rgb, return_conf, return_probs):
-        crf = self.crf_iters > 0
-        out = hip.seg_predict(scores, hp, wp, h, w, conf=return_conf and not crf, probs=return_probs or crf,
-                              label_dtype=self.label_dtype)
-        return self._crf(out, rgb, return_conf, return_probs)
+    def _views_merge(self, vs):
+        """the merge of the K views (scores, hp, wp, flip) of one image or batch; one plain view is the single-view kernel"""
+        if len(vs) == 1 and not vs[0][3]:
+            return _Merge(lambda h, w, **kw: hip.seg_predict(*vs[0][:3], h, w, **kw),
+                          lambda gt, **kw: hip.seg_score(*vs[0][:3], gt, **kw))
+        return _Merge(lambda h, w, **kw: hip.seg_predict_views(vs, h, w, **kw), lambda gt, **kw: hip.seg_score_views(vs, gt, **kw))
 
-    def _finish_views(self, views, h, w, rgb, return_conf, return_probs):
-        """`_finish` on the mean of K views (scores, hp, wp, flip) of the same images"""
+    def _slide_merge(self, vs, sl):
+        """the merge of one image's views (scores [1, Nw, hpw*wpw, n], hpw, wpw, oh, ow, flip) under `slide` = (crop, stride): the
+        slide-views kernel on a Segmenter built with `slide_views` (for one view too), else the windows kernel on the one view"""
+        if self.slide_views:
+            # raw logits are normalised per view behind the merge (mmseg's order); the per-patch softmax and the neighbour
+            # smoothing hand over probabilities, whose merge is linear
+            softmax = self.upsample == "logits" and self.smooth_iters == 0
+            return _Merge(lambda h, w, **kw: hip.seg_predict_slide_views(vs, *sl, h, w, softmax, **kw),
+                          lambda gt, **kw: hip.seg_score_slide_views(vs, *sl, gt, softmax, **kw))
+        (one,) = vs
+        return _Merge(lambda h, w, **kw: hip.seg_predict_windows(*one[:5], *sl, h, w, **kw),
+                      lambda gt, **kw: hip.seg_score_windows(*one[:5], *sl, gt, **kw))
+
+    def _label(self, merge, h, w, rgb, return_conf, return_probs):
+        """one image (or batch) from its merge to a SegmentationResult at h x w: the predict launch, which with the CRF on hands
+        every class's value to `_crf`; rgb: the CRF's images, else None"""
         crf = self.crf_iters > 0
-        out = hip.seg_predict_views(views, h, w, conf=return_conf and not crf, probs=return_probs or crf,
-                                    label_dtype=self.label_dtype)
+        out = merge.predict(h, w, conf=return_conf and not crf, probs=return_probs or crf, label_dtype=self.label_dtype)
         return self._crf(out, rgb, return_conf, return_probs)
 
     def _crf(self, out, rgb, return_conf, return_probs):
@@ -598,9 +627,9 @@ class Segmenter:
         scores, hp, wp = self.patch_scores(patch_images)
         with torch.no_grad():
             if sizes is None:
-                return self._finish(scores, hp, wp, one[0], one[1], rgb, return_conf, return_probs)
-            return [self._finish(scores[b:b + 1], hp, wp, s[0], s[1], rgb[b:b + 1] if crf else None, return_conf, return_probs)
-                    for b, s in enumerate(sizes)]
+                return self._label(self._views_merge([(scores, hp, wp, False)]), *one, rgb, return_conf, return_probs)
+            return [self._label(self._views_merge([(scores[b:b + 1], hp, wp, False)]), *s, rgb[b:b + 1] if crf else None,
+                                return_conf, return_probs) for b, s in enumerate(sizes)]
 
     # -- raw images of any size ----------------------------------------------------------
     def segment_raw(self, images, max_batch=8, mean=None, std=None, reverse_channels=False, return_conf=False,
@@ -636,7 +665,7 @@ class Segmenter:
         or an (h, w) pair: as given.  The image is resized to `eval_size(H, W, P, scales[0])` and cut into overlapping windows
         (`imageio.slide_windows`), written directly by `hip.image_load_windows`; every window runs the forward above (and
         the smoothing, per window) at the window's size -- with crop = P the trained grid, so no resized-bias entry is
-        built and the windows of all images fill the same batches (`imageio.plan_slide`) -- and ONE launch of
+        built and the windows of all images fill the same batches (`imageio.plan_slide_views`) -- and ONE launch of
         `hip.seg_predict_windows` per image resizes the windows' scores, averages them where windows overlap and resizes
         the result to [H_i, W_i]: no per-window [n, crop, crop] tensor, sum or count plane is written.  `slide_reference` is
         the specification; the reference never slides, so there is no golden for it.  Both `upsample` modes are allowed:
@@ -656,33 +685,11 @@ class Segmenter:
         plan = self._plan_slide(checked, sl, max_batch)
         if checked is None:
             return []
+        imgs, shapes, merges = self._front(checked, sl, plan, max_batch, mean, std, reverse_channels)
         crf, out = self.crf_iters > 0, []
-        if sl is not None and self.slide_views:
-            imgs, shapes, per_image = self._raw_window_views(checked[1], sl, plan, mean, std, reverse_channels)
-            with torch.no_grad():
-                for i, vs in enumerate(per_image):
-                    r = hip.seg_predict_slide_views(vs, sl[0], sl[1], *shapes[i], self._views_softmax(), conf=return_conf and not crf,
-                                                    probs=return_probs or crf, label_dtype=self.label_dtype)
-                    r = self._crf(r, imgs[i][None].float() if crf else None, return_conf, return_probs)
-                    out.append(SegmentationResult(*(None if t is None else t[0] for t in r)))
-            return out
-        if sl is not None:
-            imgs, shapes, per_image = self._raw_windows(checked[1], sl, plan, mean, std, reverse_channels)
-            with torch.no_grad():
-                for i, (scores, hpw, wpw, (oh, ow)) in enumerate(per_image):
-                    r = hip.seg_predict_windows(scores, hpw, wpw, oh, ow, sl[0], sl[1], *shapes[i], conf=return_conf and not crf,
-                                                probs=return_probs or crf, label_dtype=self.label_dtype)
-                    r = self._crf(r, imgs[i][None].float() if crf else None, return_conf, return_probs)
-                    out.append(SegmentationResult(*(None if t is None else t[0] for t in r)))
-            return out
-        imgs, shapes, per_image = self._raw_views(*checked, max_batch, mean, std, reverse_channels)
         with torch.no_grad():
-            for i, vs in enumerate(per_image):
-                (H, W), rgb = shapes[i], imgs[i][None].float() if crf else None
-                if len(vs) == 1 and not vs[0][3]:             # one plain view: the single-view kernel
-                    r = self._finish(*vs[0][:3], H, W, rgb, return_conf, return_probs)
-                else:
-                    r = self._finish_views(vs, H, W, rgb, return_conf, return_probs)
+            for i, merge in enumerate(merges):
+                r = self._label(merge, *shapes[i], imgs[i][None].float() if crf else None, return_conf, return_probs)
                 out.append(SegmentationResult(*(None if t is None else t[0] for t in r)))
         return out
 
@@ -720,46 +727,25 @@ class Segmenter:
 
     def _plan_slide(self, checked, sl, max_batch):
         """the windows and launches of a `slide` call, on the host (more than 64 windows of an image is a ValueError here) ->
-        (the images' (H, W), `imageio.plan_slide`'s result), or None without `slide` or images"""
+        (the images' (H, W), `imageio.plan_slide_views`' result: one unflipped view without `slide_views`), or None without `slide`
+        or images"""
         if sl is None or checked is None:
             return None
         shapes = [(int(im.shape[0]), int(im.shape[1])) for im in checked[1]]
-        if self.slide_views:
-            return shapes, plan_slide_views(shapes, self.model.cfg.patch_image_size, sl[0], sl[1], checked[2], checked[3], max_batch)
-        return shapes, plan_slide(shapes, self.model.cfg.patch_image_size, sl[0], sl[1], float(checked[2][0]), max_batch)
+        return shapes, plan_slide_views(shapes, self.model.cfg.patch_image_size, sl[0], sl[1], checked[2], checked[3], max_batch)
 
-    def _raw_windows(self, imgs, sl, plan, mean, std, reverse_channels):
-        """the front of `segment_raw` and `evaluate_raw` with `slide`: every image's windows loaded in one launch per source
-        shape, one forward per window size and `max_batch` windows (`plan`: what `_plan_slide` gave) -> (the images on the
-        device, their (H, W), per image
-        (scores [1, Nw, hpw*wpw, n], hpw, wpw, (oh, ow)))"""
-        mean, std = HALF if mean is None else mean, HALF if std is None else std
-        dev = next(self.model.parameters()).device
-        shapes, (per_image, loads, forwards) = plan
-        imgs = [im.to(dev, non_blocking=True) for im in imgs]
-        x, got, grid = {}, [[None] * (len(ys) * len(xs)) for _, ys, xs, _ in per_image], {}
-        with torch.no_grad():
-            for _, size, idx in loads:
-                t = hip.image_load_windows(torch.stack([imgs[i] for i in idx]), size[0], size[1], sl[0], sl[1], mean, std,
-                                           reverse_channels)
-                for k, wins in enumerate(t.chunk(len(idx))):
-                    x[idx[k]] = wins
-            for size, ik in forwards:
-                scores, hp, wp = self.patch_scores(torch.stack([x[i][k] for i, k in ik]))
-                for j, (i, k) in enumerate(ik):
-                    got[i][k], grid[i] = scores[j], (hp, wp)
-        return imgs, shapes, [(torch.stack(got[i])[None], *grid[i], per_image[i][0]) for i in range(len(imgs))]
-
-    def _views_softmax(self):
-        """the `softmax` of the slide-views launch: raw logits are normalised per view behind the merge (mmseg's order); the
-        per-patch softmax and the neighbour smoothing hand over probabilities, whose merge is linear"""
-        return self.upsample == "logits" and self.smooth_iters == 0
+    def _front(self, checked, sl, plan, max_batch, mean, std, reverse_channels):
+        """everything of `segment_raw` and `evaluate_raw` in front of the last launch per image: the loads and the forwards of the
+        setting -> (the images on the device, their (H, W), per image its `_Merge`)"""
+        if sl is None:
+            return self._raw_views(*checked, max_batch, mean, std, reverse_channels)
+        return self._raw_window_views(checked[1], sl, plan, mean, std, reverse_channels)
 
     def _raw_window_views(self, imgs, sl, plan, mean, std, reverse_channels):
-        """`_raw_windows` for `slide_views`: the windows of every view loaded in one launch per (source shape, size, flip), one
-        forward per window size and `max_batch` windows of whatever view and image (`plan`: what `_plan_slide` gave) -> (the
-        images on the device, their (H, W), per image its views (scores [1, Nw, hpw*wpw, n], hpw, wpw, oh, ow, flip) in view
-        order)"""
+        """the front with `slide`: the windows of every view loaded in one launch per (source shape, size, flip), one forward per
+        window size and `max_batch` windows of whatever view and image (`plan`: what `_plan_slide` gave; without `slide_views`
+        it holds the one unflipped view) -> (the images on the device, their (H, W), per image the `_slide_merge` of its views
+        (scores [1, Nw, hpw*wpw, n], hpw, wpw, oh, ow, flip) in view order)"""
         mean, std = HALF if mean is None else mean, HALF if std is None else std
         dev = next(self.model.parameters()).device
         shapes, (views, per_image, loads, forwards) = plan
@@ -776,12 +762,12 @@ class Segmenter:
                 scores, hp, wp = self.patch_scores(torch.stack([x[i, per_image[i][v][0], views[v][1]][k] for i, v, k in ivk]))
                 for j, (i, v, k) in enumerate(ivk):
                     got[i][v][k], grid[i, v] = scores[j], (hp, wp)
-        return imgs, shapes, [[(torch.stack(got[i][v])[None], *grid[i, v], *per_image[i][v][0], views[v][1])
-                               for v in range(len(views))] for i in range(len(imgs))]
+        return imgs, shapes, [self._slide_merge([(torch.stack(got[i][v])[None], *grid[i, v], *per_image[i][v][0], views[v][1])
+                                                 for v in range(len(views))], sl) for i in range(len(imgs))]
 
     def _raw_views(self, views, imgs, scales, flip, max_batch, mean, std, reverse_channels):
-        """the front of `segment_raw` and `evaluate_raw`: every image loaded once per ratio, one forward per network size ->
-        (the images on the device, their (H, W), per image its views (scores [1, hp*wp, n], hp, wp, flip) in view order)"""
+        """the front without `slide`: every image loaded once per ratio, one forward per network size -> (the images on the
+        device, their (H, W), per image the `_views_merge` of its views (scores [1, hp*wp, n], hp, wp, flip) in view order)"""
         mean, std = HALF if mean is None else mean, HALF if std is None else std
         dev = next(self.model.parameters()).device
         imgs = [im.to(dev, non_blocking=True) for im in imgs]
@@ -797,7 +783,7 @@ class Segmenter:
                 scores, hp, wp = self.patch_scores(torch.stack([x[i, size].flip(-1) if views[v][1] else x[i, size] for i, v in iv]))
                 for k, (i, v) in enumerate(iv):
                     per_image[i][v] = (scores[k:k + 1], hp, wp, views[v][1])
-        return imgs, shapes, per_image
+        return imgs, shapes, [self._views_merge(vs) for vs in per_image]
 
     # -- the label map as a picture --------------------------------------------------------
     def render_raw(self, images, palette=None, opacity=0.5, boundary=0, boundary_color=(255, 255, 255), fade_by_conf=False,
@@ -855,35 +841,22 @@ class Segmenter:
                              "confusion=True))" % what)
         return into
 
-    def _count(self, score, gt, raw_labels, return_labels, launch=None, labels=None):
-        """The scoring step of every branch of `evaluate_raw` / `evaluate`, for gt [B, h, w] -> the labels [B, h, w] or None.
-        launch(want_labels, counters): the scoring launch, whose epilogue adds to `counters` (raw_labels, areas, tally as
-        keywords) -> its label map or None.  labels instead: a label map from elsewhere (the CRF's argmax), counted by
-        `hip.seg_areas`.  Where the score carries a confusion matrix, the launch is asked for its label map and
-        `hip.seg_confusion` counts the pairs of the same labels behind it on the same stream."""
+    def _count(self, score, merge, gt, raw_labels, rgb, return_labels):
+        """The scoring step of `evaluate_raw` / `evaluate`: one image's (or batch's) merge against gt [B, h, w] into `score` -> its
+        labels [B, h, w] or None.  The epilogue of the merge's scoring launch adds to the counters.  With the CRF on, the label
+        map comes from the CRF (`_label`; rgb: its images), not from the predict kernel, and `hip.seg_areas` counts it.  Where
+        the score carries a confusion matrix, the launch is asked for its label map and `hip.seg_confusion` counts the pairs
+        of the same labels behind it on the same stream."""
         kw = dict(raw_labels=raw_labels, areas=score.areas, tally=score.tally)
         pairs = score.confusion is not None
-        if labels is None:
-            labels = launch(return_labels or pairs, kw)
-        else:
-            labels = labels.contiguous()
+        if self.crf_iters > 0:
+            labels = self._label(merge, int(gt.shape[1]), int(gt.shape[2]), rgb, False, False).labels.contiguous()
             hip.seg_areas(labels, gt, self.n, **kw)
+        else:
+            labels = merge.score(gt, labels=return_labels or pairs, label_dtype=self.label_dtype, **kw)[2]
         if pairs:
             hip.seg_confusion(labels, gt, self.n, raw_labels, confusion=score.confusion)
         return labels if return_labels else None
-
-    def _score(self, score, vs, gt, raw_labels, rgb, return_labels):
-        """one image's (or batch's) views against gt [B, h, w] into `score` -> its labels [B, h, w] or None"""
-        h, w = int(gt.shape[1]), int(gt.shape[2])
-        one = len(vs) == 1 and not vs[0][3]
-        if self.crf_iters > 0:                                # the label map comes from the CRF, not from the predict kernel
-            labels = (self._finish(*vs[0][:3], h, w, rgb, False, False) if one else self._finish_views(vs, h, w, rgb, False, False)).labels
-            return self._count(score, gt, raw_labels, return_labels, labels=labels)
-        if one:
-            return self._count(score, gt, raw_labels, return_labels,
-                               lambda want, kw: hip.seg_score(*vs[0][:3], gt, labels=want, label_dtype=self.label_dtype, **kw)[2])
-        return self._count(score, gt, raw_labels, return_labels,
-                           lambda want, kw: hip.seg_score_views(vs, gt, labels=want, label_dtype=self.label_dtype, **kw)[2])
 
     def evaluate_raw(self, images, label_maps, raw_labels=True, scales=(1.0,), flip=False, max_batch=8, mean=None, std=None,
                      reverse_channels=False, into=None, return_labels=False, slide=None, confusion=False):
@@ -922,39 +895,11 @@ class Segmenter:
         if checked is None:
             return (score, []) if return_labels else score
         gts = [g.to(dev, non_blocking=True).contiguous() for g in gts]
+        imgs, shapes, merges = self._front(checked, sl, plan, max_batch, mean, std, reverse_channels)
         crf, out = self.crf_iters > 0, []
-        if sl is not None and self.slide_views:
-            imgs, shapes, per_image = self._raw_window_views(checked[1], sl, plan, mean, std, reverse_channels)
-            with torch.no_grad():
-                for i, vs in enumerate(per_image):
-                    if crf:                                   # the label map comes from the CRF, not from the predict kernel
-                        r = hip.seg_predict_slide_views(vs, sl[0], sl[1], *shapes[i], self._views_softmax(), probs=True,
-                                                        label_dtype=self.label_dtype)
-                        labels = self._count(score, gts[i][None], raw_labels, return_labels,
-                                             labels=self._crf(r, imgs[i][None].float(), False, False).labels)
-                    else:
-                        labels = self._count(score, gts[i][None], raw_labels, return_labels, lambda want, kw: hip.seg_score_slide_views(
-                            vs, sl[0], sl[1], gts[i][None], self._views_softmax(), labels=want, label_dtype=self.label_dtype, **kw)[2])
-                    out.append(labels[0] if return_labels else None)
-            return (score, out) if return_labels else score
-        if sl is not None:
-            imgs, shapes, per_image = self._raw_windows(checked[1], sl, plan, mean, std, reverse_channels)
-            with torch.no_grad():
-                for i, (scores, hpw, wpw, (oh, ow)) in enumerate(per_image):
-                    if crf:                                   # the label map comes from the CRF, not from the predict kernel
-                        r = hip.seg_predict_windows(scores, hpw, wpw, oh, ow, sl[0], sl[1], *shapes[i], probs=True,
-                                                    label_dtype=self.label_dtype)
-                        labels = self._count(score, gts[i][None], raw_labels, return_labels,
-                                             labels=self._crf(r, imgs[i][None].float(), False, False).labels)
-                    else:
-                        labels = self._count(score, gts[i][None], raw_labels, return_labels, lambda want, kw: hip.seg_score_windows(
-                            scores, hpw, wpw, oh, ow, sl[0], sl[1], gts[i][None], labels=want, label_dtype=self.label_dtype, **kw)[2])
-                    out.append(labels[0] if return_labels else None)
-            return (score, out) if return_labels else score
-        imgs, shapes, per_image = self._raw_views(*checked, max_batch, mean, std, reverse_channels)
         with torch.no_grad():
-            for i, vs in enumerate(per_image):
-                labels = self._score(score, vs, gts[i][None], raw_labels, imgs[i][None].float() if crf else None, return_labels)
+            for i, merge in enumerate(merges):
+                labels = self._count(score, merge, gts[i][None], raw_labels, imgs[i][None].float() if crf else None, return_labels)
                 out.append(None if labels is None else labels[0])
         return (score, out) if return_labels else score
 
@@ -981,6 +926,6 @@ class Segmenter:
             rgb = ((patch_images.float() * 0.5 + 0.5) * 255.0).permute(0, 2, 3, 1).contiguous()
         scores, hp, wp = self.patch_scores(patch_images)
         with torch.no_grad():
-            labels = self._score(score, [(scores, hp, wp, False)], gt.to(patch_images.device).contiguous(), raw_labels, rgb,
-                                 return_labels)
+            labels = self._count(score, self._views_merge([(scores, hp, wp, False)]), gt.to(patch_images.device).contiguous(),
+                                 raw_labels, rgb, return_labels)
         return (score, labels) if return_labels else score
