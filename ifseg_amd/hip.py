@@ -1376,6 +1376,76 @@ def seg_render(labels, image, palette, opacity=0.5, boundary=0, boundary_color=(
     return out
 
 
+# --------------------------------------------------------------------------- confidence-filtered pseudo-labels
+SEG_CONF_BINS = 256                 # bins of the confidence histogram: clamp(floor(conf * 256), 0, 255)
+SEG_CONF_HIST_DIRECT_CLASSES = 64   # == HC_DIRECT_CLASSES (csrc/pseudo.hip): n up to this counts in a direct LDS table, else hashed
+SEG_CONF_HIST_SLOTS = 4096          # == HC_SLOTS: the (label, bin) pairs a workgroup's hashed table holds at most
+SEG_PSEUDO_MAX_CLASSES = 255        # the uint8 output keeps 255 for "ignore"; with raw_labels class c is stored as c + 1: 254
+
+
+def seg_pseudo_max_classes(raw_labels=True):
+    return SEG_PSEUDO_MAX_CLASSES - 1 if raw_labels else SEG_PSEUDO_MAX_CLASSES
+
+
+def _labels_conf(labels, conf, what):
+    assert labels.dtype in (torch.uint8, torch.int16) and labels.is_contiguous(), (what, labels.dtype, labels.stride())
+    assert conf.dtype == torch.float32 and conf.is_contiguous() and conf.shape == labels.shape and conf.device == labels.device, \
+        (what, conf.dtype, tuple(conf.shape), conf.stride(), tuple(labels.shape), conf.device, labels.device)
+    assert 1 <= labels.numel() < 2 ** 31, (what, tuple(labels.shape))
+
+
+def seg_conf_hist(labels, conf, n, hist=None, tally=None):
+    """labels uint8 / int16 [...] (predicted classes), conf fp32 of the same shape -> (hist int64 [n, 256], tally int64 [2]):
+    hist[c, b] = #(label = c and clamp(floor(conf * 256), 0, 255) = b), tally = #labels in [0, n), #labels outside
+    (csrc/pseudo.hip; `predict.confidence_histogram_reference` is the specification).  `hist` / `tally` given: ACCUMULATED
+    into, else fresh zeroed ones.  1 <= n <= 512."""
+    _labels_conf(labels, conf, "seg_conf_hist")
+    assert isinstance(n, int) and 1 <= n <= SEG_PREDICT_MAX_CLASSES, n
+    dev = labels.device
+    if hist is None:
+        hist = torch.zeros(n, SEG_CONF_BINS, dtype=torch.int64, device=dev)
+    if tally is None:
+        tally = torch.zeros(2, dtype=torch.int64, device=dev)
+    assert hist.dtype == torch.int64 and tuple(hist.shape) == (n, SEG_CONF_BINS) and hist.is_contiguous() and hist.device == dev, \
+        (hist.dtype, tuple(hist.shape), hist.device, n)
+    assert tally.dtype == torch.int64 and tuple(tally.shape) == (2,) and tally.is_contiguous() and tally.device == dev, \
+        (tally.dtype, tuple(tally.shape), tally.device)
+    _check(lib().ifseg_seg_conf_hist(_ptr(labels), c_int(labels.element_size()), _ptr(conf), c_ll(labels.numel()), c_int(n),
+                                     _ptr(hist), _ptr(tally), _stream()), "seg_conf_hist")
+    return hist, tally
+
+
+def seg_pseudo(labels, conf, thresholds, n, boundary=0, raw_labels=True, kept=None, out=None):
+    """labels uint8 / int16 [H, W] or [B, H, W], conf fp32 of the same shape, thresholds int32 [n] (bins, 0 .. 256) ->
+    (out uint8 of the labels' shape, kept int64 [2, n]) in one launch (csrc/pseudo.hip): a pixel of label l in [0, n) whose
+    confidence bin is at least thresholds[l] and, with boundary = r in 1..4, that has no other label value within r pixels
+    becomes l + 1 (raw_labels: the label-PNG convention `augment.remap_label` undoes) or l, every other pixel 255.
+    kept[1, c] = #(label = c), kept[0, c] = those kept; `kept` given: ACCUMULATED into.  out: written in place when given
+    (contiguous, at any byte offset of its storage; it must not overlap labels or conf).
+    `predict.pseudo_label_reference` is the specification.  n <= 254 with raw_labels, 255 without."""
+    assert labels.dim() in (2, 3), tuple(labels.shape)
+    _labels_conf(labels, conf, "seg_pseudo")
+    assert isinstance(n, int) and 1 <= n <= seg_pseudo_max_classes(raw_labels), (n, raw_labels)
+    assert isinstance(boundary, int) and 0 <= boundary <= SEG_RENDER_MAX_BOUNDARY, boundary
+    dev = labels.device
+    assert thresholds.dtype == torch.int32 and tuple(thresholds.shape) == (n,) and thresholds.is_contiguous() \
+        and thresholds.device == dev, (thresholds.dtype, tuple(thresholds.shape), thresholds.device, n)
+    if kept is None:
+        kept = torch.zeros(2, n, dtype=torch.int64, device=dev)
+    assert kept.dtype == torch.int64 and tuple(kept.shape) == (2, n) and kept.is_contiguous() and kept.device == dev, \
+        (kept.dtype, tuple(kept.shape), kept.device, n)
+    if out is None:
+        out = torch.empty(labels.shape, dtype=torch.uint8, device=dev)
+    assert out.dtype == torch.uint8 and out.shape == labels.shape and out.is_contiguous() and out.device == dev, \
+        (out.dtype, tuple(out.shape), out.stride(), out.device)
+    assert not _overlap(out, labels) and not _overlap(out, conf), "seg_pseudo: out overlaps the labels or conf"
+    H, W = labels.shape[-2:]
+    _check(lib().ifseg_seg_pseudo(_ptr(labels), c_int(labels.element_size()), _ptr(conf), _ptr(thresholds), c_int(n),
+                                  c_int(labels.numel() // (H * W)), c_int(H), c_int(W), c_int(boundary),
+                                  c_int(1 if raw_labels else 0), _ptr(out), _ptr(kept), _stream()), "seg_pseudo")
+    return out, kept
+
+
 _image_luts = {}        # (mean, std, device) -> fp32 [3, 256] on the device; at most 16 entries
 
 

@@ -24,7 +24,9 @@ against ground truth, stand-alone and in the predict kernel's epilogue: mIoU on 
 confusion matrix of a label map against ground truth, [n, n + 1] with an "outside" column), `image_load` (csrc/imgload.hip: raw uint8 images to
 normalised patch_images, the reference's evaluation transform) and the three ops of sliding-window inference (`image_load_windows`,
 `seg_predict_windows`, `seg_score_windows`: the window batch written directly, and the windows' scores merged into one label
-map in one launch), `seg_render` (csrc/render.hip: the label map coloured over its image, with class contours) and the two of multi-scale + flip over sliding windows (`seg_predict_slide_views`, `seg_score_slide_views`:
+map in one launch), `seg_render` (csrc/render.hip: the label map coloured over its image, with class contours), `seg_conf_hist` / `seg_pseudo`
+(csrc/pseudo.hip: the per-class confidence histogram of a label map, and the label map filtered by per-class thresholds and an
+ignore band along class edges into pseudo-labels for self-training) and the two of multi-scale + flip over sliding windows (`seg_predict_slide_views`, `seg_score_slide_views`:
 K views, each a set of windows, merged in one launch, optionally softmaxed per view as mmseg does) are inference only and
 have no backward; `train_load`
 (csrc/trainload.hip: raw images and label maps of any sizes to a training batch under given records, the reference's training
@@ -911,6 +913,75 @@ def seg_render(labels: torch.Tensor, image: torch.Tensor, palette: torch.Tensor,
 def _(labels, image, palette, opacity, boundary, boundary_color, conf):
     _seg_render_check(labels, image, palette, opacity, boundary, boundary_color, conf)
     return image.new_empty(tuple(labels.shape) + (3,), dtype=torch.uint8)
+
+
+# ----------------------------------------------------------------------------------------------- seg_conf_hist, seg_pseudo
+def _labels_conf_check(op, labels, conf):
+    if labels.dtype not in (torch.uint8, torch.int16):
+        raise ValueError("%s: labels must be uint8 or int16 (what seg_predict gives), got dtype %s" % (op, labels.dtype))
+    if conf.dtype != torch.float32 or conf.shape != labels.shape:
+        raise ValueError("%s: conf must be float32 of the labels' shape %s, got %s %s"
+                         % (op, tuple(labels.shape), conf.dtype, tuple(conf.shape)))
+    if labels.numel() < 1 or labels.numel() >= 2 ** 31:
+        raise ValueError("%s: 1 <= pixels < 2**31, got %s" % (op, tuple(labels.shape)))
+
+
+@custom_op("ifseg::seg_conf_hist", mutates_args=(), device_types="cuda")
+def seg_conf_hist(labels: torch.Tensor, conf: torch.Tensor, n: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """predicted labels (uint8 / int16) with their confidences (fp32, the same shape) (csrc/pseudo.hip) -> (hist int64 [n, 256] =
+    pixels per (label, clamp(floor(conf * 256), 0, 255)), tally int64 [2] = labels inside / outside [0, n)), fresh tensors;
+    `ifseg_amd.predict.confidence_histogram_reference` is the specification.  Counts: not differentiable."""
+    _labels_conf_check("ifseg::seg_conf_hist", labels, conf)
+    if n < 1 or n > hip.SEG_PREDICT_MAX_CLASSES:
+        raise ValueError("ifseg::seg_conf_hist: n = %d classes, the kernel takes 1 .. %d" % (n, hip.SEG_PREDICT_MAX_CLASSES))
+    prev = _stream_scope(labels)
+    try:
+        return hip.seg_conf_hist(labels.contiguous(), conf.contiguous(), n)
+    finally:
+        hip.set_stream(prev)
+
+
+@seg_conf_hist.register_fake
+def _(labels, conf, n):
+    _labels_conf_check("ifseg::seg_conf_hist", labels, conf)
+    if n < 1 or n > hip.SEG_PREDICT_MAX_CLASSES:
+        raise ValueError("ifseg::seg_conf_hist: n = %d classes, the kernel takes 1 .. %d" % (n, hip.SEG_PREDICT_MAX_CLASSES))
+    return labels.new_empty((n, hip.SEG_CONF_BINS), dtype=torch.int64), labels.new_empty((2,), dtype=torch.int64)
+
+
+def _seg_pseudo_check(labels, conf, thresholds, n, boundary, raw_labels):
+    op = "ifseg::seg_pseudo"
+    _labels_conf_check(op, labels, conf)
+    if labels.dim() not in (2, 3):
+        raise ValueError("%s: labels must be [H, W] or [B, H, W], got %s" % (op, tuple(labels.shape)))
+    if n < 1 or n > hip.seg_pseudo_max_classes(raw_labels):
+        raise ValueError("%s: n = %d classes, the uint8 output holds 1 .. %d with raw_labels=%s"
+                         % (op, n, hip.seg_pseudo_max_classes(raw_labels), raw_labels))
+    if thresholds.dtype != torch.int32 or tuple(thresholds.shape) != (n,):
+        raise ValueError("%s: thresholds must be int32 [%d], got %s %s" % (op, n, thresholds.dtype, tuple(thresholds.shape)))
+    if not 0 <= boundary <= hip.SEG_RENDER_MAX_BOUNDARY:
+        raise ValueError("%s: boundary must be in 0 .. %d, got %d" % (op, hip.SEG_RENDER_MAX_BOUNDARY, boundary))
+
+
+@custom_op("ifseg::seg_pseudo", mutates_args=(), device_types="cuda")
+def seg_pseudo(labels: torch.Tensor, conf: torch.Tensor, thresholds: torch.Tensor, n: int, boundary: int,
+               raw_labels: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """the confidence filter of self-training (csrc/pseudo.hip): labels uint8 / int16 [.., H, W], conf fp32 of that shape,
+    thresholds int32 [n] in bins -> (the pseudo-label map uint8 [.., H, W]: class + 1 with raw_labels, else class, 255 where
+    the pixel is not kept; kept int64 [2, n]: kept and predicted pixels per class), fresh tensors;
+    `ifseg_amd.predict.pseudo_label_reference` is the specification.  Integer outputs: not differentiable."""
+    _seg_pseudo_check(labels, conf, thresholds, n, boundary, raw_labels)
+    prev = _stream_scope(labels)
+    try:
+        return hip.seg_pseudo(labels.contiguous(), conf.contiguous(), thresholds.contiguous(), n, boundary, raw_labels)
+    finally:
+        hip.set_stream(prev)
+
+
+@seg_pseudo.register_fake
+def _(labels, conf, thresholds, n, boundary, raw_labels):
+    _seg_pseudo_check(labels, conf, thresholds, n, boundary, raw_labels)
+    return labels.new_empty(tuple(labels.shape), dtype=torch.uint8), labels.new_empty((2, n), dtype=torch.int64)
 
 
 # ----------------------------------------------------------------------------------------------- image_load

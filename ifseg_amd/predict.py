@@ -76,6 +76,20 @@ PIL): parity is exact to `render_reference`, which equals the demo's formula at 
 
     pics = seg.render_raw(photos, opacity=0.5, boundary=1)          # [RenderResult(picture uint8 [H_i, W_i, 3], labels, conf)]
 
+Pseudo-labels for self-training (adapting the image-free model to unlabeled photographs of the target domain, the CBST /
+MaskCLIP+ recipe): `seg.pseudo_label_raw(photos, keep=0.5, boundary=1)` is `segment_raw(return_conf=True)`, one launch of
+`hip.seg_conf_hist` per image (csrc/pseudo.hip: the per-class histogram of the winning probability, into a
+`ConfidenceHistogram` that can span a data set), the per-class thresholds from it on the device (`pseudo_thresholds`: a fixed
+threshold, or the most confident share of every class) and one launch of `hip.seg_pseudo` per image, which writes the uint8
+label map `task.train_sample` takes: kept pixels carry their class, everything else -- below its class's threshold, or within
+`boundary` pixels of a class edge -- is 255.  `confidence_histogram_reference` and `pseudo_label_reference` are the
+specifications, in integers.  `task.self_train_sample(model, photos, first_ordinal, keep=0.5)` is both steps.
+
+    hist = ConfidenceHistogram(seg.n, device)
+    for photos in batches: seg.pseudo_label_raw(photos, hist=hist)                 # pass 1: what "confident" means per class
+    t = hist.thresholds(keep=0.5, floor=0.3)
+    out = seg.pseudo_label_raw(photos, thresholds=t, boundary=1)                   # [PseudoLabelResult(labels, predicted, conf, kept)]
+
 How the four settings share their code: a front (`Segmenter._raw_views` without `slide`, `_raw_window_views` with it, for one
 view or many) runs the loads and the forwards and hands back one `_Merge` per image -- the setting's last launch, as its
 `hip.seg_predict*` and its `hip.seg_score*`, bound to the image's scores and geometry.  `Segmenter._label` finishes an image
@@ -312,6 +326,158 @@ def render_reference(labels, image, palette, opacity=0.5, boundary=0, boundary_c
             edge[(..., *here)] |= lab[(..., *here)] != lab[(..., *there)]
     out = torch.where(edge[..., None], torch.tensor(color, dtype=torch.int32), out)
     return out.to(torch.uint8)
+
+
+CONF_BINS = hip.SEG_CONF_BINS
+
+
+def conf_bin(conf):
+    """fp32 confidences -> their histogram bin, int64 of the same shape: clamp(floor(conf * 256), 0, 255) evaluated in fp32
+    (the product is exact), NaN -> 0 (the kernels' fmaxf(NaN, 0) = 0, as `render_reference`'s q), +inf -> 255.  Runs on any
+    device."""
+    conf = torch.as_tensor(conf)
+    if conf.dtype != torch.float32:
+        raise ValueError("conf_bin: conf must be float32, got %s" % conf.dtype)
+    q = torch.floor(conf * 256.0)
+    return torch.where(torch.isnan(q), torch.zeros_like(q), q).clamp(0.0, 255.0).long()
+
+
+def _labels_conf(what, labels, conf, n):
+    labels, conf = torch.as_tensor(labels), torch.as_tensor(conf)
+    if labels.dtype.is_floating_point or labels.dtype == torch.bool:
+        raise ValueError("%s: labels must be integer, got %s" % (what, labels.dtype))
+    if conf.dtype != torch.float32 or conf.shape != labels.shape:
+        raise ValueError("%s: conf must be float32 %s, got %s %s" % (what, tuple(labels.shape), conf.dtype, tuple(conf.shape)))
+    if int(n) < 1:
+        raise ValueError("%s: n = %d classes" % (what, n))
+    return labels.long(), conf.to(labels.device)
+
+
+def confidence_histogram_reference(labels, conf, n):
+    """Specification of hip.seg_conf_hist: labels integer [...] (predicted classes), conf fp32 of the same shape ->
+    (hist int64 [n, 256], tally int64 [2]): hist[c, b] = #(label = c and conf_bin(conf) = b), tally[0] = #labels in [0, n),
+    tally[1] = #labels outside (255, a negative int16).  hist.sum() == tally[0].  Runs on any device."""
+    lab, conf = _labels_conf("confidence_histogram_reference", labels, conf, n)
+    lab, b = lab.reshape(-1), conf_bin(conf).reshape(-1)
+    inside = (lab >= 0) & (lab < n)
+    hist = torch.bincount(lab[inside] * CONF_BINS + b[inside], minlength=n * CONF_BINS).reshape(n, CONF_BINS)
+    return hist, torch.stack([inside.sum(), (~inside).sum()])
+
+
+def pseudo_thresholds(hist, keep=1.0, floor=0.0):
+    """The per-class confidence thresholds of self-training from a confidence histogram int64 [n, 256] -> int32 [n], values in
+    0 .. 256 (bins: a pixel of class c passes iff conf_bin(conf) >= t_c), on hist's device with no host round trip.  In integers:
+
+      N_c = sum_b hist[c, b],  K_c = (N_c round(keep * 65536)) >> 16,  S_c(t) = sum_{b >= t} hist[c, b]
+      q_c = #{t in 0 .. 255 : S_c(t) > K_c}: the smallest t that keeps at most the `keep` share of class c (a bin that ties is
+            rejected whole); t_c = max(q_c, ceil(floor * 256))
+
+    keep=1, floor=tau is the fixed threshold (every kept pixel has conf >= tau); keep < 1 the class-balanced one (CBST: the
+    most confident share of every class, so rare classes are not starved by a global threshold); a class without pixels
+    gets the floor.  keep or floor outside [0, 1]: ValueError."""
+    import math
+    if not isinstance(keep, (int, float)) or isinstance(keep, bool) or not 0.0 <= keep <= 1.0:
+        raise ValueError("pseudo_thresholds: keep must be a number in [0, 1], got %r" % (keep,))
+    if not isinstance(floor, (int, float)) or isinstance(floor, bool) or not 0.0 <= floor <= 1.0:
+        raise ValueError("pseudo_thresholds: floor must be a number in [0, 1], got %r" % (floor,))
+    if not torch.is_tensor(hist) or hist.dtype != torch.int64 or hist.dim() != 2 or hist.shape[1] != CONF_BINS:
+        raise ValueError("pseudo_thresholds: hist must be int64 [n, %d], got %s" % (
+            CONF_BINS, (hist.dtype, tuple(hist.shape)) if torch.is_tensor(hist) else type(hist)))
+    K = (hist.sum(1) * int(round(float(keep) * 65536.0))) >> 16
+    S = hist.flip(1).cumsum(1).flip(1)
+    q = (S > K[:, None]).sum(1)
+    return q.clamp_min(int(math.ceil(float(floor) * 256.0))).to(torch.int32)
+
+
+def _boundary_arg(what, boundary):
+    if not isinstance(boundary, int) or isinstance(boundary, bool) or not 0 <= boundary <= hip.SEG_RENDER_MAX_BOUNDARY:
+        raise ValueError("%s: boundary must be an int in 0 .. %d (the ignore band's half width in pixels), got %r"
+                         % (what, hip.SEG_RENDER_MAX_BOUNDARY, boundary))
+    return boundary
+
+
+def pseudo_label_reference(labels, conf, thresholds, n, boundary=0, raw_labels=True):
+    """Specification of hip.seg_pseudo, in integers: labels integer [H, W] (or [B, H, W]), conf fp32 of that shape, thresholds
+    integer [n] (bins) -> (out uint8 [.., H, W], kept int64 [2, n]).  A pixel of label l is kept iff
+
+      0 <= l < n,  conf_bin(conf) >= thresholds[l],  and with boundary = r (0 .. 4) no pixel INSIDE the image with |dx| <= r and
+      |dy| <= r carries a different label value: `render_reference`'s contour predicate, on the labels given (the predicted
+      ones), not on the filtered ones.
+
+    A kept pixel becomes l + 1 with raw_labels (the label-PNG convention `augment.remap_label` undoes) or l without; every
+    other pixel 255, which both conventions ignore.  kept[1, c] = #(label = c), kept[0, c] = those that were kept.
+    n <= 254 with raw_labels, n <= 255 without (ValueError).  Runs on any device."""
+    r = _boundary_arg("pseudo_label_reference", boundary)
+    lab, conf = _labels_conf("pseudo_label_reference", labels, conf, n)
+    if lab.dim() not in (2, 3):
+        raise ValueError("pseudo_label_reference: labels must be [H, W] or [B, H, W], got %s" % (tuple(lab.shape),))
+    if n > hip.seg_pseudo_max_classes(raw_labels):
+        raise ValueError("pseudo_label_reference: n = %d classes, the uint8 output holds at most %d with raw_labels=%s"
+                         % (n, hip.seg_pseudo_max_classes(raw_labels), bool(raw_labels)))
+    thr = torch.as_tensor(thresholds)
+    if thr.dtype.is_floating_point or thr.dtype == torch.bool or tuple(thr.shape) != (n,):
+        raise ValueError("pseudo_label_reference: thresholds must be integer [%d], got %s %s" % (n, thr.dtype, tuple(thr.shape)))
+    thr = thr.long().to(lab.device)
+    inside = (lab >= 0) & (lab < n)
+    cls = lab.clamp(0, n - 1)
+    H, W = lab.shape[-2:]
+    edge = torch.zeros_like(inside)
+    for dy in range(-r, r + 1):
+        for dx in range(-r, r + 1):
+            if abs(dy) >= H or abs(dx) >= W:
+                continue                                   # no pixel of the image has this neighbour
+            here = (slice(max(-dy, 0), H - max(dy, 0)), slice(max(-dx, 0), W - max(dx, 0)))
+            there = (slice(max(dy, 0), H - max(-dy, 0)), slice(max(dx, 0), W - max(-dx, 0)))
+            edge[(..., *here)] |= lab[(..., *here)] != lab[(..., *there)]
+    keep = inside & ~edge & (conf_bin(conf) >= thr[cls])
+    out = torch.where(keep, cls + (1 if raw_labels else 0), torch.full_like(cls, 255)).to(torch.uint8)
+    kept = torch.stack([torch.bincount(cls[keep], minlength=n), torch.bincount(cls[inside], minlength=n)])
+    return out, kept
+
+
+class PseudoLabelResult(NamedTuple):
+    labels: torch.Tensor                       # [H, W] uint8: the pseudo-label map `train_sample` takes (255 = ignored)
+    predicted: torch.Tensor                    # [H, W] uint8 / int16: what `segment_raw` gave
+    conf: torch.Tensor                         # [H, W] fp32: the winning class's probability
+    kept: torch.Tensor                         # [2, n] int64: per class the kept and the predicted pixels of this image
+
+
+class ConfidenceHistogram:
+    """`confidence_histogram_reference`'s counters on the device, summed over everything counted into them: `hist` int64
+    [n, 256] (class, confidence bin) and `tally` int64 [2].  `hip.seg_conf_hist` adds to these tensors in place, so one
+    histogram can span a whole data set (`Segmenter.pseudo_label_raw(..., hist=h)`) and the thresholds be balanced over it."""
+
+    def __init__(self, n, device=None, hist=None, tally=None):
+        self.n = int(n)
+        self.hist = torch.zeros(self.n, CONF_BINS, dtype=torch.int64, device=device) if hist is None else hist
+        self.tally = torch.zeros(2, dtype=torch.int64, device=self.hist.device) if tally is None else tally
+        if self.hist.dtype != torch.int64 or tuple(self.hist.shape) != (self.n, CONF_BINS) or self.tally.dtype != torch.int64 \
+                or tuple(self.tally.shape) != (2,) or self.hist.device != self.tally.device:
+            raise ValueError("ConfidenceHistogram: hist must be int64 [%d, %d] and tally int64 [2] on one device, got %s %s and %s %s"
+                             % (self.n, CONF_BINS, self.hist.dtype, tuple(self.hist.shape), self.tally.dtype, tuple(self.tally.shape)))
+
+    def add_(self, other):
+        if other.n != self.n:
+            raise ValueError("ConfidenceHistogram.add_: %d classes against %d" % (other.n, self.n))
+        self.hist += other.hist.to(self.hist.device)
+        self.tally += other.tally.to(self.tally.device)
+        return self
+
+    def thresholds(self, keep=1.0, floor=0.0):
+        """`pseudo_thresholds(self.hist, keep, floor)`: int32 [n] on the device, no host round trip"""
+        return pseudo_thresholds(self.hist, keep, floor)
+
+    def summary(self):
+        """-> {"pixels", "outside", "share": [n], "median_bin": [n]}: the labels inside / outside [0, n), per class its share of
+        the inside pixels (rounded to 4 digits; NaN without pixels) and the bin of its median confidence -- the smallest b with
+        2 sum_{b' <= b} hist[c, b'] >= N_c, None for a class without pixels.  One host round trip."""
+        N = self.hist.sum(1)
+        median = (2 * self.hist.cumsum(1) < N[:, None]).sum(1)
+        flat = torch.cat([N, median, self.tally]).tolist()
+        n, pixels = self.n, flat[-2]
+        return {"pixels": int(pixels), "outside": int(flat[-1]),
+                "share": [round(flat[c] / pixels, 4) if pixels else float("nan") for c in range(n)],
+                "median_bin": [int(flat[n + c]) if flat[c] else None for c in range(n)]}
 
 
 class SegmentationScore:
@@ -826,6 +992,77 @@ class Segmenter:
             return [RenderResult(hip.seg_render(r.labels, im.contiguous(), palette, opacity, boundary, tuple(boundary_color),
                                                 conf=r.conf if fade_by_conf else None), r.labels, r.conf if fade_by_conf else None)
                     for im, r in zip(imgs, res)]
+
+    # -- pseudo-labels for self-training ---------------------------------------------------
+    def _conf_setting(self, sl):
+        """-> None where `segment_raw(return_conf=True)`'s conf is a probability in this construction (sl: what `_check_slide`
+        gave), else the name of the setting that makes it something else"""
+        if self.crf_iters > 0 or self.smooth_iters > 0 or self.upsample == "probs":
+            return None         # the CRF's marginal; the smoothing's probabilities; the per-patch softmax, merged linearly
+        if self.slide_views and sl is not None:
+            return None         # `_slide_merge` asks the launch for the softmax per view behind the merge
+        return "upsample=%r (conf is the winning class's resized raw logit)" % (self.upsample,)
+
+    def pseudo_label_raw(self, images, keep=1.0, floor=0.0, boundary=0, raw_labels=True, hist=None, thresholds=None,
+                         scales=(1.0,), flip=False, slide=None, max_batch=8, mean=None, std=None, reverse_channels=False):
+        """Unlabeled photographs -> label maps `task.train_sample` accepts, holding only the pixels the model is confident
+        of: the self-training step (CBST, MaskCLIP+) that adapts the image-free model to a target domain, on the device ->
+        a list of `PseudoLabelResult(labels uint8 [H_i, W_i], predicted, conf, kept)` in input order.
+
+        images, scales, flip, slide, max_batch, mean, std, reverse_channels: as in `segment_raw`.  In this order:
+          1. `segment_raw(..., return_conf=True)`, unchanged: the label map and the winning class's probability per image;
+          2. one launch of `hip.seg_conf_hist` per image adds its (class, confidence bin) pairs to `hist` -- a
+             `ConfidenceHistogram` to accumulate into, so that the thresholds are balanced over a whole data set across
+             calls, or None for a fresh one that spans this call's images;
+          3. `hist.thresholds(keep, floor)` (`pseudo_thresholds` states the rule; on the device): keep=1, floor=tau is the fixed
+             threshold tau, keep < 1 keeps the most confident `keep` share of every class.  thresholds: int32 [n] bins given by
+             the caller instead (a previous pass's): steps 2 and 3 are skipped, and keep, floor and hist are not read;
+          4. one launch of `hip.seg_pseudo` per image: a pixel is kept where its class's threshold is met and, with
+             boundary = r in 1 .. 4, no other class lies within r pixels (`pseudo_label_reference` states the rule); kept pixels
+             become class + 1 with raw_labels (what a `TrainTransform(raw_labels=True)`, the default, takes), else the class id;
+             every other pixel 255, ignored by both.
+        Nothing synchronises with the host.  Between the passes every image's labels and conf stay alive: 5 bytes per pixel
+        (6 with int16 labels) for the whole call, which bounds the images of one call, not of a data set.
+
+        The confidence must be a probability: upsample="probs", the smoothing, the CRF, or `slide_views` sliding (the softmax
+        inside the launch).  Raw logits (upsample="logits" elsewhere) are a ValueError naming the setting, as are more than
+        254 classes (255 without raw_labels) for the uint8 map, before anything is launched."""
+        what = "Segmenter.pseudo_label_raw"
+        _boundary_arg(what, boundary)
+        if self.n > hip.seg_pseudo_max_classes(raw_labels):
+            raise ValueError("%s: the uint8 pseudo-label map holds at most %d classes with raw_labels=%s, the model has n = %d"
+                             % (what, hip.seg_pseudo_max_classes(raw_labels), bool(raw_labels), self.n))
+        sl = self._check_slide("pseudo_label_raw", slide, scales, flip)
+        bad = self._conf_setting(sl)
+        if bad is not None:
+            raise ValueError("%s: the confidence must be a probability, this Segmenter has %s; use upsample='probs', the "
+                             "smoothing, the CRF, or slide_views with slide" % (what, bad))
+        dev = next(self.model.parameters()).device
+        if thresholds is not None:
+            if not torch.is_tensor(thresholds) or thresholds.dtype != torch.int32 or tuple(thresholds.shape) != (self.n,):
+                raise ValueError("%s: thresholds must be an int32 [%d] tensor of bins, got %s" % (
+                    what, self.n, (thresholds.dtype, tuple(thresholds.shape)) if torch.is_tensor(thresholds) else type(thresholds)))
+        else:
+            pseudo_thresholds(torch.zeros(1, CONF_BINS, dtype=torch.int64), keep, floor)          # keep and floor, on the host
+            if hist is None:
+                hist = ConfidenceHistogram(self.n, dev)
+            elif not isinstance(hist, ConfidenceHistogram) or hist.n != self.n or hist.hist.device != dev:
+                raise ValueError("%s: hist must be a ConfidenceHistogram of %d classes on %s" % (what, self.n, dev))
+        res = self.segment_raw(images, max_batch=max_batch, mean=mean, std=std, reverse_channels=reverse_channels, return_conf=True,
+                               scales=scales, flip=flip, slide=slide)
+        with torch.no_grad():
+            pairs = [(r.labels.contiguous(), r.conf.contiguous()) for r in res]
+            if thresholds is None:
+                for labels, conf in pairs:
+                    hip.seg_conf_hist(labels, conf, self.n, hist=hist.hist, tally=hist.tally)
+                thresholds = hist.thresholds(keep, floor)
+            else:
+                thresholds = thresholds.to(dev).contiguous()
+            out = []
+            for labels, conf in pairs:
+                pseudo, kept = hip.seg_pseudo(labels, conf, thresholds, self.n, boundary, bool(raw_labels))
+                out.append(PseudoLabelResult(pseudo, labels, conf, kept))
+        return out
 
     # -- scoring against ground truth -----------------------------------------------------
     def _score_into(self, what, into, dev, confusion=False):

@@ -222,6 +222,30 @@ class SegmentationTask(TaskBase):
         seg = self.build_segmenter(model, **{k: kw.pop(k) for k in ctor if k in kw})
         return seg.render_raw(images, **kw)
 
+    def pseudo_label_raw(self, model, images, **kw):
+        """unlabeled raw uint8 images -> a list of `PseudoLabelResult(labels, predicted, conf, kept)`, label maps that hold only
+        the pixels the model is confident of: `build_segmenter(model, ...).pseudo_label_raw(images, ...)`.  Keywords of the
+        Segmenter's constructor go to it, the others to `Segmenter.pseudo_label_raw`."""
+        ctor = ("category_token_ids", "prompt_ids", "upsample", "smooth_iters", "smooth_topk", "temperature", "crf_iters",
+                "full_context_alignment", "label_dtype", "slide_views")
+        seg = self.build_segmenter(model, **{k: kw.pop(k) for k in ctor if k in kw})
+        return seg.pseudo_label_raw(images, **kw)
+
+    def self_train_sample(self, model, images, first_ordinal, **kw):
+        """One batch of self-training on unlabeled photographs: `pseudo_label_raw(model, images, **kw)` and then
+        `train_sample(images, [r.labels ...], first_ordinal)` on the model's own confident pixels -> the batch
+        `Trainer.train_step` takes; every pixel that was not kept carries the ignore class.  `raw_labels` (default: the
+        train transform's) must agree with the transform's, else the classes would shift by one: ValueError.  No teacher or
+        EMA copy is kept here: `model` is whichever weights the caller wants the labels from."""
+        tf = getattr(self, "train_transform", None) or self.build_train_transform()
+        raw = kw.setdefault("raw_labels", tf.raw_labels)
+        if bool(raw) != tf.raw_labels:
+            raise ValueError("self_train_sample: raw_labels=%r, but the train transform was built with raw_labels=%r"
+                             % (raw, tf.raw_labels))
+        images = [images] if torch.is_tensor(images) else list(images)
+        res = self.pseudo_label_raw(model, images, **kw)
+        return self.train_sample(images, [r.labels.to(tf.device) for r in res], first_ordinal)
+
     def inference_step(self, generator, models, sample, prefix_tokens=None, constraints=None):
         """fairseq_task.py `inference_step` -> [B, max_len] seg-class indices of the best beam (segmentation.py:266-268)"""
         with torch.no_grad():

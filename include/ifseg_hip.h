@@ -754,6 +754,34 @@ int ifseg_seg_predict_slide_views_staging(int max_bytes);
 int ifseg_seg_render(const void* labels, int label_bytes, const void* image, const void* palette, int n, const float* conf,
                      int B, int H, int W, int alpha, int boundary, int boundary_rgb, void* out, void* stream);
 
+/* ---- confidence-filtered pseudo-labels (Segmenter.pseudo_label_raw: self-training on unlabeled photographs, the CBST /
+ * MaskCLIP+ recipe; the reference has no counterpart) ----  Everything is integer: bin(conf) = clamp(floor(conf * 256), 0, 255)
+ * in fp32 (the product is exact), NaN -> 0 (fmaxf(NaN, 0) = 0), +inf -> 255.  ifseg_amd/predict.py states the rules
+ * (confidence_histogram_reference, pseudo_thresholds, pseudo_label_reference); csrc/pseudo.hip.
+ *
+ * ifseg_seg_conf_hist counts npix predicted labels (uint8, label_bytes 1, or int16, 2; any element alignment) with their
+ * confidences conf fp32 [npix]: hist uint64 [n][256] += #(label = c and bin(conf) = b), tally uint64 [2] += #labels in [0, n),
+ * #labels outside.  Both are ADDED to and never cleared; integer sums, exact and bit-reproducible.  A workgroup counts in a
+ * private LDS table -- the histogram itself up to n = 64, a hashed table of 4096 (label, bin) pairs above, a pair that finds no
+ * slot adding to global memory directly -- and only the pairs it met leave it, one 64-bit atomic each.  NULL labels / conf /
+ * hist / tally, label_bytes outside {1, 2}, n outside 1..512, an int16 pointer at an odd address, conf not 4-byte aligned, hist
+ * or tally not 8-byte aligned: IFSEG_ERR_BAD_ARG; npix < 1 or >= 2^31: IFSEG_ERR_BAD_SHAPE; nothing is launched on a refusal. */
+int ifseg_seg_conf_hist(const void* labels, int label_bytes, const float* conf, long long npix, int n,
+                        unsigned long long* hist, unsigned long long* tally, void* stream);
+/* ifseg_seg_pseudo filters labels [B, H, W] (uint8 / int16) by conf fp32 [B, H, W] into out uint8 [B, H, W], one launch: a
+ * pixel of label l is KEPT iff 0 <= l < n, bin(conf) >= thresholds[l] (int32 [n] on the device, 0 keeps every bin, 256 none)
+ * and, with boundary = r (0..4), no pixel INSIDE the image at |dx| <= r and |dy| <= r carries a different label value
+ * (ifseg_seg_render's contour predicate, on the labels given, not on the filtered ones).  A kept pixel becomes l + 1 with
+ * raw_labels != 0 (the label-PNG convention ifseg_train_draw / ifseg_train_load undo), l without; every other pixel 255.
+ * kept uint64 [2][n] is ADDED to: kept[1][c] += #(label = c), kept[0][c] += those that were kept; one 64-bit atomic per
+ * workgroup and non-zero entry.  out may sit at any byte address with rows of W bytes; plain per-lane byte stores, nothing
+ * outside out's B H W bytes is written.  out must not overlap labels (the caller's duty).
+ * NULL labels / conf / thresholds / out / kept, label_bytes outside {1, 2}, int16 labels at an odd address, conf or thresholds
+ * not 4-byte aligned, kept not 8-byte aligned, n outside 1..254 (1..255 with raw_labels == 0), boundary outside 0..4:
+ * IFSEG_ERR_BAD_ARG; B, H, W < 1 or B*H*W >= 2^31: IFSEG_ERR_BAD_SHAPE.  Nothing is launched on a refusal. */
+int ifseg_seg_pseudo(const void* labels, int label_bytes, const float* conf, const int* thresholds, int n, int B, int H, int W,
+                     int boundary, int raw_labels, void* out, unsigned long long* kept, void* stream);
+
 /* ---- raw images and raw label maps in, a training batch out (ifseg_amd/augment.py is the specification, bit for bit; the
  * reference's training transform, segmentation_dataset.py:157-163, 239-251: Resize(ratio_range), RandomCrop(cat_max_ratio 0.75),
  * RandomFlip, PhotoMetricDistortion, Normalize) ----
