@@ -877,6 +877,29 @@ def adam_step(p32, g, m, v, p16, lr, beta1, beta2, eps, wd, step, grad_scale=1.0
                                  c_float(grad_scale), c_float(max_norm), _ptr(sumsq), _ptr(overflow), _ptr(hyper), _stream()), "adam")
 
 
+def adam_ema_step(p32, g, m, v, p16, e32, e16, lr, beta1, beta2, eps, wd, step, ema_decay, ema_rest, grad_scale=1.0,
+                  max_norm=0.0, sumsq=None, overflow=None, hyper=None):
+    """`adam_step` with the teacher (e32 fp32, e16 bf16) stepped towards the new bf16 weights in the same launch
+    (ifseg_amd/ema.py: e32 = fma(ema_rest, p16, round32(e32 * ema_decay))); `hyper` has six floats here, the last two
+    override (ema_decay, ema_rest); (1, 0) leaves the teacher alone"""
+    from .ema import check_arenas
+    check_arenas("adam_ema_step", p32, p16, e32, e16)
+    if hyper is not None and hyper.numel() < 6:
+        raise ValueError("adam_ema_step: hyper needs six floats, got %d" % hyper.numel())
+    _check(lib().ifseg_adam_ema_step(_ptr(p32), _ptr(g), _ptr(m), _ptr(v), _ptr(p16), _ptr(e32), _ptr(e16), c_ll(p32.numel()),
+                                     c_float(lr), c_float(beta1), c_float(beta2), c_float(eps), c_float(wd), c_int(step),
+                                     c_float(grad_scale), c_float(max_norm), _ptr(sumsq), _ptr(overflow), _ptr(hyper),
+                                     c_float(ema_decay), c_float(ema_rest), _stream()), "adam_ema")
+
+
+def ema_swap(p32, p16, e32, e16):
+    """p32 <-> e32 and p16 <-> e16 in place (one launch, no temporary); overlapping ranges, a wrong dtype or unequal lengths:
+    ValueError"""
+    from .ema import check_arenas
+    n = check_arenas("ema_swap", p32, p16, e32, e16)
+    _check(lib().ifseg_ema_swap(_ptr(p32), _ptr(p16), _ptr(e32), _ptr(e16), c_ll(n), _stream()), "ema_swap")
+
+
 def rel_gather(table, idx, out):
     n, H = idx.numel(), table.shape[1]
     _check(lib().ifseg_rel_gather(_ptr(table), _ptr(idx), _ptr(out), c_int(n), c_int(H), _stream()), "rel_gather")

@@ -11,6 +11,7 @@ section 2.1): ``load_dataset`` refuses; samples for the bundled harness are synt
 (SURVEY.md 8d), and ``train_sample`` turns decoded images and label maps into a batch of that layout through the
 training transform of the pipeline (ifseg_amd/augment.py, csrc/trainload.hip).
 """
+import contextlib
 import os
 from dataclasses import dataclass, field
 from typing import Optional
@@ -231,19 +232,27 @@ class SegmentationTask(TaskBase):
         seg = self.build_segmenter(model, **{k: kw.pop(k) for k in ctor if k in kw})
         return seg.pseudo_label_raw(images, **kw)
 
-    def self_train_sample(self, model, images, first_ordinal, **kw):
+    def self_train_sample(self, model, images, first_ordinal, trainer=None, **kw):
         """One batch of self-training on unlabeled photographs: `pseudo_label_raw(model, images, **kw)` and then
         `train_sample(images, [r.labels ...], first_ordinal)` on the model's own confident pixels -> the batch
         `Trainer.train_step` takes; every pixel that was not kept carries the ignore class.  `raw_labels` (default: the
-        train transform's) must agree with the transform's, else the classes would shift by one: ValueError.  No teacher or
-        EMA copy is kept here: `model` is whichever weights the caller wants the labels from."""
+        train transform's) must agree with the transform's, else the classes would shift by one: ValueError.
+        `trainer`: the Trainer of `model`.  With `Trainer(store_ema=True)` the labels come from its teacher -- the averaged
+        weights, inside `trainer.ema_weights()` -- instead of the weights being trained (mean teacher; the remedy for the
+        confirmation bias of labelling with the student).  Without `trainer`, or with one that keeps no teacher, `model` labels
+        as it stands.  Not built: `ema_seed_model`, and a teacher for the fairseq plugin's own trainer (its `EMA` deep-copies
+        the model, which is untested with the arena-backed parameters)."""
         tf = getattr(self, "train_transform", None) or self.build_train_transform()
         raw = kw.setdefault("raw_labels", tf.raw_labels)
         if bool(raw) != tf.raw_labels:
             raise ValueError("self_train_sample: raw_labels=%r, but the train transform was built with raw_labels=%r"
                              % (raw, tf.raw_labels))
         images = [images] if torch.is_tensor(images) else list(images)
-        res = self.pseudo_label_raw(model, images, **kw)
+        teacher = trainer is not None and getattr(trainer, "store_ema", False)
+        if teacher and trainer.model is not model:
+            raise ValueError("self_train_sample: `trainer` trains another model than the one given")
+        with trainer.ema_weights() if teacher else contextlib.nullcontext():
+            res = self.pseudo_label_raw(model, images, **kw)
         return self.train_sample(images, [r.labels.to(tf.device) for r in res], first_ordinal)
 
     def inference_step(self, generator, models, sample, prefix_tokens=None, constraints=None):

@@ -12,6 +12,9 @@ MI355X realisation: gradients live in one flat bf16 arena (engine.g16); RCCL all
 is issued per layer slice from inside the backward (engine.grad_ready_hook) so it rides
 the xGMI links while the remaining backward kernels run; scaling, clipping, Adam and the
 bf16 write-back are ONE kernel over the arena with the norm kept on the device.
+
+store_ema (trainer.py:270, 412, 964-976 -> fairseq/models/ema/ema.py): an averaged copy of the trainable weights, stepped by
+the SAME launch (hip.adam_ema_step; ifseg_amd/ema.py is its specification) -- see `Trainer.__init__` and `ema_weights`.
 """
 import contextlib
 import math
@@ -232,7 +235,20 @@ class ArenaReducer:
 
 class Trainer:
     def __init__(self, model, criterion, task, lr=5e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.1,
-                 clip_norm=1.0, max_update=2000, min_lr=0.0, seed=1, device=None, lazy_logs=False):
+                 clip_norm=1.0, max_update=2000, min_lr=0.0, seed=1, device=None, lazy_logs=False,
+                 store_ema=False, ema_decay=0.9999, ema_start_update=0, ema_update_freq=1):
+        """store_ema / ema_decay / ema_start_update / ema_update_freq: fairseq's EMAConfig names and defaults; `ema_fp32` is
+        always on (an fp32 teacher `ema.e32` whose bf16 rounding `ema.e16` is what the engine computes with after a swap), and
+        `ema_seed_model` is not built (checkpoint files are out of scope: `load_ema_state_dict` takes its place).  After every
+        update of `ema_update_freq` the teacher moves towards the ROUNDED bf16 weights with decay
+        `ema_decay_at(num_updates + 1, ...)` -- a copy before `ema_start_update` -- inside the optimizer launch.
+        The teacher is seeded as a copy of the student here (after the rank-0 broadcast) and once more right before the first
+        optimizer launch unless something has loaded it: whatever the criterion's lazy initialisation wrote into trainable
+        embeddings during the first forward is then in the teacher.  fairseq deep-copies the model at construction instead; the
+        two differ in that corner only.
+        The frequency counter (fairseq's `update_freq_counter`) lives on the host and also advances on an update that the
+        kernel skipped for a non-finite gradient norm: the host learns of that one step late (`check_overflow`), and the run is
+        meant to be restarted then."""
         self.model, self.criterion, self.task = model, criterion, task
         self.lr0, self.betas, self.eps, self.wd, self.clip = lr, betas, eps, weight_decay, clip_norm
         self.max_update, self.min_lr, self.seed = max_update, min_lr, seed
@@ -280,6 +296,10 @@ class Trainer:
                     dist.broadcast(t, 0)
             eng._pack_resnet()
             eng.refresh_frozen()
+        self.store_ema, self.ema, self._ema_dr, self._ema_inside = bool(store_ema), None, None, False
+        if self.store_ema:
+            from .ema import ArenaEMA
+            self.ema = ArenaEMA(self.p32, eng.p16[:n], ema_decay, ema_start_update, ema_update_freq)
 
     # -- DDP over the flat arena ---------------------------------------------------------
     def _on_grads_ready(self, prefix):
@@ -399,14 +419,18 @@ class Trainer:
     # -- steps ------------------------------------------------------------------------------
     def _upload_hyper(self, lr, step, gscale):
         """{lr, 1 - beta1^step, 1 - beta2^step, grad_scale} -> device (async copy from a ring of pinned rows): what a
-        captured step's Adam kernel reads on replay"""
+        captured step's Adam kernel reads on replay.  With store_ema two more: this update's {ema_decay, 1 - ema_decay}, or
+        {1, 0} -- the teacher is left alone -- on an off-update of ema_update_freq."""
+        w = 4 if self.ema is None else 6
         if self._hyper is None:
-            self._hyper = torch.zeros(4, dtype=torch.float32, device=self.device)
-            self._hyper_pin = torch.zeros(64, 4, dtype=torch.float32).pin_memory()
+            self._hyper = torch.zeros(w, dtype=torch.float32, device=self.device)
+            self._hyper_pin = torch.zeros(64, w, dtype=torch.float32).pin_memory()
             self._hyper_i = 0
         i = self._hyper_i = (self._hyper_i + 1) % 64
         row = self._hyper_pin[i]
         row[0], row[1], row[2], row[3] = lr, 1.0 - self.betas[0] ** step, 1.0 - self.betas[1] ** step, gscale
+        if w == 6:
+            row[4], row[5] = self._ema_dr or (1.0, 0.0)
         self._hyper.copy_(row, non_blocking=True)
 
     def _step_body(self, samples, captured=False):
@@ -454,8 +478,18 @@ class Trainer:
         step = self.num_updates + 1
         if not captured:
             self._upload_hyper(lr, step, gscale)
+        ema = self.ema
+        if ema is not None and ema.fresh:
+            ema.seed()                      # (never inside a capture: two eager updates come first)
+            ema.fresh = False
         if self._defer and not captured and eng.overlap and torch.device(self.device).type == "cuda":
             self._adam_deferred(lr, step, gscale)
+        elif ema is not None and (captured or self._ema_dr is not None):
+            # a captured launch is always the EMA variant: a replay reads (decay, rest) from `_hyper`, (1, 0) on an off-update
+            d, r = self._ema_dr or (1.0, 0.0)
+            hip.adam_ema_step(self.p32, eng.g16, self.m, self.v, eng.p16[: eng.n_train], ema.e32, ema.e16, lr, self.betas[0],
+                              self.betas[1], self.eps, self.wd, step, d, r, gscale, self.clip, self.sumsq, self.overflow,
+                              hyper=self._hyper)
         else:
             hip.adam_step(self.p32, eng.g16, self.m, self.v, eng.p16[: eng.n_train], lr, self.betas[0],
                           self.betas[1], self.eps, self.wd, step, gscale, self.clip, self.sumsq, self.overflow, hyper=self._hyper)
@@ -534,8 +568,14 @@ class Trainer:
             prev = hip.set_stream(self._opt_stream.cuda_stream)
             try:
                 p16 = eng.p16
+                ema, dr = self.ema, self._ema_dr
                 for key, ranges in self._opt_plan:
                     for lo, hi in ranges:
+                        if ema is not None and dr is not None:      # the teacher's slices travel with the student's
+                            hip.adam_ema_step(self.p32[lo:hi], eng.g16[lo:hi], self.m[lo:hi], self.v[lo:hi], p16[lo:hi],
+                                              ema.e32[lo:hi], ema.e16[lo:hi], lr, self.betas[0], self.betas[1], self.eps, self.wd,
+                                              step, dr[0], dr[1], gscale, self.clip, self.sumsq, self.overflow, hyper=self._hyper)
+                            continue
                         hip.adam_step(self.p32[lo:hi], eng.g16[lo:hi], self.m[lo:hi], self.v[lo:hi], p16[lo:hi], lr, self.betas[0],
                                       self.betas[1], self.eps, self.wd, step, gscale, self.clip, self.sumsq, self.overflow,
                                       hyper=self._hyper)
@@ -562,6 +602,8 @@ class Trainer:
         into a HIP graph the first time a (sample, prefetch) pair of tensors is seen and REPLAYED afterwards: one graph
         launch instead of ~9 ms of host enqueue per step.  The sample tensors are the graph's static inputs: a data
         iterator copies each new batch into them (bench.py alternates two resident batches)."""
+        if self._ema_inside:
+            raise RuntimeError("Trainer.train_step inside Trainer.ema_weights(): the arenas hold the teacher")
         self.check_overflow()
         self._quiesced_for_eval = False
         # defer_optimizer (default: IFSEG_DEFER_OPTIMIZER, off): clip + Adam run on their own stream underneath the NEXT
@@ -573,6 +615,10 @@ class Trainer:
             self.model.train()
         eng.step_seed = self.seed + self.num_updates
         self._ahead = None
+        if self.ema is not None:
+            # fairseq's EMA.step(model, updates=num_updates after the update): (decay, 1 - decay) of this update's EMA step, None
+            # on an off-update of ema_update_freq
+            self._ema_dr = self.ema.schedule(self.num_updates + 1)
         if graph and self.world == 1 and len(samples) == 1:
             logs = self._graph_step(samples[0], prefetch[0] if prefetch else None)
         else:
@@ -586,7 +632,73 @@ class Trainer:
             ev = torch.cuda.Event()
             ev.record()
         self._ovf_events = self._ovf_events[-3:] + [ev]
-        return self._sync_logs(logs)
+        logs = self._sync_logs(logs)
+        if self.ema is not None:
+            for lg in logs:
+                lg["ema_decay"] = self.ema.last_decay       # trainer.py:970-976 logs EMA.get_decay() after every update
+        return logs
+
+    # -- the teacher ------------------------------------------------------------------------
+    def _ema_need(self, what):
+        if self.ema is None:
+            raise RuntimeError("Trainer.%s: this trainer keeps no teacher (store_ema=False)" % what)
+        if self._ema_inside:
+            raise RuntimeError("Trainer.%s inside Trainer.ema_weights(): student and teacher have changed places" % what)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the block the arenas hold the teacher: the engine, `model.state_dict()`, a Segmenter, `valid_step` and
+        `evaluate_raw` compute with the averaged weights (fairseq's `EMA.reverse`, without a second model); on exit the student
+        is back, bit for bit.  One `hip.ema_swap` launch each way (24 bytes per trainable parameter), behind a still-running
+        deferred optimizer.  Every swap retires the engine's cached resized rel-pos biases (`weights_changed`): a whole-image
+        multi-scale + flip Segmenter rebuilds them on both sides, `slide=True` builds none.  `train_step` inside the block,
+        nesting it and a trainer without store_ema: RuntimeError."""
+        self._ema_need("ema_weights")
+        self.params_ready()
+        self.ema.swap()
+        self.eng.weights_changed()
+        self._ema_inside = True
+        try:
+            yield self
+        finally:
+            self.params_ready()
+            self.ema.swap()
+            self.eng.weights_changed()
+            self._ema_inside = False
+
+    def _ema_entries(self):
+        """[(state-dict key, offset into the trainable arena, shape)] of every entry of the model's state dict that lives in the
+        trainable arena, tied entries (several keys, one tensor) included"""
+        base, n = self.eng.p16.data_ptr(), self.eng.n_train
+        out = []
+        for k, t in self.model.state_dict().items():
+            off = (t.data_ptr() - base) // 2
+            if t.dtype == torch.bfloat16 and t.is_cuda and 0 <= off and off + t.numel() <= n and t.is_contiguous():
+                out.append((k, off, tuple(t.shape)))
+        return out
+
+    def ema_state_dict(self):
+        """The teacher under the model's own `state_dict()` keys: trainable entries are fp32 clones out of `ema.e32`, everything
+        else (frozen parameters, the trunk, buffers) is the model's own tensor, shared with the student and never averaged.
+        Loaded into a fresh SegOFAModel it gives the teacher."""
+        self._ema_need("ema_state_dict")
+        self.params_ready()
+        sd = dict(self.model.state_dict())
+        for k, off, shape in self._ema_entries():
+            sd[k] = self.ema.e32[off:off + math.prod(shape)].view(shape).clone()
+        return sd
+
+    def load_ema_state_dict(self, sd):
+        """inverse of `ema_state_dict`: the trainable entries of `sd` become the fp32 teacher, its bf16 copy their rounding (what
+        the optimizer launch would have stored); a missing trainable entry: KeyError"""
+        self._ema_need("load_ema_state_dict")
+        self.params_ready()
+        for k, off, shape in self._ema_entries():
+            if tuple(sd[k].shape) != shape:
+                raise ValueError("load_ema_state_dict: %s has shape %s, the model's is %s" % (k, tuple(sd[k].shape), shape))
+            self.ema.e32[off:off + math.prod(shape)].view(shape).copy_(sd[k].to(self.device, torch.float32))
+        self.ema.e16.copy_(self.ema.e32)
+        self.ema.fresh = False
 
     def _graph_step(self, sample, nxt):
         eng = self.eng

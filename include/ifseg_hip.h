@@ -834,6 +834,23 @@ int ifseg_adam_step(float* p32, const void* g, float* m, float* v, void* p16, lo
                     const float* sumsq, int* overflow, const float* hyper, void* stream);
 /* `hyper` (device, may be NULL): {lr, 1 - beta1^step, 1 - beta2^step, grad_scale} override the by-value arguments --
  * a captured training step (HIP graph) is replayed with the schedule's current values. */
+/* ifseg_adam_step with a teacher averaged in the same launch (fairseq/models/ema/ema.py:134-167 with ema_fp32 on a 16-bit
+ * model; ifseg_amd/ema.py is the specification).  Per element, with q the bf16 weight this launch stores to p16:
+ *     e32 = fma(ema_rest, float(q), round32(e32 * ema_decay))        e16 = bf16_rne(e32)
+ * -- a rounded product and ONE fused multiply-add, which is what `ema.mul_(decay); ema.add_(p.float(), alpha=1 - decay)`
+ * computes; ema_rest = float(1.0 - decay) is formed by the caller in double.  (p32, m, v, p16) come out bit-equal to
+ * ifseg_adam_step.  `hyper` (device, may be NULL) has SIX floats here: the four above, then {ema_decay, ema_rest}.
+ * (ema_decay, ema_rest) == (1, 0) neither reads nor writes the teacher (the off-updates of ema_update_freq in a captured
+ * step); a non-finite *sumsq skips the teacher with the update.  e32 / e16: n elements, aligned like p32 / p16 (16 / 8
+ * bytes); NULL: IFSEG_ERR_BAD_ARG.  40 bytes of traffic per element against ifseg_adam_step's 30. */
+int ifseg_adam_ema_step(float* p32, const void* g, float* m, float* v, void* p16, float* e32, void* e16, long long n,
+                        float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
+                        float max_norm, const float* sumsq, int* overflow, const float* hyper, float ema_decay,
+                        float ema_rest, void* stream);
+/* p32 <-> e32 (fp32) and p16 <-> e16 (bf16), n elements each, in place and without a temporary: student and teacher change
+ * places (fairseq's EMA.reverse without a second model).  The two sides must not overlap (the binding checks); a NULL
+ * pointer: IFSEG_ERR_BAD_ARG.  24 bytes of traffic per element. */
+int ifseg_ema_swap(float* p32, void* p16, float* e32, void* e16, long long n, void* stream);
 
 /* ------------------------------------------------- dense-CRF post-processing (crf.py:19-37) */
 /* Mean-field inference of the reference's DenseCRF2D (pydensecrf, third party, absent: parity unpinned) with the EXACT
