@@ -32,13 +32,16 @@
 // from elsewhere.  Only the non-zero bins leave a workgroup, one 64-bit integer atomic each: integer sums, so the counters
 // are bit-reproducible.  The instantiations without the flag have none of this.
 // The confusion matrix (ifseg_seg_confusion) is a second stand-alone kernel on a label map, seg_confusion_kernel: its table does
-// not fit the epilogues' LDS budget.
+// not fit the epilogues' LDS budget.  The wave pre-aggregated add (bin_add), the walk over a flat label map (walk_pixels,
+// walk_split) and the direct / hashed workgroup table (table_*) are count.h's, shared with pseudo.hip.
+#include "count.h"
 #include "tile.h"
 #include "../../include/ifseg_hip.h"
 
 namespace {
 
 using namespace tile;
+using namespace count;
 
 constexpr int PT_MAX_CLASSES = 512;
 constexpr int PT_TILE_LDS = TILE_ROWS * TILE_COLS * 8;            // the label + conf tile of phase 2
@@ -176,19 +179,6 @@ __device__ __forceinline__ void score_zero(uint32_t* tab, int n) {
   for (int i = threadIdx.x; i < 3 * n + 2; i += 256) tab[i] = 0;
 }
 
-// tab[idx] += 1 for every lane with `on`; whole (converged) waves call it.  A label map is piecewise constant, so most lanes
-// of a wave name the same bin, and an LDS atomic takes the lanes of one address one after the other: the lanes that share the
-// first active lane's bin leave as one add of their count, the others one each
-__device__ __forceinline__ void bin_add(uint32_t* tab, int idx, bool on) {
-  const unsigned long long m = __ballot(on);
-  if (!m) return;
-  const int lead = __ffsll((long long)m) - 1;
-  const int first = __builtin_amdgcn_readlane(idx, lead);
-  const unsigned long long same = __ballot(on && idx == first);
-  if ((int)(threadIdx.x & 63) == lead) atomicAdd(&tab[first], (uint32_t)__popcll(same));
-  else if (on && idx != first) atomicAdd(&tab[idx], 1u);
-}
-
 // the ground-truth rule of include/ifseg_hip.h, its one statement: the class of the value g, whether the pixel (where `live`)
 // is scored, and whether it is not ignored but of a class outside [0, n)
 struct GtClass {
@@ -229,11 +219,6 @@ __device__ __forceinline__ void score_flush(uint32_t* tab, int n, int scored, in
     const uint32_t v = tab[i];
     if (v) atomicAdd(i < 3 * n ? areas + i : tally + (i - 3 * n), (unsigned long long)v);
   }
-}
-
-template <int EB>
-__device__ __forceinline__ int elem_at(const void* p, long long i) {
-  return EB == 1 ? (int)((const unsigned char*)p)[i] : (int)((const short*)p)[i];
 }
 
 // the epilogue of both predict kernels: lane = x, the wave's four rows; pred[j] is the label of row wave * 4 + j
@@ -1006,87 +991,7 @@ __global__ __launch_bounds__(256) void seg_predict_slide_views_kernel(SlideViewT
 }
 
 // ---- labels from elsewhere (the CRF's argmax, another model) against ground truth ----
-// A lane takes 16 consecutive pixels per step: their labels and their ground truth come as aligned 16-byte loads.  The body
-// starts at the first 16-byte boundary of `lab`; the ground truth of the same pixels then sits s bytes behind a boundary of
-// its own, s the same for every lane: it is read as the aligned chunks around it and shifted into place.  The pixels in front
-// of the body and behind its last whole group of 16 (fewer than 16 each) are read one by one.  Grid-stride over at most
-// SA_MAX_BLOCKS workgroups, so the flush does not grow with the image.
-constexpr int SA_MAX_BLOCKS = 512;
-
-// o[i] = dword i of the byte string w shifted down by 4 SD + sb bytes
-template <int SD, int N>
-__device__ __forceinline__ void shifted(const uint32_t (&w)[N + 4], int sb, uint32_t (&o)[N]) {
-#pragma unroll
-  for (int i = 0; i < N; ++i) o[i] = __builtin_amdgcn_alignbyte(w[i + SD + 1], w[i + SD], (uint32_t)sb);
-}
-
-// v[0..16) = the 16 elements of EB bytes that start s bytes (0 <= s < 16, wave-uniform) behind the 16-byte boundary p: EB
-// aligned chunks, and one more only where s != 0 -- that one holds bytes of the elements, so it lies inside their buffer's pages
-template <int EB>
-__device__ __forceinline__ void load16(const unsigned char* p, int s, int (&v)[16]) {
-  constexpr int N = 4 * EB;
-  uint32_t w[N + 4], o[N];
-#pragma unroll
-  for (int c = 0; c <= EB; ++c) {
-    uint4 q = make_uint4(0, 0, 0, 0);
-    if (c < EB || s) q = *reinterpret_cast<const uint4*>(p + 16 * c);
-    w[4 * c] = q.x; w[4 * c + 1] = q.y; w[4 * c + 2] = q.z; w[4 * c + 3] = q.w;
-  }
-  switch (s >> 2) {
-    case 0: shifted<0, N>(w, s & 3, o); break;
-    case 1: shifted<1, N>(w, s & 3, o); break;
-    case 2: shifted<2, N>(w, s & 3, o); break;
-    default: shifted<3, N>(w, s & 3, o); break;
-  }
-#pragma unroll
-  for (int i = 0; i < 16; ++i)
-    v[i] = EB == 1 ? (int)((o[i >> 2] >> (8 * (i & 3))) & 255u) : (int)(short)(o[i >> 1] >> (16 * (i & 1)));
-}
-
-// the walk of a label map and its ground truth, its one statement: f(pred, g, live) for every pixel, called by whole
-// (converged) waves.  Head and tail go to lanes 0..15 and 16..31 of the grid's first wave, one pixel each; the body's groups
-// of 16 to the lanes, grid-stride
-template <int LB, int GB, typename F>
-__device__ __forceinline__ void walk_pixels(const unsigned char* lab, const unsigned char* gt, int head, int groups, int tail, F f) {
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (blockIdx.x == 0 && wave == 0) {
-    long long i = -1;
-    if (lane < head) i = lane;
-    else if (lane >= 16 && lane - 16 < tail) i = (long long)head + (long long)groups * 16 + (lane - 16);
-    const bool live = i >= 0;
-    f(live ? elem_at<LB>(lab, i) : 0, live ? elem_at<GB>(gt, i) : 0, live);
-  }
-  const unsigned char* lb = lab + (long long)head * LB;           // on a 16-byte boundary
-  const unsigned char* gb = gt + (long long)head * GB;
-  const int s = __builtin_amdgcn_readfirstlane((int)((size_t)gb & 15));
-  gb -= s;
-  for (long long base = (long long)blockIdx.x * 256 + wave * 64; base < groups; base += (long long)gridDim.x * 256) {
-    const long long g = base + lane;
-    const bool live = g < groups;
-    int pv[16] = {}, gv[16] = {};
-    if (live) {
-      load16<LB>(lb + g * (16 * LB), 0, pv);
-      load16<GB>(gb + g * (16 * GB), s, gv);
-    }
-#pragma unroll
-    for (int i = 0; i < 16; ++i) f(pv[i], gv[i], live);
-  }
-}
-
-// the host's side of the walk: the pixels in front of the labels' first 16-byte boundary, whole groups of 16, the rest, and
-// the workgroups of the launch
-struct WalkSplit {
-  int head, groups, tail, blocks;
-};
-WalkSplit walk_split(const void* labels, int label_bytes, long long npix) {
-  WalkSplit w;
-  w.head = (int)std::min<long long>(npix, (long long)((0 - (size_t)labels) & 15) / label_bytes);
-  w.groups = (int)((npix - w.head) / 16);
-  w.tail = (int)(npix - w.head - 16ll * w.groups);
-  w.blocks = std::min(std::max((w.groups + 255) / 256, 1), SA_MAX_BLOCKS);
-  return w;
-}
-
+// count.h's walk over the label map with the ground truth as its second stream, into the scoring epilogues' table.
 template <int LB, int GB>
 __global__ __launch_bounds__(256) void seg_areas_kernel(const unsigned char* __restrict__ lab, const unsigned char* __restrict__ gt,
                                                         int head, int groups, int tail, int n, int raw,
@@ -1095,66 +1000,21 @@ __global__ __launch_bounds__(256) void seg_areas_kernel(const unsigned char* __r
   score_zero(tab, n);
   __syncthreads();
   int scored = 0, bad = 0;
-  walk_pixels<LB, GB>(lab, gt, head, groups, tail,
-                      [&](int pred, int g, bool live) { score_pixel(tab, n, raw, pred, g, live, scored, bad); });
+  walk_pixels<LB, MapStream<GB>>(lab, gt, head, groups, tail,
+                  [&](int pred, int g, bool live) { score_pixel(tab, n, raw, pred, g, live, scored, bad); });
   score_flush(tab, n, scored, bad, areas, tally);
 }
 
 // ---- which class is taken for which: the confusion matrix of a label map ----
 // confusion[c][p] counts the scored pixels of ground-truth class c with predicted label p; column n takes every label outside
-// [0, n).  The walk over the two maps is seg_areas_kernel's; the table of a workgroup is one of two, chosen by the host:
-//   direct   n (n + 1) <= SC_DIRECT_MAX (n <= 127): uint32 [n][n + 1] in LDS, the pair's key = c (n + 1) + p its index
-//   hashed   the matrix does not fit 64 KiB: SC_SLOTS keys (SC_EMPTY = free) and SC_SLOTS counts.  A key takes the first slot of
-//            its SC_PROBES-long probe sequence that is free (claimed by an LDS compare-and-swap) or already its own; a key
-//            that finds none adds to the global matrix directly, so the result never depends on the table's size
-// In front of both, pair_add's wave pre-aggregation (bin_add's: label maps are piecewise constant).  A workgroup sees fewer
-// than 2^31 pixels in all (npix < 2^31), so no uint32 count wraps.  After a barrier every non-zero bin / claimed slot leaves
-// as one 64-bit atomic; a workgroup never walks the global matrix.
+// [0, n).  The walk over the two maps is seg_areas_kernel's, the table count.h's under the pair's key = c (n + 1) + p:
+//   direct   n (n + 1) <= SC_DIRECT_MAX (n <= 127): uint32 [n][n + 1] in LDS
+//   hashed   the matrix does not fit 64 KiB
 constexpr int SC_DIRECT_MAX = 16384;     // table entries of the direct regime: 64 KiB
-constexpr int SC_SLOT_BITS = 12;
-constexpr int SC_SLOTS = 1 << SC_SLOT_BITS;     // slots of the hashed regime (4096): 32 KiB of keys and counts
 constexpr int SC_STEP_PIXELS = 256 * 16;  // the pixels a workgroup takes per step of the walk
-constexpr int SC_PROBES = 16;
-constexpr uint32_t SC_EMPTY = 0xffffffffu;     // no key: keys are below 512 * 513
 
 __host__ __device__ inline bool sc_hashed(int n) { return n * (n + 1) > SC_DIRECT_MAX; }
-__host__ __device__ inline int sc_dwords(int n) { return sc_hashed(n) ? 2 * SC_SLOTS : n * (n + 1); }
-
-// cnt pixels of the pair `key` into the workgroup's table, or past a crowded hashed table into the matrix itself
-__device__ __forceinline__ void pair_count(uint32_t* tab, bool hashed, uint32_t key, uint32_t cnt, unsigned long long* confusion) {
-  if (!hashed) {
-    atomicAdd(&tab[key], cnt);
-    return;
-  }
-  uint32_t s = (key * 2654435761u) >> (32 - SC_SLOT_BITS);        // Fibonacci hashing to a slot
-  for (int probe = 0; probe < SC_PROBES; ++probe, s = (s + 1) & (SC_SLOTS - 1)) {
-    const uint32_t was = atomicCAS(&tab[s], SC_EMPTY, key);
-    if (was == SC_EMPTY || was == key) {
-      atomicAdd(&tab[SC_SLOTS + s], cnt);
-      return;
-    }
-  }
-  atomicAdd(&confusion[key], (unsigned long long)cnt);
-}
-
-// bin_add for a pair: the lanes that share the first active lane's key leave as one add of their count, the others one each;
-// whole (converged) waves call it
-__device__ __forceinline__ void pair_add(uint32_t* tab, bool hashed, int key, bool on, unsigned long long* confusion) {
-  const unsigned long long m = __ballot(on);
-  if (!m) return;
-  const int lead = __ffsll((long long)m) - 1;
-  const int first = __builtin_amdgcn_readlane(key, lead);
-  const unsigned long long same = __ballot(on && key == first);
-  if ((int)(threadIdx.x & 63) == lead) pair_count(tab, hashed, (uint32_t)first, (uint32_t)__popcll(same), confusion);
-  else if (on && key != first) pair_count(tab, hashed, (uint32_t)key, 1u, confusion);
-}
-
-__device__ __forceinline__ void confusion_pixel(uint32_t* tab, bool hashed, int n, int raw, int pred, int g, bool live,
-                                                unsigned long long* confusion) {
-  const GtClass t = gt_class(n, raw, g, live);
-  const int col = (unsigned)pred < (unsigned)n ? pred : n;
-  pair_add(tab, hashed, t.sc ? t.cls * (n + 1) + col : 0, t.sc, confusion);
-}
+__host__ __device__ inline int sc_dwords(int n) { return sc_hashed(n) ? 2 * SLOTS : n * (n + 1); }
 
 template <int LB, int GB>
 __global__ __launch_bounds__(256) void seg_confusion_kernel(const unsigned char* __restrict__ lab, const unsigned char* __restrict__ gt,
@@ -1162,23 +1022,14 @@ __global__ __launch_bounds__(256) void seg_confusion_kernel(const unsigned char*
                                                             unsigned long long* confusion) {
   extern __shared__ __attribute__((aligned(16))) uint32_t ctab[];  // sc_dwords(n)
   const bool hashed = sc_hashed(n);                                // uniform over the grid
-  const int keys = hashed ? SC_SLOTS : 0, dwords = sc_dwords(n);
-  for (int i = threadIdx.x; i < dwords; i += 256) ctab[i] = i < keys ? SC_EMPTY : 0u;
-  __syncthreads();
-  walk_pixels<LB, GB>(lab, gt, head, groups, tail,
-                      [&](int pred, int g, bool live) { confusion_pixel(ctab, hashed, n, raw, pred, g, live, confusion); });
-  __syncthreads();
-  if (hashed) {
-    for (int i = threadIdx.x; i < SC_SLOTS; i += 256) {
-      const uint32_t key = ctab[i];
-      if (key != SC_EMPTY) atomicAdd(&confusion[key], (unsigned long long)ctab[SC_SLOTS + i]);
-    }
-  } else {
-    for (int i = threadIdx.x; i < dwords; i += 256) {
-      const uint32_t v = ctab[i];
-      if (v) atomicAdd(&confusion[i], (unsigned long long)v);
-    }
-  }
+  const int dwords = sc_dwords(n);
+  table_zero(ctab, hashed, dwords);
+  walk_pixels<LB, MapStream<GB>>(lab, gt, head, groups, tail, [&](int pred, int g, bool live) {
+    const GtClass t = gt_class(n, raw, g, live);
+    const int col = (unsigned)pred < (unsigned)n ? pred : n;
+    table_add(ctab, hashed, t.sc ? t.cls * (n + 1) + col : 0, t.sc, confusion);
+  });
+  table_flush(ctab, hashed, dwords, confusion);
 }
 
 // what the scoring entry points refuse on top of their predict counterparts
@@ -1468,9 +1319,9 @@ extern "C" int ifseg_seg_confusion(const void* labels, int label_bytes, const vo
 extern "C" int ifseg_seg_confusion_limit(int which) {
   switch (which) {
     case 0: return SC_DIRECT_MAX;
-    case 1: return SC_SLOTS;
+    case 1: return SLOTS;
     case 2: return SC_STEP_PIXELS;
-    case 3: return SA_MAX_BLOCKS;
+    case 3: return MAX_BLOCKS;
     default: return IFSEG_ERR_BAD_ARG;
   }
 }

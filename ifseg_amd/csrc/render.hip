@@ -6,9 +6,9 @@
 // A workgroup owns a 16 x 64 tile (tile.h).  Source and destination rows are 3 W bytes and start at any byte alignment, so a
 // tile row of 192 bytes neither starts nor ends on a dword and neighbouring workgroups share dwords:
 //   phase 0  the tile's image bytes go to LDS with tile.h's aligned dword loads (u8_stage under the identity coordinate), the
-//            tile's labels plus a halo of r, coordinates clamped to the image, and the palette as one dword per class;
-//   phase 1  lane = x, a wave takes 4 rows: contour test on the staged labels, blend, three bytes into the staged output row,
-//            which keeps the shift (address modulo 4) of its destination row;
+//            tile's labels plus a halo of r (tile.h's halo_stage), and the palette as one dword per class;
+//   phase 1  lane = x, a wave takes 4 rows: contour test on the staged labels (tile.h's halo_differs), blend, three bytes into
+//            the staged output row, which keeps the shift (address modulo 4) of its destination row;
 //   phase 2  the staged rows leave as aligned dwords where a dword lies entirely inside the tile's bytes of the row -- such a
 //            dword has this workgroup as its only writer -- and as single bytes in front of the first and behind the last one.
 // Nothing outside the output's bytes is written, and no dword is written by two workgroups or lanes with partial contents.
@@ -20,9 +20,8 @@ namespace {
 
 using namespace tile;
 
-constexpr int MAX_R = 4, MAX_N = 512;
+constexpr int MAX_N = 512;
 constexpr int ROW_BYTES = 196;                                    // u8_rstride(TILE_COLS): 192 bytes, up to 3 of shift, whole dwords
-constexpr int HALO_W = TILE_COLS + 2 * MAX_R, HALO_H = TILE_ROWS + 2 * MAX_R;
 
 // source sample = destination sample: the footprint of a tile is the tile
 struct SameCoord {
@@ -50,13 +49,7 @@ __global__ __launch_bounds__(256) void seg_render_kernel(const L* labels, const 
   // phase 0
   for (int c = threadIdx.x; c < n; c += 256)
     pal[c] = (uint32_t)palette[3 * c] | (uint32_t)palette[3 * c + 1] << 8 | (uint32_t)palette[3 * c + 2] << 16;
-  const int hw = TILE_COLS + 2 * r;
-  for (int i = threadIdx.x; i < (TILE_ROWS + 2 * r) * hw; i += 256) {
-    const int hy = i / hw, hx = i - hy * hw;
-    // a neighbour outside the image reads the nearest pixel inside, which lies in the same window: it adds no contour
-    const int y = min(max(t.Y0 - r + hy, 0), H - 1), x = min(max(t.X0 - r + hx, 0), W - 1);
-    halo[hy * HALO_W + hx] = (short)labels[pix0 + (long long)y * W + x];
-  }
+  halo_stage(labels, pix0, t, H, W, r, halo);
   const SameCoord same;
   const U8Source s = u8_stage(image + pix0 * 3, W, same, t.Y0, t.yend - 1, same, t.X0, t.xend - 1, src, (int)sizeof(src));
   __syncthreads();
@@ -67,10 +60,8 @@ __global__ __launch_bounds__(256) void seg_render_kernel(const L* labels, const 
   for (int j = 0; j < 4; ++j) {
     const int ry = t.wave * 4 + j;
     if (ry >= rows || t.lane >= cols) continue;
-    const int l = halo[(ry + r) * HALO_W + t.lane + r];
-    bool edge = false;
-    for (int dy = 0; dy <= 2 * r; ++dy)
-      for (int dx = 0; dx <= 2 * r; ++dx) edge |= halo[(ry + dy) * HALO_W + t.lane + dx] != l;
+    const int l = halo_label(halo, ry, t.lane, r);
+    const bool edge = halo_differs(halo, ry, t.lane, r, l);
     const unsigned char* p = s.stage + ry * s.rstride + (int)((size_t)(s.row0 + (long long)ry * W * 3) & 3) + t.lane * 3;
     uint32_t v = (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16;
     if (edge) {
@@ -113,7 +104,7 @@ extern "C" int ifseg_seg_render(const void* labels, int label_bytes, const void*
   (void)hipGetLastError();
   if (!labels || !image || !palette || !out || (label_bytes != 1 && label_bytes != 2)) return IFSEG_ERR_BAD_ARG;
   if ((label_bytes == 2 && ((size_t)labels & 1)) || ((size_t)conf & 3)) return IFSEG_ERR_BAD_ARG;
-  if (n < 1 || n > MAX_N || boundary < 0 || boundary > MAX_R || alpha < 0 || alpha > 256) return IFSEG_ERR_BAD_ARG;
+  if (n < 1 || n > MAX_N || boundary < 0 || boundary > HALO_MAX_R || alpha < 0 || alpha > 256) return IFSEG_ERR_BAD_ARG;
   if (boundary_rgb < 0 || boundary_rgb > 0xffffff) return IFSEG_ERR_BAD_ARG;
   if (B < 1 || H < 1 || W < 1 || (long long)B * H * W >= (1ll << 31)) return IFSEG_ERR_BAD_SHAPE;
   int tiles_x, tiles_y;

@@ -5,7 +5,8 @@
 // the destination, so the tile's first and last pixel bound its source footprint; the footprint is staged in LDS where it fits
 // the buffer the host gave the launch and read from global memory otherwise.  Here: the tile decode, the two coordinate rules
 // and the footprint on top of them, everything the two uint8 kernels share (staging with aligned dwords, the pixel loop, the
-// plane stores), and the host's grid / bound / staging-limit helpers.
+// plane stores), the label halo of the two kernels that look at a label's neighbours (render.hip, pseudo.hip), and the host's
+// grid / bound / staging-limit helpers.
 #pragma once
 #include <algorithm>
 #include "common.h"
@@ -206,6 +207,36 @@ __device__ __forceinline__ void u8_pixels(const U8Source& s, const int (&y0)[4],
     for (int j = 0; j < 4; ++j) { r0[j] = (long long)y0[j] * s.W0 * 3; r1[j] = (long long)y1[j] * s.W0 * 3; }
     pixel_loop<T>(s.sb, r0, r1, x0 * 3, x1 * 3, ly, lx, lut, rev, hook, out, erow, plane, ok, lane, x, xend);
   }
+}
+
+// ---- the label halo of a tile (render.hip, pseudo.hip) ----
+// The tile's labels plus the r pixels around it, as shorts in LDS rows of HALO_W; r <= HALO_MAX_R, which the launchers refuse
+// beyond.
+constexpr int HALO_MAX_R = 4;
+constexpr int HALO_W = TILE_COLS + 2 * HALO_MAX_R, HALO_H = TILE_ROWS + 2 * HALO_MAX_R;
+
+// phase 0: halo[hy][hx] = the label at (Y0 - r + hy, X0 - r + hx) of the image that starts at pix0.  The caller's barrier
+// publishes it
+template <typename L>
+__device__ __forceinline__ void halo_stage(const L* labels, long long pix0, const Tile& t, int H, int W, int r, short* halo) {
+  const int hw = TILE_COLS + 2 * r;
+  for (int i = threadIdx.x; i < (TILE_ROWS + 2 * r) * hw; i += 256) {
+    const int hy = i / hw, hx = i - hy * hw;
+    // a neighbour outside the image reads the nearest pixel inside, which lies in the same window: it adds no edge
+    const int y = min(max(t.Y0 - r + hy, 0), H - 1), x = min(max(t.X0 - r + hx, 0), W - 1);
+    halo[hy * HALO_W + hx] = (short)labels[pix0 + (long long)y * W + x];
+  }
+}
+
+// the tile's own label at row ry, column lane
+__device__ __forceinline__ int halo_label(const short* halo, int ry, int lane, int r) { return halo[(ry + r) * HALO_W + lane + r]; }
+
+// whether another label value than l lies within r pixels of it: the (2 r + 1)^2 window
+__device__ __forceinline__ bool halo_differs(const short* halo, int ry, int lane, int r, int l) {
+  bool edge = false;
+  for (int dy = 0; dy <= 2 * r; ++dy)
+    for (int dx = 0; dx <= 2 * r; ++dx) edge |= halo[(ry + dy) * HALO_W + lane + dx] != l;
+  return edge;
 }
 
 // ---- host ----

@@ -1161,17 +1161,27 @@ def _seg_views(views):
 
 
 # --------------------------------------------------------------------------- scoring against ground truth
+def _counter(t, shape, dev):
+    """a counter a call adds to: the caller's `t` (int64 of `shape`, contiguous, on `dev`), checked, or fresh zeros"""
+    if t is None:
+        return torch.zeros(*shape, dtype=torch.int64, device=dev)
+    assert t.dtype == torch.int64 and tuple(t.shape) == tuple(shape) and t.is_contiguous() and t.device == dev, \
+        (t.dtype, tuple(t.shape), t.stride(), t.device, tuple(shape))
+    return t
+
+
 def _score_counters(n, dev, areas, tally):
     """the counters a scoring call adds to: the caller's (int64 [3, n] and [2], contiguous, on `dev`) or fresh zeroed ones"""
-    if areas is None:
-        areas = torch.zeros(3, n, dtype=torch.int64, device=dev)
-    if tally is None:
-        tally = torch.zeros(2, dtype=torch.int64, device=dev)
-    assert areas.dtype == torch.int64 and tuple(areas.shape) == (3, n) and areas.is_contiguous() and areas.device == dev, \
-        (areas.dtype, tuple(areas.shape), areas.device, n)
-    assert tally.dtype == torch.int64 and tuple(tally.shape) == (2,) and tally.is_contiguous() and tally.device == dev, \
-        (tally.dtype, tuple(tally.shape), tally.device)
-    return areas, tally
+    return _counter(areas, (3, n), dev), _counter(tally, (2,), dev)
+
+
+def _label_pair(labels, gt, n):
+    """what seg_areas and seg_confusion ask of their two maps"""
+    assert labels.dtype in (torch.uint8, torch.int16) and labels.is_contiguous(), (labels.dtype, labels.stride())
+    assert gt.dtype in (torch.uint8, torch.int16) and gt.is_contiguous(), (gt.dtype, gt.stride())
+    assert labels.shape == gt.shape and labels.device == gt.device, (tuple(labels.shape), tuple(gt.shape), labels.device, gt.device)
+    assert 1 <= n <= SEG_PREDICT_MAX_CLASSES, n
+    assert 1 <= labels.numel() < 2 ** 31, tuple(labels.shape)
 
 
 def _score_gt(gt, B, dev):
@@ -1185,11 +1195,7 @@ def seg_areas(labels, gt, n, raw_labels=True, areas=None, tally=None):
     per class #(pred = gt = c), #(pred = c), #(gt = c) over the scored pixels; #scored pixels, #pixels with a ground truth out of
     range (csrc/predict.hip; `predict.areas_reference` is the specification and states the ground-truth rule).  `areas` / `tally`
     given: ACCUMULATED into, else fresh zeroed ones.  For label maps that do not come out of seg_score / seg_score_views."""
-    assert labels.dtype in (torch.uint8, torch.int16) and labels.is_contiguous(), (labels.dtype, labels.stride())
-    assert gt.dtype in (torch.uint8, torch.int16) and gt.is_contiguous(), (gt.dtype, gt.stride())
-    assert labels.shape == gt.shape and labels.device == gt.device, (tuple(labels.shape), tuple(gt.shape), labels.device, gt.device)
-    assert 1 <= n <= SEG_PREDICT_MAX_CLASSES, n
-    assert 1 <= labels.numel() < 2 ** 31, tuple(labels.shape)
+    _label_pair(labels, gt, n)
     areas, tally = _score_counters(n, labels.device, areas, tally)
     _check(lib().ifseg_seg_areas(_ptr(labels), c_int(labels.element_size()), _ptr(gt), c_int(gt.element_size()),
                                  c_ll(labels.numel()), c_int(n), c_int(1 if raw_labels else 0), _ptr(areas), _ptr(tally),
@@ -1197,11 +1203,11 @@ def seg_areas(labels, gt, n, raw_labels=True, areas=None, tally=None):
     return areas, tally
 
 
-# the tables of seg_confusion_kernel (csrc/predict.hip), for callers and tests that size an input against them
+# the tables of seg_confusion_kernel (csrc/predict.hip, csrc/count.h), for callers and tests that size an input against them
 SEG_CONFUSION_DIRECT_MAX = 16384    # == SC_DIRECT_MAX: n (n + 1) up to this (n <= 127) counts in a direct LDS table, else hashed
-SEG_CONFUSION_SLOTS = 4096          # == SC_SLOTS: the (class, label) pairs a workgroup's hashed table holds at most
+SEG_CONFUSION_SLOTS = 4096          # == count::SLOTS: the (class, label) pairs a workgroup's hashed table holds at most
 SEG_CONFUSION_STEP_PIXELS = 4096    # the pixels a workgroup takes per step: 256 lanes of 16
-SEG_CONFUSION_MAX_BLOCKS = 512      # == SA_MAX_BLOCKS: the workgroups of a launch at most (grid-stride beyond)
+SEG_CONFUSION_MAX_BLOCKS = 512      # == count::MAX_BLOCKS: the workgroups of a launch at most (grid-stride beyond)
 
 
 def seg_confusion_limits():
@@ -1215,15 +1221,8 @@ def seg_confusion(labels, gt, n, raw_labels=True, confusion=None):
     scored pixels of `seg_areas`, [c, p] = #(gt = c and pred = p), column n taking every predicted label outside [0, n)
     (csrc/predict.hip; `predict.confusion_reference` is the specification).  `confusion` given: ACCUMULATED into, else fresh
     zeros.  Its sum is seg_areas' tally[0], the diagonal / column sums of [:, :n] areas[0] / areas[1], its row sums areas[2]."""
-    assert labels.dtype in (torch.uint8, torch.int16) and labels.is_contiguous(), (labels.dtype, labels.stride())
-    assert gt.dtype in (torch.uint8, torch.int16) and gt.is_contiguous(), (gt.dtype, gt.stride())
-    assert labels.shape == gt.shape and labels.device == gt.device, (tuple(labels.shape), tuple(gt.shape), labels.device, gt.device)
-    assert 1 <= n <= SEG_PREDICT_MAX_CLASSES, n
-    assert 1 <= labels.numel() < 2 ** 31, tuple(labels.shape)
-    if confusion is None:
-        confusion = torch.zeros(n, n + 1, dtype=torch.int64, device=labels.device)
-    assert confusion.dtype == torch.int64 and tuple(confusion.shape) == (n, n + 1) and confusion.is_contiguous() \
-        and confusion.device == labels.device, (confusion.dtype, tuple(confusion.shape), confusion.device, n)
+    _label_pair(labels, gt, n)
+    confusion = _counter(confusion, (n, n + 1), labels.device)
     _check(lib().ifseg_seg_confusion(_ptr(labels), c_int(labels.element_size()), _ptr(gt), c_int(gt.element_size()),
                                      c_ll(labels.numel()), c_int(n), c_int(1 if raw_labels else 0), _ptr(confusion), _stream()),
            "seg_confusion")
@@ -1402,7 +1401,7 @@ def seg_render(labels, image, palette, opacity=0.5, boundary=0, boundary_color=(
 # --------------------------------------------------------------------------- confidence-filtered pseudo-labels
 SEG_CONF_BINS = 256                 # bins of the confidence histogram: clamp(floor(conf * 256), 0, 255)
 SEG_CONF_HIST_DIRECT_CLASSES = 64   # == HC_DIRECT_CLASSES (csrc/pseudo.hip): n up to this counts in a direct LDS table, else hashed
-SEG_CONF_HIST_SLOTS = 4096          # == HC_SLOTS: the (label, bin) pairs a workgroup's hashed table holds at most
+SEG_CONF_HIST_SLOTS = SEG_CONFUSION_SLOTS   # the same table (count::SLOTS): the (label, bin) pairs a workgroup's hashed table holds
 SEG_PSEUDO_MAX_CLASSES = 255        # the uint8 output keeps 255 for "ignore"; with raw_labels class c is stored as c + 1: 254
 
 
@@ -1424,15 +1423,7 @@ def seg_conf_hist(labels, conf, n, hist=None, tally=None):
     into, else fresh zeroed ones.  1 <= n <= 512."""
     _labels_conf(labels, conf, "seg_conf_hist")
     assert isinstance(n, int) and 1 <= n <= SEG_PREDICT_MAX_CLASSES, n
-    dev = labels.device
-    if hist is None:
-        hist = torch.zeros(n, SEG_CONF_BINS, dtype=torch.int64, device=dev)
-    if tally is None:
-        tally = torch.zeros(2, dtype=torch.int64, device=dev)
-    assert hist.dtype == torch.int64 and tuple(hist.shape) == (n, SEG_CONF_BINS) and hist.is_contiguous() and hist.device == dev, \
-        (hist.dtype, tuple(hist.shape), hist.device, n)
-    assert tally.dtype == torch.int64 and tuple(tally.shape) == (2,) and tally.is_contiguous() and tally.device == dev, \
-        (tally.dtype, tuple(tally.shape), tally.device)
+    hist, tally = _counter(hist, (n, SEG_CONF_BINS), labels.device), _counter(tally, (2,), labels.device)
     _check(lib().ifseg_seg_conf_hist(_ptr(labels), c_int(labels.element_size()), _ptr(conf), c_ll(labels.numel()), c_int(n),
                                      _ptr(hist), _ptr(tally), _stream()), "seg_conf_hist")
     return hist, tally
@@ -1453,10 +1444,7 @@ def seg_pseudo(labels, conf, thresholds, n, boundary=0, raw_labels=True, kept=No
     dev = labels.device
     assert thresholds.dtype == torch.int32 and tuple(thresholds.shape) == (n,) and thresholds.is_contiguous() \
         and thresholds.device == dev, (thresholds.dtype, tuple(thresholds.shape), thresholds.device, n)
-    if kept is None:
-        kept = torch.zeros(2, n, dtype=torch.int64, device=dev)
-    assert kept.dtype == torch.int64 and tuple(kept.shape) == (2, n) and kept.is_contiguous() and kept.device == dev, \
-        (kept.dtype, tuple(kept.shape), kept.device, n)
+    kept = _counter(kept, (2, n), dev)
     if out is None:
         out = torch.empty(labels.shape, dtype=torch.uint8, device=dev)
     assert out.dtype == torch.uint8 and out.shape == labels.shape and out.is_contiguous() and out.device == dev, \

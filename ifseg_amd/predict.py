@@ -268,13 +268,33 @@ def default_palette(n):
     return rgb.to(torch.uint8)
 
 
+def _boundary_arg(what, boundary, band="ignore band"):
+    if not isinstance(boundary, int) or isinstance(boundary, bool) or not 0 <= boundary <= hip.SEG_RENDER_MAX_BOUNDARY:
+        raise ValueError("%s: boundary must be an int in 0 .. %d (the %s's half width in pixels), got %r"
+                         % (what, hip.SEG_RENDER_MAX_BOUNDARY, band, boundary))
+    return boundary
+
+
+def _label_edges(lab, r):
+    """labels [..., H, W] -> bool of the same shape: some pixel INSIDE the image with |dx| <= r and |dy| <= r carries a different
+    label value (the contour of `render_reference`, the ignore band of `pseudo_label_reference`)"""
+    H, W = lab.shape[-2:]
+    edge = torch.zeros(lab.shape, dtype=torch.bool, device=lab.device)
+    for dy in range(-r, r + 1):
+        for dx in range(-r, r + 1):
+            if abs(dy) >= H or abs(dx) >= W:
+                continue                                   # no pixel of the image has this neighbour
+            here = (slice(max(-dy, 0), H - max(dy, 0)), slice(max(-dx, 0), W - max(dx, 0)))
+            there = (slice(max(dy, 0), H - max(-dy, 0)), slice(max(dx, 0), W - max(-dx, 0)))
+            edge[(..., *here)] |= lab[(..., *here)] != lab[(..., *there)]
+    return edge
+
+
 def _render_args(what, opacity, boundary, boundary_color):
     """the scalar arguments of a rendering call, checked on the host -> (alpha in 0..256, r, the contour colour as three ints)"""
     if not isinstance(opacity, (int, float)) or not 0.0 <= opacity <= 1.0:
         raise ValueError("%s: opacity must be a number in [0, 1], got %r" % (what, opacity))
-    if not isinstance(boundary, int) or isinstance(boundary, bool) or not 0 <= boundary <= hip.SEG_RENDER_MAX_BOUNDARY:
-        raise ValueError("%s: boundary must be an int in 0 .. %d (the contour's half width in pixels), got %r"
-                         % (what, hip.SEG_RENDER_MAX_BOUNDARY, boundary))
+    boundary = _boundary_arg(what, boundary, "contour")
     color = tuple(boundary_color)
     if len(color) != 3 or any(not isinstance(c, int) or not 0 <= c <= 255 for c in color):
         raise ValueError("%s: boundary_color must be three ints in 0 .. 255, got %r" % (what, boundary_color))
@@ -315,16 +335,7 @@ def render_reference(labels, image, palette, opacity=0.5, boundary=0, boundary_c
     inside = (lab >= 0) & (lab < n)
     colour = palette.cpu().int()[lab.clamp(0, n - 1)]
     out = torch.where(inside[..., None], (img * (256 - a[..., None]) + colour * a[..., None]) >> 8, img)
-    H, W = lab.shape[-2:]
-    edge = torch.zeros_like(inside)
-    for dy in range(-r, r + 1):
-        for dx in range(-r, r + 1):
-            if abs(dy) >= H or abs(dx) >= W:
-                continue                                   # no pixel of the image has this neighbour
-            here = (slice(max(-dy, 0), H - max(dy, 0)), slice(max(-dx, 0), W - max(dx, 0)))
-            there = (slice(max(dy, 0), H - max(-dy, 0)), slice(max(dx, 0), W - max(-dx, 0)))
-            edge[(..., *here)] |= lab[(..., *here)] != lab[(..., *there)]
-    out = torch.where(edge[..., None], torch.tensor(color, dtype=torch.int32), out)
+    out = torch.where(_label_edges(lab, r)[..., None], torch.tensor(color, dtype=torch.int32), out)
     return out.to(torch.uint8)
 
 
@@ -389,13 +400,6 @@ def pseudo_thresholds(hist, keep=1.0, floor=0.0):
     return q.clamp_min(int(math.ceil(float(floor) * 256.0))).to(torch.int32)
 
 
-def _boundary_arg(what, boundary):
-    if not isinstance(boundary, int) or isinstance(boundary, bool) or not 0 <= boundary <= hip.SEG_RENDER_MAX_BOUNDARY:
-        raise ValueError("%s: boundary must be an int in 0 .. %d (the ignore band's half width in pixels), got %r"
-                         % (what, hip.SEG_RENDER_MAX_BOUNDARY, boundary))
-    return boundary
-
-
 def pseudo_label_reference(labels, conf, thresholds, n, boundary=0, raw_labels=True):
     """Specification of hip.seg_pseudo, in integers: labels integer [H, W] (or [B, H, W]), conf fp32 of that shape, thresholds
     integer [n] (bins) -> (out uint8 [.., H, W], kept int64 [2, n]).  A pixel of label l is kept iff
@@ -420,16 +424,7 @@ def pseudo_label_reference(labels, conf, thresholds, n, boundary=0, raw_labels=T
     thr = thr.long().to(lab.device)
     inside = (lab >= 0) & (lab < n)
     cls = lab.clamp(0, n - 1)
-    H, W = lab.shape[-2:]
-    edge = torch.zeros_like(inside)
-    for dy in range(-r, r + 1):
-        for dx in range(-r, r + 1):
-            if abs(dy) >= H or abs(dx) >= W:
-                continue                                   # no pixel of the image has this neighbour
-            here = (slice(max(-dy, 0), H - max(dy, 0)), slice(max(-dx, 0), W - max(dx, 0)))
-            there = (slice(max(dy, 0), H - max(-dy, 0)), slice(max(dx, 0), W - max(-dx, 0)))
-            edge[(..., *here)] |= lab[(..., *here)] != lab[(..., *there)]
-    keep = inside & ~edge & (conf_bin(conf) >= thr[cls])
+    keep = inside & ~_label_edges(lab, r) & (conf_bin(conf) >= thr[cls])
     out = torch.where(keep, cls + (1 if raw_labels else 0), torch.full_like(cls, 255)).to(torch.uint8)
     kept = torch.stack([torch.bincount(cls[keep], minlength=n), torch.bincount(cls[inside], minlength=n)])
     return out, kept

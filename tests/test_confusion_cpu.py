@@ -259,11 +259,13 @@ def test_header_declares_the_entry_point_and_keeps_the_abi_version():
     assert callable(hip.seg_confusion)
     with open(os.path.join(ROOT, "ifseg_amd", "csrc", "predict.hip")) as f:
         src = f.read()
+    with open(os.path.join(ROOT, "ifseg_amd", "csrc", "count.h")) as f:      # the walk and the hashed table, namespace count
+        shared = f.read()
     # the exported constants are the kernel's
     assert int(re.search(r"constexpr int SC_DIRECT_MAX = (\d+);", src).group(1)) == hip.SEG_CONFUSION_DIRECT_MAX
-    assert 1 << int(re.search(r"constexpr int SC_SLOT_BITS = (\d+);", src).group(1)) == hip.SEG_CONFUSION_SLOTS
+    assert 1 << int(re.search(r"constexpr int SLOT_BITS = (\d+);", shared).group(1)) == hip.SEG_CONFUSION_SLOTS
     assert re.search(r"^int ifseg_seg_confusion_limit\(int which\);", header, re.M) and callable(hip.seg_confusion_limits)
-    assert int(re.search(r"constexpr int SA_MAX_BLOCKS = (\d+);", src).group(1)) == hip.SEG_CONFUSION_MAX_BLOCKS
+    assert int(re.search(r"constexpr int MAX_BLOCKS = (\d+);", shared).group(1)) == hip.SEG_CONFUSION_MAX_BLOCKS
     assert hip.SEG_CONFUSION_STEP_PIXELS == 256 * 16
     # and the loaded library states the same four
     assert hip.seg_confusion_limits() == (hip.SEG_CONFUSION_DIRECT_MAX, hip.SEG_CONFUSION_SLOTS, hip.SEG_CONFUSION_STEP_PIXELS,

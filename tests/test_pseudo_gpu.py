@@ -269,6 +269,51 @@ def test_filter_entry_point_refusals():
     assert int(kept[1]) == 16 and int(kept[1 + 255]) == 16 and int(kept.sum()) == 32
 
 
+# ------------------------------------------------------------------------------------------------- the shared parts
+@pytest.mark.parametrize("n,dtype", [(15, torch.uint8), (150, torch.uint8), (150, torch.int16)], ids=["n15_direct", "n150_hashed", "n150_i16_hashed"])
+def test_four_counters_agree_on_one_input(n, dtype):
+    """one label map through everything csrc/count.h and tile.h's halo section hold: the walk with an integer second stream
+    (seg_areas, seg_confusion), with a float one (seg_conf_hist), both table regimes (n = 15 direct, n = 150 hashed for the
+    histogram and the matrix alike) and the halo kernel's counters (seg_pseudo).  With every pixel scored and every threshold
+    0, each of the four counts the pixels per predicted label: torch.bincount of the labels in [0, n).  The labels start 5
+    elements behind a 16-byte boundary and 3 x 37 x 91 = 10 101 pixels leave a tail"""
+    from ifseg_amd import hip
+    from ifseg_amd.predict import areas_reference, confidence_histogram_reference, confusion_reference, pseudo_label_reference
+    dev = _dev()
+    B, H, W = 3, 37, 91
+    g = torch.Generator().manual_seed(n)
+    labels = torch.randint(0, n, (B, (H + 7) // 8, (W + 31) // 32), generator=g).repeat_interleave(8, 1).repeat_interleave(32, 2)
+    labels = labels[:, :H, :W].clone()
+    outside = [255] if dtype == torch.uint8 else [-1, n, 32767]
+    for k, (b, y, x) in enumerate(((0, 0, 0), (0, 0, 7), (1, 16, 63), (1, 16, 64), (2, 36, 90), (2, 20, 45))):
+        labels[b, y, x] = outside[k % len(outside)]
+    labels = labels.to(dtype)
+    conf, thr = make_conf((B, H, W), n + 1), torch.zeros(n, dtype=torch.int32)
+    gt = torch.randint(1, n + 1, (B, H, W), generator=g).to(dtype)           # raw values: class + 1, none ignored
+    inside = (labels.long() >= 0) & (labels.long() < n)
+    want, n_out = torch.bincount(labels.long()[inside], minlength=n), int((~inside).sum())
+    assert n_out == 6 and int(want.sum()) == B * H * W - 6 and int((want > 0).sum()) > 1
+    # the specifications agree by construction
+    ref_h, ref_t = confidence_histogram_reference(labels, conf, n)
+    ref_c = confusion_reference(labels, gt, n)
+    assert torch.equal(ref_h.sum(1), want) and int(ref_t[1]) == n_out
+    assert torch.equal(pseudo_label_reference(labels, conf, thr, n, 1)[1][1], want)
+    assert torch.equal(areas_reference(labels, gt, n)[0][1], want)
+    assert torch.equal(ref_c[:, :n].sum(0), want) and int(ref_c[:, n].sum()) == n_out
+
+    buf = torch.zeros(5 + B * H * W + 16, dtype=dtype, device=dev)
+    ld = buf[5:5 + B * H * W].view(B, H, W).copy_(labels)
+    assert buf.data_ptr() % 16 == 0 and ld.data_ptr() % 16 == 5 * ld.element_size()      # a head, and with it a tail
+    cd, gd, td, want = conf.to(dev), gt.to(dev), thr.to(dev), want.to(dev)
+    hist, tally = hip.seg_conf_hist(ld, cd, n)
+    kept = hip.seg_pseudo(ld, cd, td, n, boundary=1)[1]
+    areas = hip.seg_areas(ld, gd, n)[0]
+    confusion = hip.seg_confusion(ld, gd, n)
+    same = torch.stack([(hist.sum(1) == want).all(), (kept[1] == want).all(), (areas[1] == want).all(),
+                        (confusion[:, :n].sum(0) == want).all(), tally[1] == n_out, confusion[:, n].sum() == n_out])
+    assert same.cpu().tolist() == [True] * 6       # (histogram, filter, areas, confusion, outside: histogram, confusion)
+
+
 # ------------------------------------------------------------------------------------------------- the dispatcher
 def test_ops_match_the_bindings():
     from ifseg_amd import hip
