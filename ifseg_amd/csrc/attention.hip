@@ -24,6 +24,7 @@
 #include <type_traits>
 #include "common.h"
 #include "prof.h"
+#include "attn_tile.h"
 #include "../../include/ifseg_hip.h"
 
 namespace {
@@ -56,37 +57,16 @@ constexpr int KT_BYTES = 64 * 256;  // K_ext tile  [64 keys][128] bf16
 constexpr int VT_BYTES = 64 * 128;  // V tile      [64 keys][64]  bf16
 constexpr int DKV_STAGE_BYTES = 32 * 256 + 32 * 128 + 256;  // dK/dV kernel: Q_ext, dO, lse|delta of 32 queries
 static_assert(2 * DKV_STAGE_BYTES == KT_BYTES + VT_BYTES + 512, "host-side LDS size formula");
-constexpr float NEG_INF = -INFINITY;
-constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
+constexpr float LN2 = 0.6931471805599453f;
 // forward: the running reference maximum is only raised when a tile exceeds it by more than this
 // (log2 units), so the O / l rescale is a rare wave-uniform branch; P stays <= 2^8 in between
 constexpr float LAZY_MAX_SLACK = 8.f;
 
-// LDS images that are read BOTH row-wise (ds_read_b128: 16 rows x one 16-byte chunk per lane
-// group) and transposed (ds_read_b64_tr_b16: 4 consecutive rows x one 64-byte granule):
-// the chunk index is XOR-ed with a bit-rotated row id so that 16 consecutive rows hit 16
-// different 16-byte slots of the 256-byte bank line AND 4 consecutive rows hit 4 different
-// 64-byte bank quarters.
-// K_ext / Q_ext tile: 256-byte rows (16 chunks)
+// K_ext / Q_ext tile: 256-byte rows (16 chunks), attn_tile.h's swizzle on the chunk index
 __device__ __forceinline__ int kx_off(int r, int c) {
   const int f = ((r & 3) << 2) | ((r >> 2) & 3);
   return r * 256 + ((c ^ f) << 4);
 }
-// V / dO tile: 128-byte rows (8 chunks, two rows per bank line)
-__device__ __forceinline__ int vx_off(int r, int colbyte) {
-  const int u = r >> 1, hsw = ((u & 1) << 2) | ((u >> 1) & 3);
-  return r * 128 + ((((colbyte >> 4) ^ hsw) & 7) << 4) + (colbyte & 15);
-}
-
-// Marks a register fragment as used here.  Fragments loaded from global memory in a kernel prologue and first read
-// inside the main loop leave their loads "pending" at the loop header in the compiler's wait-count model; it then puts
-// s_waitcnt vmcnt(N) with small N in front of their uses INSIDE the loop, and from the second iteration on those waits
-// hit the loop's own prefetch (global loads / LDS-DMA for the next tile), serialising it with the MFMAs.
-__device__ __forceinline__ void consume_frag(const bf16x8& f) {
-  typedef __attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned u32x4_t;
-  asm volatile("" :: "v"(__builtin_bit_cast(u32x4_t, f)));
-}
-
 struct RelCtx {
   const float* tbl;   // LDS copy of rel2d[h]
   const int* gc;      // LDS copy of gcode
@@ -109,22 +89,6 @@ __device__ __forceinline__ void stage_table(T* dst, const T* __restrict__ src, i
   }
 }
 
-
-// Epilogue of a 32 x 32 accumulator tile whose row (query / key) is the lane: element r of lane (half, x) is column
-// (r&3) + 8*(r>>2) + 4*half, i.e. 8-byte runs.  The two lanes of a row exchange one run each (v_permlane32_swap), so
-// that every lane stores 16 contiguous bytes: half as many store instructions (the store tail is issue-bound).
-__device__ __forceinline__ void store_tile_bf16(bf16_t* rowp, const f32x16& acc, float scale, int half, bool valid) {
-#pragma unroll
-  for (int rgp = 0; rgp < 2; ++rgp) {
-    const int e0 = rgp * 8, e1 = rgp * 8 + 4;
-    const unsigned x0 = pack2bf(acc[e0] * scale, acc[e0 + 1] * scale), x1 = pack2bf(acc[e0 + 2] * scale, acc[e0 + 3] * scale);
-    const unsigned y0 = pack2bf(acc[e1] * scale, acc[e1 + 1] * scale), y1 = pack2bf(acc[e1 + 2] * scale, acc[e1 + 3] * scale);
-    const auto p0 = __builtin_amdgcn_permlane32_swap(x0, y0, false, false);
-    const auto p1 = __builtin_amdgcn_permlane32_swap(x1, y1, false, false);
-    // lanes 0..31: columns 16*rgp .. +7 (own run, partner's run); lanes 32..63: columns 16*rgp + 8 .. +15
-    if (valid) *reinterpret_cast<uint4*>(rowp + 16 * rgp + 8 * half) = make_uint4(p0[0], p1[0], p0[1], p1[1]);
-  }
-}
 
 template <bool HAS_POS>
 __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs a) {
@@ -476,14 +440,6 @@ __device__ __forceinline__ float rot32(float v) {
   else return __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), 0xC000 | (DKV_ROT_DIR << 10) | (N << 5)));
 }
 
-
-__device__ __forceinline__ uint4 scale_bf16x8(uint4 v, float f) {
-  unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    w[i] = pack2bf(__uint_as_float(w[i] << 16) * f, __uint_as_float(w[i] & 0xffff0000u) * f);
-  return make_uint4(w[0], w[1], w[2], w[3]);
-}
 
 // (dK/dV kernel, grids of any width that is a multiple of 8 and >= 32)  One rotated dS register h -- rotation amount C = c_r,
 // so lane x holds the term of key lane (x + C) & 31 -- added to the four class sums of its query set:

@@ -26,12 +26,10 @@
 #include <type_traits>
 #include "common.h"
 #include "prof.h"
+#include "attn_tile.h"
 #include "../../include/ifseg_hip.h"
 
 namespace {
-
-constexpr float NEG_INF = -INFINITY;
-constexpr float LOG2E = 1.4426950408889634f;
 
 struct BiArgs {
   const bf16_t *q, *k, *v, *dO;
@@ -74,19 +72,7 @@ __device__ __forceinline__ float attn_keep(const AttnDrop& d, unsigned rk, int j
   return (mix32(rk + (unsigned)j * 0x9E3779B9u) >> 8) >= d.thr ? d.inv : 0.f;
 }
 
-// 32 x (128-byte row) tile image read BOTH row-wise (ds_read_b128: 16 rows x one 16-byte chunk per lane group) and
-// transposed (ds_read_b64_tr_b16: 4 consecutive rows x one 64-byte granule): chunk index XOR-ed with a bit-rotated row id
-// (two rows per 256-byte bank line).  Used for the bf16 operand tiles [32][64] and the fp32 bias tiles [32][32].
-__device__ __forceinline__ int vx_off(int r, int colbyte) {
-  const int u = r >> 1, hsw = ((u & 1) << 2) | ((u >> 1) & 3);
-  return r * 128 + ((((colbyte >> 4) ^ hsw) & 7) << 4) + (colbyte & 15);
-}
-__device__ __forceinline__ int vx_swz(int r) { const int u = r >> 1; return ((u & 1) << 2) | ((u >> 1) & 3); }
-
-__device__ __forceinline__ void consume_frag(const bf16x8& f) {
-  typedef __attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned u32x4_t;
-  asm volatile("" :: "v"(__builtin_bit_cast(u32x4_t, f)));
-}
+// The operand tiles [32][64] bf16 and the fp32 bias tiles [32][32] are attn_tile.h's 128-byte-row image (vx_off / vx_swz).
 
 // Key padding (unify_multihead_attention.py:477-489: attn_weights.masked_fill(key_padding_mask, -inf); the padding mask of a
 // batch element is a suffix of its key sequence, encoder_module.py:730-752): score seeds of keys at or beyond the element's
@@ -96,28 +82,6 @@ __device__ __forceinline__ void mask_padded_keys(f32x16& s, int j0, int half, in
 #pragma unroll
   for (int e = 0; e < 16; ++e)
     if (j0 + (e & 3) + 8 * (e >> 2) + 4 * half >= kl) s[e] = NEG_INF;
-}
-
-__device__ __forceinline__ uint4 scale_bf16x8(uint4 v, float f) {
-  unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    w[i] = pack2bf(__uint_as_float(w[i] << 16) * f, __uint_as_float(w[i] & 0xffff0000u) * f);
-  return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-// Epilogue of a 32 x 32 accumulator tile whose row is the lane: element r of lane (half, x) is column
-// (r&3) + 8*(r>>2) + 4*half.  The two lanes of a row exchange one 8-byte run each so that every lane stores 16 bytes.
-__device__ __forceinline__ void store_tile_bf16(bf16_t* rowp, const f32x16& acc, float scale, int half, bool valid) {
-#pragma unroll
-  for (int rgp = 0; rgp < 2; ++rgp) {
-    const int e0 = rgp * 8, e1 = rgp * 8 + 4;
-    const unsigned x0 = pack2bf(acc[e0] * scale, acc[e0 + 1] * scale), x1 = pack2bf(acc[e0 + 2] * scale, acc[e0 + 3] * scale);
-    const unsigned y0 = pack2bf(acc[e1] * scale, acc[e1 + 1] * scale), y1 = pack2bf(acc[e1 + 2] * scale, acc[e1 + 3] * scale);
-    const auto p0 = __builtin_amdgcn_permlane32_swap(x0, y0, false, false);
-    const auto p1 = __builtin_amdgcn_permlane32_swap(x1, y1, false, false);
-    if (valid) *reinterpret_cast<uint4*>(rowp + 16 * rgp + 8 * half) = make_uint4(p0[0], p1[0], p0[1], p1[1]);
-  }
 }
 
 // LDS image of one stage (both kernels): four batch elements' two operand tiles, two bias tiles, the dK/dV kernel's

@@ -306,12 +306,6 @@ def _f32(t):
     return c
 
 
-def attn_fwd(q, k, v, pos_q, pos_k, out, lse, B, H, T, S, rel=None, causal=False, P=None, dense_bias=None,
-             gain=None):
-    """q/k/v/out: [B, T|S, *] bf16 row-strided views (head h at cols h*64..); pos_q/pos_k: [T|S, H*64]."""
-    return attn_fwd_gain(q, k, v, pos_q, pos_k, out, lse, B, H, T, S, rel, causal, P, dense_bias, gain)
-
-
 class _AttnBwdArgs(ctypes.Structure):
     _fields_ = ([(n, c_void_p) for n in ("q", "k", "v", "pos_q", "pos_k", "out", "dout", "lse", "delta", "dq", "dk",
                                           "dv", "dpos_q_part", "dpos_k_part")]
@@ -328,24 +322,26 @@ def _p(t):
     return t.data_ptr() if t is not None else None
 
 
-def attn_fwd_gain(q, k, v, pos_q, pos_k, out, lse, B, H, T, S, rel=None, causal=False, P=None, dense_bias=None,
-                  gain=None):
-    L = lib()
-    if rel is not None:
-        P = rel.P
-    if P is None:
-        P = S
-    rc = L.ifseg_attn_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(pos_q), _ptr(pos_k), _ptr(out), _ptr(lse), c_int(B),
-                          c_int(H), c_int(T), c_int(S), c_int(q.stride(1)), c_int(k.stride(1)), c_int(v.stride(1)),
-                          c_int(out.stride(1)), c_int(pos_q.stride(0) if pos_q is not None else 0),
-                          c_int(pos_k.stride(0) if pos_k is not None else 0), c_ll(q.stride(0)), c_ll(k.stride(0)),
-                          c_ll(v.stride(0)), c_ll(out.stride(0)), c_int(1 if rel is not None else 0), c_int(P),
-                          _ptr(rel.gcode) if rel is not None else None, c_int(rel.code_bias if rel is not None else 0),
-                          c_int(rel.rel2d.shape[1] if rel is not None else 0),
-                          _ptr(rel.rel2d) if rel is not None else None, _ptr(rel.rel1d) if rel is not None else None,
-                          _ptr(rel.relx) if rel is not None else None, c_int(1 if causal else 0), _ptr(dense_bias),
-                          _ptr(_f32(gain)), c_int(rel.grid_w if rel is not None else 0),
-                          c_int(dense_bias.stride(1) if dense_bias is not None else 0), _stream())
+def _rel_fields(rel, P, S):
+    """-> (rel_mode, P, gcode, code_bias, n2d, rel2d, rel1d, relx, grid_w) of the three entry points that take a RelBias:
+    the grid size is the bias's, else the caller's P, else all S keys"""
+    if rel is None:
+        return 0, (S if P is None else P), None, 0, 0, None, None, None, 0
+    return 1, rel.P, rel.gcode, rel.code_bias, rel.rel2d.shape[1], rel.rel2d, rel.rel1d, rel.relx, rel.grid_w
+
+
+def attn_fwd(q, k, v, pos_q, pos_k, out, lse, B, H, T, S, rel=None, causal=False, P=None, dense_bias=None,
+             gain=None):
+    """q/k/v/out: [B, T|S, *] bf16 row-strided views (head h at cols h*64..); pos_q/pos_k: [T|S, H*64]."""
+    rel_mode, P, gcode, code_bias, n2d, rel2d, rel1d, relx, grid_w = _rel_fields(rel, P, S)
+    rc = lib().ifseg_attn_fwd(_ptr(q), _ptr(k), _ptr(v), _ptr(pos_q), _ptr(pos_k), _ptr(out), _ptr(lse), c_int(B),
+                              c_int(H), c_int(T), c_int(S), c_int(q.stride(1)), c_int(k.stride(1)), c_int(v.stride(1)),
+                              c_int(out.stride(1)), c_int(pos_q.stride(0) if pos_q is not None else 0),
+                              c_int(pos_k.stride(0) if pos_k is not None else 0), c_ll(q.stride(0)), c_ll(k.stride(0)),
+                              c_ll(v.stride(0)), c_ll(out.stride(0)), c_int(rel_mode), c_int(P), _ptr(gcode),
+                              c_int(code_bias), c_int(n2d), _ptr(rel2d), _ptr(rel1d), _ptr(relx),
+                              c_int(1 if causal else 0), _ptr(dense_bias), _ptr(_f32(gain)), c_int(grid_w),
+                              c_int(dense_bias.stride(1) if dense_bias is not None else 0), _stream())
     _check(rc, "attn_fwd")
     return out
 
@@ -359,14 +355,12 @@ def attn_bwd(q, k, v, pos_q, pos_k, out, dout, lse, delta, dq, dk, dv, dpq_part,
     a = _AttnBwdArgs()
     a.dgain_rows = _p(dgain_rows)
     assert all(t is None or t.dtype == torch.bfloat16 for t in (dpq_part, dpk_part)), "abs-pos partials are bf16"
-    if rel is not None:
-        P = rel.P
-    if P is None:
-        P = S
+    a.rel_mode, P, gcode, a.code_bias, a.n2d, rel2d, rel1d, relx, a.grid_w = _rel_fields(rel, P, S)
     for name, t in (("q", q), ("k", k), ("v", v), ("pos_q", pos_q), ("pos_k", pos_k), ("out", out), ("dout", dout),
                     ("lse", lse), ("delta", delta), ("dq", dq), ("dk", dk), ("dv", dv), ("dpos_q_part", dpq_part),
                     ("dpos_k_part", dpk_part), ("gain", _f32(gain)), ("drel2d_part", drel2d_part),
-                    ("drel1d_part", drel1d_part), ("drelx_part", drelx_part)):
+                    ("drel1d_part", drel1d_part), ("drelx_part", drelx_part), ("gcode", gcode), ("rel2d", rel2d),
+                    ("rel1d", rel1d), ("relx", relx)):
         setattr(a, name, _p(t))
     a.B, a.H, a.T, a.S = B, H, T, S
     a.ldq, a.ldk, a.ldv = q.stride(1), k.stride(1), v.stride(1)
@@ -375,16 +369,23 @@ def attn_bwd(q, k, v, pos_q, pos_k, out, dout, lse, delta, dq, dk, dv, dpq_part,
     a.ldout, a.lddo, a.lddq, a.lddk, a.lddv = out.stride(1), dout.stride(1), dq.stride(1), dk.stride(1), dv.stride(1)
     a.q_bs, a.k_bs, a.v_bs, a.out_bs = q.stride(0), k.stride(0), v.stride(0), out.stride(0)
     a.do_bs, a.dq_bs, a.dk_bs, a.dv_bs = dout.stride(0), dq.stride(0), dk.stride(0), dv.stride(0)
-    a.rel_mode = 1 if rel is not None else 0
     a.P, a.causal, a.nparts = P, 1 if causal else 0, nparts
-    if rel is not None:
-        a.code_bias, a.n2d = rel.code_bias, rel.rel2d.shape[1]
-        a.gcode, a.rel2d, a.rel1d, a.relx = _p(rel.gcode), _p(rel.rel2d), _p(rel.rel1d), _p(rel.relx)
-        a.grid_w = rel.grid_w
     a.dq_scale, a.dpq_scale = dq_scale, dpq_scale
     a.phases = phases
     rc = lib().ifseg_attn_bwd(ctypes.byref(a), _stream())
     _check(rc, "attn_bwd")
+
+
+def attn_delta(out, dout, delta, B, H, T):
+    """delta [B, H, T] fp32 = rowsum(dout * out) per head: the delta launch of ifseg_attn_bwd alone, for both kernel
+    generations.  Only the fields that launch reads are filled; the others stay zero, which passes the entry point's checks."""
+    a = _AttnBwdArgs()
+    a.out, a.dout, a.delta = _p(out), _p(dout), _p(delta)
+    a.B, a.H, a.T, a.S, a.P = B, H, T, T, T
+    a.ldout, a.lddo, a.out_bs, a.do_bs = out.stride(1), dout.stride(1), out.stride(0), dout.stride(0)
+    a.dq_scale, a.dpq_scale = 1.0, 1.0
+    a.phases = ATTN_BWD_DELTA
+    _check(lib().ifseg_attn_bwd(ctypes.byref(a), _stream()), "attn_bwd")
 
 
 # ---- attention backward with the batch as a workgroup's inner dimension (csrc/attention_bi.hip)
@@ -402,18 +403,12 @@ class DenseBias:
 
 
 def attn_dense_bias(dense, pos_q, pos_k, rel=None, causal=False, P=None):
-    if rel is not None:
-        P = rel.P
-    if P is None:
-        P = dense.S
+    rel_mode, P, gcode, code_bias, n2d, rel2d, rel1d, relx, _ = _rel_fields(rel, P, dense.S)
     rc = lib().ifseg_attn_dense_bias(
         _ptr(pos_q), _ptr(pos_k), c_int(pos_q.stride(0) if pos_q is not None else 0),
         c_int(pos_k.stride(0) if pos_k is not None else 0), c_int(dense.H), c_int(dense.T), c_int(dense.S),
-        c_int(1 if rel is not None else 0), c_int(P), _ptr(rel.gcode) if rel is not None else None,
-        c_int(rel.code_bias if rel is not None else 0), c_int(rel.rel2d.shape[1] if rel is not None else 0),
-        _ptr(rel.rel2d) if rel is not None else None, _ptr(rel.rel1d) if rel is not None else None,
-        _ptr(rel.relx) if rel is not None else None, c_int(1 if causal else 0), _ptr(dense.D), c_int(dense.Sp),
-        c_int(dense.Tp), _stream())
+        c_int(rel_mode), c_int(P), _ptr(gcode), c_int(code_bias), c_int(n2d), _ptr(rel2d), _ptr(rel1d), _ptr(relx),
+        c_int(1 if causal else 0), _ptr(dense.D), c_int(dense.Sp), c_int(dense.Tp), _stream())
     _check(rc, "attn_dense_bias")
     return dense
 
@@ -448,25 +443,31 @@ def _kvlen(kv_len, B):
     return kv_len
 
 
+def _bi_args(q, k, v, dense, B, H, T, S, causal, P, gain, kv_len, drop):
+    """the fields the two batch-inner entry points share"""
+    a = _AttnBiArgs()
+    a.q, a.k, a.v, a.D, a.gain = _p(q), _p(k), _p(v), _p(dense.D), _p(_f32(gain))
+    a.B, a.H, a.T, a.S, a.Sp, a.Tp = B, H, T, S, dense.Sp, dense.Tp
+    a.ldq, a.ldk, a.ldv = q.stride(1), k.stride(1), v.stride(1)
+    a.q_bs, a.k_bs, a.v_bs = q.stride(0), k.stride(0), v.stride(0)
+    a.causal, a.P = (1 if causal else 0), (P if P is not None else S)
+    a.kv_len = _p(_kvlen(kv_len, B))
+    _attn_drop(a, drop)
+    return a
+
+
 def attn_bwd_bi(q, k, v, dout, lse, delta, dense, dq, dk, dv, dbias, B, H, T, S, causal=False, P=None, gain=None,
                 dq_scale=1.0, phases=0, dgain_rows=None, kv_len=None, drop=None):
     """dbias: bf16 [ceil(B/4), H, T, dense.Sp] -- zero-filled once by the caller when causal (skipped blocks are not written);
     kv_len: int32 [B] valid key counts (key padding), None = no padding"""
-    a = _AttnBiArgs()
-    for name, t in (("q", q), ("k", k), ("v", v), ("dout", dout), ("lse", lse), ("delta", delta), ("D", dense.D),
-                    ("gain", _f32(gain)), ("dq", dq), ("dk", dk), ("dv", dv), ("dbias", dbias)):
-        setattr(a, name, _p(t))
+    a = _bi_args(q, k, v, dense, B, H, T, S, causal, P, gain, kv_len, drop)
+    a.dout, a.lse, a.delta = _p(dout), _p(lse), _p(delta)
+    a.dq, a.dk, a.dv, a.dbias = _p(dq), _p(dk), _p(dv), _p(dbias)
     assert dbias.dtype == torch.bfloat16 and tuple(dbias.shape) == ((B + 3) // 4, H, T, dense.Sp) and dbias.is_contiguous()
-    a.B, a.H, a.T, a.S, a.Sp, a.Tp = B, H, T, S, dense.Sp, dense.Tp
-    a.ldq, a.ldk, a.ldv, a.lddo = q.stride(1), k.stride(1), v.stride(1), dout.stride(1)
-    a.lddq, a.lddk, a.lddv = dq.stride(1), dk.stride(1), dv.stride(1)
-    a.q_bs, a.k_bs, a.v_bs, a.do_bs = q.stride(0), k.stride(0), v.stride(0), dout.stride(0)
-    a.dq_bs, a.dk_bs, a.dv_bs = dq.stride(0), dk.stride(0), dv.stride(0)
-    a.causal, a.P = (1 if causal else 0), (P if P is not None else S)
+    a.lddo, a.lddq, a.lddk, a.lddv = dout.stride(1), dq.stride(1), dk.stride(1), dv.stride(1)
+    a.do_bs, a.dq_bs, a.dk_bs, a.dv_bs = dout.stride(0), dq.stride(0), dk.stride(0), dv.stride(0)
     a.dq_scale, a.phases = dq_scale, phases
     a.dgain_rows = _p(dgain_rows)
-    a.kv_len = _p(_kvlen(kv_len, B))
-    _attn_drop(a, drop)
     _check(lib().ifseg_attn_bwd_bi(ctypes.byref(a), _stream()), "attn_bwd_bi")
 
 
@@ -476,15 +477,8 @@ def dbias_nparts():
 
 def attn_fwd_bi(q, k, v, dense, out, lse, B, H, T, S, causal=False, P=None, gain=None, kv_len=None, drop=None):
     """out = gain softmax(q k^T + dense.D) v, four batch elements per workgroup (csrc/attention_bi.hip)"""
-    a = _AttnBiArgs()
-    for name, t in (("q", q), ("k", k), ("v", v), ("lse", lse), ("D", dense.D), ("gain", _f32(gain)), ("out", out)):
-        setattr(a, name, _p(t))
-    a.B, a.H, a.T, a.S, a.Sp, a.Tp = B, H, T, S, dense.Sp, dense.Tp
-    a.ldq, a.ldk, a.ldv, a.ldout = q.stride(1), k.stride(1), v.stride(1), out.stride(1)
-    a.q_bs, a.k_bs, a.v_bs, a.out_bs = q.stride(0), k.stride(0), v.stride(0), out.stride(0)
-    a.causal, a.P = (1 if causal else 0), (P if P is not None else S)
-    a.kv_len = _p(_kvlen(kv_len, B))
-    _attn_drop(a, drop)
+    a = _bi_args(q, k, v, dense, B, H, T, S, causal, P, gain, kv_len, drop)
+    a.lse, a.out, a.ldout, a.out_bs = _p(lse), _p(out), out.stride(1), out.stride(0)
     _check(lib().ifseg_attn_fwd_bi(ctypes.byref(a), _stream()), "attn_fwd_bi")
     return out
 

@@ -450,26 +450,42 @@ class HipEngine:
             e.record(self._side)
             torch.cuda.current_stream().wait_event(e)
 
-    def _dense_bias(self, tag, H, T, S, pq, pk, rel, causal, P):
-        """dense batch-invariant bias operands of one attention (hip.DenseBias), built on the CURRENT stream"""
+    def _dense_ws(self, tag, H, T, S):
+        """the workspace's dense bias operand of one attention -> (hip.DenseBias, whether it was allocated just now)"""
         key = "dense_" + tag
         d = self.ws.get(key)
         if d is None or (d.H, d.T, d.S) != (H, T, S):
-            d = hip.DenseBias(H, T, S, self.device)
-            self.ws[key] = d
+            d = self.ws[key] = hip.DenseBias(H, T, S, self.device)
+            return d, True
+        return d, False
+
+    def _dense_bias(self, tag, H, T, S, pq, pk, rel, causal, P):
+        """dense batch-invariant bias operands of one attention (hip.DenseBias), built on the CURRENT stream"""
+        d, _ = self._dense_ws(tag, H, T, S)
         hip.attn_dense_bias(d, pq, pk, rel=rel, causal=causal, P=P)
         return d
 
     def _dense_from(self, tag, H, T, S, bias):
         """a dense bias operand from a ready fp32 [H, T, S] tensor (training on a resized grid: models/segofa/resized.py)"""
-        key = "dense_" + tag
-        d = self.ws.get(key)
-        if d is None or (d.H, d.T, d.S) != (H, T, S):
-            d = hip.DenseBias(H, T, S, self.device)
+        d, new = self._dense_ws(tag, H, T, S)
+        if new:
             d.D.fill_(float("-inf"))              # rows / columns of the padding stay masked
-            self.ws[key] = d
         d.D[:, :T, :S].copy_(bias)
         return d
+
+    def _dense_layer(self, ctx, tag, T, S, pq, pk, rel, causal, P, bias=None):
+        """(side stream) one attention's dense operand into ctx["dense"][tag] and its event: from the kernels' own operands, or
+        (`bias`, resized grid) from a ready fp32 [H, T, S] tensor"""
+        H = self.cfg.heads
+        ctx["dense"][tag] = (self._dense_bias(tag, H, T, S, pq, pk, rel, causal, P) if bias is None
+                             else self._dense_from(tag, H, T, S, bias))
+        self._dense_built(ctx, tag)
+
+    @staticmethod
+    def _rel(g, P, w, tabs, l):
+        """layer l's rel-pos bias operands from the stacks' delta tables `tabs` = (2-d, 1-d, cross) on a grid P = h * w"""
+        r2, r1, rx = tabs
+        return hip.RelBias(P, g["gcode"], g["code_bias"], r2[l], r1[l], rx[l], grid_w=w)
 
     def _dense_built(self, ctx, tag):
         """(side stream) one event per dense bias: the forward attention of that layer waits for ITS operand only"""
@@ -1037,22 +1053,21 @@ class HipEngine:
         ctx["dense"] = {}
         if resized:
             bi_which = ["e", "d", "c"]
-            with self._wgrad():          # parameters only: torch ops on [H, T, T] tensors (models/segofa/resized.py), side stream
-                bufs = dict(self.model.named_buffers())
-                absb = R.abs_bias(ctx["e_pq"], ctx["e_pk"], H)
-                for l in range(cfg.enc_layers):
-                    relb = R.encoder_rel_bias(W("%stoken_rel_pos_table_list.%d.weight" % (e, l)).float(),
-                                              W("%simage_rel_pos_table_list.%d.weight" % (e, l)).float(),
-                                              bufs["encoder.token_rp_bucket"], bufs["encoder.image_rp_bucket"], (h, w), oh, bsz, L)
-                    ctx["dense"]["e%d" % l] = self._dense_from(("e%d" % l), H, T, T, absb + relb)
-                    self._dense_built(ctx, "e%d" % l)
-        elif bi and "e" in bi_which:
-            # parameters only: every layer's dense bias on the side stream, under the first blocks of the forward
+        if bi and "e" in bi_which:
+            # parameters only: every layer's dense bias on the side stream, under the first blocks of the forward (resized grid:
+            # torch ops on [H, T, T] tensors, models/segofa/resized.py)
             with self._wgrad():
+                if resized:
+                    bufs = dict(self.model.named_buffers())
+                    absb = R.abs_bias(ctx["e_pq"], ctx["e_pk"], H)
                 for l in range(cfg.enc_layers):
-                    rel = hip.RelBias(P, g["gcode"], g["code_bias"], e_r2[l], e_r1[l], e_rx[l], grid_w=w)
-                    ctx["dense"]["e%d" % l] = self._dense_bias("e%d" % l, H, T, T, ctx["e_pq"], ctx["e_pk"], rel, False, P)
-                    self._dense_built(ctx, "e%d" % l)
+                    if resized:
+                        relb = R.encoder_rel_bias(W("%stoken_rel_pos_table_list.%d.weight" % (e, l)).float(),
+                                                  W("%simage_rel_pos_table_list.%d.weight" % (e, l)).float(),
+                                                  bufs["encoder.token_rp_bucket"], bufs["encoder.image_rp_bucket"], (h, w), oh, bsz, L)
+                        self._dense_layer(ctx, "e%d" % l, T, T, None, None, None, False, None, bias=absb + relb)
+                    else:
+                        self._dense_layer(ctx, "e%d" % l, T, T, ctx["e_pq"], ctx["e_pk"], self._rel(g, P, w, (e_r2, e_r1, e_rx), l), False, P)
         # (profiles/round6_early_decoder_dense_ab.txt: -0.11 ms per step; a pending deferred optimizer keeps the late place)
         if need_grad and bi and self.overlap and not self._popt:
             self._dec_pos_dense(ctx, g, pos_all, scaling, bi, bi_which, resized)
@@ -1068,7 +1083,7 @@ class HipEngine:
             p = "%slayers.%d." % (e, l)
             tg = "e%d" % l
             self._params_wait([tg])
-            rel = None if resized else hip.RelBias(P, g["gcode"], g["code_bias"], e_r2[l], e_r1[l], e_rx[l], grid_w=w)
+            rel = None if resized else self._rel(g, P, w, (e_r2, e_r1, e_rx), l)
             x, xn = self._self_block_fwd(tg, p, "self_attn", "self_attn_layer_norm", "attn_ln", x, B, T,
                                          ctx["e_pq"], ctx["e_pk"], rel, False, scaling, site=("e", l, 0), xn_pre=x_pre,
                                          next_ln=(p + "final_layer_norm", tg + "_fln1", buf(tg + "_fxn", (B * T, C))))
@@ -1123,13 +1138,13 @@ class HipEngine:
         if "d_cpq" not in ctx:       # (not already done ahead of the encoder layers)
             self._dec_pos_dense(ctx, g, pos_all, scaling, bi, bi_which, resized)
         cpq, cpk, causal = ctx["d_cpq"], ctx["d_cpk"], ctx["d_causal"]
-        d_r2, d_r1, d_rx = ctx["d_rel"]
+        d_rel = ctx["d_rel"]
         y_pre = None
         for l in range(cfg.dec_layers):
             p = "%slayers.%d." % (d, l)
             tg = "d%d" % l
             # (resized grid: the causal mask is inside the dense operand, the kernels walk every block)
-            rel = None if resized else hip.RelBias(P, g["gcode"], g["code_bias"], d_r2[l], d_r1[l], d_rx[l], grid_w=w)
+            rel = None if resized else self._rel(g, P, w, d_rel, l)
             y, yn = self._self_block_fwd(tg, p, "self_attn", "self_attn_layer_norm", "self_attn_ln", y, B, Td,
                                          ctx["d_spq"], ctx["d_spk"], rel, causal and not resized, scaling, site=("d", l, 0), xn_pre=y_pre,
                                          next_ln=(p + "encoder_attn_layer_norm", tg + "_cln1", buf(tg + "_cyn", (B * Td, C))))
@@ -1190,37 +1205,26 @@ class HipEngine:
         d_r2, d_r1, d_rx = self._rel_tables_all(
             "d_seg", ["%sseg_rel_pos_table_list.%d.weight" % (d, l) for l in range(cfg.dec_layers)],
             [(True, g["dec_idx2d"]), (True, g["dec_idx1d"]), (True, g["dec_idxx"])])
-        if resized:
+        if bi:
+            # every self attention's operand, and the cross attentions' one (no per-layer part, decoder_module.py:556-558) behind
+            # layer 0's: the first decoder layer's cross attention follows its self attention
+            order = list(range(cfg.dec_layers if "d" in bi_which else 0))
+            if "c" in bi_which:
+                order.insert(1, "c")
             with self._wgrad():
-                bufs = dict(self.model.named_buffers())
-                absb = R.abs_bias(ctx["d_spq"], ctx["d_spk"], H)
-                if causal:
-                    absb = absb.masked_fill(R.causal_mask(P, dev)[None], float("-inf"))
-                for l in range(cfg.dec_layers):
-                    relb = R.decoder_rel_bias(W("%sseg_rel_pos_table_list.%d.weight" % (d, l)).float(), bufs["decoder.seg_rp_bucket"], (h, w), sb)
-                    ctx["dense"]["d%d" % l] = self._dense_from("d%d" % l, H, Td, Td, absb + relb)
-                    self._dense_built(ctx, "d%d" % l)
-                    if l == 0:
-                        ctx["dense"]["dc"] = self._dense_bias("dc", H, Td, T, cpq, cpk, None, False, None)
-                        self._dense_built(ctx, "dc")
-                if self.overlap:
-                    if getattr(self, "_dense_ev", None) is None:
-                        self._dense_ev = torch.cuda.Event()
-                    self._dense_ev.record(self._side)
-                    ctx["dense_ready"] = self._dense_ev
-        elif bi:
-            with self._wgrad():
-                for l in range(cfg.dec_layers if "d" in bi_which else 0):
-                    rel = hip.RelBias(P, g["gcode"], g["code_bias"], d_r2[l], d_r1[l], d_rx[l], grid_w=w)
-                    ctx["dense"]["d%d" % l] = self._dense_bias("d%d" % l, H, Td, Td, ctx["d_spq"], ctx["d_spk"], rel, causal, P)
-                    self._dense_built(ctx, "d%d" % l)
-                    if l == 0 and "c" in bi_which:      # (the first decoder layer's cross attention follows its self attention)
-                        ctx["dense"]["dc"] = self._dense_bias("dc", H, Td, T, cpq, cpk, None, False, None)
-                        self._dense_built(ctx, "dc")
-                # the cross-attention bias has no per-layer part (decoder_module.py:556-558): one operand for all layers
-                if "c" in bi_which and "dc" not in ctx["dense"]:
-                    ctx["dense"]["dc"] = self._dense_bias("dc", H, Td, T, cpq, cpk, None, False, None)
-                    self._dense_built(ctx, "dc")
+                if resized:      # (bi_which is e+d+c) torch ops on [H, Td, Td] tensors, models/segofa/resized.py
+                    bufs = dict(self.model.named_buffers())
+                    absb = R.abs_bias(ctx["d_spq"], ctx["d_spk"], H)
+                    if causal:
+                        absb = absb.masked_fill(R.causal_mask(P, dev)[None], float("-inf"))
+                for l in order:
+                    if l == "c":
+                        self._dense_layer(ctx, "dc", Td, T, cpq, cpk, None, False, None)
+                    elif resized:
+                        relb = R.decoder_rel_bias(W("%sseg_rel_pos_table_list.%d.weight" % (d, l)).float(), bufs["decoder.seg_rp_bucket"], (h, w), sb)
+                        self._dense_layer(ctx, "d%d" % l, Td, Td, None, None, None, False, None, bias=absb + relb)
+                    else:
+                        self._dense_layer(ctx, "d%d" % l, Td, Td, ctx["d_spq"], ctx["d_spk"], self._rel(g, P, w, (d_r2, d_r1, d_rx), l), causal, P)
                 if self.overlap:        # (a dedicated event: the ring of `_ev` wraps around long before the backward waits for it)
                     if getattr(self, "_dense_ev", None) is None:
                         self._dense_ev = torch.cuda.Event()
@@ -1366,17 +1370,48 @@ class HipEngine:
         kind, l, k = site
         return 16 + (l * 4 + k) * 2 + (0 if kind == "e" else 1)
 
+    def _pre_ln(self, x, pname, stats_tag, out_name, rows):
+        """the pre-LN of an attention block whose predecessor did not already produce it"""
+        C = self.cfg.embed_dim
+        xn = self.buf(out_name, (rows, C))
+        mu, rs = self._ln_stats(stats_tag, rows)
+        hip.ln_fwd(x.view(rows, C), self.Wf(pname + ".weight"), self.Wf(pname + ".bias"), xn, mu, rs)
+        return xn
+
+    def _attn_fwd(self, tag, dense_tag, q, k, v, pq, pk, o, lse, B, T, S, rel, causal, gain, kv_len, dense=None):
+        """the attention launch of a forward block.  tag: the attention's name in the backward (e<l>, d<l>, d<l>c); dense_tag: its
+        operand in ctx["dense"] (the batch-inner generation, when the forward built one); dense: the fp32 bias of the
+        evaluation path on a resized grid (round-3 generation)"""
+        H = self.cfg.heads
+        dd = self.ctx_building.get("dense", {}).get(dense_tag) if (self.bi_fwd and self.ctx_building is not None) else None
+        if dd is not None:
+            # the forward of the batch-inner formulation: dense bias tile shared by four batch elements, no abs-pos columns in
+            # the contraction, no table look-ups, one path for every grid width (csrc/attention_bi.hip: attn_bi_fwd_kernel)
+            self._dense_wait(dense_tag)
+            # (measured and dropped: the round-3 kernel seeded from the dense bias by global loads, 94.2 vs 91.3 ms on C4)
+            hip.attn_fwd_bi(q, k, v, dd, o, lse, B, H, T, S, causal=causal, P=rel.P if rel is not None else None, gain=gain,
+                            kv_len=kv_len, drop=self._attn_drop(tag, self.attn_drop_p))
+        elif self.attn_drop_p:
+            raise NotImplementedError("ifseg_amd HIP engine: attention dropout needs the batch-inner attention kernels")
+        else:
+            hip.attn_fwd(q, k, v, pq, pk, o, lse, B, H, T, S, rel=rel, causal=causal, gain=gain, dense_bias=dense)
+
+    def _attn_tail(self, a_, o, x, a_name, out_name, ln, stats_tag, B, T, site, next_ln):
+        """out_proj, then out = x + drop(LN(a)) and, with next_ln, the next block's pre-LN (`_post_ln`) -> (a, out, that pre-LN)"""
+        C = self.cfg.embed_dim
+        a = self.buf(a_name, (B * T, C))
+        hip.linear_fwd(o.view(B * T, C), self.W(a_ + ".out_proj.weight"), self.W(a_ + ".out_proj.bias"), out=a)
+        out = self.buf(out_name, (B, T, C))
+        drop = self._dropargs(self._site_id(site), self._dp(*site), T) if (self.drop_on and site is not None) else None
+        return a, out, self._post_ln(a, ln, stats_tag, x.view(B * T, C), out.view(B * T, C), drop, B * T, next_ln)
+
     def _self_block_fwd(self, tg, p, attn, ln1, ln2, x, B, T, pq, pk, rel, causal, scaling, dense=None, site=None,
                         next_ln=None, xn_pre=None):
         """xn_pre: ln1(x) if the previous layer already produced it.  -> (block output, pre-LN of the next block or None)"""
         C, H = self.cfg.embed_dim, self.cfg.heads
-        W, Wf, buf = self.W, self.Wf, self.buf
+        buf = self.buf
         a_ = p + attn
-        xn = xn_pre
-        if xn is None:
-            xn = buf(tg + "_xn", (B * T, C))
-            mu, rs = self._ln_stats(tg + "_ln1", B * T)
-            hip.ln_fwd(x.view(B * T, C), Wf(p + ln1 + ".weight"), Wf(p + ln1 + ".bias"), xn, mu, rs)
+        xn = xn_pre if xn_pre is not None else self._pre_ln(x, p + ln1, tg + "_ln1", tg + "_xn", B * T)
         qkv = buf(tg + "_qkv", (B, T, 3 * C))
         hip.linear_fwd(xn, self._fused(self.p16, a_ + ".q_proj.weight", 3 * C, C),
                        self._fused(self.p16, a_ + ".q_proj.bias", 3 * C), out=qkv.view(B * T, 3 * C),
@@ -1384,38 +1419,20 @@ class HipEngine:
         o = buf(tg + "_o", (B, T, C))
         lse = buf(tg + "_lse", (B, H, T), torch.float32)
         gain = self._gain32(tg + "_sa", a_ + ".c_attn")
-        dd = self.ctx_building.get("dense", {}).get(tg) if (self.bi_fwd and self.ctx_building is not None) else None
-        if dd is not None:
-            # the forward of the batch-inner formulation: dense bias tile shared by four batch elements, no abs-pos columns in
-            # the contraction, no table look-ups, one path for every grid width (csrc/attention_bi.hip: attn_bi_fwd_kernel)
-            self._dense_wait(tg)
-            # (measured and dropped: the round-3 kernel seeded from the dense bias by global loads, 94.2 vs 91.3 ms on C4)
-            hip.attn_fwd_bi(qkv[:, :, :C], qkv[:, :, C:2 * C], qkv[:, :, 2 * C:], dd, o, lse, B, H, T, T, causal=causal,
-                            P=rel.P if rel is not None else None, gain=gain, kv_len=self.ctx_building.get("klen") if tg[0] == "e" else None,
-                            drop=self._attn_drop(tg, self.attn_drop_p))
-        elif self.attn_drop_p:
-            raise NotImplementedError("ifseg_amd HIP engine: attention dropout needs the batch-inner attention kernels")
-        else:
-            hip.attn_fwd(qkv[:, :, :C], qkv[:, :, C:2 * C], qkv[:, :, 2 * C:], pq, pk, o, lse, B, H, T, T, rel=rel,
-                         causal=causal, gain=gain, dense_bias=dense)
-        a = buf(tg + "_a", (B * T, C))
-        hip.linear_fwd(o.view(B * T, C), W(a_ + ".out_proj.weight"), W(a_ + ".out_proj.bias"), out=a)
-        x1 = buf(tg + "_x1", (B, T, C))
-        drop = self._dropargs(self._site_id(site), self._dp(*site), T) if (self.drop_on and site is not None) else None
-        nxt = self._post_ln(a, p + ln2, tg + "_ln2", x.view(B * T, C), x1.view(B * T, C), drop, B * T, next_ln)
+        # key padding: the encoder's positions are the keys of its self attentions (and of the cross attentions)
+        klen = self.ctx_building.get("klen") if (tg[0] == "e" and self.ctx_building is not None) else None
+        self._attn_fwd(tg, tg, qkv[:, :, :C], qkv[:, :, C:2 * C], qkv[:, :, 2 * C:], pq, pk, o, lse, B, T, T, rel, causal, gain,
+                       klen, dense)
+        a, x1, nxt = self._attn_tail(a_, o, x, tg + "_a", tg + "_x1", p + ln2, tg + "_ln2", B, T, site, next_ln)
         self._save(tg + "_sa", x=x, xn=xn, qkv=qkv, o=o, lse=lse, a=a, rel=rel, gain=gain, causal=causal, site=site)
         return x1, nxt
 
     def _cross_block_fwd(self, tg, p, y1, enc_out, B, Td, Te, cpq, cpk, scaling, site=None, yn_pre=None, next_ln=None):
         """yn_pre: encoder_attn_layer_norm(y1) if the previous block already produced it.  -> (y2, next pre-LN or None)"""
         C, H = self.cfg.embed_dim, self.cfg.heads
-        W, Wf, buf = self.W, self.Wf, self.buf
+        W, buf = self.W, self.buf
         a_ = p + "encoder_attn"
-        yn = yn_pre
-        if yn is None:
-            yn = buf(tg + "_cyn", (B * Td, C))
-            mu, rs = self._ln_stats(tg + "_cln1", B * Td)
-            hip.ln_fwd(y1.view(B * Td, C), Wf(p + "encoder_attn_layer_norm.weight"), Wf(p + "encoder_attn_layer_norm.bias"), yn, mu, rs)
+        yn = yn_pre if yn_pre is not None else self._pre_ln(y1, p + "encoder_attn_layer_norm", tg + "_cln1", tg + "_cyn", B * Td)
         q = buf(tg + "_cq", (B, Td, C))
         hip.linear_fwd(yn, W(a_ + ".q_proj.weight"), W(a_ + ".q_proj.bias"), out=q.view(B * Td, C), alpha=scaling)
         kv = buf(tg + "_ckv", (B, Te, 2 * C))
@@ -1428,20 +1445,9 @@ class HipEngine:
         o = buf(tg + "_co", (B, Td, C))
         lse = buf(tg + "_clse", (B, H, Td), torch.float32)
         gain = self._gain32(tg + "_ca", a_ + ".c_attn")
-        dd = self.ctx_building.get("dense", {}).get("dc") if (self.bi_fwd and self.ctx_building is not None) else None
-        if dd is not None:
-            self._dense_wait("dc")
-            hip.attn_fwd_bi(q, kv[:, :, :C], kv[:, :, C:], dd, o, lse, B, H, Td, Te, gain=gain, kv_len=self.ctx_building.get("klen"),
-                            drop=self._attn_drop(tg + "c", self.attn_drop_p))
-        elif self.attn_drop_p:
-            raise NotImplementedError("ifseg_amd HIP engine: attention dropout needs the batch-inner attention kernels")
-        else:
-            hip.attn_fwd(q, kv[:, :, :C], kv[:, :, C:], cpq, cpk, o, lse, B, H, Td, Te, gain=gain)
-        a = buf(tg + "_ca_a", (B * Td, C))
-        hip.linear_fwd(o.view(B * Td, C), W(a_ + ".out_proj.weight"), W(a_ + ".out_proj.bias"), out=a)
-        y2 = buf(tg + "_y2", (B, Td, C))
-        drop = self._dropargs(self._site_id(site), self._dp(*site), Td) if (self.drop_on and site is not None) else None
-        nxt = self._post_ln(a, p + "cross_attn_ln", tg + "_cln2", y1.view(B * Td, C), y2.view(B * Td, C), drop, B * Td, next_ln)
+        klen = self.ctx_building.get("klen") if self.ctx_building is not None else None
+        self._attn_fwd(tg + "c", "dc", q, kv[:, :, :C], kv[:, :, C:], cpq, cpk, o, lse, B, Td, Te, None, False, gain, klen)
+        a, y2, nxt = self._attn_tail(a_, o, y1, tg + "_ca_a", tg + "_y2", p + "cross_attn_ln", tg + "_cln2", B, Td, site, next_ln)
         self._save(tg + "_ca", x=y1, xn=yn, q=q, kv=kv, o=o, lse=lse, a=a, gain=gain, site=site)
         return y2, nxt
 
@@ -1634,11 +1640,39 @@ class HipEngine:
         hip.linear_dx_rowdot(da, W(a_ + ".out_proj.weight"), do.view(rows, C), o.view(rows, C), delta, T)
         return delta
 
+    def _attn_t0(self):
+        """the start of an attn_bwd_timing event pair on the main stream (bench.py's roofline object), None when this attention
+        is not sampled"""
+        timing = self.attn_bwd_timing
+        timing["seen"] += 1
+        if (timing["seen"] - 1) % timing["stride"]:
+            return None
+        t0 = torch.cuda.Event(enable_timing=True)
+        t0.record()
+        return t0
+
+    def _attn_t1(self, t0, B, H, T, S):
+        t1 = torch.cuda.Event(enable_timing=True)
+        t1.record()
+        self.attn_bwd_timing["pairs"].append((t0, t1, 8.0 * 64 * T * S * B * H))   # dV, dP, dK, dQ of the reference at d = 64
+
+    def _dgain_rows(self, B, H, T):
+        """-> (per-row terms of d c_attn (sum_j P dP = dO . O_pre) that the dQ kernels write: no division by c_attn anywhere;
+        the [H] ones that stand in `attn_bwd_reduce` for the gain the round-3 formula divided delta by)"""
+        ones = self.ws.get("ones_h")
+        if ones is None or ones.numel() != H:
+            ones = self.ws["ones_h"] = torch.ones(H, dtype=torch.float32, device=self.device)
+        return self.gbuf("g_dgain_rows_%d" % T, (B, H, T), torch.float32), ones
+
+    def _table_parts(self, rel, rel_grads, parts):
+        """(side stream) -> [(partial tables, bucket index, accumulator)] of the rel-pos tables this attention trains"""
+        if rel is None:
+            return []
+        return [(part, idx, self._table_acc(tabname)) for (tabname, idx), part in zip(rel_grads, parts) if tabname is not None]
+
     def _attn_core_bwd(self, tag, q, k, v, pq, pk, o, lse, do, dq, dk, dv, B, T, S, rel, causal, gain, gain_name,
                        scaling, dpq_acc, dpk_acc, first_pos, rel_grads, delta=None, dense=None):
-        cfg = self.cfg
-        C, H = cfg.embed_dim, cfg.heads
-        buf = self.buf
+        C, H = self.cfg.embed_dim, self.cfg.heads
         gbuf = self.gbuf
         have_delta = delta is not None
         if not have_delta:
@@ -1661,27 +1695,16 @@ class HipEngine:
         if rel is not None:
             parts = [gbuf("g_relp%d_%d" % (i, t.shape[1]), (H, nparts, t.shape[1]), torch.float32)
                      for i, t in enumerate((rel.rel2d, rel.rel1d, rel.relx))]
-        # per-row terms of d c_attn (sum_j P dP = dO . O_pre) from the dQ kernel: no division by c_attn anywhere
-        dgr = gbuf("g_dgain_rows_%d" % T, (B, H, T), torch.float32)
-        ones = self.ws.get("ones_h")
-        if ones is None or ones.numel() != H:
-            ones = self.ws["ones_h"] = torch.ones(H, dtype=torch.float32, device=self.device)
+        dgr, ones = self._dgain_rows(B, H, T)
         kw = dict(rel=rel, causal=causal, gain=gain, dq_scale=scaling, dpq_scale=scaling, drel2d_part=parts[0],
                   drel1d_part=parts[1], drelx_part=parts[2], nparts=nparts, dgain_rows=dgr)
         args = (q, k, v, pq, pk, o, do, lse, delta, dq, dk, dv, dpq_part, dpk_part, B, H, T, S)
-        timing = self.attn_bwd_timing
-        if timing is not None:
-            timing["seen"] += 1
-            if (timing["seen"] - 1) % timing["stride"]:
-                timing = None
-            else:       # one event pair on the main stream around delta + dK/dV + dQ (bench.py's roofline object)
-                t0 = torch.cuda.Event(enable_timing=True)
-                t0.record()
+        t0 = self._attn_t0() if self.attn_bwd_timing is not None else None        # around delta + dK/dV + dQ
         if self.overlap and not lab.get("DQ_SERIAL"):
             # dK/dV and dQ are independent once delta exists; each leaves its last round of workgroups partly
             # empty (864 workgroups on 512 slots), so they run on two streams and fill each other's holes
             if not have_delta:
-                hip.attn_bwd(*args, phases=hip.ATTN_BWD_DELTA, **kw)
+                hip.attn_delta(o, do, delta, B, H, T)
             with self._fork(self._dq_stream_get()):
                 if "dq" not in _EXP_SKIP:
                     hip.attn_bwd(*args, phases=hip.ATTN_BWD_DQ, **kw)
@@ -1692,21 +1715,14 @@ class HipEngine:
             torch.cuda.current_stream().wait_event(dq_done)
         else:
             hip.attn_bwd(*args, phases=(hip.ATTN_BWD_DKV | hip.ATTN_BWD_DQ) if have_delta else 0, **kw)
-        if timing is not None:
-            t1 = torch.cuda.Event(enable_timing=True)
-            t1.record()
-            timing["pairs"].append((t0, t1, 8.0 * 64 * T * S * B * H))   # dV, dP, dK, dQ of the reference at d = 64
+        if t0 is not None:
+            self._attn_t1(t0, B, H, T, S)
+
         def reductions():
-            # one launch: batch sums of the abs-pos operand gradients, d c_attn[h] = sum_{b,t} delta / c_attn[h], and for
+            # one launch: batch sums of the abs-pos operand gradients, d c_attn[h] = the sum of the dQ kernel's row terms, and for
             # every rel-pos table the sum over the workgroup partials scattered into its bucket accumulator
-            tables = []
-            if rel is not None:
-                for (tabname, idx), part in zip(rel_grads, parts):
-                    if tabname is not None:
-                        tables.append((part, idx, self._table_acc(tabname)))
-            # (d c_attn[h] = sum of the dQ kernel's row terms: `ones` stands in for the gain the round-3 formula divided delta by)
             hip.attn_bwd_reduce(B, H, T, S, C, dpq_part, dpk_part, dpq_acc, dpk_acc, not first_pos, dgr, ones,
-                                self.G(gain_name), nparts if rel is not None else 1, tables)
+                                self.G(gain_name), nparts if rel is not None else 1, self._table_parts(rel, rel_grads, parts))
         if "reduce" not in _EXP_SKIP:
             self._side_do(reductions)
 
@@ -1730,21 +1746,10 @@ class HipEngine:
             dbias.zero_()
             dbias._ifseg_zeroed = True
         if not have_delta:
-            hip.attn_bwd(q, k, v, None, None, o, do, lse, delta, dq, dk, dv, None, None, B, H, T, S, phases=hip.ATTN_BWD_DELTA)
-        timing = self.attn_bwd_timing
-        if timing is not None:
-            timing["seen"] += 1
-            if (timing["seen"] - 1) % timing["stride"]:
-                timing = None
-            else:
-                t0 = torch.cuda.Event(enable_timing=True)
-                t0.record()
+            hip.attn_delta(o, do, delta, B, H, T)
+        t0 = self._attn_t0() if self.attn_bwd_timing is not None else None        # around the dQ and dK/dV kernels
         P = rel.P if rel is not None else None
-        # per-row terms of d c_attn (sum_j P dP = dO . O_pre) from the dQ kernel: no division by c_attn anywhere
-        dgr = gbuf("g_dgain_rows_%d" % T, (B, H, T), torch.float32)
-        ones = self.ws.get("ones_h")
-        if ones is None or ones.numel() != H:
-            ones = self.ws["ones_h"] = torch.ones(H, dtype=torch.float32, device=self.device)
+        dgr, ones = self._dgain_rows(B, H, T)
         ph = 0
         if "dq" in _EXP_SKIP:
             ph = hip.ATTN_BWD_DKV
@@ -1753,10 +1758,8 @@ class HipEngine:
         if ph >= 0:
             hip.attn_bwd_bi(q, k, v, do, lse, delta, dense, dq, dk, dv, dbias, B, H, T, S, causal=causal, P=P, gain=gain,
                             dq_scale=scaling, phases=ph, dgain_rows=dgr, kv_len=kv_len, drop=adrop)
-        if timing is not None:
-            t1 = torch.cuda.Event(enable_timing=True)
-            t1.record()
-            timing["pairs"].append((t0, t1, 8.0 * 64 * T * S * B * H))
+        if t0 is not None:
+            self._attn_t1(t0, B, H, T, S)
         parts = [None, None, None]
         if rel is not None:
             parts = [gbuf("g_relg%d_%d" % (i, t.shape[1]), (H, hip.dbias_nparts(), t.shape[1]), torch.float32)
@@ -1768,15 +1771,9 @@ class HipEngine:
                 kw = dict(P=rel.P, grid_h=rel.P // rel.grid_w, grid_w=rel.grid_w, drel2d=parts[0], drel1d=parts[1], drelx=parts[2])
             hip.attn_dbias_grads(dbias, S, pos_q=pq, pos_k=pk, dpq_acc=dpq_acc, dpk_acc=dpk_acc, accumulate_pos=not first_pos,
                                  dpq_scale=scaling, causal=causal, **kw)
-            tables = []
-            if rel is not None:
-                for (tabname, idx), part in zip(rel_grads, parts):
-                    if tabname is not None:
-                        tables.append((part, idx, self._table_acc(tabname)))
             # bucket scatter of the delta-table gradients and d c_attn (no abs-pos partials: nothing to sum over the batch)
-            # (d c_attn[h] = sum of the dQ kernel's row terms: `ones` stands in for the gain the round-3 formula divides by)
             hip.attn_bwd_reduce(B, H, T, S, C, None, None, dpq_acc, dpk_acc, True, dgr, ones, self.G(gain_name),
-                                hip.dbias_nparts(), tables)
+                                hip.dbias_nparts(), self._table_parts(rel, rel_grads, parts))
             if self.ctx.get("resized") and rel_grads is not None:
                 self._resized_rel_grads(rel_grads, dbias, T)
         if "reduce" not in _EXP_SKIP:
@@ -1828,25 +1825,38 @@ class HipEngine:
         if flat is not None:
             flat.zero_()
 
+    def _attn_out_bwd(self, s, a_, dy, da_pre, ln, stats_tag, B, T):
+        """the post-LN backward of dy (with the adjoint of the dropout fused into the forward LN) unless the previous block of
+        the backward already ran it (da_pre), then the out_proj backward -> (dO, delta or None as `_out_proj_bwd`)"""
+        C = self.cfg.embed_dim
+        rows = B * T
+        da = da_pre
+        if da is None:
+            da = self.gbuf("g_da_%d" % rows, (rows, C))
+            drop = None
+            if self.drop_on and s["site"] is not None:
+                drop = self._dropargs(self._site_id(s["site"]), self._dp(*s["site"]), T)
+            self._ln_bwd(dy, s["a"], ln, stats_tag, da, drop=drop)
+        do = self.buf("g_do_%d" % rows, (B, T, C))
+        return do, self._out_proj_bwd(da, s["o"], a_, do, B, T)
+
+    def _pre_ln_bwd(self, dxn, s, ln, stats_tag, out_name, dy, nxt):
+        """the block's input gradient: the pre-LN backward of dxn plus the residual branch's dy (`_ln_bwd_fused`)"""
+        rows, C = dxn.shape
+        dx = self.gbuf(out_name % rows, (rows, C))
+        self._ln_bwd_fused(dxn, s["x"].view(rows, C), ln, stats_tag, dx, dy, nxt)
+        return dx
+
     def _self_block_bwd(self, tg, p, attn, ln1, ln2, dx1, B, T, pq, pk, scaling, dpq_acc, dpk_acc, first_pos, rel_grads,
                         da_pre=None, nxt=None):
         """da_pre: the post-LN backward of dx1 if the previous block of the backward already ran it; nxt: `_ln_bwd_fused`"""
         C = self.cfg.embed_dim
         s = self.saved[tg + "_sa"]
-        W, Wf, G, buf = self.W, self.Wf, self.G, self.buf
+        G, buf, gbuf = self.G, self.buf, self.gbuf
         a_ = p + attn
         rows = B * T
         self._bt = tg + "s"
-        gbuf = self.gbuf
-        da = da_pre
-        if da is None:
-            da = gbuf("g_da_%d" % rows, (rows, C))
-            drop = None
-            if self.drop_on and s["site"] is not None:       # adjoint of the dropout fused into the forward LN
-                drop = self._dropargs(self._site_id(s["site"]), self._dp(*s["site"]), T)
-            self._ln_bwd(dx1, s["a"], p + ln2, tg + "_ln2", da, drop=drop)
-        do = buf("g_do_%d" % rows, (B, T, C))
-        delta = self._out_proj_bwd(da, s["o"], a_, do, B, T)
+        do, delta = self._attn_out_bwd(s, a_, dx1, da_pre, p + ln2, tg + "_ln2", B, T)
         dqkv = gbuf("g_dqkv_%d" % rows, (B, T, 3 * C))
         qkv = s["qkv"]
         self._attn_core_bwd(tg, qkv[:, :, :C], qkv[:, :, C:2 * C], qkv[:, :, 2 * C:], pq, pk, s["o"], s["lse"], do,
@@ -1859,28 +1869,18 @@ class HipEngine:
                          self._fused(self.g16, a_ + ".q_proj.bias", 3 * C), dx_out=dxn)
         if self.kproj_fix:
             self._kfix_tasks.append((G(a_ + ".k_proj.weight"), G(a_ + ".k_proj.bias"), s["xn"], tg))
-        dx = gbuf("g_dx0_%d" % rows, (rows, C))
-        self._ln_bwd_fused(dxn, s["x"].view(rows, C), p + ln1, tg + "_ln1", dx, dx1, nxt)
-        return dx                # the caller flushes the side queue together with the layer's hook
+        # (the caller flushes the side queue together with the layer's hook)
+        return self._pre_ln_bwd(dxn, s, p + ln1, tg + "_ln1", "g_dx0_%d", dx1, nxt)
 
     def _cross_block_bwd(self, tg, p, dy2, B, Td, Te, cpq, cpk, scaling, d_enc_out, first_cross, dcpq_acc, dcpk_acc,
                          da_pre=None, nxt=None):
         C = self.cfg.embed_dim
         s = self.saved[tg + "_ca"]
-        W, Wf, G, buf = self.W, self.Wf, self.G, self.buf
+        W, G, buf, gbuf = self.W, self.G, self.buf, self.gbuf
         a_ = p + "encoder_attn"
         rows = B * Td
         self._bt = tg + "c"
-        gbuf = self.gbuf
-        da = da_pre
-        if da is None:
-            da = gbuf("g_da_%d" % rows, (rows, C))
-            drop = None
-            if self.drop_on and s["site"] is not None:
-                drop = self._dropargs(self._site_id(s["site"]), self._dp(*s["site"]), Td)
-            self._ln_bwd(dy2, s["a"], p + "cross_attn_ln", tg + "_cln2", da, drop=drop)
-        do = buf("g_do_%d" % rows, (B, Td, C))
-        delta = self._out_proj_bwd(da, s["o"], a_, do, B, Td)
+        do, delta = self._attn_out_bwd(s, a_, dy2, da_pre, p + "cross_attn_ln", tg + "_cln2", B, Td)
         dq = gbuf("g_cdq", (B, Td, C))
         dkv = gbuf("g_cdkv", (B, Te, 2 * C))
         kv = s["kv"]
@@ -1910,8 +1910,7 @@ class HipEngine:
                              dx_accumulate=not first_cross)
         if self.kproj_fix:       # (every layer's K|V projection reads the same encoder output: one column sum per step)
             self._kfix_tasks.append((G(a_ + ".k_proj.weight"), G(a_ + ".k_proj.bias"), enc2d, "enc_out"))
-        dy1 = gbuf("g_dy1c_%d" % rows, (rows, C))
-        self._ln_bwd_fused(dyn, s["x"].view(rows, C), p + "encoder_attn_layer_norm", tg + "_cln1", dy1, dy2, nxt)
+        dy1 = self._pre_ln_bwd(dyn, s, p + "encoder_attn_layer_norm", tg + "_cln1", "g_dy1c_%d", dy2, nxt)
         self._side_flush()
         return dy1
 

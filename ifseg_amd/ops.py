@@ -392,7 +392,7 @@ def _bwd_bi(dout, q, k, v, gain, kv_len, out, lse, dense, causal, P, dropout_p, 
     dgr = torch.empty(B, H, T, dtype=torch.float32, device=dev)
     # causal launches skip the 32-blocks above the diagonal: those entries of the slabs are never written
     slabs = (torch.zeros if zero_slabs else torch.empty)((B + 3) // 4, H, T, dense.Sp, dtype=BF, device=dev)
-    hip.attn_bwd(q, k, v, None, None, out, dout, lse, delta, dq, dk, dv, None, None, B, H, T, S, phases=hip.ATTN_BWD_DELTA)
+    hip.attn_delta(out, dout, delta, B, H, T)
     with _seed_as_given():
         hip.attn_bwd_bi(q, k, v, dout, lse, delta, dense, dq, dk, dv, slabs, B, H, T, S, causal=causal, P=P, gain=gain,
                         dgain_rows=dgr, kv_len=kv_len, drop=(dropout_p, seed) if dropout_p > 0 else None)

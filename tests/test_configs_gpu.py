@@ -217,6 +217,72 @@ def test_base_config1_with_the_round3_attention_kernels(golden_dir, monkeypatch)
     assert not m.engine.ctx.get("dense")
 
 
+def _attention_launches(monkeypatch):
+    """one training step of the fixture model (2 + 2 layers, 128 x 128 images: an 8-wide grid, the smallest the batch-inner
+    path takes; B = 2, dropout off) with call-through recorders on the attention bindings -> (engine, [(name, phases or None)])"""
+    import test_model_gpu as T
+    from ifseg_amd import hip
+    calls = []
+
+    def record(name):
+        real = getattr(hip, name)
+
+        def through(*a, **k):
+            calls.append((name, k.get("phases") or None))
+            return real(*a, **k)
+        monkeypatch.setattr(hip, name, through)
+    for name in ("attn_fwd", "attn_fwd_bi", "attn_bwd", "attn_bwd_bi", "attn_delta", "attn_dense_bias", "attn_dbias_grads",
+                 "attn_bwd_reduce"):
+        record(name)
+    dev = torch.device("cuda:0")
+    ocfg = O.fixture_config()
+    m = T._build(ocfg, O.procedural_state_dict(ocfg), dev).train()
+    loss, _, _ = _crit(ocfg)(m, _sample(O.synthetic_batch(ocfg, 2, 12), dev))
+    loss.backward()
+    torch.cuda.synchronize()
+    assert m.engine.ctx["w"] == 8 and m.engine.overlap and not m.engine.attn_drop_p
+    return m.engine, calls
+
+
+def test_attention_block_dispatch_by_launch_count(monkeypatch):
+    """The folded attention block launches what the engine's docstrings say, no more and no less.  With A = enc_layers +
+    2 dec_layers attentions per step -- default: one dense operand per self attention and ONE for all cross attentions
+    (`_dec_pos_dense`), every forward and backward through the batch-inner bindings (one attn_bwd_bi with phases 0 each), and
+    behind each the two side-stream launches (`_attn_core_bwd_bi`); IFSEG_ATTN_BI=0: none of that, A round-3 forwards, dQ and
+    dK/dV as two launches on two streams (`_attn_core_bwd`, overlap on), one reduction each.  delta comes from the out_proj
+    dX GEMM's epilogue (`_out_proj_bwd`) when eng.delta_fused, else from one delta launch per attention."""
+    from collections import Counter
+    from ifseg_amd import hip
+    ocfg = O.fixture_config()
+    E, D = ocfg.enc_layers, ocfg.dec_layers
+    A = E + 2 * D
+
+    def deltas(eng, calls):
+        n = sum(1 for name, ph in calls if name == "attn_delta" or (name == "attn_bwd" and ph == hip.ATTN_BWD_DELTA))
+        assert n == (0 if eng.delta_fused else A), (n, eng.delta_fused)
+
+    eng, calls = _attention_launches(monkeypatch)
+    n = Counter(name for name, _ in calls)
+    print("default:", sorted(Counter(calls).items(), key=str))
+    assert n["attn_dense_bias"] == E + D + 1 and n["attn_fwd_bi"] == A and n["attn_fwd"] == 0
+    assert [ph for name, ph in calls if name == "attn_bwd_bi"] == [None] * A
+    assert n["attn_dbias_grads"] == A and n["attn_bwd_reduce"] == A
+    assert not [ph for name, ph in calls if name == "attn_bwd" and ph != hip.ATTN_BWD_DELTA]      # no DQ / DKV phase
+    deltas(eng, calls)
+
+    monkeypatch.undo()
+    monkeypatch.setenv("IFSEG_LAB", "1")
+    monkeypatch.setenv("IFSEG_ATTN_BI", "0")
+    eng, calls = _attention_launches(monkeypatch)
+    n = Counter(name for name, _ in calls)
+    print("IFSEG_ATTN_BI=0:", sorted(Counter(calls).items(), key=str))
+    assert not any(n[k] for k in ("attn_fwd_bi", "attn_bwd_bi", "attn_dense_bias", "attn_dbias_grads"))
+    assert n["attn_fwd"] == A and n["attn_bwd_reduce"] == A
+    ph = Counter(ph for name, ph in calls if name == "attn_bwd")
+    assert ph[hip.ATTN_BWD_DQ] == A and ph[hip.ATTN_BWD_DKV] == A and set(ph) <= {hip.ATTN_BWD_DQ, hip.ATTN_BWD_DKV, hip.ATTN_BWD_DELTA}
+    deltas(eng, calls)
+
+
 def test_base_config3_geometry_vs_reference_golden(golden_dir):
     """BASELINE configs[2] per-GPU geometry: Base width, 150 ADE20K classes, L = 215 prompt tokens, T_enc = 1239 (a T
     that is a multiple of nothing), log-spaced token buckets beyond |i-j| = 128 (reference outputs: base_c3.npz, generated
