@@ -283,6 +283,29 @@ def train_load_reference(images, labels, params, P, nseg, seg_id_offset, mean=HA
     return norm, target, torch.stack(qs), torch.stack(q0s)
 
 
+def train_plane_reference(planes, params, P):
+    """CPU specification of hip.train_load_plane.  planes: uint8 [H0, W0] each (per-pixel loss weights, or anything else that
+    must follow the label map), params int32 [B, 16] -> uint8 [B, P*P]: the label tap of `train_load_reference`
+    (src = min(dst in // out, in - 1) on the resized grid, the window at the record's offset, mirrored under flip) on the
+    plane's own bytes, nothing remapped."""
+    P = int(P)
+    B = len(planes)
+    params = torch.as_tensor(params).cpu()
+    if tuple(params.shape) != (B, RECORD):
+        raise ValueError("train transform: %d planes, records %s" % (B, tuple(params.shape)))
+    out = torch.empty(B, P * P, dtype=torch.uint8)
+    for b in range(B):
+        pl, rec = torch.as_tensor(planes[b]).cpu(), params[b].tolist()
+        if pl.dtype != torch.uint8 or pl.dim() != 2:
+            raise ValueError("train transform: planes must be uint8 [H0, W0], got %s %s" % (pl.dtype, tuple(pl.shape)))
+        H0, W0 = pl.shape
+        new_h, new_w, off_h, off_w = check_record(rec, H0, W0, P)
+        ys = off_h + torch.arange(P)
+        xs = off_w + (torch.arange(P - 1, -1, -1) if rec[R_FLIP] else torch.arange(P))
+        out[b] = pl[nearest_axis(new_h, H0)[ys]][:, nearest_axis(new_w, W0)[xs]].reshape(-1)
+    return out
+
+
 class TrainTransform:
     def __init__(self, P, nseg, seg_id_offset, mean=HALF, std=HALF, seed=1, device="cpu", photometric=True, flip=True,
                  ratio_range=(0.5, 2.0), raw_labels=True, dtype=torch.float32, reverse_channels=False, eos=EOS):
@@ -326,10 +349,32 @@ class TrainTransform:
         return hip.train_draw(labels, self.P, self.nseg, self.seed, first_ordinal, self.ratio_range, self.photometric, self.flip,
                               self.raw_labels, table=table)
 
-    def apply(self, images, labels, params):
-        """the caller's records -> (patch_images [B, 3, P, P], target int64 [B, P*P + 1])"""
+    def _planes(self, weights, labels):
+        """per-pixel weight planes: uint8 [H0, W0] of their label map's size, moved to the transform's device"""
+        if len(weights) != len(labels):
+            raise ValueError("TrainTransform: %d weight planes for %d label maps" % (len(weights), len(labels)))
+        for w, lab in zip(weights, labels):
+            if not torch.is_tensor(w) or w.dtype != torch.uint8 or tuple(w.shape) != tuple(lab.shape):
+                raise ValueError("TrainTransform: weight planes must be uint8 [H0, W0] of the label map's size, got %s for %s"
+                                 % ((w.dtype, tuple(w.shape)) if torch.is_tensor(w) else type(w), tuple(lab.shape)))
+        if self.device.type == "cpu":
+            return list(weights)
+        return [w.to(self.device, non_blocking=True).contiguous() for w in weights]
+
+    def _apply_planes(self, planes, params):
+        if self.device.type == "cpu":
+            return train_plane_reference(planes, params, self.P)
+        from . import hip
+        return hip.train_load_plane(planes, params, self.P)
+
+    def apply(self, images, labels, params, weights=None):
+        """the caller's records -> (patch_images [B, 3, P, P], target int64 [B, P*P + 1]); with `weights` (uint8 [H0, W0]
+        per sample) a third tensor, uint8 [B, P*P]: the planes sampled where the labels were (`train_plane_reference`)"""
         images, labels = self._sources(images, labels)
-        return self._apply(images, labels, params)
+        if weights is None:
+            return self._apply(images, labels, params)
+        planes = self._planes(weights, labels)
+        return tuple(self._apply(images, labels, params)) + (self._apply_planes(planes, params),)
 
     def _apply(self, images, labels, params, table=None):
         if self.device.type == "cpu":
@@ -339,6 +384,10 @@ class TrainTransform:
         return hip.train_load(images, labels, params, self.P, self.nseg, self.seg_id_offset, self.mean, self.std,
                               self.reverse_channels, self.raw_labels, self.dtype, self.eos, table=table)
 
-    def __call__(self, images, labels, first_ordinal):
+    def __call__(self, images, labels, first_ordinal, weights=None):
         images, labels = self._sources(images, labels)
-        return self._apply(images, labels, self._draw(labels, first_ordinal))
+        if weights is None:
+            return self._apply(images, labels, self._draw(labels, first_ordinal))
+        planes = self._planes(weights, labels)
+        params = self._draw(labels, first_ordinal)
+        return tuple(self._apply(images, labels, params)) + (self._apply_planes(planes, params),)

@@ -11,6 +11,10 @@ The loss math is one fused HIP kernel pair (csrc/loss.hip: upsample + CE + gradi
 histograms) whenever the image is exactly 16x the feature grid and
 label smoothing is off; otherwise the same math runs as stock PyTorch ops (eval on odd
 image sizes).  ``compute_loss_torch`` is kept as the in-framework reference of the kernel.
+
+Opt-in weights (self-training on pseudo-labels): ``SegCriterion(class_weight=, weight_norm=)`` and a sample's
+``"target_weight"`` (uint8 per pixel) select the weighted instantiation of the same kernel; ``weighted_loss_reference``
+states the rule.  Without them every call is the unweighted one.
 """
 from dataclasses import dataclass, field
 from typing import Optional
@@ -51,12 +55,91 @@ class SegCriterionConfig(DataclassBase):
     resnet_iters: int = _f(0, "resnet filtering iterations")
 
 
+PAD, EOS = 1, 2
+WEIGHT_NORMS = ("weights", "pixels")
+
+
+def check_weight_norm(weight_norm):
+    if weight_norm not in WEIGHT_NORMS:
+        raise ValueError("weight_norm must be one of %s, got %r" % (WEIGHT_NORMS, weight_norm))
+    return weight_norm == "pixels"
+
+
+def check_class_weight(class_weight, nseg):
+    """-> fp32 (fp64 stays fp64) [nseg] on the device it was given on (or the CPU), or None.  Negative, NaN or infinite entries, another length:
+    ValueError.  Reads the values: one host round trip for a device tensor, so callers check once, not per step."""
+    if class_weight is None:
+        return None
+    cw = torch.as_tensor(class_weight)
+    if cw.dtype == torch.bool or cw.dtype.is_complex or tuple(cw.shape) != (nseg,):
+        raise ValueError("class_weight must be %d real numbers, got %s %s" % (nseg, cw.dtype, tuple(cw.shape)))
+    cw = cw.detach()
+    if cw.dtype != torch.float64:
+        cw = cw.to(torch.float32)
+    if not bool((torch.isfinite(cw) & (cw >= 0)).all()):
+        raise ValueError("class_weight must be finite and non-negative (zeros allowed)")
+    return cw.contiguous()
+
+
+def check_pixel_weight(pixel_weight, B, npix):
+    """the per-pixel weight plane: uint8 [B, npix], q in 0 .. 255 (ValueError otherwise); None passes"""
+    if pixel_weight is None:
+        return None
+    if not torch.is_tensor(pixel_weight) or pixel_weight.dtype != torch.uint8 or tuple(pixel_weight.shape) != (B, npix):
+        raise ValueError("pixel_weight must be uint8 [%d, %d], got %s" % (
+            B, npix, (pixel_weight.dtype, tuple(pixel_weight.shape)) if torch.is_tensor(pixel_weight) else type(pixel_weight)))
+    return pixel_weight
+
+
+def weighted_loss_reference(scores_up, target, seg_id_offset, nseg, class_weight=None, pixel_weight=None, label_smoothing=0.0,
+                            weight_norm="weights"):
+    """Specification of the weighted fused criterion (csrc/loss.hip, ifseg_seg_loss_tiles_weighted), runs on any device and is
+    differentiable in scores_up.  scores_up [B, H*W, n] (already upsampled; a trailing eos row is ignored), target int64
+    [B, H*W (+1)], pixel_weight uint8 [B, H*W] (q_i in 0 .. 255; None: 1), class_weight fp32 [n] >= 0 (None: ones).
+    A pixel is valid iff its target is a class (not pad / eos / <seg_n>: `compute_loss_torch`'s mask).  With
+      l_i = F.cross_entropy(v_i, y_i, weight=cw, reduction="none", label_smoothing=eps)
+          = (1 - eps) cw[y_i] (lse_i - v_i[y_i]) + (eps / n) sum_c cw[c] (lse_i - v_i[c]):
+      loss = sum_valid q_i l_i / Z,   Z = sum_valid q_i cw[y_i]             weight_norm="weights": torch's weighted mean, so the
+                                                                           loss does not depend on the scale of q
+                                      Z = qmax N_valid, qmax = 255 | 1      weight_norm="pixels": with | without a plane; a batch
+                                                                           of unsure pixels gives a smaller gradient
+    and loss = 0 (with a zero gradient) when Z = 0."""
+    norm_pixels = check_weight_norm(weight_norm)
+    B, n = scores_up.shape[0], int(nseg)
+    if scores_up.dim() != 3 or scores_up.shape[2] != n:
+        raise ValueError("weighted_loss_reference: scores_up must be [B, H*W, %d], got %s" % (n, tuple(scores_up.shape)))
+    npix = min(scores_up.shape[1], target.shape[1])
+    if torch.is_tensor(pixel_weight) and pixel_weight.dim() == 2 and pixel_weight.shape[1] == npix - 1:
+        npix -= 1                                   # scores and target both carry the eos row: the plane says so
+    if target.dtype != torch.int64 or target.dim() != 2 or target.shape[0] != B or target.shape[1] - npix not in (0, 1) \
+            or scores_up.shape[1] - npix not in (0, 1):
+        raise ValueError("weighted_loss_reference: target must be int64 [B, H*W (+1)], got %s %s for scores %s"
+                         % (target.dtype, tuple(target.shape), tuple(scores_up.shape)))
+    check_pixel_weight(pixel_weight, B, npix)
+    cw = check_class_weight(class_weight, n)
+    dev, dt = scores_up.device, scores_up.dtype
+    tgt = target[:, :npix].to(dev)
+    mask = ~((tgt == PAD) | (tgt == seg_id_offset + n) | (tgt == EOS))
+    s, t = scores_up[:, :npix][mask], tgt[mask] - seg_id_offset
+    cw = cw.to(dev, dt) if cw is not None else None
+    l = F.cross_entropy(s, t, weight=cw, reduction="none", label_smoothing=float(label_smoothing))
+    q = pixel_weight.to(dev)[mask].to(dt) if pixel_weight is not None else torch.ones_like(l)
+    if norm_pixels:
+        Z = (255.0 if pixel_weight is not None else 1.0) * l.new_tensor(float(t.numel()))
+    else:
+        Z = (q * cw[t]).sum() if cw is not None else q.sum()
+    num = (q * l).sum()
+    return torch.where(Z > 0, num / torch.where(Z > 0, Z, torch.ones_like(Z)), num * 0.0)
+
+
 class _FusedSegLossFn(torch.autograd.Function):
     """loss = mean CE(bilinear_x16(logits[:, :P]), target); backward hands out the gradient the
-    forward kernel already produced."""
+    forward kernel already produced.  pixel_weight / class_weight / norm_pixels: the weighted kernel
+    (`weighted_loss_reference`); all of them None / False: the unweighted launch, as before they existed."""
 
     @staticmethod
-    def forward(ctx, logits, logits_pad, target, hp, wp, H, W, nseg, seg0, bufs, eps=0.0):
+    def forward(ctx, logits, logits_pad, target, hp, wp, H, W, nseg, seg0, bufs, eps=0.0, pixel_weight=None,
+                class_weight=None, norm_pixels=False):
         B = logits_pad.shape[0]
         dev = logits_pad.device
         n_tiles = B * hp * wp
@@ -71,8 +154,13 @@ class _FusedSegLossFn(torch.autograd.Function):
             bufs["dl"] = torch.empty_like(logits_pad)
             bufs["loss"] = torch.empty(1, dtype=torch.float32, device=dev)
             bufs["bad"] = torch.zeros(1, dtype=torch.int32, device=dev)
-        hip.seg_loss(logits_pad, target, hp, wp, H, W, nseg, seg0, bufs["tile"], bufs["sp"], bufs["stats"],
-                     bufs["dl"], bufs["loss"], bad_label=bufs["bad"], label_smoothing=float(eps))
+        if pixel_weight is None and class_weight is None and not norm_pixels:
+            hip.seg_loss(logits_pad, target, hp, wp, H, W, nseg, seg0, bufs["tile"], bufs["sp"], bufs["stats"],
+                         bufs["dl"], bufs["loss"], bad_label=bufs["bad"], label_smoothing=float(eps))
+        else:
+            hip.seg_loss_weighted(logits_pad, target, hp, wp, H, W, nseg, seg0, bufs["tile"], bufs["sp"], bufs["stats"],
+                                  bufs["dl"], bufs["loss"], pixel_weight=pixel_weight, class_weight=class_weight,
+                                  norm_pixels=norm_pixels, bad_label=bufs["bad"], label_smoothing=float(eps))
         ctx.dl = bufs["dl"]
         ctx.nseg = nseg
         # fresh tensors: callers keep them in logging outputs across calls (update_freq > 1, validation loops)
@@ -81,9 +169,9 @@ class _FusedSegLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gloss, gstats):
         g = ctx.dl[:, :, : ctx.nseg]
-        return g * gloss.to(g.dtype), None, None, None, None, None, None, None, None, None, None
+        return (g * gloss.to(g.dtype),) + (None,) * 13
 
-PAD, EOS = 1, 2
+
 FUSED_MAX_CLASSES = 512      # csrc/loss.hip NS_MAX
 
 
@@ -94,10 +182,12 @@ class SegCriterion(CriterionBase):
                  sample_patch_num=196, constraint_range=None, upscale_lprobs="true", unsupervised_segmentation="true",
                  criterion_update_freq=1, freeze_embedding_iter=-1, full_context_alignment="false",
                  init_seg_with_text="true", resnet_topk=3, resnet_prob_temperature=1.0, resnet_iters=0,
-                 num_seg_tokens=None, seg_id_offset=None):
+                 num_seg_tokens=None, seg_id_offset=None, class_weight=None, weight_norm="weights"):
         """Signature of the reference (seg_criterion.py:115-161; fairseq's `build_criterion` fills it from
         SegCriterionConfig by name).  `num_seg_tokens` / `seg_id_offset` stand in for `task.cfg.num_seg_tokens` and
-        `task.target_dictionary.index("<seg_0>")` when the criterion is used without a task."""
+        `task.target_dictionary.index("<seg_0>")` when the criterion is used without a task.  `class_weight` (n numbers >= 0,
+        F.cross_entropy's `weight`) and `weight_norm` ("weights" | "pixels": the normaliser of `weighted_loss_reference`) are
+        constructor keywords only as well; a sample that carries `"target_weight"` (uint8 [B, H*W]) is weighted per pixel."""
         super().__init__(task)
         self.sentence_avg = sentence_avg
         self.eps = label_smoothing
@@ -119,6 +209,11 @@ class SegCriterion(CriterionBase):
         if self.id2rawtext and len(self.id2rawtext) != self.num_seg:
             raise AssertionError("category_list names %d classes, num_seg_tokens is %d" % (len(self.id2rawtext), self.num_seg))
         self.padding_idx = PAD
+        self.class_weight = check_class_weight(class_weight, self.num_seg)
+        if self.class_weight is not None:
+            self.class_weight = self.class_weight.float()          # what the kernel reads
+        self.norm_pixels = check_weight_norm(weight_norm)
+        self.weight_norm = weight_norm
         # image-free samples drawn on the device (ifseg_amd/artificial.py).  The trainer sets the seed and, before every
         # micro-batch, the ordinal of its first sample (an int, or a device int64 word inside a captured step); without a
         # trainer the criterion counts the samples it has drawn.
@@ -269,12 +364,19 @@ class SegCriterion(CriterionBase):
         hp, wp = extra["encoder_returns"]["image_embed_shape"][0]
         h, w = sample["net_input"]["patch_images"].shape[-2:]
         pad = extra.get("logits_padded")
+        pw = check_pixel_weight(sample.get("target_weight"), target.shape[0], h * w)
         if (pad is not None and self.upscale_lprobs and h == 16 * hp and w == 16 * wp
                 and self.num_seg <= FUSED_MAX_CLASSES and target.shape[1] == h * w + 1):
             if not hasattr(self, bufs_name):
                 setattr(self, bufs_name, {})
-            loss, stats = _FusedSegLossFn.apply(scores_low, pad, target.contiguous(), hp, wp, h, w, self.num_seg,
-                                                self.seg_id_offset, getattr(self, bufs_name), self.eps)
+            if pw is None and self.class_weight is None:
+                loss, stats = _FusedSegLossFn.apply(scores_low, pad, target.contiguous(), hp, wp, h, w, self.num_seg,
+                                                    self.seg_id_offset, getattr(self, bufs_name), self.eps)
+            else:
+                loss, stats = _FusedSegLossFn.apply(scores_low, pad, target.contiguous(), hp, wp, h, w, self.num_seg,
+                                                    self.seg_id_offset, getattr(self, bufs_name), self.eps,
+                                                    pw.contiguous() if pw is not None else None,
+                                                    self._class_weight_on(pad.device), self.norm_pixels)
             # the loss kernel flags labels that are neither a class nor pad / eos / ignore (read back without a sync)
             model.engine.deferred_check(
                 getattr(self, bufs_name)["bad"], lambda t: ((t[0] != 0).clone(), t.zero_())[0],
@@ -299,9 +401,21 @@ class SegCriterion(CriterionBase):
         s = scores[~mask]
         metrics = dict(zip(("area_intersect", "area_pred_label", "area_label", "area_union"),
                            self.compute_metric(s.detach(), t.detach())))
-        loss = F.cross_entropy(s, t, label_smoothing=self.eps)
+        pw = check_pixel_weight(sample.get("target_weight"), target.shape[0], h * w)
+        if pw is None and self.class_weight is None:
+            loss = F.cross_entropy(s, t, label_smoothing=self.eps)
+        else:
+            loss = weighted_loss_reference(scores[:, :h * w], target, self.seg_id_offset, self.num_seg,
+                                           self._class_weight_on(scores.device), pw, self.eps, self.weight_norm)
         metrics["nll_loss"] = loss
         return loss, metrics, 1
+
+    def _class_weight_on(self, dev):
+        """the class weights on `dev` (moved there once), or None"""
+        cw = self.class_weight
+        if cw is not None and cw.device != dev:
+            cw = self.class_weight = cw.to(dev)
+        return cw
 
     @staticmethod
     def compute_metric(lprobs, target):

@@ -11,6 +11,13 @@
 // the adjoint of the interpolation is applied separably (over x, then over y) in LDS, giving
 // a [3][3][nseg] partial per tile; a second kernel gathers the <=9 partials of every cell.
 // No global atomics: deterministic.
+//
+// WT (ifseg_seg_loss_tiles_weighted): the same tile with a per-pixel weight q (uint8 plane, or 1) and a per-class weight cw
+// (fp32 [nseg] staged in LDS behind the histograms, or ones):
+//   l_i = (1 - eps) cw[y] (lse - v_y) + (eps / n) (lse sum_c cw[c] - sum_c cw[c] v_c)       F.cross_entropy(weight=cw)
+//   d_c = q (p_c A - [c = y] (1 - eps) cw[y] - (eps / n) cw[c]),   A = (1 - eps) cw[y] + (eps / n) sum_c cw[c]
+// sp[0] = sum q l, sp[1] = the tile's share of the normaliser (sum q cw[y], or qmax per valid pixel), so the reduction and the
+// gather kernel below serve both.  q enters by one multiplication each: a plane times two gives the same bits.
 #include "common.h"
 #include "prof.h"
 #include "../../include/ifseg_hip.h"
@@ -19,17 +26,21 @@ namespace {
 
 constexpr int TS = 16;       // pixels per cell side
 constexpr int CH = 16;       // classes per gradient chunk
-constexpr int NS_MAX = 512;  // max classes (LDS: 9 x (nseg | 1) floats + 3 x nseg ints, sized per launch)
+constexpr int NS_MAX = 512;  // max classes (LDS: 9 x (nseg | 1) floats + 3 x nseg ints (+ nseg floats, WT), sized per launch)
 
+template <bool WT>
 __global__ __launch_bounds__(256) void seg_loss_tile_kernel(const bf16_t* logits, int ldl, long long lbs,
                                                             const long long* target, long long tbs, int hp, int wp,
                                                             int W, int nseg, long long seg0, long long pad_id,
                                                             long long eos_id, float* tile_partial, float* stats_part,
-                                                            int* bad_label, float eps) {
+                                                            int* bad_label, float eps, const unsigned char* pixel_weight,
+                                                            long long pwbs, const float* class_weight, int norm_pixels) {
   extern __shared__ float dyn[];
   const int ls = nseg | 1;                   // row stride of the 3 x 3 cells' logits: odd, so the four taps of a pixel
   float* sLog = dyn;                         // (rows k apart) fall into different banks
   int* sHist = reinterpret_cast<int*>(dyn + 9 * ls);      // [3][nseg]
+  [[maybe_unused]] float* sCw = dyn + 9 * ls + 3 * nseg;  // [nseg] (WT)
+  [[maybe_unused]] __shared__ float sCwSum[4];
   __shared__ float sWY[TS][3], sWX[TS][3];
   __shared__ float sD[256][CH + 1];
   __shared__ float sE[TS][3][CH];
@@ -48,6 +59,16 @@ __global__ __launch_bounds__(256) void seg_loss_tile_kernel(const bf16_t* logits
     sLog[k * ls + c] = v;
   }
   for (int i = tid; i < 3 * nseg; i += 256) sHist[i] = 0;
+  if constexpr (WT) {
+    float part = 0.f;                                       // nseg <= 512: at most two classes per thread
+    for (int i = tid; i < nseg; i += 256) {
+      const float w = class_weight ? class_weight[i] : 1.f;
+      sCw[i] = w;
+      part += w;
+    }
+    part = warp_sum(part);
+    if ((tid & 63) == 0) sCwSum[tid >> 6] = part;
+  }
   if (tid < 2 * TS) {
     // source index of F.interpolate(mode='bilinear', align_corners=False): max((dst+0.5)/s-0.5, 0)
     const bool isx = tid >= TS;
@@ -98,14 +119,27 @@ __global__ __launch_bounds__(256) void seg_loss_tile_kernel(const bf16_t* logits
     if (v > m) { sum = sum * __expf(m - v) + 1.f; m = v; pred = c; }
     else sum += __expf(v - m);
     if (c == label) vl = v;
-    vall += v;
+    if constexpr (WT) vall += sCw[c] * v;                   // sum_c cw[c] v_c
+    else vall += v;
   }
   const float lse = m + __logf(sum);
   // F.cross_entropy(label_smoothing = eps): (1 - eps) * nll(label) + eps * mean_c nll(c)   (seg_criterion.py:269-287 with
   // --label-smoothing; eps == 0 keeps the plain expression, bit for bit)
   float lpix = valid ? (lse - vl) : 0.f, cnt = valid ? 1.f : 0.f;
   if (eps != 0.f && valid) lpix = (1.f - eps) * (lse - vl) + eps * (lse - vall / nseg);
-  const float hot = 1.f - eps, unif = eps / nseg;
+  float hot = 1.f - eps;
+  const float unif = eps / nseg;
+  [[maybe_unused]] float q = 0.f, soft = 1.f;
+  if constexpr (WT) {
+    const float scw = (sCwSum[0] + sCwSum[1]) + (sCwSum[2] + sCwSum[3]);
+    const float cwy = valid ? sCw[label] : 0.f;
+    if (valid) q = pixel_weight ? (float)pixel_weight[b * pwbs + (long long)(cy * TS + py) * W + (cx * TS + px)] : 1.f;
+    hot *= cwy;
+    soft = hot + unif * scw;
+    // every term of the pixel's loss before q, then q once
+    lpix = q * (hot * (lse - vl) + unif * (scw * lse - vall));
+    cnt = !valid ? 0.f : norm_pixels ? (pixel_weight ? 255.f : 1.f) : q * cwy;
+  }
   if (valid) {
     atomicAdd(&sHist[nseg + pred], 1);
     atomicAdd(&sHist[2 * nseg + label], 1);
@@ -121,7 +155,11 @@ __global__ __launch_bounds__(256) void seg_loss_tile_kernel(const bf16_t* logits
     for (int cc = 0; cc < CH; ++cc) {
       const int c = c0 + cc;
       float d = 0.f;
-      if (valid && c < nseg) d = __expf(value(c) - lse) - (c == label ? hot : 0.f) - unif;
+      if constexpr (WT) {
+        if (valid && c < nseg) d = q * (__expf(value(c) - lse) * soft - (c == label ? hot : 0.f) - unif * sCw[c]);
+      } else {
+        if (valid && c < nseg) d = __expf(value(c) - lse) - (c == label ? hot : 0.f) - unif;
+      }
       sD[tid][cc] = d;
     }
     __syncthreads();
@@ -188,9 +226,29 @@ extern "C" int ifseg_seg_loss_tiles(const void* logits, int ldl, long long logit
   if (H != hp * TS || W != wp * TS || nseg > NS_MAX || nseg < 1) return IFSEG_ERR_BAD_SHAPE;
   if (!(label_smoothing >= 0.f && label_smoothing <= 1.f)) return IFSEG_ERR_BAD_ARG;
   const size_t dyn = (size_t)(9 * (nseg | 1) + 3 * nseg) * 4;
-  hipLaunchKernelGGL(seg_loss_tile_kernel, dim3(B * hp * wp), dim3(256), dyn, (hipStream_t)stream,
+  hipLaunchKernelGGL(seg_loss_tile_kernel<false>, dim3(B * hp * wp), dim3(256), dyn, (hipStream_t)stream,
                      (const bf16_t*)logits, ldl, logits_bs, target, target_bs, hp, wp, W, nseg, seg_id_offset, pad_id,
-                     eos_id, tile_partial, stats_part, bad_label, label_smoothing);
+                     eos_id, tile_partial, stats_part, bad_label, label_smoothing, nullptr, 0ll, nullptr, 0);
+  IFSEG_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ifseg_seg_loss_tiles_weighted(const void* logits, int ldl, long long logits_bs, const long long* target,
+                                             long long target_bs, int B, int hp, int wp, int H, int W, int nseg,
+                                             long long seg_id_offset, long long pad_id, long long eos_id,
+                                             const unsigned char* pixel_weight, long long pw_bs, const float* class_weight,
+                                             int norm_pixels, float* tile_partial, float* stats_part, int* bad_label,
+                                             float label_smoothing, void* stream) {
+  (void)hipGetLastError();
+  if (H != hp * TS || W != wp * TS || nseg > NS_MAX || nseg < 1) return IFSEG_ERR_BAD_SHAPE;
+  if (!(label_smoothing >= 0.f && label_smoothing <= 1.f)) return IFSEG_ERR_BAD_ARG;
+  if (B < 1 || hp < 1 || wp < 1 || (pixel_weight && pw_bs < (long long)H * W) || ((size_t)class_weight & 3))
+    return IFSEG_ERR_BAD_ARG;
+  const size_t dyn = (size_t)(9 * (nseg | 1) + 3 * nseg + nseg) * 4;
+  hipLaunchKernelGGL(seg_loss_tile_kernel<true>, dim3(B * hp * wp), dim3(256), dyn, (hipStream_t)stream,
+                     (const bf16_t*)logits, ldl, logits_bs, target, target_bs, hp, wp, W, nseg, seg_id_offset, pad_id,
+                     eos_id, tile_partial, stats_part, bad_label, label_smoothing, pixel_weight, pw_bs, class_weight,
+                     norm_pixels ? 1 : 0);
   IFSEG_CHECK_LAUNCH();
   return 0;
 }

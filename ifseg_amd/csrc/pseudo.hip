@@ -66,7 +66,7 @@ template <typename L>
 __global__ __launch_bounds__(256) void seg_pseudo_kernel(const L* __restrict__ labels, const float* __restrict__ conf,
                                                          const int* __restrict__ thresholds, int n, int H, int W, int r, int raw,
                                                          unsigned char* __restrict__ out, unsigned long long* kept, int tiles_x,
-                                                         int tiles_y) {
+                                                         int tiles_y, unsigned char* __restrict__ weight) {
   __shared__ short halo[HALO_H * HALO_W];
   __shared__ int thr[PL_MAX_CLASSES];
   __shared__ uint32_t ktab[2 * PL_MAX_CLASSES];                   // [0, n) kept, [n, 2 n) predicted
@@ -91,8 +91,14 @@ __global__ __launch_bounds__(256) void seg_pseudo_kernel(const L* __restrict__ l
       l = halo_label(halo, ry, t.lane, r);
       in = (unsigned)l < (unsigned)n;
       const long long p = pix0 + (long long)(t.Y0 + ry) * W + t.X0 + t.lane;
-      if (in) keep = !halo_differs(halo, ry, t.lane, r, l) && conf_bin(conf[p]) >= thr[l];
+      int bin = 0;
+      if (in) {
+        bin = conf_bin(conf[p]);
+        keep = !halo_differs(halo, ry, t.lane, r, l) && bin >= thr[l];
+      }
       out[p] = keep ? (unsigned char)(l + raw) : (unsigned char)255;
+      // the loss weight of the pixel (ifseg_seg_loss_tiles_weighted): its confidence bin, at least 1 where it is kept
+      if (weight) weight[p] = keep ? (unsigned char)max(bin, 1) : (unsigned char)0;
     }
     bin_add(ktab, n + l, in);
     bin_add(ktab, l, keep);
@@ -127,8 +133,9 @@ extern "C" int ifseg_seg_conf_hist(const void* labels, int label_bytes, const fl
   return 0;
 }
 
-extern "C" int ifseg_seg_pseudo(const void* labels, int label_bytes, const float* conf, const int* thresholds, int n, int B, int H,
-                                int W, int boundary, int raw_labels, void* out, unsigned long long* kept, void* stream) {
+namespace {
+int seg_pseudo_launch(const void* labels, int label_bytes, const float* conf, const int* thresholds, int n, int B, int H, int W,
+                      int boundary, int raw_labels, void* out, unsigned long long* kept, unsigned char* weight, void* stream) {
   (void)hipGetLastError();
   if (!labels || !conf || !thresholds || !out || !kept || (label_bytes != 1 && label_bytes != 2)) return IFSEG_ERR_BAD_ARG;
   if ((label_bytes == 2 && ((size_t)labels & 1)) || ((size_t)conf & 3) || ((size_t)thresholds & 3) || ((size_t)kept & 7))
@@ -142,10 +149,24 @@ extern "C" int ifseg_seg_pseudo(const void* labels, int label_bytes, const float
   if (label_bytes == 1)
     hipLaunchKernelGGL(seg_pseudo_kernel<unsigned char>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
                        (const unsigned char*)labels, conf, thresholds, n, H, W, boundary, raw, (unsigned char*)out, kept, tiles_x,
-                       tiles_y);
+                       tiles_y, weight);
   else
     hipLaunchKernelGGL(seg_pseudo_kernel<short>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const short*)labels,
-                       conf, thresholds, n, H, W, boundary, raw, (unsigned char*)out, kept, tiles_x, tiles_y);
+                       conf, thresholds, n, H, W, boundary, raw, (unsigned char*)out, kept, tiles_x, tiles_y, weight);
   IFSEG_CHECK_LAUNCH();
   return 0;
+}
+}  // namespace
+
+extern "C" int ifseg_seg_pseudo(const void* labels, int label_bytes, const float* conf, const int* thresholds, int n, int B, int H,
+                                int W, int boundary, int raw_labels, void* out, unsigned long long* kept, void* stream) {
+  return seg_pseudo_launch(labels, label_bytes, conf, thresholds, n, B, H, W, boundary, raw_labels, out, kept, nullptr, stream);
+}
+
+extern "C" int ifseg_seg_pseudo_weighted(const void* labels, int label_bytes, const float* conf, const int* thresholds, int n,
+                                         int B, int H, int W, int boundary, int raw_labels, void* out, void* weight,
+                                         unsigned long long* kept, void* stream) {
+  if (!weight || weight == out) return IFSEG_ERR_BAD_ARG;
+  return seg_pseudo_launch(labels, label_bytes, conf, thresholds, n, B, H, W, boundary, raw_labels, out, kept,
+                           (unsigned char*)weight, stream);
 }

@@ -248,6 +248,37 @@ __global__ __launch_bounds__(256) void train_load_kernel(const ifseg_train_src* 
             plane, ok, lane, x, xend);
 }
 
+// ------------------------------------------------------------------------------------------------------------- plane
+// a uint8 plane that travels with the label map (per-pixel loss weights): train_load_kernel's label tap on the plane's own
+// bytes.  One 16 x 64 tile per workgroup, lane = x, plain byte stores; a record train_load_kernel would poison writes 0.
+__global__ __launch_bounds__(256) void train_plane_kernel(const ifseg_train_src* __restrict__ tab, const int* __restrict__ params,
+                                                          int P, int tiles_x, int tiles_y, unsigned char* __restrict__ out) {
+  const auto [b, X0, Y0, xend, yend, lane, wave] = tile_decode(tiles_x, tiles_y, P, P);
+  const ifseg_train_src s = tab[b];
+  const int* rec = params + (long long)b * 16;
+  const int H0 = s.H0, W0 = s.W0, nh = rec[R_NEW_H], nw = rec[R_NEW_W], offh = rec[R_OFF_H], offw = rec[R_OFF_W];
+  const bool flip = rec[R_FLIP] != 0;
+  const bool bad = nh < P || nw < P || offh < 0 || offw < 0 || offh > nh - P || offw > nw - P || 2ll * H0 * nh >= (1ll << 31) ||
+                   2ll * W0 * nw >= (1ll << 31);                                 // workgroup-uniform
+  const int x = X0 + lane;
+  if (x >= xend) return;
+  const unsigned char* src = (const unsigned char*)s.label;
+  unsigned char* o = out + (long long)b * P * P;
+  const int xs = offw + (flip ? P - 1 - x : x);
+  const int lsx = bad ? 0 : min((int)((long long)xs * W0 / nw), W0 - 1);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int y = Y0 + wave * 4 + j;
+    if (y >= yend) break;
+    unsigned char v = 0;
+    if (!bad) {
+      const int lsy = min((int)((long long)(offh + y) * H0 / nh), H0 - 1);
+      v = src[(long long)lsy * W0 + lsx];
+    }
+    o[(long long)y * P + x] = v;
+  }
+}
+
 // what both entry points ask of the host copy of the table
 int check_table(const ifseg_train_src* th, int B, bool want_images, long long max_short) {
   const long long lim = 1ll << 31;
@@ -260,6 +291,20 @@ int check_table(const ifseg_train_src* th, int B, bool want_images, long long ma
       const long long s = std::min(H0, W0), lg = (2 * max_short * std::max(H0, W0) + s) / (2 * s);
       if (2 * s * max_short >= lim || 2 * std::max(H0, W0) * lg >= lim) return IFSEG_ERR_BAD_SHAPE;
     }
+  }
+  return 0;
+}
+
+// the records a caller holds in host memory (may be NULL): one that does not hold a P x P window is refused before the launch
+int check_records(const ifseg_train_src* th, const int* params_host, int B, int P) {
+  const long long lim = 1ll << 31;
+  if (!params_host) return 0;
+  for (int b = 0; b < B; ++b) {
+    const int* r = params_host + 16 * b;
+    if (r[R_NEW_H] < P || r[R_NEW_W] < P || r[R_OFF_H] < 0 || r[R_OFF_W] < 0 || r[R_OFF_H] > r[R_NEW_H] - P ||
+        r[R_OFF_W] > r[R_NEW_W] - P)
+      return IFSEG_ERR_BAD_SHAPE;
+    if (2ll * th[b].H0 * r[R_NEW_H] >= lim || 2ll * th[b].W0 * r[R_NEW_W] >= lim) return IFSEG_ERR_BAD_SHAPE;
   }
   return 0;
 }
@@ -301,15 +346,7 @@ extern "C" int ifseg_train_load(const ifseg_train_src* table_host, const ifseg_t
   const long long lim = 1ll << 31;
   if ((long long)B * 3 * P * P >= lim) return IFSEG_ERR_BAD_SHAPE;
   if (int rc = check_table(table_host, B, true, 0)) return rc;
-  if (params_host) {
-    for (int b = 0; b < B; ++b) {
-      const int* r = params_host + 16 * b;
-      if (r[R_NEW_H] < P || r[R_NEW_W] < P || r[R_OFF_H] < 0 || r[R_OFF_W] < 0 || r[R_OFF_H] > r[R_NEW_H] - P ||
-          r[R_OFF_W] > r[R_NEW_W] - P)
-        return IFSEG_ERR_BAD_SHAPE;
-      if (2ll * table_host[b].H0 * r[R_NEW_H] >= lim || 2ll * table_host[b].W0 * r[R_NEW_W] >= lim) return IFSEG_ERR_BAD_SHAPE;
-    }
-  }
+  if (int rc = check_records(table_host, params_host, B, P)) return rc;
   int tiles_x, tiles_y;
   long long blocks;
   if (!tile_grid(P, P, B, &tiles_x, &tiles_y, &blocks)) return IFSEG_ERR_BAD_SHAPE;
@@ -328,6 +365,23 @@ extern "C" int ifseg_train_load(const ifseg_train_src* table_host, const ifseg_t
   else
     hipLaunchKernelGGL(train_load_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, table, params, P,
                        tiles_x, tiles_y, nseg, raw_labels, seg_id_offset, eos, lut, reverse_channels, (bf16_t*)out, target, stage);
+  IFSEG_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ifseg_train_load_plane(const ifseg_train_src* table_host, const ifseg_train_src* table, const int* params,
+                                      const int* params_host, int B, int P, void* out, void* stream) {
+  (void)hipGetLastError();
+  if (!table_host || !table || !params || !out || ((size_t)params & 3) || ((size_t)table & 7)) return IFSEG_ERR_BAD_ARG;
+  if (B < 1 || P < 1 || P > TL_MAX_P) return IFSEG_ERR_BAD_SHAPE;              // any P: no 16-pixel patch grid behind a plane
+  if ((long long)B * P * P >= (1ll << 31)) return IFSEG_ERR_BAD_SHAPE;
+  if (int rc = check_table(table_host, B, false, 0)) return rc;
+  if (int rc = check_records(table_host, params_host, B, P)) return rc;
+  int tiles_x, tiles_y;
+  long long blocks;
+  if (!tile_grid(P, P, B, &tiles_x, &tiles_y, &blocks)) return IFSEG_ERR_BAD_SHAPE;
+  hipLaunchKernelGGL(train_plane_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, table, params, P, tiles_x,
+                     tiles_y, (unsigned char*)out);
   IFSEG_CHECK_LAUNCH();
   return 0;
 }

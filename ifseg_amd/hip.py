@@ -992,6 +992,37 @@ def seg_loss(logits_pad, target, hp, wp, H, W, nseg, seg_id_offset, tile_partial
     return loss_out
 
 
+def seg_loss_weighted(logits_pad, target, hp, wp, H, W, nseg, seg_id_offset, tile_partial, stats_part, stats, dlogits_pad,
+                      loss_out, pixel_weight=None, class_weight=None, norm_pixels=False, pad_id=1, eos_id=2, bad_label=None,
+                      label_smoothing=0.0):
+    """`seg_loss` with per-pixel and per-class weights (csrc/loss.hip, the weighted instantiation of the tile kernel;
+    `criterions.seg_criterion.weighted_loss_reference` is the specification): pixel_weight uint8 [B, H*W] (rows H*W bytes
+    apart or more) or None, class_weight fp32 [nseg] (non-negative and finite: the caller's duty) or None.  stats[0] is the
+    weighted sum, stats[1] the normaliser Z (sum q cw[y], or qmax N_valid with norm_pixels), the histograms are the
+    unweighted launch's; the reduction and the gather launch are `seg_loss`'s."""
+    B = logits_pad.shape[0]
+    dev = logits_pad.device
+    pw_bs = 0
+    if pixel_weight is not None:
+        assert pixel_weight.dtype == torch.uint8 and tuple(pixel_weight.shape) == (B, H * W) and pixel_weight.stride(1) == 1 \
+            and pixel_weight.device == dev, (pixel_weight.dtype, tuple(pixel_weight.shape), pixel_weight.stride(), pixel_weight.device)
+        pw_bs = pixel_weight.stride(0) if B > 1 else H * W
+    if class_weight is not None:
+        assert class_weight.dtype == torch.float32 and tuple(class_weight.shape) == (nseg,) and class_weight.is_contiguous() \
+            and class_weight.device == dev, (class_weight.dtype, tuple(class_weight.shape), class_weight.device)
+    _check(lib().ifseg_seg_loss_tiles_weighted(_ptr(logits_pad), c_int(logits_pad.stride(1)), c_ll(logits_pad.stride(0)),
+                                               _ptr(target), c_ll(target.stride(0)), c_int(B), c_int(hp), c_int(wp), c_int(H),
+                                               c_int(W), c_int(nseg), c_ll(seg_id_offset), c_ll(pad_id), c_ll(eos_id),
+                                               _ptr(pixel_weight), c_ll(pw_bs), _ptr(class_weight),
+                                               c_int(1 if norm_pixels else 0), _ptr(tile_partial), _ptr(stats_part),
+                                               _ptr(bad_label), c_float(label_smoothing), _stream()), "seg_loss_tiles_weighted")
+    reduce_parts(stats_part, stats, 1, B * hp * wp, 2 + 3 * nseg)
+    _check(lib().ifseg_seg_loss_gather(_ptr(tile_partial), _ptr(stats), _ptr(dlogits_pad), c_int(dlogits_pad.stride(1)),
+                                       c_ll(dlogits_pad.stride(0)), c_int(B), c_int(hp), c_int(wp), c_int(nseg),
+                                       _ptr(loss_out), _stream()), "seg_loss_gather")
+    return loss_out
+
+
 # ---------------------------------------------------------------------- eval post-processing
 def rows_to_f32(logits_pad, nseg, rows_per_batch, softmax=False, temperature=1.0):
     """logits_pad bf16 [B, T, ld] -> fp32 [B, rows_per_batch, nseg] (first rows of every sample), optionally softmaxed"""
@@ -1423,14 +1454,16 @@ def seg_conf_hist(labels, conf, n, hist=None, tally=None):
     return hist, tally
 
 
-def seg_pseudo(labels, conf, thresholds, n, boundary=0, raw_labels=True, kept=None, out=None):
+def seg_pseudo(labels, conf, thresholds, n, boundary=0, raw_labels=True, kept=None, out=None, weight=False):
     """labels uint8 / int16 [H, W] or [B, H, W], conf fp32 of the same shape, thresholds int32 [n] (bins, 0 .. 256) ->
     (out uint8 of the labels' shape, kept int64 [2, n]) in one launch (csrc/pseudo.hip): a pixel of label l in [0, n) whose
     confidence bin is at least thresholds[l] and, with boundary = r in 1..4, that has no other label value within r pixels
     becomes l + 1 (raw_labels: the label-PNG convention `augment.remap_label` undoes) or l, every other pixel 255.
     kept[1, c] = #(label = c), kept[0, c] = those kept; `kept` given: ACCUMULATED into.  out: written in place when given
     (contiguous, at any byte offset of its storage; it must not overlap labels or conf).
-    `predict.pseudo_label_reference` is the specification.  n <= 254 with raw_labels, 255 without."""
+    `predict.pseudo_label_reference` is the specification.  n <= 254 with raw_labels, 255 without.
+    weight=True: the same launch also writes the loss weight of every pixel, and the call returns (out, kept, weight uint8 of
+    the labels' shape): 0 where out is 255, max(conf_bin(conf), 1) where the pixel was kept."""
     assert labels.dim() in (2, 3), tuple(labels.shape)
     _labels_conf(labels, conf, "seg_pseudo")
     assert isinstance(n, int) and 1 <= n <= seg_pseudo_max_classes(raw_labels), (n, raw_labels)
@@ -1445,6 +1478,13 @@ def seg_pseudo(labels, conf, thresholds, n, boundary=0, raw_labels=True, kept=No
         (out.dtype, tuple(out.shape), out.stride(), out.device)
     assert not _overlap(out, labels) and not _overlap(out, conf), "seg_pseudo: out overlaps the labels or conf"
     H, W = labels.shape[-2:]
+    if weight:
+        wt = torch.empty(labels.shape, dtype=torch.uint8, device=dev)
+        _check(lib().ifseg_seg_pseudo_weighted(_ptr(labels), c_int(labels.element_size()), _ptr(conf), _ptr(thresholds), c_int(n),
+                                               c_int(labels.numel() // (H * W)), c_int(H), c_int(W), c_int(boundary),
+                                               c_int(1 if raw_labels else 0), _ptr(out), _ptr(wt), _ptr(kept), _stream()),
+               "seg_pseudo_weighted")
+        return out, kept, wt
     _check(lib().ifseg_seg_pseudo(_ptr(labels), c_int(labels.element_size()), _ptr(conf), _ptr(thresholds), c_int(n),
                                   c_int(labels.numel() // (H * W)), c_int(H), c_int(W), c_int(boundary),
                                   c_int(1 if raw_labels else 0), _ptr(out), _ptr(kept), _stream()), "seg_pseudo")
@@ -1602,6 +1642,35 @@ def train_load(images, labels, params, P, nseg, seg_id_offset, mean=(0.5, 0.5, 0
                                       c_int(1 if reverse_channels else 0), _ptr(out), c_int(out.element_size()), _ptr(target),
                                       _stream()), "train_load")
     return out, target
+
+
+def train_load_plane(planes, params, P, out=None, table=None):
+    """uint8 planes [H0, W0] of any sizes on the device, under the records of `train_draw` / the caller -> uint8 [B, P*P]: the
+    label tap of `train_load` on the plane's own bytes, one launch (csrc/trainload.hip; `augment.train_plane_reference` is the
+    specification).  The planes travel in a descriptor table through its label pointers: table = `_train_table(None, planes)`
+    when the caller already has it.  Records on the host are checked by the entry point, records on the device by the
+    kernel (a bad one writes 0 for its sample).  Any 1 <= P <= 4096."""
+    B = len(planes)
+    assert B >= 1
+    dev = planes[0].device
+    assert params.dtype == torch.int32 and tuple(params.shape) == (B, 16), (params.dtype, tuple(params.shape))
+    params_host = None
+    if not params.is_cuda:
+        params_host = params.contiguous()
+        params = params_host.to(dev)
+    params = params.contiguous()
+    host, table = table if table is not None else _train_table(None, planes)
+    assert host.shape[0] == B, (tuple(host.shape), B)
+    P = int(P)
+    if out is None:
+        out = torch.empty(B, P * P, dtype=torch.uint8, device=dev)
+    else:
+        assert out.dtype == torch.uint8 and tuple(out.shape) == (B, P * P) and out.is_contiguous() and out.device == dev, \
+            (out.dtype, tuple(out.shape), out.stride(), out.device)
+    _check(lib().ifseg_train_load_plane(c_void_p(host.data_ptr()), _ptr(table), _ptr(params),
+                                        c_void_p(params_host.data_ptr()) if params_host is not None else None, c_int(B),
+                                        c_int(P), _ptr(out), _stream()), "train_load_plane")
+    return out
 
 
 def dropout(x, resid, out, p, seed, drop_path_scale=None, rows_per_batch=None):

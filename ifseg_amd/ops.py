@@ -16,7 +16,8 @@ is dispatcher-visible too.  No CPU implementation is registered: on a CPU tensor
 
 The second half of the file puts the training-path kernels there as well (see the comment above `_check_qkv`):
 `attention_bias` (the bias is an ordinary tensor with a gradient), `bias_attention_bi` (bias_attention on the batch-inner
-kernels, with key counts and attention dropout) and `seg_loss` (csrc/loss.hip), with `*_bwd` ops of their own;
+kernels, with key counts and attention dropout), `seg_loss` (csrc/loss.hip) and `seg_loss_weighted` (the same kernel with a
+weight per pixel and per class; it shares `seg_loss_bwd`), with `*_bwd` ops of their own;
 `ifseg_amd.modules.MultiheadAttention` composes `linear` and `attention_bias` under the reference module's parameter names.
 `seg_predict` (csrc/predict.hip: label maps at image resolution), `seg_predict_views` (the same from the mean of K views of
 differing grids, mirrored ones included: multi-scale + flip inference), `seg_areas` / `seg_score_views` (label maps counted
@@ -264,6 +265,8 @@ bias_attention.register_autograd(_attn_backward, setup_context=_attn_setup)
 #   torch.ops.ifseg.bias_attention_bi(q, k, v, pos_q, pos_k, gain, gcode, rel2d, rel1d, relx, P, code_bias, grid_w, causal,
 #                                     kv_len, dropout_p, seed)                                   bias_attention + key counts + dropout
 #   torch.ops.ifseg.seg_loss(logits, target, hp, wp, H, W, seg_id_offset, label_smoothing)       x16 upsample + CE + histograms
+#   torch.ops.ifseg.seg_loss_weighted(logits, target, pixel_weight, class_weight, hp, wp, H, W, seg_id_offset, label_smoothing,
+#                                     norm_pixels)                                               the same with per-pixel / per-class weights
 #
 # Every op has ONE check helper that its real and its fake implementation call first: tracing refuses what running refuses,
 # and nothing is launched (the library is not even loaded) before the arguments have passed.
@@ -671,6 +674,73 @@ def _sl_backward(ctx, gloss, gstats, gdl, gbad):
 
 
 seg_loss.register_autograd(_sl_backward, setup_context=_sl_setup)
+
+
+# ----------------------------------------------------------------------------------------------- seg_loss_weighted
+def _seg_loss_weighted_check(logits, target, pixel_weight, class_weight, hp, wp, H, W, label_smoothing):
+    op = "ifseg::seg_loss_weighted"
+    B, nseg, npad = _seg_loss_check(logits, target, hp, wp, H, W)
+    if pixel_weight is not None and (pixel_weight.dtype != torch.uint8 or tuple(pixel_weight.shape) != (B, H * W)):
+        raise ValueError("%s: pixel_weight must be uint8 [B, H * W] = [%d, %d], got %s %s"
+                         % (op, B, H * W, pixel_weight.dtype, tuple(pixel_weight.shape)))
+    if class_weight is not None and (class_weight.dtype != torch.float32 or tuple(class_weight.shape) != (nseg,)):
+        raise ValueError("%s: class_weight must be fp32 [nseg] = [%d], got %s %s"
+                         % (op, nseg, class_weight.dtype, tuple(class_weight.shape)))
+    if not (0.0 <= label_smoothing <= 1.0):
+        raise ValueError("%s: label_smoothing must lie in [0, 1], got %r" % (op, label_smoothing))
+    return B, nseg, npad
+
+
+@custom_op("ifseg::seg_loss_weighted", mutates_args=(), device_types="cuda")
+def seg_loss_weighted(logits: torch.Tensor, target: torch.Tensor, pixel_weight: Optional[torch.Tensor],
+                      class_weight: Optional[torch.Tensor], hp: int, wp: int, H: int, W: int, seg_id_offset: int,
+                      label_smoothing: float, norm_pixels: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """`seg_loss` with a weight per pixel and per class, in the weighted instantiation of the same kernel
+    (`criterions.seg_criterion.weighted_loss_reference` is the specification): pixel_weight None or uint8 [B, H*W]
+    (q in 0 .. 255), class_weight None or fp32 [nseg], finite and non-negative (the caller's duty: the op reads no values).
+    loss = sum q l / Z over the valid pixels, l = F.cross_entropy(weight=class_weight, reduction="none", label_smoothing);
+    Z = sum q cw[y], or with norm_pixels qmax N_valid (qmax = 255 with a plane, else 1); 0 when Z = 0.
+    -> (loss, stats, dlogits, bad) as `seg_loss`, with stats[0] the weighted sum, stats[1] = Z and the area histograms
+    counted over the valid pixels whatever their weights.  Differentiable in logits only."""
+    B, nseg, npad = _seg_loss_weighted_check(logits, target, pixel_weight, class_weight, hp, wp, H, W, label_smoothing)
+    prev = _stream_scope(logits)
+    try:
+        dev, P = logits.device, hp * wp
+        lp = logits
+        if not (lp.stride(2) == 1 and lp.stride(1) % 8 == 0 and lp.stride(1) >= npad and lp.stride(0) % 8 == 0
+                and lp.data_ptr() % 16 == 0):
+            lp = torch.zeros(B, P + 1, npad, dtype=BF, device=dev)
+            lp[:, :, :nseg].copy_(logits)
+        n_tiles, nstat = B * P, 2 + 3 * nseg
+        tile = torch.empty(n_tiles * 9 * nseg, dtype=torch.float32, device=dev)
+        sp = torch.empty(n_tiles * nstat, dtype=torch.float32, device=dev)
+        stats = torch.empty(nstat, dtype=torch.float32, device=dev)
+        dl = torch.empty(B, P + 1, npad, dtype=BF, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        hip.seg_loss_weighted(lp, target.contiguous(), hp, wp, H, W, nseg, seg_id_offset, tile, sp, stats, dl, loss,
+                              pixel_weight=pixel_weight.contiguous() if pixel_weight is not None else None,
+                              class_weight=class_weight.contiguous() if class_weight is not None else None,
+                              norm_pixels=norm_pixels, bad_label=bad, label_smoothing=float(label_smoothing))
+        return loss, stats, dl, bad
+    finally:
+        hip.set_stream(prev)
+
+
+@seg_loss_weighted.register_fake
+def _(logits, target, pixel_weight, class_weight, hp, wp, H, W, seg_id_offset, label_smoothing, norm_pixels):
+    B, nseg, npad = _seg_loss_weighted_check(logits, target, pixel_weight, class_weight, hp, wp, H, W, label_smoothing)
+    f32 = torch.float32
+    return (logits.new_empty((), dtype=f32), logits.new_empty(2 + 3 * nseg, dtype=f32), logits.new_empty(B, hp * wp + 1, npad),
+            logits.new_empty(1, dtype=torch.int32))
+
+
+def _slw_backward(ctx, gloss, gstats, gdl, gbad):
+    (dl,) = ctx.saved_tensors
+    return (torch.ops.ifseg.seg_loss_bwd(gloss, dl, ctx.nseg),) + (None,) * 10
+
+
+seg_loss_weighted.register_autograd(_slw_backward, setup_context=_sl_setup)
 
 
 # ----------------------------------------------------------------------------------------------- seg_predict

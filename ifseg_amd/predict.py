@@ -400,7 +400,7 @@ def pseudo_thresholds(hist, keep=1.0, floor=0.0):
     return q.clamp_min(int(math.ceil(float(floor) * 256.0))).to(torch.int32)
 
 
-def pseudo_label_reference(labels, conf, thresholds, n, boundary=0, raw_labels=True):
+def pseudo_label_reference(labels, conf, thresholds, n, boundary=0, raw_labels=True, weight=False):
     """Specification of hip.seg_pseudo, in integers: labels integer [H, W] (or [B, H, W]), conf fp32 of that shape, thresholds
     integer [n] (bins) -> (out uint8 [.., H, W], kept int64 [2, n]).  A pixel of label l is kept iff
 
@@ -410,7 +410,9 @@ def pseudo_label_reference(labels, conf, thresholds, n, boundary=0, raw_labels=T
 
     A kept pixel becomes l + 1 with raw_labels (the label-PNG convention `augment.remap_label` undoes) or l without; every
     other pixel 255, which both conventions ignore.  kept[1, c] = #(label = c), kept[0, c] = those that were kept.
-    n <= 254 with raw_labels, n <= 255 without (ValueError).  Runs on any device."""
+    n <= 254 with raw_labels, n <= 255 without (ValueError).  Runs on any device.
+    weight=True: -> (out, kept, weight uint8 of out's shape), the per-pixel loss weight of the weighted criterion: 0 where
+    the pixel was dropped, max(conf_bin(conf), 1) where it was kept."""
     r = _boundary_arg("pseudo_label_reference", boundary)
     lab, conf = _labels_conf("pseudo_label_reference", labels, conf, n)
     if lab.dim() not in (2, 3):
@@ -427,6 +429,9 @@ def pseudo_label_reference(labels, conf, thresholds, n, boundary=0, raw_labels=T
     keep = inside & ~_label_edges(lab, r) & (conf_bin(conf) >= thr[cls])
     out = torch.where(keep, cls + (1 if raw_labels else 0), torch.full_like(cls, 255)).to(torch.uint8)
     kept = torch.stack([torch.bincount(cls[keep], minlength=n), torch.bincount(cls[inside], minlength=n)])
+    if weight:
+        b = conf_bin(conf)
+        return out, kept, torch.where(keep, b.clamp_min(1), torch.zeros_like(b)).to(torch.uint8)
     return out, kept
 
 
@@ -435,6 +440,7 @@ class PseudoLabelResult(NamedTuple):
     predicted: torch.Tensor                    # [H, W] uint8 / int16: what `segment_raw` gave
     conf: torch.Tensor                         # [H, W] fp32: the winning class's probability
     kept: torch.Tensor                         # [2, n] int64: per class the kept and the predicted pixels of this image
+    weight: Optional[torch.Tensor] = None      # [H, W] uint8 (return_weight): 0 = dropped, else max(conf_bin(conf), 1)
 
 
 class ConfidenceHistogram:
@@ -999,7 +1005,8 @@ class Segmenter:
         return "upsample=%r (conf is the winning class's resized raw logit)" % (self.upsample,)
 
     def pseudo_label_raw(self, images, keep=1.0, floor=0.0, boundary=0, raw_labels=True, hist=None, thresholds=None,
-                         scales=(1.0,), flip=False, slide=None, max_batch=8, mean=None, std=None, reverse_channels=False):
+                         scales=(1.0,), flip=False, slide=None, max_batch=8, mean=None, std=None, reverse_channels=False,
+                         return_weight=False):
         """Unlabeled photographs -> label maps `task.train_sample` accepts, holding only the pixels the model is confident
         of: the self-training step (CBST, MaskCLIP+) that adapts the image-free model to a target domain, on the device ->
         a list of `PseudoLabelResult(labels uint8 [H_i, W_i], predicted, conf, kept)` in input order.
@@ -1015,7 +1022,9 @@ class Segmenter:
           4. one launch of `hip.seg_pseudo` per image: a pixel is kept where its class's threshold is met and, with
              boundary = r in 1 .. 4, no other class lies within r pixels (`pseudo_label_reference` states the rule); kept pixels
              become class + 1 with raw_labels (what a `TrainTransform(raw_labels=True)`, the default, takes), else the class id;
-             every other pixel 255, ignored by both.
+             every other pixel 255, ignored by both.  return_weight: the same launch also writes the result's `weight`, uint8
+             [H_i, W_i]: 0 where the pixel was dropped, else max(conf_bin(conf), 1) -- the per-pixel loss weight that
+             `task.train_sample(..., weights=)` carries to the weighted criterion.
         Nothing synchronises with the host.  Between the passes every image's labels and conf stay alive: 5 bytes per pixel
         (6 with int16 labels) for the whole call, which bounds the images of one call, not of a data set.
 
@@ -1055,6 +1064,10 @@ class Segmenter:
                 thresholds = thresholds.to(dev).contiguous()
             out = []
             for labels, conf in pairs:
+                if return_weight:
+                    pseudo, kept, wt = hip.seg_pseudo(labels, conf, thresholds, self.n, boundary, bool(raw_labels), weight=True)
+                    out.append(PseudoLabelResult(pseudo, labels, conf, kept, wt))
+                    continue
                 pseudo, kept = hip.seg_pseudo(labels, conf, thresholds, self.n, boundary, bool(raw_labels))
                 out.append(PseudoLabelResult(pseudo, labels, conf, kept))
         return out

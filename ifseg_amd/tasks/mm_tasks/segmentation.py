@@ -232,7 +232,7 @@ class SegmentationTask(TaskBase):
         seg = self.build_segmenter(model, **{k: kw.pop(k) for k in ctor if k in kw})
         return seg.pseudo_label_raw(images, **kw)
 
-    def self_train_sample(self, model, images, first_ordinal, trainer=None, **kw):
+    def self_train_sample(self, model, images, first_ordinal, trainer=None, confidence_weight=False, **kw):
         """One batch of self-training on unlabeled photographs: `pseudo_label_raw(model, images, **kw)` and then
         `train_sample(images, [r.labels ...], first_ordinal)` on the model's own confident pixels -> the batch
         `Trainer.train_step` takes; every pixel that was not kept carries the ignore class.  `raw_labels` (default: the
@@ -241,8 +241,14 @@ class SegmentationTask(TaskBase):
         weights, inside `trainer.ema_weights()` -- instead of the weights being trained (mean teacher; the remedy for the
         confirmation bias of labelling with the student).  Without `trainer`, or with one that keeps no teacher, `model` labels
         as it stands.  Not built: `ema_seed_model`, and a teacher for the fairseq plugin's own trainer (its `EMA` deep-copies
-        the model, which is untested with the arena-backed parameters)."""
+        the model, which is untested with the arena-backed parameters).
+        confidence_weight: the labelling launch also writes every pixel's confidence as a loss weight
+        (`pseudo_label_raw(return_weight=True)`), the transform carries the planes to the batch and the sample gains
+        `"target_weight"` (uint8 [B, P*P]), which the criterion's weighted kernel reads: a kept pixel counts by how sure the
+        teacher was of it instead of 0 or 1."""
         tf = getattr(self, "train_transform", None) or self.build_train_transform()
+        if confidence_weight:
+            kw["return_weight"] = True
         raw = kw.setdefault("raw_labels", tf.raw_labels)
         if bool(raw) != tf.raw_labels:
             raise ValueError("self_train_sample: raw_labels=%r, but the train transform was built with raw_labels=%r"
@@ -253,7 +259,10 @@ class SegmentationTask(TaskBase):
             raise ValueError("self_train_sample: `trainer` trains another model than the one given")
         with trainer.ema_weights() if teacher else contextlib.nullcontext():
             res = self.pseudo_label_raw(model, images, **kw)
-        return self.train_sample(images, [r.labels.to(tf.device) for r in res], first_ordinal)
+        labels = [r.labels.to(tf.device) for r in res]
+        if not confidence_weight:
+            return self.train_sample(images, labels, first_ordinal)
+        return self.train_sample(images, labels, first_ordinal, weights=[r.weight.to(tf.device) for r in res])
 
     def inference_step(self, generator, models, sample, prefix_tokens=None, constraints=None):
         """fairseq_task.py `inference_step` -> [B, max_len] seg-class indices of the best beam (segmentation.py:266-268)"""
@@ -377,25 +386,32 @@ class SegmentationTask(TaskBase):
             self._train_src = source_tokens(names, self.prompt_ids, self.num_seg_tokens)
         return self._train_src
 
-    def train_sample(self, images, labels, first_ordinal):
+    def train_sample(self, images, labels, first_ordinal, weights=None):
         """Raw uint8 images [H0, W0, 3] (RGB) and raw uint8 label maps [H0, W0] of any sizes -> the batch `Trainer.train_step`
         takes, in `synthetic_sample`'s layout, through `build_train_transform`'s transform (built on first use, on the CPU,
         if the caller has not built one).  `first_ordinal` is the ordinal of sample 0 (`artificial.trainer_first_ordinal`):
-        the batch is a pure function of (seed, ordinal)."""
+        the batch is a pure function of (seed, ordinal).  weights: uint8 [H0, W0] per sample, per-pixel loss weights that
+        follow their label map through the transform; the sample then carries `"target_weight"` (uint8 [B, P*P])."""
         tf = getattr(self, "train_transform", None) or self.build_train_transform()
-        img, tgt = tf(images, labels, first_ordinal)
+        if weights is None:
+            img, tgt = tf(images, labels, first_ordinal)
+        else:
+            img, tgt, wgt = tf(images, labels, first_ordinal, weights=weights)
         B, P, dev = len(images), tf.P, tf.device
         src = self._train_src_tokens()
         if src.device != dev:
             src = self._train_src = src.to(dev)
         L = src.numel()
-        return {
+        sample = {
             "id": list(range(B)), "nsentences": B, "ntokens": int(B * (P * P + 1)),
             "net_input": {"src_tokens": src.repeat(B, 1), "src_lengths": torch.full((B,), L, device=dev),
                           "patch_images": img, "patch_masks": torch.ones(B, dtype=torch.bool, device=dev),
                           "prev_output_tokens": torch.zeros(B, 1, dtype=torch.long, device=dev)},
             "target": tgt,
         }
+        if weights is not None:
+            sample["target_weight"] = wgt
+        return sample
 
     def train_step(self, sample, model, criterion, optimizer, update_num, ignore_grad=False, **extra_kwargs):
         """tasks/mm_tasks/segmentation.py:190-222."""

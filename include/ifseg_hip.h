@@ -488,6 +488,24 @@ int ifseg_seg_loss_tiles(const void* logits, int ldl, long long logits_bs, const
                          pad / eos / ignore (F.cross_entropy would raise); may be NULL */, float label_smoothing, void* stream);
 int ifseg_seg_loss_gather(const float* tile_partial, const float* stats, void* dlogits, int ldl,
                           long long dlogits_bs, int B, int hp, int wp, int nseg, float* loss_out, void* stream);
+/* ifseg_seg_loss_tiles with a weight per pixel and per class (ifseg_amd.criterions.seg_criterion.weighted_loss_reference is
+ * the specification; F.cross_entropy(weight=class_weight, reduction="none", label_smoothing) per pixel, times q):
+ *   pixel_weight  uint8 [B][H*W] on the device, batch stride pw_bs >= H*W bytes, q in 0..255; NULL: q = 1
+ *   class_weight  fp32 [nseg] on the device, non-negative (the caller's duty); NULL: ones
+ *   stats_part[tile][0] = sum q l over the tile's valid pixels
+ *   stats_part[tile][1] = its share of the normaliser Z: sum q cw[y] (norm_pixels == 0, torch's weighted mean; the loss does
+ *                         not depend on the scale of q), or qmax per valid pixel (norm_pixels != 0; qmax = 255 with a plane,
+ *                         else 1: a batch of unsure pixels gives a smaller gradient)
+ * the histograms and bad_label count valid pixels whatever their weights, and tile_partial carries the weighted gradient, so
+ * ifseg_reduce_parts and ifseg_seg_loss_gather follow unchanged: loss = stats[0] / stats[1], 0 with a zero gradient when
+ * Z = 0.  No global atomics.  The refusals of ifseg_seg_loss_tiles; B, hp or wp < 1, pw_bs < H*W, class_weight not 4-byte
+ * aligned: IFSEG_ERR_BAD_ARG. */
+int ifseg_seg_loss_tiles_weighted(const void* logits, int ldl, long long logits_bs, const long long* target,
+                                  long long target_bs, int B, int hp, int wp, int H, int W, int nseg,
+                                  long long seg_id_offset, long long pad_id, long long eos_id,
+                                  const unsigned char* pixel_weight, long long pw_bs, const float* class_weight,
+                                  int norm_pixels, float* tile_partial, float* stats_part, int* bad_label,
+                                  float label_smoothing, void* stream);
 
 /* ---------------------------------------------------- image-free samples */
 /* The artificial image of `--artificial-image-type rand_k-L-R` (data/mm_data/segmentation_dataset.py:303-345) and its collater
@@ -781,6 +799,12 @@ int ifseg_seg_conf_hist(const void* labels, int label_bytes, const float* conf, 
  * IFSEG_ERR_BAD_ARG; B, H, W < 1 or B*H*W >= 2^31: IFSEG_ERR_BAD_SHAPE.  Nothing is launched on a refusal. */
 int ifseg_seg_pseudo(const void* labels, int label_bytes, const float* conf, const int* thresholds, int n, int B, int H, int W,
                      int boundary, int raw_labels, void* out, unsigned long long* kept, void* stream);
+/* ifseg_seg_pseudo that also writes the loss weight of every pixel, weight uint8 [B, H, W] (any byte address, not out): 0
+ * where out is 255, max(bin(conf), 1) where the pixel was kept -- what ifseg_train_load_plane carries to the batch and
+ * ifseg_seg_loss_tiles_weighted reads.  Same launch, same refusals; a NULL weight: IFSEG_ERR_BAD_ARG. */
+int ifseg_seg_pseudo_weighted(const void* labels, int label_bytes, const float* conf, const int* thresholds, int n, int B, int H,
+                              int W, int boundary, int raw_labels, void* out, void* weight, unsigned long long* kept,
+                              void* stream);
 
 /* ---- raw images and raw label maps in, a training batch out (ifseg_amd/augment.py is the specification, bit for bit; the
  * reference's training transform, segmentation_dataset.py:157-163, 239-251: Resize(ratio_range), RandomCrop(cat_max_ratio 0.75),
@@ -822,6 +846,13 @@ int ifseg_train_load(const ifseg_train_src* table_host, const ifseg_train_src* t
                      int B, int P, int nseg, int raw_labels, long long seg_id_offset, long long eos, const float* lut,
                      int reverse_channels, void* out, int out_bytes, long long* target, void* stream);
 int ifseg_train_load_staging(int max_bytes);
+/* ifseg_train_load_plane: uint8 planes [H0, W0] of any sizes, given through the `label` pointers of the table (`image` is not
+ * read), under the same records -> out uint8 [B, P*P]: ifseg_train_load's label tap (src = min(dst in / out, in - 1), the
+ * window at the record's offset, mirrored under flip) on the plane's bytes, nothing remapped -- per-pixel loss weights that
+ * follow their label map.  One launch, one 16 x 64 tile per workgroup, byte stores; any 1 <= P <= 4096.  params_host as in
+ * ifseg_train_load; without it a bad record writes 0 for its sample.  Refusals as ifseg_train_load's. */
+int ifseg_train_load_plane(const ifseg_train_src* table_host, const ifseg_train_src* table, const int* params,
+                           const int* params_host, int B, int P, void* out, void* stream);
 
 /* sum of squares of a bf16 gradient arena -> out_sumsq[0] (device). */
 int ifseg_grad_sumsq_bf16(const void* g, long long n, float* workspace, float* out_sumsq, void* stream);
