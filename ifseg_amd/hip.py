@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("IFSEG_LIB", os.path.join(_HERE, "lib", "libifseg_hip.
 _lib = None
 
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
-GEMM_RELU, GEMM_OUT_F32, GEMM_ACCUMULATE = 1, 2, 4
+GEMM_RELU, GEMM_OUT_F32, GEMM_ACCUMULATE, GEMM_COLSUM = 1, 2, 4, 8
 
 c_void_p, c_int, c_float, c_ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_longlong
 
@@ -184,15 +184,19 @@ def ffn_ln_param_grads(w2, dw2, db2, gamma, beta, dgamma, dbeta, dy=None, u=None
 _splitk_ws = {}
 
 
-GEMM_COLSUM = 8
 # workgroups a dW GEMM is split over: it runs on the side stream next to the dX chain, so filling the chip alone is not
 # the goal (256 / 512 / 128 measured within 1% of each other; fewer slabs = less fp32 workspace traffic)
 DW_TARGET_WGS = int(lab.get("DW_WGS", "256"))
-DW_XCD_SLICES = lab.get("DW_NO_XCD_SLICES") is None
 # dW GEMMs with at least this many 128x128 tiles run without split-K (bf16 dW and db written once, no slabs, no
 # reduction).  Off by default: measured on the Base step, 144-tile GEMMs that walk all 8480 tokens per workgroup make the
 # weight-gradient stream lag (372-382 img/s vs 388 with split-K 2); the path is kept for models with wider layers.
 DW_DIRECT_TILES = int(lab.get("DW_DIRECT", "1000000"))
+
+
+def _db_follows(out, bias_out):
+    """does db lie right behind dW in memory (a Linear's weight and bias in the gradient arena), in the same dtype?"""
+    return (bias_out is not None and bias_out.dtype == out.dtype and bias_out.is_contiguous()
+            and bias_out.data_ptr() == out.data_ptr() + out.numel() * out.element_size())
 
 
 def linear_dw(dy, x, out, accumulate=False, bias_out=None):
@@ -206,15 +210,14 @@ def linear_dw(dy, x, out, accumulate=False, bias_out=None):
     K = x.shape[1]
     tiles = ((N + 127) // 128) * ((K + 127) // 128)
     splitk = max(1, min(16, DW_TARGET_WGS // max(1, tiles), M // 512))
-    if DW_XCD_SLICES and M >= 4096:
+    if M >= 4096:
         # k-slices pinned to XCDs (ifseg_gemm_bf16, TN): 8 slices for few-tile products, else 4 or 2; the count must divide
         # 8 and 8/splitk must divide the tile count
         for cand in (8, 4, 2):
             if tiles * cand <= max(DW_TARGET_WGS, 288) * (1 if cand == 8 else 2) and tiles % (8 // cand) == 0:
                 splitk = cand
                 break
-    adjacent = (bias_out is not None and N % 4 == 0 and bias_out.dtype == out.dtype and bias_out.is_contiguous()
-                and out.is_contiguous() and bias_out.data_ptr() == out.data_ptr() + out.numel() * out.element_size())
+    adjacent = N % 4 == 0 and out.is_contiguous() and _db_follows(out, bias_out)
     if tiles >= DW_DIRECT_TILES and out.dtype == torch.bfloat16 and out.is_contiguous():
         # enough tiles for a side-stream GEMM: one pass over all M tokens per workgroup, dW (and db) written once as bf16
         # -- no fp32 slabs, no reduction launch
@@ -226,8 +229,7 @@ def linear_dw(dy, x, out, accumulate=False, bias_out=None):
     if splitk > 1 and out.is_contiguous():
         kchunk = (((M + splitk - 1) // splitk) + 63) // 64 * 64
         nsl = (M + kchunk - 1) // kchunk
-        fuse_b = (bias_out is not None and N % 4 == 0 and bias_out.dtype == out.dtype and bias_out.is_contiguous()
-                  and bias_out.data_ptr() == out.data_ptr() + out.numel() * out.element_size())
+        fuse_b = N % 4 == 0 and _db_follows(out, bias_out)
         slab = N * K + (N if fuse_b else 0)
         ws = _splitk_ws.get(dy.device)
         if ws is None or ws.numel() < nsl * slab:
@@ -255,8 +257,7 @@ def dw_groupable(dy, x, out, bias_out):
     """can this dW = dy^T x (+ db) ride in a grouped launch?  bf16 dW contiguous in the arena, db right behind it"""
     if out.dtype != torch.bfloat16 or not out.is_contiguous() or dy.stride(1) != 1 or x.stride(1) != 1:
         return False
-    if bias_out is not None and not (bias_out.is_contiguous() and bias_out.dtype == out.dtype and
-                                     bias_out.data_ptr() == out.data_ptr() + out.numel() * out.element_size()):
+    if bias_out is not None and not _db_follows(out, bias_out):
         return False
     return dy.shape[1] % 8 == 0 and x.shape[1] % 8 == 0
 

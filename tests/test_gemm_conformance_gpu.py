@@ -933,3 +933,28 @@ def test_refusals_leave_the_output_alone():
     assert not wrong, "return codes (got, expected): %s" % wrong
     assert null_rc in (BAD_SHAPE, BAD_ARG), null_rc
     assert torch.equal(_bits(C), _bits(want)) and torch.equal(_bits(dot_out), _bits(dwant)), "a refused call wrote to its output"
+
+
+@gpu
+def test_refused_call_leaves_the_profiler_alone():
+    """a refusal comes before the profiler bracket: it counts no launch, no flops, no bytes and leaves no slot open, so the
+    next valid call of the family is counted and timed as the one launch it is"""
+    from ifseg_amd import hip
+    dev = _dev()
+    A = torch.ones(256, 256, dtype=BF16, device=dev)
+    Bm = torch.ones(256, 256, dtype=BF16, device=dev)
+    C = torch.zeros(256, 256, dtype=BF16, device=dev)
+    kind = hip.PROF_KINDS.index("gemm_tn")
+    hip.prof_enable(1 << kind)
+    hip.prof_reset()
+    try:
+        assert _raw_gemm(TN, A, Bm, C, 64, 64, 64, 256, 256, 72, flags=COLSUM) == BAD_ARG      # COLSUM with ldc != N
+        r = hip.prof_read(kind)
+        assert (r["launches"], r["flops"], r["bytes"]) == (0, 0.0, 0.0), r
+        assert _raw_gemm(TN, A, Bm, C, 64, 64, 64, 256, 256, 64) == 0
+        r = hip.prof_read(kind)
+        assert r["launches"] == 1 and math.isfinite(r["ms"]) and r["ms"] >= 0.0, r
+        assert (r["flops"], r["bytes"]) == (2.0 * 64 ** 3, 2.0 * 3 * 64 * 64), r
+    finally:
+        hip.prof_enable(0)
+        hip.prof_reset()
