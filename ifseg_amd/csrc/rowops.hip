@@ -723,6 +723,7 @@ extern "C" int ifseg_ln_bwd(const void* dy, const void* x, const void* gamma, co
   (void)hipGetLastError();
   if (rows <= 0) return 0;
   if ((C & 7) || C > 4096 || nblocks <= 0) return IFSEG_ERR_BAD_SHAPE;
+  if (((lddy | ldx | lddx) & 7) || (dx_add && (ldadd & 7))) return IFSEG_ERR_BAD_SHAPE;
   DropArgs dr{};
   if (drop) {
     if (drop->p < 0.f || drop->p >= 1.f || drop->rows_per_batch <= 0) return IFSEG_ERR_BAD_ARG;
@@ -751,7 +752,7 @@ extern "C" int ifseg_ln_bwd_drop(const void* dy, const void* x, const void* gamm
   (void)hipGetLastError();
   if (rows <= 0) return 0;
   if ((C & 7) || C > 1024 || nblocks <= 0) return IFSEG_ERR_BAD_SHAPE;
-  if (!dx2) return IFSEG_ERR_BAD_ARG;
+  if (!dx2 || (flags & IFSEG_LN_GELU)) return IFSEG_ERR_BAD_ARG;     // (no GELU instantiation of the lean kernel)
   if (((lddy | ldx | lddx | lddx2) & 7) || (dx_add && (ldadd & 7))) return IFSEG_ERR_BAD_SHAPE;
   DropArgs dr{};
   if (drop2) {
@@ -838,7 +839,7 @@ extern "C" int ifseg_colsum_bf16(const void* x, float* part, int nblk_rows, int 
                                  int ldx, void* stream) {
   (void)hipGetLastError();
   if (M <= 0) return 0;
-  if (N & 7) return IFSEG_ERR_BAD_SHAPE;
+  if ((N & 7) || (ldx & 7) || (rpb > 0 && (x_bs & 7)) || nblk_rows <= 0) return IFSEG_ERR_BAD_SHAPE;
   RowMap mx = row_map(rpb, x_bs, ldx);
   const int rows_per_blk = (M + nblk_rows - 1) / nblk_rows;
   dim3 g((N / 8 + 255) / 256, nblk_rows);
@@ -885,7 +886,7 @@ extern "C" int ifseg_embed_rows(const void* table, const long long* ids, const v
                                 int rpb, long long o_bs, int ldo, void* stream) {
   (void)hipGetLastError();
   if (n <= 0) return 0;
-  if (C & 7) return IFSEG_ERR_BAD_SHAPE;
+  if ((C & 7) || (ldo & 7) || (rpb > 0 && (o_bs & 7))) return IFSEG_ERR_BAD_SHAPE;
   RowMap mo = row_map(rpb, o_bs, ldo);
   const long long total = (long long)n * (C / 8);
   hipLaunchKernelGGL(embed_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
@@ -929,7 +930,7 @@ extern "C" int ifseg_embed_bag_mean(const void* table, const long long* ids, con
                                     void* stream) {
   (void)hipGetLastError();
   if (B <= 0 || P <= 0) return 0;
-  if ((C & 7) || maxlen <= 0) return IFSEG_ERR_BAD_SHAPE;
+  if ((C & 7) || maxlen <= 0 || (ldo & 7) || (rpb > 0 && (o_bs & 7))) return IFSEG_ERR_BAD_SHAPE;
   RowMap mo = row_map(rpb, o_bs, ldo);
   const long long total = (long long)B * P * (C / 8);
   hipLaunchKernelGGL(embed_bag_mean_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
@@ -1055,6 +1056,7 @@ extern "C" int ifseg_check_inputs(const void* x, long long n, int mode, long lon
                                   unsigned char* verdict_host_pinned, void* stream) {
   (void)hipGetLastError();
   if (!x || !verdict_host_pinned || mode < 0 || mode > 3 || n < 0 || (mode == 1 && row_len <= 0)) return IFSEG_ERR_BAD_ARG;
+  if (mode == 1 && n % row_len != 0) return IFSEG_ERR_BAD_ARG;      // a ragged last row would read x[n]
   hipLaunchKernelGGL(check_inputs_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, x, n, mode, value, row_len, verdict_host_pinned);
   IFSEG_CHECK_LAUNCH();
   return 0;
@@ -1148,6 +1150,7 @@ extern "C" int ifseg_dropout(const void* x, const void* resid, void* out, long l
   (void)hipGetLastError();
   if (rows <= 0) return 0;
   if ((C & 7) || p < 0.f || p >= 1.f || rows_per_batch <= 0) return IFSEG_ERR_BAD_ARG;
+  if (((ldx | ldo) & 7) || (resid && (ldr & 7)) || (rpb > 0 && (((x_bs | o_bs) & 7) || (resid && (r_bs & 7))))) return IFSEG_ERR_BAD_SHAPE;
   const long long nchunks = rows * (C / 8);
   RowMap mx = row_map(rpb, x_bs, ldx), mr = row_map(rpb, r_bs, ldr), mo = row_map(rpb, o_bs, ldo);
   hipLaunchKernelGGL(dropout_kernel, dim3((unsigned)((nchunks + 255) / 256)), dim3(256), 0, (hipStream_t)stream,

@@ -348,14 +348,16 @@ int ifseg_ln_fwd_pair(const void* x, const void* gamma, const void* beta, const 
                       long long y2_bs, int ldy2, const ifseg_drop_args* drop, void* stream);
 /* dx = [dx_add +] d/dx of the above (dy is first masked like the forward output when `drop` is given);
  * per-block partials of dgamma / dbeta are written to dgamma_part / dbeta_part [nblocks][C]
- * (sum with ifseg_reduce_parts). */
+ * (sum with ifseg_reduce_parts).  Rows are read and written 16 bytes at a time: C and every leading dimension in use a
+ * multiple of 8 (IFSEG_ERR_BAD_SHAPE), here and in every entry point that takes a (rpb, bs, ld) row map. */
 int ifseg_ln_bwd(const void* dy, const void* x, const void* gamma, const float* mean, const float* rstd,
                  const void* dx_add, void* dx, float* dgamma_part, float* dbeta_part, int nblocks, int rows,
                  int C, int act_gelu, int rpb, long long dy_bs, int lddy, long long x_bs, int ldx,
                  long long dx_bs, int lddx, long long add_bs, int ldadd, const ifseg_drop_args* drop, void* stream);
 /* ifseg_ln_bwd (C <= 1024, no GELU) with a second output dx2 = drop2(dx as stored in bf16): the pre-LN backward that
  * closes a block of the backward and the adjoint of the dropout + DropPath after fc2 (unify_transformer_layer.py:288-292,
- * 564-568) that opens the next one, in one launch.  Bit-identical to ifseg_ln_bwd followed by ifseg_dropout. */
+ * 564-568) that opens the next one, in one launch.  Bit-identical to ifseg_ln_bwd followed by ifseg_dropout.  IFSEG_LN_GELU in `flags`:
+ * IFSEG_ERR_BAD_ARG (there is no GELU instantiation). */
 int ifseg_ln_bwd_drop(const void* dy, const void* x, const void* gamma, const float* mean, const float* rstd,
                       const void* dx_add, void* dx, float* dgamma_part, float* dbeta_part, void* dx2, int nblocks, int rows,
                       int C, int flags, int rpb, long long dy_bs, int lddy, long long x_bs, int ldx, long long dx_bs, int lddx,
@@ -363,7 +365,7 @@ int ifseg_ln_bwd_drop(const void* dy, const void* x, const void* gamma, const fl
 /* Input validation in one launch, the verdict (0 / 1) written to PINNED host memory in stream order (read it after an event):
  * mode 0: any int64 x[i] == value; mode 1: rows of row_len int64: `value` entries that are not a suffix of their row (fairseq pads on
  * the right: encoder_module.py:730-752); mode 2: any byte x[i] == 0 (the bool `patch_masks`); mode 3: *x (int32 device flag) != 0,
- * and the flag is cleared.  Replaces compare + reduce + cast + copy torch kernels on the main queue between two steps. */
+ * and the flag is cleared.  Mode 1 needs n to be a multiple of row_len (IFSEG_ERR_BAD_ARG).  Replaces compare + reduce + cast + copy torch kernels on the main queue between two steps. */
 int ifseg_check_inputs(const void* x, long long n, int mode, long long value, long long row_len,
                        unsigned char* verdict_host_pinned, void* stream);
 /* fp32 master copy <- bf16 arena wherever bf16(master[i]) != p16[i] (an optimizer outside this library stepped the bf16
