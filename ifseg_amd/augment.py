@@ -55,6 +55,9 @@ the long side as int(long * float(scale) + 0.5) in Python floats, here it is the
 not available where this project is tested.  The reference reverses the channels in front of mmseg and back behind it
 (:218, :243), so its HSV reads true colours; here the input is RGB and stays RGB, and `reverse_channels` applies to the
 order of the output planes only, as in `image_load`.  The reference's `downsampled_target` is not produced.
+
+The second half of the module mixes two such batches (ClassMix / CutMix: `mix_draw_reference`, `mix_apply_reference`,
+`BatchMix`; csrc/mix.hip) on the slots of the same stream behind the transform's 28; its rule stands above `check_mix`.
 """
 import numpy as np
 import torch
@@ -391,3 +394,215 @@ class TrainTransform:
         planes = self._planes(weights, labels)
         params = self._draw(labels, first_ordinal)
         return tuple(self._apply(images, labels, params)) + (self._apply_planes(planes, params),)
+
+
+# ------------------------------------------------------------------------------------------------- the batch mix
+# ClassMix / CutMix of a labelled (source) batch into a pseudo-labelled (destination) batch: the CPU specification of
+# `hip.mix_draw` / `hip.mix_apply` (csrc/mix.hip) and `BatchMix`, the caller of both.  Two batches in `train_sample`'s layout
+# and of the same B and P: patch_images [B, 3, P, P] (fp32 or bf16, the same in both), target int64 [B, P*P + 1] and
+# optionally target_weight uint8 [B, P*P].
+#
+# CLASS OF A SOURCE PIXEL.  c = target - seg_id_offset in 64 bits (wrapping); the pixel has a class only if 0 <= c < nseg.
+# `nseg` ('unknown'), -1 (a poisoned sample of `train_load`) and any other value have none: never present, never pasted.
+#
+# RANDOM STREAM.  The transform's t(n, i) for the sample ordinal n = first_ordinal + b, on the slots behind the transform's
+# 28: a mix with the transform's seed and ordinal is independent of the transform's draws.
+#
+#     slot i     parameter
+#     28, 29     bh, bw = P // 4 + ((t (P // 2 + 1)) >> 32)                     mask "box" (CutMix)
+#     30, 31     y0 = (t (P - bh + 1)) >> 32,  x0 = (t (P - bw + 1)) >> 32      the box is rows y0 .. y0 + bh, columns x0 .. x0 + bw
+#     32 + i     j = i + ((t (n - i)) >> 32), swap c_i and c_j, i = 0 .. m - 1  mask "class" (ClassMix)
+#
+# "class": c_0 < ... < c_{n-1} the classes present in the source sample, m = (n + 1) // 2; after the partial Fisher-Yates
+# above the chosen set is c_0 .. c_{m-1} (nothing when n = 0).  The box rule is this project's own: neither the reference nor
+# mmseg has one to pin against.
+#
+# The record of a sample, int32 [16]:
+#
+#     0..7 chosen-class bits (class c is bit c & 31 of word c >> 5)   8 y0  9 x0  10 y1  11 x1 (exclusive ends)
+#     12 n present   13 m chosen   14, 15 zero
+#
+# "class" leaves 8..11 zero, "box" leaves 0..7, 12 and 13 zero.
+#
+# APPLY.  Pixel (y, x) of sample b is selected if its source class's bit is set or y0 <= y < y1 and x0 <= x < x1 (the union:
+# a caller's own record may carry both).  Selected pixels take the source's three image values, target value and weight,
+# all others keep the destination's; a missing weight plane reads as 255, and no plane comes out if neither batch has one.
+# out_target[b, P*P] (EOS) is the destination's.  Everything is a copy: parity is exact, NaN payloads included.  No address
+# depends on a record: a box outside the image selects less, bits at or above nseg are never consulted.
+MIX_SLOT_BOX, MIX_SLOT_CLASS = 28, 32
+(M_BITS, M_Y0, M_X0, M_Y1, M_X1, M_PRESENT, M_CHOSEN) = (0, 8, 9, 10, 11, 12, 13)
+MIX_MASKS = ("class", "box")
+MIX_MAX_P = 4096
+
+
+def check_mix(P, nseg, mask="class", what="batch mix"):
+    if P < 16 or P % 16 or P > MIX_MAX_P or not 1 <= nseg <= 255:
+        raise ValueError("%s: P must be a multiple of 16 in 16 .. %d and 1 <= nseg <= 255, got P = %d, nseg = %d"
+                         % (what, MIX_MAX_P, P, nseg))
+    if mask not in MIX_MASKS:
+        raise ValueError("%s: mask must be one of %r, got %r" % (what, MIX_MASKS, mask))
+
+
+def mix_patch_size(target, what="batch mix"):
+    """P of a target int64 [B, P*P + 1]"""
+    if not torch.is_tensor(target) or target.dtype != torch.int64 or target.dim() != 2 or target.shape[0] < 1 or target.shape[1] < 2:
+        raise ValueError("%s: a target must be int64 [B, P*P + 1] with B >= 1, got %s"
+                         % (what, (target.dtype, tuple(target.shape)) if torch.is_tensor(target) else type(target)))
+    P = int(round((target.shape[1] - 1) ** 0.5))
+    if P * P + 1 != target.shape[1]:
+        raise ValueError("%s: a target row holds P*P + 1 entries, got %d" % (what, target.shape[1]))
+    return P
+
+
+def check_mix_batches(src_images, src_target, src_weight, dst_images, dst_target, dst_weight, what="batch mix"):
+    """the shapes and dtypes of two batches that can be mixed -> (B, P); reads no values"""
+    P = mix_patch_size(src_target, what)
+    B = src_target.shape[0]
+    if tuple(dst_target.shape) != tuple(src_target.shape) or dst_target.dtype != torch.int64:
+        raise ValueError("%s: the two targets must be int64 of one shape (equal B and P), got %s and %s %s"
+                         % (what, tuple(src_target.shape), dst_target.dtype, tuple(dst_target.shape)))
+    for name, img in (("source", src_images), ("destination", dst_images)):
+        if img.dtype not in (torch.float32, torch.bfloat16) or tuple(img.shape) != (B, 3, P, P):
+            raise ValueError("%s: the %s images must be fp32 or bf16 [%d, 3, %d, %d], got %s %s"
+                             % (what, name, B, P, P, img.dtype, tuple(img.shape)))
+    if src_images.dtype != dst_images.dtype:
+        raise ValueError("%s: the two image batches must share a dtype, got %s and %s" % (what, src_images.dtype, dst_images.dtype))
+    for name, w in (("source", src_weight), ("destination", dst_weight)):
+        if w is not None and (w.dtype != torch.uint8 or tuple(w.shape) != (B, P * P)):
+            raise ValueError("%s: the %s weight plane must be uint8 [%d, %d], got %s %s" % (what, name, B, P * P, w.dtype, tuple(w.shape)))
+    return B, P
+
+
+def mix_batch(x):
+    """a sample in `train_sample`'s layout, or (images, target[, weight]) -> (images, target, weight | None)"""
+    if isinstance(x, dict):
+        return x["net_input"]["patch_images"], x["target"], x.get("target_weight")
+    x = tuple(x)
+    if len(x) not in (2, 3):
+        raise ValueError("batch mix: a batch is a sample or (images, target[, weight]), got %d entries" % len(x))
+    return x[0], x[1], (x[2] if len(x) == 3 else None)
+
+
+def mix_classes(target_row, nseg, seg_id_offset):
+    """the classes present in one source target row (int64 [P*P], EOS not included), ascending"""
+    c = torch.as_tensor(target_row).reshape(-1) - int(seg_id_offset)               # wraps in 64 bits, as on the device
+    return torch.unique(c[(c >= 0) & (c < nseg)]).tolist()
+
+
+def mix_choice(present, seed, ordinal):
+    """the chosen half of the ascending class list `present`: the partial Fisher-Yates on slots 32 .. 32 + m - 1"""
+    c, n = list(present), len(present)
+    m = (n + 1) // 2
+    t = draws(seed, ordinal, MIX_SLOT_CLASS + m)
+    for i in range(m):
+        j = i + ((t[MIX_SLOT_CLASS + i] * (n - i)) >> 32)
+        c[i], c[j] = c[j], c[i]
+    return c[:m]
+
+
+def mix_box(P, seed, ordinal):
+    """-> (y0, x0, y1, x1) of the CutMix box, exclusive ends"""
+    t = draws(seed, ordinal, MIX_SLOT_BOX + 4)[MIX_SLOT_BOX:]
+    bh, bw = P // 4 + ((t[0] * (P // 2 + 1)) >> 32), P // 4 + ((t[1] * (P // 2 + 1)) >> 32)
+    y0, x0 = (t[2] * (P - bh + 1)) >> 32, (t[3] * (P - bw + 1)) >> 32
+    return y0, x0, y0 + bh, x0 + bw
+
+
+def mix_draw_reference(src_target, nseg, seg_id_offset, seed, first_ordinal, mask="class"):
+    """CPU specification of hip.mix_draw.  src_target int64 [B, P*P + 1] -> the records int32 [B, 16] of the samples at
+    ordinals first_ordinal + b."""
+    src_target = torch.as_tensor(src_target).cpu()
+    P, nseg, first = mix_patch_size(src_target), int(nseg), int(first_ordinal)
+    check_mix(P, nseg, mask)
+    B = src_target.shape[0]
+    if first < 0 or first + B > 1 << 32:
+        raise ValueError("batch mix: ordinals must lie in [0, 2^32)")
+    out = np.zeros((B, RECORD), dtype=np.uint32)
+    for b in range(B):
+        if mask == "box":
+            out[b, M_Y0:M_X1 + 1] = mix_box(P, seed, first + b)
+            continue
+        present = mix_classes(src_target[b, :-1], nseg, seg_id_offset)
+        chosen = mix_choice(present, seed, first + b)
+        for c in chosen:
+            out[b, M_BITS + (c >> 5)] |= np.uint32(1 << (c & 31))
+        out[b, M_PRESENT], out[b, M_CHOSEN] = len(present), len(chosen)
+    return torch.from_numpy(out.view(np.int32))
+
+
+def mix_selection(records, src_target, nseg, seg_id_offset):
+    """bool [B, P*P]: the pixels the records select"""
+    records = torch.as_tensor(records).cpu()
+    src_target = torch.as_tensor(src_target).cpu()
+    P = mix_patch_size(src_target)
+    B = src_target.shape[0]
+    if records.dtype != torch.int32 or tuple(records.shape) != (B, RECORD):
+        raise ValueError("batch mix: records must be int32 [%d, 16], got %s %s" % (B, records.dtype, tuple(records.shape)))
+    rec = records.long()
+    c = src_target[:, :-1] - int(seg_id_offset)
+    has = (c >= 0) & (c < nseg)
+    cc = torch.where(has, c, torch.zeros_like(c))
+    word = rec[:, M_BITS:M_BITS + 8].gather(1, cc >> 5)
+    sel = has & (((word >> (cc & 31)) & 1) == 1)
+    y, x = torch.arange(P)[None, :, None], torch.arange(P)[None, None, :]
+    r = lambda k: rec[:, k, None, None]
+    box = (y >= r(M_Y0)) & (y < r(M_Y1)) & (x >= r(M_X0)) & (x < r(M_X1))
+    return sel | box.reshape(B, P * P)
+
+
+def mix_apply_reference(records, src, dst, nseg, seg_id_offset):
+    """CPU specification of hip.mix_apply.  records int32 [B, 16], src / dst: samples in `train_sample`'s layout or
+    (images, target[, weight]) -> (images [B, 3, P, P], target int64 [B, P*P + 1], weight uint8 [B, P*P] | None)"""
+    (si, st, sw), (di, dt, dw) = ([None if t is None else torch.as_tensor(t).cpu() for t in mix_batch(x)] for x in (src, dst))
+    B, P = check_mix_batches(si, st, sw, di, dt, dw)
+    check_mix(P, int(nseg))
+    sel = mix_selection(records, st, int(nseg), seg_id_offset)
+    # images through an integer view: a copy, whatever the bits say
+    iv = torch.int32 if si.dtype == torch.float32 else torch.int16
+    images = torch.where(sel.reshape(B, 1, P, P), si.contiguous().view(iv), di.contiguous().view(iv)).view(si.dtype)
+    target = dt.clone()
+    target[:, :-1] = torch.where(sel, st[:, :-1], dt[:, :-1])
+    if sw is None and dw is None:
+        return images, target, None
+    full = torch.full((B, P * P), 255, dtype=torch.uint8)
+    return images, target, torch.where(sel, full if sw is None else sw, full if dw is None else dw)
+
+
+class BatchMix:
+    def __init__(self, P, nseg, seg_id_offset, seed=1, device="cpu", mask="class"):
+        """device "cpu" runs the specification of this module, any other device the kernels of csrc/mix.hip"""
+        self.P, self.nseg, self.seg_id_offset = int(P), int(nseg), int(seg_id_offset)
+        check_mix(self.P, self.nseg, mask, "BatchMix")
+        self.seed, self.device, self.mask = int(seed) & _M64, torch.device(device), mask
+
+    def _batch(self, x):
+        img, tgt, wgt = mix_batch(x)
+        if mix_patch_size(tgt, "BatchMix") != self.P:
+            raise ValueError("BatchMix: built for P = %d, got a target of %s" % (self.P, tuple(tgt.shape)))
+        return tuple(None if t is None else t.to(self.device) for t in (img, tgt, wgt))
+
+    def draw(self, src, first_ordinal):
+        """src: a sample, (images, target[, weight]) or the source target itself -> int32 [B, 16] on the mix's device"""
+        tgt = src if torch.is_tensor(src) else mix_batch(src)[1]
+        if mix_patch_size(tgt, "BatchMix") != self.P:
+            raise ValueError("BatchMix: built for P = %d, got a target of %s" % (self.P, tuple(tgt.shape)))
+        tgt = tgt.to(self.device)
+        if self.device.type == "cpu":
+            return mix_draw_reference(tgt, self.nseg, self.seg_id_offset, self.seed, first_ordinal, self.mask)
+        from . import hip
+        return hip.mix_draw(tgt.contiguous(), self.nseg, self.seg_id_offset, self.seed, first_ordinal, self.mask)
+
+    def apply(self, records, src, dst, out=None):
+        """the caller's records -> (images, target, weight | None); out: (images, target, weight | None) to write into on a
+        GPU device, which may be the destination's own tensors"""
+        (si, st, sw), (di, dt, dw) = self._batch(src), self._batch(dst)
+        check_mix_batches(si, st, sw, di, dt, dw, "BatchMix")
+        if self.device.type == "cpu":
+            return mix_apply_reference(records, (si, st, sw), (di, dt, dw), self.nseg, self.seg_id_offset)
+        from . import hip
+        c = lambda t: None if t is None else t.contiguous()
+        return hip.mix_apply(records.to(self.device).contiguous(), c(si), c(st), c(di), c(dt), self.nseg, self.seg_id_offset,
+                             src_weight=c(sw), dst_weight=c(dw), out=out)
+
+    def __call__(self, src, dst, first_ordinal):
+        return self.apply(self.draw(src, first_ordinal), src, dst)

@@ -1674,6 +1674,89 @@ def train_load_plane(planes, params, P, out=None, table=None):
     return out
 
 
+# --------------------------------------------------------------------------- ClassMix / CutMix of two batches
+MIX_MASKS = {"class": 0, "box": 1}
+MIX_MAX_P = 4096             # == MX_MAX_P (csrc/mix.hip)
+
+
+def _mix_target(t, what):
+    """int64 [B, P*P + 1] on the device, contiguous -> (B, P)"""
+    assert t.is_cuda and t.dtype == torch.int64 and t.dim() == 2 and t.is_contiguous() and t.data_ptr() % 8 == 0, \
+        (what, t.device, t.dtype, tuple(t.shape), t.stride())
+    B, P = t.shape[0], int(round((t.shape[1] - 1) ** 0.5))
+    assert B >= 1 and P * P + 1 == t.shape[1] and P >= 16 and P % 16 == 0 and P <= MIX_MAX_P, (what, tuple(t.shape))
+    return B, P
+
+
+def mix_draw(src_target, nseg, seg_id_offset, seed, first_ordinal, mask="class", out=None):
+    """records int32 [B, 16] of the batch mix for the samples at ordinals first_ordinal + b, one launch (csrc/mix.hip;
+    `augment.mix_draw_reference` is the specification and states the rule).  src_target: int64 [B, P*P + 1], the labelled
+    batch's targets; mask "class" (ClassMix: half of the classes present in each sample) or "box" (CutMix: a rectangle)."""
+    B, P = _mix_target(src_target, "mix_draw")
+    assert isinstance(nseg, int) and 1 <= nseg <= 255, nseg
+    assert mask in MIX_MASKS, mask
+    first = int(first_ordinal)
+    assert 0 <= first and first + B <= 2 ** 32, (first, B)
+    if out is None:
+        out = torch.empty(B, 16, dtype=torch.int32, device=src_target.device)
+    else:
+        assert out.dtype == torch.int32 and tuple(out.shape) == (B, 16) and out.is_contiguous() and out.device == src_target.device \
+            and not _overlap(out, src_target), (out.dtype, tuple(out.shape), out.stride(), out.device)
+    _check(lib().ifseg_mix_draw(_ptr(src_target), c_int(B), c_int(P), c_int(nseg), c_ll(int(seg_id_offset)),
+                                ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), c_ll(first), c_int(MIX_MASKS[mask]), _ptr(out),
+                                _stream()), "mix_draw")
+    return out
+
+
+def mix_apply(records, src_images, src_target, dst_images, dst_target, nseg, seg_id_offset, src_weight=None, dst_weight=None,
+              out=None):
+    """the batch mix under the given records, one launch (csrc/mix.hip; `augment.mix_apply_reference` is the specification):
+    the pixels a record selects -- a chosen class of the SOURCE pixel, or the record's box -- take the source's image values,
+    target and weight, the others keep the destination's -> (images [B, 3, P, P], target int64 [B, P*P + 1], weight uint8
+    [B, P*P] or None).  Images fp32 or bf16, the same in both batches; weights uint8 [B, P*P] or None, a missing plane reads
+    as 255 and no plane comes out if both are missing.  Everything contiguous.  out: (images, target, weight | None) to
+    write into; each may be the destination's own tensor (in place), and must not overlap anything else."""
+    B, P = _mix_target(src_target, "mix_apply")
+    dev, n = src_target.device, P * P
+    assert _mix_target(dst_target, "mix_apply") == (B, P) and dst_target.device == dev, (tuple(src_target.shape), tuple(dst_target.shape))
+    assert isinstance(nseg, int) and 1 <= nseg <= 255, nseg
+    assert records.is_cuda and records.device == dev and records.dtype == torch.int32 and tuple(records.shape) == (B, 16) \
+        and records.is_contiguous(), (records.device, records.dtype, tuple(records.shape))
+    assert src_images.dtype in (torch.float32, torch.bfloat16) and src_images.dtype == dst_images.dtype, (src_images.dtype, dst_images.dtype)
+    assert B * 3 * n < 2 ** 31, (B, P)
+    for t in (src_images, dst_images):
+        assert t.device == dev and tuple(t.shape) == (B, 3, P, P) and t.is_contiguous() and t.data_ptr() % 16 == 0, \
+            (t.device, tuple(t.shape), t.stride())
+    for t in (src_weight, dst_weight):
+        assert t is None or (t.device == dev and t.dtype == torch.uint8 and tuple(t.shape) == (B, n) and t.is_contiguous()
+                             and t.data_ptr() % 8 == 0), (t.device, t.dtype, tuple(t.shape), t.stride())
+    weighted = src_weight is not None or dst_weight is not None
+    if out is None:
+        out = (torch.empty_like(dst_images), torch.empty_like(dst_target),
+               torch.empty(B, n, dtype=torch.uint8, device=dev) if weighted else None)
+    oi, ot, ow = out
+    assert oi.dtype == dst_images.dtype and oi.shape == dst_images.shape and oi.is_contiguous() and oi.device == dev \
+        and oi.data_ptr() % 16 == 0, (oi.dtype, tuple(oi.shape), oi.stride(), oi.device)
+    assert ot.dtype == torch.int64 and ot.shape == dst_target.shape and ot.is_contiguous() and ot.device == dev \
+        and ot.data_ptr() % 8 == 0, (ot.dtype, tuple(ot.shape), ot.stride(), ot.device)
+    assert (ow is not None) == weighted, "mix_apply: a weight plane comes out exactly when one goes in"
+    assert ow is None or (ow.dtype == torch.uint8 and tuple(ow.shape) == (B, n) and ow.is_contiguous() and ow.device == dev
+                          and ow.data_ptr() % 8 == 0), (ow.dtype, tuple(ow.shape), ow.stride(), ow.device)
+    outs, dsts = (oi, ot, ow), (dst_images, dst_target, dst_weight)
+    for i, o in enumerate(outs):
+        if o is None:
+            continue
+        for t in (records, src_images, src_target, src_weight) + outs[i + 1:]:
+            assert t is None or not _overlap(o, t), "mix_apply: out overlaps the source, the records or another output"
+        for j, t in enumerate(dsts):
+            assert t is None or not _overlap(o, t) or (i == j and o.data_ptr() == t.data_ptr()), \
+                "mix_apply: out may be the destination tensor it replaces, and overlaps the destination in no other way"
+    _check(lib().ifseg_mix_apply(_ptr(records), _ptr(src_images), _ptr(src_target), _ptr(src_weight), _ptr(dst_images),
+                                 _ptr(dst_target), _ptr(dst_weight), c_int(B), c_int(P), c_int(nseg), c_ll(int(seg_id_offset)),
+                                 c_int(src_images.element_size()), _ptr(oi), _ptr(ot), _ptr(ow), _stream()), "mix_apply")
+    return oi, ot, ow
+
+
 def dropout(x, resid, out, p, seed, drop_path_scale=None, rows_per_batch=None):
     """x / resid / out: [rows, C] or [B, rpb, C] bf16 views (last dim contiguous)"""
     C = x.shape[-1]

@@ -31,7 +31,9 @@ ignore band along class edges into pseudo-labels for self-training) and the two 
 K views, each a set of windows, merged in one launch, optionally softmaxed per view as mmseg does) are inference only and
 have no backward; `train_load`
 (csrc/trainload.hip: raw images and label maps of any sizes to a training batch under given records, the reference's training
-transform) has integer inputs and no backward either.
+transform) has integer inputs and no backward either, and neither have `mix_draw` / `mix_apply` (csrc/mix.hip: ClassMix /
+CutMix of a labelled batch into a pseudo-labelled one -- the choice of classes or of a box, and the paste of images, targets
+and weight planes, which copies bits).
 """
 from typing import Optional, Sequence, Tuple
 
@@ -1358,3 +1360,73 @@ def train_load(images: Sequence[torch.Tensor], labels: Sequence[torch.Tensor], p
 def _(images, labels, params, P, nseg, seg_id_offset, mean, std, reverse_channels, raw_labels, dtype):
     B = _train_load_check(images, labels, params, P, nseg, mean, std, dtype)
     return params.new_empty((B, 3, P, P), dtype=dtype), params.new_empty((B, P * P + 1), dtype=torch.int64)
+
+
+# ----------------------------------------------------------------------------------------------- mix_draw / mix_apply
+def _mix_draw_check(src_target, nseg, first_ordinal, mask):
+    from .augment import check_mix, mix_patch_size
+    op = "ifseg::mix_draw"
+    P = mix_patch_size(src_target, op)
+    check_mix(P, nseg, mask, op)
+    B = src_target.shape[0]
+    if first_ordinal < 0 or first_ordinal + B > 2 ** 32:
+        raise ValueError("%s: ordinals must lie in [0, 2**32), got %d .. %d" % (op, first_ordinal, first_ordinal + B - 1))
+    return B
+
+
+@custom_op("ifseg::mix_draw", mutates_args=(), device_types="cuda")
+def mix_draw(src_target: torch.Tensor, nseg: int, seg_id_offset: int, seed: int, first_ordinal: int, mask: str) -> torch.Tensor:
+    """the records int32 [B, 16] of the batch mix (csrc/mix.hip; `augment.mix_draw_reference` is the specification):
+    src_target int64 [B, P*P + 1], mask "class" (ClassMix) or "box" (CutMix); a pure function of (seed, first_ordinal + b) and,
+    for "class", of the classes present in sample b.  Integer inputs: not differentiable."""
+    _mix_draw_check(src_target, nseg, first_ordinal, mask)
+    prev = _stream_scope(src_target)
+    try:
+        return hip.mix_draw(src_target.contiguous(), nseg, seg_id_offset, seed, first_ordinal, mask)
+    finally:
+        hip.set_stream(prev)
+
+
+@mix_draw.register_fake
+def _(src_target, nseg, seg_id_offset, seed, first_ordinal, mask):
+    B = _mix_draw_check(src_target, nseg, first_ordinal, mask)
+    return src_target.new_empty((B, 16), dtype=torch.int32)
+
+
+def _mix_apply_check(records, src_images, src_target, src_weight, dst_images, dst_target, dst_weight, nseg):
+    from .augment import check_mix, check_mix_batches
+    op = "ifseg::mix_apply"
+    B, P = check_mix_batches(src_images, src_target, src_weight, dst_images, dst_target, dst_weight, op)
+    check_mix(P, nseg, what=op)
+    if records.dtype != torch.int32 or tuple(records.shape) != (B, 16):
+        raise ValueError("%s: records must be int32 [%d, 16], got %s %s" % (op, B, records.dtype, tuple(records.shape)))
+    if B * 3 * P * P >= 2 ** 31:
+        raise ValueError("%s: B * 3 * P * P must stay below 2**31, got B = %d, P = %d" % (op, B, P))
+    return B, P
+
+
+@custom_op("ifseg::mix_apply", mutates_args=(), device_types="cuda")
+def mix_apply(records: torch.Tensor, src_images: torch.Tensor, src_target: torch.Tensor, src_weight: Optional[torch.Tensor],
+              dst_images: torch.Tensor, dst_target: torch.Tensor, dst_weight: Optional[torch.Tensor], nseg: int,
+              seg_id_offset: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """the batch mix under the given records (csrc/mix.hip; `augment.mix_apply_reference` is the specification): the pixels
+    a record selects take the source's image values, target and weight, the others keep the destination's ->
+    (images [B, 3, P, P], target int64 [B, P*P + 1], weight uint8 [B, P*P] -- an empty tensor when neither batch has a plane).
+    A copy of bits: not differentiable."""
+    _mix_apply_check(records, src_images, src_target, src_weight, dst_images, dst_target, dst_weight, nseg)
+    prev = _stream_scope(records)
+    try:
+        c = lambda t: None if t is None else t.contiguous()
+        img, tgt, wgt = hip.mix_apply(records.contiguous(), c(src_images), c(src_target), c(dst_images), c(dst_target), nseg,
+                                      seg_id_offset, src_weight=c(src_weight), dst_weight=c(dst_weight))
+        return img, tgt, torch.empty(0, dtype=torch.uint8, device=records.device) if wgt is None else wgt
+    finally:
+        hip.set_stream(prev)
+
+
+@mix_apply.register_fake
+def _(records, src_images, src_target, src_weight, dst_images, dst_target, dst_weight, nseg, seg_id_offset):
+    B, P = _mix_apply_check(records, src_images, src_target, src_weight, dst_images, dst_target, dst_weight, nseg)
+    weighted = src_weight is not None or dst_weight is not None
+    return (dst_images.new_empty((B, 3, P, P)), dst_target.new_empty((B, P * P + 1)),
+            records.new_empty((B, P * P) if weighted else (0,), dtype=torch.uint8))

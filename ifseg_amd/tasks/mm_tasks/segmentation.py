@@ -413,6 +413,57 @@ class SegmentationTask(TaskBase):
             sample["target_weight"] = wgt
         return sample
 
+    def build_batch_mix(self, mask="class"):
+        """The ClassMix / CutMix of two batches (ifseg_amd/augment.py `BatchMix`) with the train transform's patch size,
+        class count, seed and device; on a GPU device it runs csrc/mix.hip.  One per mask, kept."""
+        from ...augment import BatchMix
+        tf = getattr(self, "train_transform", None) or self.build_train_transform()
+        mixes = self.__dict__.setdefault("_batch_mixes", {})
+        key = (mask, tf.P, tf.nseg, tf.seg_id_offset, tf.seed, tf.device)
+        if key not in mixes:
+            mixes[key] = BatchMix(tf.P, tf.nseg, tf.seg_id_offset, seed=tf.seed, device=tf.device, mask=mask)
+        return mixes[key]
+
+    def mix_samples(self, source_sample, target_sample, first_ordinal, mask="class"):
+        """Two batches in `train_sample`'s layout -> one: the pixels of half of the classes present in each source (labelled)
+        sample (mask "class", ClassMix) or of a random rectangle (mask "box", CutMix) are pasted over the target
+        (pseudo-labelled) sample -- image, label and loss weight travel together (`augment.BatchMix` states the rule; a pure
+        function of (seed, first_ordinal + b)).  -> the batch `Trainer.train_step` takes: the target sample with
+        `patch_images`, `target` and, if either sample has one, `target_weight` replaced (a missing plane counts as 255).
+        A different B, P or prompt length: ValueError."""
+        from ...augment import check_mix_batches, mix_batch
+        mix = self.build_batch_mix(mask)
+        src, dst = mix_batch(source_sample), mix_batch(target_sample)
+        check_mix_batches(*src, *dst, what="mix_samples")
+        s_tok, d_tok = source_sample["net_input"]["src_tokens"], target_sample["net_input"]["src_tokens"]
+        if tuple(s_tok.shape) != tuple(d_tok.shape):
+            raise ValueError("mix_samples: the two samples carry prompts of different lengths, %s and %s"
+                             % (tuple(s_tok.shape), tuple(d_tok.shape)))
+        img, tgt, wgt = mix(src, dst, first_ordinal)
+        sample = {k: v for k, v in target_sample.items() if k != "target_weight"}
+        sample["net_input"] = dict(target_sample["net_input"], patch_images=img)
+        sample["target"] = tgt
+        if wgt is not None:
+            sample["target_weight"] = wgt
+        return sample
+
+    def dacs_sample(self, model, images, labels, unlabeled, first_ordinal, trainer=None, mask="class", **kw):
+        """One batch of cross-domain mixed self-training (DACS, Tranheden et al. 2021; ClassMix / CutMix): the labelled batch
+        `train_sample(images, labels, first_ordinal)` pasted by `mix_samples(..., first_ordinal)` over the pseudo-labelled
+        batch `self_train_sample(model, unlabeled, first_ordinal + 2**31, trainer=trainer, confidence_weight=True, **kw)`.
+        The unlabelled samples take their ordinals from the upper half of the ordinal range, so the two transforms draw
+        independently: first_ordinal + B <= 2**31, else ValueError.  Pasted labelled pixels weigh 255, the rest the teacher's
+        confidence; the criterion's default `weight_norm="weights"` is scale-free.  DACS applies its colour jitter after the
+        mix; here each half keeps its own transform's jitter."""
+        images = [images] if torch.is_tensor(images) else list(images)
+        first = int(first_ordinal)
+        if first < 0 or first + len(images) > 2 ** 31:
+            raise ValueError("dacs_sample: first_ordinal + B must stay within 2**31 (the unlabelled batch draws at "
+                             "first_ordinal + 2**31), got %d + %d" % (first, len(images)))
+        source = self.train_sample(images, labels, first)
+        target = self.self_train_sample(model, unlabeled, first + 2 ** 31, trainer=trainer, confidence_weight=True, **kw)
+        return self.mix_samples(source, target, first, mask=mask)
+
     def train_step(self, sample, model, criterion, optimizer, update_num, ignore_grad=False, **extra_kwargs):
         """tasks/mm_tasks/segmentation.py:190-222."""
         if not model.training:      # nn.Module.train() walks every sub-module: only when the mode changes

@@ -856,6 +856,36 @@ int ifseg_train_load_staging(int max_bytes);
 int ifseg_train_load_plane(const ifseg_train_src* table_host, const ifseg_train_src* table, const int* params,
                            const int* params_host, int B, int P, void* out, void* stream);
 
+/* ---- ClassMix / CutMix of a labelled (source) batch into a pseudo-labelled (destination) batch, both in ifseg_train_load's
+ * layout and of one B and P (ifseg_amd/augment.py, "the batch mix", is the specification, bit for bit; csrc/mix.hip; the
+ * reference has no counterpart: DACS / ClassMix choose with torch.unique and numpy on the host) ----
+ * The class of a source pixel is c = target - seg_id_offset in 64 bits, a class only if 0 <= c < nseg.
+ * ifseg_mix_draw writes the records int32 [B, 16] of the samples at ordinals first_ordinal + b, from the transform's stream
+ * t(n, i) = splitmix64(seed + (n << 32) + i) >> 32 on the slots behind the transform's 28:
+ *   0..7 chosen-class bits (class c is bit c & 31 of word c >> 5)   8 y0  9 x0  10 y1  11 x1 (exclusive)   12 n present
+ *   13 m chosen   14, 15 zero
+ * box == 0 (ClassMix): c_0 < .. < c_{n-1} the classes present in src_target[b] (int64 [B, P*P + 1], the last entry of a row is
+ * not read), m = (n + 1) / 2; for i = 0 .. m-1: j = i + ((t(32 + i) (n - i)) >> 32), swap c_i and c_j; chosen c_0 .. c_{m-1};
+ * words 8..11 zero.  box == 1 (CutMix): bh, bw = P/4 + ((t28|t29 (P/2 + 1)) >> 32), y0 = (t30 (P - bh + 1)) >> 32,
+ * x0 = (t31 (P - bw + 1)) >> 32, y1 = y0 + bh, x1 = x0 + bw; words 0..7, 12, 13 zero and src_target is not read.
+ * One launch of B workgroups, no scratch, nothing read back.  NULL or misaligned pointers (target 8 bytes, records 4), nseg
+ * outside 1..255, box outside {0, 1}, ordinals outside [0, 2^32): IFSEG_ERR_BAD_ARG; B outside 1..65535, P not a multiple of
+ * 16 in 16..4096: IFSEG_ERR_BAD_SHAPE. */
+int ifseg_mix_draw(const long long* src_target, int B, int P, int nseg, long long seg_id_offset, unsigned long long seed,
+                   long long first_ordinal, int box, int* records, void* stream);
+/* ifseg_mix_apply pastes, one launch: pixel (y, x) of sample b is selected if its source class's bit is set in the record or
+ * y0 <= y < y1 and x0 <= x < x1 (the union; a box outside the image selects less, bits at or above nseg are not consulted).
+ * Selected pixels take the source's three image values (elem_bytes 4: fp32, 2: bf16; copied as bits), target and weight,
+ * the others the destination's; out_target[b][P*P] is the destination's.  A NULL weight plane reads as 255; out_weight is
+ * NULL exactly when both planes are.  An output may be the destination tensor it replaces, the same pointer; any other
+ * shared byte between an output and an input, the records or another output: IFSEG_ERR_BAD_ARG.  NULL / misaligned pointers
+ * (images 16 bytes, targets and weights 8, records 4), elem_bytes, nseg outside 1..255: IFSEG_ERR_BAD_ARG; B outside
+ * 1..65535, P not a multiple of 16 in 16..4096, B*3*P*P >= 2^31: IFSEG_ERR_BAD_SHAPE.  Nothing is launched on a refusal. */
+int ifseg_mix_apply(const int* records, const void* src_images, const long long* src_target, const void* src_weight,
+                    const void* dst_images, const long long* dst_target, const void* dst_weight, int B, int P, int nseg,
+                    long long seg_id_offset, int elem_bytes, void* out_images, long long* out_target, void* out_weight,
+                    void* stream);
+
 /* sum of squares of a bf16 gradient arena -> out_sumsq[0] (device). */
 int ifseg_grad_sumsq_bf16(const void* g, long long n, float* workspace, float* out_sumsq, void* stream);
 /* Fused grad scaling + clip-by-global-norm + Adam with decoupled weight decay over a
