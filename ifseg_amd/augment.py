@@ -58,6 +58,8 @@ order of the output planes only, as in `image_load`.  The reference's `downsampl
 
 The second half of the module mixes two such batches (ClassMix / CutMix: `mix_draw_reference`, `mix_apply_reference`,
 `BatchMix`; csrc/mix.hip) on the slots of the same stream behind the transform's 28; its rule stands above `check_mix`.
+The third section is the strong augmentation of a mixed batch (colour jitter, then Gaussian blur: `strong_draw_reference`,
+`strong_apply_reference`, `StrongAugment`; csrc/strong.hip) on slots 192..199; its rule stands above `BLUR_WEIGHTS`.
 """
 import numpy as np
 import torch
@@ -606,3 +608,215 @@ class BatchMix:
 
     def __call__(self, src, dst, first_ordinal):
         return self.apply(self.draw(src, first_ordinal), src, dst)
+
+
+# ------------------------------------------------------------------------------------------------- the strong augmentation
+# DACS' `strong_transform` behind the mix: colour jitter (p = 0.8), then Gaussian blur (p = 0.5), on the images of a mixed
+# sample -- the CPU specification of `hip.strong_draw` / `hip.strong_apply` (csrc/strong.hip) and `StrongAugment`, the caller
+# of both.  Images [B, 3, P, P], fp32 or bf16, in `train_sample`'s layout -> the same shape and dtype; labels and weight
+# planes are not touched.  Everything between the input and the output is integer.
+#
+# GREY LEVELS.  lut = imageio.normalisation_table(mean, std) (fp32 [3, 256], increasing per row: std <= 0 is refused) and
+# mid[c][k] = fp32((float64(lut[c][k-1]) + float64(lut[c][k])) / 2), k = 1..255.  The grey level of a value x in plane c is
+# q = #{k : fp32(x) >= mid[c][k]}: comparisons only.  Every table value gives its own index back, a NaN gives 0, +inf 255,
+# anything else the nearest level.  Plane c holds colour 2 - c under `reverse_channels`, else c, and uses lut[c].
+#
+# JITTER.  `photometric(q_rgb, record)` above, unchanged, on true colours (planes un-reversed first).
+#
+# BLUR.  Separable, 9 taps, integer weights w0..w4 with w0 + 2 (w1 + w2 + w3 + w4) = 4096, the border reflected without
+# repeating the edge, r(i) = -i for i < 0, 2 (P - 1) - i for i >= P:
+#     h[y][x] = sum_{d=-4..4} w|d| q'[y][r(x + d)]      v[y][x] = sum_d w|d| h[r(y + d)][x]      q'' = (v + 2^23) >> 24
+# inside unsigned 32 bits (<= 255 2^24 + 2^23); weights (4096, 0, 0, 0, 0) are the identity.  `BLUR_WEIGHTS` int [64, 5]: for
+# sigma index s, sigma = 0.15 + s / 64 in [0.15, 1.135), g_i = exp(-i^2 / (2 sigma^2)), Z = g_0 + 2 sum_{i>=1} g_i in float64,
+# w_i = floor(4096 g_i / Z + 0.5) for i = 1..4, w_0 = 4096 - 2 sum w_i.  No tap beyond 4 rounds to a non-zero weight, and no
+# product 4096 g_i / Z lies closer than 1.3e-3 to a rounding boundary: a libm off by an ulp cannot change the table.
+#
+# OUTPUT.  lut[c][q''], cast to the image dtype.
+#
+# RANDOM STREAM.  The transform's t(n, i) at the sample ordinal n = first_ordinal + b, slots 192..199 (the transform ends at
+# slot 27, the box uses 28..31, ClassMix at most 32..159):
+#
+#     192        jitter gate: on iff (t >> 24) < jitter_p8 (205: 0.80)
+#     193        bits of t, in slot 23's positions: 1 brightness on, 2 mode, 3 contrast on, 4 saturation on, 5 hue on; the four
+#                "on" bits ANDed with the gate
+#     194..197   beta, alpha_c, alpha_s, delta by the formulas of slots 24..27
+#     198        blur gate: on iff (t >> 24) < blur_p8 (128: 0.50)
+#     199        sigma index t >> 26
+#
+# The record of a sample, int32 [16]:
+#
+#     0 bright  1 contrast  2 sat  3 hue  4 mode  5 beta  6 alpha_c  7 alpha_s (fp32 bit patterns)  8 delta
+#     9 sigma index (-1: blur off)  10..14 w0..w4  15 zero
+#
+# With blur off words 10..14 are (4096, 0, 0, 0, 0).  A caller may pass its own records (a box filter, say).  A record is
+# valid iff words 0..4 are in {0, 1}, the three floats are finite, every w_i >= 0 and w0 + 2 sum w = 4096; delta is reduced
+# mod 180.  An invalid record poisons its sample with NaN images; nothing is indexed through a record.
+#
+# NOT pinned: kornia's float `ColorJitter` and its kernel-size rule (neither kornia nor DACS is available where this project
+# is tested).  The jitter is this project's integer PhotoMetricDistortion chain at its existing strengths; the blur truncates
+# at radius 4 because 12-bit weights are zero beyond it.
+STRONG_SLOT = 192
+(S_BRIGHT, S_CONTRAST, S_SAT, S_HUE, S_MODE, S_BETA, S_ALPHA_C, S_ALPHA_S, S_DELTA, S_SIGMA, S_W0) = range(11)
+BLUR_RADIUS, BLUR_ONE, BLUR_SIGMAS = 4, 4096, 64
+STRONG_MAX_P = 4096
+
+
+def blur_weights(sigma, taps=BLUR_RADIUS, tail=16):
+    """(w0, .., w_taps) of one sigma by the rule above; Z sums every tap up to `tail`, behind which g_i vanishes beside g_0 in
+    float64 for any sigma of the table.  Every tap beyond `taps` must round to a zero weight."""
+    g = [float(np.exp(np.float64(-i * i) / (2 * np.float64(sigma) ** 2))) for i in range(tail + 1)]
+    Z = g[0] + 2 * sum(g[1:])
+    w = [int(np.floor(BLUR_ONE * g[i] / Z + 0.5)) for i in range(1, tail + 1)]
+    if any(w[taps:]):
+        raise ValueError("blur_weights: sigma %r needs more than %d taps" % (sigma, taps))
+    return [BLUR_ONE - 2 * sum(w[:taps])] + w[:taps]
+
+
+BLUR_WEIGHTS = np.array([blur_weights(0.15 + s / 64.0) for s in range(BLUR_SIGMAS)], dtype=np.int64)
+BLUR_IDENTITY = (BLUR_ONE, 0, 0, 0, 0)
+
+
+def check_strong(P, mean=HALF, std=HALF, jitter_p8=205, blur_p8=128, what="strong augmentation"):
+    if P < 16 or P % 16 or P > STRONG_MAX_P:
+        raise ValueError("%s: P must be a multiple of 16 in 16 .. %d, got %d" % (what, STRONG_MAX_P, P))
+    if len(tuple(mean)) != 3 or len(tuple(std)) != 3 or not all(float(s) > 0 for s in std):
+        raise ValueError("%s: mean and std hold three entries and std > 0 (the table must increase), got %r %r" % (what, mean, std))
+    for name, p8 in (("jitter_p8", jitter_p8), ("blur_p8", blur_p8)):
+        if not 0 <= int(p8) <= 256:
+            raise ValueError("%s: %s must lie in 0 .. 256, got %r" % (what, name, p8))
+
+
+def check_strong_images(images, what="strong augmentation"):
+    """-> (B, P) of images fp32 or bf16 [B, 3, P, P]; reads no values"""
+    if not torch.is_tensor(images) or images.dtype not in (torch.float32, torch.bfloat16) or images.dim() != 4 \
+            or images.shape[0] < 1 or images.shape[1] != 3 or images.shape[2] != images.shape[3]:
+        raise ValueError("%s: images must be fp32 or bf16 [B, 3, P, P] with B >= 1, got %s"
+                         % (what, (images.dtype, tuple(images.shape)) if torch.is_tensor(images) else type(images)))
+    B, P = int(images.shape[0]), int(images.shape[2])
+    if P < 16 or P % 16 or P > STRONG_MAX_P:
+        raise ValueError("%s: P must be a multiple of 16 in 16 .. %d, got %d" % (what, STRONG_MAX_P, P))
+    if B * 3 * P * P >= 2 ** 31:
+        raise ValueError("%s: B * 3 * P * P must stay below 2**31, got B = %d, P = %d" % (what, B, P))
+    return B, P
+
+
+def strong_draw_reference(B, seed, first_ordinal, jitter_p8=205, blur_p8=128):
+    """CPU specification of hip.strong_draw -> the records int32 [B, 16] of the samples at ordinals first_ordinal + b"""
+    B, first, jitter_p8, blur_p8 = int(B), int(first_ordinal), int(jitter_p8), int(blur_p8)
+    check_strong(16, jitter_p8=jitter_p8, blur_p8=blur_p8)
+    if B < 1 or first < 0 or first + B > 1 << 32:
+        raise ValueError("strong augmentation: B >= 1 and ordinals in [0, 2^32), got B = %d at %d" % (B, first))
+    out = np.zeros((B, RECORD), dtype=np.int32)
+    for b in range(B):
+        t = draws(seed, first + b, STRONG_SLOT + 8)[STRONG_SLOT:]
+        gate = 1 if (t[0] >> 24) < jitter_p8 else 0
+        bits = t[1]
+        blur = (t[6] >> 24) < blur_p8
+        s = t[7] >> 26
+        out[b, :S_W0] = (gate & (bits >> 1), gate & (bits >> 3), gate & (bits >> 4), gate & (bits >> 5), (bits >> 2) & 1,
+                         f32_bits(((t[2] >> 9) - 2 ** 22) / 2.0 ** 17), f32_bits((2 ** 22 + (t[3] >> 9)) / 2.0 ** 23),
+                         f32_bits((2 ** 22 + (t[4] >> 9)) / 2.0 ** 23), ((t[5] * 36) >> 32) - 18, s if blur else -1)
+        out[b, S_W0:S_W0 + 5] = BLUR_WEIGHTS[s] if blur else BLUR_IDENTITY
+    return torch.from_numpy(out)
+
+
+def strong_midpoints(lut):
+    """fp32 [3, 255]: mid[c][k - 1] = fp32((float64(lut[c][k-1]) + float64(lut[c][k])) / 2), k = 1..255"""
+    t = np.asarray(lut, dtype=np.float32).astype(np.float64)
+    return ((t[:, :-1] + t[:, 1:]) / 2).astype(np.float32)
+
+
+def grey_levels(images, mean=HALF, std=HALF):
+    """images fp32 or bf16 [..., 3, H, W] -> int64 of the same shape: per plane c the number of midpoints of lut[c] at or
+    below the value (0 for a NaN).  The midpoints do not decrease, so the count is a search."""
+    check_strong(16, mean, std)
+    mid = strong_midpoints(normalisation_table(mean, std).numpy())
+    x = torch.as_tensor(images).cpu().float().numpy()
+    q = np.empty(x.shape, dtype=np.int64)
+    for c in range(3):
+        assert bool((np.diff(mid[c]) >= 0).all())
+        plane = x[..., c, :, :]
+        q[..., c, :, :] = np.where(np.isnan(plane), 0, np.searchsorted(mid[c], plane, side="right"))
+    return q
+
+
+def strong_record_valid(rec):
+    rec = [int(v) for v in rec]
+    w = rec[S_W0:S_W0 + 5]
+    return (all(v in (0, 1) for v in rec[S_BRIGHT:S_MODE + 1]) and all(bool(np.isfinite(bits_f32(v))) for v in rec[S_BETA:S_ALPHA_S + 1])
+            and all(v >= 0 for v in w) and w[0] + 2 * sum(w[1:]) == BLUR_ONE)
+
+
+def blur_levels(q, w):
+    """integer grey levels [P, P, C] under weights (w0..w4) -> int64 [P, P, C] by the rule above"""
+    q = np.asarray(q).astype(np.int64)
+    P, R = q.shape[0], BLUR_RADIUS
+    w = [int(v) for v in w]
+    pad = np.pad(q, ((R, R), (R, R), (0, 0)), mode="reflect")                      # numpy's "reflect" does not repeat the edge
+    h = sum(w[abs(d)] * pad[:, R + d:R + d + P] for d in range(-R, R + 1))         # [P + 8, P, C]: h at the reflected rows
+    v = sum(w[abs(d)] * h[R + d:R + d + P] for d in range(-R, R + 1))
+    assert int(v.max()) <= 255 << 24
+    return (v + (1 << 23)) >> 24
+
+
+def strong_apply_reference(records, images, mean=HALF, std=HALF, reverse_channels=False):
+    """CPU specification of hip.strong_apply.  records int32 [B, 16], images fp32 or bf16 [B, 3, P, P] -> images of the same
+    shape and dtype: grey levels, jitter, blur, table, per sample under its record; NaN for an invalid record."""
+    images = torch.as_tensor(images).cpu()
+    B, P = check_strong_images(images)
+    check_strong(P, mean, std)
+    records = torch.as_tensor(records).cpu()
+    if records.dtype != torch.int32 or tuple(records.shape) != (B, RECORD):
+        raise ValueError("strong augmentation: records must be int32 [%d, 16], got %s %s" % (B, records.dtype, tuple(records.shape)))
+    lut = normalisation_table(mean, std)
+    q = grey_levels(images, mean, std)                                             # [B, 3, P, P], planes
+    out = torch.empty(B, 3, P, P, dtype=images.dtype)
+    for b in range(B):
+        rec = records[b].tolist()
+        if not strong_record_valid(rec):
+            out[b] = float("nan")
+            continue
+        rgb = np.moveaxis(q[b][::-1] if reverse_channels else q[b], 0, -1)         # [P, P, 3], true colours
+        train_rec = [0] * RECORD
+        for k_train, k in ((R_BRIGHT, S_BRIGHT), (R_CONTRAST, S_CONTRAST), (R_SAT, S_SAT), (R_HUE, S_HUE), (R_MODE, S_MODE),
+                           (R_BETA, S_BETA), (R_ALPHA_C, S_ALPHA_C), (R_ALPHA_S, S_ALPHA_S), (R_DELTA, S_DELTA)):
+            train_rec[k_train] = rec[k]
+        train_rec[R_DELTA] %= 180
+        qq = blur_levels(photometric(rgb, train_rec), rec[S_W0:S_W0 + 5])
+        planes = torch.from_numpy(np.ascontiguousarray(np.moveaxis(qq, -1, 0)))
+        if reverse_channels:
+            planes = planes.flip(0)
+        out[b] = torch.stack([lut[c][planes[c]] for c in range(3)]).to(images.dtype)
+    return out
+
+
+class StrongAugment:
+    def __init__(self, P, mean=HALF, std=HALF, seed=1, device="cpu", jitter_p8=205, blur_p8=128, reverse_channels=False):
+        """device "cpu" runs the specification of this module, any other device the kernels of csrc/strong.hip"""
+        self.P = int(P)
+        check_strong(self.P, mean, std, jitter_p8, blur_p8, "StrongAugment")
+        self.mean, self.std = tuple(float(x) for x in mean), tuple(float(x) for x in std)
+        self.seed, self.device = int(seed) & _M64, torch.device(device)
+        self.jitter_p8, self.blur_p8, self.reverse_channels = int(jitter_p8), int(blur_p8), bool(reverse_channels)
+
+    def draw(self, B, first_ordinal):
+        """-> int32 [B, 16] on the augmentation's device"""
+        if self.device.type == "cpu":
+            return strong_draw_reference(B, self.seed, first_ordinal, self.jitter_p8, self.blur_p8)
+        from . import hip
+        return hip.strong_draw(B, self.seed, first_ordinal, self.jitter_p8, self.blur_p8, device=self.device)
+
+    def apply(self, records, images, out=None):
+        """the caller's records -> images; out: a tensor to write into on a GPU device, which shares no byte with `images`"""
+        B, P = check_strong_images(images, "StrongAugment")
+        if P != self.P:
+            raise ValueError("StrongAugment: built for P = %d, got images of %s" % (self.P, tuple(images.shape)))
+        images = images.to(self.device)
+        if self.device.type == "cpu":
+            return strong_apply_reference(records, images, self.mean, self.std, self.reverse_channels)
+        from . import hip
+        return hip.strong_apply(records.to(self.device).contiguous(), images.contiguous(), self.mean, self.std,
+                                self.reverse_channels, out=out)
+
+    def __call__(self, images, first_ordinal):
+        return self.apply(self.draw(images.shape[0], first_ordinal), images)

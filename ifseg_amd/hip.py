@@ -1757,6 +1757,66 @@ def mix_apply(records, src_images, src_target, dst_images, dst_target, nseg, seg
     return oi, ot, ow
 
 
+# --------------------------------------------------------------------------- strong augmentation of a mixed batch
+STRONG_MAX_P = 4096          # == SG_MAX_P (csrc/strong.hip)
+
+
+def strong_blur_table():
+    """the library's copy of `augment.BLUR_WEIGHTS`, int32 [64, 5] on the host; touches no device"""
+    buf = (c_int * 320)()
+    _check(lib().ifseg_strong_blur_table(buf), "strong_blur_table")
+    return torch.tensor(list(buf), dtype=torch.int32).reshape(64, 5)
+
+
+def strong_draw(B, seed, first_ordinal, jitter_p8=205, blur_p8=128, device=None, out=None):
+    """records int32 [B, 16] of the strong augmentation for the samples at ordinals first_ordinal + b, one launch
+    (csrc/strong.hip; `augment.strong_draw_reference` is the specification and states the rule).  jitter_p8 / blur_p8: the
+    two gates in 256ths, 0 never fires and 256 always does."""
+    B, first = int(B), int(first_ordinal)
+    assert B >= 1 and 0 <= first and first + B <= 2 ** 32, (first, B)
+    assert isinstance(jitter_p8, int) and isinstance(blur_p8, int) and 0 <= jitter_p8 <= 256 and 0 <= blur_p8 <= 256, (jitter_p8, blur_p8)
+    if out is None:
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        out = torch.empty(B, 16, dtype=torch.int32, device=dev)
+    else:
+        assert out.is_cuda and out.dtype == torch.int32 and tuple(out.shape) == (B, 16) and out.is_contiguous() \
+            and (device is None or out.device == torch.device(device)), (out.dtype, tuple(out.shape), out.stride(), out.device)
+    with torch.cuda.device(out.device):
+        _check(lib().ifseg_strong_draw(c_int(B), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), c_ll(first), c_int(jitter_p8),
+                                       c_int(blur_p8), _ptr(out), _stream()), "strong_draw")
+    return out
+
+
+def strong_apply(records, images, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), reverse_channels=False, out=None, lut=None):
+    """colour jitter and Gaussian blur of images [B, 3, P, P] (fp32 or bf16, the values of a normalised batch) under the
+    given records, one launch (csrc/strong.hip; `augment.strong_apply_reference` is the specification): grey levels back
+    from the values, the photometric chain, the 9-tap blur, the table -> images of the same shape and dtype.  An invalid
+    record gives NaN for its sample.  out: a tensor to write into, sharing no byte with the images (the blur reads
+    neighbours).  lut: the fp32 [3, 256] table on the device when the caller holds one, else cached per (mean, std, device)."""
+    assert images.is_cuda and images.dtype in (torch.float32, torch.bfloat16) and images.dim() == 4 and images.shape[1] == 3 \
+        and images.shape[2] == images.shape[3] and images.is_contiguous() and images.data_ptr() % 16 == 0, \
+        (images.device, images.dtype, tuple(images.shape), images.stride())
+    B, P, dev = images.shape[0], images.shape[2], images.device
+    assert B >= 1 and P >= 16 and P % 16 == 0 and P <= STRONG_MAX_P and B * 3 * P * P < 2 ** 31, (B, P)
+    assert records.is_cuda and records.device == dev and records.dtype == torch.int32 and tuple(records.shape) == (B, 16) \
+        and records.is_contiguous(), (records.device, records.dtype, tuple(records.shape))
+    assert len(tuple(std)) == 3 and all(float(s) > 0 for s in std), "strong_apply: std must be > 0 (the table must increase): %r" % (std,)
+    if lut is None:
+        lut = _image_lut(mean, std, dev)
+    assert lut.device == dev and lut.dtype == torch.float32 and tuple(lut.shape) == (3, 256) and lut.is_contiguous(), \
+        (lut.device, lut.dtype, tuple(lut.shape))
+    if out is None:
+        out = torch.empty_like(images)
+    else:
+        assert out.dtype == images.dtype and out.shape == images.shape and out.is_contiguous() and out.device == dev \
+            and out.data_ptr() % 16 == 0, (out.dtype, tuple(out.shape), out.stride(), out.device)
+        for t in (images, records, lut):
+            assert not _overlap(out, t), "strong_apply: out shares memory with the images, the records or the table (no in-place form)"
+    _check(lib().ifseg_strong_apply(_ptr(records), _ptr(images), c_int(B), c_int(P), c_int(images.element_size()), _ptr(lut),
+                                    c_int(1 if reverse_channels else 0), _ptr(out), _stream()), "strong_apply")
+    return out
+
+
 def dropout(x, resid, out, p, seed, drop_path_scale=None, rows_per_batch=None):
     """x / resid / out: [rows, C] or [B, rpb, C] bf16 views (last dim contiguous)"""
     C = x.shape[-1]

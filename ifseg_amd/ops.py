@@ -33,7 +33,8 @@ have no backward; `train_load`
 (csrc/trainload.hip: raw images and label maps of any sizes to a training batch under given records, the reference's training
 transform) has integer inputs and no backward either, and neither have `mix_draw` / `mix_apply` (csrc/mix.hip: ClassMix /
 CutMix of a labelled batch into a pseudo-labelled one -- the choice of classes or of a box, and the paste of images, targets
-and weight planes, which copies bits).
+and weight planes, which copies bits) and `strong_draw` / `strong_apply` (csrc/strong.hip: colour jitter and Gaussian blur of a
+mixed batch's images, integer between input and output).
 """
 from typing import Optional, Sequence, Tuple
 
@@ -1430,3 +1431,62 @@ def _(records, src_images, src_target, src_weight, dst_images, dst_target, dst_w
     weighted = src_weight is not None or dst_weight is not None
     return (dst_images.new_empty((B, 3, P, P)), dst_target.new_empty((B, P * P + 1)),
             records.new_empty((B, P * P) if weighted else (0,), dtype=torch.uint8))
+
+
+# ----------------------------------------------------------------------------------------------- strong_draw / strong_apply
+def _strong_draw_check(B, first_ordinal, jitter_p8, blur_p8):
+    from .augment import check_strong
+    op = "ifseg::strong_draw"
+    check_strong(16, jitter_p8=jitter_p8, blur_p8=blur_p8, what=op)
+    if B < 1 or first_ordinal < 0 or first_ordinal + B > 2 ** 32:
+        raise ValueError("%s: B >= 1 and ordinals in [0, 2**32), got %d .. %d" % (op, first_ordinal, first_ordinal + B - 1))
+    return B
+
+
+@custom_op("ifseg::strong_draw", mutates_args=(), device_types="cuda")
+def strong_draw(B: int, seed: int, first_ordinal: int, jitter_p8: int, blur_p8: int, device: torch.device) -> torch.Tensor:
+    """the records int32 [B, 16] of the strong augmentation (csrc/strong.hip; `augment.strong_draw_reference` is the
+    specification): a pure function of (seed, first_ordinal + b) and the two gates.  No tensor goes in: `device` says where
+    the records are written.  Not differentiable."""
+    _strong_draw_check(B, first_ordinal, jitter_p8, blur_p8)
+    prev = hip.set_stream(torch.cuda.current_stream(device).cuda_stream)
+    try:
+        return hip.strong_draw(B, seed, first_ordinal, jitter_p8, blur_p8, device=device)
+    finally:
+        hip.set_stream(prev)
+
+
+@strong_draw.register_fake
+def _(B, seed, first_ordinal, jitter_p8, blur_p8, device):
+    B = _strong_draw_check(B, first_ordinal, jitter_p8, blur_p8)
+    return torch.empty((B, 16), dtype=torch.int32, device=device)
+
+
+def _strong_apply_check(records, images, mean, std):
+    from .augment import check_strong, check_strong_images
+    op = "ifseg::strong_apply"
+    B, P = check_strong_images(images, op)
+    check_strong(P, mean, std, what=op)
+    if records.dtype != torch.int32 or tuple(records.shape) != (B, 16):
+        raise ValueError("%s: records must be int32 [%d, 16], got %s %s" % (op, B, records.dtype, tuple(records.shape)))
+    return B, P
+
+
+@custom_op("ifseg::strong_apply", mutates_args=(), device_types="cuda")
+def strong_apply(records: torch.Tensor, images: torch.Tensor, mean: Sequence[float], std: Sequence[float],
+                 reverse_channels: bool) -> torch.Tensor:
+    """colour jitter and Gaussian blur of images [B, 3, P, P] (fp32 or bf16) under the given records (csrc/strong.hip;
+    `augment.strong_apply_reference` is the specification) -> images of the same shape and dtype.  Integer between the
+    input and the output: not differentiable."""
+    _strong_apply_check(records, images, mean, std)
+    prev = _stream_scope(images)
+    try:
+        return hip.strong_apply(records.contiguous(), images.contiguous(), mean, std, reverse_channels)
+    finally:
+        hip.set_stream(prev)
+
+
+@strong_apply.register_fake
+def _(records, images, mean, std, reverse_channels):
+    B, P = _strong_apply_check(records, images, mean, std)
+    return images.new_empty((B, 3, P, P))

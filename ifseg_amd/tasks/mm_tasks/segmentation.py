@@ -447,14 +447,36 @@ class SegmentationTask(TaskBase):
             sample["target_weight"] = wgt
         return sample
 
-    def dacs_sample(self, model, images, labels, unlabeled, first_ordinal, trainer=None, mask="class", **kw):
+    def build_strong_augment(self, **kw):
+        """The strong augmentation of a mixed batch (ifseg_amd/augment.py `StrongAugment`: colour jitter, then Gaussian blur)
+        with the train transform's patch size, normalisation, channel order, seed and device; on a GPU device it runs
+        csrc/strong.hip.  kw: `jitter_p8`, `blur_p8`.  One per key, kept."""
+        from ...augment import StrongAugment
+        tf = getattr(self, "train_transform", None) or self.build_train_transform()
+        augs = self.__dict__.setdefault("_strong_augments", {})
+        key = (tf.P, tf.mean, tf.std, tf.reverse_channels, tf.seed, tf.device, tuple(sorted(kw.items())))
+        if key not in augs:
+            augs[key] = StrongAugment(tf.P, tf.mean, tf.std, seed=tf.seed, device=tf.device, reverse_channels=tf.reverse_channels, **kw)
+        return augs[key]
+
+    def strong_augment(self, sample, first_ordinal, **kw):
+        """A batch in `train_sample`'s layout -> the same batch with `patch_images` jittered and blurred
+        (`augment.StrongAugment` states the rule; a pure function of (seed, first_ordinal + b), on slots of the stream that
+        neither the transform nor the mix draws from).  Target, weight plane and prompt are the sample's own tensors."""
+        aug = self.build_strong_augment(**kw)
+        out = dict(sample)
+        out["net_input"] = dict(sample["net_input"], patch_images=aug(sample["net_input"]["patch_images"], first_ordinal))
+        return out
+
+    def dacs_sample(self, model, images, labels, unlabeled, first_ordinal, trainer=None, mask="class", strong=False, **kw):
         """One batch of cross-domain mixed self-training (DACS, Tranheden et al. 2021; ClassMix / CutMix): the labelled batch
         `train_sample(images, labels, first_ordinal)` pasted by `mix_samples(..., first_ordinal)` over the pseudo-labelled
         batch `self_train_sample(model, unlabeled, first_ordinal + 2**31, trainer=trainer, confidence_weight=True, **kw)`.
         The unlabelled samples take their ordinals from the upper half of the ordinal range, so the two transforms draw
         independently: first_ordinal + B <= 2**31, else ValueError.  Pasted labelled pixels weigh 255, the rest the teacher's
-        confidence; the criterion's default `weight_norm="weights"` is scale-free.  DACS applies its colour jitter after the
-        mix; here each half keeps its own transform's jitter."""
+        confidence; the criterion's default `weight_norm="weights"` is scale-free.  DACS applies a colour jitter and a
+        Gaussian blur after the mix: `strong=True` sends the mixed images through `strong_augment(sample, first_ordinal)`;
+        by default each half keeps its own transform's jitter and nothing more."""
         images = [images] if torch.is_tensor(images) else list(images)
         first = int(first_ordinal)
         if first < 0 or first + len(images) > 2 ** 31:
@@ -462,7 +484,8 @@ class SegmentationTask(TaskBase):
                              "first_ordinal + 2**31), got %d + %d" % (first, len(images)))
         source = self.train_sample(images, labels, first)
         target = self.self_train_sample(model, unlabeled, first + 2 ** 31, trainer=trainer, confidence_weight=True, **kw)
-        return self.mix_samples(source, target, first, mask=mask)
+        sample = self.mix_samples(source, target, first, mask=mask)
+        return self.strong_augment(sample, first) if strong else sample
 
     def train_step(self, sample, model, criterion, optimizer, update_num, ignore_grad=False, **extra_kwargs):
         """tasks/mm_tasks/segmentation.py:190-222."""

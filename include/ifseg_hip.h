@@ -886,6 +886,36 @@ int ifseg_mix_apply(const int* records, const void* src_images, const long long*
                     long long seg_id_offset, int elem_bytes, void* out_images, long long* out_target, void* out_weight,
                     void* stream);
 
+/* ---- The strong augmentation of a mixed batch: colour jitter, then Gaussian blur, on images [B, 3, P, P] (fp32 or bf16) in
+ * ifseg_train_load's layout (ifseg_amd/augment.py, "the strong augmentation", is the specification, bit for bit;
+ * csrc/strong.hip; DACS' strong_transform behind the mix) ----
+ * The record of a sample, int32 [16]:
+ *   0 brightness on  1 contrast on  2 saturation on  3 hue on  4 mode  5 beta  6 alpha_c  7 alpha_s (fp32 bit patterns)
+ *   8 delta  9 sigma index (-1: blur off)  10..14 blur weights w0..w4, w0 + 2 (w1 + w2 + w3 + w4) = 4096  15 zero
+ * ifseg_strong_blur_table copies the 64 x 5 weight table (sigma = 0.15 + s / 64) to HOST memory out[320]; no device is
+ * touched.  NULL: IFSEG_ERR_BAD_ARG. */
+int ifseg_strong_blur_table(int* out);
+/* ifseg_strong_draw writes the records of the samples at ordinals first_ordinal + b from the transform's stream
+ * t(n, i) = splitmix64(seed + (n << 32) + i) >> 32 on slots 192..199: jitter gate (t192 >> 24) < jitter_p8, bits of t193 in
+ * slot 23's positions (the four "on" bits ANDed with the gate), beta / alpha_c / alpha_s / delta from t194..t197 by the
+ * formulas of slots 24..27, blur gate (t198 >> 24) < blur_p8, sigma index t199 >> 26.  One launch, one thread per sample.
+ * NULL or misaligned records (4 bytes), a gate outside 0..256, ordinals outside [0, 2^32): IFSEG_ERR_BAD_ARG; B < 1:
+ * IFSEG_ERR_BAD_SHAPE. */
+int ifseg_strong_draw(int B, unsigned long long seed, long long first_ordinal, int jitter_p8, int blur_p8, int* records,
+                      void* stream);
+/* ifseg_strong_apply, one launch: per pixel the grey level q = #{k in 1..255 : x >= (lut[c][k-1] + lut[c][k]) / 2} of each
+ * plane (plane c is colour 2 - c under reverse_channels), the photometric chain of ifseg_train_load under the record, the
+ * separable 9-tap blur with the record's weights on a border reflected without repeating the edge,
+ * q'' = (v + 2^23) >> 24, and out = lut[c][q''] in the images' type (elem_bytes 4: fp32, 2: bf16).  lut: fp32 [3, 256] on
+ * the device, increasing per row.  A record is valid iff words 0..4 are 0 or 1, the three floats are finite, every weight is
+ * >= 0 and they sum to 4096 as above; delta is reduced mod 180; an invalid record writes NaN for its sample.  No address
+ * depends on a record.  NULL or misaligned pointers (images and out 16 bytes, records and lut 4), elem_bytes, or any byte
+ * shared between out and images, the records or lut (the blur reads neighbours: there is no in-place form):
+ * IFSEG_ERR_BAD_ARG; B < 1, P not a multiple of 16 in 16..4096, B*3*P*P >= 2^31: IFSEG_ERR_BAD_SHAPE.  Nothing is launched on
+ * a refusal. */
+int ifseg_strong_apply(const int* records, const void* images, int B, int P, int elem_bytes, const float* lut,
+                       int reverse_channels, void* out, void* stream);
+
 /* sum of squares of a bf16 gradient arena -> out_sumsq[0] (device). */
 int ifseg_grad_sumsq_bf16(const void* g, long long n, float* workspace, float* out_sumsq, void* stream);
 /* Fused grad scaling + clip-by-global-norm + Adam with decoupled weight decay over a
