@@ -15,6 +15,10 @@ image sizes).  ``compute_loss_torch`` is kept as the in-framework reference of t
 Opt-in weights (self-training on pseudo-labels): ``SegCriterion(class_weight=, weight_norm=)`` and a sample's
 ``"target_weight"`` (uint8 per pixel) select the weighted instantiation of the same kernel; ``weighted_loss_reference``
 states the rule.  Without them every call is the unweighted one.
+
+Opt-in online hard example mining: ``SegCriterion(ohem_thresh=, ohem_min_kept=)`` builds that plane on the device
+(csrc/ohem.hip: the probability of every pixel's own label, then an exact radix select over the batch);
+``hardness_reference`` and ``ohem_reference`` state the rule.
 """
 from dataclasses import dataclass, field
 from typing import Optional
@@ -132,6 +136,76 @@ def weighted_loss_reference(scores_up, target, seg_id_offset, nseg, class_weight
     return torch.where(Z > 0, num / torch.where(Z > 0, Z, torch.ones_like(Z)), num * 0.0)
 
 
+OHEM_MIN_KEPT = 100000         # mmseg's default
+OHEM_ONE_BITS = 0x3F800000     # the bits of 1.0f: the largest candidate
+
+
+def check_ohem(thresh, min_kept=OHEM_MIN_KEPT):
+    """the sampler's two numbers -> (thresh or None, min_kept).  thresh=None switches the sampler off; with a min_kept of its own
+    that would be mmseg's loss-ranked variant, which is not built: ValueError, as thresh outside [0, 1] and a negative min_kept."""
+    if thresh is None:
+        if min_kept != OHEM_MIN_KEPT:
+            raise ValueError("ohem_thresh=None with ohem_min_kept=%r: mmseg's loss-ranked OHEMPixelSampler (thresh=None) is not "
+                             "built; give ohem_thresh" % (min_kept,))
+        return None, OHEM_MIN_KEPT
+    return hip.check_ohem(thresh, min_kept)
+
+
+def hardness_reference(scores_up, target, seg_id_offset, nseg):
+    """Specification of `hip.seg_hardness` (csrc/ohem.hip), runs on any device.  scores_up fp32 or fp64 [B, H*W (+1), n] (already
+    upsampled), target int64 [B, H*W (+1)] -> [B, H*W] in the dtype of the scores: softmax(scores_up)[y], clamped to <= 1, where
+    the target is a class (seg_id_offset <= t < seg_id_offset + n and not pad / eos: the loss kernel's predicate), -1 elsewhere.
+    A trailing row that scores and target both carry and whose targets are all eos is the eos row and is left out."""
+    n = int(nseg)
+    if scores_up.dim() != 3 or scores_up.shape[2] != n or not scores_up.dtype.is_floating_point:
+        raise ValueError("hardness_reference: scores_up must be floating point [B, H*W, %d], got %s %s"
+                         % (n, scores_up.dtype, tuple(scores_up.shape)))
+    B = scores_up.shape[0]
+    npix = min(scores_up.shape[1], target.shape[1]) if target.dim() == 2 else -1
+    if target.dtype != torch.int64 or target.dim() != 2 or target.shape[0] != B or target.shape[1] - npix not in (0, 1) \
+            or scores_up.shape[1] - npix not in (0, 1):
+        raise ValueError("hardness_reference: target must be int64 [B, H*W (+1)], got %s %s for scores %s"
+                         % (target.dtype, tuple(target.shape), tuple(scores_up.shape)))
+    if target.shape[1] == scores_up.shape[1] and bool((target[:, -1] == EOS).all()):
+        npix -= 1                                   # scores and target both carry the eos row
+    s = scores_up.detach()[:, :npix]
+    if s.dtype not in (torch.float32, torch.float64):
+        s = s.float()
+    tgt = target[:, :npix].to(s.device)
+    valid = (tgt >= seg_id_offset) & (tgt < seg_id_offset + n) & (tgt != PAD) & (tgt != EOS)
+    label = torch.where(valid, tgt - seg_id_offset, torch.zeros_like(tgt))
+    p = torch.softmax(s, dim=-1).gather(2, label.unsqueeze(-1)).squeeze(-1).clamp(max=1.0)
+    return torch.where(valid, p, torch.full_like(p, -1.0))
+
+
+def ohem_reference(hardness, thresh, min_kept, weight=None):
+    """Specification of `hip.ohem_select` (csrc/ohem.hip) -- mmseg's OHEMPixelSampler.sample with `thresh` given, restated from
+    upstream's behaviour (sort, min(batch_kept, numel - 1), max, <) -- runs on any device.  hardness [B, N] (rounded to fp32),
+    weight None or uint8 [B, N] -> (plane uint8 [B, N], info int64 [4]).  Integer from here on: a value is the uint32 bit
+    pattern of its fp32, and an entry is a candidate iff bits <= 0x3F800000 (0 <= v <= 1 with the sign bit clear; -1, -0.0, NaN
+    and anything above 1 are none).  With k = min(min_kept * B, #candidates - 1):
+      kth = the k-th smallest candidate, counted from 0 (0 without a candidate),   tau = max(bits(fp32(thresh)), kth)
+      plane = weight[i] (None: 255) where the entry is a candidate and bits < tau -- strictly, so the entries that tie with the
+      k-th value are dropped -- and 0 elsewhere;   info = [#candidates, #kept, tau, kth]."""
+    thresh, min_kept = hip.check_ohem(thresh, min_kept)
+    if not torch.is_tensor(hardness) or hardness.dim() != 2 or not hardness.dtype.is_floating_point:
+        raise ValueError("ohem_reference: hardness must be a floating-point [B, N] tensor")
+    B, N = hardness.shape
+    if weight is not None and (weight.dtype != torch.uint8 or tuple(weight.shape) != (B, N)):
+        raise ValueError("ohem_reference: weight must be uint8 [%d, %d], got %s %s" % (B, N, weight.dtype, tuple(weight.shape)))
+    dev = hardness.device
+    bits = hardness.detach().to(torch.float32).contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    cand = bits <= OHEM_ONE_BITS
+    tb = int(torch.tensor(thresh, dtype=torch.float32).view(torch.int32))
+    nv = int(cand.sum())
+    kth = int(bits[cand].sort().values[min(min_kept * B, nv - 1)]) if nv else 0
+    tau = max(tb, kth)
+    keep = cand & (bits < tau)
+    full = weight.to(dev) if weight is not None else torch.full((B, N), 255, dtype=torch.uint8, device=dev)
+    plane = torch.where(keep, full, torch.zeros_like(full))
+    return plane, torch.tensor([nv, int(keep.sum()), tau, kth], dtype=torch.int64, device=dev)
+
+
 class _FusedSegLossFn(torch.autograd.Function):
     """loss = mean CE(bilinear_x16(logits[:, :P]), target); backward hands out the gradient the
     forward kernel already produced.  pixel_weight / class_weight / norm_pixels: the weighted kernel
@@ -182,12 +256,20 @@ class SegCriterion(CriterionBase):
                  sample_patch_num=196, constraint_range=None, upscale_lprobs="true", unsupervised_segmentation="true",
                  criterion_update_freq=1, freeze_embedding_iter=-1, full_context_alignment="false",
                  init_seg_with_text="true", resnet_topk=3, resnet_prob_temperature=1.0, resnet_iters=0,
-                 num_seg_tokens=None, seg_id_offset=None, class_weight=None, weight_norm="weights"):
+                 num_seg_tokens=None, seg_id_offset=None, class_weight=None, weight_norm="weights", ohem_thresh=None,
+                 ohem_min_kept=OHEM_MIN_KEPT):
         """Signature of the reference (seg_criterion.py:115-161; fairseq's `build_criterion` fills it from
         SegCriterionConfig by name).  `num_seg_tokens` / `seg_id_offset` stand in for `task.cfg.num_seg_tokens` and
         `task.target_dictionary.index("<seg_0>")` when the criterion is used without a task.  `class_weight` (n numbers >= 0,
         F.cross_entropy's `weight`) and `weight_norm` ("weights" | "pixels": the normaliser of `weighted_loss_reference`) are
-        constructor keywords only as well; a sample that carries `"target_weight"` (uint8 [B, H*W]) is weighted per pixel."""
+        constructor keywords only as well; a sample that carries `"target_weight"` (uint8 [B, H*W]) is weighted per pixel.
+        `ohem_thresh` (0 .. 1) / `ohem_min_kept` (constructor keywords only): mmseg's `OHEMPixelSampler(thresh, min_kept)` on the
+        supervised loss while the model trains -- `ohem_reference` states the rule; the kept pixels carry the sample's
+        `target_weight` (or 255), the dropped ones 0, and the plane goes to the weighted kernel.  weight_norm="weights" is then the
+        mean over the kept pixels, weight_norm="pixels" divides by 255 N_valid (mmseg's `avg_non_ignore=True` under a sampler).
+        `self.ohem_info` holds the last call's int64 [4] on the device: valid pixels, kept pixels, the bits of tau and of the
+        k-th value.  Not built: `ohem_thresh=None` with a min_kept (the loss-ranked sampler), OHEM in the image-free loss and in
+        evaluation."""
         super().__init__(task)
         self.sentence_avg = sentence_avg
         self.eps = label_smoothing
@@ -214,6 +296,8 @@ class SegCriterion(CriterionBase):
             self.class_weight = self.class_weight.float()          # what the kernel reads
         self.norm_pixels = check_weight_norm(weight_norm)
         self.weight_norm = weight_norm
+        self.ohem_thresh, self.ohem_min_kept = check_ohem(ohem_thresh, ohem_min_kept)
+        self.ohem_info = None
         # image-free samples drawn on the device (ifseg_amd/artificial.py).  The trainer sets the seed and, before every
         # micro-batch, the ordinal of its first sample (an int, or a device int64 word inside a captured step); without a
         # trainer the criterion counts the samples it has drawn.
@@ -369,6 +453,8 @@ class SegCriterion(CriterionBase):
                 and self.num_seg <= FUSED_MAX_CLASSES and target.shape[1] == h * w + 1):
             if not hasattr(self, bufs_name):
                 setattr(self, bufs_name, {})
+            if self.ohem_thresh is not None and model.training:
+                pw = self._ohem_plane(pad, target.contiguous(), pw, hp, wp, h, w, bufs_name + "_ohem")
             if pw is None and self.class_weight is None:
                 loss, stats = _FusedSegLossFn.apply(scores_low, pad, target.contiguous(), hp, wp, h, w, self.num_seg,
                                                     self.seg_id_offset, getattr(self, bufs_name), self.eps)
@@ -402,6 +488,9 @@ class SegCriterion(CriterionBase):
         metrics = dict(zip(("area_intersect", "area_pred_label", "area_label", "area_union"),
                            self.compute_metric(s.detach(), t.detach())))
         pw = check_pixel_weight(sample.get("target_weight"), target.shape[0], h * w)
+        if self.ohem_thresh is not None and model.training:
+            hard = hardness_reference(scores[:, :h * w], target, self.seg_id_offset, self.num_seg)
+            pw, self.ohem_info = ohem_reference(hard, self.ohem_thresh, self.ohem_min_kept, pw)
         if pw is None and self.class_weight is None:
             loss = F.cross_entropy(s, t, label_smoothing=self.eps)
         else:
@@ -409,6 +498,24 @@ class SegCriterion(CriterionBase):
                                            self._class_weight_on(scores.device), pw, self.eps, self.weight_norm)
         metrics["nll_loss"] = loss
         return loss, metrics, 1
+
+    def _ohem_plane(self, pad, target, pw, hp, wp, h, w, name):
+        """the sampler's two stages on the device (hip.seg_hardness, hip.ohem_select), no gradient and no read-back -> the
+        weight plane of this call, in buffers kept under `name` and re-allocated only when the shape changes"""
+        B, dev = pad.shape[0], pad.device
+        ob = getattr(self, name, None)
+        key = (B, h * w, dev)
+        if ob is None or ob["key"] != key:
+            ob = {"key": key, "hard": torch.empty(B, h * w, dtype=torch.float32, device=dev),
+                  "plane": torch.empty(B, h * w, dtype=torch.uint8, device=dev),
+                  "info": torch.zeros(4, dtype=torch.int64, device=dev), "work": hip.ohem_workspace(dev)}
+            setattr(self, name, ob)
+        with torch.no_grad():
+            hip.seg_hardness(pad, target, hp, wp, h, w, self.num_seg, self.seg_id_offset, out=ob["hard"])
+            hip.ohem_select(ob["hard"], self.ohem_thresh, self.ohem_min_kept, weight=pw.contiguous() if pw is not None else None,
+                            out=ob["plane"], info=ob["info"], work=ob["work"])
+        self.ohem_info = ob["info"]
+        return ob["plane"]
 
     def _class_weight_on(self, dev):
         """the class weights on `dev` (moved there once), or None"""

@@ -1024,6 +1024,83 @@ def seg_loss_weighted(logits_pad, target, hp, wp, H, W, nseg, seg_id_offset, til
     return loss_out
 
 
+# ---------------------------------------------------------------------- online hard example mining
+OHEM_WORK_WORDS = 3 * 1024 + 16     # == OHEM_WORK_WORDS (csrc/ohem.hip): three histograms of 1024 bins and the state words
+OHEM_MAX_MIN_KEPT = 2 ** 40
+
+
+def seg_hardness(logits_pad, target, hp, wp, H, W, nseg, seg_id_offset, out=None, pad_id=1, eos_id=2):
+    """logits_pad bf16 [B, P+1, ldl], target int64 [B, H*W (+1)] -> fp32 [B, H*W] in one launch (csrc/ohem.hip, the front half of
+    the loss tile kernel): the softmax probability of every pixel's own label under the x16 bilinear upsample, clamped to <= 1,
+    and -1 where the target is no class (`seg_loss`'s predicate).  `criterions.seg_criterion.hardness_reference` is the
+    specification.  out: written in place when given (contiguous)."""
+    assert logits_pad.dtype == torch.bfloat16 and logits_pad.dim() == 3 and logits_pad.stride(2) == 1 \
+        and logits_pad.shape[1] >= hp * wp and logits_pad.stride(1) >= nseg, (logits_pad.dtype, tuple(logits_pad.shape), logits_pad.stride())
+    B, dev = logits_pad.shape[0], logits_pad.device
+    assert target.dtype == torch.int64 and target.dim() == 2 and target.shape[0] == B and target.shape[1] >= H * W \
+        and target.stride(1) == 1 and target.device == dev, (target.dtype, tuple(target.shape), target.stride(), target.device)
+    assert B >= 1 and hp >= 1 and wp >= 1 and H == 16 * hp and W == 16 * wp and 1 <= nseg <= 512, (B, hp, wp, H, W, nseg)
+    if out is None:
+        out = torch.empty(B, H * W, dtype=torch.float32, device=dev)
+    assert out.dtype == torch.float32 and tuple(out.shape) == (B, H * W) and out.is_contiguous() and out.device == dev, \
+        (out.dtype, tuple(out.shape), out.stride(), out.device)
+    assert not _overlap(out, logits_pad) and not _overlap(out, target), "seg_hardness: out overlaps the logits or the target"
+    _check(lib().ifseg_seg_hardness(_ptr(logits_pad), c_int(logits_pad.stride(1)), c_ll(logits_pad.stride(0) if B > 1 else hp * wp * logits_pad.stride(1)),
+                                    _ptr(target), c_ll(target.stride(0) if B > 1 else H * W), c_int(B), c_int(hp), c_int(wp),
+                                    c_int(H), c_int(W), c_int(nseg), c_ll(seg_id_offset), c_ll(pad_id), c_ll(eos_id), _ptr(out),
+                                    c_ll(H * W), _stream()), "seg_hardness")
+    return out
+
+
+def ohem_workspace(device):
+    """the workspace of `ohem_select`: allocated (and zeroed) once, every call leaves it ready for the next"""
+    return torch.zeros(OHEM_WORK_WORDS, dtype=torch.int64, device=device)
+
+
+def check_ohem(thresh, min_kept):
+    """0 <= thresh <= 1 and 0 <= min_kept < 2^40 (ValueError otherwise) -> (float, int); -0.0 becomes 0.0"""
+    if isinstance(thresh, bool) or not isinstance(thresh, (int, float)) or not 0.0 <= thresh <= 1.0:
+        raise ValueError("ohem: thresh must be a number in [0, 1], got %r" % (thresh,))
+    if isinstance(min_kept, bool) or not isinstance(min_kept, int) or not 0 <= min_kept < OHEM_MAX_MIN_KEPT:
+        raise ValueError("ohem: min_kept must be an integer in [0, 2**40), got %r" % (min_kept,))
+    return float(thresh) + 0.0, min_kept
+
+
+def ohem_select(hardness, thresh, min_kept, weight=None, out=None, info=None, work=None):
+    """hardness fp32 [B, N] -> (plane uint8 [B, N], info int64 [4]) in four launches with no read-back (csrc/ohem.hip; an exact
+    radix select over the batch; `criterions.seg_criterion.ohem_reference` is the specification, bit for bit): with
+    k = min(min_kept * B, #candidates - 1) and tau = max(thresh, k-th smallest candidate), a candidate (0 <= v <= 1) strictly
+    below tau gets weight[i] (uint8 [B, N]; None: 255), every other entry 0.  info = #candidates, #kept, the bits of tau and of
+    the k-th value.  out / info: written in place when given; work: `ohem_workspace(device)`, kept by the caller between calls
+    (a fresh one otherwise)."""
+    thresh, min_kept = check_ohem(thresh, min_kept)
+    assert hardness.dtype == torch.float32 and hardness.dim() == 2 and hardness.is_contiguous() and hardness.is_cuda, \
+        (hardness.dtype, tuple(hardness.shape), hardness.stride(), hardness.device)
+    B, N = hardness.shape
+    dev = hardness.device
+    assert B >= 1 and N >= 1 and B < 2 ** 20 and B * N < 2 ** 31, (B, N)
+    if weight is not None:
+        assert weight.dtype == torch.uint8 and tuple(weight.shape) == (B, N) and weight.is_contiguous() and weight.device == dev, \
+            (weight.dtype, tuple(weight.shape), weight.stride(), weight.device)
+    if out is None:
+        out = torch.empty(B, N, dtype=torch.uint8, device=dev)
+    assert out.dtype == torch.uint8 and tuple(out.shape) == (B, N) and out.is_contiguous() and out.device == dev, \
+        (out.dtype, tuple(out.shape), out.stride(), out.device)
+    assert not _overlap(out, hardness) and (weight is None or not _overlap(out, weight)), "ohem_select: out overlaps its inputs"
+    if info is None:
+        info = torch.empty(4, dtype=torch.int64, device=dev)
+    assert info.dtype == torch.int64 and tuple(info.shape) == (4,) and info.is_contiguous() and info.device == dev, \
+        (info.dtype, tuple(info.shape), info.device)
+    if work is None:
+        work = ohem_workspace(dev)
+    assert work.dtype == torch.int64 and tuple(work.shape) == (OHEM_WORK_WORDS,) and work.is_contiguous() and work.device == dev, \
+        (work.dtype, tuple(work.shape), work.device)
+    assert not any(_overlap(a, b) for a, b in ((info, out), (info, hardness), (work, out), (work, hardness), (work, info)))
+    _check(lib().ifseg_ohem_select(_ptr(hardness), c_int(B), c_ll(N), c_float(thresh), c_ll(min_kept), _ptr(weight), _ptr(out),
+                                   _ptr(info), _ptr(work), _stream()), "ohem_select")
+    return out, info
+
+
 # ---------------------------------------------------------------------- eval post-processing
 def rows_to_f32(logits_pad, nseg, rows_per_batch, softmax=False, temperature=1.0):
     """logits_pad bf16 [B, T, ld] -> fp32 [B, rows_per_batch, nseg] (first rows of every sample), optionally softmaxed"""

@@ -17,7 +17,8 @@ is dispatcher-visible too.  No CPU implementation is registered: on a CPU tensor
 The second half of the file puts the training-path kernels there as well (see the comment above `_check_qkv`):
 `attention_bias` (the bias is an ordinary tensor with a gradient), `bias_attention_bi` (bias_attention on the batch-inner
 kernels, with key counts and attention dropout), `seg_loss` (csrc/loss.hip) and `seg_loss_weighted` (the same kernel with a
-weight per pixel and per class; it shares `seg_loss_bwd`), with `*_bwd` ops of their own;
+weight per pixel and per class; it shares `seg_loss_bwd`), with `*_bwd` ops of their own, and `seg_ohem` (csrc/ohem.hip: the
+online-hard-example sampler that makes that weight plane; a constant of the step, no backward);
 `ifseg_amd.modules.MultiheadAttention` composes `linear` and `attention_bias` under the reference module's parameter names.
 `seg_predict` (csrc/predict.hip: label maps at image resolution), `seg_predict_views` (the same from the mean of K views of
 differing grids, mirrored ones included: multi-scale + flip inference), `seg_areas` / `seg_score_views` (label maps counted
@@ -744,6 +745,41 @@ def _slw_backward(ctx, gloss, gstats, gdl, gbad):
 
 
 seg_loss_weighted.register_autograd(_slw_backward, setup_context=_sl_setup)
+
+
+# ----------------------------------------------------------------------------------------------- seg_ohem
+def _seg_ohem_check(logits, target, pixel_weight, hp, wp, H, W, thresh, min_kept):
+    op = "ifseg::seg_ohem"
+    B, nseg, npad = _seg_loss_check(logits, target, hp, wp, H, W)
+    if pixel_weight is not None and (pixel_weight.dtype != torch.uint8 or tuple(pixel_weight.shape) != (B, H * W)):
+        raise ValueError("%s: pixel_weight must be uint8 [B, H * W] = [%d, %d], got %s %s"
+                         % (op, B, H * W, pixel_weight.dtype, tuple(pixel_weight.shape)))
+    hip.check_ohem(thresh, min_kept)
+    return B, nseg, npad
+
+
+@custom_op("ifseg::seg_ohem", mutates_args=(), device_types="cuda")
+def seg_ohem(logits: torch.Tensor, target: torch.Tensor, pixel_weight: Optional[torch.Tensor], hp: int, wp: int, H: int, W: int,
+             seg_id_offset: int, thresh: float, min_kept: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """mmseg's OHEMPixelSampler(thresh, min_kept) for `seg_loss_weighted` (csrc/ohem.hip: hip.seg_hardness, then
+    hip.ohem_select; `criterions.seg_criterion.hardness_reference` / `ohem_reference` are the specifications).  logits and
+    target as `seg_loss`, pixel_weight None or uint8 [B, H*W] -> (weight uint8 [B, H*W]: pixel_weight (None: 255) on the kept
+    pixels, 0 on the others; info int64 [4]: valid pixels, kept pixels, the bits of tau and of the k-th value), fresh tensors.
+    The selection is a constant of the step: not differentiable."""
+    B, nseg, npad = _seg_ohem_check(logits, target, pixel_weight, hp, wp, H, W, thresh, min_kept)
+    prev = _stream_scope(logits)
+    try:
+        lp = logits if logits.stride(2) == 1 else logits.contiguous()
+        hard = hip.seg_hardness(lp, target.contiguous(), hp, wp, H, W, nseg, seg_id_offset)
+        return hip.ohem_select(hard, thresh, min_kept, weight=pixel_weight.contiguous() if pixel_weight is not None else None)
+    finally:
+        hip.set_stream(prev)
+
+
+@seg_ohem.register_fake
+def _(logits, target, pixel_weight, hp, wp, H, W, seg_id_offset, thresh, min_kept):
+    B, nseg, npad = _seg_ohem_check(logits, target, pixel_weight, hp, wp, H, W, thresh, min_kept)
+    return logits.new_empty((B, H * W), dtype=torch.uint8), logits.new_empty((4,), dtype=torch.int64)
 
 
 # ----------------------------------------------------------------------------------------------- seg_predict

@@ -720,7 +720,14 @@ class Trainer:
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                logs = self._step_body([sample], captured=True)
+                # every launch of the step belongs to the capture: a stream handle somebody left pinned (hip.set_stream) would
+                # send the launches outside the engine's forward / backward -- the criterion, clip + Adam -- to that stream,
+                # where they run once, now, and are missing from every replay
+                pinned = hip.set_stream(torch.cuda.current_stream().cuda_stream)
+                try:
+                    logs = self._step_body([sample], captured=True)
+                finally:
+                    hip.set_stream(pinned)
             if eng._pf is not None:
                 # the graph joins the trunk stream itself; its (captured) event must not be waited on by later steps
                 eng._pf = dict(eng._pf, done=None)

@@ -509,6 +509,27 @@ int ifseg_seg_loss_tiles_weighted(const void* logits, int ldl, long long logits_
                                   int norm_pixels, float* tile_partial, float* stats_part, int* bad_label,
                                   float label_smoothing, void* stream);
 
+/* ---- online hard example mining (mmseg's OHEMPixelSampler with `thresh` given) as a producer of the pixel_weight plane above;
+ * csrc/ohem.hip, ifseg_amd.criterions.seg_criterion.hardness_reference / ohem_reference are the specifications ----
+ * ifseg_seg_hardness: the front half of ifseg_seg_loss_tiles (same logits, target, x16 bilinear upsample, same validity
+ * predicate) -> hardness fp32 [B][H*W] (batch stride hardness_bs >= H*W floats): the softmax probability of the pixel's own
+ * label, clamped to <= 1, on a valid pixel, -1 elsewhere.  One launch, no atomics.  NULL / misaligned pointers, strides below a
+ * sample: IFSEG_ERR_BAD_ARG; B, hp, wp < 1, H != 16 hp, W != 16 wp, nseg outside 1..512, ldl < nseg: IFSEG_ERR_BAD_SHAPE. */
+int ifseg_seg_hardness(const void* logits, int ldl, long long logits_bs, const long long* target, long long target_bs, int B,
+                       int hp, int wp, int H, int W, int nseg, long long seg_id_offset, long long pad_id, long long eos_id,
+                       float* hardness, long long hardness_bs, void* stream);
+/* ifseg_ohem_select: hardness fp32 [B][n] (contiguous) -> out uint8 [B][n] and info int64 [4], four launches, nothing read back.
+ * Values are compared as the uint32 bit patterns of their fp32; an entry is a candidate iff bits <= 0x3F800000 (0 <= v <= 1, sign
+ * clear).  k = min(min_kept * B, #candidates - 1), kth = the k-th smallest candidate (from 0) by an exact radix select (three
+ * digits of 10 bits, 64-bit integer counters: bit-reproducible), tau = max(bits(thresh), kth); out = weight[i] (uint8 [B][n],
+ * NULL: 255) where the entry is a candidate below tau (strictly), else 0.  info = #candidates, #kept, tau, kth (0 without a
+ * candidate).  work: uint64 [3 * 1024 + 16], zeroed once by the caller; every call leaves it zeroed where the next one needs it, so
+ * the same sequence replays inside a captured graph.  out must not overlap hardness or weight (the caller's duty).
+ * NULL / misaligned pointers (hardness 4 bytes, info and work 8), thresh outside [0, 1] or NaN, min_kept outside [0, 2^40):
+ * IFSEG_ERR_BAD_ARG; B outside [1, 2^20), n < 1, B*n >= 2^31: IFSEG_ERR_BAD_SHAPE.  Nothing is launched on a refusal. */
+int ifseg_ohem_select(const float* hardness, int B, long long n, float thresh, long long min_kept, const unsigned char* weight,
+                      unsigned char* out, long long* info, unsigned long long* work, void* stream);
+
 /* ---------------------------------------------------- image-free samples */
 /* The artificial image of `--artificial-image-type rand_k-L-R` (data/mm_data/segmentation_dataset.py:303-345) and its collater
  * layout (:85-107), generated on the device (csrc/imfree.hip; ifseg_amd/artificial.py is the bit-exact host specification).
