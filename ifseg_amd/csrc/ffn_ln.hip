@@ -12,13 +12,6 @@
 #include "prof.h"
 #include "../../include/ifseg_hip.h"
 
-namespace {
-__device__ __forceinline__ void unpack8(const uint4& v, float* f) {
-  f[0] = bflo(v.x); f[1] = bfhi(v.x); f[2] = bflo(v.y); f[3] = bfhi(v.y);
-  f[4] = bflo(v.z); f[5] = bfhi(v.z); f[6] = bflo(v.w); f[7] = bfhi(v.w);
-}
-}  // namespace
-
 // ---------------------------------------------------------------------------------------------------------------------
 // The FFN's ffn_layernorm(gelu(fc1)) on the way back WITHOUT a 3072-wide LayerNorm-backward pass
 // (unify_transformer_layer.py:279-283 under autograd).  With z = gamma * xh + beta the input of fc2 (t = z W2^T + b2 its

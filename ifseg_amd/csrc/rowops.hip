@@ -31,16 +31,12 @@ static inline RowMap row_map(int rpb, long long bs, int ld) {
 __device__ __forceinline__ float gelu_f(float x) {
   return 0.5f * x * (1.f + erf_as(x, __expf(-0.5f * x * x)));
 }
-__device__ __forceinline__ float gelu_grad_f(float x) {
-  return 0.5f * (1.f + erff(x * 0.70710678118654752f)) + x * 0.39894228040143268f * __expf(-0.5f * x * x);
-}
-
-__device__ __forceinline__ void unpack8(const uint4& v, float* f) {
-  f[0] = bflo(v.x); f[1] = bfhi(v.x); f[2] = bflo(v.y); f[3] = bfhi(v.y);
-  f[4] = bflo(v.z); f[5] = bfhi(v.z); f[6] = bflo(v.w); f[7] = bfhi(v.w);
-}
-__device__ __forceinline__ uint4 pack8(const float* f) {
-  return make_uint4(pack2bf(f[0], f[1]), pack2bf(f[2], f[3]), pack2bf(f[4], f[5]), pack2bf(f[6], f[7]));
+// f[0..8) += the eight bf16 at p (a residual / dx_add chunk)
+__device__ __forceinline__ void add8(float* f, const bf16_t* p) {
+  float r[8];
+  unpack8(*reinterpret_cast<const uint4*>(p), r);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) f[e] += r[e];
 }
 
 // ---- dropout + DropPath (training-time stochastic regularisers) -------------------------------
@@ -80,6 +76,28 @@ __device__ __forceinline__ void ldp8(const bf16_t* p, int c, int pf32, float* o)
   }
 }
 
+// mean and 1 / sqrt(var + eps) of the row a wave holds in v (NCH chunks per lane), s = the lane's sum of its elements
+template <int NCH>
+__device__ __forceinline__ void row_stats(const float (&v)[NCH][8], float s, int lane, int nch, int C, float eps, float& mu, float& rs) {
+  mu = warp_sum(s) / C;
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < NCH; ++i)
+    if (lane + i * 64 < nch) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { const float d = v[i][e] - mu; q += d * d; }
+    }
+  rs = rsqrtf(warp_sum(q) / C + eps);
+}
+// o = (v - mu) * rs * gamma + beta for chunk c
+__device__ __forceinline__ void ln_affine8(const float* v, float mu, float rs, const bf16_t* gamma, const bf16_t* beta, int c, int pf32, float* o) {
+  float g[8], b[8];
+  ldp8(gamma, c, pf32, g);
+  ldp8(beta, c, pf32, b);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) o[e] = (v[e] - mu) * rs * g[e] + b[e];
+}
+
 // y = [resid +] drop(LN(act(x)) * gamma + beta) ; one wave per row, NCH 8-element chunks per lane
 template <int NCH, bool GELU>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const bf16_t* x, const bf16_t* gamma, const bf16_t* beta,
@@ -109,15 +127,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const bf16_t* x, const bf16
   // gamma == nullptr: the first stage is the identity (y = [resid +] drop(x)), only the second LayerNorm runs
   float mu = 0.f, rs = 1.f;
   if (gamma) {
-    mu = warp_sum(s) / C;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i)
-      if (lane + i * 64 < nch) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { const float d = v[i][e] - mu; q += d * d; }
-      }
-    rs = rsqrtf(warp_sum(q) / C + eps);
+    row_stats<NCH>(v, s, lane, nch, C, eps, mu, rs);
     if (lane == 0 && mean) { mean[row] = mu; rstd[row] = rs; }
   }
   bf16_t* yp = y + my.off(row);
@@ -128,22 +138,13 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const bf16_t* x, const bf16
     if (c < nch) {
       float o[8];
       if (gamma) {
-        float g[8], b[8];
-        ldp8(gamma, c, pf32, g);
-        ldp8(beta, c, pf32, b);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (v[i][e] - mu) * rs * g[e] + b[e];
+        ln_affine8(v[i], mu, rs, gamma, beta, c, pf32, o);
       } else {
 #pragma unroll
         for (int e = 0; e < 8; ++e) o[e] = v[i][e];
       }
       if (drop.on) drop8(o, drop, (long long)row * nch + c, row);
-      if (rp) {
-        float r[8];
-        unpack8(*reinterpret_cast<const uint4*>(rp + c * 8), r);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] += r[e];
-      }
+      if (rp) add8(o, rp + c * 8);
       const uint4 packed = pack8(o);
       *reinterpret_cast<uint4*>(yp + c * 8) = packed;
       if (y2) unpack8(packed, v[i]);        // the second LayerNorm sees y exactly as it is stored (bf16)
@@ -159,27 +160,42 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const bf16_t* x, const bf16
 #pragma unroll
         for (int e = 0; e < 8; ++e) s2 += v[i][e];
       }
-    const float mu2 = warp_sum(s2) / C;
-    float q2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i)
-      if (lane + i * 64 < nch) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { const float d = v[i][e] - mu2; q2 += d * d; }
-      }
-    const float rs2 = rsqrtf(warp_sum(q2) / C + eps);
+    float mu2, rs2;
+    row_stats<NCH>(v, s2, lane, nch, C, eps, mu2, rs2);
     if (lane == 0 && mean2) { mean2[row] = mu2; rstd2[row] = rs2; }
     bf16_t* y2p = y2 + my2.off(row);
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
       const int c = lane + i * 64;
       if (c < nch) {
-        float g[8], b[8], o[8];
-        ldp8(gamma2, c, pf32, g);
-        ldp8(beta2, c, pf32, b);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (v[i][e] - mu2) * rs2 * g[e] + b[e];
+        float o[8];
+        ln_affine8(v[i], mu2, rs2, gamma2, beta2, c, pf32, o);
         *reinterpret_cast<uint4*>(y2p + c * 8) = pack8(o);
+      }
+    }
+  }
+}
+
+// dgamma / dbeta partial sums of a block with one wave per row: the four waves' per-column sums, added chunk by chunk
+// through LDS (red: 4 * (64 * 8 + 8) floats), go to row blockIdx.x of the part buffers
+template <int NCH>
+__device__ __forceinline__ void store_part_sums4(float* red, const float (&dg)[NCH][8], const float (&db)[NCH][8], float* dgamma_part,
+                                                 float* dbeta_part, int C, int lane, int wave) {
+  float (*r4)[64 * 8 + 8] = reinterpret_cast<float (*)[64 * 8 + 8]>(red);
+#pragma unroll
+  for (int i = 0; i < NCH; ++i) {
+#pragma unroll
+    for (int pass = 0; pass < 2; ++pass) {
+      __syncthreads();
+#pragma unroll
+      for (int e = 0; e < 8; ++e) r4[wave][lane * 8 + e] = pass ? db[i][e] : dg[i][e];
+      __syncthreads();
+      for (int t = threadIdx.x; t < 512; t += 256) {
+        const int c = (t >> 3) + i * 64;
+        if (c < (C >> 3)) {
+          const float sum = r4[0][t] + r4[1][t] + r4[2][t] + r4[3][t];
+          (pass ? dbeta_part : dgamma_part)[(long long)blockIdx.x * C + c * 8 + (t & 7)] = sum;
+        }
       }
     }
   }
@@ -276,12 +292,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* dy, const bf1
           const float xh = xr[i][e], dact = GELU ? da[i][e] : 1.f;
           o[e] = rs * (gv[i][e] - s1 - xh * s2) * dact;
         }
-        if (ap) {
-          float r[8];
-          unpack8(*reinterpret_cast<const uint4*>(ap + c * 8), r);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] += r[e];
-        }
+        if (ap) add8(o, ap + c * 8);
         *reinterpret_cast<uint4*>(dxp + c * 8) = pack8(o);
       }
     }
@@ -302,34 +313,17 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* dy, const bf1
       }
     }
   } else {
-    // cross-wave reduction of the four rows' partials (chunk by chunk through LDS)
-    float (*r4)[64 * 8 + 8] = reinterpret_cast<float (*)[64 * 8 + 8]>(red);
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-#pragma unroll
-      for (int pass = 0; pass < 2; ++pass) {
-        __syncthreads();
-#pragma unroll
-        for (int e = 0; e < 8; ++e) r4[wave][lane * 8 + e] = pass ? db[i][e] : dg[i][e];
-        __syncthreads();
-        for (int t = threadIdx.x; t < 512; t += 256) {
-          const int c = (t >> 3) + i * 64;
-          if (c < nch) {
-            const float sum = r4[0][t] + r4[1][t] + r4[2][t] + r4[3][t];
-            (pass ? dbeta_part : dgamma_part)[(long long)blockIdx.x * C + c * 8 + (t & 7)] = sum;
-          }
-        }
-      }
-    }
+    store_part_sums4<NCH>(red, dg, db, dgamma_part, dbeta_part, C, lane, wave);
   }
 }
 
 // ln_bwd, narrow rows (C <= 1024, one wave per row, no GELU), register-lean (round 5): the row's dy / x stay PACKED (bf16)
 // across the two row reductions and the second pass re-derives g and xhat from them with the first pass's statements -- g by an
 // explicitly rounded multiply -- instead of holding two fp32 copies of the row; no software prefetch.  118 VGPRs instead of
-// 146 (4 waves per SIMD), 11-13 % faster alone (tools/ln_bench.py).  Against ln_bwd_kernel<2, false, 1> the per-block partial
-// sums are bit-identical and dx differs in ~1e-5 of its elements by one bf16 ulp (tools/ln_hash.py: the compiler fuses the
-// row sums' multiply-adds differently in the two kernels).  DX2: the second output of ifseg_ln_bwd_drop,
+// 146 (4 waves per SIMD), 11-13 % faster alone (tools/ln_bench.py).  Against ln_bwd_kernel<2, false, 1> (which it replaced:
+// no longer instantiated) the per-block partial sums were bit-identical and dx differed in ~1e-5 of its elements by one bf16
+// ulp (the bit-compare tool, now tools/rowops_bits.py: the compiler fuses the row sums' multiply-adds differently in the two
+// kernels).  DX2: the second output of ifseg_ln_bwd_drop,
 // dx2 = drop2(dx as stored in bf16) -- the same instantiation as the plain call, so the pair stays bit-identical to
 // ifseg_ln_bwd followed by ifseg_dropout.  (ln_bwd_kernel remains for the GELU / wide rows.)
 template <int NCH, bool DX2>
@@ -403,12 +397,7 @@ __global__ __launch_bounds__(256) void ln_bwd_lean_kernel(const bf16_t* dy, cons
           const float g = __fmul_rn(d[e], gam[i][e]);           // (rounded as the first pass's g was)
           o[e] = rs * (g - s1 - xh * s2) * 1.f;
         }
-        if (ap) {
-          float r[8];
-          unpack8(*reinterpret_cast<const uint4*>(ap + c * 8), r);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] += r[e];
-        }
+        if (ap) add8(o, ap + c * 8);
         const uint4 pk = pack8(o);
         *reinterpret_cast<uint4*>(dxp + c * 8) = pk;
         if (DX2) {
@@ -420,24 +409,20 @@ __global__ __launch_bounds__(256) void ln_bwd_lean_kernel(const bf16_t* dy, cons
       }
     }
   }
-  if (!dgamma_part) return;
-  float (*r4)[64 * 8 + 8] = reinterpret_cast<float (*)[64 * 8 + 8]>(red);
-#pragma unroll
-  for (int i = 0; i < NCH; ++i) {
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-      __syncthreads();
-#pragma unroll
-      for (int e = 0; e < 8; ++e) r4[wave][lane * 8 + e] = pass ? db[i][e] : dg[i][e];
-      __syncthreads();
-      for (int t = threadIdx.x; t < 512; t += 256) {
-        const int c = (t >> 3) + i * 64;
-        if (c < nch) {
-          const float sum = r4[0][t] + r4[1][t] + r4[2][t] + r4[3][t];
-          (pass ? dbeta_part : dgamma_part)[(long long)blockIdx.x * C + c * 8 + (t & 7)] = sum;
-        }
-      }
-    }
+  if (dgamma_part) store_part_sums4<NCH>(red, dg, db, dgamma_part, dbeta_part, C, lane, wave);
+}
+
+// out[gid] = [out[gid] +] t, out bf16 or fp32: the end of every part reduction
+template <bool OUT_BF16>
+__device__ __forceinline__ void reduce_store(void* out, long long gid, float t, int accumulate) {
+  if (OUT_BF16) {
+    bf16_t* op = reinterpret_cast<bf16_t*>(out) + gid;
+    if (accumulate) t += bf2f(*op);
+    *op = f2bf(t);
+  } else {
+    float* op = reinterpret_cast<float*>(out) + gid;
+    if (accumulate) t += *op;
+    *op = t;
   }
 }
 
@@ -451,26 +436,20 @@ __global__ void reduce_parts_kernel(const float* in, void* out, int outer, int p
   const float* p = in + o * parts * n + i;
   float s = 0.f;
   for (int k = 0; k < parts; ++k) s += p[(long long)k * n];
-  s *= scale;
-  if (OUT_BF16) {
-    bf16_t* op = reinterpret_cast<bf16_t*>(out) + gid;
-    if (accumulate) s += bf2f(*op);
-    *op = f2bf(s);
-  } else {
-    float* op = reinterpret_cast<float*>(out) + gid;
-    if (accumulate) s += *op;
-    *op = s;
-  }
+  reduce_store<OUT_BF16>(out, gid, s * scale, accumulate);
 }
 
-// same reduction for many parts / few columns: 32 columns x 8 part-groups per block
-template <bool OUT_BF16>
-__global__ __launch_bounds__(256) void reduce_parts2d_kernel(const float* in, void* out, int outer, int parts,
-                                                             long long n, int accumulate, float scale) {
+// same reduction for many parts / few columns: 32 columns x 8 part-groups per block.  Block `blk` of a reduction sums its
+// columns of in[o][.][i] through LDS; the threads that then hold a sum t for out[gid] call store(gid, t).  (in, parts and
+// scale are references so that the multi kernel reads those fields of its task where the written-out kernel read them: by
+// value its scalar loads were grouped differently, with n by reference too the 2d kernel lost a wait -- profiles/rowops_fold_isa.txt.)
+template <typename Store>
+__device__ __forceinline__ void reduce_cols32(const float* const& in, const int& parts, long long n, long long blk,
+                                              const float& scale, Store store) {
   __shared__ float red[8][33];
   const int c = threadIdx.x & 31, g = threadIdx.x >> 5;
   const long long nchunk = (n + 31) / 32;
-  const long long o = blockIdx.x / nchunk, i = (blockIdx.x % nchunk) * 32 + c;
+  const long long o = blk / nchunk, i = (blk % nchunk) * 32 + c;
   float s = 0.f;
   if (i < n) {
     const float* p = in + o * parts * n + i;
@@ -483,18 +462,13 @@ __global__ __launch_bounds__(256) void reduce_parts2d_kernel(const float* in, vo
     float t = 0.f;
 #pragma unroll
     for (int k = 0; k < 8; ++k) t += red[k][c];
-    t *= scale;
-    const long long gid = o * n + i;
-    if (OUT_BF16) {
-      bf16_t* op = reinterpret_cast<bf16_t*>(out) + gid;
-      if (accumulate) t += bf2f(*op);
-      *op = f2bf(t);
-    } else {
-      float* op = reinterpret_cast<float*>(out) + gid;
-      if (accumulate) t += *op;
-      *op = t;
-    }
+    store(o * n + i, t * scale);
   }
+}
+template <bool OUT_BF16>
+__global__ __launch_bounds__(256) void reduce_parts2d_kernel(const float* in, void* out, int outer, int parts,
+                                                             long long n, int accumulate, float scale) {
+  reduce_cols32(in, parts, n, blockIdx.x, scale, [&](long long gid, float t) { reduce_store<OUT_BF16>(out, gid, t, accumulate); });
 }
 
 // the same for MANY parts and few columns (the loss kernel's 8192 per-tile statistics rows of 2 + 3 nseg floats): one block per
@@ -516,56 +490,19 @@ __global__ __launch_bounds__(256) void reduce_parts_tall_kernel(const float* in,
     if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
     __syncthreads();
   }
-  if (threadIdx.x == 0) {
-    float t = red[0] * scale;
-    const long long gid = o * n + i;
-    if (OUT_BF16) {
-      bf16_t* op = reinterpret_cast<bf16_t*>(out) + gid;
-      if (accumulate) t += bf2f(*op);
-      *op = f2bf(t);
-    } else {
-      float* op = reinterpret_cast<float*>(out) + gid;
-      if (accumulate) t += *op;
-      *op = t;
-    }
-  }
+  if (threadIdx.x == 0) reduce_store<OUT_BF16>(out, o * n + i, red[0] * scale, accumulate);
 }
 
 // several reductions in one launch: block ranges by task
 struct ReduceTasks { ifseg_reduce_task t[16]; int start[17]; int n; };
 __global__ __launch_bounds__(256) void reduce_parts_multi_kernel(ReduceTasks ts) {
-  __shared__ float red[8][33];
   int k = 0;
   for (int i = 1; i < ts.n; ++i) k = ((int)blockIdx.x >= ts.start[i]) ? i : k;
   const ifseg_reduce_task& T = ts.t[k];
-  const int blk = blockIdx.x - ts.start[k];
-  const int c = threadIdx.x & 31, g = threadIdx.x >> 5;
-  const long long nchunk = (T.n + 31) / 32;
-  const long long o = blk / nchunk, i = (blk % nchunk) * 32 + c;
-  float s = 0.f;
-  if (i < T.n) {
-    const float* p = T.in + o * T.parts * T.n + i;
-#pragma unroll 8
-    for (int q = g; q < T.parts; q += 8) s += p[(long long)q * T.n];
-  }
-  red[g][c] = s;
-  __syncthreads();
-  if (g == 0 && i < T.n) {
-    float t = 0.f;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) t += red[q][c];
-    t *= T.scale;
-    const long long gid = o * T.n + i;
-    if (T.out_bf16) {
-      bf16_t* op = reinterpret_cast<bf16_t*>(T.out) + gid;
-      if (T.accumulate) t += bf2f(*op);
-      *op = f2bf(t);
-    } else {
-      float* op = reinterpret_cast<float*>(T.out) + gid;
-      if (T.accumulate) t += *op;
-      *op = t;
-    }
-  }
+  reduce_cols32(T.in, T.parts, T.n, (int)blockIdx.x - ts.start[k], T.scale, [&](long long gid, float t) {
+    if (T.out_bf16) reduce_store<true>(T.out, gid, t, T.accumulate);
+    else reduce_store<false>(T.out, gid, t, T.accumulate);
+  });
 }
 
 // column sums of a bf16 matrix: part[blockIdx.y][n] = sum over the block's row slab
@@ -645,23 +582,12 @@ __global__ void nchw_to_nhwc_kernel(const TIN* in, bf16_t* out, int B, int Cc, i
   out[gid] = f2bf(v);
 }
 
-template <int NCH>
-int launch_ln_fwd(int gelu_flags, dim3 g, hipStream_t s, const bf16_t* x, const bf16_t* gamma, const bf16_t* beta,
-                  const bf16_t* resid, bf16_t* y, float* mean, float* rstd, int rows, int C, float eps, RowMap mx,
-                  RowMap my, RowMap mr, DropArgs dr, const bf16_t* g2 = nullptr, const bf16_t* b2 = nullptr, bf16_t* y2 = nullptr,
-                  float* mean2 = nullptr, float* rstd2 = nullptr, RowMap my2 = RowMap{0, 0, 0}) {
-  const int pf32 = (gelu_flags & IFSEG_LN_PARAMS_F32) ? 1 : 0;
-  if (gelu_flags & IFSEG_LN_GELU) hipLaunchKernelGGL((ln_fwd_kernel<NCH, true>), g, dim3(256), 0, s, x, gamma, beta, resid, y, mean, rstd, rows, C, eps, mx, my, mr, dr, g2, b2, y2, mean2, rstd2, my2, pf32);
-  else hipLaunchKernelGGL((ln_fwd_kernel<NCH, false>), g, dim3(256), 0, s, x, gamma, beta, resid, y, mean, rstd, rows, C, eps, mx, my, mr, dr, g2, b2, y2, mean2, rstd2, my2, pf32);
-  return 0;
-}
-template <int NCH, int WPR>
-int launch_ln_bwd(int gelu_flags, dim3 g, hipStream_t s, const bf16_t* dy, const bf16_t* x, const bf16_t* gamma,
-                  const float* mean, const float* rstd, const bf16_t* add, bf16_t* dx, float* dgp, float* dbp, int rows,
-                  int C, RowMap mdy, RowMap mx, RowMap mdx, RowMap madd, DropArgs dr) {
-  const int pf32 = (gelu_flags & IFSEG_LN_PARAMS_F32) ? 1 : 0;
-  if (gelu_flags & IFSEG_LN_GELU) hipLaunchKernelGGL((ln_bwd_kernel<NCH, true, WPR>), g, dim3(256), 0, s, dy, x, gamma, mean, rstd, add, dx, dgp, dbp, rows, C, mdy, mx, mdx, madd, dr, pf32);
-  else hipLaunchKernelGGL((ln_bwd_kernel<NCH, false, WPR>), g, dim3(256), 0, s, dy, x, gamma, mean, rstd, add, dx, dgp, dbp, rows, C, mdy, mx, mdx, madd, dr, pf32);
+// the kernels' DropArgs of an optional ifseg_drop_args (NULL: off); IFSEG_ERR_BAD_ARG for a p outside [0, 1) or no rows per batch
+int drop_args(const ifseg_drop_args* d, DropArgs& out) {
+  out = DropArgs{};
+  if (!d) return 0;
+  if (d->p < 0.f || d->p >= 1.f || d->rows_per_batch <= 0) return IFSEG_ERR_BAD_ARG;
+  out = DropArgs{1, d->p, d->seed, d->drop_path_scale, d->rows_per_batch, d->seed_add};
   return 0;
 }
 
@@ -676,20 +602,19 @@ static int ln_fwd_impl(const void* x, const void* gamma, const void* beta, const
   if (rows <= 0) return 0;
   if ((C & 7) || C > 4096 || (ldx & 7) || (ldy & 7) || (resid && (ldr & 7)) || (y2 && (ldy2 & 7))) return IFSEG_ERR_BAD_SHAPE;
   if (y2 && (!gamma2 || !beta2)) return IFSEG_ERR_BAD_ARG;
-  DropArgs dr{};
-  if (drop) {
-    if (drop->p < 0.f || drop->p >= 1.f || drop->rows_per_batch <= 0) return IFSEG_ERR_BAD_ARG;
-    dr = DropArgs{1, drop->p, drop->seed, drop->drop_path_scale, drop->rows_per_batch, drop->seed_add};
-  }
+  DropArgs dr;
+  if (const int rc = drop_args(drop, dr)) return rc;
   RowMap mx = row_map(rpb, x_bs, ldx), my = row_map(rpb, y_bs, ldy), mr = row_map(rpb, r_bs, ldr), my2 = row_map(rpb, y2_bs, ldy2);
-  dim3 g((rows + 3) / 4);
   hipStream_t s = (hipStream_t)stream;
-  const bf16_t *X = (const bf16_t*)x, *G = (const bf16_t*)gamma, *Bt = (const bf16_t*)beta, *R = (const bf16_t*)resid;
-  const bf16_t *G2 = (const bf16_t*)gamma2, *B2 = (const bf16_t*)beta2;
+  const bool gelu = act_gelu & IFSEG_LN_GELU;
+  // chunks per lane by row width (every instantiation has the same signature)
+  auto* kernel = C <= 1024 ? (gelu ? ln_fwd_kernel<2, true> : ln_fwd_kernel<2, false>)
+               : C <= 3072 ? (gelu ? ln_fwd_kernel<6, true> : ln_fwd_kernel<6, false>)
+                           : (gelu ? ln_fwd_kernel<8, true> : ln_fwd_kernel<8, false>);
   ifseg_prof_begin(IFSEG_K_LN_FWD, s, 0, (double)rows * C * ((resid ? 6.0 : 4.0) + (y2 ? 2.0 : 0.0)));
-  if (C <= 1024) launch_ln_fwd<2>(act_gelu, g, s, X, G, Bt, R, (bf16_t*)y, mean, rstd, rows, C, eps, mx, my, mr, dr, G2, B2, (bf16_t*)y2, mean2, rstd2, my2);
-  else if (C <= 3072) launch_ln_fwd<6>(act_gelu, g, s, X, G, Bt, R, (bf16_t*)y, mean, rstd, rows, C, eps, mx, my, mr, dr, G2, B2, (bf16_t*)y2, mean2, rstd2, my2);
-  else launch_ln_fwd<8>(act_gelu, g, s, X, G, Bt, R, (bf16_t*)y, mean, rstd, rows, C, eps, mx, my, mr, dr, G2, B2, (bf16_t*)y2, mean2, rstd2, my2);
+  hipLaunchKernelGGL(kernel, dim3((rows + 3) / 4), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)gamma, (const bf16_t*)beta,
+                     (const bf16_t*)resid, (bf16_t*)y, mean, rstd, rows, C, eps, mx, my, mr, dr, (const bf16_t*)gamma2,
+                     (const bf16_t*)beta2, (bf16_t*)y2, mean2, rstd2, my2, (act_gelu & IFSEG_LN_PARAMS_F32) ? 1 : 0);
   ifseg_prof_end(IFSEG_K_LN_FWD, s);
   IFSEG_CHECK_LAUNCH();
   return 0;
@@ -715,33 +640,44 @@ extern "C" int ifseg_ln_fwd_pair(const void* x, const void* gamma, const void* b
                      beta2, y2, mean2, rstd2, y2_bs, ldy2, stream);
 }
 
+// dx2 == NULL: ifseg_ln_bwd, `drop` masks dy.  dx2 given (ifseg_ln_bwd_drop, which has checked C <= 1024 and no GELU): `drop`
+// is the mask of the second output, dy is taken as it is.
+static int ln_bwd_impl(const void* dy, const void* x, const void* gamma, const float* mean, const float* rstd,
+                       const void* dx_add, void* dx, float* dgamma_part, float* dbeta_part, void* dx2, int nblocks,
+                       int rows, int C, int flags, int rpb, long long dy_bs, int lddy, long long x_bs, int ldx,
+                       long long dx_bs, int lddx, long long add_bs, int ldadd, long long dx2_bs, int lddx2,
+                       const ifseg_drop_args* drop, void* stream) {
+  (void)hipGetLastError();
+  if (rows <= 0) return 0;
+  if ((C & 7) || C > 4096 || nblocks <= 0) return IFSEG_ERR_BAD_SHAPE;
+  if (((lddy | ldx | lddx) & 7) || (dx2 && (lddx2 & 7)) || (dx_add && (ldadd & 7))) return IFSEG_ERR_BAD_SHAPE;
+  DropArgs dr;
+  if (const int rc = drop_args(drop, dr)) return rc;
+  RowMap mdy = row_map(rpb, dy_bs, lddy), mx = row_map(rpb, x_bs, ldx), mdx = row_map(rpb, dx_bs, lddx), madd = row_map(rpb, add_bs, ldadd);
+  hipStream_t s = (hipStream_t)stream;
+  const bool gelu = flags & IFSEG_LN_GELU;
+  const int pf32 = (flags & IFSEG_LN_PARAMS_F32) ? 1 : 0;
+  auto launch = [&](auto* kernel, auto... more) {
+    hipLaunchKernelGGL(kernel, dim3(nblocks), dim3(256), 0, s, (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)gamma, mean, rstd,
+                       (const bf16_t*)dx_add, (bf16_t*)dx, dgamma_part, dbeta_part, rows, C, mdy, mx, mdx, madd, more...);
+  };
+  ifseg_prof_begin(IFSEG_K_LN_BWD, s, 0, (double)rows * C * ((dx_add ? 8.0 : 6.0) + (dx2 ? 2.0 : 0.0)));
+  if (dx2) launch(ln_bwd_lean_kernel<2, true>, DropArgs{}, pf32, (bf16_t*)dx2, row_map(rpb, dx2_bs, lddx2), dr);
+  else if (C <= 1024 && !gelu) launch(ln_bwd_lean_kernel<2, false>, dr, pf32, (bf16_t*)nullptr, RowMap{}, DropArgs{});
+  else if (C <= 1024) launch(ln_bwd_kernel<2, true, 1>, dr, pf32);
+  else launch(gelu ? ln_bwd_kernel<2, true, 4> : ln_bwd_kernel<2, false, 4>, dr, pf32);
+  ifseg_prof_end(IFSEG_K_LN_BWD, s);
+  IFSEG_CHECK_LAUNCH();
+  return 0;
+}
+
 extern "C" int ifseg_ln_bwd(const void* dy, const void* x, const void* gamma, const float* mean, const float* rstd,
                             const void* dx_add, void* dx, float* dgamma_part, float* dbeta_part, int nblocks,
                             int rows, int C, int act_gelu, int rpb, long long dy_bs, int lddy, long long x_bs,
                             int ldx, long long dx_bs, int lddx, long long add_bs, int ldadd,
                             const ifseg_drop_args* drop, void* stream) {
-  (void)hipGetLastError();
-  if (rows <= 0) return 0;
-  if ((C & 7) || C > 4096 || nblocks <= 0) return IFSEG_ERR_BAD_SHAPE;
-  if (((lddy | ldx | lddx) & 7) || (dx_add && (ldadd & 7))) return IFSEG_ERR_BAD_SHAPE;
-  DropArgs dr{};
-  if (drop) {
-    if (drop->p < 0.f || drop->p >= 1.f || drop->rows_per_batch <= 0) return IFSEG_ERR_BAD_ARG;
-    dr = DropArgs{1, drop->p, drop->seed, drop->drop_path_scale, drop->rows_per_batch, drop->seed_add};
-  }
-  RowMap mdy = row_map(rpb, dy_bs, lddy), mx = row_map(rpb, x_bs, ldx), mdx = row_map(rpb, dx_bs, lddx), madd = row_map(rpb, add_bs, ldadd);
-  dim3 g(nblocks);
-  hipStream_t s = (hipStream_t)stream;
-  const bf16_t *DY = (const bf16_t*)dy, *X = (const bf16_t*)x, *G = (const bf16_t*)gamma, *A = (const bf16_t*)dx_add;
-  ifseg_prof_begin(IFSEG_K_LN_BWD, s, 0, (double)rows * C * (dx_add ? 8.0 : 6.0));
-  if (C <= 1024 && !(act_gelu & IFSEG_LN_GELU))
-    hipLaunchKernelGGL((ln_bwd_lean_kernel<2, false>), g, dim3(256), 0, s, DY, X, G, mean, rstd, A, (bf16_t*)dx, dgamma_part, dbeta_part, rows, C,
-                       mdy, mx, mdx, madd, dr, (act_gelu & IFSEG_LN_PARAMS_F32) ? 1 : 0, (bf16_t*)nullptr, RowMap{}, DropArgs{});
-  else if (C <= 1024) launch_ln_bwd<2, 1>(act_gelu, g, s, DY, X, G, mean, rstd, A, (bf16_t*)dx, dgamma_part, dbeta_part, rows, C, mdy, mx, mdx, madd, dr);
-  else launch_ln_bwd<2, 4>(act_gelu, g, s, DY, X, G, mean, rstd, A, (bf16_t*)dx, dgamma_part, dbeta_part, rows, C, mdy, mx, mdx, madd, dr);
-  ifseg_prof_end(IFSEG_K_LN_BWD, s);
-  IFSEG_CHECK_LAUNCH();
-  return 0;
+  return ln_bwd_impl(dy, x, gamma, mean, rstd, dx_add, dx, dgamma_part, dbeta_part, nullptr, nblocks, rows, C, act_gelu, rpb, dy_bs,
+                     lddy, x_bs, ldx, dx_bs, lddx, add_bs, ldadd, 0, 0, drop, stream);
 }
 
 extern "C" int ifseg_ln_bwd_drop(const void* dy, const void* x, const void* gamma, const float* mean, const float* rstd,
@@ -753,21 +689,8 @@ extern "C" int ifseg_ln_bwd_drop(const void* dy, const void* x, const void* gamm
   if (rows <= 0) return 0;
   if ((C & 7) || C > 1024 || nblocks <= 0) return IFSEG_ERR_BAD_SHAPE;
   if (!dx2 || (flags & IFSEG_LN_GELU)) return IFSEG_ERR_BAD_ARG;     // (no GELU instantiation of the lean kernel)
-  if (((lddy | ldx | lddx | lddx2) & 7) || (dx_add && (ldadd & 7))) return IFSEG_ERR_BAD_SHAPE;
-  DropArgs dr{};
-  if (drop2) {
-    if (drop2->p < 0.f || drop2->p >= 1.f || drop2->rows_per_batch <= 0) return IFSEG_ERR_BAD_ARG;
-    dr = DropArgs{1, drop2->p, drop2->seed, drop2->drop_path_scale, drop2->rows_per_batch, drop2->seed_add};
-  }
-  RowMap mdy = row_map(rpb, dy_bs, lddy), mx = row_map(rpb, x_bs, ldx), mdx = row_map(rpb, dx_bs, lddx), madd = row_map(rpb, add_bs, ldadd), mdx2 = row_map(rpb, dx2_bs, lddx2);
-  hipStream_t s = (hipStream_t)stream;
-  ifseg_prof_begin(IFSEG_K_LN_BWD, s, 0, (double)rows * C * (dx_add ? 10.0 : 8.0));
-  hipLaunchKernelGGL((ln_bwd_lean_kernel<2, true>), dim3(nblocks), dim3(256), 0, s, (const bf16_t*)dy, (const bf16_t*)x,
-                     (const bf16_t*)gamma, mean, rstd, (const bf16_t*)dx_add, (bf16_t*)dx, dgamma_part, dbeta_part, rows, C,
-                     mdy, mx, mdx, madd, DropArgs{}, (flags & IFSEG_LN_PARAMS_F32) ? 1 : 0, (bf16_t*)dx2, mdx2, dr);
-  ifseg_prof_end(IFSEG_K_LN_BWD, s);
-  IFSEG_CHECK_LAUNCH();
-  return 0;
+  return ln_bwd_impl(dy, x, gamma, mean, rstd, dx_add, dx, dgamma_part, dbeta_part, dx2, nblocks, rows, C, flags, rpb, dy_bs, lddy,
+                     x_bs, ldx, dx_bs, lddx, add_bs, ldadd, dx2_bs, lddx2, drop2, stream);
 }
 
 namespace {
@@ -795,22 +718,13 @@ extern "C" int ifseg_reduce_parts(const float* in, void* out, int outer, int par
   (void)hipGetLastError();
   const long long total = (long long)outer * n;
   if (total <= 0) return 0;
-  if (parts >= 2048 && total <= 4096) {
-    if (out_bf16) hipLaunchKernelGGL(reduce_parts_tall_kernel<true>, dim3((unsigned)total), dim3(256), 0, (hipStream_t)stream, in, out, outer, parts, n, accumulate, scale);
-    else hipLaunchKernelGGL(reduce_parts_tall_kernel<false>, dim3((unsigned)total), dim3(256), 0, (hipStream_t)stream, in, out, outer, parts, n, accumulate, scale);
-    IFSEG_CHECK_LAUNCH();
-    return 0;
-  }
-  if (parts >= 32) {
-    dim3 g2((unsigned)(outer * ((n + 31) / 32)));
-    if (out_bf16) hipLaunchKernelGGL(reduce_parts2d_kernel<true>, g2, dim3(256), 0, (hipStream_t)stream, in, out, outer, parts, n, accumulate, scale);
-    else hipLaunchKernelGGL(reduce_parts2d_kernel<false>, g2, dim3(256), 0, (hipStream_t)stream, in, out, outer, parts, n, accumulate, scale);
-    IFSEG_CHECK_LAUNCH();
-    return 0;
-  }
-  dim3 g((unsigned)((total + 255) / 256));
-  if (out_bf16) hipLaunchKernelGGL(reduce_parts_kernel<true>, g, dim3(256), 0, (hipStream_t)stream, in, out, outer, parts, n, accumulate, scale);
-  else hipLaunchKernelGGL(reduce_parts_kernel<false>, g, dim3(256), 0, (hipStream_t)stream, in, out, outer, parts, n, accumulate, scale);
+  // one block per output element (tall) / per 32 columns / one thread per element
+  const bool tall = parts >= 2048 && total <= 4096, cols32 = parts >= 32, bf = out_bf16;
+  const long long grid = tall ? total : cols32 ? outer * ((n + 31) / 32) : (total + 255) / 256;
+  auto* kernel = tall   ? (bf ? reduce_parts_tall_kernel<true> : reduce_parts_tall_kernel<false>)
+               : cols32 ? (bf ? reduce_parts2d_kernel<true> : reduce_parts2d_kernel<false>)
+                        : (bf ? reduce_parts_kernel<true> : reduce_parts_kernel<false>);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, in, out, outer, parts, n, accumulate, scale);
   IFSEG_CHECK_LAUNCH();
   return 0;
 }
@@ -1133,12 +1047,7 @@ __global__ void dropout_kernel(const bf16_t* x, const bf16_t* resid, bf16_t* out
   float f[8];
   unpack8(*reinterpret_cast<const uint4*>(x + mx.off(row) + col), f);
   drop8(f, DropArgs{1, p, seed, dpscale, rows_per_batch, seed_add}, c8, row);
-  if (resid) {
-    float r[8];
-    unpack8(*reinterpret_cast<const uint4*>(resid + mr.off(row) + col), r);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) f[e] += r[e];
-  }
+  if (resid) add8(f, resid + mr.off(row) + col);
   *reinterpret_cast<uint4*>(out + mo.off(row) + col) = pack8(f);
 }
 }  // namespace
@@ -1149,7 +1058,9 @@ extern "C" int ifseg_dropout(const void* x, const void* resid, void* out, long l
                              const unsigned long long* seed_add, void* stream) {
   (void)hipGetLastError();
   if (rows <= 0) return 0;
-  if ((C & 7) || p < 0.f || p >= 1.f || rows_per_batch <= 0) return IFSEG_ERR_BAD_ARG;
+  const ifseg_drop_args da{p, seed, drop_path_scale, rows_per_batch, seed_add};
+  DropArgs checked;
+  if ((C & 7) || drop_args(&da, checked)) return IFSEG_ERR_BAD_ARG;
   if (((ldx | ldo) & 7) || (resid && (ldr & 7)) || (rpb > 0 && (((x_bs | o_bs) & 7) || (resid && (r_bs & 7))))) return IFSEG_ERR_BAD_SHAPE;
   const long long nchunks = rows * (C / 8);
   RowMap mx = row_map(rpb, x_bs, ldx), mr = row_map(rpb, r_bs, ldr), mo = row_map(rpb, o_bs, ldo);

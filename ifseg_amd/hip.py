@@ -591,35 +591,34 @@ def _ln_flags(gamma, gelu=False, other=None):
     return (1 if gelu else 0) | (2 if f32 else 0)
 
 
+def _ln_geom(x, *tensors):
+    """(rows, C, rpb) of x, [rows, C] or [B, rpb, C], and the flattened (c_ll(bs), c_int(ld)) pairs of `tensors` in order"""
+    C = x.shape[-1]
+    rpb = x.shape[1] if x.dim() == 3 else 0
+    maps = []
+    for t in tensors:
+        bs, ld = _map(t, rpb)
+        maps += [c_ll(bs), c_int(ld)]
+    return x.numel() // C, C, rpb, maps
+
+
 def ln_fwd(x, gamma, beta, y, mean=None, rstd=None, resid=None, gelu=False, eps=1e-5, drop=None):
     """x, y, resid: [rows, C] or [B, rpb, C] (strided views allowed, last dim contiguous).
     drop: fused dropout/DropPath of the normalised output before the residual add (see _drop_ref)."""
-    C = x.shape[-1]
-    rows = x.numel() // C
-    rpb = x.shape[1] if x.dim() == 3 else 0
-    xb, xl = _map(x, rpb)
-    yb, yl = _map(y, rpb)
-    rb, rl = _map(resid, rpb)
+    rows, C, rpb, maps = _ln_geom(x, x, y, resid)
     rc = lib().ifseg_ln_fwd(_ptr(x), _ptr(gamma), _ptr(beta), _ptr(resid), _ptr(y), _ptr(mean), _ptr(rstd),
-                            c_int(rows), c_int(C), c_float(eps), c_int(_ln_flags(gamma, gelu)), c_int(rpb), c_ll(xb),
-                            c_int(xl), c_ll(yb), c_int(yl), c_ll(rb), c_int(rl), _drop_ref(drop, rpb or rows), _stream())
+                            c_int(rows), c_int(C), c_float(eps), c_int(_ln_flags(gamma, gelu)), c_int(rpb), *maps,
+                            _drop_ref(drop, rpb or rows), _stream())
     _check(rc, "ln_fwd")
     return y
 
 
 def ln_fwd_pair(x, gamma, beta, y, mean, rstd, gamma2, beta2, y2, mean2, rstd2, resid=None, eps=1e-5, drop=None):
     """y = [resid +] drop(LN(x)), y2 = LN2(y): the post-LN of a block and the pre-LN of the next in one launch"""
-    C = x.shape[-1]
-    rows = x.numel() // C
-    rpb = x.shape[1] if x.dim() == 3 else 0
-    xb, xl = _map(x, rpb)
-    yb, yl = _map(y, rpb)
-    rb, rl = _map(resid, rpb)
-    y2b, y2l = _map(y2, rpb)
+    rows, C, rpb, maps = _ln_geom(x, x, y, resid, y2)
     rc = lib().ifseg_ln_fwd_pair(_ptr(x), _ptr(gamma), _ptr(beta), _ptr(resid), _ptr(y), _ptr(mean), _ptr(rstd), _ptr(gamma2),
                                  _ptr(beta2), _ptr(y2), _ptr(mean2), _ptr(rstd2), c_int(rows), c_int(C), c_float(eps),
-                                 c_int(_ln_flags(gamma, False, gamma2)), c_int(rpb), c_ll(xb), c_int(xl), c_ll(yb), c_int(yl), c_ll(rb), c_int(rl), c_ll(y2b),
-                                 c_int(y2l), _drop_ref(drop, rpb or rows), _stream())
+                                 c_int(_ln_flags(gamma, False, gamma2)), c_int(rpb), *maps, _drop_ref(drop, rpb or rows), _stream())
     _check(rc, "ln_fwd_pair")
     return y, y2
 
@@ -630,34 +629,19 @@ LN_BWD_BLOCKS = int(lab.get("LN_BWD_BLOCKS", "768"))   # three resident blocks p
 def ln_bwd_drop(dy, x, gamma, mean, rstd, dx, dgamma_part, dbeta_part, dx2, dx_add=None, drop2=None):
     """dx = [dx_add +] LN'(x; gamma)(dy) and dx2 = drop2(dx): the pre-LN backward that closes a block of the backward and the
     fc2-dropout adjoint that opens the next one in one launch"""
-    C = x.shape[-1]
-    rows = x.numel() // C
-    rpb = x.shape[1] if x.dim() == 3 else 0
-    db_, dl = _map(dy, rpb)
-    xb, xl = _map(x, rpb)
-    ob, ol = _map(dx, rpb)
-    ab, al = _map(dx_add, rpb)
-    o2b, o2l = _map(dx2, rpb)
+    rows, C, rpb, maps = _ln_geom(x, dy, x, dx, dx_add, dx2)
     rc = lib().ifseg_ln_bwd_drop(_ptr(dy), _ptr(x), _ptr(gamma), _ptr(mean), _ptr(rstd), _ptr(dx_add), _ptr(dx),
                                  _ptr(dgamma_part), _ptr(dbeta_part), _ptr(dx2), c_int(LN_BWD_BLOCKS), c_int(rows), c_int(C),
-                                 c_int(_ln_flags(gamma)), c_int(rpb), c_ll(db_), c_int(dl), c_ll(xb), c_int(xl), c_ll(ob), c_int(ol), c_ll(ab),
-                                 c_int(al), c_ll(o2b), c_int(o2l), _drop_ref(drop2, rpb or rows), _stream())
+                                 c_int(_ln_flags(gamma)), c_int(rpb), *maps, _drop_ref(drop2, rpb or rows), _stream())
     _check(rc, "ln_bwd_drop")
     return dx, dx2
 
 
 def ln_bwd(dy, x, gamma, mean, rstd, dx, dgamma_part, dbeta_part, dx_add=None, gelu=False, drop=None):
-    C = x.shape[-1]
-    rows = x.numel() // C
-    rpb = x.shape[1] if x.dim() == 3 else 0
-    db_, dl = _map(dy, rpb)
-    xb, xl = _map(x, rpb)
-    ob, ol = _map(dx, rpb)
-    ab, al = _map(dx_add, rpb)
+    rows, C, rpb, maps = _ln_geom(x, dy, x, dx, dx_add)
     rc = lib().ifseg_ln_bwd(_ptr(dy), _ptr(x), _ptr(gamma), _ptr(mean), _ptr(rstd), _ptr(dx_add), _ptr(dx),
                             _ptr(dgamma_part), _ptr(dbeta_part), c_int(LN_BWD_BLOCKS), c_int(rows), c_int(C),
-                            c_int(_ln_flags(gamma, gelu)), c_int(rpb), c_ll(db_), c_int(dl), c_ll(xb), c_int(xl), c_ll(ob),
-                            c_int(ol), c_ll(ab), c_int(al), _drop_ref(drop, rpb or rows), _stream())
+                            c_int(_ln_flags(gamma, gelu)), c_int(rpb), *maps, _drop_ref(drop, rpb or rows), _stream())
     _check(rc, "ln_bwd")
     return dx
 

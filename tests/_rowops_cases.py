@@ -207,8 +207,8 @@ BWD_DROP_CASES = ([_bwd(C, "ln_bwd_lean_kernel<2,true>", 25, 3, drop=True) for C
 LN_INSTANTIATIONS = (["ln_fwd_kernel<%d,%s>" % (n, g) for n in (2, 6, 8) for g in ("false", "true")]
                      + ["ln_bwd_lean_kernel<2,false>", "ln_bwd_lean_kernel<2,true>", "ln_bwd_kernel<2,true,1>",
                         "ln_bwd_kernel<2,false,4>", "ln_bwd_kernel<2,true,4>"])
-# (ln_bwd_kernel<2,false,1> cannot be reached through the C ABI: narrow rows without GELU always take the lean kernel.  The
-# bit-identity "lean partials == ln_bwd_kernel<2,false,1> partials" therefore has no case.)
+# (ln_bwd_kernel<2,false,1> is not instantiated: narrow rows without GELU always take the lean kernel, so nothing could reach
+# it through the C ABI.  The bit-identity "lean partials == ln_bwd_kernel<2,false,1> partials" therefore has no case.)
 
 DROP_P, DROP_SEED, DROP_RPB = 0.1, 0x9E3779B97F4A7C15 ^ 0x1234567, 2      # (the seed has bit 63 set)
 DROP_DPSCALE = (1.25, 0.0, 2.0, 1.0, 0.5, 1.25, 0.0, 2.0, 1.0, 0.5, 1.25, 0.0, 2.0)   # per batch of DROP_RPB rows; DropPath zeros included
