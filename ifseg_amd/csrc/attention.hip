@@ -1556,6 +1556,13 @@ static int attn_check(const AttnArgs& a) {
   if (((size_t)a.q | (size_t)a.k | (size_t)a.v | (size_t)a.o | (size_t)a.dO | (size_t)a.dq | (size_t)a.dk | (size_t)a.dv) & 15)
     return IFSEG_ERR_BAD_ARG;
   if ((a.q_bs | a.k_bs | a.v_bs | a.o_bs | a.do_bs | a.dq_bs | a.dk_bs | a.dv_bs) & 7) return IFSEG_ERR_BAD_SHAPE;
+  // the abs-pos operands are the second half of Q_ext / K_ext: both or neither, rows read 16 bytes at a time like q and k
+  if ((a.pq == nullptr) != (a.pk == nullptr)) return IFSEG_ERR_BAD_ARG;
+  if (a.pq) {
+    if ((a.ldpq | a.ldpk) & 7) return IFSEG_ERR_BAD_SHAPE;
+    if (((size_t)a.pq | (size_t)a.pk) & 15) return IFSEG_ERR_BAD_ARG;
+  }
+  if (a.rel_mode && (!a.gcode || !a.rel2d || !a.rel1d || !a.relx)) return IFSEG_ERR_BAD_ARG;
   return 0;
 }
 
@@ -1575,7 +1582,10 @@ extern "C" int ifseg_attn_fwd(const void* q, const void* k, const void* v, const
   a.rel_mode = rel_mode; a.P = P; a.gcode = gcode; a.code_bias = code_bias; a.n2d = rel_mode ? n2d : 0;
   a.Lt = T - P; a.rel2d = rel2d; a.rel1d = rel1d; a.relx = relx; a.causal = causal; a.dense = dense_bias; a.gain = (const float*)gain;
   a.dense_ld = dense_bias ? (dense_ld > 0 ? dense_ld : S) : 0;
+  if (!q || !k || !v || !out || !lse) return IFSEG_ERR_BAD_ARG;
   if (dense_bias && a.dense_ld < S) return IFSEG_ERR_BAD_ARG;
+  // the seeded path (no rel_mode, dense_ld % 4 == 0) reads the rows of the dense bias as float4
+  if (dense_bias && !rel_mode && !(a.dense_ld & 3) && ((size_t)dense_bias & 15)) return IFSEG_ERR_BAD_ARG;
 #ifdef IFSEG_EXP_NOBIAS_FWD
   pos_q = nullptr; a.pq = nullptr; a.pk = nullptr; a.rel_mode = 0; a.n2d = 0; rel_mode = 0;   // timing bound only
 #endif
@@ -1629,6 +1639,9 @@ extern "C" int ifseg_attn_bwd(const ifseg_attn_bwd_args* x, void* stream) {
   int rc = attn_check(a);
   if (rc) return rc;
   if ((x->lddo | x->lddq | x->lddk | x->lddv | x->ldout) & 7) return IFSEG_ERR_BAD_SHAPE;
+  // the delta kernel reads rows of `out` as uint4; the abs-pos partials are stored 16 bytes at a time (store_tile_bf16)
+  if (x->out_bs & 7) return IFSEG_ERR_BAD_SHAPE;
+  if (((size_t)x->out | (size_t)x->dpos_q_part | (size_t)x->dpos_k_part) & 15) return IFSEG_ERR_BAD_ARG;
   {   // the dK/dV kernel addresses a query row by a 32-bit byte offset from the batch element's base
     const long long ldmax = a.ldq > a.lddo ? (a.ldq > a.ldpq ? a.ldq : a.ldpq) : (a.lddo > a.ldpq ? a.lddo : a.ldpq);
     if ((long long)a.T * ldmax * 2 >= (1ll << 31)) return IFSEG_ERR_BAD_SHAPE;
@@ -1637,6 +1650,13 @@ extern "C" int ifseg_attn_bwd(const ifseg_attn_bwd_args* x, void* stream) {
   if (a.rel_mode && a.nparts != a.B * nkt) return IFSEG_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
   const int ph = x->phases ? x->phases : (IFSEG_ATTN_BWD_DELTA | IFSEG_ATTN_BWD_DKV | IFSEG_ATTN_BWD_DQ);
+  // every pointer a launched kernel dereferences without looking at it
+  if ((ph & IFSEG_ATTN_BWD_DELTA) && (!x->out || !a.dO || !x->delta)) return IFSEG_ERR_BAD_ARG;
+  if ((ph & (IFSEG_ATTN_BWD_DKV | IFSEG_ATTN_BWD_DQ)) && (!a.q || !a.k || !a.v || !a.dO || !a.lse || !a.delta)) return IFSEG_ERR_BAD_ARG;
+  if ((ph & IFSEG_ATTN_BWD_DKV) &&
+      (!a.dk || !a.dv || (a.pq && !a.dpk) || (a.rel_mode && (!a.drel2d_part || !a.drel1d_part || !a.drelx_part))))
+    return IFSEG_ERR_BAD_ARG;
+  if ((ph & IFSEG_ATTN_BWD_DQ) && (!a.dq || (a.pq && !a.dpq))) return IFSEG_ERR_BAD_ARG;
   if (ph & IFSEG_ATTN_BWD_DELTA) {  // delta = rowsum(dO * O)
     const long long threads = (long long)a.B * a.T * a.H * 8;
     hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s,

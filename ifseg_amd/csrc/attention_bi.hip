@@ -1270,6 +1270,7 @@ extern "C" int ifseg_attn_dense_bias(const void* pos_q, const void* pos_k, int l
   (void)hipGetLastError();
   if (!D || H <= 0 || T <= 0 || S <= 0 || (Sp & 31) || (Tp & 31) || Sp < S || Tp < T) return IFSEG_ERR_BAD_ARG;
   if ((pos_q == nullptr) != (pos_k == nullptr) || ((ldpq | ldpk) & 7)) return IFSEG_ERR_BAD_ARG;
+  if (((size_t)pos_q | (size_t)pos_k) & 15) return IFSEG_ERR_BAD_ARG;      // rows are read 16 bytes at a time
   if (rel_mode && (!gcode || !rel2d || !rel1d || !relx)) return IFSEG_ERR_BAD_ARG;
   if ((rel_mode || causal) && (P > T || P > S || P < 0)) return IFSEG_ERR_BAD_SHAPE;
   DenseArgs a{};
@@ -1305,6 +1306,8 @@ extern "C" int ifseg_attn_bwd_bi(const ifseg_attn_bi_args* x, void* stream) {
   if ((a.ldq | a.ldk | a.ldv | a.lddo | a.lddq | a.lddk | a.lddv) & 7) return IFSEG_ERR_BAD_SHAPE;
   if (((size_t)a.q | (size_t)a.k | (size_t)a.v | (size_t)a.dO | (size_t)a.dq | (size_t)a.dk | (size_t)a.dv | (size_t)a.dbias) & 15)
     return IFSEG_ERR_BAD_ARG;
+  // the bias tiles are fetched 16 bytes per lane; both kernels read q, k, v, dout, lse and delta without looking at the pointers
+  if (((size_t)a.D & 15) || !a.q || !a.k || !a.v || !a.dO || !a.lse || !a.delta) return IFSEG_ERR_BAD_ARG;
   if ((a.q_bs | a.k_bs | a.v_bs | a.do_bs | a.dq_bs | a.dk_bs | a.dv_bs) & 7) return IFSEG_ERR_BAD_SHAPE;
   if (a.causal && ((a.P & 63) || a.P > a.T || a.P > a.S)) return IFSEG_ERR_BAD_SHAPE;
   {   // rows are addressed by 32-bit byte offsets from a per-(batch, head) or per-head base
@@ -1317,8 +1320,10 @@ extern "C" int ifseg_attn_bwd_bi(const ifseg_attn_bi_args* x, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   const int nbg = (a.B + 3) / 4;
   const int ph = x->phases ? x->phases : (IFSEG_ATTN_BWD_DKV | IFSEG_ATTN_BWD_DQ);
+  // (the outputs of every requested phase, before the first launch)
+  if ((ph & IFSEG_ATTN_BWD_DKV) && (!a.dk || !a.dv)) return IFSEG_ERR_BAD_ARG;
+  if ((ph & IFSEG_ATTN_BWD_DQ) && (!a.dq || !a.dbias)) return IFSEG_ERR_BAD_ARG;
   if (ph & IFSEG_ATTN_BWD_DKV) {
-    if (!a.dk || !a.dv) return IFSEG_ERR_BAD_ARG;
     auto kern = dropping ? attn_bi_dkv_drop_kernel : attn_bi_dkv_kernel;
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DKV);
     ifseg_prof_begin(IFSEG_K_ATTN_DKV, s, 6.0 * 64 * (double)a.T * a.S * a.B * a.H, 0);
@@ -1326,7 +1331,6 @@ extern "C" int ifseg_attn_bwd_bi(const ifseg_attn_bi_args* x, void* stream) {
     ifseg_prof_end(IFSEG_K_ATTN_DKV, s);
   }
   if (ph & IFSEG_ATTN_BWD_DQ) {
-    if (!a.dq || !a.dbias) return IFSEG_ERR_BAD_ARG;
     auto kern = dropping ? attn_bi_dq_drop_kernel : attn_bi_dq_kernel;
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DQ);
     ifseg_prof_begin(IFSEG_K_ATTN_DQ, s, 2.0 * 64 * (double)a.T * a.S * a.B * a.H, 0);
@@ -1350,7 +1354,7 @@ extern "C" int ifseg_attn_fwd_bi(const ifseg_attn_bi_args* x, void* stream) {
   a.drop_p = x->drop_p; a.drop_seed = x->drop_seed; a.drop_seed_add = x->drop_seed_add;
   if (!(a.drop_p >= 0.f && a.drop_p < 1.f)) return IFSEG_ERR_BAD_ARG;
   if ((a.ldq | a.ldk | a.ldv | a.ldo) & 7) return IFSEG_ERR_BAD_SHAPE;
-  if (((size_t)a.q | (size_t)a.k | (size_t)a.v | (size_t)a.out) & 15) return IFSEG_ERR_BAD_ARG;
+  if (((size_t)a.q | (size_t)a.k | (size_t)a.v | (size_t)a.out | (size_t)a.D) & 15) return IFSEG_ERR_BAD_ARG;   // (D: 16-byte tile fetches)
   if ((a.q_bs | a.k_bs | a.v_bs | a.o_bs) & 7) return IFSEG_ERR_BAD_SHAPE;
   if (a.causal && ((a.P & 63) || a.P > a.T || a.P > a.S)) return IFSEG_ERR_BAD_SHAPE;
   {
@@ -1381,6 +1385,8 @@ extern "C" int ifseg_attn_dbias_grads(const ifseg_attn_dbias_args* x, void* stre
   if (a.causal && (a.P <= 0 || (a.P & 31))) return IFSEG_ERR_BAD_SHAPE;
   a.drel2d = x->drel2d; a.drel1d = x->drel1d; a.drelx = x->drelx;
   const bool pos = a.pq != nullptr;
+  // the slabs and the pos rows are read 16 bytes at a time
+  if (((size_t)a.dbias | (size_t)a.pq | (size_t)a.pk) & 15) return IFSEG_ERR_BAD_ARG;
   if (pos && (!a.pk || !a.dpq || !a.dpk || ((a.ldpq | a.ldpk) & 7) || (a.C & 3) || a.C < a.H * 64)) return IFSEG_ERR_BAD_ARG;
   const bool rel = a.drel2d != nullptr;
   if (rel) {

@@ -135,7 +135,16 @@ int ifseg_conv2d_nhwc_bf16(const void* in, const void* w, const void* shift, con
  * keys; tail query i sees tail keys j<=i only.  dense_bias: optional fp32 [H,T,dense_ld]
  * (resized grids: ifseg_resized_rel_bias; dense_ld >= S is the row stride, 0 = S; a multiple of 4 with no rel_mode / causal
  * takes the seeded path: four 16-byte loads per 32-key block into the score accumulator, -inf entries = masked keys).
- * Requires P % 64 == 0 when rel_mode or causal. */
+ * Requires P % 64 == 0 when rel_mode or causal.
+ * Refused (nothing is launched): q, k, v, out, pos_q, pos_k not 16-byte aligned or a row / batch stride of theirs (ldpq and
+ * ldpk included) that is no multiple of 8 elements -- every row is read 16 bytes at a time; pos_q without pos_k or the
+ * reverse; rel_mode without gcode / rel2d / rel1d / relx; a NULL q, k, v, out or lse; a dense_bias that takes the seeded path
+ * (no rel_mode, dense_ld % 4 == 0) from a base that is not 16-byte aligned (its rows are read as float4; any other dense_ld
+ * takes the scalar path and needs no alignment).  ifseg_attn_bwd refuses the same, and any pointer a requested phase
+ * dereferences that is NULL: out / dout / delta (DELTA), q, k, v, dout, lse, delta (DKV, DQ), dk, dv, dpos_k_part with pos_k
+ * and the three table partials with rel_mode (DKV), dq and dpos_q_part with pos_q (DQ); and `out`, dpos_q_part or dpos_k_part
+ * not 16-byte aligned or out_bs no multiple of 8 (the delta launch reads `out` and the abs-pos partials are stored 16 bytes at a
+ * time). */
 int ifseg_attn_fwd(const void* q, const void* k, const void* v, const void* pos_q, const void* pos_k,
                    void* out, float* lse, int B, int H, int T, int S, int ldq, int ldk, int ldv, int ldo,
                    int ldpq, int ldpk, long long q_bs, long long k_bs, long long v_bs, long long o_bs,
@@ -220,7 +229,8 @@ int ifseg_attn_bwd_reduce(const ifseg_attn_reduce_args* args, void* stream);
  *   to 32; D 16-byte aligned); -inf where the causal mask ("tail-first" order of ifseg_attn_fwd) hides (i,j), for padded columns j >= S
  *   and padded rows i >= T.  Parameters only: built once per layer and step.  (Causal: 32 x 32 tiles no kernel's block
  *   schedule reaches are not written.)
- *   rel(i,j) as documented at ifseg_attn_fwd (rel_mode = 1), pos_q / pos_k may be NULL (no abs-pos term). */
+ *   rel(i,j) as documented at ifseg_attn_fwd (rel_mode = 1), pos_q / pos_k may be NULL (no abs-pos term); both 16-byte aligned
+ *   with ldpq, ldpk multiples of 8 (refused otherwise). */
 int ifseg_attn_dense_bias(const void* pos_q, const void* pos_k, int ldpq, int ldpk, int H, int T, int S, int rel_mode,
                           int P, const int* gcode, int code_bias, int n2d, const float* rel2d, const float* rel1d,
                           const float* relx, int causal, void* D, int Sp, int Tp, void* stream);
@@ -256,6 +266,10 @@ typedef struct ifseg_attn_bi_args {
                                   (ifseg_attn_dropout_mask writes it out); 0 = off.  `delta` must come from the dropped output. */
   unsigned long long drop_seed;
   const unsigned long long* drop_seed_add;   /* device word or NULL (as ifseg_drop_args.seed_add) */
+  /* Refused by both entry points (nothing is launched): q, k, v, out / dout, dq, dk, dv, dbias or D not 16-byte aligned (rows
+     and bias tiles move 16 bytes per lane), row / batch strides that are no multiple of 8 elements, Sp / Tp no multiple of 32;
+     by ifseg_attn_bwd_bi also a NULL q, k, v, dout, lse or delta, and a NULL output of any requested phase (all of them are
+     looked at before the first launch). */
 } ifseg_attn_bi_args;
 int ifseg_attn_bwd_bi(const ifseg_attn_bi_args* args, void* stream);
 /* ifseg_attn_fwd_bi: the forward of the same formulation -- out = gain softmax_fp32(q k^T + D) v, `lse` (written) as
@@ -274,7 +288,8 @@ int ifseg_attn_dropout_mask(unsigned char* keep, int B, int H, int T, int S, flo
  *     drel1d[h][p][(i-j)+Lt-1] = sum over tail pairs;  drelx[h][p][0] = sum_{i<P<=j<S} dB,  drelx[h][p][1] = sum_{j<P<=i<T} dB
  *   as NP = ifseg_attn_dbias_nparts() partial tables per head (part p = the rows i = p mod NP): they feed
  *   ifseg_attn_bwd_reduce with nparts = NP.  pos_q == NULL skips the operand gradients, drel2d == NULL the tables.
- *   Fixed summation order.  Any ng: the slabs are taken two per launch pair, later pairs add to the first's results. */
+ *   Fixed summation order.  Any ng: the slabs are taken two per launch pair, later pairs add to the first's results.
+ *   dbias, pos_q and pos_k must be 16-byte aligned (refused otherwise). */
 typedef struct ifseg_attn_dbias_args {
   const void* dbias;           /* bf16 [ng][H][T][Sp] */
   int ng, H, T, S, Sp, C;
