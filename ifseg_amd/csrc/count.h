@@ -25,6 +25,19 @@ __device__ __forceinline__ void bin_add(uint32_t* tab, int idx, bool on) {
   else if (on && idx != first) atomicAdd(&tab[idx], 1u);
 }
 
+// the ground-truth rule of include/ifseg_hip.h, its one statement (predict.hip's scoring, boundary.hip): the class of the
+// value g, whether the pixel (where `live`) is scored, and whether it is not ignored but of a class outside [0, n)
+struct GtClass {
+  int cls;
+  bool sc, oor;
+};
+__device__ __forceinline__ GtClass gt_class(int n, int raw, int g, bool live) {
+  const bool ign = raw ? (g == 0 || g == 255) : (g == n || g == 255);
+  const int cls = raw ? g - 1 : g;
+  const bool inr = (unsigned)cls < (unsigned)n;
+  return {cls, live && !ign && inr, live && !ign && !inr};
+}
+
 // ---- the walk ----
 // A lane takes 16 consecutive pixels per step: their labels come as aligned 16-byte loads.  The body starts at the first
 // 16-byte boundary of `lab`; the second stream's elements of the same pixels sit wherever they sit (MapStream, FloatStream).

@@ -179,19 +179,6 @@ __device__ __forceinline__ void score_zero(uint32_t* tab, int n) {
   for (int i = threadIdx.x; i < 3 * n + 2; i += 256) tab[i] = 0;
 }
 
-// the ground-truth rule of include/ifseg_hip.h, its one statement: the class of the value g, whether the pixel (where `live`)
-// is scored, and whether it is not ignored but of a class outside [0, n)
-struct GtClass {
-  int cls;
-  bool sc, oor;
-};
-__device__ __forceinline__ GtClass gt_class(int n, int raw, int g, bool live) {
-  const bool ign = raw ? (g == 0 || g == 255) : (g == n || g == 255);
-  const int cls = raw ? g - 1 : g;
-  const bool inr = (unsigned)cls < (unsigned)n;
-  return {cls, live && !ign && inr, live && !ign && !inr};
-}
-
 // one pixel (where `live`) into the table: the ground-truth rule, then the three bins.  scored / bad: the thread's own
 // tallies, added by score_flush
 __device__ __forceinline__ void score_pixel(uint32_t* tab, int n, int raw, int pred, int g, bool live, int& scored, int& bad) {

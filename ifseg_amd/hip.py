@@ -1316,6 +1316,36 @@ def seg_confusion(labels, gt, n, raw_labels=True, confusion=None):
     return confusion
 
 
+# the limits of seg_boundary_kernel (csrc/boundary.hip)
+SEG_BOUNDARY_MAX_D = 64             # == SEG_BOUNDARY_MAX_D there: the band's half width at most, 2 % of a 3200-pixel diagonal
+
+
+def seg_boundary_limits():
+    """-> (the largest d, the largest n) as the loaded library states them (`ifseg_seg_boundary_limit`): SEG_BOUNDARY_MAX_D and
+    SEG_PREDICT_MAX_CLASSES, which the tests hold against it"""
+    return tuple(int(lib().ifseg_seg_boundary_limit(c_int(k))) for k in range(2))
+
+
+def seg_boundary_areas(labels, gt, n, d, raw_labels=True, bareas=None, band=False):
+    """labels uint8 / int16 [B, h, w] or [h, w] (predicted classes), gt uint8 / int16 of the same shape, d an int in 1 ..
+    SEG_BOUNDARY_MAX_D -> (bareas int64 [3, n], band uint8 of the maps' shape | None): Boundary IoU's band areas, `seg_areas`'
+    three counters restricted to the pixels within d of a contour of the ground truth / of the labels / of both, and with
+    `band` the two bands themselves, bit 0 the ground truth's and bit 1 the labels', for every pixel (csrc/boundary.hip;
+    `predict.boundary_areas_reference` is the specification and states the rule).  `bareas` given: ACCUMULATED into, else fresh
+    zeros.  One launch, nothing else allocated."""
+    _label_pair(labels, gt, n)
+    assert labels.dim() in (2, 3), tuple(labels.shape)
+    assert isinstance(d, int) and not isinstance(d, bool) and 1 <= d <= SEG_BOUNDARY_MAX_D, d
+    bareas = _counter(bareas, (3, n), labels.device)
+    out = torch.empty(labels.shape, dtype=torch.uint8, device=labels.device) if band else None
+    B = labels.shape[0] if labels.dim() == 3 else 1
+    h, w = labels.shape[-2:]
+    _check(lib().ifseg_seg_boundary_areas(_ptr(labels), c_int(labels.element_size()), _ptr(gt), c_int(gt.element_size()), c_int(B),
+                                          c_int(h), c_int(w), c_int(n), c_int(d), c_int(1 if raw_labels else 0), _ptr(bareas),
+                                          _ptr(out), _stream()), "seg_boundary_areas")
+    return bareas, out
+
+
 def seg_score(scores, hp, wp, gt, raw_labels=True, labels=False, conf=False, probs=False, areas=None, tally=None,
               staging_bytes=None, label_dtype=None):
     """`seg_predict` at gt's own [B, h, w] with the scoring in the kernel's epilogue: -> (areas, tally, labels | None,

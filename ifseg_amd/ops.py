@@ -23,7 +23,7 @@ online-hard-example sampler that makes that weight plane; a constant of the step
 `seg_predict` (csrc/predict.hip: label maps at image resolution), `seg_predict_views` (the same from the mean of K views of
 differing grids, mirrored ones included: multi-scale + flip inference), `seg_areas` / `seg_score_views` (label maps counted
 against ground truth, stand-alone and in the predict kernel's epilogue: mIoU on the device), `seg_confusion` (the class
-confusion matrix of a label map against ground truth, [n, n + 1] with an "outside" column), `image_load` (csrc/imgload.hip: raw uint8 images to
+confusion matrix of a label map against ground truth, [n, n + 1] with an "outside" column), `seg_boundary_areas` (csrc/boundary.hip: Boundary IoU's band areas and the two bands), `image_load` (csrc/imgload.hip: raw uint8 images to
 normalised patch_images, the reference's evaluation transform) and the three ops of sliding-window inference (`image_load_windows`,
 `seg_predict_windows`, `seg_score_windows`: the window batch written directly, and the windows' scores merged into one label
 map in one launch), `seg_render` (csrc/render.hip: the label map coloured over its image, with class contours), `seg_conf_hist` / `seg_pseudo`
@@ -935,6 +935,36 @@ def seg_confusion(labels: torch.Tensor, gt: torch.Tensor, n: int, raw_labels: bo
 def _(labels, gt, n, raw_labels):
     _seg_areas_check(labels, gt, n, "ifseg::seg_confusion")
     return labels.new_empty((n, n + 1), dtype=torch.int64)
+
+
+# ----------------------------------------------------------------------------------------------- seg_boundary_areas
+def _seg_boundary_check(labels, gt, n, d):
+    op = "ifseg::seg_boundary_areas"
+    _seg_areas_check(labels, gt, n, op)
+    if labels.dim() not in (2, 3):
+        raise ValueError("%s: the maps must be [B, h, w] or [h, w], got %s" % (op, tuple(labels.shape)))
+    if d < 1 or d > hip.SEG_BOUNDARY_MAX_D:
+        raise ValueError("%s: d = %d, the band's half width must be in 1 .. SEG_BOUNDARY_MAX_D = %d" % (op, d, hip.SEG_BOUNDARY_MAX_D))
+
+
+@custom_op("ifseg::seg_boundary_areas", mutates_args=(), device_types="cuda")
+def seg_boundary_areas(labels: torch.Tensor, gt: torch.Tensor, n: int, d: int, raw_labels: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """predicted labels (uint8 / int16) against ground truth (uint8 / int16), both [B, h, w] or [h, w] (csrc/boundary.hip) ->
+    (bareas int64 [3, n] = `seg_areas`' counters over the scored pixels within d of a contour of both maps / the labels / the
+    ground truth, band uint8 of the maps' shape = bit 0 in the ground truth's band, bit 1 in the labels'), fresh tensors;
+    `ifseg_amd.predict.boundary_areas_reference` is the specification.  Integer inputs: not differentiable."""
+    _seg_boundary_check(labels, gt, n, d)
+    prev = _stream_scope(labels)
+    try:
+        return hip.seg_boundary_areas(labels.contiguous(), gt.contiguous(), n, d, raw_labels, band=True)
+    finally:
+        hip.set_stream(prev)
+
+
+@seg_boundary_areas.register_fake
+def _(labels, gt, n, d, raw_labels):
+    _seg_boundary_check(labels, gt, n, d)
+    return labels.new_empty((3, n), dtype=torch.int64), labels.new_empty(labels.shape, dtype=torch.uint8)
 
 
 # ----------------------------------------------------------------------------------------------- seg_score_views

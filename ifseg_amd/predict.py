@@ -68,6 +68,16 @@ writes its label map and one launch of `hip.seg_confusion` per image counts the 
     score.merged(class_to_super_category).summary()    # the same evaluation under a coarser label set, no second pass
     score.group_summary({"seen": seen_ids, "unseen": unseen_ids})   # per-group mIoU / mAcc and hIoU (needs `areas` only)
 
+Whether the contours are in the right place: `seg.evaluate_raw(..., boundary_iou=True)` also fills `score.boundary`, int64
+[3, n]: Boundary IoU's band areas (Cheng et al., CVPR 2021), the three rows of `areas` restricted to the pixels within d of a
+contour of both maps / the labels / the ground truth, d = `boundary_distance(H_i, W_i)` = 2 % of the image's diagonal.  As for
+the matrix, the scoring launch writes its label map and one launch of `hip.seg_boundary_areas` (csrc/boundary.hip) per image
+counts it, behind `hip.seg_confusion` where both are asked for, in every setting above; `summary()` then carries "mBIoU" and
+"BIoU".  `boundary_areas_reference` is the specification and says what is not pinned; d <= 64.
+
+    score = seg.evaluate_raw(photos, label_pngs, boundary_iou=True)                # or a ratio: boundary_iou=0.01
+    score.summary()["mBIoU"]
+
 The label map as a picture: `seg.render_raw(photos, ...)` is `segment_raw` followed by one launch of `hip.seg_render`
 (csrc/render.hip) per image, which blends the classes' colours over the original photo and draws class contours -- the demo's
 `cmap[labels]` and `image * (1 - opacity) + cmap[labels] * opacity`, without the label map leaving the device.  The rule is
@@ -94,12 +104,13 @@ How the four settings share their code: a front (`Segmenter._raw_views` without 
 view or many) runs the loads and the forwards and hands back one `_Merge` per image -- the setting's last launch, as its
 `hip.seg_predict*` and its `hip.seg_score*`, bound to the image's scores and geometry.  `Segmenter._label` finishes an image
 from its merge (the predict launch, then the CRF) and `Segmenter._count` scores it (the scoring launch; with the CRF on
-`_label` and `hip.seg_areas`; `hip.seg_confusion` behind either); `__call__` and `evaluate` go through the same two with the
+`_label` and `hip.seg_areas`; `hip.seg_confusion` and `hip.seg_boundary_areas` behind either); `__call__` and `evaluate` go through the same two with the
 single-view merge of their batch.
 
 Nothing in the call synchronises with the host; `labels`, `conf` and `probs` stay on the device.  There is no CPU fallback:
 `upsample_argmax_reference` is the specification the tests compare against, not a second implementation of the path.
 """
+import math
 from typing import Callable, NamedTuple, Optional
 
 import torch
@@ -222,8 +233,15 @@ def areas_reference(labels, gt, n, raw_labels=True):
 
 
 def _scored_pixels(what, labels, gt, n, raw_labels):
-    """the ground-truth rule of `areas_reference`, its one statement -> (the predicted labels and the classes of the scored
-    pixels, int64 [tally[0]] each, and tally)"""
+    """the ground-truth rule of `areas_reference` -> (the predicted labels and the classes of the scored pixels, int64
+    [tally[0]] each, and tally)"""
+    pred, cls, scored, tally = _scored_mask(what, labels, gt, n, raw_labels)
+    return pred[scored], cls[scored], tally
+
+
+def _scored_mask(what, labels, gt, n, raw_labels):
+    """the ground-truth rule of `areas_reference`, its one statement -> (the predicted labels and the classes of ALL pixels,
+    int64 [pixels] each, which of them are scored, bool [pixels], and tally)"""
     labels, gt = torch.as_tensor(labels), torch.as_tensor(gt)
     if gt.dtype not in (torch.uint8, torch.int16):
         raise ValueError("%s: ground truth must be uint8 or int16, got %s" % (what, gt.dtype))
@@ -236,7 +254,7 @@ def _scored_pixels(what, labels, gt, n, raw_labels):
     in_range = (cls >= 0) & (cls < n)
     scored = ~ignored & in_range
     tally = torch.stack([scored.sum(), (~ignored & ~in_range).sum()])
-    return pred[scored], cls[scored], tally
+    return pred, cls, scored, tally
 
 
 def confusion_reference(labels, gt, n, raw_labels=True):
@@ -248,6 +266,59 @@ def confusion_reference(labels, gt, n, raw_labels=True):
     pred, cls, _ = _scored_pixels("confusion_reference", labels, gt, n, raw_labels)
     col = torch.where((pred >= 0) & (pred < n), pred, torch.full_like(pred, n))
     return torch.bincount(cls * (n + 1) + col, minlength=n * (n + 1)).reshape(n, n + 1)
+
+
+def boundary_distance(h, w, ratio=0.02):
+    """The half width of Boundary IoU's band for an h x w image: `ratio` of the diagonal, rounded, 1 at least -- upstream's
+    line in `mask_to_boundary`.  Evaluated on the host in float64; the kernel only ever sees the integer."""
+    return max(1, int(round(ratio * math.sqrt(h * h + w * w))))
+
+
+def _in_band(v, d):
+    """v int64 [N, h, w] -> bool [N, h, w]: some position within |dx| <= d and |dy| <= d lies outside the image or carries
+    another value.  Separable: the window's minimum and maximum inside the image (a row pass, then a column pass; the pooling's
+    padding is -inf, so positions outside the image take no part) differ, or the window leaves the image."""
+    h, w = v.shape[-2:]
+    f = v.double()[:, None]                       # exact up to 2^53
+
+    def window_max(t):
+        return F.max_pool2d(F.max_pool2d(t, (1, 2 * d + 1), 1, (0, d)), (2 * d + 1, 1), 1, (d, 0))
+
+    differs = (window_max(f) != -window_max(-f))[:, 0]
+    y, x = torch.arange(h, device=v.device)[:, None], torch.arange(w, device=v.device)[None, :]
+    return differs | (y < d) | (y >= h - d) | (x < d) | (x >= w - d)
+
+
+def boundary_areas_reference(labels, gt, n, d, raw_labels=True):
+    """Specification of Boundary IoU's counters (hip.seg_boundary_areas; Cheng et al., CVPR 2021, in its semantic-segmentation
+    form, per-class band areas summed over the data set): labels and gt [..., h, w] as in `areas_reference`, whose ground-truth
+    rule and set of scored pixels these are; d an int >= 1 -> (bareas int64 [3, n], band uint8 of the maps' shape).
+
+    A pixel p of a map is in the band of that map iff some position q with |dx| <= d and |dy| <= d either lies outside the
+    image or carries a different value than p.  Values are compared as they are: the ground truth's raw values, so an ignore
+    value is a value of its own, and the labels, so a label outside [0, n) is a value of its own.  That is upstream's
+    `mask_to_boundary` (a zero border, d iterations of a 3 x 3 erosion, mask - eroded) applied to every class mask at once.
+    Over the scored pixels only: bareas[2][c] = #(gt class c and in the gt band), bareas[1][c] = #(pred = c and in the pred
+    band), bareas[0][c] = #(gt class = pred = c and in both bands); a predicted label outside [0, n) is in no bin of rows 0
+    and 1.  band: bit 0 = in the gt band, bit 1 = in the pred band, for EVERY pixel, scored or not.  With d >= max(h, w)
+    every pixel is in both bands and bareas is `areas_reference`'s areas.
+
+    NOT pinned: upstream's code (`boundary_iou`, on `cv2`) is not available where this is tested, and its handling of ignore
+    labels is not reproduced from it; the rule above is this project's statement, held against a literal transcription of
+    `mask_to_boundary` class by class.  Runs on any device."""
+    if not isinstance(d, int) or isinstance(d, bool) or d < 1:
+        raise ValueError("boundary_areas_reference: d must be an int >= 1 (the band's half width in pixels), got %r" % (d,))
+    pred, cls, scored, _ = _scored_mask("boundary_areas_reference", labels, gt, n, raw_labels)
+    shape = torch.as_tensor(gt).shape
+    if len(shape) < 2:
+        raise ValueError("boundary_areas_reference: the maps must be [..., h, w], got %s" % (tuple(shape),))
+    maps = (-1,) + tuple(shape[-2:])
+    gb = _in_band(torch.as_tensor(gt).to(pred.device).long().reshape(maps), d).reshape(-1)
+    pb = _in_band(pred.reshape(maps), d).reshape(-1)
+    known = scored & (pred >= 0) & (pred < n)
+    bareas = torch.stack([torch.bincount(pred[known & (pred == cls) & gb & pb], minlength=n),
+                          torch.bincount(pred[known & pb], minlength=n), torch.bincount(cls[scored & gb], minlength=n)])
+    return bareas, (gb.to(torch.uint8) | (pb.to(torch.uint8) << 1)).reshape(shape)
 
 
 class RenderResult(NamedTuple):
@@ -266,6 +337,14 @@ def default_palette(n):
         for c in range(3):
             rgb[:, c] |= ((idx >> (3 * j + c)) & 1) << (7 - j)
     return rgb.to(torch.uint8)
+
+
+def _boundary_ratio(what, ratio):
+    """the share of the diagonal that Boundary IoU's band is wide, checked -> float"""
+    if isinstance(ratio, bool) or not isinstance(ratio, (int, float)) or not 0.0 < ratio < 1.0:
+        raise ValueError("%s: the boundary ratio must be a number in (0, 1), the band's half width as a share of the image "
+                         "diagonal, got %r" % (what, ratio))
+    return float(ratio)
 
 
 def _boundary_arg(what, boundary, band="ignore band"):
@@ -487,9 +566,14 @@ class SegmentationScore:
 
     confusion: None (the default: no matrix, memory and behaviour as without the argument), True (a zeroed one) or a tensor:
     `confusion_reference`'s matrix int64 [n, n + 1] on the same device, which class is taken for which; `evaluate_raw(...,
-    confusion=True)` fills it (`hip.seg_confusion`).  `confusions`, `confusion_summary` and `merged` read it."""
+    confusion=True)` fills it (`hip.seg_confusion`).  `confusions`, `confusion_summary` and `merged` read it.
 
-    def __init__(self, n, device=None, areas=None, tally=None, confusion=None):
+    boundary: None (the default: no counters, memory and behaviour as without the argument), True (zeroed ones) or a tensor:
+    `boundary_areas_reference`'s counters int64 [3, n] on the same device, the three rows of `areas` restricted to the pixels
+    within d of a contour, d = `boundary_distance(h, w, boundary_ratio)` per image; `evaluate_raw(..., boundary_iou=True)` fills
+    them (`hip.seg_boundary_areas`), and `summary` / `group_summary` then report Boundary IoU beside IoU."""
+
+    def __init__(self, n, device=None, areas=None, tally=None, confusion=None, boundary=None, boundary_ratio=0.02):
         self.n = int(n)
         self.areas = torch.zeros(3, self.n, dtype=torch.int64, device=device) if areas is None else areas
         self.tally = torch.zeros(2, dtype=torch.int64, device=device) if tally is None else tally
@@ -508,16 +592,35 @@ class SegmentationScore:
                 raise ValueError("SegmentationScore: confusion must be None, True or int64 [%d, %d] on the device of areas, got %s"
                                  % (self.n, self.n + 1, (confusion.dtype, tuple(confusion.shape), confusion.device)
                                     if torch.is_tensor(confusion) else type(confusion)))
+        self.boundary_ratio = _boundary_ratio("SegmentationScore", boundary_ratio)
+        if boundary is None or boundary is False:
+            self.boundary = None
+        elif boundary is True:
+            self.boundary = torch.zeros(3, self.n, dtype=torch.int64, device=self.areas.device)
+        else:
+            self.boundary = boundary
+            if not torch.is_tensor(boundary) or boundary.dtype != torch.int64 or tuple(boundary.shape) != (3, self.n) \
+                    or boundary.device != self.areas.device:
+                raise ValueError("SegmentationScore: boundary must be None, True or int64 [3, %d] on the device of areas, got %s"
+                                 % (self.n, (boundary.dtype, tuple(boundary.shape), boundary.device)
+                                    if torch.is_tensor(boundary) else type(boundary)))
 
     def add_(self, other):
         if other.n != self.n:
             raise ValueError("SegmentationScore.add_: %d classes against %d" % (other.n, self.n))
         if (self.confusion is None) != (other.confusion is None):
             raise ValueError("SegmentationScore.add_: one score has a confusion matrix and the other has none")
+        if (self.boundary is None) != (other.boundary is None):
+            raise ValueError("SegmentationScore.add_: one score has boundary counters and the other has none")
+        if self.boundary is not None and self.boundary_ratio != other.boundary_ratio:
+            raise ValueError("SegmentationScore.add_: boundary counters of ratio %r against ratio %r: bands of different widths "
+                             "do not add" % (self.boundary_ratio, other.boundary_ratio))
         self.areas += other.areas.to(self.areas.device)
         self.tally += other.tally.to(self.tally.device)
         if self.confusion is not None:
             self.confusion += other.confusion.to(self.confusion.device)
+        if self.boundary is not None:
+            self.boundary += other.boundary.to(self.boundary.device)
         return self
 
     def _matrix(self, what):
@@ -552,7 +655,10 @@ class SegmentationScore:
         new id; the rows of dropped classes are removed, and predictions of a dropped class go to the outside column.  areas
         and tally[0] are rebuilt from it (the identities of `confusion_reference`), tally[1] is carried over.  By
         specification this is scoring the mapped label maps: `confusion_reference(mapping[labels], mapping[gt], m,
-        raw_labels=False)` with -1 -> m in the ground truth.  Needs a confusion matrix (ValueError without one)."""
+        raw_labels=False)` with -1 -> m in the ground truth.  Needs a confusion matrix (ValueError without one).
+        The new score carries NO boundary counters, whether this one does or not: merging classes erases the contours between
+        them, so the band areas of a coarser label set do not follow from the finer one's (they need a second pass over the
+        mapped label maps)."""
         C = self._matrix("merged")
         mp = torch.as_tensor(mapping).reshape(-1)
         if mp.dtype.is_floating_point or mp.dtype == torch.bool or mp.numel() != self.n:
@@ -570,7 +676,8 @@ class SegmentationScore:
 
     def group_summary(self, groups):
         """groups: {name: class ids} (seen / unseen, things / stuff) -> {name: {"mIoU", "mAcc"}, ..., "hIoU"}: per group the nanmean
-        of `summary()`'s per-class IoU / Acc over the group's classes, unrounded, then rounded to 4 digits as `summary()` does;
+        of `summary()`'s per-class IoU / Acc over the group's classes, unrounded, then rounded to 4 digits as `summary()` does
+        (and "mBIoU", the same of the per-class Boundary IoU, where the score carries boundary counters);
         hIoU is the harmonic mean of the groups' mIoU, the seen / unseen figure of zero-shot segmentation tables (0 where a
         group's mIoU is 0, NaN where a group has no class with pixels).  Needs `areas` only; one host round trip; ground
         truth out of range is `summary()`'s IndexError."""
@@ -582,13 +689,19 @@ class SegmentationScore:
                 raise ValueError("SegmentationScore.group_summary: group %r must hold class ids in [0, %d) (and not be named "
                                  "'hIoU'), got %s" % (name, self.n, c.tolist()))
             ids.append(c)
-        flat = torch.cat([self.areas.reshape(-1), self.tally]).cpu()
-        self._refuse_out_of_range(int(flat[-1]))
+        counters = [self.areas.reshape(-1), self.tally] + ([] if self.boundary is None else [self.boundary.reshape(-1)])
+        flat = torch.cat(counters).cpu()
+        self._refuse_out_of_range(int(flat[3 * self.n + 1]))
         a = flat[:3 * self.n].reshape(3, self.n).double()
         iou, acc = a[0] / (a[1] + a[2] - a[0]), a[0] / a[2]
         r4 = lambda v: round(float(v), 4)
         mious = [torch.nanmean(iou[c]) for c in ids]
         out = {name: {"mIoU": r4(mi), "mAcc": r4(torch.nanmean(acc[c]))} for name, c, mi in zip(names, ids, mious)}
+        if self.boundary is not None:
+            b = flat[3 * self.n + 2:].reshape(3, self.n).double()
+            biou = b[0] / (b[1] + b[2] - b[0])
+            for name, c in zip(names, ids):
+                out[name]["mBIoU"] = r4(torch.nanmean(biou[c]))
         mi = torch.stack(mious)
         out["hIoU"] = r4(0.0 if bool((mi == 0).any()) else len(names) / (1.0 / mi).sum())
         return out
@@ -609,16 +722,25 @@ class SegmentationScore:
         """-> {"aAcc", "mIoU", "mAcc", "IoU": [n], "Acc": [n], "pixels"} by `SegCriterion.reduce_metrics`' formulas and rounding
         (nanmean over the classes, round(..., 4)).  The one place that synchronises with the host.  Ground truth out of range
         is an IndexError: the reference's F.cross_entropy fails on such a label, and a score that left pixels out is not
-        reported as if it had not."""
+        reported as if it had not.  A score with boundary counters b also gives "mBIoU" and "BIoU": [n], Boundary IoU =
+        b[0] / (b[1] + b[2] - b[0]) per class, with the same nanmean and rounding, in the same round trip."""
         m, n = self.logging_output(), self.n
         ai, ap, al, au = m["area_intersect"], m["area_pred_label"], m["area_label"], m["area_union"]
         iou, acc = ai / au, ai / al
-        flat = torch.cat([torch.stack([ai.sum() / ap.sum(), torch.nanmean(iou), torch.nanmean(acc)]), iou, acc,
-                          self.tally.double()]).tolist()
-        self._refuse_out_of_range(flat[-1])
+        parts = [torch.stack([ai.sum() / ap.sum(), torch.nanmean(iou), torch.nanmean(acc)]), iou, acc, self.tally.double()]
+        if self.boundary is not None:
+            b = self.boundary.double()
+            biou = b[0] / (b[1] + b[2] - b[0])
+            parts += [torch.nanmean(biou)[None], biou]
+        flat = torch.cat(parts).tolist()
+        self._refuse_out_of_range(flat[3 + 2 * n + 1])
         r4 = lambda v: round(float(v), 4)
-        return {"aAcc": r4(flat[0]), "mIoU": r4(flat[1]), "mAcc": r4(flat[2]), "IoU": [r4(v) for v in flat[3:3 + n]],
-                "Acc": [r4(v) for v in flat[3 + n:3 + 2 * n]], "pixels": int(flat[-2])}
+        out = {"aAcc": r4(flat[0]), "mIoU": r4(flat[1]), "mAcc": r4(flat[2]), "IoU": [r4(v) for v in flat[3:3 + n]],
+               "Acc": [r4(v) for v in flat[3 + n:3 + 2 * n]], "pixels": int(flat[3 + 2 * n])}
+        if self.boundary is not None:
+            out["mBIoU"] = r4(flat[5 + 2 * n])
+            out["BIoU"] = [r4(v) for v in flat[6 + 2 * n:6 + 3 * n]]
+        return out
 
 
 def source_tokens(category_token_ids, prompt_ids=PROMPT_IDS, num_seg_tokens=None):
@@ -1073,38 +1195,64 @@ class Segmenter:
         return out
 
     # -- scoring against ground truth -----------------------------------------------------
-    def _score_into(self, what, into, dev, confusion=False):
+    def _score_into(self, what, into, dev, confusion=False, boundary_iou=False, shapes=()):
+        """the score a scoring call adds to, its arguments checked before anything is launched.  shapes: the (h, w) of the
+        ground-truth maps, in order: with boundary counters, each one's band must fit the kernel"""
         if not isinstance(confusion, bool):
             raise ValueError("Segmenter.%s: confusion must be True or False (a matrix to add to goes in with `into`), got %s"
                              % (what, type(confusion)))
+        ratio = None
+        if boundary_iou is not False:
+            ratio = 0.02 if boundary_iou is True else _boundary_ratio("Segmenter.%s: boundary_iou is True, False or a ratio" % what,
+                                                                      boundary_iou)
         if into is None:
-            return SegmentationScore(self.n, dev, confusion=confusion)
-        if not isinstance(into, SegmentationScore) or into.n != self.n or into.areas.device != dev:
-            raise ValueError("Segmenter.%s: into must be a SegmentationScore of %d classes on %s" % (what, self.n, dev))
-        if confusion and into.confusion is None:
-            raise ValueError("Segmenter.%s: confusion=True, but `into` carries no confusion matrix (SegmentationScore(n, device, "
-                             "confusion=True))" % what)
-        return into
+            score = SegmentationScore(self.n, dev, confusion=confusion, boundary=ratio is not None,
+                                      boundary_ratio=0.02 if ratio is None else ratio)
+        else:
+            if not isinstance(into, SegmentationScore) or into.n != self.n or into.areas.device != dev:
+                raise ValueError("Segmenter.%s: into must be a SegmentationScore of %d classes on %s" % (what, self.n, dev))
+            if confusion and into.confusion is None:
+                raise ValueError("Segmenter.%s: confusion=True, but `into` carries no confusion matrix (SegmentationScore(n, device, "
+                                 "confusion=True))" % what)
+            if ratio is not None and into.boundary is None:
+                raise ValueError("Segmenter.%s: boundary_iou=%r, but `into` carries no boundary counters (SegmentationScore(n, "
+                                 "device, boundary=True))" % (what, boundary_iou))
+            if ratio is not None and into.boundary_ratio != ratio:
+                raise ValueError("Segmenter.%s: boundary_iou asks for a band of ratio %r, `into` counts bands of ratio %r"
+                                 % (what, ratio, into.boundary_ratio))
+            score = into
+        if score.boundary is not None:
+            for i, (h, w) in enumerate(shapes):
+                d = boundary_distance(h, w, score.boundary_ratio)
+                if d > hip.SEG_BOUNDARY_MAX_D:
+                    raise ValueError("Segmenter.%s: image %d (%d x %d) has a boundary band of d = %d pixels at ratio %r, "
+                                     "hip.seg_boundary_areas takes 1 .. %d" % (what, i, h, w, d, score.boundary_ratio,
+                                                                               hip.SEG_BOUNDARY_MAX_D))
+        return score
 
     def _count(self, score, merge, gt, raw_labels, rgb, return_labels):
         """The scoring step of `evaluate_raw` / `evaluate`: one image's (or batch's) merge against gt [B, h, w] into `score` -> its
         labels [B, h, w] or None.  The epilogue of the merge's scoring launch adds to the counters.  With the CRF on, the label
         map comes from the CRF (`_label`; rgb: its images), not from the predict kernel, and `hip.seg_areas` counts it.  Where
         the score carries a confusion matrix, the launch is asked for its label map and `hip.seg_confusion` counts the pairs
-        of the same labels behind it on the same stream."""
+        of the same labels behind it on the same stream; where it carries boundary counters, likewise, and
+        `hip.seg_boundary_areas` counts the band areas of the same labels with d = `boundary_distance` of gt's size."""
         kw = dict(raw_labels=raw_labels, areas=score.areas, tally=score.tally)
-        pairs = score.confusion is not None
+        pairs, bands = score.confusion is not None, score.boundary is not None
         if self.crf_iters > 0:
             labels = self._label(merge, int(gt.shape[1]), int(gt.shape[2]), rgb, False, False).labels.contiguous()
             hip.seg_areas(labels, gt, self.n, **kw)
         else:
-            labels = merge.score(gt, labels=return_labels or pairs, label_dtype=self.label_dtype, **kw)[2]
+            labels = merge.score(gt, labels=return_labels or pairs or bands, label_dtype=self.label_dtype, **kw)[2]
         if pairs:
             hip.seg_confusion(labels, gt, self.n, raw_labels, confusion=score.confusion)
+        if bands:
+            hip.seg_boundary_areas(labels, gt, self.n, boundary_distance(int(gt.shape[1]), int(gt.shape[2]), score.boundary_ratio),
+                                   raw_labels, bareas=score.boundary)
         return labels if return_labels else None
 
     def evaluate_raw(self, images, label_maps, raw_labels=True, scales=(1.0,), flip=False, max_batch=8, mean=None, std=None,
-                     reverse_channels=False, into=None, return_labels=False, slide=None, confusion=False):
+                     reverse_channels=False, into=None, return_labels=False, slide=None, confusion=False, boundary_iou=False):
         """`segment_raw` scored against ground truth on the device -> a `SegmentationScore` (or (score, [labels [H_i, W_i], ...])
         with `return_labels`, the labels being `segment_raw`'s).
 
@@ -1123,7 +1271,16 @@ class Segmenter:
         scoring launch then writes its label map and one launch of `hip.seg_confusion` per image counts the pairs of the same
         labels on the same stream; areas / tally still come from the epilogue and are bit for bit what they are without it,
         and no host synchronisation is added.  confusion=True with an `into` that has no matrix is a ValueError before
-        anything is launched."""
+        anything is launched.
+        boundary_iou: True (a band of 2 % of the image diagonal), a ratio in (0, 1), or an `into` that carries boundary
+        counters: the score also counts Boundary IoU's band areas (`SegmentationScore.boundary`, int64 [3, n];
+        `boundary_areas_reference` is the specification), and `summary()` gains "mBIoU" and "BIoU".  As with the matrix, the
+        scoring launch writes its label map and one launch of `hip.seg_boundary_areas` per image counts the same labels (the
+        CRF's with the CRF on) on the same stream, with d = `boundary_distance(H_i, W_i, ratio)`: the band is measured at the
+        ground truth's resolution, the image's own.  areas, tally, the matrix and the labels are bit for bit what they are
+        without it, no host synchronisation is added, and a call without it makes the launches it always made.  A ValueError
+        before anything is launched: a ratio other than `into`'s, `into` without the counters, an image whose d passes
+        `hip.SEG_BOUNDARY_MAX_D` = 64 (a diagonal above 3200 pixels at 2 %)."""
         sl = self._check_slide("evaluate_raw", slide, scales, flip)
         checked = self._check_raw("evaluate_raw", images, scales, flip, sl)
         plan = self._plan_slide(checked, sl, max_batch)
@@ -1136,7 +1293,7 @@ class Segmenter:
                 raise ValueError("Segmenter.evaluate_raw: label map %d must be a uint8 or int16 tensor of its image's shape %s, got %s"
                                  % (i, tuple(im.shape[:2]), (g.dtype, tuple(g.shape)) if torch.is_tensor(g) else type(g)))
         dev = next(self.model.parameters()).device
-        score = self._score_into("evaluate_raw", into, dev, confusion)
+        score = self._score_into("evaluate_raw", into, dev, confusion, boundary_iou, [tuple(g.shape) for g in gts])
         if checked is None:
             return (score, []) if return_labels else score
         gts = [g.to(dev, non_blocking=True).contiguous() for g in gts]
@@ -1148,11 +1305,12 @@ class Segmenter:
                 out.append(None if labels is None else labels[0])
         return (score, out) if return_labels else score
 
-    def evaluate(self, images, label_maps, raw_labels=True, into=None, return_labels=False, confusion=False):
+    def evaluate(self, images, label_maps, raw_labels=True, into=None, return_labels=False, confusion=False, boundary_iou=False):
         """`__call__` scored against ground truth: images as `__call__` takes them (normalised float [B, 3, H, W] or uint8 RGB
         [B, H, W, 3] / [H, W, 3]), label_maps uint8 / int16 [B, h, w] (or [h, w] for one image): the label map is taken at the
         ground truth's own size, as `out_hw` would.  -> a `SegmentationScore`, or (score, labels [B, h, w]) with `return_labels`;
-        raw_labels, into, confusion: as in `evaluate_raw`."""
+        raw_labels, into, confusion, boundary_iou: as in `evaluate_raw`; the band areas of the whole batch are one launch of
+        `hip.seg_boundary_areas`, d from the label maps' size."""
         gt = label_maps
         if not torch.is_tensor(gt) or gt.dtype not in (torch.uint8, torch.int16) or gt.dim() not in (2, 3) or gt.numel() == 0:
             raise ValueError("Segmenter.evaluate: label_maps must be a uint8 or int16 tensor [B, h, w], got %s"
@@ -1166,7 +1324,7 @@ class Segmenter:
         if crf and tuple(gt.shape[1:]) != (H, W):
             raise ValueError("Segmenter.evaluate: with the CRF on, the label maps must have the images' size %s, got %s"
                              % ((H, W), tuple(gt.shape[1:])))
-        score = self._score_into("evaluate", into, patch_images.device, confusion)
+        score = self._score_into("evaluate", into, patch_images.device, confusion, boundary_iou, [tuple(gt.shape[1:])])
         if crf and rgb is None:
             rgb = ((patch_images.float() * 0.5 + 0.5) * 255.0).permute(0, 2, 3, 1).contiguous()
         scores, hp, wp = self.patch_scores(patch_images)

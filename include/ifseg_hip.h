@@ -678,6 +678,24 @@ int ifseg_seg_confusion(const void* labels, int label_bytes, const void* gt, int
  * up to this counts in it), 1 the slots of the hashed table, 2 the pixels a workgroup takes per step, 3 the workgroups of a
  * launch at most; any other which: IFSEG_ERR_BAD_ARG. */
 int ifseg_seg_confusion_limit(int which);
+/* ifseg_seg_boundary_areas counts Boundary IoU's band areas (Cheng et al., CVPR 2021, semantic form; csrc/boundary.hip):
+ * labels and gt are [B][h][w] maps (uint8, bytes 1, or int16, 2; any element alignment).  A pixel p of a map is IN THE BAND of
+ * that map iff some position q with |dx| <= d and |dy| <= d lies outside the image or carries another value than p; values are
+ * compared as they are (an ignore value of the ground truth, a label outside [0, n) are values of their own).  The
+ * ground-truth rule and the set of scored pixels are ifseg_seg_areas'; over the scored pixels only
+ *   bareas[2][c] += #(gt class c and in the gt band)         bareas[1][c] += #(pred = c and in the pred band)
+ *   bareas[0][c] += #(gt class = pred = c and in both bands)
+ * a predicted label outside [0, n) being in no bin of rows 0 and 1.  bareas uint64 [3][n] is ADDED to and never cleared
+ * (64-bit integer atomics, one per workgroup and non-zero bin: exact and bit-reproducible).  band, where not NULL, is uint8
+ * [B][h][w] and is written for EVERY pixel, scored or not: bit 0 = in the gt band, bit 1 = in the pred band.  d >= max(h, w)
+ * puts every pixel in both bands: bareas then takes what ifseg_seg_areas adds to areas.
+ * NULL labels / gt / bareas, label_bytes or gt_bytes outside {1, 2}, an int16 map at an odd address, bareas not 8-byte
+ * aligned, n outside 1..512, d outside 1..64: IFSEG_ERR_BAD_ARG; B, h or w < 1 or B h w >= 2^31: IFSEG_ERR_BAD_SHAPE; nothing
+ * is launched on a refusal.  Nothing is allocated.  The dynamic LDS of a launch grows with d (71 488 bytes at d = 64, n = 512). */
+int ifseg_seg_boundary_areas(const void* labels, int label_bytes, const void* gt, int gt_bytes, int B, int h, int w, int n, int d,
+                             int raw_labels, void* bareas, void* band, void* stream);
+/* which = 0: the largest d, 1: the largest n; any other which: IFSEG_ERR_BAD_ARG. */
+int ifseg_seg_boundary_limit(int which);
 int ifseg_seg_score(const float* scores, int B, int hp, int wp, int n, int h, int w, void* labels, int label_bytes, float* conf,
                     float* probs, const void* gt, int gt_bytes, int raw_labels, unsigned long long* areas,
                     unsigned long long* tally, void* stream);
