@@ -19,6 +19,10 @@ states the rule.  Without them every call is the unweighted one.
 Opt-in online hard example mining: ``SegCriterion(ohem_thresh=, ohem_min_kept=)`` builds that plane on the device
 (csrc/ohem.hip: the probability of every pixel's own label, then an exact radix select over the batch);
 ``hardness_reference`` and ``ohem_reference`` state the rule.
+
+Opt-in Dice auxiliary loss: ``SegCriterion(dice_weight=, dice_smooth=, dice_class_weight=)`` adds ``dice_weight`` times the
+per-sample soft Dice loss of the same upsampled logits (csrc/dice.hip: two tile passes with a device-side reduction between
+them, one gradient); ``dice_sums_reference`` and ``dice_loss_reference`` state the rule.  Without it every call is as before.
 """
 from dataclasses import dataclass, field
 from typing import Optional
@@ -151,6 +155,16 @@ def check_ohem(thresh, min_kept=OHEM_MIN_KEPT):
     return hip.check_ohem(thresh, min_kept)
 
 
+def check_dice(dice_weight, dice_smooth=1.0):
+    """the Dice term's two numbers -> (dice_weight or None, dice_smooth).  dice_weight=None switches the term off; a number
+    > 0 switches it on; dice_smooth is a number > 0 either way (a bad one is a mistake in the configuration whether or not the
+    term is on).  Anything else: ValueError naming the keyword."""
+    smooth = hip.check_dice_number("dice_smooth", dice_smooth, "seg_criterion")
+    if dice_weight is None:
+        return None, smooth
+    return hip.check_dice_number("dice_weight", dice_weight, "seg_criterion"), smooth
+
+
 def hardness_reference(scores_up, target, seg_id_offset, nseg):
     """Specification of `hip.seg_hardness` (csrc/ohem.hip), runs on any device.  scores_up fp32 or fp64 [B, H*W (+1), n] (already
     upsampled), target int64 [B, H*W (+1)] -> [B, H*W] in the dtype of the scores: softmax(scores_up)[y], clamped to <= 1, where
@@ -206,6 +220,82 @@ def ohem_reference(hardness, thresh, min_kept, weight=None):
     return plane, torch.tensor([nv, int(keep.sum()), tau, kth], dtype=torch.int64, device=dev)
 
 
+def _dice_terms(scores_up, target, seg_id_offset, nseg, what):
+    """-> (p [B, npix, n] with zeros on the invalid pixels, onehot of the same shape and dtype): the two factors of the sums"""
+    n = int(nseg)
+    if scores_up.dim() != 3 or scores_up.shape[2] != n or not scores_up.dtype.is_floating_point:
+        raise ValueError("%s: scores_up must be floating point [B, H*W, %d], got %s %s"
+                         % (what, n, scores_up.dtype, tuple(scores_up.shape)))
+    B = scores_up.shape[0]
+    npix = min(scores_up.shape[1], target.shape[1]) if target.dim() == 2 else -1
+    if target.dtype != torch.int64 or target.dim() != 2 or target.shape[0] != B or target.shape[1] - npix not in (0, 1) \
+            or scores_up.shape[1] - npix not in (0, 1):
+        raise ValueError("%s: target must be int64 [B, H*W (+1)], got %s %s for scores %s"
+                         % (what, target.dtype, tuple(target.shape), tuple(scores_up.shape)))
+    if target.shape[1] == scores_up.shape[1] and bool((target[:, -1] == EOS).all()):
+        npix -= 1                                   # scores and target both carry the eos row
+    s = scores_up[:, :npix]
+    if s.dtype not in (torch.float32, torch.float64):
+        s = s.float()
+    tgt = target[:, :npix].to(s.device)
+    valid = (tgt >= seg_id_offset) & (tgt < seg_id_offset + n) & (tgt != PAD) & (tgt != EOS)
+    label = torch.where(valid, tgt - seg_id_offset, torch.zeros_like(tgt))
+    v = valid.unsqueeze(-1).to(s.dtype)
+    return torch.softmax(s, dim=-1) * v, F.one_hot(label, n).to(s.dtype) * v
+
+
+def dice_sums_reference(scores_up, target, seg_id_offset, nseg):
+    """Specification of `hip.seg_dice_sums` (csrc/dice.hip, pass A and the reduction), runs on any device.  scores_up fp32 or fp64
+    [B, H*W (+1), n] (already upsampled), target int64 [B, H*W (+1)] -> [B, 3, n] in the dtype of the scores.  A pixel is valid iff
+    its target is a class (seg_id_offset <= t < seg_id_offset + n and not pad / eos: the loss kernel's predicate); with
+    p_ic = softmax_c(v_i), over the valid pixels i of sample b only:
+      [b, 0, c] = I_bc = sum_i p_ic [y_i = c]     [b, 1, c] = P_bc = sum_i p_ic^2     [b, 2, c] = Y_bc = sum_i [y_i = c]
+    A trailing row that scores and target both carry and whose targets are all eos is the eos row and is left out."""
+    p, onehot = _dice_terms(scores_up.detach(), target, seg_id_offset, nseg, "dice_sums_reference")
+    return torch.stack([(p * onehot).sum(1), (p * p).sum(1), onehot.sum(1)], dim=1)
+
+
+def dice_loss_reference(scores_up, target, seg_id_offset, nseg, smooth=1.0, class_weight=None):
+    """Specification of the Dice term of the fused criterion (csrc/dice.hip; `hip.seg_dice` computes dice_weight times this and its
+    gradient), unscaled, runs on any device and dtype and is differentiable in scores_up.  Inputs as `dice_sums_reference`;
+    smooth = s > 0, class_weight fp32 / fp64 [n] >= 0 (None: ones).  With I, P, Y of `dice_sums_reference`:
+      N_bc = 2 I_bc + s       Q_bc = P_bc + Y_bc + s
+      L_dice = (1 / B) sum_b (1 / n) sum_c w_c (1 - N_bc / Q_bc)
+    This is mmseg 0.x's DiceLoss(smooth=1, exponent=2) in form -- one binary_dice_loss per class, taken per sample, averaged over
+    the batch, summed over the classes and divided by num_classes -- restated from upstream's behaviour (mmseg is no dependency:
+    the rule is not checked against its code).  Upstream applies the valid mask to the numerator only and clamps ignored labels
+    into class n - 1 in the denominator; this rule masks all three sums, so the two agree exactly only on samples without ignored
+    pixels.  mmseg 1.x's flattened variant, exponent=1 and naive_dice are not built.
+    A sample without a valid pixel has I = P = Y = 0: every class gives 1 - s / s = 0 with a zero gradient.  The sums run per
+    sample, so under data parallelism the term needs no reduction across ranks: a rank's value is the mean over its own samples.
+    Gradient in closed form (what the kernel computes), with k_c = w_c / (B n), a_bc = -2 k_c / Q_bc, e_bc = k_c N_bc / Q_bc^2:
+      g_ic = a_bc [y_i = c] + 2 p_ic e_bc on a valid pixel,  S_i = sum_k p_ik g_ik,  d L_dice / d v_ic = p_ic (g_ic - S_i)."""
+    if isinstance(smooth, bool) or not isinstance(smooth, (int, float)) or not 0 < smooth < float("inf"):
+        raise ValueError("dice_loss_reference: dice_smooth must be a finite number > 0, got %r" % (smooth,))
+    p, onehot = _dice_terms(scores_up, target, seg_id_offset, nseg, "dice_loss_reference")
+    cw = check_class_weight(class_weight, int(nseg))
+    num = 2.0 * (p * onehot).sum(1) + smooth
+    den = (p * p).sum(1) + onehot.sum(1) + smooth
+    per_class = 1.0 - num / den                                             # [B, n]
+    if cw is not None:
+        per_class = per_class * cw.to(p.device, p.dtype)
+    return per_class.sum(1).div(int(nseg)).mean()
+
+
+def dice_grad_closed_form(scores_up, target, seg_id_offset, nseg, smooth=1.0, class_weight=None):
+    """d `dice_loss_reference` / d scores_up by the closed form of its docstring (the arithmetic of csrc/dice.hip's pass B), no
+    autograd -> the shape of scores_up's pixel rows (the eos row, when carried, left out)"""
+    p, onehot = _dice_terms(scores_up.detach(), target, seg_id_offset, nseg, "dice_grad_closed_form")
+    B, n = p.shape[0], int(nseg)
+    cw = check_class_weight(class_weight, n)
+    k = (cw.to(p.device, p.dtype) if cw is not None else p.new_ones(n)) / (B * n)
+    N = 2.0 * (p * onehot).sum(1) + smooth
+    Q = (p * p).sum(1) + onehot.sum(1) + smooth
+    a, e = (-2.0 * k / Q).unsqueeze(1), (k * N / (Q * Q)).unsqueeze(1)      # [B, 1, n]
+    g = a * onehot + 2.0 * p * e                                            # zero where p and onehot are (invalid pixels)
+    return p * (g - (p * g).sum(-1, keepdim=True))
+
+
 class _FusedSegLossFn(torch.autograd.Function):
     """loss = mean CE(bilinear_x16(logits[:, :P]), target); backward hands out the gradient the
     forward kernel already produced.  pixel_weight / class_weight / norm_pixels: the weighted kernel
@@ -246,6 +336,33 @@ class _FusedSegLossFn(torch.autograd.Function):
         return (g * gloss.to(g.dtype),) + (None,) * 13
 
 
+class _FusedSegLossDiceFn(torch.autograd.Function):
+    """loss = CE + dice_weight * Dice of the same upsampled logits (`hip.seg_loss_dice`): `_FusedSegLossFn`'s CE launch, csrc/dice.hip's
+    two passes and one gather that sums both gradients.  -> (total, CE, weighted Dice, stats); only the total is differentiable."""
+
+    @staticmethod
+    def forward(ctx, logits, logits_pad, target, hp, wp, H, W, nseg, seg0, bufs, eps, pixel_weight, class_weight, norm_pixels,
+                dice_weight, dice_smooth, dice_class_weight):
+        B = logits_pad.shape[0]
+        key = (B, hp, wp, nseg, logits_pad.shape[2], logits_pad.device, "dice")
+        if bufs.get("key") != key:
+            bufs.clear()
+            bufs["key"] = key
+        loss3, dl = hip.seg_loss_dice(logits_pad, target, hp, wp, H, W, nseg, seg0, dice_weight, dice_smooth, dice_class_weight,
+                                      bufs=bufs, pixel_weight=pixel_weight, class_weight=class_weight, norm_pixels=norm_pixels,
+                                      label_smoothing=float(eps))
+        ctx.dl = dl
+        ctx.nseg = nseg
+        out = (loss3[0].clone(), loss3[1].clone(), loss3[2].clone(), bufs["stats"].clone())
+        ctx.mark_non_differentiable(*out[1:])
+        return out
+
+    @staticmethod
+    def backward(ctx, gloss, gce, gdice, gstats):
+        g = ctx.dl[:, :, : ctx.nseg]
+        return (g * gloss.to(g.dtype),) + (None,) * 16
+
+
 FUSED_MAX_CLASSES = 512      # csrc/loss.hip NS_MAX
 
 
@@ -257,7 +374,7 @@ class SegCriterion(CriterionBase):
                  criterion_update_freq=1, freeze_embedding_iter=-1, full_context_alignment="false",
                  init_seg_with_text="true", resnet_topk=3, resnet_prob_temperature=1.0, resnet_iters=0,
                  num_seg_tokens=None, seg_id_offset=None, class_weight=None, weight_norm="weights", ohem_thresh=None,
-                 ohem_min_kept=OHEM_MIN_KEPT):
+                 ohem_min_kept=OHEM_MIN_KEPT, dice_weight=None, dice_smooth=1.0, dice_class_weight=None):
         """Signature of the reference (seg_criterion.py:115-161; fairseq's `build_criterion` fills it from
         SegCriterionConfig by name).  `num_seg_tokens` / `seg_id_offset` stand in for `task.cfg.num_seg_tokens` and
         `task.target_dictionary.index("<seg_0>")` when the criterion is used without a task.  `class_weight` (n numbers >= 0,
@@ -269,7 +386,16 @@ class SegCriterion(CriterionBase):
         mean over the kept pixels, weight_norm="pixels" divides by 255 N_valid (mmseg's `avg_non_ignore=True` under a sampler).
         `self.ohem_info` holds the last call's int64 [4] on the device: valid pixels, kept pixels, the bits of tau and of the
         k-th value.  Not built: `ohem_thresh=None` with a min_kept (the loss-ranked sampler), OHEM in the image-free loss and in
-        evaluation."""
+        evaluation.
+        `dice_weight` (> 0; None: off) / `dice_smooth` (> 0) / `dice_class_weight` (n numbers >= 0), constructor keywords only:
+        mmseg's second decode loss, `DiceLoss(loss_weight=dice_weight, smooth=dice_smooth, class_weight=dice_class_weight)` --
+        `dice_loss_reference` states the rule.  The returned loss is CE + dice_weight * Dice, `metrics["nll_loss"]` stays the CE
+        term, `metrics["dice_loss"]` is the weighted Dice term and `self.dice_sums` holds the last call's fp32 [B, 3, n] on the
+        device.  Pixel weights and the OHEM plane do not enter the Dice term.  It applies wherever `compute_loss` runs.  That
+        includes the no-grad pass over the real images of image-free training (`unsupervised_segmentation`): there
+        `seg_loss`, `nll_loss` and `dice_loss` are logged monitors of the real images and nothing of them is trained, as `seg_loss`
+        and `nll_loss` always were in that mode; the trained image-free loss has no Dice term.  Not built: Dice in the image-free
+        loss and in the `ori_semantic_seg` evaluation."""
         super().__init__(task)
         self.sentence_avg = sentence_avg
         self.eps = label_smoothing
@@ -298,6 +424,11 @@ class SegCriterion(CriterionBase):
         self.weight_norm = weight_norm
         self.ohem_thresh, self.ohem_min_kept = check_ohem(ohem_thresh, ohem_min_kept)
         self.ohem_info = None
+        self.dice_weight, self.dice_smooth = check_dice(dice_weight, dice_smooth)
+        self.dice_class_weight = check_class_weight(dice_class_weight, self.num_seg)
+        if self.dice_class_weight is not None:
+            self.dice_class_weight = self.dice_class_weight.float()          # what the kernel reads
+        self.dice_sums = None
         # image-free samples drawn on the device (ifseg_amd/artificial.py).  The trainer sets the seed and, before every
         # micro-batch, the ordinal of its first sample (an int, or a device int64 word inside a captured step); without a
         # trainer the criterion counts the samples it has drawn.
@@ -455,7 +586,15 @@ class SegCriterion(CriterionBase):
                 setattr(self, bufs_name, {})
             if self.ohem_thresh is not None and model.training:
                 pw = self._ohem_plane(pad, target.contiguous(), pw, hp, wp, h, w, bufs_name + "_ohem")
-            if pw is None and self.class_weight is None:
+            dice = None
+            if self.dice_weight is not None:
+                weighted = pw is not None or self.class_weight is not None
+                loss, ce, dice, stats = _FusedSegLossDiceFn.apply(
+                    scores_low, pad, target.contiguous(), hp, wp, h, w, self.num_seg, self.seg_id_offset, getattr(self, bufs_name),
+                    self.eps, pw.contiguous() if pw is not None else None, self._class_weight_on(pad.device) if weighted else None,
+                    self.norm_pixels and weighted, self.dice_weight, self.dice_smooth, self._dice_class_weight_on(pad.device))
+                self.dice_sums = getattr(self, bufs_name)["dice_sums"]
+            elif pw is None and self.class_weight is None:
                 loss, stats = _FusedSegLossFn.apply(scores_low, pad, target.contiguous(), hp, wp, h, w, self.num_seg,
                                                     self.seg_id_offset, getattr(self, bufs_name), self.eps)
             else:
@@ -472,6 +611,8 @@ class SegCriterion(CriterionBase):
             ai, ap, al = stats[2:2 + n], stats[2 + n:2 + 2 * n], stats[2 + 2 * n:2 + 3 * n]
             metrics = {"area_intersect": ai, "area_pred_label": ap, "area_label": al, "area_union": ap + al - ai,
                        "nll_loss": loss}
+            if dice is not None:
+                metrics.update(nll_loss=ce, dice_loss=dice)
             return loss, metrics, 1
         return self.compute_loss_torch(model, net_output, sample, update_num, reduce)
 
@@ -497,6 +638,12 @@ class SegCriterion(CriterionBase):
             loss = weighted_loss_reference(scores[:, :h * w], target, self.seg_id_offset, self.num_seg,
                                            self._class_weight_on(scores.device), pw, self.eps, self.weight_norm)
         metrics["nll_loss"] = loss
+        if self.dice_weight is not None:
+            self.dice_sums = dice_sums_reference(scores[:, :h * w], target, self.seg_id_offset, self.num_seg)
+            dice = self.dice_weight * dice_loss_reference(scores[:, :h * w], target, self.seg_id_offset, self.num_seg,
+                                                          self.dice_smooth, self._dice_class_weight_on(scores.device))
+            metrics["dice_loss"] = dice
+            loss = loss + dice
         return loss, metrics, 1
 
     def _ohem_plane(self, pad, target, pw, hp, wp, h, w, name):
@@ -524,6 +671,13 @@ class SegCriterion(CriterionBase):
             cw = self.class_weight = cw.to(dev)
         return cw
 
+    def _dice_class_weight_on(self, dev):
+        """the Dice class weights on `dev` (moved there once), or None"""
+        cw = self.dice_class_weight
+        if cw is not None and cw.device != dev:
+            cw = self.dice_class_weight = cw.to(dev)
+        return cw
+
     @staticmethod
     def compute_metric(lprobs, target):
         """seg_criterion.py:349-362."""
@@ -544,6 +698,9 @@ class SegCriterion(CriterionBase):
         ss = tot("sample_size")
         out = {k: float(tot(k)) / max(float(ss), 1e-9) for k in ("loss", "imfree_loss", "seg_loss", "nll_loss")}
         out.update(ntokens=tot("ntokens"), nsentences=tot("nsentences"), sample_size=ss)
+        has_dice = any("dice_loss" in l for l in logging_outputs)             # only a criterion with dice_weight logs it
+        if has_dice:
+            out["dice_loss"] = float(tot("dice_loss")) / max(float(ss), 1e-9)
         areas = {}
         for suf in ("", "_resnet_postprocess", "_lowres"):
             if "area_intersect" + suf not in logging_outputs[0]:
@@ -559,7 +716,7 @@ class SegCriterion(CriterionBase):
             return out
         ntok = out["ntokens"]
         metrics.log_scalar("loss", out["loss"], ss, round=3)
-        for k in ("imfree_loss", "seg_loss", "nll_loss"):
+        for k in ("imfree_loss", "seg_loss", "nll_loss") + (("dice_loss",) if has_dice else ()):
             metrics.log_scalar(k, out[k], ntok, round=3)
         for k in ("ntokens", "nsentences", "sample_size"):
             metrics.log_scalar(k, out[k], 1, round=3)

@@ -1085,6 +1085,151 @@ def ohem_select(hardness, thresh, min_kept, weight=None, out=None, info=None, wo
     return out, info
 
 
+# ---------------------------------------------------------------------- per-sample soft Dice
+def check_dice_number(name, v, what="dice"):
+    """a finite number > 0 (ValueError naming `name` otherwise) -> float"""
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 < v < float("inf"):
+        raise ValueError("%s: %s must be a finite number > 0, got %r" % (what, name, v))
+    return float(v)
+
+
+def check_dice(dice_weight, smooth, what="dice"):
+    """dice_weight > 0 and smooth > 0, both finite numbers (ValueError otherwise) -> (float, float)"""
+    return check_dice_number("dice_weight", dice_weight, what), check_dice_number("dice_smooth", smooth, what)
+
+
+def _dice_geometry(logits_pad, target, hp, wp, H, W, nseg):
+    assert logits_pad.dtype == torch.bfloat16 and logits_pad.dim() == 3 and logits_pad.stride(2) == 1 and logits_pad.is_cuda \
+        and logits_pad.shape[1] >= hp * wp and logits_pad.stride(1) >= nseg, (logits_pad.dtype, tuple(logits_pad.shape), logits_pad.stride())
+    B, dev = logits_pad.shape[0], logits_pad.device
+    assert target.dtype == torch.int64 and target.dim() == 2 and target.shape[0] == B and target.shape[1] >= H * W \
+        and target.stride(1) == 1 and target.device == dev, (target.dtype, tuple(target.shape), target.stride(), target.device)
+    assert B >= 1 and hp >= 1 and wp >= 1 and H == 16 * hp and W == 16 * wp and 1 <= nseg <= 512, (B, hp, wp, H, W, nseg)
+    return B, dev
+
+
+def _dice_bufs(bufs, logits_pad, target, B, hp, wp, nseg, names):
+    """the buffers `names` of a Dice call in `bufs` (a dict the caller keeps): made on the first call, checked on every call"""
+    dev, tiles, f32 = logits_pad.device, B * hp * wp, torch.float32
+    shapes = {"dice_part": ((tiles * 3 * nseg,), f32), "dice_sums": ((B, 3, nseg), f32), "dice_tile": ((tiles * 9 * nseg,), f32),
+              "dice_val": ((1,), f32), "loss3": ((3,), f32), "dl": (None, torch.bfloat16),
+              "tile": ((tiles * 9 * nseg,), f32), "sp": ((tiles * (2 + 3 * nseg),), f32), "stats": ((2 + 3 * nseg,), f32),
+              "bad": ((1,), torch.int32)}
+    for k in names:
+        shape, dt = shapes[k]
+        if k == "dl":
+            # the gradient has a layout of its own, whatever the logits' (a row-strided view [B, P+1, nseg] of a padded buffer
+            # included): the gather writes whole rows of stride(1) elements, hp * wp + 1 of them per sample
+            if k not in bufs:
+                bufs[k] = torch.empty(B, hp * wp + 1, logits_pad.stride(1), dtype=dt, device=dev)
+            t = bufs[k]
+            assert t.dtype == dt and t.device == dev and t.dim() == 3 and t.shape[0] == B and t.shape[1] == hp * wp + 1 \
+                and t.stride(2) == 1 and t.stride(1) == t.shape[2] >= nseg and (B == 1 or t.stride(0) >= t.shape[1] * t.stride(1)), \
+                (k, t.dtype, tuple(t.shape), t.stride(), t.device)
+        else:
+            if k not in bufs:
+                bufs[k] = (torch.zeros if k == "bad" else torch.empty)(shape, dtype=dt, device=dev)
+            t = bufs[k]
+            assert t.dtype == dt and tuple(t.shape) == shape and t.device == dev and t.is_contiguous(), \
+                (k, t.dtype, tuple(t.shape), t.stride(), t.device)
+        assert not _overlap(t, logits_pad) and not _overlap(t, target), "dice: buffer %r overlaps the logits or the target" % k
+    held = [bufs[k] for k in names]
+    assert not any(_overlap(a, b) for i, a in enumerate(held) for b in held[i + 1:]), "dice: two buffers overlap"
+    return bufs
+
+
+def _dice_tile_args(logits_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, pad_id, eos_id):
+    ld = logits_pad.stride(1)
+    return (_ptr(logits_pad), c_int(ld), c_ll(logits_pad.stride(0) if B > 1 else hp * wp * ld), _ptr(target),
+            c_ll(target.stride(0) if B > 1 else H * W), c_int(B), c_int(hp), c_int(wp), c_int(H), c_int(W), c_int(nseg),
+            c_ll(seg_id_offset), c_ll(pad_id), c_ll(eos_id))
+
+
+def seg_dice_sums(logits_pad, target, hp, wp, H, W, nseg, seg_id_offset, bufs=None, pad_id=1, eos_id=2):
+    """logits_pad bf16 [B, P+1, ldl], target int64 [B, H*W (+1)] -> fp32 [B, 3, nseg] in two launches (csrc/dice.hip pass A, then
+    `reduce_parts` over a sample's tiles, a fixed order): per sample and class I = sum p [y = c], P = sum p^2, Y = sum [y = c] over
+    the valid pixels (`seg_loss`'s predicate), p the softmax of the x16 bilinear upsample.
+    `criterions.seg_criterion.dice_sums_reference` is the specification.  bufs: a dict the caller keeps between calls (the result
+    is bufs["dice_sums"]); nothing is allocated after the first call with it."""
+    B, dev = _dice_geometry(logits_pad, target, hp, wp, H, W, nseg)
+    bufs = _dice_bufs({} if bufs is None else bufs, logits_pad, target, B, hp, wp, nseg, ("dice_part", "dice_sums"))
+    _check(lib().ifseg_seg_dice_sums(*_dice_tile_args(logits_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, pad_id, eos_id),
+                                     _ptr(bufs["dice_part"]), _stream()), "seg_dice_sums")
+    reduce_parts(bufs["dice_part"], bufs["dice_sums"], B, hp * wp, 3 * nseg)
+    return bufs["dice_sums"]
+
+
+def _dice_class_weight(class_weight, nseg, dev):
+    if class_weight is not None:
+        assert class_weight.dtype == torch.float32 and tuple(class_weight.shape) == (nseg,) and class_weight.is_contiguous() \
+            and class_weight.device == dev, (class_weight.dtype, tuple(class_weight.shape), class_weight.device)
+    return class_weight
+
+
+def _dice_tiles(logits_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, dice_weight, smooth, class_weight, bufs, pad_id, eos_id):
+    """pass A, the reduction and pass B into bufs["dice_sums"], bufs["dice_tile"], bufs["dice_val"]"""
+    seg_dice_sums(logits_pad, target, hp, wp, H, W, nseg, seg_id_offset, bufs, pad_id, eos_id)
+    _check(lib().ifseg_seg_dice_tiles(*_dice_tile_args(logits_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, pad_id, eos_id),
+                                      _ptr(bufs["dice_sums"]), _ptr(class_weight), c_float(dice_weight), c_float(smooth),
+                                      _ptr(bufs["dice_tile"]), _ptr(bufs["dice_val"]), _stream()), "seg_dice_tiles")
+
+
+def seg_dice(logits_pad, target, hp, wp, H, W, nseg, seg_id_offset, dice_weight, smooth=1.0, class_weight=None, bufs=None,
+             pad_id=1, eos_id=2):
+    """Dice alone (csrc/dice.hip): sums -> reduce -> tiles -> gather, four launches, nothing read back, no atomics.
+    -> (loss fp32 [] = dice_weight * `criterions.seg_criterion.dice_loss_reference`, dlogits_pad bf16 [B, hp*wp+1, ld >= nseg] = its
+    gradient, padding columns and the eos row zero).  class_weight fp32 [nseg] (non-negative and finite: the caller's duty) or
+    None.  bufs as `seg_dice_sums` (loss is bufs["loss3"][0], the gradient bufs["dl"], the sums bufs["dice_sums"])."""
+    dice_weight, smooth = check_dice(dice_weight, smooth, "seg_dice")
+    B, dev = _dice_geometry(logits_pad, target, hp, wp, H, W, nseg)
+    _dice_class_weight(class_weight, nseg, dev)
+    bufs = _dice_bufs({} if bufs is None else bufs, logits_pad, target, B, hp, wp, nseg,
+                      ("dice_part", "dice_sums", "dice_tile", "dice_val", "loss3", "dl"))
+    _dice_tiles(logits_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, dice_weight, smooth, class_weight, bufs, pad_id, eos_id)
+    dl = bufs["dl"]
+    _check(lib().ifseg_seg_loss_gather_sum(None, None, _ptr(bufs["dice_tile"]), _ptr(bufs["dice_val"]), _ptr(dl), c_int(dl.stride(1)),
+                                           c_ll(dl.stride(0)), c_int(B), c_int(hp), c_int(wp), c_int(nseg), _ptr(bufs["loss3"]),
+                                           _stream()), "seg_loss_gather_sum")
+    return bufs["loss3"][0], dl
+
+
+def seg_loss_dice(logits_pad, target, hp, wp, H, W, nseg, seg_id_offset, dice_weight, smooth=1.0, dice_class_weight=None, bufs=None,
+                  pixel_weight=None, class_weight=None, norm_pixels=False, pad_id=1, eos_id=2, label_smoothing=0.0):
+    """cross entropy + dice_weight * Dice in one gradient: `seg_loss`'s tile launch and reduction (`seg_loss_weighted`'s when
+    pixel_weight, class_weight or norm_pixels is given) as they are, then `seg_dice`'s launches and the
+    two-source gather -> (loss_out fp32 [3] = total, CE, weighted Dice; dlogits_pad bf16 = d total / d logits, one rounding).
+    loss_out[1] and bufs["stats"] are the bits the CE call gives alone.  bufs as `seg_dice_sums`; it also holds the CE call's
+    tile / sp / stats / bad."""
+    dice_weight, smooth = check_dice(dice_weight, smooth, "seg_loss_dice")
+    B, dev = _dice_geometry(logits_pad, target, hp, wp, H, W, nseg)
+    assert target.shape[1] == H * W + 1, tuple(target.shape)
+    _dice_class_weight(dice_class_weight, nseg, dev)
+    bufs = _dice_bufs({} if bufs is None else bufs, logits_pad, target, B, hp, wp, nseg,
+                      ("dice_part", "dice_sums", "dice_tile", "dice_val", "loss3", "dl", "tile", "sp", "stats", "bad"))
+    dl, ld = bufs["dl"], logits_pad.stride(1)
+    weighted = pixel_weight is not None or class_weight is not None or bool(norm_pixels)
+    head = (_ptr(logits_pad), c_int(ld), c_ll(logits_pad.stride(0)), _ptr(target), c_ll(target.stride(0)), c_int(B), c_int(hp),
+            c_int(wp), c_int(H), c_int(W), c_int(nseg), c_ll(seg_id_offset), c_ll(pad_id), c_ll(eos_id))
+    tail = (_ptr(bufs["tile"]), _ptr(bufs["sp"]), _ptr(bufs["bad"]), c_float(label_smoothing), _stream())
+    if not weighted:
+        _check(lib().ifseg_seg_loss_tiles(*head, *tail), "seg_loss_tiles")
+    else:
+        pw_bs = 0
+        if pixel_weight is not None:
+            assert pixel_weight.dtype == torch.uint8 and tuple(pixel_weight.shape) == (B, H * W) and pixel_weight.stride(1) == 1 \
+                and pixel_weight.device == dev, (pixel_weight.dtype, tuple(pixel_weight.shape), pixel_weight.stride(), pixel_weight.device)
+            pw_bs = pixel_weight.stride(0) if B > 1 else H * W
+        _dice_class_weight(class_weight, nseg, dev)
+        _check(lib().ifseg_seg_loss_tiles_weighted(*head, _ptr(pixel_weight), c_ll(pw_bs), _ptr(class_weight),
+                                                   c_int(1 if norm_pixels else 0), *tail), "seg_loss_tiles_weighted")
+    reduce_parts(bufs["sp"], bufs["stats"], 1, B * hp * wp, 2 + 3 * nseg)
+    _dice_tiles(logits_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, dice_weight, smooth, dice_class_weight, bufs, pad_id, eos_id)
+    _check(lib().ifseg_seg_loss_gather_sum(_ptr(bufs["tile"]), _ptr(bufs["stats"]), _ptr(bufs["dice_tile"]), _ptr(bufs["dice_val"]),
+                                           _ptr(dl), c_int(dl.stride(1)), c_ll(dl.stride(0)), c_int(B), c_int(hp), c_int(wp),
+                                           c_int(nseg), _ptr(bufs["loss3"]), _stream()), "seg_loss_gather_sum")
+    return bufs["loss3"], dl
+
+
 # ---------------------------------------------------------------------- eval post-processing
 def rows_to_f32(logits_pad, nseg, rows_per_batch, softmax=False, temperature=1.0):
     """logits_pad bf16 [B, T, ld] -> fp32 [B, rows_per_batch, nseg] (first rows of every sample), optionally softmaxed"""

@@ -18,7 +18,8 @@ The second half of the file puts the training-path kernels there as well (see th
 `attention_bias` (the bias is an ordinary tensor with a gradient), `bias_attention_bi` (bias_attention on the batch-inner
 kernels, with key counts and attention dropout), `seg_loss` (csrc/loss.hip) and `seg_loss_weighted` (the same kernel with a
 weight per pixel and per class; it shares `seg_loss_bwd`), with `*_bwd` ops of their own, and `seg_ohem` (csrc/ohem.hip: the
-online-hard-example sampler that makes that weight plane; a constant of the step, no backward);
+online-hard-example sampler that makes that weight plane; a constant of the step, no backward) and `seg_dice` (csrc/dice.hip: the
+per-sample soft Dice loss of the same upsampled logits, with `seg_loss_bwd` as its backward);
 `ifseg_amd.modules.MultiheadAttention` composes `linear` and `attention_bias` under the reference module's parameter names.
 `seg_predict` (csrc/predict.hip: label maps at image resolution), `seg_predict_views` (the same from the mean of K views of
 differing grids, mirrored ones included: multi-scale + flip inference), `seg_areas` / `seg_score_views` (label maps counted
@@ -271,6 +272,7 @@ bias_attention.register_autograd(_attn_backward, setup_context=_attn_setup)
 #   torch.ops.ifseg.seg_loss(logits, target, hp, wp, H, W, seg_id_offset, label_smoothing)       x16 upsample + CE + histograms
 #   torch.ops.ifseg.seg_loss_weighted(logits, target, pixel_weight, class_weight, hp, wp, H, W, seg_id_offset, label_smoothing,
 #                                     norm_pixels)                                               the same with per-pixel / per-class weights
+#   torch.ops.ifseg.seg_dice(logits, target, class_weight, hp, wp, H, W, seg_id_offset, dice_weight, smooth)   per-sample soft Dice
 #
 # Every op has ONE check helper that its real and its fake implementation call first: tracing refuses what running refuses,
 # and nothing is launched (the library is not even loaded) before the arguments have passed.
@@ -780,6 +782,64 @@ def seg_ohem(logits: torch.Tensor, target: torch.Tensor, pixel_weight: Optional[
 def _(logits, target, pixel_weight, hp, wp, H, W, seg_id_offset, thresh, min_kept):
     B, nseg, npad = _seg_ohem_check(logits, target, pixel_weight, hp, wp, H, W, thresh, min_kept)
     return logits.new_empty((B, H * W), dtype=torch.uint8), logits.new_empty((4,), dtype=torch.int64)
+
+
+# ----------------------------------------------------------------------------------------------- seg_dice
+def _seg_dice_check(logits, target, class_weight, hp, wp, H, W, dice_weight, smooth):
+    op = "ifseg::seg_dice"
+    B, nseg, npad = _seg_loss_check(logits, target, hp, wp, H, W)
+    if class_weight is not None and (class_weight.dtype != torch.float32 or tuple(class_weight.shape) != (nseg,)):
+        raise ValueError("%s: class_weight must be fp32 [nseg] = [%d], got %s %s"
+                         % (op, nseg, class_weight.dtype, tuple(class_weight.shape)))
+    hip.check_dice(dice_weight, smooth, op)
+    return B, nseg, npad
+
+
+@custom_op("ifseg::seg_dice", mutates_args=(), device_types="cuda")
+def seg_dice(logits: torch.Tensor, target: torch.Tensor, class_weight: Optional[torch.Tensor], hp: int, wp: int, H: int, W: int,
+             seg_id_offset: int, dice_weight: float, smooth: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """dice_weight times the per-sample soft Dice loss of the x16 bilinear upsample of the per-patch logits (csrc/dice.hip:
+    hip.seg_dice; `criterions.seg_criterion.dice_loss_reference` is the specification).  logits and target as `seg_loss`,
+    class_weight None or fp32 [nseg], finite and non-negative (the caller's duty: the op reads no values).
+    -> (loss fp32 [], sums fp32 [B, 3, nseg] = I, P, Y of `dice_sums_reference`,
+        dlogits bf16 [B, hp*wp+1, nseg rounded up to 8] = d loss / d logits, padding columns and the eos row zero), fresh tensors.
+    Differentiable in logits only."""
+    B, nseg, npad = _seg_dice_check(logits, target, class_weight, hp, wp, H, W, dice_weight, smooth)
+    prev = _stream_scope(logits)
+    try:
+        dev, P = logits.device, hp * wp
+        lp = logits
+        if not (lp.stride(2) == 1 and lp.stride(1) % 8 == 0 and lp.stride(1) >= npad and lp.stride(0) % 8 == 0
+                and lp.data_ptr() % 16 == 0):
+            lp = torch.zeros(B, P + 1, npad, dtype=BF, device=dev)
+            lp[:, :, :nseg].copy_(logits)
+        bufs = {"dl": torch.empty(B, P + 1, npad, dtype=BF, device=dev)}
+        loss, dl = hip.seg_dice(lp, target.contiguous(), hp, wp, H, W, nseg, seg_id_offset, dice_weight, smooth,
+                                class_weight=class_weight.contiguous() if class_weight is not None else None, bufs=bufs)
+        return loss.clone(), bufs["dice_sums"], dl
+    finally:
+        hip.set_stream(prev)
+
+
+@seg_dice.register_fake
+def _(logits, target, class_weight, hp, wp, H, W, seg_id_offset, dice_weight, smooth):
+    B, nseg, npad = _seg_dice_check(logits, target, class_weight, hp, wp, H, W, dice_weight, smooth)
+    f32 = torch.float32
+    return (logits.new_empty((), dtype=f32), logits.new_empty((B, 3, nseg), dtype=f32), logits.new_empty(B, hp * wp + 1, npad))
+
+
+def _sd_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[2])
+    ctx.mark_non_differentiable(output[1], output[2])
+    ctx.nseg = inputs[0].shape[2]
+
+
+def _sd_backward(ctx, gloss, gsums, gdl):
+    (dl,) = ctx.saved_tensors
+    return (torch.ops.ifseg.seg_loss_bwd(gloss, dl, ctx.nseg),) + (None,) * 9
+
+
+seg_dice.register_autograd(_sd_backward, setup_context=_sd_setup)
 
 
 # ----------------------------------------------------------------------------------------------- seg_predict

@@ -544,6 +544,30 @@ int ifseg_seg_hardness(const void* logits, int ldl, long long logits_bs, const l
  * IFSEG_ERR_BAD_ARG; B outside [1, 2^20), n < 1, B*n >= 2^31: IFSEG_ERR_BAD_SHAPE.  Nothing is launched on a refusal. */
 int ifseg_ohem_select(const float* hardness, int B, long long n, float thresh, long long min_kept, const unsigned char* weight,
                       unsigned char* out, long long* info, unsigned long long* work, void* stream);
+/* Per-sample soft Dice on the same x16 upsample (csrc/dice.hip; criterions/seg_criterion.py: dice_sums_reference and
+ * dice_loss_reference state the rule).  With p_ic = softmax_c(v_i) over the valid pixels i of sample b (the validity predicate of
+ * ifseg_seg_loss_tiles): I_bc = sum p_ic [y_i = c], P_bc = sum p_ic^2, Y_bc = sum [y_i = c], N = 2 I + smooth, Q = P + Y + smooth,
+ *   dice_weight L_dice = sum_b sum_c k_c (1 - N_bc / Q_bc),   k_c = dice_weight class_weight[c] / (B nseg)   (NULL: ones).
+ * ifseg_seg_dice_sums (pass A): sums_part fp32 [B*hp*wp][3*nseg] = every tile's I, P, Y; ifseg_reduce_parts(outer = B,
+ *   parts = hp*wp, n = 3*nseg) gives sums [B][3][nseg] in a fixed order.
+ * ifseg_seg_dice_tiles (pass B): from sums, tile_partial fp32 [B*hp*wp][9][nseg] = the adjoint of the interpolation applied to
+ *   d (dice_weight L_dice) / d v, in final scale, and dice_out[0] = dice_weight L_dice (summed by workgroup 0 in a fixed order).
+ * ifseg_seg_loss_gather_sum: ifseg_seg_loss_gather with two sources, dlogits = bf16(sum of the CE partials * (1 / stats[1]) +
+ *   sum of the Dice partials) in one rounding (eos row and padding columns zero), loss_out[3] = total, CE (stats[0] / stats[1], 0
+ *   when stats[1] = 0), Dice.  ce_partial NULL (stats is then not read): Dice alone, CE = 0.
+ * One workgroup of 256 per cell, no atomics: two runs give equal bits.  Refusals, nothing launched: NULL / misaligned pointers
+ * (class_weight 4 bytes), strides below a sample, smooth or dice_weight <= 0 or not finite: IFSEG_ERR_BAD_ARG; B, hp, wp < 1,
+ * H != 16 hp, W != 16 wp, nseg outside 1..512, ldl < nseg, B*hp*wp >= 2^31: IFSEG_ERR_BAD_SHAPE. */
+int ifseg_seg_dice_sums(const void* logits, int ldl, long long logits_bs, const long long* target, long long target_bs, int B,
+                        int hp, int wp, int H, int W, int nseg, long long seg_id_offset, long long pad_id, long long eos_id,
+                        float* sums_part, void* stream);
+int ifseg_seg_dice_tiles(const void* logits, int ldl, long long logits_bs, const long long* target, long long target_bs, int B,
+                         int hp, int wp, int H, int W, int nseg, long long seg_id_offset, long long pad_id, long long eos_id,
+                         const float* sums, const float* class_weight, float dice_weight, float smooth, float* tile_partial,
+                         float* dice_out, void* stream);
+int ifseg_seg_loss_gather_sum(const float* ce_partial, const float* stats, const float* dice_partial, const float* dice_value,
+                              void* dlogits, int ldl, long long dlogits_bs, int B, int hp, int wp, int nseg, float* loss_out,
+                              void* stream);
 
 /* ---------------------------------------------------- image-free samples */
 /* The artificial image of `--artificial-image-type rand_k-L-R` (data/mm_data/segmentation_dataset.py:303-345) and its collater
