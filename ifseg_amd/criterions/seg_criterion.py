@@ -23,6 +23,11 @@ Opt-in online hard example mining: ``SegCriterion(ohem_thresh=, ohem_min_kept=)`
 Opt-in Dice auxiliary loss: ``SegCriterion(dice_weight=, dice_smooth=, dice_class_weight=)`` adds ``dice_weight`` times the
 per-sample soft Dice loss of the same upsampled logits (csrc/dice.hip: two tile passes with a device-side reduction between
 them, one gradient); ``dice_sums_reference`` and ``dice_loss_reference`` state the rule.  Without it every call is as before.
+
+Opt-in distillation: ``SegCriterion(distill_weight=, distill_temperature=, distill_mask=)`` adds ``distill_weight`` times the
+per-pixel KL divergence from a teacher's upsampled logits (the sample's ``"teacher_logits"``) to the student's, at a temperature
+(csrc/distill.hip: one tile pass over both logits, one gradient); ``distill_loss_reference`` states the rule.  Without it every
+call is as before.
 """
 from dataclasses import dataclass, field
 from typing import Optional
@@ -296,6 +301,86 @@ def dice_grad_closed_form(scores_up, target, seg_id_offset, nseg, smooth=1.0, cl
     return p * (g - (p * g).sum(-1, keepdim=True))
 
 
+def check_distill(distill_weight, distill_temperature=1.0, distill_mask="valid"):
+    """the distillation term's three settings -> (distill_weight or None, temperature, mask).  distill_weight=None switches the
+    term off; the temperature (a finite number > 0) and the mask ("valid" | "all") are checked either way.  Anything else:
+    ValueError naming the keyword."""
+    w, T, _ = hip.check_distill(distill_weight, distill_temperature, distill_mask, "seg_criterion")
+    return w, T, distill_mask
+
+
+def _distill_terms(scores_up, teacher_up, target, seg_id_offset, nseg, temperature, mask, what):
+    """-> (p, q [B, npix, n], m bool [B, npix], T): the two tempered softmaxes and the mask M of the rule"""
+    _, T, mask_all = hip.check_distill(None, temperature, mask, what)
+    n = int(nseg)
+    for nm, x in (("scores_up", scores_up), ("teacher_up", teacher_up)):
+        if not torch.is_tensor(x) or x.dim() != 3 or x.shape[2] != n or not x.dtype.is_floating_point:
+            raise ValueError("%s: %s must be floating point [B, H*W, %d], got %s" % (
+                what, nm, n, (x.dtype, tuple(x.shape)) if torch.is_tensor(x) else type(x)))
+    B = scores_up.shape[0]
+    if target is None:
+        if not mask_all:
+            raise ValueError("%s: distill_mask=\"valid\" needs the target" % what)
+        npix = scores_up.shape[1]                    # every row is a pixel: the caller leaves the eos row out
+    else:
+        npix = min(scores_up.shape[1], target.shape[1]) if target.dim() == 2 else -1
+        if target.dtype != torch.int64 or target.dim() != 2 or target.shape[0] != B or target.shape[1] - npix not in (0, 1) \
+                or scores_up.shape[1] - npix not in (0, 1):
+            raise ValueError("%s: target must be int64 [B, H*W (+1)], got %s %s for scores %s"
+                             % (what, target.dtype, tuple(target.shape), tuple(scores_up.shape)))
+        if target.shape[1] == scores_up.shape[1] and bool((target[:, -1] == EOS).all()):
+            npix -= 1                                   # scores and target both carry the eos row
+    if teacher_up.shape[0] != B or teacher_up.shape[1] - npix not in (0, 1) or teacher_up.device != scores_up.device:
+        raise ValueError("%s: teacher_up must be [%d, %d (+1), %d] on %s, got %s on %s"
+                         % (what, B, npix, n, scores_up.device, tuple(teacher_up.shape), teacher_up.device))
+    s = scores_up[:, :npix]
+    if s.dtype not in (torch.float32, torch.float64):
+        s = s.float()
+    t = teacher_up.detach()[:, :npix].to(s.dtype)
+    if mask_all:
+        m = torch.ones(B, npix, dtype=torch.bool, device=s.device)
+    else:
+        tgt = target[:, :npix].to(s.device)
+        m = (tgt >= seg_id_offset) & (tgt < seg_id_offset + n) & (tgt != PAD) & (tgt != EOS)
+    return s / T, t / T, m, T
+
+
+def distill_sums_reference(scores_up, teacher_up, target, seg_id_offset, nseg, temperature=1.0, mask="valid"):
+    """-> ([sum_{i in M} KL(q_i || p_i), N = |M|] in the dtype of the scores, differentiable in scores_up): the two numbers
+    `distill_loss_reference` is made of, and what `hip.seg_distill` leaves in bufs["kd_stats"]"""
+    s, t, m, _ = _distill_terms(scores_up, teacher_up, target, seg_id_offset, nseg, temperature, mask, "distill_sums_reference")
+    kl = F.kl_div(F.log_softmax(s, dim=-1), F.softmax(t, dim=-1), reduction="none").sum(-1)
+    return torch.stack([torch.where(m, kl, torch.zeros_like(kl)).sum(), m.sum().to(kl.dtype)])
+
+
+def distill_loss_reference(scores_up, teacher_up, target, seg_id_offset, nseg, temperature=1.0, mask="valid"):
+    """Specification of the distillation term of the fused criterion (csrc/distill.hip; `hip.seg_distill` computes distill_weight
+    times this and its gradient), unscaled, runs on any device and dtype and is differentiable in scores_up only.  scores_up /
+    teacher_up fp32 or fp64 [B, H*W (+1), n] (already upsampled: `SegCriterion.upsample_logits` of the student's and the teacher's
+    per-patch logits), target int64 [B, H*W (+1)] (None with mask="all": every row of the scores is then a pixel).  With
+    p_i = softmax(s_i / T), q_i = softmax(t_i / T):
+      L_kd = T^2 (1 / N) sum_{i in M} sum_c q_ic (log q_ic - log p_ic),   N = |M| over the WHOLE batch
+    built on F.kl_div(log_softmax(s / T), softmax(t / T)).  M is, with mask="valid", the pixels whose target is a class
+    (seg_id_offset <= y < seg_id_offset + n and not pad / eos: the loss kernel's predicate); with mask="all" every pixel -- the
+    usual choice on unlabelled or pseudo-labelled batches, a poisoned or out-of-range target is then irrelevant.  N = 0 gives
+    exactly 0 with a zero gradient.  A trailing row that scores and target both carry and whose targets are all eos is the eos
+    row and is left out.  With mask="all" this is mmrazor's KLDivergence(tau=T, reduction="batchmean") on [B, n, H, W] scores
+    divided by H*W (its batchmean divides by B only); no other relation to upstream is claimed.
+    Gradient in closed form (what the kernel computes, `distill_grad_closed_form`): d L_kd / d s_ic = (T / N) (p_ic - q_ic) on M."""
+    T = hip.check_distill(None, temperature, mask, "distill_loss_reference")[1]
+    kl_sum, N = distill_sums_reference(scores_up, teacher_up, target, seg_id_offset, nseg, temperature, mask)
+    return (T * T) * kl_sum / N.clamp(min=1.0)
+
+
+def distill_grad_closed_form(scores_up, teacher_up, target, seg_id_offset, nseg, temperature=1.0, mask="valid"):
+    """d `distill_loss_reference` / d scores_up by the closed form of its docstring (the arithmetic of csrc/distill.hip and its
+    gather), no autograd -> the shape of scores_up's pixel rows (the eos row, when carried, left out)"""
+    s, t, m, T = _distill_terms(scores_up.detach(), teacher_up, target, seg_id_offset, nseg, temperature, mask,
+                                "distill_grad_closed_form")
+    N = m.sum().to(s.dtype).clamp(min=1.0)
+    return (torch.softmax(s, dim=-1) - torch.softmax(t, dim=-1)) * m.unsqueeze(-1).to(s.dtype) * (T / N)
+
+
 class _FusedSegLossFn(torch.autograd.Function):
     """loss = mean CE(bilinear_x16(logits[:, :P]), target); backward hands out the gradient the
     forward kernel already produced.  pixel_weight / class_weight / norm_pixels: the weighted kernel
@@ -363,6 +448,35 @@ class _FusedSegLossDiceFn(torch.autograd.Function):
         return (g * gloss.to(g.dtype),) + (None,) * 16
 
 
+class _FusedSegLossDistillFn(torch.autograd.Function):
+    """loss = CE (+ dice_weight * Dice) + distill_weight * KD of the same upsampled logits (`hip.seg_loss_distill`): `_FusedSegLossFn`'s
+    CE launch, csrc/dice.hip's passes when dice_weight is given, csrc/distill.hip's tile pass and one gather that sums the
+    gradients.  -> (total, CE, weighted Dice, weighted KD, stats); only the total is differentiable, and only in the student."""
+
+    @staticmethod
+    def forward(ctx, logits, logits_pad, teacher_pad, target, hp, wp, H, W, nseg, seg0, bufs, eps, pixel_weight, class_weight,
+                norm_pixels, dice_weight, dice_smooth, dice_class_weight, kd_weight, kd_temperature, kd_mask):
+        B = logits_pad.shape[0]
+        key = (B, hp, wp, nseg, logits_pad.shape[2], logits_pad.device, "distill", dice_weight is not None)
+        if bufs.get("key") != key:
+            bufs.clear()
+            bufs["key"] = key
+        loss4, dl = hip.seg_loss_distill(logits_pad, teacher_pad, target, hp, wp, H, W, nseg, seg0, kd_weight, kd_temperature, kd_mask,
+                                         dice_weight=dice_weight, dice_smooth=dice_smooth, dice_class_weight=dice_class_weight,
+                                         bufs=bufs, pixel_weight=pixel_weight, class_weight=class_weight, norm_pixels=norm_pixels,
+                                         label_smoothing=float(eps))
+        ctx.dl = dl
+        ctx.nseg = nseg
+        out = (loss4[0].clone(), loss4[1].clone(), loss4[2].clone(), loss4[3].clone(), bufs["stats"].clone())
+        ctx.mark_non_differentiable(*out[1:])
+        return out
+
+    @staticmethod
+    def backward(ctx, gloss, gce, gdice, gkd, gstats):
+        g = ctx.dl[:, :, : ctx.nseg]
+        return (g * gloss.to(g.dtype),) + (None,) * 20
+
+
 FUSED_MAX_CLASSES = 512      # csrc/loss.hip NS_MAX
 
 
@@ -374,7 +488,8 @@ class SegCriterion(CriterionBase):
                  criterion_update_freq=1, freeze_embedding_iter=-1, full_context_alignment="false",
                  init_seg_with_text="true", resnet_topk=3, resnet_prob_temperature=1.0, resnet_iters=0,
                  num_seg_tokens=None, seg_id_offset=None, class_weight=None, weight_norm="weights", ohem_thresh=None,
-                 ohem_min_kept=OHEM_MIN_KEPT, dice_weight=None, dice_smooth=1.0, dice_class_weight=None):
+                 ohem_min_kept=OHEM_MIN_KEPT, dice_weight=None, dice_smooth=1.0, dice_class_weight=None, distill_weight=None,
+                 distill_temperature=1.0, distill_mask="valid"):
         """Signature of the reference (seg_criterion.py:115-161; fairseq's `build_criterion` fills it from
         SegCriterionConfig by name).  `num_seg_tokens` / `seg_id_offset` stand in for `task.cfg.num_seg_tokens` and
         `task.target_dictionary.index("<seg_0>")` when the criterion is used without a task.  `class_weight` (n numbers >= 0,
@@ -395,7 +510,17 @@ class SegCriterion(CriterionBase):
         includes the no-grad pass over the real images of image-free training (`unsupervised_segmentation`): there
         `seg_loss`, `nll_loss` and `dice_loss` are logged monitors of the real images and nothing of them is trained, as `seg_loss`
         and `nll_loss` always were in that mode; the trained image-free loss has no Dice term.  Not built: Dice in the image-free
-        loss and in the `ori_semantic_seg` evaluation."""
+        loss and in the `ori_semantic_seg` evaluation.
+        `distill_weight` (> 0; None: off) / `distill_temperature` (> 0) / `distill_mask` ("valid" | "all"), constructor keywords
+        only: distillation from a teacher's whole output -- `distill_loss_reference` states the rule.  The term is computed when
+        the sample carries `"teacher_logits"`: bf16 [B, P+1, >= n] on the logits' device, the teacher's per-patch logits on the
+        same grid and classes (`task.distill_sample` attaches them); anything else is a ValueError that names what differs.  The
+        returned loss is CE (+ dice_weight * Dice) + distill_weight * KD, `metrics["kd_loss"]` is the weighted KD term and
+        `self.distill_stats` holds the last call's fp32 [sum KL, N] on the device.  Pixel weights, class weights and the OHEM
+        plane do not enter the term.  A supervised training call (`model.training`, gradients enabled) whose sample lacks the
+        key is a ValueError; under `torch.no_grad()` and in evaluation a missing key just skips the term (the no-grad monitor
+        pass of image-free training is such a case).  Not built: KD in the image-free loss and in the `ori_semantic_seg`
+        evaluation."""
         super().__init__(task)
         self.sentence_avg = sentence_avg
         self.eps = label_smoothing
@@ -429,6 +554,9 @@ class SegCriterion(CriterionBase):
         if self.dice_class_weight is not None:
             self.dice_class_weight = self.dice_class_weight.float()          # what the kernel reads
         self.dice_sums = None
+        self.distill_weight, self.distill_temperature, self.distill_mask = check_distill(distill_weight, distill_temperature,
+                                                                                         distill_mask)
+        self.distill_stats = None
         # image-free samples drawn on the device (ifseg_amd/artificial.py).  The trainer sets the seed and, before every
         # micro-batch, the ordinal of its first sample (an int, or a device int64 word inside a captured step); without a
         # trainer the criterion counts the samples it has drawn.
@@ -586,8 +714,22 @@ class SegCriterion(CriterionBase):
                 setattr(self, bufs_name, {})
             if self.ohem_thresh is not None and model.training:
                 pw = self._ohem_plane(pad, target.contiguous(), pw, hp, wp, h, w, bufs_name + "_ohem")
-            dice = None
-            if self.dice_weight is not None:
+            dice = kd = None
+            teacher = self._teacher_logits(model, sample, scores_low, hp * wp)
+            if teacher is not None:
+                weighted = pw is not None or self.class_weight is not None
+                loss, ce, dice, kd, stats = _FusedSegLossDistillFn.apply(
+                    scores_low, pad, teacher, target.contiguous(), hp, wp, h, w, self.num_seg, self.seg_id_offset,
+                    getattr(self, bufs_name), self.eps, pw.contiguous() if pw is not None else None,
+                    self._class_weight_on(pad.device) if weighted else None, self.norm_pixels and weighted, self.dice_weight,
+                    self.dice_smooth, self._dice_class_weight_on(pad.device), self.distill_weight, self.distill_temperature,
+                    self.distill_mask)
+                self.distill_stats = getattr(self, bufs_name)["kd_stats"]
+                if self.dice_weight is not None:
+                    self.dice_sums = getattr(self, bufs_name)["dice_sums"]
+                else:
+                    dice = None
+            elif self.dice_weight is not None:
                 weighted = pw is not None or self.class_weight is not None
                 loss, ce, dice, stats = _FusedSegLossDiceFn.apply(
                     scores_low, pad, target.contiguous(), hp, wp, h, w, self.num_seg, self.seg_id_offset, getattr(self, bufs_name),
@@ -613,6 +755,8 @@ class SegCriterion(CriterionBase):
                        "nll_loss": loss}
             if dice is not None:
                 metrics.update(nll_loss=ce, dice_loss=dice)
+            if kd is not None:
+                metrics.update(nll_loss=ce, kd_loss=kd)
             return loss, metrics, 1
         return self.compute_loss_torch(model, net_output, sample, update_num, reduce)
 
@@ -644,7 +788,38 @@ class SegCriterion(CriterionBase):
                                                           self.dice_smooth, self._dice_class_weight_on(scores.device))
             metrics["dice_loss"] = dice
             loss = loss + dice
+        teacher = self._teacher_logits(model, sample, scores_low, hp * wp)
+        if teacher is not None:
+            teacher_up = self.upsample_logits(teacher[:, :, :self.num_seg].float(), hp, wp, h, w)
+            args = (scores[:, :h * w], teacher_up[:, :h * w], target, self.seg_id_offset, self.num_seg, self.distill_temperature,
+                    self.distill_mask)
+            self.distill_stats = distill_sums_reference(*args).detach()
+            kd = self.distill_weight * distill_loss_reference(*args)
+            metrics["kd_loss"] = kd
+            loss = loss + kd
         return loss, metrics, 1
+
+    def _teacher_logits(self, model, sample, scores_low, P):
+        """the sample's `"teacher_logits"` when the distillation term applies to this call, checked against the student's logits
+        (ValueError naming what differs), or None: the term is off, or the key is missing in a call that trains nothing"""
+        if self.distill_weight is None:
+            return None
+        teacher = sample.get("teacher_logits")
+        if teacher is None:
+            if model.training and torch.is_grad_enabled():
+                raise ValueError("seg_criterion: distill_weight is set and the sample carries no \"teacher_logits\" "
+                                 "(task.distill_sample attaches them)")
+            return None
+        B, n = scores_low.shape[0], self.num_seg
+        if not torch.is_tensor(teacher) or teacher.dtype != torch.bfloat16:
+            raise ValueError("seg_criterion: teacher_logits must be a bf16 tensor, got %s"
+                             % (teacher.dtype if torch.is_tensor(teacher) else type(teacher)))
+        if teacher.dim() != 3 or teacher.shape[0] != B or teacher.shape[1] != P + 1 or teacher.shape[2] < n:
+            raise ValueError("seg_criterion: teacher_logits must have the shape [B, P+1, >= n] = [%d, %d, >= %d] of the student's "
+                             "grid and classes, got %s" % (B, P + 1, n, tuple(teacher.shape)))
+        if teacher.device != scores_low.device:
+            raise ValueError("seg_criterion: teacher_logits are on device %s, the logits on %s" % (teacher.device, scores_low.device))
+        return teacher if teacher.stride(2) == 1 else teacher.contiguous()
 
     def _ohem_plane(self, pad, target, pw, hp, wp, h, w, name):
         """the sampler's two stages on the device (hip.seg_hardness, hip.ohem_select), no gradient and no read-back -> the
@@ -701,6 +876,9 @@ class SegCriterion(CriterionBase):
         has_dice = any("dice_loss" in l for l in logging_outputs)             # only a criterion with dice_weight logs it
         if has_dice:
             out["dice_loss"] = float(tot("dice_loss")) / max(float(ss), 1e-9)
+        has_kd = any("kd_loss" in l for l in logging_outputs)                 # only a criterion with distill_weight logs it
+        if has_kd:
+            out["kd_loss"] = float(tot("kd_loss")) / max(float(ss), 1e-9)
         areas = {}
         for suf in ("", "_resnet_postprocess", "_lowres"):
             if "area_intersect" + suf not in logging_outputs[0]:
@@ -716,7 +894,7 @@ class SegCriterion(CriterionBase):
             return out
         ntok = out["ntokens"]
         metrics.log_scalar("loss", out["loss"], ss, round=3)
-        for k in ("imfree_loss", "seg_loss", "nll_loss") + (("dice_loss",) if has_dice else ()):
+        for k in ("imfree_loss", "seg_loss", "nll_loss") + (("dice_loss",) if has_dice else ()) + (("kd_loss",) if has_kd else ()):
             metrics.log_scalar(k, out[k], ntok, round=3)
         for k in ("ntokens", "nsentences", "sample_size"):
             metrics.log_scalar(k, out[k], 1, round=3)

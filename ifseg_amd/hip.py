@@ -1114,7 +1114,8 @@ def _dice_bufs(bufs, logits_pad, target, B, hp, wp, nseg, names):
     shapes = {"dice_part": ((tiles * 3 * nseg,), f32), "dice_sums": ((B, 3, nseg), f32), "dice_tile": ((tiles * 9 * nseg,), f32),
               "dice_val": ((1,), f32), "loss3": ((3,), f32), "dl": (None, torch.bfloat16),
               "tile": ((tiles * 9 * nseg,), f32), "sp": ((tiles * (2 + 3 * nseg),), f32), "stats": ((2 + 3 * nseg,), f32),
-              "bad": ((1,), torch.int32)}
+              "bad": ((1,), torch.int32),
+              "kd_tile": ((tiles * 9 * nseg,), f32), "kd_part": ((tiles * 2,), f32), "kd_stats": ((2,), f32), "loss4": ((4,), f32)}
     for k in names:
         shape, dt = shapes[k]
         if k == "dl":
@@ -1132,7 +1133,8 @@ def _dice_bufs(bufs, logits_pad, target, B, hp, wp, nseg, names):
             t = bufs[k]
             assert t.dtype == dt and tuple(t.shape) == shape and t.device == dev and t.is_contiguous(), \
                 (k, t.dtype, tuple(t.shape), t.stride(), t.device)
-        assert not _overlap(t, logits_pad) and not _overlap(t, target), "dice: buffer %r overlaps the logits or the target" % k
+        assert not _overlap(t, logits_pad) and (target is None or not _overlap(t, target)), \
+            "dice: buffer %r overlaps the logits or the target" % k
     held = [bufs[k] for k in names]
     assert not any(_overlap(a, b) for i, a in enumerate(held) for b in held[i + 1:]), "dice: two buffers overlap"
     return bufs
@@ -1206,7 +1208,21 @@ def seg_loss_dice(logits_pad, target, hp, wp, H, W, nseg, seg_id_offset, dice_we
     _dice_class_weight(dice_class_weight, nseg, dev)
     bufs = _dice_bufs({} if bufs is None else bufs, logits_pad, target, B, hp, wp, nseg,
                       ("dice_part", "dice_sums", "dice_tile", "dice_val", "loss3", "dl", "tile", "sp", "stats", "bad"))
-    dl, ld = bufs["dl"], logits_pad.stride(1)
+    dl = bufs["dl"]
+    _ce_tiles(logits_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, pixel_weight, class_weight, norm_pixels, bufs, pad_id, eos_id,
+              label_smoothing)
+    _dice_tiles(logits_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, dice_weight, smooth, dice_class_weight, bufs, pad_id, eos_id)
+    _check(lib().ifseg_seg_loss_gather_sum(_ptr(bufs["tile"]), _ptr(bufs["stats"]), _ptr(bufs["dice_tile"]), _ptr(bufs["dice_val"]),
+                                           _ptr(dl), c_int(dl.stride(1)), c_ll(dl.stride(0)), c_int(B), c_int(hp), c_int(wp),
+                                           c_int(nseg), _ptr(bufs["loss3"]), _stream()), "seg_loss_gather_sum")
+    return bufs["loss3"], dl
+
+
+def _ce_tiles(logits_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, pixel_weight, class_weight, norm_pixels, bufs, pad_id, eos_id,
+              label_smoothing):
+    """`seg_loss`'s tile launch (`seg_loss_weighted`'s when pixel_weight, class_weight or norm_pixels is given) and the reduction
+    into bufs["tile"], bufs["sp"], bufs["stats"], bufs["bad"]: the CE call's own launches, without its gather"""
+    dev, ld = logits_pad.device, logits_pad.stride(1)
     weighted = pixel_weight is not None or class_weight is not None or bool(norm_pixels)
     head = (_ptr(logits_pad), c_int(ld), c_ll(logits_pad.stride(0)), _ptr(target), c_ll(target.stride(0)), c_int(B), c_int(hp),
             c_int(wp), c_int(H), c_int(W), c_int(nseg), c_ll(seg_id_offset), c_ll(pad_id), c_ll(eos_id))
@@ -1223,11 +1239,129 @@ def seg_loss_dice(logits_pad, target, hp, wp, H, W, nseg, seg_id_offset, dice_we
         _check(lib().ifseg_seg_loss_tiles_weighted(*head, _ptr(pixel_weight), c_ll(pw_bs), _ptr(class_weight),
                                                    c_int(1 if norm_pixels else 0), *tail), "seg_loss_tiles_weighted")
     reduce_parts(bufs["sp"], bufs["stats"], 1, B * hp * wp, 2 + 3 * nseg)
-    _dice_tiles(logits_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, dice_weight, smooth, dice_class_weight, bufs, pad_id, eos_id)
-    _check(lib().ifseg_seg_loss_gather_sum(_ptr(bufs["tile"]), _ptr(bufs["stats"]), _ptr(bufs["dice_tile"]), _ptr(bufs["dice_val"]),
-                                           _ptr(dl), c_int(dl.stride(1)), c_ll(dl.stride(0)), c_int(B), c_int(hp), c_int(wp),
-                                           c_int(nseg), _ptr(bufs["loss3"]), _stream()), "seg_loss_gather_sum")
-    return bufs["loss3"], dl
+
+
+# ---------------------------------------------------------------------- distillation: per-pixel KL to a teacher
+DISTILL_MASKS = ("valid", "all")
+
+
+def check_distill(weight, temperature=1.0, mask="valid", who="distill"):
+    """the distillation term's three settings -> (weight or None, temperature, mask_all).  weight=None switches the term off; a
+    finite number > 0 switches it on; the temperature is a finite number > 0 and the mask one of ("valid", "all") either way.
+    Anything else (a bool, a string) is a ValueError naming distill_weight / distill_temperature / distill_mask."""
+    temperature = check_dice_number("distill_temperature", temperature, who)
+    if not isinstance(mask, str) or mask not in DISTILL_MASKS:
+        raise ValueError("%s: distill_mask must be one of %s, got %r" % (who, DISTILL_MASKS, mask))
+    if weight is not None:
+        weight = check_dice_number("distill_weight", weight, who)
+    return weight, temperature, mask == "all"
+
+
+def _span(t):
+    """(first byte, one past the last byte) a view can touch, whatever its strides"""
+    n = 1 + sum((s - 1) * st for s, st in zip(t.shape, t.stride())) if t.numel() else 0
+    return t.data_ptr(), t.data_ptr() + n * t.element_size()
+
+
+def _distill_geometry(logits_pad, teacher_pad, target, hp, wp, H, W, nseg, mask_all):
+    assert logits_pad.dtype == torch.bfloat16 and logits_pad.dim() == 3 and logits_pad.stride(2) == 1 and logits_pad.is_cuda \
+        and logits_pad.shape[1] >= hp * wp and logits_pad.stride(1) >= nseg, (logits_pad.dtype, tuple(logits_pad.shape), logits_pad.stride())
+    B, dev = logits_pad.shape[0], logits_pad.device
+    assert torch.is_tensor(teacher_pad) and teacher_pad.dtype == torch.bfloat16 and teacher_pad.dim() == 3 \
+        and teacher_pad.device == dev and teacher_pad.shape[0] == B and teacher_pad.shape[1] >= hp * wp \
+        and teacher_pad.shape[2] >= nseg and teacher_pad.stride(2) == 1 and teacher_pad.stride(1) >= nseg \
+        and (B == 1 or teacher_pad.stride(0) >= hp * wp * teacher_pad.stride(1)), \
+        "distill: the teacher's logits must be bf16 [%d, >= %d, >= %d] on %s, got %s" % (
+            B, hp * wp, nseg, dev, (teacher_pad.dtype, tuple(teacher_pad.shape), teacher_pad.stride(), teacher_pad.device)
+            if torch.is_tensor(teacher_pad) else type(teacher_pad))
+    if target is None:
+        assert mask_all, "distill: mask=\"valid\" needs the target"
+    else:
+        assert target.dtype == torch.int64 and target.dim() == 2 and target.shape[0] == B and target.shape[1] >= H * W \
+            and target.stride(1) == 1 and target.device == dev, (target.dtype, tuple(target.shape), target.stride(), target.device)
+    assert B >= 1 and hp >= 1 and wp >= 1 and H == 16 * hp and W == 16 * wp and 1 <= nseg <= 512, (B, hp, wp, H, W, nseg)
+    return B, dev
+
+
+def _distill_bufs(bufs, logits_pad, teacher_pad, target, B, hp, wp, nseg, names):
+    """`_dice_bufs` for a call with a teacher: made on the first call, checked on every call, overlap with the teacher refused"""
+    bufs = _dice_bufs({} if bufs is None else bufs, logits_pad, target, B, hp, wp, nseg, names)
+    t0, t1 = _span(teacher_pad)
+    for k in names:
+        b0, b1 = _span(bufs[k])
+        assert not (b0 < t1 and t0 < b1), "distill: buffer %r overlaps the teacher's logits" % k
+    return bufs
+
+
+def _distill_tiles(logits_pad, teacher_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, temperature, mask_all, bufs, pad_id, eos_id):
+    """the KD tile launch and the reduction into bufs["kd_tile"], bufs["kd_part"], bufs["kd_stats"]"""
+    ld, ldt = logits_pad.stride(1), teacher_pad.stride(1)
+    _check(lib().ifseg_seg_distill_tiles(
+        _ptr(logits_pad), c_int(ld), c_ll(logits_pad.stride(0) if B > 1 else hp * wp * ld), _ptr(teacher_pad), c_int(ldt),
+        c_ll(teacher_pad.stride(0) if B > 1 else hp * wp * ldt), _ptr(target),
+        c_ll(0 if target is None else target.stride(0) if B > 1 else H * W), c_int(B), c_int(hp), c_int(wp), c_int(H), c_int(W),
+        c_int(nseg), c_ll(seg_id_offset), c_ll(pad_id), c_ll(eos_id), c_float(temperature), c_int(1 if mask_all else 0),
+        _ptr(bufs["kd_tile"]), _ptr(bufs["kd_part"]), _stream()), "seg_distill_tiles")
+    reduce_parts(bufs["kd_part"], bufs["kd_stats"], 1, B * hp * wp, 2)
+
+
+def _gather3(bufs, ce, dice, weight, temperature, B, hp, wp, nseg):
+    dl = bufs["dl"]
+    _check(lib().ifseg_seg_loss_gather3(
+        _ptr(bufs["tile"]) if ce else None, _ptr(bufs["stats"]) if ce else None, _ptr(bufs["dice_tile"]) if dice else None,
+        _ptr(bufs["dice_val"]) if dice else None, _ptr(bufs["kd_tile"]), _ptr(bufs["kd_stats"]), c_float(weight),
+        c_float(temperature), _ptr(dl), c_int(dl.stride(1)), c_ll(dl.stride(0)), c_int(B), c_int(hp), c_int(wp), c_int(nseg),
+        _ptr(bufs["loss4"]), _stream()), "seg_loss_gather3")
+    return bufs["loss4"], dl
+
+
+def seg_distill(logits_pad, teacher_pad, target, hp, wp, H, W, nseg, seg_id_offset, weight, temperature=1.0, mask="valid", bufs=None,
+                pad_id=1, eos_id=2):
+    """Distillation alone (csrc/distill.hip): tiles -> reduce -> gather, three launches, nothing read back, no atomics.
+    logits_pad / teacher_pad bf16 [B, >= hp*wp, ld >= nseg] (row-strided views, each with strides of its own; the teacher's padding
+    columns and eos row are never read), target int64 [B, H*W (+1)], or None with mask="all"
+    -> (loss fp32 [] = weight * `criterions.seg_criterion.distill_loss_reference`, dlogits_pad bf16 [B, hp*wp+1, ld] = its gradient
+    in the student's logits, padding columns and the eos row zero).  bufs: a dict the caller keeps between calls (the loss is
+    bufs["loss4"][3], the gradient bufs["dl"], [sum KL, N] bufs["kd_stats"]); nothing is allocated after the first call with it."""
+    weight, temperature, mask_all = check_distill(weight, temperature, mask, "seg_distill")
+    if weight is None:
+        raise ValueError("seg_distill: distill_weight must be a finite number > 0, got None")
+    B, dev = _distill_geometry(logits_pad, teacher_pad, target, hp, wp, H, W, nseg, mask_all)
+    bufs = _distill_bufs(bufs, logits_pad, teacher_pad, target, B, hp, wp, nseg, ("kd_tile", "kd_part", "kd_stats", "loss4", "dl"))
+    _distill_tiles(logits_pad, teacher_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, temperature, mask_all, bufs, pad_id, eos_id)
+    loss4, dl = _gather3(bufs, False, False, weight, temperature, B, hp, wp, nseg)
+    return loss4[3], dl
+
+
+def seg_loss_distill(logits_pad, teacher_pad, target, hp, wp, H, W, nseg, seg_id_offset, weight, temperature=1.0, mask="valid",
+                     dice_weight=None, dice_smooth=1.0, dice_class_weight=None, bufs=None, pixel_weight=None, class_weight=None,
+                     norm_pixels=False, pad_id=1, eos_id=2, label_smoothing=0.0):
+    """cross entropy (+ dice_weight * Dice) + weight * distillation in one gradient: `seg_loss`'s tile launch and reduction
+    (`seg_loss_weighted`'s when pixel_weight, class_weight or norm_pixels is given) as they are, `seg_dice`'s launches when
+    dice_weight is given, the KD tiles and reduction, and the three-source gather: five launches, eight with Dice
+    -> (loss_out fp32 [4] = total, CE, weighted Dice, weighted KD; dlogits_pad bf16 = d total / d logits, one rounding).
+    loss_out[1] and bufs["stats"] are the bits the CE call gives alone, loss_out[2] the bits `seg_loss_dice` gives, loss_out[3]
+    the bits `seg_distill` gives.  bufs as `seg_distill`; it also holds the CE call's tile / sp / stats / bad and the Dice buffers."""
+    weight, temperature, mask_all = check_distill(weight, temperature, mask, "seg_loss_distill")
+    if weight is None:
+        raise ValueError("seg_loss_distill: distill_weight must be a finite number > 0, got None")
+    dice = dice_weight is not None
+    if dice:
+        dice_weight, dice_smooth = check_dice(dice_weight, dice_smooth, "seg_loss_distill")
+    assert target is not None, "seg_loss_distill: the cross entropy needs the target"
+    B, dev = _distill_geometry(logits_pad, teacher_pad, target, hp, wp, H, W, nseg, mask_all)
+    assert target.shape[1] == H * W + 1, tuple(target.shape)
+    _dice_class_weight(dice_class_weight, nseg, dev)
+    names = ("kd_tile", "kd_part", "kd_stats", "loss4", "dl", "tile", "sp", "stats", "bad") \
+        + (("dice_part", "dice_sums", "dice_tile", "dice_val") if dice else ())
+    bufs = _distill_bufs(bufs, logits_pad, teacher_pad, target, B, hp, wp, nseg, names)
+    _ce_tiles(logits_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, pixel_weight, class_weight, norm_pixels, bufs, pad_id, eos_id,
+              label_smoothing)
+    if dice:
+        _dice_tiles(logits_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, dice_weight, dice_smooth, dice_class_weight, bufs,
+                    pad_id, eos_id)
+    _distill_tiles(logits_pad, teacher_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, temperature, mask_all, bufs, pad_id, eos_id)
+    return _gather3(bufs, True, dice, weight, temperature, B, hp, wp, nseg)
 
 
 # ---------------------------------------------------------------------- eval post-processing

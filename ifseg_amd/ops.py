@@ -19,7 +19,8 @@ The second half of the file puts the training-path kernels there as well (see th
 kernels, with key counts and attention dropout), `seg_loss` (csrc/loss.hip) and `seg_loss_weighted` (the same kernel with a
 weight per pixel and per class; it shares `seg_loss_bwd`), with `*_bwd` ops of their own, and `seg_ohem` (csrc/ohem.hip: the
 online-hard-example sampler that makes that weight plane; a constant of the step, no backward) and `seg_dice` (csrc/dice.hip: the
-per-sample soft Dice loss of the same upsampled logits, with `seg_loss_bwd` as its backward);
+per-sample soft Dice loss of the same upsampled logits, with `seg_loss_bwd` as its backward) and `seg_distill` (csrc/distill.hip:
+the per-pixel KL divergence from a teacher's upsampled logits at a temperature, `seg_loss_bwd` again; no gradient to the teacher);
 `ifseg_amd.modules.MultiheadAttention` composes `linear` and `attention_bias` under the reference module's parameter names.
 `seg_predict` (csrc/predict.hip: label maps at image resolution), `seg_predict_views` (the same from the mean of K views of
 differing grids, mirrored ones included: multi-scale + flip inference), `seg_areas` / `seg_score_views` (label maps counted
@@ -273,6 +274,8 @@ bias_attention.register_autograd(_attn_backward, setup_context=_attn_setup)
 #   torch.ops.ifseg.seg_loss_weighted(logits, target, pixel_weight, class_weight, hp, wp, H, W, seg_id_offset, label_smoothing,
 #                                     norm_pixels)                                               the same with per-pixel / per-class weights
 #   torch.ops.ifseg.seg_dice(logits, target, class_weight, hp, wp, H, W, seg_id_offset, dice_weight, smooth)   per-sample soft Dice
+#   torch.ops.ifseg.seg_distill(logits, teacher_logits, target, hp, wp, H, W, seg_id_offset, weight, temperature, mask_all)
+#                                                                                                per-pixel KL to a teacher
 #
 # Every op has ONE check helper that its real and its fake implementation call first: tracing refuses what running refuses,
 # and nothing is launched (the library is not even loaded) before the arguments have passed.
@@ -840,6 +843,71 @@ def _sd_backward(ctx, gloss, gsums, gdl):
 
 
 seg_dice.register_autograd(_sd_backward, setup_context=_sd_setup)
+
+
+# ----------------------------------------------------------------------------------------------- seg_distill
+def _seg_distill_check(logits, teacher_logits, target, hp, wp, H, W, weight, temperature, mask_all):
+    op = "ifseg::seg_distill"
+    if target is None:
+        if not mask_all:
+            raise ValueError("%s: target=None needs mask_all=True (the valid pixels are read from the target)" % op)
+        stand_in = torch.empty((logits.shape[0] if logits.dim() == 3 else 0, H * W + 1), dtype=torch.int64, device="meta")
+        B, nseg, npad = _seg_loss_check(logits, stand_in, hp, wp, H, W)
+    else:
+        B, nseg, npad = _seg_loss_check(logits, target, hp, wp, H, W)
+    if teacher_logits.dtype != BF or teacher_logits.dim() != 3 or teacher_logits.shape[0] != B \
+            or teacher_logits.shape[1] != hp * wp + 1 or teacher_logits.shape[2] < nseg or teacher_logits.device != logits.device:
+        raise ValueError("%s: teacher_logits must be bf16 [B, hp*wp + 1, >= nseg] = [%d, %d, >= %d] on %s, got %s %s on %s"
+                         % (op, B, hp * wp + 1, nseg, logits.device, teacher_logits.dtype, tuple(teacher_logits.shape),
+                            teacher_logits.device))
+    hip.check_distill(weight, temperature, "all" if mask_all else "valid", op)
+    return B, nseg, npad
+
+
+@custom_op("ifseg::seg_distill", mutates_args=(), device_types="cuda")
+def seg_distill(logits: torch.Tensor, teacher_logits: torch.Tensor, target: Optional[torch.Tensor], hp: int, wp: int, H: int, W: int,
+                seg_id_offset: int, weight: float, temperature: float, mask_all: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """weight times the distillation loss of the x16 bilinear upsample of the per-patch logits against a teacher's (csrc/distill.hip:
+    hip.seg_distill; `criterions.seg_criterion.distill_loss_reference` is the specification): T^2 times the mean over the masked
+    pixels of KL(softmax(teacher / T) || softmax(student / T)).  logits and target as `seg_loss`; teacher_logits bf16
+    [B, hp*wp+1, >= nseg], a row-strided view allowed; mask_all: every pixel instead of the pixels whose target is a class (the
+    target may then be None).
+    -> (loss fp32 [], stats fp32 [2] = sum KL and the number of masked pixels,
+        dlogits bf16 [B, hp*wp+1, nseg rounded up to 8] = d loss / d logits, padding columns and the eos row zero), fresh tensors.
+    Differentiable in logits only: the teacher gets no gradient."""
+    B, nseg, npad = _seg_distill_check(logits, teacher_logits, target, hp, wp, H, W, weight, temperature, mask_all)
+    prev = _stream_scope(logits)
+    try:
+        dev, P = logits.device, hp * wp
+        lp = logits
+        if not (lp.stride(2) == 1 and lp.stride(1) % 8 == 0 and lp.stride(1) >= npad and lp.stride(0) % 8 == 0
+                and lp.data_ptr() % 16 == 0):
+            lp = torch.zeros(B, P + 1, npad, dtype=BF, device=dev)
+            lp[:, :, :nseg].copy_(logits)
+        tp = teacher_logits.detach()
+        if tp.stride(2) != 1:
+            tp = tp.contiguous()
+        bufs = {"dl": torch.empty(B, P + 1, npad, dtype=BF, device=dev)}
+        loss, dl = hip.seg_distill(lp, tp, target.contiguous() if target is not None else None, hp, wp, H, W, nseg, seg_id_offset,
+                                   weight, temperature, "all" if mask_all else "valid", bufs=bufs)
+        return loss.clone(), bufs["kd_stats"], dl
+    finally:
+        hip.set_stream(prev)
+
+
+@seg_distill.register_fake
+def _(logits, teacher_logits, target, hp, wp, H, W, seg_id_offset, weight, temperature, mask_all):
+    B, nseg, npad = _seg_distill_check(logits, teacher_logits, target, hp, wp, H, W, weight, temperature, mask_all)
+    f32 = torch.float32
+    return (logits.new_empty((), dtype=f32), logits.new_empty((2,), dtype=f32), logits.new_empty(B, hp * wp + 1, npad))
+
+
+def _skd_backward(ctx, gloss, gstats, gdl):
+    (dl,) = ctx.saved_tensors
+    return (torch.ops.ifseg.seg_loss_bwd(gloss, dl, ctx.nseg),) + (None,) * 10
+
+
+seg_distill.register_autograd(_skd_backward, setup_context=_sd_setup)
 
 
 # ----------------------------------------------------------------------------------------------- seg_predict

@@ -265,6 +265,48 @@ class SegmentationTask(TaskBase):
             return self.train_sample(images, labels, first_ordinal)
         return self.train_sample(images, labels, first_ordinal, weights=[r.weight.to(tf.device) for r in res])
 
+    def distill_sample(self, sample, model, teacher=None, trainer=None, full_context_alignment=False):
+        """`sample` plus `"teacher_logits"`: what `SegCriterion(distill_weight=)` trains `model` on -> a new dict, the sample's own
+        entries shared.  The teacher runs on `sample["net_input"]` in eval mode under `torch.no_grad()` and a CLONE of its padded
+        per-patch logits (bf16 [B, P+1, npad]) is attached: the buffer itself is the engine's workspace, the next forward
+        overwrites it.
+        `teacher`: another SegOFAModel on the same device (Large for a Base student, say); its training flag is restored
+        afterwards.  Another class count or feature grid than the student's: ValueError.
+        `trainer` (and no `teacher`): the Trainer of `model`, built with `Trainer(store_ema=True)` -- the student's own averaged
+        weights label the sample, inside `trainer.ema_weights()`, in eval mode (mean teacher with soft targets).  A trainer that
+        keeps no teacher or trains another model: ValueError, as is giving neither.
+        The sample is the static input of a captured step (`train_step(graph=True)`), so the tensor attached here is one too: a
+        caller who captures must copy new teacher logits INTO that tensor (`sample["teacher_logits"].copy_(...)`) instead of
+        attaching a fresh one.  A second model's engine shares the hardware queues with the student's, see README.
+        Not built: a fairseq command-line flag, a teacher at another grid or class set, feature-level distillation."""
+        if teacher is None and trainer is None:
+            raise ValueError("distill_sample: give `teacher` (a second model) or `trainer` (Trainer(store_ema=True) of `model`)")
+        if teacher is None:
+            if not getattr(trainer, "store_ema", False):
+                raise ValueError("distill_sample: `trainer` keeps no teacher (Trainer(store_ema=True)) and no `teacher` was given")
+            if trainer.model is not model:
+                raise ValueError("distill_sample: `trainer` trains another model than the one given")
+        net = teacher if teacher is not None else model
+        if teacher is not None:
+            n_t, n_s = teacher.decoder.seg_embed_tokens.weight.shape[0], model.decoder.seg_embed_tokens.weight.shape[0]
+            if n_t != n_s:
+                raise ValueError("distill_sample: the teacher has %d classes, the student %d" % (n_t, n_s))
+        was_training = net.training
+        net.eval()
+        try:
+            with torch.no_grad(), (trainer.ema_weights() if teacher is None else contextlib.nullcontext()):
+                _, extra = net(**sample["net_input"], full_context_alignment=full_context_alignment)
+                logits = extra["logits_padded"].clone()
+                grid = tuple(extra["encoder_returns"]["image_embed_shape"][0])
+        finally:
+            net.train(was_training)
+        if teacher is not None:
+            h, w = sample["net_input"]["patch_images"].shape[-2:]
+            # (the student's trunk has stride 16; at other image sizes the criterion's own shape check decides)
+            if h % 16 == 0 and w % 16 == 0 and (h // 16, w // 16) != grid:
+                raise ValueError("distill_sample: the teacher's feature grid is %s, the student's %s" % (grid, (h // 16, w // 16)))
+        return dict(sample, teacher_logits=logits)
+
     def inference_step(self, generator, models, sample, prefix_tokens=None, constraints=None):
         """fairseq_task.py `inference_step` -> [B, max_len] seg-class indices of the best beam (segmentation.py:266-268)"""
         with torch.no_grad():

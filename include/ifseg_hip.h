@@ -568,6 +568,28 @@ int ifseg_seg_dice_tiles(const void* logits, int ldl, long long logits_bs, const
 int ifseg_seg_loss_gather_sum(const float* ce_partial, const float* stats, const float* dice_partial, const float* dice_value,
                               void* dlogits, int ldl, long long dlogits_bs, int B, int hp, int wp, int nseg, float* loss_out,
                               void* stream);
+/* Distillation on the same x16 upsample (csrc/distill.hip; criterions/seg_criterion.py: distill_loss_reference states the rule).
+ * With s_i, t_i the upsampled student / teacher logits, p_i = softmax(s_i / T), q_i = softmax(t_i / T), M the pixels the loss
+ * kernel calls valid (mask_all = 0) or every pixel (mask_all != 0; target may then be NULL), N = |M| over the batch:
+ *   L_kd = T^2 (1 / N) sum_{i in M} KL(q_i || p_i),   d (w L_kd) / d s_ic = w (T / N) (p_ic - q_ic) on M.
+ * ifseg_seg_distill_tiles: teacher bf16 [B, >= hp*wp, ldt >= nseg] with strides of its own (its padding columns and eos row are
+ *   never read); tile_partial fp32 [B*hp*wp][9][nseg] = the adjoint of the interpolation applied to p - q on M, unnormalised;
+ *   kd_part fp32 [B*hp*wp][2] = every tile's sum of KL and its pixels in M.  ifseg_reduce_parts(outer = 1, parts = B*hp*wp, n = 2)
+ *   gives kd_stats [2] in a fixed order.
+ * ifseg_seg_loss_gather3: ifseg_seg_loss_gather_sum with a third source; any source may be NULL, not all three:
+ *   dlogits = bf16(CE partials * (1 / stats[1]) + Dice partials + KD partials * (kd_weight T / max(kd_stats[1], 1))) in one
+ *   rounding (eos row and padding columns zero), loss_out[4] = total, CE, Dice, KD = kd_weight T^2 kd_stats[0] / kd_stats[1]
+ *   (0 when kd_stats[1] = 0).
+ * One workgroup of 256 per cell, no atomics: two runs give equal bits.  Refusals, nothing launched: NULL / misaligned pointers, a
+ * source without its value / statistics, strides below a sample, kd_weight <= 0 or not finite: IFSEG_ERR_BAD_ARG; B, hp, wp < 1,
+ * H != 16 hp, W != 16 wp, nseg outside 1..512, ldl or ldt < nseg, B*hp*wp >= 2^31, T <= 0 or not finite: IFSEG_ERR_BAD_SHAPE. */
+int ifseg_seg_distill_tiles(const void* logits, int ldl, long long logits_bs, const void* teacher, int ldt, long long teacher_bs,
+                            const long long* target, long long target_bs, int B, int hp, int wp, int H, int W, int nseg,
+                            long long seg_id_offset, long long pad_id, long long eos_id, float temperature, int mask_all,
+                            float* tile_partial, float* kd_part, void* stream);
+int ifseg_seg_loss_gather3(const float* ce_partial, const float* stats, const float* dice_partial, const float* dice_value,
+                           const float* kd_partial, const float* kd_stats, float kd_weight, float kd_temperature, void* dlogits,
+                           int ldl, long long dlogits_bs, int B, int hp, int wp, int nseg, float* loss_out, void* stream);
 
 /* ---------------------------------------------------- image-free samples */
 /* The artificial image of `--artificial-image-type rand_k-L-R` (data/mm_data/segmentation_dataset.py:303-345) and its collater
