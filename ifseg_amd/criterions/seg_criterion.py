@@ -382,99 +382,63 @@ def distill_grad_closed_form(scores_up, teacher_up, target, seg_id_offset, nseg,
 
 
 class _FusedSegLossFn(torch.autograd.Function):
-    """loss = mean CE(bilinear_x16(logits[:, :P]), target); backward hands out the gradient the
-    forward kernel already produced.  pixel_weight / class_weight / norm_pixels: the weighted kernel
-    (`weighted_loss_reference`); all of them None / False: the unweighted launch, as before they existed."""
+    """loss = mean CE(bilinear_x16(logits[:, :P]), target) (+ dice_weight * Dice) (+ distill_weight * KD) of the same upsampled
+    logits; backward hands out the gradient the forward kernels already produced.  pixel_weight / class_weight / norm_pixels: the
+    weighted CE kernel (`weighted_loss_reference`); all of them None / False: the unweighted launch, as before they existed.
+    dice = (dice_weight, dice_smooth, dice_class_weight) adds csrc/dice.hip's two passes (`hip.seg_loss_dice`),
+    kd = (teacher_pad, distill_weight, temperature, mask) csrc/distill.hip's tile pass (`hip.seg_loss_distill`); one gather sums
+    the gradients.  -> (total, CE, weighted Dice, weighted KD, stats), None for a term that is absent (CE too when it is the
+    total); only the total is differentiable, and only in the student."""
 
     @staticmethod
     def forward(ctx, logits, logits_pad, target, hp, wp, H, W, nseg, seg0, bufs, eps=0.0, pixel_weight=None,
-                class_weight=None, norm_pixels=False):
+                class_weight=None, norm_pixels=False, dice=None, kd=None):
         B = logits_pad.shape[0]
         dev = logits_pad.device
-        n_tiles = B * hp * wp
-        nstat = 2 + 3 * nseg
-        key = (B, hp, wp, nseg, logits_pad.shape[2], dev)
-        if bufs.get("key") != key:
+        key = (B, hp, wp, nseg, logits_pad.shape[2], dev, dice is not None, kd is not None)
+        fresh = bufs.get("key") != key
+        if fresh:
             bufs.clear()
             bufs["key"] = key
-            bufs["tile"] = torch.empty(n_tiles * 9 * nseg, dtype=torch.float32, device=dev)
-            bufs["sp"] = torch.empty(n_tiles * nstat, dtype=torch.float32, device=dev)
-            bufs["stats"] = torch.empty(nstat, dtype=torch.float32, device=dev)
-            bufs["dl"] = torch.empty_like(logits_pad)
-            bufs["loss"] = torch.empty(1, dtype=torch.float32, device=dev)
-            bufs["bad"] = torch.zeros(1, dtype=torch.int32, device=dev)
-        if pixel_weight is None and class_weight is None and not norm_pixels:
-            hip.seg_loss(logits_pad, target, hp, wp, H, W, nseg, seg0, bufs["tile"], bufs["sp"], bufs["stats"],
-                         bufs["dl"], bufs["loss"], bad_label=bufs["bad"], label_smoothing=float(eps))
+        weights = dict(pixel_weight=pixel_weight, class_weight=class_weight, norm_pixels=norm_pixels, label_smoothing=float(eps))
+        ce = dice_loss = kd_loss = None
+        if kd is not None:
+            dw, ds, dcw = dice if dice is not None else (None, 1.0, None)
+            loss4, dl = hip.seg_loss_distill(logits_pad, kd[0], target, hp, wp, H, W, nseg, seg0, kd[1], kd[2], kd[3], dice_weight=dw,
+                                             dice_smooth=ds, dice_class_weight=dcw, bufs=bufs, **weights)
+            total, ce, kd_loss = loss4[0].clone(), loss4[1].clone(), loss4[3].clone()
+            if dice is not None:
+                dice_loss = loss4[2].clone()
+        elif dice is not None:
+            loss3, dl = hip.seg_loss_dice(logits_pad, target, hp, wp, H, W, nseg, seg0, *dice, bufs=bufs, **weights)
+            total, ce, dice_loss = loss3[0].clone(), loss3[1].clone(), loss3[2].clone()
         else:
-            hip.seg_loss_weighted(logits_pad, target, hp, wp, H, W, nseg, seg0, bufs["tile"], bufs["sp"], bufs["stats"],
-                                  bufs["dl"], bufs["loss"], pixel_weight=pixel_weight, class_weight=class_weight,
-                                  norm_pixels=norm_pixels, bad_label=bufs["bad"], label_smoothing=float(eps))
-        ctx.dl = bufs["dl"]
+            if fresh:
+                n_tiles, nstat = B * hp * wp, 2 + 3 * nseg
+                bufs["tile"] = torch.empty(n_tiles * 9 * nseg, dtype=torch.float32, device=dev)
+                bufs["sp"] = torch.empty(n_tiles * nstat, dtype=torch.float32, device=dev)
+                bufs["stats"] = torch.empty(nstat, dtype=torch.float32, device=dev)
+                bufs["dl"] = torch.empty_like(logits_pad)
+                bufs["loss"] = torch.empty(1, dtype=torch.float32, device=dev)
+                bufs["bad"] = torch.zeros(1, dtype=torch.int32, device=dev)
+            dl = bufs["dl"]
+            args = (logits_pad, target, hp, wp, H, W, nseg, seg0, bufs["tile"], bufs["sp"], bufs["stats"], dl, bufs["loss"])
+            if pixel_weight is None and class_weight is None and not norm_pixels:
+                hip.seg_loss(*args, bad_label=bufs["bad"], label_smoothing=float(eps))
+            else:
+                hip.seg_loss_weighted(*args, bad_label=bufs["bad"], **weights)
+            total = bufs["loss"][0].clone()
+        ctx.dl = dl
         ctx.nseg = nseg
         # fresh tensors: callers keep them in logging outputs across calls (update_freq > 1, validation loops)
-        return bufs["loss"][0].clone(), bufs["stats"].clone()
-
-    @staticmethod
-    def backward(ctx, gloss, gstats):
-        g = ctx.dl[:, :, : ctx.nseg]
-        return (g * gloss.to(g.dtype),) + (None,) * 13
-
-
-class _FusedSegLossDiceFn(torch.autograd.Function):
-    """loss = CE + dice_weight * Dice of the same upsampled logits (`hip.seg_loss_dice`): `_FusedSegLossFn`'s CE launch, csrc/dice.hip's
-    two passes and one gather that sums both gradients.  -> (total, CE, weighted Dice, stats); only the total is differentiable."""
-
-    @staticmethod
-    def forward(ctx, logits, logits_pad, target, hp, wp, H, W, nseg, seg0, bufs, eps, pixel_weight, class_weight, norm_pixels,
-                dice_weight, dice_smooth, dice_class_weight):
-        B = logits_pad.shape[0]
-        key = (B, hp, wp, nseg, logits_pad.shape[2], logits_pad.device, "dice")
-        if bufs.get("key") != key:
-            bufs.clear()
-            bufs["key"] = key
-        loss3, dl = hip.seg_loss_dice(logits_pad, target, hp, wp, H, W, nseg, seg0, dice_weight, dice_smooth, dice_class_weight,
-                                      bufs=bufs, pixel_weight=pixel_weight, class_weight=class_weight, norm_pixels=norm_pixels,
-                                      label_smoothing=float(eps))
-        ctx.dl = dl
-        ctx.nseg = nseg
-        out = (loss3[0].clone(), loss3[1].clone(), loss3[2].clone(), bufs["stats"].clone())
-        ctx.mark_non_differentiable(*out[1:])
+        out = (total, ce, dice_loss, kd_loss, bufs["stats"].clone())
+        ctx.mark_non_differentiable(*(t for t in out[1:] if t is not None))
         return out
 
     @staticmethod
-    def backward(ctx, gloss, gce, gdice, gstats):
+    def backward(ctx, gloss, *_):
         g = ctx.dl[:, :, : ctx.nseg]
-        return (g * gloss.to(g.dtype),) + (None,) * 16
-
-
-class _FusedSegLossDistillFn(torch.autograd.Function):
-    """loss = CE (+ dice_weight * Dice) + distill_weight * KD of the same upsampled logits (`hip.seg_loss_distill`): `_FusedSegLossFn`'s
-    CE launch, csrc/dice.hip's passes when dice_weight is given, csrc/distill.hip's tile pass and one gather that sums the
-    gradients.  -> (total, CE, weighted Dice, weighted KD, stats); only the total is differentiable, and only in the student."""
-
-    @staticmethod
-    def forward(ctx, logits, logits_pad, teacher_pad, target, hp, wp, H, W, nseg, seg0, bufs, eps, pixel_weight, class_weight,
-                norm_pixels, dice_weight, dice_smooth, dice_class_weight, kd_weight, kd_temperature, kd_mask):
-        B = logits_pad.shape[0]
-        key = (B, hp, wp, nseg, logits_pad.shape[2], logits_pad.device, "distill", dice_weight is not None)
-        if bufs.get("key") != key:
-            bufs.clear()
-            bufs["key"] = key
-        loss4, dl = hip.seg_loss_distill(logits_pad, teacher_pad, target, hp, wp, H, W, nseg, seg0, kd_weight, kd_temperature, kd_mask,
-                                         dice_weight=dice_weight, dice_smooth=dice_smooth, dice_class_weight=dice_class_weight,
-                                         bufs=bufs, pixel_weight=pixel_weight, class_weight=class_weight, norm_pixels=norm_pixels,
-                                         label_smoothing=float(eps))
-        ctx.dl = dl
-        ctx.nseg = nseg
-        out = (loss4[0].clone(), loss4[1].clone(), loss4[2].clone(), loss4[3].clone(), bufs["stats"].clone())
-        ctx.mark_non_differentiable(*out[1:])
-        return out
-
-    @staticmethod
-    def backward(ctx, gloss, gce, gdice, gkd, gstats):
-        g = ctx.dl[:, :, : ctx.nseg]
-        return (g * gloss.to(g.dtype),) + (None,) * 20
+        return (g * gloss.to(g.dtype),) + (None,) * 15
 
 
 FUSED_MAX_CLASSES = 512      # csrc/loss.hip NS_MAX
@@ -663,9 +627,8 @@ class SegCriterion(CriterionBase):
         if (pad is not None and self.num_seg <= FUSED_MAX_CLASSES and target.shape[1] == h * w + 1):
             if not hasattr(self, "_bufs_imfree"):
                 self._bufs_imfree = {}
-            loss, _ = _FusedSegLossFn.apply(scores_low, pad, target.contiguous(), hp, wp, h, w, self.num_seg,
-                                            self.seg_id_offset, self._bufs_imfree, self.eps)
-            return loss
+            return _FusedSegLossFn.apply(scores_low, pad, target.contiguous(), hp, wp, h, w, self.num_seg,
+                                         self.seg_id_offset, self._bufs_imfree, self.eps)[0]
         scores = self.upsample_logits(scores_low.float(), hp, wp, h, w)[:, :-1]
         tgt = target[:, :-1]
         scores = scores.reshape(-1, scores.shape[-1])
@@ -714,39 +677,22 @@ class SegCriterion(CriterionBase):
                 setattr(self, bufs_name, {})
             if self.ohem_thresh is not None and model.training:
                 pw = self._ohem_plane(pad, target.contiguous(), pw, hp, wp, h, w, bufs_name + "_ohem")
-            dice = kd = None
+            bufs = getattr(self, bufs_name)
             teacher = self._teacher_logits(model, sample, scores_low, hp * wp)
-            if teacher is not None:
-                weighted = pw is not None or self.class_weight is not None
-                loss, ce, dice, kd, stats = _FusedSegLossDistillFn.apply(
-                    scores_low, pad, teacher, target.contiguous(), hp, wp, h, w, self.num_seg, self.seg_id_offset,
-                    getattr(self, bufs_name), self.eps, pw.contiguous() if pw is not None else None,
-                    self._class_weight_on(pad.device) if weighted else None, self.norm_pixels and weighted, self.dice_weight,
-                    self.dice_smooth, self._dice_class_weight_on(pad.device), self.distill_weight, self.distill_temperature,
-                    self.distill_mask)
-                self.distill_stats = getattr(self, bufs_name)["kd_stats"]
-                if self.dice_weight is not None:
-                    self.dice_sums = getattr(self, bufs_name)["dice_sums"]
-                else:
-                    dice = None
-            elif self.dice_weight is not None:
-                weighted = pw is not None or self.class_weight is not None
-                loss, ce, dice, stats = _FusedSegLossDiceFn.apply(
-                    scores_low, pad, target.contiguous(), hp, wp, h, w, self.num_seg, self.seg_id_offset, getattr(self, bufs_name),
-                    self.eps, pw.contiguous() if pw is not None else None, self._class_weight_on(pad.device) if weighted else None,
-                    self.norm_pixels and weighted, self.dice_weight, self.dice_smooth, self._dice_class_weight_on(pad.device))
-                self.dice_sums = getattr(self, bufs_name)["dice_sums"]
-            elif pw is None and self.class_weight is None:
-                loss, stats = _FusedSegLossFn.apply(scores_low, pad, target.contiguous(), hp, wp, h, w, self.num_seg,
-                                                    self.seg_id_offset, getattr(self, bufs_name), self.eps)
-            else:
-                loss, stats = _FusedSegLossFn.apply(scores_low, pad, target.contiguous(), hp, wp, h, w, self.num_seg,
-                                                    self.seg_id_offset, getattr(self, bufs_name), self.eps,
-                                                    pw.contiguous() if pw is not None else None,
-                                                    self._class_weight_on(pad.device), self.norm_pixels)
+            weighted = pw is not None or self.class_weight is not None
+            loss, ce, dice, kd, stats = _FusedSegLossFn.apply(
+                scores_low, pad, target.contiguous(), hp, wp, h, w, self.num_seg, self.seg_id_offset, bufs, self.eps,
+                pw.contiguous() if pw is not None else None, self._weight_on("class_weight", pad.device) if weighted else None,
+                self.norm_pixels and weighted,
+                None if self.dice_weight is None else (self.dice_weight, self.dice_smooth, self._weight_on("dice_class_weight", pad.device)),
+                None if teacher is None else (teacher, self.distill_weight, self.distill_temperature, self.distill_mask))
+            if kd is not None:
+                self.distill_stats = bufs["kd_stats"]
+            if dice is not None:
+                self.dice_sums = bufs["dice_sums"]
             # the loss kernel flags labels that are neither a class nor pad / eos / ignore (read back without a sync)
             model.engine.deferred_check(
-                getattr(self, bufs_name)["bad"], lambda t: ((t[0] != 0).clone(), t.zero_())[0],
+                bufs["bad"], lambda t: ((t[0] != 0).clone(), t.zero_())[0],
                 "seg_criterion: target label outside [<seg_0>, <seg_%d>] (F.cross_entropy: target out of bounds)" % self.num_seg,
                 exc=IndexError, native=(hip.CHECK_FLAG, 0, 1))
             n = self.num_seg
@@ -780,12 +726,12 @@ class SegCriterion(CriterionBase):
             loss = F.cross_entropy(s, t, label_smoothing=self.eps)
         else:
             loss = weighted_loss_reference(scores[:, :h * w], target, self.seg_id_offset, self.num_seg,
-                                           self._class_weight_on(scores.device), pw, self.eps, self.weight_norm)
+                                           self._weight_on("class_weight", scores.device), pw, self.eps, self.weight_norm)
         metrics["nll_loss"] = loss
         if self.dice_weight is not None:
             self.dice_sums = dice_sums_reference(scores[:, :h * w], target, self.seg_id_offset, self.num_seg)
             dice = self.dice_weight * dice_loss_reference(scores[:, :h * w], target, self.seg_id_offset, self.num_seg,
-                                                          self.dice_smooth, self._dice_class_weight_on(scores.device))
+                                                          self.dice_smooth, self._weight_on("dice_class_weight", scores.device))
             metrics["dice_loss"] = dice
             loss = loss + dice
         teacher = self._teacher_logits(model, sample, scores_low, hp * wp)
@@ -839,18 +785,12 @@ class SegCriterion(CriterionBase):
         self.ohem_info = ob["info"]
         return ob["plane"]
 
-    def _class_weight_on(self, dev):
-        """the class weights on `dev` (moved there once), or None"""
-        cw = self.class_weight
+    def _weight_on(self, name, dev):
+        """the class weights kept as `self.<name>` (class_weight, dice_class_weight) on `dev` (moved there once), or None"""
+        cw = getattr(self, name)
         if cw is not None and cw.device != dev:
-            cw = self.class_weight = cw.to(dev)
-        return cw
-
-    def _dice_class_weight_on(self, dev):
-        """the Dice class weights on `dev` (moved there once), or None"""
-        cw = self.dice_class_weight
-        if cw is not None and cw.device != dev:
-            cw = self.dice_class_weight = cw.to(dev)
+            cw = cw.to(dev)
+            setattr(self, name, cw)
         return cw
 
     @staticmethod

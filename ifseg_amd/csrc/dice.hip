@@ -2,13 +2,13 @@
 // recipe (DiceLoss(smooth, exponent=2) beside CrossEntropyLoss), without the [B, H*W, nseg] score tensor.
 // criterions/seg_criterion.py states the rule (dice_sums_reference, dice_loss_reference); include/ifseg_hip.h the entry points.
 //
-// With p_ic = softmax_c(v_i) over the valid pixels i of sample b (loss.hip's predicate):
+// With p_ic = softmax_c(v_i) over the valid pixels i of sample b (seg_tile.h's predicate):
 //   I_bc = sum_i p_ic [y_i = c]   P_bc = sum_i p_ic^2   Y_bc = sum_i [y_i = c]      N = 2 I + s,  Q = P + Y + s
 //   dice_weight L_dice = sum_b sum_c k_c (1 - N_bc / Q_bc),   k_c = dice_weight w_c / (B n)
 // The gradient at a pixel needs the three sums of its whole sample: two passes with a device-side reduction between them.
 //
-//   seg_dice_sums_kernel   pass A.  loss.hip's tile: one workgroup per low-res cell = one 16 x 16 pixel tile, the 3 x 3 cells staged
-//                          in LDS at an odd row stride, the same four-tap value(c) in the same order, one online-softmax walk; a
+//   seg_dice_sums_kernel   pass A.  seg_tile.h's tile: one workgroup per low-res cell = one 16 x 16 pixel tile, the 3 x 3 cells staged
+//                          in LDS at an odd row stride, the four-tap value(c), one online-softmax walk; a
 //                          second walk in chunks of 16 classes puts p into sD[256][17] and reduces it over the tile in two fixed
 //                          steps (16 pixels of a row, then 16 rows; in fp64, rounded once) -> [tiles][3 n] fp32 partials.
 //                          ifseg_reduce_parts(outer = B, parts = hp wp, n = 3 n) gives sums [B][3][n].
@@ -16,20 +16,17 @@
 //                          the online softmax with T = sum_k exp(v_k - m)^2 e_bk carried beside the denominator (rescaled by
 //                          exp(m - v)^2 when the maximum moves), so that S_i = a_{b,y} p_y + 2 T / sum^2, and forms
 //                            d loss / d v_ic = p_ic (a_bc [y_i = c] + 2 p_ic e_bc - S_i)
-//                          on the valid pixels; loss.hip's separable adjoint (sD -> sE -> 9 x n) gives tile_partial [tiles][9][n] in
+//                          on the valid pixels; seg_tile.h's separable adjoint (sD -> sE -> 9 x n) gives tile_partial [tiles][9][n] in
 //                          final scale.  Workgroup 0 also sums k_c (1 - N / Q) over (b, c) in a fixed order into dice_out[0].
-//   seg_loss_gather_sum_kernel   loss.hip's gather with two sources: dlogits = bf16(ce_sum * (1 / Z) + dice_sum), one rounding,
-//                          loss_out = [total, ce, dice]; a null CE source is Dice alone.
+//   loss.hip's gather (ifseg_seg_loss_gather_sum) adds the partials to the CE's: dlogits = bf16(ce_sum * (1 / Z) + dice_sum), one
+//                          rounding, loss_out = [total, ce, dice]; a null CE source is Dice alone.
 // No global atomics: two runs give equal bits.  All LDS is dynamic, every carve offset a multiple of 16 bytes.
 #include <math.h>
-#include "common.h"
-#include "../../include/ifseg_hip.h"
+#include "seg_tile.h"
 
 namespace {
 
-constexpr int TS = 16;       // pixels per cell side
-constexpr int CH = 16;       // classes per chunk
-constexpr int NS_MAX = 512;  // max classes
+using namespace seg_tile;
 
 __host__ __device__ constexpr int r4(int x) { return (x + 3) & ~3; }
 
@@ -52,63 +49,6 @@ __host__ __device__ inline Carve carve(int nseg, bool pass_b) {
   return c;
 }
 
-// the 3 x 3 cells around (cy, cx) of sample b -> sLog[9][ls] (zeros outside the grid), and the tap weights of the tile's 16 rows
-// and 16 columns (source index of F.interpolate(mode='bilinear', align_corners=False): max((dst+0.5)/s-0.5, 0)) -- loss.hip's
-__device__ __forceinline__ void stage_tile(float* sLog, int ls, float (*sWY)[3], float (*sWX)[3], const bf16_t* logits, int ldl,
-                                           long long lbs, int b, int cy, int cx, int hp, int wp, int nseg) {
-  const int tid = threadIdx.x;
-  for (int i = tid; i < 9 * nseg; i += 256) {
-    const int k = i / nseg, c = i % nseg;
-    const int ry = cy - 1 + k / 3, rx = cx - 1 + k % 3;
-    float v = 0.f;
-    if (ry >= 0 && ry < hp && rx >= 0 && rx < wp) v = bf2f(logits[b * lbs + (long long)(ry * wp + rx) * ldl + c]);
-    sLog[k * ls + c] = v;
-  }
-  if (tid < 2 * TS) {
-    const bool isx = tid >= TS;
-    const int t = tid & (TS - 1);
-    const int c0 = isx ? cx : cy, lim = isx ? wp : hp;
-    float src = ((c0 * TS + t) + 0.5f) * (1.f / TS) - 0.5f;
-    src = fmaxf(src, 0.f);
-    const int i0 = (int)src;
-    const int i1 = min(i0 + 1, lim - 1);
-    const float l1 = src - i0, l0 = 1.f - l1;
-    const int s0 = i0 - (c0 - 1), s1 = i1 - (c0 - 1);
-    float* wrow = isx ? sWX[t] : sWY[t];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) wrow[k] = (k == s0 ? l0 : 0.f) + (k == s1 ? l1 : 0.f);
-  }
-}
-
-// the 2 x 2 non-zero taps among the 3 x 3 cells, accumulated in the order of loss.hip's value(c)
-struct Taps {
-  float wA, wB, wC, wD;
-  const float* lg;
-  int ls;
-  __device__ __forceinline__ Taps(const float* sLog, int ls_, const float (*sWY)[3], const float (*sWX)[3], int py, int px) {
-    const float wy0 = sWY[py][0], wy1 = sWY[py][1], wy2 = sWY[py][2];
-    const float wx0 = sWX[px][0], wx1 = sWX[px][1], wx2 = sWX[px][2];
-    const int kyl = (wy0 != 0.f) ? 0 : 1, kxl = (wx0 != 0.f) ? 0 : 1;
-    const float wya = kyl ? wy1 : wy0, wyb = kyl ? wy2 : wy1, wxa = kxl ? wx1 : wx0, wxb = kxl ? wx2 : wx1;
-    wA = wya * wxa; wB = wya * wxb; wC = wyb * wxa; wD = wyb * wxb;
-    ls = ls_;
-    lg = sLog + (kyl * 3 + kxl) * ls;
-  }
-  __device__ __forceinline__ float operator()(int c) const {
-    float v = 0.f;
-    v += wA * lg[c];
-    v += wB * lg[ls + c];
-    v += wC * lg[3 * ls + c];
-    v += wD * lg[4 * ls + c];
-    return v;
-  }
-};
-
-// the loss kernel's predicate: a class, not pad / eos / the ignore label
-__device__ __forceinline__ bool is_class(long long tg, long long seg0, int nseg, long long pad_id, long long eos_id) {
-  return !(tg == pad_id || tg == eos_id || tg == seg0 + nseg) && tg >= seg0 && tg < seg0 + nseg;
-}
-
 // ---- pass A: the tile's I_c, P_c, Y_c ----
 __global__ __launch_bounds__(256) void seg_dice_sums_kernel(const bf16_t* logits, int ldl, long long lbs, const long long* target,
                                                             long long tbs, int hp, int wp, int W, int nseg, long long seg0,
@@ -126,11 +66,12 @@ __global__ __launch_bounds__(256) void seg_dice_sums_kernel(const bf16_t* logits
   const int ncell = hp * wp;
   const int b = blockIdx.x / ncell, cell = blockIdx.x % ncell;
   const int cy = cell / wp, cx = cell % wp;
-  stage_tile(sLog, ls, sWY, sWX, logits, ldl, lbs, b, cy, cx, hp, wp, nseg);
+  stage_cells(sLog, ls, logits, ldl, lbs, b, cy, cx, hp, wp, nseg);
+  stage_weights(sWY, sWX, cy, cx, hp, wp);
   __syncthreads();
 
   const int py = tid >> 4, px = tid & 15;
-  const Taps value(sLog, ls, sWY, sWX, py, px);
+  const Taps value(ls, sWY, sWX, py, px);
   const long long tg = target[b * tbs + (long long)(cy * TS + py) * W + (cx * TS + px)];
   const bool valid = is_class(tg, seg0, nseg, pad_id, eos_id);
   sLab[tid] = valid ? (int)(tg - seg0) : -1;
@@ -141,7 +82,7 @@ __global__ __launch_bounds__(256) void seg_dice_sums_kernel(const bf16_t* logits
   float m = -INFINITY;
   double sum = 0.0;
   for (int c = 0; c < nseg; ++c) {
-    const float v = value(c);
+    const float v = value(sLog, c);
     if (v > m) { sum = sum * exp((double)(m - v)) + 1.0; m = v; }   // (rare: it scales the whole sum, so in fp64 as well)
     else sum += (double)expf(v - m);
   }
@@ -153,7 +94,7 @@ __global__ __launch_bounds__(256) void seg_dice_sums_kernel(const bf16_t* logits
 #pragma unroll
     for (int cc = 0; cc < CH; ++cc) {
       const int c = c0 + cc;
-      sD[tid][cc] = (valid && c < nseg) ? (float)((double)expf(value(c) - m) * rsum) : 0.f;
+      sD[tid][cc] = (valid && c < nseg) ? (float)((double)expf(value(sLog, c) - m) * rsum) : 0.f;
     }
     __syncthreads();
     {
@@ -204,7 +145,8 @@ __global__ __launch_bounds__(256) void seg_dice_tile_kernel(const bf16_t* logits
   const int cy = cell / wp, cx = cell % wp;
   const float kscale = dice_weight / ((float)B * (float)nseg);  // k_c = kscale w_c
 
-  stage_tile(sLog, ls, sWY, sWX, logits, ldl, lbs, b, cy, cx, hp, wp, nseg);
+  stage_cells(sLog, ls, logits, ldl, lbs, b, cy, cx, hp, wp, nseg);
+  stage_weights(sWY, sWX, cy, cx, hp, wp);
   for (int c = tid; c < nseg; c += 256) {
     const float* sb = sums + (long long)b * 3 * nseg;
     const float N = 2.f * sb[c] + smooth, Q = sb[nseg + c] + sb[2 * nseg + c] + smooth;
@@ -232,13 +174,13 @@ __global__ __launch_bounds__(256) void seg_dice_tile_kernel(const bf16_t* logits
   __syncthreads();
 
   const int py = tid >> 4, px = tid & 15;
-  const Taps value(sLog, ls, sWY, sWX, py, px);
+  const Taps value(ls, sWY, sWX, py, px);
   const long long tg = target[b * tbs + (long long)(cy * TS + py) * W + (cx * TS + px)];
   const bool valid = is_class(tg, seg0, nseg, pad_id, eos_id);
   const int label = valid ? (int)(tg - seg0) : 0;
   float m = -INFINITY, sum = 0.f, tt = 0.f, vl = 0.f;            // tt = sum_k exp(v_k - m)^2 e_k
   for (int c = 0; c < nseg; ++c) {
-    const float v = value(c);
+    const float v = value(sLog, c);
     const float ec = sEc[c];
     if (v > m) {
       const float r = __expf(m - v);
@@ -264,81 +206,13 @@ __global__ __launch_bounds__(256) void seg_dice_tile_kernel(const bf16_t* logits
       const int c = c0 + cc;
       float d = 0.f;
       if (valid && c < nseg) {
-        const float p = __expf(value(c) - lse);
+        const float p = __expf(value(sLog, c) - lse);
         d = p * ((c == label ? sA[c] : 0.f) + 2.f * p * sEc[c] - S);
       }
       sD[tid][cc] = d;
     }
-    __syncthreads();
-    for (int i = tid; i < TS * 3 * CH; i += 256) {          // E[py][kx][cc] = sum_px WX[px][kx] D[py,px][cc]
-      const int cc = i % CH, kx = (i / CH) % 3, yy = i / (3 * CH);
-      float e = 0.f;
-#pragma unroll
-      for (int xx = 0; xx < TS; ++xx) e += sWX[xx][kx] * sD[yy * TS + xx][cc];
-      sE[yy][kx][cc] = e;
-    }
-    __syncthreads();
-    if (tid < 9 * CH) {                                      // G[ky][kx][cc] = sum_py WY[py][ky] E[py][kx][cc]
-      const int cc = tid % CH, k = tid / CH, ky = k / 3, kx = k % 3;
-      float gsum = 0.f;
-#pragma unroll
-      for (int yy = 0; yy < TS; ++yy) gsum += sWY[yy][ky] * sE[yy][kx][cc];
-      if (c0 + cc < nseg) tp[k * nseg + c0 + cc] = gsum;
-    }
-    __syncthreads();
+    adjoint_chunk(sD, sE, sWY, sWX, tp, c0, nseg);
   }
-}
-
-// dlogits[b, cell, c] = bf16((1/Z) sum of the <=9 CE partials + sum of the <=9 Dice partials); loss_out = [total, ce, dice]
-__global__ void seg_loss_gather_sum_kernel(const float* ce_partial, const float* stats, const float* dice_partial,
-                                           const float* dice_value, bf16_t* dlogits, int ldl, long long dbs, int B, int hp, int wp,
-                                           int nseg, float* loss_out) {
-  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const int ncell = hp * wp;
-  const long long total = (long long)B * (ncell + 1) * ldl;
-  if (gid == 0) {
-    const float ce = ce_partial ? (stats[1] > 0.f ? stats[0] / stats[1] : 0.f) : 0.f;
-    const float dv = dice_value[0];
-    loss_out[0] = ce + dv;
-    loss_out[1] = ce;
-    loss_out[2] = dv;
-  }
-  if (gid >= total) return;
-  const int c = (int)(gid % ldl);
-  const long long r = gid / ldl;
-  const int cell = (int)(r % (ncell + 1)), b = (int)(r / (ncell + 1));
-  float g = 0.f;
-  if (cell < ncell && c < nseg) {
-    const int cy = cell / wp, cx = cell % wp;
-    float gd = 0.f;
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky) {
-      const int ty = cy - (ky - 1);
-      if (ty < 0 || ty >= hp) continue;
-#pragma unroll
-      for (int kx = 0; kx < 3; ++kx) {
-        const int tx = cx - (kx - 1);
-        if (tx < 0 || tx >= wp) continue;
-        const long long at = (((long long)b * ncell + ty * wp + tx) * 9 + ky * 3 + kx) * nseg + c;
-        if (ce_partial) g += ce_partial[at];
-        gd += dice_partial[at];
-      }
-    }
-    if (ce_partial) g *= stats[1] > 0.f ? 1.f / stats[1] : 0.f;
-    g += gd;
-  }
-  dlogits[b * dbs + (long long)cell * ldl + c] = f2bf(g);
-}
-
-// the refusals the three tile launches share
-int check_tile_args(const void* logits, int ldl, long long logits_bs, const long long* target, long long target_bs, int B, int hp,
-                    int wp, int H, int W, int nseg) {
-  if (!logits || !target || ((size_t)logits & 1) || ((size_t)target & 7)) return IFSEG_ERR_BAD_ARG;
-  if (B < 1 || hp < 1 || wp < 1 || H != hp * TS || W != wp * TS || nseg > NS_MAX || nseg < 1 || ldl < nseg ||
-      (long long)B * hp * wp >= (1ll << 31))
-    return IFSEG_ERR_BAD_SHAPE;
-  if (target_bs < (long long)H * W || logits_bs < (long long)hp * wp * ldl) return IFSEG_ERR_BAD_ARG;
-  return 0;
 }
 
 }  // namespace
@@ -370,24 +244,6 @@ extern "C" int ifseg_seg_dice_tiles(const void* logits, int ldl, long long logit
   hipLaunchKernelGGL(seg_dice_tile_kernel, dim3(B * hp * wp), dim3(256), dyn, (hipStream_t)stream, (const bf16_t*)logits, ldl,
                      logits_bs, target, target_bs, B, hp, wp, W, nseg, seg_id_offset, pad_id, eos_id, sums, class_weight,
                      dice_weight, smooth, tile_partial, dice_out);
-  IFSEG_CHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int ifseg_seg_loss_gather_sum(const float* ce_partial, const float* stats, const float* dice_partial,
-                                         const float* dice_value, void* dlogits, int ldl, long long dlogits_bs, int B, int hp,
-                                         int wp, int nseg, float* loss_out, void* stream) {
-  (void)hipGetLastError();
-  if (!dice_partial || !dice_value || !dlogits || !loss_out || (ce_partial && !stats) || ((size_t)ce_partial & 3) ||
-      ((size_t)stats & 3) || ((size_t)dice_partial & 3) || ((size_t)dice_value & 3) || ((size_t)dlogits & 1) ||
-      ((size_t)loss_out & 3))
-    return IFSEG_ERR_BAD_ARG;
-  if (B < 1 || hp < 1 || wp < 1 || nseg > NS_MAX || nseg < 1 || ldl < nseg || (long long)B * hp * wp >= (1ll << 31))
-    return IFSEG_ERR_BAD_SHAPE;
-  if (dlogits_bs < (long long)(hp * wp + 1) * ldl) return IFSEG_ERR_BAD_ARG;
-  const long long total = (long long)B * (hp * wp + 1) * ldl;
-  hipLaunchKernelGGL(seg_loss_gather_sum_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     ce_partial, stats, dice_partial, dice_value, (bf16_t*)dlogits, ldl, dlogits_bs, B, hp, wp, nseg, loss_out);
   IFSEG_CHECK_LAUNCH();
   return 0;
 }

@@ -2,8 +2,8 @@
 // producer of the uint8 weight plane ifseg_seg_loss_tiles_weighted reads.  criterions/seg_criterion.py states the rule
 // (hardness_reference, ohem_reference); include/ifseg_hip.h the entry points.
 //
-//   seg_hardness_kernel   the front half of loss.hip's tile kernel: one workgroup per low-res cell = one 16 x 16 pixel tile, the
-//                         3 x 3 cells staged in LDS at an odd row stride, the same four-tap value(c) in the same order, one
+//   seg_hardness_kernel   the front half of loss.hip's tile kernel, from seg_tile.h: one workgroup per low-res cell = one 16 x 16
+//                         pixel tile, the 3 x 3 cells staged in LDS at an odd row stride, the four-tap value(c), one
 //                         online-softmax walk -> p = softmax(v)[y] clamped to <= 1, or -1 on a pixel that is no class, as an
 //                         fp32 plane [B, H*W].  The [B, H*W, nseg] scores are never built.
 //   the select            an exact k-th smallest over the candidates (bit patterns 0 .. 0x3F800000) of the whole batch by a
@@ -21,71 +21,34 @@
 // just copied, the apply launch the histogram of digit 0 -- so a call leaves the workspace as it found it.
 #include <string.h>
 #include "count.h"
-#include "../../include/ifseg_hip.h"
+#include "seg_tile.h"
 
 namespace {
 
 using namespace count;
-
-constexpr int TS = 16;       // pixels per cell side
-constexpr int NS_MAX = 512;  // max classes (LDS: 9 x (nseg | 1) floats, sized per launch)
+using namespace seg_tile;
 
 __global__ __launch_bounds__(256) void seg_hardness_kernel(const bf16_t* logits, int ldl, long long lbs, const long long* target,
                                                            long long tbs, int hp, int wp, int W, int nseg, long long seg0,
                                                            long long pad_id, long long eos_id, float* hardness, long long hbs) {
   extern __shared__ float dyn[];
-  const int ls = nseg | 1;                   // row stride of the 3 x 3 cells' logits: odd, so the four taps of a pixel
-  float* sLog = dyn;                         // (rows k apart) fall into different banks
+  const int ls = nseg | 1;
+  float* sLog = dyn;                         // [9][ls]
   __shared__ float sWY[TS][3], sWX[TS][3];
   const int tid = threadIdx.x;
   const int ncell = hp * wp;
   const int b = blockIdx.x / ncell, cell = blockIdx.x % ncell;
   const int cy = cell / wp, cx = cell % wp;
 
-  for (int i = tid; i < 9 * nseg; i += 256) {
-    const int k = i / nseg, c = i % nseg;
-    const int ry = cy - 1 + k / 3, rx = cx - 1 + k % 3;
-    float v = 0.f;
-    if (ry >= 0 && ry < hp && rx >= 0 && rx < wp) v = bf2f(logits[b * lbs + (long long)(ry * wp + rx) * ldl + c]);
-    sLog[k * ls + c] = v;
-  }
-  if (tid < 2 * TS) {
-    // source index of F.interpolate(mode='bilinear', align_corners=False): max((dst+0.5)/s-0.5, 0)
-    const bool isx = tid >= TS;
-    const int t = tid & (TS - 1);
-    const int c0 = isx ? cx : cy, lim = isx ? wp : hp;
-    float src = ((c0 * TS + t) + 0.5f) * (1.f / TS) - 0.5f;
-    src = fmaxf(src, 0.f);
-    const int i0 = (int)src;
-    const int i1 = min(i0 + 1, lim - 1);
-    const float l1 = src - i0, l0 = 1.f - l1;
-    const int s0 = i0 - (c0 - 1), s1 = i1 - (c0 - 1);
-    float* wrow = isx ? sWX[t] : sWY[t];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) wrow[k] = (k == s0 ? l0 : 0.f) + (k == s1 ? l1 : 0.f);
-  }
+  stage_cells(sLog, ls, logits, ldl, lbs, b, cy, cx, hp, wp, nseg);
+  stage_weights(sWY, sWX, cy, cx, hp, wp);
   __syncthreads();
 
   const int py = tid >> 4, px = tid & 15;
-  const float wy0 = sWY[py][0], wy1 = sWY[py][1], wy2 = sWY[py][2];
-  const float wx0 = sWX[px][0], wx1 = sWX[px][1], wx2 = sWX[px][2];
-  // the 2 x 2 non-zero taps among the 3 x 3 cells, in the order of loss.hip's value(c) (a copy: that file stays as it is)
-  const int kyl = (wy0 != 0.f) ? 0 : 1, kxl = (wx0 != 0.f) ? 0 : 1;
-  const float wya = kyl ? wy1 : wy0, wyb = kyl ? wy2 : wy1, wxa = kxl ? wx1 : wx0, wxb = kxl ? wx2 : wx1;
-  const float wA = wya * wxa, wB = wya * wxb, wC = wyb * wxa, wD = wyb * wxb;
-  const float* lg = sLog + (kyl * 3 + kxl) * ls;
-  auto value = [&](int c) {
-    float v = 0.f;
-    v += wA * lg[c];
-    v += wB * lg[ls + c];
-    v += wC * lg[3 * ls + c];
-    v += wD * lg[4 * ls + c];
-    return v;
-  };
+  const Taps value(ls, sWY, sWX, py, px);
   const long long pix = (long long)(cy * TS + py) * W + (cx * TS + px);
   const long long tg = target[b * tbs + pix];
-  // the loss kernel's predicate: a class, not pad / eos / the ignore label
-  const bool valid = !(tg == pad_id || tg == eos_id || tg == seg0 + nseg) && tg >= seg0 && tg < seg0 + nseg;
+  const bool valid = is_class(tg, seg0, nseg, pad_id, eos_id);
   const int label = valid ? (int)(tg - seg0) : 0;
   // p = exp(v_y - lse) as exp(v_y - m) / sum.  The plane feeds an order statistic and must sit within 4 e of the specification,
   // e a fraction of an ulp of p at 150 classes: the accurate expf, the sum of up to 512 terms kept in fp64 (an fp32 running sum
@@ -93,7 +56,7 @@ __global__ __launch_bounds__(256) void seg_hardness_kernel(const bf16_t* logits,
   float m = -INFINITY, vl = 0.f;
   double sum = 0.0;
   for (int c = 0; c < nseg; ++c) {
-    const float v = value(c);
+    const float v = value(sLog, c);
     if (v > m) { sum = sum * exp((double)(m - v)) + 1.0; m = v; }   // (rare: it scales the whole sum, so in fp64 as well)
     else sum += (double)expf(v - m);
     if (c == label) vl = v;
@@ -267,13 +230,9 @@ extern "C" int ifseg_seg_hardness(const void* logits, int ldl, long long logits_
                                   int B, int hp, int wp, int H, int W, int nseg, long long seg_id_offset, long long pad_id,
                                   long long eos_id, float* hardness, long long hardness_bs, void* stream) {
   (void)hipGetLastError();
-  if (!logits || !target || !hardness || ((size_t)logits & 1) || ((size_t)target & 7) || ((size_t)hardness & 3))
-    return IFSEG_ERR_BAD_ARG;
-  if (B < 1 || hp < 1 || wp < 1 || H != hp * TS || W != wp * TS || nseg > NS_MAX || nseg < 1 || ldl < nseg ||
-      (long long)B * hp * wp >= (1ll << 31))
-    return IFSEG_ERR_BAD_SHAPE;
-  if (hardness_bs < (long long)H * W || target_bs < (long long)H * W || logits_bs < (long long)hp * wp * ldl)
-    return IFSEG_ERR_BAD_ARG;
+  if (!hardness || ((size_t)hardness & 3)) return IFSEG_ERR_BAD_ARG;
+  if (const int rc = check_tile_args(logits, ldl, logits_bs, target, target_bs, B, hp, wp, H, W, nseg)) return rc;
+  if (hardness_bs < (long long)H * W) return IFSEG_ERR_BAD_ARG;
   const size_t dyn = (size_t)(9 * (nseg | 1)) * 4;
   hipLaunchKernelGGL(seg_hardness_kernel, dim3(B * hp * wp), dim3(256), dyn, (hipStream_t)stream, (const bf16_t*)logits, ldl,
                      logits_bs, target, target_bs, hp, wp, W, nseg, seg_id_offset, pad_id, eos_id, hardness, hardness_bs);

@@ -961,20 +961,142 @@ def prof_read(kind):
     return {"kind": PROF_KINDS[kind], "ms": ms.value, "flops": fl.value, "bytes": by.value, "launches": n.value}
 
 
+# ---------------------------------------------------------------------- the fused segmentation criterion (csrc/seg_tile.h)
+# One 16 x 16 pixel tile per low-res cell, four sources of terms on it: cross entropy (csrc/loss.hip, plain or weighted), the OHEM
+# hardness plane (csrc/ohem.hip), Dice (csrc/dice.hip), distillation (csrc/distill.hip); one gather (csrc/loss.hip) sums the
+# gradients of the terms that are present.  The helpers below are what the public calls share.
+def _span(t):
+    """(first byte, one past the last byte) a view can touch, whatever its strides"""
+    n = 1 + sum((s - 1) * st for s, st in zip(t.shape, t.stride())) if t.numel() else 0
+    return t.data_ptr(), t.data_ptr() + n * t.element_size()
+
+
+def _seg_geometry(logits_pad, target, hp, wp, H, W, nseg, teacher=None, target_optional=False):
+    """what every tile call asserts of its logits, target (None allowed with target_optional) and teacher -> (B, device)"""
+    assert logits_pad.dtype == torch.bfloat16 and logits_pad.dim() == 3 and logits_pad.stride(2) == 1 and logits_pad.is_cuda \
+        and logits_pad.shape[1] >= hp * wp and logits_pad.stride(1) >= nseg, (logits_pad.dtype, tuple(logits_pad.shape), logits_pad.stride())
+    B, dev = logits_pad.shape[0], logits_pad.device
+    if teacher is not None:
+        assert torch.is_tensor(teacher) and teacher.dtype == torch.bfloat16 and teacher.dim() == 3 \
+            and teacher.device == dev and teacher.shape[0] == B and teacher.shape[1] >= hp * wp \
+            and teacher.shape[2] >= nseg and teacher.stride(2) == 1 and teacher.stride(1) >= nseg \
+            and (B == 1 or teacher.stride(0) >= hp * wp * teacher.stride(1)), \
+            "distill: the teacher's logits must be bf16 [%d, >= %d, >= %d] on %s, got %s" % (
+                B, hp * wp, nseg, dev, (teacher.dtype, tuple(teacher.shape), teacher.stride(), teacher.device)
+                if torch.is_tensor(teacher) else type(teacher))
+    if target is None:
+        assert target_optional, "distill: mask=\"valid\" needs the target"
+    else:
+        assert target.dtype == torch.int64 and target.dim() == 2 and target.shape[0] == B and target.shape[1] >= H * W \
+            and target.stride(1) == 1 and target.device == dev, (target.dtype, tuple(target.shape), target.stride(), target.device)
+    assert B >= 1 and hp >= 1 and wp >= 1 and H == 16 * hp and W == 16 * wp and 1 <= nseg <= 512, (B, hp, wp, H, W, nseg)
+    return B, dev
+
+
+def _seg_tile_args(logits_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, pad_id, eos_id):
+    """the 14 leading arguments of every tile entry point; a single sample's batch stride is the sample's extent"""
+    ld = logits_pad.stride(1)
+    return (_ptr(logits_pad), c_int(ld), c_ll(logits_pad.stride(0) if B > 1 else hp * wp * ld), _ptr(target),
+            c_ll(0 if target is None else target.stride(0) if B > 1 else H * W), c_int(B), c_int(hp), c_int(wp), c_int(H), c_int(W),
+            c_int(nseg), c_ll(seg_id_offset), c_ll(pad_id), c_ll(eos_id))
+
+
+def _seg_class_weight(class_weight, nseg, dev):
+    if class_weight is not None:
+        assert class_weight.dtype == torch.float32 and tuple(class_weight.shape) == (nseg,) and class_weight.is_contiguous() \
+            and class_weight.device == dev, (class_weight.dtype, tuple(class_weight.shape), class_weight.device)
+    return class_weight
+
+
+def _seg_bufs(bufs, logits_pad, target, B, hp, wp, nseg, names, teacher=None):
+    """the buffers `names` of a Dice / distillation call in `bufs` (a dict the caller keeps, or None): made on the first call,
+    checked on every call, overlap with the logits, the target and the teacher refused"""
+    bufs = {} if bufs is None else bufs
+    dev, tiles, f32 = logits_pad.device, B * hp * wp, torch.float32
+    shapes = {"dice_part": ((tiles * 3 * nseg,), f32), "dice_sums": ((B, 3, nseg), f32), "dice_tile": ((tiles * 9 * nseg,), f32),
+              "dice_val": ((1,), f32), "loss3": ((3,), f32), "dl": (None, torch.bfloat16),
+              "tile": ((tiles * 9 * nseg,), f32), "sp": ((tiles * (2 + 3 * nseg),), f32), "stats": ((2 + 3 * nseg,), f32),
+              "bad": ((1,), torch.int32),
+              "kd_tile": ((tiles * 9 * nseg,), f32), "kd_part": ((tiles * 2,), f32), "kd_stats": ((2,), f32), "loss4": ((4,), f32)}
+    for k in names:
+        shape, dt = shapes[k]
+        if k == "dl":
+            # the gradient has a layout of its own, whatever the logits' (a row-strided view [B, P+1, nseg] of a padded buffer
+            # included): the gather writes whole rows of stride(1) elements, hp * wp + 1 of them per sample
+            if k not in bufs:
+                bufs[k] = torch.empty(B, hp * wp + 1, logits_pad.stride(1), dtype=dt, device=dev)
+            t = bufs[k]
+            assert t.dtype == dt and t.device == dev and t.dim() == 3 and t.shape[0] == B and t.shape[1] == hp * wp + 1 \
+                and t.stride(2) == 1 and t.stride(1) == t.shape[2] >= nseg and (B == 1 or t.stride(0) >= t.shape[1] * t.stride(1)), \
+                (k, t.dtype, tuple(t.shape), t.stride(), t.device)
+        else:
+            if k not in bufs:
+                bufs[k] = (torch.zeros if k == "bad" else torch.empty)(shape, dtype=dt, device=dev)
+            t = bufs[k]
+            assert t.dtype == dt and tuple(t.shape) == shape and t.device == dev and t.is_contiguous(), \
+                (k, t.dtype, tuple(t.shape), t.stride(), t.device)
+        assert not _overlap(t, logits_pad) and (target is None or not _overlap(t, target)), \
+            "dice: buffer %r overlaps the logits or the target" % k
+    held = [bufs[k] for k in names]
+    assert not any(_overlap(a, b) for i, a in enumerate(held) for b in held[i + 1:]), "dice: two buffers overlap"
+    if teacher is not None:
+        t0, t1 = _span(teacher)
+        for k in names:
+            b0, b1 = _span(bufs[k])
+            assert not (b0 < t1 and t0 < b1), "distill: buffer %r overlaps the teacher's logits" % k
+    return bufs
+
+
+def _ce_tiles(logits_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, pixel_weight, class_weight, norm_pixels, bufs, pad_id, eos_id,
+              label_smoothing, weighted=None):
+    """the CE tile launch (csrc/loss.hip: the weighted instantiation when pixel_weight, class_weight or norm_pixels is given, or
+    for `seg_loss_weighted`, whatever it is given) and the reduction into bufs["tile"], bufs["sp"], bufs["stats"], bufs["bad"]"""
+    dev = logits_pad.device
+    if weighted is None:
+        weighted = pixel_weight is not None or class_weight is not None or bool(norm_pixels)
+    head = _seg_tile_args(logits_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, pad_id, eos_id)
+    tail = (_ptr(bufs["tile"]), _ptr(bufs["sp"]), _ptr(bufs["bad"]), c_float(label_smoothing), _stream())
+    if not weighted:
+        _check(lib().ifseg_seg_loss_tiles(*head, *tail), "seg_loss_tiles")
+    else:
+        pw_bs = 0
+        if pixel_weight is not None:
+            assert pixel_weight.dtype == torch.uint8 and tuple(pixel_weight.shape) == (B, H * W) and pixel_weight.stride(1) == 1 \
+                and pixel_weight.device == dev, (pixel_weight.dtype, tuple(pixel_weight.shape), pixel_weight.stride(), pixel_weight.device)
+            pw_bs = pixel_weight.stride(0) if B > 1 else H * W
+        _seg_class_weight(class_weight, nseg, dev)
+        _check(lib().ifseg_seg_loss_tiles_weighted(*head, _ptr(pixel_weight), c_ll(pw_bs), _ptr(class_weight),
+                                                   c_int(1 if norm_pixels else 0), *tail), "seg_loss_tiles_weighted")
+    reduce_parts(bufs["sp"], bufs["stats"], 1, B * hp * wp, 2 + 3 * nseg)
+
+
+def _seg_gather(bufs, ce, dice, kd, B, hp, wp, nseg):
+    """the one gather kernel through the entry point of the terms present: CE alone -> bufs["loss"] [1], with Dice ->
+    bufs["loss3"], with distillation (kd = (weight, temperature, ..)) -> bufs["loss4"]; the gradient goes to bufs["dl"]"""
+    dl = bufs["dl"]
+    out = (_ptr(dl), c_int(dl.stride(1)), c_ll(dl.stride(0)), c_int(B), c_int(hp), c_int(wp), c_int(nseg))
+    ce_src = (_ptr(bufs["tile"]), _ptr(bufs["stats"])) if ce else (None, None)
+    dice_src = (_ptr(bufs["dice_tile"]), _ptr(bufs["dice_val"])) if dice else (None, None)
+    if kd is not None:
+        loss = bufs["loss4"]
+        _check(lib().ifseg_seg_loss_gather3(*ce_src, *dice_src, _ptr(bufs["kd_tile"]), _ptr(bufs["kd_stats"]), c_float(kd[0]),
+                                            c_float(kd[1]), *out, _ptr(loss), _stream()), "seg_loss_gather3")
+    elif dice:
+        loss = bufs["loss3"]
+        _check(lib().ifseg_seg_loss_gather_sum(*ce_src, *dice_src, *out, _ptr(loss), _stream()), "seg_loss_gather_sum")
+    else:
+        loss = bufs["loss"]
+        _check(lib().ifseg_seg_loss_gather(*ce_src, *out, _ptr(loss), _stream()), "seg_loss_gather")
+    return loss, dl
+
+
 def seg_loss(logits_pad, target, hp, wp, H, W, nseg, seg_id_offset, tile_partial, stats_part, stats, dlogits_pad,
              loss_out, pad_id=1, eos_id=2, bad_label=None, label_smoothing=0.0):
     """fused upsample + CE + grad + histograms; logits_pad / dlogits_pad: bf16 [B, P+1, ldl]"""
     B = logits_pad.shape[0]
-    ldl = logits_pad.stride(1)
-    _check(lib().ifseg_seg_loss_tiles(_ptr(logits_pad), c_int(ldl), c_ll(logits_pad.stride(0)), _ptr(target),
-                                      c_ll(target.stride(0)), c_int(B), c_int(hp), c_int(wp), c_int(H), c_int(W),
-                                      c_int(nseg), c_ll(seg_id_offset), c_ll(pad_id), c_ll(eos_id),
-                                      _ptr(tile_partial), _ptr(stats_part), _ptr(bad_label), c_float(label_smoothing), _stream()), "seg_loss_tiles")
-    reduce_parts(stats_part, stats, 1, B * hp * wp, 2 + 3 * nseg)
-    _check(lib().ifseg_seg_loss_gather(_ptr(tile_partial), _ptr(stats), _ptr(dlogits_pad), c_int(dlogits_pad.stride(1)),
-                                       c_ll(dlogits_pad.stride(0)), c_int(B), c_int(hp), c_int(wp), c_int(nseg),
-                                       _ptr(loss_out), _stream()), "seg_loss_gather")
-    return loss_out
+    bufs = {"tile": tile_partial, "sp": stats_part, "stats": stats, "bad": bad_label, "dl": dlogits_pad, "loss": loss_out}
+    _ce_tiles(logits_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, None, None, False, bufs, pad_id, eos_id, label_smoothing)
+    return _seg_gather(bufs, True, False, None, B, hp, wp, nseg)[0]
 
 
 def seg_loss_weighted(logits_pad, target, hp, wp, H, W, nseg, seg_id_offset, tile_partial, stats_part, stats, dlogits_pad,
@@ -986,26 +1108,10 @@ def seg_loss_weighted(logits_pad, target, hp, wp, H, W, nseg, seg_id_offset, til
     weighted sum, stats[1] the normaliser Z (sum q cw[y], or qmax N_valid with norm_pixels), the histograms are the
     unweighted launch's; the reduction and the gather launch are `seg_loss`'s."""
     B = logits_pad.shape[0]
-    dev = logits_pad.device
-    pw_bs = 0
-    if pixel_weight is not None:
-        assert pixel_weight.dtype == torch.uint8 and tuple(pixel_weight.shape) == (B, H * W) and pixel_weight.stride(1) == 1 \
-            and pixel_weight.device == dev, (pixel_weight.dtype, tuple(pixel_weight.shape), pixel_weight.stride(), pixel_weight.device)
-        pw_bs = pixel_weight.stride(0) if B > 1 else H * W
-    if class_weight is not None:
-        assert class_weight.dtype == torch.float32 and tuple(class_weight.shape) == (nseg,) and class_weight.is_contiguous() \
-            and class_weight.device == dev, (class_weight.dtype, tuple(class_weight.shape), class_weight.device)
-    _check(lib().ifseg_seg_loss_tiles_weighted(_ptr(logits_pad), c_int(logits_pad.stride(1)), c_ll(logits_pad.stride(0)),
-                                               _ptr(target), c_ll(target.stride(0)), c_int(B), c_int(hp), c_int(wp), c_int(H),
-                                               c_int(W), c_int(nseg), c_ll(seg_id_offset), c_ll(pad_id), c_ll(eos_id),
-                                               _ptr(pixel_weight), c_ll(pw_bs), _ptr(class_weight),
-                                               c_int(1 if norm_pixels else 0), _ptr(tile_partial), _ptr(stats_part),
-                                               _ptr(bad_label), c_float(label_smoothing), _stream()), "seg_loss_tiles_weighted")
-    reduce_parts(stats_part, stats, 1, B * hp * wp, 2 + 3 * nseg)
-    _check(lib().ifseg_seg_loss_gather(_ptr(tile_partial), _ptr(stats), _ptr(dlogits_pad), c_int(dlogits_pad.stride(1)),
-                                       c_ll(dlogits_pad.stride(0)), c_int(B), c_int(hp), c_int(wp), c_int(nseg),
-                                       _ptr(loss_out), _stream()), "seg_loss_gather")
-    return loss_out
+    bufs = {"tile": tile_partial, "sp": stats_part, "stats": stats, "bad": bad_label, "dl": dlogits_pad, "loss": loss_out}
+    _ce_tiles(logits_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, pixel_weight, class_weight, norm_pixels, bufs, pad_id, eos_id,
+              label_smoothing, weighted=True)
+    return _seg_gather(bufs, True, False, None, B, hp, wp, nseg)[0]
 
 
 # ---------------------------------------------------------------------- online hard example mining
@@ -1018,21 +1124,14 @@ def seg_hardness(logits_pad, target, hp, wp, H, W, nseg, seg_id_offset, out=None
     the loss tile kernel): the softmax probability of every pixel's own label under the x16 bilinear upsample, clamped to <= 1,
     and -1 where the target is no class (`seg_loss`'s predicate).  `criterions.seg_criterion.hardness_reference` is the
     specification.  out: written in place when given (contiguous)."""
-    assert logits_pad.dtype == torch.bfloat16 and logits_pad.dim() == 3 and logits_pad.stride(2) == 1 \
-        and logits_pad.shape[1] >= hp * wp and logits_pad.stride(1) >= nseg, (logits_pad.dtype, tuple(logits_pad.shape), logits_pad.stride())
-    B, dev = logits_pad.shape[0], logits_pad.device
-    assert target.dtype == torch.int64 and target.dim() == 2 and target.shape[0] == B and target.shape[1] >= H * W \
-        and target.stride(1) == 1 and target.device == dev, (target.dtype, tuple(target.shape), target.stride(), target.device)
-    assert B >= 1 and hp >= 1 and wp >= 1 and H == 16 * hp and W == 16 * wp and 1 <= nseg <= 512, (B, hp, wp, H, W, nseg)
+    B, dev = _seg_geometry(logits_pad, target, hp, wp, H, W, nseg)
     if out is None:
         out = torch.empty(B, H * W, dtype=torch.float32, device=dev)
     assert out.dtype == torch.float32 and tuple(out.shape) == (B, H * W) and out.is_contiguous() and out.device == dev, \
         (out.dtype, tuple(out.shape), out.stride(), out.device)
     assert not _overlap(out, logits_pad) and not _overlap(out, target), "seg_hardness: out overlaps the logits or the target"
-    _check(lib().ifseg_seg_hardness(_ptr(logits_pad), c_int(logits_pad.stride(1)), c_ll(logits_pad.stride(0) if B > 1 else hp * wp * logits_pad.stride(1)),
-                                    _ptr(target), c_ll(target.stride(0) if B > 1 else H * W), c_int(B), c_int(hp), c_int(wp),
-                                    c_int(H), c_int(W), c_int(nseg), c_ll(seg_id_offset), c_ll(pad_id), c_ll(eos_id), _ptr(out),
-                                    c_ll(H * W), _stream()), "seg_hardness")
+    _check(lib().ifseg_seg_hardness(*_seg_tile_args(logits_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, pad_id, eos_id),
+                                    _ptr(out), c_ll(H * W), _stream()), "seg_hardness")
     return out
 
 
@@ -1098,82 +1197,66 @@ def check_dice(dice_weight, smooth, what="dice"):
     return check_dice_number("dice_weight", dice_weight, what), check_dice_number("dice_smooth", smooth, what)
 
 
-def _dice_geometry(logits_pad, target, hp, wp, H, W, nseg):
-    assert logits_pad.dtype == torch.bfloat16 and logits_pad.dim() == 3 and logits_pad.stride(2) == 1 and logits_pad.is_cuda \
-        and logits_pad.shape[1] >= hp * wp and logits_pad.stride(1) >= nseg, (logits_pad.dtype, tuple(logits_pad.shape), logits_pad.stride())
-    B, dev = logits_pad.shape[0], logits_pad.device
-    assert target.dtype == torch.int64 and target.dim() == 2 and target.shape[0] == B and target.shape[1] >= H * W \
-        and target.stride(1) == 1 and target.device == dev, (target.dtype, tuple(target.shape), target.stride(), target.device)
-    assert B >= 1 and hp >= 1 and wp >= 1 and H == 16 * hp and W == 16 * wp and 1 <= nseg <= 512, (B, hp, wp, H, W, nseg)
-    return B, dev
-
-
-def _dice_bufs(bufs, logits_pad, target, B, hp, wp, nseg, names):
-    """the buffers `names` of a Dice call in `bufs` (a dict the caller keeps): made on the first call, checked on every call"""
-    dev, tiles, f32 = logits_pad.device, B * hp * wp, torch.float32
-    shapes = {"dice_part": ((tiles * 3 * nseg,), f32), "dice_sums": ((B, 3, nseg), f32), "dice_tile": ((tiles * 9 * nseg,), f32),
-              "dice_val": ((1,), f32), "loss3": ((3,), f32), "dl": (None, torch.bfloat16),
-              "tile": ((tiles * 9 * nseg,), f32), "sp": ((tiles * (2 + 3 * nseg),), f32), "stats": ((2 + 3 * nseg,), f32),
-              "bad": ((1,), torch.int32),
-              "kd_tile": ((tiles * 9 * nseg,), f32), "kd_part": ((tiles * 2,), f32), "kd_stats": ((2,), f32), "loss4": ((4,), f32)}
-    for k in names:
-        shape, dt = shapes[k]
-        if k == "dl":
-            # the gradient has a layout of its own, whatever the logits' (a row-strided view [B, P+1, nseg] of a padded buffer
-            # included): the gather writes whole rows of stride(1) elements, hp * wp + 1 of them per sample
-            if k not in bufs:
-                bufs[k] = torch.empty(B, hp * wp + 1, logits_pad.stride(1), dtype=dt, device=dev)
-            t = bufs[k]
-            assert t.dtype == dt and t.device == dev and t.dim() == 3 and t.shape[0] == B and t.shape[1] == hp * wp + 1 \
-                and t.stride(2) == 1 and t.stride(1) == t.shape[2] >= nseg and (B == 1 or t.stride(0) >= t.shape[1] * t.stride(1)), \
-                (k, t.dtype, tuple(t.shape), t.stride(), t.device)
-        else:
-            if k not in bufs:
-                bufs[k] = (torch.zeros if k == "bad" else torch.empty)(shape, dtype=dt, device=dev)
-            t = bufs[k]
-            assert t.dtype == dt and tuple(t.shape) == shape and t.device == dev and t.is_contiguous(), \
-                (k, t.dtype, tuple(t.shape), t.stride(), t.device)
-        assert not _overlap(t, logits_pad) and (target is None or not _overlap(t, target)), \
-            "dice: buffer %r overlaps the logits or the target" % k
-    held = [bufs[k] for k in names]
-    assert not any(_overlap(a, b) for i, a in enumerate(held) for b in held[i + 1:]), "dice: two buffers overlap"
-    return bufs
-
-
-def _dice_tile_args(logits_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, pad_id, eos_id):
-    ld = logits_pad.stride(1)
-    return (_ptr(logits_pad), c_int(ld), c_ll(logits_pad.stride(0) if B > 1 else hp * wp * ld), _ptr(target),
-            c_ll(target.stride(0) if B > 1 else H * W), c_int(B), c_int(hp), c_int(wp), c_int(H), c_int(W), c_int(nseg),
-            c_ll(seg_id_offset), c_ll(pad_id), c_ll(eos_id))
-
-
 def seg_dice_sums(logits_pad, target, hp, wp, H, W, nseg, seg_id_offset, bufs=None, pad_id=1, eos_id=2):
     """logits_pad bf16 [B, P+1, ldl], target int64 [B, H*W (+1)] -> fp32 [B, 3, nseg] in two launches (csrc/dice.hip pass A, then
     `reduce_parts` over a sample's tiles, a fixed order): per sample and class I = sum p [y = c], P = sum p^2, Y = sum [y = c] over
     the valid pixels (`seg_loss`'s predicate), p the softmax of the x16 bilinear upsample.
     `criterions.seg_criterion.dice_sums_reference` is the specification.  bufs: a dict the caller keeps between calls (the result
     is bufs["dice_sums"]); nothing is allocated after the first call with it."""
-    B, dev = _dice_geometry(logits_pad, target, hp, wp, H, W, nseg)
-    bufs = _dice_bufs({} if bufs is None else bufs, logits_pad, target, B, hp, wp, nseg, ("dice_part", "dice_sums"))
-    _check(lib().ifseg_seg_dice_sums(*_dice_tile_args(logits_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, pad_id, eos_id),
+    B, dev = _seg_geometry(logits_pad, target, hp, wp, H, W, nseg)
+    bufs = _seg_bufs(bufs, logits_pad, target, B, hp, wp, nseg, ("dice_part", "dice_sums"))
+    _check(lib().ifseg_seg_dice_sums(*_seg_tile_args(logits_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, pad_id, eos_id),
                                      _ptr(bufs["dice_part"]), _stream()), "seg_dice_sums")
     reduce_parts(bufs["dice_part"], bufs["dice_sums"], B, hp * wp, 3 * nseg)
     return bufs["dice_sums"]
 
 
-def _dice_class_weight(class_weight, nseg, dev):
-    if class_weight is not None:
-        assert class_weight.dtype == torch.float32 and tuple(class_weight.shape) == (nseg,) and class_weight.is_contiguous() \
-            and class_weight.device == dev, (class_weight.dtype, tuple(class_weight.shape), class_weight.device)
-    return class_weight
-
-
 def _dice_tiles(logits_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, dice_weight, smooth, class_weight, bufs, pad_id, eos_id):
     """pass A, the reduction and pass B into bufs["dice_sums"], bufs["dice_tile"], bufs["dice_val"]"""
     seg_dice_sums(logits_pad, target, hp, wp, H, W, nseg, seg_id_offset, bufs, pad_id, eos_id)
-    _check(lib().ifseg_seg_dice_tiles(*_dice_tile_args(logits_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, pad_id, eos_id),
+    _check(lib().ifseg_seg_dice_tiles(*_seg_tile_args(logits_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, pad_id, eos_id),
                                       _ptr(bufs["dice_sums"]), _ptr(class_weight), c_float(dice_weight), c_float(smooth),
                                       _ptr(bufs["dice_tile"]), _ptr(bufs["dice_val"]), _stream()), "seg_dice_tiles")
+
+
+def _distill_tiles(logits_pad, teacher_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, temperature, mask_all, bufs, pad_id, eos_id):
+    """the KD tile launch and the reduction into bufs["kd_tile"], bufs["kd_part"], bufs["kd_stats"]"""
+    head = _seg_tile_args(logits_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, pad_id, eos_id)
+    ldt = teacher_pad.stride(1)
+    _check(lib().ifseg_seg_distill_tiles(
+        *head[:3], _ptr(teacher_pad), c_int(ldt), c_ll(teacher_pad.stride(0) if B > 1 else hp * wp * ldt), *head[3:],
+        c_float(temperature), c_int(1 if mask_all else 0), _ptr(bufs["kd_tile"]), _ptr(bufs["kd_part"]), _stream()), "seg_distill_tiles")
+    reduce_parts(bufs["kd_part"], bufs["kd_stats"], 1, B * hp * wp, 2)
+
+
+_CE_BUFS = ("tile", "sp", "stats", "bad")
+_DICE_BUFS = ("dice_part", "dice_sums", "dice_tile", "dice_val")
+_KD_BUFS = ("kd_tile", "kd_part", "kd_stats")
+
+
+def _seg_terms(logits_pad, teacher_pad, target, hp, wp, H, W, nseg, seg_id_offset, ce, dice, kd, bufs, pad_id, eos_id):
+    """The terms that are present on one gradient: each term's own tile launches and reduction, in the order CE, Dice,
+    distillation, then the gather entry of that set -> (bufs["loss4"] with distillation, else bufs["loss3"]; bufs["dl"]).
+    ce: None or (pixel_weight, class_weight, norm_pixels, label_smoothing); dice: None or (dice_weight, smooth, class_weight);
+    kd: None or (weight, temperature, mask_all) -- every number already validated by the caller."""
+    B, dev = _seg_geometry(logits_pad, target, hp, wp, H, W, nseg, teacher=teacher_pad if kd is not None else None,
+                           target_optional=kd is not None and kd[2] and ce is None and dice is None)
+    if ce is not None:
+        assert target.shape[1] == H * W + 1, tuple(target.shape)
+    if dice is not None:
+        _seg_class_weight(dice[2], nseg, dev)
+    if kd is not None:
+        names = _KD_BUFS + ("loss4", "dl") + (_CE_BUFS if ce is not None else ()) + (_DICE_BUFS if dice is not None else ())
+    else:
+        names = _DICE_BUFS + ("loss3", "dl") + (_CE_BUFS if ce is not None else ())
+    bufs = _seg_bufs(bufs, logits_pad, target, B, hp, wp, nseg, names, teacher=teacher_pad if kd is not None else None)
+    if ce is not None:
+        _ce_tiles(logits_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, ce[0], ce[1], ce[2], bufs, pad_id, eos_id, ce[3])
+    if dice is not None:
+        _dice_tiles(logits_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, dice[0], dice[1], dice[2], bufs, pad_id, eos_id)
+    if kd is not None:
+        _distill_tiles(logits_pad, teacher_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, kd[1], kd[2], bufs, pad_id, eos_id)
+    return _seg_gather(bufs, ce is not None, dice is not None, kd, B, hp, wp, nseg)
 
 
 def seg_dice(logits_pad, target, hp, wp, H, W, nseg, seg_id_offset, dice_weight, smooth=1.0, class_weight=None, bufs=None,
@@ -1182,17 +1265,9 @@ def seg_dice(logits_pad, target, hp, wp, H, W, nseg, seg_id_offset, dice_weight,
     -> (loss fp32 [] = dice_weight * `criterions.seg_criterion.dice_loss_reference`, dlogits_pad bf16 [B, hp*wp+1, ld >= nseg] = its
     gradient, padding columns and the eos row zero).  class_weight fp32 [nseg] (non-negative and finite: the caller's duty) or
     None.  bufs as `seg_dice_sums` (loss is bufs["loss3"][0], the gradient bufs["dl"], the sums bufs["dice_sums"])."""
-    dice_weight, smooth = check_dice(dice_weight, smooth, "seg_dice")
-    B, dev = _dice_geometry(logits_pad, target, hp, wp, H, W, nseg)
-    _dice_class_weight(class_weight, nseg, dev)
-    bufs = _dice_bufs({} if bufs is None else bufs, logits_pad, target, B, hp, wp, nseg,
-                      ("dice_part", "dice_sums", "dice_tile", "dice_val", "loss3", "dl"))
-    _dice_tiles(logits_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, dice_weight, smooth, class_weight, bufs, pad_id, eos_id)
-    dl = bufs["dl"]
-    _check(lib().ifseg_seg_loss_gather_sum(None, None, _ptr(bufs["dice_tile"]), _ptr(bufs["dice_val"]), _ptr(dl), c_int(dl.stride(1)),
-                                           c_ll(dl.stride(0)), c_int(B), c_int(hp), c_int(wp), c_int(nseg), _ptr(bufs["loss3"]),
-                                           _stream()), "seg_loss_gather_sum")
-    return bufs["loss3"][0], dl
+    dice = check_dice(dice_weight, smooth, "seg_dice") + (class_weight,)
+    loss3, dl = _seg_terms(logits_pad, None, target, hp, wp, H, W, nseg, seg_id_offset, None, dice, None, bufs, pad_id, eos_id)
+    return loss3[0], dl
 
 
 def seg_loss_dice(logits_pad, target, hp, wp, H, W, nseg, seg_id_offset, dice_weight, smooth=1.0, dice_class_weight=None, bufs=None,
@@ -1202,43 +1277,9 @@ def seg_loss_dice(logits_pad, target, hp, wp, H, W, nseg, seg_id_offset, dice_we
     two-source gather -> (loss_out fp32 [3] = total, CE, weighted Dice; dlogits_pad bf16 = d total / d logits, one rounding).
     loss_out[1] and bufs["stats"] are the bits the CE call gives alone.  bufs as `seg_dice_sums`; it also holds the CE call's
     tile / sp / stats / bad."""
-    dice_weight, smooth = check_dice(dice_weight, smooth, "seg_loss_dice")
-    B, dev = _dice_geometry(logits_pad, target, hp, wp, H, W, nseg)
-    assert target.shape[1] == H * W + 1, tuple(target.shape)
-    _dice_class_weight(dice_class_weight, nseg, dev)
-    bufs = _dice_bufs({} if bufs is None else bufs, logits_pad, target, B, hp, wp, nseg,
-                      ("dice_part", "dice_sums", "dice_tile", "dice_val", "loss3", "dl", "tile", "sp", "stats", "bad"))
-    dl = bufs["dl"]
-    _ce_tiles(logits_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, pixel_weight, class_weight, norm_pixels, bufs, pad_id, eos_id,
-              label_smoothing)
-    _dice_tiles(logits_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, dice_weight, smooth, dice_class_weight, bufs, pad_id, eos_id)
-    _check(lib().ifseg_seg_loss_gather_sum(_ptr(bufs["tile"]), _ptr(bufs["stats"]), _ptr(bufs["dice_tile"]), _ptr(bufs["dice_val"]),
-                                           _ptr(dl), c_int(dl.stride(1)), c_ll(dl.stride(0)), c_int(B), c_int(hp), c_int(wp),
-                                           c_int(nseg), _ptr(bufs["loss3"]), _stream()), "seg_loss_gather_sum")
-    return bufs["loss3"], dl
-
-
-def _ce_tiles(logits_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, pixel_weight, class_weight, norm_pixels, bufs, pad_id, eos_id,
-              label_smoothing):
-    """`seg_loss`'s tile launch (`seg_loss_weighted`'s when pixel_weight, class_weight or norm_pixels is given) and the reduction
-    into bufs["tile"], bufs["sp"], bufs["stats"], bufs["bad"]: the CE call's own launches, without its gather"""
-    dev, ld = logits_pad.device, logits_pad.stride(1)
-    weighted = pixel_weight is not None or class_weight is not None or bool(norm_pixels)
-    head = (_ptr(logits_pad), c_int(ld), c_ll(logits_pad.stride(0)), _ptr(target), c_ll(target.stride(0)), c_int(B), c_int(hp),
-            c_int(wp), c_int(H), c_int(W), c_int(nseg), c_ll(seg_id_offset), c_ll(pad_id), c_ll(eos_id))
-    tail = (_ptr(bufs["tile"]), _ptr(bufs["sp"]), _ptr(bufs["bad"]), c_float(label_smoothing), _stream())
-    if not weighted:
-        _check(lib().ifseg_seg_loss_tiles(*head, *tail), "seg_loss_tiles")
-    else:
-        pw_bs = 0
-        if pixel_weight is not None:
-            assert pixel_weight.dtype == torch.uint8 and tuple(pixel_weight.shape) == (B, H * W) and pixel_weight.stride(1) == 1 \
-                and pixel_weight.device == dev, (pixel_weight.dtype, tuple(pixel_weight.shape), pixel_weight.stride(), pixel_weight.device)
-            pw_bs = pixel_weight.stride(0) if B > 1 else H * W
-        _dice_class_weight(class_weight, nseg, dev)
-        _check(lib().ifseg_seg_loss_tiles_weighted(*head, _ptr(pixel_weight), c_ll(pw_bs), _ptr(class_weight),
-                                                   c_int(1 if norm_pixels else 0), *tail), "seg_loss_tiles_weighted")
-    reduce_parts(bufs["sp"], bufs["stats"], 1, B * hp * wp, 2 + 3 * nseg)
+    dice = check_dice(dice_weight, smooth, "seg_loss_dice") + (dice_class_weight,)
+    return _seg_terms(logits_pad, None, target, hp, wp, H, W, nseg, seg_id_offset,
+                      (pixel_weight, class_weight, norm_pixels, label_smoothing), dice, None, bufs, pad_id, eos_id)
 
 
 # ---------------------------------------------------------------------- distillation: per-pixel KL to a teacher
@@ -1257,64 +1298,6 @@ def check_distill(weight, temperature=1.0, mask="valid", who="distill"):
     return weight, temperature, mask == "all"
 
 
-def _span(t):
-    """(first byte, one past the last byte) a view can touch, whatever its strides"""
-    n = 1 + sum((s - 1) * st for s, st in zip(t.shape, t.stride())) if t.numel() else 0
-    return t.data_ptr(), t.data_ptr() + n * t.element_size()
-
-
-def _distill_geometry(logits_pad, teacher_pad, target, hp, wp, H, W, nseg, mask_all):
-    assert logits_pad.dtype == torch.bfloat16 and logits_pad.dim() == 3 and logits_pad.stride(2) == 1 and logits_pad.is_cuda \
-        and logits_pad.shape[1] >= hp * wp and logits_pad.stride(1) >= nseg, (logits_pad.dtype, tuple(logits_pad.shape), logits_pad.stride())
-    B, dev = logits_pad.shape[0], logits_pad.device
-    assert torch.is_tensor(teacher_pad) and teacher_pad.dtype == torch.bfloat16 and teacher_pad.dim() == 3 \
-        and teacher_pad.device == dev and teacher_pad.shape[0] == B and teacher_pad.shape[1] >= hp * wp \
-        and teacher_pad.shape[2] >= nseg and teacher_pad.stride(2) == 1 and teacher_pad.stride(1) >= nseg \
-        and (B == 1 or teacher_pad.stride(0) >= hp * wp * teacher_pad.stride(1)), \
-        "distill: the teacher's logits must be bf16 [%d, >= %d, >= %d] on %s, got %s" % (
-            B, hp * wp, nseg, dev, (teacher_pad.dtype, tuple(teacher_pad.shape), teacher_pad.stride(), teacher_pad.device)
-            if torch.is_tensor(teacher_pad) else type(teacher_pad))
-    if target is None:
-        assert mask_all, "distill: mask=\"valid\" needs the target"
-    else:
-        assert target.dtype == torch.int64 and target.dim() == 2 and target.shape[0] == B and target.shape[1] >= H * W \
-            and target.stride(1) == 1 and target.device == dev, (target.dtype, tuple(target.shape), target.stride(), target.device)
-    assert B >= 1 and hp >= 1 and wp >= 1 and H == 16 * hp and W == 16 * wp and 1 <= nseg <= 512, (B, hp, wp, H, W, nseg)
-    return B, dev
-
-
-def _distill_bufs(bufs, logits_pad, teacher_pad, target, B, hp, wp, nseg, names):
-    """`_dice_bufs` for a call with a teacher: made on the first call, checked on every call, overlap with the teacher refused"""
-    bufs = _dice_bufs({} if bufs is None else bufs, logits_pad, target, B, hp, wp, nseg, names)
-    t0, t1 = _span(teacher_pad)
-    for k in names:
-        b0, b1 = _span(bufs[k])
-        assert not (b0 < t1 and t0 < b1), "distill: buffer %r overlaps the teacher's logits" % k
-    return bufs
-
-
-def _distill_tiles(logits_pad, teacher_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, temperature, mask_all, bufs, pad_id, eos_id):
-    """the KD tile launch and the reduction into bufs["kd_tile"], bufs["kd_part"], bufs["kd_stats"]"""
-    ld, ldt = logits_pad.stride(1), teacher_pad.stride(1)
-    _check(lib().ifseg_seg_distill_tiles(
-        _ptr(logits_pad), c_int(ld), c_ll(logits_pad.stride(0) if B > 1 else hp * wp * ld), _ptr(teacher_pad), c_int(ldt),
-        c_ll(teacher_pad.stride(0) if B > 1 else hp * wp * ldt), _ptr(target),
-        c_ll(0 if target is None else target.stride(0) if B > 1 else H * W), c_int(B), c_int(hp), c_int(wp), c_int(H), c_int(W),
-        c_int(nseg), c_ll(seg_id_offset), c_ll(pad_id), c_ll(eos_id), c_float(temperature), c_int(1 if mask_all else 0),
-        _ptr(bufs["kd_tile"]), _ptr(bufs["kd_part"]), _stream()), "seg_distill_tiles")
-    reduce_parts(bufs["kd_part"], bufs["kd_stats"], 1, B * hp * wp, 2)
-
-
-def _gather3(bufs, ce, dice, weight, temperature, B, hp, wp, nseg):
-    dl = bufs["dl"]
-    _check(lib().ifseg_seg_loss_gather3(
-        _ptr(bufs["tile"]) if ce else None, _ptr(bufs["stats"]) if ce else None, _ptr(bufs["dice_tile"]) if dice else None,
-        _ptr(bufs["dice_val"]) if dice else None, _ptr(bufs["kd_tile"]), _ptr(bufs["kd_stats"]), c_float(weight),
-        c_float(temperature), _ptr(dl), c_int(dl.stride(1)), c_ll(dl.stride(0)), c_int(B), c_int(hp), c_int(wp), c_int(nseg),
-        _ptr(bufs["loss4"]), _stream()), "seg_loss_gather3")
-    return bufs["loss4"], dl
-
-
 def seg_distill(logits_pad, teacher_pad, target, hp, wp, H, W, nseg, seg_id_offset, weight, temperature=1.0, mask="valid", bufs=None,
                 pad_id=1, eos_id=2):
     """Distillation alone (csrc/distill.hip): tiles -> reduce -> gather, three launches, nothing read back, no atomics.
@@ -1323,13 +1306,10 @@ def seg_distill(logits_pad, teacher_pad, target, hp, wp, H, W, nseg, seg_id_offs
     -> (loss fp32 [] = weight * `criterions.seg_criterion.distill_loss_reference`, dlogits_pad bf16 [B, hp*wp+1, ld] = its gradient
     in the student's logits, padding columns and the eos row zero).  bufs: a dict the caller keeps between calls (the loss is
     bufs["loss4"][3], the gradient bufs["dl"], [sum KL, N] bufs["kd_stats"]); nothing is allocated after the first call with it."""
-    weight, temperature, mask_all = check_distill(weight, temperature, mask, "seg_distill")
-    if weight is None:
+    kd = check_distill(weight, temperature, mask, "seg_distill")
+    if kd[0] is None:
         raise ValueError("seg_distill: distill_weight must be a finite number > 0, got None")
-    B, dev = _distill_geometry(logits_pad, teacher_pad, target, hp, wp, H, W, nseg, mask_all)
-    bufs = _distill_bufs(bufs, logits_pad, teacher_pad, target, B, hp, wp, nseg, ("kd_tile", "kd_part", "kd_stats", "loss4", "dl"))
-    _distill_tiles(logits_pad, teacher_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, temperature, mask_all, bufs, pad_id, eos_id)
-    loss4, dl = _gather3(bufs, False, False, weight, temperature, B, hp, wp, nseg)
+    loss4, dl = _seg_terms(logits_pad, teacher_pad, target, hp, wp, H, W, nseg, seg_id_offset, None, None, kd, bufs, pad_id, eos_id)
     return loss4[3], dl
 
 
@@ -1342,26 +1322,15 @@ def seg_loss_distill(logits_pad, teacher_pad, target, hp, wp, H, W, nseg, seg_id
     -> (loss_out fp32 [4] = total, CE, weighted Dice, weighted KD; dlogits_pad bf16 = d total / d logits, one rounding).
     loss_out[1] and bufs["stats"] are the bits the CE call gives alone, loss_out[2] the bits `seg_loss_dice` gives, loss_out[3]
     the bits `seg_distill` gives.  bufs as `seg_distill`; it also holds the CE call's tile / sp / stats / bad and the Dice buffers."""
-    weight, temperature, mask_all = check_distill(weight, temperature, mask, "seg_loss_distill")
-    if weight is None:
+    kd = check_distill(weight, temperature, mask, "seg_loss_distill")
+    if kd[0] is None:
         raise ValueError("seg_loss_distill: distill_weight must be a finite number > 0, got None")
-    dice = dice_weight is not None
-    if dice:
-        dice_weight, dice_smooth = check_dice(dice_weight, dice_smooth, "seg_loss_distill")
+    dice = None
+    if dice_weight is not None:
+        dice = check_dice(dice_weight, dice_smooth, "seg_loss_distill") + (dice_class_weight,)
     assert target is not None, "seg_loss_distill: the cross entropy needs the target"
-    B, dev = _distill_geometry(logits_pad, teacher_pad, target, hp, wp, H, W, nseg, mask_all)
-    assert target.shape[1] == H * W + 1, tuple(target.shape)
-    _dice_class_weight(dice_class_weight, nseg, dev)
-    names = ("kd_tile", "kd_part", "kd_stats", "loss4", "dl", "tile", "sp", "stats", "bad") \
-        + (("dice_part", "dice_sums", "dice_tile", "dice_val") if dice else ())
-    bufs = _distill_bufs(bufs, logits_pad, teacher_pad, target, B, hp, wp, nseg, names)
-    _ce_tiles(logits_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, pixel_weight, class_weight, norm_pixels, bufs, pad_id, eos_id,
-              label_smoothing)
-    if dice:
-        _dice_tiles(logits_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, dice_weight, dice_smooth, dice_class_weight, bufs,
-                    pad_id, eos_id)
-    _distill_tiles(logits_pad, teacher_pad, target, B, hp, wp, H, W, nseg, seg_id_offset, temperature, mask_all, bufs, pad_id, eos_id)
-    return _gather3(bufs, True, dice, weight, temperature, B, hp, wp, nseg)
+    return _seg_terms(logits_pad, teacher_pad, target, hp, wp, H, W, nseg, seg_id_offset,
+                      (pixel_weight, class_weight, norm_pixels, label_smoothing), dice, kd, bufs, pad_id, eos_id)
 
 
 # ---------------------------------------------------------------------- eval post-processing

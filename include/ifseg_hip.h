@@ -497,7 +497,12 @@ int ifseg_maxpool3x3s2(const void* in, void* out, int B, int H, int W, int C, vo
  * gathers dlogits (bf16 [B, P+1, ldl], eos row and padding columns zero) scaled by 1/valid and
  * writes the mean loss.  target: int64 [B, H*W+1] dictionary ids; a pixel is ignored when its
  * target is pad, eos or <seg_nseg>.  label_smoothing in [0, 1]: F.cross_entropy's epsilon (seg_criterion.py:265; 0 = plain CE,
- * bit-identical to ABI <= 14).  Requires H == 16*hp, W == 16*wp, 1 <= nseg <= 512. */
+ * bit-identical to ABI <= 14).  Requires H == 16*hp, W == 16*wp, 1 <= nseg <= 512.  Every tile entry point of this section
+ * (csrc/seg_tile.h: check_tile_args) refuses NULL / misaligned logits or target and batch strides below a sample with
+ * IFSEG_ERR_BAD_ARG, B, hp, wp < 1, H != 16 hp, W != 16 wp, nseg outside 1..512, ldl < nseg, B*hp*wp >= 2^31 with
+ * IFSEG_ERR_BAD_SHAPE.  ifseg_seg_loss_gather, ifseg_seg_loss_gather_sum and ifseg_seg_loss_gather3 below are three doors of ONE
+ * kernel (csrc/loss.hip: seg_loss_gather_kernel), which sums the partials of the sources it is given -- a NULL source is not
+ * added as a zero -- and writes 1, 3 or 4 words of loss_out; this entry passes the CE source alone. */
 int ifseg_seg_loss_tiles(const void* logits, int ldl, long long logits_bs, const long long* target,
                          long long target_bs, int B, int hp, int wp, int H, int W, int nseg,
                          long long seg_id_offset, long long pad_id, long long eos_id, float* tile_partial,
@@ -515,8 +520,8 @@ int ifseg_seg_loss_gather(const float* tile_partial, const float* stats, void* d
  *                         else 1: a batch of unsure pixels gives a smaller gradient)
  * the histograms and bad_label count valid pixels whatever their weights, and tile_partial carries the weighted gradient, so
  * ifseg_reduce_parts and ifseg_seg_loss_gather follow unchanged: loss = stats[0] / stats[1], 0 with a zero gradient when
- * Z = 0.  No global atomics.  The refusals of ifseg_seg_loss_tiles; B, hp or wp < 1, pw_bs < H*W, class_weight not 4-byte
- * aligned: IFSEG_ERR_BAD_ARG. */
+ * Z = 0.  No global atomics.  The refusals of ifseg_seg_loss_tiles; pw_bs < H*W, class_weight not 4-byte aligned:
+ * IFSEG_ERR_BAD_ARG. */
 int ifseg_seg_loss_tiles_weighted(const void* logits, int ldl, long long logits_bs, const long long* target,
                                   long long target_bs, int B, int hp, int wp, int H, int W, int nseg,
                                   long long seg_id_offset, long long pad_id, long long eos_id,
@@ -552,7 +557,7 @@ int ifseg_ohem_select(const float* hardness, int B, long long n, float thresh, l
  *   parts = hp*wp, n = 3*nseg) gives sums [B][3][nseg] in a fixed order.
  * ifseg_seg_dice_tiles (pass B): from sums, tile_partial fp32 [B*hp*wp][9][nseg] = the adjoint of the interpolation applied to
  *   d (dice_weight L_dice) / d v, in final scale, and dice_out[0] = dice_weight L_dice (summed by workgroup 0 in a fixed order).
- * ifseg_seg_loss_gather_sum: ifseg_seg_loss_gather with two sources, dlogits = bf16(sum of the CE partials * (1 / stats[1]) +
+ * ifseg_seg_loss_gather_sum: ifseg_seg_loss_gather's kernel with two sources, dlogits = bf16(sum of the CE partials * (1 / stats[1]) +
  *   sum of the Dice partials) in one rounding (eos row and padding columns zero), loss_out[3] = total, CE (stats[0] / stats[1], 0
  *   when stats[1] = 0), Dice.  ce_partial NULL (stats is then not read): Dice alone, CE = 0.
  * One workgroup of 256 per cell, no atomics: two runs give equal bits.  Refusals, nothing launched: NULL / misaligned pointers
@@ -576,7 +581,8 @@ int ifseg_seg_loss_gather_sum(const float* ce_partial, const float* stats, const
  *   never read); tile_partial fp32 [B*hp*wp][9][nseg] = the adjoint of the interpolation applied to p - q on M, unnormalised;
  *   kd_part fp32 [B*hp*wp][2] = every tile's sum of KL and its pixels in M.  ifseg_reduce_parts(outer = 1, parts = B*hp*wp, n = 2)
  *   gives kd_stats [2] in a fixed order.
- * ifseg_seg_loss_gather3: ifseg_seg_loss_gather_sum with a third source; any source may be NULL, not all three:
+ * ifseg_seg_loss_gather3: ifseg_seg_loss_gather's kernel with all three sources; any source may be NULL, not all three (a NULL
+ *   source's term enters neither dlogits nor the total, its loss_out word is 0):
  *   dlogits = bf16(CE partials * (1 / stats[1]) + Dice partials + KD partials * (kd_weight T / max(kd_stats[1], 1))) in one
  *   rounding (eos row and padding columns zero), loss_out[4] = total, CE, Dice, KD = kd_weight T^2 kd_stats[0] / kd_stats[1]
  *   (0 when kd_stats[1] = 0).

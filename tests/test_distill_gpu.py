@@ -311,6 +311,43 @@ def test_entry_point_refusals():
     torch.cuda.synchronize()
 
 
+def test_gather_entries_are_one_kernel():
+    """one gather, three doors: on the same fp32 partials (seeded, made on the host) an entry with fewer sources writes the
+    `dlogits` bits and the `loss_out[0]` of `ifseg_seg_loss_gather3` with the other sources null; the eos row and the padding
+    columns are exactly zero in every call.  B = 2, 2 x 3 cells, 5 classes in rows of 8."""
+    from ifseg_amd import hip
+    dev = _dev()
+    B, hp, wp, nseg, ld = 2, 2, 3, 5, 8
+    g = torch.Generator().manual_seed(41)
+    tiles = B * hp * wp
+    ce, dice = (torch.randn(tiles * 9 * nseg, generator=g).to(dev) for _ in range(2))
+    stats = torch.cat([torch.tensor([731.5, 1400.0]), torch.zeros(3 * nseg)]).to(dev)           # CE sum, Z, the histograms
+    dval = (torch.rand(1, generator=g) + 0.5).to(dev)
+    lib, p = hip.lib(), hip._ptr
+    c_int, c_ll, c_float = ctypes.c_int, ctypes.c_longlong, ctypes.c_float
+
+    def call(entry, *sources, words):
+        dl = torch.full((B, hp * wp + 1, ld), 3.0, dtype=torch.bfloat16, device=dev)
+        lo = torch.full((words,), 7.0, device=dev)
+        rc = entry(*sources, p(dl), c_int(ld), c_ll(dl.stride(0)), c_int(B), c_int(hp), c_int(wp), c_int(nseg), p(lo), hip._stream())
+        assert rc == 0, rc
+        torch.cuda.synchronize()
+        assert bool((dl[:, hp * wp] == 0).all()) and bool((dl[:, :, nseg:] == 0).all())        # the eos row, the padding columns
+        assert float(dl[:, :hp * wp, :nseg].float().abs().min()) > 0.0                           # and everything else is written
+        return dl.view(torch.int16), lo
+
+    no_kd = (None, None, c_float(1.0), c_float(1.0))
+    for name, few, three in (
+            ("gather(ce)", call(lib.ifseg_seg_loss_gather, p(ce), p(stats), words=1),
+             call(lib.ifseg_seg_loss_gather3, p(ce), p(stats), None, None, *no_kd, words=4)),
+            ("gather_sum(ce, dice)", call(lib.ifseg_seg_loss_gather_sum, p(ce), p(stats), p(dice), p(dval), words=3),
+             call(lib.ifseg_seg_loss_gather3, p(ce), p(stats), p(dice), p(dval), *no_kd, words=4)),
+            ("gather_sum(-, dice)", call(lib.ifseg_seg_loss_gather_sum, None, None, p(dice), p(dval), words=3),
+             call(lib.ifseg_seg_loss_gather3, None, None, p(dice), p(dval), *no_kd, words=4))):
+        assert torch.equal(few[0], three[0]), name
+        assert torch.equal(few[1][:1].view(torch.int32), three[1][:1].view(torch.int32)), (name, few[1], three[1])
+
+
 # ------------------------------------------------------------------------------------------------- the dispatcher
 def test_op_is_the_binding_and_differentiable():
     from ifseg_amd import hip

@@ -72,7 +72,7 @@ def main():
         both = lambda: hip.seg_loss_dice(lp, tgt, HP, WP, Hl, Wl, n, SEG0, DICE_WEIGHT, 1.0, bufs=bufs)
         plain = lambda: hip.seg_loss(lp, tgt, HP, WP, Hl, Wl, n, SEG0, tile, sp, stats, dl, loss)
         sums = lambda: hip.seg_dice_sums(lp, tgt, HP, WP, Hl, Wl, n, SEG0, bufs=bufs)
-        head = hip._dice_tile_args(lp, tgt, B, HP, WP, Hl, Wl, n, SEG0, 1, 2)
+        head = hip._seg_tile_args(lp, tgt, B, HP, WP, Hl, Wl, n, SEG0, 1, 2)
         lib, p = hip.lib(), hip._ptr
 
         def pass_b():

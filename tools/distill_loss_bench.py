@@ -127,7 +127,7 @@ def main():
             hip.reduce_parts(bufs["kd_part"], bufs["kd_stats"], 1, B * HP * WP, 2)
 
         def gather():
-            hip._gather3(bufs, True, False, WEIGHT, T, B, HP, WP, n)
+            hip._seg_gather(bufs, True, False, (WEIGHT, T), B, HP, WP, n)
 
         def ce_tiles():
             hip._check(lib.ifseg_seg_loss_tiles(
