@@ -1,8 +1,9 @@
 // Counting over a finished label map (predict.hip: seg_areas_kernel, seg_confusion_kernel and the scoring epilogues;
-// pseudo.hip: seg_conf_hist_kernel, seg_pseudo_kernel), each part written once:
+// pseudo.hip: seg_conf_hist_kernel, seg_pseudo_kernel; calib.hip: seg_calibration_kernel), each part written once:
 //   bin_add       the wave pre-aggregated add into an LDS count
 //   walk_pixels   the grid-stride walk over a flat label map and a second stream of the same pixels -- an integer map
-//                 (ground truth: MapStream) or fp32 values (confidences: FloatStream) -- with walk_split, the host's side of it
+//                 (ground truth: MapStream) or fp32 values (confidences: FloatStream) -- with walk_split, the host's side of it;
+//                 walk_pixels3 is the same walk with both
 //   table_*       the workgroup-private table of keyed counts, direct or hashed: table_zero, table_add, table_flush
 // Integers throughout, so every counter built from these is bit-reproducible.
 #pragma once
@@ -36,6 +37,12 @@ __device__ __forceinline__ GtClass gt_class(int n, int raw, int g, bool live) {
   const int cls = raw ? g - 1 : g;
   const bool inr = (unsigned)cls < (unsigned)n;
   return {cls, live && !ign && inr, live && !ign && !inr};
+}
+
+// the confidence bin of the histogram, the filter and the calibration counters (pseudo.hip, calib.hip), its one statement:
+// bin(conf) = clamp(floor(conf * 256), 0, 255): the product is exact (a power of two), NaN -> 0 by fmaxf(NaN, 0) = 0
+__device__ __forceinline__ int conf_bin(float conf) {
+  return (int)fminf(fmaxf(floorf(__fmul_rn(conf, 256.f)), 0.f), 255.f);
 }
 
 // ---- the walk ----
@@ -148,6 +155,40 @@ __device__ __forceinline__ void walk_pixels(const unsigned char* lab, typename S
     }
 #pragma unroll
     for (int i = 0; i < 16; ++i) f(pv[i], sv[i], live);
+  }
+}
+
+// the walk with a third stream of the same pixels (calib.hip: the confidences and the ground truth beside the labels), the
+// statement above with one more load per group: f(label, second, third, live).  The two-stream walks do not go through it
+template <int LB, typename Second, typename Third, typename F>
+__device__ __forceinline__ void walk_pixels3(const unsigned char* lab, typename Second::P sec, typename Third::P thi, int head,
+                                             int groups, int tail, F f) {
+  using T = typename Second::T;
+  using U = typename Third::T;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (blockIdx.x == 0 && wave == 0) {
+    long long i = -1;
+    if (lane < head) i = lane;
+    else if (lane >= 16 && lane - 16 < tail) i = (long long)head + (long long)groups * 16 + (lane - 16);
+    const bool live = i >= 0;
+    f(live ? elem_at<LB>(lab, i) : 0, live ? Second::at(sec, i) : T(0), live ? Third::at(thi, i) : U(0), live);
+  }
+  const unsigned char* lb = lab + (long long)head * LB;           // on a 16-byte boundary
+  const Second second(sec, head);
+  const Third third(thi, head);
+  for (long long base = (long long)blockIdx.x * 256 + wave * 64; base < groups; base += (long long)gridDim.x * 256) {
+    const long long g = base + lane;
+    const bool live = g < groups;
+    int pv[16] = {};
+    T sv[16] = {};
+    U tv[16] = {};
+    if (live) {
+      load16<LB>(lb + g * (16 * LB), 0, pv);
+      second.group(g, sv);
+      third.group(g, tv);
+    }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) f(pv[i], sv[i], tv[i], live);
   }
 }
 

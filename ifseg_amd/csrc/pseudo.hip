@@ -18,13 +18,8 @@ namespace {
 using namespace tile;
 using namespace count;
 
-// bin(conf) = clamp(floor(conf * 256), 0, 255): the product is exact (a power of two), NaN -> 0 by fmaxf(NaN, 0) = 0
-__device__ __forceinline__ int conf_bin(float conf) {
-  return (int)fminf(fmaxf(floorf(__fmul_rn(conf, 256.f)), 0.f), 255.f);
-}
-
 // ---- the histogram ----
-// key = label * 256 + bin, below 512 * 256, into count.h's table: direct (uint32 [n][256] in LDS, 64 KiB at n = 64) up to
+// key = label * 256 + bin (count.h's conf_bin), below 512 * 256, into count.h's table: direct (uint32 [n][256] in LDS, 64 KiB at n = 64) up to
 // HC_DIRECT_CLASSES, hashed above.  The two tallies stay in registers and leave per wave (the direct table at n = 64 fills
 // the LDS budget).
 constexpr int HC_MAX_CLASSES = 512;

@@ -1794,6 +1794,37 @@ def seg_conf_hist(labels, conf, n, hist=None, tally=None):
     return hist, tally
 
 
+# the tables of seg_calibration_kernel (csrc/calib.hip, csrc/count.h)
+SEG_CALIBRATION_DIRECT_CLASSES = 32             # == CB_DIRECT_CLASSES: n up to this counts in a direct LDS table (n * 512 dwords), else hashed
+SEG_CALIBRATION_SLOTS = SEG_CONFUSION_SLOTS     # the same table (count::SLOTS): the (label, bin, hit) keys a workgroup's hashed table holds
+SEG_CALIBRATION_STEP_PIXELS = SEG_CONFUSION_STEP_PIXELS
+SEG_CALIBRATION_MAX_BLOCKS = SEG_CONFUSION_MAX_BLOCKS
+
+
+def seg_calibration_limits():
+    """-> (direct classes, hashed slots, pixels per workgroup step, workgroups at most) as the loaded library states them
+    (`ifseg_seg_calibration_limit`): the four constants above, which the tests hold against it"""
+    return tuple(int(lib().ifseg_seg_calibration_limit(c_int(k))) for k in range(4))
+
+
+def seg_calibration(labels, conf, gt, n, raw_labels=True, calibration=None, tally=None):
+    """labels uint8 / int16 [...] (predicted classes), conf fp32 and gt uint8 / int16 of the same shape -> (calibration int64
+    [n, 256, 2], tally int64 [2]): over the scored pixels of `seg_areas`, calibration[l, b, hit] = #(label = l in [0, n),
+    clamp(floor(conf * 256), 0, 255) = b, (l == gt class) = hit); tally = #scored pixels with a label in [0, n), #scored pixels
+    with a label outside (csrc/calib.hip; `predict.calibration_reference` is the specification).  `calibration` / `tally`
+    given: ACCUMULATED into and returned, else fresh zeroed ones.  One launch on the current stream.  1 <= n <= 512."""
+    _labels_conf(labels, conf, "seg_calibration")
+    assert gt.dtype in (torch.uint8, torch.int16) and gt.is_contiguous() and gt.shape == labels.shape and gt.device == labels.device, \
+        ("seg_calibration", gt.dtype, gt.stride(), tuple(gt.shape), tuple(labels.shape), gt.device, labels.device)
+    assert isinstance(n, int) and 1 <= n <= SEG_PREDICT_MAX_CLASSES, n
+    calibration = _counter(calibration, (n, SEG_CONF_BINS, 2), labels.device)
+    tally = _counter(tally, (2,), labels.device)
+    _check(lib().ifseg_seg_calibration(_ptr(labels), c_int(labels.element_size()), _ptr(conf), _ptr(gt), c_int(gt.element_size()),
+                                       c_ll(labels.numel()), c_int(n), c_int(1 if raw_labels else 0), _ptr(calibration),
+                                       _ptr(tally), _stream()), "seg_calibration")
+    return calibration, tally
+
+
 def seg_pseudo(labels, conf, thresholds, n, boundary=0, raw_labels=True, kept=None, out=None, weight=False):
     """labels uint8 / int16 [H, W] or [B, H, W], conf fp32 of the same shape, thresholds int32 [n] (bins, 0 .. 256) ->
     (out uint8 of the labels' shape, kept int64 [2, n]) in one launch (csrc/pseudo.hip): a pixel of label l in [0, n) whose

@@ -30,7 +30,8 @@ normalised patch_images, the reference's evaluation transform) and the three ops
 `seg_predict_windows`, `seg_score_windows`: the window batch written directly, and the windows' scores merged into one label
 map in one launch), `seg_render` (csrc/render.hip: the label map coloured over its image, with class contours), `seg_conf_hist` / `seg_pseudo`
 (csrc/pseudo.hip: the per-class confidence histogram of a label map, and the label map filtered by per-class thresholds and an
-ignore band along class edges into pseudo-labels for self-training) and the two of multi-scale + flip over sliding windows (`seg_predict_slide_views`, `seg_score_slide_views`:
+ignore band along class edges into pseudo-labels for self-training), `seg_calibration` (csrc/calib.hip: how often a confidence
+is right, pixels per predicted class, confidence bin and hit against ground truth) and the two of multi-scale + flip over sliding windows (`seg_predict_slide_views`, `seg_score_slide_views`:
 K views, each a set of windows, merged in one launch, optionally softmaxed per view as mmseg does) are inference only and
 have no backward; `train_load`
 (csrc/trainload.hip: raw images and label maps of any sizes to a training batch under given records, the reference's training
@@ -1214,6 +1215,37 @@ def _(labels, conf, n):
     if n < 1 or n > hip.SEG_PREDICT_MAX_CLASSES:
         raise ValueError("ifseg::seg_conf_hist: n = %d classes, the kernel takes 1 .. %d" % (n, hip.SEG_PREDICT_MAX_CLASSES))
     return labels.new_empty((n, hip.SEG_CONF_BINS), dtype=torch.int64), labels.new_empty((2,), dtype=torch.int64)
+
+
+def _seg_calibration_check(labels, conf, gt, n):
+    op = "ifseg::seg_calibration"
+    _labels_conf_check(op, labels, conf)
+    _gt_check(op, gt)
+    if gt.shape != labels.shape:
+        raise ValueError("%s: labels %s and ground truth %s must have one shape" % (op, tuple(labels.shape), tuple(gt.shape)))
+    if n < 1 or n > hip.SEG_PREDICT_MAX_CLASSES:
+        raise ValueError("%s: n = %d classes, the kernel takes 1 .. %d" % (op, n, hip.SEG_PREDICT_MAX_CLASSES))
+
+
+@custom_op("ifseg::seg_calibration", mutates_args=(), device_types="cuda")
+def seg_calibration(labels: torch.Tensor, conf: torch.Tensor, gt: torch.Tensor, n: int,
+                    raw_labels: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """predicted labels (uint8 / int16) with their confidences (fp32) against ground truth (uint8 / int16), one shape
+    (csrc/calib.hip) -> (calibration int64 [n, 256, 2] = over `seg_areas`' scored pixels, pixels per (label in [0, n),
+    clamp(floor(conf * 256), 0, 255), label == gt class), tally int64 [2] = scored pixels with a label inside / outside [0, n)),
+    fresh tensors; `ifseg_amd.predict.calibration_reference` is the specification.  Counts: not differentiable."""
+    _seg_calibration_check(labels, conf, gt, n)
+    prev = _stream_scope(labels)
+    try:
+        return hip.seg_calibration(labels.contiguous(), conf.contiguous(), gt.contiguous(), n, raw_labels)
+    finally:
+        hip.set_stream(prev)
+
+
+@seg_calibration.register_fake
+def _(labels, conf, gt, n, raw_labels):
+    _seg_calibration_check(labels, conf, gt, n)
+    return labels.new_empty((n, hip.SEG_CONF_BINS, 2), dtype=torch.int64), labels.new_empty((2,), dtype=torch.int64)
 
 
 def _seg_pseudo_check(labels, conf, thresholds, n, boundary, raw_labels):

@@ -78,6 +78,17 @@ counts it, behind `hip.seg_confusion` where both are asked for, in every setting
     score = seg.evaluate_raw(photos, label_pngs, boundary_iou=True)                # or a ratio: boundary_iou=0.01
     score.summary()["mBIoU"]
 
+Whether the confidence means anything: `seg.evaluate_raw(..., calibration=True)` also fills `score.calibration`, int64
+[n, 256, 2]: per predicted class and confidence bin (`conf_bin`, the pseudo-label path's) the scored pixels that were wrong and
+right -- the reliability diagram and ECE (Guo et al., ICML 2017).  The scoring launch writes its labels and conf and one launch
+of `hip.seg_calibration` (csrc/calib.hip) per image counts them against the ground truth, behind the other two, in every
+setting above; `summary()` then carries "ECE", "MCE" and "cECE".  `calibration_reference` is the specification.
+
+    score = seg.evaluate_raw(photos, label_pngs, calibration=True)                 # a labelled validation set
+    score.summary()["ECE"];  score.reliability(bins=16)                            # (pixels, accuracy, confidence) per bin
+    t = score.precision_thresholds(0.9)                                            # per class: the bin above which it is 90 % right
+    seg.pseudo_label_raw(unlabelled_photos, thresholds=t)
+
 The label map as a picture: `seg.render_raw(photos, ...)` is `segment_raw` followed by one launch of `hip.seg_render`
 (csrc/render.hip) per image, which blends the classes' colours over the original photo and draws class contours -- the demo's
 `cmap[labels]` and `image * (1 - opacity) + cmap[labels] * opacity`, without the label map leaving the device.  The rule is
@@ -104,7 +115,7 @@ How the four settings share their code: a front (`Segmenter._raw_views` without 
 view or many) runs the loads and the forwards and hands back one `_Merge` per image -- the setting's last launch, as its
 `hip.seg_predict*` and its `hip.seg_score*`, bound to the image's scores and geometry.  `Segmenter._label` finishes an image
 from its merge (the predict launch, then the CRF) and `Segmenter._count` scores it (the scoring launch; with the CRF on
-`_label` and `hip.seg_areas`; `hip.seg_confusion` and `hip.seg_boundary_areas` behind either); `__call__` and `evaluate` go through the same two with the
+`_label` and `hip.seg_areas`; `hip.seg_confusion`, `hip.seg_boundary_areas` and `hip.seg_calibration` behind either); `__call__` and `evaluate` go through the same two with the
 single-view merge of their batch.
 
 Nothing in the call synchronises with the host; `labels`, `conf` and `probs` stay on the device.  There is no CPU fallback:
@@ -454,6 +465,50 @@ def confidence_histogram_reference(labels, conf, n):
     return hist, torch.stack([inside.sum(), (~inside).sum()])
 
 
+def calibration_reference(labels, conf, gt, n, raw_labels=True):
+    """Specification of hip.seg_calibration, the counts behind the reliability diagram and ECE (Guo et al., ICML 2017) per
+    predicted class: labels integer [...] (predicted classes), conf fp32 and gt uint8 / int16 of the same shape ->
+    (calibration int64 [n, 256, 2], tally int64 [2]).  The ground-truth rule and the set of scored pixels are
+    `areas_reference`'s; over those only, calibration[l, b, hit] = #(label = l in [0, n), conf_bin(conf) = b,
+    (l == gt class) = hit), tally[0] = #scored pixels with a label in [0, n), tally[1] = #scored pixels with a label outside.
+    A pixel that is not scored (ignored ground truth, or ground truth outside the classes) is counted nowhere.  With (areas, _)
+    of `areas_reference` on the same maps: calibration.sum((1, 2)) == areas[1], calibration[..., 1].sum(1) == areas[0],
+    calibration.sum() == tally[0].  Runs on any device."""
+    pred, cls, scored, _ = _scored_mask("calibration_reference", labels, gt, n, raw_labels)
+    conf = torch.as_tensor(conf)
+    if conf.dtype != torch.float32 or conf.shape != torch.as_tensor(labels).shape:
+        raise ValueError("calibration_reference: conf must be float32 %s, got %s %s"
+                         % (tuple(torch.as_tensor(labels).shape), conf.dtype, tuple(conf.shape)))
+    if int(n) < 1:
+        raise ValueError("calibration_reference: n = %d classes" % n)
+    b = conf_bin(conf.to(pred.device)).reshape(-1)
+    inside = scored & (pred >= 0) & (pred < n)
+    key = (pred[inside] * CONF_BINS + b[inside]) * 2 + (pred[inside] == cls[inside]).long()
+    calibration = torch.bincount(key, minlength=n * CONF_BINS * 2).reshape(n, CONF_BINS, 2)
+    return calibration, torch.stack([inside.sum(), (scored & ~inside).sum()])
+
+
+def _reliability_bins(cal, bins, per_class):
+    """calibration counters int64 [n, 256, 2] -> (pixels, hits, confidence mass) float64 [n | 1, bins]: the fine bins summed
+    in runs of 256 / bins, a fine bin's confidence being its midpoint (b + 0.5) / 256.  Exact: integers and multiples of 1/512
+    far below 2^53"""
+    c = cal.double() if per_class else cal.sum(0, keepdim=True).double()
+    mid = (torch.arange(CONF_BINS, dtype=torch.float64, device=cal.device) + 0.5) / CONF_BINS
+    fine = c.sum(-1)
+    run = (c.shape[0], bins, CONF_BINS // bins)
+    return fine.reshape(run).sum(-1), c[..., 1].reshape(run).sum(-1), (fine * mid).reshape(run).sum(-1)
+
+
+def _calibration_errors(N, H, C):
+    """(pixels, hits, confidence mass) [k, bins] -> (ECE, MCE) float64 [k]: sum_m (N_m / N) |acc_m - conf_m| and the largest
+    gap over the non-empty bins; NaN without pixels"""
+    total = N.sum(-1)
+    gap = (H / N - C / N).abs()                                  # NaN where the bin is empty
+    ece = torch.nansum(N * gap, -1) / total
+    mce = torch.nan_to_num(gap, nan=-1.0).amax(-1)
+    return ece, torch.where(total > 0, mce, torch.full_like(mce, float("nan")))
+
+
 def pseudo_thresholds(hist, keep=1.0, floor=0.0):
     """The per-class confidence thresholds of self-training from a confidence histogram int64 [n, 256] -> int32 [n], values in
     0 .. 256 (bins: a pixel of class c passes iff conf_bin(conf) >= t_c), on hist's device with no host round trip.  In integers:
@@ -571,9 +626,16 @@ class SegmentationScore:
     boundary: None (the default: no counters, memory and behaviour as without the argument), True (zeroed ones) or a tensor:
     `boundary_areas_reference`'s counters int64 [3, n] on the same device, the three rows of `areas` restricted to the pixels
     within d of a contour, d = `boundary_distance(h, w, boundary_ratio)` per image; `evaluate_raw(..., boundary_iou=True)` fills
-    them (`hip.seg_boundary_areas`), and `summary` / `group_summary` then report Boundary IoU beside IoU."""
+    them (`hip.seg_boundary_areas`), and `summary` / `group_summary` then report Boundary IoU beside IoU.
 
-    def __init__(self, n, device=None, areas=None, tally=None, confusion=None, boundary=None, boundary_ratio=0.02):
+    calibration: None (the default: no counters, memory and behaviour as without the argument), True (zeroed ones) or a tensor:
+    `calibration_reference`'s counters int64 [n, 256, 2] on the same device, pixels per (predicted class, confidence bin, hit);
+    `evaluate_raw(..., calibration=True)` fills them (`hip.seg_calibration`), with `calibration_tally` int64 [2] beside them
+    (scored pixels with a label inside / outside [0, n)).  `reliability`, `precision_thresholds` and `summary` ("ECE", "MCE",
+    "cECE") read them."""
+
+    def __init__(self, n, device=None, areas=None, tally=None, confusion=None, boundary=None, boundary_ratio=0.02,
+                 calibration=None):
         self.n = int(n)
         self.areas = torch.zeros(3, self.n, dtype=torch.int64, device=device) if areas is None else areas
         self.tally = torch.zeros(2, dtype=torch.int64, device=device) if tally is None else tally
@@ -604,6 +666,18 @@ class SegmentationScore:
                 raise ValueError("SegmentationScore: boundary must be None, True or int64 [3, %d] on the device of areas, got %s"
                                  % (self.n, (boundary.dtype, tuple(boundary.shape), boundary.device)
                                     if torch.is_tensor(boundary) else type(boundary)))
+        if calibration is None or calibration is False:
+            self.calibration = self.calibration_tally = None
+        else:
+            if calibration is True:
+                calibration = torch.zeros(self.n, CONF_BINS, 2, dtype=torch.int64, device=self.areas.device)
+            if not torch.is_tensor(calibration) or calibration.dtype != torch.int64 \
+                    or tuple(calibration.shape) != (self.n, CONF_BINS, 2) or calibration.device != self.areas.device:
+                raise ValueError("SegmentationScore: calibration must be None, True or int64 [%d, %d, 2] on the device of areas, got %s"
+                                 % (self.n, CONF_BINS, (calibration.dtype, tuple(calibration.shape), calibration.device)
+                                    if torch.is_tensor(calibration) else type(calibration)))
+            self.calibration = calibration
+            self.calibration_tally = torch.zeros(2, dtype=torch.int64, device=self.areas.device)
 
     def add_(self, other):
         if other.n != self.n:
@@ -612,6 +686,8 @@ class SegmentationScore:
             raise ValueError("SegmentationScore.add_: one score has a confusion matrix and the other has none")
         if (self.boundary is None) != (other.boundary is None):
             raise ValueError("SegmentationScore.add_: one score has boundary counters and the other has none")
+        if (self.calibration is None) != (other.calibration is None):
+            raise ValueError("SegmentationScore.add_: one score has calibration counters and the other has none")
         if self.boundary is not None and self.boundary_ratio != other.boundary_ratio:
             raise ValueError("SegmentationScore.add_: boundary counters of ratio %r against ratio %r: bands of different widths "
                              "do not add" % (self.boundary_ratio, other.boundary_ratio))
@@ -621,6 +697,9 @@ class SegmentationScore:
             self.confusion += other.confusion.to(self.confusion.device)
         if self.boundary is not None:
             self.boundary += other.boundary.to(self.boundary.device)
+        if self.calibration is not None:
+            self.calibration += other.calibration.to(self.calibration.device)
+            self.calibration_tally += other.calibration_tally.to(self.calibration_tally.device)
         return self
 
     def _matrix(self, what):
@@ -658,7 +737,8 @@ class SegmentationScore:
         raw_labels=False)` with -1 -> m in the ground truth.  Needs a confusion matrix (ValueError without one).
         The new score carries NO boundary counters, whether this one does or not: merging classes erases the contours between
         them, so the band areas of a coarser label set do not follow from the finer one's (they need a second pass over the
-        mapped label maps)."""
+        mapped label maps).  It carries NO calibration counters either: a merged class's confidence is the SUM of its
+        members' probabilities, not their maximum, so the (class, confidence bin) counts cannot be re-keyed."""
         C = self._matrix("merged")
         mp = torch.as_tensor(mapping).reshape(-1)
         if mp.dtype.is_floating_point or mp.dtype == torch.bool or mp.numel() != self.n:
@@ -673,6 +753,44 @@ class SegmentationScore:
         M = torch.zeros(m + 1, m + 1, dtype=torch.int64, device=C.device).index_add_(1, cols, rows)[:m].contiguous()
         areas = torch.stack([M[:, :m].diagonal(), M[:, :m].sum(0), M.sum(1)])
         return SegmentationScore(m, areas=areas, tally=torch.stack([M.sum(), self.tally[1].to(C.device)]), confusion=M)
+
+    def _counters(self, what):
+        if self.calibration is None:
+            raise ValueError("SegmentationScore.%s needs calibration counters: SegmentationScore(n, calibration=True), "
+                             "evaluate_raw(..., calibration=True)" % what)
+        return self.calibration
+
+    def reliability(self, bins=16, per_class=False):
+        """The reliability diagram (Guo et al., ICML 2017) -> (pixels int64, accuracy float64, confidence float64), each [bins],
+        or [n, bins] per predicted class with `per_class`: coarse bin m holds the pixels whose confidence lies in
+        [m / bins, (m + 1) / bins), accuracy is the share of them whose label is the ground truth's class and confidence their
+        mean confidence; both NaN where the bin is empty.  bins must divide 256 (ValueError).  The confidence of a fine bin b
+        is taken as its midpoint (b + 0.5) / 256, so the confidence reported for a coarse bin differs from the true mean
+        confidence of its pixels by at most 1 / 512.  On the score's device, float64 from the integers; not synchronising."""
+        cal = self._counters("reliability")
+        if not isinstance(bins, int) or isinstance(bins, bool) or bins < 1 or CONF_BINS % bins:
+            raise ValueError("SegmentationScore.reliability: bins must be an int that divides %d, got %r" % (CONF_BINS, bins))
+        N, H, C = _reliability_bins(cal, bins, per_class)
+        out = (N.long(), H / N, C / N)
+        return out if per_class else tuple(t[0] for t in out)
+
+    def precision_thresholds(self, target, min_pixels=1):
+        """Per-class pseudo-label thresholds by MEASURED precision -> int32 [n] bins on the score's device, what
+        `Segmenter.pseudo_label_raw(thresholds=)` and `hip.seg_pseudo` take.  With N_cb / H_cb the pixels / hits of predicted
+        class c in fine bin b: t_c is the smallest t with  sum_{b >= t} N_cb >= min_pixels  and
+        sum_{b >= t} H_cb >= target * sum_{b >= t} N_cb  (integer suffix sums, compared in float64); 256 -- nothing kept --
+        where no t does, as for a class never predicted.  target outside (0, 1] or min_pixels < 1: ValueError.  Not
+        synchronising."""
+        cal = self._counters("precision_thresholds")
+        if isinstance(target, bool) or not isinstance(target, (int, float)) or not 0.0 < target <= 1.0:
+            raise ValueError("SegmentationScore.precision_thresholds: target must be a number in (0, 1], got %r" % (target,))
+        if not isinstance(min_pixels, int) or isinstance(min_pixels, bool) or min_pixels < 1:
+            raise ValueError("SegmentationScore.precision_thresholds: min_pixels must be an int >= 1, got %r" % (min_pixels,))
+        SN = cal.sum(-1).flip(1).cumsum(1).flip(1)
+        SH = cal[..., 1].flip(1).cumsum(1).flip(1)
+        ok = (SN >= min_pixels) & (SH.double() >= float(target) * SN.double())
+        t = torch.arange(CONF_BINS, device=cal.device).expand_as(ok)
+        return torch.where(ok, t, torch.full_like(t, CONF_BINS)).amin(1).to(torch.int32)
 
     def group_summary(self, groups):
         """groups: {name: class ids} (seen / unseen, things / stuff) -> {name: {"mIoU", "mAcc"}, ..., "hIoU"}: per group the nanmean
@@ -723,7 +841,12 @@ class SegmentationScore:
         (nanmean over the classes, round(..., 4)).  The one place that synchronises with the host.  Ground truth out of range
         is an IndexError: the reference's F.cross_entropy fails on such a label, and a score that left pixels out is not
         reported as if it had not.  A score with boundary counters b also gives "mBIoU" and "BIoU": [n], Boundary IoU =
-        b[0] / (b[1] + b[2] - b[0]) per class, with the same nanmean and rounding, in the same round trip."""
+        b[0] / (b[1] + b[2] - b[0]) per class, with the same nanmean and rounding, in the same round trip.  A score with
+        calibration counters also gives "ECE" = sum_m (N_m / N) |acc_m - conf_m| over `reliability(16)`'s bins of all classes
+        together, "MCE", the largest |acc_m - conf_m| of a non-empty bin, and "cECE": [n], the ECE of every predicted class
+        alone (NaN for a class never predicted; ECE and MCE are NaN without pixels): float64 from the integers, NOT rounded, in
+        the same round trip.  A fine bin's confidence is its midpoint, so each is within 1 / 512 of the figure the raw
+        confidences would give for the same bins."""
         m, n = self.logging_output(), self.n
         ai, ap, al, au = m["area_intersect"], m["area_pred_label"], m["area_label"], m["area_union"]
         iou, acc = ai / au, ai / al
@@ -732,6 +855,9 @@ class SegmentationScore:
             b = self.boundary.double()
             biou = b[0] / (b[1] + b[2] - b[0])
             parts += [torch.nanmean(biou)[None], biou]
+        if self.calibration is not None:
+            ece, mce = _calibration_errors(*_reliability_bins(self.calibration, 16, False))
+            parts += [ece, mce, _calibration_errors(*_reliability_bins(self.calibration, 16, True))[0]]
         flat = torch.cat(parts).tolist()
         self._refuse_out_of_range(flat[3 + 2 * n + 1])
         r4 = lambda v: round(float(v), 4)
@@ -740,6 +866,9 @@ class SegmentationScore:
         if self.boundary is not None:
             out["mBIoU"] = r4(flat[5 + 2 * n])
             out["BIoU"] = [r4(v) for v in flat[6 + 2 * n:6 + 3 * n]]
+        if self.calibration is not None:
+            at = len(flat) - n - 2
+            out["ECE"], out["MCE"], out["cECE"] = flat[at], flat[at + 1], flat[at + 2:]
         return out
 
 
@@ -1195,19 +1324,22 @@ class Segmenter:
         return out
 
     # -- scoring against ground truth -----------------------------------------------------
-    def _score_into(self, what, into, dev, confusion=False, boundary_iou=False, shapes=()):
+    def _score_into(self, what, into, dev, confusion=False, boundary_iou=False, shapes=(), calibration=False, sl=None):
         """the score a scoring call adds to, its arguments checked before anything is launched.  shapes: the (h, w) of the
         ground-truth maps, in order: with boundary counters, each one's band must fit the kernel"""
         if not isinstance(confusion, bool):
             raise ValueError("Segmenter.%s: confusion must be True or False (a matrix to add to goes in with `into`), got %s"
                              % (what, type(confusion)))
+        if not isinstance(calibration, bool):
+            raise ValueError("Segmenter.%s: calibration must be True or False (counters to add to go in with `into`), got %s"
+                             % (what, type(calibration)))
         ratio = None
         if boundary_iou is not False:
             ratio = 0.02 if boundary_iou is True else _boundary_ratio("Segmenter.%s: boundary_iou is True, False or a ratio" % what,
                                                                       boundary_iou)
         if into is None:
             score = SegmentationScore(self.n, dev, confusion=confusion, boundary=ratio is not None,
-                                      boundary_ratio=0.02 if ratio is None else ratio)
+                                      boundary_ratio=0.02 if ratio is None else ratio, calibration=calibration)
         else:
             if not isinstance(into, SegmentationScore) or into.n != self.n or into.areas.device != dev:
                 raise ValueError("Segmenter.%s: into must be a SegmentationScore of %d classes on %s" % (what, self.n, dev))
@@ -1220,7 +1352,15 @@ class Segmenter:
             if ratio is not None and into.boundary_ratio != ratio:
                 raise ValueError("Segmenter.%s: boundary_iou asks for a band of ratio %r, `into` counts bands of ratio %r"
                                  % (what, ratio, into.boundary_ratio))
+            if calibration and into.calibration is None:
+                raise ValueError("Segmenter.%s: calibration=True, but `into` carries no calibration counters (SegmentationScore(n, "
+                                 "device, calibration=True))" % what)
             score = into
+        if score.calibration is not None:
+            bad = self._conf_setting(sl)
+            if bad is not None:
+                raise ValueError("Segmenter.%s: the confidence must be a probability, this Segmenter has %s; use upsample='probs', the "
+                                 "smoothing, the CRF, or slide_views with slide" % (what, bad))
         if score.boundary is not None:
             for i, (h, w) in enumerate(shapes):
                 d = boundary_distance(h, w, score.boundary_ratio)
@@ -1236,23 +1376,31 @@ class Segmenter:
         map comes from the CRF (`_label`; rgb: its images), not from the predict kernel, and `hip.seg_areas` counts it.  Where
         the score carries a confusion matrix, the launch is asked for its label map and `hip.seg_confusion` counts the pairs
         of the same labels behind it on the same stream; where it carries boundary counters, likewise, and
-        `hip.seg_boundary_areas` counts the band areas of the same labels with d = `boundary_distance` of gt's size."""
+        `hip.seg_boundary_areas` counts the band areas of the same labels with d = `boundary_distance` of gt's size.  Where
+        it carries calibration counters, the launch (with the CRF, `_label`) is asked for its conf as well and
+        `hip.seg_calibration` counts labels, conf and gt behind the other two."""
         kw = dict(raw_labels=raw_labels, areas=score.areas, tally=score.tally)
-        pairs, bands = score.confusion is not None, score.boundary is not None
+        pairs, bands, cal = score.confusion is not None, score.boundary is not None, score.calibration is not None
         if self.crf_iters > 0:
-            labels = self._label(merge, int(gt.shape[1]), int(gt.shape[2]), rgb, False, False).labels.contiguous()
+            res = self._label(merge, int(gt.shape[1]), int(gt.shape[2]), rgb, cal, False)
+            labels, conf = res.labels.contiguous(), res.conf
             hip.seg_areas(labels, gt, self.n, **kw)
         else:
-            labels = merge.score(gt, labels=return_labels or pairs or bands, label_dtype=self.label_dtype, **kw)[2]
+            labels, conf = merge.score(gt, labels=return_labels or pairs or bands or cal, conf=cal, label_dtype=self.label_dtype,
+                                       **kw)[2:4]
         if pairs:
             hip.seg_confusion(labels, gt, self.n, raw_labels, confusion=score.confusion)
         if bands:
             hip.seg_boundary_areas(labels, gt, self.n, boundary_distance(int(gt.shape[1]), int(gt.shape[2]), score.boundary_ratio),
                                    raw_labels, bareas=score.boundary)
+        if cal:
+            hip.seg_calibration(labels, conf.contiguous(), gt, self.n, raw_labels, calibration=score.calibration,
+                                tally=score.calibration_tally)
         return labels if return_labels else None
 
     def evaluate_raw(self, images, label_maps, raw_labels=True, scales=(1.0,), flip=False, max_batch=8, mean=None, std=None,
-                     reverse_channels=False, into=None, return_labels=False, slide=None, confusion=False, boundary_iou=False):
+                     reverse_channels=False, into=None, return_labels=False, slide=None, confusion=False, boundary_iou=False,
+                     calibration=False):
         """`segment_raw` scored against ground truth on the device -> a `SegmentationScore` (or (score, [labels [H_i, W_i], ...])
         with `return_labels`, the labels being `segment_raw`'s).
 
@@ -1280,7 +1428,18 @@ class Segmenter:
         ground truth's resolution, the image's own.  areas, tally, the matrix and the labels are bit for bit what they are
         without it, no host synchronisation is added, and a call without it makes the launches it always made.  A ValueError
         before anything is launched: a ratio other than `into`'s, `into` without the counters, an image whose d passes
-        `hip.SEG_BOUNDARY_MAX_D` = 64 (a diagonal above 3200 pixels at 2 %)."""
+        `hip.SEG_BOUNDARY_MAX_D` = 64 (a diagonal above 3200 pixels at 2 %).
+        calibration: True, or an `into` that carries calibration counters: the score also counts how often a confidence is
+        right (`SegmentationScore.calibration`, int64 [n, 256, 2]: pixels per predicted class, confidence bin and hit;
+        `calibration_reference` is the specification), and `summary()` gains "ECE", "MCE" and "cECE";
+        `score.reliability()` is the diagram and `score.precision_thresholds(target)` the per-class thresholds of a measured
+        precision for `pseudo_label_raw(thresholds=)`.  The scoring launch then also writes its labels and conf
+        (`segment_raw(return_conf=True)`'s; with the CRF on, the CRF's) and one launch of `hip.seg_calibration` per image
+        counts them on the same stream, behind the matrix's and the bands' launches.  Everything else is bit for bit what it
+        is without it, no host synchronisation is added, and a call without it makes the launches it always made.  The
+        confidence must be a probability: raw logits (upsample="logits" outside `slide_views` sliding) are a ValueError naming
+        the setting, as in `pseudo_label_raw`; so are anything but a bool and calibration=True with an `into` that lacks the
+        counters, all before anything is launched."""
         sl = self._check_slide("evaluate_raw", slide, scales, flip)
         checked = self._check_raw("evaluate_raw", images, scales, flip, sl)
         plan = self._plan_slide(checked, sl, max_batch)
@@ -1293,7 +1452,7 @@ class Segmenter:
                 raise ValueError("Segmenter.evaluate_raw: label map %d must be a uint8 or int16 tensor of its image's shape %s, got %s"
                                  % (i, tuple(im.shape[:2]), (g.dtype, tuple(g.shape)) if torch.is_tensor(g) else type(g)))
         dev = next(self.model.parameters()).device
-        score = self._score_into("evaluate_raw", into, dev, confusion, boundary_iou, [tuple(g.shape) for g in gts])
+        score = self._score_into("evaluate_raw", into, dev, confusion, boundary_iou, [tuple(g.shape) for g in gts], calibration, sl)
         if checked is None:
             return (score, []) if return_labels else score
         gts = [g.to(dev, non_blocking=True).contiguous() for g in gts]
@@ -1305,12 +1464,13 @@ class Segmenter:
                 out.append(None if labels is None else labels[0])
         return (score, out) if return_labels else score
 
-    def evaluate(self, images, label_maps, raw_labels=True, into=None, return_labels=False, confusion=False, boundary_iou=False):
+    def evaluate(self, images, label_maps, raw_labels=True, into=None, return_labels=False, confusion=False, boundary_iou=False,
+                 calibration=False):
         """`__call__` scored against ground truth: images as `__call__` takes them (normalised float [B, 3, H, W] or uint8 RGB
         [B, H, W, 3] / [H, W, 3]), label_maps uint8 / int16 [B, h, w] (or [h, w] for one image): the label map is taken at the
         ground truth's own size, as `out_hw` would.  -> a `SegmentationScore`, or (score, labels [B, h, w]) with `return_labels`;
-        raw_labels, into, confusion, boundary_iou: as in `evaluate_raw`; the band areas of the whole batch are one launch of
-        `hip.seg_boundary_areas`, d from the label maps' size."""
+        raw_labels, into, confusion, boundary_iou, calibration: as in `evaluate_raw`; the band areas of the whole batch are one
+        launch of `hip.seg_boundary_areas`, d from the label maps' size, and its calibration counts one of `hip.seg_calibration`."""
         gt = label_maps
         if not torch.is_tensor(gt) or gt.dtype not in (torch.uint8, torch.int16) or gt.dim() not in (2, 3) or gt.numel() == 0:
             raise ValueError("Segmenter.evaluate: label_maps must be a uint8 or int16 tensor [B, h, w], got %s"
@@ -1324,7 +1484,7 @@ class Segmenter:
         if crf and tuple(gt.shape[1:]) != (H, W):
             raise ValueError("Segmenter.evaluate: with the CRF on, the label maps must have the images' size %s, got %s"
                              % ((H, W), tuple(gt.shape[1:])))
-        score = self._score_into("evaluate", into, patch_images.device, confusion, boundary_iou, [tuple(gt.shape[1:])])
+        score = self._score_into("evaluate", into, patch_images.device, confusion, boundary_iou, [tuple(gt.shape[1:])], calibration)
         if crf and rgb is None:
             rgb = ((patch_images.float() * 0.5 + 0.5) * 255.0).permute(0, 2, 3, 1).contiguous()
         scores, hp, wp = self.patch_scores(patch_images)

@@ -209,7 +209,9 @@ class SegmentationTask(TaskBase):
         the device: `build_segmenter(model, ...).evaluate_raw(images, label_maps, ...)`.  Keywords of the Segmenter's constructor
         go to it, the others to `Segmenter.evaluate_raw`; `slide` (None, True or (crop, stride)) is its sliding-window switch,
         `confusion=True` asks for the class confusion matrix (`score.confusion`) beside the three histograms,
-        `boundary_iou=True` (or a ratio of the diagonal) for Boundary IoU's band areas (`score.boundary`; "mBIoU" in the summary)."""
+        `boundary_iou=True` (or a ratio of the diagonal) for Boundary IoU's band areas (`score.boundary`; "mBIoU" in the summary),
+        `calibration=True` for how often a confidence is right (`score.calibration`; "ECE" in the summary,
+        `score.precision_thresholds(target)` for `self_train_sample`'s thresholds)."""
         ctor = ("category_token_ids", "prompt_ids", "upsample", "smooth_iters", "smooth_topk", "temperature", "crf_iters",
                 "full_context_alignment", "label_dtype", "slide_views")
         seg = self.build_segmenter(model, **{k: kw.pop(k) for k in ctor if k in kw})

@@ -894,6 +894,26 @@ int ifseg_seg_render(const void* labels, int label_bytes, const void* image, con
  * or tally not 8-byte aligned: IFSEG_ERR_BAD_ARG; npix < 1 or >= 2^31: IFSEG_ERR_BAD_SHAPE; nothing is launched on a refusal. */
 int ifseg_seg_conf_hist(const void* labels, int label_bytes, const float* conf, long long npix, int n,
                         unsigned long long* hist, unsigned long long* tally, void* stream);
+/* ifseg_seg_calibration counts how often a confidence is right (the reliability diagram and ECE, Guo et al., ICML 2017, per
+ * predicted class; csrc/calib.hip; predict.py: calibration_reference): npix predicted labels (uint8, label_bytes 1, or int16,
+ * 2; any element alignment), their confidences conf fp32 [npix] and npix ground-truth values (uint8 / int16, gt_bytes; any
+ * element alignment of their own).  The ground-truth rule and the set of scored pixels are ifseg_seg_areas'.  A scored pixel
+ * with predicted label l in [0, n) adds 1 to calibration[l][bin(conf)][hit], hit = (l == the ground truth's class), bin as
+ * above; calibration is uint64 [n][256][2].  tally uint64 [2] += #scored pixels with a label in [0, n), #scored pixels with a
+ * label outside it.  Pixels that are not scored (an ignored ground truth, or one outside the classes) are counted nowhere.
+ * Both are ADDED to and never cleared; integer sums, exact and bit-reproducible.  So, over the same inputs: calibration summed
+ * over bins and hit is the per-class count of the scored, in-range labels (areas[1]), calibration[.][.][1] summed over bins is
+ * areas[0], and the sum of all entries is tally[0] here.
+ * A workgroup counts in a private LDS table -- the counters themselves up to n = 32, a hashed table of 4096 (label, bin, hit)
+ * keys above, a key that finds no slot adding to global memory directly -- and only the keys it met leave it, one 64-bit
+ * atomic each.  NULL labels / conf / gt / calibration / tally, label_bytes or gt_bytes outside {1, 2}, n outside 1..512, an
+ * int16 pointer at an odd address, conf not 4-byte aligned, calibration or tally not 8-byte aligned: IFSEG_ERR_BAD_ARG;
+ * npix < 1 or >= 2^31: IFSEG_ERR_BAD_SHAPE; nothing is launched on a refusal. */
+int ifseg_seg_calibration(const void* labels, int label_bytes, const float* conf, const void* gt, int gt_bytes, long long npix,
+                          int n, int raw_labels, unsigned long long* calibration, unsigned long long* tally, void* stream);
+/* the kernel's table sizes: which = 0 the classes up to which the direct table counts, 1 the slots of the hashed table, 2 the
+ * pixels a workgroup takes per step, 3 the workgroups of a launch at most; any other which: IFSEG_ERR_BAD_ARG. */
+int ifseg_seg_calibration_limit(int which);
 /* ifseg_seg_pseudo filters labels [B, H, W] (uint8 / int16) by conf fp32 [B, H, W] into out uint8 [B, H, W], one launch: a
  * pixel of label l is KEPT iff 0 <= l < n, bin(conf) >= thresholds[l] (int32 [n] on the device, 0 keeps every bin, 256 none)
  * and, with boundary = r (0..4), no pixel INSIDE the image at |dx| <= r and |dy| <= r carries a different label value
