@@ -36,12 +36,14 @@
 // walk_split) and the direct / hashed workgroup table (table_*) are count.h's, shared with pseudo.hip.
 #include "count.h"
 #include "tile.h"
+#include "upsample.h"
 #include "../../include/ifseg_hip.h"
 
 namespace {
 
 using namespace tile;
 using namespace count;
+using namespace upsample;
 
 constexpr int PT_MAX_CLASSES = 512;
 constexpr int PT_TILE_LDS = TILE_ROWS * TILE_COLS * 8;            // the label + conf tile of phase 2
@@ -49,24 +51,8 @@ constexpr int PT_STAGE_LIMIT = 65536 - PT_TILE_LDS;               // 64 KiB of L
 
 int g_stage_limit = PT_STAGE_LIMIT;
 
-// LDS stride of one patch row of n classes, in floats: a multiple of 4 whose quarter is odd
-__host__ __device__ inline int pt_stride(int n) {
-  const int q = (n + 3) >> 2;
-  return ((q & 1) ? q : q + 1) << 2;
-}
-
-struct Best {
-  float v;
-  int c;
-};
-
-// one class of one pixel: the flat four-weight rule, first maximum wins.  Four rounded products, added in order: contraction
-// is off here, because which of the products the compiler fuses into an fma depends on the code around the call, and the two
-// kernels of this file have to give the same bits for the same view
-__device__ __forceinline__ float blend(float w00, float w01, float w10, float w11, float a, float b, float c, float d) {
-#pragma clang fp contract(off)
-  return w00 * a + w01 * b + w10 * c + w11 * d;
-}
+// (pt_stride, Best, blend and blend4 -- the stride of a staged patch, the running first maximum and the flat four-weight value
+// of one class, and of four at once -- are upsample.h's, shared with tsweep.hip)
 
 // classes [0, n) of the thread's four pixels (rows j = 0..3 of its wave, one x).  VEC: 16-byte reads of 4 classes (the staged
 // rows: stride and base are multiples of 4 floats), else one class per read.  o0 / o1: per-lane offset of the left / right
@@ -364,14 +350,6 @@ __device__ __forceinline__ f32x4 quad(const float* p, int c, int cn) {
   for (int k = 0; k < 4; ++k)
     if (c + k < cn) v[k] = p[c + k];
   return v;
-}
-
-// blend for four consecutive classes at once, element by element the same operations in the same order.  Written on the
-// vectors, so that the compiler packs two classes into one instruction and not the two products of one class, whose sum
-// would then be an addition across the halves of a register pair (tools/check_isa.py)
-__device__ __forceinline__ f32x4 blend4(float w00, float w01, float w10, float w11, f32x4 a, f32x4 b, f32x4 c, f32x4 d) {
-#pragma clang fp contract(off)
-  return w00 * a + w01 * b + w10 * c + w11 * d;
 }
 
 // acc[c] += the view's value of class c at one pixel, whose four patches start at p00 .. p11

@@ -1825,6 +1825,48 @@ def seg_calibration(labels, conf, gt, n, raw_labels=True, calibration=None, tall
     return calibration, tally
 
 
+# the limits of seg_tsweep_kernel (csrc/tsweep.hip)
+SEG_SWEEP_MAX_TEMPERATURES = 16     # == TS_MAX_K: the grids of one launch at most (2 KiB of LDS table each)
+SEG_SWEEP_STAGING_BYTES = 31728     # == ts_stage_limit(16): what 16 tables and the waves' sums leave of 64 KiB for the footprint
+
+
+def seg_temperature_sweep_limits():
+    """-> (the largest K, the largest n, a tile's rows, a tile's columns, the staging bytes at the largest K) as the loaded
+    library states them (`ifseg_seg_temperature_sweep_limit`): SEG_SWEEP_MAX_TEMPERATURES, SEG_PREDICT_MAX_CLASSES, 16, 64 and
+    SEG_SWEEP_STAGING_BYTES, which the tests hold against it"""
+    return tuple(int(lib().ifseg_seg_temperature_sweep_limit(c_int(k))) for k in range(5))
+
+
+def seg_temperature_sweep(grids, hp, wp, gt, raw_labels=True, hist=None, sums=None, tally=None, staging_bytes=None):
+    """grids fp32 [K, B, hp*wp, n], contiguous: K grids of class PROBABILITIES of the same images (what `rows_to_f32(softmax=True,
+    temperature=T_k)` / `neighbour_smoothing(..., T_k)` return, stacked), 1 <= K <= SEG_SWEEP_MAX_TEMPERATURES; gt uint8 / int16
+    [B, h, w] -> (hist int64 [K, 256, 2], sums float64 [K, 2], tally int64 [2]): every grid resized to gt's size by `seg_predict`'s
+    rule, bit for bit, and over `seg_areas`' scored pixels hist[k, bin(conf_k), label_k == gt class] += 1,
+    sums[k, 0] += -log(max(p_k[gt class], FLT_MIN)), sums[k, 1] += sum_c p_kc^2 - 2 p_k[gt class] + 1 (both in fp64 on the
+    fp32 values); tally = #scored pixels, #pixels with a ground truth out of range (csrc/tsweep.hip;
+    `predict.temperature_sweep_reference` is the specification).  One launch for all K and a small one that adds the tiles' sums
+    in a fixed order: two calls give equal bits, nothing synchronises, and no [n, h, w] tensor exists.  `hist` / `sums` / `tally`
+    given: ACCUMULATED into and returned, else fresh zeroed ones.  staging_bytes: as in `seg_predict`."""
+    assert grids.dtype == torch.float32 and grids.dim() == 4 and grids.is_contiguous(), (grids.dtype, tuple(grids.shape), grids.stride())
+    K, B, P, n = grids.shape
+    assert 1 <= K <= SEG_SWEEP_MAX_TEMPERATURES and 1 <= n <= SEG_PREDICT_MAX_CLASSES, (K, n)
+    assert P == hp * wp and B >= 1 and hp >= 1 and wp >= 1, (tuple(grids.shape), hp, wp)
+    dev = grids.device
+    h, w = _score_gt(gt, B, dev)
+    assert B * h * w < 2 ** 31, (B, h, w)
+    hist, tally = _counter(hist, (K, SEG_CONF_BINS, 2), dev), _counter(tally, (2,), dev)
+    if sums is None:
+        sums = torch.zeros(K, 2, dtype=torch.float64, device=dev)
+    assert sums.dtype == torch.float64 and tuple(sums.shape) == (K, 2) and sums.is_contiguous() and sums.device == dev, \
+        (sums.dtype, tuple(sums.shape), sums.stride(), sums.device)
+    partials = torch.empty(B * ((h + 15) // 16) * ((w + 63) // 64), K, 2, dtype=torch.float64, device=dev)
+    with _staging(lib().ifseg_seg_temperature_sweep_staging, staging_bytes) if staging_bytes is not None else _UNSTAGED:
+        _check(lib().ifseg_seg_temperature_sweep(_ptr(grids), c_int(K), c_int(B), c_int(hp), c_int(wp), c_int(n), c_int(h), c_int(w),
+                                                 _ptr(gt), c_int(gt.element_size()), c_int(1 if raw_labels else 0), _ptr(hist),
+                                                 _ptr(tally), _ptr(sums), _ptr(partials), _stream()), "seg_temperature_sweep")
+    return hist, sums, tally
+
+
 def seg_pseudo(labels, conf, thresholds, n, boundary=0, raw_labels=True, kept=None, out=None, weight=False):
     """labels uint8 / int16 [H, W] or [B, H, W], conf fp32 of the same shape, thresholds int32 [n] (bins, 0 .. 256) ->
     (out uint8 of the labels' shape, kept int64 [2, n]) in one launch (csrc/pseudo.hip): a pixel of label l in [0, n) whose

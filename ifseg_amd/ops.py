@@ -31,7 +31,8 @@ normalised patch_images, the reference's evaluation transform) and the three ops
 map in one launch), `seg_render` (csrc/render.hip: the label map coloured over its image, with class contours), `seg_conf_hist` / `seg_pseudo`
 (csrc/pseudo.hip: the per-class confidence histogram of a label map, and the label map filtered by per-class thresholds and an
 ignore band along class edges into pseudo-labels for self-training), `seg_calibration` (csrc/calib.hip: how often a confidence
-is right, pixels per predicted class, confidence bin and hit against ground truth) and the two of multi-scale + flip over sliding windows (`seg_predict_slide_views`, `seg_score_slide_views`:
+is right, pixels per predicted class, confidence bin and hit against ground truth), `seg_temperature_sweep` (csrc/tsweep.hip: K
+grids of one forward at K temperatures against one ground truth, per temperature the reliability counts, NLL and Brier) and the two of multi-scale + flip over sliding windows (`seg_predict_slide_views`, `seg_score_slide_views`:
 K views, each a set of windows, merged in one launch, optionally softmaxed per view as mmseg does) are inference only and
 have no backward; `train_load`
 (csrc/trainload.hip: raw images and label maps of any sizes to a training batch under given records, the reference's training
@@ -1246,6 +1247,46 @@ def seg_calibration(labels: torch.Tensor, conf: torch.Tensor, gt: torch.Tensor, 
 def _(labels, conf, gt, n, raw_labels):
     _seg_calibration_check(labels, conf, gt, n)
     return labels.new_empty((n, hip.SEG_CONF_BINS, 2), dtype=torch.int64), labels.new_empty((2,), dtype=torch.int64)
+
+
+def _seg_temperature_sweep_check(grids, hp, wp, gt):
+    op = "ifseg::seg_temperature_sweep"
+    if grids.dtype != torch.float32 or grids.dim() != 4:
+        raise ValueError("%s: grids must be float32 [K, B, hp*wp, n], got %s %s" % (op, grids.dtype, tuple(grids.shape)))
+    K, B, P, n = grids.shape
+    if not 1 <= K <= hip.SEG_SWEEP_MAX_TEMPERATURES:
+        raise ValueError("%s: K = %d grids, the kernel takes 1 .. %d" % (op, K, hip.SEG_SWEEP_MAX_TEMPERATURES))
+    if n < 1 or n > hip.SEG_PREDICT_MAX_CLASSES:
+        raise ValueError("%s: n = %d classes, the kernel takes 1 .. %d" % (op, n, hip.SEG_PREDICT_MAX_CLASSES))
+    if hp < 1 or wp < 1 or B < 1 or P != hp * wp:
+        raise ValueError("%s: grids %s do not hold B >= 1 grids of %d x %d patches" % (op, tuple(grids.shape), hp, wp))
+    _gt_check(op, gt)
+    if gt.dim() != 3 or gt.shape[0] != B or gt.shape[1] < 1 or gt.shape[2] < 1 or gt.numel() >= 2 ** 31:
+        raise ValueError("%s: the ground truth must be [%d, h, w] with fewer than 2**31 pixels, got %s" % (op, B, tuple(gt.shape)))
+    return K
+
+
+@custom_op("ifseg::seg_temperature_sweep", mutates_args=(), device_types="cuda")
+def seg_temperature_sweep(grids: torch.Tensor, hp: int, wp: int, gt: torch.Tensor,
+                          raw_labels: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """K grids of class probabilities fp32 [K, B, hp*wp, n] (one forward's logits softmaxed at K temperatures) against ground
+    truth uint8 / int16 [B, h, w] in one launch (csrc/tsweep.hip) -> (hist int64 [K, 256, 2] = per grid the scored pixels per
+    (confidence bin, hit), sums float64 [K, 2] = per grid the summed negative log likelihood and Brier score, tally int64 [2] =
+    scored pixels, pixels with a ground truth out of range), fresh tensors; `ifseg_amd.predict.temperature_sweep_reference` is
+    the specification.  Counts and sums for choosing a temperature: no autograd."""
+    _seg_temperature_sweep_check(grids, hp, wp, gt)
+    prev = _stream_scope(grids)
+    try:
+        return hip.seg_temperature_sweep(grids.contiguous(), hp, wp, gt.contiguous(), raw_labels)
+    finally:
+        hip.set_stream(prev)
+
+
+@seg_temperature_sweep.register_fake
+def _(grids, hp, wp, gt, raw_labels):
+    K = _seg_temperature_sweep_check(grids, hp, wp, gt)
+    return (grids.new_empty((K, hip.SEG_CONF_BINS, 2), dtype=torch.int64), grids.new_empty((K, 2), dtype=torch.float64),
+            grids.new_empty((2,), dtype=torch.int64))
 
 
 def _seg_pseudo_check(labels, conf, thresholds, n, boundary, raw_labels):

@@ -89,6 +89,18 @@ setting above; `summary()` then carries "ECE", "MCE" and "cECE".  `calibration_r
     t = score.precision_thresholds(0.9)                                            # per class: the bin above which it is 90 % right
     seg.pseudo_label_raw(unlabelled_photos, thresholds=t)
 
+Making the confidence mean something: `seg.calibrate_raw(photos, label_pngs)` is temperature scaling (the same paper's
+one-parameter remedy) from a labelled validation set.  The network's logits do not depend on the temperature, so the forward
+runs once per batch; `patch_scores_at` softmaxes its padded logits at K temperatures (`default_temperatures()`: 16 from 0.297
+to 4.0) and ONE launch of `hip.seg_temperature_sweep` per image (csrc/tsweep.hip) scores all K grids against the ground truth:
+per temperature the reliability counts, NLL and Brier -- the proper scores a temperature is fitted on, which need the true
+class's probability at image resolution and are computed without an [n, H, W] tensor.  `temperature_sweep_reference` is the
+specification.  One plain view only; the Segmenter's own `temperature` is not consulted.
+
+    sweep = seg.calibrate_raw(photos, label_pngs)                                  # a `TemperatureSweep`; into=sweep for more batches
+    sweep.summary()                                    # {"temperatures", "NLL", "Brier", "ECE", "MCE", "aAcc": [K] each, "pixels", "best"}
+    seg.temperature = sweep.best()                     # lowest mean NLL; the confidences of every later call are calibrated
+
 The label map as a picture: `seg.render_raw(photos, ...)` is `segment_raw` followed by one launch of `hip.seg_render`
 (csrc/render.hip) per image, which blends the classes' colours over the original photo and draws class contours -- the demo's
 `cmap[labels]` and `image * (1 - opacity) + cmap[labels] * opacity`, without the label map leaving the device.  The rule is
@@ -507,6 +519,156 @@ def _calibration_errors(N, H, C):
     ece = torch.nansum(N * gap, -1) / total
     mce = torch.nan_to_num(gap, nan=-1.0).amax(-1)
     return ece, torch.where(total > 0, mce, torch.full_like(mce, float("nan")))
+
+
+FLT_MIN = float(torch.finfo(torch.float32).tiny)          # 2^-126: the smallest normal fp32, C's FLT_MIN
+MAX_TEMPERATURES = hip.SEG_SWEEP_MAX_TEMPERATURES
+
+
+def default_temperatures():
+    """the 16 temperatures a sweep tries by default: 2^(j/4), j = -7 .. 8 -- 0.297 to 4.0 in quarter octaves, with 1.0 (the
+    model as it is) and 2.0 on the grid"""
+    return tuple(2 ** (j / 4) for j in range(-7, 9))
+
+
+def _check_temperatures(what, temperatures):
+    """the temperature list of a sweep, checked -> a tuple of 1 .. 16 floats, each finite and > 0"""
+    try:
+        ts = tuple(temperatures)
+    except TypeError:
+        raise ValueError("%s: temperatures must be a sequence of numbers, got %r" % (what, temperatures))
+    if not 1 <= len(ts) <= MAX_TEMPERATURES:
+        raise ValueError("%s: temperatures must hold 1 .. %d values (one launch scores them all), got %d" % (what, MAX_TEMPERATURES, len(ts)))
+    for t in ts:
+        if isinstance(t, bool) or not isinstance(t, (int, float)) or not math.isfinite(t) or t <= 0:
+            raise ValueError("%s: every one of temperatures must be a finite number > 0, got %r" % (what, t))
+    return tuple(float(t) for t in ts)
+
+
+def temperature_sweep_from_probs(probs_k, gt, n, raw_labels=True):
+    """The scoring half of `temperature_sweep_reference`, starting from values at image resolution: probs_k a sequence of K
+    floating tensors [B, n, h, w] (every class's value per pixel under temperature k: `upsample_argmax_reference`'s or
+    `hip.seg_predict`'s `probs`), gt uint8 / int16 [B, h, w] -> (hist int64 [K, 256, 2], sums float64 [K, 2], tally int64 [2]).
+
+    Per k: l = the first maximum over the classes, conf = its value.  The ground-truth rule and the set of scored pixels are
+    `areas_reference`'s; tally[0] = #scored pixels, tally[1] = #pixels with a ground truth out of range; a pixel that is not
+    scored contributes nowhere.  Over the scored pixels, t the true class and p the values AS GIVEN, taken to float64:
+      hist[k, conf_bin(conf), l == t] += 1          (conf rounded to fp32 first where the values are wider)
+      sums[k, 0] += -log(max(p_t, FLT_MIN))         NLL; a probability that underflowed to 0 costs 87.3, not infinity
+      sums[k, 1] += sum_c p_c^2 - 2 p_t + 1         Brier, = sum_c (p_c - onehot_c)^2; every product and sum in float64
+    Runs on any device."""
+    what = "temperature_sweep_from_probs"
+    probs_k = list(probs_k)
+    if not probs_k:
+        raise ValueError("%s: no temperatures" % what)
+    gt = torch.as_tensor(gt)
+    hist, sums, tally = [], [], None
+    for k, probs in enumerate(probs_k):
+        if not torch.is_tensor(probs) or not probs.dtype.is_floating_point or probs.dim() != 4 or probs.shape[1] != n \
+                or (probs.shape[0],) + tuple(probs.shape[2:]) != tuple(gt.shape):
+            raise ValueError("%s: values %d must be floating [B, %d, h, w] for a ground truth [B, h, w] = %s, got %s" % (
+                what, k, n, tuple(gt.shape), (probs.dtype, tuple(probs.shape)) if torch.is_tensor(probs) else type(probs)))
+        labels = probs.argmax(dim=1)
+        lab, cls, scored, tally = _scored_mask(what, labels, gt, n, raw_labels)
+        p = probs.permute(0, 2, 3, 1).reshape(-1, n)[scored]
+        lab, t = lab[scored], cls[scored]
+        conf = p.gather(1, lab[:, None])[:, 0]
+        pt = p.gather(1, t[:, None])[:, 0].double()
+        key = conf_bin(conf.float()) * 2 + (lab == t).long()
+        hist.append(torch.bincount(key, minlength=CONF_BINS * 2).reshape(CONF_BINS, 2))
+        pd = p.double()
+        sums.append(torch.stack([-(pt.clamp_min(FLT_MIN).log()).sum(), ((pd * pd).sum(1) - 2.0 * pt + 1.0).sum()]))
+    return torch.stack(hist), torch.stack(sums), tally
+
+
+def temperature_sweep_reference(grids, hp, wp, gt, raw_labels=True, dtype=torch.float64):
+    """Specification of hip.seg_temperature_sweep: grids [K, B, hp*wp, n] (or a sequence of K [B, hp*wp, n]), class fastest --
+    K grids of class PROBABILITIES of the same images, one forward's logits softmaxed at K temperatures; gt uint8 / int16
+    [B, h, w] -> (hist int64 [K, 256, 2], sums float64 [K, 2], tally int64 [2]).  Per k the grid is resized to gt's (h, w) by
+    `upsample_argmax_reference` (bilinear, align_corners=False, evaluated in `dtype`), and `temperature_sweep_from_probs`
+    scores the K results: per temperature the reliability counts of all classes together -- row k is
+    `calibration_reference(labels_k, conf_k, gt, n)[0].sum(0)` -- and the two proper scores a temperature is fitted on (Guo et
+    al., ICML 2017), summed over the scored pixels.  The kernel interpolates in fp32 (`hip.seg_predict`'s values, bit for
+    bit); this is the fp64 statement it is held against.  Runs on any device."""
+    gt = torch.as_tensor(gt)
+    if gt.dim() != 3:
+        raise ValueError("temperature_sweep_reference: the ground truth must be [B, h, w], got %s" % (tuple(gt.shape),))
+    h, w = int(gt.shape[1]), int(gt.shape[2])
+    grids = list(grids)
+    if not grids:
+        raise ValueError("temperature_sweep_reference: no temperatures")
+    n = int(grids[0].shape[-1])
+    return temperature_sweep_from_probs([upsample_argmax_reference(g, hp, wp, h, w, dtype)[2] for g in grids], gt, n, raw_labels)
+
+
+class TemperatureSweep:
+    """`temperature_sweep_reference`'s counters on the device, summed over everything swept into them: for the K temperatures
+    `temperatures` (a tuple of floats), `hist` int64 [K, 256, 2] (confidence bin, hit), `sums` float64 [K, 2] (NLL, Brier;
+    sums over the scored pixels) and `tally` int64 [2].  `hip.seg_temperature_sweep` adds to these tensors in place, so one
+    sweep can span a validation set (`Segmenter.calibrate_raw(..., into=sweep)`).  n: the class count of what was swept
+    (None: not known yet; `calibrate_raw` sets it)."""
+
+    def __init__(self, temperatures, device=None, n=None):
+        self.temperatures = _check_temperatures("TemperatureSweep", temperatures)
+        K = len(self.temperatures)
+        self.n = None if n is None else int(n)
+        self.hist = torch.zeros(K, CONF_BINS, 2, dtype=torch.int64, device=device)
+        self.sums = torch.zeros(K, 2, dtype=torch.float64, device=device)
+        self.tally = torch.zeros(2, dtype=torch.int64, device=device)
+
+    def add_(self, other):
+        if tuple(other.temperatures) != self.temperatures:
+            raise ValueError("TemperatureSweep.add_: temperatures %r against %r: sweeps of different lists do not add"
+                             % (other.temperatures, self.temperatures))
+        if self.n is not None and other.n is not None and self.n != other.n:
+            raise ValueError("TemperatureSweep.add_: %d classes against %d" % (other.n, self.n))
+        self.n = other.n if self.n is None else self.n
+        self.hist += other.hist.to(self.hist.device)
+        self.sums += other.sums.to(self.sums.device)
+        self.tally += other.tally.to(self.tally.device)
+        return self
+
+    def _bins(self, what, bins):
+        if not isinstance(bins, int) or isinstance(bins, bool) or bins < 1 or CONF_BINS % bins:
+            raise ValueError("TemperatureSweep.%s: bins must be an int that divides %d, got %r" % (what, CONF_BINS, bins))
+        return _reliability_bins(self.hist, bins, True)
+
+    def reliability(self, k, bins=16):
+        """row k's reliability diagram -> (pixels int64, accuracy float64, confidence float64), each [bins], as
+        `SegmentationScore.reliability` gives them for all classes together.  Not synchronising."""
+        if not isinstance(k, int) or isinstance(k, bool) or not 0 <= k < len(self.temperatures):
+            raise ValueError("TemperatureSweep.reliability: k must be an int in 0 .. %d, got %r" % (len(self.temperatures) - 1, k))
+        N, H, C = self._bins("reliability", bins)
+        return N[k].long(), H[k] / N[k], C[k] / N[k]
+
+    def summary(self):
+        """-> {"temperatures": [K], "NLL": [K], "Brier": [K] (means per scored pixel), "ECE": [K], "MCE": [K] (16 bins, as
+        `SegmentationScore.summary`), "aAcc": [K], "pixels", "best"}: float64 from the counters, not rounded; NaN (and best
+        None) without pixels.  "best" is the temperature of lowest mean NLL, the first one on a tie.  The one place that
+        synchronises with the host.  Ground truth out of range is an IndexError, as in `SegmentationScore.summary`."""
+        K = len(self.temperatures)
+        ece, mce = _calibration_errors(*self._bins("summary", 16))
+        h = self.hist.double()
+        flat = torch.cat([self.sums.reshape(-1), ece, mce, h[..., 1].sum(1) / h.sum((1, 2)), self.tally.double()]).tolist()
+        pixels, bad = int(flat[5 * K]), int(flat[5 * K + 1])
+        if bad != 0:
+            raise IndexError("TemperatureSweep: tally[1] = %d ground-truth pixels hold a class outside [0, n) that is not an "
+                             "ignore value (wrong raw_labels, or a label map of another dataset?)" % bad)
+        nan = float("nan")
+        nll = [flat[2 * k] / pixels if pixels else nan for k in range(K)]
+        best = min(range(K), key=lambda k: nll[k]) if pixels else None          # min keeps the first of equal values
+        return {"temperatures": list(self.temperatures), "NLL": nll,
+                "Brier": [flat[2 * k + 1] / pixels if pixels else nan for k in range(K)],
+                "ECE": flat[2 * K:3 * K], "MCE": flat[3 * K:4 * K], "aAcc": flat[4 * K:5 * K], "pixels": pixels,
+                "best": None if best is None else self.temperatures[best]}
+
+    def best(self):
+        """the temperature of lowest mean NLL over what was swept, the first one on a tie (`summary()["best"]`: one host round
+        trip, and `summary`'s IndexError); a ValueError without scored pixels.  Then: `seg.temperature = sweep.best()`."""
+        best = self.summary()["best"]
+        if best is None:
+            raise ValueError("TemperatureSweep.best: no scored pixels have been swept")
+        return best
 
 
 def pseudo_thresholds(hist, keep=1.0, floor=0.0):
@@ -976,6 +1138,17 @@ class Segmenter:
     # -- the call ------------------------------------------------------------------------
     def patch_scores(self, patch_images):
         """model forward -> (scores fp32 [B, hp*wp, n] in the chosen mode, hp, wp)"""
+        pad, hp, wp, feat = self._padded_logits(patch_images)
+        with torch.no_grad():
+            if self.smooth_iters > 0:
+                scores = hip.neighbour_smoothing(pad, self.n, feat, self.smooth_iters, self.smooth_topk, self.temperature)
+            else:
+                scores = hip.rows_to_f32(pad, self.n, hp * wp, softmax=self.upsample == "probs", temperature=self.temperature)
+        return scores, hp, wp
+
+    def _padded_logits(self, patch_images):
+        """model forward in eval mode -> (the padded logits bf16 [B, T, ld], hp, wp, the trunk features [B, hp*wp, D]): what
+        `patch_scores` turns into scores, before the temperature enters"""
         model = self.model
         was_training = model.training
         if was_training:
@@ -983,17 +1156,24 @@ class Segmenter:
         try:
             with torch.no_grad():
                 _, extra = model(**self.net_input(patch_images), full_context_alignment=self.full_context_alignment)
-                pad = extra["logits_padded"]
-                hp, wp = extra["encoder_returns"]["image_embed_shape"][0]
-                if self.smooth_iters > 0:
-                    feat = extra["encoder_returns"]["image_embed_before_proj"][0]
-                    scores = hip.neighbour_smoothing(pad, self.n, feat, self.smooth_iters, self.smooth_topk, self.temperature)
-                else:
-                    scores = hip.rows_to_f32(pad, self.n, hp * wp, softmax=self.upsample == "probs", temperature=self.temperature)
         finally:
             if was_training:
                 model.train()
-        return scores, hp, wp
+        hp, wp = extra["encoder_returns"]["image_embed_shape"][0]
+        return extra["logits_padded"], hp, wp, extra["encoder_returns"]["image_embed_before_proj"][0]
+
+    def patch_scores_at(self, patch_images, temperatures):
+        """ONE model forward -> (grids fp32 [K, B, hp*wp, n], hp, wp): the class probabilities of that forward's padded logits at
+        each of the K temperatures, `hip.rows_to_f32(softmax=True, temperature=T_k)` (with `smooth_iters > 0`:
+        `hip.neighbour_smoothing(..., T_k)`) run K times -- grid k is bit for bit what `patch_scores` of a
+        `Segmenter(temperature=T_k, upsample="probs")` gives.  The Segmenter's own `temperature` is not consulted."""
+        pad, hp, wp, feat = self._padded_logits(patch_images)
+        with torch.no_grad():
+            if self.smooth_iters > 0:
+                grids = [hip.neighbour_smoothing(pad, self.n, feat, self.smooth_iters, self.smooth_topk, T) for T in temperatures]
+            else:
+                grids = [hip.rows_to_f32(pad, self.n, hp * wp, softmax=True, temperature=T) for T in temperatures]
+            return torch.stack(grids), hp, wp
 
     def _views_merge(self, vs):
         """the merge of the K views (scores, hp, wp, flip) of one image or batch; one plain view is the single-view kernel"""
@@ -1492,3 +1672,97 @@ class Segmenter:
             labels = self._count(score, self._views_merge([(scores, hp, wp, False)]), gt.to(patch_images.device).contiguous(),
                                  raw_labels, rgb, return_labels)
         return (score, labels) if return_labels else score
+
+    # -- choosing the temperature ---------------------------------------------------------
+    def _sweep_into(self, what, temperatures, into, dev, scales=(1.0,), flip=False, slide=None):
+        """the sweep a calibrating call adds to, every argument and setting checked before anything is launched"""
+        if len(view_list(scales, flip)) != 1 or flip:
+            raise ValueError("Segmenter.%s: a temperature sweep takes one plain view, got scales=%r, flip=%r (the mean of several "
+                             "views' probabilities is not one softmax of one forward's logits)" % (what, tuple(scales), flip))
+        if slide is not None and slide is not False:
+            raise ValueError("Segmenter.%s: a temperature sweep does not slide, got slide=%r (windows are merged before the "
+                             "temperature could be applied per pixel)" % (what, slide))
+        if self.crf_iters > 0:
+            raise ValueError("Segmenter.%s: a temperature sweep scores the network's probabilities, this Segmenter has "
+                             "crf_iters = %d (the CRF's marginals are not a function of one temperature)" % (what, self.crf_iters))
+        bad = self._conf_setting(None)
+        if bad is not None:
+            raise ValueError("Segmenter.%s: the values must be probabilities, this Segmenter has %s; use upsample='probs' or the "
+                             "smoothing" % (what, bad))
+        temps = _check_temperatures("Segmenter.%s" % what, default_temperatures() if temperatures is None else temperatures)
+        if into is None:
+            return TemperatureSweep(temps, dev, self.n)
+        if not isinstance(into, TemperatureSweep) or into.temperatures != temps or into.n not in (None, self.n) or into.hist.device != dev:
+            raise ValueError("Segmenter.%s: into must be a TemperatureSweep of the temperatures %r and %d classes on %s, got %s"
+                             % (what, temps, self.n, dev, (into.temperatures, into.n, into.hist.device)
+                                if isinstance(into, TemperatureSweep) else type(into)))
+        into.n = self.n
+        return into
+
+    def calibrate_raw(self, images, label_maps, temperatures=None, raw_labels=True, max_batch=8, mean=None, std=None,
+                      reverse_channels=False, into=None, scales=(1.0,), flip=False, slide=None):
+        """Temperature scaling (Guo et al., ICML 2017) from a labelled validation set -> a `TemperatureSweep`: which softmax
+        temperature makes this model's confidences mean what they say.  `evaluate_raw`'s front for a single plain view
+        (images, label_maps, raw_labels, max_batch, mean, std, reverse_channels and the checks of images and label maps: as
+        there), but the forward runs ONCE per batch; `patch_scores_at` then turns its padded logits into K grids of
+        probabilities, one `hip.rows_to_f32(softmax=True, temperature=T_k)` (with the smoothing: `hip.neighbour_smoothing`)
+        per temperature, and ONE launch of `hip.seg_temperature_sweep` per image (csrc/tsweep.hip) scores all K against the
+        image's ground truth: per temperature the reliability counts, the summed NLL and the summed Brier score.  No
+        [n, H, W] tensor exists and nothing synchronises with the host; `sweep.summary()` is the one round trip.
+        temperatures: 1 .. 16 finite numbers > 0, None: `default_temperatures()`.  The Segmenter's own `temperature` is not
+        consulted; afterwards `seg.temperature = sweep.best()`.  into: a sweep of the same temperatures, class count and
+        device to accumulate into (a whole validation set).  `temperature_sweep_reference` is the specification.
+        A ValueError naming the setting, before anything is launched: `scales` / `flip` other than one plain view, `slide`,
+        `crf_iters > 0`, upsample="logits" without the smoothing (the values must be probabilities), a bad temperature list,
+        an `into` that does not match."""
+        what = "calibrate_raw"
+        dev = next(self.model.parameters()).device
+        sweep = self._sweep_into(what, temperatures, into, dev, scales, flip, slide)
+        checked = self._check_raw(what, images, scales, flip)
+        gts = [label_maps] if torch.is_tensor(label_maps) else list(label_maps)
+        imgs = [] if checked is None else checked[1]
+        if len(gts) != len(imgs):
+            raise ValueError("Segmenter.calibrate_raw: %d label maps for %d images" % (len(gts), len(imgs)))
+        for i, (im, g) in enumerate(zip(imgs, gts)):
+            if not torch.is_tensor(g) or g.dtype not in (torch.uint8, torch.int16) or tuple(g.shape) != tuple(im.shape[:2]):
+                raise ValueError("Segmenter.calibrate_raw: label map %d must be a uint8 or int16 tensor of its image's shape %s, got %s"
+                                 % (i, tuple(im.shape[:2]), (g.dtype, tuple(g.shape)) if torch.is_tensor(g) else type(g)))
+        if checked is None:
+            return sweep
+        mean, std = HALF if mean is None else mean, HALF if std is None else std
+        imgs = [im.to(dev, non_blocking=True) for im in imgs]
+        gts = [g.to(dev, non_blocking=True).contiguous() for g in gts]
+        _, loads, forwards = plan_views([(int(im.shape[0]), int(im.shape[1])) for im in imgs], self.model.cfg.patch_image_size,
+                                        scales, False, max_batch)
+        x, per_image = {}, [None] * len(imgs)
+        with torch.no_grad():
+            for _, size, idx in loads:
+                t = hip.image_load(torch.stack([imgs[i] for i in idx]), size[0], size[1], mean, std, reverse_channels)
+                for k, i in enumerate(idx):
+                    x[i, size] = t[k]
+            for size, iv in forwards:
+                grids, hp, wp = self.patch_scores_at(torch.stack([x[i, size] for i, _ in iv]), sweep.temperatures)
+                for k, (i, _) in enumerate(iv):
+                    per_image[i] = (grids[:, k:k + 1].contiguous(), hp, wp)
+            for (grids, hp, wp), g in zip(per_image, gts):           # in image order: the sums do not depend on the batches
+                hip.seg_temperature_sweep(grids, hp, wp, g[None], raw_labels, hist=sweep.hist, sums=sweep.sums, tally=sweep.tally)
+        return sweep
+
+    def calibrate(self, images, label_maps, temperatures=None, raw_labels=True, into=None):
+        """`calibrate_raw` for what `evaluate` takes: images normalised float [B, 3, H, W] or uint8 RGB [B, H, W, 3] / [H, W, 3],
+        label_maps uint8 / int16 [B, h, w] (or [h, w] for one image) -> a `TemperatureSweep`: one forward, K
+        `hip.rows_to_f32` and one launch of `hip.seg_temperature_sweep` for the whole batch, at the ground truth's own size."""
+        gt = label_maps
+        if not torch.is_tensor(gt) or gt.dtype not in (torch.uint8, torch.int16) or gt.dim() not in (2, 3) or gt.numel() == 0:
+            raise ValueError("Segmenter.calibrate: label_maps must be a uint8 or int16 tensor [B, h, w], got %s"
+                             % ((gt.dtype, tuple(gt.shape)) if torch.is_tensor(gt) else type(gt),))
+        gt = gt[None] if gt.dim() == 2 else gt
+        if torch.is_tensor(images) and images.dim() >= 3 and gt.shape[0] != (1 if images.dim() == 3 else images.shape[0]):
+            raise ValueError("Segmenter.calibrate: %d label maps for images %s" % (gt.shape[0], tuple(images.shape)))
+        patch_images, _ = self.prepare_images(images)
+        sweep = self._sweep_into("calibrate", temperatures, into, patch_images.device)
+        grids, hp, wp = self.patch_scores_at(patch_images, sweep.temperatures)
+        with torch.no_grad():
+            hip.seg_temperature_sweep(grids, hp, wp, gt.to(patch_images.device).contiguous(), raw_labels, hist=sweep.hist,
+                                      sums=sweep.sums, tally=sweep.tally)
+        return sweep

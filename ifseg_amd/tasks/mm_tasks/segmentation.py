@@ -217,6 +217,16 @@ class SegmentationTask(TaskBase):
         seg = self.build_segmenter(model, **{k: kw.pop(k) for k in ctor if k in kw})
         return seg.evaluate_raw(images, label_maps, slide=slide, **kw)
 
+    def calibrate_raw(self, model, images, label_maps, **kw):
+        """raw uint8 images and their label maps -> a `TemperatureSweep`: one forward per batch scored at every temperature of
+        `temperatures` (None: `predict.default_temperatures()`) on the device, `sweep.best()` being the temperature of lowest
+        mean NLL: `build_segmenter(model, ...).calibrate_raw(images, label_maps, ...)`.  Keywords of the Segmenter's constructor
+        go to it, the others to `Segmenter.calibrate_raw`."""
+        ctor = ("category_token_ids", "prompt_ids", "upsample", "smooth_iters", "smooth_topk", "temperature", "crf_iters",
+                "full_context_alignment", "label_dtype", "slide_views")
+        seg = self.build_segmenter(model, **{k: kw.pop(k) for k in ctor if k in kw})
+        return seg.calibrate_raw(images, label_maps, **kw)
+
     def render_raw(self, model, images, **kw):
         """raw uint8 images -> a list of `RenderResult(picture, labels, conf)`, the label maps coloured over the photos on the
         device: `build_segmenter(model, ...).render_raw(images, ...)`.  Keywords of the Segmenter's constructor go to it, the

@@ -914,6 +914,37 @@ int ifseg_seg_calibration(const void* labels, int label_bytes, const float* conf
 /* the kernel's table sizes: which = 0 the classes up to which the direct table counts, 1 the slots of the hashed table, 2 the
  * pixels a workgroup takes per step, 3 the workgroups of a launch at most; any other which: IFSEG_ERR_BAD_ARG. */
 int ifseg_seg_calibration_limit(int which);
+/* ifseg_seg_temperature_sweep scores K score grids of the same images against one ground truth in one launch (temperature
+ * scaling, Guo et al., ICML 2017: the grids are one forward's logits softmaxed at K temperatures; csrc/tsweep.hip; predict.py:
+ * temperature_sweep_reference).  grids fp32 [K][B][hp*wp][n], class fastest, contiguous, PROBABILITIES; gt [B][h][w] uint8 /
+ * int16 (gt_bytes).  Per pixel and k: p_kc is ifseg_seg_predict's value of class c on grid k, bit for bit (the coordinate rule
+ * and the flat four-weight value above), l_k the smallest c with maximal p_kc, conf_k = p_{k,l_k}.  The ground-truth rule and
+ * the set of scored pixels are ifseg_seg_areas'; tally uint64 [2] += #scored pixels, #pixels whose ground truth is out of
+ * range, once per pixel, not per k.  A pixel that is not scored contributes nowhere.  Over the scored pixels, t the true class:
+ *   hist[k][bin(conf_k)][l_k == t] += 1          uint64 [K][256][2], all classes together; bin as for ifseg_seg_conf_hist
+ *   sums[k][0] += -log(max(p_kt, FLT_MIN))       the negative log likelihood: fp64 log of the fp32 value, so a probability
+ *                                                that underflowed to 0 costs 87.3, not infinity
+ *   sums[k][1] += sum_c p_kc^2 - 2 p_kt + 1      the Brier score: every product and sum in fp64 on the fp32 values
+ * hist, tally and sums (fp64 [K][2]) are ADDED to and never cleared.  The integers leave a workgroup's private LDS table as
+ * one 64-bit atomic per non-zero bin: exact.  The floats are reduced in a fixed order -- lanes by a butterfly, the four waves
+ * in order, into partials fp64 [tiles][K][2], tiles = B * ceil(h / 16) * ceil(w / 64) (limits 2 and 3), which the caller
+ * provides and the call overwrites; a second launch adds the tiles in index order into sums -- so two calls give equal bits
+ * and there are no floating-point atomics.  Nothing else is written, nothing is allocated, and the call does not synchronise.
+ * hist row k is ifseg_seg_calibration's counters of (l_k, conf_k) summed over the classes.
+ * A workgroup owns 16 x 64 pixels and stages the footprint of one grid at a time in LDS; what is left of 64 KiB beside the
+ * table (2 KiB per temperature) and the waves' sums is the staging buffer, and a footprint that exceeds it reads global
+ * memory instead (same bits).  ifseg_seg_temperature_sweep_staging sets the size of that buffer like
+ * ifseg_seg_predict_staging, for this entry point only.
+ * NULL or misaligned pointers (grids 4 bytes; hist, tally, sums, partials 8; an int16 gt at an odd address), K outside 1..16,
+ * n outside 1..512, gt_bytes outside {1, 2}: IFSEG_ERR_BAD_ARG; B, hp, wp, h, w < 1, 2 hp h or 2 wp w >= 2^31, B*h*w >= 2^31,
+ * hp*wp >= 2^22: IFSEG_ERR_BAD_SHAPE; nothing is launched on a refusal. */
+int ifseg_seg_temperature_sweep(const float* grids, int K, int B, int hp, int wp, int n, int h, int w, const void* gt,
+                                int gt_bytes, int raw_labels, unsigned long long* hist, unsigned long long* tally, double* sums,
+                                double* partials, void* stream);
+int ifseg_seg_temperature_sweep_staging(int max_bytes);
+/* which = 0: the largest K, 1: the largest n, 2 / 3: the rows / columns of a tile (partials holds one [K][2] block per tile),
+ * 4: the staging buffer's bytes at the largest K; any other which: IFSEG_ERR_BAD_ARG. */
+int ifseg_seg_temperature_sweep_limit(int which);
 /* ifseg_seg_pseudo filters labels [B, H, W] (uint8 / int16) by conf fp32 [B, H, W] into out uint8 [B, H, W], one launch: a
  * pixel of label l is KEPT iff 0 <= l < n, bin(conf) >= thresholds[l] (int32 [n] on the device, 0 keeps every bin, 256 none)
  * and, with boundary = r (0..4), no pixel INSIDE the image at |dx| <= r and |dy| <= r carries a different label value
