@@ -5,13 +5,13 @@
 //
 //   seg_calibration_kernel   calibration[label][bin(conf)][label == gt class] over the scored pixels of a label map of any
 //                            length: seg_conf_hist_kernel's walk with the ground truth as a third stream (count.h's
-//                            walk_pixels3) -- 256 lanes x 16 pixels per step, grid-stride -- into count.h's workgroup-private
-//                            table, direct up to n = 32, hashed above
+//                            walk_pixels) -- 256 lanes x 16 pixels per step, grid-stride -- into count.h's workgroup-private
+//                            table, direct up to n = 32, hashed above; the two tallies leave by wave (tally_flush),
+//                            and the host's side is count.h's walk_launch
 // Bandwidth- and launch-bound: 6 B per pixel (8 with int16 maps), no arithmetic to speak of.  The direct table at n = 32 is
 // the whole 64 KiB LDS budget of the project, so two workgroups share a CU's 160 KiB there; the walk has no barrier between
 // table_zero and table_flush, and its LDS atomics are one per wave and step on a piecewise-constant map (table_add).
 #include "count.h"
-#include "../../include/ifseg_hip.h"
 
 namespace {
 
@@ -37,20 +37,15 @@ __global__ __launch_bounds__(256) void seg_calibration_kernel(const unsigned cha
   table_zero(btab, hashed, dwords);
 
   int inside = 0, outside = 0;
-  walk_pixels3<LB, FloatStream, MapStream<GB>>(lab, conf, gt, head, groups, tail, [&](int l, float c, int g, bool live) {
+  walk_pixels<LB, FloatStream, MapStream<GB>>(lab, conf, head, groups, tail, [&](int l, float c, int g, bool live) {
     const GtClass t = gt_class(n, raw, g, live);
     const bool in = t.sc && (unsigned)l < (unsigned)n;
     inside += in;
     outside += t.sc && !in;
     table_add(btab, hashed, in ? (l * 256 + conf_bin(c)) * 2 + (l == t.cls ? 1 : 0) : 0, in, calibration);
-  });
+  }, gt);
 
-#pragma unroll
-  for (int o = 32; o; o >>= 1) { inside += __shfl_xor(inside, o); outside += __shfl_xor(outside, o); }
-  if ((threadIdx.x & 63) == 0) {
-    if (inside) atomicAdd(&tally[0], (unsigned long long)inside);
-    if (outside) atomicAdd(&tally[1], (unsigned long long)outside);
-  }
+  tally_flush(inside, outside, tally);
   table_flush(btab, hashed, dwords, calibration);
 }
 
@@ -59,29 +54,12 @@ __global__ __launch_bounds__(256) void seg_calibration_kernel(const unsigned cha
 extern "C" int ifseg_seg_calibration(const void* labels, int label_bytes, const float* conf, const void* gt, int gt_bytes,
                                      long long npix, int n, int raw_labels, unsigned long long* calibration,
                                      unsigned long long* tally, void* stream) {
-  (void)hipGetLastError();
-  if (!labels || !conf || !gt || !calibration || !tally) return IFSEG_ERR_BAD_ARG;
-  if ((label_bytes != 1 && label_bytes != 2) || (gt_bytes != 1 && gt_bytes != 2)) return IFSEG_ERR_BAD_ARG;
-  if (((size_t)labels & (size_t)(label_bytes - 1)) || ((size_t)gt & (size_t)(gt_bytes - 1)) || ((size_t)conf & 3) ||
-      ((size_t)calibration & 7) || ((size_t)tally & 7))
-    return IFSEG_ERR_BAD_ARG;
-  if (n < 1 || n > CB_MAX_CLASSES) return IFSEG_ERR_BAD_ARG;
-  if (npix < 1 || npix >= (1ll << 31)) return IFSEG_ERR_BAD_SHAPE;
-  const WalkSplit w = walk_split(labels, label_bytes, npix);
-  const size_t lds = (size_t)cb_dwords(n) * sizeof(uint32_t);
-  const unsigned char* l = (const unsigned char*)labels;
-  const unsigned char* g = (const unsigned char*)gt;
-  const int raw = raw_labels != 0;
-#define IFSEG_CALIBRATION(LB, GB)                                                                                            \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(seg_calibration_kernel<LB, GB>), dim3(w.blocks), dim3(256), lds, (hipStream_t)stream, l, \
-                     conf, g, w.head, w.groups, w.tail, n, raw, calibration, tally)
-  if (label_bytes == 1 && gt_bytes == 1) IFSEG_CALIBRATION(1, 1);
-  else if (label_bytes == 1) IFSEG_CALIBRATION(1, 2);
-  else if (gt_bytes == 1) IFSEG_CALIBRATION(2, 1);
-  else IFSEG_CALIBRATION(2, 2);
-#undef IFSEG_CALIBRATION
-  IFSEG_CHECK_LAUNCH();
-  return 0;
+  return walk_launch<true, true>({labels, label_bytes, gt, gt_bytes, conf}, calibration, tally, n, CB_MAX_CLASSES, npix,
+                                 [&](auto LB, auto GB, const WalkSplit& w) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(seg_calibration_kernel<LB(), GB()>), dim3(w.blocks), dim3(256),
+                       (size_t)cb_dwords(n) * sizeof(uint32_t), (hipStream_t)stream, (const unsigned char*)labels, conf,
+                       (const unsigned char*)gt, w.head, w.groups, w.tail, n, raw_labels != 0, calibration, tally);
+  });
 }
 
 extern "C" int ifseg_seg_calibration_limit(int which) {

@@ -2,13 +2,15 @@
 // pseudo.hip: seg_conf_hist_kernel, seg_pseudo_kernel; calib.hip: seg_calibration_kernel), each part written once:
 //   bin_add       the wave pre-aggregated add into an LDS count
 //   walk_pixels   the grid-stride walk over a flat label map and a second stream of the same pixels -- an integer map
-//                 (ground truth: MapStream) or fp32 values (confidences: FloatStream) -- with walk_split, the host's side of it;
-//                 walk_pixels3 is the same walk with both
+//                 (ground truth: MapStream) or fp32 values (confidences: FloatStream) -- or of both
 //   table_*       the workgroup-private table of keyed counts, direct or hashed: table_zero, table_add, table_flush
+//   tally_flush, bins_flush   the two ways a thread's pair of tallies leaves: by wave, or through a table of plain bins
+//   walk_launch   the host's side of the walk: what every counter on it refuses, walk_split, the (label, gt) element sizes
 // Integers throughout, so every counter built from these is bit-reproducible.
 #pragma once
 #include <algorithm>
 #include "common.h"
+#include "../../include/ifseg_hip.h"
 
 namespace count {
 
@@ -128,67 +130,50 @@ struct FloatStream {
   }
 };
 
-// the walk of a label map (LB bytes per label) and a second stream, its one statement: f(label, second, live) for every
-// pixel, called by whole (converged) waves.  Head and tail go to lanes 0..15 and 16..31 of the grid's first wave, one pixel
-// each; the body's groups of 16 to the lanes, grid-stride
-template <int LB, typename Second, typename F>
-__device__ __forceinline__ void walk_pixels(const unsigned char* lab, typename Second::P sec, int head, int groups, int tail, F f) {
-  using T = typename Second::T;
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (blockIdx.x == 0 && wave == 0) {
-    long long i = -1;
-    if (lane < head) i = lane;
-    else if (lane >= 16 && lane - 16 < tail) i = (long long)head + (long long)groups * 16 + (lane - 16);
-    const bool live = i >= 0;
-    f(live ? elem_at<LB>(lab, i) : 0, live ? Second::at(sec, i) : T(0), live);
-  }
-  const unsigned char* lb = lab + (long long)head * LB;           // on a 16-byte boundary
-  const Second second(sec, head);
-  for (long long base = (long long)blockIdx.x * 256 + wave * 64; base < groups; base += (long long)gridDim.x * 256) {
-    const long long g = base + lane;
-    const bool live = g < groups;
-    int pv[16] = {};
-    T sv[16] = {};
-    if (live) {
-      load16<LB>(lb + g * (16 * LB), 0, pv);
-      second.group(g, sv);
-    }
-#pragma unroll
-    for (int i = 0; i < 16; ++i) f(pv[i], sv[i], live);
-  }
-}
+// no further stream
+struct NoStream {
+  using T = int;
+  using P = const void*;
+  __device__ __forceinline__ NoStream(P, int) {}
+};
 
-// the walk with a third stream of the same pixels (calib.hip: the confidences and the ground truth beside the labels), the
-// statement above with one more load per group: f(label, second, third, live).  The two-stream walks do not go through it
-template <int LB, typename Second, typename Third, typename F>
-__device__ __forceinline__ void walk_pixels3(const unsigned char* lab, typename Second::P sec, typename Third::P thi, int head,
-                                             int groups, int tail, F f) {
+// the walk of a label map (LB bytes per label) and one or two further streams, its one statement: f(label, second, live), or
+// f(label, second, third, live) where there is a Third, for every pixel, called by whole (converged) waves.  Head and tail go
+// to lanes 0..15 and 16..31 of the grid's first wave, one pixel each; the body's groups of 16 to the lanes, grid-stride
+template <int LB, typename Second, typename Third = NoStream, typename F>
+__device__ __forceinline__ void walk_pixels(const unsigned char* lab, typename Second::P sec, int head, int groups, int tail, F f,
+                                            typename Third::P thi = nullptr) {
   using T = typename Second::T;
   using U = typename Third::T;
+  constexpr bool three = !std::is_same<Third, NoStream>::value;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (blockIdx.x == 0 && wave == 0) {
     long long i = -1;
     if (lane < head) i = lane;
     else if (lane >= 16 && lane - 16 < tail) i = (long long)head + (long long)groups * 16 + (lane - 16);
     const bool live = i >= 0;
-    f(live ? elem_at<LB>(lab, i) : 0, live ? Second::at(sec, i) : T(0), live ? Third::at(thi, i) : U(0), live);
+    if constexpr (three) f(live ? elem_at<LB>(lab, i) : 0, live ? Second::at(sec, i) : T(0), live ? Third::at(thi, i) : U(0), live);
+    else f(live ? elem_at<LB>(lab, i) : 0, live ? Second::at(sec, i) : T(0), live);
   }
   const unsigned char* lb = lab + (long long)head * LB;           // on a 16-byte boundary
   const Second second(sec, head);
-  const Third third(thi, head);
+  [[maybe_unused]] const Third third(thi, head);
   for (long long base = (long long)blockIdx.x * 256 + wave * 64; base < groups; base += (long long)gridDim.x * 256) {
     const long long g = base + lane;
     const bool live = g < groups;
     int pv[16] = {};
     T sv[16] = {};
-    U tv[16] = {};
+    [[maybe_unused]] U tv[three ? 16 : 1] = {};
     if (live) {
       load16<LB>(lb + g * (16 * LB), 0, pv);
       second.group(g, sv);
-      third.group(g, tv);
+      if constexpr (three) third.group(g, tv);
     }
 #pragma unroll
-    for (int i = 0; i < 16; ++i) f(pv[i], sv[i], tv[i], live);
+    for (int i = 0; i < 16; ++i) {
+      if constexpr (three) f(pv[i], sv[i], tv[i], live);
+      else f(pv[i], sv[i], live);
+    }
   }
 }
 
@@ -204,6 +189,42 @@ inline WalkSplit walk_split(const void* labels, int label_bytes, long long npix)
   w.tail = (int)(npix - w.head - 16ll * w.groups);
   w.blocks = std::min(std::max((w.groups + 255) / 256, 1), MAX_BLOCKS);
   return w;
+}
+
+// The launch of a counter on the walk (ifseg_seg_areas, _confusion, _conf_hist, _calibration), its one statement.  GT / CONF:
+// the counter reads a ground truth / confidences beside the labels.  Refused, as IFSEG_ERR_BAD_ARG: a missing map or counter
+// array, an element size other than 1 | 2, a misaligned pointer, n outside [1, max_n]; then, as IFSEG_ERR_BAD_SHAPE, npix
+// outside [1, 2^31).  launch(LB, GB, w) starts the kernel of the label / ground-truth element sizes LB() / GB() (a
+// std::integral_constant each; GB() = 1 without GT) on the split w
+struct WalkMaps {
+  const void* labels;
+  int label_bytes;
+  const void* gt;
+  int gt_bytes;
+  const float* conf;
+};
+
+template <bool GT, bool CONF, typename Launch>
+int walk_launch(const WalkMaps& m, const unsigned long long* counts, const unsigned long long* tally, int n, int max_n,
+                long long npix, Launch launch) {
+  (void)hipGetLastError();
+  const int gb = GT ? m.gt_bytes : 1;
+  if (!m.labels || (GT && !m.gt) || (CONF && !m.conf) || !counts || !tally) return IFSEG_ERR_BAD_ARG;
+  if ((m.label_bytes != 1 && m.label_bytes != 2) || (gb != 1 && gb != 2)) return IFSEG_ERR_BAD_ARG;
+  if (((size_t)m.labels & (size_t)(m.label_bytes - 1)) || (GT && ((size_t)m.gt & (size_t)(gb - 1))) ||
+      (CONF && ((size_t)m.conf & 3)) || ((size_t)counts & 7) || ((size_t)tally & 7))
+    return IFSEG_ERR_BAD_ARG;
+  if (n < 1 || n > max_n) return IFSEG_ERR_BAD_ARG;
+  if (npix < 1 || npix >= (1ll << 31)) return IFSEG_ERR_BAD_SHAPE;
+  const WalkSplit w = walk_split(m.labels, m.label_bytes, npix);
+  using B1 = std::integral_constant<int, 1>;
+  using B2 = std::integral_constant<int, 2>;
+  if (m.label_bytes == 1 && gb == 1) launch(B1{}, B1{}, w);
+  else if (m.label_bytes == 1) launch(B1{}, B2{}, w);
+  else if (gb == 1) launch(B2{}, B1{}, w);
+  else launch(B2{}, B2{}, w);
+  IFSEG_CHECK_LAUNCH();
+  return 0;
 }
 
 // ---- the table ----
@@ -268,6 +289,37 @@ __device__ __forceinline__ void table_flush(uint32_t* tab, bool hashed, int dwor
       const uint32_t v = tab[i];
       if (v) atomicAdd(&global[i], (unsigned long long)v);
     }
+  }
+}
+
+// ---- the tallies ----
+// A thread's pair of tallies, kept in registers over the walk or the tile.  Summed over the wave, they leave as two 64-bit
+// atomics where the table is keyed or fills the LDS budget (tally_flush) ...
+__device__ __forceinline__ void wave_tallies(int& a, int& b) {
+#pragma unroll
+  for (int o = 32; o; o >>= 1) { a += __shfl_xor(a, o); b += __shfl_xor(b, o); }
+}
+__device__ __forceinline__ void tally_flush(int a, int b, unsigned long long* tally) {
+  wave_tallies(a, b);
+  if ((threadIdx.x & 63) == 0) {
+    if (a) atomicAdd(&tally[0], (unsigned long long)a);
+    if (b) atomicAdd(&tally[1], (unsigned long long)b);
+  }
+}
+
+// ... or join a direct table of `bins` plain bins as two more (tab holds bins + 2 dwords); then a barrier, and the non-zero
+// bins leave to counts[bins] / tally[2]: one 64-bit atomic per workgroup and bin
+__device__ __forceinline__ void bins_flush(uint32_t* tab, int bins, int a, int b, unsigned long long* counts,
+                                           unsigned long long* tally) {
+  wave_tallies(a, b);
+  if ((threadIdx.x & 63) == 0) {
+    if (a) atomicAdd(&tab[bins], (uint32_t)a);
+    if (b) atomicAdd(&tab[bins + 1], (uint32_t)b);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < bins + 2; i += 256) {
+    const uint32_t v = tab[i];
+    if (v) atomicAdd(i < bins ? counts + i : tally + (i - bins), (unsigned long long)v);
   }
 }
 

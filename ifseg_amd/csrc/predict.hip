@@ -32,8 +32,9 @@
 // from elsewhere.  Only the non-zero bins leave a workgroup, one 64-bit integer atomic each: integer sums, so the counters
 // are bit-reproducible.  The instantiations without the flag have none of this.
 // The confusion matrix (ifseg_seg_confusion) is a second stand-alone kernel on a label map, seg_confusion_kernel: its table does
-// not fit the epilogues' LDS budget.  The wave pre-aggregated add (bin_add), the walk over a flat label map (walk_pixels,
-// walk_split) and the direct / hashed workgroup table (table_*) are count.h's, shared with pseudo.hip.
+// not fit the epilogues' LDS budget.  The wave pre-aggregated add (bin_add), the walk over a flat label map (walk_pixels), the
+// direct / hashed workgroup table (table_*), the exit of the epilogues' table with its two tallies (bins_flush) and the host's
+// launch path of the two stand-alone kernels (walk_launch) are count.h's, shared with pseudo.hip, calib.hip and tsweep.hip.
 #include "count.h"
 #include "tile.h"
 #include "upsample.h"
@@ -166,7 +167,7 @@ __device__ __forceinline__ void score_zero(uint32_t* tab, int n) {
 }
 
 // one pixel (where `live`) into the table: the ground-truth rule, then the three bins.  scored / bad: the thread's own
-// tallies, added by score_flush
+// tallies, which leave through the table (count.h's bins_flush)
 __device__ __forceinline__ void score_pixel(uint32_t* tab, int n, int raw, int pred, int g, bool live, int& scored, int& bad) {
   const GtClass t = gt_class(n, raw, g, live);
   const int cls = t.cls;
@@ -176,22 +177,6 @@ __device__ __forceinline__ void score_pixel(uint32_t* tab, int n, int raw, int p
   bin_add(tab, 2 * n + cls, sc);
   bin_add(tab, n + pred, pin);
   bin_add(tab, cls, pin && pred == cls);
-}
-
-// the tallies join the table, a barrier, and the non-zero bins leave: one 64-bit atomic per workgroup and bin
-__device__ __forceinline__ void score_flush(uint32_t* tab, int n, int scored, int bad, unsigned long long* areas,
-                                            unsigned long long* tally) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) { scored += __shfl_xor(scored, o); bad += __shfl_xor(bad, o); }
-  if ((threadIdx.x & 63) == 0) {
-    if (scored) atomicAdd(&tab[3 * n], (uint32_t)scored);
-    if (bad) atomicAdd(&tab[3 * n + 1], (uint32_t)bad);
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < 3 * n + 2; i += 256) {
-    const uint32_t v = tab[i];
-    if (v) atomicAdd(i < 3 * n ? areas + i : tally + (i - 3 * n), (unsigned long long)v);
-  }
 }
 
 // the epilogue of both predict kernels: lane = x, the wave's four rows; pred[j] is the label of row wave * 4 + j
@@ -204,7 +189,7 @@ __device__ __forceinline__ void score_tile(const Score& sc, uint32_t* tab, int n
     if (ok[j]) g = sc.gt_bytes == 1 ? elem_at<1>(sc.gt, image + pofs[j]) : elem_at<2>(sc.gt, image + pofs[j]);
     score_pixel(tab, n, sc.raw, pred[j], g, ok[j], scored, bad);
   }
-  score_flush(tab, n, scored, bad, sc.areas, sc.tally);
+  bins_flush(tab, 3 * n, scored, bad, sc.areas, sc.tally);
 }
 
 // phase 2 of the four predict kernels, behind the barrier that publishes the label / conf tile: store_tile writes the tile
@@ -967,7 +952,7 @@ __global__ __launch_bounds__(256) void seg_areas_kernel(const unsigned char* __r
   int scored = 0, bad = 0;
   walk_pixels<LB, MapStream<GB>>(lab, gt, head, groups, tail,
                   [&](int pred, int g, bool live) { score_pixel(tab, n, raw, pred, g, live, scored, bad); });
-  score_flush(tab, n, scored, bad, areas, tally);
+  bins_flush(tab, 3 * n, scored, bad, areas, tally);
 }
 
 // ---- which class is taken for which: the confusion matrix of a label map ----
@@ -1045,9 +1030,7 @@ int launch_predict(const float* scores, int B, int hp, int wp, int n, int h, int
   if (rc) return rc;
   // the scoring launches take their table out of the staging budget
   const int table = S::on ? score_dwords(n) * 4 : 0;
-  const int limit = std::max(std::min(g_stage_limit, PT_STAGE_LIMIT - table), 0);
-  const long long need = footprint_bound(hp, hp, h, TILE_ROWS, 3) * footprint_bound(wp, wp, w, TILE_COLS, 3) * pt_stride(n) * 4;
-  const int lds = (int)std::min<long long>(need, limit) & ~15;
+  const int lds = stage_bytes(hp, wp, n, h, w, std::min(g_stage_limit, PT_STAGE_LIMIT - table));
   hipLaunchKernelGGL(seg_predict_kernel<S>, dim3((unsigned)blocks), dim3(256), lds + table, (hipStream_t)stream, scores, hp, wp,
                      n, h, w, tiles_x, tiles_y, labels, label_bytes, conf, probs, lds / 4, sc);
   IFSEG_CHECK_LAUNCH();
@@ -1235,50 +1218,22 @@ extern "C" int ifseg_seg_score_windows(const float* scores, int B, int hpw, int 
 
 extern "C" int ifseg_seg_areas(const void* labels, int label_bytes, const void* gt, int gt_bytes, long long npix, int n,
                                int raw_labels, unsigned long long* areas, unsigned long long* tally, void* stream) {
-  (void)hipGetLastError();
-  if (!labels || (label_bytes != 1 && label_bytes != 2) || ((size_t)labels & (size_t)(label_bytes - 1))) return IFSEG_ERR_BAD_ARG;
-  if (const int rc = score_refusal(gt, gt_bytes, areas, tally)) return rc;
-  if (n < 1 || n > PT_MAX_CLASSES) return IFSEG_ERR_BAD_ARG;
-  if (npix < 1 || npix >= (1ll << 31)) return IFSEG_ERR_BAD_SHAPE;
-  const WalkSplit w = walk_split(labels, label_bytes, npix);
-  const unsigned char* l = (const unsigned char*)labels;
-  const unsigned char* g = (const unsigned char*)gt;
-  const int raw = raw_labels != 0;
-#define IFSEG_AREAS(LB, GB)                                                                                                  \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(seg_areas_kernel<LB, GB>), dim3(w.blocks), dim3(256), 0, (hipStream_t)stream, l, g,  \
-                     w.head, w.groups, w.tail, n, raw, areas, tally)
-  if (label_bytes == 1 && gt_bytes == 1) IFSEG_AREAS(1, 1);
-  else if (label_bytes == 1) IFSEG_AREAS(1, 2);
-  else if (gt_bytes == 1) IFSEG_AREAS(2, 1);
-  else IFSEG_AREAS(2, 2);
-#undef IFSEG_AREAS
-  IFSEG_CHECK_LAUNCH();
-  return 0;
+  return walk_launch<true, false>({labels, label_bytes, gt, gt_bytes, nullptr}, areas, tally, n, PT_MAX_CLASSES, npix,
+                                  [&](auto LB, auto GB, const WalkSplit& w) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(seg_areas_kernel<LB(), GB()>), dim3(w.blocks), dim3(256), 0, (hipStream_t)stream,
+                       (const unsigned char*)labels, (const unsigned char*)gt, w.head, w.groups, w.tail, n, raw_labels != 0, areas,
+                       tally);
+  });
 }
 
 extern "C" int ifseg_seg_confusion(const void* labels, int label_bytes, const void* gt, int gt_bytes, long long npix, int n,
                                    int raw_labels, unsigned long long* confusion, void* stream) {
-  (void)hipGetLastError();
-  if (!labels || (label_bytes != 1 && label_bytes != 2) || ((size_t)labels & (size_t)(label_bytes - 1))) return IFSEG_ERR_BAD_ARG;
-  if (!gt || !confusion || (gt_bytes != 1 && gt_bytes != 2)) return IFSEG_ERR_BAD_ARG;
-  if (((size_t)confusion & 7) || ((size_t)gt & (size_t)(gt_bytes - 1))) return IFSEG_ERR_BAD_ARG;
-  if (n < 1 || n > PT_MAX_CLASSES) return IFSEG_ERR_BAD_ARG;
-  if (npix < 1 || npix >= (1ll << 31)) return IFSEG_ERR_BAD_SHAPE;
-  const WalkSplit w = walk_split(labels, label_bytes, npix);
-  const size_t lds = (size_t)sc_dwords(n) * sizeof(uint32_t);
-  const unsigned char* l = (const unsigned char*)labels;
-  const unsigned char* g = (const unsigned char*)gt;
-  const int raw = raw_labels != 0;
-#define IFSEG_CONFUSION(LB, GB)                                                                                            \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(seg_confusion_kernel<LB, GB>), dim3(w.blocks), dim3(256), lds, (hipStream_t)stream, l, \
-                     g, w.head, w.groups, w.tail, n, raw, confusion)
-  if (label_bytes == 1 && gt_bytes == 1) IFSEG_CONFUSION(1, 1);
-  else if (label_bytes == 1) IFSEG_CONFUSION(1, 2);
-  else if (gt_bytes == 1) IFSEG_CONFUSION(2, 1);
-  else IFSEG_CONFUSION(2, 2);
-#undef IFSEG_CONFUSION
-  IFSEG_CHECK_LAUNCH();
-  return 0;
+  return walk_launch<true, false>({labels, label_bytes, gt, gt_bytes, nullptr}, confusion, confusion, n, PT_MAX_CLASSES, npix,
+                                  [&](auto LB, auto GB, const WalkSplit& w) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(seg_confusion_kernel<LB(), GB()>), dim3(w.blocks), dim3(256),
+                       (size_t)sc_dwords(n) * sizeof(uint32_t), (hipStream_t)stream, (const unsigned char*)labels,
+                       (const unsigned char*)gt, w.head, w.groups, w.tail, n, raw_labels != 0, confusion);
+  });
 }
 
 extern "C" int ifseg_seg_confusion_limit(int which) {

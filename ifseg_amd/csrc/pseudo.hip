@@ -5,7 +5,8 @@
 //
 //   seg_conf_hist_kernel   hist[label][bin(conf)] over a label map of any length: count.h's walk with the confidences as its
 //                          second stream -- 256 lanes x 16 pixels per step, grid-stride -- into count.h's workgroup-private
-//                          table, direct up to n = 64, hashed above
+//                          table, direct up to n = 64, hashed above; the two tallies leave by wave (tally_flush), and the
+//                          host's side is count.h's walk_launch
 //   seg_pseudo_kernel      one 16 x 64 tile (tile.h) per workgroup: labels plus a halo of r (tile.h's halo_stage /
 //                          halo_differs), the thresholds staged, lane = x reads its own conf and stores its own byte
 // Both are bandwidth- and launch-bound: 5 B (hist) and 6 B (filter) per pixel, no arithmetic to speak of.
@@ -45,12 +46,7 @@ __global__ __launch_bounds__(256) void seg_conf_hist_kernel(const unsigned char*
     table_add(htab, hashed, in ? l * 256 + conf_bin(c) : 0, in, hist);
   });
 
-#pragma unroll
-  for (int o = 32; o; o >>= 1) { inside += __shfl_xor(inside, o); outside += __shfl_xor(outside, o); }
-  if ((threadIdx.x & 63) == 0) {
-    if (inside) atomicAdd(&tally[0], (unsigned long long)inside);
-    if (outside) atomicAdd(&tally[1], (unsigned long long)outside);
-  }
+  tally_flush(inside, outside, tally);
   table_flush(htab, hashed, dwords, hist);
 }
 
@@ -109,23 +105,11 @@ __global__ __launch_bounds__(256) void seg_pseudo_kernel(const L* __restrict__ l
 
 extern "C" int ifseg_seg_conf_hist(const void* labels, int label_bytes, const float* conf, long long npix, int n,
                                    unsigned long long* hist, unsigned long long* tally, void* stream) {
-  (void)hipGetLastError();
-  if (!labels || !conf || !hist || !tally || (label_bytes != 1 && label_bytes != 2)) return IFSEG_ERR_BAD_ARG;
-  if ((label_bytes == 2 && ((size_t)labels & 1)) || ((size_t)conf & 3) || ((size_t)hist & 7) || ((size_t)tally & 7))
-    return IFSEG_ERR_BAD_ARG;
-  if (n < 1 || n > HC_MAX_CLASSES) return IFSEG_ERR_BAD_ARG;
-  if (npix < 1 || npix >= (1ll << 31)) return IFSEG_ERR_BAD_SHAPE;
-  const WalkSplit w = walk_split(labels, label_bytes, npix);
-  const int lds = hc_dwords(n) * 4;
-  const unsigned char* l = (const unsigned char*)labels;
-  if (label_bytes == 1)
-    hipLaunchKernelGGL(seg_conf_hist_kernel<1>, dim3(w.blocks), dim3(256), lds, (hipStream_t)stream, l, conf, w.head, w.groups,
-                       w.tail, n, hist, tally);
-  else
-    hipLaunchKernelGGL(seg_conf_hist_kernel<2>, dim3(w.blocks), dim3(256), lds, (hipStream_t)stream, l, conf, w.head, w.groups,
-                       w.tail, n, hist, tally);
-  IFSEG_CHECK_LAUNCH();
-  return 0;
+  return walk_launch<false, true>({labels, label_bytes, nullptr, 0, conf}, hist, tally, n, HC_MAX_CLASSES, npix,
+                                  [&](auto LB, auto, const WalkSplit& w) {
+    hipLaunchKernelGGL(seg_conf_hist_kernel<LB()>, dim3(w.blocks), dim3(256), hc_dwords(n) * 4, (hipStream_t)stream,
+                       (const unsigned char*)labels, conf, w.head, w.groups, w.tail, n, hist, tally);
+  });
 }
 
 namespace {

@@ -9,10 +9,11 @@
 //                           outer loop.  Per k the footprint of grid k is staged in LDS at pt_stride(n) as phase 0 of
 //                           seg_predict_kernel stages it (a footprint that does not fit reads global memory in the same loop),
 //                           and the class walk gives per pixel the running first maximum and sum_c p^2 in fp64; the true
-//                           class's value is one more blend.  blend (blend4), pt_stride and Best are upsample.h's, shared with
-//                           predict.hip: the value of a class is seg_predict's bit for bit.
+//                           class's value is one more blend.  blend (blend4), pt_stride, Best and the host's stage_bytes are
+//                           upsample.h's, shared with predict.hip: the value of a class is seg_predict's bit for bit.
 //                           Integers: a workgroup-private uint32 table [K][256][2] (+ the two tallies) in LDS, filled through
-//                           count.h's wave-aggregated bin_add; only the non-zero bins leave, one 64-bit atomic each.
+//                           count.h's wave-aggregated bin_add; only the non-zero bins leave, one 64-bit atomic each
+//                           (count.h's bins_flush, the exit of seg_predict's scoring epilogue).
 //                           Floats: the pixel's terms are fp64; a wave adds its lanes' by a butterfly, the workgroup its four
 //                           waves in wave order, and the tile's K x 2 sums go to partials[tile][k][2].  No floating-point
 //                           atomics, so every output is bit-reproducible.
@@ -207,18 +208,7 @@ __global__ __launch_bounds__(256) void seg_tsweep_kernel(const float* __restrict
     if (lane == 0) { red[(k * 4 + wave) * 2] = nll; red[(k * 4 + wave) * 2 + 1] = brier; }
   }
 
-  // the tallies join the table, a barrier, and the non-zero bins leave: one 64-bit atomic per workgroup and bin
-#pragma unroll
-  for (int o = 32; o; o >>= 1) { scored += __shfl_xor(scored, o); bad += __shfl_xor(bad, o); }
-  if (lane == 0) {
-    if (scored) atomicAdd(&tab[K * TS_BINS * 2], (uint32_t)scored);
-    if (bad) atomicAdd(&tab[K * TS_BINS * 2 + 1], (uint32_t)bad);
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < K * TS_BINS * 2 + 2; i += 256) {
-    const uint32_t v = tab[i];
-    if (v) atomicAdd(i < K * TS_BINS * 2 ? hist + i : tally + (i - K * TS_BINS * 2), (unsigned long long)v);
-  }
+  bins_flush(tab, K * TS_BINS * 2, scored, bad, hist, tally);
   // the tile's sums: the four waves in wave order
   if ((int)threadIdx.x < 2 * K) {
     const int k = threadIdx.x >> 1, which = threadIdx.x & 1;
@@ -261,9 +251,7 @@ extern "C" int ifseg_seg_temperature_sweep(const float* grids, int K, int B, int
   long long blocks;
   if (!tile_grid(h, w, B, &tiles_x, &tiles_y, &blocks)) return IFSEG_ERR_BAD_SHAPE;
   const int fixed = ts_table_dwords(K) * 4 + ts_red_bytes(K);
-  const int limit = std::max(std::min(g_ts_stage_limit, ts_stage_limit(K)), 0);
-  const long long need = footprint_bound(hp, hp, h, TILE_ROWS, 3) * footprint_bound(wp, wp, w, TILE_COLS, 3) * pt_stride(n) * 4;
-  const int lds = (int)std::min<long long>(need, limit) & ~15;
+  const int lds = stage_bytes(hp, wp, n, h, w, std::min(g_ts_stage_limit, ts_stage_limit(K)));
   hipLaunchKernelGGL(seg_tsweep_kernel, dim3((unsigned)blocks), dim3(256), lds + fixed, (hipStream_t)stream, grids, K,
                      (long long)B * hp * wp * n, hp, wp, n, h, w, tiles_x, tiles_y, gt, gt_bytes, raw_labels != 0, hist, tally,
                      partials, lds / 4);

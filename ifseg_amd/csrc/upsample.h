@@ -1,8 +1,9 @@
 // The value rule of the score-grid upsampling kernels (predict.hip: the four seg_predict* kernels; tsweep.hip:
 // seg_tsweep_kernel), each part written once: the LDS stride of a staged patch, a pixel's running first maximum and the flat
-// four-weight value of one class (and of four at once).  Both files promise the same bits for the same grid, so neither keeps a copy.
+// four-weight value of one class (and of four at once); and the host's size of the staged patches under a tile (stage_bytes:
+// seg_predict_kernel, seg_tsweep_kernel).  Both files promise the same bits for the same grid, so neither keeps a copy.
 #pragma once
-#include "common.h"
+#include "tile.h"
 
 namespace upsample {
 
@@ -33,6 +34,15 @@ template <typename W>
 __device__ __forceinline__ f32x4 blend4(W w00, W w01, W w10, W w11, f32x4 a, f32x4 b, f32x4 c, f32x4 d) {
 #pragma clang fp contract(off)
   return w00 * a + w01 * b + w10 * c + w11 * d;
+}
+
+// ---- host ----
+// the dynamic LDS, in bytes, of the staged patches of an [hp, wp, n] grid under any tile of an [h, w] output: the bound of
+// the footprint, at most `limit`, in whole 16-byte slots
+inline int stage_bytes(int hp, int wp, int n, int h, int w, int limit) {
+  const long long need = tile::footprint_bound(hp, hp, h, tile::TILE_ROWS, 3) * tile::footprint_bound(wp, wp, w, tile::TILE_COLS, 3) *
+                         pt_stride(n) * 4;
+  return (int)std::min<long long>(need, std::max(limit, 0)) & ~15;
 }
 
 }  // namespace upsample

@@ -1396,6 +1396,16 @@ def _staging(setter, staging_bytes):
 _UNSTAGED = contextlib.nullcontext()
 
 
+def _staged(setter, staging_bytes):
+    """`_staging` for the short launches: a call that leaves the limit alone (None) pays for no generator context"""
+    return _staging(getattr(lib(), setter), staging_bytes) if staging_bytes is not None else _UNSTAGED
+
+
+def _limits(symbol, count):
+    """the first `count` values of one of the library's ifseg_*_limit(which) entry points"""
+    return tuple(int(getattr(lib(), symbol)(c_int(k))) for k in range(count))
+
+
 def _predict_outputs(B, n, h, w, dev, conf, probs, label_dtype, want_labels=True):
     """-> (labels [B, h, w] uint8 for n <= 256 else int16, or `label_dtype` (None without want_labels: the scoring calls); conf
     fp32 [B, h, w] or None; probs fp32 [B, n, h, w] or None), uninitialised"""
@@ -1429,8 +1439,7 @@ def _seg_launch(checked, hw, gt, raw_labels=True, labels=True, conf=False, probs
     if gt is not None:
         args += (_ptr(gt), c_int(gt.element_size()), c_int(1 if raw_labels else 0), _ptr(areas), _ptr(tally))
     symbol = symbols[0] if gt is None else symbols[1]
-    # (a call that leaves the staging limit alone pays for no context manager: these launches are short)
-    with _staging(getattr(lib(), symbols[2]), staging_bytes) if staging_bytes is not None else _UNSTAGED:
+    with _staged(symbols[2], staging_bytes):
         _check(getattr(lib(), symbol)(*args, _stream()), symbol[6:])
     return (lab, cf, pr) if gt is None else (areas, tally, lab, cf, pr)
 
@@ -1510,13 +1519,19 @@ def _score_counters(n, dev, areas, tally):
     return _counter(areas, (3, n), dev), _counter(tally, (2,), dev)
 
 
-def _label_pair(labels, gt, n):
-    """what seg_areas and seg_confusion ask of their two maps"""
-    assert labels.dtype in (torch.uint8, torch.int16) and labels.is_contiguous(), (labels.dtype, labels.stride())
-    assert gt.dtype in (torch.uint8, torch.int16) and gt.is_contiguous(), (gt.dtype, gt.stride())
-    assert labels.shape == gt.shape and labels.device == gt.device, (tuple(labels.shape), tuple(gt.shape), labels.device, gt.device)
-    assert 1 <= n <= SEG_PREDICT_MAX_CLASSES, n
-    assert 1 <= labels.numel() < 2 ** 31, tuple(labels.shape)
+def _label_maps(what, labels, conf, gt, n=None):
+    """what the kernels over a finished label map ask of it and of the maps beside it, its confidences and / or its ground
+    truth (None: the kernel takes none): contiguous, of one shape on one device, 1 .. 2^31 - 1 pixels (and, where given,
+    1 <= n <= SEG_PREDICT_MAX_CLASSES)"""
+    assert labels.dtype in (torch.uint8, torch.int16) and labels.is_contiguous(), (what, labels.dtype, labels.stride())
+    assert conf is None or (conf.dtype == torch.float32 and conf.is_contiguous() and conf.shape == labels.shape
+                            and conf.device == labels.device), \
+        (what, conf.dtype, tuple(conf.shape), conf.stride(), tuple(labels.shape), conf.device, labels.device)
+    assert gt is None or (gt.dtype in (torch.uint8, torch.int16) and gt.is_contiguous() and gt.shape == labels.shape
+                          and gt.device == labels.device), \
+        (what, gt.dtype, tuple(gt.shape), gt.stride(), tuple(labels.shape), gt.device, labels.device)
+    assert n is None or (isinstance(n, int) and 1 <= n <= SEG_PREDICT_MAX_CLASSES), (what, n)
+    assert 1 <= labels.numel() < 2 ** 31, (what, tuple(labels.shape))
 
 
 def _score_gt(gt, B, dev):
@@ -1530,7 +1545,7 @@ def seg_areas(labels, gt, n, raw_labels=True, areas=None, tally=None):
     per class #(pred = gt = c), #(pred = c), #(gt = c) over the scored pixels; #scored pixels, #pixels with a ground truth out of
     range (csrc/predict.hip; `predict.areas_reference` is the specification and states the ground-truth rule).  `areas` / `tally`
     given: ACCUMULATED into, else fresh zeroed ones.  For label maps that do not come out of seg_score / seg_score_views."""
-    _label_pair(labels, gt, n)
+    _label_maps("seg_areas", labels, None, gt, n)
     areas, tally = _score_counters(n, labels.device, areas, tally)
     _check(lib().ifseg_seg_areas(_ptr(labels), c_int(labels.element_size()), _ptr(gt), c_int(gt.element_size()),
                                  c_ll(labels.numel()), c_int(n), c_int(1 if raw_labels else 0), _ptr(areas), _ptr(tally),
@@ -1548,7 +1563,7 @@ SEG_CONFUSION_MAX_BLOCKS = 512      # == count::MAX_BLOCKS: the workgroups of a 
 def seg_confusion_limits():
     """-> (direct table entries, hashed slots, pixels per workgroup step, workgroups at most) as the loaded library states them
     (`ifseg_seg_confusion_limit`): the four constants above, which the tests hold against it"""
-    return tuple(int(lib().ifseg_seg_confusion_limit(c_int(k))) for k in range(4))
+    return _limits("ifseg_seg_confusion_limit", 4)
 
 
 def seg_confusion(labels, gt, n, raw_labels=True, confusion=None):
@@ -1556,7 +1571,7 @@ def seg_confusion(labels, gt, n, raw_labels=True, confusion=None):
     scored pixels of `seg_areas`, [c, p] = #(gt = c and pred = p), column n taking every predicted label outside [0, n)
     (csrc/predict.hip; `predict.confusion_reference` is the specification).  `confusion` given: ACCUMULATED into, else fresh
     zeros.  Its sum is seg_areas' tally[0], the diagonal / column sums of [:, :n] areas[0] / areas[1], its row sums areas[2]."""
-    _label_pair(labels, gt, n)
+    _label_maps("seg_confusion", labels, None, gt, n)
     confusion = _counter(confusion, (n, n + 1), labels.device)
     _check(lib().ifseg_seg_confusion(_ptr(labels), c_int(labels.element_size()), _ptr(gt), c_int(gt.element_size()),
                                      c_ll(labels.numel()), c_int(n), c_int(1 if raw_labels else 0), _ptr(confusion), _stream()),
@@ -1571,7 +1586,7 @@ SEG_BOUNDARY_MAX_D = 64             # == SEG_BOUNDARY_MAX_D there: the band's ha
 def seg_boundary_limits():
     """-> (the largest d, the largest n) as the loaded library states them (`ifseg_seg_boundary_limit`): SEG_BOUNDARY_MAX_D and
     SEG_PREDICT_MAX_CLASSES, which the tests hold against it"""
-    return tuple(int(lib().ifseg_seg_boundary_limit(c_int(k))) for k in range(2))
+    return _limits("ifseg_seg_boundary_limit", 2)
 
 
 def seg_boundary_areas(labels, gt, n, d, raw_labels=True, bareas=None, band=False):
@@ -1581,7 +1596,7 @@ def seg_boundary_areas(labels, gt, n, d, raw_labels=True, bareas=None, band=Fals
     `band` the two bands themselves, bit 0 the ground truth's and bit 1 the labels', for every pixel (csrc/boundary.hip;
     `predict.boundary_areas_reference` is the specification and states the rule).  `bareas` given: ACCUMULATED into, else fresh
     zeros.  One launch, nothing else allocated."""
-    _label_pair(labels, gt, n)
+    _label_maps("seg_boundary_areas", labels, None, gt, n)
     assert labels.dim() in (2, 3), tuple(labels.shape)
     assert isinstance(d, int) and not isinstance(d, bool) and 1 <= d <= SEG_BOUNDARY_MAX_D, d
     bareas = _counter(bareas, (3, n), labels.device)
@@ -1774,20 +1789,12 @@ def seg_pseudo_max_classes(raw_labels=True):
     return SEG_PSEUDO_MAX_CLASSES - 1 if raw_labels else SEG_PSEUDO_MAX_CLASSES
 
 
-def _labels_conf(labels, conf, what):
-    assert labels.dtype in (torch.uint8, torch.int16) and labels.is_contiguous(), (what, labels.dtype, labels.stride())
-    assert conf.dtype == torch.float32 and conf.is_contiguous() and conf.shape == labels.shape and conf.device == labels.device, \
-        (what, conf.dtype, tuple(conf.shape), conf.stride(), tuple(labels.shape), conf.device, labels.device)
-    assert 1 <= labels.numel() < 2 ** 31, (what, tuple(labels.shape))
-
-
 def seg_conf_hist(labels, conf, n, hist=None, tally=None):
     """labels uint8 / int16 [...] (predicted classes), conf fp32 of the same shape -> (hist int64 [n, 256], tally int64 [2]):
     hist[c, b] = #(label = c and clamp(floor(conf * 256), 0, 255) = b), tally = #labels in [0, n), #labels outside
     (csrc/pseudo.hip; `predict.confidence_histogram_reference` is the specification).  `hist` / `tally` given: ACCUMULATED
     into, else fresh zeroed ones.  1 <= n <= 512."""
-    _labels_conf(labels, conf, "seg_conf_hist")
-    assert isinstance(n, int) and 1 <= n <= SEG_PREDICT_MAX_CLASSES, n
+    _label_maps("seg_conf_hist", labels, conf, None, n)
     hist, tally = _counter(hist, (n, SEG_CONF_BINS), labels.device), _counter(tally, (2,), labels.device)
     _check(lib().ifseg_seg_conf_hist(_ptr(labels), c_int(labels.element_size()), _ptr(conf), c_ll(labels.numel()), c_int(n),
                                      _ptr(hist), _ptr(tally), _stream()), "seg_conf_hist")
@@ -1804,7 +1811,7 @@ SEG_CALIBRATION_MAX_BLOCKS = SEG_CONFUSION_MAX_BLOCKS
 def seg_calibration_limits():
     """-> (direct classes, hashed slots, pixels per workgroup step, workgroups at most) as the loaded library states them
     (`ifseg_seg_calibration_limit`): the four constants above, which the tests hold against it"""
-    return tuple(int(lib().ifseg_seg_calibration_limit(c_int(k))) for k in range(4))
+    return _limits("ifseg_seg_calibration_limit", 4)
 
 
 def seg_calibration(labels, conf, gt, n, raw_labels=True, calibration=None, tally=None):
@@ -1813,10 +1820,7 @@ def seg_calibration(labels, conf, gt, n, raw_labels=True, calibration=None, tall
     clamp(floor(conf * 256), 0, 255) = b, (l == gt class) = hit); tally = #scored pixels with a label in [0, n), #scored pixels
     with a label outside (csrc/calib.hip; `predict.calibration_reference` is the specification).  `calibration` / `tally`
     given: ACCUMULATED into and returned, else fresh zeroed ones.  One launch on the current stream.  1 <= n <= 512."""
-    _labels_conf(labels, conf, "seg_calibration")
-    assert gt.dtype in (torch.uint8, torch.int16) and gt.is_contiguous() and gt.shape == labels.shape and gt.device == labels.device, \
-        ("seg_calibration", gt.dtype, gt.stride(), tuple(gt.shape), tuple(labels.shape), gt.device, labels.device)
-    assert isinstance(n, int) and 1 <= n <= SEG_PREDICT_MAX_CLASSES, n
+    _label_maps("seg_calibration", labels, conf, gt, n)
     calibration = _counter(calibration, (n, SEG_CONF_BINS, 2), labels.device)
     tally = _counter(tally, (2,), labels.device)
     _check(lib().ifseg_seg_calibration(_ptr(labels), c_int(labels.element_size()), _ptr(conf), _ptr(gt), c_int(gt.element_size()),
@@ -1834,7 +1838,7 @@ def seg_temperature_sweep_limits():
     """-> (the largest K, the largest n, a tile's rows, a tile's columns, the staging bytes at the largest K) as the loaded
     library states them (`ifseg_seg_temperature_sweep_limit`): SEG_SWEEP_MAX_TEMPERATURES, SEG_PREDICT_MAX_CLASSES, 16, 64 and
     SEG_SWEEP_STAGING_BYTES, which the tests hold against it"""
-    return tuple(int(lib().ifseg_seg_temperature_sweep_limit(c_int(k))) for k in range(5))
+    return _limits("ifseg_seg_temperature_sweep_limit", 5)
 
 
 def seg_temperature_sweep(grids, hp, wp, gt, raw_labels=True, hist=None, sums=None, tally=None, staging_bytes=None):
@@ -1860,7 +1864,7 @@ def seg_temperature_sweep(grids, hp, wp, gt, raw_labels=True, hist=None, sums=No
     assert sums.dtype == torch.float64 and tuple(sums.shape) == (K, 2) and sums.is_contiguous() and sums.device == dev, \
         (sums.dtype, tuple(sums.shape), sums.stride(), sums.device)
     partials = torch.empty(B * ((h + 15) // 16) * ((w + 63) // 64), K, 2, dtype=torch.float64, device=dev)
-    with _staging(lib().ifseg_seg_temperature_sweep_staging, staging_bytes) if staging_bytes is not None else _UNSTAGED:
+    with _staged("ifseg_seg_temperature_sweep_staging", staging_bytes):
         _check(lib().ifseg_seg_temperature_sweep(_ptr(grids), c_int(K), c_int(B), c_int(hp), c_int(wp), c_int(n), c_int(h), c_int(w),
                                                  _ptr(gt), c_int(gt.element_size()), c_int(1 if raw_labels else 0), _ptr(hist),
                                                  _ptr(tally), _ptr(sums), _ptr(partials), _stream()), "seg_temperature_sweep")
@@ -1878,7 +1882,7 @@ def seg_pseudo(labels, conf, thresholds, n, boundary=0, raw_labels=True, kept=No
     weight=True: the same launch also writes the loss weight of every pixel, and the call returns (out, kept, weight uint8 of
     the labels' shape): 0 where out is 255, max(conf_bin(conf), 1) where the pixel was kept."""
     assert labels.dim() in (2, 3), tuple(labels.shape)
-    _labels_conf(labels, conf, "seg_pseudo")
+    _label_maps("seg_pseudo", labels, conf, None)
     assert isinstance(n, int) and 1 <= n <= seg_pseudo_max_classes(raw_labels), (n, raw_labels)
     assert isinstance(boundary, int) and 0 <= boundary <= SEG_RENDER_MAX_BOUNDARY, boundary
     dev = labels.device

@@ -1014,14 +1014,23 @@ def _gt_check(op, gt):
         raise ValueError("%s: ground truth must be uint8 or int16 (label PNG values or class ids), got dtype %s" % (op, gt.dtype))
 
 
-def _seg_areas_check(labels, gt, n, op="ifseg::seg_areas"):
+def _maps_check(op, labels, conf=None, gt=None):
+    """a predicted label map and what lies beside it, its confidences and / or its ground truth: one shape, 1 .. 2**31 - 1 pixels"""
     if labels.dtype not in (torch.uint8, torch.int16):
         raise ValueError("%s: labels must be uint8 or int16 (what seg_predict gives), got dtype %s" % (op, labels.dtype))
-    _gt_check(op, gt)
-    if labels.shape != gt.shape:
-        raise ValueError("%s: labels %s and ground truth %s must have one shape" % (op, tuple(labels.shape), tuple(gt.shape)))
+    if conf is not None and (conf.dtype != torch.float32 or conf.shape != labels.shape):
+        raise ValueError("%s: conf must be float32 of the labels' shape %s, got %s %s"
+                         % (op, tuple(labels.shape), conf.dtype, tuple(conf.shape)))
+    if gt is not None:
+        _gt_check(op, gt)
+        if labels.shape != gt.shape:
+            raise ValueError("%s: labels %s and ground truth %s must have one shape" % (op, tuple(labels.shape), tuple(gt.shape)))
     if labels.numel() < 1 or labels.numel() >= 2 ** 31:
         raise ValueError("%s: 1 <= pixels < 2**31, got %s" % (op, tuple(labels.shape)))
+
+
+def _seg_areas_check(labels, gt, n, op="ifseg::seg_areas"):
+    _maps_check(op, labels, gt=gt)
     if n < 1 or n > SEG_LOSS_MAX_CLASSES:
         raise ValueError("%s: n = %d classes, the kernel takes 1 .. FUSED_MAX_CLASSES = %d" % (op, n, SEG_LOSS_MAX_CLASSES))
 
@@ -1185,22 +1194,12 @@ def _(labels, image, palette, opacity, boundary, boundary_color, conf):
 
 
 # ----------------------------------------------------------------------------------------------- seg_conf_hist, seg_pseudo
-def _labels_conf_check(op, labels, conf):
-    if labels.dtype not in (torch.uint8, torch.int16):
-        raise ValueError("%s: labels must be uint8 or int16 (what seg_predict gives), got dtype %s" % (op, labels.dtype))
-    if conf.dtype != torch.float32 or conf.shape != labels.shape:
-        raise ValueError("%s: conf must be float32 of the labels' shape %s, got %s %s"
-                         % (op, tuple(labels.shape), conf.dtype, tuple(conf.shape)))
-    if labels.numel() < 1 or labels.numel() >= 2 ** 31:
-        raise ValueError("%s: 1 <= pixels < 2**31, got %s" % (op, tuple(labels.shape)))
-
-
 @custom_op("ifseg::seg_conf_hist", mutates_args=(), device_types="cuda")
 def seg_conf_hist(labels: torch.Tensor, conf: torch.Tensor, n: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """predicted labels (uint8 / int16) with their confidences (fp32, the same shape) (csrc/pseudo.hip) -> (hist int64 [n, 256] =
     pixels per (label, clamp(floor(conf * 256), 0, 255)), tally int64 [2] = labels inside / outside [0, n)), fresh tensors;
     `ifseg_amd.predict.confidence_histogram_reference` is the specification.  Counts: not differentiable."""
-    _labels_conf_check("ifseg::seg_conf_hist", labels, conf)
+    _maps_check("ifseg::seg_conf_hist", labels, conf)
     if n < 1 or n > hip.SEG_PREDICT_MAX_CLASSES:
         raise ValueError("ifseg::seg_conf_hist: n = %d classes, the kernel takes 1 .. %d" % (n, hip.SEG_PREDICT_MAX_CLASSES))
     prev = _stream_scope(labels)
@@ -1212,7 +1211,7 @@ def seg_conf_hist(labels: torch.Tensor, conf: torch.Tensor, n: int) -> Tuple[tor
 
 @seg_conf_hist.register_fake
 def _(labels, conf, n):
-    _labels_conf_check("ifseg::seg_conf_hist", labels, conf)
+    _maps_check("ifseg::seg_conf_hist", labels, conf)
     if n < 1 or n > hip.SEG_PREDICT_MAX_CLASSES:
         raise ValueError("ifseg::seg_conf_hist: n = %d classes, the kernel takes 1 .. %d" % (n, hip.SEG_PREDICT_MAX_CLASSES))
     return labels.new_empty((n, hip.SEG_CONF_BINS), dtype=torch.int64), labels.new_empty((2,), dtype=torch.int64)
@@ -1220,10 +1219,7 @@ def _(labels, conf, n):
 
 def _seg_calibration_check(labels, conf, gt, n):
     op = "ifseg::seg_calibration"
-    _labels_conf_check(op, labels, conf)
-    _gt_check(op, gt)
-    if gt.shape != labels.shape:
-        raise ValueError("%s: labels %s and ground truth %s must have one shape" % (op, tuple(labels.shape), tuple(gt.shape)))
+    _maps_check(op, labels, conf, gt)
     if n < 1 or n > hip.SEG_PREDICT_MAX_CLASSES:
         raise ValueError("%s: n = %d classes, the kernel takes 1 .. %d" % (op, n, hip.SEG_PREDICT_MAX_CLASSES))
 
@@ -1291,7 +1287,7 @@ def _(grids, hp, wp, gt, raw_labels):
 
 def _seg_pseudo_check(labels, conf, thresholds, n, boundary, raw_labels):
     op = "ifseg::seg_pseudo"
-    _labels_conf_check(op, labels, conf)
+    _maps_check(op, labels, conf)
     if labels.dim() not in (2, 3):
         raise ValueError("%s: labels must be [H, W] or [B, H, W], got %s" % (op, tuple(labels.shape)))
     if n < 1 or n > hip.seg_pseudo_max_classes(raw_labels):

@@ -545,6 +545,30 @@ def _check_temperatures(what, temperatures):
     return tuple(float(t) for t in ts)
 
 
+def _check_label_maps(what, imgs, label_maps):
+    """the ground truth of `evaluate_raw` / `calibrate_raw`, checked against the images [H_i, W_i, 3] -> the maps as a list"""
+    gts = [label_maps] if torch.is_tensor(label_maps) else list(label_maps)
+    if len(gts) != len(imgs):
+        raise ValueError("%s: %d label maps for %d images" % (what, len(gts), len(imgs)))
+    for i, (im, g) in enumerate(zip(imgs, gts)):
+        if not torch.is_tensor(g) or g.dtype not in (torch.uint8, torch.int16) or tuple(g.shape) != tuple(im.shape[:2]):
+            raise ValueError("%s: label map %d must be a uint8 or int16 tensor of its image's shape %s, got %s"
+                             % (what, i, tuple(im.shape[:2]), (g.dtype, tuple(g.shape)) if torch.is_tensor(g) else type(g)))
+    return gts
+
+
+def _check_batch_gt(what, images, label_maps):
+    """the ground truth of `evaluate` / `calibrate`, checked against the batch -> it as [B, h, w]"""
+    gt = label_maps
+    if not torch.is_tensor(gt) or gt.dtype not in (torch.uint8, torch.int16) or gt.dim() not in (2, 3) or gt.numel() == 0:
+        raise ValueError("%s: label_maps must be a uint8 or int16 tensor [B, h, w], got %s"
+                         % (what, (gt.dtype, tuple(gt.shape)) if torch.is_tensor(gt) else type(gt)))
+    gt = gt[None] if gt.dim() == 2 else gt
+    if torch.is_tensor(images) and images.dim() >= 3 and gt.shape[0] != (1 if images.dim() == 3 else images.shape[0]):
+        raise ValueError("%s: %d label maps for images %s" % (what, gt.shape[0], tuple(images.shape)))
+    return gt
+
+
 def temperature_sweep_from_probs(probs_k, gt, n, raw_labels=True):
     """The scoring half of `temperature_sweep_reference`, starting from values at image resolution: probs_k a sequence of K
     floating tensors [B, n, h, w] (every class's value per pixel under temperature k: `upsample_argmax_reference`'s or
@@ -1363,9 +1387,12 @@ class Segmenter:
         return imgs, shapes, [self._slide_merge([(torch.stack(got[i][v])[None], *grid[i, v], *per_image[i][v][0], views[v][1])
                                                  for v in range(len(views))], sl) for i in range(len(imgs))]
 
-    def _raw_views(self, views, imgs, scales, flip, max_batch, mean, std, reverse_channels):
+    def _raw_views(self, views, imgs, scales, flip, max_batch, mean, std, reverse_channels, scores=None, merge=None):
         """the front without `slide`: every image loaded once per ratio, one forward per network size -> (the images on the
-        device, their (H, W), per image the `_views_merge` of its views (scores [1, hp*wp, n], hp, wp, flip) in view order)"""
+        device, their (H, W), per image the `_views_merge` of its views (scores [1, hp*wp, n], hp, wp, flip) in view order).
+        scores: what a batch goes through in place of `patch_scores`, -> (a tensor whose first dimension is the batch's, hp,
+        wp); merge: what an image's views go through in place of `_views_merge`"""
+        scores, merge = scores or self.patch_scores, merge or self._views_merge
         mean, std = HALF if mean is None else mean, HALF if std is None else std
         dev = next(self.model.parameters()).device
         imgs = [im.to(dev, non_blocking=True) for im in imgs]
@@ -1378,10 +1405,10 @@ class Segmenter:
                 for k, i in enumerate(idx):
                     x[i, size] = t[k]
             for size, iv in forwards:
-                scores, hp, wp = self.patch_scores(torch.stack([x[i, size].flip(-1) if views[v][1] else x[i, size] for i, v in iv]))
+                got, hp, wp = scores(torch.stack([x[i, size].flip(-1) if views[v][1] else x[i, size] for i, v in iv]))
                 for k, (i, v) in enumerate(iv):
-                    per_image[i][v] = (scores[k:k + 1], hp, wp, views[v][1])
-        return imgs, shapes, [self._views_merge(vs) for vs in per_image]
+                    per_image[i][v] = (got[k:k + 1], hp, wp, views[v][1])
+        return imgs, shapes, [merge(vs) for vs in per_image]
 
     # -- the label map as a picture --------------------------------------------------------
     def render_raw(self, images, palette=None, opacity=0.5, boundary=0, boundary_color=(255, 255, 255), fade_by_conf=False,
@@ -1435,6 +1462,13 @@ class Segmenter:
             return None         # `_slide_merge` asks the launch for the softmax per view behind the merge
         return "upsample=%r (conf is the winning class's resized raw logit)" % (self.upsample,)
 
+    def _need_probability(self, what, sl, need="the confidence must be a probability",
+                          remedy="use upsample='probs', the smoothing, the CRF, or slide_views with slide"):
+        """a ValueError naming the setting where `_conf_setting(sl)` names one"""
+        bad = self._conf_setting(sl)
+        if bad is not None:
+            raise ValueError("%s: %s, this Segmenter has %s; %s" % (what, need, bad, remedy))
+
     def pseudo_label_raw(self, images, keep=1.0, floor=0.0, boundary=0, raw_labels=True, hist=None, thresholds=None,
                          scales=(1.0,), flip=False, slide=None, max_batch=8, mean=None, std=None, reverse_channels=False,
                          return_weight=False):
@@ -1468,10 +1502,7 @@ class Segmenter:
             raise ValueError("%s: the uint8 pseudo-label map holds at most %d classes with raw_labels=%s, the model has n = %d"
                              % (what, hip.seg_pseudo_max_classes(raw_labels), bool(raw_labels), self.n))
         sl = self._check_slide("pseudo_label_raw", slide, scales, flip)
-        bad = self._conf_setting(sl)
-        if bad is not None:
-            raise ValueError("%s: the confidence must be a probability, this Segmenter has %s; use upsample='probs', the "
-                             "smoothing, the CRF, or slide_views with slide" % (what, bad))
+        self._need_probability(what, sl)
         dev = next(self.model.parameters()).device
         if thresholds is not None:
             if not torch.is_tensor(thresholds) or thresholds.dtype != torch.int32 or tuple(thresholds.shape) != (self.n,):
@@ -1537,10 +1568,7 @@ class Segmenter:
                                  "device, calibration=True))" % what)
             score = into
         if score.calibration is not None:
-            bad = self._conf_setting(sl)
-            if bad is not None:
-                raise ValueError("Segmenter.%s: the confidence must be a probability, this Segmenter has %s; use upsample='probs', the "
-                                 "smoothing, the CRF, or slide_views with slide" % (what, bad))
+            self._need_probability("Segmenter.%s" % what, sl)
         if score.boundary is not None:
             for i, (h, w) in enumerate(shapes):
                 d = boundary_distance(h, w, score.boundary_ratio)
@@ -1623,14 +1651,7 @@ class Segmenter:
         sl = self._check_slide("evaluate_raw", slide, scales, flip)
         checked = self._check_raw("evaluate_raw", images, scales, flip, sl)
         plan = self._plan_slide(checked, sl, max_batch)
-        gts = [label_maps] if torch.is_tensor(label_maps) else list(label_maps)
-        imgs = [] if checked is None else checked[1]
-        if len(gts) != len(imgs):
-            raise ValueError("Segmenter.evaluate_raw: %d label maps for %d images" % (len(gts), len(imgs)))
-        for i, (im, g) in enumerate(zip(imgs, gts)):
-            if not torch.is_tensor(g) or g.dtype not in (torch.uint8, torch.int16) or tuple(g.shape) != tuple(im.shape[:2]):
-                raise ValueError("Segmenter.evaluate_raw: label map %d must be a uint8 or int16 tensor of its image's shape %s, got %s"
-                                 % (i, tuple(im.shape[:2]), (g.dtype, tuple(g.shape)) if torch.is_tensor(g) else type(g)))
+        gts = _check_label_maps("Segmenter.evaluate_raw", [] if checked is None else checked[1], label_maps)
         dev = next(self.model.parameters()).device
         score = self._score_into("evaluate_raw", into, dev, confusion, boundary_iou, [tuple(g.shape) for g in gts], calibration, sl)
         if checked is None:
@@ -1651,13 +1672,7 @@ class Segmenter:
         ground truth's own size, as `out_hw` would.  -> a `SegmentationScore`, or (score, labels [B, h, w]) with `return_labels`;
         raw_labels, into, confusion, boundary_iou, calibration: as in `evaluate_raw`; the band areas of the whole batch are one
         launch of `hip.seg_boundary_areas`, d from the label maps' size, and its calibration counts one of `hip.seg_calibration`."""
-        gt = label_maps
-        if not torch.is_tensor(gt) or gt.dtype not in (torch.uint8, torch.int16) or gt.dim() not in (2, 3) or gt.numel() == 0:
-            raise ValueError("Segmenter.evaluate: label_maps must be a uint8 or int16 tensor [B, h, w], got %s"
-                             % ((gt.dtype, tuple(gt.shape)) if torch.is_tensor(gt) else type(gt),))
-        gt = gt[None] if gt.dim() == 2 else gt
-        if torch.is_tensor(images) and images.dim() >= 3 and gt.shape[0] != (1 if images.dim() == 3 else images.shape[0]):
-            raise ValueError("Segmenter.evaluate: %d label maps for images %s" % (gt.shape[0], tuple(images.shape)))
+        gt = _check_batch_gt("Segmenter.evaluate", images, label_maps)
         patch_images, rgb = self.prepare_images(images)
         B, _, H, W = patch_images.shape
         crf = self.crf_iters > 0
@@ -1685,10 +1700,7 @@ class Segmenter:
         if self.crf_iters > 0:
             raise ValueError("Segmenter.%s: a temperature sweep scores the network's probabilities, this Segmenter has "
                              "crf_iters = %d (the CRF's marginals are not a function of one temperature)" % (what, self.crf_iters))
-        bad = self._conf_setting(None)
-        if bad is not None:
-            raise ValueError("Segmenter.%s: the values must be probabilities, this Segmenter has %s; use upsample='probs' or the "
-                             "smoothing" % (what, bad))
+        self._need_probability("Segmenter.%s" % what, None, "the values must be probabilities", "use upsample='probs' or the smoothing")
         temps = _check_temperatures("Segmenter.%s" % what, default_temperatures() if temperatures is None else temperatures)
         if into is None:
             return TemperatureSweep(temps, dev, self.n)
@@ -1719,32 +1731,19 @@ class Segmenter:
         dev = next(self.model.parameters()).device
         sweep = self._sweep_into(what, temperatures, into, dev, scales, flip, slide)
         checked = self._check_raw(what, images, scales, flip)
-        gts = [label_maps] if torch.is_tensor(label_maps) else list(label_maps)
-        imgs = [] if checked is None else checked[1]
-        if len(gts) != len(imgs):
-            raise ValueError("Segmenter.calibrate_raw: %d label maps for %d images" % (len(gts), len(imgs)))
-        for i, (im, g) in enumerate(zip(imgs, gts)):
-            if not torch.is_tensor(g) or g.dtype not in (torch.uint8, torch.int16) or tuple(g.shape) != tuple(im.shape[:2]):
-                raise ValueError("Segmenter.calibrate_raw: label map %d must be a uint8 or int16 tensor of its image's shape %s, got %s"
-                                 % (i, tuple(im.shape[:2]), (g.dtype, tuple(g.shape)) if torch.is_tensor(g) else type(g)))
+        gts = _check_label_maps("Segmenter.calibrate_raw", [] if checked is None else checked[1], label_maps)
         if checked is None:
             return sweep
-        mean, std = HALF if mean is None else mean, HALF if std is None else std
-        imgs = [im.to(dev, non_blocking=True) for im in imgs]
         gts = [g.to(dev, non_blocking=True).contiguous() for g in gts]
-        _, loads, forwards = plan_views([(int(im.shape[0]), int(im.shape[1])) for im in imgs], self.model.cfg.patch_image_size,
-                                        scales, False, max_batch)
-        x, per_image = {}, [None] * len(imgs)
+
+        def grids_at(x):                # sample-major, as `_raw_views` cuts a batch into its images
+            grids, hp, wp = self.patch_scores_at(x, sweep.temperatures)
+            return grids.transpose(0, 1), hp, wp
+
+        per_image = self._raw_views(*checked, max_batch, mean, std, reverse_channels, scores=grids_at, merge=lambda vs: vs[0])[2]
         with torch.no_grad():
-            for _, size, idx in loads:
-                t = hip.image_load(torch.stack([imgs[i] for i in idx]), size[0], size[1], mean, std, reverse_channels)
-                for k, i in enumerate(idx):
-                    x[i, size] = t[k]
-            for size, iv in forwards:
-                grids, hp, wp = self.patch_scores_at(torch.stack([x[i, size] for i, _ in iv]), sweep.temperatures)
-                for k, (i, _) in enumerate(iv):
-                    per_image[i] = (grids[:, k:k + 1].contiguous(), hp, wp)
-            for (grids, hp, wp), g in zip(per_image, gts):           # in image order: the sums do not depend on the batches
+            for (grids, hp, wp, _), g in zip(per_image, gts):        # in image order: the sums do not depend on the batches
+                grids = grids.transpose(0, 1).contiguous()
                 hip.seg_temperature_sweep(grids, hp, wp, g[None], raw_labels, hist=sweep.hist, sums=sweep.sums, tally=sweep.tally)
         return sweep
 
@@ -1752,13 +1751,7 @@ class Segmenter:
         """`calibrate_raw` for what `evaluate` takes: images normalised float [B, 3, H, W] or uint8 RGB [B, H, W, 3] / [H, W, 3],
         label_maps uint8 / int16 [B, h, w] (or [h, w] for one image) -> a `TemperatureSweep`: one forward, K
         `hip.rows_to_f32` and one launch of `hip.seg_temperature_sweep` for the whole batch, at the ground truth's own size."""
-        gt = label_maps
-        if not torch.is_tensor(gt) or gt.dtype not in (torch.uint8, torch.int16) or gt.dim() not in (2, 3) or gt.numel() == 0:
-            raise ValueError("Segmenter.calibrate: label_maps must be a uint8 or int16 tensor [B, h, w], got %s"
-                             % ((gt.dtype, tuple(gt.shape)) if torch.is_tensor(gt) else type(gt),))
-        gt = gt[None] if gt.dim() == 2 else gt
-        if torch.is_tensor(images) and images.dim() >= 3 and gt.shape[0] != (1 if images.dim() == 3 else images.shape[0]):
-            raise ValueError("Segmenter.calibrate: %d label maps for images %s" % (gt.shape[0], tuple(images.shape)))
+        gt = _check_batch_gt("Segmenter.calibrate", images, label_maps)
         patch_images, _ = self.prepare_images(images)
         sweep = self._sweep_into("calibrate", temperatures, into, patch_images.device)
         grids, hp, wp = self.patch_scores_at(patch_images, sweep.temperatures)
