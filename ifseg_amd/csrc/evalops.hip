@@ -33,6 +33,14 @@ __global__ __launch_bounds__(256) void l2norm_rows_kernel(const bf16_t* x, bf16_
   }
 }
 
+// the order of top-k: NaN first (as torch.topk ranks it, above +inf), then the larger value, then the lower index.  Every entry
+// of a row comes before the empty slot (-inf, 0x7fffffff), so with k <= N a winner is always an index inside the row.
+__device__ __forceinline__ bool topk_before(float v, int c, float bv, int bi) {
+  const bool vn = v != v, bn = bv != bv;
+  if (vn != bn) return vn;
+  return vn ? c < bi : (v > bv || (v == bv && c < bi));
+}
+
 // idx[r, 0..k) = indices of the k largest entries of sim[r, 0..N) (ties: lower index first), one wave per row
 __global__ __launch_bounds__(256) void topk_rows_kernel(const float* sim, int* idx, int rows, int N, int k) {
   const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -45,12 +53,12 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* sim, int* i
       bool taken = false;
       for (int t = 0; t < j; ++t) taken |= (won[t] == c);
       const float v = sp[c];
-      if (!taken && (v > bv || (v == bv && c < bi))) { bv = v; bi = c; }
+      if (!taken && topk_before(v, c, bv, bi)) { bv = v; bi = c; }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
       const float ov = __shfl_xor(bv, o); const int oi = __shfl_xor(bi, o);
-      if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+      if (topk_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
     }
     won[j] = bi;
     if (lane == 0) idx[(long long)row * k + j] = bi;

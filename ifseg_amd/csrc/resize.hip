@@ -114,7 +114,7 @@ extern "C" int ifseg_resized_rel_bias(float* out, const float* table2d, const fl
   if (ld <= 0) ld = T;
   if (ld < T) return IFSEG_ERR_BAD_ARG;
   const size_t lds = (size_t)n2d0 * sizeof(float);
-  if (lds > 160 * 1024) return IFSEG_ERR_BAD_SHAPE;
+  if (lds > 160 * 1000) return IFSEG_ERR_BAD_SHAPE;   // 160 000 bytes: a 100 x 100 trained grid (158 404) is the largest square one
   if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)resized_bias_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   TapGeo g{h, w, oh, ow};
   const int bx = (T + 255) / 256 < 8 ? (T + 255) / 256 : 8;

@@ -445,7 +445,8 @@ int ifseg_rel_scatter_add(const float* d, const int* idx, float* acc, int n, int
  * delta table table2d [H, (2oh-1)(2ow-1)] (ifseg_rel_gather on the original geometry); tail x tail = rel1d [H, 2Lt-1]
  * (NULL: 0); grid x tail / tail x grid = relx [H, 2] (NULL: 0) -- the decoder's bos column / row, which the reference's
  * resize passes through.  causal != 0 (decoder_module.py:592-600, buffered_future_mask in the internal order with the tail =
- * bos first): -inf where the key lies after the query. */
+ * bos first): -inf where the key lies after the query.  The delta table of one head is staged in LDS: tables above
+ * 160 000 bytes (trained grids beyond 100 x 100) are refused with IFSEG_ERR_BAD_SHAPE. */
 int ifseg_resized_rel_bias(float* out, const float* table2d, const float* rel1d, const float* relx, int H, int h, int w,
                            int oh, int ow, int Lt, int causal, int ld /* row stride of out, >= T (0: T) */, void* stream);
 /* dst bf16 [h*w, C] = bilinear resize (align_corners = False, fp32 arithmetic, one rounding) of the oh x ow grid of rows
@@ -638,7 +639,9 @@ int ifseg_imfree_expand(const int* shapes, const int* coarse, int max_side, cons
  * bilinearly (align_corners=False, any ratio) to [h, w], takes the argmax and accumulates hist[3][n] =
  * {intersect, predicted, label} pixel counts (uint64, caller zeroes them) and per-block {CE sum, pixel count}
  * partials loss_part[nblocks][2], nblocks = ceil(h*w / 256).  target: int64 [h*w] dictionary ids
- * (seg_id_offset + class; anything outside [0, n) after the offset is ignored). */
+ * (seg_id_offset + class; anything outside [0, n) after the offset is ignored).
+ * ifseg_topk_rows_f32 orders like torch.topk: NaN first, then the larger value, the lower index first among equals; the k
+ * indices of a row are distinct and inside [0, N). */
 int ifseg_l2norm_rows_bf16(const void* x, void* out, int rows, int D, void* stream);
 int ifseg_topk_rows_f32(const float* sim, int* idx, int rows, int N, int k /* <= 8 */, void* stream);
 int ifseg_softmax_rows(const void* logits /* bf16 */, long long batch_stride, int rows_per_batch, int ld, float* prob,
