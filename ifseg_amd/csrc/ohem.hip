@@ -18,7 +18,8 @@
 //                         The counters are integers: the result is bit-reproducible.
 // Workspace (uint64 [OHEM_WORK_WORDS], zeroed once when it is allocated): three histograms and 16 state words.  A launch zeroes
 // only what no workgroup of the same launch reads: pass 0 the histograms of digits 1 and 2, pass 1 the below-thresh counter it has
-// just copied, the apply launch the histogram of digit 0 -- so a call leaves the workspace as it found it.
+// just copied, the apply launch the histogram of digit 0; the last workgroup of the apply launch to have read the state and the
+// third histogram zeroes those and the second -- so a call leaves the workspace as it found it, every word zero.
 #include <string.h>
 #include "count.h"
 #include "seg_tile.h"
@@ -79,6 +80,7 @@ constexpr int S_BT = 5;
 constexpr int S_D1 = 6;        // the same for the second digit (pass 2); S_LOW1 counts the candidates below (D0, D1)
 constexpr int S_LOW1 = 7;
 constexpr int S_K2 = 8;
+constexpr int S_DONE = 9;      // the workgroups of the apply launch that have read the state (the last one zeroes it)
 constexpr int OHEM_WORK_WORDS = STATE + 16;  // == hip.OHEM_WORK_WORDS
 
 typedef unsigned long long u64;
@@ -216,6 +218,19 @@ __global__ __launch_bounds__(256) void ohem_apply_kernel(const float* __restrict
       info[2] = (long long)tau;
       info[3] = (long long)kth;
     }
+  }
+  // every read of the state and of the last histogram lies above this line: the last workgroup to get here zeroes them (and the
+  // second histogram), so that the workspace is all zeros again after the call.  An integer count, no waiting.
+  __shared__ int sLast;
+  __syncthreads();
+  if (tid == 0) {
+    __threadfence();
+    sLast = atomicAdd(&state[S_DONE], (u64)1) == (u64)gridDim.x - 1;
+  }
+  __syncthreads();
+  if (sLast) {
+    __threadfence();
+    for (int i = tid; i < 2 * BINS + 16; i += 256) work[BINS + i] = 0;
   }
   for (long long i = (long long)blockIdx.x * 256 + tid; i < total; i += (long long)gridDim.x * 256) {
     const uint32_t key = __float_as_uint(hardness[i]);

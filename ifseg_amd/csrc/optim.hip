@@ -142,11 +142,20 @@ __global__ __launch_bounds__(256) void ema_swap_kernel(float* p32, bf16_t* p16, 
   }
 }
 
+// the refusals the two Adam entries share: the kernel reads and writes p32 / m / v as float4 and g / p16 as uint2
+inline int check_adam_args(const float* p32, const void* g, const float* m, const float* v, const void* p16) {
+  if (!p32 || !g || !m || !v || !p16) return IFSEG_ERR_BAD_ARG;
+  if (((size_t)p32 & 15) || ((size_t)m & 15) || ((size_t)v & 15) || ((size_t)g & 7) || ((size_t)p16 & 7)) return IFSEG_ERR_BAD_ARG;
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int ifseg_grad_sumsq_bf16(const void* g, long long n, float* workspace /* >= 1024 floats */,
                                      float* out_sumsq, void* stream) {
   (void)hipGetLastError();
+  if (!g || !workspace || !out_sumsq || ((size_t)g & 15) || ((size_t)workspace & 3) || ((size_t)out_sumsq & 3) || n < 0)
+    return IFSEG_ERR_BAD_ARG;     // (n == 0: no block reads g, every part is 0 and so is the sum)
   const int nblk = 1024;
   hipLaunchKernelGGL(sumsq_bf16_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)g, n, workspace);
   hipLaunchKernelGGL(finish_norm_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, workspace, nblk, out_sumsq);
@@ -159,6 +168,7 @@ extern "C" int ifseg_adam_step(float* p32, const void* g, float* m, float* v, vo
                                float max_norm, const float* sumsq, int* overflow, const float* hyper, void* stream) {
   (void)hipGetLastError();
   if (n <= 0) return 0;
+  if (const int rc = check_adam_args(p32, g, m, v, p16)) return rc;
   const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
   // grid: two blocks per CU.  Sweep on MI355X over 109 M parameters (tools/adam_bench.py, profiles/round6_adam_grid.txt): 256 blocks
   // 789 us, 512: 573, 768: 578, 1024: 588, 1536: 618, 2048 (until round 6): 620, 4096: 620 -- 5.33 TB/s against a torch copy's 5.0
@@ -175,7 +185,8 @@ extern "C" int ifseg_adam_ema_step(float* p32, const void* g, float* m, float* v
                                    float ema_decay, float ema_rest, void* stream) {
   (void)hipGetLastError();
   if (n <= 0) return 0;
-  if (!e32 || !e16) return IFSEG_ERR_BAD_ARG;
+  if (const int rc = check_adam_args(p32, g, m, v, p16)) return rc;
+  if (!e32 || !e16 || ((size_t)e32 & 15) || ((size_t)e16 & 7)) return IFSEG_ERR_BAD_ARG;
   const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
   // the grid of ifseg_adam_step: the same sweep with 40 instead of 30 bytes per element
   hipLaunchKernelGGL(adam_kernel<true>, dim3(512), dim3(256), 0, (hipStream_t)stream, p32, (const bf16_t*)g, m, v,

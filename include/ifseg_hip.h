@@ -544,7 +544,7 @@ int ifseg_seg_hardness(const void* logits, int ldl, long long logits_bs, const l
  * clear).  k = min(min_kept * B, #candidates - 1), kth = the k-th smallest candidate (from 0) by an exact radix select (three
  * digits of 10 bits, 64-bit integer counters: bit-reproducible), tau = max(bits(thresh), kth); out = weight[i] (uint8 [B][n],
  * NULL: 255) where the entry is a candidate below tau (strictly), else 0.  info = #candidates, #kept, tau, kth (0 without a
- * candidate).  work: uint64 [3 * 1024 + 16], zeroed once by the caller; every call leaves it zeroed where the next one needs it, so
+ * candidate).  work: uint64 [3 * 1024 + 16], zeroed once by the caller; every call leaves every word of it zero again, so
  * the same sequence replays inside a captured graph.  out must not overlap hardness or weight (the caller's duty).
  * NULL / misaligned pointers (hardness 4 bytes, info and work 8), thresh outside [0, 1] or NaN, min_kept outside [0, 2^40):
  * IFSEG_ERR_BAD_ARG; B outside [1, 2^20), n < 1, B*n >= 2^31: IFSEG_ERR_BAD_SHAPE.  Nothing is launched on a refusal. */
@@ -1076,7 +1076,9 @@ int ifseg_strong_draw(int B, unsigned long long seed, long long first_ordinal, i
 int ifseg_strong_apply(const int* records, const void* images, int B, int P, int elem_bytes, const float* lut,
                        int reverse_channels, void* out, void* stream);
 
-/* sum of squares of a bf16 gradient arena -> out_sumsq[0] (device). */
+/* sum of squares of a bf16 gradient arena -> out_sumsq[0] (device).  workspace: 1024 floats.  g is read 16 bytes at a time:
+ * NULL g / workspace / out_sumsq, g not 16-byte aligned, workspace or out_sumsq not 4-byte aligned, n < 0: IFSEG_ERR_BAD_ARG,
+ * nothing launched.  n == 0 writes 0. */
 int ifseg_grad_sumsq_bf16(const void* g, long long n, float* workspace, float* out_sumsq, void* stream);
 /* Fused grad scaling + clip-by-global-norm + Adam with decoupled weight decay over a
  * flat arena; writes the bf16 model copy.  Mirrors trainer.py:874-907 +
@@ -1086,7 +1088,10 @@ int ifseg_adam_step(float* p32, const void* g, float* m, float* v, void* p16, lo
                     float beta2, float eps, float weight_decay, int step, float grad_scale, float max_norm,
                     const float* sumsq, int* overflow, const float* hyper, void* stream);
 /* `hyper` (device, may be NULL): {lr, 1 - beta1^step, 1 - beta2^step, grad_scale} override the by-value arguments --
- * a captured training step (HIP graph) is replayed with the schedule's current values. */
+ * a captured training step (HIP graph) is replayed with the schedule's current values.
+ * n <= 0 returns 0 and launches nothing.  With n > 0 (here and in ifseg_adam_ema_step): p32, m, v are read and written 16 bytes
+ * at a time, g and p16 8 bytes at a time -- a NULL p32 / g / m / v / p16, p32 / m / v not 16-byte aligned, g / p16 not 8-byte
+ * aligned: IFSEG_ERR_BAD_ARG, nothing launched. */
 /* ifseg_adam_step with a teacher averaged in the same launch (fairseq/models/ema/ema.py:134-167 with ema_fp32 on a 16-bit
  * model; ifseg_amd/ema.py is the specification).  Per element, with q the bf16 weight this launch stores to p16:
  *     e32 = fma(ema_rest, float(q), round32(e32 * ema_decay))        e16 = bf16_rne(e32)
@@ -1095,7 +1100,7 @@ int ifseg_adam_step(float* p32, const void* g, float* m, float* v, void* p16, lo
  * ifseg_adam_step.  `hyper` (device, may be NULL) has SIX floats here: the four above, then {ema_decay, ema_rest}.
  * (ema_decay, ema_rest) == (1, 0) neither reads nor writes the teacher (the off-updates of ema_update_freq in a captured
  * step); a non-finite *sumsq skips the teacher with the update.  e32 / e16: n elements, aligned like p32 / p16 (16 / 8
- * bytes); NULL: IFSEG_ERR_BAD_ARG.  40 bytes of traffic per element against ifseg_adam_step's 30. */
+ * bytes); NULL or misaligned: IFSEG_ERR_BAD_ARG.  40 bytes of traffic per element against ifseg_adam_step's 30. */
 int ifseg_adam_ema_step(float* p32, const void* g, float* m, float* v, void* p16, float* e32, void* e16, long long n,
                         float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
                         float max_norm, const float* sumsq, int* overflow, const float* hyper, float ema_decay,
