@@ -1908,6 +1908,95 @@ def seg_pseudo(labels, conf, thresholds, n, boundary=0, raw_labels=True, kept=No
     return out, kept
 
 
+# --------------------------------------------------------------------------- pixel-adaptive mask refinement (csrc/pamr.hip)
+SEG_PAMR_MAX_DILATIONS = 8          # == PM_MAX_D: the dilations of a call at most (8 neighbours each)
+SEG_PAMR_MAX_DILATION = 32          # == PM_MAX_DILATION: the largest dilation (a tile's halo: 40 KiB of LDS)
+SEG_PAMR_DILATIONS = (1, 2, 4, 8, 12, 24)       # the published defaults, with ten iterations
+
+
+def seg_pamr_limits():
+    """-> (dilations at most, the largest dilation, the largest n) as the loaded library states them (`ifseg_pamr_limit`):
+    SEG_PAMR_MAX_DILATIONS, SEG_PAMR_MAX_DILATION and SEG_PREDICT_MAX_CLASSES, which the tests hold against it"""
+    return _limits("ifseg_pamr_limit", 3)
+
+
+def _pamr_dilations(dilations):
+    """the dilations of a call, checked -> (a ctypes int array, D)"""
+    d = tuple(dilations)
+    assert 1 <= len(d) <= SEG_PAMR_MAX_DILATIONS and all(isinstance(v, int) and 1 <= v <= SEG_PAMR_MAX_DILATION for v in d), dilations
+    return (c_int * len(d))(*d), len(d)
+
+
+def pamr_affinity(image, dilations=SEG_PAMR_DILATIONS):
+    """image uint8 [H, W, 3] (HWC, contiguous, at any byte offset of its storage), dilations: 1 .. 8 ints in 1 .. 32 -> w fp32
+    [8 D, H, W] in one launch (csrc/pamr.hip): per pixel the softmax over its 8 D neighbours (every dilation's 3 x 3 ring,
+    coordinates clamped to the image) of minus the mean over the channels of |difference| / (1e-8 + 0.1 local deviation).
+    `predict.pamr_affinity_reference` is the specification and states the rule."""
+    assert image.dtype == torch.uint8 and image.dim() == 3 and image.shape[2] == 3 and image.is_contiguous(), \
+        (image.dtype, tuple(image.shape), image.stride())
+    arr, D = _pamr_dilations(dilations)
+    H, W = int(image.shape[0]), int(image.shape[1])
+    assert H >= 1 and W >= 1 and 8 * D * H * W < 2 ** 31, (D, H, W)
+    w = torch.empty(8 * D, H, W, dtype=torch.float32, device=image.device)
+    _check(lib().ifseg_pamr_affinity(_ptr(image), c_int(H), c_int(W), arr, c_int(D), _ptr(w), _stream()), "pamr_affinity")
+    return w
+
+
+def pamr_iterate(w, src, dst, dilations=SEG_PAMR_DILATIONS, labels=None, conf=None):
+    """One iteration in one launch (csrc/pamr.hip): w fp32 [8 D, H, W] (`pamr_affinity` of the same dilations), src fp32
+    [n, H, W] -> dst fp32 [n, H, W], dst[c, p] = sum_k w[k, p] src[c, neighbour k of p]; dst must not overlap src or w.
+    labels (uint8 for n <= 256, or int16) and conf (fp32) [H, W] given: also written, per pixel the first maximum of dst over
+    the classes and its value -- the caller asks on its last iteration, there is no argmax pass.  Every tensor contiguous.
+    `predict.pamr_iterate_reference` is the specification.  -> dst"""
+    arr, D = _pamr_dilations(dilations)
+    assert w.dtype == torch.float32 and w.dim() == 3 and w.shape[0] == 8 * D and w.is_contiguous(), \
+        (w.dtype, tuple(w.shape), w.stride(), D)
+    H, W = int(w.shape[1]), int(w.shape[2])
+    for name, t in (("src", src), ("dst", dst)):
+        assert t.dtype == torch.float32 and t.dim() == 3 and tuple(t.shape[1:]) == (H, W) and t.is_contiguous() \
+            and t.device == w.device, (name, t.dtype, tuple(t.shape), t.stride(), t.device, (H, W))
+    n = int(src.shape[0])
+    assert dst.shape == src.shape and 1 <= n <= SEG_PREDICT_MAX_CLASSES and H >= 1 and W >= 1 and n * H * W < 2 ** 31 \
+        and 8 * D * H * W < 2 ** 31, (tuple(src.shape), tuple(dst.shape))
+    assert not _overlap(dst, src) and not _overlap(dst, w), "pamr_iterate: dst overlaps src or w"
+    if labels is not None:
+        assert labels.dtype in (torch.uint8, torch.int16) and (n <= 256 or labels.dtype == torch.int16) \
+            and tuple(labels.shape) == (H, W) and labels.is_contiguous() and labels.device == w.device, \
+            (labels.dtype, tuple(labels.shape), labels.stride(), labels.device, n)
+    if conf is not None:
+        assert conf.dtype == torch.float32 and tuple(conf.shape) == (H, W) and conf.is_contiguous() and conf.device == w.device, \
+            (conf.dtype, tuple(conf.shape), conf.stride(), conf.device)
+    _check(lib().ifseg_pamr_iterate(_ptr(w), _ptr(src), _ptr(dst), c_int(n), c_int(H), c_int(W), arr, c_int(D), _ptr(labels),
+                                    c_int(labels.element_size() if labels is not None else 0), _ptr(conf), _stream()),
+           "pamr_iterate")
+    return dst
+
+
+def seg_pamr(probs, image, iters=10, dilations=SEG_PAMR_DILATIONS, conf=False, probs_out=False, label_dtype=None):
+    """Pixel-adaptive mask refinement (PAMR, Araslanov & Roth, CVPR 2020) of ONE image: probs fp32 [n, H, W] (what
+    `seg_predict(probs=True)` hands over, one image of it), image uint8 [H, W, 3], the photograph at the same resolution ->
+    (labels [H, W], uint8 for n <= 256 else int16 (or `label_dtype`); conf fp32 [H, W] or None; the refined values fp32
+    [n, H, W] or None).  One `pamr_affinity` launch, `iters` >= 1 `pamr_iterate` launches over two ping-pong buffers, the last
+    of which also writes the labels and conf; `probs` is not modified and nothing synchronises with the host.
+    `predict.pamr_reference` is the specification.  Every value is a convex combination of `probs`' values: probabilities
+    stay probabilities."""
+    assert probs.dtype == torch.float32 and probs.dim() == 3 and probs.is_contiguous(), (probs.dtype, tuple(probs.shape), probs.stride())
+    n, H, W = (int(v) for v in probs.shape)
+    assert image.dim() == 3 and tuple(image.shape) == (H, W, 3) and image.device == probs.device, \
+        (tuple(image.shape), image.device, (H, W), probs.device)
+    assert isinstance(iters, int) and iters >= 1, iters
+    w = pamr_affinity(image, dilations)
+    labels, cf, _ = _predict_outputs(1, n, H, W, probs.device, conf, False, label_dtype)
+    bufs = [torch.empty_like(probs), torch.empty_like(probs) if iters > 1 else None]
+    src = probs
+    for it in range(iters):
+        last = it == iters - 1
+        dst = bufs[it & 1]
+        pamr_iterate(w, src, dst, dilations, labels[0] if last else None, cf[0] if last and conf else None)
+        src = dst
+    return labels[0], cf[0] if conf else None, src if probs_out else None
+
+
 _image_luts = {}        # (mean, std, device) -> fp32 [3, 256] on the device; at most 16 entries
 
 

@@ -32,7 +32,8 @@ map in one launch), `seg_render` (csrc/render.hip: the label map coloured over i
 (csrc/pseudo.hip: the per-class confidence histogram of a label map, and the label map filtered by per-class thresholds and an
 ignore band along class edges into pseudo-labels for self-training), `seg_calibration` (csrc/calib.hip: how often a confidence
 is right, pixels per predicted class, confidence bin and hit against ground truth), `seg_temperature_sweep` (csrc/tsweep.hip: K
-grids of one forward at K temperatures against one ground truth, per temperature the reliability counts, NLL and Brier) and the two of multi-scale + flip over sliding windows (`seg_predict_slide_views`, `seg_score_slide_views`:
+grids of one forward at K temperatures against one ground truth, per temperature the reliability counts, NLL and Brier),
+`seg_pamr` (csrc/pamr.hip: pixel-adaptive mask refinement of one image's class values, guided by its photograph) and the two of multi-scale + flip over sliding windows (`seg_predict_slide_views`, `seg_score_slide_views`:
 K views, each a set of windows, merged in one launch, optionally softmaxed per view as mmseg does) are inference only and
 have no backward; `train_load`
 (csrc/trainload.hip: raw images and label maps of any sizes to a training batch under given records, the reference's training
@@ -1318,6 +1319,54 @@ def seg_pseudo(labels: torch.Tensor, conf: torch.Tensor, thresholds: torch.Tenso
 def _(labels, conf, thresholds, n, boundary, raw_labels):
     _seg_pseudo_check(labels, conf, thresholds, n, boundary, raw_labels)
     return labels.new_empty(tuple(labels.shape), dtype=torch.uint8), labels.new_empty((2, n), dtype=torch.int64)
+
+
+# ----------------------------------------------------------------------------------------------- seg_pamr
+def _seg_pamr_check(probs, image, iters, dilations):
+    op = "ifseg::seg_pamr"
+    if probs.dtype != torch.float32 or probs.dim() != 3:
+        raise ValueError("%s: probs must be float32 [n, H, W] (one image of seg_predict's probs), got %s %s"
+                         % (op, probs.dtype, tuple(probs.shape)))
+    n, H, W = probs.shape
+    if n < 1 or n > hip.SEG_PREDICT_MAX_CLASSES:
+        raise ValueError("%s: n = %d classes, the kernel takes 1 .. %d" % (op, n, hip.SEG_PREDICT_MAX_CLASSES))
+    if image.dtype != torch.uint8 or tuple(image.shape) != (H, W, 3):
+        raise ValueError("%s: the image must be uint8 %s (HWC, at the values' resolution), got %s %s"
+                         % (op, (H, W, 3), image.dtype, tuple(image.shape)))
+    if iters < 1:
+        raise ValueError("%s: iters must be >= 1, got %d" % (op, iters))
+    D = len(dilations)
+    if not 1 <= D <= hip.SEG_PAMR_MAX_DILATIONS or any(not 1 <= d <= hip.SEG_PAMR_MAX_DILATION for d in dilations):
+        raise ValueError("%s: dilations must be 1 .. %d ints in 1 .. %d, got %s"
+                         % (op, hip.SEG_PAMR_MAX_DILATIONS, hip.SEG_PAMR_MAX_DILATION, list(dilations)))
+    if H < 1 or W < 1 or n * H * W >= 2 ** 31 or 8 * D * H * W >= 2 ** 31:
+        raise ValueError("%s: [%d, %d, %d] values under %d dilations: n H W and 8 D H W must stay below 2**31" % (op, n, H, W, D))
+    return n, H, W, (torch.uint8 if n <= 256 else torch.int16)
+
+
+@custom_op("ifseg::seg_pamr", mutates_args=(), device_types="cuda")
+def seg_pamr(probs: torch.Tensor, image: torch.Tensor, iters: int, dilations: Sequence[int], want_conf: bool, want_probs: bool
+             ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """pixel-adaptive mask refinement of one image (csrc/pamr.hip): probs fp32 [n, H, W], image uint8 [H, W, 3] -> (labels [H, W]
+    uint8 (n <= 256) or int16, conf fp32 [H, W], the refined values fp32 [n, H, W]), fresh tensors; an output that was not asked
+    for is an empty tensor.  `ifseg_amd.predict.pamr_reference` is the specification.  No autograd."""
+    _seg_pamr_check(probs, image, iters, dilations)
+    prev = _stream_scope(probs)
+    try:
+        labels, conf, out = hip.seg_pamr(probs.contiguous(), image.contiguous(), iters, tuple(int(d) for d in dilations),
+                                         conf=want_conf, probs_out=want_probs)
+        e = lambda t: torch.empty(0, dtype=torch.float32, device=probs.device) if t is None else t
+        return labels, e(conf), e(out)
+    finally:
+        hip.set_stream(prev)
+
+
+@seg_pamr.register_fake
+def _(probs, image, iters, dilations, want_conf, want_probs):
+    n, H, W, ldt = _seg_pamr_check(probs, image, iters, dilations)
+    f32 = torch.float32
+    return (probs.new_empty((H, W), dtype=ldt), probs.new_empty((H, W) if want_conf else (0,), dtype=f32),
+            probs.new_empty((n, H, W) if want_probs else (0,), dtype=f32))
 
 
 # ----------------------------------------------------------------------------------------------- image_load

@@ -123,6 +123,18 @@ specifications, in integers.  `task.self_train_sample(model, photos, first_ordin
     t = hist.thresholds(keep=0.5, floor=0.3)
     out = seg.pseudo_label_raw(photos, thresholds=t, boundary=1)                   # [PseudoLabelResult(labels, predicted, conf, kept)]
 
+A cheap refinement that looks at the photograph: `Segmenter(..., pamr_iters=10)` runs pixel-adaptive mask refinement (PAMR,
+Araslanov & Roth, CVPR 2020; what MaskCLIP applies to its pseudo-labels) on the resized values of every image, in the slot of
+the CRF: `hip.seg_pamr` (csrc/pamr.hip), one affinity launch on the original uint8 photo and one launch per iteration.  Each
+iteration replaces a pixel's class values by a convex combination of its neighbours' (8 per dilation, 1, 2, 4, 8, 12, 24 by
+default), weighted by how alike the colours are against the local contrast.  Linear in the pixels, where the CRF's exact dense
+kernels are quadratic, and probabilities stay probabilities: conf, the calibration counters, the pseudo-label thresholds and
+`fade_by_conf` keep their meaning behind it.  `pamr_reference` is the specification; the reference has no counterpart, so
+there is no golden.
+
+    seg = Segmenter(model, task, pamr_iters=10)
+    out = seg.pseudo_label_raw(unlabelled_photos, keep=0.5)         # the labels hug the photo's edges
+
 How the four settings share their code: a front (`Segmenter._raw_views` without `slide`, `_raw_window_views` with it, for one
 view or many) runs the loads and the forwards and hands back one `_Merge` per image -- the setting's last launch, as its
 `hip.seg_predict*` and its `hip.seg_score*`, bound to the image's scores and geometry.  `Segmenter._label` finishes an image
@@ -236,6 +248,66 @@ def slide_views_reference(views, crop, stride, h, w, softmax, dtype=torch.float6
     probs = total * torch.tensor(1.0 / len(views), dtype=dtype, device=total.device)
     labels = probs.argmax(dim=1)
     return labels, probs.gather(1, labels[:, None]).squeeze(1), probs
+
+
+PAMR_TAPS = ((-1, -1), (-1, 0), (-1, 1), (0, -1), (0, 1), (1, -1), (1, 0), (1, 1))
+PAMR_DILATIONS = hip.SEG_PAMR_DILATIONS
+
+
+def _pamr_neighbours(H, W, dilations, device):
+    """neighbour k = 8 i + t of every pixel, t over PAMR_TAPS at dilation i: (rows [H, 1], columns [1, W]), clamped to the image"""
+    ys, xs = torch.arange(H, device=device), torch.arange(W, device=device)
+    return [((ys + d * oy).clamp(0, H - 1)[:, None], (xs + d * ox).clamp(0, W - 1)[None, :]) for d in dilations for oy, ox in PAMR_TAPS]
+
+
+def pamr_affinity_reference(image, dilations=PAMR_DILATIONS, dtype=torch.float64):
+    """CPU specification of hip.pamr_affinity: image uint8 [H, W, 3] -> w [8 D, H, W] in `dtype`.  Per channel, in integers:
+    S1, S2 = the sums of x and x^2 (grey levels) over the 9 taps of every dilation -- the 8 neighbours and the centre, which is
+    thereby counted once per dilation -- M = 9 D, and the numerator M S2 - S1^2 of the unbiased variance, exact at every
+    precision.  Then, in `dtype`: std = sqrt(numerator / (M (M - 1))), a_k = -((t_0 + t_1) + t_2) / 3 with
+    t_ch = |x_ch(p) - x_ch(q_k)| / (1e-8 + 0.1 std_ch), and w = softmax_k a_k.  This is PAMR's affinity (Araslanov & Roth, CVPR
+    2020: LocalStDev, LocalAffinityAbs, mean over the channels, softmax) on the grey levels in place of the normalised image:
+    the ratio is scale-free per channel, so only the 1e-8 differs.  Runs on any device."""
+    H, W = int(image.shape[0]), int(image.shape[1])
+    D = len(dilations)
+    M = 9 * D
+    x = image.to(torch.int64)
+    taps = [x[yy, xx] for yy, xx in _pamr_neighbours(H, W, dilations, image.device)]
+    s1, s2 = D * x, D * x * x
+    for t in taps:
+        s1, s2 = s1 + t, s2 + t * t
+    den = 1e-8 + 0.1 * ((M * s2 - s1 * s1).to(dtype) / (M * (M - 1))).sqrt()
+    a = []
+    for t in taps:
+        q = (x - t).abs().to(dtype) / den
+        a.append(-((q[..., 0] + q[..., 1]) + q[..., 2]) / 3)
+    return torch.stack(a).softmax(0)
+
+
+def pamr_iterate_reference(w, m, dilations=PAMR_DILATIONS):
+    """CPU specification of hip.pamr_iterate: w [8 D, H, W], m [n, H, W] -> m' [n, H, W] in w's dtype,
+    m'(c, p) = sum_k w(k, p) m(c, q_k(p)), added in the order k = 0 .. 8 D - 1.  Runs on any device."""
+    H, W = int(m.shape[1]), int(m.shape[2])
+    m, out = m.to(w.dtype), None
+    for k, (yy, xx) in enumerate(_pamr_neighbours(H, W, dilations, m.device)):
+        term = w[k] * m[:, yy, xx]
+        out = term if out is None else out + term
+    return out
+
+
+def pamr_reference(image, m, dilations=PAMR_DILATIONS, iters=10, dtype=torch.float64):
+    """CPU specification of hip.seg_pamr, pixel-adaptive mask refinement: image uint8 RGB [H, W, 3], m [n, H, W] (the values
+    `seg_predict(probs=True)` hands over) -> (labels int64 [H, W], conf [H, W], the refined values [n, H, W]) in `dtype`:
+    `pamr_affinity_reference` once, `pamr_iterate_reference` `iters` >= 1 times, then per pixel the first maximum over the
+    classes and its value.  Upstream also resizes the mask to the image (align_corners=True); here the values arrive at image
+    resolution by `seg_predict`'s own rule, so that step does not exist.  Runs on any device."""
+    assert iters >= 1, iters
+    w = pamr_affinity_reference(image, dilations, dtype)
+    m = m.to(dtype)
+    for _ in range(iters):
+        m = pamr_iterate_reference(w, m, dilations)
+    labels = m.argmax(dim=0)
+    return labels, m.gather(0, labels[None]).squeeze(0), m
 
 
 def areas_reference(labels, gt, n, raw_labels=True):
@@ -1075,14 +1147,43 @@ def _check_classes(n, want_uint8=False):
         raise ValueError("Segmenter: uint8 labels hold at most 256 classes, the model has n = %d (int16 labels)" % n)
 
 
+def _check_pamr(pamr_iters, pamr_dilations, crf_iters):
+    """the two PAMR keywords of the Segmenter, checked -> (pamr_iters, the dilations as a tuple of ints)"""
+    if isinstance(pamr_iters, bool) or not isinstance(pamr_iters, int) or pamr_iters < 0:
+        raise ValueError("Segmenter: pamr_iters must be an int >= 0, got %r" % (pamr_iters,))
+    if pamr_iters > 0 and crf_iters > 0:
+        raise ValueError("Segmenter: pamr_iters = %d together with crf_iters = %d: the two refinements take the same slot, "
+                         "choose one" % (pamr_iters, crf_iters))
+    if not isinstance(pamr_dilations, (tuple, list)) or not 1 <= len(pamr_dilations) <= hip.SEG_PAMR_MAX_DILATIONS \
+            or any(isinstance(d, bool) or not isinstance(d, int) or not 1 <= d <= hip.SEG_PAMR_MAX_DILATION for d in pamr_dilations):
+        raise ValueError("Segmenter: pamr_dilations must be 1 .. %d ints in 1 .. %d, got %r"
+                         % (hip.SEG_PAMR_MAX_DILATIONS, hip.SEG_PAMR_MAX_DILATION, pamr_dilations))
+    return pamr_iters, tuple(pamr_dilations)
+
+
+def _pamr_bytes(rgb):
+    """the CRF's images (RGB in 0 .. 255, any dtype) as what `hip.seg_pamr` takes: rounded and clamped to bytes"""
+    if torch.is_tensor(rgb):
+        return rgb if rgb.dtype == torch.uint8 else rgb.round().clamp(0, 255).to(torch.uint8)
+    return [_pamr_bytes(t) for t in rgb]
+
+
 class Segmenter:
     def __init__(self, model, task=None, category_token_ids=None, prompt_ids=PROMPT_IDS, upsample="probs", smooth_iters=0,
-                 smooth_topk=3, temperature=1.0, crf_iters=0, full_context_alignment=False, label_dtype=None, slide_views=False):
+                 smooth_topk=3, temperature=1.0, crf_iters=0, full_context_alignment=False, label_dtype=None, slide_views=False,
+                 pamr_iters=0, pamr_dilations=PAMR_DILATIONS):
         """model: a SegOFAModel on the device.  The class names come from `category_token_ids` (one id sequence per class),
         else the task's `category_token_ids`, else the task's `category_list` through `task.encode_category`.
         upsample: "probs" resizes the per-patch softmax (temperature), the reference demo's order; "logits" resizes the raw
         scores, the criterion's eval order.  smooth_iters > 0: both feed hip.neighbour_smoothing's probabilities.
         crf_iters > 0: mean-field iterations of crf.rgb_dense_crf on the resized values.
+        pamr_iters > 0: iterations of pixel-adaptive mask refinement (`hip.seg_pamr`, csrc/pamr.hip; `pamr_reference` is the
+        specification) on the resized values, guided by the ORIGINAL uint8 photo, in the slot of the CRF and not together with
+        it: the predict launch hands over every class's value and `hip.seg_pamr` supplies the labels, conf and probs, in every
+        setting (single view, ms+flip, slide, slide over views).  Its cost is linear in the pixels, and every value stays a
+        convex combination of the values it was given, so conf keeps its meaning (a probability where it was one).
+        pamr_dilations: 1 .. 8 ints in 1 .. 32, the rings of 8 neighbours; the defaults are the published ones, with
+        pamr_iters=10.  Not built: a batch dimension (one `hip.seg_pamr` per image), PAMR inside `calibrate_raw` (a ValueError).
         label_dtype: None (uint8 up to 256 classes, else int16) or torch.uint8 to insist on bytes.
         slide_views: False: `slide` takes a single view, as ever.  True: `segment_raw` / `evaluate_raw(slide=...)` slide over
         EVERY view of `scales` and `flip` and finish each image with one launch of `hip.seg_predict_slide_views` (see
@@ -1107,6 +1208,7 @@ class Segmenter:
         self.src = source_tokens(names, prompt_ids, self.n)
         self.upsample, self.temperature = upsample, float(temperature)
         self.smooth_iters, self.smooth_topk, self.crf_iters = int(smooth_iters), int(smooth_topk), int(crf_iters)
+        self.pamr_iters, self.pamr_dilations = _check_pamr(pamr_iters, pamr_dilations, self.crf_iters)
         self.full_context_alignment = bool(full_context_alignment)
         self.label_dtype = label_dtype
         self.slide_views = bool(slide_views)
@@ -1221,8 +1323,8 @@ class Segmenter:
 
     def _label(self, merge, h, w, rgb, return_conf, return_probs):
         """one image (or batch) from its merge to a SegmentationResult at h x w: the predict launch, which with the CRF on hands
-        every class's value to `_crf`; rgb: the CRF's images, else None"""
-        crf = self.crf_iters > 0
+        every class's value to `_crf`, as it does with PAMR on; rgb: the CRF's images (with PAMR: as uint8), else None"""
+        crf = self.crf_iters > 0 or self.pamr_iters > 0
         out = merge.predict(h, w, conf=return_conf and not crf, probs=return_probs or crf, label_dtype=self.label_dtype)
         return self._crf(out, rgb, return_conf, return_probs)
 
@@ -1234,18 +1336,25 @@ class Segmenter:
             labels = q.argmax(1).to(labels.dtype)
             conf = q.amax(1) if return_conf else None
             probs = q if return_probs else None
+        elif self.pamr_iters > 0:
+            res = [hip.seg_pamr(probs[b], rgb[b].contiguous(), self.pamr_iters, self.pamr_dilations, conf=return_conf,
+                                probs_out=return_probs, label_dtype=labels.dtype) for b in range(probs.shape[0])]
+            labels, conf, probs = (None if col[0] is None else col[0][None] if len(col) == 1 else torch.stack(col)
+                                   for col in zip(*res))
         return SegmentationResult(labels, conf, probs)
 
     def __call__(self, images, out_hw=None, crf_images=None, return_conf=False, return_probs=False):
         patch_images, rgb = self.prepare_images(images)
         B, _, H, W = patch_images.shape
-        crf = self.crf_iters > 0
+        crf = self.crf_iters > 0 or self.pamr_iters > 0
         sizes, one = self._sizes(out_hw, B, (H, W), crf, crf_images is not None)
         if crf:
             if crf_images is not None:
                 rgb = [torch.as_tensor(c).to(patch_images.device).float() for c in crf_images]
             elif rgb is None:
                 rgb = ((patch_images.float() * 0.5 + 0.5) * 255.0).permute(0, 2, 3, 1).contiguous()
+            if self.pamr_iters > 0:
+                rgb = _pamr_bytes(rgb)
         scores, hp, wp = self.patch_scores(patch_images)
         with torch.no_grad():
             if sizes is None:
@@ -1311,7 +1420,8 @@ class Segmenter:
         crf, out = self.crf_iters > 0, []
         with torch.no_grad():
             for i, merge in enumerate(merges):
-                r = self._label(merge, *shapes[i], imgs[i][None].float() if crf else None, return_conf, return_probs)
+                rgb = imgs[i][None].float() if crf else imgs[i][None] if self.pamr_iters > 0 else None
+                r = self._label(merge, *shapes[i], rgb, return_conf, return_probs)
                 out.append(SegmentationResult(*(None if t is None else t[0] for t in r)))
         return out
 
@@ -1580,8 +1690,8 @@ class Segmenter:
 
     def _count(self, score, merge, gt, raw_labels, rgb, return_labels):
         """The scoring step of `evaluate_raw` / `evaluate`: one image's (or batch's) merge against gt [B, h, w] into `score` -> its
-        labels [B, h, w] or None.  The epilogue of the merge's scoring launch adds to the counters.  With the CRF on, the label
-        map comes from the CRF (`_label`; rgb: its images), not from the predict kernel, and `hip.seg_areas` counts it.  Where
+        labels [B, h, w] or None.  The epilogue of the merge's scoring launch adds to the counters.  With the CRF (or PAMR) on, the
+        label map comes from the CRF (`_label`; rgb: its images), not from the predict kernel, and `hip.seg_areas` counts it.  Where
         the score carries a confusion matrix, the launch is asked for its label map and `hip.seg_confusion` counts the pairs
         of the same labels behind it on the same stream; where it carries boundary counters, likewise, and
         `hip.seg_boundary_areas` counts the band areas of the same labels with d = `boundary_distance` of gt's size.  Where
@@ -1589,7 +1699,7 @@ class Segmenter:
         `hip.seg_calibration` counts labels, conf and gt behind the other two."""
         kw = dict(raw_labels=raw_labels, areas=score.areas, tally=score.tally)
         pairs, bands, cal = score.confusion is not None, score.boundary is not None, score.calibration is not None
-        if self.crf_iters > 0:
+        if self.crf_iters > 0 or self.pamr_iters > 0:
             res = self._label(merge, int(gt.shape[1]), int(gt.shape[2]), rgb, cal, False)
             labels, conf = res.labels.contiguous(), res.conf
             hip.seg_areas(labels, gt, self.n, **kw)
@@ -1661,7 +1771,8 @@ class Segmenter:
         crf, out = self.crf_iters > 0, []
         with torch.no_grad():
             for i, merge in enumerate(merges):
-                labels = self._count(score, merge, gts[i][None], raw_labels, imgs[i][None].float() if crf else None, return_labels)
+                rgb = imgs[i][None].float() if crf else imgs[i][None] if self.pamr_iters > 0 else None
+                labels = self._count(score, merge, gts[i][None], raw_labels, rgb, return_labels)
                 out.append(None if labels is None else labels[0])
         return (score, out) if return_labels else score
 
@@ -1675,13 +1786,15 @@ class Segmenter:
         gt = _check_batch_gt("Segmenter.evaluate", images, label_maps)
         patch_images, rgb = self.prepare_images(images)
         B, _, H, W = patch_images.shape
-        crf = self.crf_iters > 0
+        crf = self.crf_iters > 0 or self.pamr_iters > 0
         if crf and tuple(gt.shape[1:]) != (H, W):
-            raise ValueError("Segmenter.evaluate: with the CRF on, the label maps must have the images' size %s, got %s"
-                             % ((H, W), tuple(gt.shape[1:])))
+            raise ValueError("Segmenter.evaluate: with the CRF (crf_iters) or PAMR (pamr_iters) on, the label maps must have the "
+                             "images' size %s, got %s" % ((H, W), tuple(gt.shape[1:])))
         score = self._score_into("evaluate", into, patch_images.device, confusion, boundary_iou, [tuple(gt.shape[1:])], calibration)
         if crf and rgb is None:
             rgb = ((patch_images.float() * 0.5 + 0.5) * 255.0).permute(0, 2, 3, 1).contiguous()
+        if self.pamr_iters > 0:
+            rgb = _pamr_bytes(rgb)
         scores, hp, wp = self.patch_scores(patch_images)
         with torch.no_grad():
             labels = self._count(score, self._views_merge([(scores, hp, wp, False)]), gt.to(patch_images.device).contiguous(),
@@ -1700,6 +1813,10 @@ class Segmenter:
         if self.crf_iters > 0:
             raise ValueError("Segmenter.%s: a temperature sweep scores the network's probabilities, this Segmenter has "
                              "crf_iters = %d (the CRF's marginals are not a function of one temperature)" % (what, self.crf_iters))
+        if self.pamr_iters > 0:
+            raise ValueError("Segmenter.%s: a temperature sweep scores the network's probabilities, this Segmenter has "
+                             "pamr_iters = %d (the sweep's launch resizes and scores in one pass: PAMR inside it is not built)"
+                             % (what, self.pamr_iters))
         self._need_probability("Segmenter.%s" % what, None, "the values must be probabilities", "use upsample='probs' or the smoothing")
         temps = _check_temperatures("Segmenter.%s" % what, default_temperatures() if temperatures is None else temperatures)
         if into is None:
@@ -1725,7 +1842,7 @@ class Segmenter:
         consulted; afterwards `seg.temperature = sweep.best()`.  into: a sweep of the same temperatures, class count and
         device to accumulate into (a whole validation set).  `temperature_sweep_reference` is the specification.
         A ValueError naming the setting, before anything is launched: `scales` / `flip` other than one plain view, `slide`,
-        `crf_iters > 0`, upsample="logits" without the smoothing (the values must be probabilities), a bad temperature list,
+        `crf_iters > 0`, `pamr_iters > 0`, upsample="logits" without the smoothing (the values must be probabilities), a bad temperature list,
         an `into` that does not match."""
         what = "calibrate_raw"
         dev = next(self.model.parameters()).device

@@ -213,7 +213,7 @@ class SegmentationTask(TaskBase):
         `calibration=True` for how often a confidence is right (`score.calibration`; "ECE" in the summary,
         `score.precision_thresholds(target)` for `self_train_sample`'s thresholds)."""
         ctor = ("category_token_ids", "prompt_ids", "upsample", "smooth_iters", "smooth_topk", "temperature", "crf_iters",
-                "full_context_alignment", "label_dtype", "slide_views")
+                "full_context_alignment", "label_dtype", "slide_views", "pamr_iters", "pamr_dilations")
         seg = self.build_segmenter(model, **{k: kw.pop(k) for k in ctor if k in kw})
         return seg.evaluate_raw(images, label_maps, slide=slide, **kw)
 
@@ -223,7 +223,7 @@ class SegmentationTask(TaskBase):
         mean NLL: `build_segmenter(model, ...).calibrate_raw(images, label_maps, ...)`.  Keywords of the Segmenter's constructor
         go to it, the others to `Segmenter.calibrate_raw`."""
         ctor = ("category_token_ids", "prompt_ids", "upsample", "smooth_iters", "smooth_topk", "temperature", "crf_iters",
-                "full_context_alignment", "label_dtype", "slide_views")
+                "full_context_alignment", "label_dtype", "slide_views", "pamr_iters", "pamr_dilations")
         seg = self.build_segmenter(model, **{k: kw.pop(k) for k in ctor if k in kw})
         return seg.calibrate_raw(images, label_maps, **kw)
 
@@ -232,7 +232,7 @@ class SegmentationTask(TaskBase):
         device: `build_segmenter(model, ...).render_raw(images, ...)`.  Keywords of the Segmenter's constructor go to it, the
         others to `Segmenter.render_raw`."""
         ctor = ("category_token_ids", "prompt_ids", "upsample", "smooth_iters", "smooth_topk", "temperature", "crf_iters",
-                "full_context_alignment", "label_dtype", "slide_views")
+                "full_context_alignment", "label_dtype", "slide_views", "pamr_iters", "pamr_dilations")
         seg = self.build_segmenter(model, **{k: kw.pop(k) for k in ctor if k in kw})
         return seg.render_raw(images, **kw)
 
@@ -241,7 +241,7 @@ class SegmentationTask(TaskBase):
         the pixels the model is confident of: `build_segmenter(model, ...).pseudo_label_raw(images, ...)`.  Keywords of the
         Segmenter's constructor go to it, the others to `Segmenter.pseudo_label_raw`."""
         ctor = ("category_token_ids", "prompt_ids", "upsample", "smooth_iters", "smooth_topk", "temperature", "crf_iters",
-                "full_context_alignment", "label_dtype", "slide_views")
+                "full_context_alignment", "label_dtype", "slide_views", "pamr_iters", "pamr_dilations")
         seg = self.build_segmenter(model, **{k: kw.pop(k) for k in ctor if k in kw})
         return seg.pseudo_label_raw(images, **kw)
 

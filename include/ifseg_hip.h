@@ -968,6 +968,33 @@ int ifseg_seg_pseudo_weighted(const void* labels, int label_bytes, const float* 
                               int W, int boundary, int raw_labels, void* out, void* weight, unsigned long long* kept,
                               void* stream);
 
+/* ---- pixel-adaptive mask refinement (PAMR: Araslanov & Roth, CVPR 2020; Segmenter(pamr_iters=); the reference has no
+ * counterpart) ----  A few iterations of a local, image-adaptive, convex averaging of the class values of ONE image at image
+ * resolution, linear in the pixels; csrc/pamr.hip; ifseg_amd/predict.py pamr_reference is the specification.
+ * image uint8 [H][W][3] (HWC, any byte address); dilations: D ints on the HOST, 1 <= D <= 8, each 1..32.  Neighbour
+ * k = 8 i + t of pixel p is the pixel at p + dilations[i] (oy, ox), (oy, ox) = (-1,-1) (-1,0) (-1,1) (0,-1) (0,1) (1,-1) (1,0)
+ * (1,1) for t = 0..7, every coordinate clamped to the image (replicate padding).
+ *
+ * ifseg_pamr_affinity writes w fp32 [8 D][H][W], one launch: per channel S1, S2 = the sums of x and x^2 (grey levels) over the
+ * 9 taps of every dilation, the centre counted once per dilation, M = 9 D, in integers; std = sqrt((M S2 - S1^2) / (M (M - 1)))
+ * (the integer numerator rounded to fp32 once, IEEE division and square root);
+ *   a_k = -(sum_ch |x_ch(p) - x_ch(q_k)| / (1e-8 + 0.1 std_ch)) / 3    channels added in order, IEEE divisions
+ *   w_k = exp(a_k - max a) / sum_k exp(a_k - max a)                    the accurate expf, the sum in order k = 0 .. 8 D - 1
+ * ifseg_pamr_iterate is one iteration, one launch: dst[c][p] = sum_k w[k][p] src[c][q_k(p)], fused multiply-adds in order
+ * k = 0 .. 8 D - 1 from 0, for src / dst fp32 [n][H][W]; dst must share no byte with src or w (refused).  labels (uint8,
+ * label_bytes 1, n <= 256, or int16, 2) and conf fp32 [H][W], each may be NULL: per pixel the smallest c with maximal dst[c][p]
+ * and that value (the caller asks on its last iteration; there is no argmax pass).  No atomics, no sum across threads: two
+ * calls give equal bits.  A workgroup owns 16 x 64 pixels (8 x 64 for D > 2), keeps its pixels' weights in registers and
+ * stages one class plane's tile plus a halo of max d in LDS at a time (40 KiB at d = 32).
+ * NULL or misaligned pointers (w, src, dst, conf 4 bytes; int16 labels 2), D outside 1..8, a dilation outside 1..32, n outside
+ * 1..512, label_bytes outside {1, 2} or 1 with n > 256, dst overlapping src or w: IFSEG_ERR_BAD_ARG; H, W < 1, n H W >= 2^31 or
+ * 8 D H W >= 2^31: IFSEG_ERR_BAD_SHAPE.  Nothing is launched on a refusal. */
+int ifseg_pamr_affinity(const void* image, int H, int W, const int* dilations, int D, float* w, void* stream);
+int ifseg_pamr_iterate(const float* w, const float* src, float* dst, int n, int H, int W, const int* dilations, int D,
+                       void* labels, int label_bytes, float* conf, void* stream);
+/* which = 0: the dilations of a call at most, 1: the largest dilation, 2: the largest n; any other which: IFSEG_ERR_BAD_ARG. */
+int ifseg_pamr_limit(int which);
+
 /* ---- raw images and raw label maps in, a training batch out (ifseg_amd/augment.py is the specification, bit for bit; the
  * reference's training transform, segmentation_dataset.py:157-163, 239-251: Resize(ratio_range), RandomCrop(cat_max_ratio 0.75),
  * RandomFlip, PhotoMetricDistortion, Normalize) ----
