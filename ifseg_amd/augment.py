@@ -102,6 +102,27 @@ def check_axis(inn, out, what="train transform"):
         raise ValueError("%s: 2 * in * out must stay below 2**31 per axis, got %d -> %d" % (what, inn, out))
 
 
+def check_patch(P, what, max_p=None):
+    if P < 16 or P % 16 or (max_p is not None and P > max_p):
+        raise ValueError("%s: P must be a multiple of 16%s, got %d" % (what, "" if max_p is None else " in 16 .. %d" % max_p, P))
+
+
+def check_nseg(nseg, what):
+    if not 1 <= nseg <= 255:
+        raise ValueError("%s: 1 <= nseg <= 255 (uint8 label maps), got %d" % (what, nseg))
+
+
+def check_ordinals(first, B, what):
+    """the ordinals first .. first + B - 1 of a call: the stream's n has 32 bits"""
+    if B < 1 or first < 0 or first + B > 1 << 32:
+        raise ValueError("%s: B >= 1 and ordinals in [0, 2**32), got B = %d at %d" % (what, B, first))
+
+
+def check_records(records, B, what, name="records"):
+    if records.dtype != torch.int32 or tuple(records.shape) != (B, RECORD):
+        raise ValueError("%s: %s must be int32 [%d, 16], got %s %s" % (what, name, B, records.dtype, tuple(records.shape)))
+
+
 def f32_bits(x):
     return int(np.float32(x).view(np.int32))
 
@@ -140,16 +161,25 @@ def crop_ok(window, P):
     return int((cnt > 0).sum()) > 1 and 4 * int(cnt.max()) < 3 * P * P
 
 
+def photo_words(t, gate):
+    """the nine photometric words of a record -- brightness on, contrast on, saturation on, hue on, mode, beta, alpha_c,
+    alpha_s, delta -- from five consecutive draws t (slots 23..27 of the transform, 193..197 of the strong augmentation);
+    the four "on" bits are ANDed with `gate`"""
+    bits, g = t[0], 1 if gate else 0
+    return (g & (bits >> 1), g & (bits >> 3), g & (bits >> 4), g & (bits >> 5), (bits >> 2) & 1,
+            f32_bits(((t[1] >> 9) - 2 ** 22) / 2.0 ** 17), f32_bits((2 ** 22 + (t[2] >> 9)) / 2.0 ** 23),
+            f32_bits((2 ** 22 + (t[3] >> 9)) / 2.0 ** 23), ((t[4] * 36) >> 32) - 18)
+
+
 def draw_params(shapes, labels, P, nseg, seed, first_ordinal, ratio_range=(0.5, 2.0), photometric=True, flip=True,
                 raw_labels=True):
     """int32 [B, 16]: the records of the samples at ordinals first_ordinal + b.  shapes: [(H0, W0)], labels: uint8 [H0, W0]
     label maps (the crop choice reads them)."""
     P, nseg, first = int(P), int(nseg), int(first_ordinal)
     B = len(shapes)
-    if P < 16 or P % 16 or not 1 <= nseg <= 255:
-        raise ValueError("train transform: P must be a multiple of 16 and 1 <= nseg <= 255, got P = %d, nseg = %d" % (P, nseg))
-    if first < 0 or first + B > 1 << 32:
-        raise ValueError("train transform: ordinals must lie in [0, 2^32)")
+    check_patch(P, "train transform")
+    check_nseg(nseg, "train transform")
+    check_ordinals(first, B, "train transform")
     if len(labels) != B:
         raise ValueError("train transform: %d shapes for %d label maps" % (B, len(labels)))
     lo2, span2 = ratio_halves(ratio_range)
@@ -168,12 +198,7 @@ def draw_params(shapes, labels, P, nseg, seed, first_ordinal, ratio_range=(0.5, 
             off_h, off_w = (t[1 + 2 * k] * (new_h - P + 1)) >> 32, (t[2 + 2 * k] * (new_w - P + 1)) >> 32
             if k == CANDIDATES - 1 or crop_ok(cls[iy[off_h:off_h + P]][:, ix[off_w:off_w + P]], P):
                 break
-        bits = t[23]
-        m = t[24] >> 9
-        ph = 1 if photometric else 0
-        out[b] = (new_h, new_w, off_h, off_w, k, (bits & 1) if flip else 0, ph & (bits >> 1), ph & (bits >> 3), ph & (bits >> 4),
-                  ph & (bits >> 5), (bits >> 2) & 1, f32_bits((m - 2 ** 22) / 2.0 ** 17), f32_bits((2 ** 22 + (t[25] >> 9)) / 2.0 ** 23),
-                  f32_bits((2 ** 22 + (t[26] >> 9)) / 2.0 ** 23), ((t[27] * 36) >> 32) - 18, 0)
+        out[b] = (new_h, new_w, off_h, off_w, k, (t[23] & 1) if flip else 0) + photo_words(t[23:28], photometric) + (0,)
     return torch.from_numpy(out)
 
 
@@ -217,24 +242,25 @@ def hsv8_to_rgb(hsv):
     return np.stack([pick([V, q, p, p, t, V]), pick([t, V, V, q, p, p]), pick([p, p, t, V, V, q])], -1)
 
 
-def photometric(q_rgb, record):
-    """the photometric stage on grey levels [..., 3] (RGB) under one record -> uint8 [..., 3]"""
-    rec = [int(v) for v in record]
+def photometric(q_rgb, record, base=R_BRIGHT):
+    """the photometric stage on grey levels [..., 3] (RGB) under the nine words of one record that start at `base`
+    (`photo_words`' order; R_BRIGHT in a transform's record, S_BRIGHT in a strong one) -> uint8 [..., 3]"""
+    bright, contrast_on, sat, hue, mode, beta, alpha_c, alpha_s, delta = [int(v) for v in record][base:base + 9]
     img = np.asarray(q_rgb).astype(np.int64)
-    contrast = lambda x: convert(x, alpha=bits_f32(rec[R_ALPHA_C])) if rec[R_CONTRAST] else x
-    if rec[R_BRIGHT]:
-        img = convert(img, beta=bits_f32(rec[R_BETA]))
-    if rec[R_MODE] == 1:
+    contrast = lambda x: convert(x, alpha=bits_f32(alpha_c)) if contrast_on else x
+    if bright:
+        img = convert(img, beta=bits_f32(beta))
+    if mode == 1:
         img = contrast(img)
-    if rec[R_SAT]:
+    if sat:
         hsv = rgb_to_hsv8(img)
-        hsv[..., 1] = convert(hsv[..., 1], alpha=bits_f32(rec[R_ALPHA_S]))
+        hsv[..., 1] = convert(hsv[..., 1], alpha=bits_f32(alpha_s))
         img = hsv8_to_rgb(hsv)
-    if rec[R_HUE]:
+    if hue:
         hsv = rgb_to_hsv8(img)
-        hsv[..., 0] = (hsv[..., 0] + rec[R_DELTA]) % 180
+        hsv[..., 0] = (hsv[..., 0] + delta) % 180                                  # any delta: reduced mod 180 here
         img = hsv8_to_rgb(hsv)
-    if rec[R_MODE] == 0:
+    if mode == 0:
         img = contrast(img)
     return img.astype(np.uint8)
 
@@ -316,9 +342,8 @@ class TrainTransform:
                  ratio_range=(0.5, 2.0), raw_labels=True, dtype=torch.float32, reverse_channels=False, eos=EOS):
         """device "cpu" runs the specification of this module, any other device the kernels of csrc/trainload.hip"""
         self.P, self.nseg, self.seg_id_offset = int(P), int(nseg), int(seg_id_offset)
-        if self.P < 16 or self.P % 16 or not 1 <= self.nseg <= 255:
-            raise ValueError("TrainTransform: P must be a multiple of 16 and 1 <= nseg <= 255, got P = %d, nseg = %d"
-                             % (self.P, self.nseg))
+        check_patch(self.P, "TrainTransform")
+        check_nseg(self.nseg, "TrainTransform")
         if dtype not in (torch.float32, torch.bfloat16):
             raise ValueError("TrainTransform: dtype must be torch.float32 or torch.bfloat16, got %s" % dtype)
         self.mean, self.std = tuple(float(x) for x in mean), tuple(float(x) for x in std)
@@ -438,9 +463,8 @@ MIX_MAX_P = 4096
 
 
 def check_mix(P, nseg, mask="class", what="batch mix"):
-    if P < 16 or P % 16 or P > MIX_MAX_P or not 1 <= nseg <= 255:
-        raise ValueError("%s: P must be a multiple of 16 in 16 .. %d and 1 <= nseg <= 255, got P = %d, nseg = %d"
-                         % (what, MIX_MAX_P, P, nseg))
+    check_patch(P, what, MIX_MAX_P)
+    check_nseg(nseg, what)
     if mask not in MIX_MASKS:
         raise ValueError("%s: mask must be one of %r, got %r" % (what, MIX_MASKS, mask))
 
@@ -517,8 +541,7 @@ def mix_draw_reference(src_target, nseg, seg_id_offset, seed, first_ordinal, mas
     P, nseg, first = mix_patch_size(src_target), int(nseg), int(first_ordinal)
     check_mix(P, nseg, mask)
     B = src_target.shape[0]
-    if first < 0 or first + B > 1 << 32:
-        raise ValueError("batch mix: ordinals must lie in [0, 2^32)")
+    check_ordinals(first, B, "batch mix")
     out = np.zeros((B, RECORD), dtype=np.uint32)
     for b in range(B):
         if mask == "box":
@@ -538,8 +561,7 @@ def mix_selection(records, src_target, nseg, seg_id_offset):
     src_target = torch.as_tensor(src_target).cpu()
     P = mix_patch_size(src_target)
     B = src_target.shape[0]
-    if records.dtype != torch.int32 or tuple(records.shape) != (B, RECORD):
-        raise ValueError("batch mix: records must be int32 [%d, 16], got %s %s" % (B, records.dtype, tuple(records.shape)))
+    check_records(records, B, "batch mix")
     rec = records.long()
     c = src_target[:, :-1] - int(seg_id_offset)
     has = (c >= 0) & (c < nseg)
@@ -677,8 +699,7 @@ BLUR_IDENTITY = (BLUR_ONE, 0, 0, 0, 0)
 
 
 def check_strong(P, mean=HALF, std=HALF, jitter_p8=205, blur_p8=128, what="strong augmentation"):
-    if P < 16 or P % 16 or P > STRONG_MAX_P:
-        raise ValueError("%s: P must be a multiple of 16 in 16 .. %d, got %d" % (what, STRONG_MAX_P, P))
+    check_patch(P, what, STRONG_MAX_P)
     if len(tuple(mean)) != 3 or len(tuple(std)) != 3 or not all(float(s) > 0 for s in std):
         raise ValueError("%s: mean and std hold three entries and std > 0 (the table must increase), got %r %r" % (what, mean, std))
     for name, p8 in (("jitter_p8", jitter_p8), ("blur_p8", blur_p8)):
@@ -693,8 +714,7 @@ def check_strong_images(images, what="strong augmentation"):
         raise ValueError("%s: images must be fp32 or bf16 [B, 3, P, P] with B >= 1, got %s"
                          % (what, (images.dtype, tuple(images.shape)) if torch.is_tensor(images) else type(images)))
     B, P = int(images.shape[0]), int(images.shape[2])
-    if P < 16 or P % 16 or P > STRONG_MAX_P:
-        raise ValueError("%s: P must be a multiple of 16 in 16 .. %d, got %d" % (what, STRONG_MAX_P, P))
+    check_patch(P, what, STRONG_MAX_P)
     if B * 3 * P * P >= 2 ** 31:
         raise ValueError("%s: B * 3 * P * P must stay below 2**31, got B = %d, P = %d" % (what, B, P))
     return B, P
@@ -704,18 +724,13 @@ def strong_draw_reference(B, seed, first_ordinal, jitter_p8=205, blur_p8=128):
     """CPU specification of hip.strong_draw -> the records int32 [B, 16] of the samples at ordinals first_ordinal + b"""
     B, first, jitter_p8, blur_p8 = int(B), int(first_ordinal), int(jitter_p8), int(blur_p8)
     check_strong(16, jitter_p8=jitter_p8, blur_p8=blur_p8)
-    if B < 1 or first < 0 or first + B > 1 << 32:
-        raise ValueError("strong augmentation: B >= 1 and ordinals in [0, 2^32), got B = %d at %d" % (B, first))
+    check_ordinals(first, B, "strong augmentation")
     out = np.zeros((B, RECORD), dtype=np.int32)
     for b in range(B):
         t = draws(seed, first + b, STRONG_SLOT + 8)[STRONG_SLOT:]
-        gate = 1 if (t[0] >> 24) < jitter_p8 else 0
-        bits = t[1]
         blur = (t[6] >> 24) < blur_p8
         s = t[7] >> 26
-        out[b, :S_W0] = (gate & (bits >> 1), gate & (bits >> 3), gate & (bits >> 4), gate & (bits >> 5), (bits >> 2) & 1,
-                         f32_bits(((t[2] >> 9) - 2 ** 22) / 2.0 ** 17), f32_bits((2 ** 22 + (t[3] >> 9)) / 2.0 ** 23),
-                         f32_bits((2 ** 22 + (t[4] >> 9)) / 2.0 ** 23), ((t[5] * 36) >> 32) - 18, s if blur else -1)
+        out[b, :S_W0] = photo_words(t[1:6], (t[0] >> 24) < jitter_p8) + (s if blur else -1,)
         out[b, S_W0:S_W0 + 5] = BLUR_WEIGHTS[s] if blur else BLUR_IDENTITY
     return torch.from_numpy(out)
 
@@ -766,8 +781,7 @@ def strong_apply_reference(records, images, mean=HALF, std=HALF, reverse_channel
     B, P = check_strong_images(images)
     check_strong(P, mean, std)
     records = torch.as_tensor(records).cpu()
-    if records.dtype != torch.int32 or tuple(records.shape) != (B, RECORD):
-        raise ValueError("strong augmentation: records must be int32 [%d, 16], got %s %s" % (B, records.dtype, tuple(records.shape)))
+    check_records(records, B, "strong augmentation")
     lut = normalisation_table(mean, std)
     q = grey_levels(images, mean, std)                                             # [B, 3, P, P], planes
     out = torch.empty(B, 3, P, P, dtype=images.dtype)
@@ -777,12 +791,7 @@ def strong_apply_reference(records, images, mean=HALF, std=HALF, reverse_channel
             out[b] = float("nan")
             continue
         rgb = np.moveaxis(q[b][::-1] if reverse_channels else q[b], 0, -1)         # [P, P, 3], true colours
-        train_rec = [0] * RECORD
-        for k_train, k in ((R_BRIGHT, S_BRIGHT), (R_CONTRAST, S_CONTRAST), (R_SAT, S_SAT), (R_HUE, S_HUE), (R_MODE, S_MODE),
-                           (R_BETA, S_BETA), (R_ALPHA_C, S_ALPHA_C), (R_ALPHA_S, S_ALPHA_S), (R_DELTA, S_DELTA)):
-            train_rec[k_train] = rec[k]
-        train_rec[R_DELTA] %= 180
-        qq = blur_levels(photometric(rgb, train_rec), rec[S_W0:S_W0 + 5])
+        qq = blur_levels(photometric(rgb, rec, base=S_BRIGHT), rec[S_W0:S_W0 + 5])
         planes = torch.from_numpy(np.ascontiguousarray(np.moveaxis(qq, -1, 0)))
         if reverse_channels:
             planes = planes.flip(0)

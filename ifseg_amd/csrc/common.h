@@ -72,13 +72,29 @@ __device__ __forceinline__ float erf_as(float x, float e) {
   const float r = 1.f - poly * e;
   return x < 0.f ? -r : r;
 }
-// Counter-based generator of the dropout / DropPath masks (rowops.hip) and of the artificial images (imfree.hip):
-// one 64-bit draw per counter value, nothing stored.
+// Counter-based generator of the dropout / DropPath masks (rowops.hip) and of the device-side input path (the counter stream
+// below): one 64-bit draw per counter value, nothing stored.
 __device__ __forceinline__ unsigned long long splitmix64(unsigned long long z) {
   z += 0x9E3779B97F4A7C15ull;
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   return z ^ (z >> 31);
+}
+// ---- the counter stream of the device-side input path (trainload.hip, mix.hip, strong.hip, imfree.hip) ----
+// t(n, i) = splitmix64(seed + (n << 32) + i) >> 32 for the sample ordinal n = first + b and the slot i; which slot draws
+// what is each file's own table (ifseg_amd/augment.py, ifseg_amd/artificial.py state them)
+__device__ __forceinline__ unsigned long long stream_base(unsigned long long seed, unsigned long long first, int b) {
+  return seed + ((first + (unsigned)b) << 32);
+}
+__device__ __forceinline__ unsigned draw32(unsigned long long base, unsigned slot) { return (unsigned)(splitmix64(base + slot) >> 32); }
+// an integer below m, (t m) >> 32: torch.randint's range without modulo bias worth speaking of (m <= 2^16)
+__device__ __forceinline__ int draw_below(unsigned long long base, unsigned slot, unsigned m) { return (int)__umulhi(draw32(base, slot), m); }
+// host: the ordinals first .. first + B - 1 of a call lie in [0, 2^32)
+static inline bool ordinals_ok(long long first, int B) { return first >= 0 && first + (long long)B <= (1ll << 32); }
+// host: [a, a + na) and [b, b + nb) share a byte; a null pointer shares none
+static inline bool overlaps(const void* a, long long na, const void* b, long long nb) {
+  const size_t x = (size_t)a, y = (size_t)b;
+  return a && b && x < y + (size_t)nb && y < x + (size_t)na;
 }
 union U128 {
   uint4 v;

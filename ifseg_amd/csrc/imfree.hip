@@ -8,7 +8,7 @@
 //                        text2seg_target (the bandwidth part: B * (S_h * S_w + 1) * 8 bytes)
 //
 // Every launch shape depends on the arguments only (never on drawn data), nothing is read back: capturable into a HIP graph;
-// with the ordinal in a device word a replayed graph draws new images.
+// with the ordinal in a device word a replayed graph draws new images.  The counter stream and the ordinal check: common.h.
 #include "common.h"
 #include "../../include/ifseg_hip.h"
 
@@ -21,18 +21,12 @@ __device__ __forceinline__ int nearest_src(int dst, float scale, int in) {
 }
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
-// u(n, i) >> 32 scaled to [0, m): torch.randint's range without modulo bias worth speaking of (m <= 2^16)
-__device__ __forceinline__ int draw_below(unsigned long long base, unsigned i, unsigned m) {
-  return (int)__umulhi((unsigned)(splitmix64(base + i) >> 32), m);
-}
-
 __global__ __launch_bounds__(256) void imfree_draw_kernel(unsigned long long seed, unsigned long long first, const long long* first_dev,
                                                           int l, int r, int nseg, int* shapes, int* coarse) {
   const int b = blockIdx.y, cs = (r - 1) * (r - 1);
   const unsigned i = blockIdx.x * 256u + threadIdx.x;
   if (i >= (unsigned)cs) return;
-  const unsigned long long n = (first_dev ? (unsigned long long)*first_dev : first) + (unsigned)b;
-  const unsigned long long base = seed + (n << 32);
+  const unsigned long long base = stream_base(seed, first_dev ? (unsigned long long)*first_dev : first, b);
   const int sh = l + draw_below(base, 0, r - l), sw = l + draw_below(base, 1, r - l);
   if (i == 0) {
     shapes[2 * b] = sh;
@@ -143,7 +137,7 @@ extern "C" int ifseg_imfree_draw(unsigned long long seed, long long first_ordina
                                  int r, int nseg, int* shapes, int* coarse, void* stream) {
   (void)hipGetLastError();
   if (l < 1 || l >= r || r > 129 || nseg < 1 || nseg > 65535) return IFSEG_ERR_BAD_ARG;
-  if (!first_ordinal_dev && (first_ordinal < 0 || first_ordinal + (long long)B > (1ll << 32))) return IFSEG_ERR_BAD_ARG;
+  if (!first_ordinal_dev && !ordinals_ok(first_ordinal, B)) return IFSEG_ERR_BAD_ARG;
   if (B <= 0) return 0;
   if (B > 65535) return IFSEG_ERR_BAD_SHAPE;
   const int cs = (r - 1) * (r - 1);

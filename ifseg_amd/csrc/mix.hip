@@ -17,6 +17,7 @@
 // The class of a source pixel: c = target - seg_id_offset in 64 bits, a class only if 0 <= c < nseg ('unknown', a poisoned -1
 // and seg_id_offset + 2^32 + 3 have none).  No address depends on a record or on a target's value beyond that test.
 // No scratch buffer, no memset, static launch shapes, nothing read back.
+// The counter stream, the ordinal check and the byte-range overlap test are common.h's.
 #include "common.h"
 #include "../../include/ifseg_hip.h"
 
@@ -26,8 +27,6 @@ constexpr int MX_MAX_P = 4096;
 constexpr int MX_RUN = 8;                        // pixels per thread of the apply kernel
 constexpr int MX_SLOT_BOX = 28, MX_SLOT_CLASS = 32;
 enum { M_BITS = 0, M_Y0 = 8, M_X0, M_Y1, M_X1, M_PRESENT, M_CHOSEN };
-
-__device__ __forceinline__ unsigned mix_draw32(unsigned long long base, unsigned slot) { return (unsigned)(splitmix64(base + slot) >> 32); }
 
 // the class of a target value, or -1
 __device__ __forceinline__ int mix_class(long long t, long long seg0, int nseg) {
@@ -61,14 +60,14 @@ __global__ __launch_bounds__(MX_DRAW_THREADS) void mix_draw_kernel(const long lo
   __shared__ uint32_t bits[8];
   __shared__ int npresent;
   const int b = blockIdx.x, tid = threadIdx.x;
-  const unsigned long long base = seed + ((first + (unsigned)b) << 32);
+  const unsigned long long base = stream_base(seed, first, b);
   int* rec = records + (long long)b * 16;
   if (box) {
     if (tid < 16) {
-      const int bh = P / 4 + (int)__umulhi(mix_draw32(base, MX_SLOT_BOX), (unsigned)(P / 2 + 1));
-      const int bw = P / 4 + (int)__umulhi(mix_draw32(base, MX_SLOT_BOX + 1), (unsigned)(P / 2 + 1));
-      const int y0 = (int)__umulhi(mix_draw32(base, MX_SLOT_BOX + 2), (unsigned)(P - bh + 1));
-      const int x0 = (int)__umulhi(mix_draw32(base, MX_SLOT_BOX + 3), (unsigned)(P - bw + 1));
+      const int bh = P / 4 + draw_below(base, MX_SLOT_BOX, (unsigned)(P / 2 + 1));
+      const int bw = P / 4 + draw_below(base, MX_SLOT_BOX + 1, (unsigned)(P / 2 + 1));
+      const int y0 = draw_below(base, MX_SLOT_BOX + 2, (unsigned)(P - bh + 1));
+      const int x0 = draw_below(base, MX_SLOT_BOX + 3, (unsigned)(P - bw + 1));
       rec[tid] = tid == M_Y0 ? y0 : tid == M_X0 ? x0 : tid == M_Y1 ? y0 + bh : tid == M_X1 ? x0 + bw : 0;
     }
     return;
@@ -114,7 +113,7 @@ __global__ __launch_bounds__(MX_DRAW_THREADS) void mix_draw_kernel(const long lo
   }
   __syncthreads();
   const int np = npresent, m = (np + 1) / 2;
-  if (tid < m) pick[tid] = tid + (int)__umulhi(mix_draw32(base, MX_SLOT_CLASS + tid), (unsigned)(np - tid));
+  if (tid < m) pick[tid] = tid + draw_below(base, MX_SLOT_CLASS + tid, (unsigned)(np - tid));
   __syncthreads();
   if (tid == 0) {
     for (int i = 0; i < m; ++i) {
@@ -219,12 +218,6 @@ __global__ __launch_bounds__(256) void mix_apply_kernel(const int* __restrict__ 
   }
 }
 
-// [a, a + na) and [b, b + nb) share a byte
-bool overlaps(const void* a, long long na, const void* b, long long nb) {
-  const size_t x = (size_t)a, y = (size_t)b;
-  return a && b && x < y + (size_t)nb && y < x + (size_t)na;
-}
-
 }  // namespace
 
 extern "C" int ifseg_mix_draw(const long long* src_target, int B, int P, int nseg, long long seg_id_offset,
@@ -232,7 +225,7 @@ extern "C" int ifseg_mix_draw(const long long* src_target, int B, int P, int nse
   (void)hipGetLastError();
   if (!src_target || !records || ((size_t)src_target & 7) || ((size_t)records & 3)) return IFSEG_ERR_BAD_ARG;
   if (nseg < 1 || nseg > 255 || (box != 0 && box != 1)) return IFSEG_ERR_BAD_ARG;
-  if (first_ordinal < 0 || first_ordinal + (long long)B > (1ll << 32)) return IFSEG_ERR_BAD_ARG;
+  if (!ordinals_ok(first_ordinal, B)) return IFSEG_ERR_BAD_ARG;
   if (B < 1 || B > 65535 || P < 16 || P % 16 || P > MX_MAX_P) return IFSEG_ERR_BAD_SHAPE;
   hipLaunchKernelGGL(mix_draw_kernel, dim3(B), dim3(MX_DRAW_THREADS), 0, (hipStream_t)stream, src_target, seed,
                      (unsigned long long)first_ordinal, P, nseg, seg_id_offset, box, records);

@@ -217,11 +217,6 @@ int check_dilations(const int* dilations, int D, Dilations* dil) {
   return R;
 }
 
-bool shares_bytes(const void* a, long long na, const void* b, long long nb) {
-  const char *pa = (const char*)a, *pb = (const char*)b;
-  return pa < pb + nb && pb < pa + na;
-}
-
 }  // namespace
 
 extern "C" int ifseg_pamr_limit(int which) {
@@ -271,7 +266,7 @@ extern "C" int ifseg_pamr_iterate(const float* w, const float* src, float* dst, 
   if (R < 0) return R;
   if (H < 1 || W < 1 || (long long)H * W * n >= (1ll << 31) || (long long)H * W * 8 * D >= (1ll << 31)) return IFSEG_ERR_BAD_SHAPE;
   const long long vbytes = (long long)H * W * n * 4, wbytes = (long long)H * W * 8 * D * 4;
-  if (shares_bytes(dst, vbytes, src, vbytes) || shares_bytes(dst, vbytes, w, wbytes)) return IFSEG_ERR_BAD_ARG;
+  if (overlaps(dst, vbytes, src, vbytes) || overlaps(dst, vbytes, w, wbytes)) return IFSEG_ERR_BAD_ARG;
   // rows per thread, chosen by measurement (profiles/pamr_bench.txt): 4 (16 x 64 tiles, the smaller share of halo) while four
   // rows of weights leave four waves per SIMD (D <= 2), else 2 (8 x 64 tiles: half the registers, twice the waves).
   // IFSEG_PAMR_RPT=2 / 4 (a laboratory switch, common.h) forces one of them, 4 up to D = 6 (its registers run out above)

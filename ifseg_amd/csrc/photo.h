@@ -1,7 +1,7 @@
 // The photometric chain on grey levels (mmseg PhotoMetricDistortion; ifseg_amd/augment.py `photometric` is the specification,
 // bit for bit): brightness; contrast if mode = 1; saturation; hue; contrast if mode = 0.  In registers, integers throughout,
 // and convert() as ONE fp32 operation.  Shared by trainload.hip (behind the resize) and strong.hip (on the grey levels recovered
-// from a normalised batch).
+// from a normalised batch), and with it the nine record words that drive it: how they are drawn, read back and validated.
 #pragma once
 #include "common.h"
 
@@ -56,6 +56,41 @@ __device__ __forceinline__ void photometric(const Photo& ph, int* r, int* g, int
     hsv8_to_rgb(H >= 180 ? H - 180 : H, S, V, r, g, b);
   }
   if (ph.contrast && ph.mode == 0) { *r = cvt_mul(*r, ph.alpha_c); *g = cvt_mul(*g, ph.alpha_c); *b = cvt_mul(*b, ph.alpha_c); }
+}
+
+// ---- the photometric part of a record: nine consecutive int32 words, wherever the record keeps them ----
+enum { PH_BRIGHT, PH_CONTRAST, PH_SAT, PH_HUE, PH_MODE, PH_BETA, PH_ALPHA_C, PH_ALPHA_S, PH_DELTA };
+// drawn from five consecutive slots of the sample's stream (common.h): bits 1 brightness on, 2 mode, 3 contrast on, 4 saturation
+// on, 5 hue on of the first, the four "on" bits ANDed with `gate`; beta, alpha_c, alpha_s, delta of the other four
+__device__ __forceinline__ void photo_draw(int* w, unsigned long long base, unsigned slot, int gate) {
+  const unsigned bits = draw32(base, slot);
+  w[PH_BRIGHT] = gate & (bits >> 1);
+  w[PH_MODE] = (bits >> 2) & 1;
+  w[PH_CONTRAST] = gate & (bits >> 3);
+  w[PH_SAT] = gate & (bits >> 4);
+  w[PH_HUE] = gate & (bits >> 5);
+  // exact in fp32: integers below 2^24 times a power of two
+  w[PH_BETA] = __float_as_int((float)((int)(draw32(base, slot + 1) >> 9) - (1 << 22)) * (1.f / 131072.f));
+  w[PH_ALPHA_C] = __float_as_int((float)((1 << 22) + (int)(draw32(base, slot + 2) >> 9)) * (1.f / 8388608.f));
+  w[PH_ALPHA_S] = __float_as_int((float)((1 << 22) + (int)(draw32(base, slot + 3) >> 9)) * (1.f / 8388608.f));
+  w[PH_DELTA] = draw_below(base, slot + 4, 36u) - 18;
+}
+// as the chain takes them: delta reduced mod 180, whatever its sign
+__device__ __forceinline__ Photo photo_read(const int* w) {
+  Photo ph;
+  ph.bright = w[PH_BRIGHT]; ph.contrast = w[PH_CONTRAST]; ph.sat = w[PH_SAT]; ph.hue = w[PH_HUE]; ph.mode = w[PH_MODE];
+  ph.delta = (w[PH_DELTA] % 180 + 180) % 180;
+  ph.beta = __int_as_float(w[PH_BETA]); ph.alpha_c = __int_as_float(w[PH_ALPHA_C]); ph.alpha_s = __int_as_float(w[PH_ALPHA_S]);
+  return ph;
+}
+// the five flags in {0, 1} and the three floats finite (strong.hip refuses a record that fails; trainload.hip does not ask)
+__device__ __forceinline__ bool photo_valid(const int* w) {
+  bool bad = false;
+#pragma unroll
+  for (int i = PH_BRIGHT; i <= PH_MODE; ++i) bad |= (unsigned)w[i] > 1u;
+#pragma unroll
+  for (int i = PH_BETA; i <= PH_ALPHA_S; ++i) bad |= (w[i] & 0x7f800000) == 0x7f800000;
+  return !bad;
 }
 
 }  // namespace photo

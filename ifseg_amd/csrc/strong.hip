@@ -14,6 +14,8 @@
 //                        LDS: 3 KiB table + 3 KiB midpoints + 5 KiB levels + 18 KiB sums.
 //                        A record that is not valid poisons its sample with NaN; nothing is indexed through a record.
 // No scratch buffer, no memset, static launch shapes, nothing read back.
+// The counter stream, the ordinal check and the overlap test: common.h; words 0..8 of a record, drawn, read back and validated:
+// photo.h; the NaN tile: tile.h.
 #include "tile.h"
 #include "photo.h"
 #include "../../include/ifseg_hip.h"
@@ -27,7 +29,7 @@ constexpr int SG_MAX_P = 4096;
 constexpr int SG_R = 4;                                      // blur radius
 constexpr int SG_HW = TILE_COLS + 2 * SG_R, SG_HH = TILE_ROWS + 2 * SG_R;
 constexpr int SG_SLOT = 192;
-enum { S_BRIGHT, S_CONTRAST, S_SAT, S_HUE, S_MODE, S_BETA, S_ALPHA_C, S_ALPHA_S, S_DELTA, S_SIGMA, S_W0, S_ZERO = 15 };
+enum { S_PHOTO = 0, S_SIGMA = 9, S_W0, S_ZERO = 15 };         // S_PHOTO: photo.h's nine words
 
 // w0..w4 for sigma = 0.15 + s / 64, s = 0..63: w_i = floor(4096 g_i / Z + 0.5), w_0 = 4096 - 2 sum w_i (augment.BLUR_WEIGHTS)
 #define SG_BLUR_TABLE                                                                                   \
@@ -51,29 +53,17 @@ enum { S_BRIGHT, S_CONTRAST, S_SAT, S_HUE, S_MODE, S_BETA, S_ALPHA_C, S_ALPHA_S,
 const int g_blur_table[320] = {SG_BLUR_TABLE};
 __constant__ int c_blur_table[320] = {SG_BLUR_TABLE};
 
-__device__ __forceinline__ unsigned sg_draw32(unsigned long long base, unsigned slot) { return (unsigned)(splitmix64(base + slot) >> 32); }
-
 // ------------------------------------------------------------------------------------------------------------- draw
 __global__ __launch_bounds__(64) void strong_draw_kernel(int B, unsigned long long seed, unsigned long long first, int jitter_p8,
                                                          int blur_p8, int* __restrict__ records) {
   const int b = blockIdx.x * 64 + threadIdx.x;
   if (b >= B) return;
-  const unsigned long long base = seed + ((first + (unsigned)b) << 32);
-  const int gate = (int)(sg_draw32(base, SG_SLOT) >> 24) < jitter_p8 ? 1 : 0;
-  const unsigned bits = sg_draw32(base, SG_SLOT + 1);
-  const bool blur = (int)(sg_draw32(base, SG_SLOT + 6) >> 24) < blur_p8;
-  const int s = (int)(sg_draw32(base, SG_SLOT + 7) >> 26);
+  const unsigned long long base = stream_base(seed, first, b);
+  const int gate = (int)(draw32(base, SG_SLOT) >> 24) < jitter_p8 ? 1 : 0;
+  const bool blur = (int)(draw32(base, SG_SLOT + 6) >> 24) < blur_p8;
+  const int s = (int)(draw32(base, SG_SLOT + 7) >> 26);
   int* rec = records + (long long)b * 16;
-  rec[S_BRIGHT] = gate & (bits >> 1);
-  rec[S_MODE] = (bits >> 2) & 1;
-  rec[S_CONTRAST] = gate & (bits >> 3);
-  rec[S_SAT] = gate & (bits >> 4);
-  rec[S_HUE] = gate & (bits >> 5);
-  // exact in fp32: integers below 2^24 times a power of two
-  rec[S_BETA] = __float_as_int((float)((int)(sg_draw32(base, SG_SLOT + 2) >> 9) - (1 << 22)) * (1.f / 131072.f));
-  rec[S_ALPHA_C] = __float_as_int((float)((1 << 22) + (int)(sg_draw32(base, SG_SLOT + 3) >> 9)) * (1.f / 8388608.f));
-  rec[S_ALPHA_S] = __float_as_int((float)((1 << 22) + (int)(sg_draw32(base, SG_SLOT + 4) >> 9)) * (1.f / 8388608.f));
-  rec[S_DELTA] = (int)__umulhi(sg_draw32(base, SG_SLOT + 5), 36u) - 18;
+  photo_draw(rec + S_PHOTO, base, SG_SLOT + 1, gate);
   rec[S_SIGMA] = blur ? s : -1;
 #pragma unroll
   for (int i = 0; i < 5; ++i) rec[S_W0 + i] = blur ? c_blur_table[5 * s + i] : (i == 0 ? 4096 : 0);
@@ -110,7 +100,8 @@ __global__ __launch_bounds__(256) void strong_apply_kernel(const int* __restrict
   __shared__ unsigned char lev[3][SG_HH][SG_HW];              // the jittered grey levels of the halo, per plane
   __shared__ uint32_t hsum[3][SG_HH][TILE_COLS];              // the horizontal pass
 
-  const auto [b, X0, Y0, xend, yend, lane, wave] = tile_decode(tiles_x, tiles_y, P, P);
+  const Tile t = tile_decode(tiles_x, tiles_y, P, P);
+  const auto [b, X0, Y0, xend, yend, lane, wave] = t;
   const int tid = threadIdx.x;
   const int* rec = records + (long long)b * 16;
   const long long plane = (long long)P * P, img0 = (long long)b * 3 * plane;
@@ -126,26 +117,12 @@ __global__ __launch_bounds__(256) void strong_apply_kernel(const int* __restrict
     wsum += (i ? 2ll : 1ll) * w[i];
   }
   bad |= wsum != 4096;
-#pragma unroll
-  for (int i = S_BRIGHT; i <= S_MODE; ++i) bad |= (unsigned)rec[i] > 1u;
-#pragma unroll
-  for (int i = S_BETA; i <= S_ALPHA_S; ++i) bad |= (rec[i] & 0x7f800000) == 0x7f800000;
+  bad |= !photo_valid(rec + S_PHOTO);
   if (bad) {
-    const float nanv = __int_as_float(0x7fc00000);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int yr = Y0 + wave * 4 + j;
-      const bool ok = yr < P && X0 + lane < P;
-      const long long erow = img0 + (long long)min(yr, P - 1) * P;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) store_plane(out, erow + c * plane + x, ok, nanv, lane, x, xend);
-    }
+    store_nan_tile(out, img0, plane, P, t, x);
     return;
   }
-  Photo ph;
-  ph.bright = rec[S_BRIGHT]; ph.contrast = rec[S_CONTRAST]; ph.sat = rec[S_SAT]; ph.hue = rec[S_HUE]; ph.mode = rec[S_MODE];
-  ph.delta = (rec[S_DELTA] % 180 + 180) % 180;
-  ph.beta = __int_as_float(rec[S_BETA]); ph.alpha_c = __int_as_float(rec[S_ALPHA_C]); ph.alpha_s = __int_as_float(rec[S_ALPHA_S]);
+  const Photo ph = photo_read(rec + S_PHOTO);
 
   for (int i = tid; i < 768; i += 256) lut[i] = lut_g[i];
   __syncthreads();
@@ -206,12 +183,6 @@ __global__ __launch_bounds__(256) void strong_apply_kernel(const int* __restrict
   }
 }
 
-// [a, a + na) and [b, b + nb) share a byte
-bool sg_overlaps(const void* a, long long na, const void* b, long long nb) {
-  const size_t x = (size_t)a, y = (size_t)b;
-  return x < y + (size_t)nb && y < x + (size_t)na;
-}
-
 }  // namespace
 
 extern "C" int ifseg_strong_blur_table(int* out) {
@@ -226,7 +197,7 @@ extern "C" int ifseg_strong_draw(int B, unsigned long long seed, long long first
   if (!records || ((size_t)records & 3)) return IFSEG_ERR_BAD_ARG;
   if (jitter_p8 < 0 || jitter_p8 > 256 || blur_p8 < 0 || blur_p8 > 256) return IFSEG_ERR_BAD_ARG;
   if (B < 1) return IFSEG_ERR_BAD_SHAPE;
-  if (first_ordinal < 0 || first_ordinal + (long long)B > (1ll << 32)) return IFSEG_ERR_BAD_ARG;
+  if (!ordinals_ok(first_ordinal, B)) return IFSEG_ERR_BAD_ARG;
   hipLaunchKernelGGL(strong_draw_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)stream, B, seed,
                      (unsigned long long)first_ordinal, jitter_p8, blur_p8, records);
   IFSEG_CHECK_LAUNCH();
@@ -242,8 +213,8 @@ extern "C" int ifseg_strong_apply(const int* records, const void* images, int B,
   const long long n = (long long)B * 3 * P * P;
   if (n >= (1ll << 31)) return IFSEG_ERR_BAD_SHAPE;
   // the blur reads neighbours: no in-place form
-  if (sg_overlaps(out, n * elem_bytes, images, n * elem_bytes) || sg_overlaps(out, n * elem_bytes, records, (long long)B * 64) ||
-      sg_overlaps(out, n * elem_bytes, lut, 3 * 256 * 4))
+  if (overlaps(out, n * elem_bytes, images, n * elem_bytes) || overlaps(out, n * elem_bytes, records, (long long)B * 64) ||
+      overlaps(out, n * elem_bytes, lut, 3 * 256 * 4))
     return IFSEG_ERR_BAD_ARG;
   int tiles_x, tiles_y;
   long long blocks;

@@ -5,8 +5,8 @@
 // the destination, so the tile's first and last pixel bound its source footprint; the footprint is staged in LDS where it fits
 // the buffer the host gave the launch and read from global memory otherwise.  Here: the tile decode, the two coordinate rules
 // and the footprint on top of them, everything the two uint8 kernels share (staging with aligned dwords, the pixel loop, the
-// plane stores), the label halo of the two kernels that look at a label's neighbours (render.hip, pseudo.hip), and the host's
-// grid / bound / staging-limit helpers.
+// plane stores, the NaN tile of a poisoned sample, which strong.hip stores too), the label halo of the two kernels that look at
+// a label's neighbours (render.hip, pseudo.hip), and the host's grid / bound / staging-limit helpers.
 #pragma once
 #include <algorithm>
 #include "common.h"
@@ -150,6 +150,23 @@ __device__ __forceinline__ void store_plane(bf16_t* out, long long e, bool ok, f
     else out[e] = (bf16_t)h;
   } else if (lane == 0) {
     out[e] = (bf16_t)h;                                                   // (any other odd element left with lane - 1)
+  }
+}
+
+// a poisoned sample (trainload.hip, strong.hip): NaN in the thread's four pixels of the three planes of an image of a
+// [B, 3, P, P] batch.  img0: the image's first element, plane = P P, x = min(X0 + lane, P - 1): the callers hold all three,
+// and taking theirs keeps the callers' register counts (recomputed here, the bf16 kernels needed one to three SGPRs more)
+template <typename T>
+__device__ __forceinline__ void store_nan_tile(T* out, long long img0, long long plane, int P, const Tile& t, int x) {
+  const int X0 = t.X0, Y0 = t.Y0, xend = t.xend, lane = t.lane, wave = t.wave;
+  const float nanv = __int_as_float(0x7fc00000);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int yr = Y0 + wave * 4 + j;
+    const bool ok = yr < P && X0 + lane < P;
+    const long long erow = img0 + (long long)min(yr, P - 1) * P;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) store_plane(out, erow + c * plane + x, ok, nanv, lane, x, xend);
   }
 }
 

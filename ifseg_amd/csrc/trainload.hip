@@ -18,6 +18,7 @@
 //                      A record that does not hold a P x P window (only a caller's own records can) poisons its sample: NaN
 //                      images and target -1, nothing is read through it.
 // No scratch buffer, static launch shapes, nothing read back.
+// The counter stream and the ordinal check: common.h; words 6..14 of a record, drawn and read back: photo.h; the NaN tile: tile.h.
 #include "tile.h"
 #include "photo.h"
 #include "../../include/ifseg_hip.h"
@@ -32,10 +33,14 @@ constexpr int TL_MAX_P = 4096;
 
 int g_tl_stage_limit = U8_STAGE_LIMIT;
 
-enum { R_NEW_H, R_NEW_W, R_OFF_H, R_OFF_W, R_K, R_FLIP, R_BRIGHT, R_CONTRAST, R_SAT, R_HUE, R_MODE, R_BETA, R_ALPHA_C, R_ALPHA_S,
-       R_DELTA, R_ZERO };
+constexpr unsigned TL_SLOT_PHOTO = 23;             // bit 0 of its first draw is the flip
+enum { R_NEW_H, R_NEW_W, R_OFF_H, R_OFF_W, R_K, R_FLIP, R_PHOTO, R_ZERO = 15 };      // R_PHOTO: photo.h's nine words
 
-__device__ __forceinline__ unsigned draw32(unsigned long long base, unsigned slot) { return (unsigned)(splitmix64(base + slot) >> 32); }
+// a record that holds no P x P window of its H0 x W0 source, or whose resize leaves the 31 bits of tile.h's integer rule
+__host__ __device__ __forceinline__ bool no_window(int nh, int nw, int offh, int offw, int H0, int W0, int P) {
+  return nh < P || nw < P || offh < 0 || offw < 0 || offh > nh - P || offw > nw - P || 2ll * H0 * nh >= (1ll << 31) ||
+         2ll * W0 * nw >= (1ll << 31);
+}
 
 __device__ __forceinline__ int remap_class(int x, int nseg, int raw) {
   if (raw) x = (x == 0 || x == 255) ? nseg : x - 1;
@@ -61,13 +66,13 @@ __global__ __launch_bounds__(256) void train_draw_kernel(const ifseg_train_src* 
   int* sxt = syt + P;                   // [P]
   const int b = blockIdx.y, k = blockIdx.x, tid = threadIdx.x;
   const ifseg_train_src s = tab[b];
-  const unsigned long long base = seed + ((first + (unsigned)b) << 32);
+  const unsigned long long base = stream_base(seed, first, b);
   const unsigned t0 = draw32(base, 0);
   const int ns = max(P, (int)(((unsigned long long)P * (((unsigned long long)lo2 << 32) + (unsigned long long)span2 * t0)) >> 33));
   int nh, nw;
   resized_size(s.H0, s.W0, ns, &nh, &nw);
-  const int oh = (int)__umulhi(draw32(base, 1 + 2 * k), (unsigned)(nh - P + 1));
-  const int ow = (int)__umulhi(draw32(base, 2 + 2 * k), (unsigned)(nw - P + 1));
+  const int oh = draw_below(base, 1 + 2 * k, (unsigned)(nh - P + 1));
+  const int ow = draw_below(base, 2 + 2 * k, (unsigned)(nw - P + 1));
   hist[tid] = 0;
   for (int i = tid; i < P; i += 256) {
     syt[i] = min((int)((long long)(oh + i) * s.H0 / nh), s.H0 - 1) * s.W0;
@@ -103,24 +108,13 @@ __global__ __launch_bounds__(256) void train_draw_kernel(const ifseg_train_src* 
   // the tenth arrival: `old` carries the nine other verdicts (distinct bits: the sum is their union)
   const int mask = (old | (ok << k)) & ((1 << TL_CANDIDATES) - 1);
   const int kk = mask ? __ffs(mask) - 1 : TL_CANDIDATES;
-  const unsigned bits = draw32(base, 23);
-  const int ph = (enable >> 1) & 1;
   rec[R_NEW_H] = nh;
   rec[R_NEW_W] = nw;
-  rec[R_OFF_H] = (int)__umulhi(draw32(base, 1 + 2 * kk), (unsigned)(nh - P + 1));
-  rec[R_OFF_W] = (int)__umulhi(draw32(base, 2 + 2 * kk), (unsigned)(nw - P + 1));
+  rec[R_OFF_H] = draw_below(base, 1 + 2 * kk, (unsigned)(nh - P + 1));
+  rec[R_OFF_W] = draw_below(base, 2 + 2 * kk, (unsigned)(nw - P + 1));
   rec[R_K] = kk;
-  rec[R_FLIP] = (enable & 1) & bits;
-  rec[R_BRIGHT] = ph & (bits >> 1);
-  rec[R_MODE] = (bits >> 2) & 1;
-  rec[R_CONTRAST] = ph & (bits >> 3);
-  rec[R_SAT] = ph & (bits >> 4);
-  rec[R_HUE] = ph & (bits >> 5);
-  // exact in fp32: integers below 2^24 times a power of two
-  rec[R_BETA] = __float_as_int((float)((int)(draw32(base, 24) >> 9) - (1 << 22)) * (1.f / 131072.f));
-  rec[R_ALPHA_C] = __float_as_int((float)((1 << 22) + (int)(draw32(base, 25) >> 9)) * (1.f / 8388608.f));
-  rec[R_ALPHA_S] = __float_as_int((float)((1 << 22) + (int)(draw32(base, 26) >> 9)) * (1.f / 8388608.f));
-  rec[R_DELTA] = (int)__umulhi(draw32(base, 27), 36u) - 18;
+  rec[R_FLIP] = (enable & 1) & draw32(base, TL_SLOT_PHOTO);
+  photo_draw(rec + R_PHOTO, base, TL_SLOT_PHOTO, (enable >> 1) & 1);
   rec[R_ZERO] = 0;
 }
 
@@ -133,33 +127,25 @@ __global__ __launch_bounds__(256) void train_load_kernel(const ifseg_train_src* 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* lut = reinterpret_cast<float*>(smem);
 
-  const auto [b, X0, Y0, xend, yend, lane, wave] = tile_decode(tiles_x, tiles_y, P, P);
+  const Tile t = tile_decode(tiles_x, tiles_y, P, P);
+  const auto [b, X0, Y0, xend, yend, lane, wave] = t;
   const ifseg_train_src s = tab[b];
   const int* rec = params + (long long)b * 16;
   const int H0 = s.H0, W0 = s.W0, nh = rec[R_NEW_H], nw = rec[R_NEW_W], offh = rec[R_OFF_H], offw = rec[R_OFF_W];
   const bool flip = rec[R_FLIP] != 0;
-  Photo ph;
-  ph.bright = rec[R_BRIGHT]; ph.contrast = rec[R_CONTRAST]; ph.sat = rec[R_SAT]; ph.hue = rec[R_HUE]; ph.mode = rec[R_MODE];
-  ph.delta = (rec[R_DELTA] % 180 + 180) % 180;
-  ph.beta = __int_as_float(rec[R_BETA]); ph.alpha_c = __int_as_float(rec[R_ALPHA_C]); ph.alpha_s = __int_as_float(rec[R_ALPHA_S]);
+  const Photo ph = photo_read(rec + R_PHOTO);               // not validated: any words make some chain, none an address
 
   const long long plane = (long long)P * P;
   long long* tgt = target + (long long)b * (plane + 1);
   if (blockIdx.x % (tiles_x * tiles_y) == 0 && threadIdx.x == 0) tgt[plane] = eos;
 
   const int x = min(X0 + lane, P - 1);
-  const bool bad = nh < P || nw < P || offh < 0 || offw < 0 || offh > nh - P || offw > nw - P || 2ll * H0 * nh >= (1ll << 31) ||
-                   2ll * W0 * nw >= (1ll << 31);                                 // workgroup-uniform
-  if (bad) {
-    const float nanv = __int_as_float(0x7fc00000);
+  if (no_window(nh, nw, offh, offw, H0, W0, P)) {           // workgroup-uniform
+    store_nan_tile(out, (long long)b * 3 * plane, plane, P, t, x);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int yr = Y0 + wave * 4 + j;
-      const bool ok = yr < P && X0 + lane < P;
-      const long long erow = (long long)b * 3 * plane + (long long)min(yr, P - 1) * P;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) store_plane(out, erow + c * plane + x, ok, nanv, lane, x, xend);
-      if (ok) tgt[(long long)yr * P + x] = -1;
+      if (yr < P && X0 + lane < P) tgt[(long long)yr * P + x] = -1;
     }
     return;
   }
@@ -209,8 +195,7 @@ __global__ __launch_bounds__(256) void train_plane_kernel(const ifseg_train_src*
   const int* rec = params + (long long)b * 16;
   const int H0 = s.H0, W0 = s.W0, nh = rec[R_NEW_H], nw = rec[R_NEW_W], offh = rec[R_OFF_H], offw = rec[R_OFF_W];
   const bool flip = rec[R_FLIP] != 0;
-  const bool bad = nh < P || nw < P || offh < 0 || offw < 0 || offh > nh - P || offw > nw - P || 2ll * H0 * nh >= (1ll << 31) ||
-                   2ll * W0 * nw >= (1ll << 31);                                 // workgroup-uniform
+  const bool bad = no_window(nh, nw, offh, offw, H0, W0, P);                     // workgroup-uniform
   const int x = X0 + lane;
   if (x >= xend) return;
   const unsigned char* src = (const unsigned char*)s.label;
@@ -248,14 +233,10 @@ int check_table(const ifseg_train_src* th, int B, bool want_images, long long ma
 
 // the records a caller holds in host memory (may be NULL): one that does not hold a P x P window is refused before the launch
 int check_records(const ifseg_train_src* th, const int* params_host, int B, int P) {
-  const long long lim = 1ll << 31;
   if (!params_host) return 0;
   for (int b = 0; b < B; ++b) {
     const int* r = params_host + 16 * b;
-    if (r[R_NEW_H] < P || r[R_NEW_W] < P || r[R_OFF_H] < 0 || r[R_OFF_W] < 0 || r[R_OFF_H] > r[R_NEW_H] - P ||
-        r[R_OFF_W] > r[R_NEW_W] - P)
-      return IFSEG_ERR_BAD_SHAPE;
-    if (2ll * th[b].H0 * r[R_NEW_H] >= lim || 2ll * th[b].W0 * r[R_NEW_W] >= lim) return IFSEG_ERR_BAD_SHAPE;
+    if (no_window(r[R_NEW_H], r[R_NEW_W], r[R_OFF_H], r[R_OFF_W], th[b].H0, th[b].W0, P)) return IFSEG_ERR_BAD_SHAPE;
   }
   return 0;
 }
@@ -268,7 +249,7 @@ extern "C" int ifseg_train_draw(const ifseg_train_src* table_host, const ifseg_t
   (void)hipGetLastError();
   if (!table_host || !table || !params || ((size_t)params & 3) || ((size_t)table & 7)) return IFSEG_ERR_BAD_ARG;
   if (nseg < 1 || nseg > 255 || ratio_lo2 < 0 || ratio_span2 < 0 || ratio_lo2 + ratio_span2 > 64) return IFSEG_ERR_BAD_ARG;
-  if (first_ordinal < 0 || first_ordinal + (long long)B > (1ll << 32)) return IFSEG_ERR_BAD_ARG;
+  if (!ordinals_ok(first_ordinal, B)) return IFSEG_ERR_BAD_ARG;
   if (B < 1 || B > 65535 || P < 16 || P % 16 || P > TL_MAX_P) return IFSEG_ERR_BAD_SHAPE;
   const long long max_short = std::max<long long>(P, ((long long)P * (ratio_lo2 + ratio_span2)) >> 1);
   if (int rc = check_table(table_host, B, false, max_short)) return rc;

@@ -742,7 +742,7 @@ def imfree_draw(seed, first_ordinal, B, l, r, nseg, shapes, coarse):
     word = first_ordinal if isinstance(first_ordinal, torch.Tensor) else None
     if word is not None:
         assert word.dtype == torch.int64 and word.numel() == 1
-    rc = lib().ifseg_imfree_draw(ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), c_ll(0 if word is not None else int(first_ordinal)),
+    rc = lib().ifseg_imfree_draw(_seed64(seed), c_ll(0 if word is not None else int(first_ordinal)),
                                  _ptr(word), c_int(B), c_int(l), c_int(r), c_int(nseg), _ptr(shapes), _ptr(coarse), _stream())
     _check(rc, "imfree_draw")
     return shapes, coarse
@@ -2000,6 +2000,56 @@ def seg_pamr(probs, image, iters=10, dilations=SEG_PAMR_DILATIONS, conf=False, p
 _image_luts = {}        # (mean, std, device) -> fp32 [3, 256] on the device; at most 16 entries
 
 
+# ------------------- the front of the device-side input path (imgload.hip, trainload.hip, mix.hip, strong.hip): each rule once
+def _hptr(t):                       # the address of a host tensor, or None
+    return None if t is None else c_void_p(t.data_ptr())
+
+
+def _seed64(seed):
+    return ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+
+def _ordinals(first_ordinal, B):                    # -> the first of B ordinals as an int: the stream's ordinal has 32 bits
+    first = int(first_ordinal)
+    assert B >= 1 and 0 <= first and first + B <= 2 ** 32, (first, B)
+    return first
+
+
+def _out(out, shape, dtype, dev, align=1, like=None):
+    """the tensor a wrapper writes into: allocated here (as `like`, a contiguous tensor of that shape, dtype and device,
+    where the caller has one: the cheaper call; else with the sizes unpacked, cheaper than a tuple), or the caller's, checked"""
+    if out is None:
+        return torch.empty_like(like) if like is not None else torch.empty(*shape, dtype=dtype, device=dev)
+    assert out.dtype == dtype and tuple(out.shape) == tuple(shape) and out.is_contiguous() and out.device == dev \
+        and (align == 1 or out.data_ptr() % align == 0), (out.dtype, tuple(out.shape), out.stride(), out.device, align)
+    return out
+
+
+def _records(records, B, dev):
+    assert records.is_cuda and records.device == dev and records.dtype == torch.int32 and tuple(records.shape) == (B, 16) \
+        and records.is_contiguous(), (records.device, records.dtype, tuple(records.shape), records.stride())
+    return records
+
+
+def _records_in(params, B, dev):
+    """records on the host or on the device -> (the device tensor, the host tensor the entry point checks first, or None)"""
+    host = None
+    if not params.is_cuda:
+        host = params.contiguous()
+        params = host.to(dev)
+    return _records(params.contiguous(), B, dev), host
+
+
+def _u8_batch(images_u8, dtype):
+    """uint8 [B, H0, W0, 3] (HWC, contiguous) and the output dtype of a loader -> (B, H0, W0)"""
+    assert images_u8.dtype == torch.uint8 and images_u8.dim() == 4 and images_u8.shape[-1] == 3 and images_u8.is_contiguous(), \
+        (images_u8.dtype, tuple(images_u8.shape), images_u8.stride())
+    B, H0, W0, _ = images_u8.shape
+    assert B >= 1 and H0 >= 1 and W0 >= 1, tuple(images_u8.shape)
+    assert dtype in (torch.float32, torch.bfloat16), dtype
+    return B, H0, W0
+
+
 def image_load(images_u8, oh, ow, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), reverse_channels=False, dtype=torch.float32,
                staging_bytes=None, out=None):
     """uint8 [B, H0, W0, 3] (HWC, contiguous, on the device) -> patch_images [B, 3, oh, ow] in `dtype` (fp32 or bf16): the
@@ -2009,20 +2059,13 @@ def image_load(images_u8, oh, ow, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), rev
     (x / 255 - mean) / std from a [3, 256] table built on the host.  `imageio.image_load_reference` is the specification.
     staging_bytes: size of the kernel's LDS staging buffer for this call (0: every tile reads global memory), None: the default;
     out: a contiguous [B, 3, oh, ow] tensor of `dtype` to write into."""
-    assert images_u8.dtype == torch.uint8 and images_u8.dim() == 4 and images_u8.shape[-1] == 3 and images_u8.is_contiguous(), \
-        (images_u8.dtype, tuple(images_u8.shape), images_u8.stride())
-    B, H0, W0, _ = images_u8.shape
+    B, H0, W0 = _u8_batch(images_u8, dtype)
     oh, ow = int(oh), int(ow)
-    assert B >= 1 and H0 >= 1 and W0 >= 1 and oh >= 1 and ow >= 1, (tuple(images_u8.shape), oh, ow)
-    assert dtype in (torch.float32, torch.bfloat16), dtype
+    assert oh >= 1 and ow >= 1, (tuple(images_u8.shape), oh, ow)
     assert images_u8.is_cuda, "device tensor required"
     dev = images_u8.device
     lut = _image_lut(mean, std, dev)
-    if out is None:
-        out = torch.empty(B, 3, oh, ow, dtype=dtype, device=dev)
-    else:
-        assert out.dtype == dtype and tuple(out.shape) == (B, 3, oh, ow) and out.is_contiguous() and out.device == dev, \
-            (out.dtype, tuple(out.shape), out.stride(), out.device)
+    out = _out(out, (B, 3, oh, ow), dtype, dev)
     with _staging(lib().ifseg_image_load_staging, staging_bytes):
         _check(lib().ifseg_image_load(_ptr(images_u8), c_int(B), c_int(H0), c_int(W0), c_int(oh), c_int(ow), _ptr(lut),
                                       c_int(1 if reverse_channels else 0), _ptr(out), c_int(out.element_size()), _stream()),
@@ -2039,12 +2082,8 @@ def image_load_windows(images_u8, oh, ow, crop, stride, mean=(0.5, 0.5, 0.5), st
     arguments as in `image_load`.  flip: the windows of the MIRRORED resized image, bit for bit the `slide_windows` slices of
     `image_load(...).flip(-1)` (mirrored after the resize, as mmseg does; not the unmirrored windows flipped: the last window
     of an axis is pulled back inside, so the starts are not symmetric)."""
-    assert images_u8.dtype == torch.uint8 and images_u8.dim() == 4 and images_u8.shape[-1] == 3 and images_u8.is_contiguous(), \
-        (images_u8.dtype, tuple(images_u8.shape), images_u8.stride())
-    B, H0, W0, _ = images_u8.shape
-    assert B >= 1 and H0 >= 1 and W0 >= 1, tuple(images_u8.shape)
+    B, H0, W0 = _u8_batch(images_u8, dtype)
     oh, ow, crop, stride, nw, ch, cw = _slide_geometry(oh, ow, crop, stride)
-    assert dtype in (torch.float32, torch.bfloat16), dtype
     assert images_u8.is_cuda, "device tensor required"
     dev = images_u8.device
     lut = _image_lut(mean, std, dev)
@@ -2104,13 +2143,9 @@ def train_draw(labels, P, nseg, seed, first_ordinal, ratio_range=(0.5, 2.0), pho
     B = len(labels)
     assert B >= 1
     host, table = table if table is not None else _train_table(None, labels)
-    if out is None:
-        out = torch.empty(B, 16, dtype=torch.int32, device=labels[0].device)
-    else:
-        assert out.dtype == torch.int32 and tuple(out.shape) == (B, 16) and out.is_contiguous() and out.device == labels[0].device
-    _check(lib().ifseg_train_draw(c_void_p(host.data_ptr()), _ptr(table), c_int(B), c_int(P), c_int(nseg),
-                                  c_int(1 if raw_labels else 0), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
-                                  c_ll(int(first_ordinal)), c_int(lo2), c_int(span2),
+    out = _out(out, (B, 16), torch.int32, labels[0].device)
+    _check(lib().ifseg_train_draw(_hptr(host), _ptr(table), c_int(B), c_int(P), c_int(nseg),
+                                  c_int(1 if raw_labels else 0), _seed64(seed), c_ll(int(first_ordinal)), c_int(lo2), c_int(span2),
                                   c_int((1 if flip else 0) | (2 if photometric else 0)), _ptr(out), _stream()), "train_draw")
     return out
 
@@ -2125,25 +2160,13 @@ def train_load(images, labels, params, P, nseg, seg_id_offset, mean=(0.5, 0.5, 0
     B = len(images)
     assert B >= 1 and len(labels) == B and dtype in (torch.float32, torch.bfloat16), (B, len(labels), dtype)
     dev = labels[0].device
-    assert params.dtype == torch.int32 and tuple(params.shape) == (B, 16), (params.dtype, tuple(params.shape))
-    params_host = None
-    if not params.is_cuda:
-        params_host = params.contiguous()
-        params = params_host.to(dev)
-    params = params.contiguous()
+    params, params_host = _records_in(params, B, dev)
     lut = _image_lut(mean, std, dev)
     host, table = table if table is not None else _train_table(images, labels)
-    if out is None:
-        out = torch.empty(B, 3, P, P, dtype=dtype, device=dev)
-    else:
-        assert out.dtype == dtype and tuple(out.shape) == (B, 3, P, P) and out.is_contiguous() and out.device == dev
-    if target is None:
-        target = torch.empty(B, P * P + 1, dtype=torch.int64, device=dev)
-    else:
-        assert target.dtype == torch.int64 and tuple(target.shape) == (B, P * P + 1) and target.is_contiguous() and target.device == dev
+    out = _out(out, (B, 3, P, P), dtype, dev)
+    target = _out(target, (B, P * P + 1), torch.int64, dev)
     with _staging(lib().ifseg_train_load_staging, staging_bytes):
-        _check(lib().ifseg_train_load(c_void_p(host.data_ptr()), _ptr(table), _ptr(params),
-                                      c_void_p(params_host.data_ptr()) if params_host is not None else None, c_int(B), c_int(P),
+        _check(lib().ifseg_train_load(_hptr(host), _ptr(table), _ptr(params), _hptr(params_host), c_int(B), c_int(P),
                                       c_int(nseg), c_int(1 if raw_labels else 0), c_ll(seg_id_offset), c_ll(eos), _ptr(lut),
                                       c_int(1 if reverse_channels else 0), _ptr(out), c_int(out.element_size()), _ptr(target),
                                       _stream()), "train_load")
@@ -2159,23 +2182,13 @@ def train_load_plane(planes, params, P, out=None, table=None):
     B = len(planes)
     assert B >= 1
     dev = planes[0].device
-    assert params.dtype == torch.int32 and tuple(params.shape) == (B, 16), (params.dtype, tuple(params.shape))
-    params_host = None
-    if not params.is_cuda:
-        params_host = params.contiguous()
-        params = params_host.to(dev)
-    params = params.contiguous()
+    params, params_host = _records_in(params, B, dev)
     host, table = table if table is not None else _train_table(None, planes)
     assert host.shape[0] == B, (tuple(host.shape), B)
     P = int(P)
-    if out is None:
-        out = torch.empty(B, P * P, dtype=torch.uint8, device=dev)
-    else:
-        assert out.dtype == torch.uint8 and tuple(out.shape) == (B, P * P) and out.is_contiguous() and out.device == dev, \
-            (out.dtype, tuple(out.shape), out.stride(), out.device)
-    _check(lib().ifseg_train_load_plane(c_void_p(host.data_ptr()), _ptr(table), _ptr(params),
-                                        c_void_p(params_host.data_ptr()) if params_host is not None else None, c_int(B),
-                                        c_int(P), _ptr(out), _stream()), "train_load_plane")
+    out = _out(out, (B, P * P), torch.uint8, dev)
+    _check(lib().ifseg_train_load_plane(_hptr(host), _ptr(table), _ptr(params), _hptr(params_host), c_int(B), c_int(P),
+                                        _ptr(out), _stream()), "train_load_plane")
     return out
 
 
@@ -2200,16 +2213,11 @@ def mix_draw(src_target, nseg, seg_id_offset, seed, first_ordinal, mask="class",
     B, P = _mix_target(src_target, "mix_draw")
     assert isinstance(nseg, int) and 1 <= nseg <= 255, nseg
     assert mask in MIX_MASKS, mask
-    first = int(first_ordinal)
-    assert 0 <= first and first + B <= 2 ** 32, (first, B)
-    if out is None:
-        out = torch.empty(B, 16, dtype=torch.int32, device=src_target.device)
-    else:
-        assert out.dtype == torch.int32 and tuple(out.shape) == (B, 16) and out.is_contiguous() and out.device == src_target.device \
-            and not _overlap(out, src_target), (out.dtype, tuple(out.shape), out.stride(), out.device)
-    _check(lib().ifseg_mix_draw(_ptr(src_target), c_int(B), c_int(P), c_int(nseg), c_ll(int(seg_id_offset)),
-                                ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), c_ll(first), c_int(MIX_MASKS[mask]), _ptr(out),
-                                _stream()), "mix_draw")
+    first = _ordinals(first_ordinal, B)
+    assert out is None or not _overlap(out, src_target), (out.data_ptr(), src_target.data_ptr())
+    out = _out(out, (B, 16), torch.int32, src_target.device)
+    _check(lib().ifseg_mix_draw(_ptr(src_target), c_int(B), c_int(P), c_int(nseg), c_ll(int(seg_id_offset)), _seed64(seed),
+                                c_ll(first), c_int(MIX_MASKS[mask]), _ptr(out), _stream()), "mix_draw")
     return out
 
 
@@ -2225,8 +2233,7 @@ def mix_apply(records, src_images, src_target, dst_images, dst_target, nseg, seg
     dev, n = src_target.device, P * P
     assert _mix_target(dst_target, "mix_apply") == (B, P) and dst_target.device == dev, (tuple(src_target.shape), tuple(dst_target.shape))
     assert isinstance(nseg, int) and 1 <= nseg <= 255, nseg
-    assert records.is_cuda and records.device == dev and records.dtype == torch.int32 and tuple(records.shape) == (B, 16) \
-        and records.is_contiguous(), (records.device, records.dtype, tuple(records.shape))
+    _records(records, B, dev)
     assert src_images.dtype in (torch.float32, torch.bfloat16) and src_images.dtype == dst_images.dtype, (src_images.dtype, dst_images.dtype)
     assert B * 3 * n < 2 ** 31, (B, P)
     for t in (src_images, dst_images):
@@ -2236,17 +2243,11 @@ def mix_apply(records, src_images, src_target, dst_images, dst_target, nseg, seg
         assert t is None or (t.device == dev and t.dtype == torch.uint8 and tuple(t.shape) == (B, n) and t.is_contiguous()
                              and t.data_ptr() % 8 == 0), (t.device, t.dtype, tuple(t.shape), t.stride())
     weighted = src_weight is not None or dst_weight is not None
-    if out is None:
-        out = (torch.empty_like(dst_images), torch.empty_like(dst_target),
-               torch.empty(B, n, dtype=torch.uint8, device=dev) if weighted else None)
-    oi, ot, ow = out
-    assert oi.dtype == dst_images.dtype and oi.shape == dst_images.shape and oi.is_contiguous() and oi.device == dev \
-        and oi.data_ptr() % 16 == 0, (oi.dtype, tuple(oi.shape), oi.stride(), oi.device)
-    assert ot.dtype == torch.int64 and ot.shape == dst_target.shape and ot.is_contiguous() and ot.device == dev \
-        and ot.data_ptr() % 8 == 0, (ot.dtype, tuple(ot.shape), ot.stride(), ot.device)
-    assert (ow is not None) == weighted, "mix_apply: a weight plane comes out exactly when one goes in"
-    assert ow is None or (ow.dtype == torch.uint8 and tuple(ow.shape) == (B, n) and ow.is_contiguous() and ow.device == dev
-                          and ow.data_ptr() % 8 == 0), (ow.dtype, tuple(ow.shape), ow.stride(), ow.device)
+    oi, ot, ow = out if out is not None else (None, None, None)
+    assert out is None or (ow is not None) == weighted, "mix_apply: a weight plane comes out exactly when one goes in"
+    oi = _out(oi, dst_images.shape, dst_images.dtype, dev, 16, dst_images)
+    ot = _out(ot, dst_target.shape, torch.int64, dev, 8, dst_target)
+    ow = _out(ow, (B, n), torch.uint8, dev, 8) if weighted else None
     outs, dsts = (oi, ot, ow), (dst_images, dst_target, dst_weight)
     for i, o in enumerate(outs):
         if o is None:
@@ -2277,18 +2278,14 @@ def strong_draw(B, seed, first_ordinal, jitter_p8=205, blur_p8=128, device=None,
     """records int32 [B, 16] of the strong augmentation for the samples at ordinals first_ordinal + b, one launch
     (csrc/strong.hip; `augment.strong_draw_reference` is the specification and states the rule).  jitter_p8 / blur_p8: the
     two gates in 256ths, 0 never fires and 256 always does."""
-    B, first = int(B), int(first_ordinal)
-    assert B >= 1 and 0 <= first and first + B <= 2 ** 32, (first, B)
+    B = int(B)
+    first = _ordinals(first_ordinal, B)
     assert isinstance(jitter_p8, int) and isinstance(blur_p8, int) and 0 <= jitter_p8 <= 256 and 0 <= blur_p8 <= 256, (jitter_p8, blur_p8)
-    if out is None:
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        out = torch.empty(B, 16, dtype=torch.int32, device=dev)
-    else:
-        assert out.is_cuda and out.dtype == torch.int32 and tuple(out.shape) == (B, 16) and out.is_contiguous() \
-            and (device is None or out.device == torch.device(device)), (out.dtype, tuple(out.shape), out.stride(), out.device)
+    here = out.device if out is not None else torch.device("cuda", torch.cuda.current_device())
+    out = _out(out, (B, 16), torch.int32, here if device is None else torch.device(device))
     with torch.cuda.device(out.device):
-        _check(lib().ifseg_strong_draw(c_int(B), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), c_ll(first), c_int(jitter_p8),
-                                       c_int(blur_p8), _ptr(out), _stream()), "strong_draw")
+        _check(lib().ifseg_strong_draw(c_int(B), _seed64(seed), c_ll(first), c_int(jitter_p8), c_int(blur_p8), _ptr(out),
+                                       _stream()), "strong_draw")
     return out
 
 
@@ -2303,20 +2300,15 @@ def strong_apply(records, images, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), rev
         (images.device, images.dtype, tuple(images.shape), images.stride())
     B, P, dev = images.shape[0], images.shape[2], images.device
     assert B >= 1 and P >= 16 and P % 16 == 0 and P <= STRONG_MAX_P and B * 3 * P * P < 2 ** 31, (B, P)
-    assert records.is_cuda and records.device == dev and records.dtype == torch.int32 and tuple(records.shape) == (B, 16) \
-        and records.is_contiguous(), (records.device, records.dtype, tuple(records.shape))
+    _records(records, B, dev)
     assert len(tuple(std)) == 3 and all(float(s) > 0 for s in std), "strong_apply: std must be > 0 (the table must increase): %r" % (std,)
     if lut is None:
         lut = _image_lut(mean, std, dev)
     assert lut.device == dev and lut.dtype == torch.float32 and tuple(lut.shape) == (3, 256) and lut.is_contiguous(), \
         (lut.device, lut.dtype, tuple(lut.shape))
-    if out is None:
-        out = torch.empty_like(images)
-    else:
-        assert out.dtype == images.dtype and out.shape == images.shape and out.is_contiguous() and out.device == dev \
-            and out.data_ptr() % 16 == 0, (out.dtype, tuple(out.shape), out.stride(), out.device)
-        for t in (images, records, lut):
-            assert not _overlap(out, t), "strong_apply: out shares memory with the images, the records or the table (no in-place form)"
+    for t in (images, records, lut):
+        assert out is None or not _overlap(out, t), "strong_apply: out shares memory with the images, the records or the table (no in-place form)"
+    out = _out(out, images.shape, images.dtype, dev, 16, images)
     _check(lib().ifseg_strong_apply(_ptr(records), _ptr(images), c_int(B), c_int(P), c_int(images.element_size()), _ptr(lut),
                                     c_int(1 if reverse_channels else 0), _ptr(out), _stream()), "strong_apply")
     return out

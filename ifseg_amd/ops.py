@@ -42,6 +42,7 @@ CutMix of a labelled batch into a pseudo-labelled one -- the choice of classes o
 and weight planes, which copies bits) and `strong_draw` / `strong_apply` (csrc/strong.hip: colour jitter and Gaussian blur of a
 mixed batch's images, integer between input and output).
 """
+import contextlib
 from typing import Optional, Sequence, Tuple
 
 import torch
@@ -1626,8 +1627,20 @@ def _(scores, hpws, wpws, ohs, ows, flips, crop, stride, gt, softmax, raw_labels
             s.new_empty((B, n, h, w) if want_probs else (0,), dtype=f32))
 
 
+# --------------------------------------------- the training input path (train_load, mix_*, strong_*): what its ops share
+@contextlib.contextmanager
+def _on_stream(where):
+    """the kernels inside run on PyTorch's current stream of a tensor's device, or of the device itself"""
+    prev = hip.set_stream(torch.cuda.current_stream(where.device if torch.is_tensor(where) else where).cuda_stream)
+    try:
+        yield
+    finally:
+        hip.set_stream(prev)
+
+
 # ----------------------------------------------------------------------------------------------- train_load
 def _train_load_check(images, labels, params, P, nseg, mean, std, dtype):
+    from .augment import check_records
     op = "ifseg::train_load"
     B = len(images)
     if B == 0 or len(labels) != B:
@@ -1640,8 +1653,7 @@ def _train_load_check(images, labels, params, P, nseg, mean, std, dtype):
                              % (op, lab.dtype, tuple(lab.shape), tuple(img.shape)))
         if img.shape[0] * img.shape[1] * 3 >= 2 ** 31:
             raise ValueError("%s: H0 * W0 * 3 must stay below 2**31, got %s" % (op, tuple(img.shape)))
-    if params.dtype != torch.int32 or tuple(params.shape) != (B, 16):
-        raise ValueError("%s: params must be int32 [%d, 16], got %s %s" % (op, B, params.dtype, tuple(params.shape)))
+    check_records(params, B, op, "params")
     if P < 16 or P % 16 or P > 4096 or B * 3 * P * P >= 2 ** 31:
         raise ValueError("%s: P must be a multiple of 16 in 16 .. 4096 with B * 3 * P * P < 2**31, got P = %d, B = %d" % (op, P, B))
     if not 1 <= nseg <= 255:
@@ -1661,12 +1673,9 @@ def train_load(images: Sequence[torch.Tensor], labels: Sequence[torch.Tensor], p
     specification): uint8 images [H0, W0, 3] and label maps [H0, W0] of any sizes, params int32 [B, 16] ->
     (patch_images [B, 3, P, P] in `dtype`, target int64 [B, P*P + 1]).  Integer inputs: not differentiable."""
     _train_load_check(images, labels, params, P, nseg, mean, std, dtype)
-    prev = _stream_scope(params)
-    try:
+    with _on_stream(params):
         return hip.train_load([t.contiguous() for t in images], [t.contiguous() for t in labels], params.contiguous(), P, nseg,
                               seg_id_offset, mean, std, reverse_channels, raw_labels, dtype)
-    finally:
-        hip.set_stream(prev)
 
 
 @train_load.register_fake
@@ -1677,13 +1686,12 @@ def _(images, labels, params, P, nseg, seg_id_offset, mean, std, reverse_channel
 
 # ----------------------------------------------------------------------------------------------- mix_draw / mix_apply
 def _mix_draw_check(src_target, nseg, first_ordinal, mask):
-    from .augment import check_mix, mix_patch_size
+    from .augment import check_mix, check_ordinals, mix_patch_size
     op = "ifseg::mix_draw"
     P = mix_patch_size(src_target, op)
     check_mix(P, nseg, mask, op)
     B = src_target.shape[0]
-    if first_ordinal < 0 or first_ordinal + B > 2 ** 32:
-        raise ValueError("%s: ordinals must lie in [0, 2**32), got %d .. %d" % (op, first_ordinal, first_ordinal + B - 1))
+    check_ordinals(first_ordinal, B, op)
     return B
 
 
@@ -1693,11 +1701,8 @@ def mix_draw(src_target: torch.Tensor, nseg: int, seg_id_offset: int, seed: int,
     src_target int64 [B, P*P + 1], mask "class" (ClassMix) or "box" (CutMix); a pure function of (seed, first_ordinal + b) and,
     for "class", of the classes present in sample b.  Integer inputs: not differentiable."""
     _mix_draw_check(src_target, nseg, first_ordinal, mask)
-    prev = _stream_scope(src_target)
-    try:
+    with _on_stream(src_target):
         return hip.mix_draw(src_target.contiguous(), nseg, seg_id_offset, seed, first_ordinal, mask)
-    finally:
-        hip.set_stream(prev)
 
 
 @mix_draw.register_fake
@@ -1707,12 +1712,11 @@ def _(src_target, nseg, seg_id_offset, seed, first_ordinal, mask):
 
 
 def _mix_apply_check(records, src_images, src_target, src_weight, dst_images, dst_target, dst_weight, nseg):
-    from .augment import check_mix, check_mix_batches
+    from .augment import check_mix, check_mix_batches, check_records
     op = "ifseg::mix_apply"
     B, P = check_mix_batches(src_images, src_target, src_weight, dst_images, dst_target, dst_weight, op)
     check_mix(P, nseg, what=op)
-    if records.dtype != torch.int32 or tuple(records.shape) != (B, 16):
-        raise ValueError("%s: records must be int32 [%d, 16], got %s %s" % (op, B, records.dtype, tuple(records.shape)))
+    check_records(records, B, op)
     if B * 3 * P * P >= 2 ** 31:
         raise ValueError("%s: B * 3 * P * P must stay below 2**31, got B = %d, P = %d" % (op, B, P))
     return B, P
@@ -1727,14 +1731,11 @@ def mix_apply(records: torch.Tensor, src_images: torch.Tensor, src_target: torch
     (images [B, 3, P, P], target int64 [B, P*P + 1], weight uint8 [B, P*P] -- an empty tensor when neither batch has a plane).
     A copy of bits: not differentiable."""
     _mix_apply_check(records, src_images, src_target, src_weight, dst_images, dst_target, dst_weight, nseg)
-    prev = _stream_scope(records)
-    try:
+    with _on_stream(records):
         c = lambda t: None if t is None else t.contiguous()
         img, tgt, wgt = hip.mix_apply(records.contiguous(), c(src_images), c(src_target), c(dst_images), c(dst_target), nseg,
                                       seg_id_offset, src_weight=c(src_weight), dst_weight=c(dst_weight))
         return img, tgt, torch.empty(0, dtype=torch.uint8, device=records.device) if wgt is None else wgt
-    finally:
-        hip.set_stream(prev)
 
 
 @mix_apply.register_fake
@@ -1747,11 +1748,10 @@ def _(records, src_images, src_target, src_weight, dst_images, dst_target, dst_w
 
 # ----------------------------------------------------------------------------------------------- strong_draw / strong_apply
 def _strong_draw_check(B, first_ordinal, jitter_p8, blur_p8):
-    from .augment import check_strong
+    from .augment import check_ordinals, check_strong
     op = "ifseg::strong_draw"
     check_strong(16, jitter_p8=jitter_p8, blur_p8=blur_p8, what=op)
-    if B < 1 or first_ordinal < 0 or first_ordinal + B > 2 ** 32:
-        raise ValueError("%s: B >= 1 and ordinals in [0, 2**32), got %d .. %d" % (op, first_ordinal, first_ordinal + B - 1))
+    check_ordinals(first_ordinal, B, op)
     return B
 
 
@@ -1761,11 +1761,8 @@ def strong_draw(B: int, seed: int, first_ordinal: int, jitter_p8: int, blur_p8: 
     specification): a pure function of (seed, first_ordinal + b) and the two gates.  No tensor goes in: `device` says where
     the records are written.  Not differentiable."""
     _strong_draw_check(B, first_ordinal, jitter_p8, blur_p8)
-    prev = hip.set_stream(torch.cuda.current_stream(device).cuda_stream)
-    try:
+    with _on_stream(device):
         return hip.strong_draw(B, seed, first_ordinal, jitter_p8, blur_p8, device=device)
-    finally:
-        hip.set_stream(prev)
 
 
 @strong_draw.register_fake
@@ -1775,12 +1772,11 @@ def _(B, seed, first_ordinal, jitter_p8, blur_p8, device):
 
 
 def _strong_apply_check(records, images, mean, std):
-    from .augment import check_strong, check_strong_images
+    from .augment import check_records, check_strong, check_strong_images
     op = "ifseg::strong_apply"
     B, P = check_strong_images(images, op)
     check_strong(P, mean, std, what=op)
-    if records.dtype != torch.int32 or tuple(records.shape) != (B, 16):
-        raise ValueError("%s: records must be int32 [%d, 16], got %s %s" % (op, B, records.dtype, tuple(records.shape)))
+    check_records(records, B, op)
     return B, P
 
 
@@ -1791,11 +1787,8 @@ def strong_apply(records: torch.Tensor, images: torch.Tensor, mean: Sequence[flo
     `augment.strong_apply_reference` is the specification) -> images of the same shape and dtype.  Integer between the
     input and the output: not differentiable."""
     _strong_apply_check(records, images, mean, std)
-    prev = _stream_scope(images)
-    try:
+    with _on_stream(images):
         return hip.strong_apply(records.contiguous(), images.contiguous(), mean, std, reverse_channels)
-    finally:
-        hip.set_stream(prev)
 
 
 @strong_apply.register_fake
