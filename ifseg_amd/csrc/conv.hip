@@ -10,6 +10,13 @@ namespace {
 constexpr int ST_TH = 8, ST_TW = 32;                 // output tile per block (256 pixels)
 constexpr int ST_PH = (ST_TH - 1) * 2 + 7, ST_PW = (ST_TW - 1) * 2 + 7;  // 21 x 69 input patch
 
+// NON-FINITE VALUES pass as torch.relu and F.max_pool2d pass them.  max_nan is the IEEE 754-2019 `maximum`, which returns NaN if
+// either operand is NaN (fmaxf returns the other operand, and turned the NaN image of a poisoned sample into a plausible
+// all-zero feature map); on gfx950 it is ONE VALU operation, v_maximum3_f32, in the place of the v_max_f32 of fmaxf.  A compare
+// and a select instead (x <= 0 ? 0 : x) cost the matrix-core kernel 9 % (101.9 -> 110.3 us at 16 x 512 x 512).
+// relu(NaN) = NaN, relu(+inf) = +inf, relu(-inf) = relu(-0) = +0; a pool window that holds a NaN gives NaN.
+__device__ __forceinline__ float max_nan(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+
 // in: NHWC bf16 with C padded to 4; w: fp32 [7*7*3][64] (BN scale folded); shift fp32 [64]
 __global__ __launch_bounds__(256) void stem_conv_kernel(const bf16_t* in, const float* w, const float* shift,
                                                         bf16_t* out, int B, int H, int W, int OH, int OW) {
@@ -58,7 +65,7 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const bf16_t* in, const 
     for (int c = 0; c < 64; c += 8) {
       float o[8];
 #pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] = fmaxf(acc[c + e] + shift[c + e], 0.f);
+      for (int e = 0; e < 8; ++e) o[e] = max_nan(acc[c + e] + shift[c + e], 0.f);
       *reinterpret_cast<uint4*>(op + c) =
           make_uint4(pack2bf(o[0], o[1]), pack2bf(o[2], o[3]), pack2bf(o[4], o[5]), pack2bf(o[6], o[7]));
     }
@@ -159,7 +166,7 @@ __global__ __launch_bounds__(256) void stem_conv_mfma_kernel(const bf16_t* in, c
         for (int rg = 0; rg < 4; ++rg) {
           float o[4];
 #pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = fmaxf(acc[i][ct][rg * 4 + e] + sh[ct][rg][e], 0.f);
+          for (int e = 0; e < 4; ++e) o[e] = max_nan(acc[i][ct][rg * 4 + e] + sh[ct][rg][e], 0.f);
           *reinterpret_cast<uint2*>(op + ct * 32 + 8 * rg) = make_uint2(pack2bf(o[0], o[1]), pack2bf(o[2], o[3]));
         }
     }
@@ -185,22 +192,30 @@ __global__ void maxpool3x3s2_kernel(const bf16_t* in, bf16_t* out, int B, int H,
       const int ix = ox * 2 - 1 + kx;
       if (ix < 0 || ix >= W) continue;
       uint4 u = *reinterpret_cast<const uint4*>(in + (((long long)b * H + iy) * W + ix) * C + c * 8);
-      m[0] = fmaxf(m[0], bflo(u.x)); m[1] = fmaxf(m[1], bfhi(u.x)); m[2] = fmaxf(m[2], bflo(u.y));
-      m[3] = fmaxf(m[3], bfhi(u.y)); m[4] = fmaxf(m[4], bflo(u.z)); m[5] = fmaxf(m[5], bfhi(u.z));
-      m[6] = fmaxf(m[6], bflo(u.w)); m[7] = fmaxf(m[7], bfhi(u.w));
+      m[0] = max_nan(m[0], bflo(u.x)); m[1] = max_nan(m[1], bfhi(u.x)); m[2] = max_nan(m[2], bflo(u.y));
+      m[3] = max_nan(m[3], bfhi(u.y)); m[4] = max_nan(m[4], bflo(u.z)); m[5] = max_nan(m[5], bfhi(u.z));
+      m[6] = max_nan(m[6], bflo(u.w)); m[7] = max_nan(m[7], bfhi(u.w));
     }
   }
   *reinterpret_cast<uint4*>(out + p * C + c * 8) =
       make_uint4(pack2bf(m[0], m[1]), pack2bf(m[2], m[3]), pack2bf(m[4], m[5]), pack2bf(m[6], m[7]));
 }
 
+// what the three entries refuse before any launch: a workgroup count or an element count (in, out) beyond 31 bits
+bool fits31(long long v) { return v > 0 && v <= 0x7fffffffLL; }
+
 }  // namespace
 
 extern "C" int ifseg_stem_conv7x7(const void* in_nhwc4, const float* w, const float* shift, void* out, int B, int H,
                                   int W, void* stream) {
   (void)hipGetLastError();
+  // in_nhwc4 is read as uint2, out written as uint4
+  if (!in_nhwc4 || !w || !shift || !out || B <= 0 || H <= 0 || W <= 0 || ((size_t)in_nhwc4 & 7) || (((size_t)w | (size_t)shift) & 3) ||
+      ((size_t)out & 15))
+    return IFSEG_ERR_BAD_ARG;
   const int OH = (H + 6 - 7) / 2 + 1, OW = (W + 6 - 7) / 2 + 1;
   const int tiles = ((OH + ST_TH - 1) / ST_TH) * ((OW + ST_TW - 1) / ST_TW);
+  if (!fits31((long long)B * tiles) || !fits31((long long)B * H * W * 4) || !fits31((long long)B * OH * OW * 64)) return IFSEG_ERR_BAD_SHAPE;
   const size_t lds = (147 * 64 + ST_PH * ST_PW * 3) * sizeof(float);
   (void)hipFuncSetAttribute((const void*)stem_conv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL(stem_conv_kernel, dim3(B * tiles), dim3(256), lds, (hipStream_t)stream, (const bf16_t*)in_nhwc4,
@@ -212,9 +227,14 @@ extern "C" int ifseg_stem_conv7x7(const void* in_nhwc4, const float* w, const fl
 extern "C" int ifseg_stem_conv7x7_mfma(const void* in_nhwc4, const void* wt, const float* shift, void* out, int B, int H,
                                        int W, void* stream) {
   (void)hipGetLastError();
-  if (!in_nhwc4 || !wt || !shift || !out || B <= 0 || H <= 0 || W <= 0 || (((size_t)wt | (size_t)shift | (size_t)out) & 15)) return IFSEG_ERR_BAD_ARG;
+  // in_nhwc4 is read as uint2; wt, shift as 16-byte vectors
+  if (!in_nhwc4 || !wt || !shift || !out || B <= 0 || H <= 0 || W <= 0 || (((size_t)wt | (size_t)shift | (size_t)out) & 15) ||
+      ((size_t)in_nhwc4 & 7))
+    return IFSEG_ERR_BAD_ARG;
   const int OH = (H + 6 - 7) / 2 + 1, OW = (W + 6 - 7) / 2 + 1;
-  const int total = B * ((OH + ST_TH - 1) / ST_TH) * ((OW + ST_TW - 1) / ST_TW);
+  const long long tiles = (long long)B * ((OH + ST_TH - 1) / ST_TH) * ((OW + ST_TW - 1) / ST_TW);
+  if (!fits31(tiles) || !fits31((long long)B * H * W * 4) || !fits31((long long)B * OH * OW * 64)) return IFSEG_ERR_BAD_SHAPE;
+  const int total = (int)tiles;
   const int grid = total < 1024 ? total : 1024;
   hipLaunchKernelGGL(stem_conv_mfma_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)in_nhwc4,
                      (const bf16_t*)wt, shift, (bf16_t*)out, B, H, W, OH, OW);
@@ -224,9 +244,11 @@ extern "C" int ifseg_stem_conv7x7_mfma(const void* in_nhwc4, const void* wt, con
 
 extern "C" int ifseg_maxpool3x3s2(const void* in, void* out, int B, int H, int W, int C, void* stream) {
   (void)hipGetLastError();
+  if (!in || !out || B <= 0 || H <= 0 || W <= 0 || C <= 0 || (((size_t)in | (size_t)out) & 15)) return IFSEG_ERR_BAD_ARG;
   if (C & 7) return IFSEG_ERR_BAD_SHAPE;
   const int OH = (H + 2 - 3) / 2 + 1, OW = (W + 2 - 3) / 2 + 1;
   const long long total = (long long)B * OH * OW * (C / 8);
+  if (!fits31((long long)B * H * W * C) || !fits31(total)) return IFSEG_ERR_BAD_SHAPE;
   hipLaunchKernelGGL(maxpool3x3s2_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)in, (bf16_t*)out, B, H, W, C, OH, OW);
   IFSEG_CHECK_LAUNCH();

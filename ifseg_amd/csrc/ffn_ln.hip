@@ -183,7 +183,10 @@ extern "C" int ifseg_ffn_ln_coef(const void* const* w2, int ldw, const float* co
   if (!w2 || !gamma || !beta || !coef || L <= 0 || L > 32 || J <= 0 || N <= 0 || (N & 7) || (ldw & 7)) return IFSEG_ERR_BAD_ARG;
   FfnCoefPtrs pt{};
   for (int l = 0; l < L; ++l) {
-    if (!w2[l] || !gamma[l] || !beta[l] || !coef[l] || (((size_t)gamma[l] | (size_t)beta[l]) & 15)) return IFSEG_ERR_BAD_ARG;
+    // W2 rows, gamma and beta are read 16 bytes at a time
+    if (!w2[l] || !gamma[l] || !beta[l] || !coef[l] || (((size_t)w2[l] | (size_t)gamma[l] | (size_t)beta[l]) & 15) || ((size_t)coef[l] & 3) ||
+        (b2 && b2[l] && ((size_t)b2[l] & 1)))
+      return IFSEG_ERR_BAD_ARG;
     pt.w2[l] = (const bf16_t*)w2[l]; pt.gamma[l] = gamma[l]; pt.beta[l] = beta[l];
     pt.b2[l] = b2 ? (const bf16_t*)b2[l] : nullptr; pt.coef[l] = coef[l];
   }
@@ -195,7 +198,8 @@ extern "C" int ifseg_ffn_ln_coef(const void* const* w2, int ldw, const float* co
 extern "C" int ifseg_ffn_ln_rowstats(const void* dy, int lddy, const void* t, int ldt, const float* coef, float* c, int rows,
                                      int J, int N, void* stream) {
   (void)hipGetLastError();
-  if (!dy || !t || !coef || !c || rows <= 0 || J <= 0 || N <= 0 || (J & 7) || (lddy & 7) || (ldt & 7) || ((size_t)coef & 15))
+  if (!dy || !t || !coef || !c || rows <= 0 || J <= 0 || N <= 0 || (J & 7) || (lddy & 7) || (ldt & 7) ||
+      (((size_t)dy | (size_t)t | (size_t)coef) & 15) || ((size_t)c & 3))
     return IFSEG_ERR_BAD_ARG;
   hipLaunchKernelGGL(ffn_ln_rowstats_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy, lddy,
                      (const bf16_t*)t, ldt, coef, c, rows, J, 1.f / (float)N);
@@ -209,7 +213,8 @@ extern "C" int ifseg_ffn_ln_param_grads(const void* w2, const void* dw2, const v
                                         int M, void* stream) {
   (void)hipGetLastError();
   if (!w2 || !dw2 || !db2 || !gamma || !beta || !dgamma || !dbeta || !workspace || J <= 0 || N <= 0 || (N & 7)) return IFSEG_ERR_BAD_ARG;
-  if (dy && (!u || !mean || !rstd || M <= 0 || (J & 7) || J > 1024 || (lddy & 7))) return IFSEG_ERR_BAD_ARG;
+  if ((((size_t)w2 | (size_t)dw2) & 15) || (((size_t)gamma | (size_t)beta | (size_t)workspace) & 3)) return IFSEG_ERR_BAD_ARG;   // uint4 rows
+  if (dy && (!u || !mean || !rstd || M <= 0 || (J & 7) || J > 1024 || (lddy & 7) || ((size_t)dy & 15))) return IFSEG_ERR_BAD_ARG;
   hipLaunchKernelGGL(ffn_ln_pg_partial_kernel, dim3((N + 127) / 128, PG_SLABS), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)w2, (const bf16_t*)dw2, (const bf16_t*)db2, workspace, J, N);
   hipLaunchKernelGGL(ffn_ln_pg_final_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, workspace, gamma, beta,

@@ -916,8 +916,10 @@ extern "C" int ifseg_add_bf16(const void* a, const void* b, void* out, long long
 extern "C" int ifseg_nchw_to_nhwc_bf16(const void* in, int in_is_f32, void* out, int B, int C, int H, int W, int Cpad,
                                        void* stream) {
   (void)hipGetLastError();
+  if (!in || !out || B <= 0 || C <= 0 || H <= 0 || W <= 0 || Cpad < C || ((size_t)in & (in_is_f32 ? 3 : 1)) || ((size_t)out & 1))
+    return IFSEG_ERR_BAD_ARG;
   const long long total = (long long)B * H * W * Cpad;
-  if (total <= 0) return 0;
+  if (total > 0x7fffffffLL) return IFSEG_ERR_BAD_SHAPE;
   dim3 g((unsigned)((total + 255) / 256));
   if (in_is_f32) hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, g, dim3(256), 0, (hipStream_t)stream, (const float*)in, (bf16_t*)out, B, C, H, W, Cpad);
   else hipLaunchKernelGGL(nchw_to_nhwc_kernel<bf16_t>, g, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)in, (bf16_t*)out, B, C, H, W, Cpad);

@@ -90,7 +90,12 @@ int ifseg_gemm_nn_rowdot(const void* A, const void* B, void* C, int M, int N, in
  *   ifseg_gemm_nn_gelu_ln_bwd   C = du [M, N] (bf16) = rstd (gamma dz - c1 - xh c2) gelu'(u), dz = A . B in the accumulators
  *                           (A = dY [M, K = J], B = W2 [K, N]); dz never reaches HBM
  *   ifseg_ffn_ln_param_grads    dbeta_k = sum_j db2_j W2[j,k], dgamma_k = (sum_j W2[j,k] dW2[j,k] - beta_k dbeta_k) / gamma_k
- *                           from the (bf16) weight / bias gradient of fc2, written as bf16 */
+ *                           from the (bf16) weight / bias gradient of fc2, written as bf16
+ * Refused with IFSEG_ERR_BAD_ARG before any launch: a null pointer (b2, and dy with its operands, may be NULL), L outside
+ * 1..32, J, N, rows <= 0, N % 8, ldw % 8, (rowstats; param_grads with dy) J % 8, lddy % 8, ldt % 8, with dy J > 1024 or M <= 0,
+ * and a misaligned operand: 16 bytes for what is read 16 bytes at a time -- w2[l], gamma[l], beta[l] (coef); dy, t, coef
+ * (rowstats); w2, dw2 and dy (param_grads) --, the element's own size for the rest that is checked: 4 bytes for coef[l]
+ * (coef), c (rowstats), gamma, beta and workspace (param_grads), 2 bytes for b2[l].  Without dy, param_grads takes any J. */
 int ifseg_ffn_ln_coef(const void* const* w2, int ldw, const float* const* gamma, const float* const* beta,
                       const void* const* b2 /* bf16 [J] each, or NULL */, float* const* coef /* [2][J] each */,
                       int L /* layers in this launch (host arrays of L device pointers), <= 32 */, int J, int N, void* stream);
@@ -424,7 +429,9 @@ int ifseg_embed_bag_mean(const void* table, const long long* ids, const long lon
                          int B, int P, int C, int maxlen, int rpb, long long o_bs, int ldo, void* stream);
 int ifseg_cast_f32_bf16(const float* in, void* out, long long n, float scale, void* stream);
 int ifseg_add_bf16(const void* a, const void* b, void* out, long long n, void* stream);
-/* NCHW (fp32 / bf16) image -> NHWC bf16 with channels zero-padded to Cpad */
+/* NCHW (fp32 / bf16) image -> NHWC bf16 with channels zero-padded to Cpad (round to nearest even; -0, infinities and NaN are
+ * kept; the pad channels are +0).  Refused before any launch: a null or misaligned pointer, B, C, H or W <= 0, Cpad < C
+ * (IFSEG_ERR_BAD_ARG); B H W Cpad >= 2^31 (IFSEG_ERR_BAD_SHAPE). */
 int ifseg_nchw_to_nhwc_bf16(const void* in, int in_is_f32, void* out, int B, int C, int H, int W, int Cpad,
                             void* stream);
 
@@ -475,7 +482,17 @@ int ifseg_droppath_scale(float* out, const float* keep, int n, int B, unsigned l
 
 /* ------------------------------------------------------------ ResNet stem */
 /* conv1 7x7/2 (3->64) + folded FrozenBN + ReLU on an NHWC(4) bf16 image; w fp32
- * [7][7][3][64] with the BN scale folded, shift fp32 [64] (resnet.py:215-218). */
+ * [7][7][3][64] with the BN scale folded, shift fp32 [64] (resnet.py:215-218).
+ * Non-finite values pass as torch.relu and F.max_pool2d pass them (the ReLU and the pool use the IEEE 754-2019 maximum, one
+ * v_maximum3_f32): relu(NaN) = NaN, relu(+inf) = +inf, relu(-inf) = +0, and a pool window that holds a NaN gives NaN -- an image
+ * of NaNs (the poisoned sample of ifseg_train_load) leaves stem and pool as NaN.  The matrix-core kernel multiplies its zero
+ * weights (tap kx = 7: the input column 2 ox + 4, right of the window) with the patch as well: a NaN or an infinity in that
+ * column makes the output NaN too, and an infinity inside the window gives +inf only where all three weight terms are positive
+ * (inf * 0 and inf - inf are NaN).
+ * All three entries refuse, before any launch: a null pointer, B, H, W (pool: C) <= 0, a pointer the kernels' wide accesses
+ * need aligned -- in_nhwc4 8 bytes; out, wt and the matrix-core kernel's shift, the pool's in and out 16 bytes; w and
+ * the direct kernel's shift 4 bytes -- with IFSEG_ERR_BAD_ARG; C % 8 != 0, and an input, output or workgroup count of
+ * 2^31 or more with IFSEG_ERR_BAD_SHAPE. */
 int ifseg_stem_conv7x7(const void* in_nhwc4, const float* w, const float* shift, void* out, int B, int H, int W,
                        void* stream);
 /* The same on the matrix cores: wt bf16 [3][64][224], wt[0][c][ky*32 + kx*4 + ci] = bf16(w[ky][kx][ci][c]) (BN scale folded; the
