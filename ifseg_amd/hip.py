@@ -1908,6 +1908,115 @@ def seg_pseudo(labels, conf, thresholds, n, boundary=0, raw_labels=True, kept=No
     return out, kept
 
 
+# --------------------------------------------------------------------------- connected regions of a label map (csrc/regions.hip)
+SEG_REGION_MAX_CLASSES = 255        # == RG_MAX_CLASSES: the classes of seg_region_drop's counter, the values of a uint8 map
+
+
+def seg_regions_limits():
+    """-> (a tile's rows, a tile's columns, the largest n of the drop) as the loaded library states them
+    (`ifseg_seg_regions_limit`): 16, 64 and SEG_REGION_MAX_CLASSES, which the tests hold against it"""
+    return _limits("ifseg_seg_regions_limit", 3)
+
+
+def _region_maps(what, labels, connectivity, dtypes):
+    """what the region kernels ask of a label map, as ValueErrors that name the argument -> (B, H, W)"""
+    if not torch.is_tensor(labels) or labels.dtype not in dtypes:
+        raise ValueError("%s: labels must be a %s tensor, got %s" % (
+            what, " / ".join(str(d).replace("torch.", "") for d in dtypes), labels.dtype if torch.is_tensor(labels) else type(labels)))
+    if labels.dim() not in (2, 3) or not labels.is_contiguous() or not 1 <= labels.numel() < 2 ** 31:
+        raise ValueError("%s: labels must be contiguous [H, W] or [B, H, W] with 1 .. 2**31 - 1 pixels, got %s with strides %s"
+                         % (what, tuple(labels.shape), labels.stride()))
+    if not isinstance(connectivity, int) or isinstance(connectivity, bool) or connectivity not in (4, 8):
+        raise ValueError("%s: connectivity must be the int 4 or 8, got %r" % (what, connectivity))
+    H, W = labels.shape[-2:]
+    return labels.numel() // (H * W), int(H), int(W)
+
+
+def _region_plane(what, name, t, labels, dtype=torch.int32):
+    """an output plane of the labels' shape: the caller's, checked, or a fresh one"""
+    if t is None:
+        return torch.empty(labels.shape, dtype=dtype, device=labels.device)
+    if not torch.is_tensor(t) or t.dtype != dtype or t.shape != labels.shape or not t.is_contiguous() or t.device != labels.device:
+        raise ValueError("%s: %s must be a contiguous %s tensor of the labels' shape %s on %s, got %s" % (
+            what, name, str(dtype).replace("torch.", ""), tuple(labels.shape), labels.device,
+            (t.dtype, tuple(t.shape), t.stride(), t.device) if torch.is_tensor(t) else type(t)))
+    if _overlap(t, labels):
+        raise ValueError("%s: %s overlaps the labels" % (what, name))
+    return t
+
+
+def _region_flag(what, flag, dev):
+    if flag is None:
+        return torch.zeros(1, dtype=torch.int32, device=dev)
+    if not torch.is_tensor(flag) or flag.dtype != torch.int32 or flag.numel() != 1 or flag.device != dev:
+        raise ValueError("%s: flag must be an int32 tensor of one element on %s, got %s" % (
+            what, dev, (flag.dtype, tuple(flag.shape), flag.device) if torch.is_tensor(flag) else type(flag)))
+    return flag
+
+
+def seg_regions(labels, connectivity=4, root=None, size=None, flag=None):
+    """labels uint8 / int16 [H, W] or [B, H, W] -> (root, size), both int32 of the labels' shape (csrc/regions.hip;
+    `predict.regions_reference` is the specification and states the rule): root[p] = the smallest y W + x inside its image
+    over the pixels of p's connected region of equal values (connectivity 4 or 8), size[p] = the region's pixel count.  Four
+    launches on the current stream (three where an image is one 16 x 64 tile), nothing synchronises; the results are
+    canonical, so two calls give equal bits.  root / size: written in place when given (contiguous int32).  flag: an int32
+    word that a thread whose loop ran out of its step budget sets to 1 -- it stays 0; given: never cleared here, so one word
+    can watch many calls (pass your own to read it), else a fresh zeroed one.
+    The two int32 work planes of the labels' shape are allocated here.  Bad arguments: ValueError, before anything is
+    launched."""
+    what = "seg_regions"
+    B, H, W = _region_maps(what, labels, connectivity, (torch.uint8, torch.int16))
+    root, size = _region_plane(what, "root", root, labels), _region_plane(what, "size", size, labels)
+    if root is size or _overlap(root, size):
+        raise ValueError("%s: root and size overlap" % what)
+    flag = _region_flag(what, flag, labels.device)
+    work = torch.empty(2, B, H, W, dtype=torch.int32, device=labels.device)
+    _check(lib().ifseg_seg_regions(_ptr(labels), c_int(labels.element_size()), c_int(B), c_int(H), c_int(W), c_int(connectivity),
+                                   _ptr(work[0]), _ptr(work[1]), _ptr(root), _ptr(size), _ptr(flag), _stream()), "seg_regions")
+    return root, size
+
+
+def seg_region_drop(labels, connectivity=4, min_region=1, fill=255, n=None, raw_labels=True, weight=None, out=None, dropped=None,
+                    flag=None):
+    """labels uint8 [H, W] or [B, H, W] -> (out uint8 of the labels' shape, dropped int64 [n], size int32 of the labels'
+    shape): `seg_regions` with the drop rule in its last launch (`predict.region_drop_reference` states it): a pixel whose
+    value is not `fill` and whose region holds fewer than min_region pixels becomes `fill`, every other pixel is copied.
+    weight uint8 of the labels' shape: its dropped pixels are set to 0 IN PLACE.  dropped[c] = the dropped pixels of class c
+    (value - 1 with raw_labels, else the value; values outside [0, n) are dropped but not counted); given: ACCUMULATED into.
+    n None: every class a uint8 map holds (254 with raw_labels, 255 without).  out: written in place when given; it must
+    not overlap labels.  flag: as in `seg_regions`.  Bad arguments: ValueError, before anything is launched."""
+    what = "seg_region_drop"
+    B, H, W = _region_maps(what, labels, connectivity, (torch.uint8,))
+    if not isinstance(min_region, int) or isinstance(min_region, bool) or not 1 <= min_region < 2 ** 31:
+        raise ValueError("%s: min_region must be an int in 1 .. 2**31 - 1 (1 drops nothing), got %r" % (what, min_region))
+    if not isinstance(fill, int) or isinstance(fill, bool) or not 0 <= fill <= 255:
+        raise ValueError("%s: fill must be an int in 0 .. 255, got %r" % (what, fill))
+    if n is None:
+        n = seg_pseudo_max_classes(raw_labels)
+    if not isinstance(n, int) or isinstance(n, bool) or not 1 <= n <= SEG_REGION_MAX_CLASSES:
+        raise ValueError("%s: n must be an int in 1 .. %d, got %r" % (what, SEG_REGION_MAX_CLASSES, n))
+    dev = labels.device
+    out = _region_plane(what, "out", out, labels, torch.uint8)
+    if weight is not None:
+        _region_plane(what, "weight", weight, labels, torch.uint8)
+        if _overlap(weight, out):
+            raise ValueError("%s: weight overlaps out" % what)
+    if dropped is None:
+        dropped = torch.zeros(n, dtype=torch.int64, device=dev)
+    elif not torch.is_tensor(dropped) or dropped.dtype != torch.int64 or tuple(dropped.shape) != (n,) \
+            or not dropped.is_contiguous() or dropped.device != dev:
+        raise ValueError("%s: dropped must be a contiguous int64 [%d] tensor on %s, got %s" % (
+            what, n, dev, (dropped.dtype, tuple(dropped.shape), dropped.device) if torch.is_tensor(dropped) else type(dropped)))
+    flag = _region_flag(what, flag, dev)
+    work = torch.empty(3, B, H, W, dtype=torch.int32, device=dev)
+    size = torch.empty(labels.shape, dtype=torch.int32, device=dev)
+    _check(lib().ifseg_seg_region_drop(_ptr(labels), c_int(B), c_int(H), c_int(W), c_int(connectivity), c_int(min_region),
+                                       c_int(fill), c_int(n), c_int(1 if raw_labels else 0), _ptr(work[0]), _ptr(work[1]),
+                                       _ptr(work[2]), _ptr(size), _ptr(out), _ptr(weight), _ptr(dropped), _ptr(flag), _stream()),
+           "seg_region_drop")
+    return out, dropped, size
+
+
 # --------------------------------------------------------------------------- pixel-adaptive mask refinement (csrc/pamr.hip)
 SEG_PAMR_MAX_DILATIONS = 8          # == PM_MAX_D: the dilations of a call at most (8 neighbours each)
 SEG_PAMR_MAX_DILATION = 32          # == PM_MAX_DILATION: the largest dilation (a tile's halo: 40 KiB of LDS)

@@ -30,7 +30,8 @@ normalised patch_images, the reference's evaluation transform) and the three ops
 `seg_predict_windows`, `seg_score_windows`: the window batch written directly, and the windows' scores merged into one label
 map in one launch), `seg_render` (csrc/render.hip: the label map coloured over its image, with class contours), `seg_conf_hist` / `seg_pseudo`
 (csrc/pseudo.hip: the per-class confidence histogram of a label map, and the label map filtered by per-class thresholds and an
-ignore band along class edges into pseudo-labels for self-training), `seg_calibration` (csrc/calib.hip: how often a confidence
+ignore band along class edges into pseudo-labels for self-training), `seg_regions` / `seg_region_drop` (csrc/regions.hip: the
+connected regions of equal values of a label map, and the map with its regions below a pixel count dropped), `seg_calibration` (csrc/calib.hip: how often a confidence
 is right, pixels per predicted class, confidence bin and hit against ground truth), `seg_temperature_sweep` (csrc/tsweep.hip: K
 grids of one forward at K temperatures against one ground truth, per temperature the reliability counts, NLL and Brier),
 `seg_pamr` (csrc/pamr.hip: pixel-adaptive mask refinement of one image's class values, guided by its photograph) and the two of multi-scale + flip over sliding windows (`seg_predict_slide_views`, `seg_score_slide_views`:
@@ -1320,6 +1321,70 @@ def seg_pseudo(labels: torch.Tensor, conf: torch.Tensor, thresholds: torch.Tenso
 def _(labels, conf, thresholds, n, boundary, raw_labels):
     _seg_pseudo_check(labels, conf, thresholds, n, boundary, raw_labels)
     return labels.new_empty(tuple(labels.shape), dtype=torch.uint8), labels.new_empty((2, n), dtype=torch.int64)
+
+
+# ----------------------------------------------------------------------------------------------- seg_regions, seg_region_drop
+def _seg_regions_check(labels, connectivity, op="ifseg::seg_regions", dtypes=(torch.uint8, torch.int16)):
+    if labels.dtype not in dtypes:
+        raise ValueError("%s: labels must be %s, got dtype %s" % (op, " or ".join(str(d).replace("torch.", "") for d in dtypes),
+                                                                 labels.dtype))
+    if labels.dim() not in (2, 3) or labels.numel() < 1 or labels.numel() >= 2 ** 31:
+        raise ValueError("%s: labels must be [H, W] or [B, H, W] with 1 <= pixels < 2**31, got %s" % (op, tuple(labels.shape)))
+    if connectivity not in (4, 8):
+        raise ValueError("%s: connectivity must be 4 or 8, got %d" % (op, connectivity))
+
+
+@custom_op("ifseg::seg_regions", mutates_args=(), device_types="cuda")
+def seg_regions(labels: torch.Tensor, connectivity: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """the connected regions of equal values of a label map uint8 / int16 [.., H, W] (csrc/regions.hip) -> (root int32 = per
+    pixel the smallest y W + x of its region inside its image, size int32 = the region's pixel count), fresh tensors of the
+    labels' shape; `ifseg_amd.predict.regions_reference` is the specification.  Integer outputs: not differentiable."""
+    _seg_regions_check(labels, connectivity)
+    prev = _stream_scope(labels)
+    try:
+        return hip.seg_regions(labels.contiguous(), connectivity)
+    finally:
+        hip.set_stream(prev)
+
+
+@seg_regions.register_fake
+def _(labels, connectivity):
+    _seg_regions_check(labels, connectivity)
+    return labels.new_empty(tuple(labels.shape), dtype=torch.int32), labels.new_empty(tuple(labels.shape), dtype=torch.int32)
+
+
+def _seg_region_drop_check(labels, connectivity, min_region, fill, n):
+    op = "ifseg::seg_region_drop"
+    _seg_regions_check(labels, connectivity, op, (torch.uint8,))
+    if not 1 <= min_region < 2 ** 31:
+        raise ValueError("%s: min_region must be in 1 .. 2**31 - 1 (1 drops nothing), got %d" % (op, min_region))
+    if not 0 <= fill <= 255:
+        raise ValueError("%s: fill must be in 0 .. 255, got %d" % (op, fill))
+    if not 1 <= n <= hip.SEG_REGION_MAX_CLASSES:
+        raise ValueError("%s: n = %d classes, the counter takes 1 .. %d" % (op, n, hip.SEG_REGION_MAX_CLASSES))
+
+
+@custom_op("ifseg::seg_region_drop", mutates_args=(), device_types="cuda")
+def seg_region_drop(labels: torch.Tensor, connectivity: int, min_region: int, fill: int, n: int,
+                    raw_labels: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """the area filter of a pseudo-label map uint8 [.., H, W] (csrc/regions.hip): every connected region of a value other than
+    `fill` with fewer than min_region pixels becomes `fill` -> (out uint8, dropped int64 [n] = the dropped pixels per class,
+    size int32 = every pixel's region size), fresh tensors; `ifseg_amd.predict.region_drop_reference` on
+    `regions_reference`'s sizes is the specification.  A weight plane goes through `hip.seg_region_drop`, which zeroes it in
+    place.  Integer outputs: not differentiable."""
+    _seg_region_drop_check(labels, connectivity, min_region, fill, n)
+    prev = _stream_scope(labels)
+    try:
+        return hip.seg_region_drop(labels.contiguous(), connectivity, min_region, fill, n, raw_labels)
+    finally:
+        hip.set_stream(prev)
+
+
+@seg_region_drop.register_fake
+def _(labels, connectivity, min_region, fill, n, raw_labels):
+    _seg_region_drop_check(labels, connectivity, min_region, fill, n)
+    return (labels.new_empty(tuple(labels.shape), dtype=torch.uint8), labels.new_empty((n,), dtype=torch.int64),
+            labels.new_empty(tuple(labels.shape), dtype=torch.int32))
 
 
 # ----------------------------------------------------------------------------------------------- seg_pamr

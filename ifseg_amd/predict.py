@@ -123,6 +123,14 @@ specifications, in integers.  `task.self_train_sample(model, photos, first_ordin
     t = hist.thresholds(keep=0.5, floor=0.3)
     out = seg.pseudo_label_raw(photos, thresholds=t, boundary=1)                   # [PseudoLabelResult(labels, predicted, conf, kept)]
 
+Those filters judge a pixel; what they leave behind is a matter of regions: speckles of a few confident but wrong pixels, and
+the crumbs left where the filters cut a region apart.  `min_region=K` adds one `hip.seg_region_drop` per image on the filtered
+map (csrc/regions.hip: connected regions of equal values by a block-based union-find, four launches): every region of fewer
+than K pixels becomes 255 and its weights 0, and the result's `region_dropped` counts them per class.  `regions_reference`
+and `region_drop_reference` are the specifications.
+
+    out = seg.pseudo_label_raw(photos, thresholds=t, boundary=1, min_region=16, region_connectivity=8)
+
 A cheap refinement that looks at the photograph: `Segmenter(..., pamr_iters=10)` runs pixel-adaptive mask refinement (PAMR,
 Araslanov & Roth, CVPR 2020; what MaskCLIP applies to its pseudo-labels) on the resized values of every image, in the slot of
 the CRF: `hip.seg_pamr` (csrc/pamr.hip), one affinity launch on the original uint8 photo and one launch per iteration.  Each
@@ -827,12 +835,122 @@ def pseudo_label_reference(labels, conf, thresholds, n, boundary=0, raw_labels=T
     return out, kept
 
 
-class PseudoLabelResult(NamedTuple):
+def _connectivity_arg(what, connectivity):
+    if not isinstance(connectivity, int) or isinstance(connectivity, bool) or connectivity not in (4, 8):
+        raise ValueError("%s: connectivity must be the int 4 or 8, got %r" % (what, connectivity))
+    return connectivity
+
+
+def _min_region_arg(what, min_region):
+    if not isinstance(min_region, int) or isinstance(min_region, bool) or not 1 <= min_region < 2 ** 31:
+        raise ValueError("%s: min_region must be an int in 1 .. 2**31 - 1 (1 drops nothing), got %r" % (what, min_region))
+    return min_region
+
+
+def _region_labels(what, labels):
+    labels = torch.as_tensor(labels)
+    if labels.dtype.is_floating_point or labels.dtype.is_complex or labels.dtype == torch.bool:
+        raise ValueError("%s: labels must be integer, got %s" % (what, labels.dtype))
+    if labels.dim() not in (2, 3) or labels.numel() < 1:
+        raise ValueError("%s: labels must be [H, W] or [B, H, W] with at least one pixel, got %s" % (what, tuple(labels.shape)))
+    if labels.numel() >= 2 ** 31:
+        raise ValueError("%s: labels %s hold 2**31 pixels or more" % (what, tuple(labels.shape)))
+    return labels
+
+
+def regions_reference(labels, connectivity=4):
+    """Specification of hip.seg_regions: labels integer [H, W] (or [B, H, W]) -> (root, size), both int32 of labels' shape.
+
+    Two pixels of one image are adjacent under connectivity=4 iff they differ by one step in x or in y; under connectivity=8 the
+    diagonal steps count too (any other connectivity: ValueError).  A region is a maximal set of pixels that is connected
+    through adjacency and carries the same label value: values are compared as they are (as `boundary_areas_reference` does),
+    so 255, a negative int16 and anything outside [0, n) are values of their own and form regions like any other; regions
+    never cross from one image of a batch into the next.
+      root[p] = the smallest y W + x inside its image over the pixels of p's region: canonical, no numbering by discovery
+      size[p] = the region's pixel count
+    Computed by iterating "the minimum over the equal-valued neighbours, then a pointer jump" until nothing moves: root[p] <= p
+    always names a pixel of p's region, so the fixed point is the region's smallest index.  Runs on any device."""
+    what = "regions_reference"
+    conn = _connectivity_arg(what, connectivity)
+    labels = _region_labels(what, labels)
+    lab = labels.reshape((-1,) + tuple(labels.shape[-2:]))
+    B, H, W = lab.shape
+    steps = [(0, 1), (1, 0)] + ([(1, 1), (1, -1)] if conn == 8 else [])
+    pairs = []                                  # (here, there) slices with their equal-value masks, both directions
+    for dy, dx in steps:
+        if dy >= H or abs(dx) >= W:
+            continue
+        here = (slice(None), slice(0, H - dy), slice(max(-dx, 0), W - max(dx, 0)))
+        there = (slice(None), slice(dy, H), slice(max(dx, 0), W - max(-dx, 0)))
+        pairs.append((here, there, lab[here] == lab[there]))
+    root = torch.arange(H * W, dtype=torch.int64, device=lab.device).reshape(1, H, W).expand(B, H, W).contiguous()
+    while True:
+        new = root.clone()
+        for here, there, same in pairs:
+            new[here] = torch.where(same, torch.minimum(new[here], root[there]), new[here])
+            new[there] = torch.where(same, torch.minimum(new[there], root[here]), new[there])
+        flat = new.reshape(B, H * W)
+        new = flat.gather(1, flat).reshape(B, H, W)                # the pointer jump
+        if torch.equal(new, root):
+            break
+        root = new
+    offs = torch.arange(B, dtype=torch.int64, device=lab.device).reshape(B, 1, 1) * (H * W)
+    size = torch.bincount((root + offs).reshape(-1), minlength=B * H * W)[(root + offs)]
+    return root.to(torch.int32).reshape(labels.shape), size.to(torch.int32).reshape(labels.shape)
+
+
+def region_drop_reference(labels, size, min_region, fill=255, n=None, raw_labels=True, weight=None):
+    """Specification of hip.seg_region_drop's last step: labels integer [H, W] (or [B, H, W]), size = `regions_reference`'s of
+    them -> (out, dropped) or, with a weight plane (labels' shape), (out, dropped, weight).
+
+    A pixel whose value is not `fill` and whose size < min_region becomes `fill`, and its weight 0; every other pixel and
+    weight is unchanged, so regions of the value `fill` are never touched.  dropped int64 [n]: the dropped pixels per class,
+    the class being value - 1 with raw_labels, else the value; values outside the classes are dropped but not counted.
+    n None: every class a uint8 map holds (254 with raw_labels, else 255).  min_region: an int >= 1, 1 drops nothing; fill:
+    an int in 0 .. 255; anything else is a ValueError.  Runs on any device."""
+    what = "region_drop_reference"
+    min_region = _min_region_arg(what, min_region)
+    labels = _region_labels(what, labels)
+    size = torch.as_tensor(size)
+    if size.dtype.is_floating_point or size.dtype == torch.bool or size.shape != labels.shape:
+        raise ValueError("%s: size must be integer %s, got %s %s" % (what, tuple(labels.shape), size.dtype, tuple(size.shape)))
+    if not isinstance(fill, int) or isinstance(fill, bool) or not 0 <= fill <= 255:
+        raise ValueError("%s: fill must be an int in 0 .. 255, got %r" % (what, fill))
+    if n is None:
+        n = hip.seg_pseudo_max_classes(raw_labels)
+    if not isinstance(n, int) or isinstance(n, bool) or not 1 <= n <= hip.SEG_REGION_MAX_CLASSES:
+        raise ValueError("%s: n must be an int in 1 .. %d, got %r" % (what, hip.SEG_REGION_MAX_CLASSES, n))
+    if weight is not None:
+        weight = torch.as_tensor(weight)
+        if weight.shape != labels.shape:
+            raise ValueError("%s: weight must have the labels' shape %s, got %s" % (what, tuple(labels.shape), tuple(weight.shape)))
+    drop = (labels != fill) & (size.to(labels.device) < min_region)
+    out = torch.where(drop, torch.full_like(labels, fill), labels)
+    cls = labels.long() - (1 if raw_labels else 0)
+    dropped = torch.bincount(cls[drop & (cls >= 0) & (cls < n)], minlength=n)
+    if weight is not None:
+        return out, dropped, torch.where(drop.to(weight.device), torch.zeros_like(weight), weight)
+    return out, dropped
+
+
+class _PseudoLabelFields(NamedTuple):
     labels: torch.Tensor                       # [H, W] uint8: the pseudo-label map `train_sample` takes (255 = ignored)
     predicted: torch.Tensor                    # [H, W] uint8 / int16: what `segment_raw` gave
     conf: torch.Tensor                         # [H, W] fp32: the winning class's probability
     kept: torch.Tensor                         # [2, n] int64: per class the kept and the predicted pixels of this image
     weight: Optional[torch.Tensor] = None      # [H, W] uint8 (return_weight): 0 = dropped, else max(conf_bin(conf), 1)
+
+
+class PseudoLabelResult(_PseudoLabelFields):
+    """The five fields above, as a tuple (it unpacks and compares as it always did), and one attribute behind them:
+    region_dropped, int64 [n] or None -- with `pseudo_label_raw(min_region=)` the pixels per class that the region filter took
+    out of `labels` (and out of kept[0]).  Keyword-only; it is not an element of the tuple."""
+    region_dropped: Optional[torch.Tensor] = None
+
+    def __new__(cls, labels, predicted, conf, kept, weight=None, *, region_dropped=None):
+        self = super().__new__(cls, labels, predicted, conf, kept, weight)
+        self.region_dropped = region_dropped
+        return self
 
 
 class ConfidenceHistogram:
@@ -1581,7 +1699,7 @@ class Segmenter:
 
     def pseudo_label_raw(self, images, keep=1.0, floor=0.0, boundary=0, raw_labels=True, hist=None, thresholds=None,
                          scales=(1.0,), flip=False, slide=None, max_batch=8, mean=None, std=None, reverse_channels=False,
-                         return_weight=False):
+                         return_weight=False, min_region=None, region_connectivity=4):
         """Unlabeled photographs -> label maps `task.train_sample` accepts, holding only the pixels the model is confident
         of: the self-training step (CBST, MaskCLIP+) that adapts the image-free model to a target domain, on the device ->
         a list of `PseudoLabelResult(labels uint8 [H_i, W_i], predicted, conf, kept)` in input order.
@@ -1599,7 +1717,13 @@ class Segmenter:
              become class + 1 with raw_labels (what a `TrainTransform(raw_labels=True)`, the default, takes), else the class id;
              every other pixel 255, ignored by both.  return_weight: the same launch also writes the result's `weight`, uint8
              [H_i, W_i]: 0 where the pixel was dropped, else max(conf_bin(conf), 1) -- the per-pixel loss weight that
-             `task.train_sample(..., weights=)` carries to the weighted criterion.
+             `task.train_sample(..., weights=)` carries to the weighted criterion;
+          5. with min_region = K (an int >= 1; None: this step does not exist and the call is the one above, launch for
+             launch): one `hip.seg_region_drop` per image on the FILTERED map -- every connected region (region_connectivity 4
+             or 8; `regions_reference` states the rule) of fewer than K pixels becomes 255 and its weights 0, the speckles the
+             model predicted and the crumbs the filters of step 4 cut off alike; 255 itself is never a region to drop.  The
+             result's `region_dropped` int64 [n] holds the dropped pixels per class, and kept[0] has them subtracted, on the
+             device (`region_drop_reference` states the rule).
         Nothing synchronises with the host.  Between the passes every image's labels and conf stay alive: 5 bytes per pixel
         (6 with int16 labels) for the whole call, which bounds the images of one call, not of a data set.
 
@@ -1611,6 +1735,9 @@ class Segmenter:
         if self.n > hip.seg_pseudo_max_classes(raw_labels):
             raise ValueError("%s: the uint8 pseudo-label map holds at most %d classes with raw_labels=%s, the model has n = %d"
                              % (what, hip.seg_pseudo_max_classes(raw_labels), bool(raw_labels), self.n))
+        _connectivity_arg(what + ": region_connectivity", region_connectivity)
+        if min_region is not None:
+            _min_region_arg(what, min_region)
         sl = self._check_slide("pseudo_label_raw", slide, scales, flip)
         self._need_probability(what, sl)
         dev = next(self.model.parameters()).device
@@ -1636,12 +1763,18 @@ class Segmenter:
                 thresholds = thresholds.to(dev).contiguous()
             out = []
             for labels, conf in pairs:
+                wt = None
                 if return_weight:
                     pseudo, kept, wt = hip.seg_pseudo(labels, conf, thresholds, self.n, boundary, bool(raw_labels), weight=True)
+                else:
+                    pseudo, kept = hip.seg_pseudo(labels, conf, thresholds, self.n, boundary, bool(raw_labels))
+                if min_region is None:
                     out.append(PseudoLabelResult(pseudo, labels, conf, kept, wt))
                     continue
-                pseudo, kept = hip.seg_pseudo(labels, conf, thresholds, self.n, boundary, bool(raw_labels))
-                out.append(PseudoLabelResult(pseudo, labels, conf, kept))
+                pseudo, dropped, _ = hip.seg_region_drop(pseudo, region_connectivity, min_region, fill=255, n=self.n,
+                                                         raw_labels=bool(raw_labels), weight=wt)
+                kept[0] -= dropped
+                out.append(PseudoLabelResult(pseudo, labels, conf, kept, wt, region_dropped=dropped))
         return out
 
     # -- scoring against ground truth -----------------------------------------------------

@@ -239,7 +239,9 @@ class SegmentationTask(TaskBase):
     def pseudo_label_raw(self, model, images, **kw):
         """unlabeled raw uint8 images -> a list of `PseudoLabelResult(labels, predicted, conf, kept)`, label maps that hold only
         the pixels the model is confident of: `build_segmenter(model, ...).pseudo_label_raw(images, ...)`.  Keywords of the
-        Segmenter's constructor go to it, the others to `Segmenter.pseudo_label_raw`."""
+        Segmenter's constructor go to it, the others to `Segmenter.pseudo_label_raw` -- `min_region=K` and
+        `region_connectivity` among them: connected regions of the filtered map below K pixels become 255 too, and the
+        results carry `region_dropped`."""
         ctor = ("category_token_ids", "prompt_ids", "upsample", "smooth_iters", "smooth_topk", "temperature", "crf_iters",
                 "full_context_alignment", "label_dtype", "slide_views", "pamr_iters", "pamr_dilations")
         seg = self.build_segmenter(model, **{k: kw.pop(k) for k in ctor if k in kw})
@@ -258,7 +260,9 @@ class SegmentationTask(TaskBase):
         confidence_weight: the labelling launch also writes every pixel's confidence as a loss weight
         (`pseudo_label_raw(return_weight=True)`), the transform carries the planes to the batch and the sample gains
         `"target_weight"` (uint8 [B, P*P]), which the criterion's weighted kernel reads: a kept pixel counts by how sure the
-        teacher was of it instead of 0 or 1."""
+        teacher was of it instead of 0 or 1.
+        `min_region=K`, `region_connectivity` (in `kw`, as every keyword of `pseudo_label_raw`): the labels and the weight
+        planes leave without their connected regions below K pixels."""
         tf = getattr(self, "train_transform", None) or self.build_train_transform()
         if confidence_weight:
             kw["return_weight"] = True
@@ -531,7 +535,9 @@ class SegmentationTask(TaskBase):
         independently: first_ordinal + B <= 2**31, else ValueError.  Pasted labelled pixels weigh 255, the rest the teacher's
         confidence; the criterion's default `weight_norm="weights"` is scale-free.  DACS applies a colour jitter and a
         Gaussian blur after the mix: `strong=True` sends the mixed images through `strong_augment(sample, first_ordinal)`;
-        by default each half keeps its own transform's jitter and nothing more."""
+        by default each half keeps its own transform's jitter and nothing more.  `min_region=K` and `region_connectivity` in
+        `kw` reach `pseudo_label_raw` through `self_train_sample`: the small regions leave the pseudo-labelled half before
+        the mix."""
         images = [images] if torch.is_tensor(images) else list(images)
         first = int(first_ordinal)
         if first < 0 or first + len(images) > 2 ** 31:

@@ -985,6 +985,38 @@ int ifseg_seg_pseudo_weighted(const void* labels, int label_bytes, const float* 
                               int W, int boundary, int raw_labels, void* out, void* weight, unsigned long long* kept,
                               void* stream);
 
+/* ---- connected regions of a label map (csrc/regions.hip; ifseg_amd/predict.py regions_reference and
+ * region_drop_reference are the specifications; the reference has no counterpart) ----
+ * labels [B][H][W], uint8 (label_bytes 1) or int16 (2).  Two pixels of one image are adjacent under connectivity 4 iff they
+ * differ by one step in x or in y, under 8 the diagonal steps count too.  A region is a maximal set of pixels connected
+ * through adjacency that carry the same value; values are compared as they are (255, negative shorts and anything outside a
+ * class range are values of their own), and regions never cross from one image into the next.
+ * ifseg_seg_regions writes root int32 [B][H][W] = the smallest y W + x inside its image over the pixels of p's region, and
+ * size int32 [B][H][W] = the region's pixel count: four launches on `stream` (a union-find per 16 x 64 tile in LDS; the unions
+ * across the tiles' seams, every access to the plane an agent-scope atomic; the chains flattened into `root` and the tiles'
+ * counts added at the regions' roots, one 32-bit integer atomic per tile-local region; size gathered), three where an image
+ * is one tile.  work and count: int32 [B][H][W] each, the caller's, written in full (nothing needs zeroing).  The results are
+ * canonical, so two calls give equal bits.  Every loop's step count is bounded (a chase: H W + 1, a union: 2 H W + 1); a
+ * thread that runs out sets *flag to 1 and leaves.  flag is never cleared here: the caller zeroes it, and one word can watch
+ * many calls.
+ * NULL pointers, label_bytes outside {1, 2}, int16 labels at an odd address, a plane or flag not 4-byte aligned, two of
+ * work / count / root / size / labels / flag sharing a byte, connectivity other than 4 or 8: IFSEG_ERR_BAD_ARG; B, H, W < 1 or
+ * B*H*W >= 2^31: IFSEG_ERR_BAD_SHAPE.  Nothing is launched on a refusal. */
+int ifseg_seg_regions(const void* labels, int label_bytes, int B, int H, int W, int connectivity, int* work, int* count,
+                      int* root, int* size, int* flag, void* stream);
+/* ifseg_seg_regions on uint8 labels with the drop rule in its last launch: out uint8 [B][H][W] (any byte address) = fill
+ * where labels != fill and size < min_region, labels elsewhere (regions of the value fill are never touched); weight uint8
+ * [B][H][W] or NULL: set to 0 where the pixel was dropped, left as it is elsewhere; dropped uint64 [n] is ADDED to: the
+ * dropped pixels per class, class = value - 1 with raw_labels != 0, else the value; values outside the classes are dropped
+ * but not counted.  One 64-bit atomic per workgroup and non-zero entry.
+ * Also refused with IFSEG_ERR_BAD_ARG: NULL out / dropped, dropped not 8-byte aligned, min_region < 1, fill outside 0..255,
+ * n outside 1..255, out / weight / labels / the planes sharing a byte. */
+int ifseg_seg_region_drop(const void* labels, int B, int H, int W, int connectivity, int min_region, int fill, int n,
+                          int raw_labels, int* work, int* count, int* root, int* size, void* out, void* weight,
+                          unsigned long long* dropped, int* flag, void* stream);
+/* which = 0 / 1: the rows / columns of a tile, 2: the largest n of the drop; any other which: IFSEG_ERR_BAD_ARG. */
+int ifseg_seg_regions_limit(int which);
+
 /* ---- pixel-adaptive mask refinement (PAMR: Araslanov & Roth, CVPR 2020; Segmenter(pamr_iters=); the reference has no
  * counterpart) ----  A few iterations of a local, image-adaptive, convex averaging of the class values of ONE image at image
  * resolution, linear in the pixels; csrc/pamr.hip; ifseg_amd/predict.py pamr_reference is the specification.
