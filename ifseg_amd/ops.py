@@ -4,46 +4,53 @@ BASELINE.json north_star asks for "Python host code calling hand-written HIP ker
 ops"; SURVEY 8b names torch.library.  The engine (models/segofa/engine.py) keeps calling the C ABI directly through
 `ifseg_amd.hip` -- one ctypes call per launch, no dispatcher hop on a ~570-launch step -- and this module puts the same
 kernels IN FRONT OF the dispatcher as functional ops with autograd and fake (meta) implementations, for callers that
-compose them with other PyTorch code (`torch.compile`, `torch.autograd.gradcheck`-style tests, export):
+compose them with other PyTorch code (`torch.compile`, `torch.autograd.gradcheck`-style tests, export).
 
-  torch.ops.ifseg.linear(x, w, bias)                       F.linear                      unify_multihead_attention.py:327-346,513
-  torch.ops.ifseg.layer_norm(x, gamma, beta, eps, gelu)    LayerNorm (+ GELU in front)   unify_transformer_layer.py:256-292
-  torch.ops.ifseg.bias_attention(q, k, v, pos_q, pos_k, gain, gcode, rel2d, rel1d, relx, P, code_bias, grid_w, causal)
-                                                           position-biased attention     unify_multihead_attention.py:459-512,
-                                                                                         encoder_module.py:757-809
-Each op has its backward registered as further ops (`linear_bwd`, `layer_norm_bwd`, `bias_attention_bwd`), so the backward
-is dispatcher-visible too.  No CPU implementation is registered: on a CPU tensor the dispatcher raises.
+  op                        csrc/              backward op             mirrors
+  linear                    gemm.hip           linear_bwd              F.linear, unify_multihead_attention.py:327-346,513
+  layer_norm                rowops.hip         layer_norm_bwd          LayerNorm (+ GELU in front), unify_transformer_layer.py:256-292
+  bias_attention            attention.hip      bias_attention_bwd      unify_multihead_attention.py:459-512, encoder_module.py:757-809
+  attention_bias            attention_bi.hip   attention_bias_bwd      unify_multihead_attention.py:459-512 (:130,464-465: the bias a tensor)
+  bias_attention_bi         attention_bi.hip   bias_attention_bi_bwd   bias_attention + key counts + attention dropout
+  seg_loss                  loss.hip           seg_loss_bwd            seg_criterion.py:237-244,269-347
+  seg_loss_weighted         loss.hip           seg_loss_bwd            seg_loss with a weight per pixel and per class
+  seg_dice                  dice.hip           seg_loss_bwd            per-sample soft Dice of the same upsampled logits
+  seg_distill               distill.hip        seg_loss_bwd            per-pixel KL to a teacher (no gradient to the teacher)
+  seg_ohem                  ohem.hip           -                       mmseg's OHEMPixelSampler: seg_loss_weighted's weight plane
+  seg_predict               predict.hip        -                       label maps at image resolution
+  seg_predict_views         predict.hip        -                       the mean of K views: multi-scale + flip inference
+  seg_areas                 predict.hip        -                       label maps counted against ground truth: mIoU
+  seg_confusion             predict.hip        -                       the class confusion matrix [n, n + 1]
+  seg_boundary_areas        boundary.hip       -                       Boundary IoU's band areas and the two bands
+  seg_score_views           predict.hip        -                       seg_areas in seg_predict_views' epilogue
+  seg_render                render.hip         -                       the label map coloured over its image, with contours
+  seg_conf_hist             pseudo.hip         -                       the per-class confidence histogram of a label map
+  seg_pseudo                pseudo.hip         -                       pseudo-labels by thresholds and an ignore band
+  seg_regions               regions.hip        -                       the connected regions of a label map
+  seg_region_drop           regions.hip        -                       the map without its regions below a pixel count
+  seg_calibration           calib.hip          -                       how often a confidence is right, per class and bin
+  seg_temperature_sweep     tsweep.hip         -                       K temperatures of one forward: reliability, NLL, Brier
+  seg_pamr                  pamr.hip           -                       pixel-adaptive mask refinement of one image
+  image_load                imgload.hip        -                       the reference's evaluation transform
+  image_load_windows        imgload.hip        -                       the window batch of sliding-window inference
+  seg_predict_windows       predict.hip        -                       the windows' scores merged into one label map
+  seg_score_windows         predict.hip        -                       seg_areas in seg_predict_windows' epilogue
+  seg_predict_slide_views   predict.hip        -                       K views, each a set of windows (softmax per view: mmseg)
+  seg_score_slide_views     predict.hip        -                       seg_areas in seg_predict_slide_views' epilogue
+  train_load                trainload.hip      -                       the reference's training transform under given records
+  mix_draw                  mix.hip            -                       ClassMix / CutMix: the choice of classes or of a box
+  mix_apply                 mix.hip            -                       the paste of images, targets and weight planes (copies bits)
+  strong_draw               strong.hip         -                       the records of colour jitter and Gaussian blur
+  strong_apply              strong.hip         -                       a mixed batch's images under them (integer in between)
 
-The second half of the file puts the training-path kernels there as well (see the comment above `_check_qkv`):
-`attention_bias` (the bias is an ordinary tensor with a gradient), `bias_attention_bi` (bias_attention on the batch-inner
-kernels, with key counts and attention dropout), `seg_loss` (csrc/loss.hip) and `seg_loss_weighted` (the same kernel with a
-weight per pixel and per class; it shares `seg_loss_bwd`), with `*_bwd` ops of their own, and `seg_ohem` (csrc/ohem.hip: the
-online-hard-example sampler that makes that weight plane; a constant of the step, no backward) and `seg_dice` (csrc/dice.hip: the
-per-sample soft Dice loss of the same upsampled logits, with `seg_loss_bwd` as its backward) and `seg_distill` (csrc/distill.hip:
-the per-pixel KL divergence from a teacher's upsampled logits at a temperature, `seg_loss_bwd` again; no gradient to the teacher);
-`ifseg_amd.modules.MultiheadAttention` composes `linear` and `attention_bias` under the reference module's parameter names.
-`seg_predict` (csrc/predict.hip: label maps at image resolution), `seg_predict_views` (the same from the mean of K views of
-differing grids, mirrored ones included: multi-scale + flip inference), `seg_areas` / `seg_score_views` (label maps counted
-against ground truth, stand-alone and in the predict kernel's epilogue: mIoU on the device), `seg_confusion` (the class
-confusion matrix of a label map against ground truth, [n, n + 1] with an "outside" column), `seg_boundary_areas` (csrc/boundary.hip: Boundary IoU's band areas and the two bands), `image_load` (csrc/imgload.hip: raw uint8 images to
-normalised patch_images, the reference's evaluation transform) and the three ops of sliding-window inference (`image_load_windows`,
-`seg_predict_windows`, `seg_score_windows`: the window batch written directly, and the windows' scores merged into one label
-map in one launch), `seg_render` (csrc/render.hip: the label map coloured over its image, with class contours), `seg_conf_hist` / `seg_pseudo`
-(csrc/pseudo.hip: the per-class confidence histogram of a label map, and the label map filtered by per-class thresholds and an
-ignore band along class edges into pseudo-labels for self-training), `seg_regions` / `seg_region_drop` (csrc/regions.hip: the
-connected regions of equal values of a label map, and the map with its regions below a pixel count dropped), `seg_calibration` (csrc/calib.hip: how often a confidence
-is right, pixels per predicted class, confidence bin and hit against ground truth), `seg_temperature_sweep` (csrc/tsweep.hip: K
-grids of one forward at K temperatures against one ground truth, per temperature the reliability counts, NLL and Brier),
-`seg_pamr` (csrc/pamr.hip: pixel-adaptive mask refinement of one image's class values, guided by its photograph) and the two of multi-scale + flip over sliding windows (`seg_predict_slide_views`, `seg_score_slide_views`:
-K views, each a set of windows, merged in one launch, optionally softmaxed per view as mmseg does) are inference only and
-have no backward; `train_load`
-(csrc/trainload.hip: raw images and label maps of any sizes to a training batch under given records, the reference's training
-transform) has integer inputs and no backward either, and neither have `mix_draw` / `mix_apply` (csrc/mix.hip: ClassMix /
-CutMix of a labelled batch into a pseudo-labelled one -- the choice of classes or of a box, and the paste of images, targets
-and weight planes, which copies bits) and `strong_draw` / `strong_apply` (csrc/strong.hip: colour jitter and Gaussian blur of a
-mixed batch's images, integer between input and output).
+The backward ops are dispatcher-visible ops themselves; `ifseg_amd.modules.MultiheadAttention` composes `linear` and
+`attention_bias` under the reference module's parameter names.  No CPU implementation is registered: on a CPU tensor the
+dispatcher raises.
+
+Every op has ONE check helper that its real and its fake implementation call first: tracing refuses what running refuses,
+and nothing is launched (the library is not even loaded) before the arguments have passed.  Behind the check every real
+body runs inside ONE stream scope, `with _on_stream(...)`: nowhere else is the stream of the launches set.
 """
-import contextlib
 from typing import Optional, Sequence, Tuple
 
 import torch
@@ -54,21 +61,38 @@ from . import hip
 BF = torch.bfloat16
 
 
-def _stream_scope(t):
-    """the kernels run on PyTorch's current stream of the tensor's device"""
-    return hip.set_stream(torch.cuda.current_stream(t.device).cuda_stream)
+class _on_stream:
+    """the kernels inside run on PyTorch's current stream of a tensor's device, or of the device itself; the handle that was
+    pinned before comes back on every exit, a raised exception included"""
+    __slots__ = ("where", "prev")
+
+    def __init__(self, where):
+        self.where = where
+
+    def __enter__(self):
+        where = self.where
+        self.prev = hip.set_stream(torch.cuda.current_stream(where.device if torch.is_tensor(where) else where).cuda_stream)
+
+    def __exit__(self, *exc):
+        hip.set_stream(self.prev)
+
+
+def _c(t):
+    return None if t is None else t.contiguous()
+
+
+def _or_empty(t, dtype, device):
+    """an output that was not asked for (None) is an empty tensor of this dtype on this device"""
+    return torch.empty(0, dtype=dtype, device=device) if t is None else t
 
 
 # ----------------------------------------------------------------------------------------------- linear
 @custom_op("ifseg::linear", mutates_args=(), device_types="cuda")
 def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
-    prev = _stream_scope(x)
-    try:
+    with _on_stream(x):
         x2 = x.reshape(-1, x.shape[-1]).contiguous()
         out = hip.linear_fwd(x2, w.contiguous(), bias)
         return out.view(*x.shape[:-1], w.shape[0])
-    finally:
-        hip.set_stream(prev)
 
 
 @linear.register_fake
@@ -79,8 +103,7 @@ def _(x, w, bias):
 @custom_op("ifseg::linear_bwd", mutates_args=(), device_types="cuda")
 def linear_bwd(g: torch.Tensor, x: torch.Tensor, w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """-> (dx, dw, db): dx = g w, dw = g^T x, db = column sums of g (one GEMM carries dw and db)"""
-    prev = _stream_scope(g)
-    try:
+    with _on_stream(g):
         g2 = g.reshape(-1, g.shape[-1]).contiguous()
         x2 = x.reshape(-1, x.shape[-1]).contiguous()
         N, K = w.shape
@@ -90,8 +113,6 @@ def linear_bwd(g: torch.Tensor, x: torch.Tensor, w: torch.Tensor) -> Tuple[torch
         if not hip.linear_dw(g2, x2, dw, bias_out=db):
             db.copy_(g2.float().sum(0))
         return dx.view(x.shape), dw, db.clone()           # (returns of a custom op must not share storage)
-    finally:
-        hip.set_stream(prev)
 
 
 @linear_bwd.register_fake
@@ -118,8 +139,7 @@ linear.register_autograd(_linear_backward, setup_context=_linear_setup)
 @custom_op("ifseg::layer_norm", mutates_args=(), device_types="cuda")
 def layer_norm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, gelu: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """-> (y, mean, rstd); gelu: y = LN(GELU(x)) (the FFN's ffn_layernorm(gelu(fc1)), GELU evaluated in fp32)"""
-    prev = _stream_scope(x)
-    try:
+    with _on_stream(x):
         C = x.shape[-1]
         x2 = x.reshape(-1, C).contiguous()
         y = torch.empty_like(x2)
@@ -127,8 +147,6 @@ def layer_norm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: fl
         rstd = torch.empty_like(mean)
         hip.ln_fwd(x2, gamma, beta, y, mean, rstd, gelu=gelu, eps=eps)
         return y.view(x.shape), mean, rstd
-    finally:
-        hip.set_stream(prev)
 
 
 @layer_norm.register_fake
@@ -140,8 +158,7 @@ def _(x, gamma, beta, eps, gelu):
 @custom_op("ifseg::layer_norm_bwd", mutates_args=(), device_types="cuda")
 def layer_norm_bwd(dy: torch.Tensor, x: torch.Tensor, gamma: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor,
                    gelu: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    prev = _stream_scope(x)
-    try:
+    with _on_stream(x):
         C = x.shape[-1]
         x2, dy2 = x.reshape(-1, C).contiguous(), dy.reshape(-1, C).contiguous()
         dx = torch.empty_like(x2)
@@ -150,8 +167,6 @@ def layer_norm_bwd(dy: torch.Tensor, x: torch.Tensor, gamma: torch.Tensor, mean:
         dgb = torch.empty(2, C, dtype=gamma.dtype if gamma.dtype in (BF, torch.float32) else torch.float32, device=x.device)
         hip.reduce_parts(part, dgb, 2, hip.LN_BWD_BLOCKS, C)
         return dx.view(x.shape), dgb[0].clone(), dgb[1].clone()
-    finally:
-        hip.set_stream(prev)
 
 
 @layer_norm_bwd.register_fake
@@ -179,6 +194,20 @@ def _rel(P, gcode, rel2d, rel1d, relx, code_bias, grid_w):
     return None if gcode is None else hip.RelBias(P, gcode, code_bias, rel2d, rel1d, relx, grid_w=grid_w)
 
 
+def _attn_bwd_fake(q, k, v, pos_q, pos_k, gain, rel2d, rel1d, relx):
+    """the nine of `bias_attention_bwd` and `bias_attention_bi_bwd`"""
+    f = lambda t: q.new_empty(0, dtype=torch.float32) if t is None else t.new_empty(t.shape)
+    return (q.new_empty(q.shape), k.new_empty(k.shape), v.new_empty(v.shape), pos_q.new_empty(pos_q.shape),
+            pos_k.new_empty(pos_k.shape), gain.new_empty(gain.shape, dtype=torch.float32), f(rel2d), f(rel1d), f(relx))
+
+
+def _attn_grads(nine, gcode, settings):
+    """those nine as the gradients of the forward's inputs: none for gcode, the tables' only when there are tables, none for
+    the `settings` arguments behind them"""
+    has = gcode is not None
+    return tuple(nine[:6]) + (None,) + tuple(d if has else None for d in nine[6:]) + (None,) * settings
+
+
 @custom_op("ifseg::bias_attention", mutates_args=(), device_types="cuda")
 def bias_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pos_q: torch.Tensor, pos_k: torch.Tensor,
                    gain: torch.Tensor, gcode: Optional[torch.Tensor], rel2d: Optional[torch.Tensor],
@@ -187,8 +216,7 @@ def bias_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pos_q: tor
     """q [B,T,H*64] (already scaled), k / v [B,S,H*64], pos_q [T,H*64] (scaled), pos_k [S,H*64], gain fp32 [H];
     gcode int32 [P] + fp32 delta tables rel2d [H,n2d] / rel1d [H,2Lt-1] / relx [H,2] (or all None: no relative bias).
     -> (out [B,T,H*64] = gain_h * softmax(q k^T + pos_q pos_k^T + rel) v, lse [B,H,T] in log2 units)"""
-    prev = _stream_scope(q)
-    try:
+    with _on_stream(q):
         B, T, C = q.shape
         S, H = k.shape[1], C // 64
         out = torch.empty_like(q)
@@ -196,8 +224,6 @@ def bias_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pos_q: tor
         hip.attn_fwd(q, k, v, pos_q, pos_k, out, lse, B, H, T, S, rel=_rel(P, gcode, rel2d, rel1d, relx, code_bias, grid_w),
                      causal=causal, P=P, gain=gain)
         return out, lse
-    finally:
-        hip.set_stream(prev)
 
 
 @bias_attention.register_fake
@@ -215,8 +241,7 @@ def bias_attention_bwd(dout: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v: 
                                   torch.Tensor, torch.Tensor, torch.Tensor]:
     """-> (dq, dk, dv, dpos_q, dpos_k, dgain, drel2d, drel1d, drelx); the three table gradients are empty tensors when the
     attention has no relative bias"""
-    prev = _stream_scope(q)
-    try:
+    with _on_stream(q):
         B, T, C = q.shape
         S, H = k.shape[1], C // 64
         dev = q.device
@@ -237,16 +262,11 @@ def bias_attention_bwd(dout: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v: 
         tabs = [p.sum(1) if p is not None else e for p in parts]
         dgain = dgr.sum((0, 2))
         return dq, dk, dv, dpq.float().sum(0).to(pos_q.dtype), dpk.float().sum(0).to(pos_k.dtype), dgain, tabs[0], tabs[1], tabs[2]
-    finally:
-        hip.set_stream(prev)
 
 
 @bias_attention_bwd.register_fake
 def _(dout, q, k, v, pos_q, pos_k, gain, out, lse, gcode, rel2d, rel1d, relx, P, code_bias, grid_w, causal):
-    e = q.new_empty(0, dtype=torch.float32)
-    f = lambda t: e if t is None else t.new_empty(t.shape)
-    return (q.new_empty(q.shape), k.new_empty(k.shape), v.new_empty(v.shape), pos_q.new_empty(pos_q.shape),
-            pos_k.new_empty(pos_k.shape), gain.new_empty(gain.shape, dtype=torch.float32), f(rel2d), f(rel1d), f(relx))
+    return _attn_bwd_fake(q, k, v, pos_q, pos_k, gain, rel2d, rel1d, relx)
 
 
 def _attn_setup(ctx, inputs, output):
@@ -258,11 +278,9 @@ def _attn_setup(ctx, inputs, output):
 def _attn_backward(ctx, gout, glse):
     q, k, v, pos_q, pos_k, gain, out, lse, gcode, rel2d, rel1d, relx = ctx.saved_tensors
     P, code_bias, grid_w, causal = ctx.meta
-    dq, dk, dv, dpq, dpk, dgain, d2, d1, dx = torch.ops.ifseg.bias_attention_bwd(
-        gout, q, k, v, pos_q, pos_k, gain, out, lse, gcode, rel2d, rel1d, relx, P, code_bias, grid_w, causal)
-    has = gcode is not None
-    return (dq, dk, dv, dpq, dpk, dgain, None, d2 if has else None, d1 if has else None, dx if has else None,
-            None, None, None, None)
+    nine = torch.ops.ifseg.bias_attention_bwd(gout, q, k, v, pos_q, pos_k, gain, out, lse, gcode, rel2d, rel1d, relx, P, code_bias,
+                                              grid_w, causal)
+    return _attn_grads(nine, gcode, 4)
 
 
 bias_attention.register_autograd(_attn_backward, setup_context=_attn_setup)
@@ -281,9 +299,6 @@ bias_attention.register_autograd(_attn_backward, setup_context=_attn_setup)
 #   torch.ops.ifseg.seg_dice(logits, target, class_weight, hp, wp, H, W, seg_id_offset, dice_weight, smooth)   per-sample soft Dice
 #   torch.ops.ifseg.seg_distill(logits, teacher_logits, target, hp, wp, H, W, seg_id_offset, weight, temperature, mask_all)
 #                                                                                                per-pixel KL to a teacher
-#
-# Every op has ONE check helper that its real and its fake implementation call first: tracing refuses what running refuses,
-# and nothing is launched (the library is not even loaded) before the arguments have passed.
 _pad32 = hip._pad32
 
 
@@ -437,14 +452,11 @@ def attention_bias(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bias: Opti
     Whole leading key blocks of a row may be masked.
     -> (out [B,T,H*64] bf16, lse fp32 [B,H,T] in log2 units, the packed bias operand bf16 [H,T_p,S_p] (not differentiable))"""
     B, T, S, H, Tp, Sp = _attention_bias_check(q, k, v, bias, gain, kv_len, causal, P, dropout_p)
-    prev = _stream_scope(q)
-    try:
+    with _on_stream(q):
         dense = hip.DenseBias(H, T, S, q.device)
         hip.attn_bias_pack(dense, bias, causal=causal, P=P)
         out, lse = _fwd_bi(q, k, v, dense, gain, kv_len, causal, P, dropout_p, seed)
         return out, lse, dense.D
-    finally:
-        hip.set_stream(prev)
 
 
 @attention_bias.register_fake
@@ -461,8 +473,7 @@ def attention_bias_bwd(dout: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v: 
     """-> (dq, dk, dv, dbias, dgain): dbias = sum_b dS in bias's dtype and shape (an empty tensor without a bias; exactly 0
     where the bias is -inf), dgain fp32 [H]"""
     B, T, S, H, Tp, Sp = _attention_bias_check(q, k, v, bias, gain, kv_len, causal, P, dropout_p)
-    prev = _stream_scope(q)
-    try:
+    with _on_stream(q):
         dense = _dense_view(packed, H, T, S)
         dq, dk, dv, slabs, dgr = _bwd_bi(dout, q, k, v, gain, kv_len, out, lse, dense, causal, P, dropout_p, seed, causal)
         if bias is not None:
@@ -471,8 +482,6 @@ def attention_bias_bwd(dout: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v: 
         else:
             dbias = torch.empty(0, dtype=torch.float32, device=q.device)
         return dq, dk, dv, dbias, dgr.sum((0, 2))
-    finally:
-        hip.set_stream(prev)
 
 
 @attention_bias_bwd.register_fake
@@ -512,16 +521,13 @@ def bias_attention_bi(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pos_q: 
     -> (out, lse, the dense operand bf16 [H,T_p,S_p] (not differentiable))"""
     B, T, S, H, Tp, Sp = _bias_attention_bi_check(q, k, v, pos_q, pos_k, gain, gcode, rel2d, rel1d, relx, P, code_bias, grid_w,
                                                   causal, kv_len, dropout_p)
-    prev = _stream_scope(q)
-    try:
+    with _on_stream(q):
         dense = hip.DenseBias(H, T, S, q.device)
         if causal:
             dense.D.fill_(float("-inf"))       # the builder leaves masked tiles that no schedule reads unwritten
         hip.attn_dense_bias(dense, _aligned(pos_q), _aligned(pos_k), rel=_rel(P, gcode, rel2d, rel1d, relx, code_bias, grid_w), causal=causal, P=P)
         out, lse = _fwd_bi(q, k, v, dense, gain, kv_len, causal, P, dropout_p, seed)
         return out, lse, dense.D
-    finally:
-        hip.set_stream(prev)
 
 
 @bias_attention_bi.register_fake
@@ -543,8 +549,7 @@ def bias_attention_bi_bwd(dout: torch.Tensor, q: torch.Tensor, k: torch.Tensor, 
     from ifseg_attn_dbias_grads, the partial tables summed in part order"""
     B, T, S, H, Tp, Sp = _bias_attention_bi_check(q, k, v, pos_q, pos_k, gain, gcode, rel2d, rel1d, relx, P, code_bias, grid_w,
                                                   causal, kv_len, dropout_p)
-    prev = _stream_scope(q)
-    try:
+    with _on_stream(q):
         dev, C = q.device, H * 64
         dense = _dense_view(packed, H, T, S)
         # (zero-filled always: on grids that are not 32 wide the table kernel reads masked pairs of blocks a causal launch skips)
@@ -565,17 +570,13 @@ def bias_attention_bi_bwd(dout: torch.Tensor, q: torch.Tensor, k: torch.Tensor, 
                 t = torch.empty(H, p.shape[2], dtype=torch.float32, device=dev)
                 tabs.append(hip.reduce_parts(p, t, H, p.shape[1], p.shape[2]) if p.shape[2] else t)
         return dq, dk, dv, dpq.to(pos_q.dtype), dpk.to(pos_k.dtype), dgr.sum((0, 2)), tabs[0], tabs[1], tabs[2]
-    finally:
-        hip.set_stream(prev)
 
 
 @bias_attention_bi_bwd.register_fake
 def _(dout, q, k, v, pos_q, pos_k, gain, out, lse, packed, gcode, rel2d, rel1d, relx, P, code_bias, grid_w, causal, kv_len,
       dropout_p, seed):
     _bias_attention_bi_check(q, k, v, pos_q, pos_k, gain, gcode, rel2d, rel1d, relx, P, code_bias, grid_w, causal, kv_len, dropout_p)
-    f = lambda t: q.new_empty(0, dtype=torch.float32) if t is None else t.new_empty(t.shape)
-    return (q.new_empty(q.shape), k.new_empty(k.shape), v.new_empty(v.shape), pos_q.new_empty(pos_q.shape),
-            pos_k.new_empty(pos_k.shape), gain.new_empty(gain.shape, dtype=torch.float32), f(rel2d), f(rel1d), f(relx))
+    return _attn_bwd_fake(q, k, v, pos_q, pos_k, gain, rel2d, rel1d, relx)
 
 
 def _abi_setup(ctx, inputs, output):
@@ -588,19 +589,21 @@ def _abi_setup(ctx, inputs, output):
 def _abi_backward(ctx, gout, glse, gpacked):
     q, k, v, pos_q, pos_k, gain, out, lse, packed, gcode, rel2d, rel1d, relx, kv_len = ctx.saved_tensors
     P, code_bias, grid_w, causal, dropout_p, seed = ctx.meta
-    dq, dk, dv, dpq, dpk, dgain, d2, d1, dx = torch.ops.ifseg.bias_attention_bi_bwd(
-        gout, q, k, v, pos_q, pos_k, gain, out, lse, packed, gcode, rel2d, rel1d, relx, P, code_bias, grid_w, causal, kv_len,
-        dropout_p, seed)
-    has = gcode is not None
-    return (dq, dk, dv, dpq, dpk, dgain, None, d2 if has else None, d1 if has else None, dx if has else None,
-            None, None, None, None, None, None, None)
+    nine = torch.ops.ifseg.bias_attention_bi_bwd(gout, q, k, v, pos_q, pos_k, gain, out, lse, packed, gcode, rel2d, rel1d, relx, P,
+                                                 code_bias, grid_w, causal, kv_len, dropout_p, seed)
+    return _attn_grads(nine, gcode, 7)
 
 
 bias_attention_bi.register_autograd(_abi_backward, setup_context=_abi_setup)
 
 
-# ----------------------------------------------------------------------------------------------- seg_loss
+# ----------------------------------------------------------------------------------------------- the seg-loss family
 SEG_LOSS_MAX_CLASSES = 512       # csrc/loss.hip NS_MAX (criterions.seg_criterion.FUSED_MAX_CLASSES)
+
+
+def _fused_classes_check(op, n, name="n"):
+    if n < 1 or n > SEG_LOSS_MAX_CLASSES:
+        raise ValueError("%s: %s = %d classes, the kernel takes 1 .. FUSED_MAX_CLASSES = %d" % (op, name, n, SEG_LOSS_MAX_CLASSES))
 
 
 def _seg_loss_check(logits, target, hp, wp, H, W):
@@ -613,12 +616,74 @@ def _seg_loss_check(logits, target, hp, wp, H, W):
     if H != 16 * hp or W != 16 * wp:
         raise ValueError("%s: the fused kernel upsamples x16: H = %d, W = %d, expected H == 16 * hp = %d and W == 16 * wp = %d"
                          % (op, H, W, 16 * hp, 16 * wp))
-    if nseg < 1 or nseg > SEG_LOSS_MAX_CLASSES:
-        raise ValueError("%s: nseg = %d classes, the kernel takes 1 .. FUSED_MAX_CLASSES = %d" % (op, nseg, SEG_LOSS_MAX_CLASSES))
+    _fused_classes_check(op, nseg, "nseg")
     if target.dtype != torch.int64 or target.dim() != 2 or target.shape[0] != B or target.shape[1] != H * W + 1:
         raise ValueError("%s: target must be int64 [B, H * W + 1] = [%d, %d], got %s %s"
                          % (op, B, H * W + 1, target.dtype, tuple(target.shape)))
     return B, nseg, (nseg + 7) // 8 * 8
+
+
+def _pixel_weight_check(op, pixel_weight, B, H, W):
+    if pixel_weight is not None and (pixel_weight.dtype != torch.uint8 or tuple(pixel_weight.shape) != (B, H * W)):
+        raise ValueError("%s: pixel_weight must be uint8 [B, H * W] = [%d, %d], got %s %s"
+                         % (op, B, H * W, pixel_weight.dtype, tuple(pixel_weight.shape)))
+
+
+def _class_weight_check(op, class_weight, nseg):
+    if class_weight is not None and (class_weight.dtype != torch.float32 or tuple(class_weight.shape) != (nseg,)):
+        raise ValueError("%s: class_weight must be fp32 [nseg] = [%d], got %s %s"
+                         % (op, nseg, class_weight.dtype, tuple(class_weight.shape)))
+
+
+def _padded_logits(logits, B, P, nseg, npad):
+    """the kernels read 16-byte pieces of a class axis padded to a multiple of 8: a view that already lies in such a buffer is
+    taken as it is, anything else is copied into a zero-filled one"""
+    lp = logits
+    if not (lp.stride(2) == 1 and lp.stride(1) % 8 == 0 and lp.stride(1) >= npad and lp.stride(0) % 8 == 0
+            and lp.data_ptr() % 16 == 0):
+        lp = torch.zeros(B, P + 1, npad, dtype=BF, device=logits.device)
+        lp[:, :, :nseg].copy_(logits)
+    return lp
+
+
+def _seg_loss_fwd(kernel, logits, target, hp, wp, H, W, seg_id_offset, label_smoothing, B, nseg, npad, **weights):
+    """the body of `seg_loss` (kernel = hip.seg_loss) and of `seg_loss_weighted` (hip.seg_loss_weighted, with its weights)"""
+    with _on_stream(logits):
+        dev, P = logits.device, hp * wp
+        lp = _padded_logits(logits, B, P, nseg, npad)
+        n_tiles, nstat = B * P, 2 + 3 * nseg
+        tile = torch.empty(n_tiles * 9 * nseg, dtype=torch.float32, device=dev)
+        sp = torch.empty(n_tiles * nstat, dtype=torch.float32, device=dev)
+        stats = torch.empty(nstat, dtype=torch.float32, device=dev)
+        dl = torch.empty(B, P + 1, npad, dtype=BF, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        kernel(lp, target.contiguous(), hp, wp, H, W, nseg, seg_id_offset, tile, sp, stats, dl, loss, bad_label=bad,
+               label_smoothing=float(label_smoothing), **weights)
+        return loss, stats, dl, bad
+
+
+def _seg_loss_fake(logits, hp, wp, B, nseg, npad):
+    f32 = torch.float32
+    return (logits.new_empty((), dtype=f32), logits.new_empty(2 + 3 * nseg, dtype=f32), logits.new_empty(B, hp * wp + 1, npad),
+            logits.new_empty(1, dtype=torch.int32))
+
+
+def _seg_setup(*constants):
+    """setup_context of the family: dlogits is output 2 everywhere, `constants` are the outputs that carry no gradient"""
+    def setup(ctx, inputs, output):
+        ctx.save_for_backward(output[2])
+        ctx.mark_non_differentiable(*(output[i] for i in constants))
+        ctx.nseg = inputs[0].shape[2]
+    return setup
+
+
+def _seg_backward(n_inputs):
+    """backward of the family: differentiable in logits, the first of the op's n_inputs arguments, only"""
+    def backward(ctx, gloss, *rest):
+        (dl,) = ctx.saved_tensors
+        return (torch.ops.ifseg.seg_loss_bwd(gloss, dl, ctx.nseg),) + (None,) * (n_inputs - 1)
+    return backward
 
 
 @custom_op("ifseg::seg_loss", mutates_args=(), device_types="cuda")
@@ -632,36 +697,13 @@ def seg_loss(logits: torch.Tensor, target: torch.Tensor, hp: int, wp: int, H: in
         bad int32 [1]: non-zero when a label is neither a class nor pad / eos / ignore -- read it when convenient, the op
         does not synchronise).  Differentiable in logits only."""
     B, nseg, npad = _seg_loss_check(logits, target, hp, wp, H, W)
-    prev = _stream_scope(logits)
-    try:
-        dev, P = logits.device, hp * wp
-        # the kernel reads 16-byte pieces of a class axis padded to a multiple of 8: a view that already lies in such a
-        # buffer is taken as it is
-        lp = logits
-        if not (lp.stride(2) == 1 and lp.stride(1) % 8 == 0 and lp.stride(1) >= npad and lp.stride(0) % 8 == 0
-                and lp.data_ptr() % 16 == 0):
-            lp = torch.zeros(B, P + 1, npad, dtype=BF, device=dev)
-            lp[:, :, :nseg].copy_(logits)
-        n_tiles, nstat = B * P, 2 + 3 * nseg
-        tile = torch.empty(n_tiles * 9 * nseg, dtype=torch.float32, device=dev)
-        sp = torch.empty(n_tiles * nstat, dtype=torch.float32, device=dev)
-        stats = torch.empty(nstat, dtype=torch.float32, device=dev)
-        dl = torch.empty(B, P + 1, npad, dtype=BF, device=dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        bad = torch.zeros(1, dtype=torch.int32, device=dev)
-        hip.seg_loss(lp, target.contiguous(), hp, wp, H, W, nseg, seg_id_offset, tile, sp, stats, dl, loss, bad_label=bad,
-                     label_smoothing=float(label_smoothing))
-        return loss, stats, dl, bad
-    finally:
-        hip.set_stream(prev)
+    return _seg_loss_fwd(hip.seg_loss, logits, target, hp, wp, H, W, seg_id_offset, label_smoothing, B, nseg, npad)
 
 
 @seg_loss.register_fake
 def _(logits, target, hp, wp, H, W, seg_id_offset, label_smoothing):
     B, nseg, npad = _seg_loss_check(logits, target, hp, wp, H, W)
-    f32 = torch.float32
-    return (logits.new_empty((), dtype=f32), logits.new_empty(2 + 3 * nseg, dtype=f32), logits.new_empty(B, hp * wp + 1, npad),
-            logits.new_empty(1, dtype=torch.int32))
+    return _seg_loss_fake(logits, hp, wp, B, nseg, npad)
 
 
 @custom_op("ifseg::seg_loss_bwd", mutates_args=(), device_types="cuda")
@@ -676,30 +718,15 @@ def _(grad_loss, dlogits, nseg):
     return dlogits.new_empty(dlogits.shape[0], dlogits.shape[1], nseg)
 
 
-def _sl_setup(ctx, inputs, output):
-    ctx.save_for_backward(output[2])
-    ctx.mark_non_differentiable(output[1], output[2], output[3])
-    ctx.nseg = inputs[0].shape[2]
-
-
-def _sl_backward(ctx, gloss, gstats, gdl, gbad):
-    (dl,) = ctx.saved_tensors
-    return torch.ops.ifseg.seg_loss_bwd(gloss, dl, ctx.nseg), None, None, None, None, None, None, None
-
-
-seg_loss.register_autograd(_sl_backward, setup_context=_sl_setup)
+seg_loss.register_autograd(_seg_backward(8), setup_context=_seg_setup(1, 2, 3))
 
 
 # ----------------------------------------------------------------------------------------------- seg_loss_weighted
 def _seg_loss_weighted_check(logits, target, pixel_weight, class_weight, hp, wp, H, W, label_smoothing):
     op = "ifseg::seg_loss_weighted"
     B, nseg, npad = _seg_loss_check(logits, target, hp, wp, H, W)
-    if pixel_weight is not None and (pixel_weight.dtype != torch.uint8 or tuple(pixel_weight.shape) != (B, H * W)):
-        raise ValueError("%s: pixel_weight must be uint8 [B, H * W] = [%d, %d], got %s %s"
-                         % (op, B, H * W, pixel_weight.dtype, tuple(pixel_weight.shape)))
-    if class_weight is not None and (class_weight.dtype != torch.float32 or tuple(class_weight.shape) != (nseg,)):
-        raise ValueError("%s: class_weight must be fp32 [nseg] = [%d], got %s %s"
-                         % (op, nseg, class_weight.dtype, tuple(class_weight.shape)))
+    _pixel_weight_check(op, pixel_weight, B, H, W)
+    _class_weight_check(op, class_weight, nseg)
     if not (0.0 <= label_smoothing <= 1.0):
         raise ValueError("%s: label_smoothing must lie in [0, 1], got %r" % (op, label_smoothing))
     return B, nseg, npad
@@ -717,53 +744,24 @@ def seg_loss_weighted(logits: torch.Tensor, target: torch.Tensor, pixel_weight: 
     -> (loss, stats, dlogits, bad) as `seg_loss`, with stats[0] the weighted sum, stats[1] = Z and the area histograms
     counted over the valid pixels whatever their weights.  Differentiable in logits only."""
     B, nseg, npad = _seg_loss_weighted_check(logits, target, pixel_weight, class_weight, hp, wp, H, W, label_smoothing)
-    prev = _stream_scope(logits)
-    try:
-        dev, P = logits.device, hp * wp
-        lp = logits
-        if not (lp.stride(2) == 1 and lp.stride(1) % 8 == 0 and lp.stride(1) >= npad and lp.stride(0) % 8 == 0
-                and lp.data_ptr() % 16 == 0):
-            lp = torch.zeros(B, P + 1, npad, dtype=BF, device=dev)
-            lp[:, :, :nseg].copy_(logits)
-        n_tiles, nstat = B * P, 2 + 3 * nseg
-        tile = torch.empty(n_tiles * 9 * nseg, dtype=torch.float32, device=dev)
-        sp = torch.empty(n_tiles * nstat, dtype=torch.float32, device=dev)
-        stats = torch.empty(nstat, dtype=torch.float32, device=dev)
-        dl = torch.empty(B, P + 1, npad, dtype=BF, device=dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        bad = torch.zeros(1, dtype=torch.int32, device=dev)
-        hip.seg_loss_weighted(lp, target.contiguous(), hp, wp, H, W, nseg, seg_id_offset, tile, sp, stats, dl, loss,
-                              pixel_weight=pixel_weight.contiguous() if pixel_weight is not None else None,
-                              class_weight=class_weight.contiguous() if class_weight is not None else None,
-                              norm_pixels=norm_pixels, bad_label=bad, label_smoothing=float(label_smoothing))
-        return loss, stats, dl, bad
-    finally:
-        hip.set_stream(prev)
+    return _seg_loss_fwd(hip.seg_loss_weighted, logits, target, hp, wp, H, W, seg_id_offset, label_smoothing, B, nseg, npad,
+                         pixel_weight=_c(pixel_weight), class_weight=_c(class_weight), norm_pixels=norm_pixels)
 
 
 @seg_loss_weighted.register_fake
 def _(logits, target, pixel_weight, class_weight, hp, wp, H, W, seg_id_offset, label_smoothing, norm_pixels):
     B, nseg, npad = _seg_loss_weighted_check(logits, target, pixel_weight, class_weight, hp, wp, H, W, label_smoothing)
-    f32 = torch.float32
-    return (logits.new_empty((), dtype=f32), logits.new_empty(2 + 3 * nseg, dtype=f32), logits.new_empty(B, hp * wp + 1, npad),
-            logits.new_empty(1, dtype=torch.int32))
+    return _seg_loss_fake(logits, hp, wp, B, nseg, npad)
 
 
-def _slw_backward(ctx, gloss, gstats, gdl, gbad):
-    (dl,) = ctx.saved_tensors
-    return (torch.ops.ifseg.seg_loss_bwd(gloss, dl, ctx.nseg),) + (None,) * 10
-
-
-seg_loss_weighted.register_autograd(_slw_backward, setup_context=_sl_setup)
+seg_loss_weighted.register_autograd(_seg_backward(11), setup_context=_seg_setup(1, 2, 3))
 
 
 # ----------------------------------------------------------------------------------------------- seg_ohem
 def _seg_ohem_check(logits, target, pixel_weight, hp, wp, H, W, thresh, min_kept):
     op = "ifseg::seg_ohem"
     B, nseg, npad = _seg_loss_check(logits, target, hp, wp, H, W)
-    if pixel_weight is not None and (pixel_weight.dtype != torch.uint8 or tuple(pixel_weight.shape) != (B, H * W)):
-        raise ValueError("%s: pixel_weight must be uint8 [B, H * W] = [%d, %d], got %s %s"
-                         % (op, B, H * W, pixel_weight.dtype, tuple(pixel_weight.shape)))
+    _pixel_weight_check(op, pixel_weight, B, H, W)
     hip.check_ohem(thresh, min_kept)
     return B, nseg, npad
 
@@ -777,13 +775,10 @@ def seg_ohem(logits: torch.Tensor, target: torch.Tensor, pixel_weight: Optional[
     pixels, 0 on the others; info int64 [4]: valid pixels, kept pixels, the bits of tau and of the k-th value), fresh tensors.
     The selection is a constant of the step: not differentiable."""
     B, nseg, npad = _seg_ohem_check(logits, target, pixel_weight, hp, wp, H, W, thresh, min_kept)
-    prev = _stream_scope(logits)
-    try:
+    with _on_stream(logits):
         lp = logits if logits.stride(2) == 1 else logits.contiguous()
         hard = hip.seg_hardness(lp, target.contiguous(), hp, wp, H, W, nseg, seg_id_offset)
-        return hip.ohem_select(hard, thresh, min_kept, weight=pixel_weight.contiguous() if pixel_weight is not None else None)
-    finally:
-        hip.set_stream(prev)
+        return hip.ohem_select(hard, thresh, min_kept, weight=_c(pixel_weight))
 
 
 @seg_ohem.register_fake
@@ -796,9 +791,7 @@ def _(logits, target, pixel_weight, hp, wp, H, W, seg_id_offset, thresh, min_kep
 def _seg_dice_check(logits, target, class_weight, hp, wp, H, W, dice_weight, smooth):
     op = "ifseg::seg_dice"
     B, nseg, npad = _seg_loss_check(logits, target, hp, wp, H, W)
-    if class_weight is not None and (class_weight.dtype != torch.float32 or tuple(class_weight.shape) != (nseg,)):
-        raise ValueError("%s: class_weight must be fp32 [nseg] = [%d], got %s %s"
-                         % (op, nseg, class_weight.dtype, tuple(class_weight.shape)))
+    _class_weight_check(op, class_weight, nseg)
     hip.check_dice(dice_weight, smooth, op)
     return B, nseg, npad
 
@@ -813,20 +806,13 @@ def seg_dice(logits: torch.Tensor, target: torch.Tensor, class_weight: Optional[
         dlogits bf16 [B, hp*wp+1, nseg rounded up to 8] = d loss / d logits, padding columns and the eos row zero), fresh tensors.
     Differentiable in logits only."""
     B, nseg, npad = _seg_dice_check(logits, target, class_weight, hp, wp, H, W, dice_weight, smooth)
-    prev = _stream_scope(logits)
-    try:
-        dev, P = logits.device, hp * wp
-        lp = logits
-        if not (lp.stride(2) == 1 and lp.stride(1) % 8 == 0 and lp.stride(1) >= npad and lp.stride(0) % 8 == 0
-                and lp.data_ptr() % 16 == 0):
-            lp = torch.zeros(B, P + 1, npad, dtype=BF, device=dev)
-            lp[:, :, :nseg].copy_(logits)
-        bufs = {"dl": torch.empty(B, P + 1, npad, dtype=BF, device=dev)}
+    with _on_stream(logits):
+        P = hp * wp
+        lp = _padded_logits(logits, B, P, nseg, npad)
+        bufs = {"dl": torch.empty(B, P + 1, npad, dtype=BF, device=logits.device)}
         loss, dl = hip.seg_dice(lp, target.contiguous(), hp, wp, H, W, nseg, seg_id_offset, dice_weight, smooth,
-                                class_weight=class_weight.contiguous() if class_weight is not None else None, bufs=bufs)
+                                class_weight=_c(class_weight), bufs=bufs)
         return loss.clone(), bufs["dice_sums"], dl
-    finally:
-        hip.set_stream(prev)
 
 
 @seg_dice.register_fake
@@ -836,18 +822,7 @@ def _(logits, target, class_weight, hp, wp, H, W, seg_id_offset, dice_weight, sm
     return (logits.new_empty((), dtype=f32), logits.new_empty((B, 3, nseg), dtype=f32), logits.new_empty(B, hp * wp + 1, npad))
 
 
-def _sd_setup(ctx, inputs, output):
-    ctx.save_for_backward(output[2])
-    ctx.mark_non_differentiable(output[1], output[2])
-    ctx.nseg = inputs[0].shape[2]
-
-
-def _sd_backward(ctx, gloss, gsums, gdl):
-    (dl,) = ctx.saved_tensors
-    return (torch.ops.ifseg.seg_loss_bwd(gloss, dl, ctx.nseg),) + (None,) * 9
-
-
-seg_dice.register_autograd(_sd_backward, setup_context=_sd_setup)
+seg_dice.register_autograd(_seg_backward(10), setup_context=_seg_setup(1, 2))
 
 
 # ----------------------------------------------------------------------------------------------- seg_distill
@@ -881,23 +856,16 @@ def seg_distill(logits: torch.Tensor, teacher_logits: torch.Tensor, target: Opti
         dlogits bf16 [B, hp*wp+1, nseg rounded up to 8] = d loss / d logits, padding columns and the eos row zero), fresh tensors.
     Differentiable in logits only: the teacher gets no gradient."""
     B, nseg, npad = _seg_distill_check(logits, teacher_logits, target, hp, wp, H, W, weight, temperature, mask_all)
-    prev = _stream_scope(logits)
-    try:
-        dev, P = logits.device, hp * wp
-        lp = logits
-        if not (lp.stride(2) == 1 and lp.stride(1) % 8 == 0 and lp.stride(1) >= npad and lp.stride(0) % 8 == 0
-                and lp.data_ptr() % 16 == 0):
-            lp = torch.zeros(B, P + 1, npad, dtype=BF, device=dev)
-            lp[:, :, :nseg].copy_(logits)
+    with _on_stream(logits):
+        P = hp * wp
+        lp = _padded_logits(logits, B, P, nseg, npad)
         tp = teacher_logits.detach()
         if tp.stride(2) != 1:
             tp = tp.contiguous()
-        bufs = {"dl": torch.empty(B, P + 1, npad, dtype=BF, device=dev)}
-        loss, dl = hip.seg_distill(lp, tp, target.contiguous() if target is not None else None, hp, wp, H, W, nseg, seg_id_offset,
-                                   weight, temperature, "all" if mask_all else "valid", bufs=bufs)
+        bufs = {"dl": torch.empty(B, P + 1, npad, dtype=BF, device=logits.device)}
+        loss, dl = hip.seg_distill(lp, tp, _c(target), hp, wp, H, W, nseg, seg_id_offset, weight, temperature,
+                                   "all" if mask_all else "valid", bufs=bufs)
         return loss.clone(), bufs["kd_stats"], dl
-    finally:
-        hip.set_stream(prev)
 
 
 @seg_distill.register_fake
@@ -907,19 +875,59 @@ def _(logits, teacher_logits, target, hp, wp, H, W, seg_id_offset, weight, tempe
     return (logits.new_empty((), dtype=f32), logits.new_empty((2,), dtype=f32), logits.new_empty(B, hp * wp + 1, npad))
 
 
-def _skd_backward(ctx, gloss, gstats, gdl):
-    (dl,) = ctx.saved_tensors
-    return (torch.ops.ifseg.seg_loss_bwd(gloss, dl, ctx.nseg),) + (None,) * 10
+seg_distill.register_autograd(_seg_backward(11), setup_context=_seg_setup(1, 2))
 
 
-seg_distill.register_autograd(_skd_backward, setup_context=_sd_setup)
+# ------------------------------------------------------------------ the predict / score family: what its checks and outputs share
+def _label_dtype(n):
+    return torch.uint8 if n <= 256 else torch.int16
+
+
+def _scores_f32_check(op, s, view=None):
+    if s.dtype != torch.float32:
+        raise ValueError("%s: scores must be fp32 (hip.rows_to_f32 / hip.neighbour_smoothing give it), %s dtype %s"
+                         % (op, "got" if view is None else "view %d has" % view, s.dtype))
+
+
+def _views_count_check(op, K):
+    if K < 1 or K > hip.SEG_PREDICT_MAX_VIEWS:
+        raise ValueError("%s: %d views, the kernel takes 1 .. %d" % (op, K, hip.SEG_PREDICT_MAX_VIEWS))
+
+
+def _label_map_check(op, B, h, w):
+    if h < 1 or w < 1 or B * h * w >= 2 ** 31:
+        raise ValueError("%s: the label map [%d, %d, %d] must have 1 <= h, w and B * h * w < 2**31" % (op, B, h, w))
+
+
+def _triple(labels, conf, probs, device):
+    """(labels, conf, probs) of a predict kernel as an op returns them"""
+    return labels, _or_empty(conf, torch.float32, device), _or_empty(probs, torch.float32, device)
+
+
+def _five(scored, n, device):
+    """(areas, tally, labels, conf, probs) of a score kernel as an op returns them"""
+    areas, tally, labels, conf, probs = scored
+    return (areas, tally) + _triple(_or_empty(labels, _label_dtype(n), device), conf, probs, device)
+
+
+def _fake_triple(like, lead, n, h, w, ldt, want_conf, want_probs, want_labels=True):
+    """the fake (labels, conf, probs); lead = (B,), or () for the single image of seg_pamr"""
+    f32 = torch.float32
+    return (like.new_empty(lead + (h, w) if want_labels else (0,), dtype=ldt),
+            like.new_empty(lead + (h, w) if want_conf else (0,), dtype=f32),
+            like.new_empty(lead + (n, h, w) if want_probs else (0,), dtype=f32))
+
+
+def _fake_five(like, B, n, ldt, gt, want_labels, want_conf, want_probs):
+    """the fake (areas, tally, labels, conf, probs) of a score op, at the ground truth's size"""
+    return ((like.new_empty((3, n), dtype=torch.int64), like.new_empty((2,), dtype=torch.int64))
+            + _fake_triple(like, (B,), n, gt.shape[1], gt.shape[2], ldt, want_conf, want_probs, want_labels))
 
 
 # ----------------------------------------------------------------------------------------------- seg_predict
 def _seg_predict_check(scores, hp, wp, h, w):
     op = "ifseg::seg_predict"
-    if scores.dtype != torch.float32:
-        raise ValueError("%s: scores must be fp32 (hip.rows_to_f32 / hip.neighbour_smoothing give it), got dtype %s" % (op, scores.dtype))
+    _scores_f32_check(op, scores)
     if scores.dim() != 3:
         raise ValueError("%s: scores must be [B, hp*wp, n], got %s" % (op, tuple(scores.shape)))
     B, P, n = scores.shape
@@ -927,11 +935,9 @@ def _seg_predict_check(scores, hp, wp, h, w):
         raise ValueError("%s: empty batch" % op)
     if hp <= 0 or wp <= 0 or P != hp * wp:
         raise ValueError("%s: scores.shape[1] = %d, expected hp * wp = %d" % (op, P, hp * wp))
-    if n < 1 or n > SEG_LOSS_MAX_CLASSES:
-        raise ValueError("%s: n = %d classes, the kernel takes 1 .. FUSED_MAX_CLASSES = %d" % (op, n, SEG_LOSS_MAX_CLASSES))
-    if h < 1 or w < 1 or B * h * w >= 2 ** 31:
-        raise ValueError("%s: the label map [%d, %d, %d] must have 1 <= h, w and B * h * w < 2**31" % (op, B, h, w))
-    return B, n, (torch.uint8 if n <= 256 else torch.int16)
+    _fused_classes_check(op, n)
+    _label_map_check(op, B, h, w)
+    return B, n, _label_dtype(n)
 
 
 @custom_op("ifseg::seg_predict", mutates_args=(), device_types="cuda")
@@ -942,34 +948,25 @@ def seg_predict(scores: torch.Tensor, hp: int, wp: int, h: int, w: int, want_con
     -> (labels [B, h, w] uint8 (n <= 256) or int16, conf fp32 [B, h, w] = the winning value, probs fp32 [B, n, h, w] = every
     interpolated value); an output that was not asked for is an empty tensor.  Not differentiable."""
     _seg_predict_check(scores, hp, wp, h, w)
-    prev = _stream_scope(scores)
-    try:
-        labels, conf, probs = hip.seg_predict(scores.contiguous(), hp, wp, h, w, conf=want_conf, probs=want_probs)
-        e = lambda t: torch.empty(0, dtype=torch.float32, device=scores.device) if t is None else t
-        return labels, e(conf), e(probs)
-    finally:
-        hip.set_stream(prev)
+    with _on_stream(scores):
+        return _triple(*hip.seg_predict(scores.contiguous(), hp, wp, h, w, conf=want_conf, probs=want_probs), scores.device)
 
 
 @seg_predict.register_fake
 def _(scores, hp, wp, h, w, want_conf, want_probs):
     B, n, ldt = _seg_predict_check(scores, hp, wp, h, w)
-    f32 = torch.float32
-    return (scores.new_empty(B, h, w, dtype=ldt), scores.new_empty((B, h, w) if want_conf else (0,), dtype=f32),
-            scores.new_empty((B, n, h, w) if want_probs else (0,), dtype=f32))
+    return _fake_triple(scores, (B,), n, h, w, ldt, want_conf, want_probs)
 
 
 # ----------------------------------------------------------------------------------------------- seg_predict_views
 def _seg_predict_views_check(scores, hps, wps, flips, h, w):
     op = "ifseg::seg_predict_views"
     K = len(scores)
-    if K < 1 or K > hip.SEG_PREDICT_MAX_VIEWS:
-        raise ValueError("%s: %d views, the kernel takes 1 .. %d" % (op, K, hip.SEG_PREDICT_MAX_VIEWS))
+    _views_count_check(op, K)
     if len(hps) != K or len(wps) != K or len(flips) != K:
         raise ValueError("%s: %d views with %d hps, %d wps and %d flips (one of each per view)" % (op, K, len(hps), len(wps), len(flips)))
     for k, (s, hp, wp) in enumerate(zip(scores, hps, wps)):
-        if s.dtype != torch.float32:
-            raise ValueError("%s: scores must be fp32 (hip.rows_to_f32 / hip.neighbour_smoothing give it), view %d has dtype %s" % (op, k, s.dtype))
+        _scores_f32_check(op, s, k)
         if s.dim() != 3:
             raise ValueError("%s: scores must be [B, hp*wp, n], view %d is %s" % (op, k, tuple(s.shape)))
         if s.shape[0] != scores[0].shape[0] or s.shape[2] != scores[0].shape[2]:
@@ -979,11 +976,13 @@ def _seg_predict_views_check(scores, hps, wps, flips, h, w):
     B, _, n = scores[0].shape
     if B == 0:
         raise ValueError("%s: empty batch" % op)
-    if n < 1 or n > SEG_LOSS_MAX_CLASSES:
-        raise ValueError("%s: n = %d classes, the kernel takes 1 .. FUSED_MAX_CLASSES = %d" % (op, n, SEG_LOSS_MAX_CLASSES))
-    if h < 1 or w < 1 or B * h * w >= 2 ** 31:
-        raise ValueError("%s: the label map [%d, %d, %d] must have 1 <= h, w and B * h * w < 2**31" % (op, B, h, w))
-    return B, n, (torch.uint8 if n <= 256 else torch.int16)
+    _fused_classes_check(op, n)
+    _label_map_check(op, B, h, w)
+    return B, n, _label_dtype(n)
+
+
+def _views_list(scores, hps, wps, flips):
+    return [(s.contiguous(), hp, wp, bool(f)) for s, hp, wp, f in zip(scores, hps, wps, flips)]
 
 
 @custom_op("ifseg::seg_predict_views", mutates_args=(), device_types="cuda")
@@ -993,22 +992,15 @@ def seg_predict_views(scores: Sequence[torch.Tensor], hps: Sequence[int], wps: S
     along the width when flips[k]; every view is resized as `seg_predict` does, the mean over the views (fp32, in view order)
     is what labels, conf and probs are taken from, in one launch.  Outputs and conventions as `seg_predict`.  Not differentiable."""
     _seg_predict_views_check(scores, hps, wps, flips, h, w)
-    prev = _stream_scope(scores[0])
-    try:
-        views = [(s.contiguous(), hp, wp, bool(f)) for s, hp, wp, f in zip(scores, hps, wps, flips)]
-        labels, conf, probs = hip.seg_predict_views(views, h, w, conf=want_conf, probs=want_probs)
-        e = lambda t: torch.empty(0, dtype=torch.float32, device=scores[0].device) if t is None else t
-        return labels, e(conf), e(probs)
-    finally:
-        hip.set_stream(prev)
+    with _on_stream(scores[0]):
+        return _triple(*hip.seg_predict_views(_views_list(scores, hps, wps, flips), h, w, conf=want_conf, probs=want_probs),
+                       scores[0].device)
 
 
 @seg_predict_views.register_fake
 def _(scores, hps, wps, flips, h, w, want_conf, want_probs):
     B, n, ldt = _seg_predict_views_check(scores, hps, wps, flips, h, w)
-    f32, s = torch.float32, scores[0]
-    return (s.new_empty(B, h, w, dtype=ldt), s.new_empty((B, h, w) if want_conf else (0,), dtype=f32),
-            s.new_empty((B, n, h, w) if want_probs else (0,), dtype=f32))
+    return _fake_triple(scores[0], (B,), n, h, w, ldt, want_conf, want_probs)
 
 
 # ----------------------------------------------------------------------------------------------- seg_areas
@@ -1017,13 +1009,48 @@ def _gt_check(op, gt):
         raise ValueError("%s: ground truth must be uint8 or int16 (label PNG values or class ids), got dtype %s" % (op, gt.dtype))
 
 
-def _maps_check(op, labels, conf=None, gt=None):
-    """a predicted label map and what lies beside it, its confidences and / or its ground truth: one shape, 1 .. 2**31 - 1 pixels"""
+def _score_check(op, gt, predict_check):
+    """the check of a score op: the ground truth's dtype and [B, h, w], its predict op's check at that h x w (predict_check(h, w)
+    -> (B, n, label dtype)), then the ground truth's batch"""
+    _gt_check(op, gt)
+    if gt.dim() != 3:
+        raise ValueError("%s: ground truth must be [B, h, w], got %s" % (op, tuple(gt.shape)))
+    B, n, ldt = predict_check(gt.shape[1], gt.shape[2])
+    if gt.shape[0] != B:
+        raise ValueError("%s: ground truth %s for a batch of %d" % (op, tuple(gt.shape), B))
+    return B, n, ldt
+
+
+def _labels_dtype_check(op, labels):
     if labels.dtype not in (torch.uint8, torch.int16):
         raise ValueError("%s: labels must be uint8 or int16 (what seg_predict gives), got dtype %s" % (op, labels.dtype))
+
+
+def _conf_check(op, labels, conf):
     if conf is not None and (conf.dtype != torch.float32 or conf.shape != labels.shape):
         raise ValueError("%s: conf must be float32 of the labels' shape %s, got %s %s"
                          % (op, tuple(labels.shape), conf.dtype, tuple(conf.shape)))
+
+
+def _map_shape_check(op, labels):
+    if labels.dim() not in (2, 3) or labels.numel() < 1 or labels.numel() >= 2 ** 31:
+        raise ValueError("%s: labels must be [H, W] or [B, H, W] with 1 <= pixels < 2**31, got %s" % (op, tuple(labels.shape)))
+
+
+def _boundary_check(op, boundary):
+    if not 0 <= boundary <= hip.SEG_RENDER_MAX_BOUNDARY:
+        raise ValueError("%s: boundary must be in 0 .. %d, got %d" % (op, hip.SEG_RENDER_MAX_BOUNDARY, boundary))
+
+
+def _classes_check(op, n):
+    if n < 1 or n > hip.SEG_PREDICT_MAX_CLASSES:
+        raise ValueError("%s: n = %d classes, the kernel takes 1 .. %d" % (op, n, hip.SEG_PREDICT_MAX_CLASSES))
+
+
+def _maps_check(op, labels, conf=None, gt=None):
+    """a predicted label map and what lies beside it, its confidences and / or its ground truth: one shape, 1 .. 2**31 - 1 pixels"""
+    _labels_dtype_check(op, labels)
+    _conf_check(op, labels, conf)
     if gt is not None:
         _gt_check(op, gt)
         if labels.shape != gt.shape:
@@ -1034,8 +1061,7 @@ def _maps_check(op, labels, conf=None, gt=None):
 
 def _seg_areas_check(labels, gt, n, op="ifseg::seg_areas"):
     _maps_check(op, labels, gt=gt)
-    if n < 1 or n > SEG_LOSS_MAX_CLASSES:
-        raise ValueError("%s: n = %d classes, the kernel takes 1 .. FUSED_MAX_CLASSES = %d" % (op, n, SEG_LOSS_MAX_CLASSES))
+    _fused_classes_check(op, n)
 
 
 @custom_op("ifseg::seg_areas", mutates_args=(), device_types="cuda")
@@ -1045,11 +1071,8 @@ def seg_areas(labels: torch.Tensor, gt: torch.Tensor, n: int, raw_labels: bool) 
     pixels, pixels with a ground truth out of range), fresh tensors; `ifseg_amd.predict.areas_reference` is the specification.
     Integer inputs: not differentiable."""
     _seg_areas_check(labels, gt, n)
-    prev = _stream_scope(labels)
-    try:
+    with _on_stream(labels):
         return hip.seg_areas(labels.contiguous(), gt.contiguous(), n, raw_labels)
-    finally:
-        hip.set_stream(prev)
 
 
 @seg_areas.register_fake
@@ -1066,11 +1089,8 @@ def seg_confusion(labels: torch.Tensor, gt: torch.Tensor, n: int, raw_labels: bo
     labels outside [0, n); a fresh tensor.  `ifseg_amd.predict.confusion_reference` is the specification.  Integer inputs:
     not differentiable."""
     _seg_areas_check(labels, gt, n, "ifseg::seg_confusion")
-    prev = _stream_scope(labels)
-    try:
+    with _on_stream(labels):
         return hip.seg_confusion(labels.contiguous(), gt.contiguous(), n, raw_labels)
-    finally:
-        hip.set_stream(prev)
 
 
 @seg_confusion.register_fake
@@ -1096,11 +1116,8 @@ def seg_boundary_areas(labels: torch.Tensor, gt: torch.Tensor, n: int, d: int, r
     ground truth, band uint8 of the maps' shape = bit 0 in the ground truth's band, bit 1 in the labels'), fresh tensors;
     `ifseg_amd.predict.boundary_areas_reference` is the specification.  Integer inputs: not differentiable."""
     _seg_boundary_check(labels, gt, n, d)
-    prev = _stream_scope(labels)
-    try:
+    with _on_stream(labels):
         return hip.seg_boundary_areas(labels.contiguous(), gt.contiguous(), n, d, raw_labels, band=True)
-    finally:
-        hip.set_stream(prev)
 
 
 @seg_boundary_areas.register_fake
@@ -1111,14 +1128,7 @@ def _(labels, gt, n, d, raw_labels):
 
 # ----------------------------------------------------------------------------------------------- seg_score_views
 def _seg_score_views_check(scores, hps, wps, flips, gt):
-    op = "ifseg::seg_score_views"
-    _gt_check(op, gt)
-    if gt.dim() != 3:
-        raise ValueError("%s: ground truth must be [B, h, w], got %s" % (op, tuple(gt.shape)))
-    B, n, ldt = _seg_predict_views_check(scores, hps, wps, flips, gt.shape[1], gt.shape[2])
-    if gt.shape[0] != B:
-        raise ValueError("%s: ground truth %s for a batch of %d" % (op, tuple(gt.shape), B))
-    return B, n, ldt
+    return _score_check("ifseg::seg_score_views", gt, lambda h, w: _seg_predict_views_check(scores, hps, wps, flips, h, w))
 
 
 @custom_op("ifseg::seg_score_views", mutates_args=(), device_types="cuda")
@@ -1129,34 +1139,22 @@ def seg_score_views(scores: Sequence[torch.Tensor], hps: Sequence[int], wps: Seq
     in the kernel's epilogue (a single view is K = 1) -> (areas, tally, labels, conf, probs): the counters of `seg_areas`,
     fresh, and the outputs of `seg_predict_views`, each an empty tensor when it was not asked for.  Not differentiable."""
     _seg_score_views_check(scores, hps, wps, flips, gt)
-    prev = _stream_scope(scores[0])
-    try:
-        views = [(s.contiguous(), hp, wp, bool(f)) for s, hp, wp, f in zip(scores, hps, wps, flips)]
-        areas, tally, labels, conf, probs = hip.seg_score_views(views, gt.contiguous(), raw_labels, labels=want_labels,
-                                                                conf=want_conf, probs=want_probs)
-        e = lambda t, dt: torch.empty(0, dtype=dt, device=gt.device) if t is None else t
-        ldt = torch.uint8 if scores[0].shape[2] <= 256 else torch.int16
-        return areas, tally, e(labels, ldt), e(conf, torch.float32), e(probs, torch.float32)
-    finally:
-        hip.set_stream(prev)
+    with _on_stream(scores[0]):
+        return _five(hip.seg_score_views(_views_list(scores, hps, wps, flips), gt.contiguous(), raw_labels, labels=want_labels,
+                                         conf=want_conf, probs=want_probs), scores[0].shape[2], gt.device)
 
 
 @seg_score_views.register_fake
 def _(scores, hps, wps, flips, gt, raw_labels, want_labels, want_conf, want_probs):
     B, n, ldt = _seg_score_views_check(scores, hps, wps, flips, gt)
-    f32, s, (h, w) = torch.float32, scores[0], gt.shape[1:]
-    return (s.new_empty((3, n), dtype=torch.int64), s.new_empty((2,), dtype=torch.int64),
-            s.new_empty((B, h, w) if want_labels else (0,), dtype=ldt), s.new_empty((B, h, w) if want_conf else (0,), dtype=f32),
-            s.new_empty((B, n, h, w) if want_probs else (0,), dtype=f32))
+    return _fake_five(scores[0], B, n, ldt, gt, want_labels, want_conf, want_probs)
 
 
 # ----------------------------------------------------------------------------------------------- seg_render
 def _seg_render_check(labels, image, palette, opacity, boundary, boundary_color, conf):
     op = "ifseg::seg_render"
-    if labels.dtype not in (torch.uint8, torch.int16):
-        raise ValueError("%s: labels must be uint8 or int16 (what seg_predict gives), got dtype %s" % (op, labels.dtype))
-    if labels.dim() not in (2, 3) or labels.numel() < 1 or labels.numel() >= 2 ** 31:
-        raise ValueError("%s: labels must be [H, W] or [B, H, W] with 1 <= pixels < 2**31, got %s" % (op, tuple(labels.shape)))
+    _labels_dtype_check(op, labels)
+    _map_shape_check(op, labels)
     if image.dtype != torch.uint8 or tuple(image.shape) != tuple(labels.shape) + (3,):
         raise ValueError("%s: the image must be uint8 %s (HWC, the labels' shape), got %s %s"
                          % (op, tuple(labels.shape) + (3,), image.dtype, tuple(image.shape)))
@@ -1165,13 +1163,10 @@ def _seg_render_check(labels, image, palette, opacity, boundary, boundary_color,
                          % (op, hip.SEG_PREDICT_MAX_CLASSES, palette.dtype, tuple(palette.shape)))
     if not 0.0 <= opacity <= 1.0:
         raise ValueError("%s: opacity must be in [0, 1], got %r" % (op, opacity))
-    if not 0 <= boundary <= hip.SEG_RENDER_MAX_BOUNDARY:
-        raise ValueError("%s: boundary must be in 0 .. %d, got %d" % (op, hip.SEG_RENDER_MAX_BOUNDARY, boundary))
+    _boundary_check(op, boundary)
     if len(boundary_color) != 3 or any(not 0 <= c <= 255 for c in boundary_color):
         raise ValueError("%s: boundary_color must be three ints in 0 .. 255, got %s" % (op, list(boundary_color)))
-    if conf is not None and (conf.dtype != torch.float32 or conf.shape != labels.shape):
-        raise ValueError("%s: conf must be float32 of the labels' shape %s, got %s %s"
-                         % (op, tuple(labels.shape), conf.dtype, tuple(conf.shape)))
+    _conf_check(op, labels, conf)
 
 
 @custom_op("ifseg::seg_render", mutates_args=(), device_types="cuda")
@@ -1182,12 +1177,9 @@ def seg_render(labels: torch.Tensor, image: torch.Tensor, palette: torch.Tensor,
     in `boundary_color` -> uint8 [.., H, W, 3], a fresh tensor; `ifseg_amd.predict.render_reference` is the specification.
     Integer inputs: not differentiable."""
     _seg_render_check(labels, image, palette, opacity, boundary, boundary_color, conf)
-    prev = _stream_scope(labels)
-    try:
+    with _on_stream(labels):
         return hip.seg_render(labels.contiguous(), image.contiguous(), palette.contiguous(), opacity, boundary,
-                              tuple(int(c) for c in boundary_color), conf=None if conf is None else conf.contiguous())
-    finally:
-        hip.set_stream(prev)
+                              tuple(int(c) for c in boundary_color), conf=_c(conf))
 
 
 @seg_render.register_fake
@@ -1197,34 +1189,32 @@ def _(labels, image, palette, opacity, boundary, boundary_color, conf):
 
 
 # ----------------------------------------------------------------------------------------------- seg_conf_hist, seg_pseudo
+def _seg_conf_hist_check(labels, conf, n):
+    op = "ifseg::seg_conf_hist"
+    _maps_check(op, labels, conf)
+    _classes_check(op, n)
+
+
 @custom_op("ifseg::seg_conf_hist", mutates_args=(), device_types="cuda")
 def seg_conf_hist(labels: torch.Tensor, conf: torch.Tensor, n: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """predicted labels (uint8 / int16) with their confidences (fp32, the same shape) (csrc/pseudo.hip) -> (hist int64 [n, 256] =
     pixels per (label, clamp(floor(conf * 256), 0, 255)), tally int64 [2] = labels inside / outside [0, n)), fresh tensors;
     `ifseg_amd.predict.confidence_histogram_reference` is the specification.  Counts: not differentiable."""
-    _maps_check("ifseg::seg_conf_hist", labels, conf)
-    if n < 1 or n > hip.SEG_PREDICT_MAX_CLASSES:
-        raise ValueError("ifseg::seg_conf_hist: n = %d classes, the kernel takes 1 .. %d" % (n, hip.SEG_PREDICT_MAX_CLASSES))
-    prev = _stream_scope(labels)
-    try:
+    _seg_conf_hist_check(labels, conf, n)
+    with _on_stream(labels):
         return hip.seg_conf_hist(labels.contiguous(), conf.contiguous(), n)
-    finally:
-        hip.set_stream(prev)
 
 
 @seg_conf_hist.register_fake
 def _(labels, conf, n):
-    _maps_check("ifseg::seg_conf_hist", labels, conf)
-    if n < 1 or n > hip.SEG_PREDICT_MAX_CLASSES:
-        raise ValueError("ifseg::seg_conf_hist: n = %d classes, the kernel takes 1 .. %d" % (n, hip.SEG_PREDICT_MAX_CLASSES))
+    _seg_conf_hist_check(labels, conf, n)
     return labels.new_empty((n, hip.SEG_CONF_BINS), dtype=torch.int64), labels.new_empty((2,), dtype=torch.int64)
 
 
 def _seg_calibration_check(labels, conf, gt, n):
     op = "ifseg::seg_calibration"
     _maps_check(op, labels, conf, gt)
-    if n < 1 or n > hip.SEG_PREDICT_MAX_CLASSES:
-        raise ValueError("%s: n = %d classes, the kernel takes 1 .. %d" % (op, n, hip.SEG_PREDICT_MAX_CLASSES))
+    _classes_check(op, n)
 
 
 @custom_op("ifseg::seg_calibration", mutates_args=(), device_types="cuda")
@@ -1235,11 +1225,8 @@ def seg_calibration(labels: torch.Tensor, conf: torch.Tensor, gt: torch.Tensor, 
     clamp(floor(conf * 256), 0, 255), label == gt class), tally int64 [2] = scored pixels with a label inside / outside [0, n)),
     fresh tensors; `ifseg_amd.predict.calibration_reference` is the specification.  Counts: not differentiable."""
     _seg_calibration_check(labels, conf, gt, n)
-    prev = _stream_scope(labels)
-    try:
+    with _on_stream(labels):
         return hip.seg_calibration(labels.contiguous(), conf.contiguous(), gt.contiguous(), n, raw_labels)
-    finally:
-        hip.set_stream(prev)
 
 
 @seg_calibration.register_fake
@@ -1255,8 +1242,7 @@ def _seg_temperature_sweep_check(grids, hp, wp, gt):
     K, B, P, n = grids.shape
     if not 1 <= K <= hip.SEG_SWEEP_MAX_TEMPERATURES:
         raise ValueError("%s: K = %d grids, the kernel takes 1 .. %d" % (op, K, hip.SEG_SWEEP_MAX_TEMPERATURES))
-    if n < 1 or n > hip.SEG_PREDICT_MAX_CLASSES:
-        raise ValueError("%s: n = %d classes, the kernel takes 1 .. %d" % (op, n, hip.SEG_PREDICT_MAX_CLASSES))
+    _classes_check(op, n)
     if hp < 1 or wp < 1 or B < 1 or P != hp * wp:
         raise ValueError("%s: grids %s do not hold B >= 1 grids of %d x %d patches" % (op, tuple(grids.shape), hp, wp))
     _gt_check(op, gt)
@@ -1274,11 +1260,8 @@ def seg_temperature_sweep(grids: torch.Tensor, hp: int, wp: int, gt: torch.Tenso
     scored pixels, pixels with a ground truth out of range), fresh tensors; `ifseg_amd.predict.temperature_sweep_reference` is
     the specification.  Counts and sums for choosing a temperature: no autograd."""
     _seg_temperature_sweep_check(grids, hp, wp, gt)
-    prev = _stream_scope(grids)
-    try:
+    with _on_stream(grids):
         return hip.seg_temperature_sweep(grids.contiguous(), hp, wp, gt.contiguous(), raw_labels)
-    finally:
-        hip.set_stream(prev)
 
 
 @seg_temperature_sweep.register_fake
@@ -1298,8 +1281,7 @@ def _seg_pseudo_check(labels, conf, thresholds, n, boundary, raw_labels):
                          % (op, n, hip.seg_pseudo_max_classes(raw_labels), raw_labels))
     if thresholds.dtype != torch.int32 or tuple(thresholds.shape) != (n,):
         raise ValueError("%s: thresholds must be int32 [%d], got %s %s" % (op, n, thresholds.dtype, tuple(thresholds.shape)))
-    if not 0 <= boundary <= hip.SEG_RENDER_MAX_BOUNDARY:
-        raise ValueError("%s: boundary must be in 0 .. %d, got %d" % (op, hip.SEG_RENDER_MAX_BOUNDARY, boundary))
+    _boundary_check(op, boundary)
 
 
 @custom_op("ifseg::seg_pseudo", mutates_args=(), device_types="cuda")
@@ -1310,11 +1292,8 @@ def seg_pseudo(labels: torch.Tensor, conf: torch.Tensor, thresholds: torch.Tenso
     the pixel is not kept; kept int64 [2, n]: kept and predicted pixels per class), fresh tensors;
     `ifseg_amd.predict.pseudo_label_reference` is the specification.  Integer outputs: not differentiable."""
     _seg_pseudo_check(labels, conf, thresholds, n, boundary, raw_labels)
-    prev = _stream_scope(labels)
-    try:
+    with _on_stream(labels):
         return hip.seg_pseudo(labels.contiguous(), conf.contiguous(), thresholds.contiguous(), n, boundary, raw_labels)
-    finally:
-        hip.set_stream(prev)
 
 
 @seg_pseudo.register_fake
@@ -1328,8 +1307,7 @@ def _seg_regions_check(labels, connectivity, op="ifseg::seg_regions", dtypes=(to
     if labels.dtype not in dtypes:
         raise ValueError("%s: labels must be %s, got dtype %s" % (op, " or ".join(str(d).replace("torch.", "") for d in dtypes),
                                                                  labels.dtype))
-    if labels.dim() not in (2, 3) or labels.numel() < 1 or labels.numel() >= 2 ** 31:
-        raise ValueError("%s: labels must be [H, W] or [B, H, W] with 1 <= pixels < 2**31, got %s" % (op, tuple(labels.shape)))
+    _map_shape_check(op, labels)
     if connectivity not in (4, 8):
         raise ValueError("%s: connectivity must be 4 or 8, got %d" % (op, connectivity))
 
@@ -1340,11 +1318,8 @@ def seg_regions(labels: torch.Tensor, connectivity: int) -> Tuple[torch.Tensor, 
     pixel the smallest y W + x of its region inside its image, size int32 = the region's pixel count), fresh tensors of the
     labels' shape; `ifseg_amd.predict.regions_reference` is the specification.  Integer outputs: not differentiable."""
     _seg_regions_check(labels, connectivity)
-    prev = _stream_scope(labels)
-    try:
+    with _on_stream(labels):
         return hip.seg_regions(labels.contiguous(), connectivity)
-    finally:
-        hip.set_stream(prev)
 
 
 @seg_regions.register_fake
@@ -1373,11 +1348,8 @@ def seg_region_drop(labels: torch.Tensor, connectivity: int, min_region: int, fi
     `regions_reference`'s sizes is the specification.  A weight plane goes through `hip.seg_region_drop`, which zeroes it in
     place.  Integer outputs: not differentiable."""
     _seg_region_drop_check(labels, connectivity, min_region, fill, n)
-    prev = _stream_scope(labels)
-    try:
+    with _on_stream(labels):
         return hip.seg_region_drop(labels.contiguous(), connectivity, min_region, fill, n, raw_labels)
-    finally:
-        hip.set_stream(prev)
 
 
 @seg_region_drop.register_fake
@@ -1394,8 +1366,7 @@ def _seg_pamr_check(probs, image, iters, dilations):
         raise ValueError("%s: probs must be float32 [n, H, W] (one image of seg_predict's probs), got %s %s"
                          % (op, probs.dtype, tuple(probs.shape)))
     n, H, W = probs.shape
-    if n < 1 or n > hip.SEG_PREDICT_MAX_CLASSES:
-        raise ValueError("%s: n = %d classes, the kernel takes 1 .. %d" % (op, n, hip.SEG_PREDICT_MAX_CLASSES))
+    _classes_check(op, n)
     if image.dtype != torch.uint8 or tuple(image.shape) != (H, W, 3):
         raise ValueError("%s: the image must be uint8 %s (HWC, at the values' resolution), got %s %s"
                          % (op, (H, W, 3), image.dtype, tuple(image.shape)))
@@ -1407,7 +1378,7 @@ def _seg_pamr_check(probs, image, iters, dilations):
                          % (op, hip.SEG_PAMR_MAX_DILATIONS, hip.SEG_PAMR_MAX_DILATION, list(dilations)))
     if H < 1 or W < 1 or n * H * W >= 2 ** 31 or 8 * D * H * W >= 2 ** 31:
         raise ValueError("%s: [%d, %d, %d] values under %d dilations: n H W and 8 D H W must stay below 2**31" % (op, n, H, W, D))
-    return n, H, W, (torch.uint8 if n <= 256 else torch.int16)
+    return n, H, W, _label_dtype(n)
 
 
 @custom_op("ifseg::seg_pamr", mutates_args=(), device_types="cuda")
@@ -1417,25 +1388,25 @@ def seg_pamr(probs: torch.Tensor, image: torch.Tensor, iters: int, dilations: Se
     uint8 (n <= 256) or int16, conf fp32 [H, W], the refined values fp32 [n, H, W]), fresh tensors; an output that was not asked
     for is an empty tensor.  `ifseg_amd.predict.pamr_reference` is the specification.  No autograd."""
     _seg_pamr_check(probs, image, iters, dilations)
-    prev = _stream_scope(probs)
-    try:
-        labels, conf, out = hip.seg_pamr(probs.contiguous(), image.contiguous(), iters, tuple(int(d) for d in dilations),
-                                         conf=want_conf, probs_out=want_probs)
-        e = lambda t: torch.empty(0, dtype=torch.float32, device=probs.device) if t is None else t
-        return labels, e(conf), e(out)
-    finally:
-        hip.set_stream(prev)
+    with _on_stream(probs):
+        return _triple(*hip.seg_pamr(probs.contiguous(), image.contiguous(), iters, tuple(int(d) for d in dilations),
+                                     conf=want_conf, probs_out=want_probs), probs.device)
 
 
 @seg_pamr.register_fake
 def _(probs, image, iters, dilations, want_conf, want_probs):
     n, H, W, ldt = _seg_pamr_check(probs, image, iters, dilations)
-    f32 = torch.float32
-    return (probs.new_empty((H, W), dtype=ldt), probs.new_empty((H, W) if want_conf else (0,), dtype=f32),
-            probs.new_empty((n, H, W) if want_probs else (0,), dtype=f32))
+    return _fake_triple(probs, (), n, H, W, ldt, want_conf, want_probs)
 
 
 # ----------------------------------------------------------------------------------------------- image_load
+def _norm_check(op, mean, std, dtype):
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("%s: mean and std must have three entries, got %d and %d" % (op, len(mean), len(std)))
+    if dtype not in (torch.float32, BF):
+        raise ValueError("%s: the output dtype must be torch.float32 or torch.bfloat16, got %s" % (op, dtype))
+
+
 def _image_load_check(images, oh, ow, mean, std, dtype, op="ifseg::image_load"):
     if images.dtype != torch.uint8:
         raise ValueError("%s: images must be uint8 (raw grey levels; normalised floats go to the model as they are), got dtype %s"
@@ -1450,10 +1421,7 @@ def _image_load_check(images, oh, ow, mean, std, dtype, op="ifseg::image_load"):
     if B * H0 * W0 * 3 >= 2 ** 31 or B * 3 * oh * ow >= 2 ** 31 or 2 * H0 * oh >= 2 ** 31 or 2 * W0 * ow >= 2 ** 31:
         raise ValueError("%s: B * H0 * W0 * 3, B * 3 * oh * ow, 2 * H0 * oh and 2 * W0 * ow must stay below 2**31, got %s -> %d x %d"
                          % (op, tuple(images.shape), oh, ow))
-    if len(mean) != 3 or len(std) != 3:
-        raise ValueError("%s: mean and std must have three entries, got %d and %d" % (op, len(mean), len(std)))
-    if dtype not in (torch.float32, BF):
-        raise ValueError("%s: the output dtype must be torch.float32 or torch.bfloat16, got %s" % (op, dtype))
+    _norm_check(op, mean, std, dtype)
     return B
 
 
@@ -1464,11 +1432,8 @@ def image_load(images: torch.Tensor, oh: int, ow: int, mean: Sequence[float], st
     (fp32 / bf16) by bilinear resize (align_corners=False), rounding to a grey level, optional channel reversal and
     (x / 255 - mean) / std.  The input is integer: not differentiable."""
     _image_load_check(images, oh, ow, mean, std, dtype)
-    prev = _stream_scope(images)
-    try:
+    with _on_stream(images):
         return hip.image_load(images.contiguous(), oh, ow, mean, std, reverse_channels, dtype)
-    finally:
-        hip.set_stream(prev)
 
 
 @image_load.register_fake
@@ -1491,8 +1456,7 @@ def _slide_check(op, oh, ow, crop, stride):
 
 
 def _seg_predict_windows_check(scores, hpw, wpw, oh, ow, crop, stride, h, w, op="ifseg::seg_predict_windows"):
-    if scores.dtype != torch.float32:
-        raise ValueError("%s: scores must be fp32 (hip.rows_to_f32 / hip.neighbour_smoothing give it), got dtype %s" % (op, scores.dtype))
+    _scores_f32_check(op, scores)
     if scores.dim() != 4:
         raise ValueError("%s: scores must be [B, Nw, hpw*wpw, n], got %s" % (op, tuple(scores.shape)))
     B, Nw, P, n = scores.shape
@@ -1505,11 +1469,9 @@ def _seg_predict_windows_check(scores, hpw, wpw, oh, ow, crop, stride, h, w, op=
         raise ValueError("%s: scores.shape[2] = %d, expected hpw * wpw = %d" % (op, P, hpw * wpw))
     if Nw * P >= 2 ** 22:
         raise ValueError("%s: Nw * hpw * wpw = %d must stay below 2**22" % (op, Nw * P))
-    if n < 1 or n > SEG_LOSS_MAX_CLASSES:
-        raise ValueError("%s: n = %d classes, the kernel takes 1 .. FUSED_MAX_CLASSES = %d" % (op, n, SEG_LOSS_MAX_CLASSES))
-    if h < 1 or w < 1 or B * h * w >= 2 ** 31:
-        raise ValueError("%s: the label map [%d, %d, %d] must have 1 <= h, w and B * h * w < 2**31" % (op, B, h, w))
-    return B, n, (torch.uint8 if n <= 256 else torch.int16)
+    _fused_classes_check(op, n)
+    _label_map_check(op, B, h, w)
+    return B, n, _label_dtype(n)
 
 
 @custom_op("ifseg::seg_predict_windows", mutates_args=(), device_types="cuda")
@@ -1519,33 +1481,20 @@ def seg_predict_windows(scores: torch.Tensor, hpw: int, wpw: int, oh: int, ow: i
     window k of `imageio.slide_windows(oh, ow, crop, stride)`; the windows are resized, averaged where they overlap and the
     result resized to h x w in one launch.  Outputs and conventions as `seg_predict`.  Not differentiable."""
     _seg_predict_windows_check(scores, hpw, wpw, oh, ow, crop, stride, h, w)
-    prev = _stream_scope(scores)
-    try:
-        labels, conf, probs = hip.seg_predict_windows(scores.contiguous(), hpw, wpw, oh, ow, tuple(crop), tuple(stride), h, w,
-                                                      conf=want_conf, probs=want_probs)
-        e = lambda t: torch.empty(0, dtype=torch.float32, device=scores.device) if t is None else t
-        return labels, e(conf), e(probs)
-    finally:
-        hip.set_stream(prev)
+    with _on_stream(scores):
+        return _triple(*hip.seg_predict_windows(scores.contiguous(), hpw, wpw, oh, ow, tuple(crop), tuple(stride), h, w,
+                                                conf=want_conf, probs=want_probs), scores.device)
 
 
 @seg_predict_windows.register_fake
 def _(scores, hpw, wpw, oh, ow, crop, stride, h, w, want_conf, want_probs):
     B, n, ldt = _seg_predict_windows_check(scores, hpw, wpw, oh, ow, crop, stride, h, w)
-    f32 = torch.float32
-    return (scores.new_empty(B, h, w, dtype=ldt), scores.new_empty((B, h, w) if want_conf else (0,), dtype=f32),
-            scores.new_empty((B, n, h, w) if want_probs else (0,), dtype=f32))
+    return _fake_triple(scores, (B,), n, h, w, ldt, want_conf, want_probs)
 
 
 def _seg_score_windows_check(scores, hpw, wpw, oh, ow, crop, stride, gt):
     op = "ifseg::seg_score_windows"
-    _gt_check(op, gt)
-    if gt.dim() != 3:
-        raise ValueError("%s: ground truth must be [B, h, w], got %s" % (op, tuple(gt.shape)))
-    B, n, ldt = _seg_predict_windows_check(scores, hpw, wpw, oh, ow, crop, stride, gt.shape[1], gt.shape[2], op)
-    if gt.shape[0] != B:
-        raise ValueError("%s: ground truth %s for a batch of %d" % (op, tuple(gt.shape), B))
-    return B, n, ldt
+    return _score_check(op, gt, lambda h, w: _seg_predict_windows_check(scores, hpw, wpw, oh, ow, crop, stride, h, w, op))
 
 
 @custom_op("ifseg::seg_score_windows", mutates_args=(), device_types="cuda")
@@ -1555,25 +1504,16 @@ def seg_score_windows(scores: torch.Tensor, hpw: int, wpw: int, oh: int, ow: int
     """`seg_predict_windows` at the shape of the ground truth gt (uint8 / int16 [B, h, w]) with the label map counted against
     it in the kernel's epilogue -> (areas, tally, labels, conf, probs) as `seg_score_views`.  Not differentiable."""
     _seg_score_windows_check(scores, hpw, wpw, oh, ow, crop, stride, gt)
-    prev = _stream_scope(scores)
-    try:
-        areas, tally, labels, conf, probs = hip.seg_score_windows(scores.contiguous(), hpw, wpw, oh, ow, tuple(crop), tuple(stride),
-                                                                  gt.contiguous(), raw_labels, labels=want_labels, conf=want_conf,
-                                                                  probs=want_probs)
-        e = lambda t, dt: torch.empty(0, dtype=dt, device=gt.device) if t is None else t
-        ldt = torch.uint8 if scores.shape[3] <= 256 else torch.int16
-        return areas, tally, e(labels, ldt), e(conf, torch.float32), e(probs, torch.float32)
-    finally:
-        hip.set_stream(prev)
+    with _on_stream(scores):
+        return _five(hip.seg_score_windows(scores.contiguous(), hpw, wpw, oh, ow, tuple(crop), tuple(stride), gt.contiguous(),
+                                           raw_labels, labels=want_labels, conf=want_conf, probs=want_probs),
+                     scores.shape[3], gt.device)
 
 
 @seg_score_windows.register_fake
 def _(scores, hpw, wpw, oh, ow, crop, stride, gt, raw_labels, want_labels, want_conf, want_probs):
     B, n, ldt = _seg_score_windows_check(scores, hpw, wpw, oh, ow, crop, stride, gt)
-    f32, s, (h, w) = torch.float32, scores, gt.shape[1:]
-    return (s.new_empty((3, n), dtype=torch.int64), s.new_empty((2,), dtype=torch.int64),
-            s.new_empty((B, h, w) if want_labels else (0,), dtype=ldt), s.new_empty((B, h, w) if want_conf else (0,), dtype=f32),
-            s.new_empty((B, n, h, w) if want_probs else (0,), dtype=f32))
+    return _fake_five(scores, B, n, ldt, gt, want_labels, want_conf, want_probs)
 
 
 def _image_load_windows_check(images, oh, ow, crop, stride, mean, std, dtype):
@@ -1592,11 +1532,8 @@ def image_load_windows(images: torch.Tensor, oh: int, ow: int, crop: Sequence[in
     `dtype`, the slices of `image_load`'s [B, 3, oh, ow] at the windows of `imageio.slide_windows(oh, ow, crop, stride)`, bit
     for bit.  The input is integer: not differentiable."""
     _image_load_windows_check(images, oh, ow, crop, stride, mean, std, dtype)
-    prev = _stream_scope(images)
-    try:
+    with _on_stream(images):
         return hip.image_load_windows(images.contiguous(), oh, ow, tuple(crop), tuple(stride), mean, std, reverse_channels, dtype)
-    finally:
-        hip.set_stream(prev)
 
 
 @image_load_windows.register_fake
@@ -1608,8 +1545,7 @@ def _(images, oh, ow, crop, stride, mean, std, reverse_channels, dtype):
 # ----------------------------------------------------------------------------------------------- views of sliding windows
 def _seg_predict_slide_views_check(scores, hpws, wpws, ohs, ows, flips, crop, stride, h, w, op="ifseg::seg_predict_slide_views"):
     K = len(scores)
-    if K < 1 or K > hip.SEG_PREDICT_MAX_VIEWS:
-        raise ValueError("%s: %d views, the kernel takes 1 .. %d" % (op, K, hip.SEG_PREDICT_MAX_VIEWS))
+    _views_count_check(op, K)
     if any(len(x) != K for x in (hpws, wpws, ohs, ows, flips)):
         raise ValueError("%s: %d views with %d hpws, %d wpws, %d ohs, %d ows and %d flips (one of each per view)"
                          % (op, K, len(hpws), len(wpws), len(ohs), len(ows), len(flips)))
@@ -1633,33 +1569,21 @@ def seg_predict_slide_views(scores: Sequence[torch.Tensor], hpws: Sequence[int],
     as `seg_predict_windows` does, normalised over the classes when `softmax` (mmseg's order), and the mean over the views is
     what labels, conf and probs are taken from, in one launch.  Outputs and conventions as `seg_predict`.  Not differentiable."""
     _seg_predict_slide_views_check(scores, hpws, wpws, ohs, ows, flips, crop, stride, h, w)
-    prev = _stream_scope(scores[0])
-    try:
-        labels, conf, probs = hip.seg_predict_slide_views(_slide_views_list(scores, hpws, wpws, ohs, ows, flips), tuple(crop),
-                                                          tuple(stride), h, w, softmax, conf=want_conf, probs=want_probs)
-        e = lambda t: torch.empty(0, dtype=torch.float32, device=scores[0].device) if t is None else t
-        return labels, e(conf), e(probs)
-    finally:
-        hip.set_stream(prev)
+    with _on_stream(scores[0]):
+        return _triple(*hip.seg_predict_slide_views(_slide_views_list(scores, hpws, wpws, ohs, ows, flips), tuple(crop),
+                                                    tuple(stride), h, w, softmax, conf=want_conf, probs=want_probs),
+                       scores[0].device)
 
 
 @seg_predict_slide_views.register_fake
 def _(scores, hpws, wpws, ohs, ows, flips, crop, stride, h, w, softmax, want_conf, want_probs):
     B, n, ldt = _seg_predict_slide_views_check(scores, hpws, wpws, ohs, ows, flips, crop, stride, h, w)
-    f32, s = torch.float32, scores[0]
-    return (s.new_empty(B, h, w, dtype=ldt), s.new_empty((B, h, w) if want_conf else (0,), dtype=f32),
-            s.new_empty((B, n, h, w) if want_probs else (0,), dtype=f32))
+    return _fake_triple(scores[0], (B,), n, h, w, ldt, want_conf, want_probs)
 
 
 def _seg_score_slide_views_check(scores, hpws, wpws, ohs, ows, flips, crop, stride, gt):
     op = "ifseg::seg_score_slide_views"
-    _gt_check(op, gt)
-    if gt.dim() != 3:
-        raise ValueError("%s: ground truth must be [B, h, w], got %s" % (op, tuple(gt.shape)))
-    B, n, ldt = _seg_predict_slide_views_check(scores, hpws, wpws, ohs, ows, flips, crop, stride, gt.shape[1], gt.shape[2], op)
-    if gt.shape[0] != B:
-        raise ValueError("%s: ground truth %s for a batch of %d" % (op, tuple(gt.shape), B))
-    return B, n, ldt
+    return _score_check(op, gt, lambda h, w: _seg_predict_slide_views_check(scores, hpws, wpws, ohs, ows, flips, crop, stride, h, w, op))
 
 
 @custom_op("ifseg::seg_score_slide_views", mutates_args=(), device_types="cuda")
@@ -1670,37 +1594,16 @@ def seg_score_slide_views(scores: Sequence[torch.Tensor], hpws: Sequence[int], w
     """`seg_predict_slide_views` at the shape of the ground truth gt (uint8 / int16 [B, h, w]) with the label map counted
     against it in the kernel's epilogue -> (areas, tally, labels, conf, probs) as `seg_score_views`.  Not differentiable."""
     _seg_score_slide_views_check(scores, hpws, wpws, ohs, ows, flips, crop, stride, gt)
-    prev = _stream_scope(scores[0])
-    try:
-        areas, tally, labels, conf, probs = hip.seg_score_slide_views(_slide_views_list(scores, hpws, wpws, ohs, ows, flips),
-                                                                      tuple(crop), tuple(stride), gt.contiguous(), softmax,
-                                                                      raw_labels, labels=want_labels, conf=want_conf,
-                                                                      probs=want_probs)
-        e = lambda t, dt: torch.empty(0, dtype=dt, device=gt.device) if t is None else t
-        ldt = torch.uint8 if scores[0].shape[3] <= 256 else torch.int16
-        return areas, tally, e(labels, ldt), e(conf, torch.float32), e(probs, torch.float32)
-    finally:
-        hip.set_stream(prev)
+    with _on_stream(scores[0]):
+        return _five(hip.seg_score_slide_views(_slide_views_list(scores, hpws, wpws, ohs, ows, flips), tuple(crop), tuple(stride),
+                                               gt.contiguous(), softmax, raw_labels, labels=want_labels, conf=want_conf,
+                                               probs=want_probs), scores[0].shape[3], gt.device)
 
 
 @seg_score_slide_views.register_fake
 def _(scores, hpws, wpws, ohs, ows, flips, crop, stride, gt, softmax, raw_labels, want_labels, want_conf, want_probs):
     B, n, ldt = _seg_score_slide_views_check(scores, hpws, wpws, ohs, ows, flips, crop, stride, gt)
-    f32, s, (h, w) = torch.float32, scores[0], gt.shape[1:]
-    return (s.new_empty((3, n), dtype=torch.int64), s.new_empty((2,), dtype=torch.int64),
-            s.new_empty((B, h, w) if want_labels else (0,), dtype=ldt), s.new_empty((B, h, w) if want_conf else (0,), dtype=f32),
-            s.new_empty((B, n, h, w) if want_probs else (0,), dtype=f32))
-
-
-# --------------------------------------------- the training input path (train_load, mix_*, strong_*): what its ops share
-@contextlib.contextmanager
-def _on_stream(where):
-    """the kernels inside run on PyTorch's current stream of a tensor's device, or of the device itself"""
-    prev = hip.set_stream(torch.cuda.current_stream(where.device if torch.is_tensor(where) else where).cuda_stream)
-    try:
-        yield
-    finally:
-        hip.set_stream(prev)
+    return _fake_five(scores[0], B, n, ldt, gt, want_labels, want_conf, want_probs)
 
 
 # ----------------------------------------------------------------------------------------------- train_load
@@ -1723,10 +1626,7 @@ def _train_load_check(images, labels, params, P, nseg, mean, std, dtype):
         raise ValueError("%s: P must be a multiple of 16 in 16 .. 4096 with B * 3 * P * P < 2**31, got P = %d, B = %d" % (op, P, B))
     if not 1 <= nseg <= 255:
         raise ValueError("%s: nseg must lie in 1 .. 255 (uint8 label maps), got %d" % (op, nseg))
-    if len(mean) != 3 or len(std) != 3:
-        raise ValueError("%s: mean and std must have three entries, got %d and %d" % (op, len(mean), len(std)))
-    if dtype not in (torch.float32, BF):
-        raise ValueError("%s: the output dtype must be torch.float32 or torch.bfloat16, got %s" % (op, dtype))
+    _norm_check(op, mean, std, dtype)
     return B
 
 
@@ -1797,10 +1697,9 @@ def mix_apply(records: torch.Tensor, src_images: torch.Tensor, src_target: torch
     A copy of bits: not differentiable."""
     _mix_apply_check(records, src_images, src_target, src_weight, dst_images, dst_target, dst_weight, nseg)
     with _on_stream(records):
-        c = lambda t: None if t is None else t.contiguous()
-        img, tgt, wgt = hip.mix_apply(records.contiguous(), c(src_images), c(src_target), c(dst_images), c(dst_target), nseg,
-                                      seg_id_offset, src_weight=c(src_weight), dst_weight=c(dst_weight))
-        return img, tgt, torch.empty(0, dtype=torch.uint8, device=records.device) if wgt is None else wgt
+        img, tgt, wgt = hip.mix_apply(records.contiguous(), _c(src_images), _c(src_target), _c(dst_images), _c(dst_target), nseg,
+                                      seg_id_offset, src_weight=_c(src_weight), dst_weight=_c(dst_weight))
+        return img, tgt, _or_empty(wgt, torch.uint8, records.device)
 
 
 @mix_apply.register_fake
