@@ -2017,6 +2017,69 @@ def seg_region_drop(labels, connectivity=4, min_region=1, fill=255, n=None, raw_
     return out, dropped, size
 
 
+# --------------------------------------------------------------------------- the sieve of a label map (csrc/sieve.hip)
+SEG_SIEVE_MAX_PASSES = 8            # == SV_MAX_PASSES: the passes of a call at most
+SEG_SIEVE_MAX_CLASSES = 512         # == SV_MAX_CLASSES: the classes of the moved counter
+
+
+def seg_sieve_limits():
+    """-> (a tile's rows, a tile's columns, the passes of a call at most, the largest n) as the loaded library states them
+    (`ifseg_seg_sieve_limit`): 16, 64, SEG_SIEVE_MAX_PASSES and SEG_SIEVE_MAX_CLASSES, which the tests hold against it"""
+    return _limits("ifseg_seg_sieve_limit", 4)
+
+
+def seg_sieve(labels, min_region, connectivity=4, passes=1, ignore=None, n=None, raw_labels=False, conf=None, out=None,
+              moved=None, flag=None):
+    """labels uint8 / int16 [H, W] or [B, H, W] -> (out of the labels' dtype and shape, moved int64 [2, n]): the sieve filter
+    (csrc/sieve.hip; `predict.sieve_reference` is the specification and states the rule): per pass every connected region
+    (connectivity 4 or 8) of fewer than min_region pixels whose value is not `ignore` takes the value of its 4-adjacent
+    neighbour region with the largest key (size, -root), if that key exceeds its own; `passes` (1 .. SEG_SIEVE_MAX_PASSES)
+    repeats it on the result.  Per pass `seg_regions`' launches and three more, on the current stream; nothing synchronises,
+    and the result is canonical, so two calls give equal bits.
+    conf fp32 of the labels' shape: set to 0 IN PLACE where out != labels.  moved[0, c] / moved[1, c]: the pixels that left /
+    joined class c (value - 1 with raw_labels, else the value; values outside [0, n) are not counted); given: ACCUMULATED
+    into.  n None: SEG_SIEVE_MAX_CLASSES.  out: written in place when given; it must not overlap labels.  flag: as in
+    `seg_regions`.  The work planes are allocated here: four int32 and one uint64 of the labels' shape, and with passes > 1 one
+    more map of the labels' dtype (about 25 bytes per pixel live during a call).  Bad arguments: ValueError, before anything is
+    launched."""
+    what = "seg_sieve"
+    B, H, W = _region_maps(what, labels, connectivity, (torch.uint8, torch.int16))
+    if not isinstance(min_region, int) or isinstance(min_region, bool) or not 1 <= min_region < 2 ** 31:
+        raise ValueError("%s: min_region must be an int in 1 .. 2**31 - 1 (1 moves nothing), got %r" % (what, min_region))
+    if not isinstance(passes, int) or isinstance(passes, bool) or not 1 <= passes <= SEG_SIEVE_MAX_PASSES:
+        raise ValueError("%s: passes must be an int in 1 .. %d, got %r" % (what, SEG_SIEVE_MAX_PASSES, passes))
+    if ignore is not None and (not isinstance(ignore, int) or isinstance(ignore, bool)):
+        raise ValueError("%s: ignore must be None or an int, got %r" % (what, ignore))
+    if n is None:
+        n = SEG_SIEVE_MAX_CLASSES
+    if not isinstance(n, int) or isinstance(n, bool) or not 1 <= n <= SEG_SIEVE_MAX_CLASSES:
+        raise ValueError("%s: n must be an int in 1 .. %d, got %r" % (what, SEG_SIEVE_MAX_CLASSES, n))
+    dev = labels.device
+    out = _region_plane(what, "out", out, labels, labels.dtype)
+    if conf is not None:
+        _region_plane(what, "conf", conf, labels, torch.float32)
+        if _overlap(conf, out):
+            raise ValueError("%s: conf overlaps out" % what)
+    if moved is None:
+        moved = torch.zeros(2, n, dtype=torch.int64, device=dev)
+    elif not torch.is_tensor(moved) or moved.dtype != torch.int64 or tuple(moved.shape) != (2, n) \
+            or not moved.is_contiguous() or moved.device != dev:
+        raise ValueError("%s: moved must be a contiguous int64 [2, %d] tensor on %s, got %s" % (
+            what, n, dev, (moved.dtype, tuple(moved.shape), moved.device) if torch.is_tensor(moved) else type(moved)))
+    flag = _region_flag(what, flag, dev)
+    lo, hi = (0, 255) if labels.dtype == torch.uint8 else (-2 ** 15, 2 ** 15 - 1)
+    has_ignore = ignore is not None and lo <= ignore <= hi      # a value the map cannot hold ignores nothing
+    work = torch.empty(4, B, H, W, dtype=torch.int32, device=dev)
+    best = torch.empty(B, H, W, dtype=torch.int64, device=dev)
+    tmp = torch.empty_like(labels) if passes > 1 else None
+    _check(lib().ifseg_seg_sieve(_ptr(labels), c_int(labels.element_size()), c_int(B), c_int(H), c_int(W), c_int(connectivity),
+                                 c_int(min_region), c_int(passes), c_int(ignore if has_ignore else 0),
+                                 c_int(1 if has_ignore else 0), c_int(n), c_int(1 if raw_labels else 0), _ptr(work[0]),
+                                 _ptr(work[1]), _ptr(work[2]), _ptr(work[3]), _ptr(best), _ptr(tmp), _ptr(out), _ptr(conf),
+                                 _ptr(moved), _ptr(flag), _stream()), "seg_sieve")
+    return out, moved
+
+
 # --------------------------------------------------------------------------- pixel-adaptive mask refinement (csrc/pamr.hip)
 SEG_PAMR_MAX_DILATIONS = 8          # == PM_MAX_D: the dilations of a call at most (8 neighbours each)
 SEG_PAMR_MAX_DILATION = 32          # == PM_MAX_DILATION: the largest dilation (a tile's halo: 40 KiB of LDS)

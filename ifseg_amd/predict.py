@@ -933,6 +933,106 @@ def region_drop_reference(labels, size, min_region, fill=255, n=None, raw_labels
     return out, dropped
 
 
+def _passes_arg(what, passes):
+    if not isinstance(passes, int) or isinstance(passes, bool) or passes < 1:
+        raise ValueError("%s: passes must be an int >= 1, got %r" % (what, passes))
+    return passes
+
+
+def _sieve_pass(lab, K, conn, ignore):
+    """one pass of `sieve_reference` on lab int64 [B, H, W] -> the new map"""
+    B, H, W = lab.shape
+    dev = lab.device
+    root, size = regions_reference(lab, conn)
+    root, size = root.reshape(B, H, W).long(), size.reshape(B, H, W).long()
+    offs = torch.arange(B, dtype=torch.int64, device=dev).reshape(B, 1, 1) * (H * W)
+    key = size * (1 << 32) + ((1 << 32) - 1 - root)                 # (size, -root), lexicographic; size < 2^31
+    live = torch.ones_like(lab, dtype=torch.bool) if ignore is None else lab != ignore
+    small = (size < K) & live
+    best = torch.zeros(B * H * W, dtype=torch.int64, device=dev)    # per region, at its root: the largest key that may take it
+    slot = root + offs
+    for dy, dx in ((0, 1), (1, 0)):                                 # always 4-adjacency, both ways
+        if dy >= H or dx >= W:
+            continue
+        a = (slice(None), slice(0, H - dy), slice(0, W - dx))
+        b = (slice(None), slice(dy, H), slice(dx, W))
+        for here, there in ((a, b), (b, a)):
+            vote = small[here] & (slot[here] != slot[there]) & live[there] & (key[there] > key[here])
+            best.scatter_reduce_(0, slot[here][vote], key[there][vote], "amax")
+    won = best[slot]
+    take = small & (won > 0)
+    winner = (1 << 32) - 1 - (won & ((1 << 32) - 1)) + offs          # the winning neighbour's root pixel
+    return torch.where(take, lab.reshape(-1)[torch.where(take, winner, slot)], lab)
+
+
+def sieve_reference(labels, min_region, connectivity=4, passes=1, ignore=None, n=None, raw_labels=False, conf=None):
+    """Specification of hip.seg_sieve: labels integer [H, W] (or [B, H, W]) -> (out, moved) or, with a conf plane (labels'
+    shape), (out, moved, conf).  The sieve filter GIS users know from gdal_sieve, in a form whose result does not depend on any
+    order of processing: small regions take the value of their largest neighbour.
+
+    One pass, per image, everything decided from the pass's input map at once:
+      1. root, size = `regions_reference(labels, connectivity)`.  Every region has the key (size, -root), compared
+         lexicographically; keys are unique within an image.
+      2. A region R is small iff size < min_region and its value is not `ignore` (None: no value is).
+      3. The neighbours of R are the regions Q != R that hold a pixel one step in x or y from a pixel of R -- 4-adjacency
+         whatever `connectivity` is, so a neighbour always differs in value -- inside the same image; regions of the value
+         `ignore` are never neighbours.
+      4. R takes the value of the neighbour with the largest key, and only if that key is larger than R's own; otherwise it
+         stays.  So two small regions never swap (the smaller joins the larger), a region of min_region pixels or more is never
+         relabelled and only grows, and no pixel ever becomes `ignore`.
+    `passes` (an int >= 1) repeats this on the previous pass's output, the regions recomputed each time.
+      out    the labels' dtype and shape
+      moved  int64 [2, n], the final map against the input: moved[0, c] the pixels that were class c and are not any more,
+             moved[1, c] those that are class c and were not; class = value - 1 with raw_labels, else the value; values
+             outside [0, n) are not counted.  n None: hip.SEG_SIEVE_MAX_CLASSES
+      conf   0 where out != labels, untouched elsewhere: the model never stated a confidence for the label such a pixel
+             carries now
+    min_region 1 is the identity.  A bad argument is a ValueError naming it.  Runs on any device."""
+    what = "sieve_reference"
+    K = _min_region_arg(what, min_region)
+    conn = _connectivity_arg(what, connectivity)
+    passes = _passes_arg(what, passes)
+    labels = _region_labels(what, labels)
+    if ignore is not None and (not isinstance(ignore, int) or isinstance(ignore, bool)):
+        raise ValueError("%s: ignore must be None or an int, got %r" % (what, ignore))
+    if n is None:
+        n = hip.SEG_SIEVE_MAX_CLASSES
+    if not isinstance(n, int) or isinstance(n, bool) or not 1 <= n <= hip.SEG_SIEVE_MAX_CLASSES:
+        raise ValueError("%s: n must be an int in 1 .. %d, got %r" % (what, hip.SEG_SIEVE_MAX_CLASSES, n))
+    if conf is not None:
+        conf = torch.as_tensor(conf)
+        if conf.shape != labels.shape:
+            raise ValueError("%s: conf must have the labels' shape %s, got %s" % (what, tuple(labels.shape), tuple(conf.shape)))
+    first = labels.reshape((-1,) + tuple(labels.shape[-2:])).long()
+    lab = first
+    for _ in range(passes):
+        new = _sieve_pass(lab, K, conn, ignore)
+        if torch.equal(new, lab):               # a fixed point: every further pass decides the same from the same map
+            break
+        lab = new
+    changed = lab != first
+    raw = 1 if raw_labels else 0
+    was, now = first[changed] - raw, lab[changed] - raw
+    moved = torch.stack([torch.bincount(was[(was >= 0) & (was < n)], minlength=n),
+                         torch.bincount(now[(now >= 0) & (now < n)], minlength=n)])
+    out = lab.to(labels.dtype).reshape(labels.shape)
+    if conf is not None:
+        return out, moved, torch.where(changed.reshape(labels.shape).to(conf.device), torch.zeros_like(conf), conf)
+    return out, moved
+
+
+def _check_sieve(sieve, sieve_connectivity, sieve_passes):
+    """the three sieve keywords of the Segmenter, checked -> (sieve, sieve_connectivity, sieve_passes)"""
+    if sieve is not None and (not isinstance(sieve, int) or isinstance(sieve, bool) or not 1 <= sieve < 2 ** 31):
+        raise ValueError("Segmenter: sieve must be None or an int in 1 .. 2**31 - 1 (the smallest region kept; 1 moves nothing), "
+                         "got %r" % (sieve,))
+    if not isinstance(sieve_connectivity, int) or isinstance(sieve_connectivity, bool) or sieve_connectivity not in (4, 8):
+        raise ValueError("Segmenter: sieve_connectivity must be the int 4 or 8, got %r" % (sieve_connectivity,))
+    if not isinstance(sieve_passes, int) or isinstance(sieve_passes, bool) or not 1 <= sieve_passes <= hip.SEG_SIEVE_MAX_PASSES:
+        raise ValueError("Segmenter: sieve_passes must be an int in 1 .. %d, got %r" % (hip.SEG_SIEVE_MAX_PASSES, sieve_passes))
+    return sieve, sieve_connectivity, sieve_passes
+
+
 class _PseudoLabelFields(NamedTuple):
     labels: torch.Tensor                       # [H, W] uint8: the pseudo-label map `train_sample` takes (255 = ignored)
     predicted: torch.Tensor                    # [H, W] uint8 / int16: what `segment_raw` gave
@@ -1287,9 +1387,11 @@ def _pamr_bytes(rgb):
 
 
 class Segmenter:
+    sieve, sieve_connectivity, sieve_passes, sieve_moved = None, 4, 2, None      # off, unless the constructor says otherwise
+
     def __init__(self, model, task=None, category_token_ids=None, prompt_ids=PROMPT_IDS, upsample="probs", smooth_iters=0,
                  smooth_topk=3, temperature=1.0, crf_iters=0, full_context_alignment=False, label_dtype=None, slide_views=False,
-                 pamr_iters=0, pamr_dilations=PAMR_DILATIONS):
+                 pamr_iters=0, pamr_dilations=PAMR_DILATIONS, sieve=None, sieve_connectivity=4, sieve_passes=2):
         """model: a SegOFAModel on the device.  The class names come from `category_token_ids` (one id sequence per class),
         else the task's `category_token_ids`, else the task's `category_list` through `task.encode_category`.
         upsample: "probs" resizes the per-patch softmax (temperature), the reference demo's order; "logits" resizes the raw
@@ -1305,7 +1407,19 @@ class Segmenter:
         label_dtype: None (uint8 up to 256 classes, else int16) or torch.uint8 to insist on bytes.
         slide_views: False: `slide` takes a single view, as ever.  True: `segment_raw` / `evaluate_raw(slide=...)` slide over
         EVERY view of `scales` and `flip` and finish each image with one launch of `hip.seg_predict_slide_views` (see
-        `segment_raw`)."""
+        `segment_raw`).
+        sieve: None: off, the launches as ever.  K (an int >= 1): every label map this Segmenter decides on is finished by one
+        `hip.seg_sieve(labels, K, sieve_connectivity, sieve_passes, n=n, conf=conf)` (csrc/sieve.hip; `sieve_reference` is the
+        specification and states the rule): connected regions (sieve_connectivity 4 or 8) of fewer than K pixels take the
+        value of their largest 4-adjacent neighbour region, sieve_passes (1 .. 8) times over -- islands vanish, holes close.
+        It runs behind the CRF / PAMR where those are on and in every setting (single view, ms+flip, slide, slide over views;
+        `__call__`, `segment_raw` and everything built on them: `render_raw`, `pseudo_label_raw`, `evaluate_raw`, `evaluate`).
+        conf is set to 0 where the sieve changed the label (the model never stated a confidence for the label such a pixel
+        carries now: under `pseudo_label_raw` it has bin 0, is dropped by any floor > 0 or keep < 1, and has weight 1 under
+        return_weight where it is kept); probs, where asked for, are returned as they were, NOT re-ranked.  `sieve_moved`,
+        int64 [2, n] on the device (None before the first sieved call), accumulates `hip.seg_sieve`'s moved over the calls:
+        per class the pixels that left and that joined; nothing synchronises with the host.  Not built: the sieve inside
+        `calibrate_raw` / `calibrate` and calibration counters behind a sieve (both a ValueError)."""
         if upsample not in ("probs", "logits"):
             raise ValueError("Segmenter: upsample must be 'probs' or 'logits', got %r" % (upsample,))
         self.model, self.task = model, task
@@ -1327,6 +1441,8 @@ class Segmenter:
         self.upsample, self.temperature = upsample, float(temperature)
         self.smooth_iters, self.smooth_topk, self.crf_iters = int(smooth_iters), int(smooth_topk), int(crf_iters)
         self.pamr_iters, self.pamr_dilations = _check_pamr(pamr_iters, pamr_dilations, self.crf_iters)
+        self.sieve, self.sieve_connectivity, self.sieve_passes = _check_sieve(sieve, sieve_connectivity, sieve_passes)
+        self.sieve_moved = None
         self.full_context_alignment = bool(full_context_alignment)
         self.label_dtype = label_dtype
         self.slide_views = bool(slide_views)
@@ -1441,10 +1557,22 @@ class Segmenter:
 
     def _label(self, merge, h, w, rgb, return_conf, return_probs):
         """one image (or batch) from its merge to a SegmentationResult at h x w: the predict launch, which with the CRF on hands
-        every class's value to `_crf`, as it does with PAMR on; rgb: the CRF's images (with PAMR: as uint8), else None"""
+        every class's value to `_crf`, as it does with PAMR on; rgb: the CRF's images (with PAMR: as uint8), else None.  With
+        the sieve on, `_sieve` finishes the labels"""
         crf = self.crf_iters > 0 or self.pamr_iters > 0
         out = merge.predict(h, w, conf=return_conf and not crf, probs=return_probs or crf, label_dtype=self.label_dtype)
-        return self._crf(out, rgb, return_conf, return_probs)
+        res = self._crf(out, rgb, return_conf, return_probs)
+        return res if self.sieve is None else self._sieve(res)
+
+    def _sieve(self, res):
+        """the labels [B, h, w] of a result through one `hip.seg_sieve`, its conf zeroed where they changed, its probs kept"""
+        labels = res.labels.contiguous()
+        conf = None if res.conf is None else res.conf.contiguous()
+        if self.sieve_moved is None or self.sieve_moved.device != labels.device:
+            self.sieve_moved = torch.zeros(2, self.n, dtype=torch.int64, device=labels.device)
+        labels, _ = hip.seg_sieve(labels, self.sieve, self.sieve_connectivity, self.sieve_passes, n=self.n, conf=conf,
+                                  moved=self.sieve_moved)
+        return SegmentationResult(labels, conf, res.probs)
 
     def _crf(self, out, rgb, return_conf, return_probs):
         labels, conf, probs = out
@@ -1705,7 +1833,9 @@ class Segmenter:
         a list of `PseudoLabelResult(labels uint8 [H_i, W_i], predicted, conf, kept)` in input order.
 
         images, scales, flip, slide, max_batch, mean, std, reverse_channels: as in `segment_raw`.  In this order:
-          1. `segment_raw(..., return_conf=True)`, unchanged: the label map and the winning class's probability per image;
+          1. `segment_raw(..., return_conf=True)`, unchanged: the label map and the winning class's probability per image
+             (on a `Segmenter(sieve=K)` the sieved map, a relabelled pixel with conf 0: bin 0, dropped by any floor > 0 or
+             keep < 1, weight 1 under return_weight where it is kept);
           2. one launch of `hip.seg_conf_hist` per image adds its (class, confidence bin) pairs to `hist` -- a
              `ConfidenceHistogram` to accumulate into, so that the thresholds are balanced over a whole data set across
              calls, or None for a fresh one that spans this call's images;
@@ -1787,6 +1917,9 @@ class Segmenter:
         if not isinstance(calibration, bool):
             raise ValueError("Segmenter.%s: calibration must be True or False (counters to add to go in with `into`), got %s"
                              % (what, type(calibration)))
+        if self.sieve is not None and (calibration or (isinstance(into, SegmentationScore) and into.calibration is not None)):
+            raise ValueError("Segmenter.%s: calibration counters behind sieve = %d are not built (a relabelled pixel has no "
+                             "confidence to count); score with a Segmenter(sieve=None)" % (what, self.sieve))
         ratio = None
         if boundary_iou is not False:
             ratio = 0.02 if boundary_iou is True else _boundary_ratio("Segmenter.%s: boundary_iou is True, False or a ratio" % what,
@@ -1823,8 +1956,8 @@ class Segmenter:
 
     def _count(self, score, merge, gt, raw_labels, rgb, return_labels):
         """The scoring step of `evaluate_raw` / `evaluate`: one image's (or batch's) merge against gt [B, h, w] into `score` -> its
-        labels [B, h, w] or None.  The epilogue of the merge's scoring launch adds to the counters.  With the CRF (or PAMR) on, the
-        label map comes from the CRF (`_label`; rgb: its images), not from the predict kernel, and `hip.seg_areas` counts it.  Where
+        labels [B, h, w] or None.  The epilogue of the merge's scoring launch adds to the counters.  With the CRF (or PAMR, or the sieve) on, the
+        label map comes from `_label` (rgb: the CRF's images), not from the scoring kernel, and `hip.seg_areas` counts it.  Where
         the score carries a confusion matrix, the launch is asked for its label map and `hip.seg_confusion` counts the pairs
         of the same labels behind it on the same stream; where it carries boundary counters, likewise, and
         `hip.seg_boundary_areas` counts the band areas of the same labels with d = `boundary_distance` of gt's size.  Where
@@ -1832,7 +1965,7 @@ class Segmenter:
         `hip.seg_calibration` counts labels, conf and gt behind the other two."""
         kw = dict(raw_labels=raw_labels, areas=score.areas, tally=score.tally)
         pairs, bands, cal = score.confusion is not None, score.boundary is not None, score.calibration is not None
-        if self.crf_iters > 0 or self.pamr_iters > 0:
+        if self.crf_iters > 0 or self.pamr_iters > 0 or self.sieve is not None:
             res = self._label(merge, int(gt.shape[1]), int(gt.shape[2]), rgb, cal, False)
             labels, conf = res.labels.contiguous(), res.conf
             hip.seg_areas(labels, gt, self.n, **kw)
@@ -1858,7 +1991,9 @@ class Segmenter:
         images, scales, flip, max_batch, mean, std, reverse_channels: as in `segment_raw`, whose pipeline this runs unchanged
         up to the last launch per image; that launch (`hip.seg_score` / `hip.seg_score_views`) also counts the label map it
         decides on against the image's ground truth and, without `return_labels`, writes nothing else.  With the CRF on, the
-        CRF's argmax is counted by `hip.seg_areas`.
+        CRF's argmax is counted by `hip.seg_areas`; with the sieve on (`Segmenter(sieve=K)`), likewise the sieved labels --
+        predict, `hip.seg_sieve`, `hip.seg_areas` -- and the matrix and the bands follow on the sieved labels; calibration
+        counters behind a sieve are a ValueError naming the setting, before anything is launched.
         label_maps: one uint8 / int16 [H, W] tensor or a list, on the host or the device, entry i of image i's shape.
         raw_labels=True: the label PNGs' values, 0 and 255 ignored and x -> class x - 1 (`areas_reference` states the rule);
         False: class ids, n and 255 ignored.  into: a score to accumulate into (a whole validation set needs no host round
@@ -1950,6 +2085,9 @@ class Segmenter:
             raise ValueError("Segmenter.%s: a temperature sweep scores the network's probabilities, this Segmenter has "
                              "pamr_iters = %d (the sweep's launch resizes and scores in one pass: PAMR inside it is not built)"
                              % (what, self.pamr_iters))
+        if self.sieve is not None:
+            raise ValueError("Segmenter.%s: a temperature sweep scores the network's probabilities, this Segmenter has "
+                             "sieve = %d (the sweep never forms a label map to sieve)" % (what, self.sieve))
         self._need_probability("Segmenter.%s" % what, None, "the values must be probabilities", "use upsample='probs' or the smoothing")
         temps = _check_temperatures("Segmenter.%s" % what, default_temperatures() if temperatures is None else temperatures)
         if into is None:
@@ -1975,7 +2113,7 @@ class Segmenter:
         consulted; afterwards `seg.temperature = sweep.best()`.  into: a sweep of the same temperatures, class count and
         device to accumulate into (a whole validation set).  `temperature_sweep_reference` is the specification.
         A ValueError naming the setting, before anything is launched: `scales` / `flip` other than one plain view, `slide`,
-        `crf_iters > 0`, `pamr_iters > 0`, upsample="logits" without the smoothing (the values must be probabilities), a bad temperature list,
+        `crf_iters > 0`, `pamr_iters > 0`, `sieve`, upsample="logits" without the smoothing (the values must be probabilities), a bad temperature list,
         an `into` that does not match."""
         what = "calibrate_raw"
         dev = next(self.model.parameters()).device

@@ -200,7 +200,9 @@ class SegmentationTask(TaskBase):
     def build_segmenter(self, model, **kw):
         """images -> label maps at image resolution on this task's categories (ifseg_amd/predict.py); raw uint8 images of
         any size go through `Segmenter.segment_raw`, the evaluation transform of the data pipeline on the device; every keyword
-        of the constructor passes through (`slide_views=True`: multi-scale + flip over sliding windows)"""
+        of the constructor passes through (`slide_views=True`: multi-scale + flip over sliding windows; `sieve=K`: regions
+        below K pixels take their largest neighbour's label -- `evaluate_raw`, `calibrate_raw`, `render_raw` and
+        `pseudo_label_raw` below hand it on with `sieve_connectivity` and `sieve_passes`)"""
         from ...predict import Segmenter
         return Segmenter(model, task=self, **kw)
 
@@ -213,7 +215,8 @@ class SegmentationTask(TaskBase):
         `calibration=True` for how often a confidence is right (`score.calibration`; "ECE" in the summary,
         `score.precision_thresholds(target)` for `self_train_sample`'s thresholds)."""
         ctor = ("category_token_ids", "prompt_ids", "upsample", "smooth_iters", "smooth_topk", "temperature", "crf_iters",
-                "full_context_alignment", "label_dtype", "slide_views", "pamr_iters", "pamr_dilations")
+                "full_context_alignment", "label_dtype", "slide_views", "pamr_iters", "pamr_dilations", "sieve",
+                "sieve_connectivity", "sieve_passes")
         seg = self.build_segmenter(model, **{k: kw.pop(k) for k in ctor if k in kw})
         return seg.evaluate_raw(images, label_maps, slide=slide, **kw)
 
@@ -223,7 +226,8 @@ class SegmentationTask(TaskBase):
         mean NLL: `build_segmenter(model, ...).calibrate_raw(images, label_maps, ...)`.  Keywords of the Segmenter's constructor
         go to it, the others to `Segmenter.calibrate_raw`."""
         ctor = ("category_token_ids", "prompt_ids", "upsample", "smooth_iters", "smooth_topk", "temperature", "crf_iters",
-                "full_context_alignment", "label_dtype", "slide_views", "pamr_iters", "pamr_dilations")
+                "full_context_alignment", "label_dtype", "slide_views", "pamr_iters", "pamr_dilations", "sieve",
+                "sieve_connectivity", "sieve_passes")
         seg = self.build_segmenter(model, **{k: kw.pop(k) for k in ctor if k in kw})
         return seg.calibrate_raw(images, label_maps, **kw)
 
@@ -232,7 +236,8 @@ class SegmentationTask(TaskBase):
         device: `build_segmenter(model, ...).render_raw(images, ...)`.  Keywords of the Segmenter's constructor go to it, the
         others to `Segmenter.render_raw`."""
         ctor = ("category_token_ids", "prompt_ids", "upsample", "smooth_iters", "smooth_topk", "temperature", "crf_iters",
-                "full_context_alignment", "label_dtype", "slide_views", "pamr_iters", "pamr_dilations")
+                "full_context_alignment", "label_dtype", "slide_views", "pamr_iters", "pamr_dilations", "sieve",
+                "sieve_connectivity", "sieve_passes")
         seg = self.build_segmenter(model, **{k: kw.pop(k) for k in ctor if k in kw})
         return seg.render_raw(images, **kw)
 
@@ -243,7 +248,8 @@ class SegmentationTask(TaskBase):
         `region_connectivity` among them: connected regions of the filtered map below K pixels become 255 too, and the
         results carry `region_dropped`."""
         ctor = ("category_token_ids", "prompt_ids", "upsample", "smooth_iters", "smooth_topk", "temperature", "crf_iters",
-                "full_context_alignment", "label_dtype", "slide_views", "pamr_iters", "pamr_dilations")
+                "full_context_alignment", "label_dtype", "slide_views", "pamr_iters", "pamr_dilations", "sieve",
+                "sieve_connectivity", "sieve_passes")
         seg = self.build_segmenter(model, **{k: kw.pop(k) for k in ctor if k in kw})
         return seg.pseudo_label_raw(images, **kw)
 

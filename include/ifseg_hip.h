@@ -1017,6 +1017,34 @@ int ifseg_seg_region_drop(const void* labels, int B, int H, int W, int connectiv
 /* which = 0 / 1: the rows / columns of a tile, 2: the largest n of the drop; any other which: IFSEG_ERR_BAD_ARG. */
 int ifseg_seg_regions_limit(int which);
 
+/* ---- the sieve of a label map (csrc/sieve.hip; ifseg_amd/predict.py sieve_reference is the specification and states the
+ * rule; the reference has no counterpart; a relative of GDAL's sieve filter) ----
+ * labels [B][H][W], uint8 (label_bytes 1) or int16 (2), values compared as they are.  One pass, everything decided from the
+ * pass's input map: a region of ifseg_seg_regions (connectivity 4 or 8) with the key (size, -root) is small iff size <
+ * min_region and its value is not `ignore` (read only with has_ignore != 0); a small region takes the value of the region
+ * with the largest key among those that hold a pixel one step in x or y from one of its pixels and do not carry `ignore`,
+ * and only if that key exceeds its own.  `passes` (1 .. 8) repeats this on the previous pass's output.  Per pass:
+ * ifseg_seg_regions' launches, then three of this file's on the same stream (best cleared; the votes, one 64-bit integer
+ * atomic maximum each, into best[the region's root]; the map written).  The result is canonical: a maximum does not depend on
+ * the order of its operands.
+ * out [B][H][W] of the labels' type: the last pass's map.  tmp: the same, the other side of the passes' ping-pong, NULL
+ * allowed with passes == 1.  conf fp32 [B][H][W] or NULL: set to 0 where out != labels, untouched elsewhere.  moved uint64
+ * [2][n] is ADDED to: moved[0][c] the pixels that were class c in labels and are not in out, moved[1][c] those that are and
+ * were not; class = value - 1 with raw_labels != 0, else the value; values outside [0, n) are not counted.  One 64-bit atomic
+ * per workgroup and non-zero entry.  work / count / root / size: int32 [B][H][W], best: uint64 [B][H][W], all the caller's,
+ * written in full (nothing needs zeroing); flag: ifseg_seg_regions', passed through.
+ * NULL pointers (conf, and tmp with one pass, may be NULL), label_bytes outside {1, 2}, int16 maps at an odd address, a
+ * plane, conf or flag not 4-byte aligned, best or moved not 8-byte aligned, any two buffers sharing a byte, connectivity
+ * other than 4 or 8, min_region < 1, passes outside 1..8, n outside 1..512: IFSEG_ERR_BAD_ARG; B, H, W < 1 or B*H*W >= 2^31:
+ * IFSEG_ERR_BAD_SHAPE.  Nothing is launched on a refusal. */
+int ifseg_seg_sieve(const void* labels, int label_bytes, int B, int H, int W, int connectivity, int min_region, int passes,
+                    int ignore, int has_ignore, int n, int raw_labels, int* work, int* count, int* root, int* size,
+                    unsigned long long* best, void* tmp, void* out, float* conf, unsigned long long* moved, int* flag,
+                    void* stream);
+/* which = 0 / 1: the rows / columns of a tile, 2: the passes of a call at most, 3: the largest n; any other which:
+ * IFSEG_ERR_BAD_ARG. */
+int ifseg_seg_sieve_limit(int which);
+
 /* ---- pixel-adaptive mask refinement (PAMR: Araslanov & Roth, CVPR 2020; Segmenter(pamr_iters=); the reference has no
  * counterpart) ----  A few iterations of a local, image-adaptive, convex averaging of the class values of ONE image at image
  * resolution, linear in the pixels; csrc/pamr.hip; ifseg_amd/predict.py pamr_reference is the specification.
