@@ -2080,6 +2080,99 @@ def seg_sieve(labels, min_region, connectivity=4, passes=1, ignore=None, n=None,
     return out, moved
 
 
+# --------------------------------------------------------------------------- the region table of a label map (csrc/regiontab.hip)
+SEG_REGION_TABLE_MAX = 1 << 20      # == RT_MAX_REGIONS: the largest max_regions
+SEG_REGION_TABLE_BLOCK = 1024       # == RT_BLOCK: the flat pixels of a block of the counting launches
+
+
+def seg_region_table_limits():
+    """-> (a tile's rows, a tile's columns, the flat pixels of a block, the largest max_regions) as the loaded library states
+    them (`ifseg_seg_region_table_limit`): 16, 64, SEG_REGION_TABLE_BLOCK and SEG_REGION_TABLE_MAX, which the tests hold
+    against it"""
+    return _limits("ifseg_seg_region_table_limit", 4)
+
+
+def _region_table_out(what, name, t, shape, dtype, dev, others):
+    """an output of the region table: the caller's, checked against `others` (name, tensor) for shared bytes, or None"""
+    if t is None:
+        return None
+    if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != dev:
+        raise ValueError("%s: %s must be a contiguous %s tensor of shape %s on %s, got %s" % (
+            what, name, str(dtype).replace("torch.", ""), tuple(shape), dev,
+            (t.dtype, tuple(t.shape), t.stride(), t.device) if torch.is_tensor(t) else type(t)))
+    for other_name, other in others:
+        if other is not None and _overlap(t, other):
+            raise ValueError("%s: %s overlaps %s" % (what, name, other_name))
+    return t
+
+
+def seg_region_table(labels, conf=None, connectivity=4, min_region=1, ignore=None, max_regions=1024, rows=None, sums=None,
+                     count=None, slot=None, flag=None):
+    """labels uint8 / int16 [H, W] or [B, H, W] -> (rows int32 [B, R, 8], sums int64 [B, R, 3], count int32 [B], slot int32 of
+    the labels' shape), R = max_regions and the leading B absent for an [H, W] map: the table of the map's connected regions
+    (csrc/regiontab.hip; `predict.region_table_reference` is the specification and states the rule).  A region of
+    `seg_regions` (connectivity 4 or 8) is listed iff it holds at least min_region pixels and its value is not `ignore`; the
+    listed regions of an image are numbered in ascending order of their roots.  rows[s] = (value, root, size, x0, y0, x1, y1,
+    0), the box inclusive; sums[s] = (sum x, sum y, sum q) over the region's pixels, q = clamp(floor(conf * 65536), 0, 65535)
+    of conf fp32 of the labels' shape (0 without conf); count = the listed regions, which may exceed R -- rows and sums from
+    min(count, R) on are not written (fresh ones are zero there); slot[p] = the row of p's region, -1 where there is none.
+    `seg_regions`' launches and four more on the current stream; nothing synchronises, and every output is an integer, so two
+    calls give equal bits.  rows / sums / count / slot: written in place when given.  flag: as in `seg_regions`.
+    The work planes are allocated here: `seg_regions`' four int32 planes of the labels' shape and the block counts, in one
+    allocation; where neither rows nor sums is given, the two (and a fresh flag word) are views of one zero-filled allocation.
+    Bad arguments: ValueError naming the argument, before anything is launched."""
+    what = "seg_region_table"
+    B, H, W = _region_maps(what, labels, connectivity, (torch.uint8, torch.int16))
+    if not isinstance(min_region, int) or isinstance(min_region, bool) or not 1 <= min_region < 2 ** 31:
+        raise ValueError("%s: min_region must be an int in 1 .. 2**31 - 1 (1 lists every region), got %r" % (what, min_region))
+    if ignore is not None and (not isinstance(ignore, int) or isinstance(ignore, bool)):
+        raise ValueError("%s: ignore must be None or an int, got %r" % (what, ignore))
+    if not isinstance(max_regions, int) or isinstance(max_regions, bool) or not 1 <= max_regions <= SEG_REGION_TABLE_MAX:
+        raise ValueError("%s: max_regions must be an int in 1 .. %d, got %r" % (what, SEG_REGION_TABLE_MAX, max_regions))
+    dev, R = labels.device, max_regions
+    if conf is not None:
+        _region_plane(what, "conf", conf, labels, torch.float32)
+    lead = tuple(labels.shape[:-2])
+    given = [("labels", labels), ("conf", conf)]
+    outs = {}
+    for name, t, shape, dtype in (("rows", rows, lead + (R, 8), torch.int32), ("sums", sums, lead + (R, 3), torch.int64),
+                                  ("count", count, lead, torch.int32), ("slot", slot, tuple(labels.shape), torch.int32)):
+        outs[name] = _region_table_out(what, name, t, shape, dtype, dev, given)
+        given.append((name, outs[name]))
+    if flag is not None:
+        _region_flag(what, flag, dev)
+        for name, t in given[2:]:
+            if t is not None and _overlap(t, flag):
+                raise ValueError("%s: %s overlaps flag" % (what, name))
+    rows, sums = outs["rows"], outs["sums"]
+    if rows is None and sums is None:
+        # ONE zero fill for everything the call must find zeroed: the table and, behind it, a fresh flag word
+        nrow = B * R
+        zeroed = torch.zeros(7 * nrow + 1, dtype=torch.int64, device=dev)
+        rows = zeroed[:4 * nrow].view(torch.int32).view(lead + (R, 8))
+        sums = zeroed[4 * nrow:7 * nrow].view(lead + (R, 3))
+        if flag is None:
+            flag = zeroed[7 * nrow:].view(torch.int32)[:1]
+    elif rows is None:
+        rows = torch.zeros(lead + (R, 8), dtype=torch.int32, device=dev)
+    elif sums is None:
+        sums = torch.zeros(lead + (R, 3), dtype=torch.int64, device=dev)
+    flag = _region_flag(what, flag, dev)
+    count = torch.empty(lead, dtype=torch.int32, device=dev) if outs["count"] is None else outs["count"]
+    slot = torch.empty(labels.shape, dtype=torch.int32, device=dev) if outs["slot"] is None else outs["slot"]
+    lo, hi = (0, 255) if labels.dtype == torch.uint8 else (-2 ** 15, 2 ** 15 - 1)
+    has_ignore = ignore is not None and lo <= ignore <= hi      # a value the map cannot hold ignores nothing
+    npix, nblk = B * H * W, B * -(-(H * W) // SEG_REGION_TABLE_BLOCK)
+    scratch = torch.empty(4 * npix + nblk, dtype=torch.int32, device=dev)
+    work, blk = scratch[:4 * npix].view(4, npix), scratch[4 * npix:]
+    _check(lib().ifseg_seg_region_table(_ptr(labels), c_int(labels.element_size()), _ptr(conf), c_int(B), c_int(H), c_int(W),
+                                        c_int(connectivity), c_int(min_region), c_int(ignore if has_ignore else 0),
+                                        c_int(1 if has_ignore else 0), c_int(R), _ptr(work[0]), _ptr(work[1]), _ptr(work[2]),
+                                        _ptr(work[3]), _ptr(blk), _ptr(rows), _ptr(sums), _ptr(count), _ptr(slot), _ptr(flag),
+                                        _stream()), "seg_region_table")
+    return rows, sums, count, slot
+
+
 # --------------------------------------------------------------------------- pixel-adaptive mask refinement (csrc/pamr.hip)
 SEG_PAMR_MAX_DILATIONS = 8          # == PM_MAX_D: the dilations of a call at most (8 neighbours each)
 SEG_PAMR_MAX_DILATION = 32          # == PM_MAX_DILATION: the largest dilation (a tile's halo: 40 KiB of LDS)

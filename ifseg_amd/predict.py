@@ -131,6 +131,14 @@ and `region_drop_reference` are the specifications.
 
     out = seg.pseudo_label_raw(photos, thresholds=t, boundary=1, min_region=16, region_connectivity=8)
 
+The list of objects -- what a robot, a counter or an annotation tool consumes -- is `regions_raw`: `segment_raw`, then one
+`hip.seg_region_table` per image (csrc/regiontab.hip, four launches behind the regions'): one row per connected region with
+its class value, area, bounding box, coordinate sums and summed confidence, numbered in ascending order of the regions' roots,
+on the device.  `region_table_reference` is the specification; `RegionTable.to_list` is the one host round trip.
+
+    for t in seg.regions_raw(photos, min_region=50):                # [RegionTable(rows, sums, count, slot, labels, conf)]
+        print(t.to_list(names))                                     # [{"value", "name", "area", "box", "centroid", "confidence"}]
+
 A cheap refinement that looks at the photograph: `Segmenter(..., pamr_iters=10)` runs pixel-adaptive mask refinement (PAMR,
 Araslanov & Roth, CVPR 2020; what MaskCLIP applies to its pseudo-labels) on the resized values of every image, in the slot of
 the CRF: `hip.seg_pamr` (csrc/pamr.hip), one affinity launch on the original uint8 photo and one launch per iteration.  Each
@@ -1021,6 +1029,150 @@ def sieve_reference(labels, min_region, connectivity=4, passes=1, ignore=None, n
     return out, moved
 
 
+def conf_q16(conf):
+    """fp32 confidences -> 16-bit fixed point, int64 of the same shape: clamp(floor(conf * 65536), 0, 65535) evaluated in fp32
+    (the product is exact), NaN -> 0, +inf -> 65535: what the region table sums.  `conf_q16(c) >> 8 == conf_bin(c)` for every
+    fp32 c.  Runs on any device."""
+    conf = torch.as_tensor(conf)
+    if conf.dtype != torch.float32:
+        raise ValueError("conf_q16: conf must be float32, got %s" % conf.dtype)
+    q = torch.floor(conf * 65536.0)
+    return torch.where(torch.isnan(q), torch.zeros_like(q), q).clamp(0.0, 65535.0).long()
+
+
+def _max_regions_arg(what, max_regions):
+    if not isinstance(max_regions, int) or isinstance(max_regions, bool) or not 1 <= max_regions <= hip.SEG_REGION_TABLE_MAX:
+        raise ValueError("%s: max_regions must be an int in 1 .. %d, got %r" % (what, hip.SEG_REGION_TABLE_MAX, max_regions))
+    return max_regions
+
+
+def _ignore_arg(what, ignore):
+    if ignore is not None and (not isinstance(ignore, int) or isinstance(ignore, bool)):
+        raise ValueError("%s: ignore must be None or an int, got %r" % (what, ignore))
+    return ignore
+
+
+def region_table_reference(labels, conf=None, connectivity=4, min_region=1, ignore=None, max_regions=1024, regions=None):
+    """Specification of hip.seg_region_table: labels integer [H, W] (or [B, H, W]), conf fp32 of the same shape or None ->
+    (rows int32 [B, R, 8], sums int64 [B, R, 3], count int32 [B], slot int32 of the labels' shape), R = max_regions, the
+    leading B absent for an [H, W] map.
+
+    Regions, root and size are `regions_reference(labels, connectivity)`'s.  A region is listed iff size >= min_region and its
+    value is not `ignore` (None: no value is).  The listed regions of an image are numbered 0, 1, ... in ascending order of
+    root -- canonical, not an order of discovery; count[b] is their number, which may exceed R.  For a listed region with
+    number s < R:
+      rows[b, s] = (value, root, size, x0, y0, x1, y1, 0)      the box inclusive, in pixels of the image
+      sums[b, s] = (sum x, sum y, sum q) over its pixels        q = `conf_q16(conf)`; 0 without conf
+    Rows from min(count[b], R) on are zero here (the kernel does not write them).  slot[p] = the row of p's region, -1 where the
+    region is not listed or its number is >= R.  Everything is an integer.  regions: `regions_reference(labels, connectivity)`'s
+    (root, size) where the caller holds them already (they are not computed again).  A bad argument is a ValueError naming it.
+    Runs on any device."""
+    what = "region_table_reference"
+    conn = _connectivity_arg(what, connectivity)
+    K = _min_region_arg(what, min_region)
+    _ignore_arg(what, ignore)
+    R = _max_regions_arg(what, max_regions)
+    labels = _region_labels(what, labels)
+    if conf is not None:
+        conf = torch.as_tensor(conf)
+        if conf.dtype != torch.float32 or conf.shape != labels.shape:
+            raise ValueError("%s: conf must be float32 %s, got %s %s" % (what, tuple(labels.shape), conf.dtype, tuple(conf.shape)))
+    root, size = regions_reference(labels, conn) if regions is None else (torch.as_tensor(r).to(labels.device) for r in regions)
+    if root.shape != labels.shape or size.shape != labels.shape:
+        raise ValueError("%s: regions must be (root, size) of the labels' shape %s, got %s %s" % (
+            what, tuple(labels.shape), tuple(root.shape), tuple(size.shape)))
+    lead, (H, W) = tuple(labels.shape[:-2]), labels.shape[-2:]
+    dev = labels.device
+    lab = labels.reshape(-1, H * W).long()
+    root, size = root.reshape(-1, H * W).long(), size.reshape(-1, H * W).long()
+    B = lab.shape[0]
+    pix = torch.arange(H * W, dtype=torch.int64, device=dev).reshape(1, H * W)
+    listed = size >= K if ignore is None else (size >= K) & (lab != ignore)
+    flag = listed & (root == pix)                                   # the listed regions' roots
+    number = flag.long().cumsum(1) - 1                              # ascending root = ascending flat index
+    count = flag.sum(1)
+    at_root = torch.where(flag & (number < R), number, torch.full_like(number, -1))
+    slot = at_root.gather(1, root)
+    on = slot >= 0
+    key = (slot + torch.arange(B, dtype=torch.int64, device=dev).reshape(B, 1) * R)[on]
+    x, y = (pix % W).expand(B, H * W)[on], (pix // W).expand(B, H * W)[on]
+    q = conf_q16(conf.to(dev)).reshape(B, H * W)[on] if conf is not None else torch.zeros_like(x)
+    big = 2 ** 31 - 1
+    lowest = torch.full((B * R,), big, dtype=torch.int64, device=dev)
+    highest = torch.full((B * R,), -1, dtype=torch.int64, device=dev)
+    box = torch.stack([lowest.scatter_reduce(0, key, x, "amin"), lowest.scatter_reduce(0, key, y, "amin"),
+                       highest.scatter_reduce(0, key, x, "amax"), highest.scatter_reduce(0, key, y, "amax")], 1)
+    nothing = torch.zeros(B * R, dtype=torch.int64, device=dev)
+    sums = torch.stack([nothing.index_add(0, key, v) for v in (x, y, q)], 1)
+    rows = torch.zeros(B * R, 8, dtype=torch.int64, device=dev)
+    head = (at_root + torch.arange(B, dtype=torch.int64, device=dev).reshape(B, 1) * R)[at_root >= 0]
+    written = torch.zeros(B * R, dtype=torch.bool, device=dev)
+    written[head] = True
+    rows[head, 0], rows[head, 1], rows[head, 2] = lab[at_root >= 0], root[at_root >= 0], size[at_root >= 0]
+    rows[:, 3:7] = torch.where(written[:, None], box, torch.zeros_like(box))
+    return (rows.to(torch.int32).reshape(lead + (R, 8)), sums.reshape(lead + (R, 3)), count.to(torch.int32).reshape(lead),
+            slot.to(torch.int32).reshape(labels.shape))
+
+
+class RegionTable:
+    """The connected regions of ONE image's label map, on the device: what `hip.seg_region_table` wrote (rows int32 [R, 8],
+    sums int64 [R, 3], count int32 scalar, slot int32 [H, W]) beside the labels [H, W] and the conf [H, W] (or None) it was
+    made from.  count may exceed R = rows.shape[0]: `truncated()`.  The accessors return device tensors of the WRITTEN rows,
+    the first min(count, R), in ascending order of the regions' roots; which rows those are is decided on the device (a
+    boolean mask), so only `to_list` synchronises with the host."""
+
+    def __init__(self, rows, sums, count, slot, labels, conf=None):
+        self.rows, self.sums, self.count, self.slot, self.labels, self.conf = rows, sums, count, slot, labels, conf
+
+    @property
+    def max_regions(self):
+        return int(self.rows.shape[0])
+
+    def truncated(self):
+        """device bool: more regions are listed than the table holds"""
+        return self.count > self.max_regions
+
+    def _written(self):
+        return torch.arange(self.max_regions, device=self.rows.device) < self.count
+
+    def values(self):
+        return self.rows[self._written(), 0]
+
+    def roots(self):
+        return self.rows[self._written(), 1]
+
+    def areas(self):
+        return self.rows[self._written(), 2]
+
+    def boxes(self):
+        """int32 [k, 4]: (x0, y0, x1, y1), inclusive"""
+        return self.rows[self._written(), 3:7]
+
+    def centroids(self):
+        """float64 [k, 2]: (mean x, mean y) = the coordinate sums / the area"""
+        w = self._written()
+        return self.sums[w, :2].double() / self.rows[w, 2:3].double()
+
+    def mean_conf(self):
+        """float64 [k]: sum q / (65536 area); 0 where the table was made without conf"""
+        w = self._written()
+        return self.sums[w, 2].double() / (65536.0 * self.rows[w, 2].double())
+
+    def to_list(self, names=None):
+        """the one host round trip -> a list of dicts(value, name, area, box (x0, y0, x1, y1), centroid (x, y), confidence), one
+        per written row; names: a sequence indexed by value (a value outside it has the name None), or None.  confidence is
+        None where the table was made without conf"""
+        w = self._written()
+        rows, sums = self.rows[w].cpu().tolist(), self.sums[w].cpu().tolist()
+        out = []
+        for r, s in zip(rows, sums):
+            v, area = r[0], r[2]
+            out.append({"value": v, "name": names[v] if names is not None and 0 <= v < len(names) else None, "area": area,
+                        "box": tuple(r[3:7]), "centroid": (s[0] / area, s[1] / area),
+                        "confidence": None if self.conf is None else s[2] / (65536.0 * area)})
+        return out
+
+
 def _check_sieve(sieve, sieve_connectivity, sieve_passes):
     """the three sieve keywords of the Segmenter, checked -> (sieve, sieve_connectivity, sieve_passes)"""
     if sieve is not None and (not isinstance(sieve, int) or isinstance(sieve, bool) or not 1 <= sieve < 2 ** 31):
@@ -1906,6 +2058,58 @@ class Segmenter:
                 kept[0] -= dropped
                 out.append(PseudoLabelResult(pseudo, labels, conf, kept, wt, region_dropped=dropped))
         return out
+
+    # -- the list of objects -----------------------------------------------------------------
+    def _region_args(self, what, min_region, connectivity, max_regions, ignore):
+        _min_region_arg(what, min_region)
+        _connectivity_arg(what, connectivity)
+        _max_regions_arg(what, max_regions)
+        _ignore_arg(what, ignore)
+
+    def _wants_conf(self, sl):
+        """whether the region tables of this construction sum a confidence: where it is a probability (`_conf_setting`), and
+        behind PAMR, which keeps what it was given"""
+        return self._conf_setting(sl) is None or self.pamr_iters > 0
+
+    @staticmethod
+    def _region_table(labels, conf, min_region, connectivity, max_regions, ignore):
+        """one image's labels [H, W] (and conf) -> its RegionTable through one `hip.seg_region_table`"""
+        labels = labels.contiguous()
+        conf = None if conf is None else conf.contiguous()
+        rows, sums, count, slot = hip.seg_region_table(labels, conf, connectivity, min_region, ignore, max_regions)
+        return RegionTable(rows, sums, count, slot, labels, conf)
+
+    def regions_raw(self, images, min_region=1, connectivity=4, max_regions=1024, ignore=None, max_batch=8, scales=(1.0,),
+                    flip=False, slide=None, mean=None, std=None, reverse_channels=False):
+        """Raw images -> what is in them: a list of `RegionTable` in input order, one row per connected region of the image's
+        label map with its class value, area, bounding box, centroid sums and summed confidence, on the device.
+
+        images, scales, flip, slide, max_batch, mean, std, reverse_channels: as in `segment_raw`, which runs unchanged (with a
+        `Segmenter(sieve=K)` the sieved map, so behind `hip.seg_sieve`); then ONE `hip.seg_region_table` per image
+        (`region_table_reference` states the rule): regions of `connectivity` 4 or 8 with at least min_region pixels and a
+        value other than `ignore`, numbered in ascending order of their roots, the first max_regions of them in the table
+        (`RegionTable.truncated()` says whether more were listed).  The confidence is summed where this construction's conf is
+        a probability -- upsample="probs", the smoothing, the CRF, PAMR, or `slide_views` sliding; with raw logits
+        (upsample="logits" elsewhere) no conf is asked of `segment_raw`, the tables' third sum is 0 and `RegionTable.conf` is
+        None: the boxes need no confidence.  Nothing synchronises with the host; `RegionTable.to_list` is the one round trip.
+        A bad argument is a ValueError before anything is launched."""
+        what = "Segmenter.regions_raw"
+        self._region_args(what, min_region, connectivity, max_regions, ignore)
+        sl = self._check_slide("regions_raw", slide, scales, flip)
+        res = self.segment_raw(images, max_batch=max_batch, mean=mean, std=std, reverse_channels=reverse_channels,
+                               return_conf=self._wants_conf(sl), scales=scales, flip=flip, slide=slide)
+        with torch.no_grad():
+            return [self._region_table(r.labels, r.conf, min_region, connectivity, max_regions, ignore) for r in res]
+
+    def regions(self, images, out_hw=None, min_region=1, connectivity=4, max_regions=1024, ignore=None, crf_images=None):
+        """`regions_raw` for what `__call__` takes: a ready batch (and out_hw, crf_images as there) -> a list of `RegionTable`,
+        one per image of the batch, each through one `hip.seg_region_table` behind `__call__`'s launches"""
+        self._region_args("Segmenter.regions", min_region, connectivity, max_regions, ignore)
+        res = self(images, out_hw=out_hw, crf_images=crf_images, return_conf=self._wants_conf(None))
+        per_image = [(r.labels[0], None if r.conf is None else r.conf[0]) for r in res] if isinstance(res, list) else \
+            [(res.labels[b], None if res.conf is None else res.conf[b]) for b in range(res.labels.shape[0])]
+        with torch.no_grad():
+            return [self._region_table(l, c, min_region, connectivity, max_regions, ignore) for l, c in per_image]
 
     # -- scoring against ground truth -----------------------------------------------------
     def _score_into(self, what, into, dev, confusion=False, boundary_iou=False, shapes=(), calibration=False, sl=None):

@@ -253,6 +253,17 @@ class SegmentationTask(TaskBase):
         seg = self.build_segmenter(model, **{k: kw.pop(k) for k in ctor if k in kw})
         return seg.pseudo_label_raw(images, **kw)
 
+    def regions_raw(self, model, images, **kw):
+        """raw uint8 images -> a list of `RegionTable`, one row per connected region of each image's label map (class value,
+        area, box, centroid sums, summed confidence) on the device: `build_segmenter(model, ...).regions_raw(images, ...)`.
+        Keywords of the Segmenter's constructor (read from its signature) go to it, the others -- `min_region`,
+        `connectivity`, `max_regions`, `ignore` and `segment_raw`'s -- to `Segmenter.regions_raw`."""
+        import inspect
+        from ...predict import Segmenter
+        keywords = [k for k in inspect.signature(Segmenter.__init__).parameters if k not in ("self", "model", "task")]
+        seg = self.build_segmenter(model, **{k: kw.pop(k) for k in keywords if k in kw})
+        return seg.regions_raw(images, **kw)
+
     def self_train_sample(self, model, images, first_ordinal, trainer=None, confidence_weight=False, **kw):
         """One batch of self-training on unlabeled photographs: `pseudo_label_raw(model, images, **kw)` and then
         `train_sample(images, [r.labels ...], first_ordinal)` on the model's own confident pixels -> the batch

@@ -1045,6 +1045,32 @@ int ifseg_seg_sieve(const void* labels, int label_bytes, int B, int H, int W, in
  * IFSEG_ERR_BAD_ARG. */
 int ifseg_seg_sieve_limit(int which);
 
+/* ---- the region table of a label map (csrc/regiontab.hip; ifseg_amd/predict.py region_table_reference is the specification
+ * and states the rule; the reference has no counterpart) ----
+ * labels [B][H][W], uint8 (label_bytes 1) or int16 (2); conf fp32 [B][H][W] or NULL.  Regions, root and size are
+ * ifseg_seg_regions' (connectivity 4 or 8).  A region is listed iff size >= min_region and its value is not `ignore` (read
+ * only with has_ignore != 0); the listed regions of an image are numbered 0, 1, ... in ascending order of root.
+ *   nreg int32 [B]        the listed regions of each image; it may exceed R
+ *   rows int32 [B][R][8]  row s < min(nreg[b], R) = (value, root, size, x0, y0, x1, y1, 0), the box inclusive
+ *   sums int64 [B][R][3]  row s = (sum x, sum y, sum q) over the region's pixels, q = clamp(floor(conf * 65536), 0, 65535) in
+ *                         fp32 (NaN -> 0, +inf -> 65535; q >> 8 is the confidence bin of ifseg_seg_conf_hist); 0 without conf
+ *   slot int32 [B][H][W]  the row of the pixel's region, -1 where it is not listed or its number is >= R
+ * Rows from min(nreg[b], R) on are NOT written.  ifseg_seg_regions' launches, then four on the same stream (the listed roots
+ * counted per block of 1024 flat pixels of one image; one workgroup per image scans its blocks' counts; the rows' headers and
+ * the roots' slots; per 16 x 64 tile the statistics, through a workgroup-private LDS table, as 32-bit integer min / max and
+ * 64-bit integer add atomics per tile-local region).  Integers throughout: canonical, two calls give equal bits.
+ * work / count / root / size: ifseg_seg_regions' planes, blk: int32 [B][ceil(H W / 1024)], all the caller's, written in full
+ * (nothing needs zeroing); flag: ifseg_seg_regions', passed through.
+ * NULL pointers (conf may be NULL), label_bytes outside {1, 2}, int16 labels at an odd address, a buffer not 4-byte aligned,
+ * sums not 8-byte aligned, any two buffers sharing a byte, connectivity other than 4 or 8, min_region < 1, R outside
+ * 1..2^20: IFSEG_ERR_BAD_ARG; B, H, W < 1 or B*H*W >= 2^31: IFSEG_ERR_BAD_SHAPE.  Nothing is launched on a refusal. */
+int ifseg_seg_region_table(const void* labels, int label_bytes, const float* conf, int B, int H, int W, int connectivity,
+                           int min_region, int ignore, int has_ignore, int R, int* work, int* count, int* root, int* size,
+                           int* blk, int* rows, long long* sums, int* nreg, int* slot, int* flag, void* stream);
+/* which = 0 / 1: the rows / columns of a tile, 2: the flat pixels of a block, 3: the largest R; any other which:
+ * IFSEG_ERR_BAD_ARG. */
+int ifseg_seg_region_table_limit(int which);
+
 /* ---- pixel-adaptive mask refinement (PAMR: Araslanov & Roth, CVPR 2020; Segmenter(pamr_iters=); the reference has no
  * counterpart) ----  A few iterations of a local, image-adaptive, convex averaging of the class values of ONE image at image
  * resolution, linear in the pixels; csrc/pamr.hip; ifseg_amd/predict.py pamr_reference is the specification.
