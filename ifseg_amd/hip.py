@@ -2173,6 +2173,109 @@ def seg_region_table(labels, conf=None, connectivity=4, min_region=1, ignore=Non
     return rows, sums, count, slot
 
 
+# --------------------------------------------------------------------------- run-length label maps (csrc/rle.hip)
+SEG_RLE_MAX_RUNS = 1 << 24          # == RL_MAX_RUNS: the largest max_runs
+SEG_RLE_CHUNK = 32                  # == RL_CHUNK: the rows of a column segment of the counting launches
+SEG_RLE_COLS = 64                   # == RL_COLS: the columns of a workgroup
+
+
+def seg_rle_limits():
+    """-> (the rows of a chunk, the columns of a workgroup, the largest max_runs) as the loaded library states them
+    (`ifseg_seg_rle_limit`): SEG_RLE_CHUNK, SEG_RLE_COLS and SEG_RLE_MAX_RUNS, which the tests hold against it"""
+    return _limits("ifseg_seg_rle_limit", 3)
+
+
+def _rle_max_runs(what, max_runs):
+    if not isinstance(max_runs, int) or isinstance(max_runs, bool) or not 1 <= max_runs <= SEG_RLE_MAX_RUNS:
+        raise ValueError("%s: max_runs must be an int in 1 .. %d, got %r" % (what, SEG_RLE_MAX_RUNS, max_runs))
+    return max_runs
+
+
+def _rle_runs(what, runs, shape, dev):
+    """a run table: contiguous int32 of `shape` on `dev`, at an 8-byte aligned address (a run is one 8-byte word)"""
+    if not torch.is_tensor(runs) or runs.dtype != torch.int32 or tuple(runs.shape) != tuple(shape) or not runs.is_contiguous() \
+            or runs.device != dev or runs.data_ptr() % 8:
+        raise ValueError("%s: runs must be a contiguous, 8-byte aligned int32 tensor of shape %s on %s, got %s" % (
+            what, tuple(shape), dev, (runs.dtype, tuple(runs.shape), runs.stride(), runs.device, runs.data_ptr() % 8)
+            if torch.is_tensor(runs) else type(runs)))
+    return runs
+
+
+def seg_rle_encode(labels, max_runs=65536, runs=None, count=None):
+    """labels uint8 / int16 [H, W] or [B, H, W] -> (runs int32 [B, R, 2], count int32 [B]), R = max_runs and the leading B
+    absent for an [H, W] map: the map's runs in COCO's run order (csrc/rle.hip; `predict.rle_encode_reference` is the
+    specification and states the rule).  Per image f[i] = labels[i % H, i // H]; position i starts a run iff i == 0 or
+    f[i] != f[i - 1]; runs[s] = (start, value) for s < min(count, R), in ascending order of start; count may exceed R -- entries
+    from min(count, R) on are not written (a table allocated here is zero there).  Three launches on the current stream,
+    nothing synchronises; integers with one writer per word, so two calls give equal bits.  runs / count: written in place when
+    given.  The segment counts (int32, W ceil(H / 32) per image) are allocated here, and, where no runs is given, one zero-filled
+    table.  Bad arguments: ValueError naming the argument, before anything is launched."""
+    what = "seg_rle_encode"
+    B, H, W = _region_maps(what, labels, 4, (torch.uint8, torch.int16))
+    R = _rle_max_runs(what, max_runs)
+    dev, lead = labels.device, tuple(labels.shape[:-2])
+    if runs is not None:
+        _rle_runs(what, runs, lead + (R, 2), dev)
+        if _overlap(runs, labels):
+            raise ValueError("%s: runs overlaps labels" % what)
+    count = _region_table_out(what, "count", count, lead, torch.int32, dev, (("labels", labels), ("runs", runs)))
+    if runs is None:
+        runs = torch.zeros(lead + (R, 2), dtype=torch.int32, device=dev)
+    if count is None:
+        count = torch.empty(lead, dtype=torch.int32, device=dev)
+    seg = torch.empty(B * W * -(-H // SEG_RLE_CHUNK), dtype=torch.int32, device=dev)
+    _check(lib().ifseg_seg_rle_encode(_ptr(labels), c_int(labels.element_size()), c_int(B), c_int(H), c_int(W), c_int(R),
+                                      _ptr(seg), _ptr(runs), _ptr(count), _stream()), what)
+    return runs, count
+
+
+def seg_rle_decode(runs, count, H, W, dtype=torch.uint8, fill=255, out=None, flag=None):
+    """runs int32 [R, 2] or [B, R, 2], count int32 of the leading shape -> (out `dtype` [H, W] or [B, H, W], flag): the label
+    map of a run table in one launch (csrc/rle.hip; `predict.rle_decode_reference` is the specification).  With
+    m = min(count, R): out[y, x] = value[s], s the largest index below m with start[s] <= x H + y; with m <= 0 the image is
+    `fill`.  flag: an int32 word that gets bit 0 where count > R (a truncated table: the tail carries the last written run's
+    value) and bit 1 where m <= 0 or start[0] != 0; given: never cleared here, else a fresh zeroed one.  No index into the table
+    leaves [0, m), whatever it holds.  `seg_rle_decode(*seg_rle_encode(x), H, W, x.dtype)[0]` is x wherever count <= R.  out:
+    written in place when given.  Bad arguments: ValueError naming the argument, before anything is launched."""
+    what = "seg_rle_decode"
+    if not torch.is_tensor(runs) or runs.dim() not in (2, 3):
+        raise ValueError("%s: runs must be an int32 tensor [R, 2] or [B, R, 2], got %s" % (
+            what, tuple(runs.shape) if torch.is_tensor(runs) else type(runs)))
+    dev, lead = runs.device, tuple(runs.shape[:-2])
+    R = int(runs.shape[-2])
+    if not 1 <= R <= SEG_RLE_MAX_RUNS:
+        raise ValueError("%s: runs must hold 1 .. %d runs, got %d" % (what, SEG_RLE_MAX_RUNS, R))
+    _rle_runs(what, runs, lead + (R, 2), dev)
+    for name, v in (("H", H), ("W", W)):
+        if not isinstance(v, int) or isinstance(v, bool) or v < 1:
+            raise ValueError("%s: %s must be a positive int, got %r" % (what, name, v))
+    B = runs.shape[0] if lead else 1
+    if B < 1 or B * H * W >= 2 ** 31:
+        raise ValueError("%s: H and W must give 1 .. 2**31 - 1 pixels in all, got B, H, W = %d, %d, %d" % (what, B, H, W))
+    if dtype not in (torch.uint8, torch.int16):
+        raise ValueError("%s: dtype must be torch.uint8 or torch.int16, got %r" % (what, dtype))
+    lo, hi = (0, 255) if dtype == torch.uint8 else (-2 ** 15, 2 ** 15 - 1)
+    if not isinstance(fill, int) or isinstance(fill, bool) or not lo <= fill <= hi:
+        raise ValueError("%s: fill must be an int in %d .. %d, got %r" % (what, lo, hi, fill))
+    given = [("runs", runs)]
+    count = _region_table_out(what, "count", count, lead, torch.int32, dev, given)
+    if count is None:
+        raise ValueError("%s: count must be an int32 tensor of shape %s, got None" % (what, lead))
+    given.append(("count", count))
+    out = _region_table_out(what, "out", out, lead + (H, W), dtype, dev, given)
+    if flag is not None:
+        _region_flag(what, flag, dev)
+        for name, t in given + [("out", out)]:
+            if t is not None and _overlap(t, flag):
+                raise ValueError("%s: %s overlaps flag" % (what, name))
+    flag = _region_flag(what, flag, dev)
+    if out is None:
+        out = torch.empty(lead + (H, W), dtype=dtype, device=dev)
+    _check(lib().ifseg_seg_rle_decode(_ptr(runs), _ptr(count), c_int(B), c_int(H), c_int(W), c_int(R), c_int(out.element_size()),
+                                      c_int(fill), _ptr(out), _ptr(flag), _stream()), what)
+    return out, flag
+
+
 # --------------------------------------------------------------------------- pixel-adaptive mask refinement (csrc/pamr.hip)
 SEG_PAMR_MAX_DILATIONS = 8          # == PM_MAX_D: the dilations of a call at most (8 neighbours each)
 SEG_PAMR_MAX_DILATION = 32          # == PM_MAX_DILATION: the largest dilation (a tile's halo: 40 KiB of LDS)

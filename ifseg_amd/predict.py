@@ -139,6 +139,14 @@ on the device.  `region_table_reference` is the specification; `RegionTable.to_l
     for t in seg.regions_raw(photos, min_region=50):                # [RegionTable(rows, sums, count, slot, labels, conf)]
         print(t.to_list(names))                                     # [{"value", "name", "area", "box", "centroid", "confidence"}]
 
+Label maps leave the device as run tables: `export_raw` is `segment_raw`, then one `hip.seg_rle_encode` per image
+(csrc/rle.hip, three launches): the map's runs (start, value) in COCO's column-major run order, on the device.
+`rle_encode_reference` / `rle_decode_reference` are the specifications; `RunLengthMap.to_coco` is the one host round trip and
+gives COCO stuff results (`coco_counts`, `coco_rle_string`: cocoapi's RLE string, written here from its algorithm).
+
+    for i, m in enumerate(seg.export_raw(photos)):                  # [RunLengthMap(runs, count, shape, dtype)]
+        results += m.to_coco(image_id=i, category_ids=ids)          # [{"image_id", "category_id", "segmentation"}]
+
 A cheap refinement that looks at the photograph: `Segmenter(..., pamr_iters=10)` runs pixel-adaptive mask refinement (PAMR,
 Araslanov & Roth, CVPR 2020; what MaskCLIP applies to its pseudo-labels) on the resized values of every image, in the slot of
 the CRF: `hip.seg_pamr` (csrc/pamr.hip), one affinity launch on the original uint8 photo and one launch per iteration.  Each
@@ -1173,6 +1181,255 @@ class RegionTable:
         return out
 
 
+def _max_runs_arg(what, max_runs):
+    if not isinstance(max_runs, int) or isinstance(max_runs, bool) or not 1 <= max_runs <= hip.SEG_RLE_MAX_RUNS:
+        raise ValueError("%s: max_runs must be an int in 1 .. %d, got %r" % (what, hip.SEG_RLE_MAX_RUNS, max_runs))
+    return max_runs
+
+
+def rle_encode_reference(labels, max_runs=65536):
+    """Specification of hip.seg_rle_encode: labels uint8 / int16 [H, W] (or [B, H, W]) -> (runs int32 [B, R, 2], count int32
+    [B]), R = max_runs, the leading B absent for an [H, W] map: the runs of each map in COCO's run order.
+
+    Per image f[i] = labels[i % H, i // H] for 0 <= i < H W: column-major.  Position i starts a run iff i == 0 or
+    f[i] != f[i - 1], the values compared as they are (255 and negative int16 values are values of their own).  A run goes on
+    across a column boundary, as COCO's does, and never from one image into the next.  Runs are numbered 0, 1, ... in
+    ascending order of start; count[b] is their number, which may exceed R.  For s < min(count[b], R),
+    runs[b, s] = (start, value); the entries behind are zero here (the kernel does not write them).  A run's length is the
+    next run's start (H W for the last) minus its own.  Everything is an integer.  A bad argument is a ValueError naming it.
+    Runs on any device."""
+    what = "rle_encode_reference"
+    R = _max_runs_arg(what, max_runs)
+    labels = torch.as_tensor(labels)
+    if labels.dtype not in (torch.uint8, torch.int16):
+        raise ValueError("%s: labels must be uint8 or int16, got %s" % (what, labels.dtype))
+    labels = _region_labels(what, labels)
+    lead, (H, W) = tuple(labels.shape[:-2]), labels.shape[-2:]
+    dev = labels.device
+    f = labels.reshape(-1, H, W).transpose(1, 2).reshape(-1, H * W).long()
+    B = f.shape[0]
+    first = torch.ones(B, 1, dtype=torch.bool, device=dev)
+    flag = torch.cat([first, f[:, 1:] != f[:, :-1]], 1)
+    number = flag.long().cumsum(1) - 1
+    count = flag.sum(1)
+    runs = torch.zeros(B * R, 2, dtype=torch.int64, device=dev)
+    on = flag & (number < R)
+    key = (number + torch.arange(B, dtype=torch.int64, device=dev).reshape(B, 1) * R)[on]
+    pos = torch.arange(H * W, dtype=torch.int64, device=dev).reshape(1, H * W).expand(B, H * W)
+    runs[key, 0], runs[key, 1] = pos[on], f[on]
+    return runs.to(torch.int32).reshape(lead + (R, 2)), count.to(torch.int32).reshape(lead)
+
+
+def rle_decode_reference(runs, count, H, W, dtype=torch.uint8, fill=255):
+    """Specification of hip.seg_rle_decode: runs int32 [R, 2] (or [B, R, 2]), count int32 of the leading shape -> (out `dtype`
+    [H, W] (or [B, H, W]), flag int32 [1]).  With m = min(count[b], R): out[b, y, x] = (dtype) value[s], s the largest index
+    below m with start[s] <= x H + y (0 where there is none: flag bit 1 says so); with m <= 0 the image is `fill`.  flag: bit 0
+    where count[b] > R -- a truncated table, whose tail carries the last written run's value -- and bit 1 where m <= 0 or
+    start[0] != 0, over all images.  For a table whose starts do not ascend the pixels are whatever the search finds (the
+    kernel's search differs); the flag bits hold for any table.  `rle_decode_reference(*rle_encode_reference(x, R), H, W,
+    x.dtype)[0]` is x wherever count <= R.  Runs on any device."""
+    what = "rle_decode_reference"
+    runs, count = torch.as_tensor(runs), torch.as_tensor(count)
+    if runs.dtype != torch.int32 or runs.dim() not in (2, 3) or runs.shape[-1] != 2 or runs.shape[-2] < 1:
+        raise ValueError("%s: runs must be int32 [R, 2] or [B, R, 2], got %s %s" % (what, runs.dtype, tuple(runs.shape)))
+    lead, R = tuple(runs.shape[:-2]), int(runs.shape[-2])
+    if count.dtype != torch.int32 or tuple(count.shape) != lead:
+        raise ValueError("%s: count must be int32 %s, got %s %s" % (what, lead, count.dtype, tuple(count.shape)))
+    if dtype not in (torch.uint8, torch.int16):
+        raise ValueError("%s: dtype must be torch.uint8 or torch.int16, got %r" % (what, dtype))
+    dev = runs.device
+    tab, cnt = runs.reshape(-1, R, 2).long(), count.reshape(-1).long().to(dev)
+    B = tab.shape[0]
+    out = torch.empty(B, H, W, dtype=dtype, device=dev)
+    pos = (torch.arange(W, dtype=torch.int64, device=dev).reshape(1, W) * H
+           + torch.arange(H, dtype=torch.int64, device=dev).reshape(H, 1))          # [H, W]: x H + y
+    flag = 0
+    for b in range(B):
+        c = int(cnt[b])
+        m = min(c, R)
+        flag |= (1 if c > R else 0) | (2 if m <= 0 or int(tab[b, 0, 0]) != 0 else 0)
+        if m <= 0:
+            out[b] = fill
+            continue
+        s = (torch.searchsorted(tab[b, :m, 0].contiguous(), pos.reshape(-1), right=True) - 1).clamp(0, m - 1)
+        out[b] = tab[b, :m, 1][s].reshape(H, W).to(dtype)
+    return out.reshape(lead + (H, W)), torch.tensor([flag], dtype=torch.int32, device=dev)
+
+
+# ---- COCO's RLE on the host: the counts of a class's binary mask and cocoapi's string form of them (maskApi.c: rleToString,
+# rleFrString).  pycocotools is not needed; no string it produced has been compared.
+def coco_counts(starts, values, c, HW):
+    """the uncompressed COCO counts of the binary mask `labels == c`, from a label map's runs in COCO's order (starts and
+    values of equal length, ascending starts from 0, HW pixels in all) -> a list of ints that alternates 0-runs and 1-runs and
+    begins with a 0-run, which may be 0 long.  A class that is absent gives [HW]."""
+    import numpy as np
+    starts, values = np.asarray(starts, dtype=np.int64).reshape(-1), np.asarray(values, dtype=np.int64).reshape(-1)
+    if starts.shape != values.shape or starts.size < 1 or starts[0] != 0 or HW < 1 or (np.diff(starts) <= 0).any() or starts[-1] >= HW:
+        raise ValueError("coco_counts: starts must ascend from 0 below HW = %r and match values, got %d starts and %d values"
+                         % (HW, starts.size, values.size))
+    on = values == c
+    change = np.flatnonzero(on[1:] != on[:-1]) + 1                  # the runs at which the mask changes
+    bounds = np.concatenate([starts[:1], starts[change], [HW]])
+    counts = np.diff(bounds).tolist()
+    return [0] + counts if on[0] else counts
+
+
+def coco_mask_reference(labels, c):
+    """the same list as `coco_counts`, taken from the dense mask directly: labels [H, W] -> the run lengths of
+    (labels == c) in column-major order, beginning with the 0-run"""
+    import numpy as np
+    f = (np.asarray(torch.as_tensor(labels).cpu()).astype(np.int64) == c).T.reshape(-1)
+    change = np.flatnonzero(f[1:] != f[:-1]) + 1
+    counts = np.diff(np.concatenate([[0], change, [f.size]])).tolist()
+    return [0] + counts if f[0] else counts
+
+
+def coco_rle_string(counts):
+    """cocoapi's rleToString: the compressed string of uncompressed counts.  From the fourth count on the stored value is
+    counts[i] - counts[i - 2]; each value leaves 5 bits at a time, low bits first, a chunk carrying bit 0x20 while more follow
+    (more: x != -1 where bit 4 of the chunk is set, else x != 0, x shifted arithmetically), as the char chunk + 48"""
+    out = []
+    for i, x in enumerate(counts):
+        x = int(x)
+        if i > 2:
+            x -= int(counts[i - 2])
+        more = True
+        while more:
+            c = x & 0x1f
+            x >>= 5                                                 # arithmetic, as C's on a signed long
+            more = x != -1 if c & 0x10 else x != 0
+            if more:
+                c |= 0x20
+            out.append(chr(c + 48))
+    return "".join(out)
+
+
+def coco_rle_counts(string):
+    """cocoapi's rleFrString: the counts of a compressed string; the last chunk of a value sign-extends"""
+    counts, p, n = [], 0, len(string)
+    while p < n:
+        x, k, more = 0, 0, True
+        while more:
+            if p >= n:
+                raise ValueError("coco_rle_counts: the string ends inside a value")
+            c = ord(string[p]) - 48
+            if not 0 <= c < 64:
+                raise ValueError("coco_rle_counts: %r at %d is no RLE character" % (string[p], p))
+            x |= (c & 0x1f) << (5 * k)
+            more = bool(c & 0x20)
+            p += 1
+            k += 1
+            if not more and c & 0x10:
+                x |= -1 << (5 * k)
+        if len(counts) > 2:
+            x += counts[-2]
+        counts.append(x)
+    return counts
+
+
+class RunLengthMap:
+    """ONE image's label map as the table of its runs in COCO's run order, on the device: what `hip.seg_rle_encode` wrote
+    (runs int32 [R, 2] of (start, value), count int32 scalar) with the map's shape (H, W) and dtype.  count may exceed
+    R = runs.shape[0]: `truncated()`.  The accessors return device tensors of the WRITTEN runs, the first min(count, R); which
+    those are is decided on the device (a boolean mask), so only `to_coco` synchronises with the host.  n: the number of
+    classes where the maker knows it (a Segmenter does), else None."""
+
+    def __init__(self, runs, count, shape, dtype, n=None):
+        self.runs, self.count, self.shape, self.dtype, self.n = runs, count, (int(shape[0]), int(shape[1])), dtype, n
+
+    @property
+    def max_runs(self):
+        return int(self.runs.shape[0])
+
+    @property
+    def nbytes(self):
+        """the bytes of the table as it is held: 8 per entry of runs and the count word (a stored table needs the first
+        `count` entries only)"""
+        return self.runs.numel() * 4 + 4
+
+    def truncated(self):
+        """device bool: the map has more runs than the table holds"""
+        return self.count > self.max_runs
+
+    def _written(self):
+        return torch.arange(self.max_runs, device=self.runs.device) < self.count
+
+    def starts(self):
+        return self.runs[self._written(), 0]
+
+    def values(self):
+        return self.runs[self._written(), 1]
+
+    def lengths(self):
+        """int32 [k]: the next run's start minus the run's own, the last run ending at H W (in a truncated table the last
+        written run carries the rest of the map)"""
+        s = self.starts()
+        return torch.diff(s, append=s.new_full((1,), self.shape[0] * self.shape[1]))
+
+    def areas(self, n):
+        """int64 [n]: the pixels of every class 0 .. n - 1, from values and lengths"""
+        v, l = self.values().long(), self.lengths().long()
+        ok = (v >= 0) & (v < n)
+        return torch.zeros(n, dtype=torch.int64, device=v.device).index_add_(0, torch.where(ok, v, torch.zeros_like(v)),
+                                                                            torch.where(ok, l, torch.zeros_like(l)))
+
+    def decode(self, out=None):
+        """the label map [H, W] of `dtype` again: one `hip.seg_rle_decode`"""
+        return hip.seg_rle_decode(self.runs, self.count, self.shape[0], self.shape[1], self.dtype, out=out)[0]
+
+    def _classes(self, category_ids):
+        if category_ids is not None:
+            return len(category_ids)
+        return self.n if self.n is not None else 255
+
+    def to_coco(self, image_id, category_ids=None):
+        """the one host round trip -> COCO stuff results: a list of dicts(image_id, category_id, segmentation=dict(size=[H, W],
+        counts=<compressed str>)), one per value in [0, n) that the map holds, in ascending class order; n = len(category_ids)
+        where given, else the maker's class count, else 255.  category_id = category_ids[c] if given, else c.  A value outside
+        [0, n), such as 255, gets no entry.  A truncated table is a ValueError."""
+        H, W = self.shape
+        count = int(self.count)
+        if count > self.max_runs:
+            raise ValueError("RunLengthMap.to_coco: the table is truncated: the map has %d runs, max_runs is %d" % (count, self.max_runs))
+        tab = self.runs[:count].cpu().numpy()
+        starts, values = tab[:, 0], tab[:, 1]
+        n = self._classes(category_ids)
+        out = []
+        for c in sorted(set(int(v) for v in values.tolist() if 0 <= v < n)):
+            out.append({"image_id": image_id, "category_id": category_ids[c] if category_ids is not None else c,
+                        "segmentation": {"size": [H, W], "counts": coco_rle_string(coco_counts(starts, values, c, H * W))}})
+        return out
+
+    @classmethod
+    def from_coco(cls, entries, shape, class_of=None, fill=255, dtype=torch.uint8, device=None, n=None):
+        """the other way, on the host: COCO results of ONE image (dicts with category_id and segmentation: size, counts as a
+        compressed str or a list) -> the RunLengthMap of the label map that holds class_of[category_id] (category_id itself
+        without class_of) under every mask and `fill` elsewhere, equal neighbours merged into one run.  The masks must be
+        disjoint and of `shape`, else ValueError."""
+        import numpy as np
+        H, W = int(shape[0]), int(shape[1])
+        flat = np.full(H * W, fill, dtype=np.int64)
+        taken = np.zeros(H * W, dtype=bool)
+        for e in entries:
+            seg = e["segmentation"]
+            if [int(v) for v in seg["size"]] != [H, W]:
+                raise ValueError("RunLengthMap.from_coco: an entry of size %r in a map of shape %r" % (seg["size"], (H, W)))
+            counts = coco_rle_counts(seg["counts"]) if isinstance(seg["counts"], str) else [int(v) for v in seg["counts"]]
+            if sum(counts) != H * W or any(v < 0 for v in counts):
+                raise ValueError("RunLengthMap.from_coco: the counts of category %r do not add up to H W = %d" % (e["category_id"], H * W))
+            value = class_of[e["category_id"]] if class_of is not None else e["category_id"]
+            ends = np.cumsum(counts)
+            for a, b in zip(ends[0::2].tolist(), ends[1::2].tolist()):         # the 1-runs
+                if taken[a:b].any():
+                    raise ValueError("RunLengthMap.from_coco: the mask of category %r overlaps another" % (e["category_id"],))
+                taken[a:b] = True
+                flat[a:b] = value
+        starts = np.concatenate([[0], np.flatnonzero(flat[1:] != flat[:-1]) + 1])
+        runs = torch.from_numpy(np.stack([starts, flat[starts]], 1)).to(torch.int32)
+        count = torch.tensor(len(starts), dtype=torch.int32)
+        return cls(runs.to(device=device), count.to(device=device), (H, W), dtype, n)
+
+
 def _check_sieve(sieve, sieve_connectivity, sieve_passes):
     """the three sieve keywords of the Segmenter, checked -> (sieve, sieve_connectivity, sieve_passes)"""
     if sieve is not None and (not isinstance(sieve, int) or isinstance(sieve, bool) or not 1 <= sieve < 2 ** 31):
@@ -2110,6 +2367,38 @@ class Segmenter:
             [(res.labels[b], None if res.conf is None else res.conf[b]) for b in range(res.labels.shape[0])]
         with torch.no_grad():
             return [self._region_table(l, c, min_region, connectivity, max_regions, ignore) for l, c in per_image]
+
+    # -- run-length label maps ------------------------------------------------------------------
+    def _run_length_map(self, labels, max_runs):
+        """one image's labels [H, W] -> its RunLengthMap through one `hip.seg_rle_encode`"""
+        labels = labels.contiguous()
+        runs, count = hip.seg_rle_encode(labels, max_runs)
+        return RunLengthMap(runs, count, tuple(labels.shape), labels.dtype, self.n)
+
+    def export_raw(self, images, max_runs=65536, max_batch=8, scales=(1.0,), flip=False, slide=None, mean=None, std=None,
+                   reverse_channels=False):
+        """Raw images -> their label maps as run tables in COCO's run order: a list of `RunLengthMap` in input order, on the
+        device; `RunLengthMap.to_coco` gives COCO stuff results.
+
+        images, scales, flip, slide, max_batch, mean, std, reverse_channels: as in `segment_raw`, which runs unchanged, with no
+        conf asked for (behind the CRF / PAMR / sieve where this Segmenter has them); then ONE `hip.seg_rle_encode` per image
+        (`rle_encode_reference` states the rule): the first max_runs runs of the map (`RunLengthMap.truncated()` says whether
+        it has more).  Nothing synchronises with the host; `RunLengthMap.to_coco` is the one round trip.  A bad argument is a
+        ValueError before anything is launched."""
+        _max_runs_arg("Segmenter.export_raw", max_runs)
+        res = self.segment_raw(images, max_batch=max_batch, mean=mean, std=std, reverse_channels=reverse_channels, scales=scales,
+                               flip=flip, slide=slide)
+        with torch.no_grad():
+            return [self._run_length_map(r.labels, max_runs) for r in res]
+
+    def export(self, images, out_hw=None, crf_images=None, max_runs=65536):
+        """`export_raw` for what `__call__` takes: a ready batch (and out_hw, crf_images as there) -> a list of `RunLengthMap`,
+        one per image of the batch, each through one `hip.seg_rle_encode` behind `__call__`'s launches"""
+        _max_runs_arg("Segmenter.export", max_runs)
+        res = self(images, out_hw=out_hw, crf_images=crf_images)
+        maps = [r.labels[0] for r in res] if isinstance(res, list) else [res.labels[b] for b in range(res.labels.shape[0])]
+        with torch.no_grad():
+            return [self._run_length_map(l, max_runs) for l in maps]
 
     # -- scoring against ground truth -----------------------------------------------------
     def _score_into(self, what, into, dev, confusion=False, boundary_iou=False, shapes=(), calibration=False, sl=None):

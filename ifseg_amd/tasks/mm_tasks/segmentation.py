@@ -264,6 +264,17 @@ class SegmentationTask(TaskBase):
         seg = self.build_segmenter(model, **{k: kw.pop(k) for k in keywords if k in kw})
         return seg.regions_raw(images, **kw)
 
+    def export_raw(self, model, images, **kw):
+        """raw uint8 images -> a list of `RunLengthMap`, each image's label map as its runs in COCO's run order on the device
+        (`.to_coco(image_id, category_ids)` gives COCO stuff results): `build_segmenter(model, ...).export_raw(images, ...)`.
+        Keywords of the Segmenter's constructor (read from its signature) go to it, the others -- `max_runs` and
+        `segment_raw`'s -- to `Segmenter.export_raw`."""
+        import inspect
+        from ...predict import Segmenter
+        keywords = [k for k in inspect.signature(Segmenter.__init__).parameters if k not in ("self", "model", "task")]
+        seg = self.build_segmenter(model, **{k: kw.pop(k) for k in keywords if k in kw})
+        return seg.export_raw(images, **kw)
+
     def self_train_sample(self, model, images, first_ordinal, trainer=None, confidence_weight=False, **kw):
         """One batch of self-training on unlabeled photographs: `pseudo_label_raw(model, images, **kw)` and then
         `train_sample(images, [r.labels ...], first_ordinal)` on the model's own confident pixels -> the batch

@@ -1071,6 +1071,34 @@ int ifseg_seg_region_table(const void* labels, int label_bytes, const float* con
  * IFSEG_ERR_BAD_ARG. */
 int ifseg_seg_region_table_limit(int which);
 
+/* ---- run-length label maps in COCO's run order (csrc/rle.hip; ifseg_amd/predict.py rle_encode_reference and
+ * rle_decode_reference are the specifications; the reference has no counterpart) ----
+ * labels [B][H][W], uint8 (label_bytes 1) or int16 (2).  Per image f[i] = labels[i % H][i / H], 0 <= i < H W: column-major, the
+ * order of COCO's RLE.  Position i starts a run iff i == 0 or f[i] != f[i - 1], the values compared as they are; a run goes on
+ * across a column boundary and never from one image into the next.  Runs are numbered 0, 1, ... in ascending order of start.
+ *   count int32 [B]        the runs of each image; it may exceed R
+ *   runs  int32 [B][R][2]  run s < min(count[b], R) = (start, value), one 8-byte store; entries behind are NOT written
+ * A run's length is the next run's start (H W for the last one) minus its own.  Three launches on the stream (per 64 columns x
+ * 32 rows the run starts counted per column segment; one workgroup per image scans the segments' counts; the walk again with
+ * the ranks).  seg: int32 [B][W ceil(H / 32)], the caller's, written in full.  Integers, one writer per word, no atomics: two
+ * calls give equal bits.
+ * NULL pointers, label_bytes outside {1, 2}, int16 labels at an odd address, seg / count not 4-byte aligned, runs not 8-byte
+ * aligned, any two buffers sharing a byte, R outside 1..2^24: IFSEG_ERR_BAD_ARG; B, H, W < 1 or B*H*W >= 2^31:
+ * IFSEG_ERR_BAD_SHAPE.  Nothing is launched on a refusal. */
+int ifseg_seg_rle_encode(const void* labels, int label_bytes, int B, int H, int W, int R, int* seg, int* runs, int* count,
+                         void* stream);
+/* The way back, one launch: with m = min(count[b], R), out[b][y][x] = (uint8 or int16 by label_bytes) value[s], s the largest
+ * index below m with start[s] <= x H + y (s = 0 where there is none); with m <= 0 the image is `fill`.  *flag |= 1 where
+ * count[b] > R (a truncated table: the tail carries the last written run's value), |= 2 where m <= 0 or start[0] != 0; the
+ * word is never cleared here.  No index into the table leaves [0, m) whatever it holds.
+ * NULL pointers, label_bytes outside {1, 2}, int16 out at an odd address, count / flag not 4-byte aligned, runs not 8-byte
+ * aligned, any two buffers sharing a byte, R outside 1..2^24, fill outside the output type: IFSEG_ERR_BAD_ARG; B, H, W < 1 or
+ * B*H*W >= 2^31: IFSEG_ERR_BAD_SHAPE.  Nothing is launched on a refusal. */
+int ifseg_seg_rle_decode(const int* runs, const int* count, int B, int H, int W, int R, int label_bytes, int fill, void* out,
+                         int* flag, void* stream);
+/* which = 0: the rows of a chunk, 1: the columns of a workgroup, 2: the largest R; any other which: IFSEG_ERR_BAD_ARG. */
+int ifseg_seg_rle_limit(int which);
+
 /* ---- pixel-adaptive mask refinement (PAMR: Araslanov & Roth, CVPR 2020; Segmenter(pamr_iters=); the reference has no
  * counterpart) ----  A few iterations of a local, image-adaptive, convex averaging of the class values of ONE image at image
  * resolution, linear in the pixels; csrc/pamr.hip; ifseg_amd/predict.py pamr_reference is the specification.
