@@ -1609,6 +1609,121 @@ def seg_boundary_areas(labels, gt, n, d, raw_labels=True, bareas=None, band=Fals
     return bareas, out
 
 
+# the limits of csrc/distance.hip
+SEG_DISTANCE_MAX = 128              # == SEG_DISTANCE_MAX there: the largest max_distance / radius; 128^2 fits the uint16
+SEG_DISTANCE_FAR = 65535            # == SEG_DISTANCE_FAR: farther than max_distance, or no other value in the image
+SEG_TRIMAP_MAX_RADII = 8            # == SEG_TRIMAP_MAX_RADII: the rings of one counting launch (K 3 n uint32 of LDS)
+
+
+def seg_distance_limits():
+    """-> (the largest max_distance, the "far" value, the largest number of radii, the largest n) as the loaded library states
+    them (`ifseg_seg_distance_limit`): SEG_DISTANCE_MAX, SEG_DISTANCE_FAR, SEG_TRIMAP_MAX_RADII and SEG_PREDICT_MAX_CLASSES,
+    which the tests hold against it"""
+    return _limits("ifseg_seg_distance_limit", 4)
+
+
+def _distance_map(what, name, t, like=None):
+    """a label map of the distance kernels, as ValueErrors that name the argument -> (B, H, W)"""
+    if not torch.is_tensor(t) or t.dtype not in (torch.uint8, torch.int16):
+        raise ValueError("%s: %s must be a uint8 / int16 tensor, got %s" % (what, name, t.dtype if torch.is_tensor(t) else type(t)))
+    if t.dim() not in (2, 3) or not t.is_contiguous() or not 1 <= t.numel() < 2 ** 31:
+        raise ValueError("%s: %s must be contiguous [H, W] or [B, H, W] with 1 .. 2**31 - 1 pixels, got %s with strides %s"
+                         % (what, name, tuple(t.shape), t.stride()))
+    if like is not None and (t.shape != like.shape or t.device != like.device):
+        raise ValueError("%s: %s must have the labels' shape %s on %s, got %s on %s"
+                         % (what, name, tuple(like.shape), like.device, tuple(t.shape), t.device))
+    H, W = t.shape[-2:]
+    return t.numel() // (H * W), int(H), int(W)
+
+
+def _distance_plane(what, name, t, like, others):
+    """a distance plane: the caller's (contiguous uint16 of `like`'s shape on its device, sharing no byte with `others`)"""
+    if not torch.is_tensor(t) or t.dtype != torch.uint16 or t.shape != like.shape or not t.is_contiguous() or t.device != like.device:
+        raise ValueError("%s: %s must be a contiguous uint16 tensor of shape %s on %s, got %s" % (
+            what, name, tuple(like.shape), like.device,
+            (t.dtype, tuple(t.shape), t.stride(), t.device) if torch.is_tensor(t) else type(t)))
+    for other_name, other in others:
+        if _overlap(t, other):
+            raise ValueError("%s: %s overlaps %s" % (what, name, other_name))
+    return t
+
+
+def _max_distance(what, max_distance):
+    if not isinstance(max_distance, int) or isinstance(max_distance, bool) or not 1 <= max_distance <= SEG_DISTANCE_MAX:
+        raise ValueError("%s: max_distance must be an int in 1 .. %d, got %r" % (what, SEG_DISTANCE_MAX, max_distance))
+    return max_distance
+
+
+def seg_distance(labels, max_distance, border=False, out=None):
+    """labels uint8 / int16 [H, W] or [B, H, W], max_distance = R an int in 1 .. SEG_DISTANCE_MAX -> out uint16 of the labels'
+    shape: per pixel the exact squared Euclidean distance to the nearest pixel of ANOTHER value of the same image where it is
+    at most R^2, else SEG_DISTANCE_FAR = 65535 (csrc/distance.hip; `predict.distance_reference` is the specification and
+    states the rule).  border: every position outside the image counts as another value too.  Two launches on the current
+    stream, nothing synchronises; integers with one writer per element, so two calls give equal bits.  out: written in place
+    when given.  The work plane (uint8 of the labels' shape, the clamped vertical distances) is allocated here.  Bad arguments:
+    ValueError naming the argument, before anything is launched."""
+    what = "seg_distance"
+    B, H, W = _distance_map(what, "labels", labels)
+    R = _max_distance(what, max_distance)
+    if not isinstance(border, bool):
+        raise ValueError("%s: border must be True or False, got %r" % (what, border))
+    if out is None:
+        out = torch.empty(labels.shape, dtype=torch.uint16, device=labels.device)
+    else:
+        _distance_plane(what, "out", out, labels, (("labels", labels),))
+    work = torch.empty(labels.shape, dtype=torch.uint8, device=labels.device)
+    _check(lib().ifseg_seg_distance(_ptr(labels), c_int(labels.element_size()), c_int(B), c_int(H), c_int(W), c_int(R),
+                                    c_int(1 if border else 0), _ptr(work), _ptr(out), _stream()), what)
+    return out
+
+
+def _trimap_radii(what, radii):
+    ok = isinstance(radii, (tuple, list)) and 1 <= len(radii) <= SEG_TRIMAP_MAX_RADII \
+        and all(isinstance(r, int) and not isinstance(r, bool) and 1 <= r <= SEG_DISTANCE_MAX for r in radii) \
+        and all(a < b for a, b in zip(radii, radii[1:]))
+    if not ok:
+        raise ValueError("%s: radii must be 1 .. %d strictly ascending ints in 1 .. %d, got %r"
+                         % (what, SEG_TRIMAP_MAX_RADII, SEG_DISTANCE_MAX, radii))
+    return tuple(radii)
+
+
+def seg_trimap_areas(labels, gt, n, radii, raw_labels=True, border=False, trimap=None, dist=None):
+    """labels uint8 / int16 [H, W] or [B, H, W] (predicted classes), gt uint8 / int16 of the same shape, radii a tuple of K
+    strictly ascending ints in 1 .. SEG_DISTANCE_MAX, 1 <= K <= SEG_TRIMAP_MAX_RADII -> (trimap int64 [K, 3, n], the ground
+    truth's distance plane uint16 of the maps' shape): `seg_areas`' three counters per ring of the trimap, ring k holding the
+    scored pixels whose squared distance d2 to the nearest ground-truth pixel of another value has
+    radii[k - 1]^2 < d2 <= radii[k]^2 (csrc/distance.hip; `predict.trimap_areas_reference` is the specification and states the
+    rule).  dist: the plane of `seg_distance(gt, R, border)` with R >= radii[-1], where the caller has it; else it is computed
+    here as `seg_distance(gt, radii[-1], border)` (two launches) and returned.  `trimap` given: ACCUMULATED into, else fresh
+    zeros.  One counting launch behind the distance's, nothing synchronises.  Bad arguments: ValueError naming the argument,
+    before anything is launched."""
+    what = "seg_trimap_areas"
+    B, H, W = _distance_map(what, "labels", labels)
+    _distance_map(what, "gt", gt, labels)
+    if not isinstance(n, int) or isinstance(n, bool) or not 1 <= n <= SEG_PREDICT_MAX_CLASSES:
+        raise ValueError("%s: n must be an int in 1 .. %d, got %r" % (what, SEG_PREDICT_MAX_CLASSES, n))
+    radii = _trimap_radii(what, radii)
+    if not isinstance(border, bool):
+        raise ValueError("%s: border must be True or False, got %r" % (what, border))
+    K = len(radii)
+    if trimap is None:
+        trimap = torch.zeros(K, 3, n, dtype=torch.int64, device=labels.device)
+    elif not torch.is_tensor(trimap) or trimap.dtype != torch.int64 or tuple(trimap.shape) != (K, 3, n) \
+            or not trimap.is_contiguous() or trimap.device != labels.device:
+        raise ValueError("%s: trimap must be a contiguous int64 tensor of shape %s on %s, got %s" % (
+            what, (K, 3, n), labels.device,
+            (trimap.dtype, tuple(trimap.shape), trimap.stride(), trimap.device) if torch.is_tensor(trimap) else type(trimap)))
+    if dist is None:
+        dist = seg_distance(gt, radii[-1], border)
+    else:
+        _distance_plane(what, "dist", dist, labels, (("trimap", trimap),))
+    table = (c_int * K)(*radii)
+    _check(lib().ifseg_seg_trimap_areas(_ptr(labels), c_int(labels.element_size()), _ptr(gt), c_int(gt.element_size()), _ptr(dist),
+                                        c_int(B), c_int(H), c_int(W), c_int(n), table, c_int(K), c_int(1 if raw_labels else 0),
+                                        _ptr(trimap), _stream()), what)
+    return trimap, dist
+
+
 def seg_score(scores, hp, wp, gt, raw_labels=True, labels=False, conf=False, probs=False, areas=None, tally=None,
               staging_bytes=None, label_dtype=None):
     """`seg_predict` at gt's own [B, h, w] with the scoring in the kernel's epilogue: -> (areas, tally, labels | None,

@@ -440,6 +440,108 @@ def boundary_areas_reference(labels, gt, n, d, raw_labels=True):
     return bareas, (gb.to(torch.uint8) | (pb.to(torch.uint8) << 1)).reshape(shape)
 
 
+def default_trimap_radii():
+    """the radii of the trimap curve where none are given: the band widths the DeepLab / PointRend / SegFix tables use, doubled
+    up to 32 pixels"""
+    return (1, 2, 4, 8, 16, 32)
+
+
+def _max_distance(what, max_distance):
+    if not isinstance(max_distance, int) or isinstance(max_distance, bool) or not 1 <= max_distance <= hip.SEG_DISTANCE_MAX:
+        raise ValueError("%s: max_distance must be an int in 1 .. %d (the largest distance told apart, in pixels), got %r"
+                         % (what, hip.SEG_DISTANCE_MAX, max_distance))
+    return max_distance
+
+
+def _trimap_radii(what, radii, name="radii"):
+    """the radii of a trimap curve, checked -> a tuple of 1 .. 8 strictly ascending ints in 1 .. 128"""
+    ok = isinstance(radii, (tuple, list)) and 1 <= len(radii) <= hip.SEG_TRIMAP_MAX_RADII \
+        and all(isinstance(r, int) and not isinstance(r, bool) and 1 <= r <= hip.SEG_DISTANCE_MAX for r in radii) \
+        and all(a < b for a, b in zip(radii, radii[1:]))
+    if not ok:
+        raise ValueError("%s: %s must be 1 .. %d strictly ascending ints in 1 .. %d (the trimap's band widths in pixels), got %r"
+                         % (what, name, hip.SEG_TRIMAP_MAX_RADII, hip.SEG_DISTANCE_MAX, radii))
+    return tuple(radii)
+
+
+def distance_reference(labels, max_distance, border=False):
+    """Specification of the exact squared Euclidean distance to the nearest pixel of another value (hip.seg_distance): labels
+    uint8 / int16 [H, W] or [B, H, W], R = max_distance an int in 1 .. 128 -> uint16 of the labels' shape.
+
+    With D2(p) = min over q of (px - qx)^2 + (py - qy)^2 over the pixels q of the SAME image with L(q) != L(p) -- values are
+    compared as they are: 255, a negative int16, anything outside [0, n) is a value of its own, as in
+    `boundary_areas_reference` and `regions_reference` -- and, with `border`, over every position q outside the image as
+    well (so D2 <= min(x + 1, W - x, y + 1, H - y)^2): the output is D2(p) where D2(p) <= R^2 and 65535
+    (`hip.SEG_DISTANCE_FAR`) where D2(p) > R^2 or no such q exists.  Distances never cross from one image of a batch into the
+    next.  For border=False this is `scipy.ndimage.distance_transform_edt(L == c)` squared at the pixels of every value c.
+
+    Evaluated one axis after the other, each by looking at every offset in -R .. R: v(x, y) = the least |dy| at which column
+    x holds another value (or leaves the image, with `border`), then D2 = min over dx of dx^2 + (0 where row y holds another
+    value at x + dx, or leaves the image with `border`; v(x + dx, y)^2 where it holds the same value).  An offset beyond the
+    image's own extent on its axis reaches nothing new (every position there is outside) and is left out.  Runs on any
+    device."""
+    R = _max_distance("distance_reference", max_distance)
+    labels = torch.as_tensor(labels)
+    if labels.dtype not in (torch.uint8, torch.int16) or labels.dim() not in (2, 3) or labels.numel() == 0:
+        raise ValueError("distance_reference: labels must be a uint8 or int16 map [H, W] or [B, H, W], got %s %s"
+                         % (labels.dtype, tuple(labels.shape)))
+    L = labels.long().reshape((-1,) + tuple(labels.shape[-2:]))
+    H, W = L.shape[-2:]
+    OUT, NONE = 1 << 20, 1 << 24                  # no label value; no distance (its square stays below 2^63)
+    Ry, Rx = min(R, H), min(R, W)
+    Lp = F.pad(L, (Rx, Rx, Ry, Ry), value=OUT)
+    v = torch.full_like(L, NONE)
+    for k in range(1, Ry + 1):
+        for s in (-k, k):
+            nb = Lp[:, Ry + s:Ry + s + H, Rx:Rx + W]
+            differs = (nb != L) if border else (nb != L) & (nb != OUT)
+            v = torch.where(differs & (v == NONE), torch.full_like(v, k), v)
+    vp = F.pad(v, (Rx, Rx), value=NONE)
+    best = v * v
+    for k in range(1, Rx + 1):
+        for s in (-k, k):
+            nb = Lp[:, Ry:Ry + H, Rx + s:Rx + s + W]
+            differs = (nb != L) if border else (nb != L) & (nb != OUT)
+            side = vp[:, :, Rx + s:Rx + s + W]
+            best = torch.minimum(best, torch.where(differs, torch.full_like(best, k * k), k * k + side * side))
+    # 65535 as the int16 of the same bits: torch.uint16 holds it, int16 carries it there
+    far = torch.where(best <= R * R, best, torch.full_like(best, hip.SEG_DISTANCE_FAR))
+    return far.to(torch.int32).to(torch.uint16).reshape(labels.shape)
+
+
+def trimap_areas_reference(labels, gt, n, radii, raw_labels=True, border=False, dist=None):
+    """Specification of the trimap counters (hip.seg_trimap_areas): labels and gt [H, W] or [B, H, W] as in
+    `areas_reference`, whose ground-truth rule and set of scored pixels these are; radii a tuple of 1 .. 8 strictly ascending
+    ints in 1 .. 128 -> int64 [K, 3, n].
+
+    With d2 = `distance_reference(gt, radii[-1], border)` of the GROUND TRUTH -- its raw values, so an ignore value is a value
+    of its own for the distance, as for Boundary IoU's band, and is never scored -- ring k holds the pixels with
+    r_{k-1}^2 < d2 <= r_k^2 (r_{-1} = 0), and out[k] is the three rows of `areas_reference` (intersect / predicted / label)
+    restricted to ring k.  The rings are disjoint: the counters add across images, and the figures
+    (`SegmentationScore.summary`) use their cumulative sum over k, the pixels within r_k of a ground-truth contour.
+    dist: that plane where the caller has it -- as `hip.seg_trimap_areas` takes it, of any max_distance >= radii[-1], which
+    puts the same pixels into the same rings.
+
+    NOT pinned: no upstream trimap code is available where this is tested.  DeepLab's trimap is a dilation of VOC's void band;
+    this rule is the Euclidean distance to a pixel of another ground-truth value.  Runs on any device."""
+    radii = _trimap_radii("trimap_areas_reference", radii)
+    pred, cls, scored, _ = _scored_mask("trimap_areas_reference", labels, gt, n, raw_labels)
+    if dist is None:
+        dist = distance_reference(torch.as_tensor(gt), radii[-1], border)
+    elif not torch.is_tensor(dist) or dist.dtype != torch.uint16 or dist.shape != torch.as_tensor(gt).shape:
+        raise ValueError("trimap_areas_reference: dist must be a uint16 plane of the ground truth's shape %s, got %s"
+                         % (tuple(torch.as_tensor(gt).shape), (dist.dtype, tuple(dist.shape)) if torch.is_tensor(dist) else type(dist)))
+    d2 = dist.to(pred.device).reshape(-1).long()
+    known = scored & (pred >= 0) & (pred < n)
+    out, lo = [], 0
+    for r in radii:
+        ring = (d2 > lo) & (d2 <= r * r)
+        out.append(torch.stack([torch.bincount(pred[known & (pred == cls) & ring], minlength=n),
+                                torch.bincount(pred[known & ring], minlength=n), torch.bincount(cls[scored & ring], minlength=n)]))
+        lo = r * r
+    return torch.stack(out)
+
+
 class RenderResult(NamedTuple):
     picture: torch.Tensor                      # [H, W, 3] uint8: the labels' colours over the image, on the device
     labels: torch.Tensor                       # [H, W] uint8 / int16: what `segment_raw` gave
@@ -1517,10 +1619,16 @@ class SegmentationScore:
     `calibration_reference`'s counters int64 [n, 256, 2] on the same device, pixels per (predicted class, confidence bin, hit);
     `evaluate_raw(..., calibration=True)` fills them (`hip.seg_calibration`), with `calibration_tally` int64 [2] beside them
     (scored pixels with a label inside / outside [0, n)).  `reliability`, `precision_thresholds` and `summary` ("ECE", "MCE",
-    "cECE") read them."""
+    "cECE") read them.
+
+    trimap: None (the default: no counters, memory and behaviour as without the argument), True (zeroed ones) or a tensor:
+    `trimap_areas_reference`'s counters int64 [K, 3, n] on the same device, the three rows of `areas` per ring of the
+    ground truth's distance to a contour, for the K radii `trimap_radii` (None: `default_trimap_radii()`);
+    `evaluate_raw(..., trimap=True)` fills them (`hip.seg_trimap_areas`), and `summary` / `trimap_summary` / `group_summary`
+    then report mIoU and accuracy within r pixels of a ground-truth contour, for every r."""
 
     def __init__(self, n, device=None, areas=None, tally=None, confusion=None, boundary=None, boundary_ratio=0.02,
-                 calibration=None):
+                 calibration=None, trimap=None, trimap_radii=None):
         self.n = int(n)
         self.areas = torch.zeros(3, self.n, dtype=torch.int64, device=device) if areas is None else areas
         self.tally = torch.zeros(2, dtype=torch.int64, device=device) if tally is None else tally
@@ -1563,6 +1671,19 @@ class SegmentationScore:
                                     if torch.is_tensor(calibration) else type(calibration)))
             self.calibration = calibration
             self.calibration_tally = torch.zeros(2, dtype=torch.int64, device=self.areas.device)
+        if trimap is None or trimap is False:
+            self.trimap = self.trimap_radii = None
+        else:
+            self.trimap_radii = _trimap_radii("SegmentationScore", default_trimap_radii() if trimap_radii is None else trimap_radii)
+            K = len(self.trimap_radii)
+            if trimap is True:
+                trimap = torch.zeros(K, 3, self.n, dtype=torch.int64, device=self.areas.device)
+            if not torch.is_tensor(trimap) or trimap.dtype != torch.int64 or tuple(trimap.shape) != (K, 3, self.n) \
+                    or trimap.device != self.areas.device:
+                raise ValueError("SegmentationScore: trimap must be None, True or int64 [%d, 3, %d] on the device of areas, got %s"
+                                 % (K, self.n, (trimap.dtype, tuple(trimap.shape), trimap.device)
+                                    if torch.is_tensor(trimap) else type(trimap)))
+            self.trimap = trimap
 
     def add_(self, other):
         if other.n != self.n:
@@ -1576,6 +1697,11 @@ class SegmentationScore:
         if self.boundary is not None and self.boundary_ratio != other.boundary_ratio:
             raise ValueError("SegmentationScore.add_: boundary counters of ratio %r against ratio %r: bands of different widths "
                              "do not add" % (self.boundary_ratio, other.boundary_ratio))
+        if (self.trimap is None) != (other.trimap is None):
+            raise ValueError("SegmentationScore.add_: one score has trimap counters and the other has none")
+        if self.trimap is not None and self.trimap_radii != other.trimap_radii:
+            raise ValueError("SegmentationScore.add_: trimap counters of radii %r against radii %r: rings of different widths "
+                             "do not add" % (self.trimap_radii, other.trimap_radii))
         self.areas += other.areas.to(self.areas.device)
         self.tally += other.tally.to(self.tally.device)
         if self.confusion is not None:
@@ -1585,6 +1711,8 @@ class SegmentationScore:
         if self.calibration is not None:
             self.calibration += other.calibration.to(self.calibration.device)
             self.calibration_tally += other.calibration_tally.to(self.calibration_tally.device)
+        if self.trimap is not None:
+            self.trimap += other.trimap.to(self.trimap.device)
         return self
 
     def _matrix(self, what):
@@ -1622,7 +1750,8 @@ class SegmentationScore:
         raw_labels=False)` with -1 -> m in the ground truth.  Needs a confusion matrix (ValueError without one).
         The new score carries NO boundary counters, whether this one does or not: merging classes erases the contours between
         them, so the band areas of a coarser label set do not follow from the finer one's (they need a second pass over the
-        mapped label maps).  It carries NO calibration counters either: a merged class's confidence is the SUM of its
+        mapped label maps).  For the same reason it carries NO trimap counters: the rings are measured from the contours of
+        the finer ground truth.  It carries NO calibration counters either: a merged class's confidence is the SUM of its
         members' probabilities, not their maximum, so the (class, confidence bin) counts cannot be re-keyed."""
         C = self._matrix("merged")
         mp = torch.as_tensor(mapping).reshape(-1)
@@ -1680,7 +1809,8 @@ class SegmentationScore:
     def group_summary(self, groups):
         """groups: {name: class ids} (seen / unseen, things / stuff) -> {name: {"mIoU", "mAcc"}, ..., "hIoU"}: per group the nanmean
         of `summary()`'s per-class IoU / Acc over the group's classes, unrounded, then rounded to 4 digits as `summary()` does
-        (and "mBIoU", the same of the per-class Boundary IoU, where the score carries boundary counters);
+        (and "mBIoU", the same of the per-class Boundary IoU, where the score carries boundary counters, and "trimap_mIoU":
+        [K], the same of the per-class IoU within each radius, where it carries trimap counters);
         hIoU is the harmonic mean of the groups' mIoU, the seen / unseen figure of zero-shot segmentation tables (0 where a
         group's mIoU is 0, NaN where a group has no class with pixels).  Needs `areas` only; one host round trip; ground
         truth out of range is `summary()`'s IndexError."""
@@ -1693,6 +1823,8 @@ class SegmentationScore:
                                  "'hIoU'), got %s" % (name, self.n, c.tolist()))
             ids.append(c)
         counters = [self.areas.reshape(-1), self.tally] + ([] if self.boundary is None else [self.boundary.reshape(-1)])
+        if self.trimap is not None:
+            counters.append(self.trimap.cumsum(0).reshape(-1))
         flat = torch.cat(counters).cpu()
         self._refuse_out_of_range(int(flat[3 * self.n + 1]))
         a = flat[:3 * self.n].reshape(3, self.n).double()
@@ -1701,10 +1833,15 @@ class SegmentationScore:
         mious = [torch.nanmean(iou[c]) for c in ids]
         out = {name: {"mIoU": r4(mi), "mAcc": r4(torch.nanmean(acc[c]))} for name, c, mi in zip(names, ids, mious)}
         if self.boundary is not None:
-            b = flat[3 * self.n + 2:].reshape(3, self.n).double()
+            b = flat[3 * self.n + 2:6 * self.n + 2].reshape(3, self.n).double()
             biou = b[0] / (b[1] + b[2] - b[0])
             for name, c in zip(names, ids):
                 out[name]["mBIoU"] = r4(torch.nanmean(biou[c]))
+        if self.trimap is not None:
+            t = flat[len(flat) - self.trimap.numel():].reshape(-1, 3, self.n).double()
+            tiou = t[:, 0] / (t[:, 1] + t[:, 2] - t[:, 0])
+            for name, c in zip(names, ids):
+                out[name]["trimap_mIoU"] = [r4(torch.nanmean(row[c])) for row in tiou]
         mi = torch.stack(mious)
         out["hIoU"] = r4(0.0 if bool((mi == 0).any()) else len(names) / (1.0 / mi).sum())
         return out
@@ -1727,7 +1864,8 @@ class SegmentationScore:
         is an IndexError: the reference's F.cross_entropy fails on such a label, and a score that left pixels out is not
         reported as if it had not.  A score with boundary counters b also gives "mBIoU" and "BIoU": [n], Boundary IoU =
         b[0] / (b[1] + b[2] - b[0]) per class, with the same nanmean and rounding, in the same round trip.  A score with
-        calibration counters also gives "ECE" = sum_m (N_m / N) |acc_m - conf_m| over `reliability(16)`'s bins of all classes
+        trimap counters also gives `trimap_summary()`'s "trimap_radii", "trimap_mIoU", "trimap_aAcc" and "trimap_pixels", [K]
+        each, in the same round trip.  A score with calibration counters also gives "ECE" = sum_m (N_m / N) |acc_m - conf_m| over `reliability(16)`'s bins of all classes
         together, "MCE", the largest |acc_m - conf_m| of a non-empty bin, and "cECE": [n], the ECE of every predicted class
         alone (NaN for a class never predicted; ECE and MCE are NaN without pixels): float64 from the integers, NOT rounded, in
         the same round trip.  A fine bin's confidence is its midpoint, so each is within 1 / 512 of the figure the raw
@@ -1740,6 +1878,8 @@ class SegmentationScore:
             b = self.boundary.double()
             biou = b[0] / (b[1] + b[2] - b[0])
             parts += [torch.nanmean(biou)[None], biou]
+        if self.trimap is not None:
+            parts.append(self._trimap_figures(False))
         if self.calibration is not None:
             ece, mce = _calibration_errors(*_reliability_bins(self.calibration, 16, False))
             parts += [ece, mce, _calibration_errors(*_reliability_bins(self.calibration, 16, True))[0]]
@@ -1751,10 +1891,42 @@ class SegmentationScore:
         if self.boundary is not None:
             out["mBIoU"] = r4(flat[5 + 2 * n])
             out["BIoU"] = [r4(v) for v in flat[6 + 2 * n:6 + 3 * n]]
+        if self.trimap is not None:
+            at = 5 + 2 * n + (0 if self.boundary is None else 1 + n)
+            out.update(self._trimap_read(flat[at:at + 3 * len(self.trimap_radii)], False))
         if self.calibration is not None:
             at = len(flat) - n - 2
             out["ECE"], out["MCE"], out["cECE"] = flat[at], flat[at + 1], flat[at + 2:]
         return out
+
+    def _trimap_figures(self, per_class):
+        """the trimap's figures on the cumulative sums over the rings, `summary()`'s formulas: float64 [3 K] = aAcc, mIoU and
+        the scored pixels within each radius, and with `per_class` the K n per-class IoUs behind them"""
+        if self.trimap is None:
+            raise ValueError("SegmentationScore.trimap_summary needs trimap counters: SegmentationScore(n, trimap=True), "
+                             "evaluate_raw(..., trimap=True)")
+        c = self.trimap.cumsum(0).double()
+        ai, ap, al = c[:, 0], c[:, 1], c[:, 2]
+        iou = ai / (ap + al - ai)
+        parts = [ai.sum(1) / ap.sum(1), torch.stack([torch.nanmean(row) for row in iou]), al.sum(1)]
+        return torch.cat(parts + ([iou.reshape(-1)] if per_class else []))
+
+    def _trimap_read(self, flat, per_class):
+        """`_trimap_figures` as the host read it -> the dictionary's entries"""
+        K, n = len(self.trimap_radii), self.n
+        r4 = lambda v: round(float(v), 4)
+        out = {"trimap_radii": list(self.trimap_radii), "trimap_mIoU": [r4(v) for v in flat[K:2 * K]],
+               "trimap_aAcc": [r4(v) for v in flat[:K]], "trimap_pixels": [int(v) for v in flat[2 * K:3 * K]]}
+        if per_class:
+            out["trimap_IoU"] = [[r4(v) for v in flat[3 * K + k * n:3 * K + (k + 1) * n]] for k in range(K)]
+        return out
+
+    def trimap_summary(self, per_class=False):
+        """-> {"trimap_radii": [K], "trimap_mIoU": [K], "trimap_aAcc": [K], "trimap_pixels": [K]}, and with `per_class`
+        "trimap_IoU": [K][n]: `summary()`'s mIoU / aAcc / IoU (its formulas and rounding) restricted to the scored pixels within
+        r_k of a ground-truth contour -- the cumulative sums of the rings' counters -- and the number of those pixels.  Needs
+        trimap counters (ValueError without them).  One host round trip."""
+        return self._trimap_read(self._trimap_figures(per_class).tolist(), per_class)
 
 
 def source_tokens(category_token_ids, prompt_ids=PROMPT_IDS, num_seg_tokens=None):
@@ -2401,7 +2573,8 @@ class Segmenter:
             return [self._run_length_map(l, max_runs) for l in maps]
 
     # -- scoring against ground truth -----------------------------------------------------
-    def _score_into(self, what, into, dev, confusion=False, boundary_iou=False, shapes=(), calibration=False, sl=None):
+    def _score_into(self, what, into, dev, confusion=False, boundary_iou=False, shapes=(), calibration=False, sl=None,
+                    trimap=False):
         """the score a scoring call adds to, its arguments checked before anything is launched.  shapes: the (h, w) of the
         ground-truth maps, in order: with boundary counters, each one's band must fit the kernel"""
         if not isinstance(confusion, bool):
@@ -2417,9 +2590,14 @@ class Segmenter:
         if boundary_iou is not False:
             ratio = 0.02 if boundary_iou is True else _boundary_ratio("Segmenter.%s: boundary_iou is True, False or a ratio" % what,
                                                                       boundary_iou)
+        radii = None
+        if trimap is not False:
+            radii = default_trimap_radii() if trimap is True else _trimap_radii(
+                "Segmenter.%s" % what, trimap, "trimap is True, False or a tuple of radii, which")
         if into is None:
             score = SegmentationScore(self.n, dev, confusion=confusion, boundary=ratio is not None,
-                                      boundary_ratio=0.02 if ratio is None else ratio, calibration=calibration)
+                                      boundary_ratio=0.02 if ratio is None else ratio, calibration=calibration,
+                                      trimap=radii is not None, trimap_radii=radii)
         else:
             if not isinstance(into, SegmentationScore) or into.n != self.n or into.areas.device != dev:
                 raise ValueError("Segmenter.%s: into must be a SegmentationScore of %d classes on %s" % (what, self.n, dev))
@@ -2435,6 +2613,12 @@ class Segmenter:
             if calibration and into.calibration is None:
                 raise ValueError("Segmenter.%s: calibration=True, but `into` carries no calibration counters (SegmentationScore(n, "
                                  "device, calibration=True))" % what)
+            if radii is not None and into.trimap is None:
+                raise ValueError("Segmenter.%s: trimap=%r, but `into` carries no trimap counters (SegmentationScore(n, device, "
+                                 "trimap=True))" % (what, trimap))
+            if radii is not None and into.trimap_radii != radii:
+                raise ValueError("Segmenter.%s: trimap asks for the radii %r, `into` counts the radii %r"
+                                 % (what, radii, into.trimap_radii))
             score = into
         if score.calibration is not None:
             self._need_probability("Segmenter.%s" % what, sl)
@@ -2455,16 +2639,19 @@ class Segmenter:
         of the same labels behind it on the same stream; where it carries boundary counters, likewise, and
         `hip.seg_boundary_areas` counts the band areas of the same labels with d = `boundary_distance` of gt's size.  Where
         it carries calibration counters, the launch (with the CRF, `_label`) is asked for its conf as well and
-        `hip.seg_calibration` counts labels, conf and gt behind the other two."""
+        `hip.seg_calibration` counts labels, conf and gt behind the other two.  Where it carries trimap counters, the launch
+        is asked for its label map as well and `hip.seg_trimap_areas` (the ground truth's distance plane, then the rings'
+        counters) follows behind all of them."""
         kw = dict(raw_labels=raw_labels, areas=score.areas, tally=score.tally)
         pairs, bands, cal = score.confusion is not None, score.boundary is not None, score.calibration is not None
+        rings = score.trimap is not None
         if self.crf_iters > 0 or self.pamr_iters > 0 or self.sieve is not None:
             res = self._label(merge, int(gt.shape[1]), int(gt.shape[2]), rgb, cal, False)
             labels, conf = res.labels.contiguous(), res.conf
             hip.seg_areas(labels, gt, self.n, **kw)
         else:
-            labels, conf = merge.score(gt, labels=return_labels or pairs or bands or cal, conf=cal, label_dtype=self.label_dtype,
-                                       **kw)[2:4]
+            labels, conf = merge.score(gt, labels=return_labels or pairs or bands or cal or rings, conf=cal,
+                                       label_dtype=self.label_dtype, **kw)[2:4]
         if pairs:
             hip.seg_confusion(labels, gt, self.n, raw_labels, confusion=score.confusion)
         if bands:
@@ -2473,11 +2660,13 @@ class Segmenter:
         if cal:
             hip.seg_calibration(labels, conf.contiguous(), gt, self.n, raw_labels, calibration=score.calibration,
                                 tally=score.calibration_tally)
+        if rings:
+            hip.seg_trimap_areas(labels, gt, self.n, score.trimap_radii, raw_labels, trimap=score.trimap)
         return labels if return_labels else None
 
     def evaluate_raw(self, images, label_maps, raw_labels=True, scales=(1.0,), flip=False, max_batch=8, mean=None, std=None,
                      reverse_channels=False, into=None, return_labels=False, slide=None, confusion=False, boundary_iou=False,
-                     calibration=False):
+                     calibration=False, trimap=False):
         """`segment_raw` scored against ground truth on the device -> a `SegmentationScore` (or (score, [labels [H_i, W_i], ...])
         with `return_labels`, the labels being `segment_raw`'s).
 
@@ -2518,13 +2707,25 @@ class Segmenter:
         is without it, no host synchronisation is added, and a call without it makes the launches it always made.  The
         confidence must be a probability: raw logits (upsample="logits" outside `slide_views` sliding) are a ValueError naming
         the setting, as in `pseudo_label_raw`; so are anything but a bool and calibration=True with an `into` that lacks the
-        counters, all before anything is launched."""
+        counters, all before anything is launched.
+        trimap: True (`default_trimap_radii()` = 1, 2, 4, 8, 16, 32 pixels), a tuple of 1 .. 8 strictly ascending radii in
+        1 .. 128, or an `into` that carries trimap counters: the score also counts WHERE the errors sit relative to the
+        ground truth's contours (`SegmentationScore.trimap`, int64 [K, 3, n]: the three rows of `areas` per ring of the exact
+        Euclidean distance to the nearest ground-truth pixel of another value; `trimap_areas_reference` is the
+        specification), and `summary()` gains "trimap_radii", "trimap_mIoU", "trimap_aAcc" and "trimap_pixels";
+        `score.trimap_summary(per_class=True)` adds the per-class IoU within every radius.  The scoring launch then writes
+        its label map and `hip.seg_trimap_areas` counts the same labels per image on the same stream (two launches of
+        `hip.seg_distance` on the ground truth, one counting launch), behind the matrix's, the bands' and the calibration's
+        launches.  Everything else is bit for bit what it is without it, no host synchronisation is added, and a call
+        without it makes the launches it always made.  Radii other than `into`'s, `into` without the counters and anything
+        but True, False or such a tuple are ValueErrors before anything is launched."""
         sl = self._check_slide("evaluate_raw", slide, scales, flip)
         checked = self._check_raw("evaluate_raw", images, scales, flip, sl)
         plan = self._plan_slide(checked, sl, max_batch)
         gts = _check_label_maps("Segmenter.evaluate_raw", [] if checked is None else checked[1], label_maps)
         dev = next(self.model.parameters()).device
-        score = self._score_into("evaluate_raw", into, dev, confusion, boundary_iou, [tuple(g.shape) for g in gts], calibration, sl)
+        score = self._score_into("evaluate_raw", into, dev, confusion, boundary_iou, [tuple(g.shape) for g in gts], calibration, sl,
+                                 trimap)
         if checked is None:
             return (score, []) if return_labels else score
         gts = [g.to(dev, non_blocking=True).contiguous() for g in gts]
@@ -2538,12 +2739,13 @@ class Segmenter:
         return (score, out) if return_labels else score
 
     def evaluate(self, images, label_maps, raw_labels=True, into=None, return_labels=False, confusion=False, boundary_iou=False,
-                 calibration=False):
+                 calibration=False, trimap=False):
         """`__call__` scored against ground truth: images as `__call__` takes them (normalised float [B, 3, H, W] or uint8 RGB
         [B, H, W, 3] / [H, W, 3]), label_maps uint8 / int16 [B, h, w] (or [h, w] for one image): the label map is taken at the
         ground truth's own size, as `out_hw` would.  -> a `SegmentationScore`, or (score, labels [B, h, w]) with `return_labels`;
-        raw_labels, into, confusion, boundary_iou, calibration: as in `evaluate_raw`; the band areas of the whole batch are one
-        launch of `hip.seg_boundary_areas`, d from the label maps' size, and its calibration counts one of `hip.seg_calibration`."""
+        raw_labels, into, confusion, boundary_iou, calibration, trimap: as in `evaluate_raw`; the band areas of the whole batch are
+        one launch of `hip.seg_boundary_areas`, d from the label maps' size, its calibration counts one of `hip.seg_calibration`,
+        and its trimap counters one call of `hip.seg_trimap_areas` (distances never cross from one image into the next)."""
         gt = _check_batch_gt("Segmenter.evaluate", images, label_maps)
         patch_images, rgb = self.prepare_images(images)
         B, _, H, W = patch_images.shape
@@ -2551,7 +2753,8 @@ class Segmenter:
         if crf and tuple(gt.shape[1:]) != (H, W):
             raise ValueError("Segmenter.evaluate: with the CRF (crf_iters) or PAMR (pamr_iters) on, the label maps must have the "
                              "images' size %s, got %s" % ((H, W), tuple(gt.shape[1:])))
-        score = self._score_into("evaluate", into, patch_images.device, confusion, boundary_iou, [tuple(gt.shape[1:])], calibration)
+        score = self._score_into("evaluate", into, patch_images.device, confusion, boundary_iou, [tuple(gt.shape[1:])], calibration,
+                                 trimap=trimap)
         if crf and rgb is None:
             rgb = ((patch_images.float() * 0.5 + 0.5) * 255.0).permute(0, 2, 3, 1).contiguous()
         if self.pamr_iters > 0:

@@ -213,7 +213,9 @@ class SegmentationTask(TaskBase):
         `confusion=True` asks for the class confusion matrix (`score.confusion`) beside the three histograms,
         `boundary_iou=True` (or a ratio of the diagonal) for Boundary IoU's band areas (`score.boundary`; "mBIoU" in the summary),
         `calibration=True` for how often a confidence is right (`score.calibration`; "ECE" in the summary,
-        `score.precision_thresholds(target)` for `self_train_sample`'s thresholds)."""
+        `score.precision_thresholds(target)` for `self_train_sample`'s thresholds),
+        `trimap=True` (or a tuple of radii) for mIoU / accuracy within r pixels of a ground-truth contour (`score.trimap`;
+        "trimap_mIoU" in the summary)."""
         ctor = ("category_token_ids", "prompt_ids", "upsample", "smooth_iters", "smooth_topk", "temperature", "crf_iters",
                 "full_context_alignment", "label_dtype", "slide_views", "pamr_iters", "pamr_dilations", "sieve",
                 "sieve_connectivity", "sieve_passes")

@@ -768,6 +768,36 @@ int ifseg_seg_boundary_areas(const void* labels, int label_bytes, const void* gt
                              int raw_labels, void* bareas, void* band, void* stream);
 /* which = 0: the largest d, 1: the largest n; any other which: IFSEG_ERR_BAD_ARG. */
 int ifseg_seg_boundary_limit(int which);
+/* ifseg_seg_distance writes the exact squared Euclidean distance of every pixel of labels [B][h][w] (uint8, bytes 1, or int16,
+ * 2; any element alignment) to the nearest pixel of ANOTHER value of the same image (csrc/distance.hip;
+ * ifseg_amd/predict.py distance_reference is the specification): out uint16 [B][h][w] (2-byte aligned) =
+ * D2(p) = min over q with L(q) != L(p) of (px - qx)^2 + (py - qy)^2 where D2 <= R^2, R = max_distance in 1..128, and 65535
+ * where D2 > R^2 or the image holds no other value.  Values are compared as they are.  border != 0: every position outside
+ * the image counts as another value as well.  Distances never cross from one image into the next.
+ * work: B h w bytes, the clamped vertical distances (1..R, 255 for none), written by the first of the two launches and read
+ * by the second.  Integers, no atomics, one writer per element: two calls give equal bits.  Dynamic LDS (16 + 2 R) 128 bytes
+ * for the first launch (34 816 at R = 128) and 48 (64 + 2 R) for the second (15 360).
+ * NULL labels / work / out, label_bytes outside {1, 2}, int16 labels or out at an odd address, max_distance outside 1..128,
+ * any two of labels / work / out sharing a byte: IFSEG_ERR_BAD_ARG; B, h or w < 1 or B h w >= 2^31: IFSEG_ERR_BAD_SHAPE;
+ * nothing is launched on a refusal.  Nothing is allocated, nothing synchronises. */
+int ifseg_seg_distance(const void* labels, int label_bytes, int B, int h, int w, int max_distance, int border, void* work,
+                       void* out, void* stream);
+/* ifseg_seg_trimap_areas counts ifseg_seg_areas' three rows per distance ring (trimap_areas_reference is the specification):
+ * labels and gt [B][h][w] as in ifseg_seg_areas (the same ground-truth rule and scored pixels), dist uint16 [B][h][w] the
+ * ground truth's plane from ifseg_seg_distance with max_distance >= radii[K - 1], radii K ints on the HOST, strictly
+ * ascending in 1..128, 1 <= K <= 8.  Ring k holds the pixels with radii[k - 1]^2 < dist <= radii[k]^2 (radii[-1] = 0); a
+ * pixel beyond the last radius (65535 among them) is in none.  trimap uint64 [K][3][n] is ADDED to:
+ * [k][0][c] += #(pred = gt = c), [k][1][c] += #(pred = c), [k][2][c] += #(gt = c) over the scored pixels of ring k.  One
+ * launch; a workgroup counts into K 3 n uint32 of LDS (48 KiB at K = 8, n = 512) and only non-zero bins leave, one 64-bit
+ * integer atomic each.
+ * NULL labels / gt / dist / radii / trimap, an element size outside {1, 2}, an int16 map or dist at an odd address, trimap not
+ * 8-byte aligned, n outside 1..512, K outside 1..8, radii out of range or not ascending, trimap sharing a byte with a map:
+ * IFSEG_ERR_BAD_ARG; B, h or w < 1 or B h w >= 2^31: IFSEG_ERR_BAD_SHAPE; nothing is launched on a refusal. */
+int ifseg_seg_trimap_areas(const void* labels, int label_bytes, const void* gt, int gt_bytes, const void* dist, int B, int h,
+                           int w, int n, const int* radii, int K, int raw_labels, void* trimap, void* stream);
+/* which = 0: the largest max_distance, 1: the "far" value, 2: the largest K, 3: the largest n; any other which:
+ * IFSEG_ERR_BAD_ARG. */
+int ifseg_seg_distance_limit(int which);
 int ifseg_seg_score(const float* scores, int B, int hp, int wp, int n, int h, int w, void* labels, int label_bytes, float* conf,
                     float* probs, const void* gt, int gt_bytes, int raw_labels, unsigned long long* areas,
                     unsigned long long* tally, void* stream);
