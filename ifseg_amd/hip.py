@@ -1344,9 +1344,25 @@ def rows_to_f32(logits_pad, nseg, rows_per_batch, softmax=False, temperature=1.0
     return out
 
 
-def neighbour_smoothing(logits_pad, nseg, feat, iters, topk, temperature=1.0):
+def rows_to_f32_biased(logits_pad, nseg, rows_per_batch, bias, softmax=False, temperature=1.0):
+    """`rows_to_f32` with the per-class vector `bias` (fp32 [nseg], contiguous, on the logits' device) SUBTRACTED from the
+    widened logits in front of the temperature: a_c = (z_c - bias[c]) * (1 / temperature), softmaxed or (softmax=False:
+    no temperature) z_c - bias[c] itself, one fp32 subtraction (csrc/bsweep.hip).  bias = 0 gives `rows_to_f32`'s bits."""
+    assert torch.is_tensor(bias) and bias.dtype == torch.float32 and tuple(bias.shape) == (nseg,) and bias.is_contiguous() \
+        and bias.device == logits_pad.device, (getattr(bias, "dtype", type(bias)), tuple(getattr(bias, "shape", ())), nseg)
+    B = logits_pad.shape[0]
+    out = torch.empty(B, rows_per_batch, nseg, dtype=torch.float32, device=logits_pad.device)
+    _check(lib().ifseg_softmax_rows_bias(_ptr(logits_pad), c_ll(logits_pad.stride(0)), c_int(rows_per_batch),
+                                         c_int(logits_pad.stride(1)), _ptr(bias), _ptr(out), c_int(B * rows_per_batch),
+                                         c_int(nseg), c_float(1.0 / temperature), c_int(1 if softmax else 0), _stream()),
+           "softmax_rows_bias")
+    return out
+
+
+def neighbour_smoothing(logits_pad, nseg, feat, iters, topk, temperature=1.0, bias=None):
     """seg_criterion.py:197-213 on the device: logits_pad bf16 [B, P+1, ld], feat bf16 [B, P, D] (trunk features)
-    -> smoothed class probabilities fp32 [B, P, nseg]"""
+    -> smoothed class probabilities fp32 [B, P, nseg].  bias (fp32 [nseg]): the smoothing starts from
+    `rows_to_f32_biased`'s probabilities; None: from `rows_to_f32`'s, as ever"""
     B, P, D = feat.shape
     dev = feat.device
     fn = torch.empty(B * P, D, dtype=torch.bfloat16, device=dev)
@@ -1355,7 +1371,10 @@ def neighbour_smoothing(logits_pad, nseg, feat, iters, topk, temperature=1.0):
     gemm(GEMM_NT, fn, fn, sim, P, P, D, D, D, P, flags=GEMM_OUT_F32, batch=B, sA=P * D, sB=P * D, sC=P * P)
     idx = torch.empty(B * P, topk, dtype=torch.int32, device=dev)
     _check(lib().ifseg_topk_rows_f32(_ptr(sim), _ptr(idx), c_int(B * P), c_int(P), c_int(topk), _stream()), "topk_rows")
-    prob = rows_to_f32(logits_pad, nseg, P, softmax=True, temperature=temperature)
+    if bias is None:
+        prob = rows_to_f32(logits_pad, nseg, P, softmax=True, temperature=temperature)
+    else:
+        prob = rows_to_f32_biased(logits_pad, nseg, P, bias, softmax=True, temperature=temperature)
     tmp = torch.empty_like(prob)
     for _ in range(iters):
         _check(lib().ifseg_gather_mean(_ptr(prob), _ptr(idx), _ptr(tmp), c_int(B), c_int(P), c_int(nseg), c_int(topk),
@@ -1984,6 +2003,42 @@ def seg_temperature_sweep(grids, hp, wp, gt, raw_labels=True, hist=None, sums=No
                                                  _ptr(gt), c_int(gt.element_size()), c_int(1 if raw_labels else 0), _ptr(hist),
                                                  _ptr(tally), _ptr(sums), _ptr(partials), _stream()), "seg_temperature_sweep")
     return hist, sums, tally
+
+
+# the limits of seg_score_grids_kernel (csrc/bsweep.hip)
+SEG_SCORE_GRIDS_MAX = 16                    # == BS_MAX_K: the grids of one launch at most
+SEG_SCORE_GRIDS_STAGING_BYTES = 59376       # == bs_stage_limit(512): what the [3][512] table (+ tallies) leaves of 64 KiB
+
+
+def seg_score_grids_limits():
+    """-> (the largest K, the largest n, a tile's rows, a tile's columns, the staging bytes at the largest K and n) as the
+    loaded library states them (`ifseg_seg_score_grids_limit`): SEG_SCORE_GRIDS_MAX, SEG_PREDICT_MAX_CLASSES, 16, 64 and
+    SEG_SCORE_GRIDS_STAGING_BYTES, which the tests hold against it"""
+    return _limits("ifseg_seg_score_grids_limit", 5)
+
+
+def seg_score_grids(grids, hp, wp, gt, raw_labels=True, areas=None, tally=None, staging_bytes=None):
+    """grids fp32 [K, B, hp*wp, n], contiguous: K score grids of the same images, ANY fp32 values (probabilities or logits:
+    what `rows_to_f32_biased` / `neighbour_smoothing(bias=)` return for K biases, stacked), 1 <= K <= SEG_SCORE_GRIDS_MAX; gt
+    uint8 / int16 [B, h, w] -> (areas int64 [K, 3, n], tally int64 [2]): every grid resized to gt's size by `seg_predict`'s
+    rule and its label map counted against gt; row k is bit for bit `seg_score(grids[k], hp, wp, gt, raw_labels)`'s areas, and
+    tally (#scored pixels, #pixels with a ground truth out of range) is added ONCE, not K times (csrc/bsweep.hip;
+    `predict.bias_sweep_reference` is the specification).  One launch for all K, integers only: two calls give equal bits,
+    nothing synchronises, and no [n, h, w] tensor exists.  `areas` / `tally` given: ACCUMULATED into and returned, else fresh
+    zeroed ones.  staging_bytes: as in `seg_predict`."""
+    assert grids.dtype == torch.float32 and grids.dim() == 4 and grids.is_contiguous(), (grids.dtype, tuple(grids.shape), grids.stride())
+    K, B, P, n = grids.shape
+    assert 1 <= K <= SEG_SCORE_GRIDS_MAX and 1 <= n <= SEG_PREDICT_MAX_CLASSES, (K, n)
+    assert P == hp * wp and B >= 1 and hp >= 1 and wp >= 1, (tuple(grids.shape), hp, wp)
+    dev = grids.device
+    h, w = _score_gt(gt, B, dev)
+    assert B * h * w < 2 ** 31, (B, h, w)
+    areas, tally = _counter(areas, (K, 3, n), dev), _counter(tally, (2,), dev)
+    with _staged("ifseg_seg_score_grids_staging", staging_bytes):
+        _check(lib().ifseg_seg_score_grids(_ptr(grids), c_int(K), c_int(B), c_int(hp), c_int(wp), c_int(n), c_int(h), c_int(w),
+                                           _ptr(gt), c_int(gt.element_size()), c_int(1 if raw_labels else 0), _ptr(areas),
+                                           _ptr(tally), _stream()), "seg_score_grids")
+    return areas, tally
 
 
 def seg_pseudo(labels, conf, thresholds, n, boundary=0, raw_labels=True, kept=None, out=None, weight=False):

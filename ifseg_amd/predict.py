@@ -893,6 +893,207 @@ class TemperatureSweep:
         return best
 
 
+MAX_BIAS_STRENGTHS = hip.SEG_SCORE_GRIDS_MAX
+
+
+def default_bias_strengths():
+    """the 16 strengths a bias sweep tries by default: j / 4, j = 0 .. 15 -- 0 (the Segmenter as it is) to 3.75 logit units per
+    unit of the direction"""
+    return tuple(j / 4 for j in range(16))
+
+
+def _check_strengths(what, strengths):
+    """the strength list of a bias sweep, checked -> a tuple of 1 .. 16 finite floats"""
+    try:
+        gs = tuple(strengths)
+    except TypeError:
+        raise ValueError("%s: strengths must be a sequence of numbers, got %r" % (what, strengths))
+    if not 1 <= len(gs) <= MAX_BIAS_STRENGTHS:
+        raise ValueError("%s: strengths must hold 1 .. %d values (one launch scores them all), got %d" % (what, MAX_BIAS_STRENGTHS, len(gs)))
+    for g in gs:
+        if isinstance(g, bool) or not isinstance(g, (int, float)) or not math.isfinite(g):
+            raise ValueError("%s: every one of strengths must be a finite number, got %r" % (what, g))
+    return tuple(float(g) for g in gs)
+
+
+def _check_bias(what, name, v, n, device=None):
+    """a per-class vector in logit units (`class_bias`, a sweep's direction or origin), checked -> fp32 [n] on `device`: a
+    tensor or a sequence of n finite numbers; anything else is a ValueError naming it"""
+    try:
+        if isinstance(v, (str, bytes)) or (torch.is_tensor(v) and (v.dtype == torch.bool or v.dtype.is_complex)):
+            raise TypeError
+        t = (v.detach() if torch.is_tensor(v) else torch.as_tensor(v)).to(device=device, dtype=torch.float32).contiguous()
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError("%s: %s must be a tensor or sequence of %d finite numbers, got %r" % (what, name, n, v))
+    if tuple(t.shape) != (n,) or not bool(torch.isfinite(t).all()):
+        raise ValueError("%s: %s must be a tensor or sequence of %d finite numbers, got %s"
+                         % (what, name, n, "shape %s" % (tuple(t.shape),) if tuple(t.shape) != (n,) else "a value that is not finite"))
+    return t.clone() if torch.is_tensor(v) and t.data_ptr() == v.data_ptr() else t
+
+
+def scaled_bias(direction, strength, origin=None):
+    """The one place a strength becomes a bias: direction.float() * fp32(strength), plus origin.float() where given -- one
+    rounded product and one rounded sum, fp32 [n] on the direction's device.  `Segmenter.bias_sweep_raw` uses it for row k
+    and `BiasSweep.bias` to hand out the winner, so the two agree bit for bit."""
+    b = torch.as_tensor(direction).float() * torch.tensor(strength, dtype=torch.float32)
+    return b if origin is None else b + torch.as_tensor(origin).float().to(b.device)
+
+
+def first_maximum(values):
+    """the label rule of the resizing kernels on values [B, n, h, w] -> int64 [B, h, w]: the smallest class of maximal value,
+    `v > best` from -inf on -- a NaN never wins (torch.argmax would rank it first), and a pixel whose values are all NaN is
+    class 0"""
+    return torch.where(values.isnan(), torch.full_like(values, float("-inf")), values).argmax(dim=1)
+
+
+def bias_sweep_reference(grids, hp, wp, gt, raw_labels=True, dtype=torch.float64):
+    """Specification of hip.seg_score_grids: grids [K, B, hp*wp, n] (or a sequence of K [B, hp*wp, n]), class fastest -- K score
+    grids of the same images holding ANY fp32 values (one forward's logits under K biases, softmaxed or not); gt uint8 / int16
+    [B, h, w] -> (areas int64 [K, 3, n], tally int64 [2]).  Per k the grid is resized to gt's (h, w) by
+    `upsample_argmax_reference` (bilinear, align_corners=False, evaluated in `dtype`), the label is `first_maximum` of the
+    resized values (torch.argmax's, except that a NaN never wins), and `areas_reference` scores the labels: row k is by
+    definition what `hip.seg_score(grids[k], hp, wp, gt, raw_labels)` counts.  tally does not depend on k.  The kernel
+    interpolates in fp32 (`hip.seg_predict`'s values, bit for bit); this is the fp64 statement it is held against.  Runs on
+    any device."""
+    gt = torch.as_tensor(gt)
+    if gt.dim() != 3:
+        raise ValueError("bias_sweep_reference: the ground truth must be [B, h, w], got %s" % (tuple(gt.shape),))
+    h, w = int(gt.shape[1]), int(gt.shape[2])
+    grids = list(grids)
+    if not grids:
+        raise ValueError("bias_sweep_reference: no strengths")
+    n = int(grids[0].shape[-1])
+    areas, tally = [], None
+    for g in grids:
+        a, tally = areas_reference(first_maximum(upsample_argmax_reference(g, hp, wp, h, w, dtype)[2]), gt, n, raw_labels)
+        areas.append(a)
+    return torch.stack(areas), tally
+
+
+class BiasSweep:
+    """`bias_sweep_reference`'s counters on the device, summed over everything swept into them: for the K strengths
+    `strengths` (a tuple of floats) of the bias direction `direction` from `origin` (fp32 [n] each, zeros for origin=None),
+    `areas` int64 [K, 3, n] -- row k is `SegmentationScore.areas` of a Segmenter whose `class_bias` is
+    `scaled_bias(direction, strengths[k], origin)` -- and `tally` int64 [2].  `hip.seg_score_grids` adds to these tensors in
+    place, so one sweep can span a validation set (`Segmenter.bias_sweep_raw(..., into=sweep)`)."""
+
+    def __init__(self, strengths, direction, origin=None, device=None):
+        self.strengths = _check_strengths("BiasSweep", strengths)
+        try:
+            n = len(direction)
+        except TypeError:
+            n = 0
+        if n < 1:
+            raise ValueError("BiasSweep: direction must be a tensor or sequence of n >= 1 finite numbers, got %r" % (direction,))
+        self.direction = _check_bias("BiasSweep", "direction", direction, n, device)
+        self.n = n
+        dev = self.direction.device
+        self.origin = torch.zeros(self.n, dtype=torch.float32, device=dev) if origin is None \
+            else _check_bias("BiasSweep", "origin", origin, self.n, dev)
+        self.areas = torch.zeros(len(self.strengths), 3, self.n, dtype=torch.int64, device=dev)
+        self.tally = torch.zeros(2, dtype=torch.int64, device=dev)
+
+    def _same(self, strengths, direction, origin):
+        """whether a sweep of these strengths, direction and origin (fp32 [n] on this sweep's device) counts what this one counts:
+        equal strengths, bit-equal vectors"""
+        bits = lambda t: t.view(torch.int32)
+        return tuple(strengths) == self.strengths and direction.shape == self.direction.shape \
+            and direction.device == self.direction.device and origin.device == self.direction.device \
+            and torch.equal(bits(direction), bits(self.direction)) and torch.equal(bits(origin), bits(self.origin))
+
+    def add_(self, other):
+        if not isinstance(other, BiasSweep):
+            raise ValueError("BiasSweep.add_: a BiasSweep is needed, got %s" % type(other))
+        if other.n != self.n:
+            raise ValueError("BiasSweep.add_: %d classes against %d" % (other.n, self.n))
+        if other.areas.device != self.areas.device:
+            raise ValueError("BiasSweep.add_: a sweep on %s against one on %s" % (other.areas.device, self.areas.device))
+        if tuple(other.strengths) != self.strengths:
+            raise ValueError("BiasSweep.add_: strengths %r against %r: sweeps of different lists do not add"
+                             % (other.strengths, self.strengths))
+        if not self._same(other.strengths, other.direction, other.origin):
+            raise ValueError("BiasSweep.add_: the two sweeps' direction or origin differ: rows of different biases do not add")
+        self.areas += other.areas
+        self.tally += other.tally
+        return self
+
+    def _row(self, what, k):
+        if not isinstance(k, int) or isinstance(k, bool) or not 0 <= k < len(self.strengths):
+            raise ValueError("BiasSweep.%s: k must be an int in 0 .. %d, got %r" % (what, len(self.strengths) - 1, k))
+        return k
+
+    def score(self, k):
+        """row k as a `SegmentationScore` ON the sweep's counters (shared memory, nothing copied): every summary that reads
+        `areas` works on it -- `summary`, `group_summary`, `overprediction`, `logging_output`.  The sweep counts no confusion
+        matrix, so `merged` and `confusions` answer with their ValueError, as on any score without one."""
+        return SegmentationScore(self.n, areas=self.areas[self._row("score", k)], tally=self.tally)
+
+    def bias(self, k_or_strength):
+        """the fp32 [n] bias of a row, `scaled_bias(direction, strength, origin)`: an int names the row, a float one of
+        `strengths`.  Then: `seg.class_bias = sweep.bias(sweep.best())`."""
+        if isinstance(k_or_strength, int) and not isinstance(k_or_strength, bool):
+            g = self.strengths[self._row("bias", k_or_strength)]
+        elif isinstance(k_or_strength, float) and k_or_strength in self.strengths:
+            g = k_or_strength
+        else:
+            raise ValueError("BiasSweep.bias: a row 0 .. %d (int) or one of the strengths %r (float) is needed, got %r"
+                             % (len(self.strengths) - 1, self.strengths, k_or_strength))
+        return scaled_bias(self.direction, g, self.origin)
+
+    def summary(self, groups=None):
+        """-> {"strengths": [K], "mIoU": [K], "mAcc": [K], "aAcc": [K], "IoU": [K][n], "pixels"} by `SegmentationScore.summary`'s
+        formulas and rounding, row by row; with groups = {name: class ids} also name: {"mIoU": [K], "mAcc": [K]} and "hIoU":
+        [K], `SegmentationScore.group_summary`'s.  The one place that synchronises with the host: one round trip.  Ground
+        truth out of range is an IndexError, as in `SegmentationScore.summary`."""
+        K, n = len(self.strengths), self.n
+        names, ids = [], []
+        for name in ([] if groups is None else list(groups)):
+            c = torch.as_tensor(list(groups[name]), dtype=torch.long).reshape(-1)
+            if name in ("hIoU", "strengths", "mIoU", "mAcc", "aAcc", "IoU", "pixels") or c.numel() == 0 or int(c.min()) < 0 \
+                    or int(c.max()) >= n:
+                raise ValueError("BiasSweep.summary: group %r must hold class ids in [0, %d) (and not carry the name of a figure), "
+                                 "got %s" % (name, n, c.tolist()))
+            names.append(name)
+            ids.append(c)
+        flat = torch.cat([self.areas.reshape(-1), self.tally]).cpu()
+        pixels, bad = int(flat[-2]), int(flat[-1])
+        if bad != 0:
+            raise IndexError("BiasSweep: tally[1] = %d ground-truth pixels hold a class outside [0, %d) that is not an "
+                             "ignore value (wrong raw_labels, or a label map of another dataset?)" % (bad, n))
+        a = flat[:-2].reshape(K, 3, n).double()
+        ai, ap, al = a[:, 0], a[:, 1], a[:, 2]
+        iou, acc = ai / (ap + al - ai), ai / al
+        r4 = lambda v: round(float(v), 4)
+        out = {"strengths": list(self.strengths), "mIoU": [r4(torch.nanmean(row)) for row in iou],
+               "mAcc": [r4(torch.nanmean(row)) for row in acc], "aAcc": [r4(v) for v in ai.sum(1) / ap.sum(1)],
+               "IoU": [[r4(v) for v in row] for row in iou.tolist()], "pixels": pixels}
+        if names:
+            mious = [[torch.nanmean(row[c]) for c in ids] for row in iou]
+            for j, (name, c) in enumerate(zip(names, ids)):
+                out[name] = {"mIoU": [r4(m[j]) for m in mious], "mAcc": [r4(torch.nanmean(row[c])) for row in acc]}
+            out["hIoU"] = []
+            for m in mious:
+                mi = torch.stack(m)
+                out["hIoU"].append(r4(0.0 if bool((mi == 0).any()) else len(names) / (1.0 / mi).sum()))
+        return out
+
+    def best(self, metric="mIoU", groups=None):
+        """the strength whose row has the highest `metric` of `summary(groups)` (the rounded figures), the first one on a tie;
+        rows whose figure is NaN do not compete.  metric: "mIoU", "mAcc", "aAcc", or with `groups` "hIoU" or a group's name
+        (its mIoU).  One host round trip, and `summary`'s IndexError; a ValueError without scored pixels.  Then:
+        `seg.class_bias = sweep.bias(sweep.best())`."""
+        plain = ("mIoU", "mAcc", "aAcc")
+        if metric not in plain and (groups is None or (metric != "hIoU" and metric not in groups)):
+            raise ValueError("BiasSweep.best: metric must be one of %r, or with groups 'hIoU' or a group's name, got %r"
+                             % (plain, metric))
+        s = self.summary(groups)
+        vals = s[metric] if metric in plain or metric == "hIoU" else s[metric]["mIoU"]
+        live = [k for k, v in enumerate(vals) if not math.isnan(v)]
+        if not s["pixels"] or not live:
+            raise ValueError("BiasSweep.best: no scored pixels have been swept")
+        return self.strengths[max(live, key=lambda k: vals[k])]              # max keeps the first of equal values
+
+
 def pseudo_thresholds(hist, keep=1.0, floor=0.0):
     """The per-class confidence thresholds of self-training from a confidence histogram int64 [n, 256] -> int32 [n], values in
     0 .. 256 (bins: a pixel of class c passes iff conf_bin(conf) >= t_c), on hist's device with no host round trip.  In integers:
@@ -1852,6 +2053,13 @@ class SegmentationScore:
         a = self.areas.double()
         return {"area_intersect": a[0], "area_pred_label": a[1], "area_label": a[2], "area_union": a[1] + a[2] - a[0]}
 
+    def overprediction(self):
+        """-> float64 [n] on the device, log(areas[1] + 1) - log(areas[2] + 1): how much more often a class is predicted than
+        labelled, 0 for a class neither predicted nor present.  The data-driven direction of `Segmenter.bias_sweep_raw`
+        (subtracting it makes the over-predicted classes rarer).  Does not synchronise with the host."""
+        a = self.areas.double()
+        return torch.log(a[1] + 1.0) - torch.log(a[2] + 1.0)
+
     def _refuse_out_of_range(self, bad):
         """bad: tally[1] as the host read it"""
         if bad != 0:
@@ -1969,10 +2177,11 @@ def _pamr_bytes(rgb):
 
 class Segmenter:
     sieve, sieve_connectivity, sieve_passes, sieve_moved = None, 4, 2, None      # off, unless the constructor says otherwise
+    _class_bias = None
 
     def __init__(self, model, task=None, category_token_ids=None, prompt_ids=PROMPT_IDS, upsample="probs", smooth_iters=0,
                  smooth_topk=3, temperature=1.0, crf_iters=0, full_context_alignment=False, label_dtype=None, slide_views=False,
-                 pamr_iters=0, pamr_dilations=PAMR_DILATIONS, sieve=None, sieve_connectivity=4, sieve_passes=2):
+                 pamr_iters=0, pamr_dilations=PAMR_DILATIONS, sieve=None, sieve_connectivity=4, sieve_passes=2, class_bias=None):
         """model: a SegOFAModel on the device.  The class names come from `category_token_ids` (one id sequence per class),
         else the task's `category_token_ids`, else the task's `category_list` through `task.encode_category`.
         upsample: "probs" resizes the per-patch softmax (temperature), the reference demo's order; "logits" resizes the raw
@@ -2000,7 +2209,16 @@ class Segmenter:
         return_weight where it is kept); probs, where asked for, are returned as they were, NOT re-ranked.  `sieve_moved`,
         int64 [2, n] on the device (None before the first sieved call), accumulates `hip.seg_sieve`'s moved over the calls:
         per class the pixels that left and that joined; nothing synchronises with the host.  Not built: the sieve inside
-        `calibrate_raw` / `calibrate` and calibration counters behind a sieve (both a ValueError)."""
+        `calibrate_raw` / `calibrate` and calibration counters behind a sieve (both a ValueError).
+        class_bias: None: no per-class term, the launches as ever.  A tensor or sequence of n finite numbers, in logit units,
+        kept as fp32 [n] on the model's device (`seg.class_bias`, assignable afterwards through the same check): it is
+        SUBTRACTED from the logits in front of the temperature, a_c = (z_c - b_c) / T with z the bf16 logit widened to fp32
+        and the difference one fp32 subtraction -- a positive entry makes a class rarer (prior-shift correction; logit
+        adjustment, Menon et al., ICLR 2021; the calibration factor of the zero-shot segmentation tables).  "probs" and the
+        smoothing take the softmax of a, so every value stays a probability and every consumer of one keeps its meaning;
+        "logits" resizes z_c - b_c (no temperature, as without it).  `patch_scores` / `patch_scores_at` then call
+        `hip.rows_to_f32_biased` / `hip.neighbour_smoothing(bias=)` (csrc/bsweep.hip), and because the bias is part of the
+        grid it holds in every setting and method with no other change.  `bias_sweep_raw` finds its strength."""
         if upsample not in ("probs", "logits"):
             raise ValueError("Segmenter: upsample must be 'probs' or 'logits', got %r" % (upsample,))
         self.model, self.task = model, task
@@ -2029,6 +2247,17 @@ class Segmenter:
         self.slide_views = bool(slide_views)
         self._src_dev = None
         self._palette_dev = None
+        self.class_bias = class_bias
+
+    @property
+    def class_bias(self):
+        """the per-class bias, fp32 [n] on the model's device, or None (see the constructor)"""
+        return self._class_bias
+
+    @class_bias.setter
+    def class_bias(self, value):
+        self._class_bias = None if value is None else _check_bias("Segmenter", "class_bias", value, self.n,
+                                                                  next(self.model.parameters()).device)
 
     # -- inputs --------------------------------------------------------------------------
     @staticmethod
@@ -2081,11 +2310,31 @@ class Segmenter:
         """model forward -> (scores fp32 [B, hp*wp, n] in the chosen mode, hp, wp)"""
         pad, hp, wp, feat = self._padded_logits(patch_images)
         with torch.no_grad():
-            if self.smooth_iters > 0:
+            if self._class_bias is not None:
+                scores = self._biased_grid(pad, hp, wp, feat, self._class_bias)
+            elif self.smooth_iters > 0:
                 scores = hip.neighbour_smoothing(pad, self.n, feat, self.smooth_iters, self.smooth_topk, self.temperature)
             else:
                 scores = hip.rows_to_f32(pad, self.n, hp * wp, softmax=self.upsample == "probs", temperature=self.temperature)
         return scores, hp, wp
+
+    def _biased_grid(self, pad, hp, wp, feat, bias, temperature=None, softmax=None):
+        """`patch_scores`' grid of one forward's padded logits under the per-class `bias` (fp32 [n] on the device), through the
+        biased bindings; temperature / softmax: None for the Segmenter's own"""
+        T = self.temperature if temperature is None else temperature
+        if self.smooth_iters > 0:
+            return hip.neighbour_smoothing(pad, self.n, feat, self.smooth_iters, self.smooth_topk, T, bias=bias)
+        return hip.rows_to_f32_biased(pad, self.n, hp * wp, bias, softmax=self.upsample == "probs" if softmax is None else softmax,
+                                      temperature=T)
+
+    def patch_scores_biased(self, patch_images, biases):
+        """ONE model forward -> (grids fp32 [K, B, hp*wp, n], hp, wp): that forward's padded logits under each of the K per-class
+        biases (fp32 [n] on the device each), in the Segmenter's own mode, temperature and smoothing -- grid k is bit for bit
+        what `patch_scores` of this Segmenter with `class_bias = biases[k]` gives.  The Segmenter's own `class_bias` is not
+        consulted."""
+        pad, hp, wp, feat = self._padded_logits(patch_images)
+        with torch.no_grad():
+            return torch.stack([self._biased_grid(pad, hp, wp, feat, b) for b in biases]), hp, wp
 
     def _padded_logits(self, patch_images):
         """model forward in eval mode -> (the padded logits bf16 [B, T, ld], hp, wp, the trunk features [B, hp*wp, D]): what
@@ -2107,10 +2356,13 @@ class Segmenter:
         """ONE model forward -> (grids fp32 [K, B, hp*wp, n], hp, wp): the class probabilities of that forward's padded logits at
         each of the K temperatures, `hip.rows_to_f32(softmax=True, temperature=T_k)` (with `smooth_iters > 0`:
         `hip.neighbour_smoothing(..., T_k)`) run K times -- grid k is bit for bit what `patch_scores` of a
-        `Segmenter(temperature=T_k, upsample="probs")` gives.  The Segmenter's own `temperature` is not consulted."""
+        `Segmenter(temperature=T_k, upsample="probs")` gives.  The Segmenter's own `temperature` is not consulted; its
+        `class_bias`, where set, is (the biased bindings, with the same bias at every temperature)."""
         pad, hp, wp, feat = self._padded_logits(patch_images)
         with torch.no_grad():
-            if self.smooth_iters > 0:
+            if self._class_bias is not None:
+                grids = [self._biased_grid(pad, hp, wp, feat, self._class_bias, T, True) for T in temperatures]
+            elif self.smooth_iters > 0:
                 grids = [hip.neighbour_smoothing(pad, self.n, feat, self.smooth_iters, self.smooth_topk, T) for T in temperatures]
             else:
                 grids = [hip.rows_to_f32(pad, self.n, hp * wp, softmax=True, temperature=T) for T in temperatures]
@@ -2842,4 +3094,90 @@ class Segmenter:
         with torch.no_grad():
             hip.seg_temperature_sweep(grids, hp, wp, gt.to(patch_images.device).contiguous(), raw_labels, hist=sweep.hist,
                                       sums=sweep.sums, tally=sweep.tally)
+        return sweep
+
+    # -- choosing the class bias ----------------------------------------------------------
+    def _bias_sweep_into(self, what, direction, strengths, into, dev, scales=(1.0,), flip=False, slide=None):
+        """the sweep a bias-sweeping call adds to, every argument and setting checked before anything is launched"""
+        if len(view_list(scales, flip)) != 1 or flip:
+            raise ValueError("Segmenter.%s: a bias sweep takes one plain view, got scales=%r, flip=%r (the launch scores K grids of "
+                             "one forward; the mean over several views is not built into it)" % (what, tuple(scales), flip))
+        if slide is not None and slide is not False:
+            raise ValueError("Segmenter.%s: a bias sweep does not slide, got slide=%r (the launch scores K grids of one forward; "
+                             "the window merge is not built into it)" % (what, slide))
+        if self.crf_iters > 0:
+            raise ValueError("Segmenter.%s: a bias sweep scores the network's grids, this Segmenter has crf_iters = %d (the "
+                             "sweep's launch resizes and scores in one pass: the CRF inside it is not built)" % (what, self.crf_iters))
+        if self.pamr_iters > 0:
+            raise ValueError("Segmenter.%s: a bias sweep scores the network's grids, this Segmenter has pamr_iters = %d (the "
+                             "sweep's launch resizes and scores in one pass: PAMR inside it is not built)" % (what, self.pamr_iters))
+        if self.sieve is not None:
+            raise ValueError("Segmenter.%s: a bias sweep scores the network's grids, this Segmenter has sieve = %d (the sweep "
+                             "never forms a label map to sieve)" % (what, self.sieve))
+        direction = _check_bias("Segmenter.%s" % what, "direction", direction, self.n, dev)
+        gs = _check_strengths("Segmenter.%s" % what, default_bias_strengths() if strengths is None else strengths)
+        origin = torch.zeros(self.n, dtype=torch.float32, device=dev) if self._class_bias is None else self._class_bias.to(dev)
+        if into is None:
+            return BiasSweep(gs, direction, origin, dev)
+        if not isinstance(into, BiasSweep) or into.n != self.n or into.areas.device != dev or not into._same(gs, direction, origin):
+            raise ValueError("Segmenter.%s: into must be a BiasSweep of the strengths %r, this direction, this Segmenter's class_bias "
+                             "as origin and %d classes on %s, got %s"
+                             % (what, gs, self.n, dev, (into.strengths, into.n, into.areas.device) if isinstance(into, BiasSweep)
+                                else type(into)))
+        return into
+
+    def bias_sweep_raw(self, images, label_maps, direction, strengths=None, raw_labels=True, max_batch=8, mean=None, std=None,
+                       reverse_channels=False, into=None, scales=(1.0,), flip=False, slide=None):
+        """The strength of a per-class bias from a labelled validation set -> a `BiasSweep`: how far along `direction` the logits
+        must be shifted for the label maps to score best.  `evaluate_raw`'s front for a single plain view (images, label_maps,
+        raw_labels, max_batch, mean, std, reverse_channels and the checks of images and label maps: as there), but the
+        forward runs ONCE per batch; `patch_scores_biased` then turns its padded logits into K grids, one
+        `hip.rows_to_f32_biased` (with the smoothing: `hip.neighbour_smoothing(bias=)`) per strength, in the Segmenter's own
+        mode and temperature, and ONE launch of `hip.seg_score_grids` per image (csrc/bsweep.hip) scores all K against the
+        image's ground truth: per strength the three rows of `SegmentationScore.areas`, so mIoU, mAcc, aAcc, the groups' mIoU
+        and hIoU exist per strength.  No [n, H, W] tensor exists and nothing synchronises with the host; `sweep.summary()` is
+        the one round trip.
+        direction: a tensor or sequence of n finite numbers -- `score.overprediction()` (the data-driven one), a 0 / 1 mask of
+        the seen classes (the zero-shot calibration factor), log(prior_source) - log(prior_target) (prior shift).
+        strengths: 1 .. 16 finite numbers, None: `default_bias_strengths()`.  The Segmenter's own `class_bias` is the ORIGIN:
+        row k is this Segmenter with `class_bias = scaled_bias(direction, strengths[k], origin)` (zeros for None), so
+        strength 0 reproduces it and a second sweep along another direction continues from the first; afterwards
+        `seg.class_bias = sweep.bias(sweep.best())`.  "probs", "logits" and the smoothing are all allowed: the counters need
+        no probabilities.  into: a sweep of the same strengths, direction, origin, class count and device to accumulate into.
+        `bias_sweep_reference` is the specification.
+        A ValueError naming the setting, before anything is launched: `scales` / `flip` other than one plain view, `slide`,
+        `crf_iters > 0`, `pamr_iters > 0`, `sieve`, a direction that is not n finite numbers, a bad strength list, an `into`
+        that does not match."""
+        what = "bias_sweep_raw"
+        dev = next(self.model.parameters()).device
+        sweep = self._bias_sweep_into(what, direction, strengths, into, dev, scales, flip, slide)
+        checked = self._check_raw(what, images, scales, flip)
+        gts = _check_label_maps("Segmenter.bias_sweep_raw", [] if checked is None else checked[1], label_maps)
+        if checked is None:
+            return sweep
+        gts = [g.to(dev, non_blocking=True).contiguous() for g in gts]
+        biases = [sweep.bias(k) for k in range(len(sweep.strengths))]
+
+        def grids_at(x):                # sample-major, as `_raw_views` cuts a batch into its images
+            grids, hp, wp = self.patch_scores_biased(x, biases)
+            return grids.transpose(0, 1), hp, wp
+
+        per_image = self._raw_views(*checked, max_batch, mean, std, reverse_channels, scores=grids_at, merge=lambda vs: vs[0])[2]
+        with torch.no_grad():
+            for (grids, hp, wp, _), g in zip(per_image, gts):        # in image order
+                grids = grids.transpose(0, 1).contiguous()
+                hip.seg_score_grids(grids, hp, wp, g[None], raw_labels, areas=sweep.areas, tally=sweep.tally)
+        return sweep
+
+    def bias_sweep(self, images, label_maps, direction, strengths=None, raw_labels=True, into=None):
+        """`bias_sweep_raw` for what `evaluate` takes: images normalised float [B, 3, H, W] or uint8 RGB [B, H, W, 3] / [H, W, 3],
+        label_maps uint8 / int16 [B, h, w] (or [h, w] for one image) -> a `BiasSweep`: one forward, K biased row launches and
+        one launch of `hip.seg_score_grids` for the whole batch, at the ground truth's own size."""
+        gt = _check_batch_gt("Segmenter.bias_sweep", images, label_maps)
+        patch_images, _ = self.prepare_images(images)
+        sweep = self._bias_sweep_into("bias_sweep", direction, strengths, into, patch_images.device)
+        grids, hp, wp = self.patch_scores_biased(patch_images, [sweep.bias(k) for k in range(len(sweep.strengths))])
+        with torch.no_grad():
+            hip.seg_score_grids(grids, hp, wp, gt.to(patch_images.device).contiguous(), raw_labels, areas=sweep.areas,
+                                tally=sweep.tally)
         return sweep

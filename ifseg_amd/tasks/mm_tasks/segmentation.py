@@ -218,7 +218,7 @@ class SegmentationTask(TaskBase):
         "trimap_mIoU" in the summary)."""
         ctor = ("category_token_ids", "prompt_ids", "upsample", "smooth_iters", "smooth_topk", "temperature", "crf_iters",
                 "full_context_alignment", "label_dtype", "slide_views", "pamr_iters", "pamr_dilations", "sieve",
-                "sieve_connectivity", "sieve_passes")
+                "sieve_connectivity", "sieve_passes", "class_bias")
         seg = self.build_segmenter(model, **{k: kw.pop(k) for k in ctor if k in kw})
         return seg.evaluate_raw(images, label_maps, slide=slide, **kw)
 
@@ -229,9 +229,22 @@ class SegmentationTask(TaskBase):
         go to it, the others to `Segmenter.calibrate_raw`."""
         ctor = ("category_token_ids", "prompt_ids", "upsample", "smooth_iters", "smooth_topk", "temperature", "crf_iters",
                 "full_context_alignment", "label_dtype", "slide_views", "pamr_iters", "pamr_dilations", "sieve",
-                "sieve_connectivity", "sieve_passes")
+                "sieve_connectivity", "sieve_passes", "class_bias")
         seg = self.build_segmenter(model, **{k: kw.pop(k) for k in ctor if k in kw})
         return seg.calibrate_raw(images, label_maps, **kw)
+
+    def bias_sweep_raw(self, model, images, label_maps, direction, **kw):
+        """raw uint8 images and their label maps -> a `BiasSweep`: one forward per batch scored under every strength of
+        `strengths` (None: `predict.default_bias_strengths()`) of the per-class bias `direction` on the device,
+        `sweep.best()` being the strength of highest mIoU and `sweep.bias(...)` its vector for `class_bias`:
+        `build_segmenter(model, ...).bias_sweep_raw(images, label_maps, direction, ...)`.  Keywords of the Segmenter's
+        constructor (read from its signature; `class_bias` is the sweep's origin) go to it, the others to
+        `Segmenter.bias_sweep_raw`."""
+        import inspect
+        from ...predict import Segmenter
+        keywords = [k for k in inspect.signature(Segmenter.__init__).parameters if k not in ("self", "model", "task")]
+        seg = self.build_segmenter(model, **{k: kw.pop(k) for k in keywords if k in kw})
+        return seg.bias_sweep_raw(images, label_maps, direction, **kw)
 
     def render_raw(self, model, images, **kw):
         """raw uint8 images -> a list of `RenderResult(picture, labels, conf)`, the label maps coloured over the photos on the
@@ -239,7 +252,7 @@ class SegmentationTask(TaskBase):
         others to `Segmenter.render_raw`."""
         ctor = ("category_token_ids", "prompt_ids", "upsample", "smooth_iters", "smooth_topk", "temperature", "crf_iters",
                 "full_context_alignment", "label_dtype", "slide_views", "pamr_iters", "pamr_dilations", "sieve",
-                "sieve_connectivity", "sieve_passes")
+                "sieve_connectivity", "sieve_passes", "class_bias")
         seg = self.build_segmenter(model, **{k: kw.pop(k) for k in ctor if k in kw})
         return seg.render_raw(images, **kw)
 
@@ -251,7 +264,7 @@ class SegmentationTask(TaskBase):
         results carry `region_dropped`."""
         ctor = ("category_token_ids", "prompt_ids", "upsample", "smooth_iters", "smooth_topk", "temperature", "crf_iters",
                 "full_context_alignment", "label_dtype", "slide_views", "pamr_iters", "pamr_dilations", "sieve",
-                "sieve_connectivity", "sieve_passes")
+                "sieve_connectivity", "sieve_passes", "class_bias")
         seg = self.build_segmenter(model, **{k: kw.pop(k) for k in ctor if k in kw})
         return seg.pseudo_label_raw(images, **kw)
 

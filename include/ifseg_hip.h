@@ -995,6 +995,39 @@ int ifseg_seg_temperature_sweep_staging(int max_bytes);
 /* which = 0: the largest K, 1: the largest n, 2 / 3: the rows / columns of a tile (partials holds one [K][2] block per tile),
  * 4: the staging buffer's bytes at the largest K; any other which: IFSEG_ERR_BAD_ARG. */
 int ifseg_seg_temperature_sweep_limit(int which);
+/* Per-class logit bias (prior-shift correction; logit adjustment, Menon et al., ICLR 2021; the calibration factor of the
+ * zero-shot segmentation tables; csrc/bsweep.hip).  The rule: bias fp32 [n] on the device, in logit units, is SUBTRACTED in
+ * front of the temperature -- a_c = (z_c - bias[c]) * inv_temperature, z the bf16 logit widened to fp32, the difference one
+ * fp32 subtraction.
+ * ifseg_softmax_rows_bias is ifseg_softmax_rows on a: prob = softmax(a) (do_softmax != 0), else prob = z_c - bias[c] (the
+ * temperature is not applied, as there).  With bias = 0 it gives ifseg_softmax_rows' bits in both modes.  NULL logits / bias /
+ * prob, logits at an odd address, bias or prob not 4-byte aligned, bias overlapping prob, n < 1 or rows_per_batch < 1:
+ * IFSEG_ERR_BAD_ARG; rows <= 0 does nothing; nothing is launched on a refusal. */
+int ifseg_softmax_rows_bias(const void* logits /* bf16 */, long long batch_stride, int rows_per_batch, int ld, const float* bias,
+                            float* prob, int rows, int n, float inv_temperature, int do_softmax, void* stream);
+/* ifseg_seg_score_grids scores K score grids of the same images against one ground truth in one launch (the sweep over K
+ * strengths of a bias direction; predict.py: bias_sweep_reference).  grids fp32 [K][B][hp*wp][n], class fastest, contiguous,
+ * ANY values (probabilities or logits); gt [B][h][w] uint8 / int16 (gt_bytes).  Per pixel and k: l_k is ifseg_seg_predict's
+ * label on grid k, bit for bit (the coordinate rule, the flat four-weight value, the smallest c of maximal value; a NaN never
+ * wins and an all-NaN pixel is class 0).  The ground-truth rule and the set of scored pixels are ifseg_seg_areas'.  Over the
+ * scored pixels, t the true class:
+ *   areas[k][0][t] += (l_k == t),  areas[k][1][l_k] += 1,  areas[k][2][t] += 1        uint64 [K][3][n]
+ * so row k is ifseg_seg_score's areas of grid k; tally uint64 [2] += #scored pixels, #pixels whose ground truth is out of
+ * range, once per pixel, not per k.  areas and tally are ADDED to and never cleared.  A workgroup owns 16 x 64 pixels, stages
+ * the footprint of one grid at a time in LDS and keeps ONE private uint32 table [3][n] (+ the tallies), whose non-zero bins
+ * leave behind every k as one 64-bit atomic each: integers only, so two calls give equal bits.  Nothing else is written,
+ * nothing is allocated, and the call does not synchronise.  What is left of 64 KiB beside the table is the staging buffer,
+ * and a footprint that exceeds it reads global memory instead (same bits).  ifseg_seg_score_grids_staging sets the size of
+ * that buffer like ifseg_seg_predict_staging, for this entry point only.
+ * NULL or misaligned pointers (grids 4 bytes; areas, tally 8; an int16 gt at an odd address), areas or tally overlapping each
+ * other, grids or gt, K outside 1..16, n outside 1..512, gt_bytes outside {1, 2}: IFSEG_ERR_BAD_ARG; B, hp, wp, h, w < 1,
+ * 2 hp h or 2 wp w >= 2^31, B*h*w >= 2^31, hp*wp >= 2^22: IFSEG_ERR_BAD_SHAPE; nothing is launched on a refusal. */
+int ifseg_seg_score_grids(const float* grids, int K, int B, int hp, int wp, int n, int h, int w, const void* gt, int gt_bytes,
+                          int raw_labels, unsigned long long* areas, unsigned long long* tally, void* stream);
+int ifseg_seg_score_grids_staging(int max_bytes);
+/* which = 0: the largest K, 1: the largest n, 2 / 3: the rows / columns of a tile, 4: the staging buffer's bytes at the
+ * largest K and n; any other which: IFSEG_ERR_BAD_ARG. */
+int ifseg_seg_score_grids_limit(int which);
 /* ifseg_seg_pseudo filters labels [B, H, W] (uint8 / int16) by conf fp32 [B, H, W] into out uint8 [B, H, W], one launch: a
  * pixel of label l is KEPT iff 0 <= l < n, bin(conf) >= thresholds[l] (int32 [n] on the device, 0 keeps every bin, 256 none)
  * and, with boundary = r (0..4), no pixel INSIDE the image at |dx| <= r and |dy| <= r carries a different label value
